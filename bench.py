@@ -223,8 +223,15 @@ def main():
     ap.add_argument("--advance-subframe", action="store_true",
                     help="let render() advance subframe_index from frame to frame (new P-pass seeds every frame) instead of "
                          "resetting it to 0 as the shipped application does (main.cpp:402-407)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as float32 .npy files under DIR (rank 0): "
+                         "frame.npy, the rgba8 frame the caller receives (N > 1: the gathered frame) as (H, W, 4) channel values "
+                         "0-255, and, at N = 1, accum.npy, the per-pixel radiance of accum_buffer as (H, W, 3) (its 4th channel is "
+                         "the constant 1 of every written pixel); 58 MB in all")
     ap.add_argument("--child-frames", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     FRAMES_IN_FLIGHT[0] = args.frames_in_flight
     if args.child_frames:
         return child_main(args.child_frames)
@@ -364,6 +371,16 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     last_frame_host = frames[(step_no[0] - 1) % nbuf].cpu()      # rank 0: the gathered frame
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, taken before anything below renders again
+        outputs = {"frame": last_frame_host.numpy().view(np.uint8).reshape(H, W, 4).astype(np.float32)}
+        if world == 1:
+            outputs["accum"] = np.ascontiguousarray(r.downloadAccum()[..., :3])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        dumped = {name: list(a.shape) for name, a in outputs.items()}
     st = r.stats()
     rays_local = float(st.radiance_rays + st.shadow_rays)
     if world > 1:
@@ -620,6 +637,8 @@ def main():
         },
         "roofline": roofline,
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
 
     # ---- CPU baseline: the oracle (a scalar C++ port of the path) on the host cores, rank 0, N=1
     if world == 1 and not args.no_cpu_baseline:

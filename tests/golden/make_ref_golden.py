@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/ref_vectors.npz and tests/golden/ref_loaders.npz: inputs and the outputs THE REFERENCE'S OWN
+"""Writes tests/golden/ref_vectors.npz, ref_loaders.npz, ref_sweeps.json and ref_random_obj.npz: inputs and the outputs THE REFERENCE'S OWN
 CODE gives for them, through oracle/_ref/libfovpt_ref.so (= oracle/ref_shim.cpp over the reference's headers,
 Model.cpp, sutil/Camera.cpp and its vendored tinyobjloader / stb_image, compiled where they lie under
 /root/reference by `make -C oracle ref`).
 
 Run in the build container (needs /root/reference):   python tests/golden/make_ref_golden.py
 The .npz files are data (seeded inputs, expected outputs, small input files as byte arrays); no reference text.
+ref_sweeps.json holds, for three more seeds of tests/ref_cases.py, SHA-256 digests of the inputs and of the outputs
+(ref_cases.digest): the inputs are regenerated from the seed, so the digests pin them without storing them.
 """
 import ctypes as C
+import json
 import os
 import subprocess
 import sys
@@ -192,6 +195,35 @@ def main():
     L.ref_model_free(h)
     np.savez_compressed(os.path.join(HERE, "ref_loaders.npz"), **lb)
     print("ref_loaders.npz: %d arrays" % len(lb))
+    sweeps(L)
+
+
+def sweeps(L):
+    """The wider seeded sweeps of tests/test_ref_pin_cpu.py: unit-level cases for seeds 1001-1003 (digests) and the random
+    OBJ files of seeds 0-11 with the reference's loadOBJ result for each."""
+    dig = {}
+    for seed in (1001, 1002, 1003):
+        inp, out = ref_cases.run_all(L, "ref_", seed=seed)
+        dig[str(seed)] = {"inputs": {k: ref_cases.digest(v) for k, v in sorted(inp.items())},
+                          "outputs": {k: ref_cases.digest(v) for k, v in sorted(out.items())}}
+    with open(os.path.join(HERE, "ref_sweeps.json"), "w") as f:
+        json.dump(dig, f, indent=1, sort_keys=True)
+        f.write("\n")
+    L.ref_load_obj.restype = C.c_void_p
+    L.ref_model_free.argtypes = [C.c_void_p]
+    ro = {}
+    for seed in range(12):
+        with tempfile.TemporaryDirectory() as d:
+            for name, data in ref_cases.random_obj_files(seed).items():
+                with open(os.path.join(d, name), "wb") as f:
+                    f.write(data)
+                ro["seed%d/file:%s" % (seed, name)] = np.frombuffer(data, np.uint8)
+            h = L.ref_load_obj(os.path.join(d, "r.obj").encode())
+            assert h, "reference loadOBJ failed (seed %d)" % seed
+            ro.update({"seed%d/%s" % (seed, k): v for k, v in dump_model(L, h).items()})
+            L.ref_model_free(h)
+    np.savez_compressed(os.path.join(HERE, "ref_random_obj.npz"), **ro)
+    print("ref_sweeps.json: %d seeds, ref_random_obj.npz: %d arrays" % (len(dig), len(ro)))
 
 
 if __name__ == "__main__":

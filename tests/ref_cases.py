@@ -11,6 +11,7 @@ tests/golden/ref_vectors.npz; tests/test_ref_pin_cpu.py replays them on the orac
 on the GPU kernels (within the detmath-vs-libm budget).  TEST INFRASTRUCTURE ONLY.
 """
 import ctypes as C
+import hashlib
 
 import numpy as np
 
@@ -78,6 +79,53 @@ def dump_model(L, h):
         L.ref_model_texture_data(C.c_void_p(h), k, _p(px))
         out["texture%d" % k] = px
     return out
+
+
+# ---- random OBJ scenes (the loader sweep of tests/test_ref_pin_cpu.py) -------------------------------
+def random_obj(rng):
+    """A random OBJ + MTL pair: groups, several materials per group, corners shared between materials, all corner
+    syntaxes, negative indices, polygons."""
+    nv, nt, nn = int(rng.integers(6, 30)), int(rng.integers(1, 12)), int(rng.integers(1, 6))
+    lines = ["mtllib r.mtl"]
+    lines += ["v %.6g %.6g %.6g" % tuple(rng.uniform(-5, 5, 3)) for _ in range(nv)]
+    lines += ["vt %.6g %.6g" % tuple(rng.uniform(-1, 2, 2)) for _ in range(nt)]
+    lines += ["vn %.6g %.6g %.6g" % tuple(rng.normal(size=3)) for _ in range(nn)]
+    mats = ["m%d" % k for k in range(int(rng.integers(1, 5)))]
+    for g in range(int(rng.integers(1, 4))):
+        lines.append(("g grp%d" if rng.random() < 0.5 else "o obj%d") % g)
+        for _ in range(int(rng.integers(1, 5))):
+            lines.append("usemtl " + mats[int(rng.integers(0, len(mats)))])
+            style = int(rng.integers(0, 4))
+            for _ in range(int(rng.integers(1, 6))):
+                corners = []
+                for v in rng.choice(nv, size=int(rng.integers(3, 6)), replace=False):
+                    vi = int(v) + 1 if rng.random() < 0.8 else int(v) - nv
+                    ti, ni = int(rng.integers(1, nt + 1)), int(rng.integers(1, nn + 1))
+                    corners.append(["%d" % vi, "%d/%d" % (vi, ti), "%d//%d" % (vi, ni), "%d/%d/%d" % (vi, ti, ni)][style])
+                lines.append("f " + " ".join(corners))
+    mtl = []
+    for k, name in enumerate(mats):
+        mtl += ["newmtl " + name, "Kd %.4g %.4g %.4g" % tuple(rng.uniform(0, 1, 3))]
+        if rng.random() < 0.5:
+            mtl.append("Ke %.4g %.4g %.4g" % tuple(rng.uniform(0, 9, 3)))
+        if rng.random() < 0.6:
+            mtl.append("map_Kd " + ["t0.png", "t1.ppm", "missing.png"][int(rng.integers(0, 3))])
+    return "\n".join(lines) + "\n", "\n".join(mtl) + "\n"
+
+
+def random_obj_files(seed):
+    """One case of the random-OBJ loader sweep: r.obj, r.mtl and the two textures they may name, {file name: bytes}."""
+    from common import encode_png
+    rng = np.random.default_rng(500 + seed)
+    obj, mtl = random_obj(rng)
+    return {"r.obj": obj.encode(), "r.mtl": mtl.encode(), "t0.png": encode_png(rng.integers(0, 256, (4, 3, 3)), 8, 2),
+            "t1.ppm": b"P6\n3 2\n255\n" + rng.integers(0, 256, 18, dtype=np.uint8).tobytes()}
+
+
+def digest(a):
+    """SHA-256 of an array's dtype, shape and bytes (tests/golden/ref_sweeps.json holds the reference's outputs this way)."""
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(("%s %s " % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
 
 
 # ---- cases --------------------------------------------------------------------------------------
