@@ -170,6 +170,24 @@ class Config(C.Structure):
         return m
 
 
+class DenoiseConfig(C.Structure):
+    """fovpt_denoise_config: iterations per foveation level and the edge-stopping scales (defaults: fovpt_denoise_defaults)."""
+    _fields_ = [
+        ("iterations_fovea", C.c_int32), ("iterations_middle", C.c_int32), ("iterations_periphery", C.c_int32),
+        ("iterations_uniform", C.c_int32),
+        ("color_sigma", C.c_float), ("normal_sigma", C.c_float), ("albedo_sigma", C.c_float),
+        ("_reserved", C.c_int32),
+    ]
+
+    def copy(self):
+        m = DenoiseConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(DenoiseConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
@@ -191,6 +209,7 @@ class FramePtrs(C.Structure):
 assert C.sizeof(Material) == 104
 assert C.sizeof(Probe) == 64
 assert C.sizeof(LaunchParams) == 248
+assert C.sizeof(DenoiseConfig) == 32
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

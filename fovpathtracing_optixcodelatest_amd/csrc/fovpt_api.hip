@@ -114,6 +114,10 @@ struct fovpt_ctx {
     std::vector<uint32_t> plan_off;        // host copy: rank r owns plan_idx[plan_off[r] .. plan_off[r + 1])
     std::string plan_key;                  // what the plan was built for
     bool use_accum_before = false;
+    // fovpt_denoise: the size of the frame last issued with fovpt_render (0 x 0: none since create / resize), the level map,
+    // the ping-pong filter buffers and the context's own outputs (allocated on first use)
+    int dn_w = 0, dn_h = 0;
+    DevBuf dn_level, dn_i0, dn_i1, dn_color, dn_rgba;
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -697,7 +701,7 @@ void fovpt_destroy(fovpt_ctx* c)
     DevBuf* bufs[] = {&c->tri_tc, &c->meshes, &c->textures, &c->pr_data, &c->pr_pdfx, &c->pr_cdfx, &c->pr_pdfy, &c->pr_cdfy, &c->pr_guidex, &c->pr_guidey, &c->pr_rec,
                       &c->fb_frame, &c->fb_accum, &c->fb_color, &c->fb_normal, &c->fb_albedo, &c->accum_before,
                       &c->plan_owner, &c->plan_blocks, &c->plan_total, &c->plan_base, &c->plan_idx,
-                      &c->comm_packed, &c->comm_gathered};
+                      &c->comm_packed, &c->comm_gathered, &c->dn_level, &c->dn_i0, &c->dn_i1, &c->dn_color, &c->dn_rgba};
     for (DevBuf* b : bufs) b->release();
     for (int l = 0; l < FOVPT_MAX_LANES; l++) {
         if (c->lane_main[l] && c->lane_main[l] != c->stream) (void)hipStreamDestroy(c->lane_main[l]);
@@ -948,6 +952,8 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     HIPCHK(c, hipMemset(c->fb_color.p, 0, n * 16));
     HIPCHK(c, hipMemset(c->fb_normal.p, 0, n * 16));
     HIPCHK(c, hipMemset(c->fb_albedo.p, 0, n * 16));
+    if (c->dn_color.p) { HIPCHK(c, c->dn_color.reserve(n * 16)); HIPCHK(c, c->dn_rgba.reserve(n * 4)); }   // fovpt_denoise's own outputs follow the frame
+    c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
     out->color_buffer = (fovpt_float4*)c->fb_color.p; out->normal_buffer = (fovpt_float4*)c->fb_normal.p;
     out->albedo_buffer = (fovpt_float4*)c->fb_albedo.p;
@@ -994,7 +1000,94 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
     const int rc = run_passes(c, lp, P, npass, 1);
     lp->frame.subframe_index = temp_frame;                                                   // :128-129 / :210-211
     lp->frame.subframe_index++;
+    if (rc == FOVPT_OK) { c->dn_w = lp->frame.size.x; c->dn_h = lp->frame.size.y; }          // what fovpt_denoise may filter
     return rc;
+}
+
+// edge-stopping scales of fovpt_denoise_defaults (chosen by measurement: DESIGN.md, denoiser)
+#define FOVPT_DENOISE_COLOR_SIGMA 8.0f
+#define FOVPT_DENOISE_NORMAL_SIGMA 0.5f
+#define FOVPT_DENOISE_ALBEDO_SIGMA 0.2f
+
+// ---- denoiser of the rendered frame (denoise.hip; the filter's definition: tests/denoise_ref.py) ------------------------
+int fovpt_denoise_defaults(fovpt_denoise_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->iterations_fovea = 0;
+    out->iterations_middle = 2;
+    out->iterations_periphery = 3;
+    out->iterations_uniform = 3;
+    out->color_sigma = FOVPT_DENOISE_COLOR_SIGMA;
+    out->normal_sigma = FOVPT_DENOISE_NORMAL_SIGMA;
+    out->albedo_sigma = FOVPT_DENOISE_ALBEDO_SIGMA;
+    return FOVPT_OK;
+}
+
+int fovpt_denoise_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    if (!c->dn_color.p) {
+        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise_buffers: no frame rendered yet");
+        HIPCHK(c, hipSetDevice(c->device));
+        const size_t n = (size_t)c->dn_w * (size_t)c->dn_h;
+        HIPCHK(c, c->dn_color.reserve(n * 16)); HIPCHK(c, c->dn_rgba.reserve(n * 4));
+    }
+    *color = (fovpt_float4*)c->dn_color.p;
+    *rgba = (uint32_t*)c->dn_rgba.p;
+    return FOVPT_OK;
+}
+
+// Enqueued on the stream every resolve runs on (fovpt_stream()), in issue order: behind the resolve of the frame last issued
+// -- also with frames_in_flight = 2 or chains_per_frame = 2, whose chains all join that stream for their resolve -- and ahead
+// of the next frame's resolve, the first of its launches that rewrites accum / frame / guides (its memsets and snapshot copies
+// of chunked launches also run there).  Callers synchronising on fovpt_stream() see the denoised frame.
+int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoise_config* dc, fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !dc) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null argument");
+    const int32_t its[4] = {dc->iterations_fovea, dc->iterations_middle, dc->iterations_periphery, dc->iterations_uniform};
+    for (int32_t n : its)
+        if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: iteration count %d outside 0 .. %d", n, FOVPT_DENOISE_MAX_ITERATIONS);
+    const float sig[3] = {dc->color_sigma, dc->normal_sigma, dc->albedo_sigma};
+    for (float v : sig)
+        if (!(v > 0.0f) || !std::isfinite(v)) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: sigma %g must be finite and > 0", (double)v);
+    if (!c->cfg.write_guides || c->any_catcher) return fail(c, FOVPT_E_INVALID, "fovpt_denoise needs the denoiser guides: fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
+    if (c->cfg.world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: a tile shard (world = %d) has no neighbours to filter with", c->cfg.world);
+    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise: no frame rendered yet");
+    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
+        return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
+    if (!lp->frame.color_buffer || !lp->frame.normal_buffer || !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null guide buffers");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    if (!out_color || !out_rgba) { HIPCHK(c, c->dn_color.reserve(npix * 16)); HIPCHK(c, c->dn_rgba.reserve(npix * 4)); }
+    HIPCHK(c, c->dn_level.reserve(npix));
+    HIPCHK(c, c->dn_i0.reserve(npix * 16));
+    HIPCHK(c, c->dn_i1.reserve(npix * 16));
+    if (!out_color) out_color = (fovpt_float4*)c->dn_color.p;
+    if (!out_rgba) out_rgba = (uint32_t*)c->dn_rgba.p;
+
+    // the level map: the passes fovpt_render ran for this frame (on a copy: the caller's parameters stay as they are)
+    fovpt_launch_params L = *lp;
+    PassDev P[FOVPT_MAX_PASSES];
+    FrameDev fd;
+    memset(&fd, 0, sizeof(fd));
+    fd.npass = frame_passes(c->cfg, L, P);
+    for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
+    fd.w = L.frame.size.x; fd.h = L.frame.size.y;
+    fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
+    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
+    DenoiseArgs a;
+    memset(&a, 0, sizeof(a));
+    if (c->cfg.uniform) a.n_pass[0] = dc->iterations_uniform;
+    else { a.n_pass[0] = dc->iterations_periphery; a.n_pass[1] = dc->iterations_middle; a.n_pass[2] = dc->iterations_fovea; }
+    for (int p = 0; p < fd.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
+    auto inv_sq = [](float s) { const float s2 = s * s; return 1.0f / s2; };
+    a.inv_c = inv_sq(dc->color_sigma); a.inv_n = inv_sq(dc->normal_sigma); a.inv_a = inv_sq(dc->albedo_sigma);
+    fovpt_launch_denoise(c->shadow_stream, fd, a, lp->frame.color_buffer, lp->frame.normal_buffer, lp->frame.albedo_buffer,
+                         (float4*)c->dn_i0.p, (float4*)c->dn_i1.p, (uint8_t*)c->dn_level.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
 }
 
 // ---- multi-GPU: packed gather of the owned pixels ---------------------------------------------------

@@ -245,6 +245,15 @@ void fovpt_launch_plan_scan_fill(hipStream_t st, uint32_t npix, uint32_t nblocks
 void fovpt_launch_gather_pack(hipStream_t st, uint32_t n, const uint32_t* idx, const uint32_t* frame, uint32_t* packed);
 void fovpt_launch_gather_unpack(hipStream_t st, int world, uint32_t stride, uint32_t total, const uint32_t* base, const uint32_t* idx,
                                 const uint32_t* gathered, uint32_t* frame);
+// fovpt_denoise (denoise.hip): level map + demodulation, then `iterations` a-trous launches (the last writes the outputs).
+// I0 / I1: ping-pong float4 per pixel; level: one byte per pixel.
+struct DenoiseArgs {
+    int32_t n_pass[FOVPT_MAX_PASSES];   // iterations of the pixels whose last writer is pass p
+    int32_t iterations;                 // max over the passes present
+    float inv_c, inv_n, inv_a;          // 1 / sigma^2 (fp32, host)
+};
+void fovpt_launch_denoise(hipStream_t st, const FrameDev& fd, const DenoiseArgs& a, const fovpt_float4* color, const fovpt_float4* normal,
+                          const fovpt_float4* albedo, float4* I0, float4* I1, uint8_t* level, fovpt_float4* out_color, uint32_t* out_rgba);
 void fovpt_launch_build_guide(hipStream_t st, const float* cdf, int n, int segments, uint32_t* guide);
 void fovpt_launch_probe_records(hipStream_t st, size_t n, const float* cdfX, const float* pdfX, const float4* data, float4* rec);
 void fovpt_launch_build_cdf(hipStream_t st, int w, int h, const float4* data, float* pdfX, float* cdfX, float* pdfY, float* cdfY, float* row_total);

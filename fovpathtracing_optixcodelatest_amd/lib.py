@@ -18,6 +18,7 @@ EXPORTS = [
     "fovpt_synchronize", "fovpt_download", "fovpt_get_stats", "fovpt_reset_stats", "fovpt_stream",
     "fovpt_probe_build_cdf", "fovpt_camera_uvw", "fovpt_debug_math", "fovpt_debug_buffer", "fovpt_debug_trace",
     "fovpt_gather_plan", "fovpt_gather_pack", "fovpt_gather_unpack",
+    "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
     "fovpt_model_load_obj", "fovpt_model_load_gltf", "fovpt_model_destroy", "fovpt_model_counts", "fovpt_model_get_mesh", "fovpt_model_get_texture",
     "fovpt_image_load_float4", "fovpt_image_free", "fovpt_image_load_rgba8", "fovpt_image_free_rgba8",
@@ -129,6 +130,9 @@ def load():
     L.fovpt_gather_plan.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, i32]
     L.fovpt_gather_pack.argtypes = [vp, vp, vp]
     L.fovpt_gather_unpack.argtypes = [vp, vp, u32, vp]
+    L.fovpt_denoise_defaults.argtypes = [C.POINTER(abi.DenoiseConfig)]
+    L.fovpt_denoise.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.DenoiseConfig), vp, vp]
+    L.fovpt_denoise_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_comm_get_unique_id.argtypes = [vp]
     L.fovpt_comm_init.argtypes = [vp, vp, i32, i32]
     L.fovpt_comm_destroy.argtypes = [vp]

@@ -218,6 +218,38 @@ class SampleRenderer:
         self._check(self._L.fovpt_download(self._ctx, device_ptr, array.ctypes.data, array.nbytes))
         return array
 
+    # -- denoiser of the rendered frame (include/fovpt.h, fovpt_denoise): in place of the reference family's OptiXDenoiser
+    @staticmethod
+    def denoise_defaults() -> abi.DenoiseConfig:
+        d = abi.DenoiseConfig()
+        lib.check(None, lib.load().fovpt_denoise_defaults(C.byref(d)))
+        return d
+
+    def denoise(self, cfg=None, out_color=None, out_rgba=None):
+        """Filters the frame last rendered (needs config.write_guides = 1).  out_color / out_rgba: device pointers (float4 /
+        rgba8 per pixel), or None for the renderer's own buffers (downloadDenoisedColor / downloadDenoisedPixels).  Enqueued on
+        the renderer's stream, not synchronised (the downloads synchronise)."""
+        cfg = cfg if cfg is not None else self.denoise_defaults()
+        self._check(self._L.fovpt_denoise(self._ctx, C.byref(self.launchParams), C.byref(cfg), out_color, out_rgba))
+
+    def denoise_buffers(self):
+        """Device addresses of the renderer's own denoiser outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_denoise_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def downloadDenoisedPixels(self):
+        """The rgba8 output of the last denoise into the renderer's own buffer, shaped like downloadPixels()."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x), np.uint32)
+        return self.download(self.denoise_buffers()[1], out)
+
+    def downloadDenoisedColor(self):
+        """The float4 output of the last denoise into the renderer's own buffer."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x, 4), np.float32)
+        return self.download(self.denoise_buffers()[0], out)
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

@@ -99,6 +99,23 @@ public:
         check(fovpt_set_probe(ctx, probe.width, probe.height, (const fovpt_float4*)probe.data, probe.pdfValuesX, probe.cdfValuesX,
                               probe.pdfValuesY, probe.cdfValuesY, (const fovpt_float3*)&probe.offset, &launchParams.probe));
     }
+    // ---- denoiser (new with this library; replaces the reference family's OptiXDenoiser init / exec / finish and
+    // computeFinalPixelColors, OtherProjects_01/06HelloPathtracing): filters the frame just rendered -- needs
+    // fovpt_config.write_guides = 1 -- into the renderer's own buffers, then a device sync like render()
+    void denoise() { fovpt_denoise_config dc; check(fovpt_denoise_defaults(&dc)); denoise(dc); }
+    void denoise(const fovpt_denoise_config& dc)
+    {
+        check(fovpt_denoise(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &dc, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // the denoised rgba8 pixels, like downloadPixels
+    void downloadDenoisedPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_denoise_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

@@ -271,6 +271,40 @@ int fovpt_launch(fovpt_ctx* ctx, const fovpt_launch_params* lp, uint32_t width, 
  * returns FOVPT_OK when lp->frame.size.x == 0 (:81-82).  Asynchronous.            */
 int fovpt_render(fovpt_ctx* ctx, fovpt_launch_params* lp);
 
+/* ---- denoiser of the rendered frame ------------------------------------------------------------------------------------
+ * New with this library, in place of the OptiX AI denoiser of the reference family (OtherProjects_01/06HelloPathtracing/
+ * OptixDenoiser.{h,cpp}: init(DenoiseData{width, height, color, albedo, normal, output}) / exec() / finish(), and
+ * SimplePathtracer.cpp's computeFinalPixelColors for the display pixels): an edge-avoiding a-trous wavelet filter (Dammertz et
+ * al. 2010) over the denoiser guides (fovpt_config.write_guides = 1), made foveation-aware.  Each pixel is filtered according to
+ * the pass that wrote it last -- the fovea (8 spp as shipped) not at all by default, the periphery (one sample per 4 x 4 block)
+ * most -- with taps at multiples of its block fill, so a filled block is never averaged with its own copies.  Only + - * / max,
+ * no transcendental functions: the result is defined bit for bit (tests/denoise_ref.py restates it in numpy float32).
+ *   fovpt_denoise           filters the frame last issued with fovpt_render(ctx, lp): out_color float4 (colour, alpha 1) and
+ *                           out_rgba rgba8 (the resolve's tone map of out_color) per pixel, device pointers of frame.size; either
+ *                           may be NULL = the context's own buffers (allocated on first use, reallocated by fovpt_resize, freed
+ *                           by fovpt_destroy).  Pixels with 0 iterations get accum_buffer / frame_buffer's values unchanged.
+ *                           Enqueued on fovpt_stream(), not synchronised: behind that frame's resolve and ahead of the next
+ *                           frame's, whatever frames_in_flight / chains_per_frame say.  Reads the guides; writes nothing else.
+ *                           FOVPT_E_INVALID: null arguments, an iteration count outside 0 .. 5, a sigma <= 0 or not finite,
+ *                           write_guides = 0 (or shadow-catcher scenes, which cannot write guides), world > 1 (a shard has no
+ *                           neighbours); FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size differs.
+ *   fovpt_denoise_buffers   addresses of the context's own outputs (allocated for the last frame if not yet).                 */
+#define FOVPT_DENOISE_MAX_ITERATIONS 5
+typedef struct fovpt_denoise_config {
+    int32_t iterations_fovea;      /* a-trous iterations of pixels last written by pass F (fill 1); default 0             */
+    int32_t iterations_middle;     /* ... by pass M (fill 2); default 2                                                    */
+    int32_t iterations_periphery;  /* ... by pass P (fill 4); default 3                                                    */
+    int32_t iterations_uniform;    /* FOV_OFF frames (one pass, fill 1); default 3                                         */
+    float color_sigma;             /* edge-stopping scales: colour (relative to the pixel's luminance, halved per          */
+    float normal_sigma;            /* iteration), normal and albedo distance; defaults from fovpt_denoise_defaults       */
+    float albedo_sigma;
+    int32_t _reserved;             /* 0 */
+} fovpt_denoise_config;
+int fovpt_denoise_defaults(fovpt_denoise_config* out);
+int fovpt_denoise(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_denoise_config* dc,
+                  fovpt_float4* out_color, uint32_t* out_rgba);
+int fovpt_denoise_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+
 /* ---- multi-GPU: packed gather of the final framebuffer ----------------------------------
  * New with this library: the reference is single-GPU (SimplePathtracer.cpp:331-340).  With
  * fovpt_config.rank/world every handle renders the launch-index tiles it owns -- interleaved
@@ -405,6 +439,7 @@ int fovpt_debug_buffer(fovpt_ctx* ctx, const char* name, void** ptr, size_t* byt
 static_assert(sizeof(fovpt_material) == 104, "Material ABI");
 static_assert(sizeof(fovpt_probe) == 64, "Probe ABI");
 static_assert(sizeof(fovpt_launch_params) == 248, "LaunchParams ABI");
+static_assert(sizeof(fovpt_denoise_config) == 32, "denoise config ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

@@ -1,0 +1,138 @@
+"""fovpt_denoise without a GPU: the C ABI of the config (layout, defaults, argument checks) and properties of the filter's
+definition, the numpy restatement in tests/denoise_ref.py that the GPU kernels are checked against bit for bit."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import denoise_ref as dn
+from fovpathtracing_optixcodelatest_amd import abi, lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def so():
+    lib.build()
+    return lib.load()
+
+
+def test_denoise_config_mirror_matches_the_header(tmp_path):
+    names = [f[0] for f in abi.DenoiseConfig._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu", sizeof(fovpt_denoise_config));' + "".join(
+        'printf(" %%zu", offsetof(fovpt_denoise_config, %s));' % n for n in names) + "return 0;}\n"
+    exe = str(tmp_path / "dn_layout")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert got[0] == C.sizeof(abi.DenoiseConfig) == 32
+    assert got[1:] == [getattr(abi.DenoiseConfig, n).offset for n in names]
+
+
+def test_denoise_defaults_are_the_documented_ones(so):
+    d = abi.DenoiseConfig()
+    assert so.fovpt_denoise_defaults(C.byref(d)) == 0
+    assert d.as_dict() == {k: np.float32(v) if isinstance(v, float) else v for k, v in dn.DEFAULTS.items()}
+    assert d._reserved == 0
+    assert so.fovpt_denoise_defaults(None) == -1
+
+
+def test_denoise_rejects_null_arguments(so):
+    d = abi.DenoiseConfig()
+    so.fovpt_denoise_defaults(C.byref(d))
+    lp = abi.LaunchParams()
+    assert so.fovpt_denoise(None, C.byref(lp), C.byref(d), None, None) == -1        # FOVPT_E_INVALID
+    assert so.fovpt_denoise(None, None, None, None, None) == -1
+    col, rgba = C.c_void_p(), C.c_void_p()
+    assert so.fovpt_denoise_buffers(None, C.byref(col), C.byref(rgba)) == -1
+
+
+def _guides(h, w, seed=3):
+    rng = np.random.default_rng(seed)
+    color = np.zeros((h, w, 4), np.float32)
+    color[..., :3] = rng.uniform(0.0, 2.0, (h, w, 3))
+    color[..., 3] = 1
+    normal = np.zeros((h, w, 4), np.float32)
+    normal[..., 2] = 1
+    normal[..., 3] = 1
+    albedo = np.full((h, w, 4), 0.5, np.float32)
+    albedo[..., 3] = 1
+    return color, normal, albedo
+
+
+def test_zero_iterations_is_the_identity():
+    h, w = 24, 32
+    color, normal, albedo = _guides(h, w)
+    fill = np.ones((h, w), np.int32)
+    out, _ = dn.denoise(color, normal, albedo, fill, np.zeros((h, w), np.int32), {})
+    assert np.array_equal(out.view(np.uint32), color.view(np.uint32))
+
+
+def test_a_constant_image_stays_constant():
+    h, w = 40, 48
+    color, normal, albedo = _guides(h, w)
+    color[..., :3] = np.float32([0.3, 0.6, 0.9])
+    fill, pas = dn.level_map(w, h, (24, 20), 4, 12, 0)
+    n = dn.iteration_map(fill, pas, dict(dn.DEFAULTS, iterations_fovea=2), 0)
+    out, _ = dn.denoise(color, normal, albedo, fill, n, dict(iterations_fovea=2))
+    assert n.max() == 3 and (n >= 2).mean() > 0.9          # (the rings of the reference leave a few holes: n = 0)
+    assert np.abs(out[..., :3] / color[..., :3] - 1).max() <= 1e-6
+
+
+def test_a_noisy_two_albedo_step_is_smoothed_without_leaking():
+    """Two halves of different albedo (and colour), 1 spp-like noise: the variance inside each half drops at least 4x and no
+    more than 1 % of either half's mean crosses the edge."""
+    h, w = 64, 64
+    rng = np.random.default_rng(11)
+    albedo = np.zeros((h, w, 4), np.float32)
+    albedo[:, : w // 2, :3] = np.float32([0.8, 0.2, 0.2])
+    albedo[:, w // 2:, :3] = np.float32([0.2, 0.3, 0.8])
+    albedo[..., 3] = 1
+    normal = np.zeros((h, w, 4), np.float32)
+    normal[..., 1] = 1
+    color = np.zeros((h, w, 4), np.float32)
+    light = np.float32(1.0) + rng.normal(0.0, 0.3, (h, w)).astype(np.float32)
+    color[..., :3] = albedo[..., :3] * light[..., None]
+    color[..., 3] = 1
+    fill = np.ones((h, w), np.int32)
+    n = np.full((h, w), 3, np.int32)
+    out, _ = dn.denoise(color, normal, albedo, fill, n, {})
+    for sl in (np.s_[:, : w // 2], np.s_[:, w // 2:]):
+        before, after = color[sl][..., :3], out[sl][..., :3]
+        assert (after.var(axis=(0, 1)) * 4 <= before.var(axis=(0, 1))).all()
+    # what crosses the edge: brighten one half threefold and see how far the other half's output moves
+    for src, dst in ((np.s_[:, w // 2:], np.s_[:, : w // 2]), (np.s_[:, : w // 2], np.s_[:, w // 2:])):
+        bright = color.copy()
+        bright[src][..., :3] *= np.float32(3.0)
+        moved, _ = dn.denoise(bright, normal, albedo, fill, n, {})
+        delta = np.abs(moved[dst][..., :3] - out[dst][..., :3]).mean(axis=(0, 1))
+        assert (delta <= 0.01 * color[dst][..., :3].mean(axis=(0, 1))).all()
+
+
+def test_a_block_filled_periphery_is_never_tapped_below_its_fill():
+    """A periphery of 4 x 4 copies filters exactly like the 4x smaller frame at fill 1: its taps land on whole blocks only, so
+    every block stays 16 equal pixels and no pixel is averaged with its own copies."""
+    hs, ws = 12, 16
+    color, normal, albedo = _guides(hs, ws, seed=5)
+    normal[..., :3] = np.random.default_rng(6).normal(size=(hs, ws, 3)).astype(np.float32) * np.float32(0.05) + np.float32([0, 0, 1])
+    albedo[..., :3] = np.random.default_rng(7).uniform(0.4, 0.6, (hs, ws, 3)).astype(np.float32)
+    up = lambda a: np.repeat(np.repeat(a, 4, axis=0), 4, axis=1)
+    n_small = np.full((hs, ws), 3, np.int32)
+    small, _ = dn.denoise(color, normal, albedo, np.ones((hs, ws), np.int32), n_small, {})
+    big, _ = dn.denoise(up(color), up(normal), up(albedo), np.full((4 * hs, 4 * ws), 4, np.int32), up(n_small), {})
+    assert np.array_equal(big.view(np.uint32), up(small).view(np.uint32))
+    assert not np.array_equal(small, color)          # (it did filter)
+
+
+def test_level_map_follows_the_passes():
+    """P everywhere, M in its ring, F in the middle; FOV_OFF: one pass; a frame not a multiple of 4 wide has unwritten columns."""
+    fill, pas = dn.level_map(96, 64, (48, 32), 6, 18, 0)
+    assert pas[32, 48] == 2 and fill[32, 48] == 1
+    assert pas[32, 48 + 12] == 1 and fill[32, 48 + 12] == 2
+    assert pas[0, 0] == 0 and fill[0, 0] == 4
+    assert {0, 1, 2} <= set(np.unique(pas).tolist()) and (pas >= 0).mean() > 0.95
+    fill, pas = dn.level_map(30, 20, (10, 10), 2, 5, 1)
+    assert (pas == 0).all() and (fill == 1).all()
+    fill, pas = dn.level_map(30, 20, (200, 200), 2, 5, 0)       # the gaze off the frame: P, and F clamped onto the corner
+    assert pas[19, 29] == 2 and (pas[:-1, 28:] == -1).all() and (pas[:, :28] == 0).all() and (fill[:, :28] == 4).all()
