@@ -188,6 +188,31 @@ class DenoiseConfig(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+class ReconstructConfig(C.Structure):
+    """fovpt_reconstruct_config: tent support, edge-stopping scales, levels and remodulation (defaults: fovpt_reconstruct_defaults)."""
+    _fields_ = [
+        ("support", C.c_float), ("normal_sigma", C.c_float), ("depth_sigma", C.c_float),
+        ("levels", C.c_int32), ("remodulate", C.c_int32),
+        ("_reserved", C.c_int32 * 3),
+    ]
+
+    def copy(self):
+        m = ReconstructConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(ReconstructConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class GBufferPtrs(C.Structure):
+    """fovpt_gbuffer_ptrs: device pointers of the G-buffer fovpt_gbuffer filled."""
+    _fields_ = [
+        ("prim", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p),
+        ("width", C.c_int32), ("height", C.c_int32),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
@@ -210,6 +235,7 @@ assert C.sizeof(Material) == 104
 assert C.sizeof(Probe) == 64
 assert C.sizeof(LaunchParams) == 248
 assert C.sizeof(DenoiseConfig) == 32
+assert C.sizeof(ReconstructConfig) == 32 and C.sizeof(GBufferPtrs) == 40
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

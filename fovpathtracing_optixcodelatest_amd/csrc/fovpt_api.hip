@@ -118,6 +118,9 @@ struct fovpt_ctx {
     // the ping-pong filter buffers and the context's own outputs (allocated on first use)
     int dn_w = 0, dn_h = 0;
     DevBuf dn_level, dn_i0, dn_i1, dn_color, dn_rgba;
+    // fovpt_gbuffer / fovpt_reconstruct: the G-buffer's own ray queue, hit records, counters and outputs (never a render state
+    // set: a frame in flight may be using those), and the context's own reconstruction outputs; all allocated on first use
+    DevBuf gb_o, gb_d, gb_hit, gb_cnt, gb_prim, gb_pos, gb_nrm, gb_alb, rc_color, rc_rgba;
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -609,6 +612,69 @@ int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P)
     return 3;
 }
 
+// ---- post-processing of the rendered frame: fovpt_denoise (denoise.hip), fovpt_gbuffer / fovpt_reconstruct (reconstruct.hip) --
+// The passes fovpt_render ran for the frame lp describes, whole (rows 0 .. gh) and on one rank: what find_last_writer needs to
+// give every pixel its writing pass and launch index.  Computed on a copy: the caller's parameters stay as they are.
+void frame_levels(const fovpt_ctx* c, const fovpt_launch_params* lp, FrameDev& fd)
+{
+    fovpt_launch_params L = *lp;
+    PassDev P[FOVPT_MAX_PASSES];
+    memset(&fd, 0, sizeof(fd));
+    fd.npass = frame_passes(c->cfg, L, P);
+    for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
+    fd.w = L.frame.size.x; fd.h = L.frame.size.y;
+    fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
+    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
+}
+
+// the G-buffer's buffers for n pixels (the counters once: k_gbuffer_rays rewrites the queue sizes it uses on every call)
+int reserve_gbuffer(fovpt_ctx* c, size_t n)
+{
+    const bool fresh = c->gb_cnt.p == nullptr;
+    HIPCHK(c, c->gb_o.reserve(n * 16)); HIPCHK(c, c->gb_d.reserve(n * 16)); HIPCHK(c, c->gb_hit.reserve(n * 16));
+    HIPCHK(c, c->gb_prim.reserve(n * 4)); HIPCHK(c, c->gb_pos.reserve(n * 16)); HIPCHK(c, c->gb_nrm.reserve(n * 16)); HIPCHK(c, c->gb_alb.reserve(n * 16));
+    HIPCHK(c, c->gb_cnt.reserve(sizeof(Counters)));
+    if (fresh) HIPCHK(c, hipMemset(c->gb_cnt.p, 0, sizeof(Counters)));
+    return FOVPT_OK;
+}
+
+// Enqueues the G-buffer of lp (frame.size, camera) on fovpt_stream(): one ray per pixel, traced by the production closest-hit
+// k_traverse (so a ray gets the (prim, t, u, v) fovpt_debug_trace returns for it), then the per-pixel outputs.
+int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, GBufferDev& g, const char* who)
+{
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene (traversable %llu, current %llu)", who,
+                                                                     (unsigned long long)lp->traversable, (unsigned long long)c->scene_id);
+#if FOVPT_V_STEPSTAT
+    return fail(c, FOVPT_E_INVALID, "%s: not available in a diagnostic (FOVPT_V_STEPSTAT) build", who);
+#endif
+    const int w = lp->frame.size.x, h = lp->frame.size.y;
+    if (w <= 0 || h <= 0) return fail(c, FOVPT_E_INVALID, "%s: frame size %d x %d", who, w, h);
+    const size_t n = (size_t)w * (size_t)h;
+    if (n >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, w, h);
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }
+    FrameDev fd;
+    memset(&fd, 0, sizeof(fd));
+    fd.w = w; fd.h = h;
+    const fovpt_float3* cam[4] = {&lp->camera.eye, &lp->camera.U, &lp->camera.V, &lp->camera.W};
+    float* dst[4] = {fd.eye, fd.U, fd.V, fd.W};
+    for (int k = 0; k < 4; k++) { dst[k][0] = cam[k]->x; dst[k][1] = cam[k]->y; dst[k][2] = cam[k]->z; }
+    RayQueue q; q.o = (float4*)c->gb_o.p; q.d = (float4*)c->gb_d.p;
+    PathState ps;
+    memset(&ps, 0, sizeof(ps));
+    ps.hit = (float4*)c->gb_hit.p;                                   // all a closest-hit launch writes
+    ShadowQueue sq;
+    memset(&sq, 0, sizeof(sq));
+    Counters* cnt = (Counters*)c->gb_cnt.p;
+    g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = (float4*)c->gb_nrm.p; g.alb = (float4*)c->gb_alb.p;
+    hipStream_t st = c->shadow_stream;
+    fovpt_launch_gbuffer_rays(st, fd, q, cnt);
+    fovpt_launch_traverse(st, scene_view(c), ps, q, sq, (uint32_t)n, cnt, 0, -1, c->grid_trace);   // shard 0 holds all n rays
+    fovpt_launch_gbuffer_fill(st, fd, scene_view(c), q, ps.hit, g);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -701,7 +767,8 @@ void fovpt_destroy(fovpt_ctx* c)
     DevBuf* bufs[] = {&c->tri_tc, &c->meshes, &c->textures, &c->pr_data, &c->pr_pdfx, &c->pr_cdfx, &c->pr_pdfy, &c->pr_cdfy, &c->pr_guidex, &c->pr_guidey, &c->pr_rec,
                       &c->fb_frame, &c->fb_accum, &c->fb_color, &c->fb_normal, &c->fb_albedo, &c->accum_before,
                       &c->plan_owner, &c->plan_blocks, &c->plan_total, &c->plan_base, &c->plan_idx,
-                      &c->comm_packed, &c->comm_gathered, &c->dn_level, &c->dn_i0, &c->dn_i1, &c->dn_color, &c->dn_rgba};
+                      &c->comm_packed, &c->comm_gathered, &c->dn_level, &c->dn_i0, &c->dn_i1, &c->dn_color, &c->dn_rgba,
+                      &c->gb_o, &c->gb_d, &c->gb_hit, &c->gb_cnt, &c->gb_prim, &c->gb_pos, &c->gb_nrm, &c->gb_alb, &c->rc_color, &c->rc_rgba};
     for (DevBuf* b : bufs) b->release();
     for (int l = 0; l < FOVPT_MAX_LANES; l++) {
         if (c->lane_main[l] && c->lane_main[l] != c->stream) (void)hipStreamDestroy(c->lane_main[l]);
@@ -953,6 +1020,8 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     HIPCHK(c, hipMemset(c->fb_normal.p, 0, n * 16));
     HIPCHK(c, hipMemset(c->fb_albedo.p, 0, n * 16));
     if (c->dn_color.p) { HIPCHK(c, c->dn_color.reserve(n * 16)); HIPCHK(c, c->dn_rgba.reserve(n * 4)); }   // fovpt_denoise's own outputs follow the frame
+    if (c->gb_prim.p) { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }                   // so do the G-buffer's
+    if (c->rc_color.p) { HIPCHK(c, c->rc_color.reserve(n * 16)); HIPCHK(c, c->rc_rgba.reserve(n * 4)); }   // and fovpt_reconstruct's
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
     out->color_buffer = (fovpt_float4*)c->fb_color.p; out->normal_buffer = (fovpt_float4*)c->fb_normal.p;
@@ -1003,6 +1072,11 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
     if (rc == FOVPT_OK) { c->dn_w = lp->frame.size.x; c->dn_h = lp->frame.size.y; }          // what fovpt_denoise may filter
     return rc;
 }
+
+// fovpt_reconstruct_defaults (chosen by measurement: DESIGN.md, section 11)
+#define FOVPT_RECONSTRUCT_SUPPORT 2.0f
+#define FOVPT_RECONSTRUCT_NORMAL_SIGMA 0.5f
+#define FOVPT_RECONSTRUCT_DEPTH_SIGMA 0.05f
 
 // edge-stopping scales of fovpt_denoise_defaults (chosen by measurement: DESIGN.md, denoiser)
 #define FOVPT_DENOISE_COLOR_SIGMA 8.0f
@@ -1067,16 +1141,9 @@ int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoi
     if (!out_color) out_color = (fovpt_float4*)c->dn_color.p;
     if (!out_rgba) out_rgba = (uint32_t*)c->dn_rgba.p;
 
-    // the level map: the passes fovpt_render ran for this frame (on a copy: the caller's parameters stay as they are)
-    fovpt_launch_params L = *lp;
-    PassDev P[FOVPT_MAX_PASSES];
+    // the level map: the passes fovpt_render ran for this frame
     FrameDev fd;
-    memset(&fd, 0, sizeof(fd));
-    fd.npass = frame_passes(c->cfg, L, P);
-    for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
-    fd.w = L.frame.size.x; fd.h = L.frame.size.y;
-    fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
-    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
+    frame_levels(c, lp, fd);
     DenoiseArgs a;
     memset(&a, 0, sizeof(a));
     if (c->cfg.uniform) a.n_pass[0] = dc->iterations_uniform;
@@ -1086,6 +1153,95 @@ int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoi
     a.inv_c = inv_sq(dc->color_sigma); a.inv_n = inv_sq(dc->normal_sigma); a.inv_a = inv_sq(dc->albedo_sigma);
     fovpt_launch_denoise(c->shadow_stream, fd, a, lp->frame.color_buffer, lp->frame.normal_buffer, lp->frame.albedo_buffer,
                          (float4*)c->dn_i0.p, (float4*)c->dn_i1.p, (uint8_t*)c->dn_level.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- G-buffer and reconstruction of the rendered frame (reconstruct.hip; the reconstruction's definition:
+// tests/reconstruct_ref.py) --------------------------------------------------------------------------------------------
+int fovpt_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, fovpt_gbuffer_ptrs* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !out) return fail(c, FOVPT_E_INVALID, "fovpt_gbuffer: null argument");
+    GBufferDev g;
+    const int rc = enqueue_gbuffer(c, lp, g, "fovpt_gbuffer");
+    if (rc) return rc;
+    out->prim = g.prim;
+    out->position = (fovpt_float4*)g.pos; out->normal = (fovpt_float4*)g.nrm; out->albedo = (fovpt_float4*)g.alb;
+    out->width = lp->frame.size.x; out->height = lp->frame.size.y;
+    return FOVPT_OK;
+}
+
+int fovpt_reconstruct_defaults(fovpt_reconstruct_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->support = FOVPT_RECONSTRUCT_SUPPORT;
+    out->normal_sigma = FOVPT_RECONSTRUCT_NORMAL_SIGMA;
+    out->depth_sigma = FOVPT_RECONSTRUCT_DEPTH_SIGMA;
+    out->levels = 3;
+    out->remodulate = 1;
+    return FOVPT_OK;
+}
+
+int fovpt_reconstruct_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    if (!c->rc_color.p) {
+        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct_buffers: no frame rendered yet");
+        HIPCHK(c, hipSetDevice(c->device));
+        const size_t n = (size_t)c->dn_w * (size_t)c->dn_h;
+        HIPCHK(c, c->rc_color.reserve(n * 16)); HIPCHK(c, c->rc_rgba.reserve(n * 4));
+    }
+    *color = (fovpt_float4*)c->rc_color.p;
+    *rgba = (uint32_t*)c->rc_rgba.p;
+    return FOVPT_OK;
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: behind the resolve of the frame last issued, ahead of
+// the next frame's.  Builds that frame's G-buffer first (the same stream), then reconstructs.
+int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_reconstruct_config* rc, const fovpt_float4* in_color,
+                      fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !rc) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null argument");
+    if (!(rc->support >= 1.0f && rc->support <= 2.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: support %g outside [1, 2]", (double)rc->support);
+    const float sig[2] = {rc->normal_sigma, rc->depth_sigma};
+    for (float v : sig)
+        if (!(v > 0.0f) || !std::isfinite(v)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: sigma %g must be finite and > 0", (double)v);
+    if (rc->levels < 0 || rc->levels > 3) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: levels %d outside 0 .. 3", rc->levels);
+    if (rc->remodulate != 0 && rc->remodulate != 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: remodulate %d is neither 0 nor 1", rc->remodulate);
+    for (int32_t r : rc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: reserved fields must be 0");
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_reconstruct without a scene");
+    if (rc->remodulate && (!c->cfg.write_guides || c->any_catcher))
+        return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct with remodulate = 1 needs the albedo guide: fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
+    if (c->cfg.world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: a tile shard (world = %d) has no neighbours to reconstruct from", c->cfg.world);
+    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct: no frame rendered yet");
+    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
+        return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null accum_buffer");
+    if (rc->remodulate && !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null albedo guide");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    if (!out_color || !out_rgba) { HIPCHK(c, c->rc_color.reserve(npix * 16)); HIPCHK(c, c->rc_rgba.reserve(npix * 4)); }
+    if (!out_color) out_color = (fovpt_float4*)c->rc_color.p;
+    if (!out_rgba) out_rgba = (uint32_t*)c->rc_rgba.p;
+    if (in == out_color) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: the input is the output colour buffer (it reads neighbours)");
+    GBufferDev g;
+    { const int rc_ = enqueue_gbuffer(c, lp, g, "fovpt_reconstruct"); if (rc_) return rc_; }
+    FrameDev fd;
+    frame_levels(c, lp, fd);
+    ReconstructArgs a;
+    memset(&a, 0, sizeof(a));
+    const float s = rc->support;
+    a.inv_support[0] = 1.0f / (s * 2.0f);
+    a.inv_support[1] = 1.0f / (s * 4.0f);
+    auto inv_sq = [](float v) { const float v2 = v * v; return 1.0f / v2; };
+    a.inv_n = inv_sq(rc->normal_sigma); a.inv_z = inv_sq(rc->depth_sigma);
+    a.levels = rc->levels; a.remodulate = rc->remodulate;
+    fovpt_launch_reconstruct(c->shadow_stream, fd, a, in, lp->frame.albedo_buffer, g, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }

@@ -254,6 +254,25 @@ struct DenoiseArgs {
 };
 void fovpt_launch_denoise(hipStream_t st, const FrameDev& fd, const DenoiseArgs& a, const fovpt_float4* color, const fovpt_float4* normal,
                           const fovpt_float4* albedo, float4* I0, float4* I1, uint8_t* level, fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_gbuffer / fovpt_reconstruct (reconstruct.hip).  The G-buffer: one camera ray per pixel of fd (jitter 0.5) into queue 0,
+// all in shard 0 of cnt (k_gbuffer_rays); the caller traces them with fovpt_launch_traverse (closest hit, cap = w * h); then
+// k_gbuffer_fill turns the hit records into the per-pixel outputs.
+struct GBufferDev {
+    uint32_t* prim;                     // global primitive id, 0xffffffff on a miss
+    float4* pos;                        // eye + t * dir, t (miss: 0, 0, 0, -1)
+    float4* nrm;                        // face-forwarded geometric normal, 0
+    float4* alb;                        // material colour or texel, 0
+};
+void fovpt_launch_gbuffer_rays(hipStream_t st, const FrameDev& fd, RayQueue q, Counters* cnt);
+void fovpt_launch_gbuffer_fill(hipStream_t st, const FrameDev& fd, SceneView sc, RayQueue q, const float4* hit, GBufferDev g);
+struct ReconstructArgs {
+    float inv_support[2];               // 1 / (support * f) for f = 2, 4 (fp32, host)
+    float inv_n, inv_z;                 // 1 / sigma^2 of the normal and the depth term
+    int32_t levels;                     // bit 0: fill-2 pixels, bit 1: fill-4 pixels
+    int32_t remodulate;                 // 1: demodulate by the albedo guide, remodulate by the G-buffer's albedo
+};
+void fovpt_launch_reconstruct(hipStream_t st, const FrameDev& fd, const ReconstructArgs& a, const fovpt_float4* in, const fovpt_float4* albedo,
+                              GBufferDev g, fovpt_float4* out_color, uint32_t* out_rgba);
 void fovpt_launch_build_guide(hipStream_t st, const float* cdf, int n, int segments, uint32_t* guide);
 void fovpt_launch_probe_records(hipStream_t st, size_t n, const float* cdfX, const float* pdfX, const float4* data, float4* rec);
 void fovpt_launch_build_cdf(hipStream_t st, int w, int h, const float4* data, float* pdfX, float* cdfX, float* pdfY, float* cdfY, float* row_total);

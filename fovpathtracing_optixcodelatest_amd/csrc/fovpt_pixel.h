@@ -1,4 +1,5 @@
-// fovpt_pixel.h -- device helpers shared by the wavefront kernels (wavefront.hip) and the denoiser (denoise.hip): the fp32
+// fovpt_pixel.h -- device helpers shared by the wavefront kernels (wavefront.hip), the denoiser (denoise.hip) and the
+// reconstruction (reconstruct.hip): the fp32
 // vector type, the ring test, the last-writer search over a frame's passes and the resolve's tone map.
 #pragma once
 

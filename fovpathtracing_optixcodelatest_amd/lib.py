@@ -19,6 +19,7 @@ EXPORTS = [
     "fovpt_probe_build_cdf", "fovpt_camera_uvw", "fovpt_debug_math", "fovpt_debug_buffer", "fovpt_debug_trace",
     "fovpt_gather_plan", "fovpt_gather_pack", "fovpt_gather_unpack",
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
+    "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
     "fovpt_model_load_obj", "fovpt_model_load_gltf", "fovpt_model_destroy", "fovpt_model_counts", "fovpt_model_get_mesh", "fovpt_model_get_texture",
     "fovpt_image_load_float4", "fovpt_image_free", "fovpt_image_load_rgba8", "fovpt_image_free_rgba8",
@@ -133,6 +134,10 @@ def load():
     L.fovpt_denoise_defaults.argtypes = [C.POINTER(abi.DenoiseConfig)]
     L.fovpt_denoise.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.DenoiseConfig), vp, vp]
     L.fovpt_denoise_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_gbuffer.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.GBufferPtrs)]
+    L.fovpt_reconstruct_defaults.argtypes = [C.POINTER(abi.ReconstructConfig)]
+    L.fovpt_reconstruct.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.ReconstructConfig), vp, vp, vp]
+    L.fovpt_reconstruct_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_comm_get_unique_id.argtypes = [vp]
     L.fovpt_comm_init.argtypes = [vp, vp, i32, i32]
     L.fovpt_comm_destroy.argtypes = [vp]

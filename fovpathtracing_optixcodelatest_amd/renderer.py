@@ -250,6 +250,56 @@ class SampleRenderer:
         out = np.empty((f.size.y, f.size.x, 4), np.float32)
         return self.download(self.denoise_buffers()[0], out)
 
+    # -- G-buffer and reconstruction of the rendered frame (include/fovpt.h, fovpt_gbuffer / fovpt_reconstruct)
+    def gbuffer(self) -> abi.GBufferPtrs:
+        """Enqueues the primary-visibility G-buffer of the current frame size and camera on the renderer's stream (not
+        synchronised) and returns its device pointers (prim uint32, position / normal / albedo float4 per pixel)."""
+        g = abi.GBufferPtrs()
+        self._check(self._L.fovpt_gbuffer(self._ctx, C.byref(self.launchParams), C.byref(g)))
+        return g
+
+    def downloadGBuffer(self, g=None):
+        """The G-buffer as numpy arrays {prim (H, W) uint32, position / normal / albedo (H, W, 4) float32}; g: what gbuffer()
+        returned (None: build it now)."""
+        g = g if g is not None else self.gbuffer()
+        shape = (g.height, g.width)
+        out = dict(prim=self.download(g.prim, np.empty(shape, np.uint32)))
+        for k in ("position", "normal", "albedo"):
+            out[k] = self.download(getattr(g, k), np.empty(shape + (4,), np.float32))
+        return out
+
+    @staticmethod
+    def reconstruct_defaults() -> abi.ReconstructConfig:
+        d = abi.ReconstructConfig()
+        lib.check(None, lib.load().fovpt_reconstruct_defaults(C.byref(d)))
+        return d
+
+    def reconstruct(self, cfg=None, in_color=None, out_color=None, out_rgba=None):
+        """Reconstructs the block-filled pixels of the frame last rendered (remodulate = 1 needs config.write_guides = 1).
+        in_color: device pointer of a float4 frame (None: the accum buffer; e.g. denoise_buffers()[0]).  out_color / out_rgba:
+        device pointers, or None for the renderer's own buffers (downloadReconstructedColor / downloadReconstructedPixels).
+        Enqueued on the renderer's stream, not synchronised (the downloads synchronise)."""
+        cfg = cfg if cfg is not None else self.reconstruct_defaults()
+        self._check(self._L.fovpt_reconstruct(self._ctx, C.byref(self.launchParams), C.byref(cfg), in_color, out_color, out_rgba))
+
+    def reconstruct_buffers(self):
+        """Device addresses of the renderer's own reconstruction outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_reconstruct_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def downloadReconstructedPixels(self):
+        """The rgba8 output of the last reconstruct into the renderer's own buffer, shaped like downloadPixels()."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x), np.uint32)
+        return self.download(self.reconstruct_buffers()[1], out)
+
+    def downloadReconstructedColor(self):
+        """The float4 output of the last reconstruct into the renderer's own buffer."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x, 4), np.float32)
+        return self.download(self.reconstruct_buffers()[0], out)
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

@@ -116,6 +116,24 @@ public:
         check(fovpt_denoise_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- reconstruction (new with this library; the reference family has none): rebuilds the block-filled middle ring and
+    // periphery of the frame just rendered from a full-resolution G-buffer -- remodulate = 1 needs fovpt_config.write_guides = 1
+    // -- into the renderer's own buffers, then a device sync like render().  in_color: nullptr = the accum buffer, or e.g. the
+    // denoiser's colour output (fovpt_denoise_buffers)
+    void reconstruct(const fovpt_float4* in_color = nullptr) { fovpt_reconstruct_config rc; check(fovpt_reconstruct_defaults(&rc)); reconstruct(rc, in_color); }
+    void reconstruct(const fovpt_reconstruct_config& rc, const fovpt_float4* in_color = nullptr)
+    {
+        check(fovpt_reconstruct(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &rc, in_color, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // the reconstructed rgba8 pixels, like downloadPixels
+    void downloadReconstructedPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_reconstruct_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

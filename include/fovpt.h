@@ -305,6 +305,55 @@ int fovpt_denoise(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_den
                   fovpt_float4* out_color, uint32_t* out_rgba);
 int fovpt_denoise_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 
+/* ---- G-buffer and reconstruction of the rendered frame ---------------------------------------------------------------
+ * New with this library (the reference family has no counterpart; its denoiser runs on the block-filled frame).  A foveated
+ * frame leaves the periphery as 4 x 4 copies of one sample and the middle ring as 2 x 2 copies; fovpt_reconstruct rebuilds
+ * those pixels from the 3 x 3 neighbouring samples of their fill, guided by a full-resolution primary-visibility G-buffer
+ * (cf. Weier et al. 2016, Koskela et al. 2019), and remodulates with per-pixel albedo so that textures are sharp again.
+ * Only + - * / max min: the result is defined bit for bit (tests/reconstruct_ref.py restates it in numpy float32).
+ *   fovpt_gbuffer              traces one ray per pixel of lp->frame.size with lp's camera (generate_rays' expression with
+ *                              jitter 0.5, the production closest-hit traversal) into buffers the context owns (allocated on
+ *                              first use, reallocated by fovpt_resize, freed by fovpt_destroy); `out` receives their device
+ *                              pointers.  Per pixel: prim (global primitive id, 0xffffffff on a miss), position (eye + t dir,
+ *                              t; a miss (0, 0, 0, -1)), normal (the face-forwarded geometric normal of the shading kernel, w 0)
+ *                              and albedo (material colour or its texel, w 0); a miss has zero normal and albedo.  Enqueued on
+ *                              fovpt_stream(), not synchronised.  FOVPT_E_INVALID: null arguments, an empty frame size;
+ *                              FOVPT_E_NO_SCENE: no scene (or lp->traversable is not the current one).
+ *   fovpt_reconstruct          reconstructs the frame last issued with fovpt_render(ctx, lp): builds its G-buffer, then for
+ *                              every pixel whose last writer has fill f > 1 and whose level is on in rc->levels, interpolates
+ *                              in_color / albedo guide (remodulate = 1) or in_color (0) over the 3 x 3 samples around its
+ *                              block's anchor, weighted by a tent of width support * f, normal and plane-distance edge
+ *                              stopping, and multiplies by the pixel's own G-buffer albedo.  in_color NULL = accum_buffer
+ *                              (typically: fovpt_denoise's colour output otherwise).  Other pixels, and pixels whose weights
+ *                              sum to 0, get in_color unchanged.  out_color float4 (alpha 1 where reconstructed), out_rgba
+ *                              rgba8 (the resolve's tone map of out_color), device pointers of frame.size; either may be NULL
+ *                              = the context's own buffers.  Enqueued on fovpt_stream(), not synchronised, ordered like
+ *                              fovpt_denoise.  Writes its outputs and the G-buffer, nothing else.  FOVPT_E_INVALID: null
+ *                              ctx / lp / rc, a value out of range, remodulate = 1 with write_guides = 0 (or shadow-catcher
+ *                              scenes), world > 1, in_color equal to the output colour buffer; FOVPT_E_NO_SCENE: no scene;
+ *                              FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size differs.
+ *   fovpt_reconstruct_buffers  addresses of the context's own outputs (allocated for the last frame if not yet).        */
+typedef struct fovpt_gbuffer_ptrs {
+    uint32_t* prim;                /* device pointers, width * height entries each                                          */
+    fovpt_float4* position;
+    fovpt_float4* normal;
+    fovpt_float4* albedo;
+    int32_t width, height;
+} fovpt_gbuffer_ptrs;
+typedef struct fovpt_reconstruct_config {
+    float support;                 /* tent half-width in samples of the fill, 1 .. 2; default 2                             */
+    float normal_sigma;            /* normal edge stopping, > 0; default 0.5                                                */
+    float depth_sigma;             /* plane-distance edge stopping relative to the pixel's t, > 0; default 0.05             */
+    int32_t levels;                /* bit 0: middle ring (fill 2), bit 1: periphery (fill 4); default 3                     */
+    int32_t remodulate;            /* 1: interpolate colour / albedo guide, multiply by the G-buffer albedo; default 1      */
+    int32_t _reserved[3];          /* 0 */
+} fovpt_reconstruct_config;
+int fovpt_gbuffer(fovpt_ctx* ctx, const fovpt_launch_params* lp, fovpt_gbuffer_ptrs* out);
+int fovpt_reconstruct_defaults(fovpt_reconstruct_config* out);
+int fovpt_reconstruct(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_reconstruct_config* rc, const fovpt_float4* in_color,
+                      fovpt_float4* out_color, uint32_t* out_rgba);
+int fovpt_reconstruct_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+
 /* ---- multi-GPU: packed gather of the final framebuffer ----------------------------------
  * New with this library: the reference is single-GPU (SimplePathtracer.cpp:331-340).  With
  * fovpt_config.rank/world every handle renders the launch-index tiles it owns -- interleaved
@@ -440,6 +489,8 @@ static_assert(sizeof(fovpt_material) == 104, "Material ABI");
 static_assert(sizeof(fovpt_probe) == 64, "Probe ABI");
 static_assert(sizeof(fovpt_launch_params) == 248, "LaunchParams ABI");
 static_assert(sizeof(fovpt_denoise_config) == 32, "denoise config ABI");
+static_assert(sizeof(fovpt_reconstruct_config) == 32, "reconstruct config ABI");
+static_assert(sizeof(fovpt_gbuffer_ptrs) == 40, "gbuffer ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");
