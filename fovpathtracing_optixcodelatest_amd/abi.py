@@ -170,6 +170,10 @@ class Config(C.Structure):
         return m
 
 
+DENOISE_MAX_ITERATIONS = 5                     # FOVPT_DENOISE_MAX_ITERATIONS
+SIGMA_MIN, SIGMA_MAX = 1e-6, 1e6               # FOVPT_SIGMA_MIN / MAX (binary32 1e-6f / 1e6f): accepted *_sigma of both configs
+
+
 class DenoiseConfig(C.Structure):
     """fovpt_denoise_config: iterations per foveation level and the edge-stopping scales (defaults: fovpt_denoise_defaults)."""
     _fields_ = [

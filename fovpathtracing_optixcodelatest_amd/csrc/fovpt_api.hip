@@ -114,9 +114,13 @@ struct fovpt_ctx {
     std::vector<uint32_t> plan_off;        // host copy: rank r owns plan_idx[plan_off[r] .. plan_off[r + 1])
     std::string plan_key;                  // what the plan was built for
     bool use_accum_before = false;
-    // fovpt_denoise: the size of the frame last issued with fovpt_render (0 x 0: none since create / resize), the level map,
-    // the ping-pong filter buffers and the context's own outputs (allocated on first use)
+    // fovpt_denoise / fovpt_reconstruct: the frame last issued with fovpt_render as it was rendered (dn_w x dn_h; 0 x 0: none
+    // since create / resize): its passes, gaze and camera (dn_frame), and the FOV_OFF flag, guides and shard count of its config.
+    // Post-processing reads these, never the caller's current config, gaze or camera.  Then the level map, the ping-pong
+    // filter buffers and the context's own outputs (allocated on first use)
     int dn_w = 0, dn_h = 0;
+    FrameDev dn_frame{};
+    int32_t dn_uniform = 0, dn_guides = 0, dn_world = 1;
     DevBuf dn_level, dn_i0, dn_i1, dn_color, dn_rgba;
     // fovpt_gbuffer / fovpt_reconstruct: the G-buffer's own ray queue, hit records, counters and outputs (never a render state
     // set: a frame in flight may be using those), and the context's own reconstruction outputs; all allocated on first use
@@ -613,18 +617,33 @@ int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P)
 }
 
 // ---- post-processing of the rendered frame: fovpt_denoise (denoise.hip), fovpt_gbuffer / fovpt_reconstruct (reconstruct.hip) --
-// The passes fovpt_render ran for the frame lp describes, whole (rows 0 .. gh) and on one rank: what find_last_writer needs to
-// give every pixel its writing pass and launch index.  Computed on a copy: the caller's parameters stay as they are.
-void frame_levels(const fovpt_ctx* c, const fovpt_launch_params* lp, FrameDev& fd)
+// an edge-stopping scale of fovpt_denoise / fovpt_reconstruct: inside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX], so that 1 / sigma^2
+// is a normal float and the denoiser's colour scale (1 / sigma^2) * 4^(FOVPT_DENOISE_MAX_ITERATIONS - 1) / 1e-4 stays finite
+// (an infinite scale makes the centre tap 0 * inf: every weight 0, the output 0 / 0)
+bool sigma_ok(float v) { return v >= FOVPT_SIGMA_MIN && v <= FOVPT_SIGMA_MAX; }
+
+// lp's camera into fd.eye / U / V / W (the rays of a G-buffer)
+void set_camera(FrameDev& fd, const fovpt_launch_params* lp)
+{
+    const fovpt_float3* cam[4] = {&lp->camera.eye, &lp->camera.U, &lp->camera.V, &lp->camera.W};
+    float* dst[4] = {fd.eye, fd.U, fd.V, fd.W};
+    for (int k = 0; k < 4; k++) { dst[k][0] = cam[k]->x; dst[k][1] = cam[k]->y; dst[k][2] = cam[k]->z; }
+}
+
+// The passes fovpt_render ran for the frame lp describes under cfg, whole (rows 0 .. gh) and on one rank: what
+// find_last_writer needs to give every pixel its writing pass and launch index; and lp's camera.  Computed on a copy: the
+// caller's parameters stay as they are.  fovpt_render keeps this for the frame it issued (fovpt_ctx::dn_frame).
+void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd)
 {
     fovpt_launch_params L = *lp;
     PassDev P[FOVPT_MAX_PASSES];
     memset(&fd, 0, sizeof(fd));
-    fd.npass = frame_passes(c->cfg, L, P);
+    fd.npass = frame_passes(cfg, L, P);
     for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
     fd.w = L.frame.size.x; fd.h = L.frame.size.y;
     fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
     fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
+    set_camera(fd, lp);
 }
 
 // the G-buffer's buffers for n pixels (the counters once: k_gbuffer_rays rewrites the queue sizes it uses on every call)
@@ -638,9 +657,10 @@ int reserve_gbuffer(fovpt_ctx* c, size_t n)
     return FOVPT_OK;
 }
 
-// Enqueues the G-buffer of lp (frame.size, camera) on fovpt_stream(): one ray per pixel, traced by the production closest-hit
-// k_traverse (so a ray gets the (prim, t, u, v) fovpt_debug_trace returns for it), then the per-pixel outputs.
-int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, GBufferDev& g, const char* who)
+// Enqueues the G-buffer of lp's frame.size seen by view's camera (view.eye / U / V / W) on fovpt_stream(): one ray per pixel,
+// traced by the production closest-hit k_traverse (so a ray gets the (prim, t, u, v) fovpt_debug_trace returns for it), then
+// the per-pixel outputs.
+int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who)
 {
     if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene (traversable %llu, current %llu)", who,
                                                                      (unsigned long long)lp->traversable, (unsigned long long)c->scene_id);
@@ -656,9 +676,8 @@ int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, GBufferDev& g, 
     FrameDev fd;
     memset(&fd, 0, sizeof(fd));
     fd.w = w; fd.h = h;
-    const fovpt_float3* cam[4] = {&lp->camera.eye, &lp->camera.U, &lp->camera.V, &lp->camera.W};
-    float* dst[4] = {fd.eye, fd.U, fd.V, fd.W};
-    for (int k = 0; k < 4; k++) { dst[k][0] = cam[k]->x; dst[k][1] = cam[k]->y; dst[k][2] = cam[k]->z; }
+    memcpy(fd.eye, view.eye, sizeof(fd.eye)); memcpy(fd.U, view.U, sizeof(fd.U));
+    memcpy(fd.V, view.V, sizeof(fd.V)); memcpy(fd.W, view.W, sizeof(fd.W));
     RayQueue q; q.o = (float4*)c->gb_o.p; q.d = (float4*)c->gb_d.p;
     PathState ps;
     memset(&ps, 0, sizeof(ps));
@@ -1069,7 +1088,13 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
     const int rc = run_passes(c, lp, P, npass, 1);
     lp->frame.subframe_index = temp_frame;                                                   // :128-129 / :210-211
     lp->frame.subframe_index++;
-    if (rc == FOVPT_OK) { c->dn_w = lp->frame.size.x; c->dn_h = lp->frame.size.y; }          // what fovpt_denoise may filter
+    if (rc == FOVPT_OK) {                                                                     // what post-processing may filter
+        c->dn_w = lp->frame.size.x; c->dn_h = lp->frame.size.y;
+        frame_levels(c->cfg, lp, c->dn_frame);
+        c->dn_uniform = c->cfg.uniform;
+        c->dn_guides = c->cfg.write_guides;
+        c->dn_world = c->cfg.world;
+    }
     return rc;
 }
 
@@ -1125,10 +1150,10 @@ int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoi
         if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: iteration count %d outside 0 .. %d", n, FOVPT_DENOISE_MAX_ITERATIONS);
     const float sig[3] = {dc->color_sigma, dc->normal_sigma, dc->albedo_sigma};
     for (float v : sig)
-        if (!(v > 0.0f) || !std::isfinite(v)) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: sigma %g must be finite and > 0", (double)v);
-    if (!c->cfg.write_guides || c->any_catcher) return fail(c, FOVPT_E_INVALID, "fovpt_denoise needs the denoiser guides: fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
-    if (c->cfg.world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: a tile shard (world = %d) has no neighbours to filter with", c->cfg.world);
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
     if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise: no frame rendered yet");
+    if (!c->dn_guides || c->any_catcher) return fail(c, FOVPT_E_INVALID, "fovpt_denoise needs the denoiser guides: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
+    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: a tile shard (world = %d) has no neighbours to filter with", c->dn_world);
     if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
         return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
     if (!lp->frame.color_buffer || !lp->frame.normal_buffer || !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null guide buffers");
@@ -1142,11 +1167,10 @@ int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoi
     if (!out_rgba) out_rgba = (uint32_t*)c->dn_rgba.p;
 
     // the level map: the passes fovpt_render ran for this frame
-    FrameDev fd;
-    frame_levels(c, lp, fd);
+    const FrameDev& fd = c->dn_frame;
     DenoiseArgs a;
     memset(&a, 0, sizeof(a));
-    if (c->cfg.uniform) a.n_pass[0] = dc->iterations_uniform;
+    if (c->dn_uniform) a.n_pass[0] = dc->iterations_uniform;
     else { a.n_pass[0] = dc->iterations_periphery; a.n_pass[1] = dc->iterations_middle; a.n_pass[2] = dc->iterations_fovea; }
     for (int p = 0; p < fd.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
     auto inv_sq = [](float s) { const float s2 = s * s; return 1.0f / s2; };
@@ -1164,7 +1188,10 @@ int fovpt_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, fovpt_gbuffer_ptr
     if (!c) return FOVPT_E_INVALID;
     if (!lp || !out) return fail(c, FOVPT_E_INVALID, "fovpt_gbuffer: null argument");
     GBufferDev g;
-    const int rc = enqueue_gbuffer(c, lp, g, "fovpt_gbuffer");
+    FrameDev view;
+    memset(&view, 0, sizeof(view));
+    set_camera(view, lp);
+    const int rc = enqueue_gbuffer(c, lp, view, g, "fovpt_gbuffer");
     if (rc) return rc;
     out->prim = g.prim;
     out->position = (fovpt_float4*)g.pos; out->normal = (fovpt_float4*)g.nrm; out->albedo = (fovpt_float4*)g.alb;
@@ -1208,16 +1235,16 @@ int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_r
     if (!(rc->support >= 1.0f && rc->support <= 2.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: support %g outside [1, 2]", (double)rc->support);
     const float sig[2] = {rc->normal_sigma, rc->depth_sigma};
     for (float v : sig)
-        if (!(v > 0.0f) || !std::isfinite(v)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: sigma %g must be finite and > 0", (double)v);
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
     if (rc->levels < 0 || rc->levels > 3) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: levels %d outside 0 .. 3", rc->levels);
     if (rc->remodulate != 0 && rc->remodulate != 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: remodulate %d is neither 0 nor 1", rc->remodulate);
     for (int32_t r : rc->_reserved)
         if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: reserved fields must be 0");
     if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_reconstruct without a scene");
-    if (rc->remodulate && (!c->cfg.write_guides || c->any_catcher))
-        return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct with remodulate = 1 needs the albedo guide: fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
-    if (c->cfg.world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: a tile shard (world = %d) has no neighbours to reconstruct from", c->cfg.world);
     if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct: no frame rendered yet");
+    if (rc->remodulate && (!c->dn_guides || c->any_catcher))
+        return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct with remodulate = 1 needs the albedo guide: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
+    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: a tile shard (world = %d) has no neighbours to reconstruct from", c->dn_world);
     if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
         return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
     const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
@@ -1230,9 +1257,8 @@ int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_r
     if (!out_rgba) out_rgba = (uint32_t*)c->rc_rgba.p;
     if (in == out_color) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: the input is the output colour buffer (it reads neighbours)");
     GBufferDev g;
-    { const int rc_ = enqueue_gbuffer(c, lp, g, "fovpt_reconstruct"); if (rc_) return rc_; }
-    FrameDev fd;
-    frame_levels(c, lp, fd);
+    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, "fovpt_reconstruct"); if (rc_) return rc_; }   // the rendered frame's camera
+    const FrameDev& fd = c->dn_frame;
     ReconstructArgs a;
     memset(&a, 0, sizeof(a));
     const float s = rc->support;

@@ -279,24 +279,32 @@ int fovpt_render(fovpt_ctx* ctx, fovpt_launch_params* lp);
  * the pass that wrote it last -- the fovea (8 spp as shipped) not at all by default, the periphery (one sample per 4 x 4 block)
  * most -- with taps at multiples of its block fill, so a filled block is never averaged with its own copies.  Only + - * / max,
  * no transcendental functions: the result is defined bit for bit (tests/denoise_ref.py restates it in numpy float32).
- *   fovpt_denoise           filters the frame last issued with fovpt_render(ctx, lp): out_color float4 (colour, alpha 1) and
+ *   fovpt_denoise           filters the frame last issued with fovpt_render(ctx, lp) as it was rendered: its passes, gaze
+ *                           and FOV_OFF flag are those of that call (the library keeps them), not lp's or the config's now,
+ *                           so a caller may write the next gaze, camera or config before filtering.  out_color float4 (colour, alpha 1) and
  *                           out_rgba rgba8 (the resolve's tone map of out_color) per pixel, device pointers of frame.size; either
  *                           may be NULL = the context's own buffers (allocated on first use, reallocated by fovpt_resize, freed
  *                           by fovpt_destroy).  Pixels with 0 iterations get accum_buffer / frame_buffer's values unchanged.
  *                           Enqueued on fovpt_stream(), not synchronised: behind that frame's resolve and ahead of the next
  *                           frame's, whatever frames_in_flight / chains_per_frame say.  Reads the guides; writes nothing else.
- *                           FOVPT_E_INVALID: null arguments, an iteration count outside 0 .. 5, a sigma <= 0 or not finite,
- *                           write_guides = 0 (or shadow-catcher scenes, which cannot write guides), world > 1 (a shard has no
- *                           neighbours); FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size differs.
+ *                           FOVPT_E_INVALID: null arguments, an iteration count outside 0 .. 5, a sigma outside
+ *                           [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX] (or NaN), a frame rendered with write_guides = 0 (or
+ *                           shadow-catcher scenes, which cannot write guides) or world > 1 (a shard has no neighbours);
+ *                           FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size differs.
  *   fovpt_denoise_buffers   addresses of the context's own outputs (allocated for the last frame if not yet).                 */
 #define FOVPT_DENOISE_MAX_ITERATIONS 5
+/* the accepted range of every edge-stopping scale (fovpt_denoise_config and fovpt_reconstruct_config *_sigma): 1 / sigma^2
+ * stays a normal float and the denoiser's colour scale 4^(FOVPT_DENOISE_MAX_ITERATIONS - 1) / (1e-4 sigma^2) stays finite */
+#define FOVPT_SIGMA_MIN 1e-6f
+#define FOVPT_SIGMA_MAX 1e6f
 typedef struct fovpt_denoise_config {
     int32_t iterations_fovea;      /* a-trous iterations of pixels last written by pass F (fill 1); default 0             */
     int32_t iterations_middle;     /* ... by pass M (fill 2); default 2                                                    */
     int32_t iterations_periphery;  /* ... by pass P (fill 4); default 3                                                    */
     int32_t iterations_uniform;    /* FOV_OFF frames (one pass, fill 1); default 3                                         */
     float color_sigma;             /* edge-stopping scales: colour (relative to the pixel's luminance, halved per          */
-    float normal_sigma;            /* iteration), normal and albedo distance; defaults from fovpt_denoise_defaults       */
+    float normal_sigma;            /* iteration), normal and albedo distance, each FOVPT_SIGMA_MIN .. FOVPT_SIGMA_MAX;    */
+                                   /* defaults from fovpt_denoise_defaults                                                 */
     float albedo_sigma;
     int32_t _reserved;             /* 0 */
 } fovpt_denoise_config;
@@ -319,7 +327,9 @@ int fovpt_denoise_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba)
  *                              and albedo (material colour or its texel, w 0); a miss has zero normal and albedo.  Enqueued on
  *                              fovpt_stream(), not synchronised.  FOVPT_E_INVALID: null arguments, an empty frame size;
  *                              FOVPT_E_NO_SCENE: no scene (or lp->traversable is not the current one).
- *   fovpt_reconstruct          reconstructs the frame last issued with fovpt_render(ctx, lp): builds its G-buffer, then for
+ *   fovpt_reconstruct          reconstructs the frame last issued with fovpt_render(ctx, lp) as it was rendered: its passes,
+ *                              gaze and camera are those of that call, not lp's or the config's now.  Builds its G-buffer
+ *                              (that camera, lp->frame.size), then for
  *                              every pixel whose last writer has fill f > 1 and whose level is on in rc->levels, interpolates
  *                              in_color / albedo guide (remodulate = 1) or in_color (0) over the 3 x 3 samples around its
  *                              block's anchor, weighted by a tent of width support * f, normal and plane-distance edge
@@ -329,8 +339,9 @@ int fovpt_denoise_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba)
  *                              rgba8 (the resolve's tone map of out_color), device pointers of frame.size; either may be NULL
  *                              = the context's own buffers.  Enqueued on fovpt_stream(), not synchronised, ordered like
  *                              fovpt_denoise.  Writes its outputs and the G-buffer, nothing else.  FOVPT_E_INVALID: null
- *                              ctx / lp / rc, a value out of range, remodulate = 1 with write_guides = 0 (or shadow-catcher
- *                              scenes), world > 1, in_color equal to the output colour buffer; FOVPT_E_NO_SCENE: no scene;
+ *                              ctx / lp / rc, a value out of range (a sigma outside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX]),
+ *                              remodulate = 1 on a frame rendered with write_guides = 0 (or shadow-catcher scenes), a frame
+ *                              rendered with world > 1, in_color equal to the output colour buffer; FOVPT_E_NO_SCENE: no scene;
  *                              FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size differs.
  *   fovpt_reconstruct_buffers  addresses of the context's own outputs (allocated for the last frame if not yet).        */
 typedef struct fovpt_gbuffer_ptrs {
@@ -342,8 +353,8 @@ typedef struct fovpt_gbuffer_ptrs {
 } fovpt_gbuffer_ptrs;
 typedef struct fovpt_reconstruct_config {
     float support;                 /* tent half-width in samples of the fill, 1 .. 2; default 2                             */
-    float normal_sigma;            /* normal edge stopping, > 0; default 0.5                                                */
-    float depth_sigma;             /* plane-distance edge stopping relative to the pixel's t, > 0; default 0.05             */
+    float normal_sigma;            /* normal edge stopping, FOVPT_SIGMA_MIN .. MAX; default 0.5                            */
+    float depth_sigma;             /* plane-distance edge stopping relative to the pixel's t, FOVPT_SIGMA_MIN .. MAX; 0.05 */
     int32_t levels;                /* bit 0: middle ring (fill 2), bit 1: periphery (fill 4); default 3                     */
     int32_t remodulate;            /* 1: interpolate colour / albedo guide, multiply by the G-buffer albedo; default 1      */
     int32_t _reserved[3];          /* 0 */

@@ -60,7 +60,8 @@ def frame_passes(w, h, gaze, r_inner, r_outer, uniform):
 def level_map(w, h, gaze, r_inner, r_outer, uniform):
     """(fill, pass) per pixel of the last writer: every launch index that passes the ring test (on its block's top-left
     pixel, deviceProgram.cu:433-440) writes its fill x fill block, clamped onto the frame's last row / column (:546-554);
-    later passes overwrite earlier ones.  fill 0 / pass -1: no writer."""
+    later passes overwrite earlier ones.  The block's pixel indices are uint32 sums like the launch's (deviceProgram.cu:546-554):
+    a launch at a wrapped index 0xffffffff writes pixel 0 and the last row / column.  fill 0 / pass -1: no writer."""
     fill = np.zeros((h, w), np.int32)
     pas = np.full((h, w), -1, np.int32)
     cx, cy = gaze
@@ -75,8 +76,8 @@ def level_map(w, h, gaze, r_inner, r_outer, uniform):
         ix, iy = ix[alive], iy[alive]
         for v in range(fl):
             for u in range(fl):
-                px = np.minimum(ix + u, w - 1).astype(np.int64)
-                py = np.minimum(iy + v, h - 1).astype(np.int64)
+                px = np.minimum((ix + u) & 0xffffffff, w - 1).astype(np.int64)      # uint32 sums: 0xffffffff + 1 is pixel 0
+                py = np.minimum((iy + v) & 0xffffffff, h - 1).astype(np.int64)
                 fill[py, px] = fl
                 pas[py, px] = p
     return fill, pas
@@ -93,8 +94,9 @@ def iteration_map(fill, pas, cfg, uniform):
     return n
 
 
-def denoise(color, normal, albedo, fill, n, cfg):
-    """-> (out_color float32 (h, w, 4), filtered I before remodulation).  color / normal / albedo: the guide buffers."""
+def denoise(color, normal, albedo, fill, n, cfg, record=None):
+    """-> (out_color float32 (h, w, 4), filtered I before remodulation).  color / normal / albedo: the guide buffers.
+    record: a list that receives (i, active, w) for every tap of iteration i and then (i, active, sum w)."""
     cfg = dict(DEFAULTS, **cfg)
     C = np.ascontiguousarray(color[..., :3], np.float32)
     N = np.ascontiguousarray(normal[..., :3], np.float32)
@@ -125,6 +127,10 @@ def denoise(color, normal, albedo, fill, n, cfg):
                 wt = ((H[dx + 2] * H[dy + 2] * wc) * wn) * wa
                 sw = sw + wt
                 acc = acc + Iq * wt[..., None]
+                if record is not None:
+                    record.append((i, act, wt))
+        if record is not None:
+            record.append((i, act, sw))
         I = np.where(act[..., None], acc / np.where(act, sw, f32(1.0))[..., None], I)
     out = np.empty((h, w, 4), np.float32)
     out[..., :3] = np.where((n >= 1)[..., None], I * D, C)

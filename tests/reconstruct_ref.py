@@ -66,7 +66,8 @@ def frame_passes(w, h, gaze, r_inner, r_outer, uniform):
 
 def writers(w, h, gaze, r_inner, r_outer, uniform):
     """(fill, pass, anchor x, anchor y) per pixel of its last writer: every launch index that passes the ring test (on its
-    block's top-left pixel) writes its fill x fill block, clamped onto the frame's last row / column; the highest pass wins,
+    block's top-left pixel) writes its fill x fill block, clamped onto the frame's last row / column (pixel indices are uint32
+    sums, so a block at a wrapped index 0xffffffff also covers pixel 0); the highest pass wins,
     within a pass the launch index that comes last.  fill 0 / pass -1: no writer.  Anchors are the uint32 values."""
     best = np.full((h, w), -1, np.int64)
     passes = frame_passes(w, h, gaze, r_inner, r_outer, uniform)
@@ -83,7 +84,7 @@ def writers(w, h, gaze, r_inner, r_outer, uniform):
         ix, iy, key = ix[alive], iy[alive], key[alive]
         for v in range(fl):
             for u in range(fl):
-                np.maximum.at(best, (np.minimum(iy + v, h - 1), np.minimum(ix + u, w - 1)), key)
+                np.maximum.at(best, (np.minimum((iy + v) & 0xffffffff, h - 1), np.minimum((ix + u) & 0xffffffff, w - 1)), key)
     fill = np.zeros((h, w), np.int64)
     pas = np.full((h, w), -1, np.int64)
     ax = np.zeros((h, w), np.int64)

@@ -136,3 +136,65 @@ def test_level_map_follows_the_passes():
     assert (pas == 0).all() and (fill == 1).all()
     fill, pas = dn.level_map(30, 20, (200, 200), 2, 5, 0)       # the gaze off the frame: P, and F clamped onto the corner
     assert pas[19, 29] == 2 and (pas[:-1, 28:] == -1).all() and (pas[:, :28] == 0).all() and (fill[:, :28] == 4).all()
+
+
+def test_sigma_bounds_are_the_header_constants(tmp_path):
+    """abi.SIGMA_MIN / MAX are FOVPT_SIGMA_MIN / MAX (binary32) and abi.DENOISE_MAX_ITERATIONS is FOVPT_DENOISE_MAX_ITERATIONS."""
+    src = '#include <stdio.h>\n#include "fovpt.h"\nint main(void){printf("%a %a %d", (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX, ' \
+          'FOVPT_DENOISE_MAX_ITERATIONS); return 0;}\n'
+    exe = str(tmp_path / "sigma_bounds")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    lo, hi, its = subprocess.check_output([exe]).split()
+    assert float.fromhex(lo.decode()) == float(np.float32(abi.SIGMA_MIN))
+    assert float.fromhex(hi.decode()) == float(np.float32(abi.SIGMA_MAX))
+    assert int(its) == abi.DENOISE_MAX_ITERATIONS
+
+
+def test_the_sigma_bounds_keep_every_weight_finite():
+    """At both ends of [SIGMA_MIN, SIGMA_MAX] for every sigma, 5 iterations on a frame with black pixels (lum 0, where the
+    colour scale 4^i / (1e-4 sigma^2) is largest) and zero normals (misses): 1 / sigma^2 is a normal float, every tap weight
+    is finite, every filtered pixel keeps at least its centre tap's 9/64, and the output is finite.  Far below the bound the
+    scale overflows and the output is 0 / 0, which is why fovpt_denoise rejects such sigmas."""
+    h, w = 23, 37
+    color, normal, albedo = _guides(h, w, seed=8)
+    rng = np.random.default_rng(9)
+    black = rng.random((h, w)) < 0.4
+    color[black, :3] = 0.0
+    normal[rng.random((h, w)) < 0.2, :3] = 0.0
+    albedo[rng.random((h, w)) < 0.2, :3] = 0.0
+    fill, pas = dn.level_map(w, h, (18, 11), 3, 9, 0)
+    n = np.where(pas >= 0, abi.DENOISE_MAX_ITERATIONS, 0).astype(np.int32)
+    assert (n == 5).mean() > 0.8 and {1, 2, 4} <= set(np.unique(fill).tolist())
+    tiny = np.finfo(np.float32).tiny
+    for lo in (abi.SIGMA_MIN, abi.SIGMA_MAX):
+        for hi in (abi.SIGMA_MIN, abi.SIGMA_MAX):
+            inv = dn.inv_sq(lo)
+            assert tiny <= inv < np.inf and np.isfinite(inv * np.float32(4 ** (abi.DENOISE_MAX_ITERATIONS - 1)) / np.float32(1e-4))
+            cfg = dict(color_sigma=lo, normal_sigma=hi, albedo_sigma=hi)
+            rec = []
+            with np.errstate(over="ignore"):             # (|I_q - I_p|^2 k may overflow to inf: that tap's weight is 0)
+                out, _ = dn.denoise(color, normal, albedo, fill, n, cfg, record=rec)
+            assert len(rec) == 26 * abi.DENOISE_MAX_ITERATIONS
+            for k, (i, act, wt) in enumerate(rec):
+                assert np.isfinite(wt).all(), (lo, hi, i)
+                if k % 26 == 25:                                     # the sum over the 25 taps
+                    assert (wt[act] >= np.float32(9.0 / 64)).all(), (lo, hi, i)
+            assert np.isfinite(out).all(), (lo, hi)
+    with np.errstate(over="ignore", invalid="ignore"):
+        out, _ = dn.denoise(color, normal, albedo, fill, n, dict(color_sigma=1e-17))
+    assert np.isnan(out[black & (n == 5)]).any()
+
+
+@pytest.mark.parametrize("gaze", [(30, 20), (-1, -1), (-7, 12), (-2, 14), (30, -4), (44, 27)])
+def test_level_map_writes_the_pixels_the_oracle_writes(oracle, gaze):
+    """The pixels the restatement's level map gives a writer are exactly those a frame of the oracle writes (alpha 1 in a
+    zeroed accum buffer): also with the gaze off the frame, where M and F launches at wrapped (uint32) indices pass the ring
+    test and their blocks' uint32 pixel sums wrap onto row / column 0 as well as clamping onto the last ones."""
+    from fovpathtracing_optixcodelatest_amd import scenes
+    from common import cfg_foveated, make_oracle
+    w, h = 45, 28
+    cfg = cfg_foveated(3, 9, (1, 1, 1), max_depth=1)
+    S, F = make_oracle(oracle, scenes.cornell_box(), scenes.ambient_probe(8, 4, 1.0), scenes.CORNELL_CAMERA, (w, h), gaze=gaze)
+    oracle.render(S, F, cfg)
+    fill, pas = dn.level_map(w, h, tuple(v & 0xffffffff for v in gaze), cfg.r_inner, cfg.r_outer, 0)
+    assert np.array_equal(pas >= 0, F.accum[..., 3] == 1)

@@ -11,56 +11,22 @@ import denoise_ref as dn
 from fovpathtracing_optixcodelatest_amd import abi, lib, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
+from postprocess_common import bits as _bits, check_denoise as _check_bits, dcfg as _dcfg, guides as _guides
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
+SIGMAS = ("color_sigma", "normal_sigma", "albedo_sigma")
+# the binary32 neighbours just outside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX]
+SIGMA_OUTSIDE = (float(np.nextafter(np.float32(abi.SIGMA_MIN), np.float32(0))), float(np.nextafter(np.float32(abi.SIGMA_MAX), np.float32(np.inf))))
 # periphery RMSE (raw foveated frame) / periphery RMSE (denoised, defaults) against a 256-spp render, 384 x 216 atrium:
 # measured 2.27 on an MI355X (middle ring 2.28; tools/denoise_perf.py --sweep); the test keeps a margin below that
 QUALITY_MIN_GAIN = 1.8
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _guides(r):
-    f = r.launchParams.frame
-    shape = (f.size.y, f.size.x, 4)
-    return [r.download(p, np.empty(shape, np.float32)) for p in (f.color_buffer, f.normal_buffer, f.albedo_buffer)]
-
-
-def _expected(r, cfg, dcfg=None):
-    """The restatement over the GPU's guide buffers for the frame r rendered last with cfg."""
-    f = r.launchParams.frame
-    color, normal, albedo = _guides(r)
-    fill, pas = dn.level_map(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)
-    d = dict(dn.DEFAULTS, **(dcfg or {}))
-    n = dn.iteration_map(fill, pas, d, cfg.uniform)
-    out, _ = dn.denoise(color, normal, albedo, fill, n, d)
-    return out, n, pas
-
-
-def _dcfg(d):
-    c = abi.DenoiseConfig()
-    lib.check(None, lib.load().fovpt_denoise_defaults(c))
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
-
-
 def _atrium(size, cfg, gaze=None, tris=8000):
     cfg.write_guides = 1
     return make_gpu(scenes.atrium(tris), scenes.ambient_probe(96, 54, 2.5), scenes.ATRIUM_CAMERA, size, cfg, gaze=gaze)
-
-
-def _check_bits(oracle, r, cfg, dcfg=None):
-    r.denoise(_dcfg(dcfg) if dcfg else None)
-    got_c, got_px = r.downloadDenoisedColor(), r.downloadDenoisedPixels()
-    want, n, pas = _expected(r, cfg, dcfg)
-    assert np.array_equal(_bits(got_c), _bits(want))
-    assert np.array_equal(got_px, oracle.make_color(want[..., :3].reshape(-1, 3)).reshape(got_px.shape))
-    return got_c, n, pas
 
 
 @pytest.mark.parametrize("gaze", ["centre", "corner"])
@@ -135,10 +101,12 @@ def test_denoise_errors():
     r.render()
     r.denoise()
     for k, v in (("iterations_middle", 6), ("iterations_fovea", -1), ("color_sigma", 0.0), ("normal_sigma", float("inf")),
-                 ("albedo_sigma", float("nan"))):
+                 ("albedo_sigma", float("nan"))) + tuple((k, v) for k in SIGMAS for v in SIGMA_OUTSIDE):
         with pytest.raises(lib.FovptError) as e:
             r.denoise(_dcfg({k: v}))
-        assert e.value.code == E_INVALID, k
+        assert e.value.code == E_INVALID, (k, v)
+    r.denoise(_dcfg({k: abi.SIGMA_MIN for k in SIGMAS}))  # the bounds themselves are accepted
+    r.denoise(_dcfg({k: abi.SIGMA_MAX for k in SIGMAS}))
     f = r.launchParams.frame
     f.size.x -= 4                                        # not the size of the frame last rendered
     with pytest.raises(lib.FovptError) as e:

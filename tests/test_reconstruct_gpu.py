@@ -12,6 +12,8 @@ import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
+from postprocess_common import BOX_CAMERA, bits as _bits, box_model as _box_model, check_reconstruct as _check_bits, \
+    expected_gbuffer as _expected_gbuffer, rcfg as _rcfg
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,69 +25,9 @@ QUALITY_MIN_GAIN = 1.8
 QUALITY_MIN_GAIN_DENOISED = 1.2
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _f32(a):
-    return np.asarray(a, np.float32)
-
-
-def _box_model():
-    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
-    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
-    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
-    return scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 1, 1), red)])
-
-
-BOX_CAMERA = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
-
-
 def _atrium(size, cfg, gaze=None, tris=8000):
     cfg.write_guides = 1
     return make_gpu(scenes.atrium(tris), scenes.ambient_probe(96, 54, 2.5), scenes.ATRIUM_CAMERA, size, cfg, gaze=gaze)
-
-
-def _expected_gbuffer(oracle, model, r):
-    """The G-buffer restated: numpy rays, the oracle's closest hit, numpy float32 cross / normalize, oracle tex2d."""
-    f, cam = r.launchParams.frame, r.launchParams.camera
-    w, h = f.size.x, f.size.y
-    vec = lambda v: (v.x, v.y, v.z)
-    o, d = rr.primary_rays(w, h, vec(cam.eye), vec(cam.U), vec(cam.V), vec(cam.W))
-    prim, tuv, _ = oracle.OracleScene(model).trace(o, d)
-    # global primitive order: mesh order, then index order (fovpt_set_scene)
-    tri = np.concatenate([_f32(m.vertex)[np.asarray(m.index, np.int64)] for m in model.meshes])          # (T, 3, 3)
-    mesh_of = np.concatenate([np.full(len(m.index), k) for k, m in enumerate(model.meshes)])
-    hit = prim != rr.MISS
-    p = np.where(hit, prim, 0).astype(np.int64)
-    t, u, v = tuv[:, 0], tuv[:, 1], tuv[:, 2]
-    e1, e2 = tri[p, 1] - tri[p, 0], tri[p, 2] - tri[p, 0]
-    c = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                  e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
-    n0 = c * (np.float32(1.0) / np.sqrt(rr._dot(c, c)))[:, None]
-    nrm = n0 * np.copysign(np.float32(1.0), rr._dot(-d, n0))[:, None]
-    pos = o + t[:, None] * d
-    alb = np.zeros((len(p), 3), np.float32)
-    for k, m in enumerate(model.meshes):
-        sel = hit & (mesh_of[p] == k)
-        if m.texture_id >= 0 and m.texcoord is not None:
-            tc = _f32(m.texcoord)[np.asarray(m.index, np.int64)]                                           # (Tm, 3, 2)
-            first = int(np.flatnonzero(mesh_of == k)[0])
-            q = tc[p[sel] - first]
-            w0 = (np.float32(1.0) - u[sel]) - v[sel]
-            uv = (w0[:, None] * q[:, 0] + u[sel][:, None] * q[:, 1]) + v[sel][:, None] * q[:, 2]
-            alb[sel] = oracle.tex2d(model.textures[m.texture_id], uv)[:, :3]
-        else:
-            alb[sel] = np.float32([m.material.color.x, m.material.color.y, m.material.color.z])
-    out = dict(prim=prim.reshape(h, w), position=np.zeros((h * w, 4), np.float32), normal=np.zeros((h * w, 4), np.float32),
-               albedo=np.zeros((h * w, 4), np.float32))
-    out["position"][:, 3] = -1.0
-    out["position"][hit] = np.concatenate([pos, t[:, None]], axis=1)[hit]
-    out["normal"][hit, :3] = nrm[hit]
-    out["albedo"][hit, :3] = alb[hit]
-    for k in ("position", "normal", "albedo"):
-        out[k] = out[k].reshape(h, w, 4)
-    return out
 
 
 @pytest.mark.parametrize("scene", ["cornell", "atrium", "sky", "odd"])
@@ -116,33 +58,6 @@ def test_gbuffer_matches_the_restatement(oracle, scene):
     o, d = rr.primary_rays(f.size.x, f.size.y, *(vec(getattr(r.launchParams.camera, n)) for n in ("eye", "U", "V", "W")))
     assert np.array_equal(r.debug_trace(o, d)[0].reshape(got["prim"].shape), got["prim"])
     r.close()
-
-
-def _expected(r, cfg, rcfg=None, in_color=None):
-    f = r.launchParams.frame
-    shape = (f.size.y, f.size.x, 4)
-    albedo = r.download(f.albedo_buffer, np.empty(shape, np.float32))
-    inp = in_color if in_color is not None else r.downloadAccum()
-    fill, _, ax, ay = rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)
-    gb = r.downloadGBuffer()          # the same G-buffer the reconstruction built (same frame size and camera)
-    return rr.reconstruct(inp, albedo, gb, fill, ax, ay, rcfg), fill
-
-
-def _rcfg(d):
-    c = abi.ReconstructConfig()
-    lib.check(None, lib.load().fovpt_reconstruct_defaults(c))
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
-    return c
-
-
-def _check_bits(oracle, r, cfg, rcfg=None, in_color=None, in_ptr=None):
-    r.reconstruct(_rcfg(rcfg) if rcfg else None, in_ptr)
-    got_c, got_px = r.downloadReconstructedColor(), r.downloadReconstructedPixels()
-    want, fill = _expected(r, cfg, rcfg, in_color)
-    assert np.array_equal(_bits(got_c), _bits(want))
-    assert np.array_equal(got_px, oracle.make_color(want[..., :3].reshape(-1, 3)).reshape(got_px.shape))
-    return got_c, fill
 
 
 @pytest.mark.parametrize("gaze", ["centre", "corner"])
@@ -233,11 +148,15 @@ def test_reconstruct_errors():
     assert e.value.code == E_NO_FRAME
     r.render()
     r.reconstruct()
+    outside = (float(np.nextafter(np.float32(abi.SIGMA_MIN), np.float32(0))), float(np.nextafter(np.float32(abi.SIGMA_MAX), np.float32(np.inf))))
     for k, v in (("support", 0.5), ("support", 2.5), ("support", float("nan")), ("normal_sigma", 0.0), ("depth_sigma", float("inf")),
-                 ("depth_sigma", -1.0), ("levels", 4), ("levels", -1), ("remodulate", 2)):
+                 ("depth_sigma", -1.0), ("levels", 4), ("levels", -1), ("remodulate", 2)) + tuple(
+                     (k, v) for k in ("normal_sigma", "depth_sigma") for v in outside):
         with pytest.raises(lib.FovptError) as e:
             r.reconstruct(_rcfg({k: v}))
-        assert e.value.code == E_INVALID, k
+        assert e.value.code == E_INVALID, (k, v)
+    r.reconstruct(_rcfg(dict(normal_sigma=abi.SIGMA_MIN, depth_sigma=abi.SIGMA_MAX)))  # the bounds themselves are accepted
+    r.reconstruct(_rcfg(dict(normal_sigma=abi.SIGMA_MAX, depth_sigma=abi.SIGMA_MIN)))
     bad = _rcfg(None)
     bad._reserved[1] = 1
     with pytest.raises(lib.FovptError) as e:
