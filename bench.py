@@ -13,16 +13,20 @@ N > 1  : ONE frame is sharded by interleaved launch-index tiles over the ranks (
          transport, fovpt_comm_init / fovpt_gather_frame, what a C++ host uses).
 
 Prints ONE JSON line on rank 0 (contract in the task description) carrying `value` (frames back to back, two in flight) and
-`value_sync_per_frame` (one frame at a time, render() + synchronise: SURVEY 8(d)'s own definition of the metric), and
+`ms_per_step`.  A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print.  Everything else
+runs only with --full (each leg of it can still be skipped with its --no-* option):
+  frame_latency_ms, value_sync_per_frame (one frame at a time, render() + synchronise: SURVEY 8(d)'s own definition of the
+                metric), two_chains_per_frame
   roofline      dominant kernel k_traverse: algorithmic bytes / HIP-event time AS THE TIMED REGION RUNS (the contract's figure), `bound` =
                 what the evidence says binds (the CUs' L1 address / data path, with the node step's dependent chain on top: neither HBM
                 nor the vector ALU), flat keys `l1_frac` (texture-addresser busy time of a frame's loads / frame interval), `lane_use`,
                 `hbm_frac_measured`; `traffic`, `valu` and `l1_path` measured IN THIS RUN
                 by rocprofv3 --pmc child passes of this same script (or, failing that, imported from profiles/ and said so),
                 per-kernel times both overlapped (as the frame runs) and serialised (every kernel alone)
-  cpu_baseline  the CPU oracle timed on the host cores on the same frame (N = 1)
+  cpu_baseline  the CPU oracle timed on the host cores on the same frame, and parity_vs_oracle_rgba8_mismatch (N = 1)
   variants      the same measurement without the benchmark-shaped shortcuts: a non-constant HDR probe at frame
                 resolution, advancing subframe + moving camera and gaze, and 1 M / 3.8 M-triangle scenes (N = 1)
+  gather_mismatch_vs_single_gpu  (N > 1, FOVPT_BENCH_CHECK=1) the gathered frame against the unsharded one
 """
 import argparse
 import csv
@@ -211,10 +215,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: rocprofv3 counter passes, frame latency, two chains "
+                         "per frame, per-kernel times and the roofline, the CPU baseline and parity with the oracle, the variants, and "
+                         "(N > 1, FOVPT_BENCH_CHECK=1) the gathered frame against the unsharded one")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-counters", action="store_true", help="skip the rocprofv3 --pmc child passes (traffic / valu then come from profiles/, labelled imported)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the HDR-probe / moving-camera / 1 M / 3.8 M-triangle variants")
+    ap.add_argument("--no-counters", action="store_true", help="--full: skip the rocprofv3 --pmc child passes (traffic / valu then come from profiles/, labelled imported)")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the HDR-probe / moving-camera / 1 M / 3.8 M-triangle variants")
     ap.add_argument("--frames-in-flight", type=int, default=0, choices=(0, 1, 2),
                     help="fovpt_config.frames_in_flight for the timed region: 0 = the library's default (2), 1 = one frame at a time")
     ap.add_argument("--gather", choices=("packed", "reduce", "lib"), default="packed",
@@ -250,7 +258,7 @@ def main():
 
     # counters first, before this process touches the GPU (the passes are separate processes under the profiler)
     counters, counters_note = None, "not collected (N > 1 or --no-counters)"
-    if world == 1 and not args.no_counters:
+    if args.full and world == 1 and not args.no_counters:
         counters, counters_note = run_counter_passes()
 
     import numpy as np
@@ -370,7 +378,8 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    last_frame_host = frames[(step_no[0] - 1) % nbuf].cpu()      # rank 0: the gathered frame
+    # rank 0: the gathered frame, for --dump-outputs and the checks of --full
+    last_frame_host = frames[(step_no[0] - 1) % nbuf].cpu() if (args.dump_outputs or args.full) else None
     dumped = None
     if args.dump_outputs and rank == 0:
         # the last timed step's outputs, taken before anything below renders again
@@ -395,232 +404,239 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     mrays = rays_total / elapsed / 1e6
 
-    # ---- latency of ONE frame (render() + synchronise, nothing else in flight): the timed loop above keeps
-    # frames back to back, so the tail of frame k overlaps the head of frame k+1 (two state sets)
-    lat_frames = max(5, min(50, args.steps))
-    r.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(lat_frames):
-        r.launchParams.frame.subframe_index = 0
-        r.render_async()
-        r.synchronize()
-    frame_latency_ms = (time.perf_counter() - t0) / lat_frames * 1e3
-    # ... and the same two figures with fovpt_config.chains_per_frame = 2: every frame rendered as two independent chains over
-    # halves of its sample slots, frames issued one at a time -- the throughput of two frames in flight at the latency of one
-    two_chains = None
-    if world == 1:
-        cfg.chains_per_frame = 2
-        r.config = cfg
-        for _ in range(5):
-            r.launchParams.frame.subframe_index = 0
-            r.render_async()
+    timed_fif = cfg.frames_in_flight
+    lanes_env = os.environ.get("FOVPT_LANES")
+    lanes_avail = int(lanes_env) if lanes_env and lanes_env.isdigit() and 1 <= int(lanes_env) <= 4 else 2
+    fif_effective = min(timed_fif if timed_fif > 0 else lanes_avail, lanes_avail)
+
+    # everything below up to the result line runs only with --full: a plain run prints the headline and ends
+    full_keys = {}
+    if args.full:
+        # ---- latency of ONE frame (render() + synchronise, nothing else in flight): the timed loop above keeps
+        # frames back to back, so the tail of frame k overlaps the head of frame k+1 (two state sets)
+        lat_frames = max(5, min(50, args.steps))
         r.synchronize()
         t0 = time.perf_counter()
         for _ in range(lat_frames):
             r.launchParams.frame.subframe_index = 0
             r.render_async()
             r.synchronize()
-        lat2 = (time.perf_counter() - t0) / lat_frames * 1e3
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            r.launchParams.frame.subframe_index = 0
-            r.render_async()
-        r.synchronize()
-        two_chains = {"ms_per_step": round((time.perf_counter() - t0) / args.steps * 1e3, 4), "frame_latency_ms": round(lat2, 4),
-                      "note": "fovpt_config.chains_per_frame = 2 (never `value`): frames back to back / one frame alone"}
-        cfg.chains_per_frame = 0
-        r.config = cfg
+        frame_latency_ms = (time.perf_counter() - t0) / lat_frames * 1e3
+        # ... and the same two figures with fovpt_config.chains_per_frame = 2: every frame rendered as two independent chains over
+        # halves of its sample slots, frames issued one at a time -- the throughput of two frames in flight at the latency of one
+        two_chains = None
+        if world == 1:
+            cfg.chains_per_frame = 2
+            r.config = cfg
+            for _ in range(5):
+                r.launchParams.frame.subframe_index = 0
+                r.render_async()
+            r.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(lat_frames):
+                r.launchParams.frame.subframe_index = 0
+                r.render_async()
+                r.synchronize()
+            lat2 = (time.perf_counter() - t0) / lat_frames * 1e3
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                r.launchParams.frame.subframe_index = 0
+                r.render_async()
+            r.synchronize()
+            two_chains = {"ms_per_step": round((time.perf_counter() - t0) / args.steps * 1e3, 4), "frame_latency_ms": round(lat2, 4),
+                          "note": "fovpt_config.chains_per_frame = 2 (never `value`): frames back to back / one frame alone"}
+            cfg.chains_per_frame = 0
+            r.config = cfg
 
-    # ---- per-kernel device time, HIP events on the library's own streams around every kernel (fovpt_stats): once as the
-    # frame really runs (two streams, frames back to back: kernels overlap) and once with every kernel ALONE (profile 2)
-    prof_frames = max(5, min(50, args.steps))
-    per_frame_ms = {}
-    ps = None
-    timed_fif = cfg.frames_in_flight
-    for mode, fif, label in ((2, timed_fif, "serialised"), (1, 1, "one_frame_in_flight"), (1, timed_fif, "overlapped")):
-        cfg.profile = mode
-        cfg.frames_in_flight = fif
+        # ---- per-kernel device time, HIP events on the library's own streams around every kernel (fovpt_stats): once as the
+        # frame really runs (two streams, frames back to back: kernels overlap) and once with every kernel ALONE (profile 2)
+        prof_frames = max(5, min(50, args.steps))
+        per_frame_ms = {}
+        ps = None
+        for mode, fif, label in ((2, timed_fif, "serialised"), (1, 1, "one_frame_in_flight"), (1, timed_fif, "overlapped")):
+            cfg.profile = mode
+            cfg.frames_in_flight = fif
+            r.config = cfg
+            for _ in range(3):
+                r.launchParams.frame.subframe_index = 0
+                r.render_async()
+            r.synchronize()
+            r.reset_stats()
+            for _ in range(prof_frames):
+                r.launchParams.frame.subframe_index = 0
+                r.render_async()
+            r.synchronize()
+            ps = r.stats()
+            per_frame_ms[label] = {
+                "generate": round(ps.ms_generate / prof_frames, 5), "traverse_closest": round(ps.ms_trace / prof_frames, 5),
+                "traverse_occlusion": round(ps.ms_shadow / prof_frames, 5), "shade": round(ps.ms_shade / prof_frames, 5),
+                "resolve": round(ps.ms_resolve / prof_frames, 5)}
+        cfg.profile = 0
+        cfg.frames_in_flight = timed_fif
         r.config = cfg
-        for _ in range(3):
-            r.launchParams.frame.subframe_index = 0
-            r.render_async()
-        r.synchronize()
-        r.reset_stats()
-        for _ in range(prof_frames):
-            r.launchParams.frame.subframe_index = 0
-            r.render_async()
-        r.synchronize()
-        ps = r.stats()
-        per_frame_ms[label] = {
-            "generate": round(ps.ms_generate / prof_frames, 5), "traverse_closest": round(ps.ms_trace / prof_frames, 5),
-            "traverse_occlusion": round(ps.ms_shadow / prof_frames, 5), "shade": round(ps.ms_shade / prof_frames, 5),
-            "resolve": round(ps.ms_resolve / prof_frames, 5)}
-    cfg.profile = 0
-    cfg.frames_in_flight = timed_fif
-    r.config = cfg
-    # k_traverse is the one traversal kernel (4 lanes per ray): closest-hit launches run on the main
-    # stream (fovpt_stats books them under ms_trace), occlusion launches on the shadow stream
-    # (ms_shadow); rocprofv3 reports both under the one kernel name.  `ps` holds the overlapped run.
-    dom = "k_traverse"
-    ms_k = ps.ms_trace + ps.ms_shadow
-    n_launch = ps.n_trace_launches + ps.n_shadow_launches
-    n_rays = ps.radiance_rays + ps.shadow_rays
-    b_closest = algorithmic_bytes_per_ray(int(ps.num_triangles), "closest")
-    b_any = algorithmic_bytes_per_ray(int(ps.num_triangles), "any")
-    b_ray = (b_closest * ps.radiance_rays + b_any * ps.shadow_rays) / max(1, n_rays)
-    avg_ms = ms_k / max(1, n_launch)
-    bytes_per_launch = b_ray * (n_rays / max(1, n_launch))
-    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0             # as timed: two frames in flight
-    ser = per_frame_ms["serialised"]
-    one = per_frame_ms["one_frame_in_flight"]
-    launches_per_frame = n_launch / prof_frames
-    avg_ms_serialised = (ser["traverse_closest"] + ser["traverse_occlusion"]) / max(1e-9, launches_per_frame)
-    avg_ms_one = (one["traverse_closest"] + one["traverse_occlusion"]) / max(1e-9, launches_per_frame)
-    in_flight = ms_k / prof_frames / max(1e-9, ms_per_step)           # k_traverse launches running at once, on average
-    achieved_one = bytes_per_launch / (avg_ms_one * 1e-3) / 1e9 if avg_ms_one > 0 else 0.0  # one frame in flight: the line's `achieved`
+        # k_traverse is the one traversal kernel (4 lanes per ray): closest-hit launches run on the main
+        # stream (fovpt_stats books them under ms_trace), occlusion launches on the shadow stream
+        # (ms_shadow); rocprofv3 reports both under the one kernel name.  `ps` holds the overlapped run.
+        dom = "k_traverse"
+        ms_k = ps.ms_trace + ps.ms_shadow
+        n_launch = ps.n_trace_launches + ps.n_shadow_launches
+        n_rays = ps.radiance_rays + ps.shadow_rays
+        b_closest = algorithmic_bytes_per_ray(int(ps.num_triangles), "closest")
+        b_any = algorithmic_bytes_per_ray(int(ps.num_triangles), "any")
+        b_ray = (b_closest * ps.radiance_rays + b_any * ps.shadow_rays) / max(1, n_rays)
+        avg_ms = ms_k / max(1, n_launch)
+        bytes_per_launch = b_ray * (n_rays / max(1, n_launch))
+        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0             # as timed: two frames in flight
+        ser = per_frame_ms["serialised"]
+        one = per_frame_ms["one_frame_in_flight"]
+        launches_per_frame = n_launch / prof_frames
+        avg_ms_serialised = (ser["traverse_closest"] + ser["traverse_occlusion"]) / max(1e-9, launches_per_frame)
+        avg_ms_one = (one["traverse_closest"] + one["traverse_occlusion"]) / max(1e-9, launches_per_frame)
+        in_flight = ms_k / prof_frames / max(1e-9, ms_per_step)           # k_traverse launches running at once, on average
+        achieved_one = bytes_per_launch / (avg_ms_one * 1e-3) / 1e9 if avg_ms_one > 0 else 0.0  # one frame in flight: the line's `achieved`
 
-    # counters: measured in this run, else imported from the committed profile (and labelled so)
-    traffic, traffic_source, valu = None, counters_note, None
-    if counters and dom in counters:
-        c = counters[dom]
-        # units and gfx950 correction as MI355X_MICROARCH.md (HBM) prescribes: FETCH_SIZE / WRITE_SIZE in KiB, FETCH_SIZE
-        # tallies 128-B requests at 64 B -> doubled; WRITE_SIZE is exact for wide stores
-        if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
-            traffic = 2.0 * c["FETCH_SIZE"] * 1024.0 + c["WRITE_SIZE"] * 1024.0
-        tot_inst = sum(counters[k].get("SQ_INSTS_VALU", 0.0) * counters[k].get("launches_seen", 0) for k in counters)
-        frames_seen = max(1.0, counters.get("k_resolve", {}).get("launches_seen", 3))
-        if "SQ_INSTS_VALU" in c:
-            lane = c["SQ_THREAD_CYCLES_VALU"] / (64.0 * c["SQ_ACTIVE_INST_VALU"]) if c.get("SQ_ACTIVE_INST_VALU") else None
-            issue_ms = c["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / (SIMDS * CLOCK_HZ) * 1e3
-            valu = {
-                "SQ_INSTS_VALU_per_launch": round(c["SQ_INSTS_VALU"]), "lane_use": round(lane, 4) if lane else None,
-                "issue_time_ms_per_launch": round(issue_ms, 5),
-                "issue_frac_of_serialised_launch": round(issue_ms / max(1e-9, c.get("dur_us", 0.0) / 1e3), 4) if c.get("dur_us") else None,
-                "serialised_launch_ms_under_profiler": round(c.get("dur_us", 0.0) / 1e3, 5),
-                "SQ_INSTS_VALU_per_frame_all_kernels": round(tot_inst / frames_seen),
-                "issue_time_ms_per_frame_all_kernels": round(tot_inst / frames_seen * VALU_CYCLES_PER_INST / (SIMDS * CLOCK_HZ) * 1e3, 4),
-                "issue_time_ms_per_frame_at_the_measured_rate": round(tot_inst / frames_seen / (SIMDS * VALU_MEASURED_INST_PER_NS_PER_SIMD) * 1e-6, 4),
-                "issue_rate_note": "one wave64 instruction per SIMD per 2 cycles (spec) / 0.98 per ns (measured, tools/micro/valu_rate.hip)",
-                "per_kernel_lane_use": {k: round(v["SQ_THREAD_CYCLES_VALU"] / (64.0 * v["SQ_ACTIVE_INST_VALU"]), 4)
-                                        for k, v in counters.items() if v.get("SQ_ACTIVE_INST_VALU")},
+        # counters: measured in this run, else imported from the committed profile (and labelled so)
+        traffic, traffic_source, valu = None, counters_note, None
+        if counters and dom in counters:
+            c = counters[dom]
+            # units and gfx950 correction as MI355X_MICROARCH.md (HBM) prescribes: FETCH_SIZE / WRITE_SIZE in KiB, FETCH_SIZE
+            # tallies 128-B requests at 64 B -> doubled; WRITE_SIZE is exact for wide stores
+            if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
+                traffic = 2.0 * c["FETCH_SIZE"] * 1024.0 + c["WRITE_SIZE"] * 1024.0
+            tot_inst = sum(counters[k].get("SQ_INSTS_VALU", 0.0) * counters[k].get("launches_seen", 0) for k in counters)
+            frames_seen = max(1.0, counters.get("k_resolve", {}).get("launches_seen", 3))
+            if "SQ_INSTS_VALU" in c:
+                lane = c["SQ_THREAD_CYCLES_VALU"] / (64.0 * c["SQ_ACTIVE_INST_VALU"]) if c.get("SQ_ACTIVE_INST_VALU") else None
+                issue_ms = c["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / (SIMDS * CLOCK_HZ) * 1e3
+                valu = {
+                    "SQ_INSTS_VALU_per_launch": round(c["SQ_INSTS_VALU"]), "lane_use": round(lane, 4) if lane else None,
+                    "issue_time_ms_per_launch": round(issue_ms, 5),
+                    "issue_frac_of_serialised_launch": round(issue_ms / max(1e-9, c.get("dur_us", 0.0) / 1e3), 4) if c.get("dur_us") else None,
+                    "serialised_launch_ms_under_profiler": round(c.get("dur_us", 0.0) / 1e3, 5),
+                    "SQ_INSTS_VALU_per_frame_all_kernels": round(tot_inst / frames_seen),
+                    "issue_time_ms_per_frame_all_kernels": round(tot_inst / frames_seen * VALU_CYCLES_PER_INST / (SIMDS * CLOCK_HZ) * 1e3, 4),
+                    "issue_time_ms_per_frame_at_the_measured_rate": round(tot_inst / frames_seen / (SIMDS * VALU_MEASURED_INST_PER_NS_PER_SIMD) * 1e-6, 4),
+                    "issue_rate_note": "one wave64 instruction per SIMD per 2 cycles (spec) / 0.98 per ns (measured, tools/micro/valu_rate.hip)",
+                    "per_kernel_lane_use": {k: round(v["SQ_THREAD_CYCLES_VALU"] / (64.0 * v["SQ_ACTIVE_INST_VALU"]), 4)
+                                            for k, v in counters.items() if v.get("SQ_ACTIVE_INST_VALU")},
+                }
+        # The CU's address / data path (texture addresser, 64 bytes per clock): what the closest-hit launches' occupancy law has as
+        # its constant term (profiles/r03c_step_probes.txt).  TA cycles per wave-level load instruction and the
+        # load instructions per launch are measured in this run when the counter passes ran.
+        l1_path = None
+        dev_props = torch.cuda.get_device_properties(local_rank)
+        cus = int(getattr(dev_props, "multi_processor_count", CUS) or CUS)                       # 256 on MI355X: from the device, not assumed
+        clock_hz = float(getattr(dev_props, "clock_rate", 0) or 0) * 1e3 or CLOCK_HZ            # the device's engine clock (kHz -> Hz), else 2.4 GHz
+        l1_frac = None
+        if counters and dom in counters and counters[dom].get("TA_FLAT_READ_WAVEFRONTS_sum"):
+            c = counters[dom]
+            per_inst = c["TA_TA_BUSY_sum"] / c["TA_FLAT_READ_WAVEFRONTS_sum"]
+            ta_ms = c["TA_TA_BUSY_sum"] / cus / clock_hz * 1e3
+            frames_seen = max(1.0, counters.get("k_resolve", {}).get("launches_seen", 3))
+            tot_busy = sum(counters[k].get("TA_TA_BUSY_sum", 0.0) * counters[k].get("launches_seen", 0) for k in counters
+                           if k in ("k_generate", "k_traverse", "k_shade", "k_resolve"))
+            l1_path = {
+                "load_instructions_per_launch": round(c.get("SQ_INSTS_VMEM_RD", c["TA_FLAT_READ_WAVEFRONTS_sum"])),
+                "ta_cycles_per_load_instruction": round(per_inst, 2),
+                "ta_time_ms_per_launch": round(ta_ms, 5),
+                "ta_share_of_serialised_launch": round(ta_ms / max(1e-9, c.get("dur_us", 0.0) / 1e3), 4) if c.get("dur_us") else None,
+                "ta_time_ms_per_frame_all_kernels": round(tot_busy / frames_seen / cus / clock_hz * 1e3, 4),
+                "ta_share_of_the_frame_interval": round(tot_busy / frames_seen / cus / clock_hz * 1e3 / ms_per_step, 4),
+                "cus": cus, "clock_ghz": round(clock_hz / 1e9, 3),
+                "note": "TA_TA_BUSY / (the device's CU count) at the device's engine clock (a lower bound on the time: under this load the shader clock "
+                        "runs ~8 % below it); a 128-byte "
+                        "node is two 16-byte loads per lane = 2 x ~17 cycles of the CU's 64-byte-per-clock address path per wave step.  "
+                        "`ta_share_of_the_frame_interval` is the roof this design runs against: the address paths' time for ALL of a frame's "
+                        "loads over the frame interval of the timed region",
             }
-    # The CU's address / data path (texture addresser, 64 bytes per clock): what the closest-hit launches' occupancy law has as
-    # its constant term (profiles/r03c_step_probes.txt).  TA cycles per wave-level load instruction and the
-    # load instructions per launch are measured in this run when the counter passes ran.
-    l1_path = None
-    dev_props = torch.cuda.get_device_properties(local_rank)
-    cus = int(getattr(dev_props, "multi_processor_count", CUS) or CUS)                       # 256 on MI355X: from the device, not assumed
-    clock_hz = float(getattr(dev_props, "clock_rate", 0) or 0) * 1e3 or CLOCK_HZ            # the device's engine clock (kHz -> Hz), else 2.4 GHz
-    l1_frac = None
-    if counters and dom in counters and counters[dom].get("TA_FLAT_READ_WAVEFRONTS_sum"):
-        c = counters[dom]
-        per_inst = c["TA_TA_BUSY_sum"] / c["TA_FLAT_READ_WAVEFRONTS_sum"]
-        ta_ms = c["TA_TA_BUSY_sum"] / cus / clock_hz * 1e3
-        frames_seen = max(1.0, counters.get("k_resolve", {}).get("launches_seen", 3))
-        tot_busy = sum(counters[k].get("TA_TA_BUSY_sum", 0.0) * counters[k].get("launches_seen", 0) for k in counters
-                       if k in ("k_generate", "k_traverse", "k_shade", "k_resolve"))
-        l1_path = {
-            "load_instructions_per_launch": round(c.get("SQ_INSTS_VMEM_RD", c["TA_FLAT_READ_WAVEFRONTS_sum"])),
-            "ta_cycles_per_load_instruction": round(per_inst, 2),
-            "ta_time_ms_per_launch": round(ta_ms, 5),
-            "ta_share_of_serialised_launch": round(ta_ms / max(1e-9, c.get("dur_us", 0.0) / 1e3), 4) if c.get("dur_us") else None,
-            "ta_time_ms_per_frame_all_kernels": round(tot_busy / frames_seen / cus / clock_hz * 1e3, 4),
-            "ta_share_of_the_frame_interval": round(tot_busy / frames_seen / cus / clock_hz * 1e3 / ms_per_step, 4),
-            "cus": cus, "clock_ghz": round(clock_hz / 1e9, 3),
-            "note": "TA_TA_BUSY / (the device's CU count) at the device's engine clock (a lower bound on the time: under this load the shader clock "
-                    "runs ~8 % below it); a 128-byte "
-                    "node is two 16-byte loads per lane = 2 x ~17 cycles of the CU's 64-byte-per-clock address path per wave step.  "
-                    "`ta_share_of_the_frame_interval` is the roof this design runs against: the address paths' time for ALL of a frame's "
-                    "loads over the frame interval of the timed region",
-        }
-        l1_frac = l1_path["ta_share_of_the_frame_interval"]
-    if traffic is None:
-        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            l1_frac = l1_path["ta_share_of_the_frame_interval"]
+        if traffic is None:
+            pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            try:
+                with open(pmc_path) as f:
+                    traffic = json.load(f).get(dom, {}).get("hbm_bytes_per_launch")
+                traffic_source = "IMPORTED from profiles/pmc_traffic.json (not measured in this run: %s)" % counters_note
+            except Exception:
+                traffic_source = "unavailable: %s" % counters_note
+        # Latency model of the dominant kernel: what a launch should take if a wave's life is its chain of
+        # steps -- steps per wave x measured cycles per step (s_memtime stamps in a sample of the waves of a diagnostic build,
+        # profiles/r03_step_cycles.txt) -- and the launch lasts (wave life) / (wave slots busy over the launch) (every wave's
+        # start and end, profiles/r03_wave_timeline_c3.txt).  The step anatomy is IMPORTED from those committed profiles
+        # (tools/step_model.py); the launch times beside it are measured in this run.
+        latency_model = None
         try:
-            with open(pmc_path) as f:
-                traffic = json.load(f).get(dom, {}).get("hbm_bytes_per_launch")
-            traffic_source = "IMPORTED from profiles/pmc_traffic.json (not measured in this run: %s)" % counters_note
-        except Exception:
-            traffic_source = "unavailable: %s" % counters_note
-    # Latency model of the dominant kernel: what a launch should take if a wave's life is its chain of
-    # steps -- steps per wave x measured cycles per step (s_memtime stamps in a sample of the waves of a diagnostic build,
-    # profiles/r03_step_cycles.txt) -- and the launch lasts (wave life) / (wave slots busy over the launch) (every wave's
-    # start and end, profiles/r03_wave_timeline_c3.txt).  The step anatomy is IMPORTED from those committed profiles
-    # (tools/step_model.py); the launch times beside it are measured in this run.
-    latency_model = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "r03_step_model.json")) as f:
-            sm = json.load(f)["launches"]
-        c1 = sm["closest_1"]
-        model_closest = sum(sm[k]["model"]["launch_us"] for k in sm if k.startswith("closest") and "model" in sm[k]) / 1e3
-        model_anyhit = sum(sm[k]["model"]["launch_us"] for k in sm if k.startswith("any-hit") and "model" in sm[k]) / 1e3
-        latency_model = {
-            "node_step_cycles": c1["node_step_cycles"], "leaf_step_cycles": c1["leaf_step_cycles"],
-            "load_wait_share_of_node_step": c1["model"]["load_wait_share_of_node_step"],
-            "node_steps_per_wave_per_launch": {k: sm[k]["node_steps_per_wave"] for k in sorted(sm) if "node_steps_per_wave" in sm[k]},
-            "wave_slots_busy_over_a_launch": {k: sm[k]["unstamped"]["wave_slots_busy"] for k in sorted(sm) if "unstamped" in sm[k]},
-            "model_ms_per_frame": {"traverse_closest": round(model_closest, 4), "traverse_occlusion": round(model_anyhit, 4)},
-            "measured_ms_per_frame_serialised": {"traverse_closest": ser["traverse_closest"], "traverse_occlusion": ser["traverse_occlusion"]},
-            "reading": "a node step of a wave (16 rays in lockstep) is ~1000 cycles, ~62 % of it the wait for the two 16-byte node loads of "
-                       "its slowest quad, 16 % box test + rank, 8 % LDS push / pop, 14 % loop; a closest-hit launch is three one-wave "
-                       "workgroups per wave slot, started by the dispatcher as slots fall free, and lasts (waves per slot) x (a wave's "
-                       "life) / (share of the launch the slots are busy)",
-            "source": "IMPORTED from profiles/r03_step_model.json (step anatomy, steps per wave, busy share: diagnostic builds of ROUND 3's "
-                      "kernels -- the step anatomy still holds, the steps per wave are 12-40 % fewer since round 4's reinsertion and vote); "
-                      "measured_ms_per_frame_serialised from this run",
+            with open(os.path.join(ROOT, "profiles", "r03_step_model.json")) as f:
+                sm = json.load(f)["launches"]
+            c1 = sm["closest_1"]
+            model_closest = sum(sm[k]["model"]["launch_us"] for k in sm if k.startswith("closest") and "model" in sm[k]) / 1e3
+            model_anyhit = sum(sm[k]["model"]["launch_us"] for k in sm if k.startswith("any-hit") and "model" in sm[k]) / 1e3
+            latency_model = {
+                "node_step_cycles": c1["node_step_cycles"], "leaf_step_cycles": c1["leaf_step_cycles"],
+                "load_wait_share_of_node_step": c1["model"]["load_wait_share_of_node_step"],
+                "node_steps_per_wave_per_launch": {k: sm[k]["node_steps_per_wave"] for k in sorted(sm) if "node_steps_per_wave" in sm[k]},
+                "wave_slots_busy_over_a_launch": {k: sm[k]["unstamped"]["wave_slots_busy"] for k in sorted(sm) if "unstamped" in sm[k]},
+                "model_ms_per_frame": {"traverse_closest": round(model_closest, 4), "traverse_occlusion": round(model_anyhit, 4)},
+                "measured_ms_per_frame_serialised": {"traverse_closest": ser["traverse_closest"], "traverse_occlusion": ser["traverse_occlusion"]},
+                "reading": "a node step of a wave (16 rays in lockstep) is ~1000 cycles, ~62 % of it the wait for the two 16-byte node loads of "
+                           "its slowest quad, 16 % box test + rank, 8 % LDS push / pop, 14 % loop; a closest-hit launch is three one-wave "
+                           "workgroups per wave slot, started by the dispatcher as slots fall free, and lasts (waves per slot) x (a wave's "
+                           "life) / (share of the launch the slots are busy)",
+                "source": "IMPORTED from profiles/r03_step_model.json (step anatomy, steps per wave, busy share: diagnostic builds of ROUND 3's "
+                          "kernels -- the step anatomy still holds, the steps per wave are 12-40 % fewer since round 4's reinsertion and vote); "
+                          "measured_ms_per_frame_serialised from this run",
+            }
+        except Exception as e:                                      # the line is still valid without the model
+            latency_model = {"unavailable": "%s: %s" % (type(e).__name__, e)}
+        roofline = {
+            # flat keys first (the driver's parser keeps these): what binds the kernel, how close it is to THAT roof, and the two
+            # figures that say why the contract's roofs do not bind
+            "bound": "l1_address_path",
+            "l1_frac": l1_frac,                                       # TA busy time of all of a frame's loads / frame interval (measured in this run, else null)
+            "lane_use": (valu or {}).get("lane_use"),                 # k_traverse: active lanes per issued vector instruction
+            "hbm_frac_measured": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if (traffic and avg_ms > 0) else None,
+            "bound_note": "neither of the contract's roofs binds k_traverse: HBM traffic is a sixth of the algorithmic bytes (the scene stays in "
+                          "L2 / Infinity Cache).  A node step sits at the knee of the CU's own address / data path (`l1_path`: ~17 texture-addresser "
+                          "cycles per wave-level load, two per node step; a third costs +19 %, one fewer returns nothing) and is paced by its "
+                          "dependent chain (load -> box test -> stack -> pop -> load) at the hardware's 8 waves per SIMD -- closest-hit time = "
+                          "0.32 + 1.53 / (waves per SIMD) ms per frame -- with the vector ALUs about half busy (`valu`: half-empty waves, 16 "
+                          "rays in lockstep, since round 4 with a vote on when a node phase ends).  DESIGN.md section 4 and EXPERIMENTS.md (round 3) have the "
+                          "occupancy sweep and the three probes; `achieved`/`peak`/`frac` are the contract's algorithmic-bytes figure against the 8 TB/s HBM roof",
+            # the contract's figure, for the configuration `value` is timed in: algorithmic bytes per launch / the launch's
+            # HIP-event duration as the timed region runs (frames_in_flight as in `config`)
+            "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+            "avg_launch_ms": round(avg_ms, 5), "avg_launch_ms_serialised": round(avg_ms_serialised, 5),
+            "frac_serialised": round(bytes_per_launch / (avg_ms_serialised * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if avg_ms_serialised > 0 else None,
+            "avg_launch_ms_one_frame_in_flight": round(avg_ms_one, 5),
+            "frac_one_frame_in_flight": round(achieved_one / HBM_PEAK_GBS, 5),
+            "launches_in_flight": round(in_flight, 3),
+            "frac_aggregate": round(bytes_per_launch * launches_per_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+            "frac_note": "`achieved` / `frac` divide one launch's algorithmic bytes by its HIP-event duration AS THE TIMED REGION RUNS (with two "
+                         "frames in flight the traversal launches of two frames share the chip -- `launches_in_flight` at any time -- so each "
+                         "lasts longer although more gets done per second; how much longer depends on how the two chains interleave, and the "
+                         "figure has come out as 0.36-0.38 or 0.46-0.47 at the same frame interval).  `frac_one_frame_in_flight` is the same with "
+                         "one frame in flight (rounds 1-3's `frac`, stable), `frac_serialised` the kernel alone on the chip, `frac_aggregate` all "
+                         "traversal bytes of a frame over the frame interval of the timed region",
+            "launches_per_frame": launches_per_frame,
+            "rays_per_launch": n_rays / max(1, n_launch), "algorithmic_bytes_per_ray": round(b_ray, 1),
+            "per_frame_ms": per_frame_ms["overlapped"], "per_frame_ms_serialised": per_frame_ms["serialised"],
+            "per_frame_ms_one_frame_in_flight": per_frame_ms["one_frame_in_flight"],
+            "valu": valu,
+            "l1_path": l1_path,
+            "latency_model": latency_model,
         }
-    except Exception as e:                                      # the line is still valid without the model
-        latency_model = {"unavailable": "%s: %s" % (type(e).__name__, e)}
-    lanes_env = os.environ.get("FOVPT_LANES")
-    lanes_avail = int(lanes_env) if lanes_env and lanes_env.isdigit() and 1 <= int(lanes_env) <= 4 else 2
-    fif_effective = min(timed_fif if timed_fif > 0 else lanes_avail, lanes_avail)
-    roofline = {
-        # flat keys first (the driver's parser keeps these): what binds the kernel, how close it is to THAT roof, and the two
-        # figures that say why the contract's roofs do not bind
-        "bound": "l1_address_path",
-        "l1_frac": l1_frac,                                       # TA busy time of all of a frame's loads / frame interval (measured in this run, else null)
-        "lane_use": (valu or {}).get("lane_use"),                 # k_traverse: active lanes per issued vector instruction
-        "hbm_frac_measured": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if (traffic and avg_ms > 0) else None,
-        "bound_note": "neither of the contract's roofs binds k_traverse: HBM traffic is a sixth of the algorithmic bytes (the scene stays in "
-                      "L2 / Infinity Cache).  A node step sits at the knee of the CU's own address / data path (`l1_path`: ~17 texture-addresser "
-                      "cycles per wave-level load, two per node step; a third costs +19 %, one fewer returns nothing) and is paced by its "
-                      "dependent chain (load -> box test -> stack -> pop -> load) at the hardware's 8 waves per SIMD -- closest-hit time = "
-                      "0.32 + 1.53 / (waves per SIMD) ms per frame -- with the vector ALUs about half busy (`valu`: half-empty waves, 16 "
-                      "rays in lockstep, since round 4 with a vote on when a node phase ends).  DESIGN.md section 4 and EXPERIMENTS.md (round 3) have the "
-                      "occupancy sweep and the three probes; `achieved`/`peak`/`frac` are the contract's algorithmic-bytes figure against the 8 TB/s HBM roof",
-        # the contract's figure, for the configuration `value` is timed in: algorithmic bytes per launch / the launch's
-        # HIP-event duration as the timed region runs (frames_in_flight as in `config`)
-        "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-        "avg_launch_ms": round(avg_ms, 5), "avg_launch_ms_serialised": round(avg_ms_serialised, 5),
-        "frac_serialised": round(bytes_per_launch / (avg_ms_serialised * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if avg_ms_serialised > 0 else None,
-        "avg_launch_ms_one_frame_in_flight": round(avg_ms_one, 5),
-        "frac_one_frame_in_flight": round(achieved_one / HBM_PEAK_GBS, 5),
-        "launches_in_flight": round(in_flight, 3),
-        "frac_aggregate": round(bytes_per_launch * launches_per_frame / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-        "frac_note": "`achieved` / `frac` divide one launch's algorithmic bytes by its HIP-event duration AS THE TIMED REGION RUNS (with two "
-                     "frames in flight the traversal launches of two frames share the chip -- `launches_in_flight` at any time -- so each "
-                     "lasts longer although more gets done per second; how much longer depends on how the two chains interleave, and the "
-                     "figure has come out as 0.36-0.38 or 0.46-0.47 at the same frame interval).  `frac_one_frame_in_flight` is the same with "
-                     "one frame in flight (rounds 1-3's `frac`, stable), `frac_serialised` the kernel alone on the chip, `frac_aggregate` all "
-                     "traversal bytes of a frame over the frame interval of the timed region",
-        "launches_per_frame": launches_per_frame,
-        "rays_per_launch": n_rays / max(1, n_launch), "algorithmic_bytes_per_ray": round(b_ray, 1),
-        "per_frame_ms": per_frame_ms["overlapped"], "per_frame_ms_serialised": per_frame_ms["serialised"],
-        "per_frame_ms_one_frame_in_flight": per_frame_ms["one_frame_in_flight"],
-        "valu": valu,
-        "l1_path": l1_path,
-        "latency_model": latency_model,
-    }
+        full_keys = {
+            "frame_latency_ms": round(frame_latency_ms, 4),
+            # SURVEY 8(d)'s own definition of the metric -- wall time of render() INCLUDING its final synchronisation, one frame at a
+            # time as the reference's main loop runs -- beside the pipelined `value`
+            "value_sync_per_frame": round(rays_total / args.steps / (frame_latency_ms * 1e-3) / 1e6, 2) if world == 1 else None,
+            "two_chains_per_frame": two_chains,
+        }
 
     out = {
         "metric": "Mray/s", "value": round(mrays, 2), "unit": "Mray/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "frame_latency_ms": round(frame_latency_ms, 4),
-        # SURVEY 8(d)'s own definition of the metric -- wall time of render() INCLUDING its final synchronisation, one frame at a
-        # time as the reference's main loop runs -- beside the pipelined `value`
-        "value_sync_per_frame": round(rays_total / args.steps / (frame_latency_ms * 1e-3) / 1e6, 2) if world == 1 else None,
-        "two_chains_per_frame": two_chains,
+        **full_keys,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {
@@ -635,13 +651,14 @@ def main():
             "frames_in_flight": fif_effective,
             "gather": gather_mode,
         },
-        "roofline": roofline,
     }
+    if args.full:
+        out["roofline"] = roofline
     if dumped:
         out["dumped_outputs"] = dumped
 
     # ---- CPU baseline: the oracle (a scalar C++ port of the path) on the host cores, rank 0, N=1
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle_py as orc
         orc.build()
         orc.set_math_mode(True)
@@ -682,7 +699,7 @@ def main():
         if not args.advance_subframe:                        # (with advancing seeds the last timed frame is not frame 0)
             out["parity_vs_oracle_rgba8_mismatch"] = int((gpu_px != F.frame).sum())
 
-    if world > 1 and rank == 0 and os.environ.get("FOVPT_BENCH_CHECK") == "1":
+    if args.full and world > 1 and rank == 0 and os.environ.get("FOVPT_BENCH_CHECK") == "1":
         # the gathered frame on rank 0 must be the unsharded frame, bit for bit
         gathered = last_frame_host
         c1 = cfg.copy()
@@ -696,7 +713,7 @@ def main():
     r.close()
 
     # ---- variants without the benchmark-shaped shortcuts (N = 1): extra keys, never `value`
-    if world == 1 and not args.no_variants:
+    if args.full and world == 1 and not args.no_variants:
         variants = {}
         vf = max(10, min(40, args.steps))
         # (a) a seeded NON-constant HDR probe at frame resolution: every probe lookup goes to its own row (33 MB of texels,

@@ -224,7 +224,7 @@ def test_frames_in_flight_do_not_change_the_frames(accumulate):
 def test_bench_two_rank_rehearsal_gathers_the_full_frame():
     """bench.py's N > 1 path end to end on ONE GPU: two ranks share device 0 and talk over gloo
     (FOVPT_BENCH_REHEARSAL; RCCL refuses two ranks per device).  Rank 0's gathered frame must equal the
-    unsharded frame bit for bit."""
+    unsharded frame bit for bit (a check of `bench.py --full`)."""
     import json
     import os
     import subprocess
@@ -238,7 +238,7 @@ def test_bench_two_rank_rehearsal_gathers_the_full_frame():
     sock.close()
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "6", "--warmup", "2"], capture_output=True, text=True, env=env, timeout=600)
+                          "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)

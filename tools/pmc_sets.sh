@@ -24,7 +24,7 @@ NAMES="$@"
 for S in $NAMES; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/pmcset_${TAG}_$S
   mkdir -p $OUT
-  timeout -k 10 150 rocprofv3 --pmc ${SETS[$S]} --kernel-trace --output-format csv -d $OUT -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-counters --no-variants > $OUT/stdout.log 2>&1 \
+  timeout -k 10 150 rocprofv3 --pmc ${SETS[$S]} --kernel-trace --output-format csv -d $OUT -o p -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-counters --no-variants > $OUT/stdout.log 2>&1 \
     || { echo "set $S FAILED"; grep -m2 "exceeds the capabilities\|rror" $OUT/stdout.log; tail -3 $OUT/stdout.log; exit 1; }
   python3 - > gpurun_out/pmcset_${TAG}_$S.txt <<PY
 import csv, re, collections
