@@ -217,6 +217,27 @@ class GBufferPtrs(C.Structure):
     ]
 
 
+TEMPORAL_MAX_HISTORY = 64                      # FOVPT_TEMPORAL_MAX_HISTORY
+
+
+class TemporalConfig(C.Structure):
+    """fovpt_temporal_config: history caps per foveation level and the reprojection tolerances (defaults: fovpt_temporal_defaults)."""
+    _fields_ = [
+        ("history_fovea", C.c_int32), ("history_middle", C.c_int32), ("history_periphery", C.c_int32),
+        ("history_uniform", C.c_int32),
+        ("normal_tolerance", C.c_float), ("depth_tolerance", C.c_float),
+        ("_reserved", C.c_int32 * 2),
+    ]
+
+    def copy(self):
+        m = TemporalConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(TemporalConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
@@ -240,6 +261,7 @@ assert C.sizeof(Probe) == 64
 assert C.sizeof(LaunchParams) == 248
 assert C.sizeof(DenoiseConfig) == 32
 assert C.sizeof(ReconstructConfig) == 32 and C.sizeof(GBufferPtrs) == 40
+assert C.sizeof(TemporalConfig) == 32
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

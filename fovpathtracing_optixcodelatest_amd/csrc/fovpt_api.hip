@@ -125,6 +125,14 @@ struct fovpt_ctx {
     // fovpt_gbuffer / fovpt_reconstruct: the G-buffer's own ray queue, hit records, counters and outputs (never a render state
     // set: a frame in flight may be using those), and the context's own reconstruction outputs; all allocated on first use
     DevBuf gb_o, gb_d, gb_hit, gb_cnt, gb_prim, gb_pos, gb_nrm, gb_alb, rc_color, rc_rgba;
+    // fovpt_temporal: two G-buffer sets and two histories (rgb, n), used in turn by consecutive calls (tp_last: the set the
+    // last call wrote), the previous step's camera and size, and the context's own outputs; all allocated on first use.
+    // tp_valid: a previous step exists (dropped by fovpt_temporal_reset, fovpt_resize and fovpt_set_scene)
+    DevBuf tp_prim[2], tp_pos[2], tp_nrm[2], tp_alb[2], tp_hist[2], tp_color, tp_rgba;
+    int tp_last = 0;
+    bool tp_valid = false;
+    int tp_w = 0, tp_h = 0;
+    float tp_eye[3] = {}, tp_U[3] = {}, tp_V[3] = {}, tp_W[3] = {};
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -657,10 +665,47 @@ int reserve_gbuffer(fovpt_ctx* c, size_t n)
     return FOVPT_OK;
 }
 
+// fovpt_temporal's G-buffer sets, histories and outputs for n pixels
+int reserve_temporal(fovpt_ctx* c, size_t n)
+{
+    for (int k = 0; k < 2; k++) {
+        HIPCHK(c, c->tp_prim[k].reserve(n * 4)); HIPCHK(c, c->tp_pos[k].reserve(n * 16)); HIPCHK(c, c->tp_nrm[k].reserve(n * 16));
+        HIPCHK(c, c->tp_alb[k].reserve(n * 16)); HIPCHK(c, c->tp_hist[k].reserve(n * 16));
+    }
+    HIPCHK(c, c->tp_color.reserve(n * 16)); HIPCHK(c, c->tp_rgba.reserve(n * 4));
+    return FOVPT_OK;
+}
+
+GBufferDev temporal_set(fovpt_ctx* c, int k)
+{
+    GBufferDev g;
+    g.prim = (uint32_t*)c->tp_prim[k].p; g.pos = (float4*)c->tp_pos[k].p; g.nrm = (float4*)c->tp_nrm[k].p; g.alb = (float4*)c->tp_alb[k].p;
+    return g;
+}
+
+// The rows of [U V W]^-1 (U, V, W the columns), in binary64: det = U . (V x W), rows (V x W) / det, (W x U) / det,
+// (U x V) / det, each entry rounded to binary32.  false: det is 0 or not finite.
+bool camera_inverse(const float* U, const float* V, const float* W, float* inv)
+{
+    auto cross = [](const double* a, const double* b, double* r) {
+        r[0] = a[1] * b[2] - a[2] * b[1]; r[1] = a[2] * b[0] - a[0] * b[2]; r[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    const double u[3] = {U[0], U[1], U[2]}, v[3] = {V[0], V[1], V[2]}, w[3] = {W[0], W[1], W[2]};
+    double r[3][3];
+    cross(v, w, r[0]); cross(w, u, r[1]); cross(u, v, r[2]);
+    const double det = (u[0] * r[0][0] + u[1] * r[0][1]) + u[2] * r[0][2];
+    if (det == 0.0 || !std::isfinite(det)) return false;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) inv[3 * i + j] = (float)(r[i][j] / det);
+    return true;
+}
+
 // Enqueues the G-buffer of lp's frame.size seen by view's camera (view.eye / U / V / W) on fovpt_stream(): one ray per pixel,
 // traced by the production closest-hit k_traverse (so a ray gets the (prim, t, u, v) fovpt_debug_trace returns for it), then
-// the per-pixel outputs.
-int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who)
+// the per-pixel outputs: into target's buffers (frame.size entries each), or with target null into the ones fovpt_gbuffer
+// hands out.  The ray queue, hit records and counters are shared: every use is ordered on the same stream.
+int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
+                    const GBufferDev* target = nullptr)
 {
     if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene (traversable %llu, current %llu)", who,
                                                                      (unsigned long long)lp->traversable, (unsigned long long)c->scene_id);
@@ -685,7 +730,8 @@ int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev&
     ShadowQueue sq;
     memset(&sq, 0, sizeof(sq));
     Counters* cnt = (Counters*)c->gb_cnt.p;
-    g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = (float4*)c->gb_nrm.p; g.alb = (float4*)c->gb_alb.p;
+    if (target) g = *target;
+    else { g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = (float4*)c->gb_nrm.p; g.alb = (float4*)c->gb_alb.p; }
     hipStream_t st = c->shadow_stream;
     fovpt_launch_gbuffer_rays(st, fd, q, cnt);
     fovpt_launch_traverse(st, scene_view(c), ps, q, sq, (uint32_t)n, cnt, 0, -1, c->grid_trace);   // shard 0 holds all n rays
@@ -787,8 +833,10 @@ void fovpt_destroy(fovpt_ctx* c)
                       &c->fb_frame, &c->fb_accum, &c->fb_color, &c->fb_normal, &c->fb_albedo, &c->accum_before,
                       &c->plan_owner, &c->plan_blocks, &c->plan_total, &c->plan_base, &c->plan_idx,
                       &c->comm_packed, &c->comm_gathered, &c->dn_level, &c->dn_i0, &c->dn_i1, &c->dn_color, &c->dn_rgba,
-                      &c->gb_o, &c->gb_d, &c->gb_hit, &c->gb_cnt, &c->gb_prim, &c->gb_pos, &c->gb_nrm, &c->gb_alb, &c->rc_color, &c->rc_rgba};
+                      &c->gb_o, &c->gb_d, &c->gb_hit, &c->gb_cnt, &c->gb_prim, &c->gb_pos, &c->gb_nrm, &c->gb_alb, &c->rc_color, &c->rc_rgba,
+                      &c->tp_color, &c->tp_rgba};
     for (DevBuf* b : bufs) b->release();
+    for (int k = 0; k < 2; k++) { c->tp_prim[k].release(); c->tp_pos[k].release(); c->tp_nrm[k].release(); c->tp_alb[k].release(); c->tp_hist[k].release(); }
     for (int l = 0; l < FOVPT_MAX_LANES; l++) {
         if (c->lane_main[l] && c->lane_main[l] != c->stream) (void)hipStreamDestroy(c->lane_main[l]);
         if (c->lane_shadow[l] && c->lane_shadow[l] != c->shadow_stream) (void)hipStreamDestroy(c->lane_shadow[l]);
@@ -808,6 +856,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc_ = sync_all(c); if (rc_) return rc_; }
     free_scene(c);
+    c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
     uint64_t ntri = 0;
     bool any_tc = false;
     for (int m = 0; m < num_meshes; m++) {
@@ -1041,6 +1090,8 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->dn_color.p) { HIPCHK(c, c->dn_color.reserve(n * 16)); HIPCHK(c, c->dn_rgba.reserve(n * 4)); }   // fovpt_denoise's own outputs follow the frame
     if (c->gb_prim.p) { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }                   // so do the G-buffer's
     if (c->rc_color.p) { HIPCHK(c, c->rc_color.reserve(n * 16)); HIPCHK(c, c->rc_rgba.reserve(n * 4)); }   // and fovpt_reconstruct's
+    if (c->tp_hist[0].p) { const int rc_ = reserve_temporal(c, n); if (rc_) return rc_; }               // and fovpt_temporal's
+    c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
     out->color_buffer = (fovpt_float4*)c->fb_color.p; out->normal_buffer = (fovpt_float4*)c->fb_normal.p;
@@ -1102,6 +1153,14 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
 #define FOVPT_RECONSTRUCT_SUPPORT 2.0f
 #define FOVPT_RECONSTRUCT_NORMAL_SIGMA 0.5f
 #define FOVPT_RECONSTRUCT_DEPTH_SIGMA 0.05f
+
+// fovpt_temporal_defaults (chosen by measurement: DESIGN.md, section 12)
+#define FOVPT_TEMPORAL_HISTORY_FOVEA 1
+#define FOVPT_TEMPORAL_HISTORY_MIDDLE 4
+#define FOVPT_TEMPORAL_HISTORY_PERIPHERY 8
+#define FOVPT_TEMPORAL_HISTORY_UNIFORM 4
+#define FOVPT_TEMPORAL_NORMAL_TOLERANCE 0.1f
+#define FOVPT_TEMPORAL_DEPTH_TOLERANCE 0.02f
 
 // edge-stopping scales of fovpt_denoise_defaults (chosen by measurement: DESIGN.md, denoiser)
 #define FOVPT_DENOISE_COLOR_SIGMA 8.0f
@@ -1269,6 +1328,94 @@ int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_r
     a.levels = rc->levels; a.remodulate = rc->remodulate;
     fovpt_launch_reconstruct(c->shadow_stream, fd, a, in, lp->frame.albedo_buffer, g, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- temporal reprojection of the frame history (temporal.hip; its definition: tests/temporal_ref.py) ------------------
+int fovpt_temporal_defaults(fovpt_temporal_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->history_fovea = FOVPT_TEMPORAL_HISTORY_FOVEA;
+    out->history_middle = FOVPT_TEMPORAL_HISTORY_MIDDLE;
+    out->history_periphery = FOVPT_TEMPORAL_HISTORY_PERIPHERY;
+    out->history_uniform = FOVPT_TEMPORAL_HISTORY_UNIFORM;
+    out->normal_tolerance = FOVPT_TEMPORAL_NORMAL_TOLERANCE;
+    out->depth_tolerance = FOVPT_TEMPORAL_DEPTH_TOLERANCE;
+    return FOVPT_OK;
+}
+
+int fovpt_temporal_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba, const fovpt_float4** history)
+{
+    if (!c || !color || !rgba || !history) return FOVPT_E_INVALID;
+    if (!c->tp_hist[0].p) {
+        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal_buffers: no frame rendered yet");
+        HIPCHK(c, hipSetDevice(c->device));
+        const int rc_ = reserve_temporal(c, (size_t)c->dn_w * (size_t)c->dn_h);
+        if (rc_) return rc_;
+    }
+    *color = (fovpt_float4*)c->tp_color.p;
+    *rgba = (uint32_t*)c->tp_rgba.p;
+    *history = (const fovpt_float4*)c->tp_hist[c->tp_last].p;
+    return FOVPT_OK;
+}
+
+int fovpt_temporal_reset(fovpt_ctx* c)
+{
+    if (!c) return FOVPT_E_INVALID;
+    c->tp_valid = false;
+    return FOVPT_OK;
+}
+
+// Enqueued on fovpt_stream() like fovpt_reconstruct, and ordered like it.  Traces the rendered frame's G-buffer into the set
+// the last call did not write, reprojects the other set's history into it, and makes it the last written.
+int fovpt_temporal(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
+                   fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null argument");
+    const int32_t caps[4] = {tc->history_fovea, tc->history_middle, tc->history_periphery, tc->history_uniform};
+    for (int32_t v : caps)
+        if (v < 1 || v > FOVPT_TEMPORAL_MAX_HISTORY) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: history cap %d outside 1 .. %d", v, FOVPT_TEMPORAL_MAX_HISTORY);
+    if (!(tc->normal_tolerance >= 0.0f && tc->normal_tolerance <= 4.0f))
+        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: normal_tolerance %g outside [0, 4]", (double)tc->normal_tolerance);
+    if (!(tc->depth_tolerance >= 0.0f && tc->depth_tolerance <= 1.0f))
+        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: depth_tolerance %g outside [0, 1]", (double)tc->depth_tolerance);
+    for (int32_t r : tc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: reserved fields must be 0");
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_temporal without a scene");
+    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal: no frame rendered yet");
+    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: a tile shard (world = %d) has no neighbours to reproject from", c->dn_world);
+    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
+        return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null accum_buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    { const int rc_ = reserve_temporal(c, npix); if (rc_) return rc_; }
+    if (!out_color) out_color = (fovpt_float4*)c->tp_color.p;
+    if (!out_rgba) out_rgba = (uint32_t*)c->tp_rgba.p;
+    if ((void*)out_color == c->tp_hist[0].p || (void*)out_color == c->tp_hist[1].p)
+        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: the output colour buffer is the context's history");
+    const int cur = c->tp_last ^ 1, prev = c->tp_last;
+    const GBufferDev g = temporal_set(c, cur), gp = temporal_set(c, prev);
+    GBufferDev gt;
+    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, gt, "fovpt_temporal", &g); if (rc_) return rc_; }   // the rendered frame's camera
+    const FrameDev& fd = c->dn_frame;
+    TemporalArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 4; k++) a.cap[k] = caps[k];
+    a.normal_tol = tc->normal_tolerance; a.depth_tol = tc->depth_tolerance;
+    a.uniform = c->dn_uniform != 0;
+    a.reproject = c->tp_valid && c->tp_w == c->dn_w && c->tp_h == c->dn_h && camera_inverse(c->tp_U, c->tp_V, c->tp_W, a.inv);
+    memcpy(a.eye_prev, c->tp_eye, sizeof(a.eye_prev));
+    fovpt_launch_temporal(c->shadow_stream, fd, a, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    c->tp_last = cur;                                                      // this step is the next one's previous step
+    c->tp_valid = true;
+    c->tp_w = c->dn_w; c->tp_h = c->dn_h;
+    memcpy(c->tp_eye, fd.eye, sizeof(c->tp_eye)); memcpy(c->tp_U, fd.U, sizeof(c->tp_U));
+    memcpy(c->tp_V, fd.V, sizeof(c->tp_V)); memcpy(c->tp_W, fd.W, sizeof(c->tp_W));
     return FOVPT_OK;
 }
 

@@ -273,6 +273,16 @@ struct ReconstructArgs {
 };
 void fovpt_launch_reconstruct(hipStream_t st, const FrameDev& fd, const ReconstructArgs& a, const fovpt_float4* in, const fovpt_float4* albedo,
                               GBufferDev g, fovpt_float4* out_color, uint32_t* out_rgba);
+struct TemporalArgs {
+    float inv[9];                       // rows of the previous camera's inverse [U V W]^-1 (binary64 on the host, rounded to fp32)
+    float eye_prev[3];                  // the previous camera's eye
+    int32_t cap[4];                     // history caps: fill 1, fill 2, fill 4, FOV_OFF
+    float normal_tol, depth_tol;        // |N_q - N_p|^2 <= normal_tol; |N_p . (X_q - X_p)| <= depth_tol * t_p
+    int32_t reproject;                  // 0: no pixel reprojects (no previous step, or a singular previous camera)
+    int32_t uniform;                    // the frame was rendered FOV_OFF
+};
+void fovpt_launch_temporal(hipStream_t st, const FrameDev& fd, const TemporalArgs& a, const fovpt_float4* in, GBufferDev g, GBufferDev gp,
+                           const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba);
 void fovpt_launch_build_guide(hipStream_t st, const float* cdf, int n, int segments, uint32_t* guide);
 void fovpt_launch_probe_records(hipStream_t st, size_t n, const float* cdfX, const float* pdfX, const float4* data, float4* rec);
 void fovpt_launch_build_cdf(hipStream_t st, int w, int h, const float4* data, float* pdfX, float* cdfX, float* pdfY, float* cdfY, float* row_total);

@@ -300,6 +300,50 @@ class SampleRenderer:
         out = np.empty((f.size.y, f.size.x, 4), np.float32)
         return self.download(self.reconstruct_buffers()[0], out)
 
+    # -- temporal reprojection of the frame history (include/fovpt.h, fovpt_temporal)
+    @staticmethod
+    def temporal_defaults() -> abi.TemporalConfig:
+        d = abi.TemporalConfig()
+        lib.check(None, lib.load().fovpt_temporal_defaults(C.byref(d)))
+        return d
+
+    def temporal(self, cfg=None, in_color=None, out_color=None, out_rgba=None):
+        """One step of the renderer's frame history on the frame last rendered.  in_color: device pointer of a float4 frame
+        (None: the accum buffer; e.g. reconstruct_buffers()[0]).  out_color / out_rgba: device pointers (out_color may be
+        in_color), or None for the renderer's own buffers (downloadTemporalColor / downloadTemporalPixels).  Enqueued on the
+        renderer's stream, not synchronised (the downloads synchronise)."""
+        cfg = cfg if cfg is not None else self.temporal_defaults()
+        self._check(self._L.fovpt_temporal(self._ctx, C.byref(self.launchParams), C.byref(cfg), in_color, out_color, out_rgba))
+
+    def temporal_buffers(self):
+        """Device addresses of the renderer's own temporal outputs and of the history the last step wrote: (float4 colour,
+        rgba8, float4 history (rgb, history length))."""
+        col, rgba, hist = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_temporal_buffers(self._ctx, C.byref(col), C.byref(rgba), C.byref(hist)))
+        return col.value, rgba.value, hist.value
+
+    def temporal_reset(self):
+        """Drops the frame history: the next temporal() step outputs its input."""
+        self._check(self._L.fovpt_temporal_reset(self._ctx))
+
+    def downloadTemporalPixels(self):
+        """The rgba8 output of the last temporal step into the renderer's own buffer, shaped like downloadPixels()."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x), np.uint32)
+        return self.download(self.temporal_buffers()[1], out)
+
+    def downloadTemporalColor(self):
+        """The float4 output of the last temporal step into the renderer's own buffer."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x, 4), np.float32)
+        return self.download(self.temporal_buffers()[0], out)
+
+    def downloadTemporalHistory(self):
+        """The history the last temporal step wrote: (H, W, 4) float32, rgb its output colour, w the history length."""
+        f = self.launchParams.frame
+        out = np.empty((f.size.y, f.size.x, 4), np.float32)
+        return self.download(self.temporal_buffers()[2], out)
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

@@ -134,6 +134,26 @@ public:
         check(fovpt_reconstruct_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- temporal reprojection (new with this library): one step of the renderer's frame history on the frame just rendered
+    // (include/fovpt.h, fovpt_temporal) into the renderer's own buffers, then a device sync like render().  in_color: nullptr =
+    // the accum buffer, or e.g. the reconstruction's colour output (fovpt_reconstruct_buffers)
+    void temporal(const fovpt_float4* in_color = nullptr) { fovpt_temporal_config tc; check(fovpt_temporal_defaults(&tc)); temporal(tc, in_color); }
+    void temporal(const fovpt_temporal_config& tc, const fovpt_float4* in_color = nullptr)
+    {
+        check(fovpt_temporal(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &tc, in_color, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // drops the history (a caller that changes the lighting calls it: setProbe keeps the history)
+    void temporal_reset() { check(fovpt_temporal_reset(ctx)); }
+    // the temporal step's rgba8 pixels, like downloadPixels
+    void downloadTemporalPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        const fovpt_float4* history = nullptr;
+        check(fovpt_temporal_buffers(ctx, &color, &rgba, &history));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

@@ -365,6 +365,62 @@ int fovpt_reconstruct(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt
                       fovpt_float4* out_color, uint32_t* out_rgba);
 int fovpt_reconstruct_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 
+/* ---- temporal reprojection of the frame history ----------------------------------------------------------------------
+ * New with this library (the reference family's only temporal mechanism is accumulate = 1, correct for a static camera
+ * alone).  Carries a per-pixel history from one rendered frame to the next while the camera and gaze move: each pixel's
+ * primary hit (a miss: its ray direction) is projected into the previous step's camera, the previous history is read there
+ * with bilinear weights over the taps whose previous G-buffer agrees with the pixel's, and blended with the new frame as a
+ * running mean of at most `cap` frames, cap chosen by the pixel's foveation level.  No clamp to the current neighbourhood:
+ * with one sample per 4 x 4 block it is noise; the caps bound ghosting instead.  Only + - * / min floor and comparisons:
+ * the result is defined bit for bit (tests/temporal_ref.py restates it in numpy float32).
+ *   fovpt_temporal           one step of the context's history, on the frame last issued with fovpt_render(ctx, lp) as it
+ *                            was rendered (its passes, gaze and camera, not lp's or the config's now).  Traces that frame's
+ *                            G-buffer (as fovpt_gbuffer, into buffers of its own: fovpt_gbuffer's keep their contents), then
+ *                            per pixel p with hit point X_p, t_p, normal N_p:
+ *                              cap N      history_periphery / _middle / _fovea by the fill (4 / 2 / 1) of the pixel's last
+ *                                         writer, history_uniform on a FOV_OFF frame, 1 where no pass writes
+ *                              project    v = X_p - eye_prev (a miss: dx U + dy V + W, its ray before normalising);
+ *                                         a = inverse(U_prev V_prev W_prev) v (inverse in binary64, entries rounded to fp32);
+ *                                         a.z > 0, px = ((a.x / a.z + 1) * 0.5) * w - 0.5 in [-1, w), py likewise
+ *                              taps       the 4 bilinear taps around (px, py) in the frame, of p's class (both misses or both
+ *                                         hits) and, for hits, |N_q - N_p|^2 <= normal_tolerance and
+ *                                         |N_p . (X_q - X_p)| <= depth_tolerance * t_p on the previous G-buffer
+ *                              history    sum w >= 1/64: H = sum w H_q / sum w, n_h = sum w n_q / sum w; else n_h = 0
+ *                              blend      n = min(n_h + 1, N); n == 1: out = in_color bit for bit; else
+ *                                         out = H + (1 / n) (in - H), alpha 1
+ *                            and the new history (out, n).  in_color NULL = accum_buffer (typically fovpt_reconstruct's or
+ *                            fovpt_denoise's colour output otherwise); out_color may equal in_color (a pixel reads only
+ *                            itself of the input).  out_color float4, out_rgba rgba8 (the resolve's tone map of out_color),
+ *                            device pointers of frame.size; either may be NULL = the context's own buffers.  Enqueued on
+ *                            fovpt_stream(), not synchronised, ordered like fovpt_denoise.  The first step, and the first
+ *                            after fovpt_temporal_reset, fovpt_resize or fovpt_set_scene, has no history: out = in_color,
+ *                            n = 1.  fovpt_set_probe keeps the history: a caller that changes the lighting calls
+ *                            fovpt_temporal_reset.  FOVPT_E_INVALID: null ctx / lp / tc, a value out of range (NaN
+ *                            included), non-zero reserved fields, a frame rendered with world > 1, out_color equal to the
+ *                            context's history; FOVPT_E_NO_SCENE: no scene (or lp->traversable is not the current one);
+ *                            FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size differs.
+ *   fovpt_temporal_buffers   addresses of the context's own outputs and of the history the last call wrote (rgb = its
+ *                            output colour, w = n); allocated for the last frame if not yet.
+ *   fovpt_temporal_reset     drops the history: the next call starts a new one.
+ * Defaults chosen by measurement: on a 12-frame camera path they cut the periphery's RMSE against a
+ * 256-spp render 1.95x over fovpt_reconstruct alone, the middle ring's 1.42x, and leave the fovea as it is.  On an MI355X a
+ * call takes 0.29 ms at 1920 x 1080, of which 0.09 ms is the reprojection and the rest its G-buffer.                      */
+#define FOVPT_TEMPORAL_MAX_HISTORY 64
+typedef struct fovpt_temporal_config {
+    int32_t history_fovea;         /* cap on the history length of pixels last written by pass F (fill 1), 1 .. MAX; 1      */
+    int32_t history_middle;        /* ... pass M (fill 2); default 4                                                          */
+    int32_t history_periphery;     /* ... pass P (fill 4); default 8                                                          */
+    int32_t history_uniform;       /* FOV_OFF frames; default 4                                                               */
+    float normal_tolerance;        /* |N_q - N_p|^2 <= this keeps a tap, 0 .. 4; default 0.1                                  */
+    float depth_tolerance;         /* |N_p . (X_q - X_p)| <= this * t_p keeps a tap, 0 .. 1; default 0.02                     */
+    int32_t _reserved[2];          /* 0 */
+} fovpt_temporal_config;
+int fovpt_temporal_defaults(fovpt_temporal_config* out);
+int fovpt_temporal(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
+                   fovpt_float4* out_color, uint32_t* out_rgba);
+int fovpt_temporal_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba, const fovpt_float4** history);
+int fovpt_temporal_reset(fovpt_ctx* ctx);
+
 /* ---- multi-GPU: packed gather of the final framebuffer ----------------------------------
  * New with this library: the reference is single-GPU (SimplePathtracer.cpp:331-340).  With
  * fovpt_config.rank/world every handle renders the launch-index tiles it owns -- interleaved
@@ -502,6 +558,7 @@ static_assert(sizeof(fovpt_launch_params) == 248, "LaunchParams ABI");
 static_assert(sizeof(fovpt_denoise_config) == 32, "denoise config ABI");
 static_assert(sizeof(fovpt_reconstruct_config) == 32, "reconstruct config ABI");
 static_assert(sizeof(fovpt_gbuffer_ptrs) == 40, "gbuffer ABI");
+static_assert(sizeof(fovpt_temporal_config) == 32, "temporal config ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

@@ -1,0 +1,402 @@
+"""fovpt_temporal on the GPU: bit for bit against tests/temporal_ref.py on the GPU's own inputs over moving cameras and gazes,
+the reset paths, disocclusion judged by the production traversal, inputs and later frames left untouched, ordering with frames
+in flight, error codes, the gain in accuracy over single frames, the full C3 size and the C++ drop-in."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import reconstruct_ref as rr
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+
+from common import cfg_foveated, cfg_uniform, make_gpu
+from postprocess_common import BOX_CAMERA, bits, box_model
+from temporal_common import Checker, camera, quality_run, tcfg
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
+# periphery RMSE against a 256-spp render over the last frame of a 12-frame camera path, 384 x 216 atrium, radii 30 / 90,
+# spp (1, 2, 8), render -> reconstruct -> temporal with the defaults vs render -> reconstruct (tools/temporal_perf.py --sweep,
+# DESIGN.md 12): measured 1.95 on an MI355X; the test keeps a margin below it
+QUALITY_MIN_GAIN = 1.6
+ALL_CAPS = dict(history_fovea=3, history_middle=5, history_periphery=8, history_uniform=6, normal_tolerance=0.3, depth_tolerance=0.05)
+CAM = scenes.ATRIUM_CAMERA
+
+
+def _atrium(size, cfg, gaze=None, tris=8000):
+    cfg.write_guides = 1
+    return make_gpu(scenes.atrium(tris), scenes.ambient_probe(96, 54, 2.5), CAM, size, cfg, gaze=gaze)
+
+
+def _view(r, k, size):
+    """Frame k of a moving path: the eye slides and the look-at point turns; frame 4 is an asymmetric setCameraFov frustum."""
+    if k == 4:
+        fwd = np.array(CAM["lookat"], np.float64) - np.array(CAM["eye"], np.float64)
+        r.setCameraFov(tuple(np.array(CAM["eye"]) + (30.0, 5.0, 20.0)), fwd, CAM["up"], -0.85, 0.70, 0.62, -0.55)
+        return
+    eye = (CAM["eye"][0] + 25.0 * k, CAM["eye"][1] + 4.0 * k, CAM["eye"][2] + 15.0 * k)
+    look = (CAM["lookat"][0], CAM["lookat"][1] + 10.0 * k, CAM["lookat"][2] - 40.0 * k)
+    r.setCamera(renderer.Camera(eye, look, CAM["up"], CAM["fovy"], size[0] / float(size[1])))
+
+
+def _sequence(oracle, r, size, d, frames=7, pipeline="accum", in_place=False):
+    ck = Checker(oracle, r, d)
+    f = r.launchParams.frame
+    ns = []
+    for k in range(frames):
+        _view(r, k, size)
+        f.c.x, f.c.y = size[0] // 2 + 7 * k - 20, size[1] // 2 + 3 * k - 9
+        r.render()
+        inp, in_ptr, out = None, None, None
+        if pipeline in ("reconstruct", "denoise"):
+            if pipeline == "denoise":
+                r.denoise()
+                r.reconstruct(None, r.denoise_buffers()[0])
+            else:
+                r.reconstruct()
+            inp, in_ptr = r.downloadReconstructedColor(), r.reconstruct_buffers()[0]
+            if in_place:                                    # in_color == out_color
+                out = (in_ptr, r.temporal_buffers()[1])
+        _, h, cap = ck.step(inp, in_ptr, out)
+        ns.append(h[..., 3])
+    return ns, cap
+
+
+@pytest.mark.parametrize("d", [None, ALL_CAPS], ids=["defaults", "all_caps"])
+def test_temporal_matches_the_restatement_moving(oracle, d):
+    size = (193, 109)
+    r = _atrium(size, cfg_foveated(15, 48, (1, 2, 8)))
+    ns, cap = _sequence(oracle, r, size, d)
+    assert (ns[0] == 1).all()
+    assert (ns[-1] > 1).mean() > 0.5 and ns[-1].max() > 2                       # (history was carried)
+    r.close()
+
+
+def test_temporal_matches_the_restatement_fov_off(oracle):
+    size = (160, 90)
+    r = _atrium(size, cfg_uniform(1))
+    ns, cap = _sequence(oracle, r, size, ALL_CAPS, frames=6)
+    assert (cap == ALL_CAPS["history_uniform"]).all() and (ns[-1] > 1).mean() > 0.5
+    r.close()
+
+
+@pytest.mark.parametrize("pipeline, in_place", [("reconstruct", False), ("reconstruct", True), ("denoise", False)])
+def test_temporal_after_reconstruct(oracle, pipeline, in_place):
+    size = (192, 108)
+    r = _atrium(size, cfg_foveated(15, 48, (1, 2, 8)))
+    _sequence(oracle, r, size, None, frames=6, pipeline=pipeline, in_place=in_place)
+    r.close()
+
+
+def _scene_again(r):
+    from fovpathtracing_optixcodelatest_amd.renderer import pack_model
+    md, n, td, nt, keep = pack_model(r.model)
+    trav = C.c_uint64()
+    r._check(r._L.fovpt_set_scene(r._ctx, C.cast(md, C.c_void_p), n, C.cast(td, C.c_void_p), nt, C.byref(trav)))
+    r.launchParams.traversable = trav.value
+
+
+def test_temporal_reset_paths(oracle):
+    """The first step, and the step after fovpt_temporal_reset, fovpt_resize and fovpt_set_scene: out == in, n == 1."""
+    size = (160, 96)
+    r = _atrium(size, cfg_foveated(12, 36, (1, 2, 4)))
+    ck = Checker(oracle, r, ALL_CAPS)
+
+    def fresh(label):
+        r.render()
+        acc = r.downloadAccum()
+        c, h, _ = ck.step()
+        assert np.array_equal(bits(c), bits(acc)), label
+        assert (h[..., 3] == 1).all(), label
+
+    def carried():
+        r.render()
+        _, h, _ = ck.step()
+        assert (h[..., 3] > 1).mean() > 0.5
+
+    fresh("first")
+    carried()
+    r.temporal_reset()
+    ck.reset()
+    fresh("reset")
+    carried()
+    r.resize((144, 80))
+    r.setCamera(renderer.Camera(CAM["eye"], CAM["lookat"], CAM["up"], CAM["fovy"], 144 / 80.0))
+    ck.reset()
+    fresh("resize")
+    carried()
+    _scene_again(r)
+    ck.reset()
+    fresh("set_scene")
+    carried()
+    r.setProbe(renderer.ProbeData(scenes.ambient_probe(96, 54, 1.5)).BuildCDF())   # keeps the history
+    carried()
+    r.close()
+
+
+def test_temporal_disocclusion_against_the_traversal(oracle):
+    """The slab and box with the camera moving sideways: slab points hidden from the previous eye get n == 1, slab points away
+    from the box visible from both eyes get n == 2 on the second step.  Occlusion is decided with the production traversal
+    from eye_prev towards X_p, not by the restatement."""
+    size = (192, 120)
+    cfg = cfg_foveated(12, 36, (1, 2, 4))
+    cfg.write_guides = 1
+    r = make_gpu(box_model(), scenes.ambient_probe(64, 32, 2.5), BOX_CAMERA, size, cfg)
+    d = dict(history_fovea=2, history_middle=2, history_periphery=2, history_uniform=2)
+    ck = Checker(oracle, r, d)
+    r.render()
+    ck.step()
+    pg, prev_cam = ck.prev["gb"], ck.prev["cam"]
+    eye_prev = np.array(prev_cam["eye"], np.float64)
+    eye = (BOX_CAMERA["eye"][0] - 1.2, BOX_CAMERA["eye"][1], BOX_CAMERA["eye"][2] + 1.2)
+    r.setCamera(renderer.Camera(eye, BOX_CAMERA["lookat"], BOX_CAMERA["up"], BOX_CAMERA["fovy"], size[0] / float(size[1])))
+    r.render()
+    _, h, _ = ck.step()
+    gb = ck.prev["gb"]
+    slab_prims = len(r.model.meshes[0].index)
+    prim = gb["prim"]
+    slab = (prim != rr.MISS) & (prim < slab_prims)
+    X = gb["position"][..., :3].astype(np.float64)
+    v = X - eye_prev
+    dist = np.linalg.norm(v, axis=-1)
+    sel = np.flatnonzero(slab.reshape(-1))
+    dirs = (v.reshape(-1, 3)[sel] / dist.reshape(-1)[sel, None]).astype(np.float32)
+    orig = np.broadcast_to(eye_prev.astype(np.float32), dirs.shape)
+    hp, tuv, _ = r.debug_trace(orig, dirs)
+    t = tuv[:, 0].astype(np.float64)
+    dd = dist.reshape(-1)[sel]
+    occluded = np.zeros(prim.size, bool)
+    visible = np.zeros(prim.size, bool)
+    occluded[sel] = (hp != rr.MISS) & (t < dd * (1 - 1e-3))
+    visible[sel] = (hp == rr.MISS) | (t > dd * (1 - 1e-4))
+    occluded, visible = occluded.reshape(prim.shape), visible.reshape(prim.shape)
+
+    def near_edge(g):
+        """2 px from a silhouette or crease: a change of object (sky, slab, box) or face (normal) in g's view."""
+        p = g["prim"]
+        n = np.round(g["normal"][..., :3] * 2).astype(np.int64) + 2
+        cls = np.where(p == rr.MISS, 0, 1 + (p >= slab_prims) * 1000 + n[..., 0] * 25 + n[..., 1] * 5 + n[..., 2])
+        e = np.zeros(p.shape, bool)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                e |= np.roll(np.roll(cls, dy, 0), dx, 1) != cls
+        e[:2], e[-2:], e[:, :2], e[:, -2:] = True, True, True, True
+        return e
+
+    # where the point lies in the previous view, in float64: away from the previous view's silhouettes too
+    A = np.stack([np.array(prev_cam[k], np.float64) for k in ("U", "V", "W")], axis=1)
+    a = np.linalg.solve(A, v.reshape(-1, 3).T).T.reshape(prim.shape + (3,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        qx = np.round((a[..., 0] / a[..., 2] + 1) * 0.5 * size[0] - 0.5)
+        qy = np.round((a[..., 1] / a[..., 2] + 1) * 0.5 * size[1] - 0.5)
+    inside = (a[..., 2] > 0) & (qx >= 0) & (qx < size[0]) & (qy >= 0) & (qy < size[1])
+    qx, qy = np.where(inside, qx, 0).astype(np.int64), np.where(inside, qy, 0).astype(np.int64)
+    away = ~near_edge(gb) & inside & ~near_edge(pg)[qy, qx]
+    hidden, seen = occluded & away, visible & away
+    assert hidden.sum() > 50 and seen.sum() > 1000
+    assert (h[hidden][:, 3] == 1).all()
+    assert (h[seen][:, 3] == 2).all()
+    r.close()
+
+
+def test_temporal_leaves_its_inputs_and_the_next_frames_alone():
+    cfg = cfg_foveated(15, 48, (1, 2, 8))
+    size = (192, 108)
+    frames = []
+    for with_calls in (False, True):
+        r = _atrium(size, cfg)
+        f = r.launchParams.frame
+        shape = (f.size.y, f.size.x, 4)
+        seq = []
+        for k in range(4):
+            _view(r, k, size)
+            f.c.x, f.c.y = 60 + 30 * k, 50 + 5 * k
+            r.render()
+            bufs = [r.downloadAccum(), r.downloadPixels()] + [r.download(p, np.empty(shape, np.float32))
+                                                              for p in (f.color_buffer, f.normal_buffer, f.albedo_buffer)]
+            if with_calls:
+                r.reconstruct()
+                rc = r.downloadReconstructedColor()
+                g2 = r.gbuffer()
+                gb = r.downloadGBuffer(g2)
+                r.temporal(None, r.reconstruct_buffers()[0])
+                r.temporal()
+                after = [r.downloadAccum(), r.downloadPixels()] + [r.download(p, np.empty(shape, np.float32))
+                                                                   for p in (f.color_buffer, f.normal_buffer, f.albedo_buffer)]
+                for a, b in zip(bufs, after):
+                    assert np.array_equal(bits(a), bits(b))
+                assert np.array_equal(bits(r.downloadReconstructedColor()), bits(rc))
+                gb_after = r.downloadGBuffer(g2)                                  # fovpt_gbuffer's buffers keep their contents
+                for key in gb:
+                    assert np.array_equal(bits(gb[key]), bits(gb_after[key])), key
+            seq.append(bufs)
+        s = r.stats()
+        seq.append([s.radiance_rays, s.shadow_rays, s.paths, s.frames])
+        frames.append(seq)
+        r.close()
+    for a, b in zip(frames[0][:-1], frames[1][:-1]):
+        for x, y in zip(a, b):
+            assert np.array_equal(bits(x), bits(y))
+    assert frames[0][-1] == frames[1][-1]
+
+
+def test_temporal_errors():
+    cfg = cfg_foveated(15, 48, (1, 2, 8))
+    r = _atrium((96, 64), cfg)
+    with pytest.raises(lib.FovptError) as e:             # nothing rendered yet
+        r.temporal()
+    assert e.value.code == E_NO_FRAME
+    r.render()
+    r.temporal()
+    M = abi.TEMPORAL_MAX_HISTORY
+    caps = ("history_fovea", "history_middle", "history_periphery", "history_uniform")
+    bad = tuple((k, v) for k in caps for v in (0, -1, M + 1)) + tuple(
+        (k, v) for k in ("normal_tolerance", "depth_tolerance") for v in (-1e-7, float("nan"), float("inf"), -float("inf"))) + (
+        ("normal_tolerance", float(np.nextafter(np.float32(4), np.float32(5)))), ("depth_tolerance", float(np.nextafter(np.float32(1), np.float32(2)))))
+    for k, v in bad:
+        with pytest.raises(lib.FovptError) as e:
+            r.temporal(tcfg({k: v}))
+        assert e.value.code == E_INVALID, (k, v)
+    for d in (dict(zip(caps, (1, 1, 1, 1)), normal_tolerance=0.0, depth_tolerance=0.0),   # the bounds themselves are accepted
+              dict(zip(caps, (M, M, M, M)), normal_tolerance=4.0, depth_tolerance=1.0)):
+        r.temporal(tcfg(d))
+    for i in range(2):
+        c = tcfg(None)
+        c._reserved[i] = 1
+        with pytest.raises(lib.FovptError) as e:
+            r.temporal(c)
+        assert e.value.code == E_INVALID
+    hist = r.temporal_buffers()[2]
+    with pytest.raises(lib.FovptError) as e:             # writing the history it reads
+        r.temporal(None, None, hist, None)
+    assert e.value.code == E_INVALID
+    f = r.launchParams.frame
+    f.size.x -= 4
+    with pytest.raises(lib.FovptError) as e:
+        r.temporal()
+    assert e.value.code == E_NO_FRAME
+    f.size.x += 4
+    trav = r.launchParams.traversable
+    r.launchParams.traversable = 12345
+    with pytest.raises(lib.FovptError) as e:
+        r.temporal()
+    assert e.value.code == E_NO_SCENE
+    r.launchParams.traversable = trav
+    L = lib.load()
+    d = tcfg(None)
+    assert L.fovpt_temporal(r._ctx, None, C.byref(d), None, None, None) == E_INVALID
+    assert L.fovpt_temporal(r._ctx, C.byref(r.launchParams), None, None, None, None) == E_INVALID
+    p = C.c_void_p()
+    assert L.fovpt_temporal_buffers(r._ctx, None, C.byref(p), C.byref(p)) == E_INVALID
+    c = r.config
+    c.world, c.rank = 2, 0
+    r.config = c
+    r.render()
+    with pytest.raises(lib.FovptError) as e:
+        r.temporal()
+    assert e.value.code == E_INVALID
+    r.close()
+    r2 = _atrium((64, 48), cfg_foveated(10, 20))
+    with pytest.raises(lib.FovptError) as e:
+        r2.temporal_buffers()
+    assert e.value.code == E_NO_FRAME
+    r2.close()
+
+
+@pytest.mark.parametrize("mode", ["frames_in_flight", "chains_per_frame"])
+def test_temporal_is_ordered_with_frames_in_flight(mode):
+    """Four frames with a moving gaze and camera, issued back to back with a temporal step after each into caller buffers, give
+    what the same frames rendered one at a time with a synchronise after each give."""
+    import torch
+    size = (384, 216)
+    cfg = cfg_foveated(20, 60, (4, 8, 16))               # >= 16384 sample slots: chains_per_frame = 2 does split the frame
+    if mode == "frames_in_flight":
+        cfg.frames_in_flight = 2
+    else:
+        cfg.chains_per_frame = 2
+    r = _atrium(size, cfg)
+    views = [((120 + 40 * k, 90 + 15 * k), k) for k in range(4)]
+
+    def setup(g, k):
+        r.launchParams.frame.c.x, r.launchParams.frame.c.y = g
+        r.launchParams.frame.subframe_index = 0
+        _view(r, k, size)
+
+    d = tcfg(ALL_CAPS)
+    # the pixels no pass writes keep the previous frame's values: the synchronous frames get the same history (last, then all)
+    want = []
+    for g, k in views[-1:] + views:
+        setup(g, k)
+        r.render()
+        r.synchronize()
+        if len(want) == 0:
+            want.append(None)
+            continue
+        r.temporal(d)
+        r.synchronize()
+        want.append((r.downloadTemporalColor(), r.downloadTemporalPixels(), r.downloadTemporalHistory()))
+    want = want[1:]
+    outs = [(torch.empty((size[1], size[0], 4), dtype=torch.float32, device="cuda"),
+             torch.empty((size[1], size[0]), dtype=torch.int32, device="cuda")) for _ in views]
+    torch.cuda.synchronize()
+    setup(*views[-1])                                    # the same accum history as above, then the same temporal steps
+    r.render()
+    r.synchronize()
+    r.temporal_reset()
+    for (g, k), (oc, op) in zip(views, outs):
+        setup(g, k)
+        r.render_async()
+        r.temporal(d, None, oc.data_ptr(), op.data_ptr())
+    r.synchronize()
+    hist = r.downloadTemporalHistory()
+    for (wc, wp, _), (oc, op) in zip(want, outs):
+        assert np.array_equal(bits(oc.cpu().numpy()), bits(wc))
+        assert np.array_equal(op.cpu().numpy().view(np.uint32), wp)
+    assert np.array_equal(bits(hist), bits(want[-1][2]))
+    assert (want[-1][2][..., 3] > 1).mean() > 0.5
+    r.close()
+
+
+def test_temporal_reduces_the_periphery_error():
+    res = quality_run()[0]
+    gains = {k: a / b for k, (a, b) in res.items()}
+    print("RMSE gain of temporal over reconstruct only: periphery %.3f, middle %.3f, fovea %.3f" % (
+        gains["periphery"], gains["middle"], gains["fovea"]))
+    assert gains["periphery"] >= QUALITY_MIN_GAIN
+    assert gains["middle"] >= 1.0 and gains["fovea"] >= 1.0
+
+
+def test_temporal_matches_the_restatement_c3(oracle):
+    size = (1920, 1080)
+    r = _atrium(size, cfg_foveated(148, 482, (1, 2, 8)))
+    _sequence(oracle, r, size, ALL_CAPS, frames=3)
+    r.close()
+
+
+def test_cpp_dropin_temporal(tmp_path):
+    """SampleRenderer::temporal() + downloadTemporalPixels of include/SimplePathtracer.h: the same pixels as Python."""
+    exe, out = str(tmp_path / "temporal_gpu_test"), str(tmp_path / "temporal_out.bin")
+    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "temporal_gpu_test.cpp"), "-o", exe,
+                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
+    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    px = np.fromfile(out, np.uint32).reshape(3, 96, 160)
+    cfg = cfg_foveated(12, 36, (1, 2, 8))
+    cfg.write_guides = 1
+    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r.render()
+    r.temporal()
+    assert np.array_equal(px[0], r.downloadTemporalPixels())
+    eye = (BOX_CAMERA["eye"][0] - 0.5, BOX_CAMERA["eye"][1], BOX_CAMERA["eye"][2] + 0.5)
+    r.setCamera(renderer.Camera(eye, BOX_CAMERA["lookat"], BOX_CAMERA["up"], BOX_CAMERA["fovy"], 160 / 96.0))
+    r.render()
+    assert np.array_equal(px[1], r.downloadPixels())
+    r.temporal()
+    assert np.array_equal(px[2], r.downloadTemporalPixels())
+    assert not np.array_equal(px[1], px[2])
+    r.close()
