@@ -136,6 +136,14 @@ class ModelMesh(C.Structure):
     ]
 
 
+UPDATE_DEVICE, UPDATE_REBUILD = 1, 2            # fovpt_update_vertices flags (FOVPT_UPDATE_*)
+
+
+class VertexUpdate(C.Structure):
+    """fovpt_vertex_update: new xyz positions for one mesh of the scene (host, or device with UPDATE_DEVICE)."""
+    _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("vertex", C.c_void_p)]
+
+
 class TextureDesc(C.Structure):
     _fields_ = [("pixel", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -262,6 +270,7 @@ assert C.sizeof(LaunchParams) == 248
 assert C.sizeof(DenoiseConfig) == 32
 assert C.sizeof(ReconstructConfig) == 32 and C.sizeof(GBufferPtrs) == 40
 assert C.sizeof(TemporalConfig) == 32
+assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

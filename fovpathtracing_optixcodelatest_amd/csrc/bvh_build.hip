@@ -57,7 +57,7 @@ __global__ void k_tri_bounds(const float* __restrict__ flat, uint32_t n, Box* __
         }
         // pad so that every Moeller-Trumbore-accepted hit point lies well inside the box and the
         // fused-multiply-add slab test of the traversal stays conservative
-        float pad = 1e-4f * ext + 1e-5f * mag + 1e-20f;
+        float pad = fovpt_tri_pad(ext, mag);
         for (int a = 0; a < 3; a++) {
             b.lo[a] -= pad; b.hi[a] += pad;
             c[a] = 0.5f * (b.lo[a] + b.hi[a]);
@@ -851,7 +851,7 @@ __global__ void k_split_emit(const float* __restrict__ flat, uint32_t n, const u
             if (hi[a] - lo[a] > ext) { ext = hi[a] - lo[a]; ax = a; }
             mag = fmaxf(mag, fmaxf(fabsf(lo[a]), fabsf(hi[a])));
         }
-        const float pad = 1e-4f * ext + 1e-5f * mag + 1e-20f;      // as k_tri_bounds: of the WHOLE triangle (also covers the clipping's rounding)
+        const float pad = fovpt_tri_pad(ext, mag);      // as k_tri_bounds: of the WHOLE triangle (also covers the clipping's rounding)
         const uint32_t k = count[i], f = first[i];
         for (uint32_t j = 0; j < k; j++) {
             Box b;
@@ -1208,6 +1208,10 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
         out->reinserted = tree_changed ? 1u : 0u;
         out->node_bytes = node_bytes;
         out->tri_bytes = tri_bytes;
+        // the levels of the wide tree, for the refit (refit.hip); a tiny scene is its root alone
+        if (level_first.size() < 2) level_first.assign({0u, 1u});
+        out->num_levels = level_first.size() - 1 <= FOVPT_BVH_MAX_LEVELS ? (uint32_t)(level_first.size() - 1) : 0u;
+        for (uint32_t L = 0; out->num_levels && L <= out->num_levels; L++) out->level_first[L] = level_first[L];
     }
 fail:
     if (err[0]) rc = hipErrorUnknown;

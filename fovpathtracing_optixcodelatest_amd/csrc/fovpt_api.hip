@@ -101,6 +101,20 @@ struct fovpt_ctx {
     DevBuf tri_tc, meshes, textures;
     std::vector<void*> tex_pixels;
     uint32_t num_tris = 0, any_catcher = 0;
+    uint32_t bvh_levels[FOVPT_BVH_MAX_LEVELS + 1] = {};   // the wide tree's levels (BvhBuildResult::level_first), for the refit
+    uint32_t bvh_num_levels = 0;
+    // fovpt_update_vertices.  What fovpt_set_scene keeps on the host: per mesh its first global primitive, first vertex in the
+    // concatenated vertex array and vertex count; per primitive the indices of its three vertices in that array; the positions.
+    // Made on the first update: their device copies (up_vtx 12 B per vertex, up_vidx 12 B per primitive), two pinned staging
+    // buffers for host updates used in turn (each reused once its previous copy has run: ev), and the event a refit records on
+    // fovpt_stream(), which every lane stream waits for before the next job traces the scene (refit_pending).
+    std::vector<uint32_t> mesh_prim0, mesh_vbase, mesh_nv, h_tri_vidx;
+    std::vector<float> h_vtx;
+    DevBuf up_vtx, up_vidx;
+    struct Staging { void* p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } up_stage[2];
+    int up_next = 0;
+    hipEvent_t ev_scene = nullptr;
+    bool refit_pending = false;
     // probe
     DevBuf pr_data, pr_pdfx, pr_cdfx, pr_pdfy, pr_cdfy, pr_guidex, pr_guidey, pr_rec;
     bool guide_ok = false;
@@ -424,6 +438,15 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     fd.tile_w = c->cfg.tile_w > 0 ? c->cfg.tile_w : 8; fd.tile_h = c->cfg.tile_h > 0 ? c->cfg.tile_h : 4;
 
     if (slots == 0) return FOVPT_OK;
+    // a refit enqueued on fovpt_stream() since the last job (fovpt_update_vertices): every stream that may trace the scene or read
+    // its triangle records -- the lanes' main and shadow streams, both chains' -- waits for it, once
+    if (c->refit_pending) {
+        for (int l = 0; l < FOVPT_MAX_LANES; l++) {
+            if (c->lane_main[l]) HIPCHK(c, hipStreamWaitEvent(c->lane_main[l], c->ev_scene, 0));
+            if (c->lane_shadow[l] && c->lane_shadow[l] != c->shadow_stream) HIPCHK(c, hipStreamWaitEvent(c->lane_shadow[l], c->ev_scene, 0));
+        }
+        c->refit_pending = false;
+    }
     // the chunk jobs of an oversized launch all run on lane 0 (their memsets / snapshot copies are ordered on shadow_stream,
     // as before round 3) and, like every job of more than FOVPT_SETS_SLOT_LIMIT sample slots (~330 B of state each), rotate
     // through no more sets than before round 4
@@ -740,6 +763,57 @@ int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev&
     return FOVPT_OK;
 }
 
+// The hierarchy over d_flat (9 floats per triangle) on stream st, as fovpt_set_scene builds it: FOVPT_BVH, FOVPT_SPLIT, and a
+// second build without reinsertion when reinsertion made the tree too deep; *ms = its device time.  On success br holds the
+// new hierarchy (adopt_hierarchy takes it); on failure nothing is kept.
+int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br, float& ms)
+{
+    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;    // destroyed on every return path
+    HIPCHK(c, hipEventCreate(&ev0.e)); HIPCHK(c, hipEventCreate(&ev1.e));
+    const hipEvent_t e0 = ev0.e, e1 = ev1.e;
+    HIPCHK(c, hipEventRecord(e0, st));
+    memset(&br, 0, sizeof(br));
+    char errbuf[256];
+    const char* bvh_env = getenv("FOVPT_BVH");          // "lbvh" = plain Karras tree (A/B testing); default PLOC
+    const int use_ploc = !(bvh_env && strcmp(bvh_env, "lbvh") == 0);
+    float split_budget = FOVPT_SPLIT_BUDGET_DEFAULT;    // references added by spatial splits, as a fraction of the triangles
+    if (const char* sb = getenv("FOVPT_SPLIT")) split_budget = (float)atof(sb);
+    if (!(split_budget >= 0.f) || split_budget > 2.f) split_budget = 0.f;
+    hipError_t be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, use_ploc, split_budget, -1, &br, errbuf, sizeof(errbuf));
+    if (be == hipSuccess && br.reinserted && 3 * br.max_depth + 1 > FOVPT_STACK) {
+        // reinsertion lowers the tree's cost, not its depth: a hierarchy it made too deep for the traversal stack is built again without it
+        (void)hipFree(br.nodes);
+        memset(&br, 0, sizeof(br));
+        be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, use_ploc, split_budget, 0, &br, errbuf, sizeof(errbuf));
+    }
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    if (be != hipSuccess) return fail(c, FOVPT_E_DEVICE, "LBVH build: %s", errbuf);
+    if (3 * br.max_depth + 1 > FOVPT_STACK) {       // a wide node leaves at most 3 entries behind
+        (void)hipFree(br.nodes);
+        return fail(c, FOVPT_E_BVH_DEPTH, "hierarchy depth %u needs more than the %d traversal stack entries", br.max_depth, FOVPT_STACK);
+    }
+    if ((size_t)((const char*)br.tris - (const char*)br.nodes) + br.tri_bytes + 64 >= (1ull << 32)) {
+        (void)hipFree(br.nodes);
+        return fail(c, FOVPT_E_INVALID, "hierarchy of %llu bytes exceeds the 32-bit offsets of the traversal",
+                    (unsigned long long)(br.node_bytes + br.tri_bytes));
+    }
+    return FOVPT_OK;
+}
+
+// the hierarchy build_hierarchy made becomes the scene's, with its scene facts
+void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms)
+{
+    c->nodes = br.nodes; c->tris = br.tris;
+    c->num_tris = br.num_refs;                       // triangle RECORDS (>= the triangles when some were split into references)
+    c->bvh_num_levels = br.num_levels;
+    memcpy(c->bvh_levels, br.level_first, sizeof(c->bvh_levels));
+    c->stats.num_bvh_nodes = br.num_nodes; c->stats.bvh_max_depth = br.max_depth;
+    c->stats.bvh_bytes = br.node_bytes; c->stats.tri_bytes = br.tri_bytes; c->stats.ms_bvh_build = ms;
+}
+
 }  // namespace
 
 extern "C" {
@@ -834,9 +908,14 @@ void fovpt_destroy(fovpt_ctx* c)
                       &c->plan_owner, &c->plan_blocks, &c->plan_total, &c->plan_base, &c->plan_idx,
                       &c->comm_packed, &c->comm_gathered, &c->dn_level, &c->dn_i0, &c->dn_i1, &c->dn_color, &c->dn_rgba,
                       &c->gb_o, &c->gb_d, &c->gb_hit, &c->gb_cnt, &c->gb_prim, &c->gb_pos, &c->gb_nrm, &c->gb_alb, &c->rc_color, &c->rc_rgba,
-                      &c->tp_color, &c->tp_rgba};
+                      &c->tp_color, &c->tp_rgba, &c->up_vtx, &c->up_vidx};
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < 2; k++) { c->tp_prim[k].release(); c->tp_pos[k].release(); c->tp_nrm[k].release(); c->tp_alb[k].release(); c->tp_hist[k].release(); }
+    for (auto& S : c->up_stage) {
+        if (S.p) (void)hipHostFree(S.p);
+        if (S.ev) (void)hipEventDestroy(S.ev);
+    }
+    if (c->ev_scene) (void)hipEventDestroy(c->ev_scene);
     for (int l = 0; l < FOVPT_MAX_LANES; l++) {
         if (c->lane_main[l] && c->lane_main[l] != c->stream) (void)hipStreamDestroy(c->lane_main[l]);
         if (c->lane_shadow[l] && c->lane_shadow[l] != c->shadow_stream) (void)hipStreamDestroy(c->lane_shadow[l]);
@@ -857,6 +936,8 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     { const int rc_ = sync_all(c); if (rc_) return rc_; }
     free_scene(c);
     c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
+    c->up_vtx.release(); c->up_vidx.release();       // fovpt_update_vertices' device copies: made again on the scene's first update
+    c->refit_pending = false;
     uint64_t ntri = 0;
     bool any_tc = false;
     for (int m = 0; m < num_meshes; m++) {
@@ -875,9 +956,15 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     std::vector<float> tc(any_tc ? (size_t)ntri * 6 : 0, 0.0f);
     std::vector<MeshDev> md((size_t)num_meshes);
     c->any_catcher = 0;
+    // what fovpt_update_vertices needs (host only until the first update)
+    c->mesh_prim0.assign((size_t)num_meshes, 0u); c->mesh_vbase.assign((size_t)num_meshes, 0u); c->mesh_nv.assign((size_t)num_meshes, 0u);
+    c->h_tri_vidx.assign((size_t)ntri * 3, 0u);
+    c->h_vtx.clear();
     size_t t = 0;
     for (int m = 0; m < num_meshes; m++) {
         const fovpt_mesh_desc& D = meshes[m];
+        c->mesh_prim0[m] = (uint32_t)t; c->mesh_vbase[m] = (uint32_t)(c->h_vtx.size() / 3); c->mesh_nv[m] = D.num_vertices;
+        c->h_vtx.insert(c->h_vtx.end(), D.vertex, D.vertex + 3 * (size_t)D.num_vertices);
         md[m].material = D.material;
         md[m].texture_id = D.texture_id >= 0 ? D.texture_id : -1;
         md[m].has_texcoord = D.texcoord ? 1 : 0;
@@ -886,6 +973,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
             for (int v = 0; v < 3; v++) {
                 const uint32_t idx = D.index[3 * (size_t)k + v];
                 if (idx >= D.num_vertices) return fail(c, FOVPT_E_INVALID, "mesh %d triangle %u indexes vertex %u of %u", m, k, idx, D.num_vertices);
+                c->h_tri_vidx[t * 3 + v] = c->mesh_vbase[m] + idx;
                 flat[t * 9 + v * 3 + 0] = D.vertex[3 * (size_t)idx + 0];
                 flat[t * 9 + v * 3 + 1] = D.vertex[3 * (size_t)idx + 1];
                 flat[t * 9 + v * 3 + 2] = D.vertex[3 * (size_t)idx + 2];
@@ -925,47 +1013,117 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     HIPCHK(c, c->meshes.reserve(md.size() * sizeof(MeshDev)));
     HIPCHK(c, hipMemcpy(c->meshes.p, md.data(), md.size() * sizeof(MeshDev), hipMemcpyHostToDevice));
 
-    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;    // destroyed on every return path
-    HIPCHK(c, hipEventCreate(&ev0.e)); HIPCHK(c, hipEventCreate(&ev1.e));
-    const hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    HIPCHK(c, hipEventRecord(e0, c->stream));
     BvhBuildResult br;
-    memset(&br, 0, sizeof(br));
-    char errbuf[256];
-    const char* bvh_env = getenv("FOVPT_BVH");          // "lbvh" = plain Karras tree (A/B testing); default PLOC
-    const int use_ploc = !(bvh_env && strcmp(bvh_env, "lbvh") == 0);
-    float split_budget = FOVPT_SPLIT_BUDGET_DEFAULT;    // references added by spatial splits, as a fraction of the triangles
-    if (const char* sb = getenv("FOVPT_SPLIT")) split_budget = (float)atof(sb);
-    if (!(split_budget >= 0.f) || split_budget > 2.f) split_budget = 0.f;
-    hipError_t be = fovpt_build_lbvh(c->stream, d_flat, d_mesh_of, (uint32_t)ntri, use_ploc, split_budget, -1, &br, errbuf, sizeof(errbuf));
-    if (be == hipSuccess && br.reinserted && 3 * br.max_depth + 1 > FOVPT_STACK) {
-        // reinsertion lowers the tree's cost, not its depth: a hierarchy it made too deep for the traversal stack is built again without it
-        (void)hipFree(br.nodes);
-        memset(&br, 0, sizeof(br));
-        be = fovpt_build_lbvh(c->stream, d_flat, d_mesh_of, (uint32_t)ntri, use_ploc, split_budget, 0, &br, errbuf, sizeof(errbuf));
-    }
-    (void)hipEventRecord(e1, c->stream);
-    (void)hipEventSynchronize(e1);
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    if (be != hipSuccess) return fail(c, FOVPT_E_DEVICE, "LBVH build: %s", errbuf);
-    if (3 * br.max_depth + 1 > FOVPT_STACK) {       // a wide node leaves at most 3 entries behind
-        (void)hipFree(br.nodes);
-        return fail(c, FOVPT_E_BVH_DEPTH, "hierarchy depth %u needs more than the %d traversal stack entries", br.max_depth, FOVPT_STACK);
-    }
-    if ((size_t)((const char*)br.tris - (const char*)br.nodes) + br.tri_bytes + 64 >= (1ull << 32)) {
-        (void)hipFree(br.nodes);
-        return fail(c, FOVPT_E_INVALID, "hierarchy of %llu bytes exceeds the 32-bit offsets of the traversal",
-                    (unsigned long long)(br.node_bytes + br.tri_bytes));
-    }
-    c->nodes = br.nodes; c->tris = br.tris;
-    c->num_tris = br.num_refs;                       // triangle RECORDS (>= the triangles when some were split into references)
+    { const int rc_ = build_hierarchy(c, c->stream, d_flat, d_mesh_of, (uint32_t)ntri, br, ms); if (rc_) return rc_; }
+    adopt_hierarchy(c, br, ms);
+    c->stats.num_triangles = ntri;
     c->has_scene = true;
     c->scene_id = (c->scene_id & 0xffffffffull) + 1;
     c->scene_id |= 0x464f565000000000ull;          // 'FOVP' tag so a stale/foreign handle is recognisable
-    c->stats.num_triangles = ntri; c->stats.num_bvh_nodes = br.num_nodes; c->stats.bvh_max_depth = br.max_depth;
-    c->stats.bvh_bytes = br.node_bytes; c->stats.tri_bytes = br.tri_bytes; c->stats.ms_bvh_build = ms;
     if (traversable_out) *traversable_out = c->scene_id;
+    return FOVPT_OK;
+}
+
+// ---- animated geometry (refit.hip) ---------------------------------------------------------------------------------------
+// Validates everything first (all or nothing), then: the new positions into up_vtx on fovpt_stream() -- host data through a
+// pinned staging buffer and hipMemcpyAsync, device data by a gather kernel -- and either the refit, enqueued behind them on
+// the same stream (the stream every job's resolve, and so every job's last traversal launch, is ordered on), or a rebuild.
+int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_updates, int flags)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_vertices without a scene");
+    if (num_updates < 0 || (num_updates > 0 && !up)) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: %d updates at %p", num_updates, (const void*)up);
+    if (flags & ~(FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD)) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: unknown flag bits %d", flags);
+    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    const int nmesh = (int)c->mesh_nv.size();
+    std::vector<char> seen((size_t)nmesh, 0);
+    size_t floats = 0;
+    for (int k = 0; k < num_updates; k++) {
+        const fovpt_vertex_update& U = up[k];
+        if (U.mesh < 0 || U.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d of %d", U.mesh, nmesh);
+        if (seen[U.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d is listed twice", U.mesh);
+        seen[U.mesh] = 1;
+        if (U.num_vertices != c->mesh_nv[U.mesh])
+            return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d has %u vertices, the update %u", U.mesh, c->mesh_nv[U.mesh], U.num_vertices);
+        if (!U.vertex) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d has a null vertex pointer", U.mesh);
+        if (!device)
+            for (size_t i = 0; i < 3 * (size_t)U.num_vertices; i++)
+                if (!std::isfinite(U.vertex[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d vertex %zu is not finite", U.mesh, i / 3);
+        floats += 3 * (size_t)U.num_vertices;
+    }
+    if (c->h_vtx.size() / 3 >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: more than 2^32 - 1 vertices");
+    if (c->bvh_num_levels == 0) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: the hierarchy has more than %d levels", FOVPT_BVH_MAX_LEVELS);
+    if (num_updates == 0 && !rebuild) return FOVPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (rebuild) { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    const hipStream_t st = c->shadow_stream;
+    if (!c->up_vtx.p) {
+        // the first update: the device copies of what fovpt_set_scene kept (ordered on the stream like everything below)
+        if (!c->ev_scene) HIPCHK(c, hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
+        for (auto& S : c->up_stage)
+            if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+        HIPCHK(c, c->up_vidx.reserve(c->h_tri_vidx.size() * 4));
+        HIPCHK(c, c->up_vtx.reserve(c->h_vtx.size() * 4));
+        HIPCHK(c, hipMemcpyAsync(c->up_vidx.p, c->h_tri_vidx.data(), c->h_tri_vidx.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    float* vtx = (float*)c->up_vtx.p;
+    if (device) {
+        VertexGather g;
+        memset(&g, 0, sizeof(g));
+        for (int k = 0; k < num_updates; k++) {
+            g.src[g.count] = up[k].vertex; g.dst[g.count] = c->mesh_vbase[up[k].mesh]; g.n[g.count] = up[k].num_vertices;
+            g.max_n = up[k].num_vertices > g.max_n ? up[k].num_vertices : g.max_n;
+            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == num_updates) { fovpt_launch_gather_vertices(st, g, vtx); memset(&g, 0, sizeof(g)); }
+        }
+        HIPCHK(c, hipGetLastError());
+    } else if (floats) {
+        auto& S = c->up_stage[c->up_next];
+        c->up_next ^= 1;
+        if (S.pending) { HIPCHK(c, hipEventSynchronize(S.ev)); S.pending = false; }      // its previous copy has run
+        if (S.bytes < floats * 4) {
+            if (S.p) (void)hipHostFree(S.p);
+            S.p = nullptr; S.bytes = 0;
+            HIPCHK(c, hipHostMalloc(&S.p, floats * 4, hipHostMallocDefault));
+            S.bytes = floats * 4;
+        }
+        float* h = (float*)S.p;
+        for (int k = 0; k < num_updates; k++) {
+            const size_t n = 3 * (size_t)up[k].num_vertices;
+            memcpy(h, up[k].vertex, n * 4);
+            HIPCHK(c, hipMemcpyAsync(vtx + 3 * (size_t)c->mesh_vbase[up[k].mesh], h, n * 4, hipMemcpyHostToDevice, st));
+            h += n;
+        }
+        HIPCHK(c, hipEventRecord(S.ev, st));
+        S.pending = true;
+    }
+    if (!rebuild) {
+        fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, vtx);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev_scene, st));
+        c->refit_pending = true;
+        return FOVPT_OK;
+    }
+    // FOVPT_UPDATE_REBUILD: fovpt_set_scene's build over the current vertices; the old hierarchy stays if it fails
+    const uint32_t ntri = (uint32_t)c->stats.num_triangles;
+    struct Tmp { void* p = nullptr; ~Tmp() { if (p) (void)hipFree(p); } } t_flat, t_mesh_of;
+    HIPCHK(c, hipMalloc(&t_flat.p, (size_t)ntri * 36));
+    HIPCHK(c, hipMalloc(&t_mesh_of.p, (size_t)ntri * 4));
+    std::vector<uint32_t> mesh_of((size_t)ntri);
+    for (int m = 0; m < nmesh; m++) {
+        const uint32_t end = m + 1 < nmesh ? c->mesh_prim0[m + 1] : ntri;
+        for (uint32_t t = c->mesh_prim0[m]; t < end; t++) mesh_of[t] = (uint32_t)m;
+    }
+    HIPCHK(c, hipMemcpyAsync(t_mesh_of.p, mesh_of.data(), mesh_of.size() * 4, hipMemcpyHostToDevice, st));
+    fovpt_launch_flatten(st, ntri, (const uint3*)c->up_vidx.p, vtx, (float*)t_flat.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    BvhBuildResult br;
+    float ms = 0.f;
+    { const int rc_ = build_hierarchy(c, st, (const float*)t_flat.p, (const uint32_t*)t_mesh_of.p, ntri, br, ms); if (rc_) return rc_; }
+    (void)hipFree(c->nodes);                           // (the device is idle: sync_all above, and the build synchronised)
+    adopt_hierarchy(c, br, ms);
     return FOVPT_OK;
 }
 
@@ -1743,6 +1901,8 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
 {
     if (!c || !name || !ptr || !bytes) return FOVPT_E_INVALID;
     if (strcmp(name, "bvh_nodes") == 0 && c->has_scene) { *ptr = c->nodes; *bytes = (size_t)c->stats.bvh_bytes; return FOVPT_OK; }   // tools/bvhstat.py
+    if (strcmp(name, "bvh_tris") == 0 && c->has_scene) { *ptr = c->tris; *bytes = (size_t)c->stats.tri_bytes; return FOVPT_OK; }
+    if (strcmp(name, "scene_vertices") == 0 && c->up_vtx.p) { *ptr = c->up_vtx.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_update_vertices
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {
         {"sq_o", &S.sq_o[0]}, {"sq_d", &S.sq_d[0]}, {"sq_vis", &S.sq_vis[0]}, {"sq_occ", &S.sq_occ[0]}, {"counters", &S.counters},

@@ -210,7 +210,13 @@ static_assert(2 * (FOVPT_MAX_ITERS + 1) <= FOVPT_SHARD_STRIDE, "shard block hold
 #define FOVPT_CNT_Q(it) (it)                               // word index inside a shard's block
 #define FOVPT_CNT_SQ(it) (FOVPT_MAX_ITERS + 1 + (it))
 
-// ---- launchers implemented in wavefront.hip / bvh_build.hip -------------------------------
+// The padding of a triangle's box, ext its longest extent and mag its largest coordinate magnitude: the build's boxes
+// (bvh_build.hip) and the refit's (refit.hip) are this one expression, so that every Moeller-Trumbore-accepted hit point lies
+// well inside the box and the fused-multiply-add slab test of the traversal stays conservative.
+__device__ inline float fovpt_tri_pad(float ext, float mag) { return 1e-4f * ext + 1e-5f * mag + 1e-20f; }
+
+// ---- launchers implemented in wavefront.hip / bvh_build.hip / refit.hip ----------------------
+#define FOVPT_BVH_MAX_LEVELS 64   // levels of the wide tree recorded by the build (a traversable tree has at most (FOVPT_STACK - 1) / 3)
 struct BvhBuildResult {
     BvhNode4* nodes;              // ONE allocation: the emitted nodes, then (256-byte aligned) the triangles; free `nodes` only
     TriRec* tris;
@@ -219,6 +225,8 @@ struct BvhBuildResult {
     uint32_t max_depth;
     uint32_t reinserted;          // 1: reinsertion rounds changed the PLOC tree
     size_t node_bytes, tri_bytes;
+    uint32_t num_levels;          // levels of the wide tree (0: more than FOVPT_BVH_MAX_LEVELS)
+    uint32_t level_first[FOVPT_BVH_MAX_LEVELS + 1];   // level L is the contiguous nodes [level_first[L], level_first[L + 1])
 };
 
 // flat: 9 floats per triangle (v0,v1,v2), mesh_of_prim: mesh id per triangle.  All device pointers.
@@ -283,6 +291,22 @@ struct TemporalArgs {
 };
 void fovpt_launch_temporal(hipStream_t st, const FrameDev& fd, const TemporalArgs& a, const fovpt_float4* in, GBufferDev g, GBufferDev gp,
                            const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
+// tri_vidx: per global primitive id the three indices of its vertices in vtx.
+#define FOVPT_GATHER_BATCH 32
+struct VertexGather {                   // up to FOVPT_GATHER_BATCH device arrays of xyz triples, each copied into vtx at dst
+    const float* src[FOVPT_GATHER_BATCH];
+    uint32_t dst[FOVPT_GATHER_BATCH];   // first vertex in vtx
+    uint32_t n[FOVPT_GATHER_BATCH];     // vertices
+    int32_t count;
+    uint32_t max_n;
+};
+void fovpt_launch_gather_vertices(hipStream_t st, const VertexGather& g, float* vtx);
+// one launch per level of the wide tree, deepest first (levels[0 .. num_levels]: level_first of the build)
+void fovpt_launch_refit(hipStream_t st, BvhNode4* nodes, TriRec* tris, const uint32_t* levels, uint32_t num_levels, const uint3* tri_vidx,
+                        const float* vtx);
+// the build's input over the current vertices: 9 floats per primitive (v0, v1, v2)
+void fovpt_launch_flatten(hipStream_t st, uint32_t n, const uint3* tri_vidx, const float* vtx, float* flat);
 void fovpt_launch_build_guide(hipStream_t st, const float* cdf, int n, int segments, uint32_t* guide);
 void fovpt_launch_probe_records(hipStream_t st, size_t n, const float* cdfX, const float* pdfX, const float4* data, float4* rec);
 void fovpt_launch_build_cdf(hipStream_t st, int w, int h, const float4* data, float* pdfX, float* cdfX, float* pdfY, float* cdfY, float* row_total);

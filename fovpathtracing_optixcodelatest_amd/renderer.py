@@ -344,6 +344,38 @@ class SampleRenderer:
         out = np.empty((f.size.y, f.size.x, 4), np.float32)
         return self.download(self.temporal_buffers()[2], out)
 
+    # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
+    def update_vertices(self, updates, rebuild=False):
+        """New vertex positions for meshes of the scene: updates maps a mesh index to an (n, 3) float32 numpy array, or to a
+        CUDA torch tensor (device pointers, read in stream order on the renderer's stream: torch's writes of them must be ordered
+        before the call).  All host or all device.  rebuild=False refits the hierarchy asynchronously; True builds it anew
+        (synchronous).  The renderer's Model is not changed."""
+        items = sorted(updates.items())
+        on_device = [hasattr(v, "is_cuda") and bool(v.is_cuda) for _, v in items]
+        if any(on_device) and not all(on_device):
+            raise ValueError("update_vertices: mixes host arrays and device tensors")
+        device = bool(items) and all(on_device)
+        ups = (abi.VertexUpdate * max(1, len(items)))()
+        keep = []
+        for k, (mesh, v) in enumerate(items):
+            if device:
+                import torch
+                if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+                    raise ValueError("update_vertices: mesh %d needs an (n, 3) float32 tensor" % mesh)
+                v = v.contiguous()
+                ptr, n = v.data_ptr(), v.shape[0]
+            else:
+                v = np.ascontiguousarray(v, np.float32)
+                if v.ndim != 2 or v.shape[1] != 3:
+                    raise ValueError("update_vertices: mesh %d needs an (n, 3) array" % mesh)
+                ptr, n = v.ctypes.data, v.shape[0]
+            keep.append(v)
+            ups[k].mesh, ups[k].num_vertices, ups[k].vertex = int(mesh), int(n), ptr
+        flags = (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)
+        self._check(self._L.fovpt_update_vertices(self._ctx, ups, len(items), flags))
+        if device:
+            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

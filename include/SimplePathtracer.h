@@ -154,6 +154,22 @@ public:
         check(fovpt_temporal_buffers(ctx, &color, &rgba, &history));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
+    // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
+    // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true
+    // builds it anew (synchronous; include/fovpt.h, fovpt_update_vertices)
+    void updateAccel(const std::vector<int>& meshes, bool rebuild = false)
+    {
+        std::vector<fovpt_vertex_update> up(meshes.size());
+        for (size_t k = 0; k < meshes.size(); k++) {
+            if (meshes[k] < 0 || (size_t)meshes[k] >= model->meshes.size()) throw std::runtime_error("updateAccel: mesh index out of range");
+            const TriangleMesh& m = *model->meshes[meshes[k]];
+            up[k].mesh = meshes[k];
+            up[k].num_vertices = (uint32_t)m.vertex.size();
+            up[k].vertex = m.vertex.empty() ? nullptr : &m.vertex[0].x;
+        }
+        check(fovpt_update_vertices(ctx, up.data(), (int)up.size(), rebuild ? FOVPT_UPDATE_REBUILD : 0));
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

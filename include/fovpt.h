@@ -235,6 +235,41 @@ int fovpt_set_scene(fovpt_ctx* ctx, const fovpt_mesh_desc* meshes, int num_meshe
                     const fovpt_texture_desc* textures, int num_textures,
                     uint64_t* traversable_out);
 
+/* ---- animated geometry: new vertex positions for meshes of the current scene ---------------------------------------------
+ * New with this library: the reference builds its acceleration structure once (SimplePathtracer.cpp:671-706, no ALLOW_UPDATE);
+ * this is the counterpart of optixAccelBuild with OPERATION_UPDATE over the same build inputs.
+ *   geometry   the named meshes get new positions, every other mesh keeps the positions it last had.  Indices, texcoords,
+ *              materials, textures, primitive ids, the traversable handle and fovpt_temporal's history stay as they are.  After
+ *              the call every frame, G-buffer and fovpt_debug_trace is bit for bit what a context gets from fovpt_set_scene with
+ *              the updated meshes (a hit is the minimum (t, primitive id), occlusion is existence: neither depends on the tree).
+ *   refit      (the default) keeps the tree and recomputes, deepest level first, every leaf's triangle records and the boxes
+ *              of the hierarchy (the same padded triangle boxes the build unions).  Asynchronous and stream-ordered, no host
+ *              synchronisation: it runs after every frame, job, G-buffer and debug trace issued before the call, whatever
+ *              frames_in_flight and chains_per_frame say, and everything issued after the call sees the new geometry.  Host
+ *              vertex data is copied before the call returns (through a pinned staging buffer, as fovpt_set_scene copies).
+ *              With FOVPT_UPDATE_DEVICE the vertex pointers are device pointers, read in stream order on fovpt_stream(): the
+ *              caller orders its own writes of them before the call.  A refit tree keeps its shape: traversal slows as the
+ *              motion grows, which FOVPT_UPDATE_REBUILD resets.
+ *   REBUILD    builds the hierarchy anew over the updated (current) vertices, as fovpt_set_scene builds it.  Host-synchronous
+ *              like fovpt_set_scene; keeps the handle, primitive ids and history.  Updates stats.ms_bvh_build and the scene facts
+ *              as fovpt_set_scene does (a refit leaves them unchanged).  num_updates may be 0: a rebuild alone.  If the build
+ *              fails (FOVPT_E_BVH_DEPTH, FOVPT_E_DEVICE) the previous hierarchy stays.
+ *   errors     all or nothing, checked before anything changes.  FOVPT_E_NO_SCENE: no scene.  FOVPT_E_INVALID: null ctx, null
+ *              updates with num_updates > 0, num_updates < 0, a mesh out of range or listed twice, num_vertices other than the
+ *              mesh's, a null vertex pointer, unknown flag bits, a non-finite coordinate (host data only: device data is not
+ *              read by the call, and non-finite device coordinates are the caller's responsibility).
+ *              num_updates == 0 without FOVPT_UPDATE_REBUILD: FOVPT_OK, nothing happens.
+ * Device memory: on the first update the context keeps the vertex positions (12 bytes per vertex) and the vertex indices of
+ * every triangle (12 bytes per triangle); a scene that is never updated costs nothing more on the device.                 */
+typedef struct fovpt_vertex_update {
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    uint32_t num_vertices;       /* must equal that mesh's num_vertices                                                     */
+    const float* vertex;         /* xyz triples (host, or device with FOVPT_UPDATE_DEVICE)                                  */
+} fovpt_vertex_update;
+#define FOVPT_UPDATE_DEVICE  1   /* vertex pointers are device pointers, read in stream order on fovpt_stream()             */
+#define FOVPT_UPDATE_REBUILD 2   /* build the hierarchy anew over the updated vertices instead of refitting it              */
+int fovpt_update_vertices(fovpt_ctx* ctx, const fovpt_vertex_update* updates, int num_updates, int flags);
+
 /* CUDAProbeData::createBuffer (Probe.h:102-124): uploads the 5 arrays, fills *probe_out
  * with device pointers exactly as setProbe does (SimplePathtracer.cpp:292-308).   */
 int fovpt_set_probe(fovpt_ctx* ctx, int width, int height, const fovpt_float4* data,
@@ -544,7 +579,9 @@ int fovpt_debug_math(fovpt_ctx* ctx, int op, const float* a, const float* b, flo
  * hit -> global primitive id (0xffffffff = miss) and (t, u, v); occlusion ray (deviceProgram.cu:224-248) -> 0 / 1.
  * Any output may be NULL.  Synchronises.                                                                              */
 int fovpt_debug_trace(fovpt_ctx* ctx, int n, const float* origins3, const float* dirs3, uint32_t* prim_out, float* tuv_out3, uint8_t* occluded_out);
-/* tests/diagnostics only: device address and size of an internal buffer ("sq_occ", "counters", "hit", "bvh_nodes", ...) */
+/* tests/diagnostics only: device address and size of an internal buffer ("sq_occ", "counters", "hit", "bvh_nodes", "bvh_tris"
+ * -- the 48-byte triangle records of the hierarchy, stats.tri_bytes --, "scene_vertices" -- fovpt_update_vertices' vertex
+ * array, once made --, ...)                                                                                                     */
 int fovpt_debug_buffer(fovpt_ctx* ctx, const char* name, void** ptr, size_t* bytes);
 
 #ifdef __cplusplus
@@ -559,6 +596,7 @@ static_assert(sizeof(fovpt_denoise_config) == 32, "denoise config ABI");
 static_assert(sizeof(fovpt_reconstruct_config) == 32, "reconstruct config ABI");
 static_assert(sizeof(fovpt_gbuffer_ptrs) == 40, "gbuffer ABI");
 static_assert(sizeof(fovpt_temporal_config) == 32, "temporal config ABI");
+static_assert(sizeof(fovpt_vertex_update) == 16 && offsetof(fovpt_vertex_update, vertex) == 8, "vertex update ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

@@ -1,0 +1,470 @@
+"""fovpt_update_vertices on the GPU: the refit hierarchy's bytes against the build and against tests/refit_ref.py, frames, rays
+and G-buffers after motion against the CPU oracle and against a fresh build of the moved model, the ordering with frames in
+flight and post-processing, device pointers, spatial splits and tiny scenes, rejections and the C++ drop-in."""
+import ctypes as C
+import dataclasses
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import refit_ref as rf
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+
+from common import cfg_foveated, cfg_uniform, make_gpu, make_oracle
+from postprocess_common import bits
+from temporal_common import Checker
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_INVALID, E_NO_SCENE = -1, -3
+NTHREADS = 16
+CORNELL, ATRIUM = scenes.CORNELL_CAMERA, scenes.ATRIUM_CAMERA
+PROBE = scenes.ambient_probe(64, 32, 2.0)
+
+
+# ---- helpers --------------------------------------------------------------------------------------------------------------
+def hierarchy(r):
+    """The refit-visible hierarchy: (nodes (N, 32) uint32, records (R, 12) uint32)."""
+    out = []
+    for name, width in ((b"bvh_nodes", 32), (b"bvh_tris", 12)):
+        p, n = C.c_void_p(), C.c_size_t()
+        r._check(r._L.fovpt_debug_buffer(r._ctx, name, C.byref(p), C.byref(n)))
+        out.append(r.download(p.value, np.empty(n.value // 4, np.uint32)).reshape(-1, width))
+    return out
+
+
+def moved(model, new):
+    """A copy of model whose meshes new maps to new vertex arrays."""
+    m = scenes.Model(list(model.meshes), list(model.textures))
+    for k, v in new.items():
+        m.meshes[k] = dataclasses.replace(m.meshes[k], vertex=np.ascontiguousarray(v, np.float32))
+    return m
+
+
+def vertex_arrays(model):
+    """(tri_vidx (T, 3), vtx (V, 3)) of a model: the concatenated vertex array and per primitive its vertex indices."""
+    base, vidx, vtx = 0, [], []
+    for m in model.meshes:
+        vidx.append(np.asarray(m.index, np.int64) + base)
+        vtx.append(np.asarray(m.vertex, np.float32))
+        base += m.vertex.shape[0]
+    return np.concatenate(vidx), np.concatenate(vtx)
+
+
+def rotate_translate(v, deg, axis_point, t):
+    a = np.deg2rad(deg)
+    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    c = np.asarray(axis_point, np.float64)
+    return ((np.asarray(v, np.float64) - c) @ R.T + c + np.asarray(t, np.float64)).astype(np.float32)
+
+
+def jitter(v, seed, amount):
+    rng = np.random.default_rng(seed)
+    return (np.asarray(v, np.float32) + rng.uniform(-amount, amount, v.shape).astype(np.float32)).astype(np.float32)
+
+
+def oracle_frame(orc, model, cam, size, cfg, gaze=None):
+    S, Fr = make_oracle(orc, model, PROBE, cam, size, gaze=gaze)
+    cnt = orc.render(S, Fr, cfg, nthreads=NTHREADS)
+    return Fr, cnt
+
+
+def render(r):
+    r.reset_stats()
+    r.launchParams.frame.subframe_index = 0
+    r.render()
+    return r.downloadAccum(), r.downloadPixels(), r.stats()
+
+
+def assert_frame_is_oracle(orc, r, model, cam, size, cfg):
+    acc, px, st = render(r)
+    Fr, cnt = oracle_frame(orc, model, cam, size, cfg, gaze=(r.launchParams.frame.c.x, r.launchParams.frame.c.y))
+    assert np.array_equal(bits(acc), bits(Fr.accum))
+    assert np.array_equal(px, Fr.frame)
+    assert st.paths == cnt[2] and (st.radiance_rays, st.shadow_rays) == (cnt.lib_radiance, cnt.lib_shadow)
+    if cfg.write_guides:
+        for name in ("normal", "albedo", "color"):
+            f = r.launchParams.frame
+            g = r.download(getattr(f, name + "_buffer"), np.empty((size[1], size[0], 4), np.float32))
+            assert np.array_equal(bits(g), bits(getattr(Fr, name))), name
+    return acc, px
+
+
+def cornell_motions(model):
+    """(name, {mesh: vertices}): the tall block (mesh 4) turned and carried, the short block (3) scaled unevenly, the red wall
+    (2) collapsed to a point."""
+    tall, short = model.meshes[4].vertex, model.meshes[3].vertex
+    return [
+        ("rigid", {4: rotate_translate(tall, 23.0, (368.0, 0.0, 351.0), (-40.0, 12.0, -30.0))}),
+        ("scale", {3: ((short - np.float32([186, 0, 168])) * np.float32([1.3, 0.6, 0.9]) + np.float32([186, 0, 168])).astype(np.float32)}),
+        ("point", {2: np.tile(np.float32([[552.0, 274.0, 280.0]]), (model.meshes[2].vertex.shape[0], 1))}),
+    ]
+
+
+@pytest.fixture
+def env(monkeypatch):
+    return monkeypatch
+
+
+# ---- 1. identity ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bvh", ["ploc", "lbvh"])
+@pytest.mark.parametrize("scene", ["cornell", "atrium"])
+def test_identity_update_keeps_the_build_bytes(env, bvh, scene):
+    env.setenv("FOVPT_BVH", bvh)
+    model = scenes.cornell_box() if scene == "cornell" else scenes.atrium(20000)
+    r = renderer.SampleRenderer(model)
+    n0, t0 = hierarchy(r)
+    r.update_vertices({k: m.vertex for k, m in enumerate(model.meshes)})
+    n1, t1 = hierarchy(r)
+    assert np.array_equal(n0, n1) and np.array_equal(t0, t1)
+    r.close()
+
+
+# ---- 2. restatement ---------------------------------------------------------------------------------------------------------
+def test_refit_matches_the_restatement():
+    model = scenes.atrium(20000)
+    r = renderer.SampleRenderer(model)
+    n0, t0 = hierarchy(r)
+    levels = rf.levels_of(n0)
+    new = {k: jitter(model.meshes[k].vertex, k, 8.0) for k in range(0, len(model.meshes), 2)}
+    r.update_vertices(new)
+    n1, t1 = hierarchy(r)
+    vidx, vtx = vertex_arrays(moved(model, new))
+    wn, wt = rf.refit(n0, t0, levels, vidx, vtx)
+    assert np.array_equal(t1, wt)
+    assert np.array_equal(n1, wn)
+    assert not np.array_equal(n1, n0)
+    # a second update starts from the first one's positions: the meshes not named keep theirs
+    new2 = {1: jitter(model.meshes[1].vertex, 99, 5.0)}
+    r.update_vertices(new2)
+    n2, t2 = hierarchy(r)
+    vidx, vtx = vertex_arrays(moved(moved(model, new), new2))
+    wn2, wt2 = rf.refit(n1, t1, levels, vidx, vtx)
+    assert np.array_equal(t2, wt2) and np.array_equal(n2, wn2)
+    r.close()
+
+
+# ---- 3. / 4. frames against the oracle and against a fresh build --------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["foveated", "fov_off", "guides"])
+def test_cornell_frames_after_motion(oracle, mode):
+    size = (96, 64)
+    cfg = cfg_uniform(2) if mode == "fov_off" else cfg_foveated(10, 24, (1, 2, 4))
+    cfg.write_guides = 1 if mode == "guides" else 0
+    base = scenes.cornell_box()
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    cur = base
+    for name, new in cornell_motions(base):
+        r.update_vertices(new)
+        cur = moved(cur, new)
+        acc, px = assert_frame_is_oracle(oracle, r, cur, CORNELL, size, cfg)
+        fresh = make_gpu(cur, PROBE, CORNELL, size, cfg)
+        facc, fpx, _ = render(fresh)
+        assert np.array_equal(bits(acc), bits(facc)) and np.array_equal(px, fpx), name
+        fresh.close()
+    r.close()
+
+
+def test_textured_atrium_jitter_refit_and_rebuild(oracle):
+    size = (96, 64)
+    cfg = cfg_foveated(10, 24, (1, 2, 4))
+    base = scenes.atrium(8000)
+    textured = [k for k, m in enumerate(base.meshes) if m.texture_id >= 0 and m.texcoord is not None]
+    assert textured
+    new = {k: jitter(base.meshes[k].vertex, 7 + k, 6.0) for k in textured[:2]}
+    cur = moved(base, new)
+    fresh = make_gpu(cur, PROBE, ATRIUM, size, cfg)
+    want = render(fresh)
+    fresh.close()
+    for rebuild in (False, True):
+        r = make_gpu(base, PROBE, ATRIUM, size, cfg)
+        st0 = r.stats()
+        r.update_vertices(new, rebuild=rebuild)
+        st1 = r.stats()
+        if not rebuild:                                            # a refit leaves the scene facts as they were
+            assert (st1.num_bvh_nodes, st1.bvh_bytes, st1.tri_bytes, st1.ms_bvh_build) == (st0.num_bvh_nodes, st0.bvh_bytes, st0.tri_bytes, st0.ms_bvh_build)
+        else:
+            assert st1.ms_bvh_build != st0.ms_bvh_build and st1.num_triangles == st0.num_triangles
+        acc, px = assert_frame_is_oracle(oracle, r, cur, ATRIUM, size, cfg)
+        assert np.array_equal(bits(acc), bits(want[0])) and np.array_equal(px, want[1])
+        r.close()
+
+
+def test_rebuild_keeps_handle_and_matches_a_fresh_build():
+    base = scenes.cornell_box()
+    size, cfg = (96, 64), cfg_foveated(10, 24, (1, 2, 4))
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    trav = r.launchParams.traversable
+    new = cornell_motions(base)[0][1]
+    r.update_vertices(new, rebuild=True)
+    assert r.launchParams.traversable == trav
+    fresh = make_gpu(moved(base, new), PROBE, CORNELL, size, cfg)
+    st, fst = r.stats(), fresh.stats()
+    assert (st.num_triangles, st.tri_bytes) == (fst.num_triangles, fst.tri_bytes)
+    n, t = hierarchy(r)
+    rf.check_conservative(n, t, rf.levels_of(n))
+    want = render(fresh)
+    got = render(r)
+    assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(got[1], want[1])
+    r.update_vertices({}, rebuild=True)                              # a rebuild alone
+    got = render(r)
+    assert np.array_equal(bits(got[0]), bits(want[0])) and np.array_equal(got[1], want[1])
+    fresh.close()
+    r.close()
+
+
+# ---- 5. rays ------------------------------------------------------------------------------------------------------------------
+def test_rays_after_update_match_the_oracle(oracle):
+    base = scenes.cornell_box()
+    new = dict(cornell_motions(base)[0][1])
+    new.update(cornell_motions(base)[1][1])
+    cur = moved(base, new)
+    r = renderer.SampleRenderer(base)
+    r.update_vertices(new)
+    rng = np.random.default_rng(11)
+    o = (rng.uniform(0, 1, (4096, 3)) * np.float32([556, 548, 559])).astype(np.float32)
+    d = rng.standard_normal((4096, 3)).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    prim, tuv, occ = r.debug_trace(o, d)
+    wp, wt, wo = oracle.OracleScene(cur).trace(o, d)
+    assert np.array_equal(prim, wp) and np.array_equal(bits(tuv), bits(wt)) and np.array_equal(occ, wo)
+    assert (prim != 0xffffffff).mean() > 0.5
+    r.close()
+
+
+# ---- 6. conservative hierarchy after a large move -----------------------------------------------------------------------------
+def test_hierarchy_stays_conservative_after_a_large_move():
+    model = scenes.atrium(20000)
+    r = renderer.SampleRenderer(model)
+    n0, _ = hierarchy(r)
+    levels = rf.levels_of(n0)
+    lo = np.min([m.vertex.min(axis=0) for m in model.meshes], axis=0)
+    hi = np.max([m.vertex.max(axis=0) for m in model.meshes], axis=0)
+    k = int(np.argmax([m.index.shape[0] for m in model.meshes]))
+    r.update_vertices({k: (model.meshes[k].vertex + (hi - lo) * np.float32(0.8)).astype(np.float32)})
+    n1, t1 = hierarchy(r)
+    rf.check_conservative(n1, t1, levels)
+    assert rf.sah_cost(n1, levels) > rf.sah_cost(n0, levels)
+    r.close()
+
+
+# ---- 7. frames in flight ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["frames_in_flight", "chains_per_frame"])
+def test_updates_between_frames_in_flight(oracle, mode):
+    import torch
+    size = (192, 128)
+    cfg = cfg_foveated(20, 48, (2, 4, 8))                   # >= 16384 sample slots: chains_per_frame = 2 does split the frame
+    if mode == "frames_in_flight":
+        cfg.frames_in_flight = 2
+    else:
+        cfg.chains_per_frame = 2
+    base = scenes.cornell_box()
+    tall = base.meshes[4].vertex
+    poses = [{4: rotate_translate(tall, 6.0 * k, (368.0, 0.0, 351.0), (-8.0 * k, 0.0, -5.0 * k))} for k in range(8)]
+    shape = (size[1], size[0])
+
+    def buffers():
+        return (torch.zeros(shape + (4,), dtype=torch.float32, device="cuda"), torch.zeros(shape, dtype=torch.int32, device="cuda"))
+
+    def issue(r, bufs):
+        f = r.launchParams.frame
+        f.accum_buffer, f.frame_buffer = bufs[0].data_ptr(), bufs[1].data_ptr()
+        f.subframe_index = 0
+        r.render_async()
+
+    # each pose alone, a sync after it
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    want = []
+    for p in poses:
+        b = buffers()
+        torch.cuda.synchronize()
+        r.update_vertices(p)
+        issue(r, b)
+        r.synchronize()
+        want.append((b[0].cpu().numpy(), b[1].cpu().numpy()))
+    r.close()
+    # back to back, no synchronisation
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    outs = [buffers() for _ in poses]
+    torch.cuda.synchronize()
+    for p, b in zip(poses, outs):
+        r.update_vertices(p)
+        issue(r, b)
+    r.synchronize()
+    for k, (b, w) in enumerate(zip(outs, want)):
+        acc, px = b[0].cpu().numpy(), b[1].cpu().numpy()
+        assert np.array_equal(bits(acc), bits(w[0])) and np.array_equal(px, w[1]), "pose %d" % k
+    for k in (0, 3, 7):
+        Fr, _ = oracle_frame(oracle, moved(base, poses[k]), CORNELL, size, cfg)
+        assert np.array_equal(bits(want[k][0]), bits(Fr.accum)) and np.array_equal(want[k][1].view(np.uint32), Fr.frame), "pose %d" % k
+    r.close()
+
+
+# ---- 8. post-processing order -------------------------------------------------------------------------------------------------
+class _DevArray:
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(ptr, False), version=2)
+
+
+def test_gbuffer_and_temporal_around_an_update(oracle):
+    import torch
+    size = (96, 64)
+    cfg = cfg_foveated(10, 24, (1, 2, 4))
+    cfg.write_guides = 1
+    base = scenes.cornell_box()
+    new = cornell_motions(base)[0][1]
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    # G-buffer, a copy of it on the library's stream, the update, a second G-buffer: no host synchronisation in between
+    g = r.gbuffer()
+    kept = torch.empty((size[1], size[0], 4), dtype=torch.float32, device="cuda")
+    kept_prim = torch.empty((size[1], size[0]), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(torch.cuda.ExternalStream(r.stream)):
+        kept.copy_(torch.as_tensor(_DevArray(g.position, (size[1], size[0], 4), "<f4"), device="cuda"))
+        kept_prim.copy_(torch.as_tensor(_DevArray(g.prim, (size[1], size[0]), "<i4"), device="cuda"))
+    r.update_vertices(new)
+    after = r.downloadGBuffer(r.gbuffer())
+    for model, prim, pos in ((base, kept_prim.cpu().numpy().view(np.uint32), kept.cpu().numpy()), (moved(base, new), after["prim"], after["position"])):
+        f = make_gpu(model, PROBE, CORNELL, size, cfg)
+        want = f.downloadGBuffer()
+        assert np.array_equal(prim, want["prim"]) and np.array_equal(bits(pos), bits(want["position"]))
+        f.close()
+    assert not np.array_equal(after["prim"], kept_prim.cpu().numpy().view(np.uint32))
+    # a temporal step after an update keeps its history and is the restatement's on the new G-buffer
+    ck = Checker(oracle, r)
+    r.render()
+    ck.step()
+    r.update_vertices(cornell_motions(base)[1][1])
+    r.render()
+    _, h, _ = ck.step()
+    assert (h[..., 3] > 1).mean() > 0.5
+    r.close()
+
+
+# ---- 9. device pointers -------------------------------------------------------------------------------------------------------
+def test_device_pointers_give_the_host_bytes():
+    """On one context (two builds of one model may order their nodes differently): the host path's bytes, back to the build's
+    by an identity update, then the device path's bytes."""
+    import torch
+    model = scenes.atrium(8000)
+    new = {k: jitter(model.meshes[k].vertex, 30 + k, 4.0) for k in range(len(model.meshes))}
+    r = renderer.SampleRenderer(model)
+    h0 = hierarchy(r)
+    r.update_vertices(new)
+    want = hierarchy(r)
+    r.update_vertices({k: m.vertex for k, m in enumerate(model.meshes)})
+    back = hierarchy(r)
+    assert np.array_equal(back[0], h0[0]) and np.array_equal(back[1], h0[1])
+    dev = {k: torch.from_numpy(v).cuda() for k, v in new.items()}
+    torch.cuda.synchronize()
+    r.update_vertices(dev)
+    got = hierarchy(r)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert not np.array_equal(got[0], h0[0])
+    with pytest.raises(ValueError):
+        r.update_vertices({0: new[0], 1: dev[1]})
+    r.close()
+
+
+# ---- 10. splits and tiny scenes -----------------------------------------------------------------------------------------------
+def test_spatial_splits_after_motion(oracle, env):
+    env.setenv("FOVPT_SPLIT", "0.3")
+    size, cfg = (96, 64), cfg_foveated(10, 24, (1, 2, 4))
+    base = scenes.cornell_box()
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    assert r.stats().tri_bytes > 48 * base.num_triangles           # (references were split)
+    cur = base
+    for _, new in cornell_motions(base)[:2]:
+        r.update_vertices(new)
+        cur = moved(cur, new)
+    n, t = hierarchy(r)
+    rf.check_conservative(n, t, rf.levels_of(n))
+    assert_frame_is_oracle(oracle, r, cur, CORNELL, size, cfg)
+    r.close()
+
+
+@pytest.mark.parametrize("ntri", [1, 3])
+def test_tiny_scenes_after_motion(oracle, ntri):
+    size, cfg = (64, 48), cfg_uniform(2)
+    base = scenes.cornell_box()
+    tall = base.meshes[4]
+    m = scenes.Model([scenes.TriangleMesh(tall.vertex, tall.index[:ntri], tall.material)])
+    r = make_gpu(m, PROBE, CORNELL, size, cfg)
+    new = {0: rotate_translate(tall.vertex, 30.0, (368.0, 0.0, 351.0), (-60.0, 40.0, 0.0))}
+    r.update_vertices(new)
+    assert_frame_is_oracle(oracle, r, moved(m, new), CORNELL, size, cfg)
+    r.close()
+
+
+# ---- 11. rejections -----------------------------------------------------------------------------------------------------------
+def test_rejections_change_nothing():
+    size, cfg = (64, 48), cfg_foveated(8, 20, (1, 2, 4))
+    base = scenes.cornell_box()
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    L = r._L
+    before = hierarchy(r)
+    acc0, px0, _ = render(r)
+    st0 = r.stats()
+    v4 = np.ascontiguousarray(base.meshes[4].vertex + np.float32(10))
+    nv4 = v4.shape[0]
+
+    def call(entries, n=None, flags=0, ctx=None):
+        ups = (abi.VertexUpdate * max(1, len(entries)))()
+        for k, (mesh, nv, ptr) in enumerate(entries):
+            ups[k].mesh, ups[k].num_vertices, ups[k].vertex = mesh, nv, ptr
+        return L.fovpt_update_vertices(r._ctx if ctx is None else ctx, ups, len(entries) if n is None else n, flags)
+
+    bad_v = v4.copy()
+    bad_v[3, 1] = np.nan
+    inf_v = v4.copy()
+    inf_v[0, 2] = np.inf
+    ok = (4, nv4, v4.ctypes.data)
+    cases = [
+        ([ok], -1, 0),                                            # num_updates < 0
+        ([(7, nv4, v4.ctypes.data)], None, 0),                    # mesh out of range
+        ([(-1, nv4, v4.ctypes.data)], None, 0),
+        ([ok, ok], None, 0),                                      # listed twice
+        ([(4, nv4 - 1, v4.ctypes.data)], None, 0),                # vertex count
+        ([(4, nv4, None)], None, 0),                              # null vertices
+        ([ok], None, 4),                                          # unknown flag bits
+        ([(4, nv4, bad_v.ctypes.data)], None, 0),                 # NaN
+        ([(4, nv4, inf_v.ctypes.data)], None, abi.UPDATE_REBUILD),   # inf, with a rebuild asked for
+        ([ok, (3, 1, v4.ctypes.data)], None, 0),                  # the second entry is bad: nothing of the first is applied
+    ]
+    for entries, n, flags in cases:
+        assert call(entries, n, flags) == E_INVALID, (entries, n, flags)
+    assert L.fovpt_update_vertices(r._ctx, None, 1, 0) == E_INVALID
+    assert L.fovpt_update_vertices(None, None, 0, 0) == E_INVALID
+    assert L.fovpt_update_vertices(r._ctx, None, 0, 0) == 0      # nothing to do
+    after = hierarchy(r)
+    assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
+    acc1, px1, _ = render(r)
+    assert np.array_equal(bits(acc0), bits(acc1)) and np.array_equal(px0, px1)
+    st1 = r.stats()
+    assert (st1.num_triangles, st1.num_bvh_nodes, st1.bvh_bytes, st1.tri_bytes, st1.bvh_max_depth, st1.ms_bvh_build) == \
+        (st0.num_triangles, st0.num_bvh_nodes, st0.bvh_bytes, st0.tri_bytes, st0.bvh_max_depth, st0.ms_bvh_build)
+    assert call([ok]) == 0
+    st2 = r.stats()
+    assert (st2.num_bvh_nodes, st2.bvh_bytes, st2.tri_bytes, st2.ms_bvh_build) == (st0.num_bvh_nodes, st0.bvh_bytes, st0.tri_bytes, st0.ms_bvh_build)
+    r.close()
+    # no scene
+    ctx = C.c_void_p()
+    lib.check(None, L.fovpt_create(C.byref(ctx), 0))
+    assert L.fovpt_update_vertices(ctx, None, 0, 0) == E_NO_SCENE
+    L.fovpt_destroy(ctx)
+
+
+# ---- 12. C++ ------------------------------------------------------------------------------------------------------------------
+def test_cpp_update_accel(tmp_path):
+    """SampleRenderer::updateAccel of include/SimplePathtracer.h over the mutated Model: the pixels of a fresh renderer."""
+    exe, out = str(tmp_path / "refit_gpu_test"), str(tmp_path / "refit_out.bin")
+    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "refit_gpu_test.cpp"), "-o", exe,
+                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
+    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    px = np.fromfile(out, np.uint32).reshape(4, 96, 160)
+    assert np.array_equal(px[0], px[1]) and np.array_equal(px[2], px[3])     # refit / rebuild == fresh renderer
+    assert not np.array_equal(px[0], px[2])
