@@ -1,0 +1,368 @@
+// api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
+// fovpt_reconstruct (reconstruct.hip), fovpt_temporal (temporal.hip), and their defaults.
+#include <cmath>
+#include <cstring>
+
+#include "fovpt_ctx.h"
+
+namespace {
+
+// an edge-stopping scale of fovpt_denoise / fovpt_reconstruct: inside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX], so that 1 / sigma^2
+// is a normal float and the denoiser's colour scale (1 / sigma^2) * 4^(FOVPT_DENOISE_MAX_ITERATIONS - 1) / 1e-4 stays finite
+// (an infinite scale makes the centre tap 0 * inf: every weight 0, the output 0 / 0)
+bool sigma_ok(float v) { return v >= FOVPT_SIGMA_MIN && v <= FOVPT_SIGMA_MAX; }
+float inv_sq(float s) { const float s2 = s * s; return 1.0f / s2; }
+
+// What fovpt_denoise, fovpt_reconstruct and fovpt_temporal (`who`) ask of the frame last rendered: there is one, it has the guides
+// where the call needs them (need_guides: the error text, or null), it is not a tile shard (a shard has no neighbours
+// `to_what`), and lp's frame has its size.
+int check_rendered_frame(fovpt_ctx* c, const fovpt_launch_params* lp, const char* who, const char* to_what, const char* need_guides)
+{
+    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "%s: no frame rendered yet", who);
+    if (need_guides && (!c->dn_guides || c->any_catcher)) return fail(c, FOVPT_E_INVALID, "%s", need_guides);
+    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "%s: a tile shard (world = %d) has no neighbours to %s", who, c->dn_world, to_what);
+    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
+        return fail(c, FOVPT_E_NO_FRAME, "%s: frame size %d x %d differs from the last frame's %d x %d", who, lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
+    return FOVPT_OK;
+}
+
+// The caller gave no output, or asks for the context's own (the *_buffers calls): the colour / rgba pair of the last frame's
+// size, made on first use, for whichever of the two is null.
+int own_outputs(fovpt_ctx* c, const char* who, DevBuf& color, DevBuf& rgba, fovpt_float4*& out_color, uint32_t*& out_rgba)
+{
+    if (out_color && out_rgba) return FOVPT_OK;
+    if (!color.p) {
+        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "%s: no frame rendered yet", who);
+        HIPCHK(c, hipSetDevice(c->device));
+    }
+    const size_t n = (size_t)c->dn_w * (size_t)c->dn_h;
+    HIPCHK(c, color.reserve(n * 16)); HIPCHK(c, rgba.reserve(n * 4));
+    if (!out_color) out_color = (fovpt_float4*)color.p;
+    if (!out_rgba) out_rgba = (uint32_t*)rgba.p;
+    return FOVPT_OK;
+}
+
+GBufferDev temporal_set(fovpt_ctx* c, int k)
+{
+    GBufferDev g;
+    g.prim = (uint32_t*)c->tp_prim[k].p; g.pos = (float4*)c->tp_pos[k].p; g.nrm = (float4*)c->tp_nrm[k].p; g.alb = (float4*)c->tp_alb[k].p;
+    return g;
+}
+
+// The rows of [U V W]^-1 (U, V, W the columns), in binary64: det = U . (V x W), rows (V x W) / det, (W x U) / det,
+// (U x V) / det, each entry rounded to binary32.  false: det is 0 or not finite.
+bool camera_inverse(const float* U, const float* V, const float* W, float* inv)
+{
+    auto cross = [](const double* a, const double* b, double* r) {
+        r[0] = a[1] * b[2] - a[2] * b[1]; r[1] = a[2] * b[0] - a[0] * b[2]; r[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    const double u[3] = {U[0], U[1], U[2]}, v[3] = {V[0], V[1], V[2]}, w[3] = {W[0], W[1], W[2]};
+    double r[3][3];
+    cross(v, w, r[0]); cross(w, u, r[1]); cross(u, v, r[2]);
+    const double det = (u[0] * r[0][0] + u[1] * r[0][1]) + u[2] * r[0][2];
+    if (det == 0.0 || !std::isfinite(det)) return false;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) inv[3 * i + j] = (float)(r[i][j] / det);
+    return true;
+}
+
+}  // namespace
+
+// the G-buffer's buffers for n pixels (the counters once: k_gbuffer_rays rewrites the queue sizes it uses on every call)
+int reserve_gbuffer(fovpt_ctx* c, size_t n)
+{
+    const bool fresh = c->gb_cnt.p == nullptr;
+    HIPCHK(c, c->gb_o.reserve(n * 16)); HIPCHK(c, c->gb_d.reserve(n * 16)); HIPCHK(c, c->gb_hit.reserve(n * 16));
+    HIPCHK(c, c->gb_prim.reserve(n * 4)); HIPCHK(c, c->gb_pos.reserve(n * 16)); HIPCHK(c, c->gb_nrm.reserve(n * 16)); HIPCHK(c, c->gb_alb.reserve(n * 16));
+    HIPCHK(c, c->gb_cnt.reserve(sizeof(Counters)));
+    if (fresh) HIPCHK(c, hipMemset(c->gb_cnt.p, 0, sizeof(Counters)));
+    return FOVPT_OK;
+}
+
+// fovpt_temporal's G-buffer sets, histories and outputs for n pixels
+int reserve_temporal(fovpt_ctx* c, size_t n)
+{
+    for (int k = 0; k < 2; k++) {
+        HIPCHK(c, c->tp_prim[k].reserve(n * 4)); HIPCHK(c, c->tp_pos[k].reserve(n * 16)); HIPCHK(c, c->tp_nrm[k].reserve(n * 16));
+        HIPCHK(c, c->tp_alb[k].reserve(n * 16)); HIPCHK(c, c->tp_hist[k].reserve(n * 16));
+    }
+    HIPCHK(c, c->tp_color.reserve(n * 16)); HIPCHK(c, c->tp_rgba.reserve(n * 4));
+    return FOVPT_OK;
+}
+
+// Enqueues the G-buffer of lp's frame.size seen by view's camera (view.eye / U / V / W) on fovpt_stream(): one ray per pixel,
+// traced by the production closest-hit k_traverse (so a ray gets the (prim, t, u, v) fovpt_debug_trace returns for it), then
+// the per-pixel outputs: into target's buffers (frame.size entries each), or with target null into the ones fovpt_gbuffer
+// hands out.  The ray queue, hit records and counters are shared: every use is ordered on the same stream.
+int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
+                    const GBufferDev* target)
+{
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene (traversable %llu, current %llu)", who,
+                                                                     (unsigned long long)lp->traversable, (unsigned long long)c->scene_id);
+#if FOVPT_V_STEPSTAT
+    return fail(c, FOVPT_E_INVALID, "%s: not available in a diagnostic (FOVPT_V_STEPSTAT) build", who);
+#endif
+    const int w = lp->frame.size.x, h = lp->frame.size.y;
+    if (w <= 0 || h <= 0) return fail(c, FOVPT_E_INVALID, "%s: frame size %d x %d", who, w, h);
+    const size_t n = (size_t)w * (size_t)h;
+    if (n >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, w, h);
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }
+    FrameDev fd;
+    memset(&fd, 0, sizeof(fd));
+    fd.w = w; fd.h = h;
+    memcpy(fd.eye, view.eye, sizeof(fd.eye)); memcpy(fd.U, view.U, sizeof(fd.U));
+    memcpy(fd.V, view.V, sizeof(fd.V)); memcpy(fd.W, view.W, sizeof(fd.W));
+    RayQueue q; q.o = (float4*)c->gb_o.p; q.d = (float4*)c->gb_d.p;
+    PathState ps;
+    memset(&ps, 0, sizeof(ps));
+    ps.hit = (float4*)c->gb_hit.p;                                   // all a closest-hit launch writes
+    ShadowQueue sq;
+    memset(&sq, 0, sizeof(sq));
+    Counters* cnt = (Counters*)c->gb_cnt.p;
+    if (target) g = *target;
+    else { g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = (float4*)c->gb_nrm.p; g.alb = (float4*)c->gb_alb.p; }
+    hipStream_t st = c->shadow_stream;
+    fovpt_launch_gbuffer_rays(st, fd, q, cnt);
+    fovpt_launch_traverse(st, scene_view(c), ps, q, sq, (uint32_t)n, cnt, 0, -1, c->grid_trace);   // shard 0 holds all n rays
+    fovpt_launch_gbuffer_fill(st, fd, scene_view(c), q, ps.hit, g);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// fovpt_reconstruct_defaults (chosen by measurement: DESIGN.md, section 11)
+#define FOVPT_RECONSTRUCT_SUPPORT 2.0f
+#define FOVPT_RECONSTRUCT_NORMAL_SIGMA 0.5f
+#define FOVPT_RECONSTRUCT_DEPTH_SIGMA 0.05f
+
+// fovpt_temporal_defaults (chosen by measurement: DESIGN.md, section 12)
+#define FOVPT_TEMPORAL_HISTORY_FOVEA 1
+#define FOVPT_TEMPORAL_HISTORY_MIDDLE 4
+#define FOVPT_TEMPORAL_HISTORY_PERIPHERY 8
+#define FOVPT_TEMPORAL_HISTORY_UNIFORM 4
+#define FOVPT_TEMPORAL_NORMAL_TOLERANCE 0.1f
+#define FOVPT_TEMPORAL_DEPTH_TOLERANCE 0.02f
+
+// edge-stopping scales of fovpt_denoise_defaults (chosen by measurement: DESIGN.md, denoiser)
+#define FOVPT_DENOISE_COLOR_SIGMA 8.0f
+#define FOVPT_DENOISE_NORMAL_SIGMA 0.5f
+#define FOVPT_DENOISE_ALBEDO_SIGMA 0.2f
+
+extern "C" {
+
+// ---- denoiser of the rendered frame (denoise.hip; the filter's definition: tests/denoise_ref.py) ------------------------
+int fovpt_denoise_defaults(fovpt_denoise_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->iterations_fovea = 0;
+    out->iterations_middle = 2;
+    out->iterations_periphery = 3;
+    out->iterations_uniform = 3;
+    out->color_sigma = FOVPT_DENOISE_COLOR_SIGMA;
+    out->normal_sigma = FOVPT_DENOISE_NORMAL_SIGMA;
+    out->albedo_sigma = FOVPT_DENOISE_ALBEDO_SIGMA;
+    return FOVPT_OK;
+}
+
+int fovpt_denoise_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_denoise_buffers", c->dn_color, c->dn_rgba, *color, *rgba);
+}
+
+// Enqueued on the stream every resolve runs on (fovpt_stream()), in issue order: behind the resolve of the frame last issued
+// -- also with frames_in_flight = 2 or chains_per_frame = 2, whose chains all join that stream for their resolve -- and ahead
+// of the next frame's resolve, the first of its launches that rewrites accum / frame / guides (its memsets and snapshot copies
+// of chunked launches also run there).  Callers synchronising on fovpt_stream() see the denoised frame.
+int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoise_config* dc, fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !dc) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null argument");
+    const int32_t its[4] = {dc->iterations_fovea, dc->iterations_middle, dc->iterations_periphery, dc->iterations_uniform};
+    for (int32_t n : its)
+        if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: iteration count %d outside 0 .. %d", n, FOVPT_DENOISE_MAX_ITERATIONS);
+    const float sig[3] = {dc->color_sigma, dc->normal_sigma, dc->albedo_sigma};
+    for (float v : sig)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    { const int rc_ = check_rendered_frame(c, lp, "fovpt_denoise", "filter with", "fovpt_denoise needs the denoiser guides: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)"); if (rc_) return rc_; }
+    if (!lp->frame.color_buffer || !lp->frame.normal_buffer || !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null guide buffers");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    { const int rc_ = own_outputs(c, "fovpt_denoise", c->dn_color, c->dn_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    HIPCHK(c, c->dn_level.reserve(npix));
+    HIPCHK(c, c->dn_i0.reserve(npix * 16));
+    HIPCHK(c, c->dn_i1.reserve(npix * 16));
+
+    // the level map: the passes fovpt_render ran for this frame
+    const FrameDev& fd = c->dn_frame;
+    DenoiseArgs a;
+    memset(&a, 0, sizeof(a));
+    if (c->dn_uniform) a.n_pass[0] = dc->iterations_uniform;
+    else { a.n_pass[0] = dc->iterations_periphery; a.n_pass[1] = dc->iterations_middle; a.n_pass[2] = dc->iterations_fovea; }
+    for (int p = 0; p < fd.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
+    a.inv_c = inv_sq(dc->color_sigma); a.inv_n = inv_sq(dc->normal_sigma); a.inv_a = inv_sq(dc->albedo_sigma);
+    fovpt_launch_denoise(c->shadow_stream, fd, a, lp->frame.color_buffer, lp->frame.normal_buffer, lp->frame.albedo_buffer,
+                         (float4*)c->dn_i0.p, (float4*)c->dn_i1.p, (uint8_t*)c->dn_level.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- G-buffer and reconstruction of the rendered frame (reconstruct.hip; the reconstruction's definition:
+// tests/reconstruct_ref.py) --------------------------------------------------------------------------------------------
+int fovpt_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, fovpt_gbuffer_ptrs* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !out) return fail(c, FOVPT_E_INVALID, "fovpt_gbuffer: null argument");
+    GBufferDev g;
+    FrameDev view;
+    memset(&view, 0, sizeof(view));
+    set_camera(view, lp);
+    const int rc = enqueue_gbuffer(c, lp, view, g, "fovpt_gbuffer");
+    if (rc) return rc;
+    out->prim = g.prim;
+    out->position = (fovpt_float4*)g.pos; out->normal = (fovpt_float4*)g.nrm; out->albedo = (fovpt_float4*)g.alb;
+    out->width = lp->frame.size.x; out->height = lp->frame.size.y;
+    return FOVPT_OK;
+}
+
+int fovpt_reconstruct_defaults(fovpt_reconstruct_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->support = FOVPT_RECONSTRUCT_SUPPORT;
+    out->normal_sigma = FOVPT_RECONSTRUCT_NORMAL_SIGMA;
+    out->depth_sigma = FOVPT_RECONSTRUCT_DEPTH_SIGMA;
+    out->levels = 3;
+    out->remodulate = 1;
+    return FOVPT_OK;
+}
+
+int fovpt_reconstruct_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_reconstruct_buffers", c->rc_color, c->rc_rgba, *color, *rgba);
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: behind the resolve of the frame last issued, ahead of
+// the next frame's.  Builds that frame's G-buffer first (the same stream), then reconstructs.
+int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_reconstruct_config* rc, const fovpt_float4* in_color,
+                      fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !rc) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null argument");
+    if (!(rc->support >= 1.0f && rc->support <= 2.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: support %g outside [1, 2]", (double)rc->support);
+    const float sig[2] = {rc->normal_sigma, rc->depth_sigma};
+    for (float v : sig)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    if (rc->levels < 0 || rc->levels > 3) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: levels %d outside 0 .. 3", rc->levels);
+    if (rc->remodulate != 0 && rc->remodulate != 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: remodulate %d is neither 0 nor 1", rc->remodulate);
+    for (int32_t r : rc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: reserved fields must be 0");
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_reconstruct without a scene");
+    const char* need_guides = "fovpt_reconstruct with remodulate = 1 needs the albedo guide: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)";
+    { const int rc_ = check_rendered_frame(c, lp, "fovpt_reconstruct", "reconstruct from", rc->remodulate ? need_guides : nullptr); if (rc_) return rc_; }
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null accum_buffer");
+    if (rc->remodulate && !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null albedo guide");
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = own_outputs(c, "fovpt_reconstruct", c->rc_color, c->rc_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    if (in == out_color) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: the input is the output colour buffer (it reads neighbours)");
+    GBufferDev g;
+    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, "fovpt_reconstruct"); if (rc_) return rc_; }   // the rendered frame's camera
+    const FrameDev& fd = c->dn_frame;
+    ReconstructArgs a;
+    memset(&a, 0, sizeof(a));
+    const float s = rc->support;
+    a.inv_support[0] = 1.0f / (s * 2.0f);
+    a.inv_support[1] = 1.0f / (s * 4.0f);
+    a.inv_n = inv_sq(rc->normal_sigma); a.inv_z = inv_sq(rc->depth_sigma);
+    a.levels = rc->levels; a.remodulate = rc->remodulate;
+    fovpt_launch_reconstruct(c->shadow_stream, fd, a, in, lp->frame.albedo_buffer, g, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- temporal reprojection of the frame history (temporal.hip; its definition: tests/temporal_ref.py) ------------------
+int fovpt_temporal_defaults(fovpt_temporal_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->history_fovea = FOVPT_TEMPORAL_HISTORY_FOVEA;
+    out->history_middle = FOVPT_TEMPORAL_HISTORY_MIDDLE;
+    out->history_periphery = FOVPT_TEMPORAL_HISTORY_PERIPHERY;
+    out->history_uniform = FOVPT_TEMPORAL_HISTORY_UNIFORM;
+    out->normal_tolerance = FOVPT_TEMPORAL_NORMAL_TOLERANCE;
+    out->depth_tolerance = FOVPT_TEMPORAL_DEPTH_TOLERANCE;
+    return FOVPT_OK;
+}
+
+int fovpt_temporal_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba, const fovpt_float4** history)
+{
+    if (!c || !color || !rgba || !history) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    int rc_ = own_outputs(c, "fovpt_temporal_buffers", c->tp_color, c->tp_rgba, *color, *rgba);
+    if (rc_ == FOVPT_OK && !c->tp_hist[0].p) rc_ = reserve_temporal(c, (size_t)c->dn_w * (size_t)c->dn_h);      // the histories and G-buffer sets with them
+    if (rc_) return rc_;
+    *history = (const fovpt_float4*)c->tp_hist[c->tp_last].p;
+    return FOVPT_OK;
+}
+
+int fovpt_temporal_reset(fovpt_ctx* c)
+{
+    if (!c) return FOVPT_E_INVALID;
+    c->tp_valid = false;
+    return FOVPT_OK;
+}
+
+// Enqueued on fovpt_stream() like fovpt_reconstruct, and ordered like it.  Traces the rendered frame's G-buffer into the set
+// the last call did not write, reprojects the other set's history into it, and makes it the last written.
+int fovpt_temporal(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
+                   fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null argument");
+    const int32_t caps[4] = {tc->history_fovea, tc->history_middle, tc->history_periphery, tc->history_uniform};
+    for (int32_t v : caps)
+        if (v < 1 || v > FOVPT_TEMPORAL_MAX_HISTORY) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: history cap %d outside 1 .. %d", v, FOVPT_TEMPORAL_MAX_HISTORY);
+    if (!(tc->normal_tolerance >= 0.0f && tc->normal_tolerance <= 4.0f))
+        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: normal_tolerance %g outside [0, 4]", (double)tc->normal_tolerance);
+    if (!(tc->depth_tolerance >= 0.0f && tc->depth_tolerance <= 1.0f))
+        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: depth_tolerance %g outside [0, 1]", (double)tc->depth_tolerance);
+    for (int32_t r : tc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: reserved fields must be 0");
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_temporal without a scene");
+    { const int rc_ = check_rendered_frame(c, lp, "fovpt_temporal", "reproject from", nullptr); if (rc_) return rc_; }
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null accum_buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    { const int rc_ = reserve_temporal(c, npix); if (rc_) return rc_; }
+    { const int rc_ = own_outputs(c, "fovpt_temporal", c->tp_color, c->tp_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    if ((void*)out_color == c->tp_hist[0].p || (void*)out_color == c->tp_hist[1].p)
+        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: the output colour buffer is the context's history");
+    const int cur = c->tp_last ^ 1, prev = c->tp_last;
+    const GBufferDev g = temporal_set(c, cur), gp = temporal_set(c, prev);
+    GBufferDev gt;
+    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, gt, "fovpt_temporal", &g); if (rc_) return rc_; }   // the rendered frame's camera
+    const FrameDev& fd = c->dn_frame;
+    TemporalArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 4; k++) a.cap[k] = caps[k];
+    a.normal_tol = tc->normal_tolerance; a.depth_tol = tc->depth_tolerance;
+    a.uniform = c->dn_uniform != 0;
+    a.reproject = c->tp_valid && c->tp_w == c->dn_w && c->tp_h == c->dn_h && camera_inverse(c->tp_U, c->tp_V, c->tp_W, a.inv);
+    memcpy(a.eye_prev, c->tp_eye, sizeof(a.eye_prev));
+    fovpt_launch_temporal(c->shadow_stream, fd, a, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    c->tp_last = cur;                                                      // this step is the next one's previous step
+    c->tp_valid = true;
+    c->tp_w = c->dn_w; c->tp_h = c->dn_h;
+    memcpy(c->tp_eye, fd.eye, sizeof(c->tp_eye)); memcpy(c->tp_U, fd.U, sizeof(c->tp_U));
+    memcpy(c->tp_V, fd.V, sizeof(c->tp_V)); memcpy(c->tp_W, fd.W, sizeof(c->tp_W));
+    return FOVPT_OK;
+}
+
+}  // extern "C"

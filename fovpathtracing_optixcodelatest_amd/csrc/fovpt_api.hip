@@ -2,179 +2,28 @@
 //
 // One context = one device = one stream, like the reference's SampleRenderer
 // (PT_sv5_/SimplePathtracer.cpp:331-340).  Calls on a context are not thread-safe.
+//
+// The post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip; fovpt_ctx.h is what the three share.
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "fovpt_device.h"
-#ifndef FOVPT_ASYNC_LAST_SHADE_DEFAULT
-#define FOVPT_ASYNC_LAST_SHADE_DEFAULT 0
-#endif
+#include "fovpt_ctx.h"
 #ifndef FOVPT_SPLIT_BUDGET_DEFAULT
 #define FOVPT_SPLIT_BUDGET_DEFAULT 0.0f
 #endif
-#include <dlfcn.h>
-#include <rccl/rccl.h>      // types only: the library is loaded at run time (fovpt_comm_*), libfovpt.so does not link it
 
 namespace {
 
 std::string g_create_error;
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t reserve(size_t n)
-    {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
-struct EventPair { hipEvent_t a, b; int kind; };   // kind: 0 gen, 1 trace, 2 shade, 3 shadow, 4 resolve
-
 }  // namespace
 
 // for the context-free entry points of other translation units (model_loader.cpp): the text fovpt_last_error(NULL) returns
 void fovpt_internal_set_error(const char* text) { g_create_error = text ? text : ""; }
-
-// Shadow-queue buffers per state set: bounce it writes buffer it % FOVPT_NSQ, so with max_depth <= FOVPT_NSQ the
-// main chain never has to wait for an occlusion launch inside a job.
-#define FOVPT_NSQ 4
-
-struct StateSet {
-    DevBuf s_thr, s_rng, s_hit, s_rad, s_alpha, s_backplate, s_guide_n, s_guide_a, s_trace;
-    DevBuf q_o[2], q_d[2], counters;       // q_*: the two radiance-ray queues (ping-pong)
-    DevBuf sq_o[FOVPT_NSQ], sq_d[FOVPT_NSQ], sq_vis[FOVPT_NSQ], sq_occ[FOVPT_NSQ];   // shadow queues, one per bounce in flight
-    hipEvent_t ev_shade[FOVPT_MAX_ITERS + 1] = {};
-    hipEvent_t ev_shadow[FOVPT_MAX_ITERS + 1] = {};
-    hipEvent_t ev_shade2[FOVPT_MAX_ITERS + 1] = {};     // the same for the second chain of a frame (fovpt_config.chains_per_frame = 2)
-    hipEvent_t ev_shadow2[FOVPT_MAX_ITERS + 1] = {};
-    hipEvent_t ev_last_closest2 = nullptr;
-    hipEvent_t ev_done = nullptr;          // recorded after the resolve of the last job that used this set
-    hipEvent_t ev_last_closest = nullptr;  // completion of the job's last closest-hit launch (the last shading launch may run on the shadow stream)
-    bool used = false;
-    std::vector<DevBuf*> all()
-    {
-        std::vector<DevBuf*> v = {&q_o[0], &q_d[0], &q_o[1], &q_d[1], &s_thr, &s_rng, &s_hit, &s_rad, &s_alpha, &s_backplate, &s_guide_n, &s_guide_a, &s_trace, &counters};
-        for (int k = 0; k < FOVPT_NSQ; k++) { v.push_back(&sq_o[k]); v.push_back(&sq_d[k]); v.push_back(&sq_vis[k]); v.push_back(&sq_occ[k]); }
-        return v;
-    }
-};
-
-#ifndef FOVPT_LANES_DEFAULT
-#define FOVPT_LANES_DEFAULT 2
-#endif
-#define FOVPT_MAX_LANES 4
-#ifndef FOVPT_SETS_SLOT_LIMIT
-#define FOVPT_SETS_SLOT_LIMIT (16ull << 20)    // (~330 B of state and queues per slot and set)
-#endif
-
-struct fovpt_ctx {
-    int device = 0;
-    int num_cus = 256;
-    hipStream_t stream = nullptr;          // main chain: generate, closest-hit traversal, shade
-    hipStream_t shadow_stream = nullptr;   // occlusion rays of every bounce and the resolve: off the critical path
-    // Second LANE (round 3): consecutive jobs alternate between two (main, shadow) stream pairs, so the main chain of job k+1
-    // -- generate, closest-hit, shade, strictly one after the other -- runs BESIDE the main chain of job k instead of behind it:
-    // the launch gaps, ramps and tails of one chain are filled by the other.  Resolves stay in job order (each waits for the
-    // previous job's), and `shadow_stream` remains the one stream every finished frame is ordered on (fovpt_stream()).
-    hipStream_t lane_main[FOVPT_MAX_LANES] = {}, lane_shadow[FOVPT_MAX_LANES] = {};   // [0] = stream / shadow_stream
-    int lanes = FOVPT_LANES_DEFAULT;
-    int chains_default = 1;                // what fovpt_config.chains_per_frame = 0 means (FOVPT_CHAINS)
-    int partition = 1;                     // direction classes in k_shade's appends: 0 never, 1 foveated frames, 2 always (FOVPT_PARTITION)
-    std::string err;
-    fovpt_config cfg;
-    // scene
-    bool has_scene = false;
-    uint64_t scene_id = 0;
-    BvhNode4* nodes = nullptr;
-    TriRec* tris = nullptr;
-    DevBuf tri_tc, meshes, textures;
-    std::vector<void*> tex_pixels;
-    uint32_t num_tris = 0, any_catcher = 0;
-    uint32_t bvh_levels[FOVPT_BVH_MAX_LEVELS + 1] = {};   // the wide tree's levels (BvhBuildResult::level_first), for the refit
-    uint32_t bvh_num_levels = 0;
-    // fovpt_update_vertices.  What fovpt_set_scene keeps on the host: per mesh its first global primitive, first vertex in the
-    // concatenated vertex array and vertex count; per primitive the indices of its three vertices in that array; the positions.
-    // Made on the first update: their device copies (up_vtx 12 B per vertex, up_vidx 12 B per primitive), two pinned staging
-    // buffers for host updates used in turn (each reused once its previous copy has run: ev), and the event a refit records on
-    // fovpt_stream(), which every lane stream waits for before the next job traces the scene (refit_pending).
-    std::vector<uint32_t> mesh_prim0, mesh_vbase, mesh_nv, h_tri_vidx;
-    std::vector<float> h_vtx;
-    DevBuf up_vtx, up_vidx;
-    struct Staging { void* p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } up_stage[2];
-    int up_next = 0;
-    hipEvent_t ev_scene = nullptr;
-    bool refit_pending = false;
-    // probe
-    DevBuf pr_data, pr_pdfx, pr_cdfx, pr_pdfy, pr_cdfy, pr_guidex, pr_guidey, pr_rec;
-    bool guide_ok = false;
-    int guide_w = 0, guide_h = 0;
-    bool rows_identical = false;           // every row of data / pdfX / cdfX equals row 0 bit for bit
-    // frame buffers (resize)
-    DevBuf fb_frame, fb_accum, fb_color, fb_normal, fb_albedo;
-    DevBuf accum_before;                   // accumulate mode, chunked launch: the accum buffer as it was before the launch
-    // multi-GPU gather plan (fovpt_gather_plan): pixel indices grouped by owning rank
-    DevBuf plan_owner, plan_blocks, plan_total, plan_base, plan_idx;
-    std::vector<uint32_t> plan_off;        // host copy: rank r owns plan_idx[plan_off[r] .. plan_off[r + 1])
-    std::string plan_key;                  // what the plan was built for
-    bool use_accum_before = false;
-    // fovpt_denoise / fovpt_reconstruct: the frame last issued with fovpt_render as it was rendered (dn_w x dn_h; 0 x 0: none
-    // since create / resize): its passes, gaze and camera (dn_frame), and the FOV_OFF flag, guides and shard count of its config.
-    // Post-processing reads these, never the caller's current config, gaze or camera.  Then the level map, the ping-pong
-    // filter buffers and the context's own outputs (allocated on first use)
-    int dn_w = 0, dn_h = 0;
-    FrameDev dn_frame{};
-    int32_t dn_uniform = 0, dn_guides = 0, dn_world = 1;
-    DevBuf dn_level, dn_i0, dn_i1, dn_color, dn_rgba;
-    // fovpt_gbuffer / fovpt_reconstruct: the G-buffer's own ray queue, hit records, counters and outputs (never a render state
-    // set: a frame in flight may be using those), and the context's own reconstruction outputs; all allocated on first use
-    DevBuf gb_o, gb_d, gb_hit, gb_cnt, gb_prim, gb_pos, gb_nrm, gb_alb, rc_color, rc_rgba;
-    // fovpt_temporal: two G-buffer sets and two histories (rgb, n), used in turn by consecutive calls (tp_last: the set the
-    // last call wrote), the previous step's camera and size, and the context's own outputs; all allocated on first use.
-    // tp_valid: a previous step exists (dropped by fovpt_temporal_reset, fovpt_resize and fovpt_set_scene)
-    DevBuf tp_prim[2], tp_pos[2], tp_nrm[2], tp_alb[2], tp_hist[2], tp_color, tp_rgba;
-    int tp_last = 0;
-    bool tp_valid = false;
-    int tp_w = 0, tp_h = 0;
-    float tp_eye[3] = {}, tp_U[3] = {}, tp_V[3] = {}, tp_W[3] = {};
-    // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
-    ncclComm_t comm = nullptr;
-    int comm_rank = 0, comm_world = 0;
-    DevBuf comm_packed, comm_gathered;
-    // Wavefront state, several sets used in rotation by consecutive jobs: the tail of job k (its last occlusion
-    // rays and its resolve, on the shadow stream) runs beside the head of job k+1 (generate, camera rays).
-    // Round 4: TWICE as many sets as lanes, so that the job which follows job k on the same lane (job k + lanes) does not
-    // wait for job k's resolve before it may overwrite the path state: its main chain starts as soon as job k's has ended,
-    // and k's tail runs beside it.  (What a 1/N shard of a frame needs: its launches are short, and last occlusion launch +
-    // resolve were a third of a lane's cycle.)
-    StateSet set[2 * FOVPT_MAX_LANES];
-    unsigned nsets = 4;                    // sets in rotation for ordinary jobs = 2 * lanes (FOVPT_SETS: 2 .. 2 * FOVPT_MAX_LANES)
-    unsigned last_set = 0;                 // the set the most recent job used
-    unsigned jobs = 0;                     // jobs issued so far; job j runs on lane j % lanes
-    int grid = 2048, grid_trace = 2048, grid_shadow = 1024, grid_shade = 1024;
-    int spread_occlusion = 1;              // sharded frames: one occlusion launch of a first-lane job runs on the second lane's shadow stream (FOVPT_SPREAD_OCCLUSION)
-    int async_last_shade = FOVPT_ASYNC_LAST_SHADE_DEFAULT;   // 1: the last shading launch of a job runs on the shadow stream (see run_job)
-    uint64_t slot_budget = 64ull << 20;    // sample slots per wavefront job (~330 B of state and queues each and per set; jobs above FOVPT_SETS_SLOT_LIMIT rotate through one set per lane)
-    // stats
-    fovpt_stats stats;
-    std::vector<EventPair> pending;
-    std::vector<hipEvent_t> free_events;
-};
-
-namespace {
-
-int fail(fovpt_ctx* c, int code, const char* fmt, ...);
-int sync_all(fovpt_ctx* c);
 
 int fail(fovpt_ctx* c, int code, const char* fmt, ...)
 {
@@ -187,8 +36,6 @@ int fail(fovpt_ctx* c, int code, const char* fmt, ...)
     return code;
 }
 
-#define HIPCHK(c, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail((c), FOVPT_E_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 int sync_all(fovpt_ctx* c)
 {
     for (int l = 0; l < FOVPT_MAX_LANES; l++) {
@@ -198,6 +45,28 @@ int sync_all(fovpt_ctx* c)
     if (c->shadow_stream) HIPCHK(c, hipStreamSynchronize(c->shadow_stream));      // last: the resolves wait for the lanes
     return FOVPT_OK;
 }
+
+// What the traversal and shading kernels see of the scene.
+SceneView scene_view(const fovpt_ctx* c)
+{
+    SceneView sc;
+    sc.nodes = c->nodes; sc.tris = c->tris; sc.tri_tc = (const float2*)c->tri_tc.p;
+    sc.meshes = (const MeshDev*)c->meshes.p; sc.textures = (const TexDev*)c->textures.p;
+    sc.num_tris = c->num_tris; sc.any_catcher = c->any_catcher;
+    sc.tri_off = (uint32_t)((const char*)c->tris - (const char*)c->nodes);
+    sc.num_nodes = c->stats.num_bvh_nodes;
+    return sc;
+}
+
+// lp's camera into fd.eye / U / V / W
+void set_camera(FrameDev& fd, const fovpt_launch_params* lp)
+{
+    const fovpt_float3* cam[4] = {&lp->camera.eye, &lp->camera.U, &lp->camera.V, &lp->camera.W};
+    float* dst[4] = {fd.eye, fd.U, fd.V, fd.W};
+    for (int k = 0; k < 4; k++) { dst[k][0] = cam[k]->x; dst[k][1] = cam[k]->y; dst[k][2] = cam[k]->z; }
+}
+
+namespace {
 
 fovpt_config default_config()
 {
@@ -213,6 +82,16 @@ fovpt_config default_config()
     return c;
 }
 
+// An integer knob of the environment: *dst = its value if the variable is set and lies in lo .. hi (atoi: text that is no number reads as 0)
+bool env_int(const char* name, int lo, int hi, int* dst)
+{
+    const char* s = getenv(name);
+    const int v = s ? atoi(s) : 0;
+    if (!s || v < lo || v > hi) return false;
+    *dst = v;
+    return true;
+}
+
 hipEvent_t get_event(fovpt_ctx* c)
 {
     if (!c->free_events.empty()) { hipEvent_t e = c->free_events.back(); c->free_events.pop_back(); return e; }
@@ -222,8 +101,8 @@ hipEvent_t get_event(fovpt_ctx* c)
 }
 
 struct Timed {
-    fovpt_ctx* c; int kind; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-    Timed(fovpt_ctx* c_, int k, hipStream_t s = nullptr) : c(c_), kind(k), st(s ? s : c_->stream)
+    fovpt_ctx* c; TimedKind kind; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
+    Timed(fovpt_ctx* c_, TimedKind k, hipStream_t s = nullptr) : c(c_), kind(k), st(s ? s : c_->stream)
     {
         if (c->cfg.profile == 2) (void)sync_all(c);   // the kernel runs alone
         if (c->cfg.profile) {
@@ -245,11 +124,11 @@ void drain_events(fovpt_ctx* c)
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
             switch (p.kind) {
-            case 0: c->stats.ms_generate += ms; break;
-            case 1: c->stats.ms_trace += ms; c->stats.n_trace_launches++; break;
-            case 2: c->stats.ms_shade += ms; break;
-            case 3: c->stats.ms_shadow += ms; c->stats.n_shadow_launches++; break;
-            case 4: c->stats.ms_resolve += ms; break;
+            case T_GENERATE: c->stats.ms_generate += ms; break;
+            case T_TRACE: c->stats.ms_trace += ms; c->stats.n_trace_launches++; break;
+            case T_SHADE: c->stats.ms_shade += ms; break;
+            case T_SHADOW: c->stats.ms_shadow += ms; c->stats.n_shadow_launches++; break;
+            case T_RESOLVE: c->stats.ms_resolve += ms; break;
             }
         }
         c->free_events.push_back(p.a); c->free_events.push_back(p.b);
@@ -302,18 +181,26 @@ int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipSt
     return FOVPT_OK;
 }
 
-// What the traversal and shading kernels see of the scene.
-SceneView scene_view(const fovpt_ctx* c)
+// What the kernels see of a state set: its path state (the guide pointers null: run_job sets them under write_guides) ...
+PathState path_state(const fovpt_ctx* c, const StateSet& S)
 {
-    SceneView sc;
-    sc.nodes = c->nodes; sc.tris = c->tris; sc.tri_tc = (const float2*)c->tri_tc.p;
-    sc.meshes = (const MeshDev*)c->meshes.p; sc.textures = (const TexDev*)c->textures.p;
-    sc.num_tris = c->num_tris; sc.any_catcher = c->any_catcher;
-    sc.tri_off = (uint32_t)((const char*)c->tris - (const char*)c->nodes);
-    sc.num_nodes = c->stats.num_bvh_nodes;
-    return sc;
+    PathState ps;
+    memset(&ps, 0, sizeof(ps));
+    ps.thr = (float4*)S.s_thr.p; ps.rng = (uint4*)S.s_rng.p; ps.hit = (float4*)S.s_hit.p; ps.rad = (float4*)S.s_rad.p;
+    ps.stride = (size_t)c->cfg.max_depth; ps.alpha = (float4*)S.s_alpha.p; ps.backplate = (float4*)S.s_backplate.p;
+#if FOVPT_V_STEPSTAT
+    ps.trace = (uint4*)S.s_trace.p;
+#endif
+    return ps;
 }
 
+// ... and its k-th shadow queue
+ShadowQueue shadow_queue(const StateSet& S, int k)
+{
+    ShadowQueue sq;
+    sq.o = (float4*)S.sq_o[k].p; sq.d = (float4*)S.sq_d[k].p; sq.val_vis = (float4*)S.sq_vis[k].p; sq.val_occ = (float4*)S.sq_occ[k].p;
+    return sq;
+}
 
 int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame);
 
@@ -408,9 +295,7 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     fd.npass = npass;
     fd.w = lp->frame.size.x; fd.h = lp->frame.size.y;
     fd.cx = lp->frame.c.x; fd.cy = lp->frame.c.y;
-    const fovpt_float3* cam[4] = {&lp->camera.eye, &lp->camera.U, &lp->camera.V, &lp->camera.W};
-    float* dst[4] = {fd.eye, fd.U, fd.V, fd.W};
-    for (int k = 0; k < 4; k++) { dst[k][0] = cam[k]->x; dst[k][1] = cam[k]->y; dst[k][2] = cam[k]->z; }
+    set_camera(fd, lp);
     fd.probe = lp->probe;
     // the guide tables belong to the probe this context uploaded; a caller-supplied foreign probe is searched plainly
     const bool own_probe = c->guide_ok && lp->probe.cdfValuesX == (float*)c->pr_cdfx.p && lp->probe.cdfValuesY == (float*)c->pr_cdfy.p
@@ -433,7 +318,7 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     fd.max_depth = c->cfg.max_depth;
     fd.accumulate = c->cfg.accumulate;
     fd.options = c->cfg.options;
-    fd.partition = (c->partition == 2 || (c->partition == 1 && !c->cfg.uniform)) ? 1 : 0;
+    fd.partition = !c->cfg.uniform;      // direction classes in k_shade's appends: foveated frames gain, uniform ones lose
     fd.rank = c->cfg.rank; fd.world = c->cfg.world < 1 ? 1 : c->cfg.world;
     fd.tile_w = c->cfg.tile_w > 0 ? c->cfg.tile_w : 8; fd.tile_h = c->cfg.tile_h > 0 ? c->cfg.tile_h : 4;
 
@@ -479,20 +364,10 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     c->last_set = set_index;
     S.used = true;
 
-    PathState ps;
-    ps.thr = (float4*)S.s_thr.p;
-    ps.rng = (uint4*)S.s_rng.p; ps.hit = (float4*)S.s_hit.p; ps.rad = (float4*)S.s_rad.p; ps.stride = (size_t)c->cfg.max_depth;
-    ps.alpha = (float4*)S.s_alpha.p; ps.backplate = (float4*)S.s_backplate.p;
-    ps.guide_n = c->cfg.write_guides ? (float4*)S.s_guide_n.p : nullptr;
-    ps.guide_a = c->cfg.write_guides ? (float4*)S.s_guide_a.p : nullptr;
-#if FOVPT_V_STEPSTAT
-    ps.trace = (uint4*)S.s_trace.p;
-#endif
+    PathState ps = path_state(c, S);
+    if (c->cfg.write_guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
     ShadowQueue sq[FOVPT_NSQ];
-    for (int k = 0; k < FOVPT_NSQ; k++) {
-        sq[k].o = (float4*)S.sq_o[k].p; sq[k].d = (float4*)S.sq_d[k].p;
-        sq[k].val_vis = (float4*)S.sq_vis[k].p; sq[k].val_occ = (float4*)S.sq_occ[k].p;
-    }
+    for (int k = 0; k < FOVPT_NSQ; k++) sq[k] = shadow_queue(S, k);
     const SceneView sc = scene_view(c);
     Counters* cnt = (Counters*)S.counters.p;
     // (the queue counters are zero: at allocation, and again by the resolve of the set's previous job)
@@ -510,15 +385,11 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     // Every radiance cell has one writer, so the only joins are: shade(it+2) reuses the shadow queue
     // buffer of bounce it, and resolve needs everything -- it runs on the shadow stream, behind the last
     // occlusion launch (which waited for the last shade), so the main chain is free for the next job.
-    // The LAST shading launch of a job feeds nothing on the main chain (no closest-hit launch follows it): with
-    // async_last_shade it runs on the shadow stream, in front of the last occlusion launch and the resolve, so the main stream
-    // is free for the next job's generate and camera rays one shading launch earlier.
-    const bool tail_async = c->async_last_shade != 0;
     // Sharded frames (world > 1): the completion stream -- the first lane's shadow stream -- carries every job's resolve (whose
     // writer search and clearing cover the whole frame on every rank) on top of that lane's occlusion launches and is then as
     // long as the main chains (kernel trace, round 4).  One occlusion launch of a first-lane job moves to the second lane's
     // shadow stream: occlusion launches depend on their shading launch only, and the resolve waits for all of them.
-    int spread_it = (c->spread_occlusion && fd.world > 1 && lanes > 1u && lane == 0u && !two_chains && !chunked && !tail_async
+    int spread_it = (c->spread_occlusion && fd.world > 1 && lanes > 1u && lane == 0u && !two_chains && !chunked
                            && c->cfg.max_depth >= 2) ? (c->spread_occlusion == 2 ? 1 : -2) : -1;      // -2: the job's LAST one (below)
     // Which one: a launch is queued when the job is issued and holds the stream's later entries back until its own shading launch
     // has run.  The job's last occlusion launch is the smallest and the resolve waits for it anyway -- but behind it the other
@@ -528,55 +399,46 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     if (spread_it == -2) spread_it = iters <= nsq ? iters - 1 : 1;
     // One chain: the sample slots [slot_begin, slot_end) through the queue shards of `sel` (0: all eight; 1 / 2: one half), with
     // 1 / div of the usual grids.
-    auto issue_chain = [&](hipStream_t st, hipStream_t ss, uint32_t sel, uint32_t slot_begin, uint32_t slot_end, int div,
-                           hipEvent_t* ev_shade, hipEvent_t* ev_shadow, hipEvent_t ev_last_closest) -> int {
+    auto issue_chain = [&](hipStream_t st, hipStream_t ss, uint32_t sel, uint32_t slot_begin, uint32_t slot_end, int div, const ChainEvents& ev) -> int {
         RayQueue qa, qb;
         qa.o = (float4*)S.q_o[0].p; qa.d = (float4*)S.q_d[0].p;
         qb.o = (float4*)S.q_o[1].p; qb.d = (float4*)S.q_d[1].p;
         const int g_gen = c->grid / div, g_trace = c->grid_trace / div, g_shadow = c->grid_shadow / div, g_shade = c->grid_shade / div;
-        { Timed t(c, 0, st); fovpt_launch_generate(st, fd, ps, qa, cap, cnt, slot_begin, slot_end, g_gen, sel); }
-        { Timed t(c, 1, st); fovpt_launch_traverse(st, sc, ps, qa, sq[0], cap, cnt, 0, -1, g_trace, (tail_async && iters == 1) ? ev_last_closest : nullptr, sel); }
+        { Timed t(c, T_GENERATE, st); fovpt_launch_generate(st, fd, ps, qa, cap, cnt, slot_begin, slot_end, g_gen, sel); }
+        { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, sc, ps, qa, sq[0], cap, cnt, 0, -1, g_trace, nullptr, sel); }
         for (int it = 0; it < iters; it++) {
-            const bool last = it + 1 == iters;
-            if (last && tail_async) {
-                HIPCHK(c, hipStreamWaitEvent(ss, ev_last_closest, 0));      // (the shadow queue it writes was read by occlusion(it - nsq): earlier on this stream)
-                { Timed t(c, 2, ss); fovpt_launch_shade(ss, fd, sc, ps, qa, qb, sq[it % nsq], cap, cnt, it, g_shade, nullptr, sel); }
-            } else {
-                if (it >= nsq) HIPCHK(c, hipStreamWaitEvent(st, ev_shadow[it - nsq], 0));
-                // the events ride on the kernels' own completion signals (hipExtLaunchKernel): a separate
-                // hipEventRecord would put a marker packet between shade(it) and closest(it+1), ~6 us on the critical path
-                { Timed t(c, 2, st); fovpt_launch_shade(st, fd, sc, ps, qa, qb, sq[it % nsq], cap, cnt, it, g_shade, ev_shade[it], sel); }
-                HIPCHK(c, hipStreamWaitEvent(ss, ev_shade[it], 0));
-            }
-            if (it == spread_it) {
-                // (a sharded frame on the first lane: this bounce's occlusion rays run on the OTHER lane's shadow stream -- the
-                // completion stream carries every job's resolve as well; the resolve below waits for it)
-                HIPCHK(c, hipStreamWaitEvent(c->lane_shadow[1], ev_shade[it], 0));
-                { Timed t(c, 3, c->lane_shadow[1]); fovpt_launch_traverse(c->lane_shadow[1], sc, ps, qb, sq[it % nsq], cap, cnt, -1, it, g_shadow, ev_shadow[it], sel); }
-            } else
-            { Timed t(c, 3, ss); fovpt_launch_traverse(ss, sc, ps, qb, sq[it % nsq], cap, cnt, -1, it, g_shadow, ev_shadow[it], sel); }
-            if (!last) { Timed t(c, 1, st); fovpt_launch_traverse(st, sc, ps, qb, sq[0], cap, cnt, it + 1, -1, g_trace, (tail_async && it + 2 == iters) ? ev_last_closest : nullptr, sel); }
+            if (it >= nsq) HIPCHK(c, hipStreamWaitEvent(st, ev.shadow[it - nsq], 0));
+            // the events ride on the kernels' own completion signals (hipExtLaunchKernel): a separate
+            // hipEventRecord would put a marker packet between shade(it) and closest(it+1), ~6 us on the critical path
+            { Timed t(c, T_SHADE, st); fovpt_launch_shade(st, fd, sc, ps, qa, qb, sq[it % nsq], cap, cnt, it, g_shade, ev.shade[it], sel); }
+            // (a sharded frame on the first lane: bounce spread_it's occlusion rays run on the OTHER lane's shadow stream -- the
+            // completion stream carries every job's resolve as well; the resolve below waits for it)
+            const hipStream_t so = it == spread_it ? c->lane_shadow[1] : ss;
+            HIPCHK(c, hipStreamWaitEvent(ss, ev.shade[it], 0));
+            if (so != ss) HIPCHK(c, hipStreamWaitEvent(so, ev.shade[it], 0));
+            { Timed t(c, T_SHADOW, so); fovpt_launch_traverse(so, sc, ps, qb, sq[it % nsq], cap, cnt, -1, it, g_shadow, ev.shadow[it], sel); }
+            if (it + 1 < iters) { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, sc, ps, qb, sq[0], cap, cnt, it + 1, -1, g_trace, nullptr, sel); }
             const RayQueue tmp = qa; qa = qb; qb = tmp;
         }
         return FOVPT_OK;
     };
     if (two_chains) {
         const uint32_t half = (uint32_t)(slots / 2 / FOVPT_BLOCK * FOVPT_BLOCK);      // (a whole number of 256-slot block iterations)
-        rc = issue_chain(c->lane_main[0], c->lane_shadow[0], 1u, 0u, half, 2, S.ev_shade, S.ev_shadow, S.ev_last_closest);
+        rc = issue_chain(c->lane_main[0], c->lane_shadow[0], 1u, 0u, half, 2, S.chain[0]);
         if (rc) return rc;
-        rc = issue_chain(c->lane_main[1], c->lane_shadow[1], 2u, half, (uint32_t)slots, 2, S.ev_shade2, S.ev_shadow2, S.ev_last_closest2);
+        rc = issue_chain(c->lane_main[1], c->lane_shadow[1], 2u, half, (uint32_t)slots, 2, S.chain[1]);
         if (rc) return rc;
-        HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.ev_shadow2[iters - 1], 0));      // (the first chain's last occlusion launch IS on shadow_stream)
+        HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[1].shadow[iters - 1], 0));      // (the first chain's last occlusion launch IS on shadow_stream)
     } else {
-        rc = issue_chain(st, ss, 0u, 0u, (uint32_t)slots, 1, S.ev_shade, S.ev_shadow, S.ev_last_closest);
+        rc = issue_chain(st, ss, 0u, 0u, (uint32_t)slots, 1, S.chain[0]);
         if (rc) return rc;
         // Every resolve runs on shadow_stream, whatever the lane: in job order (a later job's pixels overwrite, or blend with, an
         // earlier one's), behind whatever the caller has queued on fovpt_stream() since the previous frame, and in front of what it
         // queues next.  A job of the second lane joins it behind its last occlusion launch (which waited for its last shade).
-        if (ss != c->shadow_stream) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.ev_shadow[iters - 1], 0));
-        if (spread_it >= 0 && spread_it < iters) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.ev_shadow[spread_it], 0));
+        if (ss != c->shadow_stream) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[0].shadow[iters - 1], 0));
+        if (spread_it >= 0 && spread_it < iters) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[0].shadow[spread_it], 0));
     }
-    { Timed t(c, 4, c->shadow_stream); fovpt_launch_resolve(c->shadow_stream, fd, ps, cnt, S.ev_done); }
+    { Timed t(c, T_RESOLVE, c->shadow_stream); fovpt_launch_resolve(c->shadow_stream, fd, ps, cnt, S.ev_done); }
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }
@@ -647,122 +509,6 @@ int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P)
     return 3;
 }
 
-// ---- post-processing of the rendered frame: fovpt_denoise (denoise.hip), fovpt_gbuffer / fovpt_reconstruct (reconstruct.hip) --
-// an edge-stopping scale of fovpt_denoise / fovpt_reconstruct: inside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX], so that 1 / sigma^2
-// is a normal float and the denoiser's colour scale (1 / sigma^2) * 4^(FOVPT_DENOISE_MAX_ITERATIONS - 1) / 1e-4 stays finite
-// (an infinite scale makes the centre tap 0 * inf: every weight 0, the output 0 / 0)
-bool sigma_ok(float v) { return v >= FOVPT_SIGMA_MIN && v <= FOVPT_SIGMA_MAX; }
-
-// lp's camera into fd.eye / U / V / W (the rays of a G-buffer)
-void set_camera(FrameDev& fd, const fovpt_launch_params* lp)
-{
-    const fovpt_float3* cam[4] = {&lp->camera.eye, &lp->camera.U, &lp->camera.V, &lp->camera.W};
-    float* dst[4] = {fd.eye, fd.U, fd.V, fd.W};
-    for (int k = 0; k < 4; k++) { dst[k][0] = cam[k]->x; dst[k][1] = cam[k]->y; dst[k][2] = cam[k]->z; }
-}
-
-// The passes fovpt_render ran for the frame lp describes under cfg, whole (rows 0 .. gh) and on one rank: what
-// find_last_writer needs to give every pixel its writing pass and launch index; and lp's camera.  Computed on a copy: the
-// caller's parameters stay as they are.  fovpt_render keeps this for the frame it issued (fovpt_ctx::dn_frame).
-void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd)
-{
-    fovpt_launch_params L = *lp;
-    PassDev P[FOVPT_MAX_PASSES];
-    memset(&fd, 0, sizeof(fd));
-    fd.npass = frame_passes(cfg, L, P);
-    for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
-    fd.w = L.frame.size.x; fd.h = L.frame.size.y;
-    fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
-    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
-    set_camera(fd, lp);
-}
-
-// the G-buffer's buffers for n pixels (the counters once: k_gbuffer_rays rewrites the queue sizes it uses on every call)
-int reserve_gbuffer(fovpt_ctx* c, size_t n)
-{
-    const bool fresh = c->gb_cnt.p == nullptr;
-    HIPCHK(c, c->gb_o.reserve(n * 16)); HIPCHK(c, c->gb_d.reserve(n * 16)); HIPCHK(c, c->gb_hit.reserve(n * 16));
-    HIPCHK(c, c->gb_prim.reserve(n * 4)); HIPCHK(c, c->gb_pos.reserve(n * 16)); HIPCHK(c, c->gb_nrm.reserve(n * 16)); HIPCHK(c, c->gb_alb.reserve(n * 16));
-    HIPCHK(c, c->gb_cnt.reserve(sizeof(Counters)));
-    if (fresh) HIPCHK(c, hipMemset(c->gb_cnt.p, 0, sizeof(Counters)));
-    return FOVPT_OK;
-}
-
-// fovpt_temporal's G-buffer sets, histories and outputs for n pixels
-int reserve_temporal(fovpt_ctx* c, size_t n)
-{
-    for (int k = 0; k < 2; k++) {
-        HIPCHK(c, c->tp_prim[k].reserve(n * 4)); HIPCHK(c, c->tp_pos[k].reserve(n * 16)); HIPCHK(c, c->tp_nrm[k].reserve(n * 16));
-        HIPCHK(c, c->tp_alb[k].reserve(n * 16)); HIPCHK(c, c->tp_hist[k].reserve(n * 16));
-    }
-    HIPCHK(c, c->tp_color.reserve(n * 16)); HIPCHK(c, c->tp_rgba.reserve(n * 4));
-    return FOVPT_OK;
-}
-
-GBufferDev temporal_set(fovpt_ctx* c, int k)
-{
-    GBufferDev g;
-    g.prim = (uint32_t*)c->tp_prim[k].p; g.pos = (float4*)c->tp_pos[k].p; g.nrm = (float4*)c->tp_nrm[k].p; g.alb = (float4*)c->tp_alb[k].p;
-    return g;
-}
-
-// The rows of [U V W]^-1 (U, V, W the columns), in binary64: det = U . (V x W), rows (V x W) / det, (W x U) / det,
-// (U x V) / det, each entry rounded to binary32.  false: det is 0 or not finite.
-bool camera_inverse(const float* U, const float* V, const float* W, float* inv)
-{
-    auto cross = [](const double* a, const double* b, double* r) {
-        r[0] = a[1] * b[2] - a[2] * b[1]; r[1] = a[2] * b[0] - a[0] * b[2]; r[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    const double u[3] = {U[0], U[1], U[2]}, v[3] = {V[0], V[1], V[2]}, w[3] = {W[0], W[1], W[2]};
-    double r[3][3];
-    cross(v, w, r[0]); cross(w, u, r[1]); cross(u, v, r[2]);
-    const double det = (u[0] * r[0][0] + u[1] * r[0][1]) + u[2] * r[0][2];
-    if (det == 0.0 || !std::isfinite(det)) return false;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) inv[3 * i + j] = (float)(r[i][j] / det);
-    return true;
-}
-
-// Enqueues the G-buffer of lp's frame.size seen by view's camera (view.eye / U / V / W) on fovpt_stream(): one ray per pixel,
-// traced by the production closest-hit k_traverse (so a ray gets the (prim, t, u, v) fovpt_debug_trace returns for it), then
-// the per-pixel outputs: into target's buffers (frame.size entries each), or with target null into the ones fovpt_gbuffer
-// hands out.  The ray queue, hit records and counters are shared: every use is ordered on the same stream.
-int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
-                    const GBufferDev* target = nullptr)
-{
-    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene (traversable %llu, current %llu)", who,
-                                                                     (unsigned long long)lp->traversable, (unsigned long long)c->scene_id);
-#if FOVPT_V_STEPSTAT
-    return fail(c, FOVPT_E_INVALID, "%s: not available in a diagnostic (FOVPT_V_STEPSTAT) build", who);
-#endif
-    const int w = lp->frame.size.x, h = lp->frame.size.y;
-    if (w <= 0 || h <= 0) return fail(c, FOVPT_E_INVALID, "%s: frame size %d x %d", who, w, h);
-    const size_t n = (size_t)w * (size_t)h;
-    if (n >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, w, h);
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }
-    FrameDev fd;
-    memset(&fd, 0, sizeof(fd));
-    fd.w = w; fd.h = h;
-    memcpy(fd.eye, view.eye, sizeof(fd.eye)); memcpy(fd.U, view.U, sizeof(fd.U));
-    memcpy(fd.V, view.V, sizeof(fd.V)); memcpy(fd.W, view.W, sizeof(fd.W));
-    RayQueue q; q.o = (float4*)c->gb_o.p; q.d = (float4*)c->gb_d.p;
-    PathState ps;
-    memset(&ps, 0, sizeof(ps));
-    ps.hit = (float4*)c->gb_hit.p;                                   // all a closest-hit launch writes
-    ShadowQueue sq;
-    memset(&sq, 0, sizeof(sq));
-    Counters* cnt = (Counters*)c->gb_cnt.p;
-    if (target) g = *target;
-    else { g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = (float4*)c->gb_nrm.p; g.alb = (float4*)c->gb_alb.p; }
-    hipStream_t st = c->shadow_stream;
-    fovpt_launch_gbuffer_rays(st, fd, q, cnt);
-    fovpt_launch_traverse(st, scene_view(c), ps, q, sq, (uint32_t)n, cnt, 0, -1, c->grid_trace);   // shard 0 holds all n rays
-    fovpt_launch_gbuffer_fill(st, fd, scene_view(c), q, ps.hit, g);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
-}
-
 // The hierarchy over d_flat (9 floats per triangle) on stream st, as fovpt_set_scene builds it: FOVPT_BVH, FOVPT_SPLIT, and a
 // second build without reinsertion when reinsertion made the tree too deep; *ms = its device time.  On success br holds the
 // new hierarchy (adopt_hierarchy takes it); on failure nothing is kept.
@@ -803,6 +549,45 @@ int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uin
     return FOVPT_OK;
 }
 
+// What fovpt_set_probe and fovpt_set_probe_data share once the probe's arrays are on the device: whether the CDFs (host copies
+// cdfX, cdfY) are sorted, the guide tables and packed records if so, whether all rows are alike (texels, cdfX, and pdfX where
+// the caller has it on the host), and the caller's fovpt_probe.
+int finish_probe(fovpt_ctx* c, int width, int height, const fovpt_float4* data, const float* pdfX, const float* cdfX, const float* cdfY,
+                 const fovpt_float3* offset, fovpt_probe* out)
+{
+    const size_t n = (size_t)width * height;
+    // guide tables for the two CDF searches of ProbeSample: only valid on non-decreasing CDFs
+    bool sorted = true;
+    for (int row = 0; row < height && sorted; row++) {
+        const float* cr = cdfX + (size_t)row * width;
+        for (int k = 1; k < width; k++) if (!(cr[k] >= cr[k - 1])) { sorted = false; break; }
+    }
+    for (int k = 1; k < height && sorted; k++) if (!(cdfY[k] >= cdfY[k - 1])) sorted = false;
+    c->guide_ok = false;
+    if (sorted) {
+        HIPCHK(c, c->pr_guidex.reserve((size_t)height * (width + 2) * 4));
+        HIPCHK(c, c->pr_guidey.reserve((size_t)(height + 2) * 4));
+        fovpt_launch_build_guide(c->stream, (const float*)c->pr_cdfx.p, width, height, (uint32_t*)c->pr_guidex.p);
+        fovpt_launch_build_guide(c->stream, (const float*)c->pr_cdfy.p, height, 1, (uint32_t*)c->pr_guidey.p);
+        HIPCHK(c, c->pr_rec.reserve(n * 32));
+        fovpt_launch_probe_records(c->stream, n, (const float*)c->pr_cdfx.p, (const float*)c->pr_pdfx.p, (const float4*)c->pr_data.p, (float4*)c->pr_rec.p);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->guide_ok = true;
+    }
+    c->guide_w = width; c->guide_h = height;
+    c->rows_identical = true;
+    for (int row = 1; row < height && c->rows_identical; row++)
+        if (memcmp(data + (size_t)row * width, data, (size_t)width * 16) || memcmp(cdfX + (size_t)row * width, cdfX, (size_t)width * 4)
+            || (pdfX && memcmp(pdfX + (size_t)row * width, pdfX, (size_t)width * 4))) c->rows_identical = false;
+    memset(out, 0, sizeof(*out));
+    out->width = width; out->height = height;
+    out->data = (fovpt_float4*)c->pr_data.p;
+    out->pdfValuesX = (float*)c->pr_pdfx.p; out->cdfValuesX = (float*)c->pr_cdfx.p;
+    out->pdfValuesY = (float*)c->pr_pdfy.p; out->cdfValuesY = (float*)c->pr_cdfy.p;
+    if (offset) out->offset = *offset;
+    return FOVPT_OK;
+}
+
 // the hierarchy build_hierarchy made becomes the scene's, with its scene facts
 void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms)
 {
@@ -815,6 +600,48 @@ void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms)
 }
 
 }  // namespace
+
+// The passes fovpt_render ran for the frame lp describes under cfg, whole (rows 0 .. gh) and on one rank: what
+// find_last_writer needs to give every pixel its writing pass and launch index; and lp's camera.  Computed on a copy: the
+// caller's parameters stay as they are.  fovpt_render keeps this for the frame it issued (fovpt_ctx::dn_frame).
+void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd)
+{
+    fovpt_launch_params L = *lp;
+    PassDev P[FOVPT_MAX_PASSES];
+    memset(&fd, 0, sizeof(fd));
+    fd.npass = frame_passes(cfg, L, P);
+    for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
+    fd.w = L.frame.size.x; fd.h = L.frame.size.y;
+    fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
+    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
+    set_camera(fd, lp);
+}
+
+// Everything a DevBuf member does not own.  The device is idle: fovpt_destroy has synchronised every stream.
+fovpt_ctx::~fovpt_ctx()
+{
+    free_scene(this);
+    for (auto& S : up_stage) {
+        if (S.p) (void)hipHostFree(S.p);
+        if (S.ev) (void)hipEventDestroy(S.ev);
+    }
+    if (ev_scene) (void)hipEventDestroy(ev_scene);
+    for (StateSet& S : set) {
+        for (ChainEvents& ch : S.chain)
+            for (int k = 0; k <= FOVPT_MAX_ITERS; k++) {
+                if (ch.shade[k]) (void)hipEventDestroy(ch.shade[k]);
+                if (ch.shadow[k]) (void)hipEventDestroy(ch.shadow[k]);
+            }
+        if (S.ev_done) (void)hipEventDestroy(S.ev_done);
+    }
+    for (hipEvent_t e : free_events) (void)hipEventDestroy(e);
+    for (int l = 1; l < FOVPT_MAX_LANES; l++) {          // ([0] are stream and shadow_stream)
+        if (lane_main[l]) (void)hipStreamDestroy(lane_main[l]);
+        if (lane_shadow[l]) (void)hipStreamDestroy(lane_shadow[l]);
+    }
+    if (stream) (void)hipStreamDestroy(stream);
+    if (shadow_stream) (void)hipStreamDestroy(shadow_stream);
+}
 
 extern "C" {
 
@@ -837,45 +664,42 @@ int fovpt_create(fovpt_ctx** out, int device)
     c->grid = c->num_cus * 8;                 // generate: 8 blocks of 256 = 32 waves per CU, grid-stride; a multiple of FOVPT_SHARDS
     c->grid_trace = c->num_cus * FOVPT_GRID_PER_CU;   // closest-hit launches, in units of 256 threads (k_traverse's own blocks are FOVPT_TBLOCK threads)
     c->grid_shadow = c->num_cus * FOVPT_GRID_SHADOW_PER_CU;   // occlusion launches (measured best of 2..8 with per-wave ray pools)
-    if (const char* g = getenv("FOVPT_GRID_GEN")) { const int v = atoi(g); if (v > 0 && v <= 64) c->grid = c->num_cus * v; }             // tuning: blocks per CU
-    if (const char* g = getenv("FOVPT_GRID")) { const int v = atoi(g); if (v > 0 && v <= 64) c->grid_trace = c->num_cus * v; }           // tuning: blocks per CU
-    if (const char* g = getenv("FOVPT_GRID_SHADOW")) { const int v = atoi(g); if (v > 0 && v <= 16) c->grid_shadow = c->num_cus * v; }   // tuning: blocks per CU
+    int v = 0;                                // tuning: blocks per CU
+    if (env_int("FOVPT_GRID_GEN", 1, 64, &v)) c->grid = c->num_cus * v;
+    if (env_int("FOVPT_GRID", 1, 64, &v)) c->grid_trace = c->num_cus * v;
+    if (env_int("FOVPT_GRID_SHADOW", 1, 16, &v)) c->grid_shadow = c->num_cus * v;
     c->grid = (c->grid + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;      // shard_capacity() relies on it
     c->grid_trace = (c->grid_trace + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;
     c->grid_shadow = (c->grid_shadow + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;      // the work fetch of k_traverse relies on equal shard groups
     // the shading kernel holds 4 waves per SIMD (104 VGPRs) = 4 blocks per CU; twice the resident number of blocks is
     // measured best (blocks per CU 2 / 3 / 4 / 6 / 8: shading 0.307 / 0.274 / 0.261 / 0.263 / 0.244 ms per C3 frame)
     c->grid_shade = c->num_cus * 8;
-    if (const char* g = getenv("FOVPT_GRID_SHADE")) { const int v = atoi(g); if (v > 0 && v <= 16) c->grid_shade = c->num_cus * v; }     // tuning: blocks per CU
+    if (env_int("FOVPT_GRID_SHADE", 1, 16, &v)) c->grid_shade = c->num_cus * v;
     c->grid_shade = (c->grid_shade + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;
-    if (const char* a = getenv("FOVPT_ASYNC_LAST_SHADE")) c->async_last_shade = atoi(a) != 0;
     if (const char* sb = getenv("FOVPT_SLOT_BUDGET")) { const long long v = atoll(sb); if (v > 0) c->slot_budget = (uint64_t)v; }   // tests: force chunking
     // the main chain is the critical path: give it the higher priority so occlusion waves only fill gaps
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
     e = hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_hi);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->shadow_stream, hipStreamDefault, prio_lo);
-    if (const char* l = getenv("FOVPT_LANES")) { const int v = atoi(l); if (v >= 1 && v <= FOVPT_MAX_LANES) c->lanes = v; }
-    if (const char* l = getenv("FOVPT_PARTITION")) { const int v = atoi(l); if (v >= 0 && v <= 2) c->partition = v; }
-    if (const char* l = getenv("FOVPT_SPREAD_OCCLUSION")) c->spread_occlusion = atoi(l);      // 0 off, 1 the last occlusion launch, 2 the second (A/B)
-    if (const char* l = getenv("FOVPT_CHAINS")) { const int v = atoi(l); if (v == 1 || v == 2) c->chains_default = v; }
-    c->nsets = 2u * (unsigned)c->lanes;
-    if (const char* l = getenv("FOVPT_SETS")) { const int v = atoi(l); if (v >= 2 && v <= 2 * FOVPT_MAX_LANES) c->nsets = (unsigned)v; }
+    (void)env_int("FOVPT_LANES", 1, FOVPT_MAX_LANES, &c->lanes);
+    (void)env_int("FOVPT_SPREAD_OCCLUSION", INT_MIN, INT_MAX, &c->spread_occlusion);      // 0 off, 1 the last occlusion launch, 2 the second (A/B); not range-checked
+    (void)env_int("FOVPT_CHAINS", 1, 2, &c->chains_default);
+    v = 2 * c->lanes;
+    (void)env_int("FOVPT_SETS", 2, 2 * FOVPT_MAX_LANES, &v);
+    c->nsets = (unsigned)v;
     c->lane_main[0] = c->stream; c->lane_shadow[0] = c->shadow_stream;
     for (int l = 1; l < c->lanes; l++) {
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->lane_main[l], hipStreamDefault, prio_hi);
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->lane_shadow[l], hipStreamDefault, prio_lo);
     }
     for (StateSet& S : c->set) {
-        for (int k = 0; k <= FOVPT_MAX_ITERS && e == hipSuccess; k++) {
-            e = hipEventCreateWithFlags(&S.ev_shade[k], hipEventDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_shadow[k], hipEventDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_shade2[k], hipEventDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_shadow2[k], hipEventDefault);
-        }
+        for (ChainEvents& ch : S.chain)
+            for (int k = 0; k <= FOVPT_MAX_ITERS && e == hipSuccess; k++) {
+                e = hipEventCreateWithFlags(&ch.shade[k], hipEventDefault);
+                if (e == hipSuccess) e = hipEventCreateWithFlags(&ch.shadow[k], hipEventDefault);
+            }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_done, hipEventDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_last_closest, hipEventDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_last_closest2, hipEventDefault);
     }
     if (e != hipSuccess) { fovpt_destroy(c); return fail(nullptr, FOVPT_E_DEVICE, "stream/event creation: %s", hipGetErrorString(e)); }
     *out = c;
@@ -888,40 +712,7 @@ void fovpt_destroy(fovpt_ctx* c)
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
     drain_events(c);
-    for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
-    for (StateSet& S : c->set) {
-        for (int k = 0; k <= FOVPT_MAX_ITERS; k++) {
-            if (S.ev_shade[k]) (void)hipEventDestroy(S.ev_shade[k]);
-            if (S.ev_shadow[k]) (void)hipEventDestroy(S.ev_shadow[k]);
-            if (S.ev_shade2[k]) (void)hipEventDestroy(S.ev_shade2[k]);
-            if (S.ev_shadow2[k]) (void)hipEventDestroy(S.ev_shadow2[k]);
-        }
-        if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-        if (S.ev_last_closest) (void)hipEventDestroy(S.ev_last_closest);
-        if (S.ev_last_closest2) (void)hipEventDestroy(S.ev_last_closest2);
-        for (DevBuf* b : S.all()) b->release();
-    }
     (void)fovpt_comm_destroy(c);
-    free_scene(c);
-    DevBuf* bufs[] = {&c->tri_tc, &c->meshes, &c->textures, &c->pr_data, &c->pr_pdfx, &c->pr_cdfx, &c->pr_pdfy, &c->pr_cdfy, &c->pr_guidex, &c->pr_guidey, &c->pr_rec,
-                      &c->fb_frame, &c->fb_accum, &c->fb_color, &c->fb_normal, &c->fb_albedo, &c->accum_before,
-                      &c->plan_owner, &c->plan_blocks, &c->plan_total, &c->plan_base, &c->plan_idx,
-                      &c->comm_packed, &c->comm_gathered, &c->dn_level, &c->dn_i0, &c->dn_i1, &c->dn_color, &c->dn_rgba,
-                      &c->gb_o, &c->gb_d, &c->gb_hit, &c->gb_cnt, &c->gb_prim, &c->gb_pos, &c->gb_nrm, &c->gb_alb, &c->rc_color, &c->rc_rgba,
-                      &c->tp_color, &c->tp_rgba, &c->up_vtx, &c->up_vidx};
-    for (DevBuf* b : bufs) b->release();
-    for (int k = 0; k < 2; k++) { c->tp_prim[k].release(); c->tp_pos[k].release(); c->tp_nrm[k].release(); c->tp_alb[k].release(); c->tp_hist[k].release(); }
-    for (auto& S : c->up_stage) {
-        if (S.p) (void)hipHostFree(S.p);
-        if (S.ev) (void)hipEventDestroy(S.ev);
-    }
-    if (c->ev_scene) (void)hipEventDestroy(c->ev_scene);
-    for (int l = 0; l < FOVPT_MAX_LANES; l++) {
-        if (c->lane_main[l] && c->lane_main[l] != c->stream) (void)hipStreamDestroy(c->lane_main[l]);
-        if (c->lane_shadow[l] && c->lane_shadow[l] != c->shadow_stream) (void)hipStreamDestroy(c->lane_shadow[l]);
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->shadow_stream) (void)hipStreamDestroy(c->shadow_stream);
     delete c;
 }
 
@@ -982,9 +773,9 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
             mesh_of[t] = (uint32_t)m;
         }
     }
-    struct Tmp { void* p = nullptr; ~Tmp() { if (p) (void)hipFree(p); } } t_flat, t_mesh_of;      // freed on every return path
-    HIPCHK(c, hipMalloc(&t_flat.p, flat.size() * 4));
-    HIPCHK(c, hipMalloc(&t_mesh_of.p, mesh_of.size() * 4));
+    DevBuf t_flat, t_mesh_of;
+    HIPCHK(c, t_flat.reserve(flat.size() * 4));
+    HIPCHK(c, t_mesh_of.reserve(mesh_of.size() * 4));
     float* d_flat = (float*)t_flat.p; uint32_t* d_mesh_of = (uint32_t*)t_mesh_of.p;
     HIPCHK(c, hipMemcpy(d_flat, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_mesh_of, mesh_of.data(), mesh_of.size() * 4, hipMemcpyHostToDevice));
@@ -1107,9 +898,9 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
     }
     // FOVPT_UPDATE_REBUILD: fovpt_set_scene's build over the current vertices; the old hierarchy stays if it fails
     const uint32_t ntri = (uint32_t)c->stats.num_triangles;
-    struct Tmp { void* p = nullptr; ~Tmp() { if (p) (void)hipFree(p); } } t_flat, t_mesh_of;
-    HIPCHK(c, hipMalloc(&t_flat.p, (size_t)ntri * 36));
-    HIPCHK(c, hipMalloc(&t_mesh_of.p, (size_t)ntri * 4));
+    DevBuf t_flat, t_mesh_of;
+    HIPCHK(c, t_flat.reserve((size_t)ntri * 36));
+    HIPCHK(c, t_mesh_of.reserve((size_t)ntri * 4));
     std::vector<uint32_t> mesh_of((size_t)ntri);
     for (int m = 0; m < nmesh; m++) {
         const uint32_t end = m + 1 < nmesh ? c->mesh_prim0[m + 1] : ntri;
@@ -1145,36 +936,7 @@ int fovpt_set_probe(fovpt_ctx* c, int width, int height, const fovpt_float4* dat
     HIPCHK(c, hipMemcpy(c->pr_pdfy.p, pdfY, (size_t)height * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->pr_cdfy.p, cdfY, (size_t)height * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->pr_data.p, data, n * 16, hipMemcpyHostToDevice));
-    // guide tables for the two CDF searches of ProbeSample: only valid on non-decreasing CDFs
-    bool sorted = true;
-    for (int row = 0; row < height && sorted; row++) {
-        const float* cr = cdfX + (size_t)row * width;
-        for (int k = 1; k < width; k++) if (!(cr[k] >= cr[k - 1])) { sorted = false; break; }
-    }
-    for (int k = 1; k < height && sorted; k++) if (!(cdfY[k] >= cdfY[k - 1])) sorted = false;
-    c->guide_ok = false;
-    if (sorted) {
-        HIPCHK(c, c->pr_guidex.reserve((size_t)height * (width + 2) * 4));
-        HIPCHK(c, c->pr_guidey.reserve((size_t)(height + 2) * 4));
-        fovpt_launch_build_guide(c->stream, (const float*)c->pr_cdfx.p, width, height, (uint32_t*)c->pr_guidex.p);
-        fovpt_launch_build_guide(c->stream, (const float*)c->pr_cdfy.p, height, 1, (uint32_t*)c->pr_guidey.p);
-        HIPCHK(c, c->pr_rec.reserve(n * 32));
-        fovpt_launch_probe_records(c->stream, n, (const float*)c->pr_cdfx.p, (const float*)c->pr_pdfx.p, (const float4*)c->pr_data.p, (float4*)c->pr_rec.p);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->guide_ok = true;
-    }
-    c->guide_w = width; c->guide_h = height;
-    c->rows_identical = true;
-    for (int row = 1; row < height && c->rows_identical; row++)
-        if (memcmp(data + (size_t)row * width, data, (size_t)width * 16) || memcmp(pdfX + (size_t)row * width, pdfX, (size_t)width * 4)
-            || memcmp(cdfX + (size_t)row * width, cdfX, (size_t)width * 4)) c->rows_identical = false;
-    memset(out, 0, sizeof(*out));
-    out->width = width; out->height = height;
-    out->data = (fovpt_float4*)c->pr_data.p;
-    out->pdfValuesX = (float*)c->pr_pdfx.p; out->cdfValuesX = (float*)c->pr_cdfx.p;
-    out->pdfValuesY = (float*)c->pr_pdfy.p; out->cdfValuesY = (float*)c->pr_cdfy.p;
-    if (offset) out->offset = *offset;
-    return FOVPT_OK;
+    return finish_probe(c, width, height, data, pdfX, cdfX, cdfY, offset, out);
 }
 
 int fovpt_set_probe_data(fovpt_ctx* c, int width, int height, const fovpt_float4* data, const fovpt_float3* offset, fovpt_probe* out)
@@ -1198,36 +960,8 @@ int fovpt_set_probe_data(fovpt_ctx* c, int width, int height, const fovpt_float4
     row_total.release();
     HIPCHK(c, hipMemcpy(hx.data(), c->pr_cdfx.p, n * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(hy.data(), c->pr_cdfy.p, (size_t)height * 4, hipMemcpyDeviceToHost));
-    bool sorted = true;
-    for (int row = 0; row < height && sorted; row++) {
-        const float* cr = hx.data() + (size_t)row * width;
-        for (int k = 1; k < width; k++) if (!(cr[k] >= cr[k - 1])) { sorted = false; break; }
-    }
-    for (int k = 1; k < height && sorted; k++) if (!(hy[k] >= hy[k - 1])) sorted = false;
-    c->guide_ok = false;
-    if (sorted) {
-        HIPCHK(c, c->pr_guidex.reserve((size_t)height * (width + 2) * 4));
-        HIPCHK(c, c->pr_guidey.reserve((size_t)(height + 2) * 4));
-        fovpt_launch_build_guide(c->stream, (const float*)c->pr_cdfx.p, width, height, (uint32_t*)c->pr_guidex.p);
-        fovpt_launch_build_guide(c->stream, (const float*)c->pr_cdfy.p, height, 1, (uint32_t*)c->pr_guidey.p);
-        HIPCHK(c, c->pr_rec.reserve(n * 32));
-        fovpt_launch_probe_records(c->stream, n, (const float*)c->pr_cdfx.p, (const float*)c->pr_pdfx.p, (const float4*)c->pr_data.p, (float4*)c->pr_rec.p);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->guide_ok = true;
-    }
-    c->guide_w = width; c->guide_h = height;
-    // identical texel rows give identical pdfX/cdfX rows (same arithmetic on the same inputs)
-    c->rows_identical = true;
-    for (int row = 1; row < height && c->rows_identical; row++)
-        if (memcmp(data + (size_t)row * width, data, (size_t)width * 16) || memcmp(hx.data() + (size_t)row * width, hx.data(), (size_t)width * 4))
-            c->rows_identical = false;
-    memset(out, 0, sizeof(*out));
-    out->width = width; out->height = height;
-    out->data = (fovpt_float4*)c->pr_data.p;
-    out->pdfValuesX = (float*)c->pr_pdfx.p; out->cdfValuesX = (float*)c->pr_cdfx.p;
-    out->pdfValuesY = (float*)c->pr_pdfy.p; out->cdfValuesY = (float*)c->pr_cdfy.p;
-    if (offset) out->offset = *offset;
-    return FOVPT_OK;
+    // (identical texel rows give identical pdfX rows: the same arithmetic on the same inputs, so none to compare here)
+    return finish_probe(c, width, height, data, nullptr, hx.data(), hy.data(), offset, out);
 }
 
 int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
@@ -1305,491 +1039,6 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
         c->dn_world = c->cfg.world;
     }
     return rc;
-}
-
-// fovpt_reconstruct_defaults (chosen by measurement: DESIGN.md, section 11)
-#define FOVPT_RECONSTRUCT_SUPPORT 2.0f
-#define FOVPT_RECONSTRUCT_NORMAL_SIGMA 0.5f
-#define FOVPT_RECONSTRUCT_DEPTH_SIGMA 0.05f
-
-// fovpt_temporal_defaults (chosen by measurement: DESIGN.md, section 12)
-#define FOVPT_TEMPORAL_HISTORY_FOVEA 1
-#define FOVPT_TEMPORAL_HISTORY_MIDDLE 4
-#define FOVPT_TEMPORAL_HISTORY_PERIPHERY 8
-#define FOVPT_TEMPORAL_HISTORY_UNIFORM 4
-#define FOVPT_TEMPORAL_NORMAL_TOLERANCE 0.1f
-#define FOVPT_TEMPORAL_DEPTH_TOLERANCE 0.02f
-
-// edge-stopping scales of fovpt_denoise_defaults (chosen by measurement: DESIGN.md, denoiser)
-#define FOVPT_DENOISE_COLOR_SIGMA 8.0f
-#define FOVPT_DENOISE_NORMAL_SIGMA 0.5f
-#define FOVPT_DENOISE_ALBEDO_SIGMA 0.2f
-
-// ---- denoiser of the rendered frame (denoise.hip; the filter's definition: tests/denoise_ref.py) ------------------------
-int fovpt_denoise_defaults(fovpt_denoise_config* out)
-{
-    if (!out) return FOVPT_E_INVALID;
-    memset(out, 0, sizeof(*out));
-    out->iterations_fovea = 0;
-    out->iterations_middle = 2;
-    out->iterations_periphery = 3;
-    out->iterations_uniform = 3;
-    out->color_sigma = FOVPT_DENOISE_COLOR_SIGMA;
-    out->normal_sigma = FOVPT_DENOISE_NORMAL_SIGMA;
-    out->albedo_sigma = FOVPT_DENOISE_ALBEDO_SIGMA;
-    return FOVPT_OK;
-}
-
-int fovpt_denoise_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
-{
-    if (!c || !color || !rgba) return FOVPT_E_INVALID;
-    if (!c->dn_color.p) {
-        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise_buffers: no frame rendered yet");
-        HIPCHK(c, hipSetDevice(c->device));
-        const size_t n = (size_t)c->dn_w * (size_t)c->dn_h;
-        HIPCHK(c, c->dn_color.reserve(n * 16)); HIPCHK(c, c->dn_rgba.reserve(n * 4));
-    }
-    *color = (fovpt_float4*)c->dn_color.p;
-    *rgba = (uint32_t*)c->dn_rgba.p;
-    return FOVPT_OK;
-}
-
-// Enqueued on the stream every resolve runs on (fovpt_stream()), in issue order: behind the resolve of the frame last issued
-// -- also with frames_in_flight = 2 or chains_per_frame = 2, whose chains all join that stream for their resolve -- and ahead
-// of the next frame's resolve, the first of its launches that rewrites accum / frame / guides (its memsets and snapshot copies
-// of chunked launches also run there).  Callers synchronising on fovpt_stream() see the denoised frame.
-int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoise_config* dc, fovpt_float4* out_color, uint32_t* out_rgba)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !dc) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null argument");
-    const int32_t its[4] = {dc->iterations_fovea, dc->iterations_middle, dc->iterations_periphery, dc->iterations_uniform};
-    for (int32_t n : its)
-        if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: iteration count %d outside 0 .. %d", n, FOVPT_DENOISE_MAX_ITERATIONS);
-    const float sig[3] = {dc->color_sigma, dc->normal_sigma, dc->albedo_sigma};
-    for (float v : sig)
-        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
-    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise: no frame rendered yet");
-    if (!c->dn_guides || c->any_catcher) return fail(c, FOVPT_E_INVALID, "fovpt_denoise needs the denoiser guides: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
-    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: a tile shard (world = %d) has no neighbours to filter with", c->dn_world);
-    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
-        return fail(c, FOVPT_E_NO_FRAME, "fovpt_denoise: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
-    if (!lp->frame.color_buffer || !lp->frame.normal_buffer || !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null guide buffers");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
-    if (!out_color || !out_rgba) { HIPCHK(c, c->dn_color.reserve(npix * 16)); HIPCHK(c, c->dn_rgba.reserve(npix * 4)); }
-    HIPCHK(c, c->dn_level.reserve(npix));
-    HIPCHK(c, c->dn_i0.reserve(npix * 16));
-    HIPCHK(c, c->dn_i1.reserve(npix * 16));
-    if (!out_color) out_color = (fovpt_float4*)c->dn_color.p;
-    if (!out_rgba) out_rgba = (uint32_t*)c->dn_rgba.p;
-
-    // the level map: the passes fovpt_render ran for this frame
-    const FrameDev& fd = c->dn_frame;
-    DenoiseArgs a;
-    memset(&a, 0, sizeof(a));
-    if (c->dn_uniform) a.n_pass[0] = dc->iterations_uniform;
-    else { a.n_pass[0] = dc->iterations_periphery; a.n_pass[1] = dc->iterations_middle; a.n_pass[2] = dc->iterations_fovea; }
-    for (int p = 0; p < fd.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
-    auto inv_sq = [](float s) { const float s2 = s * s; return 1.0f / s2; };
-    a.inv_c = inv_sq(dc->color_sigma); a.inv_n = inv_sq(dc->normal_sigma); a.inv_a = inv_sq(dc->albedo_sigma);
-    fovpt_launch_denoise(c->shadow_stream, fd, a, lp->frame.color_buffer, lp->frame.normal_buffer, lp->frame.albedo_buffer,
-                         (float4*)c->dn_i0.p, (float4*)c->dn_i1.p, (uint8_t*)c->dn_level.p, out_color, out_rgba);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
-}
-
-// ---- G-buffer and reconstruction of the rendered frame (reconstruct.hip; the reconstruction's definition:
-// tests/reconstruct_ref.py) --------------------------------------------------------------------------------------------
-int fovpt_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, fovpt_gbuffer_ptrs* out)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !out) return fail(c, FOVPT_E_INVALID, "fovpt_gbuffer: null argument");
-    GBufferDev g;
-    FrameDev view;
-    memset(&view, 0, sizeof(view));
-    set_camera(view, lp);
-    const int rc = enqueue_gbuffer(c, lp, view, g, "fovpt_gbuffer");
-    if (rc) return rc;
-    out->prim = g.prim;
-    out->position = (fovpt_float4*)g.pos; out->normal = (fovpt_float4*)g.nrm; out->albedo = (fovpt_float4*)g.alb;
-    out->width = lp->frame.size.x; out->height = lp->frame.size.y;
-    return FOVPT_OK;
-}
-
-int fovpt_reconstruct_defaults(fovpt_reconstruct_config* out)
-{
-    if (!out) return FOVPT_E_INVALID;
-    memset(out, 0, sizeof(*out));
-    out->support = FOVPT_RECONSTRUCT_SUPPORT;
-    out->normal_sigma = FOVPT_RECONSTRUCT_NORMAL_SIGMA;
-    out->depth_sigma = FOVPT_RECONSTRUCT_DEPTH_SIGMA;
-    out->levels = 3;
-    out->remodulate = 1;
-    return FOVPT_OK;
-}
-
-int fovpt_reconstruct_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
-{
-    if (!c || !color || !rgba) return FOVPT_E_INVALID;
-    if (!c->rc_color.p) {
-        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct_buffers: no frame rendered yet");
-        HIPCHK(c, hipSetDevice(c->device));
-        const size_t n = (size_t)c->dn_w * (size_t)c->dn_h;
-        HIPCHK(c, c->rc_color.reserve(n * 16)); HIPCHK(c, c->rc_rgba.reserve(n * 4));
-    }
-    *color = (fovpt_float4*)c->rc_color.p;
-    *rgba = (uint32_t*)c->rc_rgba.p;
-    return FOVPT_OK;
-}
-
-// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: behind the resolve of the frame last issued, ahead of
-// the next frame's.  Builds that frame's G-buffer first (the same stream), then reconstructs.
-int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_reconstruct_config* rc, const fovpt_float4* in_color,
-                      fovpt_float4* out_color, uint32_t* out_rgba)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !rc) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null argument");
-    if (!(rc->support >= 1.0f && rc->support <= 2.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: support %g outside [1, 2]", (double)rc->support);
-    const float sig[2] = {rc->normal_sigma, rc->depth_sigma};
-    for (float v : sig)
-        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
-    if (rc->levels < 0 || rc->levels > 3) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: levels %d outside 0 .. 3", rc->levels);
-    if (rc->remodulate != 0 && rc->remodulate != 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: remodulate %d is neither 0 nor 1", rc->remodulate);
-    for (int32_t r : rc->_reserved)
-        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: reserved fields must be 0");
-    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_reconstruct without a scene");
-    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct: no frame rendered yet");
-    if (rc->remodulate && (!c->dn_guides || c->any_catcher))
-        return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct with remodulate = 1 needs the albedo guide: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)");
-    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: a tile shard (world = %d) has no neighbours to reconstruct from", c->dn_world);
-    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
-        return fail(c, FOVPT_E_NO_FRAME, "fovpt_reconstruct: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
-    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
-    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null accum_buffer");
-    if (rc->remodulate && !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null albedo guide");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
-    if (!out_color || !out_rgba) { HIPCHK(c, c->rc_color.reserve(npix * 16)); HIPCHK(c, c->rc_rgba.reserve(npix * 4)); }
-    if (!out_color) out_color = (fovpt_float4*)c->rc_color.p;
-    if (!out_rgba) out_rgba = (uint32_t*)c->rc_rgba.p;
-    if (in == out_color) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: the input is the output colour buffer (it reads neighbours)");
-    GBufferDev g;
-    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, "fovpt_reconstruct"); if (rc_) return rc_; }   // the rendered frame's camera
-    const FrameDev& fd = c->dn_frame;
-    ReconstructArgs a;
-    memset(&a, 0, sizeof(a));
-    const float s = rc->support;
-    a.inv_support[0] = 1.0f / (s * 2.0f);
-    a.inv_support[1] = 1.0f / (s * 4.0f);
-    auto inv_sq = [](float v) { const float v2 = v * v; return 1.0f / v2; };
-    a.inv_n = inv_sq(rc->normal_sigma); a.inv_z = inv_sq(rc->depth_sigma);
-    a.levels = rc->levels; a.remodulate = rc->remodulate;
-    fovpt_launch_reconstruct(c->shadow_stream, fd, a, in, lp->frame.albedo_buffer, g, out_color, out_rgba);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
-}
-
-// ---- temporal reprojection of the frame history (temporal.hip; its definition: tests/temporal_ref.py) ------------------
-int fovpt_temporal_defaults(fovpt_temporal_config* out)
-{
-    if (!out) return FOVPT_E_INVALID;
-    memset(out, 0, sizeof(*out));
-    out->history_fovea = FOVPT_TEMPORAL_HISTORY_FOVEA;
-    out->history_middle = FOVPT_TEMPORAL_HISTORY_MIDDLE;
-    out->history_periphery = FOVPT_TEMPORAL_HISTORY_PERIPHERY;
-    out->history_uniform = FOVPT_TEMPORAL_HISTORY_UNIFORM;
-    out->normal_tolerance = FOVPT_TEMPORAL_NORMAL_TOLERANCE;
-    out->depth_tolerance = FOVPT_TEMPORAL_DEPTH_TOLERANCE;
-    return FOVPT_OK;
-}
-
-int fovpt_temporal_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba, const fovpt_float4** history)
-{
-    if (!c || !color || !rgba || !history) return FOVPT_E_INVALID;
-    if (!c->tp_hist[0].p) {
-        if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal_buffers: no frame rendered yet");
-        HIPCHK(c, hipSetDevice(c->device));
-        const int rc_ = reserve_temporal(c, (size_t)c->dn_w * (size_t)c->dn_h);
-        if (rc_) return rc_;
-    }
-    *color = (fovpt_float4*)c->tp_color.p;
-    *rgba = (uint32_t*)c->tp_rgba.p;
-    *history = (const fovpt_float4*)c->tp_hist[c->tp_last].p;
-    return FOVPT_OK;
-}
-
-int fovpt_temporal_reset(fovpt_ctx* c)
-{
-    if (!c) return FOVPT_E_INVALID;
-    c->tp_valid = false;
-    return FOVPT_OK;
-}
-
-// Enqueued on fovpt_stream() like fovpt_reconstruct, and ordered like it.  Traces the rendered frame's G-buffer into the set
-// the last call did not write, reprojects the other set's history into it, and makes it the last written.
-int fovpt_temporal(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
-                   fovpt_float4* out_color, uint32_t* out_rgba)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null argument");
-    const int32_t caps[4] = {tc->history_fovea, tc->history_middle, tc->history_periphery, tc->history_uniform};
-    for (int32_t v : caps)
-        if (v < 1 || v > FOVPT_TEMPORAL_MAX_HISTORY) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: history cap %d outside 1 .. %d", v, FOVPT_TEMPORAL_MAX_HISTORY);
-    if (!(tc->normal_tolerance >= 0.0f && tc->normal_tolerance <= 4.0f))
-        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: normal_tolerance %g outside [0, 4]", (double)tc->normal_tolerance);
-    if (!(tc->depth_tolerance >= 0.0f && tc->depth_tolerance <= 1.0f))
-        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: depth_tolerance %g outside [0, 1]", (double)tc->depth_tolerance);
-    for (int32_t r : tc->_reserved)
-        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: reserved fields must be 0");
-    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_temporal without a scene");
-    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal: no frame rendered yet");
-    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: a tile shard (world = %d) has no neighbours to reproject from", c->dn_world);
-    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
-        return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal: frame size %d x %d differs from the last frame's %d x %d", lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
-    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
-    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null accum_buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
-    { const int rc_ = reserve_temporal(c, npix); if (rc_) return rc_; }
-    if (!out_color) out_color = (fovpt_float4*)c->tp_color.p;
-    if (!out_rgba) out_rgba = (uint32_t*)c->tp_rgba.p;
-    if ((void*)out_color == c->tp_hist[0].p || (void*)out_color == c->tp_hist[1].p)
-        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: the output colour buffer is the context's history");
-    const int cur = c->tp_last ^ 1, prev = c->tp_last;
-    const GBufferDev g = temporal_set(c, cur), gp = temporal_set(c, prev);
-    GBufferDev gt;
-    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, gt, "fovpt_temporal", &g); if (rc_) return rc_; }   // the rendered frame's camera
-    const FrameDev& fd = c->dn_frame;
-    TemporalArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int k = 0; k < 4; k++) a.cap[k] = caps[k];
-    a.normal_tol = tc->normal_tolerance; a.depth_tol = tc->depth_tolerance;
-    a.uniform = c->dn_uniform != 0;
-    a.reproject = c->tp_valid && c->tp_w == c->dn_w && c->tp_h == c->dn_h && camera_inverse(c->tp_U, c->tp_V, c->tp_W, a.inv);
-    memcpy(a.eye_prev, c->tp_eye, sizeof(a.eye_prev));
-    fovpt_launch_temporal(c->shadow_stream, fd, a, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
-    HIPCHK(c, hipGetLastError());
-    c->tp_last = cur;                                                      // this step is the next one's previous step
-    c->tp_valid = true;
-    c->tp_w = c->dn_w; c->tp_h = c->dn_h;
-    memcpy(c->tp_eye, fd.eye, sizeof(c->tp_eye)); memcpy(c->tp_U, fd.U, sizeof(c->tp_U));
-    memcpy(c->tp_V, fd.V, sizeof(c->tp_V)); memcpy(c->tp_W, fd.W, sizeof(c->tp_W));
-    return FOVPT_OK;
-}
-
-// ---- multi-GPU: packed gather of the owned pixels ---------------------------------------------------
-int fovpt_gather_plan(fovpt_ctx* c, const fovpt_launch_params* lp, uint32_t* counts_out, int counts_len)
-{
-    if (!c || !lp) return FOVPT_E_INVALID;
-    const int world = c->cfg.world < 1 ? 1 : c->cfg.world;
-    if (world > 64) return fail(c, FOVPT_E_INVALID, "gather plans support up to 64 ranks (world = %d)", world);
-    if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
-    if (counts_out && counts_len < world) return fail(c, FOVPT_E_INVALID, "counts_out holds %d entries, world is %d", counts_len, world);
-    HIPCHK(c, hipSetDevice(c->device));
-    char key[256];
-    snprintf(key, sizeof(key), "%d x %d u%d r%d/%d c%u,%u w%d t%dx%d", lp->frame.size.x, lp->frame.size.y, c->cfg.uniform, c->cfg.r_inner, c->cfg.r_outer,
-             lp->frame.c.x, lp->frame.c.y, world, c->cfg.tile_w, c->cfg.tile_h);
-    if (c->plan_key != key) {
-        fovpt_launch_params L = *lp;
-        PassDev P[3];
-        FrameDev fd;
-        memset(&fd, 0, sizeof(fd));
-        fd.npass = frame_passes(c->cfg, L, P);
-        for (int p = 0; p < fd.npass; p++) { fd.pass[p] = P[p]; fd.pass[p].row0 = 0; fd.pass[p].row1 = P[p].gh; fd.pass[p].frame_pass = (uint32_t)p; }
-        fd.w = L.frame.size.x; fd.h = L.frame.size.y;
-        fd.cx = L.frame.c.x; fd.cy = L.frame.c.y;
-        fd.rank = c->cfg.rank; fd.world = world;
-        fd.tile_w = c->cfg.tile_w > 0 ? c->cfg.tile_w : 8; fd.tile_h = c->cfg.tile_h > 0 ? c->cfg.tile_h : 4;
-        const uint32_t npix = (uint32_t)fd.w * (uint32_t)fd.h, nblocks = (npix + FOVPT_BLOCK - 1) / FOVPT_BLOCK;
-        HIPCHK(c, c->plan_owner.reserve(npix));
-        HIPCHK(c, c->plan_blocks.reserve((size_t)nblocks * world * 4));
-        HIPCHK(c, c->plan_total.reserve(64 * 4));
-        HIPCHK(c, c->plan_base.reserve(65 * 4));
-        HIPCHK(c, c->plan_idx.reserve((size_t)npix * 4));
-        hipStream_t st = c->shadow_stream;                  // the stream frames complete on: pack / unpack run there too
-        fovpt_launch_plan_owner(st, fd, (uint8_t*)c->plan_owner.p, (uint32_t*)c->plan_blocks.p, nblocks);
-        fovpt_launch_plan_scan_fill(st, npix, nblocks, world, (const uint8_t*)c->plan_owner.p, (uint32_t*)c->plan_blocks.p,
-                                    (uint32_t*)c->plan_total.p, nullptr, nullptr, 0);
-        uint32_t total[64];
-        HIPCHK(c, hipMemcpyAsync(total, c->plan_total.p, (size_t)world * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        c->plan_off.assign((size_t)world + 1, 0u);
-        for (int r = 0; r < world; r++) c->plan_off[r + 1] = c->plan_off[r] + total[r];
-        HIPCHK(c, hipMemcpyAsync(c->plan_base.p, c->plan_off.data(), (size_t)(world + 1) * 4, hipMemcpyHostToDevice, st));
-        fovpt_launch_plan_scan_fill(st, npix, nblocks, world, (const uint8_t*)c->plan_owner.p, (uint32_t*)c->plan_blocks.p,
-                                    nullptr, (const uint32_t*)c->plan_base.p, (uint32_t*)c->plan_idx.p, 1);
-        HIPCHK(c, hipStreamSynchronize(st));                // (plan_off.data() must outlive the copy)
-        HIPCHK(c, hipGetLastError());
-        c->plan_key = key;
-    }
-    if (counts_out) for (int r = 0; r < world; r++) counts_out[r] = c->plan_off[r + 1] - c->plan_off[r];
-    return FOVPT_OK;
-}
-
-int fovpt_gather_pack(fovpt_ctx* c, const uint32_t* frame, uint32_t* packed)
-{
-    if (!c || !frame || !packed) return FOVPT_E_INVALID;
-    if (c->plan_key.empty()) return fail(c, FOVPT_E_INVALID, "fovpt_gather_pack without a plan (fovpt_gather_plan)");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int r = c->cfg.rank;
-    if (r < 0 || (size_t)r + 1 >= c->plan_off.size()) return fail(c, FOVPT_E_INVALID, "rank %d is not part of the plan", r);
-    fovpt_launch_gather_pack(c->shadow_stream, c->plan_off[r + 1] - c->plan_off[r], (const uint32_t*)c->plan_idx.p + c->plan_off[r], frame, packed);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
-}
-
-int fovpt_gather_unpack(fovpt_ctx* c, const uint32_t* gathered, uint32_t stride, uint32_t* frame)
-{
-    if (!c || !gathered || !frame) return FOVPT_E_INVALID;
-    if (c->plan_key.empty()) return fail(c, FOVPT_E_INVALID, "fovpt_gather_unpack without a plan (fovpt_gather_plan)");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int world = (int)c->plan_off.size() - 1;
-    for (int r = 0; r < world; r++)
-        if (c->plan_off[r + 1] - c->plan_off[r] > stride) return fail(c, FOVPT_E_INVALID, "stride %u is smaller than rank %d's %u pixels", stride, r, c->plan_off[r + 1] - c->plan_off[r]);
-    fovpt_launch_gather_unpack(c->shadow_stream, world, stride, c->plan_off[world], (const uint32_t*)c->plan_base.p, (const uint32_t*)c->plan_idx.p, gathered, frame);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
-}
-
-// ---- multi-GPU: the transport between pack and unpack, RCCL over xGMI, for C / C++ hosts ----------------------------
-// One process (or thread) per GPU, each with its own fovpt_ctx; the gather of a frame is
-//   plan -> pack (HIP) -> ncclGroupStart; ncclSend to the root; on the root ncclRecv from every rank; ncclGroupEnd -> unpack
-// all enqueued on fovpt_stream(), the stream frames complete on: no host synchronisation, and the transport of frame k runs
-// beside the rendering of frame k + 1.  librccl is loaded at run time so that libfovpt.so has no link-time dependency on it
-// (a process that already holds an RCCL -- PyTorch's -- gets that one: same SONAME).
-}  // extern "C"
-namespace {
-struct Rccl {
-    void* lib = nullptr;
-    bool tried = false;
-    std::string why;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-Rccl& rccl()
-{
-    static Rccl R;
-    if (R.tried) return R;
-    R.tried = true;
-    // A copy the process already holds comes first (RTLD_NOLOAD): a host that has PyTorch loaded has PyTorch's bundled
-    // librccl.so -- another file than /opt/rocm's librccl.so.1, so asking for the latter by name would put a SECOND RCCL into the
-    // process (fovpathtracing_optixcodelatest_amd/lib.py loads torch's copy first when torch is installed and not imported yet).
-    const char* names[] = {getenv("FOVPT_RCCL_LIB"), "librccl.so", "librccl.so.1", "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (int k = 0; k < 6 && !R.lib; k++) {
-        const char* n = names[k];
-        if (!n || !*n) continue;
-        const bool only_if_loaded = k == 1 || k == 2;
-        // (RTLD_LOCAL: every entry point is looked up with dlsym, and RCCL brings librocm_smi64 with it, whose `amd::smi` globals
-        // must not become the process's: /opt/rocm's libamd_smi.so -- which PyTorch's device queries load -- defines the same ones,
-        // and two libraries then run their static destructors on one object)
-        R.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL | (only_if_loaded ? RTLD_NOLOAD : 0));
-        if (!R.lib && !only_if_loaded) R.why = dlerror() ? dlerror() : "dlopen failed";
-    }
-    if (!R.lib) { if (R.why.empty()) R.why = "librccl not found"; return R; }
-    struct { const char* n; void** f; } syms[] = {
-        {"ncclGetUniqueId", (void**)&R.GetUniqueId}, {"ncclCommInitRank", (void**)&R.CommInitRank}, {"ncclCommDestroy", (void**)&R.CommDestroy},
-        {"ncclGroupStart", (void**)&R.GroupStart}, {"ncclGroupEnd", (void**)&R.GroupEnd}, {"ncclSend", (void**)&R.Send}, {"ncclRecv", (void**)&R.Recv},
-        {"ncclGetErrorString", (void**)&R.GetErrorString}};
-    for (auto& sy : syms) {
-        *sy.f = dlsym(R.lib, sy.n);
-        if (!*sy.f) { R.why = std::string("librccl lacks ") + sy.n; dlclose(R.lib); R.lib = nullptr; return R; }
-    }
-    return R;
-}
-#define NCCLCHK(c, x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) return fail((c), FOVPT_E_DEVICE, "%s: %s", #x, rccl().GetErrorString(r_)); } while (0)
-}  // namespace
-extern "C" {
-
-int fovpt_comm_get_unique_id(void* id)
-{
-    if (!id) return fail(nullptr, FOVPT_E_INVALID, "fovpt_comm_get_unique_id: null argument");
-    Rccl& R = rccl();
-    if (!R.lib) return fail(nullptr, FOVPT_E_DEVICE, "RCCL is not available: %s", R.why.c_str());
-    static_assert(FOVPT_COMM_ID_BYTES == sizeof(ncclUniqueId), "unique id size");
-    ncclUniqueId u;
-    NCCLCHK(nullptr, R.GetUniqueId(&u));
-    memcpy(id, &u, sizeof(u));
-    return FOVPT_OK;
-}
-
-int fovpt_comm_init(fovpt_ctx* c, const void* id, int rank, int world)
-{
-    if (!c || !id) return FOVPT_E_INVALID;
-    if (world < 1 || world > 64 || rank < 0 || rank >= world) return fail(c, FOVPT_E_INVALID, "bad rank %d of %d (1 .. 64 ranks)", rank, world);
-    Rccl& R = rccl();
-    if (!R.lib) return fail(c, FOVPT_E_DEVICE, "RCCL is not available: %s", R.why.c_str());
-    int rc = fovpt_comm_destroy(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof(u));
-    NCCLCHK(c, R.CommInitRank(&c->comm, world, u, rank));      // collective: every rank calls it, each on its own device
-    c->comm_rank = rank; c->comm_world = world;
-    return FOVPT_OK;
-}
-
-int fovpt_comm_destroy(fovpt_ctx* c)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->comm) return FOVPT_OK;
-    (void)hipSetDevice(c->device);
-    if (c->shadow_stream) (void)hipStreamSynchronize(c->shadow_stream);
-    ncclComm_t comm = c->comm;
-    c->comm = nullptr; c->comm_world = 0;
-    NCCLCHK(c, rccl().CommDestroy(comm));
-    return FOVPT_OK;
-}
-
-int fovpt_gather_frame(fovpt_ctx* c, const fovpt_launch_params* lp, int root, const uint32_t* frame, uint32_t* full_frame)
-{
-    if (!c || !lp || !frame) return FOVPT_E_INVALID;
-    if (!c->comm) return fail(c, FOVPT_E_INVALID, "fovpt_gather_frame without a communicator (fovpt_comm_init)");
-    const int world = c->comm_world, rank = c->comm_rank;
-    if (c->cfg.world != world || c->cfg.rank != rank)
-        return fail(c, FOVPT_E_INVALID, "the communicator is rank %d of %d, fovpt_config says %d of %d", rank, world, c->cfg.rank, c->cfg.world);
-    if (root < 0 || root >= world) return fail(c, FOVPT_E_INVALID, "bad root %d", root);
-    if (rank == root && !full_frame) return fail(c, FOVPT_E_INVALID, "the root needs a frame to gather into");
-    uint32_t counts[64];
-    int rc = fovpt_gather_plan(c, lp, counts, 64);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t stride = 0;
-    for (int r = 0; r < world; r++) stride = counts[r] > stride ? counts[r] : stride;
-    stride = (stride + 63u) & ~63u;
-    if (stride == 0) return FOVPT_OK;                               // no launch index writes any pixel
-    HIPCHK(c, c->comm_packed.reserve((size_t)stride * 4));
-    if (rank == root) HIPCHK(c, c->comm_gathered.reserve((size_t)stride * 4 * world));
-    rc = fovpt_gather_pack(c, frame, (uint32_t*)c->comm_packed.p);
-    if (rc) return rc;
-    Rccl& R = rccl();
-    hipStream_t st = c->shadow_stream;
-    // A group that was opened is always closed: the first failing call is remembered, the remaining point-to-point calls are
-    // skipped, ncclGroupEnd still runs (an open group would leave this rank's later collectives queued for ever and its peers
-    // blocked in theirs), and only then does the call fail.
-    NCCLCHK(c, R.GroupStart());
-    ncclResult_t first_err = ncclSuccess;
-    const char* first_what = "";
-    if (rank == root)
-        for (int r = 0; r < world && first_err == ncclSuccess; r++)
-            if (counts[r]) {
-                first_err = R.Recv((uint32_t*)c->comm_gathered.p + (size_t)r * stride, counts[r], ncclUint32, r, c->comm, st);
-                first_what = "ncclRecv";
-            }
-    if (counts[rank] && first_err == ncclSuccess) { first_err = R.Send(c->comm_packed.p, counts[rank], ncclUint32, root, c->comm, st); first_what = "ncclSend"; }
-    const ncclResult_t end_err = R.GroupEnd();
-    if (first_err != ncclSuccess) return fail(c, FOVPT_E_DEVICE, "%s: %s", first_what, R.GetErrorString(first_err));
-    if (end_err != ncclSuccess) return fail(c, FOVPT_E_DEVICE, "ncclGroupEnd: %s", R.GetErrorString(end_err));
-    if (rank == root) {
-        rc = fovpt_gather_unpack(c, (const uint32_t*)c->comm_gathered.p, stride, full_frame);
-        if (rc) return rc;
-    }
-    return FOVPT_OK;
 }
 
 int fovpt_synchronize(fovpt_ctx* c)
@@ -1951,15 +1200,9 @@ int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* d
     Counters* cnt = (Counters*)S.counters.p;
     HIPCHK(c, hipMemcpyAsync(&cnt->shard[0][FOVPT_CNT_Q(0)], &un, 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(&cnt->shard[0][FOVPT_CNT_SQ(0)], &un, 4, hipMemcpyHostToDevice, st));
-    PathState ps;
-    memset(&ps, 0, sizeof(ps));
-    ps.thr = (float4*)S.s_thr.p; ps.rng = (uint4*)S.s_rng.p; ps.hit = (float4*)S.s_hit.p; ps.rad = (float4*)S.s_rad.p;
-    ps.stride = (size_t)c->cfg.max_depth; ps.alpha = (float4*)S.s_alpha.p; ps.backplate = (float4*)S.s_backplate.p;
-#if FOVPT_V_STEPSTAT
-    ps.trace = (uint4*)S.s_trace.p;
-#endif
+    const PathState ps = path_state(c, S);
     RayQueue q; q.o = (float4*)S.q_o[0].p; q.d = (float4*)S.q_d[0].p;
-    ShadowQueue sq; sq.o = (float4*)S.sq_o[0].p; sq.d = (float4*)S.sq_d[0].p; sq.val_vis = (float4*)S.sq_vis[0].p; sq.val_occ = (float4*)S.sq_occ[0].p;
+    const ShadowQueue sq = shadow_queue(S, 0);
     const SceneView sc = scene_view(c);
     fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, 0, -1, c->grid_trace);        // closest hit, as run_job launches it
     fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, -1, 0, c->grid_shadow);       // occlusion, as run_job launches it
@@ -1995,7 +1238,6 @@ int fovpt_debug_math(fovpt_ctx* c, int op, const float* a, const float* b, float
     if (n == 0) return FOVPT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf ba, bb, bo;
-    struct Rel { DevBuf &a, &b, &o; ~Rel() { a.release(); b.release(); o.release(); } } rel = {ba, bb, bo};
     HIPCHK(c, ba.reserve(n * 4)); HIPCHK(c, bb.reserve(n * 4)); HIPCHK(c, bo.reserve(n * 4));
     float *da = (float*)ba.p, *db = (float*)bb.p, *dout = (float*)bo.p;
     HIPCHK(c, hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice));

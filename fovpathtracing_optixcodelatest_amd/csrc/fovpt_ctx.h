@@ -1,0 +1,159 @@
+// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_post.hip, api_gather.hip): the context, the buffers it
+// owns, and the helpers more than one of the three files uses.  Host only: no kernel file includes it.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "fovpt_device.h"
+#include <rccl/rccl.h>      // types only: the library is loaded at run time (fovpt_comm_*), libfovpt.so does not link it
+
+// Device memory with one owner: freed by release(), by a growing reserve() and when the holder goes away.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t n)
+    {
+        if (n <= bytes) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
+enum TimedKind { T_GENERATE, T_TRACE, T_SHADE, T_SHADOW, T_RESOLVE };    // what a timed launch adds to in fovpt_stats
+struct EventPair { hipEvent_t a, b; TimedKind kind; };
+
+// Shadow-queue buffers per state set: bounce it writes buffer it % FOVPT_NSQ, so with max_depth <= FOVPT_NSQ the
+// main chain never has to wait for an occlusion launch inside a job.
+#define FOVPT_NSQ 4
+
+// The completion events of one chain's shading and occlusion launches, per iteration
+struct ChainEvents { hipEvent_t shade[FOVPT_MAX_ITERS + 1], shadow[FOVPT_MAX_ITERS + 1]; };
+
+struct StateSet {
+    DevBuf s_thr, s_rng, s_hit, s_rad, s_alpha, s_backplate, s_guide_n, s_guide_a, s_trace;
+    DevBuf q_o[2], q_d[2], counters;       // q_*: the two radiance-ray queues (ping-pong)
+    DevBuf sq_o[FOVPT_NSQ], sq_d[FOVPT_NSQ], sq_vis[FOVPT_NSQ], sq_occ[FOVPT_NSQ];   // shadow queues, one per bounce in flight
+    ChainEvents chain[2] = {};             // [1]: the second chain of a frame (fovpt_config.chains_per_frame = 2)
+    hipEvent_t ev_done = nullptr;          // recorded after the resolve of the last job that used this set
+    bool used = false;
+};
+
+#ifndef FOVPT_LANES_DEFAULT
+#define FOVPT_LANES_DEFAULT 2
+#endif
+#define FOVPT_MAX_LANES 4
+#ifndef FOVPT_SETS_SLOT_LIMIT
+#define FOVPT_SETS_SLOT_LIMIT (16ull << 20)    // (~330 B of state and queues per slot and set)
+#endif
+
+struct fovpt_ctx {
+    int device = 0;
+    int num_cus = 256;
+    hipStream_t stream = nullptr;          // main chain: generate, closest-hit traversal, shade
+    hipStream_t shadow_stream = nullptr;   // occlusion rays of every bounce and the resolve: off the critical path
+    // Second LANE (round 3): consecutive jobs alternate between two (main, shadow) stream pairs, so the main chain of job k+1
+    // -- generate, closest-hit, shade, strictly one after the other -- runs BESIDE the main chain of job k instead of behind it:
+    // the launch gaps, ramps and tails of one chain are filled by the other.  Resolves stay in job order (each waits for the
+    // previous job's), and `shadow_stream` remains the one stream every finished frame is ordered on (fovpt_stream()).
+    hipStream_t lane_main[FOVPT_MAX_LANES] = {}, lane_shadow[FOVPT_MAX_LANES] = {};   // [0] = stream / shadow_stream
+    int lanes = FOVPT_LANES_DEFAULT;
+    int chains_default = 1;                // what fovpt_config.chains_per_frame = 0 means (FOVPT_CHAINS)
+    std::string err;
+    fovpt_config cfg;
+    // scene
+    bool has_scene = false;
+    uint64_t scene_id = 0;
+    BvhNode4* nodes = nullptr;
+    TriRec* tris = nullptr;
+    DevBuf tri_tc, meshes, textures;
+    std::vector<void*> tex_pixels;
+    uint32_t num_tris = 0, any_catcher = 0;
+    uint32_t bvh_levels[FOVPT_BVH_MAX_LEVELS + 1] = {};   // the wide tree's levels (BvhBuildResult::level_first), for the refit
+    uint32_t bvh_num_levels = 0;
+    // fovpt_update_vertices.  What fovpt_set_scene keeps on the host: per mesh its first global primitive, first vertex in the
+    // concatenated vertex array and vertex count; per primitive the indices of its three vertices in that array; the positions.
+    // Made on the first update: their device copies (up_vtx 12 B per vertex, up_vidx 12 B per primitive), two pinned staging
+    // buffers for host updates used in turn (each reused once its previous copy has run: ev), and the event a refit records on
+    // fovpt_stream(), which every lane stream waits for before the next job traces the scene (refit_pending).
+    std::vector<uint32_t> mesh_prim0, mesh_vbase, mesh_nv, h_tri_vidx;
+    std::vector<float> h_vtx;
+    DevBuf up_vtx, up_vidx;
+    struct Staging { void* p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } up_stage[2];
+    int up_next = 0;
+    hipEvent_t ev_scene = nullptr;
+    bool refit_pending = false;
+    // probe
+    DevBuf pr_data, pr_pdfx, pr_cdfx, pr_pdfy, pr_cdfy, pr_guidex, pr_guidey, pr_rec;
+    bool guide_ok = false;
+    int guide_w = 0, guide_h = 0;
+    bool rows_identical = false;           // every row of data / pdfX / cdfX equals row 0 bit for bit
+    // frame buffers (resize)
+    DevBuf fb_frame, fb_accum, fb_color, fb_normal, fb_albedo;
+    DevBuf accum_before;                   // accumulate mode, chunked launch: the accum buffer as it was before the launch
+    // multi-GPU gather plan (fovpt_gather_plan): pixel indices grouped by owning rank
+    DevBuf plan_owner, plan_blocks, plan_total, plan_base, plan_idx;
+    std::vector<uint32_t> plan_off;        // host copy: rank r owns plan_idx[plan_off[r] .. plan_off[r + 1])
+    std::string plan_key;                  // what the plan was built for
+    bool use_accum_before = false;
+    // fovpt_denoise / fovpt_reconstruct: the frame last issued with fovpt_render as it was rendered (dn_w x dn_h; 0 x 0: none
+    // since create / resize): its passes, gaze and camera (dn_frame), and the FOV_OFF flag, guides and shard count of its config.
+    // Post-processing reads these, never the caller's current config, gaze or camera.  Then the level map, the ping-pong
+    // filter buffers and the context's own outputs (allocated on first use)
+    int dn_w = 0, dn_h = 0;
+    FrameDev dn_frame{};
+    int32_t dn_uniform = 0, dn_guides = 0, dn_world = 1;
+    DevBuf dn_level, dn_i0, dn_i1, dn_color, dn_rgba;
+    // fovpt_gbuffer / fovpt_reconstruct: the G-buffer's own ray queue, hit records, counters and outputs (never a render state
+    // set: a frame in flight may be using those), and the context's own reconstruction outputs; all allocated on first use
+    DevBuf gb_o, gb_d, gb_hit, gb_cnt, gb_prim, gb_pos, gb_nrm, gb_alb, rc_color, rc_rgba;
+    // fovpt_temporal: two G-buffer sets and two histories (rgb, n), used in turn by consecutive calls (tp_last: the set the
+    // last call wrote), the previous step's camera and size, and the context's own outputs; all allocated on first use.
+    // tp_valid: a previous step exists (dropped by fovpt_temporal_reset, fovpt_resize and fovpt_set_scene)
+    DevBuf tp_prim[2], tp_pos[2], tp_nrm[2], tp_alb[2], tp_hist[2], tp_color, tp_rgba;
+    int tp_last = 0;
+    bool tp_valid = false;
+    int tp_w = 0, tp_h = 0;
+    float tp_eye[3] = {}, tp_U[3] = {}, tp_V[3] = {}, tp_W[3] = {};
+    // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
+    ncclComm_t comm = nullptr;
+    int comm_rank = 0, comm_world = 0;
+    DevBuf comm_packed, comm_gathered;
+    // Wavefront state, several sets used in rotation by consecutive jobs: the tail of job k (its last occlusion
+    // rays and its resolve, on the shadow stream) runs beside the head of job k+1 (generate, camera rays).
+    // Round 4: TWICE as many sets as lanes, so that the job which follows job k on the same lane (job k + lanes) does not
+    // wait for job k's resolve before it may overwrite the path state: its main chain starts as soon as job k's has ended,
+    // and k's tail runs beside it.  (What a 1/N shard of a frame needs: its launches are short, and last occlusion launch +
+    // resolve were a third of a lane's cycle.)
+    StateSet set[2 * FOVPT_MAX_LANES];
+    unsigned nsets = 4;                    // sets in rotation for ordinary jobs = 2 * lanes (FOVPT_SETS: 2 .. 2 * FOVPT_MAX_LANES)
+    unsigned last_set = 0;                 // the set the most recent job used
+    unsigned jobs = 0;                     // jobs issued so far; job j runs on lane j % lanes
+    int grid = 2048, grid_trace = 2048, grid_shadow = 1024, grid_shade = 1024;
+    int spread_occlusion = 1;              // sharded frames: one occlusion launch of a first-lane job runs on the second lane's shadow stream (FOVPT_SPREAD_OCCLUSION)
+    uint64_t slot_budget = 64ull << 20;    // sample slots per wavefront job (~330 B of state and queues each and per set; jobs above FOVPT_SETS_SLOT_LIMIT rotate through one set per lane)
+    // stats
+    fovpt_stats stats;
+    std::vector<EventPair> pending;
+    std::vector<hipEvent_t> free_events;
+    ~fovpt_ctx();                          // what no DevBuf owns; fovpt_destroy synchronises first
+};
+
+int fail(fovpt_ctx* c, int code, const char* fmt, ...);       // sets the error text (c null: the text fovpt_last_error(NULL) returns), returns code
+#define HIPCHK(c, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail((c), FOVPT_E_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+int sync_all(fovpt_ctx* c);
+SceneView scene_view(const fovpt_ctx* c);
+void set_camera(FrameDev& fd, const fovpt_launch_params* lp);
+void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd);
+// api_post.hip (fovpt_resize keeps the buffers of the post-processing calls at the frame's size)
+int reserve_gbuffer(fovpt_ctx* c, size_t n);
+int reserve_temporal(fovpt_ctx* c, size_t n);
+int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
+                    const GBufferDev* target = nullptr);

@@ -98,6 +98,26 @@ def share_torch_rccl():
             pass
 
 
+def _declare_loader(L):
+    """The signatures both libraries share: fovpt_last_error and the scene / image ingestion (fovpt_model_*, fovpt_image_*)."""
+    vp, i32 = C.c_void_p, C.c_int
+    L.fovpt_last_error.argtypes = [vp]
+    L.fovpt_last_error.restype = C.c_char_p
+    L.fovpt_model_load_obj.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.fovpt_model_load_gltf.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.fovpt_model_destroy.argtypes = [vp]
+    L.fovpt_model_destroy.restype = None
+    L.fovpt_model_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.fovpt_model_get_mesh.argtypes = [vp, i32, C.POINTER(abi.ModelMesh)]
+    L.fovpt_model_get_texture.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
+    L.fovpt_image_load_float4.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
+    L.fovpt_image_free.argtypes = [vp]
+    L.fovpt_image_free.restype = None
+    L.fovpt_image_load_rgba8.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
+    L.fovpt_image_free_rgba8.argtypes = [vp]
+    L.fovpt_image_free_rgba8.restype = None
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -110,8 +130,6 @@ def load():
     L.fovpt_create.argtypes = [C.POINTER(vp), i32]
     L.fovpt_destroy.argtypes = [vp]
     L.fovpt_destroy.restype = None
-    L.fovpt_last_error.argtypes = [vp]
-    L.fovpt_last_error.restype = C.c_char_p
     L.fovpt_set_scene.argtypes = [vp, vp, i32, vp, i32, C.POINTER(u64)]
     L.fovpt_set_probe.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(abi.Probe)]
     L.fovpt_set_probe_data.argtypes = [vp, i32, i32, vp, vp, C.POINTER(abi.Probe)]
@@ -151,19 +169,7 @@ def load():
     L.fovpt_debug_math.argtypes = [vp, i32, vp, vp, vp, sz]
     L.fovpt_debug_buffer.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(sz)]
     L.fovpt_debug_trace.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-    L.fovpt_model_load_obj.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.fovpt_model_load_gltf.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.fovpt_model_destroy.argtypes = [vp]
-    L.fovpt_model_destroy.restype = None
-    L.fovpt_model_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.fovpt_model_get_mesh.argtypes = [vp, i32, C.POINTER(abi.ModelMesh)]
-    L.fovpt_model_get_texture.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
-    L.fovpt_image_load_float4.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
-    L.fovpt_image_free.argtypes = [vp]
-    L.fovpt_image_free.restype = None
-    L.fovpt_image_load_rgba8.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
-    L.fovpt_image_free_rgba8.argtypes = [vp]
-    L.fovpt_image_free_rgba8.restype = None
+    _declare_loader(L)
     for name in EXPORTS:
         if name not in ("fovpt_destroy", "fovpt_last_error", "fovpt_stream", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8"):
             getattr(L, name).restype = i32
@@ -186,25 +192,10 @@ def load_loader():
     if _loader is not None:
         return _loader
     L = C.CDLL(LOADER_SO_PATH)
-    vp, i32 = C.c_void_p, C.c_int
-    L.fovpt_last_error.argtypes = [vp]
-    L.fovpt_last_error.restype = C.c_char_p
-    L.fovpt_model_load_obj.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.fovpt_model_load_gltf.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.fovpt_model_destroy.argtypes = [vp]
-    L.fovpt_model_destroy.restype = None
-    L.fovpt_model_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.fovpt_model_get_mesh.argtypes = [vp, i32, C.POINTER(abi.ModelMesh)]
-    L.fovpt_model_get_texture.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
-    L.fovpt_image_load_float4.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
-    L.fovpt_image_free.argtypes = [vp]
-    L.fovpt_image_free.restype = None
-    L.fovpt_image_load_rgba8.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
-    L.fovpt_image_free_rgba8.argtypes = [vp]
-    L.fovpt_image_free_rgba8.restype = None
+    _declare_loader(L)
     for name in LOADER_EXPORTS:
         if name not in ("fovpt_last_error", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8"):
-            getattr(L, name).restype = i32
+            getattr(L, name).restype = C.c_int
     _loader = L
     return L
 

@@ -202,21 +202,22 @@ class SampleRenderer:
 
     def downloadPixels(self):
         """SimplePathtracer.cpp:276-280: always the renderer's own frame_buffer."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x), np.uint32)
-        self._check(self._L.fovpt_download(self._ctx, self._frame_ptrs.frame_buffer, out.ctypes.data, out.nbytes))
-        return out
+        return self._download_frame(self._frame_ptrs.frame_buffer, 1)
 
     def downloadAccum(self):
         """The float4 accum_buffer (per-pixel radiance), the quantity parity is judged on."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x, 4), np.float32)
-        self._check(self._L.fovpt_download(self._ctx, f.accum_buffer, out.ctypes.data, out.nbytes))
-        return out
+        return self._download_frame(self.launchParams.frame.accum_buffer, 4)
 
     def download(self, device_ptr, array):
         self._check(self._L.fovpt_download(self._ctx, device_ptr, array.ctypes.data, array.nbytes))
         return array
+
+    def _download_frame(self, device_ptr, channels):
+        """A per-pixel device buffer of the current frame size: (H, W) uint32 for channels = 1 (rgba8), (H, W, channels) float32 otherwise."""
+        f = self.launchParams.frame
+        if channels == 1:
+            return self.download(device_ptr, np.empty((f.size.y, f.size.x), np.uint32))
+        return self.download(device_ptr, np.empty((f.size.y, f.size.x, channels), np.float32))
 
     # -- denoiser of the rendered frame (include/fovpt.h, fovpt_denoise): in place of the reference family's OptiXDenoiser
     @staticmethod
@@ -240,15 +241,11 @@ class SampleRenderer:
 
     def downloadDenoisedPixels(self):
         """The rgba8 output of the last denoise into the renderer's own buffer, shaped like downloadPixels()."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x), np.uint32)
-        return self.download(self.denoise_buffers()[1], out)
+        return self._download_frame(self.denoise_buffers()[1], 1)
 
     def downloadDenoisedColor(self):
         """The float4 output of the last denoise into the renderer's own buffer."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x, 4), np.float32)
-        return self.download(self.denoise_buffers()[0], out)
+        return self._download_frame(self.denoise_buffers()[0], 4)
 
     # -- G-buffer and reconstruction of the rendered frame (include/fovpt.h, fovpt_gbuffer / fovpt_reconstruct)
     def gbuffer(self) -> abi.GBufferPtrs:
@@ -290,15 +287,11 @@ class SampleRenderer:
 
     def downloadReconstructedPixels(self):
         """The rgba8 output of the last reconstruct into the renderer's own buffer, shaped like downloadPixels()."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x), np.uint32)
-        return self.download(self.reconstruct_buffers()[1], out)
+        return self._download_frame(self.reconstruct_buffers()[1], 1)
 
     def downloadReconstructedColor(self):
         """The float4 output of the last reconstruct into the renderer's own buffer."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x, 4), np.float32)
-        return self.download(self.reconstruct_buffers()[0], out)
+        return self._download_frame(self.reconstruct_buffers()[0], 4)
 
     # -- temporal reprojection of the frame history (include/fovpt.h, fovpt_temporal)
     @staticmethod
@@ -328,21 +321,15 @@ class SampleRenderer:
 
     def downloadTemporalPixels(self):
         """The rgba8 output of the last temporal step into the renderer's own buffer, shaped like downloadPixels()."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x), np.uint32)
-        return self.download(self.temporal_buffers()[1], out)
+        return self._download_frame(self.temporal_buffers()[1], 1)
 
     def downloadTemporalColor(self):
         """The float4 output of the last temporal step into the renderer's own buffer."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x, 4), np.float32)
-        return self.download(self.temporal_buffers()[0], out)
+        return self._download_frame(self.temporal_buffers()[0], 4)
 
     def downloadTemporalHistory(self):
         """The history the last temporal step wrote: (H, W, 4) float32, rgb its output colour, w the history length."""
-        f = self.launchParams.frame
-        out = np.empty((f.size.y, f.size.x, 4), np.float32)
-        return self.download(self.temporal_buffers()[2], out)
+        return self._download_frame(self.temporal_buffers()[2], 4)
 
     # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
     def update_vertices(self, updates, rebuild=False):
