@@ -1,5 +1,5 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
-// fovpt_reconstruct (reconstruct.hip), fovpt_temporal (temporal.hip), and their defaults.
+// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), and their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -66,6 +66,79 @@ bool camera_inverse(const float* U, const float* V, const float* W, float* inv)
     return true;
 }
 
+// One step of the history for fovpt_temporal (motion false: k_temporal, and no HIP call beside those of the G-buffer and
+// that launch) and fovpt_temporal_motion (motion true: k_temporal_motion; the first one of a scene switches the tracking of
+// previous positions on).  Either ends the interval in which fovpt_update_vertices marks meshes as moved.
+int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
+                  fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion, bool motion, const char* who)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const int32_t caps[4] = {tc->history_fovea, tc->history_middle, tc->history_periphery, tc->history_uniform};
+    for (int32_t v : caps)
+        if (v < 1 || v > FOVPT_TEMPORAL_MAX_HISTORY) return fail(c, FOVPT_E_INVALID, "%s: history cap %d outside 1 .. %d", who, v, FOVPT_TEMPORAL_MAX_HISTORY);
+    if (!(tc->normal_tolerance >= 0.0f && tc->normal_tolerance <= 4.0f))
+        return fail(c, FOVPT_E_INVALID, "%s: normal_tolerance %g outside [0, 4]", who, (double)tc->normal_tolerance);
+    if (!(tc->depth_tolerance >= 0.0f && tc->depth_tolerance <= 1.0f))
+        return fail(c, FOVPT_E_INVALID, "%s: depth_tolerance %g outside [0, 1]", who, (double)tc->depth_tolerance);
+    for (int32_t r : tc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    { const int rc_ = check_rendered_frame(c, lp, who, "reproject from", nullptr); if (rc_) return rc_; }
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    { const int rc_ = reserve_temporal(c, npix); if (rc_) return rc_; }
+    { const int rc_ = own_outputs(c, who, c->tp_color, c->tp_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    if ((void*)out_color == c->tp_hist[0].p || (void*)out_color == c->tp_hist[1].p)
+        return fail(c, FOVPT_E_INVALID, "%s: the output colour buffer is the context's history", who);
+    if (out_motion && (out_motion == out_color || (void*)out_motion == (void*)out_rgba || out_motion == in || (void*)out_motion == c->tp_hist[0].p ||
+                       (void*)out_motion == c->tp_hist[1].p))
+        return fail(c, FOVPT_E_INVALID, "%s: the motion buffer is another buffer of the call or the context's history", who);
+    const hipStream_t st = c->shadow_stream;
+    if (motion && !c->tm_tracking) {                                       // the marks: no mesh has moved yet (0 is no step's number)
+        const size_t nmesh = c->mesh_nv.size();
+        HIPCHK(c, c->tm_mark.reserve(nmesh * sizeof(uint64_t)));
+        HIPCHK(c, hipMemsetAsync(c->tm_mark.p, 0, nmesh * sizeof(uint64_t), st));
+        c->tm_mesh_epoch.assign(nmesh, 0ull);
+        c->tm_tracking = true;
+    }
+    const int cur = c->tp_last ^ 1, prev = c->tp_last;
+    const GBufferDev g = temporal_set(c, cur), gp = temporal_set(c, prev);
+    GBufferDev gt;
+    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, gt, who, &g); if (rc_) return rc_; }   // the rendered frame's camera
+    const FrameDev& fd = c->dn_frame;
+    TemporalArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 4; k++) a.cap[k] = caps[k];
+    a.normal_tol = tc->normal_tolerance; a.depth_tol = tc->depth_tolerance;
+    a.uniform = c->dn_uniform != 0;
+    a.reproject = c->tp_valid && c->tp_w == c->dn_w && c->tp_h == c->dn_h && camera_inverse(c->tp_U, c->tp_V, c->tp_W, a.inv);
+    memcpy(a.eye_prev, c->tp_eye, sizeof(a.eye_prev));
+    if (!motion)
+        fovpt_launch_temporal(st, fd, a, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
+    else {
+        if (c->tm_untracked) a.reproject = 0;                              // meshes moved unrecorded: where they were is not known
+        TemporalMotionArgs m;
+        memset(&m, 0, sizeof(m));
+        m.hit = (const float4*)c->gb_hit.p; m.tris = c->tris;
+        m.mark = (const uint64_t*)c->tm_mark.p; m.epoch = c->tm_epoch;
+        m.tri_vidx = (const uint3*)c->up_vidx.p; m.vtx_prev = (const float*)c->vtx_prev.p;
+        m.out_motion = out_motion;
+        fovpt_launch_temporal_motion(st, fd, a, m, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
+    }
+    HIPCHK(c, hipGetLastError());
+    c->tp_last = cur;                                                      // this step is the next one's previous step
+    c->tp_valid = true;
+    c->tp_w = c->dn_w; c->tp_h = c->dn_h;
+    memcpy(c->tp_eye, fd.eye, sizeof(c->tp_eye)); memcpy(c->tp_U, fd.U, sizeof(c->tp_U));
+    memcpy(c->tp_V, fd.V, sizeof(c->tp_V)); memcpy(c->tp_W, fd.W, sizeof(c->tp_W));
+    c->tm_epoch++;                                                         // the marks of this interval no longer hold
+    c->tm_untracked = false;
+    return FOVPT_OK;
+}
+
 }  // namespace
 
 // the G-buffer's buffers for n pixels (the counters once: k_gbuffer_rays rewrites the queue sizes it uses on every call)
@@ -108,6 +181,7 @@ int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev&
     if (n >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, w, h);
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }
+    c->gb_pixels = n;
     FrameDev fd;
     memset(&fd, 0, sizeof(fd));
     fd.w = w; fd.h = h;
@@ -322,47 +396,14 @@ int fovpt_temporal_reset(fovpt_ctx* c)
 int fovpt_temporal(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
                    fovpt_float4* out_color, uint32_t* out_rgba)
 {
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null argument");
-    const int32_t caps[4] = {tc->history_fovea, tc->history_middle, tc->history_periphery, tc->history_uniform};
-    for (int32_t v : caps)
-        if (v < 1 || v > FOVPT_TEMPORAL_MAX_HISTORY) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: history cap %d outside 1 .. %d", v, FOVPT_TEMPORAL_MAX_HISTORY);
-    if (!(tc->normal_tolerance >= 0.0f && tc->normal_tolerance <= 4.0f))
-        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: normal_tolerance %g outside [0, 4]", (double)tc->normal_tolerance);
-    if (!(tc->depth_tolerance >= 0.0f && tc->depth_tolerance <= 1.0f))
-        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: depth_tolerance %g outside [0, 1]", (double)tc->depth_tolerance);
-    for (int32_t r : tc->_reserved)
-        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: reserved fields must be 0");
-    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_temporal without a scene");
-    { const int rc_ = check_rendered_frame(c, lp, "fovpt_temporal", "reproject from", nullptr); if (rc_) return rc_; }
-    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
-    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_temporal: null accum_buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
-    { const int rc_ = reserve_temporal(c, npix); if (rc_) return rc_; }
-    { const int rc_ = own_outputs(c, "fovpt_temporal", c->tp_color, c->tp_rgba, out_color, out_rgba); if (rc_) return rc_; }
-    if ((void*)out_color == c->tp_hist[0].p || (void*)out_color == c->tp_hist[1].p)
-        return fail(c, FOVPT_E_INVALID, "fovpt_temporal: the output colour buffer is the context's history");
-    const int cur = c->tp_last ^ 1, prev = c->tp_last;
-    const GBufferDev g = temporal_set(c, cur), gp = temporal_set(c, prev);
-    GBufferDev gt;
-    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, gt, "fovpt_temporal", &g); if (rc_) return rc_; }   // the rendered frame's camera
-    const FrameDev& fd = c->dn_frame;
-    TemporalArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int k = 0; k < 4; k++) a.cap[k] = caps[k];
-    a.normal_tol = tc->normal_tolerance; a.depth_tol = tc->depth_tolerance;
-    a.uniform = c->dn_uniform != 0;
-    a.reproject = c->tp_valid && c->tp_w == c->dn_w && c->tp_h == c->dn_h && camera_inverse(c->tp_U, c->tp_V, c->tp_W, a.inv);
-    memcpy(a.eye_prev, c->tp_eye, sizeof(a.eye_prev));
-    fovpt_launch_temporal(c->shadow_stream, fd, a, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
-    HIPCHK(c, hipGetLastError());
-    c->tp_last = cur;                                                      // this step is the next one's previous step
-    c->tp_valid = true;
-    c->tp_w = c->dn_w; c->tp_h = c->dn_h;
-    memcpy(c->tp_eye, fd.eye, sizeof(c->tp_eye)); memcpy(c->tp_U, fd.U, sizeof(c->tp_U));
-    memcpy(c->tp_V, fd.V, sizeof(c->tp_V)); memcpy(c->tp_W, fd.W, sizeof(c->tp_W));
-    return FOVPT_OK;
+    return temporal_step(c, lp, tc, in_color, out_color, out_rgba, nullptr, false, "fovpt_temporal");
+}
+
+// fovpt_temporal with moved meshes reprojected by their own motion (k_temporal_motion) and, with out_motion, motion vectors.
+int fovpt_temporal_motion(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
+                          fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion)
+{
+    return temporal_step(c, lp, tc, in_color, out_color, out_rgba, out_motion, true, "fovpt_temporal_motion");
 }
 
 }  // extern "C"

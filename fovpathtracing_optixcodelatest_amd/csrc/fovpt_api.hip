@@ -729,6 +729,8 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
     c->up_vtx.release(); c->up_vidx.release();       // fovpt_update_vertices' device copies: made again on the scene's first update
     c->refit_pending = false;
+    c->tm_tracking = c->tm_untracked = false;        // fovpt_temporal_motion's tracking: switched on again by its next call
+    c->tm_mark.release(); c->vtx_prev.release();
     uint64_t ntri = 0;
     bool any_tc = false;
     for (int m = 0; m < num_meshes; m++) {
@@ -860,6 +862,27 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
         HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
     }
     float* vtx = (float*)c->up_vtx.p;
+    if (!c->tm_tracking) c->tm_untracked = c->tm_untracked || num_updates > 0;
+    else {
+        // fovpt_temporal_motion's previous positions: what a mesh holds now, ahead of the interval's first overwrite of it
+        HIPCHK(c, c->vtx_prev.reserve(c->h_vtx.size() * 4));
+        VertexTrack g;
+        memset(&g, 0, sizeof(g));
+        for (int k = 0; k < num_updates; k++) {
+            const int mesh = up[k].mesh;
+            if (c->tm_mesh_epoch[mesh] != c->tm_epoch) {
+                c->tm_mesh_epoch[mesh] = c->tm_epoch;
+                g.first[g.count] = c->mesh_vbase[mesh]; g.n[g.count] = up[k].num_vertices; g.mesh[g.count] = (uint32_t)mesh;
+                g.max_n = up[k].num_vertices > g.max_n ? up[k].num_vertices : g.max_n;
+                g.count++;
+            }
+            if (g.count == FOVPT_GATHER_BATCH || (k + 1 == num_updates && g.count)) {
+                fovpt_launch_gather_vertices_prev(st, g, vtx, (float*)c->vtx_prev.p, (uint64_t*)c->tm_mark.p, c->tm_epoch);
+                memset(&g, 0, sizeof(g));
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+    }
     if (device) {
         VertexGather g;
         memset(&g, 0, sizeof(g));
@@ -1152,6 +1175,8 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "bvh_nodes") == 0 && c->has_scene) { *ptr = c->nodes; *bytes = (size_t)c->stats.bvh_bytes; return FOVPT_OK; }   // tools/bvhstat.py
     if (strcmp(name, "bvh_tris") == 0 && c->has_scene) { *ptr = c->tris; *bytes = (size_t)c->stats.tri_bytes; return FOVPT_OK; }
     if (strcmp(name, "scene_vertices") == 0 && c->up_vtx.p) { *ptr = c->up_vtx.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_update_vertices
+    if (strcmp(name, "scene_vertices_prev") == 0 && c->vtx_prev.p) { *ptr = c->vtx_prev.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_temporal_motion
+    if (strcmp(name, "gbuffer_hit") == 0 && c->gb_hit.p) { *ptr = c->gb_hit.p; *bytes = c->gb_pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {
         {"sq_o", &S.sq_o[0]}, {"sq_d", &S.sq_d[0]}, {"sq_vis", &S.sq_vis[0]}, {"sq_occ", &S.sq_occ[0]}, {"counters", &S.counters},

@@ -122,6 +122,19 @@ struct fovpt_ctx {
     bool tp_valid = false;
     int tp_w = 0, tp_h = 0;
     float tp_eye[3] = {}, tp_U[3] = {}, tp_V[3] = {}, tp_W[3] = {};
+    // fovpt_temporal_motion: tracking of the positions meshes had at the previous temporal step.  Switched on by a context's
+    // first fovpt_temporal_motion (tm_tracking; off again after fovpt_set_scene), which makes tm_mark: per mesh the number of the
+    // step (tm_epoch, counted over both entry points) before which fovpt_update_vertices last moved it, 0 = never; the host's
+    // copy is tm_mesh_epoch.  A mesh has moved since the previous step when its mark equals tm_epoch, so ending an interval is
+    // tm_epoch++ on the host and nothing on the device.  vtx_prev (12 B per vertex, made by the first tracked update) holds, for
+    // the marked meshes, what up_vtx held before the interval's first update of them.  tm_untracked: an update ran since the
+    // previous step while tracking was off (the next fovpt_temporal_motion step has no history).  gb_pixels: the pixels of the
+    // last G-buffer trace (fovpt_debug_buffer "gbuffer_hit")
+    bool tm_tracking = false, tm_untracked = false;
+    uint64_t tm_epoch = 1;                 // (64 bits: never wraps)
+    std::vector<uint64_t> tm_mesh_epoch;
+    DevBuf tm_mark, vtx_prev;
+    size_t gb_pixels = 0;
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;

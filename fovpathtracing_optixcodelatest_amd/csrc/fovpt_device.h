@@ -291,6 +291,21 @@ struct TemporalArgs {
 };
 void fovpt_launch_temporal(hipStream_t st, const FrameDev& fd, const TemporalArgs& a, const fovpt_float4* in, GBufferDev g, GBufferDev gp,
                            const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_temporal_motion (temporal.hip, k_temporal_motion): what it reads beside k_temporal's inputs.  A hit pixel's mesh (the
+// mesh of its triangle record, found through the hit record) has moved since the previous step when mark[mesh] == epoch; only
+// then are tri_vidx, vtx_prev and the rest of the two records read.
+struct TemporalMotionArgs {
+    const float4* hit;                  // the G-buffer trace's hit records: t, u, v, record position in leaf order as bits
+    const TriRec* tris;
+    const uint64_t* mark;               // per mesh: the step (TemporalMotionArgs::epoch) before which it last moved
+    const uint3* tri_vidx;              // per global primitive id its three vertices in vtx_prev (null until a mesh is marked)
+    const float* vtx_prev;              // the positions marked meshes had at the previous step (null until a mesh is marked)
+    fovpt_float4* out_motion;           // null: no motion vectors
+    uint64_t epoch;                     // (64 bits: never wraps, so a stale mark never comes true again)
+};
+void fovpt_launch_temporal_motion(hipStream_t st, const FrameDev& fd, const TemporalArgs& a, const TemporalMotionArgs& m, const fovpt_float4* in,
+                                  GBufferDev g, GBufferDev gp, const float4* hist_prev, float4* hist_out, fovpt_float4* out_color,
+                                  uint32_t* out_rgba);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32
@@ -302,6 +317,16 @@ struct VertexGather {                   // up to FOVPT_GATHER_BATCH device array
     uint32_t max_n;
 };
 void fovpt_launch_gather_vertices(hipStream_t st, const VertexGather& g, float* vtx);
+// the copy-on-first-write of fovpt_temporal_motion's tracking: the batch's meshes (src: their positions in vtx) into vtx_prev,
+// and mark[mesh[u]] = epoch
+struct VertexTrack {
+    uint32_t first[FOVPT_GATHER_BATCH]; // first vertex in vtx and vtx_prev
+    uint32_t n[FOVPT_GATHER_BATCH];     // vertices
+    uint32_t mesh[FOVPT_GATHER_BATCH];
+    int32_t count;
+    uint32_t max_n;
+};
+void fovpt_launch_gather_vertices_prev(hipStream_t st, const VertexTrack& g, const float* vtx, float* vtx_prev, uint64_t* mark, uint64_t epoch);
 // one launch per level of the wide tree, deepest first (levels[0 .. num_levels]: level_first of the build)
 void fovpt_launch_refit(hipStream_t st, BvhNode4* nodes, TriRec* tris, const uint32_t* levels, uint32_t num_levels, const uint3* tri_vidx,
                         const float* vtx);

@@ -36,6 +36,18 @@ __global__ void k_gather_vertices(VertexGather g, float* __restrict__ vtx)
     }
 }
 
+// fovpt_temporal_motion's tracking: the positions a mesh has now into vtx_prev, before this update overwrites them, and the
+// mesh's mark (one plain vector store)
+__global__ void k_gather_vertices_prev(VertexTrack g, const float* __restrict__ vtx, float* __restrict__ vtx_prev, uint64_t* __restrict__ mark,
+                                       uint64_t epoch)
+{
+    for (int u = blockIdx.y; u < g.count; u += gridDim.y) {
+        const size_t first = 3 * (size_t)g.first[u], n = 3 * (size_t)g.n[u];
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) vtx_prev[first + i] = vtx[first + i];
+        if (blockIdx.x == 0 && threadIdx.x == 0) mark[g.mesh[u]] = epoch;
+    }
+}
+
 __global__ void k_refit_level(uint32_t first, uint32_t count, BvhNode4* __restrict__ nodes, TriRec* __restrict__ tris,
                               const uint3* __restrict__ tri_vidx, const float* __restrict__ vtx)
 {
@@ -95,6 +107,14 @@ void fovpt_launch_gather_vertices(hipStream_t st, const VertexGather& g, float* 
     const uint64_t floats = 3ull * g.max_n;
     const uint32_t gx = (uint32_t)(floats < 1024ull * FOVPT_BLOCK ? (floats + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
     hipLaunchKernelGGL(k_gather_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, vtx);
+}
+
+void fovpt_launch_gather_vertices_prev(hipStream_t st, const VertexTrack& g, const float* vtx, float* vtx_prev, uint64_t* mark, uint64_t epoch)
+{
+    if (g.count <= 0) return;
+    const uint64_t floats = 3ull * (g.max_n ? g.max_n : 1u);                  // (a mesh without vertices still gets its mark)
+    const uint32_t gx = (uint32_t)(floats < 1024ull * FOVPT_BLOCK ? (floats + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
+    hipLaunchKernelGGL(k_gather_vertices_prev, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, vtx, vtx_prev, mark, epoch);
 }
 
 void fovpt_launch_refit(hipStream_t st, BvhNode4* nodes, TriRec* tris, const uint32_t* levels, uint32_t num_levels, const uint3* tri_vidx,

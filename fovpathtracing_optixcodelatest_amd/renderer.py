@@ -93,6 +93,8 @@ class SampleRenderer:
         self.launchParams.traversable = trav.value                      # SimplePathtracer.cpp:61
         self.lastSetCamera = Camera()
         self._frame_ptrs = abi.FramePtrs()
+        self._device = int(device)
+        self._motion = None
 
     # -- plumbing -----------------------------------------------------------------------
     def _check(self, rc):
@@ -330,6 +332,32 @@ class SampleRenderer:
     def downloadTemporalHistory(self):
         """The history the last temporal step wrote: (H, W, 4) float32, rgb its output colour, w the history length."""
         return self._download_frame(self.temporal_buffers()[2], 4)
+
+    # -- the temporal step for animated scenes (include/fovpt.h, fovpt_temporal_motion)
+    def temporal_motion(self, cfg=None, in_color=None, out_color=None, out_rgba=None, out_motion=None):
+        """temporal() with the meshes update_vertices() has moved since the previous step reprojected by their own motion: the
+        same history, buffers and ordering.  out_motion: device pointer of a float4 frame for the per-pixel motion vectors
+        (px - x, py - y, depth in the previous camera, 1), zeros where the pixel does not reproject; None: none are written
+        (motion_buffer() is the renderer's own).  Call it before update_vertices() moves the meshes for the next frame."""
+        cfg = cfg if cfg is not None else self.temporal_defaults()
+        self._check(self._L.fovpt_temporal_motion(self._ctx, C.byref(self.launchParams), C.byref(cfg), in_color, out_color, out_rgba,
+                                                  out_motion))
+
+    def motion_buffer(self):
+        """Device address of the renderer's own motion-vector buffer (float4 per pixel of the current frame size), made on
+        first use and after a resize: pass it as temporal_motion(out_motion=...), read it with downloadMotion()."""
+        import torch
+        f = self.launchParams.frame
+        shape = (f.size.y, f.size.x, 4)
+        if self._motion is None or tuple(self._motion.shape) != shape:
+            self.synchronize()                 # (a step may still be writing the buffer this one replaces)
+            self._motion = torch.zeros(shape, dtype=torch.float32, device="cuda:%d" % self._device)
+            torch.cuda.synchronize(self._device)
+        return self._motion.data_ptr()
+
+    def downloadMotion(self):
+        """The motion vectors the last temporal_motion(out_motion=motion_buffer()) wrote: (H, W, 4) float32."""
+        return self._download_frame(self.motion_buffer(), 4)
 
     # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
     def update_vertices(self, updates, rebuild=False):

@@ -154,6 +154,26 @@ public:
         check(fovpt_temporal_buffers(ctx, &color, &rgba, &history));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- the temporal step for animated scenes (include/fovpt.h, fovpt_temporal_motion): temporal() with the meshes updateAccel()
+    // has moved since the previous step reprojected by their own motion -- the same history and buffers, so the two may be mixed.
+    // out_motion: device memory for one float4 per pixel (px - x, py - y, depth in the previous camera, 1; zeros where the pixel
+    // does not reproject), or nullptr.  Call it before updateAccel() moves the meshes for the next frame.
+    void temporalMotion(const fovpt_float4* in_color = nullptr, fovpt_float4* out_motion = nullptr)
+    {
+        fovpt_temporal_config tc;
+        check(fovpt_temporal_defaults(&tc));
+        temporalMotion(tc, in_color, out_motion);
+    }
+    void temporalMotion(const fovpt_temporal_config& tc, const fovpt_float4* in_color = nullptr, fovpt_float4* out_motion = nullptr)
+    {
+        check(fovpt_temporal_motion(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &tc, in_color, nullptr, nullptr, out_motion));
+        check(fovpt_synchronize(ctx));
+    }
+    // the motion vectors a temporalMotion() wrote to d_motion, one float4 per pixel
+    void downloadMotion(const fovpt_float4* d_motion, float4 h_motion[])
+    {
+        check(fovpt_download(ctx, d_motion, h_motion, sizeof(float4) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
     // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
     // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true
