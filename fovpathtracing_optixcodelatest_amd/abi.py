@@ -246,6 +246,23 @@ class TemporalConfig(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+POST_DENOISE, POST_RECONSTRUCT, POST_TEMPORAL, POST_MOTION = 1, 2, 4, 8     # FOVPT_POST_*
+
+
+class PostConfig(C.Structure):
+    """fovpt_post_config: the stages of the post-frame chain (POST_* bits) and each stage's own config (defaults: fovpt_post_defaults)."""
+    _fields_ = [
+        ("stages", C.c_int32),
+        ("_reserved", C.c_int32 * 3),
+        ("denoise", DenoiseConfig), ("reconstruct", ReconstructConfig), ("temporal", TemporalConfig),
+    ]
+
+    def copy(self):
+        m = PostConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(PostConfig))
+        return m
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
@@ -270,6 +287,7 @@ assert C.sizeof(LaunchParams) == 248
 assert C.sizeof(DenoiseConfig) == 32
 assert C.sizeof(ReconstructConfig) == 32 and C.sizeof(GBufferPtrs) == 40
 assert C.sizeof(TemporalConfig) == 32
+assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.reconstruct.offset, PostConfig.temporal.offset) == (16, 48, 80)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232

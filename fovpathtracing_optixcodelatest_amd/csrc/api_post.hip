@@ -66,14 +66,90 @@ bool camera_inverse(const float* U, const float* V, const float* W, float* inv)
     return true;
 }
 
-// One step of the history for fovpt_temporal (motion false: k_temporal, and no HIP call beside those of the G-buffer and
-// that launch) and fovpt_temporal_motion (motion true: k_temporal_motion; the first one of a scene switches the tracking of
-// previous positions on).  Either ends the interval in which fovpt_update_vertices marks meshes as moved.
-int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
-                  fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion, bool motion, const char* who)
+// ---- what the entry points and fovpt_post share: per stage its validation (nothing allocated, enqueued or changed), its kernel
+// arguments, and its launches ----------------------------------------------------------------------------------------------
+
+// fovpt_denoise's validation
+int denoise_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoise_config* dc, const char* who)
 {
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const int32_t its[4] = {dc->iterations_fovea, dc->iterations_middle, dc->iterations_periphery, dc->iterations_uniform};
+    for (int32_t n : its)
+        if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "%s: iteration count %d outside 0 .. %d", who, n, FOVPT_DENOISE_MAX_ITERATIONS);
+    const float sig[3] = {dc->color_sigma, dc->normal_sigma, dc->albedo_sigma};
+    for (float v : sig)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "%s: sigma %g outside [%g, %g]", who, (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    { const int rc_ = check_rendered_frame(c, lp, who, "filter with", "fovpt_denoise needs the denoiser guides: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)"); if (rc_) return rc_; }
+    if (!lp->frame.color_buffer || !lp->frame.normal_buffer || !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "%s: null guide buffers", who);
+    return FOVPT_OK;
+}
+
+// the denoiser's buffers and launches for a checked call; out_color / out_rgba are set
+int denoise_enqueue(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoise_config* dc, fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    HIPCHK(c, c->dn_level.reserve(npix));
+    HIPCHK(c, c->dn_i0.reserve(npix * 16));
+    HIPCHK(c, c->dn_i1.reserve(npix * 16));
+
+    // the level map: the passes fovpt_render ran for this frame
+    const FrameDev& fd = c->dn_frame;
+    DenoiseArgs a;
+    memset(&a, 0, sizeof(a));
+    if (c->dn_uniform) a.n_pass[0] = dc->iterations_uniform;
+    else { a.n_pass[0] = dc->iterations_periphery; a.n_pass[1] = dc->iterations_middle; a.n_pass[2] = dc->iterations_fovea; }
+    for (int p = 0; p < fd.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
+    a.inv_c = inv_sq(dc->color_sigma); a.inv_n = inv_sq(dc->normal_sigma); a.inv_a = inv_sq(dc->albedo_sigma);
+    fovpt_launch_denoise(c->shadow_stream, fd, a, lp->frame.color_buffer, lp->frame.normal_buffer, lp->frame.albedo_buffer,
+                         (float4*)c->dn_i0.p, (float4*)c->dn_i1.p, (uint8_t*)c->dn_level.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// fovpt_reconstruct's validation.  in: its colour input, or null where an earlier stage of fovpt_post makes it
+int reconstruct_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_reconstruct_config* rc, const fovpt_float4* in, const char* who)
+{
+    if (!(rc->support >= 1.0f && rc->support <= 2.0f)) return fail(c, FOVPT_E_INVALID, "%s: support %g outside [1, 2]", who, (double)rc->support);
+    const float sig[2] = {rc->normal_sigma, rc->depth_sigma};
+    for (float v : sig)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "%s: sigma %g outside [%g, %g]", who, (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    if (rc->levels < 0 || rc->levels > 3) return fail(c, FOVPT_E_INVALID, "%s: levels %d outside 0 .. 3", who, rc->levels);
+    if (rc->remodulate != 0 && rc->remodulate != 1) return fail(c, FOVPT_E_INVALID, "%s: remodulate %d is neither 0 nor 1", who, rc->remodulate);
+    for (int32_t r : rc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    const char* need_guides = "fovpt_reconstruct with remodulate = 1 needs the albedo guide: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)";
+    { const int rc_ = check_rendered_frame(c, lp, who, "reconstruct from", rc->remodulate ? need_guides : nullptr); if (rc_) return rc_; }
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+    if (rc->remodulate && !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "%s: null albedo guide", who);
+    return FOVPT_OK;
+}
+
+ReconstructArgs reconstruct_args(const fovpt_reconstruct_config* rc)
+{
+    ReconstructArgs a;
+    memset(&a, 0, sizeof(a));
+    const float s = rc->support;
+    a.inv_support[0] = 1.0f / (s * 2.0f);
+    a.inv_support[1] = 1.0f / (s * 4.0f);
+    a.inv_n = inv_sq(rc->normal_sigma); a.inv_z = inv_sq(rc->depth_sigma);
+    a.levels = rc->levels; a.remodulate = rc->remodulate;
+    return a;
+}
+
+// the rendered frame's G-buffer (into fovpt_gbuffer's buffers) and the reconstruction, for a checked call with its outputs set
+int reconstruct_enqueue(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_reconstruct_config* rc, const fovpt_float4* in,
+                        fovpt_float4* out_color, uint32_t* out_rgba, const char* who)
+{
+    GBufferDev g;
+    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, who); if (rc_) return rc_; }   // the rendered frame's camera
+    fovpt_launch_reconstruct(c->shadow_stream, c->dn_frame, reconstruct_args(rc), in, lp->frame.albedo_buffer, g, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// the validation of fovpt_temporal and fovpt_temporal_motion.  in: as reconstruct_check's
+int temporal_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in, const char* who)
+{
     const int32_t caps[4] = {tc->history_fovea, tc->history_middle, tc->history_periphery, tc->history_uniform};
     for (int32_t v : caps)
         if (v < 1 || v > FOVPT_TEMPORAL_MAX_HISTORY) return fail(c, FOVPT_E_INVALID, "%s: history cap %d outside 1 .. %d", who, v, FOVPT_TEMPORAL_MAX_HISTORY);
@@ -85,17 +161,31 @@ int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_tempo
         if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
     if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
     { const int rc_ = check_rendered_frame(c, lp, who, "reproject from", nullptr); if (rc_) return rc_; }
-    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
     if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
-    { const int rc_ = reserve_temporal(c, npix); if (rc_) return rc_; }
-    { const int rc_ = own_outputs(c, who, c->tp_color, c->tp_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    return FOVPT_OK;
+}
+
+// what a temporal step's outputs must not be (the histories exist: reserve_temporal)
+int temporal_alias_check(fovpt_ctx* c, const fovpt_float4* in, const fovpt_float4* out_color, const uint32_t* out_rgba, const fovpt_float4* out_motion,
+                         const char* who)
+{
     if ((void*)out_color == c->tp_hist[0].p || (void*)out_color == c->tp_hist[1].p)
         return fail(c, FOVPT_E_INVALID, "%s: the output colour buffer is the context's history", who);
     if (out_motion && (out_motion == out_color || (void*)out_motion == (void*)out_rgba || out_motion == in || (void*)out_motion == c->tp_hist[0].p ||
                        (void*)out_motion == c->tp_hist[1].p))
         return fail(c, FOVPT_E_INVALID, "%s: the motion buffer is another buffer of the call or the context's history", who);
+    return FOVPT_OK;
+}
+
+// One step of the history, for a checked call with its outputs set: fovpt_temporal's (motion false: k_temporal, and no HIP call
+// beside those of the G-buffer and that launch) or fovpt_temporal_motion's (motion true: k_temporal_motion; the first one of a
+// scene switches the tracking of previous positions on).  Either ends the interval in which fovpt_update_vertices marks meshes
+// as moved.  With `fuse` (fovpt_post) the step's input is the reconstruction of `in` by those arguments, made from the step's own
+// G-buffer set inside the step's kernel (k_reconstruct_temporal) and written nowhere.
+int temporal_enqueue(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in,
+                     fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion, bool motion, const char* who,
+                     const ReconstructArgs* fuse = nullptr)
+{
     const hipStream_t st = c->shadow_stream;
     if (motion && !c->tm_tracking) {                                       // the marks: no mesh has moved yet (0 is no step's number)
         const size_t nmesh = c->mesh_nv.size();
@@ -111,23 +201,25 @@ int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_tempo
     const FrameDev& fd = c->dn_frame;
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
-    for (int k = 0; k < 4; k++) a.cap[k] = caps[k];
+    a.cap[0] = tc->history_fovea; a.cap[1] = tc->history_middle; a.cap[2] = tc->history_periphery; a.cap[3] = tc->history_uniform;
     a.normal_tol = tc->normal_tolerance; a.depth_tol = tc->depth_tolerance;
     a.uniform = c->dn_uniform != 0;
     a.reproject = c->tp_valid && c->tp_w == c->dn_w && c->tp_h == c->dn_h && camera_inverse(c->tp_U, c->tp_V, c->tp_W, a.inv);
     memcpy(a.eye_prev, c->tp_eye, sizeof(a.eye_prev));
-    if (!motion)
-        fovpt_launch_temporal(st, fd, a, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
-    else {
+    const float4* hist_prev = (const float4*)c->tp_hist[prev].p;
+    float4* hist_out = (float4*)c->tp_hist[cur].p;
+    TemporalMotionArgs m;
+    memset(&m, 0, sizeof(m));
+    if (motion) {
         if (c->tm_untracked) a.reproject = 0;                              // meshes moved unrecorded: where they were is not known
-        TemporalMotionArgs m;
-        memset(&m, 0, sizeof(m));
         m.hit = (const float4*)c->gb_hit.p; m.tris = c->tris;
         m.mark = (const uint64_t*)c->tm_mark.p; m.epoch = c->tm_epoch;
         m.tri_vidx = (const uint3*)c->up_vidx.p; m.vtx_prev = (const float*)c->vtx_prev.p;
         m.out_motion = out_motion;
-        fovpt_launch_temporal_motion(st, fd, a, m, in, g, gp, (const float4*)c->tp_hist[prev].p, (float4*)c->tp_hist[cur].p, out_color, out_rgba);
     }
+    if (fuse) fovpt_launch_reconstruct_temporal(st, fd, *fuse, a, motion ? &m : nullptr, in, lp->frame.albedo_buffer, g, gp, hist_prev, hist_out, out_color, out_rgba);
+    else if (!motion) fovpt_launch_temporal(st, fd, a, in, g, gp, hist_prev, hist_out, out_color, out_rgba);
+    else fovpt_launch_temporal_motion(st, fd, a, m, in, g, gp, hist_prev, hist_out, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
     c->tp_last = cur;                                                      // this step is the next one's previous step
     c->tp_valid = true;
@@ -137,6 +229,21 @@ int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_tempo
     c->tm_epoch++;                                                         // the marks of this interval no longer hold
     c->tm_untracked = false;
     return FOVPT_OK;
+}
+
+// fovpt_temporal (motion false) and fovpt_temporal_motion (motion true)
+int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
+                  fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion, bool motion, const char* who)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !tc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    { const int rc_ = temporal_check(c, lp, tc, in, who); if (rc_) return rc_; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = reserve_temporal(c, (size_t)c->dn_w * (size_t)c->dn_h); if (rc_) return rc_; }
+    { const int rc_ = own_outputs(c, who, c->tp_color, c->tp_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    { const int rc_ = temporal_alias_check(c, in, out_color, out_rgba, out_motion, who); if (rc_) return rc_; }
+    return temporal_enqueue(c, lp, tc, in, out_color, out_rgba, out_motion, motion, who);
 }
 
 }  // namespace
@@ -254,33 +361,10 @@ int fovpt_denoise(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_denoi
 {
     if (!c) return FOVPT_E_INVALID;
     if (!lp || !dc) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null argument");
-    const int32_t its[4] = {dc->iterations_fovea, dc->iterations_middle, dc->iterations_periphery, dc->iterations_uniform};
-    for (int32_t n : its)
-        if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: iteration count %d outside 0 .. %d", n, FOVPT_DENOISE_MAX_ITERATIONS);
-    const float sig[3] = {dc->color_sigma, dc->normal_sigma, dc->albedo_sigma};
-    for (float v : sig)
-        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
-    { const int rc_ = check_rendered_frame(c, lp, "fovpt_denoise", "filter with", "fovpt_denoise needs the denoiser guides: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)"); if (rc_) return rc_; }
-    if (!lp->frame.color_buffer || !lp->frame.normal_buffer || !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_denoise: null guide buffers");
+    { const int rc_ = denoise_check(c, lp, dc, "fovpt_denoise"); if (rc_) return rc_; }
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
     { const int rc_ = own_outputs(c, "fovpt_denoise", c->dn_color, c->dn_rgba, out_color, out_rgba); if (rc_) return rc_; }
-    HIPCHK(c, c->dn_level.reserve(npix));
-    HIPCHK(c, c->dn_i0.reserve(npix * 16));
-    HIPCHK(c, c->dn_i1.reserve(npix * 16));
-
-    // the level map: the passes fovpt_render ran for this frame
-    const FrameDev& fd = c->dn_frame;
-    DenoiseArgs a;
-    memset(&a, 0, sizeof(a));
-    if (c->dn_uniform) a.n_pass[0] = dc->iterations_uniform;
-    else { a.n_pass[0] = dc->iterations_periphery; a.n_pass[1] = dc->iterations_middle; a.n_pass[2] = dc->iterations_fovea; }
-    for (int p = 0; p < fd.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
-    a.inv_c = inv_sq(dc->color_sigma); a.inv_n = inv_sq(dc->normal_sigma); a.inv_a = inv_sq(dc->albedo_sigma);
-    fovpt_launch_denoise(c->shadow_stream, fd, a, lp->frame.color_buffer, lp->frame.normal_buffer, lp->frame.albedo_buffer,
-                         (float4*)c->dn_i0.p, (float4*)c->dn_i1.p, (uint8_t*)c->dn_level.p, out_color, out_rgba);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
+    return denoise_enqueue(c, lp, dc, out_color, out_rgba);
 }
 
 // ---- G-buffer and reconstruction of the rendered frame (reconstruct.hip; the reconstruction's definition:
@@ -327,36 +411,12 @@ int fovpt_reconstruct(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_r
 {
     if (!c) return FOVPT_E_INVALID;
     if (!lp || !rc) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null argument");
-    if (!(rc->support >= 1.0f && rc->support <= 2.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: support %g outside [1, 2]", (double)rc->support);
-    const float sig[2] = {rc->normal_sigma, rc->depth_sigma};
-    for (float v : sig)
-        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: sigma %g outside [%g, %g]", (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
-    if (rc->levels < 0 || rc->levels > 3) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: levels %d outside 0 .. 3", rc->levels);
-    if (rc->remodulate != 0 && rc->remodulate != 1) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: remodulate %d is neither 0 nor 1", rc->remodulate);
-    for (int32_t r : rc->_reserved)
-        if (r != 0) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: reserved fields must be 0");
-    if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "fovpt_reconstruct without a scene");
-    const char* need_guides = "fovpt_reconstruct with remodulate = 1 needs the albedo guide: the frame was rendered without fovpt_config.write_guides = 1 (not available with shadow-catcher materials)";
-    { const int rc_ = check_rendered_frame(c, lp, "fovpt_reconstruct", "reconstruct from", rc->remodulate ? need_guides : nullptr); if (rc_) return rc_; }
     const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
-    if (!in) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null accum_buffer");
-    if (rc->remodulate && !lp->frame.albedo_buffer) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: null albedo guide");
+    { const int rc_ = reconstruct_check(c, lp, rc, in, "fovpt_reconstruct"); if (rc_) return rc_; }
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc_ = own_outputs(c, "fovpt_reconstruct", c->rc_color, c->rc_rgba, out_color, out_rgba); if (rc_) return rc_; }
     if (in == out_color) return fail(c, FOVPT_E_INVALID, "fovpt_reconstruct: the input is the output colour buffer (it reads neighbours)");
-    GBufferDev g;
-    { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, "fovpt_reconstruct"); if (rc_) return rc_; }   // the rendered frame's camera
-    const FrameDev& fd = c->dn_frame;
-    ReconstructArgs a;
-    memset(&a, 0, sizeof(a));
-    const float s = rc->support;
-    a.inv_support[0] = 1.0f / (s * 2.0f);
-    a.inv_support[1] = 1.0f / (s * 4.0f);
-    a.inv_n = inv_sq(rc->normal_sigma); a.inv_z = inv_sq(rc->depth_sigma);
-    a.levels = rc->levels; a.remodulate = rc->remodulate;
-    fovpt_launch_reconstruct(c->shadow_stream, fd, a, in, lp->frame.albedo_buffer, g, out_color, out_rgba);
-    HIPCHK(c, hipGetLastError());
-    return FOVPT_OK;
+    return reconstruct_enqueue(c, lp, rc, in, out_color, out_rgba, "fovpt_reconstruct");
 }
 
 // ---- temporal reprojection of the frame history (temporal.hip; its definition: tests/temporal_ref.py) ------------------
@@ -404,6 +464,84 @@ int fovpt_temporal_motion(fovpt_ctx* c, const fovpt_launch_params* lp, const fov
                           fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion)
 {
     return temporal_step(c, lp, tc, in_color, out_color, out_rgba, out_motion, true, "fovpt_temporal_motion");
+}
+
+// ---- the post-frame chain in one call (the fused kernel: post_fused.hip; its definition: tests/post_ref.py) --------------
+int fovpt_post_defaults(fovpt_post_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->stages = FOVPT_POST_RECONSTRUCT | FOVPT_POST_TEMPORAL | FOVPT_POST_MOTION;
+    (void)fovpt_denoise_defaults(&out->denoise);
+    (void)fovpt_reconstruct_defaults(&out->reconstruct);
+    (void)fovpt_temporal_defaults(&out->temporal);
+    return FOVPT_OK;
+}
+
+int fovpt_post_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_post_buffers", c->po_color, c->po_rgba, *color, *rgba);
+}
+
+// The enabled stage calls one after the other, on fovpt_stream() and ordered like them -- except that the reconstruction and the
+// temporal step together are one G-buffer trace (into the step's set) and one kernel.  Every stage is checked before the first
+// is enqueued and before any state of the step moves.
+int fovpt_post(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_post_config* pc, const fovpt_float4* in_color, fovpt_float4* out_color,
+               uint32_t* out_rgba, fovpt_float4* out_motion)
+{
+    const char* who = "fovpt_post";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !pc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const int32_t all = FOVPT_POST_DENOISE | FOVPT_POST_RECONSTRUCT | FOVPT_POST_TEMPORAL | FOVPT_POST_MOTION;
+    if (pc->stages == 0 || (pc->stages & ~all)) return fail(c, FOVPT_E_INVALID, "%s: stages %d names no stage or an unknown one", who, pc->stages);
+    const bool D = pc->stages & FOVPT_POST_DENOISE, R = pc->stages & FOVPT_POST_RECONSTRUCT, T = pc->stages & FOVPT_POST_TEMPORAL,
+               M = pc->stages & FOVPT_POST_MOTION;
+    if (M && !T) return fail(c, FOVPT_E_INVALID, "%s: FOVPT_POST_MOTION needs FOVPT_POST_TEMPORAL", who);
+    if (out_motion && !M) return fail(c, FOVPT_E_INVALID, "%s: a motion buffer without FOVPT_POST_MOTION", who);
+    if (in_color && D) return fail(c, FOVPT_E_INVALID, "%s: in_color with FOVPT_POST_DENOISE (the denoiser reads the frame's accum and guides)", who);
+    for (int32_t r : pc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+#if FOVPT_V_STEPSTAT
+    if (R || T) return fail(c, FOVPT_E_INVALID, "%s: the G-buffer is not available in a diagnostic (FOVPT_V_STEPSTAT) build", who);
+#endif
+    // the later stages' colour input where no stage makes it (a stage's output is never null: any non-null value stands for it)
+    const fovpt_float4* in0 = in_color ? in_color : lp->frame.accum_buffer;
+    const fovpt_float4* const made = (const fovpt_float4*)c;
+    if (D) { const int rc_ = denoise_check(c, lp, &pc->denoise, who); if (rc_) return rc_; }
+    if (R) { const int rc_ = reconstruct_check(c, lp, &pc->reconstruct, D ? made : in0, who); if (rc_) return rc_; }
+    if (T) { const int rc_ = temporal_check(c, lp, &pc->temporal, D || R ? made : in0, who); if (rc_) return rc_; }
+
+    // buffers: the denoiser's own where a stage follows it, the step's sets and histories, the call's outputs
+    HIPCHK(c, hipSetDevice(c->device));
+    fovpt_float4* dn_color = nullptr;
+    uint32_t* dn_rgba = nullptr;
+    if (D && (R || T)) { const int rc_ = own_outputs(c, who, c->dn_color, c->dn_rgba, dn_color, dn_rgba); if (rc_) return rc_; }
+    if (T) { const int rc_ = reserve_temporal(c, (size_t)c->dn_w * (size_t)c->dn_h); if (rc_) return rc_; }
+    { const int rc_ = own_outputs(c, who, c->po_color, c->po_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    const fovpt_float4* in = D ? dn_color : in0;                            // what the stage after the denoiser reads
+    if (R && in == out_color) return fail(c, FOVPT_E_INVALID, "%s: the reconstruction's input is the output colour buffer (it reads neighbours)", who);
+    if (T) { const int rc_ = temporal_alias_check(c, in, out_color, out_rgba, out_motion, who); if (rc_) return rc_; }
+    if (R && T) {                                                          // one kernel reads `in` and the albedo guide across pixels
+        const void* wr[4] = {out_rgba, out_motion, c->tp_hist[0].p, c->tp_hist[1].p};
+        const void* alb = pc->reconstruct.remodulate ? (const void*)lp->frame.albedo_buffer : nullptr;
+        for (const void* w : wr)
+            if (w && (w == (const void*)in || w == alb)) return fail(c, FOVPT_E_INVALID, "%s: an output or history buffer is the reconstruction's input or the albedo guide", who);
+        if (alb && (const void*)out_color == alb) return fail(c, FOVPT_E_INVALID, "%s: the output colour buffer is the albedo guide", who);
+    }
+
+    if (D) {
+        const int rc_ = R || T ? denoise_enqueue(c, lp, &pc->denoise, dn_color, dn_rgba) : denoise_enqueue(c, lp, &pc->denoise, out_color, out_rgba);
+        if (rc_) return rc_;
+    }
+    if (R && !T) return reconstruct_enqueue(c, lp, &pc->reconstruct, in, out_color, out_rgba, who);
+    if (T) {
+        ReconstructArgs ra;
+        if (R) ra = reconstruct_args(&pc->reconstruct);
+        return temporal_enqueue(c, lp, &pc->temporal, in, out_color, out_rgba, out_motion, M, who, R ? &ra : nullptr);
+    }
+    return FOVPT_OK;
 }
 
 }  // extern "C"

@@ -135,6 +135,9 @@ struct fovpt_ctx {
     std::vector<uint64_t> tm_mesh_epoch;
     DevBuf tm_mark, vtx_prev;
     size_t gb_pixels = 0;
+    // fovpt_post: the context's own outputs of the chain's last stage, allocated on first use (everything else the chain uses
+    // is the stages' own: the denoiser's buffers, the temporal step's sets, histories and state)
+    DevBuf po_color, po_rgba;
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;

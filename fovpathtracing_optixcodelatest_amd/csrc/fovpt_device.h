@@ -306,6 +306,12 @@ struct TemporalMotionArgs {
 void fovpt_launch_temporal_motion(hipStream_t st, const FrameDev& fd, const TemporalArgs& a, const TemporalMotionArgs& m, const fovpt_float4* in,
                                   GBufferDev g, GBufferDev gp, const float4* hist_prev, float4* hist_out, fovpt_float4* out_color,
                                   uint32_t* out_rgba);
+// fovpt_post with the reconstruction and the temporal step both on (post_fused.hip, k_reconstruct_temporal): fovpt_launch_reconstruct
+// into registers, then fovpt_launch_temporal's step (m null) or fovpt_launch_temporal_motion's (m given) on that colour.  `in` and
+// `albedo` are read across pixels: none of the written buffers may be one of them.
+void fovpt_launch_reconstruct_temporal(hipStream_t st, const FrameDev& fd, const ReconstructArgs& ra, const TemporalArgs& ta,
+                                       const TemporalMotionArgs* m, const fovpt_float4* in, const fovpt_float4* albedo, GBufferDev g,
+                                       GBufferDev gp, const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32

@@ -1,0 +1,248 @@
+// fovpt_post_pixel.h -- the per-pixel bodies of the reconstruction and of the temporal step, each in one place: k_reconstruct
+// (reconstruct.hip), k_temporal / k_temporal_motion (temporal.hip) and k_reconstruct_temporal (post_fused.hip) are these
+// functions between their loads of the input pixel and their stores.  Their definitions, operation by operation, are
+// tests/reconstruct_ref.py, tests/temporal_ref.py and tests/temporal_motion_ref.py; -ffp-contract=off keeps every product and
+// sum a separate binary32 op.
+//
+// A pixel's own G-buffer entry reaches the bodies through an accessor (prim() / pos() / nrm()): GLazy reads memory where the
+// body asks, which is where the separate kernels always read it; GRegs holds an entry that the fused kernel has read once.
+#pragma once
+
+#include "fovpt_device.h"
+#include "fovpt_pixel.h"
+
+namespace {
+
+struct GLazy {
+    const GBufferDev& g;
+    uint32_t idx;
+    __device__ inline uint32_t prim() const { return g.prim[idx]; }
+    __device__ inline float4 pos() const { return g.pos[idx]; }
+    __device__ inline float4 nrm() const { return g.nrm[idx]; }
+};
+struct GRegs {
+    uint32_t prim_;
+    float4 pos_, nrm_;
+    __device__ inline uint32_t prim() const { return prim_; }
+    __device__ inline float4 pos() const { return pos_; }
+    __device__ inline float4 nrm() const { return nrm_; }
+};
+
+__device__ inline V3 demod(const V3& a)                                    // as the denoiser's
+{
+    const float s = a.x + a.y + a.z;
+    if (s > 0.0f) return v3(fmaxf(a.x, 1.0f / 64.0f), fmaxf(a.y, 1.0f / 64.0f), fmaxf(a.z, 1.0f / 64.0f));
+    return v3(1.0f);
+}
+__device__ inline float edge(float d) { const float t = fmaxf(0.0f, 1.0f - d); return t * t; }
+__device__ inline float sq3(const V3& a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
+
+// whether the reconstruction is on for a pixel whose last writer has fill f
+__device__ inline bool reconstruct_level_on(const ReconstructArgs& a, int f) { return f > 1 && (a.levels & (f == 2 ? 1 : 2)); }
+
+// The reconstruction of pixel (x, y), last written by launch (wlx, wly) of pass wp: true and its colour in o, or false where
+// the pixel keeps its input (fill 1, its level masked, or weights that sum to 0).
+template <class G>
+__device__ inline bool reconstruct_pixel(const FrameDev& fd, const ReconstructArgs& a, const fovpt_float4* __restrict__ in,
+                                         const fovpt_float4* __restrict__ albedo, const GBufferDev& g, const G& own, uint32_t x, uint32_t y,
+                                         uint32_t idx, int wp, uint32_t wlx, uint32_t wly, V3& o)
+{
+    const PassDev& P = fd.pass[wp];
+    const int f = P.fill;
+    if (reconstruct_level_on(a, f)) {
+        uint32_t ix, iy;
+        (void)ring_alive(fd, P, wlx, wly, ix, iy);                      // the anchor: the block's sample pixel (may wrap)
+        const float inv_s = a.inv_support[f == 2 ? 0 : 1];
+        const bool miss_p = own.prim() == 0xffffffffu;
+        const float4 xp4 = own.pos(), np4 = own.nrm();
+        const V3 Xp = v3(xp4), Np = v3(np4);
+        const float tp2 = xp4.w * xp4.w;
+        const long long w1 = fd.w - 1, h1 = fd.h - 1;
+        float sw = 0.0f;
+        V3 acc = v3(0.0f);
+#pragma unroll
+        for (int j = -1; j <= 1; j++) {
+            const long long qy = min(max((long long)iy + (long long)(j * f), 0ll), h1);
+            const float hy = fmaxf(0.0f, 1.0f - fabsf((float)((long long)y - qy)) * inv_s);
+#pragma unroll
+            for (int i = -1; i <= 1; i++) {
+                const long long qx = min(max((long long)ix + (long long)(i * f), 0ll), w1);
+                const float hx = fmaxf(0.0f, 1.0f - fabsf((float)((long long)x - qx)) * inv_s);
+                const uint32_t q = (uint32_t)qy * (uint32_t)fd.w + (uint32_t)qx;
+                const bool miss_q = g.prim[q] == 0xffffffffu;
+                float wn = 1.0f, wz = 1.0f;
+                if (miss_p != miss_q) wn = wz = 0.0f;
+                else if (!miss_p) {
+                    const V3 Nq = v3(g.nrm[q]), Xq = v3(g.pos[q]);
+                    wn = edge(sq3(Nq - Np) * a.inv_n);
+                    const float dz = dot(Np, Xq - Xp);
+                    wz = edge(((dz * dz) * a.inv_z) / tp2);
+                }
+                const float wt = ((hx * hy) * wn) * wz;
+                const fovpt_float4 cq = in[q];
+                V3 Iq = v3(cq.x, cq.y, cq.z);
+                if (a.remodulate) {
+                    const fovpt_float4 aq = albedo[q];
+                    const V3 D = demod(v3(aq.x, aq.y, aq.z));
+                    Iq = v3(Iq.x / D.x, Iq.y / D.y, Iq.z / D.z);
+                }
+                sw = sw + wt;
+                acc = acc + Iq * wt;
+            }
+        }
+        if (sw > 0.0f) {
+            o = v3(acc.x / sw, acc.y / sw, acc.z / sw);
+            if (a.remodulate) o = o * demod(v3(g.alb[idx]));
+            return true;
+        }
+    }
+    return false;
+}
+
+// the history cap of a pixel: by the fill of its last writer (found: pass wp), 1 where no pass writes
+__device__ inline int history_cap(const FrameDev& fd, const TemporalArgs& a, bool found, int wp)
+{
+    if (!found) return 1;
+    const int f = fd.pass[wp].fill;
+    return a.uniform ? a.cap[3] : f == 4 ? a.cap[2] : f == 2 ? a.cap[1] : a.cap[0];
+}
+
+// k_gbuffer_rays' direction of pixel (x, y), before normalising
+__device__ inline V3 pixel_ray(const FrameDev& fd, uint32_t x, uint32_t y)
+{
+    const float dx = 2.0f * (((float)x + 0.5f) / (float)fd.w) - 1.0f;
+    const float dy = 2.0f * (((float)y + 0.5f) / (float)fd.h) - 1.0f;
+    const V3 U = v3(fd.U[0], fd.U[1], fd.U[2]), V = v3(fd.V[0], fd.V[1], fd.V[2]), W = v3(fd.W[0], fd.W[1], fd.W[2]);
+    return dx * U + dy * V + W;
+}
+
+// The four bilinear taps of the previous history around (px, py), kept where the previous G-buffer agrees with the pixel's
+// class, normal Np and point Xp: H and nh where enough weight remains.
+__device__ inline void history_taps(const FrameDev& fd, const TemporalArgs& a, const GBufferDev& gp, const float4* __restrict__ hist_prev,
+                                    float px, float py, bool miss_p, const V3& Xp, const V3& Np, float ztol, V3& H, float& nh)
+{
+    const float x0f = floorf(px), y0f = floorf(py);
+    const float fx = px - x0f, fy = py - y0f;
+    const int x0 = (int)x0f, y0 = (int)y0f;
+    const float wt[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
+    float sw = 0.0f, sn = 0.0f;
+    V3 acc = v3(0.0f);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+        if (qx < 0 || qx >= fd.w || qy < 0 || qy >= fd.h) continue;
+        const uint32_t q = (uint32_t)qy * (uint32_t)fd.w + (uint32_t)qx;
+        if ((gp.prim[q] == 0xffffffffu) != miss_p) continue;
+        if (!miss_p) {
+            const V3 Nq = v3(gp.nrm[q]), Xq = v3(gp.pos[q]);
+            if (!(sq3(Nq - Np) <= a.normal_tol)) continue;                   // (a degenerate previous triangle: N' is not finite)
+            if (!(fabsf(dot(Np, Xq - Xp)) <= ztol)) continue;
+        }
+        const float4 hq = hist_prev[q];
+        sw = sw + wt[k];
+        acc = acc + v3(hq) * wt[k];
+        sn = sn + hq.w * wt[k];
+    }
+    if (sw >= 1.0f / 64.0f) {
+        H = v3(acc.x / sw, acc.y / sw, acc.z / sw);
+        nh = sn / sw;
+    }
+}
+
+// k_temporal's history of pixel (x, y) with cap `cap`: H and nh (left as they are where the pixel does not reproject)
+template <class G>
+__device__ inline void temporal_history(const FrameDev& fd, const TemporalArgs& a, const G& own, const GBufferDev& gp,
+                                        const float4* __restrict__ hist_prev, uint32_t x, uint32_t y, int cap, V3& H, float& nh)
+{
+    if (a.reproject && cap > 1) {                                          // (cap 1: n is 1 whatever the history says)
+        const bool miss_p = own.prim() == 0xffffffffu;
+        const float4 xp4 = own.pos();
+        const V3 Xp = v3(xp4);
+        V3 v;
+        if (!miss_p) v = Xp - v3(a.eye_prev[0], a.eye_prev[1], a.eye_prev[2]);
+        else v = pixel_ray(fd, x, y);
+        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
+        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
+        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
+        if (az > 0.0f) {
+            const float fw = (float)fd.w, fh = (float)fd.h;
+            const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
+            const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
+            if (px >= -1.0f && px < fw && py >= -1.0f && py < fh) {        // (NaN fails): x0 in [-1, w - 1], y0 in [-1, h - 1]
+                const V3 Np = v3(own.nrm());
+                history_taps(fd, a, gp, hist_prev, px, py, miss_p, Xp, Np, a.depth_tol * xp4.w, H, nh);
+            }
+        }
+    }
+}
+
+// k_temporal_motion's: temporal_history in which a hit pixel whose mesh is marked (m.mark[mesh] == m.epoch) gets
+// X' = (w0 a' + u b') + v c' and N' = normalize(cross(b' - a', c' - a')) * s from its triangle's previous vertices a', b', c' and
+// its hit's (u, v), s the sign k_gbuffer_fill gave the current normal; every other pixel takes temporal_history's operations.
+// The common case -- an unmarked mesh -- pays for the hit record's last word, one word of the triangle record and the mark,
+// not for the vertex gathers.  With want_motion the projection also runs for cap-1 pixels and mv becomes (px - x, py - y, a.z, 1)
+// where the pixel reprojects.
+template <class G>
+__device__ inline void temporal_motion_history(const FrameDev& fd, const TemporalArgs& a, const TemporalMotionArgs& m, const G& own,
+                                               const GBufferDev& gp, const float4* __restrict__ hist_prev, uint32_t x, uint32_t y,
+                                               uint32_t idx, int cap, bool want_motion, V3& H, float& nh, float4& mv)
+{
+    if (a.reproject && (cap > 1 || want_motion)) {
+        const uint32_t prim = own.prim();
+        const bool miss_p = prim == 0xffffffffu;
+        const float4 xp4 = own.pos();
+        V3 Xp = v3(xp4), Np = v3(0.0f);
+        V3 v;
+        if (!miss_p) {
+            Np = v3(own.nrm());
+            const uint32_t rec = __float_as_uint(m.hit[idx].w) << 4;       // byte offset of the triangle record, as k_gbuffer_fill's
+            const float4* tr = (const float4*)((const char*)m.tris + rec);
+            const uint32_t mesh = __float_as_uint(tr[2].z);
+            if (m.mark[mesh] == m.epoch) {
+                const float4 hit = m.hit[idx];
+                const uint3 iv = m.tri_vidx[prim];
+                const float* pa = m.vtx_prev + 3 * (size_t)iv.x, *pb = m.vtx_prev + 3 * (size_t)iv.y, *pc = m.vtx_prev + 3 * (size_t)iv.z;
+                const V3 A = v3(pa[0], pa[1], pa[2]), B = v3(pb[0], pb[1], pb[2]), Cc = v3(pc[0], pc[1], pc[2]);
+                const float w0 = (1.0f - hit.y) - hit.z;
+                Xp = (w0 * A + hit.y * B) + hit.z * Cc;
+                // s: k_gbuffer_fill's copysignf(1, dot(wo, N_0)) over the current record's edges and k_gbuffer_rays' direction
+                const float4 t0 = tr[0], t1 = tr[1];
+                const V3 N_0 = normalize(cross(v3(t0.w, t1.x, t1.y), v3(t1.z, t1.w, tr[2].x)));
+                const V3 wo = neg(normalize(pixel_ray(fd, x, y)));
+                Np = normalize(cross(B - A, Cc - A)) * copysignf(1.0f, dot(wo, N_0));
+            }
+            v = Xp - v3(a.eye_prev[0], a.eye_prev[1], a.eye_prev[2]);
+        } else v = pixel_ray(fd, x, y);
+        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
+        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
+        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
+        if (az > 0.0f) {
+            const float fw = (float)fd.w, fh = (float)fd.h;
+            const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
+            const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
+            if (px >= -1.0f && px < fw && py >= -1.0f && py < fh) {        // (NaN fails): x0 in [-1, w - 1], y0 in [-1, h - 1]
+                mv = make_float4(px - (float)x, py - (float)y, az, 1.0f);
+                if (cap > 1) history_taps(fd, a, gp, hist_prev, px, py, miss_p, Xp, Np, a.depth_tol * xp4.w, H, nh);
+            }
+        }
+    }
+}
+
+// the blend and the three stores of a temporal step: out = lerp(H, c, 1 / n), n = min(nh + 1, cap), the new history (out, n)
+__device__ inline void temporal_blend(const fovpt_float4& c, const V3& H, float nh, int cap, uint32_t idx, float4* __restrict__ hist_out,
+                                      fovpt_float4* out_color, uint32_t* __restrict__ out_rgba)
+{
+    const float n = fminf(nh + 1.0f, (float)cap);
+    if (n == 1.0f) {                                                       // first step, disocclusion, cap 1: the input, bit for bit
+        out_color[idx] = c;
+        hist_out[idx] = make_float4(c.x, c.y, c.z, 1.0f);
+        out_rgba[idx] = make_color(reinhard(v3(c.x, c.y, c.z) * 16.0f, 1.0f));
+        return;
+    }
+    const V3 o = lerp3(H, v3(c.x, c.y, c.z), 1.0f / n);
+    out_color[idx] = fovpt_float4{o.x, o.y, o.z, 1.0f};
+    hist_out[idx] = f4(o, n);
+    out_rgba[idx] = make_color(reinhard(o * 16.0f, 1.0f));
+}
+
+}  // namespace

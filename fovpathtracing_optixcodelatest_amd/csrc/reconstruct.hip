@@ -12,6 +12,7 @@
 // tests/reconstruct_ref.py; -ffp-contract=off keeps every product and sum of it a separate binary32 op.
 #include "fovpt_device.h"
 #include "fovpt_pixel.h"
+#include "fovpt_post_pixel.h"
 #include "fovpt_scene.h"
 
 namespace {
@@ -70,15 +71,6 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_gbuffer_fill(const FrameDev fd,
     g.alb[idx] = f4(albedo, 0.f);
 }
 
-__device__ inline V3 demod(const V3& a)                                    // as the denoiser's
-{
-    const float s = a.x + a.y + a.z;
-    if (s > 0.0f) return v3(fmaxf(a.x, 1.0f / 64.0f), fmaxf(a.y, 1.0f / 64.0f), fmaxf(a.z, 1.0f / 64.0f));
-    return v3(1.0f);
-}
-__device__ inline float edge(float d) { const float t = fmaxf(0.0f, 1.0f - d); return t * t; }
-__device__ inline float sq3(const V3& a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
-
 __global__ __launch_bounds__(FOVPT_BLOCK) void k_reconstruct(const FrameDev fd, ReconstructArgs a, const fovpt_float4* __restrict__ in,
                                                              const fovpt_float4* __restrict__ albedo, GBufferDev g,
                                                              fovpt_float4* __restrict__ out_color, uint32_t* __restrict__ out_rgba)
@@ -90,56 +82,11 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_reconstruct(const FrameDev fd, 
     int wp = 0;
     uint32_t wlx, wly;
     if (find_last_writer(fd, x, y, wp, wlx, wly)) {
-        const PassDev& P = fd.pass[wp];
-        const int f = P.fill;
-        if (f > 1 && (a.levels & (f == 2 ? 1 : 2))) {
-            uint32_t ix, iy;
-            (void)ring_alive(fd, P, wlx, wly, ix, iy);                      // the anchor: the block's sample pixel (may wrap)
-            const float inv_s = a.inv_support[f == 2 ? 0 : 1];
-            const bool miss_p = g.prim[idx] == 0xffffffffu;
-            const float4 xp4 = g.pos[idx], np4 = g.nrm[idx];
-            const V3 Xp = v3(xp4), Np = v3(np4);
-            const float tp2 = xp4.w * xp4.w;
-            const long long w1 = fd.w - 1, h1 = fd.h - 1;
-            float sw = 0.0f;
-            V3 acc = v3(0.0f);
-#pragma unroll
-            for (int j = -1; j <= 1; j++) {
-                const long long qy = min(max((long long)iy + (long long)(j * f), 0ll), h1);
-                const float hy = fmaxf(0.0f, 1.0f - fabsf((float)((long long)y - qy)) * inv_s);
-#pragma unroll
-                for (int i = -1; i <= 1; i++) {
-                    const long long qx = min(max((long long)ix + (long long)(i * f), 0ll), w1);
-                    const float hx = fmaxf(0.0f, 1.0f - fabsf((float)((long long)x - qx)) * inv_s);
-                    const uint32_t q = (uint32_t)qy * (uint32_t)fd.w + (uint32_t)qx;
-                    const bool miss_q = g.prim[q] == 0xffffffffu;
-                    float wn = 1.0f, wz = 1.0f;
-                    if (miss_p != miss_q) wn = wz = 0.0f;
-                    else if (!miss_p) {
-                        const V3 Nq = v3(g.nrm[q]), Xq = v3(g.pos[q]);
-                        wn = edge(sq3(Nq - Np) * a.inv_n);
-                        const float dz = dot(Np, Xq - Xp);
-                        wz = edge(((dz * dz) * a.inv_z) / tp2);
-                    }
-                    const float wt = ((hx * hy) * wn) * wz;
-                    const fovpt_float4 cq = in[q];
-                    V3 Iq = v3(cq.x, cq.y, cq.z);
-                    if (a.remodulate) {
-                        const fovpt_float4 aq = albedo[q];
-                        const V3 D = demod(v3(aq.x, aq.y, aq.z));
-                        Iq = v3(Iq.x / D.x, Iq.y / D.y, Iq.z / D.z);
-                    }
-                    sw = sw + wt;
-                    acc = acc + Iq * wt;
-                }
-            }
-            if (sw > 0.0f) {
-                V3 o = v3(acc.x / sw, acc.y / sw, acc.z / sw);
-                if (a.remodulate) o = o * demod(v3(g.alb[idx]));
-                out_color[idx] = fovpt_float4{o.x, o.y, o.z, 1.0f};
-                out_rgba[idx] = make_color(reinhard(o * 16.0f, 1.0f));
-                return;
-            }
+        V3 o;
+        if (reconstruct_pixel(fd, a, in, albedo, g, GLazy{g, idx}, x, y, idx, wp, wlx, wly, o)) {   // (fovpt_post_pixel.h)
+            out_color[idx] = fovpt_float4{o.x, o.y, o.z, 1.0f};
+            out_rgba[idx] = make_color(reinhard(o * 16.0f, 1.0f));
+            return;
         }
     }
     out_color[idx] = c;                                                     // unchanged, bit for bit

@@ -359,6 +359,37 @@ class SampleRenderer:
         """The motion vectors the last temporal_motion(out_motion=motion_buffer()) wrote: (H, W, 4) float32."""
         return self._download_frame(self.motion_buffer(), 4)
 
+    # -- the post-frame chain in one call (include/fovpt.h, fovpt_post)
+    @staticmethod
+    def post_defaults() -> abi.PostConfig:
+        d = abi.PostConfig()
+        lib.check(None, lib.load().fovpt_post_defaults(C.byref(d)))
+        return d
+
+    def post(self, cfg=None, in_color=None, out_color=None, out_rgba=None, out_motion=None):
+        """The stages of cfg.stages (abi.POST_DENOISE | POST_RECONSTRUCT | POST_TEMPORAL | POST_MOTION; default reconstruct,
+        temporal, motion) on the frame last rendered, bit for bit denoise(), reconstruct() and temporal() / temporal_motion() made
+        one after the other -- with reconstruct and temporal both on as one G-buffer trace and one kernel.  in_color: device
+        pointer of a float4 frame (None: the accum buffer; not with POST_DENOISE).  out_color / out_rgba: device pointers, or None
+        for the renderer's own buffers (downloadPostColor / downloadPostPixels); out_motion as temporal_motion()'s.  Enqueued
+        on the renderer's stream, not synchronised (the downloads synchronise)."""
+        cfg = cfg if cfg is not None else self.post_defaults()
+        self._check(self._L.fovpt_post(self._ctx, C.byref(self.launchParams), C.byref(cfg), in_color, out_color, out_rgba, out_motion))
+
+    def post_buffers(self):
+        """Device addresses of the renderer's own post outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_post_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def downloadPostPixels(self):
+        """The rgba8 output of the last post() into the renderer's own buffer, shaped like downloadPixels()."""
+        return self._download_frame(self.post_buffers()[1], 1)
+
+    def downloadPostColor(self):
+        """The float4 output of the last post() into the renderer's own buffer."""
+        return self._download_frame(self.post_buffers()[0], 4)
+
     # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
     def update_vertices(self, updates, rebuild=False):
         """New vertex positions for meshes of the scene: updates maps a mesh index to an (n, 3) float32 numpy array, or to a

@@ -174,6 +174,28 @@ public:
     {
         check(fovpt_download(ctx, d_motion, h_motion, sizeof(float4) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- the post-frame chain in one call (include/fovpt.h, fovpt_post): by default reconstruct() and temporalMotion() of the
+    // frame just rendered, bit for bit, as one G-buffer trace and one kernel, into the renderer's own post buffers, then a device
+    // sync like render().  pc.stages chooses the stages (FOVPT_POST_*); in_color and out_motion as in those calls
+    void post()
+    {
+        fovpt_post_config pc;
+        check(fovpt_post_defaults(&pc));
+        post(pc);
+    }
+    void post(const fovpt_post_config& pc, const fovpt_float4* in_color = nullptr, fovpt_float4* out_motion = nullptr)
+    {
+        check(fovpt_post(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &pc, in_color, nullptr, nullptr, out_motion));
+        check(fovpt_synchronize(ctx));
+    }
+    // the chain's rgba8 pixels, like downloadPixels
+    void downloadPostPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_post_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
     // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
     // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true
