@@ -44,7 +44,8 @@ Rccl& rccl()
         // must not become the process's: /opt/rocm's libamd_smi.so -- which PyTorch's device queries load -- defines the same ones,
         // and two libraries then run their static destructors on one object)
         R.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL | (only_if_loaded ? RTLD_NOLOAD : 0));
-        if (!R.lib && !only_if_loaded) R.why = dlerror() ? dlerror() : "dlopen failed";
+        // (dlerror() clears the message it returns: a second call gives NULL)
+        if (!R.lib && !only_if_loaded) { const char* e = dlerror(); R.why = e ? e : "dlopen failed"; }
     }
     if (!R.lib) { if (R.why.empty()) R.why = "librccl not found"; return R; }
     struct { const char* n; void** f; } syms[] = {

@@ -133,3 +133,24 @@ def test_product_does_not_import_the_oracle():
         p = os.path.join(ROOT, "include", f)
         if os.path.isfile(p):
             assert "orc_" not in open(p).read()
+
+
+def test_a_failing_dlopen_of_rccl_is_an_error_not_a_crash(so):
+    """ADVICE r4, first item: rccl() asked dlerror() twice and gave the second answer, NULL, to a std::string, so the first
+    candidate that failed to load ended the process.  A fresh process whose FOVPT_RCCL_LIB names no file must come back from
+    fovpt_comm_get_unique_id: with another candidate's RCCL (FOVPT_OK), or with an error code and a reason."""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import ctypes\n"
+            "from fovpathtracing_optixcodelatest_amd import lib\n"
+            "L = lib.load()\n"
+            "buf = ctypes.create_string_buffer(256)\n"
+            "rc = L.fovpt_comm_get_unique_id(buf)\n"
+            "msg = L.fovpt_last_error(None) or b''\n"
+            "print('RESULT', rc, len(msg), flush=True)\n" % ROOT)
+    env = dict(os.environ, FOVPT_RCCL_LIB="/nonexistent/librccl.so")
+    res = subprocess.run([os.sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
+    assert res.returncode == 0, (res.returncode, res.stderr[-2000:])
+    line = [ln for ln in res.stdout.splitlines() if ln.startswith("RESULT")]
+    assert line, res.stdout[-2000:]
+    rc, nmsg = (int(x) for x in line[-1].split()[1:])
+    assert rc == 0 or nmsg > 0, "error code %d without a message" % rc
