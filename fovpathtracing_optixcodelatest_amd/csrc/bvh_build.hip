@@ -538,9 +538,6 @@ __device__ inline float box_area(const Box& b)
 //   C(x, i) = min( C(x, i-1), min_k C(left, k) + C(right, i - k) )        x dissolves into its parent
 // in units of node steps (a leaf step costs the traversal kernel about 2.7 of them).  Computed bottom-up,
 // the second thread to arrive at a node does the work (as in k_refit); the decisions steer k_collapse4.
-#ifndef FOVPT_V_DPCOLLAPSE
-#define FOVPT_V_DPCOLLAPSE 1
-#endif
 #ifndef FOVPT_COST_LEAF
 #define FOVPT_COST_LEAF 2.7f
 #endif
@@ -619,7 +616,6 @@ __global__ void k_collapse4(int nwork, const Work4* __restrict__ work_in, Work4*
     if (w >= nwork) return;
     const Work4 me = work_in[w];
     int ch[4];
-#if FOVPT_V_DPCOLLAPSE
     // the children the dynamic programme chose: (subtree, slots) pairs are split until every pair fills one slot
     int nch = 0;
     {
@@ -642,26 +638,6 @@ __global__ void k_collapse4(int nwork, const Work4* __restrict__ work_in, Work4*
             else ch[nch++] = y;
         }
     }
-#else
-    // greedy: the two children are expanded, largest surface area first, until four slots are used
-    int nch = 2;
-    ch[0] = left[me.node]; ch[1] = right[me.node];
-    for (;;) {
-        if (nch == 4) break;
-        int pick = -1;
-        float best = -1.0f;
-        for (int k = 0; k < nch; k++) {
-            const int x = ch[k];
-            if (x < 0 || size_int[x] <= FOVPT_LEAF_MAX) continue;          // leaf or collapsed leaf: not expandable
-            const float a = box_area(ibox[x]);
-            if (a > best) { best = a; pick = k; }
-        }
-        if (pick < 0) break;
-        const int x = ch[pick];
-        ch[pick] = left[x];
-        ch[nch++] = right[x];
-    }
-#endif
     BvhNode4 nd;
     for (int k = 0; k < 4; k++) {
         BvhChild& C = nd.c[k];
@@ -676,11 +652,7 @@ __global__ void k_collapse4(int nwork, const Work4* __restrict__ work_in, Work4*
         if (x < 0) { b = boxes[vals[~x]]; code = leaf_code((int)leaf_pos[~x], 1); }
         else {
             b = ibox[x];
-#if FOVPT_V_DPCOLLAPSE
             if (dp[x].dec & 4u) code = leaf_code((int)node_first[x], (int)size_int[x]);
-#else
-            if (size_int[x] <= FOVPT_LEAF_MAX) code = leaf_code((int)node_first[x], (int)size_int[x]);
-#endif
             else {
                 const uint32_t slot = atomicAdd(&counters[0], 1u);          // next free wide node
                 const uint32_t q = atomicAdd(&counters[1], 1u);             // next level's queue

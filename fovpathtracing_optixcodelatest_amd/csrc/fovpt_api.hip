@@ -156,9 +156,6 @@ int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipSt
     const size_t v = 16;
     HIPCHK(c, S.s_thr.reserve(slots * v)); HIPCHK(c, S.s_rng.reserve(slots * v));
     HIPCHK(c, S.s_hit.reserve((size_t)shard_capacity(slots) * FOVPT_SHARDS * v));      // indexed like the ray queues
-#if FOVPT_V_STEPSTAT
-    HIPCHK(c, S.s_trace.reserve((size_t)shard_capacity(slots) * FOVPT_SHARDS * v));
-#endif
     HIPCHK(c, S.s_alpha.reserve(slots * v));
     HIPCHK(c, S.s_rad.reserve(slots * v * (size_t)c->cfg.max_depth));
     HIPCHK(c, S.s_backplate.reserve(launches * v));
@@ -188,9 +185,6 @@ PathState path_state(const fovpt_ctx* c, const StateSet& S)
     memset(&ps, 0, sizeof(ps));
     ps.thr = (float4*)S.s_thr.p; ps.rng = (uint4*)S.s_rng.p; ps.hit = (float4*)S.s_hit.p; ps.rad = (float4*)S.s_rad.p;
     ps.stride = (size_t)c->cfg.max_depth; ps.alpha = (float4*)S.s_alpha.p; ps.backplate = (float4*)S.s_backplate.p;
-#if FOVPT_V_STEPSTAT
-    ps.trace = (uint4*)S.s_trace.p;
-#endif
     return ps;
 }
 
@@ -1182,7 +1176,7 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {
         {"sq_o", &S.sq_o[0]}, {"sq_d", &S.sq_d[0]}, {"sq_vis", &S.sq_vis[0]}, {"sq_occ", &S.sq_occ[0]}, {"counters", &S.counters},
-        {"hit", &S.s_hit}, {"trace", &S.s_trace}, {"queue_a_o", &S.q_o[0]}, {"queue_a_d", &S.q_d[0]}, {"queue_b_o", &S.q_o[1]}, {"queue_b_d", &S.q_d[1]},
+        {"hit", &S.s_hit}, {"queue_a_o", &S.q_o[0]}, {"queue_a_d", &S.q_d[0]}, {"queue_b_o", &S.q_o[1]}, {"queue_b_d", &S.q_d[1]},
     };
     for (auto& t : tab)
         if (strcmp(t.n, name) == 0) { *ptr = t.b->p; *bytes = t.b->bytes; return FOVPT_OK; }

@@ -38,7 +38,7 @@ struct EventPair { hipEvent_t a, b; TimedKind kind; };
 struct ChainEvents { hipEvent_t shade[FOVPT_MAX_ITERS + 1], shadow[FOVPT_MAX_ITERS + 1]; };
 
 struct StateSet {
-    DevBuf s_thr, s_rng, s_hit, s_rad, s_alpha, s_backplate, s_guide_n, s_guide_a, s_trace;
+    DevBuf s_thr, s_rng, s_hit, s_rad, s_alpha, s_backplate, s_guide_n, s_guide_a;
     DevBuf q_o[2], q_d[2], counters;       // q_*: the two radiance-ray queues (ping-pong)
     DevBuf sq_o[FOVPT_NSQ], sq_d[FOVPT_NSQ], sq_vis[FOVPT_NSQ], sq_occ[FOVPT_NSQ];   // shadow queues, one per bounce in flight
     ChainEvents chain[2] = {};             // [1]: the second chain of a frame (fovpt_config.chains_per_frame = 2)

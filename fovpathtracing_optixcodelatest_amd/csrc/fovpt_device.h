@@ -1,5 +1,7 @@
-// fovpt_device.h -- structures shared by the host API (fovpt_api.hip), the LBVH builder
-// (bvh_build.hip) and the wavefront kernels (wavefront.hip).  gfx950 only.
+// fovpt_device.h -- structures and launchers shared by the host API (fovpt_api.hip, api_post.hip, api_gather.hip), the BVH
+// builder and refit (bvh_build.hip, refit.hip), the wavefront kernels (wavefront.hip), the traversal (traverse.hip) and the
+// post-frame kernels.  gfx950 only.  The one compile-time switch is FOVPT_V_STEPSTAT (a diagnostic build, tools/build_variant.sh);
+// everything else that can be set with -D is a numeric knob with its measured default.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,27 +12,7 @@
 #define FOVPT_WAVE 64
 #define FOVPT_BLOCK 256
 #ifndef FOVPT_V_STEPSTAT
-#define FOVPT_V_STEPSTAT 0         // 1: diagnostic build (tools/stepstat.py, tools/raystat.py)
-#endif
-#ifndef FOVPT_V_CYCLES
-#define FOVPT_V_CYCLES 0           // 1: diagnostic build with s_memtime stamps inside the traversal steps (tools/stepcycles.py)
-#endif
-#ifndef FOVPT_V_VOTE_ANYHIT
-#define FOVPT_V_VOTE_ANYHIT 1      // occlusion rays end their node phases by the same vote as closest-hit rays (wavefront.hip, vote_leaf); 0: when
-                                   // every ray of the wave has reached a leaf, as rounds 1-3 (A/B: street occlusion launches 0.755 -> 0.600 ms, atrium 0.250 -> 0.244)
-#endif
-#ifndef FOVPT_V_MIXED
-#define FOVPT_V_MIXED 1            // the pass after a vote is a MIXED step (leaf lanes test triangles, node lanes step, behind one wait: wavefront.hip
-                                   // mixed_step); 0: a leaf step in which the node lanes idle (A/B: atrium 0.667 -> 0.663, street 1.444 -> 1.409 with both on)
-#endif
-#ifndef FOVPT_V_MIXED_ANYHIT
-#define FOVPT_V_MIXED_ANYHIT 1     // the same for occlusion rays
-#endif
-#ifndef FOVPT_V_GEN_OWNED
-#define FOVPT_V_GEN_OWNED 1         // a rank of a tile-sharded frame generates over its own tiles only (k_generate<true>)
-#endif
-#ifndef FOVPT_V_ANYHIT_SORT
-#define FOVPT_V_ANYHIT_SORT 0      // 1: occlusion rays visit a node's children nearest first, like closest-hit rays (A/B; the product uses storage order)
+#define FOVPT_V_STEPSTAT 0         // 1: diagnostic build: k_traverse counts steps (tools/stepstat.py, raystat.py, stepcount.py, raytrace_dump.py)
 #endif
 #ifndef FOVPT_LEAF_MAX
 #define FOVPT_LEAF_MAX 4          // triangles per BVH leaf (<= 8: three bits in the leaf code)
@@ -170,9 +152,6 @@ struct PathState {
     float4* guide_n;    // write_guides: prd.normal of the primary hit (deviceProgram.cu:509-512), else null
     float4* guide_a;    // write_guides: prd.albedo of the primary hit
     float4* backplate;  // per launch record: backplate of the last sample (deviceProgram.cu:495)
-#if FOVPT_V_STEPSTAT
-    uint4* trace;       // diagnostics: node steps of each of the ray's first 16 node phases, one byte each (tools/raysim.py)
-#endif
 };
 
 // Shadow (occlusion) ray queue, indexed by queue position.
@@ -199,12 +178,6 @@ struct Counters {       // device-resident, zeroed per frame except the stats bl
     // diagnostics of a -DFOVPT_V_STEPSTAT=1 build (tools/stepstat.py): per ray kind [closest, any-hit]
     // wave-level node steps, active quads in them, wave-level leaf steps, active quads in them
     unsigned long long diag[2][4];
-#if FOVPT_V_CYCLES
-    // diagnostics of a -DFOVPT_V_CYCLES=1 build (tools/stepcycles.py): s_memtime ticks (shader cycles) summed per wave
-    unsigned long long cyc[2][8][16];   // [ray kind][iteration & 7][field], fields: see struct Cyc in wavefront.hip
-    uint32_t hist[2][8][3][64];         // [kind][iteration & 7][node load wait /16 | node step /32 | leaf step /32][bin]
-    unsigned long long wtime[8][32768][2];   // [kind * 4 + iteration & 3][wave]: s_memrealtime (100 MHz) at the wave's start and end
-#endif
 };
 static_assert(2 * (FOVPT_MAX_ITERS + 1) <= FOVPT_SHARD_STRIDE, "shard block holds both queues' sizes");
 #define FOVPT_CNT_Q(it) (it)                               // word index inside a shard's block
@@ -215,7 +188,7 @@ static_assert(2 * (FOVPT_MAX_ITERS + 1) <= FOVPT_SHARD_STRIDE, "shard block hold
 // well inside the box and the fused-multiply-add slab test of the traversal stays conservative.
 __device__ inline float fovpt_tri_pad(float ext, float mag) { return 1e-4f * ext + 1e-5f * mag + 1e-20f; }
 
-// ---- launchers implemented in wavefront.hip / bvh_build.hip / refit.hip ----------------------
+// ---- launchers implemented in wavefront.hip / traverse.hip / bvh_build.hip / refit.hip ----------------------
 #define FOVPT_BVH_MAX_LEVELS 64   // levels of the wide tree recorded by the build (a traversable tree has at most (FOVPT_STACK - 1) / 3)
 struct BvhBuildResult {
     BvhNode4* nodes;              // ONE allocation: the emitted nodes, then (256-byte aligned) the triangles; free `nodes` only
@@ -239,8 +212,8 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
 // sel: 0 = all eight queue shards (a whole job); 1 / 2 = the first / second four (one of the two chains of a frame)
 void fovpt_launch_generate(hipStream_t st, const FrameDev& fd, PathState ps, RayQueue queue0, uint32_t cap, Counters* cnt, uint32_t slot_begin,
                            uint32_t slot_end, int grid, uint32_t sel = 0);
-// One launch that traces the shadow queue of iteration it_shadow (if >= 0) and the radiance queue of
-// iteration it_closest (if >= 0).
+// One launch that traces the radiance queue of iteration it_closest (closest hit) OR the shadow queue of iteration
+// it_shadow (occlusion): the other one is < 0 (traverse.hip).
 void fovpt_launch_traverse(hipStream_t st, SceneView sc, PathState ps, RayQueue queue, ShadowQueue sq, uint32_t cap,
                            Counters* cnt, int it_closest, int it_shadow, int grid, hipEvent_t done = nullptr, uint32_t sel = 0);
 void fovpt_launch_shade(hipStream_t st, const FrameDev& fd, SceneView sc, PathState ps, RayQueue queue_in, RayQueue queue_out,

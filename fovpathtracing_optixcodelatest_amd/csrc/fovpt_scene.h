@@ -6,7 +6,7 @@
 
 namespace {
 
-// triangle records: Moeller-Trumbore on them is in leaf_step, in the operation order of the parity contract
+// triangle records: Moeller-Trumbore on them is in leaf_finish (traverse.hip), in the operation order of the parity contract
 // (oracle intersect_tri)
 __device__ inline TriRec load_tri_off(const TriRec* __restrict__ tris, uint32_t byte_off)
 {

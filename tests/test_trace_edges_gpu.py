@@ -1,4 +1,4 @@
-"""k_traverse ray by ray at its edges (csrc/wavefront.hip): directions with exact zero components of either sign, origins
+"""k_traverse ray by ray at its edges (csrc/traverse.hip): directions with exact zero components of either sign, origins
 exactly on wall planes, hierarchies smaller than the root block kept in LDS, partly filled waves, several rounds per wave and
 refilled occlusion pools, scaled and shifted scenes, spatial splits, refitted hierarchies.
 

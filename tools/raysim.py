@@ -1,5 +1,6 @@
 """Offline simulation of wave scheduling policies for the closest-hit traversal, from the per-ray phase traces that
-tools/raytrace_dump.py writes (node steps of every node phase between two leaf visits, in queue order).
+tools/raytrace_dump.py wrote up to round 4 (node steps of every node phase between two leaf visits, in queue order: the `trace`
+array of a recorded .npz; the kernel no longer keeps it, so a dump made today does not have it).
 
 A wave runs 16 rays in lockstep with the while-while loop of traverse_quad: an outer iteration = a node phase that lasts
 until every active ray reached a leaf (or finished), then one leaf step for those at a leaf.  Cost model: node step

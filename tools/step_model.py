@@ -1,4 +1,5 @@
-"""profiles/r03_step_cycles.txt (tools/stepcycles.py on a FOVPT_V_CYCLES=1 build: s_memtime stamps in a sample of the waves) and
+"""(Reads recorded files only; the build and the tool that made them are tools/experiments/step_cycle_stamps.patch.)
+profiles/r03_step_cycles.txt (tools/stepcycles.py on a FOVPT_V_CYCLES=1 build: s_memtime stamps in a sample of the waves) and
 profiles/r03_wave_timeline_c3.txt (FOVPT_V_CYCLES=3: every wave's start and end, nothing else) -> profiles/r03_step_model.json:
 the latency model of a k_traverse launch that bench.py puts next to the measured launch times.
 
