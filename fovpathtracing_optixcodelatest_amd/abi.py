@@ -144,6 +144,19 @@ class VertexUpdate(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("vertex", C.c_void_p)]
 
 
+class MeshTransform(C.Structure):
+    """fovpt_mesh_transform: a row-major 3 x 4 matrix applied to the rest positions of one mesh (fovpt_update_transforms)."""
+    _fields_ = [("mesh", C.c_int32), ("m", C.c_float * 12)]
+
+
+COST_WAIT = 1                                   # fovpt_hierarchy_cost flag (FOVPT_COST_WAIT)
+
+
+class HierarchyCost(C.Structure):
+    """fovpt_hierarchy_cost_info: the SAH cost of the hierarchy as built and as last measured, and the update counters."""
+    _fields_ = [("built", C.c_double), ("current", C.c_double), ("updates", C.c_uint64), ("measured", C.c_uint64)]
+
+
 class TextureDesc(C.Structure):
     _fields_ = [("pixel", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -289,6 +302,8 @@ assert C.sizeof(ReconstructConfig) == 32 and C.sizeof(GBufferPtrs) == 40
 assert C.sizeof(TemporalConfig) == 32
 assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.reconstruct.offset, PostConfig.temporal.offset) == (16, 48, 80)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
+assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4
+assert C.sizeof(HierarchyCost) == 32 and HierarchyCost.updates.offset == 16
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

@@ -593,6 +593,201 @@ void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms)
     c->stats.bvh_bytes = br.node_bytes; c->stats.tri_bytes = br.tri_bytes; c->stats.ms_bvh_build = ms;
 }
 
+// ---- fovpt_hierarchy_cost: measurements (refit.hip) ------------------------------------------------------------------------
+// The completed measurements: the newest becomes (cost_current, cost_measured), and their slots are free again.
+void take_costs(fovpt_ctx* c)
+{
+    bool not_ready = false;
+    for (auto& S : c->cost_slot) {
+        if (!S.pending) continue;
+        if (hipEventQuery(S.ev) != hipSuccess) { not_ready = true; continue; }
+        S.pending = false;
+        if (S.update > c->cost_measured) { c->cost_current = S.rec->cost; c->cost_measured = S.update; }
+    }
+    if (not_ready) (void)hipGetLastError();      // (hipErrorNotReady is an answer, not an error a later check should find)
+}
+
+// A measurement of the present tree on st, as the one of update number `update`: into a free slot, whose event is recorded
+// behind it.  *out: the slot, or null when every slot is still in flight (the update is then not measured).
+int enqueue_cost(fovpt_ctx* c, hipStream_t st, uint64_t update, fovpt_ctx::CostSlot** out)
+{
+    *out = nullptr;
+    take_costs(c);
+    for (auto& S : c->cost_slot) {
+        if (S.pending) continue;
+        if (!S.rec) HIPCHK(c, hipHostMalloc((void**)&S.rec, sizeof(TreeCostRecord), hipHostMallocDefault));
+        if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+        TreeCostRecord* d_rec = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer((void**)&d_rec, S.rec, 0));
+        fovpt_launch_tree_cost(st, c->nodes, (uint32_t)c->stats.num_bvh_nodes, (double*)c->cost_partial.p, d_rec);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(S.ev, st));
+        S.pending = true; S.update = update;
+        *out = &S;
+        break;
+    }
+    return FOVPT_OK;
+}
+
+// The cost of the hierarchy just adopted (the device is idle: fovpt_set_scene and a rebuild synchronise): cost_built, and
+// cost_current for update number cost_updates.  Outside the window ms_bvh_build times.
+int measure_built(fovpt_ctx* c)
+{
+    HIPCHK(c, c->cost_partial.reserve(2 * sizeof(double) * (size_t)fovpt_tree_cost_blocks((uint32_t)c->stats.num_bvh_nodes)));
+    fovpt_ctx::CostSlot* S = nullptr;
+    { const int rc_ = enqueue_cost(c, c->shadow_stream, c->cost_updates, &S); if (rc_) return rc_; }
+    if (!S) return fail(c, FOVPT_E_DEVICE, "no free cost slot on an idle device");
+    HIPCHK(c, hipEventSynchronize(S->ev));
+    S->pending = false;
+    c->cost_built = c->cost_current = S->rec->cost;
+    c->cost_measured = c->cost_updates;
+    return FOVPT_OK;
+}
+
+// ---- animated geometry (refit.hip) ---------------------------------------------------------------------------------------
+// What both entry points check of the scene once their own arguments are in order
+int check_updatable(fovpt_ctx* c, const char* who)
+{
+    if (c->h_vtx.size() / 3 >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "%s: more than 2^32 - 1 vertices", who);
+    if (c->bvh_num_levels == 0) return fail(c, FOVPT_E_INVALID, "%s: the hierarchy has more than %d levels", who, FOVPT_BVH_MAX_LEVELS);
+    return FOVPT_OK;
+}
+
+// Where the new positions of update_scene come from: `up` (host arrays through a staging buffer, `floats` of them in all, or
+// device arrays by a gather kernel) or `tf` (the rest positions through per-mesh matrices); all `num` validated.
+struct UpdateSource {
+    const fovpt_vertex_update* up;
+    bool device;
+    size_t floats;
+    const fovpt_mesh_transform* tf;
+    int num;
+    int mesh(int k) const { return up ? up[k].mesh : tf[k].mesh; }
+};
+
+// The update itself, shared by fovpt_update_vertices and fovpt_update_transforms: fovpt_temporal_motion's copy of the positions
+// about to be overwritten, the new positions into up_vtx on fovpt_stream(), and either the refit, enqueued behind them on the
+// same stream (the stream every job's resolve, and so every job's last traversal launch, is ordered on) with the event the next
+// job waits for, or a rebuild.
+int update_scene(fovpt_ctx* c, const UpdateSource& s, bool rebuild)
+{
+    const int nmesh = (int)c->mesh_nv.size();
+    HIPCHK(c, hipSetDevice(c->device));
+    if (rebuild) { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    const hipStream_t st = c->shadow_stream;
+    if (!c->up_vtx.p) {
+        // the first update: the device copies of what fovpt_set_scene kept (ordered on the stream like everything below)
+        if (!c->ev_scene) HIPCHK(c, hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
+        for (auto& S : c->up_stage)
+            if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+        HIPCHK(c, c->up_vidx.reserve(c->h_tri_vidx.size() * 4));
+        HIPCHK(c, c->up_vtx.reserve(c->h_vtx.size() * 4));
+        HIPCHK(c, hipMemcpyAsync(c->up_vidx.p, c->h_tri_vidx.data(), c->h_tri_vidx.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    float* vtx = (float*)c->up_vtx.p;
+    if (!c->tm_tracking) c->tm_untracked = c->tm_untracked || s.num > 0;
+    else {
+        // fovpt_temporal_motion's previous positions: what a mesh holds now, ahead of the interval's first overwrite of it
+        HIPCHK(c, c->vtx_prev.reserve(c->h_vtx.size() * 4));
+        VertexTrack g;
+        memset(&g, 0, sizeof(g));
+        for (int k = 0; k < s.num; k++) {
+            const int mesh = s.mesh(k);
+            const uint32_t nv = c->mesh_nv[mesh];
+            if (c->tm_mesh_epoch[mesh] != c->tm_epoch) {
+                c->tm_mesh_epoch[mesh] = c->tm_epoch;
+                g.first[g.count] = c->mesh_vbase[mesh]; g.n[g.count] = nv; g.mesh[g.count] = (uint32_t)mesh;
+                g.max_n = nv > g.max_n ? nv : g.max_n;
+                g.count++;
+            }
+            if (g.count == FOVPT_GATHER_BATCH || (k + 1 == s.num && g.count)) {
+                fovpt_launch_gather_vertices_prev(st, g, vtx, (float*)c->vtx_prev.p, (uint64_t*)c->tm_mark.p, c->tm_epoch);
+                memset(&g, 0, sizeof(g));
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    if (s.tf) {
+        if (!c->rest_vtx.p) {
+            // the first transforms of the scene: the rest positions stay on the device
+            HIPCHK(c, c->rest_vtx.reserve(c->h_vtx.size() * 4));
+            HIPCHK(c, hipMemcpyAsync(c->rest_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
+        }
+        VertexTransform g;
+        memset(&g, 0, sizeof(g));
+        for (int k = 0; k < s.num; k++) {
+            const uint32_t nv = c->mesh_nv[s.tf[k].mesh];
+            memcpy(g.m[g.count], s.tf[k].m, sizeof(g.m[0]));
+            g.first[g.count] = c->mesh_vbase[s.tf[k].mesh]; g.n[g.count] = nv;
+            g.max_n = nv > g.max_n ? nv : g.max_n;
+            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == s.num) { fovpt_launch_transform_vertices(st, g, (const float*)c->rest_vtx.p, vtx); memset(&g, 0, sizeof(g)); }
+        }
+        HIPCHK(c, hipGetLastError());
+    } else if (s.device) {
+        VertexGather g;
+        memset(&g, 0, sizeof(g));
+        for (int k = 0; k < s.num; k++) {
+            g.src[g.count] = s.up[k].vertex; g.dst[g.count] = c->mesh_vbase[s.up[k].mesh]; g.n[g.count] = s.up[k].num_vertices;
+            g.max_n = s.up[k].num_vertices > g.max_n ? s.up[k].num_vertices : g.max_n;
+            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == s.num) { fovpt_launch_gather_vertices(st, g, vtx); memset(&g, 0, sizeof(g)); }
+        }
+        HIPCHK(c, hipGetLastError());
+    } else if (s.floats) {
+        auto& S = c->up_stage[c->up_next];
+        c->up_next ^= 1;
+        if (S.pending) { HIPCHK(c, hipEventSynchronize(S.ev)); S.pending = false; }      // its previous copy has run
+        if (S.bytes < s.floats * 4) {
+            if (S.p) (void)hipHostFree(S.p);
+            S.p = nullptr; S.bytes = 0;
+            HIPCHK(c, hipHostMalloc(&S.p, s.floats * 4, hipHostMallocDefault));
+            S.bytes = s.floats * 4;
+        }
+        float* h = (float*)S.p;
+        for (int k = 0; k < s.num; k++) {
+            const size_t n = 3 * (size_t)s.up[k].num_vertices;
+            memcpy(h, s.up[k].vertex, n * 4);
+            HIPCHK(c, hipMemcpyAsync(vtx + 3 * (size_t)c->mesh_vbase[s.up[k].mesh], h, n * 4, hipMemcpyHostToDevice, st));
+            h += n;
+        }
+        HIPCHK(c, hipEventRecord(S.ev, st));
+        S.pending = true;
+    }
+    if (!rebuild) {
+        fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, vtx);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev_scene, st));
+        c->refit_pending = true;
+        c->cost_updates++;
+        if (c->cost_watching) {
+            // fovpt_hierarchy_cost is watching: the refit tree's cost, behind the event the next job waits for
+            fovpt_ctx::CostSlot* S = nullptr;
+            return enqueue_cost(c, st, c->cost_updates, &S);
+        }
+        return FOVPT_OK;
+    }
+    // FOVPT_UPDATE_REBUILD: fovpt_set_scene's build over the current vertices; the old hierarchy stays if it fails
+    const uint32_t ntri = (uint32_t)c->stats.num_triangles;
+    DevBuf t_flat, t_mesh_of;
+    HIPCHK(c, t_flat.reserve((size_t)ntri * 36));
+    HIPCHK(c, t_mesh_of.reserve((size_t)ntri * 4));
+    std::vector<uint32_t> mesh_of((size_t)ntri);
+    for (int m = 0; m < nmesh; m++) {
+        const uint32_t end = m + 1 < nmesh ? c->mesh_prim0[m + 1] : ntri;
+        for (uint32_t t = c->mesh_prim0[m]; t < end; t++) mesh_of[t] = (uint32_t)m;
+    }
+    HIPCHK(c, hipMemcpyAsync(t_mesh_of.p, mesh_of.data(), mesh_of.size() * 4, hipMemcpyHostToDevice, st));
+    fovpt_launch_flatten(st, ntri, (const uint3*)c->up_vidx.p, vtx, (float*)t_flat.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    BvhBuildResult br;
+    float ms = 0.f;
+    { const int rc_ = build_hierarchy(c, st, (const float*)t_flat.p, (const uint32_t*)t_mesh_of.p, ntri, br, ms); if (rc_) return rc_; }
+    (void)hipFree(c->nodes);                           // (the device is idle: sync_all above, and the build synchronised)
+    adopt_hierarchy(c, br, ms);
+    c->cost_updates++;
+    return measure_built(c);
+}
+
 }  // namespace
 
 // The passes fovpt_render ran for the frame lp describes under cfg, whole (rows 0 .. gh) and on one rank: what
@@ -620,6 +815,10 @@ fovpt_ctx::~fovpt_ctx()
         if (S.ev) (void)hipEventDestroy(S.ev);
     }
     if (ev_scene) (void)hipEventDestroy(ev_scene);
+    for (auto& S : cost_slot) {
+        if (S.rec) (void)hipHostFree(S.rec);
+        if (S.ev) (void)hipEventDestroy(S.ev);
+    }
     for (StateSet& S : set) {
         for (ChainEvents& ch : S.chain)
             for (int k = 0; k <= FOVPT_MAX_ITERS; k++) {
@@ -725,6 +924,9 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     c->refit_pending = false;
     c->tm_tracking = c->tm_untracked = false;        // fovpt_temporal_motion's tracking: switched on again by its next call
     c->tm_mark.release(); c->vtx_prev.release();
+    c->rest_vtx.release(); c->mesh_absmax.clear();   // fovpt_update_transforms' rest positions: made again on the scene's first call
+    take_costs(c);                                   // fovpt_hierarchy_cost: (the device is idle) no measurement of the old scene stays in flight
+    c->cost_updates = c->cost_measured = 0;
     uint64_t ntri = 0;
     bool any_tc = false;
     for (int m = 0; m < num_meshes; m++) {
@@ -809,13 +1011,11 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     c->scene_id = (c->scene_id & 0xffffffffull) + 1;
     c->scene_id |= 0x464f565000000000ull;          // 'FOVP' tag so a stale/foreign handle is recognisable
     if (traversable_out) *traversable_out = c->scene_id;
-    return FOVPT_OK;
+    return measure_built(c);
 }
 
 // ---- animated geometry (refit.hip) ---------------------------------------------------------------------------------------
-// Validates everything first (all or nothing), then: the new positions into up_vtx on fovpt_stream() -- host data through a
-// pinned staging buffer and hipMemcpyAsync, device data by a gather kernel -- and either the refit, enqueued behind them on
-// the same stream (the stream every job's resolve, and so every job's last traversal launch, is ordered on), or a rebuild.
+// Both entry points validate everything first (all or nothing); update_scene does the rest.
 int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_updates, int flags)
 {
     if (!c) return FOVPT_E_INVALID;
@@ -839,99 +1039,78 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
                 if (!std::isfinite(U.vertex[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d vertex %zu is not finite", U.mesh, i / 3);
         floats += 3 * (size_t)U.num_vertices;
     }
-    if (c->h_vtx.size() / 3 >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: more than 2^32 - 1 vertices");
-    if (c->bvh_num_levels == 0) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: the hierarchy has more than %d levels", FOVPT_BVH_MAX_LEVELS);
+    { const int rc_ = check_updatable(c, "fovpt_update_vertices"); if (rc_) return rc_; }
     if (num_updates == 0 && !rebuild) return FOVPT_OK;
+    const UpdateSource src = {up, device, floats, nullptr, num_updates};
+    return update_scene(c, src, rebuild);
+}
+
+// The rest positions of the named meshes through their matrices (k_transform_vertices), then fovpt_update_vertices' refit or
+// rebuild.  The overflow rule keeps every intermediate value finite, so no device memory has to be read to know the
+// coordinates are.
+int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int num, int flags)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_transforms without a scene");
+    if (num < 0 || (num > 0 && !tf)) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: %d transforms at %p", num, (const void*)tf);
+    if (flags & ~FOVPT_UPDATE_REBUILD) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: flag bits %d (FOVPT_UPDATE_REBUILD is the only one accepted)", flags);
+    const int nmesh = (int)c->mesh_nv.size();
+    if (num > 0 && c->mesh_absmax.empty()) {
+        // once per scene: the largest |coordinate| of every mesh's rest positions
+        c->mesh_absmax.assign((size_t)nmesh, 0.0);
+        for (int m = 0; m < nmesh; m++) {
+            const float* v = c->h_vtx.data() + 3 * (size_t)c->mesh_vbase[m];
+            for (size_t i = 0; i < 3 * (size_t)c->mesh_nv[m]; i++) c->mesh_absmax[m] = std::fmax(c->mesh_absmax[m], std::fabs((double)v[i]));
+        }
+    }
+    std::vector<char> seen((size_t)nmesh, 0);
+    for (int k = 0; k < num; k++) {
+        const fovpt_mesh_transform& T = tf[k];
+        if (T.mesh < 0 || T.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d of %d", T.mesh, nmesh);
+        if (seen[T.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d is listed twice", T.mesh);
+        seen[T.mesh] = 1;
+        for (int i = 0; i < 12; i++)
+            if (!std::isfinite(T.m[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d matrix entry %d is not finite", T.mesh, i);
+        for (int r = 0; r < 3; r++) {
+            const float* row = T.m + 4 * r;
+            const double bound = (std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * c->mesh_absmax[T.mesh] + std::fabs((double)row[3]);
+            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d row %d could overflow (bound %g > 2^127)", T.mesh, r, bound);
+        }
+    }
+    { const int rc_ = check_updatable(c, "fovpt_update_transforms"); if (rc_) return rc_; }
+    const bool rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    if (num == 0 && !rebuild) return FOVPT_OK;
+    const UpdateSource src = {nullptr, false, 0, tf, num};
+    return update_scene(c, src, rebuild);
+}
+
+int fovpt_hierarchy_cost(fovpt_ctx* c, int flags, fovpt_hierarchy_cost_info* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "fovpt_hierarchy_cost: null out pointer");
+    if (flags & ~FOVPT_COST_WAIT) return fail(c, FOVPT_E_INVALID, "fovpt_hierarchy_cost: unknown flag bits %d", flags);
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_hierarchy_cost without a scene");
     HIPCHK(c, hipSetDevice(c->device));
-    if (rebuild) { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    const hipStream_t st = c->shadow_stream;
-    if (!c->up_vtx.p) {
-        // the first update: the device copies of what fovpt_set_scene kept (ordered on the stream like everything below)
-        if (!c->ev_scene) HIPCHK(c, hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
-        for (auto& S : c->up_stage)
-            if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-        HIPCHK(c, c->up_vidx.reserve(c->h_tri_vidx.size() * 4));
-        HIPCHK(c, c->up_vtx.reserve(c->h_vtx.size() * 4));
-        HIPCHK(c, hipMemcpyAsync(c->up_vidx.p, c->h_tri_vidx.data(), c->h_tri_vidx.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    float* vtx = (float*)c->up_vtx.p;
-    if (!c->tm_tracking) c->tm_untracked = c->tm_untracked || num_updates > 0;
-    else {
-        // fovpt_temporal_motion's previous positions: what a mesh holds now, ahead of the interval's first overwrite of it
-        HIPCHK(c, c->vtx_prev.reserve(c->h_vtx.size() * 4));
-        VertexTrack g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < num_updates; k++) {
-            const int mesh = up[k].mesh;
-            if (c->tm_mesh_epoch[mesh] != c->tm_epoch) {
-                c->tm_mesh_epoch[mesh] = c->tm_epoch;
-                g.first[g.count] = c->mesh_vbase[mesh]; g.n[g.count] = up[k].num_vertices; g.mesh[g.count] = (uint32_t)mesh;
-                g.max_n = up[k].num_vertices > g.max_n ? up[k].num_vertices : g.max_n;
-                g.count++;
-            }
-            if (g.count == FOVPT_GATHER_BATCH || (k + 1 == num_updates && g.count)) {
-                fovpt_launch_gather_vertices_prev(st, g, vtx, (float*)c->vtx_prev.p, (uint64_t*)c->tm_mark.p, c->tm_epoch);
-                memset(&g, 0, sizeof(g));
-            }
+    const bool wait = (flags & FOVPT_COST_WAIT) != 0, first = !c->cost_watching;
+    c->cost_watching = true;                               // from now on every refit is followed by a measurement
+    take_costs(c);
+    if (c->cost_measured != c->cost_updates && (wait || first)) {
+        // the present tree's measurement: the one already in flight, else a new one (refits made before watching began)
+        fovpt_ctx::CostSlot* S = nullptr;
+        for (auto& X : c->cost_slot)
+            if (X.pending && X.update == c->cost_updates) S = &X;
+        if (!S) { const int rc_ = enqueue_cost(c, c->shadow_stream, c->cost_updates, &S); if (rc_) return rc_; }
+        if (!S && wait) {
+            // every slot is in flight with an older tree's measurement: one of them first
+            HIPCHK(c, hipEventSynchronize(c->cost_slot[0].ev));
+            const int rc_ = enqueue_cost(c, c->shadow_stream, c->cost_updates, &S);
+            if (rc_) return rc_;
+            if (!S) return fail(c, FOVPT_E_DEVICE, "fovpt_hierarchy_cost: no free slot behind a completed measurement");
         }
-        HIPCHK(c, hipGetLastError());
+        if (wait) { HIPCHK(c, hipEventSynchronize(S->ev)); take_costs(c); }
     }
-    if (device) {
-        VertexGather g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < num_updates; k++) {
-            g.src[g.count] = up[k].vertex; g.dst[g.count] = c->mesh_vbase[up[k].mesh]; g.n[g.count] = up[k].num_vertices;
-            g.max_n = up[k].num_vertices > g.max_n ? up[k].num_vertices : g.max_n;
-            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == num_updates) { fovpt_launch_gather_vertices(st, g, vtx); memset(&g, 0, sizeof(g)); }
-        }
-        HIPCHK(c, hipGetLastError());
-    } else if (floats) {
-        auto& S = c->up_stage[c->up_next];
-        c->up_next ^= 1;
-        if (S.pending) { HIPCHK(c, hipEventSynchronize(S.ev)); S.pending = false; }      // its previous copy has run
-        if (S.bytes < floats * 4) {
-            if (S.p) (void)hipHostFree(S.p);
-            S.p = nullptr; S.bytes = 0;
-            HIPCHK(c, hipHostMalloc(&S.p, floats * 4, hipHostMallocDefault));
-            S.bytes = floats * 4;
-        }
-        float* h = (float*)S.p;
-        for (int k = 0; k < num_updates; k++) {
-            const size_t n = 3 * (size_t)up[k].num_vertices;
-            memcpy(h, up[k].vertex, n * 4);
-            HIPCHK(c, hipMemcpyAsync(vtx + 3 * (size_t)c->mesh_vbase[up[k].mesh], h, n * 4, hipMemcpyHostToDevice, st));
-            h += n;
-        }
-        HIPCHK(c, hipEventRecord(S.ev, st));
-        S.pending = true;
-    }
-    if (!rebuild) {
-        fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, vtx);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_scene, st));
-        c->refit_pending = true;
-        return FOVPT_OK;
-    }
-    // FOVPT_UPDATE_REBUILD: fovpt_set_scene's build over the current vertices; the old hierarchy stays if it fails
-    const uint32_t ntri = (uint32_t)c->stats.num_triangles;
-    DevBuf t_flat, t_mesh_of;
-    HIPCHK(c, t_flat.reserve((size_t)ntri * 36));
-    HIPCHK(c, t_mesh_of.reserve((size_t)ntri * 4));
-    std::vector<uint32_t> mesh_of((size_t)ntri);
-    for (int m = 0; m < nmesh; m++) {
-        const uint32_t end = m + 1 < nmesh ? c->mesh_prim0[m + 1] : ntri;
-        for (uint32_t t = c->mesh_prim0[m]; t < end; t++) mesh_of[t] = (uint32_t)m;
-    }
-    HIPCHK(c, hipMemcpyAsync(t_mesh_of.p, mesh_of.data(), mesh_of.size() * 4, hipMemcpyHostToDevice, st));
-    fovpt_launch_flatten(st, ntri, (const uint3*)c->up_vidx.p, vtx, (float*)t_flat.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(st));
-    BvhBuildResult br;
-    float ms = 0.f;
-    { const int rc_ = build_hierarchy(c, st, (const float*)t_flat.p, (const uint32_t*)t_mesh_of.p, ntri, br, ms); if (rc_) return rc_; }
-    (void)hipFree(c->nodes);                           // (the device is idle: sync_all above, and the build synchronised)
-    adopt_hierarchy(c, br, ms);
+    out->built = c->cost_built; out->current = c->cost_current;
+    out->updates = c->cost_updates; out->measured = c->cost_measured;
     return FOVPT_OK;
 }
 

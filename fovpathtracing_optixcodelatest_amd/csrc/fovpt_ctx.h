@@ -90,6 +90,19 @@ struct fovpt_ctx {
     int up_next = 0;
     hipEvent_t ev_scene = nullptr;
     bool refit_pending = false;
+    // fovpt_update_transforms.  Made on a scene's first call and dropped by fovpt_set_scene: the device copy of h_vtx (12 B per
+    // vertex) and, per mesh, the largest |coordinate| of its rest positions (the overflow rule)
+    DevBuf rest_vtx;
+    std::vector<double> mesh_absmax;
+    // fovpt_hierarchy_cost.  cost_built / cost_current / cost_updates / cost_measured: the caller's record.  cost_partial: the
+    // block sums of k_tree_cost, sized when a hierarchy is adopted.  cost_slot: result records in pinned host memory the final
+    // kernel writes, each with the event recorded behind it and the update number it measures; a slot is free once its event has
+    // completed and its value is taken (take_costs).  cost_watching: a refit is followed by a measurement.
+    struct CostSlot { TreeCostRecord* rec = nullptr; hipEvent_t ev = nullptr; bool pending = false; uint64_t update = 0; } cost_slot[4];
+    DevBuf cost_partial;
+    bool cost_watching = false;
+    double cost_built = 0.0, cost_current = 0.0;
+    uint64_t cost_updates = 0, cost_measured = 0;
     // probe
     DevBuf pr_data, pr_pdfx, pr_cdfx, pr_pdfy, pr_cdfy, pr_guidex, pr_guidey, pr_rec;
     bool guide_ok = false;

@@ -306,6 +306,21 @@ struct VertexTrack {
     uint32_t max_n;
 };
 void fovpt_launch_gather_vertices_prev(hipStream_t st, const VertexTrack& g, const float* vtx, float* vtx_prev, uint64_t* mark, uint64_t epoch);
+// fovpt_update_transforms: up to FOVPT_GATHER_BATCH meshes, each the n vertices from `first` on of rest through its row-major
+// 3 x 4 matrix into vtx (x' = ((m0 x + m1 y) + m2 z) + m3, unfused binary32)
+struct VertexTransform {
+    float m[FOVPT_GATHER_BATCH][12];
+    uint32_t first[FOVPT_GATHER_BATCH]; // first vertex in rest and vtx
+    uint32_t n[FOVPT_GATHER_BATCH];     // vertices
+    int32_t count;
+    uint32_t max_n;
+};
+void fovpt_launch_transform_vertices(hipStream_t st, const VertexTransform& g, const float* rest, float* vtx);
+// fovpt_hierarchy_cost: the SAH cost of the num_nodes wide nodes in binary64, the same value from run to run.  partial: two
+// doubles per block of fovpt_tree_cost_blocks(num_nodes); rec: where the result goes (device-visible memory).
+struct TreeCostRecord { double cost, root, node, leaf; };     // (root + node + 2.7 leaf) / root and its three terms
+inline uint32_t fovpt_tree_cost_blocks(uint32_t num_nodes) { return (uint32_t)((4ull * num_nodes + FOVPT_BLOCK - 1) / FOVPT_BLOCK); }
+void fovpt_launch_tree_cost(hipStream_t st, const BvhNode4* nodes, uint32_t num_nodes, double* partial, TreeCostRecord* rec);
 // one launch per level of the wide tree, deepest first (levels[0 .. num_levels]: level_first of the build)
 void fovpt_launch_refit(hipStream_t st, BvhNode4* nodes, TriRec* tris, const uint32_t* levels, uint32_t num_levels, const uint3* tri_vidx,
                         const float* vtx);

@@ -8,6 +8,9 @@
 // nothing is shared inside a launch and no fence or atomic is needed.  An empty slot (lo = hi = +inf) is left as it is: a
 // union over it would make the parent's box infinite.  min / max are exact, so a refit over unchanged vertices reproduces the
 // build's boxes bit for bit (without spatial splits: a split reference's clipped box becomes its whole triangle's box).
+//
+// Also here: fovpt_update_transforms' k_transform_vertices (rest positions through per-mesh 3 x 4 matrices into the vertex array,
+// ahead of the same refit) and fovpt_hierarchy_cost's k_tree_cost / k_tree_cost_final (the SAH cost of the nodes in binary64).
 #include "fovpt_device.h"
 
 namespace {
@@ -46,6 +49,84 @@ __global__ void k_gather_vertices_prev(VertexTrack g, const float* __restrict__ 
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) vtx_prev[first + i] = vtx[first + i];
         if (blockIdx.x == 0 && threadIdx.x == 0) mark[g.mesh[u]] = epoch;
     }
+}
+
+// fovpt_update_transforms: the y grid dimension runs over the batch's meshes, x strides over a mesh's vertices.  Each vertex of
+// rest goes through its mesh's matrix into vtx: three dependent unfused operations per row (-ffp-contract=off), 24 B of traffic.
+__global__ void k_transform_vertices(VertexTransform g, const float* __restrict__ rest, float* __restrict__ vtx)
+{
+    for (int u = blockIdx.y; u < g.count; u += gridDim.y) {
+        const float* m = g.m[u];
+        const float* __restrict__ src = rest + 3 * (size_t)g.first[u];
+        float* __restrict__ dst = vtx + 3 * (size_t)g.first[u];
+        const size_t n = g.n[u];
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+            const float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+            dst[3 * i] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+            dst[3 * i + 1] = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+            dst[3 * i + 2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+        }
+    }
+}
+
+// fovpt_hierarchy_cost: dx dy + dy dz + dz dx of a box in binary64
+__device__ inline double box_area(double dx, double dy, double dz) { return dx * dy + dy * dz + dz * dx; }
+
+// sums s[0 .. FOVPT_BLOCK) into s[0] in a fixed order (every thread of the block calls it)
+__device__ inline void block_sum(double* s)
+{
+    __syncthreads();
+    for (uint32_t w = FOVPT_BLOCK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+}
+
+// One thread per (node, child slot): the area of a live entry, as a node entry's or a leaf entry's; the block's two sums go to
+// partial[2 b], partial[2 b + 1].  No atomics: the order of every addition is fixed by the indices alone.
+__global__ void __launch_bounds__(FOVPT_BLOCK) k_tree_cost(const BvhNode4* __restrict__ nodes, uint32_t num_nodes, double* __restrict__ partial)
+{
+    __shared__ double s_node[FOVPT_BLOCK], s_leaf[FOVPT_BLOCK];
+    const uint64_t t = (uint64_t)blockIdx.x * FOVPT_BLOCK + threadIdx.x;
+    double a_node = 0.0, a_leaf = 0.0;
+    if (t < 4ull * num_nodes) {
+        const float4* rec = reinterpret_cast<const float4*>(&nodes[t >> 2].c[t & 3u]);
+        const float4 r0 = rec[0], r1 = rec[1];             // {lo.xyz, hi.x}, {hi.yz, code, rank}
+        if (r0.x < INFINITY) {
+            const double a = box_area((double)r0.w - (double)r0.x, (double)r1.x - (double)r0.y, (double)r1.y - (double)r0.z);
+            if (__float_as_int(r1.z) >= 0) a_node = a; else a_leaf = a;
+        }
+    }
+    s_node[threadIdx.x] = a_node; s_leaf[threadIdx.x] = a_leaf;
+    block_sum(s_node);
+    block_sum(s_leaf);
+    if (threadIdx.x == 0) { partial[2 * (size_t)blockIdx.x] = s_node[0]; partial[2 * (size_t)blockIdx.x + 1] = s_leaf[0]; }
+}
+
+// One block: thread k sums the partials k, k + FOVPT_BLOCK, ... in index order, the block sums those; thread 0 adds the area of
+// the union of the root's live entries and writes the record.
+__global__ void __launch_bounds__(FOVPT_BLOCK) k_tree_cost_final(const BvhNode4* __restrict__ nodes, const double* __restrict__ partial, uint32_t nblocks,
+                                                                 TreeCostRecord* __restrict__ out)
+{
+    __shared__ double s_node[FOVPT_BLOCK], s_leaf[FOVPT_BLOCK];
+    double a_node = 0.0, a_leaf = 0.0;
+    for (uint32_t b = threadIdx.x; b < nblocks; b += FOVPT_BLOCK) { a_node += partial[2 * (size_t)b]; a_leaf += partial[2 * (size_t)b + 1]; }
+    s_node[threadIdx.x] = a_node; s_leaf[threadIdx.x] = a_leaf;
+    block_sum(s_node);
+    block_sum(s_leaf);
+    if (threadIdx.x != 0) return;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int k = 0; k < 4; k++) {
+        const BvhChild c = nodes[0].c[k];
+        if (!(c.lox < INFINITY)) continue;
+        lo[0] = fminf(lo[0], c.lox); lo[1] = fminf(lo[1], c.loy); lo[2] = fminf(lo[2], c.loz);
+        hi[0] = fmaxf(hi[0], c.hix); hi[1] = fmaxf(hi[1], c.hiy); hi[2] = fmaxf(hi[2], c.hiz);
+    }
+    TreeCostRecord r;
+    r.root = box_area((double)hi[0] - (double)lo[0], (double)hi[1] - (double)lo[1], (double)hi[2] - (double)lo[2]);
+    r.node = s_node[0]; r.leaf = s_leaf[0];
+    r.cost = (r.root + r.node + 2.7 * r.leaf) / r.root;
+    *out = r;
 }
 
 __global__ void k_refit_level(uint32_t first, uint32_t count, BvhNode4* __restrict__ nodes, TriRec* __restrict__ tris,
@@ -115,6 +196,21 @@ void fovpt_launch_gather_vertices_prev(hipStream_t st, const VertexTrack& g, con
     const uint64_t floats = 3ull * (g.max_n ? g.max_n : 1u);                  // (a mesh without vertices still gets its mark)
     const uint32_t gx = (uint32_t)(floats < 1024ull * FOVPT_BLOCK ? (floats + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
     hipLaunchKernelGGL(k_gather_vertices_prev, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, vtx, vtx_prev, mark, epoch);
+}
+
+void fovpt_launch_transform_vertices(hipStream_t st, const VertexTransform& g, const float* rest, float* vtx)
+{
+    if (g.count <= 0 || g.max_n == 0) return;
+    const uint64_t n = g.max_n;
+    const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
+    hipLaunchKernelGGL(k_transform_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, vtx);
+}
+
+void fovpt_launch_tree_cost(hipStream_t st, const BvhNode4* nodes, uint32_t num_nodes, double* partial, TreeCostRecord* rec)
+{
+    const uint32_t nblocks = fovpt_tree_cost_blocks(num_nodes);
+    if (nblocks) hipLaunchKernelGGL(k_tree_cost, dim3(nblocks), dim3(FOVPT_BLOCK), 0, st, nodes, num_nodes, partial);
+    hipLaunchKernelGGL(k_tree_cost_final, dim3(1), dim3(FOVPT_BLOCK), 0, st, nodes, partial, nblocks, rec);
 }
 
 void fovpt_launch_refit(hipStream_t st, BvhNode4* nodes, TriRec* tris, const uint32_t* levels, uint32_t num_levels, const uint3* tri_vidx,

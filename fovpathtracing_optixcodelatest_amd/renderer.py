@@ -422,6 +422,34 @@ class SampleRenderer:
         if device:
             self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
 
+    # -- rigid motion and the cost of the refit tree (include/fovpt.h, fovpt_update_transforms / fovpt_hierarchy_cost)
+    def update_transforms(self, transforms, rebuild=False):
+        """Per-mesh affine transforms of the positions the scene was set with: transforms maps a mesh index to a (3, 4) array,
+        or a (4, 4) one whose last row is 0 0 0 1 (ValueError otherwise).  Absolute, not cumulative; applied on the device, then
+        update_vertices()' refit (or, rebuild=True, rebuild) with the same ordering.  The renderer's Model is not changed."""
+        items = sorted(transforms.items())
+        tfs = (abi.MeshTransform * max(1, len(items)))()
+        for k, (mesh, m) in enumerate(items):
+            m = np.asarray(m, np.float32)
+            if m.shape == (4, 4):
+                if not np.array_equal(m[3], np.float32([0, 0, 0, 1])):
+                    raise ValueError("update_transforms: mesh %d: the last row of a (4, 4) matrix must be 0 0 0 1" % mesh)
+                m = m[:3]
+            if m.shape != (3, 4):
+                raise ValueError("update_transforms: mesh %d needs a (3, 4) or (4, 4) matrix" % mesh)
+            tfs[k].mesh = int(mesh)
+            tfs[k].m[:] = [float(x) for x in m.reshape(-1)]
+        self._check(self._L.fovpt_update_transforms(self._ctx, tfs, len(items), abi.UPDATE_REBUILD if rebuild else 0))
+
+    def hierarchy_cost(self, wait=False) -> abi.HierarchyCost:
+        """The SAH cost of the hierarchy as built and as last measured on the device (built, current, updates, measured).  The
+        first call switches watching on: every later refit is followed by a measurement.  wait=False never blocks and may lag
+        (measured < updates); wait=True measures the present tree if need be and waits for it.  Rebuild when current / built
+        passes your threshold."""
+        out = abi.HierarchyCost()
+        self._check(self._L.fovpt_hierarchy_cost(self._ctx, abi.COST_WAIT if wait else 0, C.byref(out)))
+        return out
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

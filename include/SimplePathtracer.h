@@ -212,6 +212,22 @@ public:
         }
         check(fovpt_update_vertices(ctx, up.data(), (int)up.size(), rebuild ? FOVPT_UPDATE_REBUILD : 0));
     }
+    // rigid motion: the listed meshes' rest positions (the Model's, when this renderer was built) through row-major 3 x 4
+    // matrices on the device, absolute not cumulative, then updateAccel()'s refit or rebuild (include/fovpt.h,
+    // fovpt_update_transforms).  The Model is not changed.
+    void updateTransforms(const std::vector<fovpt_mesh_transform>& transforms, bool rebuild = false)
+    {
+        check(fovpt_update_transforms(ctx, transforms.data(), (int)transforms.size(), rebuild ? FOVPT_UPDATE_REBUILD : 0));
+    }
+    // the SAH cost of the hierarchy as built and as last measured (include/fovpt.h, fovpt_hierarchy_cost): the first call
+    // switches the measurements on; wait = false never blocks and may lag, wait = true returns measured == updates.  Rebuild
+    // when current / built passes your threshold.
+    fovpt_hierarchy_cost_info hierarchyCost(bool wait = false)
+    {
+        fovpt_hierarchy_cost_info info;
+        check(fovpt_hierarchy_cost(ctx, wait ? FOVPT_COST_WAIT : 0, &info));
+        return info;
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

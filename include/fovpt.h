@@ -270,6 +270,55 @@ typedef struct fovpt_vertex_update {
 #define FOVPT_UPDATE_REBUILD 2   /* build the hierarchy anew over the updated vertices instead of refitting it              */
 int fovpt_update_vertices(fovpt_ctx* ctx, const fovpt_vertex_update* updates, int num_updates, int flags);
 
+/* ---- rigid (affine) motion: per-mesh transforms applied on the device ------------------------------------------------------
+ * fovpt_update_vertices for meshes that only turn, travel, scale or shear: twelve numbers per mesh instead of its vertices.
+ *   geometry   every vertex (x, y, z) of a named mesh's REST positions -- the ones fovpt_set_scene received, not the mesh's
+ *              current ones -- becomes
+ *                  x' = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]        y', z': the same with rows 1 and 2
+ *              every * and + one unfused binary32 operation.  Transforms are absolute: M1 then M2 leaves M2 . rest, and a mesh
+ *              fovpt_update_vertices has deformed is set from rest again.  Meshes not named keep what they last had, through
+ *              either call.  (An identity matrix turns a coordinate of -0 into +0: -0 + +0 = +0.)
+ *   contract   after the call every frame, G-buffer, debug trace, "scene_vertices" buffer and hierarchy byte is what
+ *              fovpt_update_vertices gives on the same context with those x', y', z' as host arrays.  Stream ordering, the
+ *              refit, fovpt_temporal_motion's tracking and FOVPT_UPDATE_REBUILD (the only flag accepted) are that call's own.
+ *   errors     all or nothing, checked before anything changes.  FOVPT_E_NO_SCENE: no scene.  FOVPT_E_INVALID: null ctx, null
+ *              transforms with num > 0, num < 0, a mesh out of range or listed twice, flag bits other than
+ *              FOVPT_UPDATE_REBUILD, a non-finite matrix entry, or a matrix that could overflow: with A the largest
+ *              |coordinate| of the mesh's rest positions, a row with (|m0| + |m1| + |m2|) * A + |m3| > 2^127 (in binary64).
+ *              Below that bound every intermediate value is finite.  Singular matrices are allowed.
+ *              num == 0 without FOVPT_UPDATE_REBUILD: FOVPT_OK, nothing happens.
+ * Device memory: the first call keeps a device copy of the rest positions (12 bytes per vertex) until the next
+ * fovpt_set_scene; a context that never calls it pays nothing.                                                              */
+typedef struct fovpt_mesh_transform {
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    float m[12];                 /* row-major 3 x 4: row r is m[4r .. 4r+3]                                                 */
+} fovpt_mesh_transform;
+int fovpt_update_transforms(fovpt_ctx* ctx, const fovpt_mesh_transform* transforms, int num, int flags);
+
+/* ---- the cost of the hierarchy, measured on the device -----------------------------------------------------------------------
+ * A refit keeps the tree's shape, so traversal slows as the motion grows (sections 13 and 16).  What to watch is
+ * the SAH cost of the nodes, in binary64: with d = hi - lo of a live child entry and area = dx * dy + dy * dz + dz * dx,
+ *     cost = (root + sum of the areas of node entries + 2.7 * sum of the areas of leaf entries) / root
+ * root being the area of the union of the root's live entries.  The caller rebuilds (FOVPT_UPDATE_REBUILD) when
+ * current / built passes its own threshold.
+ *   built      measured whenever a hierarchy is adopted (fovpt_set_scene, FOVPT_UPDATE_REBUILD).
+ *   updates    the refits and rebuilds issued on this scene so far, through either entry point (calls that did nothing are not
+ *              counted); fovpt_set_scene sets updates = measured = 0, a rebuild sets current = built, measured = updates.
+ *   watching   a context's first fovpt_hierarchy_cost switches it on for the life of the context: from then on every refit is
+ *              followed by a measurement on fovpt_stream(), enqueued behind the event frames wait for.  A context that never
+ *              asks issues no extra work per update.
+ *   flags 0    never blocks: the newest completed measurement, (current, measured) always a pair.  measured may lag updates.
+ *   COST_WAIT  if measured != updates, measures the present tree and waits for that measurement only: measured == updates.
+ *   errors     FOVPT_E_INVALID: null ctx or out, unknown flag bits.  FOVPT_E_NO_SCENE: no scene.                               */
+typedef struct fovpt_hierarchy_cost_info {
+    double built;                /* cost of the hierarchy as last built (fovpt_set_scene, FOVPT_UPDATE_REBUILD)             */
+    double current;              /* cost measured after update number `measured`                                            */
+    uint64_t updates;            /* refits and rebuilds issued on this scene so far, through either entry point             */
+    uint64_t measured;           /* the value of `updates` that `current` belongs to                                        */
+} fovpt_hierarchy_cost_info;
+#define FOVPT_COST_WAIT 1
+int fovpt_hierarchy_cost(fovpt_ctx* ctx, int flags, fovpt_hierarchy_cost_info* out);
+
 /* CUDAProbeData::createBuffer (Probe.h:102-124): uploads the 5 arrays, fills *probe_out
  * with device pointers exactly as setProbe does (SimplePathtracer.cpp:292-308).   */
 int fovpt_set_probe(fovpt_ctx* ctx, int width, int height, const fovpt_float4* data,
@@ -685,6 +734,8 @@ static_assert(sizeof(fovpt_temporal_config) == 32, "temporal config ABI");
 static_assert(sizeof(fovpt_post_config) == 112 && offsetof(fovpt_post_config, denoise) == 16 && offsetof(fovpt_post_config, reconstruct) == 48 &&
               offsetof(fovpt_post_config, temporal) == 80, "post config ABI");
 static_assert(sizeof(fovpt_vertex_update) == 16 && offsetof(fovpt_vertex_update, vertex) == 8, "vertex update ABI");
+static_assert(sizeof(fovpt_mesh_transform) == 52 && offsetof(fovpt_mesh_transform, m) == 4, "mesh transform ABI");
+static_assert(sizeof(fovpt_hierarchy_cost_info) == 32 && offsetof(fovpt_hierarchy_cost_info, updates) == 16, "hierarchy cost ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

@@ -1,0 +1,134 @@
+"""CPU tests of tests/transform_ref.py, the restatement fovpt_update_transforms is checked against on the GPU: the arithmetic
+against a scalar loop that rounds after every operation, the overflow rule on either side of 2^127, the cost tolerance; and of
+the ABI mirrors of fovpt_mesh_transform and fovpt_hierarchy_cost_info."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import transform_ref as tf
+from fovpathtracing_optixcodelatest_amd import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+def _scalar(rest, m):
+    """One vertex and one operation at a time, every result rounded to binary32."""
+    m = np.asarray(m, F).reshape(3, 4)
+    out = np.empty((len(rest), 3), F)
+    with np.errstate(over="ignore", under="ignore"):
+        for i, (x, y, z) in enumerate(np.asarray(rest, F)):
+            for r in range(3):
+                a, b, c = F(m[r, 0] * x), F(m[r, 1] * y), F(m[r, 2] * z)
+                out[i, r] = F(F(F(a + b) + c) + m[r, 3])
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+REST = (np.random.default_rng(5).standard_normal((37, 3)) * 300).astype(F)
+EDGE = np.array([[0.0, -0.0, 1e-30], [-0.0, 0.0, -1e-30], [1e30, -1e30, 1e-30], [1e-30, 1e30, -0.0], [1e30, 1e30, 1e30]], F)
+CASES = {
+    "rigid": (REST, tf.rotation_translation(23.0, (368.0, 0.0, 351.0), (-40.0, 12.0, -30.0))),
+    "scale": (REST, tf.scale_about((186.0, 0.0, 168.0), (1.3, 0.6, 0.9))),
+    "singular": (REST, tf.collapse_to((552.0, 274.0, 280.0))),
+    "rank_one": (REST, np.array([[1, 2, 3, 4], [2, 4, 6, 8], [0, 0, 0, 0]], F)),
+    # +-0, 1e-30 and 1e30 coordinates: entries up to 1e7 keep (|m0| + |m1| + |m2|) 1e30 + |m3| below 2^127 = 1.7e38; 1e-30 x 1e-9
+    # is subnormal
+    "edge": (EDGE, np.array([[1e7, -3e6, 0.5, 1e37], [1e-9, 1e-9, -1e-9, -0.0], [-1.0, 1.0, 1e7, 1e-38]], F)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_apply_is_the_scalar_expression(name):
+    rest, m = CASES[name]
+    assert tf.accepted(rest, m)
+    got, want = tf.apply(rest, m), _scalar(rest, m)
+    assert np.isfinite(got).all()
+    assert np.array_equal(_bits(got), _bits(want))
+    if name == "singular":
+        assert (got == F([552.0, 274.0, 280.0])).all()
+
+
+def test_identity_keeps_values_and_loses_the_sign_of_zero():
+    rest = np.concatenate([REST, EDGE])
+    got = tf.apply(rest, tf.IDENTITY)
+    assert np.array_equal(got, rest)                                     # equal as numbers ...
+    assert (rest == 0).any() and np.signbit(rest[rest == 0]).any()
+    assert not np.signbit(got[rest == 0]).any()                          # ... and -0 + +0 = +0
+    nz = rest != 0
+    assert np.array_equal(_bits(got[nz]), _bits(rest[nz]))
+    assert np.array_equal(_bits(tf.apply(rest, np.eye(4, dtype=F))), _bits(got))     # the (4, 4) form
+
+
+def test_transforms_are_absolute():
+    m1, m2 = CASES["rigid"][1], CASES["scale"][1]
+
+    class M:
+        meshes = [type("Mesh", (), {"vertex": REST})()]
+
+    first = tf.restate(M, {0: m1})
+    second = tf.restate(M, {0: m2})                                       # from rest again, not from `first`
+    assert np.array_equal(_bits(second[0]), _bits(tf.apply(REST, m2)))
+    assert not np.array_equal(_bits(second[0]), _bits(tf.apply(first[0], m2)))
+
+
+def test_overflow_bound_on_either_side_of_two_to_the_127():
+    rest = np.array([[2.0 ** 100, 0, 0], [0, -(2.0 ** 99), 1.0]], F)      # A = 2^100
+    m = np.zeros((3, 4), F)
+    m[0, 0] = F(2.0 ** 27)                                               # 2^27 2^100 = 2^127: not above
+    assert tf.overflow_bound(rest, m) == 2.0 ** 127 and tf.accepted(rest, m)
+    assert np.isfinite(tf.apply(rest, m)).all()
+    m[0, 0] = np.nextafter(F(2.0 ** 27), F(np.inf))
+    assert tf.overflow_bound(rest, m) > 2.0 ** 127 and not tf.accepted(rest, m)
+    m[0, 0] = F(2.0 ** 26)
+    m[0, 1] = F(-(2.0 ** 26))                                            # the bound adds magnitudes: 2^127 again
+    assert tf.accepted(rest, m)
+    m[0, 3] = F(2.0 ** 80)                                               # 2^127 + 2^80, exact in binary64
+    assert not tf.accepted(rest, m)
+    m = tf.IDENTITY.copy()
+    m[2, 3] = F(2.0 ** 127)                                              # the translation alone reaches it: 2^100 + 2^127 > 2^127
+    assert not tf.accepted(rest, m)
+    assert tf.accepted(np.zeros((0, 3), F), m)                           # no vertices: A = 0, 2^127 is not above
+    for bad in (np.nan, np.inf, -np.inf):
+        m = tf.IDENTITY.copy()
+        m[1, 2] = bad
+        assert not tf.accepted(rest, m)
+    # below the bound nothing overflows, whatever the signs
+    rng = np.random.default_rng(9)
+    for _ in range(50):
+        m = (rng.choice([-1.0, 1.0], (3, 4)) * 2.0 ** rng.uniform(20, 26.4, (3, 4))).astype(F)
+        r = (rng.choice([-1.0, 1.0], (64, 3)) * 2.0 ** rng.uniform(90, 100, (64, 3))).astype(F)
+        if tf.accepted(r, m):
+            assert np.isfinite(tf.apply(r, m)).all()
+
+
+def test_cost_tolerance_is_the_stated_expression():
+    assert tf.cost_tolerance(0) == 16 * 2.0 ** -52
+    assert tf.cost_tolerance(1000) == 1016 * 2.0 ** -52
+    nodes = np.zeros((2, 32), np.uint32)
+    f = nodes.view(F).reshape(2, 4, 8)
+    f[:, :, 0:6] = np.inf
+    f[0, 0, 0:6] = (0, 0, 0, 1, 1, 1)
+    f[0, 2, 0:6] = (0, 0, 0, 2, 1, 1)
+    f[1, 3, 0:6] = (0, 0, 0, 2, 1, 1)
+    assert tf.live_entries(nodes, [0, 1, 2]) == 3 and tf.live_entries(nodes, [0, 1]) == 2
+
+
+def test_abi_mirrors_match_the_header(tmp_path):
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %d", '
+           'sizeof(fovpt_mesh_transform), offsetof(fovpt_mesh_transform, mesh), offsetof(fovpt_mesh_transform, m), '
+           'sizeof(fovpt_hierarchy_cost_info), offsetof(fovpt_hierarchy_cost_info, built), offsetof(fovpt_hierarchy_cost_info, current), '
+           'offsetof(fovpt_hierarchy_cost_info, updates), offsetof(fovpt_hierarchy_cost_info, measured), FOVPT_COST_WAIT); return 0;}\n')
+    exe = str(tmp_path / "tf_layout")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    T, H = abi.MeshTransform, abi.HierarchyCost
+    assert got == [ctypes.sizeof(T), T.mesh.offset, T.m.offset, ctypes.sizeof(H), H.built.offset, H.current.offset, H.updates.offset,
+                   H.measured.offset, abi.COST_WAIT]
+    assert got[0] == 52 and got[3] == 32

@@ -5,7 +5,13 @@ FOVPT_UPDATE_REBUILD (host-synchronous: wall clock, and the build's own stats.ms
 Quality: a quarter of the meshes turn about their centres by 3 degrees per frame for --frames frames, refit after each; then
 tools/bvhstat.py's SAH cost and the frame time of the refit tree against the same geometry rebuilt.  Prints one JSON line per
 scene.  Kernel statistics are a separate run:
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/refit_perf.py --scenes c3 --calls 20 --frames 0"""
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/refit_perf.py --scenes c3 --calls 20 --frames 0
+
+--transforms: fovpt_update_transforms and fovpt_hierarchy_cost instead.  On one context, every mesh moved, --rounds rounds of
+update_transforms and update_vertices with device pointers in turn (ms per call, device time), first while nobody watches the
+cost and then, after the context's first hierarchy_cost(), with a measurement behind every refit: what a measurement costs is
+the difference (its kernels' own times: the kernel-trace run above with --transforms).  Then the quality experiment with the
+device's current / built ratio polled after every frame's refit, beside the frame times."""
 import argparse
 import ctypes as C
 import json
@@ -72,7 +78,7 @@ def turn(v, deg):
     return ((v.astype(np.float64) - c) @ R.T + c).astype(np.float32)
 
 
-def run(name, calls, warmup, frames):
+def make_renderer(name):
     S = SCENES[name]
     model = S["make"]()
     W, H = S["size"]
@@ -88,6 +94,11 @@ def run(name, calls, warmup, frames):
     r.config = cfg
     r.launchParams.frame.c.x, r.launchParams.frame.c.y = W // 2, H // 2
     r.render()
+    return model, r
+
+
+def run(name, calls, warmup, frames):
+    model, r = make_renderer(name)
     st0 = r.stats()
     host = {k: np.ascontiguousarray(m.vertex, np.float32) for k, m in enumerate(model.meshes)}
     dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
@@ -122,15 +133,89 @@ def run(name, calls, warmup, frames):
     print(json.dumps(out), flush=True)
 
 
+def turn_matrix(v, deg):
+    """turn() as a row-major 3 x 4 matrix."""
+    c = v.mean(axis=0, dtype=np.float64)
+    a = np.deg2rad(deg)
+    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    return np.concatenate([R, (c - R @ c)[:, None]], axis=1).astype(np.float32)
+
+
+def run_transforms(name, calls, warmup, frames, rounds):
+    import transform_ref as tf
+    model, r = make_renderer(name)
+    st0 = r.stats()
+    ts = {k: turn_matrix(m.vertex, 3.0) for k, m in enumerate(model.meshes)}
+    dev = {k: torch.from_numpy(v).cuda() for k, v in tf.restate(model, ts).items()}
+    torch.cuda.synchronize()
+    out = dict(scene=name, triangles=model.num_triangles, meshes=len(model.meshes), bvh_nodes=int(st0.num_bvh_nodes),
+               vertices=int(sum(m.vertex.shape[0] for m in model.meshes)), rounds=rounds, calls=calls)
+    t_ms = {False: [], True: []}
+    v_ms = {False: [], True: []}
+    for watching in (False, True):
+        if watching:
+            r.hierarchy_cost()                                  # from here on a measurement follows every refit
+        for _ in range(rounds):
+            t_ms[watching].append(device_ms(r, lambda: r.update_transforms(ts), calls, warmup)[0])
+            v_ms[watching].append(device_ms(r, lambda: r.update_vertices(dev), calls, warmup)[0])
+    med = lambda x: float(np.median(x))
+    out["update_transforms_ms"] = round(med(t_ms[False]), 4)
+    out["update_vertices_device_ms"] = round(med(v_ms[False]), 4)
+    out["update_transforms_ms_rounds"] = [round(x, 4) for x in t_ms[False]]
+    out["update_vertices_device_ms_rounds"] = [round(x, 4) for x in v_ms[False]]
+    out["update_transforms_watched_ms"] = round(med(t_ms[True]), 4)
+    out["update_vertices_device_watched_ms"] = round(med(v_ms[True]), 4)
+    out["cost_measurement_ms"] = round(0.5 * (med(t_ms[True]) - med(t_ms[False]) + med(v_ms[True]) - med(v_ms[False])), 4)
+    c = r.hierarchy_cost(wait=True)
+    out["measured_of_updates"] = [int(c.measured), int(c.updates)]
+    t = time.perf_counter()
+    for _ in range(20):
+        r.hierarchy_cost()
+    out["poll_host_us"] = round((time.perf_counter() - t) / 20 * 1e6, 2)
+    if frames:
+        # the quality experiment of run(), the motion sent as matrices: turn k of a moving mesh is 3 (k + 1) degrees from rest
+        r.update_transforms({k: np.eye(3, 4, dtype=np.float32) for k in range(len(model.meshes))}, rebuild=True)
+        moving = list(range(0, len(model.meshes), 4))
+        out["frame_ms_built"] = round(frame_ms(r), 4)
+        ratios, lag = [], 0
+        for f in range(frames):
+            r.update_transforms({k: turn_matrix(model.meshes[k].vertex, 3.0 * (f + 1)) for k in moving})
+            r.launchParams.frame.subframe_index = 0
+            r.render_async()
+            c = r.hierarchy_cost()                              # the caller's poll: never waits
+            lag = max(lag, int(c.updates - c.measured))
+            ratios.append(c.current / c.built)
+        c = r.hierarchy_cost(wait=True)
+        ratios.append(c.current / c.built)
+        out["cost_ratio_every_10_frames"] = [round(x, 3) for x in ratios[9::10]]
+        out["cost_ratio_final"] = round(ratios[-1], 3)
+        out["cost_built"], out["cost_current"] = round(c.built, 3), round(c.current, 3)
+        out["poll_lag_max_updates"] = lag
+        nodes = nodes_of(r)
+        out["sah_refit_host"] = round(rf.sah_cost(nodes, rf.levels_of(nodes)), 3)
+        out["frame_ms_refit_after_%d" % frames] = round(frame_ms(r), 4)
+        r.update_transforms({}, rebuild=True)
+        out["frame_ms_rebuilt_after_%d" % frames] = round(frame_ms(r), 4)
+        out["cost_rebuilt"] = round(r.hierarchy_cost().built, 3)
+        out["moving_meshes"] = len(moving)
+    r.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c3,street")
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--transforms", action="store_true", help="fovpt_update_transforms and fovpt_hierarchy_cost instead of fovpt_update_vertices")
+    ap.add_argument("--rounds", type=int, default=5, help="--transforms: rounds of the alternated timings (at least 5)")
     a = ap.parse_args()
     for s in a.scenes.split(","):
-        run(s, a.calls, a.warmup, a.frames)
+        if a.transforms:
+            run_transforms(s, a.calls, a.warmup, a.frames, max(5, a.rounds))
+        else:
+            run(s, a.calls, a.warmup, a.frames)
 
 
 if __name__ == "__main__":
