@@ -157,6 +157,21 @@ class HierarchyCost(C.Structure):
     _fields_ = [("built", C.c_double), ("current", C.c_double), ("updates", C.c_uint64), ("measured", C.c_uint64)]
 
 
+SKIN_MAX_JOINTS = 1024                          # FOVPT_SKIN_MAX_JOINTS
+
+
+class MeshSkin(C.Structure):
+    """fovpt_mesh_skin: four joint indices and four weights per vertex of one mesh (fovpt_set_skins); num_joints 0 and two null
+    pointers remove the mesh's skin."""
+    _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("num_joints", C.c_uint32), ("_reserved", C.c_uint32),
+                ("joints", C.c_void_p), ("weights", C.c_void_p)]
+
+
+class SkinPose(C.Structure):
+    """fovpt_skin_pose: the palette of one skinned mesh, num_joints row-major 3 x 4 matrices (fovpt_update_skinned)."""
+    _fields_ = [("mesh", C.c_int32), ("num_joints", C.c_uint32), ("matrices", C.c_void_p)]
+
+
 class TextureDesc(C.Structure):
     _fields_ = [("pixel", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -304,6 +319,8 @@ assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.re
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4
 assert C.sizeof(HierarchyCost) == 32 and HierarchyCost.updates.offset == 16
+assert C.sizeof(MeshSkin) == 32 and (MeshSkin.joints.offset, MeshSkin.weights.offset) == (16, 24)
+assert C.sizeof(SkinPose) == 16 and SkinPose.matrices.offset == 8
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

@@ -143,6 +143,8 @@ void free_scene(fovpt_ctx* c)
     for (void* p : c->tex_pixels) (void)hipFree(p);
     c->tex_pixels.clear();
     c->has_scene = false;
+    c->skins.clear();                               // fovpt_set_skins: the skins are the scene's
+    c->skin_joints.release(); c->skin_weights.release(); c->skin_pal.release();
 }
 
 // A queue shard receives the appends of the blocks whose index is congruent to it modulo FOVPT_SHARDS.  The
@@ -654,17 +656,48 @@ int check_updatable(fovpt_ctx* c, const char* who)
 }
 
 // Where the new positions of update_scene come from: `up` (host arrays through a staging buffer, `floats` of them in all, or
-// device arrays by a gather kernel) or `tf` (the rest positions through per-mesh matrices); all `num` validated.
+// device arrays by a gather kernel), `tf` (the rest positions through per-mesh matrices) or `sk` (the rest positions through
+// per-vertex blends of per-mesh joint palettes: host palettes through the staging buffer, `floats` of them in all, or device
+// palettes in place); all `num` validated.
 struct UpdateSource {
     const fovpt_vertex_update* up;
     bool device;
     size_t floats;
     const fovpt_mesh_transform* tf;
     int num;
-    int mesh(int k) const { return up ? up[k].mesh : tf[k].mesh; }
+    const fovpt_skin_pose* sk;
+    int mesh(int k) const { return up ? up[k].mesh : tf ? tf[k].mesh : sk[k].mesh; }
 };
 
-// The update itself, shared by fovpt_update_vertices and fovpt_update_transforms: fovpt_temporal_motion's copy of the positions
+// The next of the two pinned staging buffers, with room for `bytes`, once the copies it last fed have run
+int take_stage(fovpt_ctx* c, size_t bytes, fovpt_ctx::Staging** out)
+{
+    auto& S = c->up_stage[c->up_next];
+    c->up_next ^= 1;
+    if (S.pending) { HIPCHK(c, hipEventSynchronize(S.ev)); S.pending = false; }      // its previous copy has run
+    if (S.bytes < bytes) {
+        if (S.p) (void)hipHostFree(S.p);
+        S.p = nullptr; S.bytes = 0;
+        HIPCHK(c, hipHostMalloc(&S.p, bytes, hipHostMallocDefault));
+        S.bytes = bytes;
+    }
+    *out = &S;
+    return FOVPT_OK;
+}
+
+// Once per scene, for the overflow rules: the largest |coordinate| of every mesh's rest positions
+void ensure_absmax(fovpt_ctx* c)
+{
+    if (!c->mesh_absmax.empty()) return;
+    const int nmesh = (int)c->mesh_nv.size();
+    c->mesh_absmax.assign((size_t)nmesh, 0.0);
+    for (int m = 0; m < nmesh; m++) {
+        const float* v = c->h_vtx.data() + 3 * (size_t)c->mesh_vbase[m];
+        for (size_t i = 0; i < 3 * (size_t)c->mesh_nv[m]; i++) c->mesh_absmax[m] = std::fmax(c->mesh_absmax[m], std::fabs((double)v[i]));
+    }
+}
+
+// The update itself, shared by fovpt_update_vertices, fovpt_update_transforms and fovpt_update_skinned: fovpt_temporal_motion's copy of the positions
 // about to be overwritten, the new positions into up_vtx on fovpt_stream(), and either the refit, enqueued behind them on the
 // same stream (the stream every job's resolve, and so every job's last traversal launch, is ordered on) with the event the next
 // job waits for, or a rebuild.
@@ -707,12 +740,45 @@ int update_scene(fovpt_ctx* c, const UpdateSource& s, bool rebuild)
         }
         HIPCHK(c, hipGetLastError());
     }
-    if (s.tf) {
-        if (!c->rest_vtx.p) {
-            // the first transforms of the scene: the rest positions stay on the device
-            HIPCHK(c, c->rest_vtx.reserve(c->h_vtx.size() * 4));
-            HIPCHK(c, hipMemcpyAsync(c->rest_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
+    if ((s.tf || s.sk) && !c->rest_vtx.p) {
+        // the first transforms or poses of the scene: the rest positions stay on the device
+        HIPCHK(c, c->rest_vtx.reserve(c->h_vtx.size() * 4));
+        HIPCHK(c, hipMemcpyAsync(c->rest_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    if (s.sk) {
+        if (!s.device && s.floats) {
+            // host palettes: staged in call order, each copied to its mesh's place in skin_pal (neighbours in one copy)
+            fovpt_ctx::Staging* S = nullptr;
+            { const int rc_ = take_stage(c, s.floats * 4, &S); if (rc_) return rc_; }
+            float* h = (float*)S->p;
+            for (int k = 0; k < s.num;) {
+                const uint32_t first = c->skins[s.sk[k].mesh].pal_first;
+                size_t joints = 0;
+                do {
+                    memcpy(h + 12 * joints, s.sk[k].matrices, 48 * (size_t)s.sk[k].num_joints);
+                    joints += s.sk[k].num_joints;
+                } while (++k < s.num && c->skins[s.sk[k].mesh].pal_first == first + joints);
+                HIPCHK(c, hipMemcpyAsync((float*)c->skin_pal.p + 12 * (size_t)first, h, 48 * joints, hipMemcpyHostToDevice, st));
+                h += 12 * joints;
+            }
+            HIPCHK(c, hipEventRecord(S->ev, st));
+            S->pending = true;
         }
+        VertexSkin g;
+        memset(&g, 0, sizeof(g));
+        for (int k = 0; k < s.num; k++) {
+            const fovpt_ctx::Skin& K = c->skins[s.sk[k].mesh];
+            const uint32_t nv = c->mesh_nv[s.sk[k].mesh];
+            g.pal[g.count] = s.device ? s.sk[k].matrices : (const float*)c->skin_pal.p + 12 * (size_t)K.pal_first;
+            g.first[g.count] = c->mesh_vbase[s.sk[k].mesh]; g.n[g.count] = nv; g.skin[g.count] = K.first;
+            g.max_n = nv > g.max_n ? nv : g.max_n;
+            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == s.num) {
+                fovpt_launch_skin_vertices(st, g, (const float*)c->rest_vtx.p, (const uint2*)c->skin_joints.p, (const float4*)c->skin_weights.p, vtx);
+                memset(&g, 0, sizeof(g));
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+    } else if (s.tf) {
         VertexTransform g;
         memset(&g, 0, sizeof(g));
         for (int k = 0; k < s.num; k++) {
@@ -733,24 +799,17 @@ int update_scene(fovpt_ctx* c, const UpdateSource& s, bool rebuild)
         }
         HIPCHK(c, hipGetLastError());
     } else if (s.floats) {
-        auto& S = c->up_stage[c->up_next];
-        c->up_next ^= 1;
-        if (S.pending) { HIPCHK(c, hipEventSynchronize(S.ev)); S.pending = false; }      // its previous copy has run
-        if (S.bytes < s.floats * 4) {
-            if (S.p) (void)hipHostFree(S.p);
-            S.p = nullptr; S.bytes = 0;
-            HIPCHK(c, hipHostMalloc(&S.p, s.floats * 4, hipHostMallocDefault));
-            S.bytes = s.floats * 4;
-        }
-        float* h = (float*)S.p;
+        fovpt_ctx::Staging* S = nullptr;
+        { const int rc_ = take_stage(c, s.floats * 4, &S); if (rc_) return rc_; }
+        float* h = (float*)S->p;
         for (int k = 0; k < s.num; k++) {
             const size_t n = 3 * (size_t)s.up[k].num_vertices;
             memcpy(h, s.up[k].vertex, n * 4);
             HIPCHK(c, hipMemcpyAsync(vtx + 3 * (size_t)c->mesh_vbase[s.up[k].mesh], h, n * 4, hipMemcpyHostToDevice, st));
             h += n;
         }
-        HIPCHK(c, hipEventRecord(S.ev, st));
-        S.pending = true;
+        HIPCHK(c, hipEventRecord(S->ev, st));
+        S->pending = true;
     }
     if (!rebuild) {
         fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, vtx);
@@ -1041,7 +1100,7 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
     }
     { const int rc_ = check_updatable(c, "fovpt_update_vertices"); if (rc_) return rc_; }
     if (num_updates == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {up, device, floats, nullptr, num_updates};
+    const UpdateSource src = {up, device, floats, nullptr, num_updates, nullptr};
     return update_scene(c, src, rebuild);
 }
 
@@ -1055,14 +1114,7 @@ int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int nu
     if (num < 0 || (num > 0 && !tf)) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: %d transforms at %p", num, (const void*)tf);
     if (flags & ~FOVPT_UPDATE_REBUILD) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: flag bits %d (FOVPT_UPDATE_REBUILD is the only one accepted)", flags);
     const int nmesh = (int)c->mesh_nv.size();
-    if (num > 0 && c->mesh_absmax.empty()) {
-        // once per scene: the largest |coordinate| of every mesh's rest positions
-        c->mesh_absmax.assign((size_t)nmesh, 0.0);
-        for (int m = 0; m < nmesh; m++) {
-            const float* v = c->h_vtx.data() + 3 * (size_t)c->mesh_vbase[m];
-            for (size_t i = 0; i < 3 * (size_t)c->mesh_nv[m]; i++) c->mesh_absmax[m] = std::fmax(c->mesh_absmax[m], std::fabs((double)v[i]));
-        }
-    }
+    if (num > 0) ensure_absmax(c);
     std::vector<char> seen((size_t)nmesh, 0);
     for (int k = 0; k < num; k++) {
         const fovpt_mesh_transform& T = tf[k];
@@ -1080,7 +1132,124 @@ int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int nu
     { const int rc_ = check_updatable(c, "fovpt_update_transforms"); if (rc_) return rc_; }
     const bool rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
     if (num == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {nullptr, false, 0, tf, num};
+    const UpdateSource src = {nullptr, false, 0, tf, num, nullptr};
+    return update_scene(c, src, rebuild);
+}
+
+// The skins are kept on the host per mesh; every call lays the device copies out anew (the skinned meshes' vertices and joints
+// in mesh order), so a mesh's places in skin_joints / skin_weights / skin_pal are fixed until the next call.
+int fovpt_set_skins(fovpt_ctx* c, const fovpt_mesh_skin* skins, int num)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_set_skins without a scene");
+    if (num < 0 || (num > 0 && !skins)) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: %d skins at %p", num, (const void*)skins);
+    const int nmesh = (int)c->mesh_nv.size();
+    std::vector<char> seen((size_t)nmesh, 0);
+    std::vector<double> sums((size_t)(num > 0 ? num : 0), 0.0);
+    for (int k = 0; k < num; k++) {
+        const fovpt_mesh_skin& K = skins[k];
+        if (K.mesh < 0 || K.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d of %d", K.mesh, nmesh);
+        if (seen[K.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d is listed twice", K.mesh);
+        seen[K.mesh] = 1;
+        if (K._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: _reserved is %u", K.mesh, K._reserved);
+        if (K.num_vertices != c->mesh_nv[K.mesh])
+            return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d has %u vertices, not %u", K.mesh, c->mesh_nv[K.mesh], K.num_vertices);
+        if (K.num_joints > FOVPT_SKIN_MAX_JOINTS) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: %u joints (at most %d)", K.mesh, K.num_joints, FOVPT_SKIN_MAX_JOINTS);
+        if (K.num_joints == 0) {
+            if (K.joints || K.weights) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: no joints, but a pointer (removing a skin takes two null pointers)", K.mesh);
+            continue;
+        }
+        if (!K.joints || !K.weights) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: null joints or weights", K.mesh);
+        for (size_t i = 0; i < 4 * (size_t)K.num_vertices; i++) {
+            if (K.joints[i] >= K.num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d vertex %zu: joint %u of %u", K.mesh, i / 4, (unsigned)K.joints[i], K.num_joints);
+            if (!(K.weights[i] >= 0.0f && K.weights[i] <= 1.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d vertex %zu: weight %g is not in [0, 1]", K.mesh, i / 4, (double)K.weights[i]);
+        }
+        for (size_t i = 0; i < (size_t)K.num_vertices; i++) {
+            const float* w = K.weights + 4 * i;
+            sums[k] = std::fmax(sums[k], (((double)w[0] + (double)w[1]) + (double)w[2]) + (double)w[3]);
+        }
+    }
+    if (num == 0) return FOVPT_OK;
+    // the new layout, and its device buffers before anything changes
+    std::vector<uint32_t> nj((size_t)nmesh, 0);
+    for (int m = 0; m < nmesh; m++) nj[m] = c->skins.empty() ? 0 : c->skins[m].num_joints;
+    for (int k = 0; k < num; k++) nj[skins[k].mesh] = skins[k].num_joints;
+    size_t verts = 0, joints = 0;
+    for (int m = 0; m < nmesh; m++)
+        if (nj[m]) { verts += c->mesh_nv[m]; joints += nj[m]; }
+    if (verts >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: more than 2^32 - 1 skinned vertices");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf d_joints, d_weights, d_pal;
+    if (joints) {
+        HIPCHK(c, d_joints.reserve(verts ? verts * 8 : 8));
+        HIPCHK(c, d_weights.reserve(verts ? verts * 16 : 16));
+        HIPCHK(c, d_pal.reserve(joints * 48));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_skinned in flight reads the buffers about to go
+    if (c->skins.empty()) c->skins.resize((size_t)nmesh);
+    for (int k = 0; k < num; k++) {
+        const fovpt_mesh_skin& K = skins[k];
+        fovpt_ctx::Skin& D = c->skins[K.mesh];
+        D.num_joints = K.num_joints; D.S = sums[k];
+        if (K.num_joints) { D.joints.assign(K.joints, K.joints + 4 * (size_t)K.num_vertices); D.weights.assign(K.weights, K.weights + 4 * (size_t)K.num_vertices); }
+        else { std::vector<uint16_t>().swap(D.joints); std::vector<float>().swap(D.weights); }
+    }
+    uint32_t first = 0, pal_first = 0;
+    for (int m = 0; m < nmesh; m++) {
+        fovpt_ctx::Skin& D = c->skins[m];
+        D.first = first; D.pal_first = pal_first;
+        if (!D.num_joints) continue;
+        if (c->mesh_nv[m]) {
+            HIPCHK(c, hipMemcpy((char*)d_joints.p + 8 * (size_t)first, D.joints.data(), 8 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy((char*)d_weights.p + 16 * (size_t)first, D.weights.data(), 16 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
+        }
+        first += c->mesh_nv[m]; pal_first += D.num_joints;
+    }
+    std::swap(c->skin_joints.p, d_joints.p); std::swap(c->skin_joints.bytes, d_joints.bytes);
+    std::swap(c->skin_weights.p, d_weights.p); std::swap(c->skin_weights.bytes, d_weights.bytes);
+    std::swap(c->skin_pal.p, d_pal.p); std::swap(c->skin_pal.bytes, d_pal.bytes);
+    return FOVPT_OK;
+}
+
+// The rest positions of the named meshes through the blends of their palettes (k_skin_vertices), then fovpt_update_vertices'
+// refit or rebuild.  For host palettes the overflow rule keeps every intermediate value finite, as fovpt_update_transforms' does.
+int fovpt_update_skinned(fovpt_ctx* c, const fovpt_skin_pose* poses, int num, int flags)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_skinned without a scene");
+    if (num < 0 || (num > 0 && !poses)) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: %d poses at %p", num, (const void*)poses);
+    if (flags & ~(FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD)) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: unknown flag bits %d", flags);
+    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    const int nmesh = (int)c->mesh_nv.size();
+    if (num > 0 && !device) ensure_absmax(c);
+    std::vector<char> seen((size_t)nmesh, 0);
+    size_t floats = 0;
+    for (int k = 0; k < num; k++) {
+        const fovpt_skin_pose& P = poses[k];
+        if (P.mesh < 0 || P.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d of %d", P.mesh, nmesh);
+        if (seen[P.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d is listed twice", P.mesh);
+        seen[P.mesh] = 1;
+        if (c->skins.empty() || !c->skins[P.mesh].num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d has no skin", P.mesh);
+        const fovpt_ctx::Skin& K = c->skins[P.mesh];
+        if (P.num_joints != K.num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d: %u joints, its skin has %u", P.mesh, P.num_joints, K.num_joints);
+        if (!P.matrices) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d: null matrices", P.mesh);
+        floats += 12 * (size_t)P.num_joints;
+        if (device) continue;
+        for (size_t i = 0; i < 12 * (size_t)P.num_joints; i++)
+            if (!std::isfinite(P.matrices[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d joint %zu entry %zu is not finite", P.mesh, i / 12, i % 12);
+        for (size_t r = 0; r < 3 * (size_t)P.num_joints; r++) {
+            const float* row = P.matrices + 4 * r;
+            const double bound = K.S * ((std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * c->mesh_absmax[P.mesh] + std::fabs((double)row[3]));
+            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d joint %zu row %zu could overflow (bound %g > 2^127)", P.mesh, r / 3, r % 3, bound);
+            // (the blended matrix is formed first: its entries are within S times the palette's, which the row's bound covers
+            // for the fourth column and, for the others, only when A >= 1)
+            const double entry = K.S * std::fmax(std::fmax(std::fabs((double)row[0]), std::fabs((double)row[1])), std::fabs((double)row[2]));
+            if (entry > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d joint %zu row %zu: a blended entry could overflow (%g > 2^127)", P.mesh, r / 3, r % 3, entry);
+        }
+    }
+    { const int rc_ = check_updatable(c, "fovpt_update_skinned"); if (rc_) return rc_; }
+    if (num == 0 && !rebuild) return FOVPT_OK;
+    const UpdateSource src = {nullptr, device, floats, nullptr, num, poses};
     return update_scene(c, src, rebuild);
 }
 

@@ -94,6 +94,14 @@ struct fovpt_ctx {
     // vertex) and, per mesh, the largest |coordinate| of its rest positions (the overflow rule)
     DevBuf rest_vtx;
     std::vector<double> mesh_absmax;
+    // fovpt_set_skins / fovpt_update_skinned.  skins: empty until a scene's first fovpt_set_skins, then one entry per mesh
+    // (num_joints 0: no skin) with the host copy of the skin, its largest weight sum S (the overflow rule), the mesh's first
+    // vertex in skin_joints / skin_weights (the skinned meshes' vertices in mesh order: 8 B of indices and 16 B of weights each)
+    // and its first joint in skin_pal (12 floats per joint, where host matrices go; rest_vtx and up_stage are shared with the
+    // calls above).  Laid out anew by every fovpt_set_skins; dropped by fovpt_set_scene.
+    struct Skin { uint32_t num_joints = 0, first = 0, pal_first = 0; double S = 0.0; std::vector<uint16_t> joints; std::vector<float> weights; };
+    std::vector<Skin> skins;
+    DevBuf skin_joints, skin_weights, skin_pal;
     // fovpt_hierarchy_cost.  cost_built / cost_current / cost_updates / cost_measured: the caller's record.  cost_partial: the
     // block sums of k_tree_cost, sized when a hierarchy is adopted.  cost_slot: result records in pinned host memory the final
     // kernel writes, each with the event recorded behind it and the update number it measures; a slot is free once its event has

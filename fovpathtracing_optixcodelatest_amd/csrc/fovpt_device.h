@@ -316,6 +316,19 @@ struct VertexTransform {
     uint32_t max_n;
 };
 void fovpt_launch_transform_vertices(hipStream_t st, const VertexTransform& g, const float* rest, float* vtx);
+// fovpt_update_skinned: up to FOVPT_GATHER_BATCH meshes, each the n vertices from `first` on of rest through the blend of its
+// four joints' matrices into vtx (M[e] = ((w0 J[j0][e] + w1 J[j1][e]) + w2 J[j2][e]) + w3 J[j3][e], then VertexTransform's
+// expression with M; unfused binary32).  Vertex i of mesh u has its four joint indices at joints[skin[u] + i] and its weights at
+// weights[skin[u] + i]; pal[u] is the mesh's palette, 12 floats per joint.
+struct VertexSkin {
+    const float* pal[FOVPT_GATHER_BATCH];
+    uint32_t first[FOVPT_GATHER_BATCH]; // first vertex in rest and vtx
+    uint32_t n[FOVPT_GATHER_BATCH];     // vertices
+    uint32_t skin[FOVPT_GATHER_BATCH];  // first vertex in joints and weights
+    int32_t count;
+    uint32_t max_n;
+};
+void fovpt_launch_skin_vertices(hipStream_t st, const VertexSkin& g, const float* rest, const uint2* joints, const float4* weights, float* vtx);
 // fovpt_hierarchy_cost: the SAH cost of the num_nodes wide nodes in binary64, the same value from run to run.  partial: two
 // doubles per block of fovpt_tree_cost_blocks(num_nodes); rec: where the result goes (device-visible memory).
 struct TreeCostRecord { double cost, root, node, leaf; };     // (root + node + 2.7 leaf) / root and its three terms

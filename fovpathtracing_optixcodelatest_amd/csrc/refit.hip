@@ -10,7 +10,8 @@
 // build's boxes bit for bit (without spatial splits: a split reference's clipped box becomes its whole triangle's box).
 //
 // Also here: fovpt_update_transforms' k_transform_vertices (rest positions through per-mesh 3 x 4 matrices into the vertex array,
-// ahead of the same refit) and fovpt_hierarchy_cost's k_tree_cost / k_tree_cost_final (the SAH cost of the nodes in binary64).
+// ahead of the same refit), fovpt_update_skinned's k_skin_vertices (the same with a matrix blended per vertex from its mesh's joint
+// palette) and fovpt_hierarchy_cost's k_tree_cost / k_tree_cost_final (the SAH cost of the nodes in binary64).
 #include "fovpt_device.h"
 
 namespace {
@@ -62,6 +63,38 @@ __global__ void k_transform_vertices(VertexTransform g, const float* __restrict_
         const size_t n = g.n[u];
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
             const float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+            dst[3 * i] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+            dst[3 * i + 1] = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+            dst[3 * i + 2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+        }
+    }
+}
+
+// fovpt_update_skinned: k_transform_vertices' launch shape.  Per vertex 12 B of rest, one 8-byte load of the four joint indices,
+// one 16-byte load of the weights and four 48-byte palette rows (at most 48 KB per mesh, read by every block of the mesh: cache
+// resident after the first touch); the blended matrix entry by entry, then the vertex through it, every operation unfused
+// (-ffp-contract=off); 12 B written.  Joint indices were checked against the palette's size by fovpt_set_skins.
+__global__ void k_skin_vertices(VertexSkin g, const float* __restrict__ rest, const uint2* __restrict__ joints, const float4* __restrict__ weights,
+                                float* __restrict__ vtx)
+{
+    for (int u = blockIdx.y; u < g.count; u += gridDim.y) {
+        const float* __restrict__ pal = g.pal[u];
+        const float* __restrict__ src = rest + 3 * (size_t)g.first[u];
+        float* __restrict__ dst = vtx + 3 * (size_t)g.first[u];
+        const uint2* __restrict__ jv = joints + g.skin[u];
+        const float4* __restrict__ wv = weights + g.skin[u];
+        const size_t n = g.n[u];
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+            const uint2 j = jv[i];
+            const float4 w = wv[i];
+            const float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+            const float* __restrict__ j0 = pal + 12 * (j.x & 0xffffu);
+            const float* __restrict__ j1 = pal + 12 * (j.x >> 16);
+            const float* __restrict__ j2 = pal + 12 * (j.y & 0xffffu);
+            const float* __restrict__ j3 = pal + 12 * (j.y >> 16);
+            float m[12];
+#pragma unroll
+            for (int e = 0; e < 12; e++) m[e] = ((w.x * j0[e] + w.y * j1[e]) + w.z * j2[e]) + w.w * j3[e];
             dst[3 * i] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
             dst[3 * i + 1] = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
             dst[3 * i + 2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
@@ -204,6 +237,14 @@ void fovpt_launch_transform_vertices(hipStream_t st, const VertexTransform& g, c
     const uint64_t n = g.max_n;
     const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
     hipLaunchKernelGGL(k_transform_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, vtx);
+}
+
+void fovpt_launch_skin_vertices(hipStream_t st, const VertexSkin& g, const float* rest, const uint2* joints, const float4* weights, float* vtx)
+{
+    if (g.count <= 0 || g.max_n == 0) return;
+    const uint64_t n = g.max_n;
+    const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
+    hipLaunchKernelGGL(k_skin_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, joints, weights, vtx);
 }
 
 void fovpt_launch_tree_cost(hipStream_t st, const BvhNode4* nodes, uint32_t num_nodes, double* partial, TreeCostRecord* rec)

@@ -21,7 +21,7 @@ EXPORTS = [
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
     "fovpt_temporal_defaults", "fovpt_temporal", "fovpt_temporal_motion", "fovpt_temporal_buffers", "fovpt_temporal_reset", "fovpt_update_vertices",
-    "fovpt_update_transforms", "fovpt_hierarchy_cost",
+    "fovpt_update_transforms", "fovpt_hierarchy_cost", "fovpt_set_skins", "fovpt_update_skinned",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
     "fovpt_model_load_obj", "fovpt_model_load_gltf", "fovpt_model_destroy", "fovpt_model_counts", "fovpt_model_get_mesh", "fovpt_model_get_texture",
@@ -170,6 +170,8 @@ def load():
     L.fovpt_update_vertices.argtypes = [vp, C.POINTER(abi.VertexUpdate), i32, i32]
     L.fovpt_update_transforms.argtypes = [vp, C.POINTER(abi.MeshTransform), i32, i32]
     L.fovpt_hierarchy_cost.argtypes = [vp, i32, C.POINTER(abi.HierarchyCost)]
+    L.fovpt_set_skins.argtypes = [vp, C.POINTER(abi.MeshSkin), i32]
+    L.fovpt_update_skinned.argtypes = [vp, C.POINTER(abi.SkinPose), i32, i32]
     L.fovpt_comm_get_unique_id.argtypes = [vp]
     L.fovpt_comm_init.argtypes = [vp, vp, i32, i32]
     L.fovpt_comm_destroy.argtypes = [vp]

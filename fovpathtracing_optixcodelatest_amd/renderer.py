@@ -450,6 +450,69 @@ class SampleRenderer:
         self._check(self._L.fovpt_hierarchy_cost(self._ctx, abi.COST_WAIT if wait else 0, C.byref(out)))
         return out
 
+    # -- skinning (include/fovpt.h, fovpt_set_skins / fovpt_update_skinned)
+    def set_skins(self, skins):
+        """Sets, replaces or removes the skins of meshes: skins maps a mesh index to (joints (n, 4) uint16, weights (n, 4)
+        float32), n the mesh's vertex count, or to None (remove).  The skin's joint count is the largest index used plus one; a
+        third element, (joints, weights, num_joints), states it instead.  Weights are used as given, not normalised.  Set-up-time
+        state of the scene: copied before the call returns, geometry does not move.  Bad shapes raise ValueError."""
+        items = sorted(skins.items())
+        sk = (abi.MeshSkin * max(1, len(items)))()
+        keep = []
+        for k, (mesh, jw) in enumerate(items):
+            if not 0 <= int(mesh) < len(self.model.meshes):
+                raise ValueError("set_skins: mesh %d of %d" % (mesh, len(self.model.meshes)))
+            sk[k].mesh, sk[k].num_vertices = int(mesh), int(self.model.meshes[mesh].vertex.shape[0])
+            if jw is None:
+                continue
+            j, w = jw[0], jw[1]
+            j = np.asarray(j)
+            if j.ndim != 2 or j.shape[1] != 4 or j.dtype.kind not in "ui" or (j.size and (j.min() < 0 or j.max() > 0xffff)):
+                raise ValueError("set_skins: mesh %d needs (n, 4) joint indices that fit uint16" % mesh)
+            j, w = np.ascontiguousarray(j, np.uint16), np.ascontiguousarray(w, np.float32)
+            if w.shape != j.shape:
+                raise ValueError("set_skins: mesh %d needs (n, 4) weights, one per joint index" % mesh)
+            keep += [j, w]
+            sk[k].num_vertices, sk[k].num_joints = j.shape[0], (int(jw[2]) if len(jw) > 2 else int(j.max()) + 1 if j.size else 1)
+            sk[k].joints, sk[k].weights = j.ctypes.data, w.ctypes.data
+        self._check(self._L.fovpt_set_skins(self._ctx, sk, len(items)))
+
+    def update_skinned(self, poses, rebuild=False):
+        """Poses of skinned meshes: poses maps a mesh index to its palette, a (J, 3, 4) array or a (J, 4, 4) one whose last rows
+        are 0 0 0 1, or a contiguous float32 CUDA torch tensor (J, 3, 4) (read in stream order on the renderer's stream, not
+        validated), J the joint count of the mesh's skin.  All host or all device.  Every vertex's rest position goes through the
+        weighted sum of its four joints' matrices on the device; absolute, not cumulative; then update_vertices()' refit (or,
+        rebuild=True, rebuild) with the same ordering.  Bad shapes raise ValueError.  The renderer's Model is not changed."""
+        items = sorted(poses.items())
+        on_device = [hasattr(v, "is_cuda") and bool(v.is_cuda) for _, v in items]
+        if any(on_device) and not all(on_device):
+            raise ValueError("update_skinned: mixes host arrays and device tensors")
+        device = bool(items) and all(on_device)
+        ps = (abi.SkinPose * max(1, len(items)))()
+        keep = []
+        for k, (mesh, m) in enumerate(items):
+            if device:
+                import torch
+                if m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (3, 4) or not m.is_contiguous():
+                    raise ValueError("update_skinned: mesh %d needs a contiguous (J, 3, 4) float32 tensor" % mesh)
+                ptr = m.data_ptr()
+            else:
+                m = np.asarray(m, np.float32)
+                if m.ndim == 3 and m.shape[1:] == (4, 4):
+                    if not (m[:, 3] == np.float32([0, 0, 0, 1])).all():
+                        raise ValueError("update_skinned: mesh %d: the last row of a (4, 4) matrix must be 0 0 0 1" % mesh)
+                    m = m[:, :3]
+                if m.ndim != 3 or m.shape[1:] != (3, 4):
+                    raise ValueError("update_skinned: mesh %d needs a (J, 3, 4) or (J, 4, 4) array" % mesh)
+                m = np.ascontiguousarray(m)
+                ptr = m.ctypes.data
+            keep.append(m)
+            ps[k].mesh, ps[k].num_joints, ps[k].matrices = int(mesh), int(m.shape[0]), ptr
+        flags = (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)
+        self._check(self._L.fovpt_update_skinned(self._ctx, ps, len(items), flags))
+        if device:
+            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

@@ -228,6 +228,16 @@ public:
         check(fovpt_hierarchy_cost(ctx, wait ? FOVPT_COST_WAIT : 0, &info));
         return info;
     }
+    // skinning: setSkins uploads, replaces or removes (num_joints 0, null pointers) the skins of the listed meshes, once;
+    // updateSkinned sends their palettes (num_joints row-major 3 x 4 matrices each; device = true: device pointers, read in
+    // stream order) and blends them per vertex over the rest positions on the device, absolute not cumulative, then
+    // updateAccel()'s refit or rebuild (include/fovpt.h, fovpt_set_skins / fovpt_update_skinned).  The Model is not changed.
+    fovpt_ctx* context() const { return ctx; }       // the C ABI's context, for calls this class does not wrap (fovpt_debug_buffer)
+    void setSkins(const std::vector<fovpt_mesh_skin>& skins) { check(fovpt_set_skins(ctx, skins.data(), (int)skins.size())); }
+    void updateSkinned(const std::vector<fovpt_skin_pose>& poses, bool rebuild = false, bool device = false)
+    {
+        check(fovpt_update_skinned(ctx, poses.data(), (int)poses.size(), (rebuild ? FOVPT_UPDATE_REBUILD : 0) | (device ? FOVPT_UPDATE_DEVICE : 0)));
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

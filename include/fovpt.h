@@ -295,6 +295,64 @@ typedef struct fovpt_mesh_transform {
 } fovpt_mesh_transform;
 int fovpt_update_transforms(fovpt_ctx* ctx, const fovpt_mesh_transform* transforms, int num, int flags);
 
+/* ---- skinning: per-mesh joint palettes blended on the device -----------------------------------------------------------------
+ * fovpt_update_vertices for skinned meshes (linear-blend skinning, four influences): the skin is uploaded once per mesh with
+ * fovpt_set_skins, and every frame carries a palette of joint matrices, 48 bytes per joint instead of 12 bytes per vertex.
+ *   geometry   for a vertex of a named mesh with REST position (x, y, z) -- the one fovpt_set_scene received --, joints
+ *              j0 .. j3, weights w0 .. w3 and the palette J of row-major 3 x 4 matrices, each entry e = 0 .. 11 of the blended
+ *              matrix is
+ *                  M[e] = ((w0 * J[j0][e] + w1 * J[j1][e]) + w2 * J[j2][e]) + w3 * J[j3][e]
+ *              and
+ *                  x' = ((M[0] * x + M[1] * y) + M[2] * z) + M[3]        y', z': the same with rows 1 and 2
+ *              every * and + one unfused binary32 operation.  Weights are used as given, NOT normalised.  Poses are absolute:
+ *              P1 then P2 leaves P2 applied to rest, and a mesh fovpt_update_vertices or fovpt_update_transforms has moved is
+ *              set from rest again.  Meshes not named keep what they last had, through any of the three calls; a skinned mesh
+ *              may still be given to the other two.
+ *   contract   after the call every frame, G-buffer, debug trace, "scene_vertices" buffer and hierarchy byte is what
+ *              fovpt_update_vertices gives on the same context with those x', y', z' as host arrays.  Stream ordering, the
+ *              refit, fovpt_temporal_motion's tracking, fovpt_hierarchy_cost's counting and FOVPT_UPDATE_REBUILD are that call's
+ *              own.
+ *   set_skins  set-up-time state of the scene: each entry sets, replaces or (num_joints == 0, both pointers null) removes the
+ *              skin of its mesh; the skins of other meshes stay; fovpt_set_scene drops them all.  Everything is copied before
+ *              the call returns; it may synchronise fovpt_stream(); it does not move geometry.  Per mesh the library keeps S,
+ *              the largest w0 + w1 + w2 + w3 over the mesh's vertices (in binary64), for the overflow rule below.
+ *              All or nothing.  FOVPT_E_NO_SCENE: no scene.  FOVPT_E_INVALID: null ctx, null skins with num > 0, num < 0, a
+ *              mesh out of range or listed twice, num_vertices other than the mesh's, num_joints above FOVPT_SKIN_MAX_JOINTS,
+ *              one null pointer of the pair (or both with num_joints > 0), non-zero _reserved, a joint index >= num_joints
+ *              (also where its weight is 0), a weight that is NaN, infinite, negative or above 1.
+ *   poses      fovpt_update_skinned: matrices are host memory, copied before the call returns (through a pinned staging
+ *              buffer into a palette the context owns), or with FOVPT_UPDATE_DEVICE device memory read in place in stream
+ *              order on fovpt_stream() and not validated, as fovpt_update_vertices' device pointers are.
+ *              All or nothing, checked before anything changes.  FOVPT_E_NO_SCENE: no scene.  FOVPT_E_INVALID: null ctx, null
+ *              poses with num > 0, num < 0, a mesh out of range or listed twice, a mesh without a skin, num_joints other than
+ *              the skin's, a null matrices pointer, unknown flag bits, and for host matrices a non-finite entry or a matrix that
+ *              could overflow: with A the largest |coordinate| of the mesh's rest positions and S as above, a row with
+ *              S * ((|m0| + |m1| + |m2|) * A + |m3|) > 2^127 (in binary64), or an entry with S * |m| > 2^127.  With S = 1
+ *              the first is fovpt_update_transforms' rule: every partial sum of a blended row applied to a vertex is bounded
+ *              by that expression.  The second bounds the entries of M themselves, which the first does only when A >= 1.
+ *              Within both every intermediate value is finite.  num == 0 without FOVPT_UPDATE_REBUILD: FOVPT_OK, nothing
+ *              happens.
+ * Memory: 24 bytes per skinned vertex on the device (8 of joint indices, 16 of weights) and the same on the host, 48 bytes per
+ * joint of palette, and the device copy of the rest positions fovpt_update_transforms makes (12 bytes per vertex, one copy shared
+ * by both, made on the first call of either).  A context that never calls these functions pays nothing.                      */
+#define FOVPT_SKIN_MAX_JOINTS 1024
+typedef struct fovpt_mesh_skin {
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    uint32_t num_vertices;       /* must equal that mesh's num_vertices                                                     */
+    uint32_t num_joints;         /* 1 .. FOVPT_SKIN_MAX_JOINTS; 0 with joints == weights == NULL: remove                    */
+    uint32_t _reserved;          /* 0                                                                                       */
+    const uint16_t* joints;      /* 4 per vertex, host, every one < num_joints (also where its weight is 0)                 */
+    const float* weights;        /* 4 per vertex, host, each finite and 0 <= w <= 1; NOT normalised by the library          */
+} fovpt_mesh_skin;               /* 32 bytes */
+int fovpt_set_skins(fovpt_ctx* ctx, const fovpt_mesh_skin* skins, int num);
+
+typedef struct fovpt_skin_pose {
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    uint32_t num_joints;         /* must equal the mesh's skin's                                                            */
+    const float* matrices;       /* num_joints row-major 3 x 4 matrices, 12 floats each (host, or device with FOVPT_UPDATE_DEVICE) */
+} fovpt_skin_pose;               /* 16 bytes */
+int fovpt_update_skinned(fovpt_ctx* ctx, const fovpt_skin_pose* poses, int num, int flags);   /* FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD */
+
 /* ---- the cost of the hierarchy, measured on the device -----------------------------------------------------------------------
  * A refit keeps the tree's shape, so traversal slows as the motion grows (sections 13 and 16).  What to watch is
  * the SAH cost of the nodes, in binary64: with d = hi - lo of a live child entry and area = dx * dy + dy * dz + dz * dx,
@@ -736,6 +794,8 @@ static_assert(sizeof(fovpt_post_config) == 112 && offsetof(fovpt_post_config, de
 static_assert(sizeof(fovpt_vertex_update) == 16 && offsetof(fovpt_vertex_update, vertex) == 8, "vertex update ABI");
 static_assert(sizeof(fovpt_mesh_transform) == 52 && offsetof(fovpt_mesh_transform, m) == 4, "mesh transform ABI");
 static_assert(sizeof(fovpt_hierarchy_cost_info) == 32 && offsetof(fovpt_hierarchy_cost_info, updates) == 16, "hierarchy cost ABI");
+static_assert(sizeof(fovpt_mesh_skin) == 32 && offsetof(fovpt_mesh_skin, joints) == 16 && offsetof(fovpt_mesh_skin, weights) == 24, "mesh skin ABI");
+static_assert(sizeof(fovpt_skin_pose) == 16 && offsetof(fovpt_skin_pose, matrices) == 8, "skin pose ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

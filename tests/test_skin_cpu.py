@@ -1,0 +1,173 @@
+"""CPU tests of tests/skin_ref.py, the restatement fovpt_update_skinned is checked against on the GPU: the arithmetic against a
+scalar loop that rounds after every operation, one joint against transform_ref, the overflow rule on either side of 2^127; and
+of the ABI mirrors of fovpt_mesh_skin and fovpt_skin_pose."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import skin_ref as sk
+import transform_ref as tf
+from fovpathtracing_optixcodelatest_amd import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+def _scalar(rest, joints, weights, pal):
+    """One vertex and one operation at a time, every result rounded to binary32."""
+    P = np.asarray(pal, F).reshape(-1, 12)
+    out = np.empty((len(rest), 3), F)
+    with np.errstate(over="ignore", under="ignore"):
+        for i, (x, y, z) in enumerate(np.asarray(rest, F)):
+            j, w = [int(a) for a in joints[i]], [F(a) for a in weights[i]]
+            M = []
+            for e in range(12):
+                p = [F(w[k] * P[j[k], e]) for k in range(4)]
+                M.append(F(F(F(p[0] + p[1]) + p[2]) + p[3]))
+            for r in range(3):
+                a, b, c = F(M[4 * r] * x), F(M[4 * r + 1] * y), F(M[4 * r + 2] * z)
+                out[i, r] = F(F(F(a + b) + c) + M[4 * r + 3])
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+REST = (np.random.default_rng(5).standard_normal((37, 3)) * 300).astype(F)
+EDGE = np.array([[0.0, -0.0, 1e-30], [-0.0, 0.0, -1e-30], [1e30, -1e30, 1e-30], [1e-30, 1e30, -0.0], [1e30, 1e30, 1e30]], F)
+
+
+def _cases():
+    rng = np.random.default_rng(11)
+    out = {}
+    out["bend"] = (REST,) + sk.bend(REST, 5)[:2] + (sk.bend_pose(REST, 5, 40.0, (30.0, -4.0, 12.0)),)
+    out["random"] = (REST,) + sk.random_skin(rng, len(REST), 9)[:2] + (sk.random_pose(rng, REST, 9),)
+    # weights 0 and 1 in every slot, and rows that are not normalised (sums 0, 2.5 and 4)
+    w = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 1], [0, 0, 0, 0], [1, 1, 1, 1], [0.5, 1, 0.25, 0.75], [0.125, 0.25, 0, 0]], F)
+    w = np.tile(w, (6, 1))[:len(REST)]
+    out["zero_one_unnormalised"] = (REST, rng.integers(0, 4, (len(REST), 4)).astype(np.uint16), w, sk.random_pose(rng, REST, 4))
+    # +-0, 1e-30 and 1e30 coordinates: entries up to 1e6 and S = 2 keep S ((|m0| + |m1| + |m2|) 1e30 + |m3|) below 2^127 = 1.7e38;
+    # 1e-30 x 1e-9 is subnormal
+    pal = np.array([[[1e6, -3e5, 0.5, 1e37], [1e-9, 1e-9, -1e-9, -0.0], [-1.0, 1.0, 1e6, 1e-38]],
+                    [[-2e5, 1e6, -0.0, -1e36], [0.0, -1e-9, 1e-9, 0.0], [1.0, 1.0, -1e6, -1e-38]]], F)
+    je = np.array([[0, 1, 0, 0], [1, 0, 0, 1], [1, 1, 1, 1], [0, 0, 0, 0], [0, 1, 1, 0]], np.uint16)
+    we = np.array([[0.5, 0.5, 0, 0], [1, 0, 0, 1], [0.25, 0.25, 0.25, 0.25], [0, 0, 0, 0], [1, 0.5, 0.25, 0.25]], F)
+    out["edge"] = (EDGE, je, we, pal)
+    return out
+
+
+CASES = _cases()
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_apply_is_the_scalar_expression(name):
+    rest, j, w, pal = CASES[name]
+    assert sk.accepted(rest, w, pal)
+    got, want = sk.apply(rest, j, w, pal), _scalar(rest, j, w, pal)
+    assert np.isfinite(got).all()
+    assert np.array_equal(_bits(got), _bits(want))
+    if name == "zero_one_unnormalised":
+        assert sk.weight_sum(w) == 4.0 and (got[3::7] == 0).all()          # a row of zero weights sends its vertex to the origin
+    if name == "edge":
+        assert sk.weight_sum(w) == 2.0
+
+
+def test_one_joint_of_weight_one_is_the_transform():
+    """Weights (1, 0, 0, 0): M[e] = ((1 J[e] + 0 J[e]) + 0 J[e]) + 0 J[e] = J[e] for J[e] != 0.  Matrices with a zero entry are
+    excluded because of the sign of zero: J[e] = -0 gives -0 + +0 = +0, and +0 * x and -0 * x differ in sign, which can reach a
+    result that is itself zero."""
+    rest = np.concatenate([REST, EDGE[:2]])
+    m = sk.dense_matrix()
+    j, w = np.zeros((len(rest), 4), np.uint16), np.zeros((len(rest), 4), F)
+    w[:, 0] = 1
+    for pal, jj in ((m[None], j), (np.stack([tf.IDENTITY, m, tf.IDENTITY]), j + np.uint16([1, 0, 2, 0]))):
+        assert np.array_equal(_bits(sk.apply(rest, jj, w, pal)), _bits(tf.apply(rest, m)))
+    assert sk.bend(rest, 1)[2] == 1 and np.array_equal(sk.bend(rest, 1)[1], w)
+    assert sk.overflow_bound(rest, w, m[None]) == tf.overflow_bound(rest, m)     # S = 1: fovpt_update_transforms' rule
+
+
+def test_bend_is_the_stated_skin():
+    j, w, n = sk.bend(REST, 5)
+    assert n == 5 and j.dtype == np.uint16 and w.dtype == F and j.max() == 4
+    assert (w[:, 2:] == 0).all() and (j[:, 2:] == 0).all()
+    assert (w >= 0).all() and (w <= 1).all() and np.allclose(w.sum(axis=1), 1, atol=1e-6)
+    assert ((j[:, 1] == j[:, 0] + 1) | ((w[:, 1] == 0) & (j[:, 1] == 0))).all()
+    top = int(np.argmax(np.ptp(REST, axis=0)))
+    assert j[np.argmax(REST[:, top]), 1] == 4 and w[np.argmax(REST[:, top]), 1] == 1       # the last joint, with weight 1
+    assert j[np.argmin(REST[:, top]), 0] == 0 and w[np.argmin(REST[:, top]), 0] == 1
+
+
+def test_overflow_bound_on_either_side_of_two_to_the_127():
+    rest = np.array([[2.0 ** 100, 0, 0], [0, -(2.0 ** 99), 1.0]], F)      # A = 2^100
+    j = np.zeros((2, 4), np.uint16)
+    for s, shift in ((1.0, 0), (4.0, 2)):
+        w = np.zeros((2, 4), F)
+        w[0, :int(s)] = 1                                                 # S = 1 or 4, on one vertex
+        w[1, 0] = 0.5
+        assert sk.weight_sum(w) == s
+        pal = np.zeros((2, 3, 4), F)
+        pal[1, 0, 0] = F(2.0 ** (27 - shift))                             # S 2^(27 - shift) 2^100 = 2^127: not above
+        assert sk.overflow_bound(rest, w, pal) == 2.0 ** 127 and sk.accepted(rest, w, pal)
+        assert np.isfinite(sk.apply(rest, j, w, pal)).all() and np.isfinite(sk.apply(rest, j + np.uint16(1), w, pal)).all()
+        pal[1, 0, 0] = np.nextafter(F(2.0 ** (27 - shift)), F(np.inf))
+        assert sk.overflow_bound(rest, w, pal) > 2.0 ** 127 and not sk.accepted(rest, w, pal)
+        pal[1, 0, 0] = F(2.0 ** (26 - shift))
+        pal[1, 0, 1] = F(-(2.0 ** (26 - shift)))                          # the bound adds magnitudes: 2^127 again
+        assert sk.accepted(rest, w, pal)
+        pal[1, 0, 3] = F(2.0 ** 80)                                       # S (2^127 / S + 2^80), exact in binary64
+        assert not sk.accepted(rest, w, pal)
+        pal = np.tile(tf.IDENTITY, (2, 1, 1))
+        pal[0, 2, 3] = F(2.0 ** (127 - shift))                            # the translation alone reaches it: S (2^100 + 2^127 / S)
+        assert not sk.accepted(rest, w, pal)
+        assert sk.accepted(np.zeros((0, 3), F), np.zeros((0, 4), F), pal)  # no vertices: A = S = 0
+        # a mesh inside the unit cube (A < 1): the entries of the blended matrix are bounded on their own
+        small = np.array([[2.0 ** -40, 0, 0]], F)
+        pal = np.zeros((1, 3, 4), F)
+        pal[0, 1, 2] = F(2.0 ** (127 - shift))
+        assert sk.overflow_bound(small, w[:1], pal) < 2.0 ** 90 and sk.entry_bound(w[:1], pal) == 2.0 ** 127 and sk.accepted(small, w[:1], pal)
+        assert np.isfinite(sk.apply(small, j[:1], w[:1], pal)).all()
+        pal[0, 1, 2] = np.nextafter(pal[0, 1, 2], F(np.inf))
+        assert not sk.accepted(small, w[:1], pal)
+        for bad in (np.nan, np.inf, -np.inf):
+            pal = np.tile(tf.IDENTITY, (2, 1, 1))
+            pal[1, 1, 2] = bad
+            assert not sk.accepted(rest, w, pal)
+    # S = 4 and A < 1 is where the row's bound alone would let the blended matrix overflow
+    w4, small = np.ones((1, 4), F), np.array([[2.0 ** -40, 0, 0]], F)
+    pal = np.zeros((1, 3, 4), F)
+    pal[0, 0, 0] = F(2.0 ** 127)
+    assert sk.overflow_bound(small, w4, pal) < 2.0 ** 127 and not sk.accepted(small, w4, pal)
+    assert not np.isfinite(sk.apply(small, j[:1], w4, pal)).all()
+    # within the bounds nothing overflows, whatever the signs, the weights and the joints
+    rng = np.random.default_rng(9)
+    n_accepted = 0
+    for k in range(50):
+        nj = int(rng.integers(1, 6))
+        pal = (rng.choice([-1.0, 1.0], (nj, 3, 4)) * 2.0 ** rng.uniform(15, 24.8, (nj, 3, 4))).astype(F)
+        r = (rng.choice([-1.0, 1.0], (64, 3)) * 2.0 ** rng.uniform(90, 100, (64, 3))).astype(F)
+        jj, ww, _ = sk.random_skin(rng, 64, nj)
+        if k % 2:
+            ww[:] = 1                                                     # S = 4
+        if sk.accepted(r, ww, pal):
+            n_accepted += 1
+            assert np.isfinite(sk.apply(r, jj, ww, pal)).all()
+    assert 10 < n_accepted < 50
+
+
+def test_abi_mirrors_match_the_header(tmp_path):
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d", '
+           'sizeof(fovpt_mesh_skin), offsetof(fovpt_mesh_skin, mesh), offsetof(fovpt_mesh_skin, num_vertices), offsetof(fovpt_mesh_skin, num_joints), '
+           'offsetof(fovpt_mesh_skin, _reserved), offsetof(fovpt_mesh_skin, joints), offsetof(fovpt_mesh_skin, weights), '
+           'sizeof(fovpt_skin_pose), offsetof(fovpt_skin_pose, mesh), offsetof(fovpt_skin_pose, num_joints), offsetof(fovpt_skin_pose, matrices), '
+           'FOVPT_SKIN_MAX_JOINTS); return 0;}\n')
+    exe = str(tmp_path / "skin_layout")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    S, P = abi.MeshSkin, abi.SkinPose
+    assert got == [ctypes.sizeof(S), S.mesh.offset, S.num_vertices.offset, S.num_joints.offset, S._reserved.offset, S.joints.offset,
+                   S.weights.offset, ctypes.sizeof(P), P.mesh.offset, P.num_joints.offset, P.matrices.offset, abi.SKIN_MAX_JOINTS]
+    assert got[0] == 32 and got[7] == 16 and got[-1] == 1024 == sk.MAX_JOINTS

@@ -11,7 +11,12 @@ scene.  Kernel statistics are a separate run:
 update_transforms and update_vertices with device pointers in turn (ms per call, device time), first while nobody watches the
 cost and then, after the context's first hierarchy_cost(), with a measurement behind every refit: what a measurement costs is
 the difference (its kernels' own times: the kernel-trace run above with --transforms).  Then the quality experiment with the
-device's current / built ratio polled after every frame's refit, beside the frame times."""
+device's current / built ratio polled after every frame's refit, beside the frame times.
+
+--skin: fovpt_update_skinned instead.  Every mesh gets a procedural skin of 2 .. 64 joints (skin_ref.bend) and one pose; on one
+context, --rounds rounds of three updates to the same positions in turn: update_skinned with host matrices, update_vertices with
+device pointers to the positions skinned beforehand, update_vertices with the same positions as host arrays (ms per call, device
+time on the library's stream; the median over the rounds and every round)."""
 import argparse
 import ctypes as C
 import json
@@ -202,6 +207,44 @@ def run_transforms(name, calls, warmup, frames, rounds):
     print(json.dumps(out), flush=True)
 
 
+def run_skin(name, calls, warmup, rounds):
+    import skin_ref as sk
+    model, r = make_renderer(name)
+    st0 = r.stats()
+    skins = {k: sk.bend(m.vertex, 2 + (7 * k) % 63) for k, m in enumerate(model.meshes)}
+    poses = {k: sk.bend_pose(m.vertex, skins[k][2], 12.0, (0.0, 0.02 * (k % 5), 0.0)) for k, m in enumerate(model.meshes)}
+    t = time.perf_counter()
+    r.set_skins(skins)
+    set_skins_ms = (time.perf_counter() - t) * 1e3
+    host = sk.restate(model, skins, poses)
+    dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+    torch.cuda.synchronize()
+    out = dict(scene=name, triangles=model.num_triangles, meshes=len(model.meshes), bvh_nodes=int(st0.num_bvh_nodes),
+               vertices=int(sum(m.vertex.shape[0] for m in model.meshes)), joints=int(sum(s[2] for s in skins.values())),
+               rounds=rounds, calls=calls, set_skins_host_ms=round(set_skins_ms, 3))
+    ms = dict(update_skinned=[], update_vertices_device=[], update_vertices_host=[])
+    host_ms = dict(update_skinned=[], update_vertices_device=[], update_vertices_host=[])
+    fns = dict(update_skinned=lambda: r.update_skinned(poses), update_vertices_device=lambda: r.update_vertices(dev),
+               update_vertices_host=lambda: r.update_vertices(host))
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            d, h = device_ms(r, fn, calls, warmup)
+            ms[k].append(d)
+            host_ms[k].append(h)
+    for k in fns:
+        out[k + "_ms"] = round(float(np.median(ms[k])), 4)
+        out[k + "_ms_rounds"] = [round(x, 4) for x in ms[k]]
+        out[k + "_host_ms"] = round(float(np.median(host_ms[k])), 4)
+    # the three leave the same positions behind
+    p, n = C.c_void_p(), C.c_size_t()
+    r._check(r._L.fovpt_debug_buffer(r._ctx, b"scene_vertices", C.byref(p), C.byref(n)))
+    r.update_skinned(poses)
+    got = r.download(p.value, np.empty(n.value // 4, np.uint32))
+    out["positions_match_restatement"] = bool(np.array_equal(got, np.concatenate([host[k] for k in range(len(model.meshes))]).view(np.uint32).reshape(-1)))
+    r.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c3,street")
@@ -209,10 +252,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--transforms", action="store_true", help="fovpt_update_transforms and fovpt_hierarchy_cost instead of fovpt_update_vertices")
-    ap.add_argument("--rounds", type=int, default=5, help="--transforms: rounds of the alternated timings (at least 5)")
+    ap.add_argument("--skin", action="store_true", help="fovpt_update_skinned against fovpt_update_vertices with device pointers and with host arrays")
+    ap.add_argument("--rounds", type=int, default=5, help="--transforms, --skin: rounds of the alternated timings (at least 5)")
     a = ap.parse_args()
     for s in a.scenes.split(","):
-        if a.transforms:
+        if a.skin:
+            run_skin(s, a.calls, a.warmup, max(5, a.rounds))
+        elif a.transforms:
             run_transforms(s, a.calls, a.warmup, a.frames, max(5, a.rounds))
         else:
             run(s, a.calls, a.warmup, a.frames)
