@@ -291,6 +291,43 @@ class PostConfig(C.Structure):
         return m
 
 
+EXPOSE_FIXED, EXPOSE_AUTO = 0, 1               # FOVPT_EXPOSE_*
+METER_FRAME, METER_GAZE = 0, 1                 # FOVPT_METER_*
+TONE_REINHARD, TONE_ACES = 0, 1                # FOVPT_TONE_*
+EXPOSE_BINS = 256                              # FOVPT_EXPOSE_BINS
+
+
+class ExposeConfig(C.Structure):
+    """fovpt_expose_config: mode, metering, tone map, the meter's weights per foveation level and its trimmed mean, the key and
+    the adaptation rates (defaults: fovpt_expose_defaults)."""
+    _fields_ = [
+        ("mode", C.c_int32), ("metering", C.c_int32), ("tone", C.c_int32), ("_reserved0", C.c_int32),
+        ("weight_fovea", C.c_int32), ("weight_middle", C.c_int32), ("weight_periphery", C.c_int32), ("weight_uniform", C.c_int32),
+        ("low_permille", C.c_int32), ("high_permille", C.c_int32),
+        ("ev_min", C.c_float), ("ev_max", C.c_float),
+        ("key", C.c_float), ("exposure", C.c_float), ("white", C.c_float),
+        ("adapt_brighter", C.c_float), ("adapt_darker", C.c_float),
+        ("_reserved", C.c_int32 * 3),
+    ]
+
+    def copy(self):
+        m = ExposeConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(ExposeConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class ExposeState(C.Structure):
+    """struct fovpt_expose_state: the metered and the adapted log2 luminance, the exposure, the last meter's total weight and the
+    AUTO steps since create / reset."""
+    _fields_ = [
+        ("ev_metered", C.c_float), ("ev", C.c_float), ("exposure", C.c_float), ("_pad", C.c_float),
+        ("weight_total", C.c_uint64), ("steps", C.c_uint64),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
@@ -316,6 +353,8 @@ assert C.sizeof(DenoiseConfig) == 32
 assert C.sizeof(ReconstructConfig) == 32 and C.sizeof(GBufferPtrs) == 40
 assert C.sizeof(TemporalConfig) == 32
 assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.reconstruct.offset, PostConfig.temporal.offset) == (16, 48, 80)
+assert C.sizeof(ExposeConfig) == 80 and (ExposeConfig.low_permille.offset, ExposeConfig.key.offset) == (32, 48)
+assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4
 assert C.sizeof(HierarchyCost) == 32 and HierarchyCost.updates.offset == 16

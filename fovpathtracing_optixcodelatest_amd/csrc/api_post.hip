@@ -1,5 +1,6 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
-// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), and their defaults.
+// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), and
+// their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -231,6 +232,34 @@ int temporal_enqueue(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_te
     return FOVPT_OK;
 }
 
+// fovpt_expose's validation (nothing allocated, enqueued or changed).  in: its colour input
+int expose_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_expose_config* ec, const fovpt_float4* in, const char* who)
+{
+    if (ec->mode != FOVPT_EXPOSE_FIXED && ec->mode != FOVPT_EXPOSE_AUTO) return fail(c, FOVPT_E_INVALID, "%s: unknown mode %d", who, ec->mode);
+    if (ec->metering != FOVPT_METER_FRAME && ec->metering != FOVPT_METER_GAZE) return fail(c, FOVPT_E_INVALID, "%s: unknown metering %d", who, ec->metering);
+    if (ec->tone != FOVPT_TONE_REINHARD && ec->tone != FOVPT_TONE_ACES) return fail(c, FOVPT_E_INVALID, "%s: unknown tone map %d", who, ec->tone);
+    const int32_t wts[4] = {ec->weight_fovea, ec->weight_middle, ec->weight_periphery, ec->weight_uniform};
+    for (int32_t v : wts)
+        if (v < 0 || v > 255) return fail(c, FOVPT_E_INVALID, "%s: weight %d outside 0 .. 255", who, v);
+    if (!(0 <= ec->low_permille && ec->low_permille < ec->high_permille && ec->high_permille <= 1000))
+        return fail(c, FOVPT_E_INVALID, "%s: permille %d .. %d is not 0 <= low < high <= 1000", who, ec->low_permille, ec->high_permille);
+    if (!(ec->ev_min >= -16.0f && ec->ev_min <= ec->ev_max && ec->ev_max <= 16.0f))
+        return fail(c, FOVPT_E_INVALID, "%s: ev range %g .. %g is not -16 <= ev_min <= ev_max <= 16", who, (double)ec->ev_min, (double)ec->ev_max);
+    const float pos[3] = {ec->key, ec->exposure, ec->white};
+    for (float v : pos)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "%s: key, exposure or white %g outside [%g, %g]", who, (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    const float rates[2] = {ec->adapt_brighter, ec->adapt_darker};
+    for (float v : rates)
+        if (!(v > 0.0f && v <= 1.0f)) return fail(c, FOVPT_E_INVALID, "%s: adapt rate %g outside (0, 1]", who, (double)v);
+    if (ec->_reserved0 != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    for (int32_t r : ec->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    { const int rc_ = check_rendered_frame(c, lp, who, "meter", nullptr); if (rc_) return rc_; }
+    if ((size_t)c->dn_w * (size_t)c->dn_h >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+    return FOVPT_OK;
+}
+
 // fovpt_temporal (motion false) and fovpt_temporal_motion (motion true)
 int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_temporal_config* tc, const fovpt_float4* in_color,
                   fovpt_float4* out_color, uint32_t* out_rgba, fovpt_float4* out_motion, bool motion, const char* who)
@@ -247,6 +276,24 @@ int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_tempo
 }
 
 }  // namespace
+
+// fovpt_expose's state record, made (zeroed) on first use
+static int reserve_expose_state(fovpt_ctx* c)
+{
+    if (c->ex_state.p) return FOVPT_OK;
+    HIPCHK(c, c->ex_state.reserve(sizeof(ExposeState)));
+    HIPCHK(c, hipMemset(c->ex_state.p, 0, sizeof(ExposeState)));
+    return FOVPT_OK;
+}
+
+// steps = 0: the next AUTO step is a first step (no record yet: it will be made that way)
+int expose_reset(fovpt_ctx* c, hipStream_t st)
+{
+    if (!c->ex_state.p) return FOVPT_OK;
+    if (st) HIPCHK(c, hipMemsetAsync(c->ex_state.p, 0, sizeof(ExposeState), st));
+    else HIPCHK(c, hipMemset(c->ex_state.p, 0, sizeof(ExposeState)));
+    return FOVPT_OK;
+}
 
 // the G-buffer's buffers for n pixels (the counters once: k_gbuffer_rays rewrites the queue sizes it uses on every call)
 int reserve_gbuffer(fovpt_ctx* c, size_t n)
@@ -541,6 +588,89 @@ int fovpt_post(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_post_con
         if (R) ra = reconstruct_args(&pc->reconstruct);
         return temporal_enqueue(c, lp, &pc->temporal, in, out_color, out_rgba, out_motion, M, who, R ? &ra : nullptr);
     }
+    return FOVPT_OK;
+}
+
+// ---- gaze-metered auto-exposure and tone map (expose.hip; its definition: tests/expose_ref.py) ---------------------------
+// (conventions, not measurements: include/fovpt.h)
+int fovpt_expose_defaults(fovpt_expose_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->mode = FOVPT_EXPOSE_AUTO;
+    out->metering = FOVPT_METER_GAZE;
+    out->tone = FOVPT_TONE_REINHARD;
+    out->weight_fovea = 64; out->weight_middle = 8; out->weight_periphery = 1; out->weight_uniform = 1;
+    out->low_permille = 100; out->high_permille = 950;
+    out->ev_min = -12.0f; out->ev_max = 12.0f;
+    out->key = 0.18f;
+    out->exposure = 16.0f;
+    out->white = FOVPT_SIGMA_MAX;
+    out->adapt_brighter = 1.0f; out->adapt_darker = 1.0f;
+    return FOVPT_OK;
+}
+
+int fovpt_expose_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_expose_buffers", c->ex_color, c->ex_rgba, *color, *rgba);
+}
+
+int fovpt_expose_state(fovpt_ctx* c, struct fovpt_expose_state* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "fovpt_expose_state: null argument");
+    memset(out, 0, sizeof(*out));
+    if (!c->ex_state.p) return FOVPT_OK;                                   // no step yet
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));
+    HIPCHK(c, hipMemcpy(out, c->ex_state.p, sizeof(*out), hipMemcpyDeviceToHost));
+    return FOVPT_OK;
+}
+
+int fovpt_expose_reset(fovpt_ctx* c)
+{
+    if (!c) return FOVPT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    return expose_reset(c, c->shadow_stream);
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  AUTO: k_expose_meter, k_expose_adapt, k_expose_apply; the
+// exposure goes from the second to the third through the state record, never through the host.  FIXED: k_expose_apply alone.
+int fovpt_expose(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_expose_config* ec, const fovpt_float4* in_color, fovpt_float4* out_color,
+                 uint32_t* out_rgba)
+{
+    const char* who = "fovpt_expose";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !ec) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    { const int rc_ = expose_check(c, lp, ec, in, who); if (rc_) return rc_; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = own_outputs(c, who, c->ex_color, c->ex_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    const bool aut = ec->mode == FOVPT_EXPOSE_AUTO;
+    const uint32_t nrows = fovpt_expose_rows(npix);
+    if (aut) {
+        { const int rc_ = reserve_expose_state(c); if (rc_) return rc_; }
+        HIPCHK(c, c->ex_rows.reserve((size_t)nrows * FOVPT_EXPOSE_BINS * sizeof(uint32_t)));
+        HIPCHK(c, c->ex_hist.reserve(FOVPT_EXPOSE_BINS * sizeof(uint64_t)));
+    }
+    ExposeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.weight[0] = ec->weight_fovea; a.weight[1] = ec->weight_middle; a.weight[2] = ec->weight_periphery; a.weight[3] = ec->weight_uniform;
+    a.uniform = c->dn_uniform != 0;
+    a.low = ec->low_permille; a.high = ec->high_permille;
+    a.ev_min = ec->ev_min; a.ev_max = ec->ev_max; a.key = ec->key;
+    a.adapt_brighter = ec->adapt_brighter; a.adapt_darker = ec->adapt_darker;
+    a.tone = ec->tone; a.white = ec->white; a.exposure = ec->exposure;
+    const hipStream_t st = c->shadow_stream;
+    if (aut) {
+        fovpt_launch_expose_meter(st, c->dn_frame, a, ec->metering == FOVPT_METER_GAZE, in, (uint32_t*)c->ex_rows.p);
+        fovpt_launch_expose_adapt(st, a, (const uint32_t*)c->ex_rows.p, nrows, (uint64_t*)c->ex_hist.p, (ExposeState*)c->ex_state.p);
+    }
+    fovpt_launch_expose_apply(st, npix, a, aut ? (const ExposeState*)c->ex_state.p : nullptr, in, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }
 

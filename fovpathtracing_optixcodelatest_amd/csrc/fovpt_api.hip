@@ -983,6 +983,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     c->refit_pending = false;
     c->tm_tracking = c->tm_untracked = false;        // fovpt_temporal_motion's tracking: switched on again by its next call
     c->tm_mark.release(); c->vtx_prev.release();
+    { const int rc_ = expose_reset(c, nullptr); if (rc_) return rc_; }   // fovpt_expose adapts to another scene from scratch
     c->rest_vtx.release(); c->mesh_absmax.clear();   // fovpt_update_transforms' rest positions: made again on the scene's first call
     take_costs(c);                                   // fovpt_hierarchy_cost: (the device is idle) no measurement of the old scene stays in flight
     c->cost_updates = c->cost_measured = 0;
@@ -1349,6 +1350,7 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->rc_color.p) { HIPCHK(c, c->rc_color.reserve(n * 16)); HIPCHK(c, c->rc_rgba.reserve(n * 4)); }   // and fovpt_reconstruct's
     if (c->tp_hist[0].p) { const int rc_ = reserve_temporal(c, n); if (rc_) return rc_; }               // and fovpt_temporal's
     if (c->po_color.p) { HIPCHK(c, c->po_color.reserve(n * 16)); HIPCHK(c, c->po_rgba.reserve(n * 4)); }   // and fovpt_post's
+    if (c->ex_color.p) { HIPCHK(c, c->ex_color.reserve(n * 16)); HIPCHK(c, c->ex_rgba.reserve(n * 4)); }   // and fovpt_expose's (its state stays)
     c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
@@ -1520,6 +1522,8 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "scene_vertices") == 0 && c->up_vtx.p) { *ptr = c->up_vtx.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_update_vertices
     if (strcmp(name, "scene_vertices_prev") == 0 && c->vtx_prev.p) { *ptr = c->vtx_prev.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_temporal_motion
     if (strcmp(name, "post_color") == 0 && c->po_color.p) { *ptr = c->po_color.p; *bytes = c->po_color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
+    if (strcmp(name, "expose_histogram") == 0 && c->ex_hist.p) { *ptr = c->ex_hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
+    if (strcmp(name, "expose_state") == 0 && c->ex_state.p) { *ptr = c->ex_state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
     if (strcmp(name, "gbuffer_hit") == 0 && c->gb_hit.p) { *ptr = c->gb_hit.p; *bytes = c->gb_pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {

@@ -159,6 +159,10 @@ struct fovpt_ctx {
     // fovpt_post: the context's own outputs of the chain's last stage, allocated on first use (everything else the chain uses
     // is the stages' own: the denoiser's buffers, the temporal step's sets, histories and state)
     DevBuf po_color, po_rgba;
+    // fovpt_expose: the device state record (a struct fovpt_expose_state, zeroed when made and by a reset: steps 0 = the next
+    // AUTO step is a first step; the host never reads it outside fovpt_expose_state), the meter's per-block histogram rows and
+    // the histogram of the last metered step, and the context's own outputs; all allocated on first use
+    DevBuf ex_state, ex_rows, ex_hist, ex_color, ex_rgba;
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -192,5 +196,6 @@ void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameD
 // api_post.hip (fovpt_resize keeps the buffers of the post-processing calls at the frame's size)
 int reserve_gbuffer(fovpt_ctx* c, size_t n);
 int reserve_temporal(fovpt_ctx* c, size_t n);
+int expose_reset(fovpt_ctx* c, hipStream_t st);      // (st null: the device is idle, reset now)
 int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
                     const GBufferDev* target = nullptr);

@@ -285,6 +285,27 @@ void fovpt_launch_temporal_motion(hipStream_t st, const FrameDev& fd, const Temp
 void fovpt_launch_reconstruct_temporal(hipStream_t st, const FrameDev& fd, const ReconstructArgs& ra, const TemporalArgs& ta,
                                        const TemporalMotionArgs* m, const fovpt_float4* in, const fovpt_float4* albedo, GBufferDev g,
                                        GBufferDev gp, const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_expose (expose.hip): the meter (AUTO: k_expose_meter into `rows`, one row of FOVPT_EXPOSE_BINS counts per block of
+// fovpt_expose_rows(pixels); k_expose_adapt from them into the histogram and the state record), then the tone map (state null:
+// at a.exposure).  ExposeState: the struct shares its name with the entry point, which hides it in C++.
+typedef struct fovpt_expose_state ExposeState;
+#define FOVPT_EXPOSE_BLOCK 1024          // threads per block of the meter and of k_expose_adapt
+#ifndef FOVPT_EXPOSE_MAX_ROWS
+#define FOVPT_EXPOSE_MAX_ROWS 512       // blocks of the meter: 2 per CU, every wave slot once; every row goes through the one block of k_expose_adapt
+#endif
+struct ExposeArgs {
+    int32_t weight[4];                  // METER_GAZE: fill 1, fill 2, fill 4, FOV_OFF
+    int32_t uniform;                    // the frame was rendered FOV_OFF
+    int32_t low, high;                  // permille ranks of the trimmed mean
+    float ev_min, ev_max, key, adapt_brighter, adapt_darker;
+    int32_t tone;                       // FOVPT_TONE_*
+    float white, exposure;              // REINHARD's white; FIXED's exposure
+};
+uint32_t fovpt_expose_rows(size_t npix);
+void fovpt_launch_expose_meter(hipStream_t st, const FrameDev& fd, const ExposeArgs& a, bool gaze, const fovpt_float4* in, uint32_t* rows);
+void fovpt_launch_expose_adapt(hipStream_t st, const ExposeArgs& a, const uint32_t* rows, uint32_t nrows, uint64_t* hist, ExposeState* state);
+void fovpt_launch_expose_apply(hipStream_t st, size_t npix, const ExposeArgs& a, const ExposeState* state, const fovpt_float4* in,
+                               fovpt_float4* out_color, uint32_t* out_rgba);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32

@@ -23,6 +23,7 @@ EXPORTS = [
     "fovpt_temporal_defaults", "fovpt_temporal", "fovpt_temporal_motion", "fovpt_temporal_buffers", "fovpt_temporal_reset", "fovpt_update_vertices",
     "fovpt_update_transforms", "fovpt_hierarchy_cost", "fovpt_set_skins", "fovpt_update_skinned",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
+    "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
     "fovpt_model_load_obj", "fovpt_model_load_gltf", "fovpt_model_destroy", "fovpt_model_counts", "fovpt_model_get_mesh", "fovpt_model_get_texture",
     "fovpt_image_load_float4", "fovpt_image_free", "fovpt_image_load_rgba8", "fovpt_image_free_rgba8",
@@ -167,6 +168,11 @@ def load():
     L.fovpt_post_defaults.argtypes = [C.POINTER(abi.PostConfig)]
     L.fovpt_post.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.PostConfig), vp, vp, vp, vp]
     L.fovpt_post_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_expose_defaults.argtypes = [C.POINTER(abi.ExposeConfig)]
+    L.fovpt_expose.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.ExposeConfig), vp, vp, vp]
+    L.fovpt_expose_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_expose_state.argtypes = [vp, C.POINTER(abi.ExposeState)]
+    L.fovpt_expose_reset.argtypes = [vp]
     L.fovpt_update_vertices.argtypes = [vp, C.POINTER(abi.VertexUpdate), i32, i32]
     L.fovpt_update_transforms.argtypes = [vp, C.POINTER(abi.MeshTransform), i32, i32]
     L.fovpt_hierarchy_cost.argtypes = [vp, i32, C.POINTER(abi.HierarchyCost)]

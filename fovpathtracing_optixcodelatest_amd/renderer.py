@@ -390,6 +390,47 @@ class SampleRenderer:
         """The float4 output of the last post() into the renderer's own buffer."""
         return self._download_frame(self.post_buffers()[0], 4)
 
+    # -- gaze-metered auto-exposure and tone map (include/fovpt.h, fovpt_expose)
+    @staticmethod
+    def expose_defaults() -> abi.ExposeConfig:
+        d = abi.ExposeConfig()
+        lib.check(None, lib.load().fovpt_expose_defaults(C.byref(d)))
+        return d
+
+    def expose(self, cfg=None, in_color=None, out_color=None, out_rgba=None):
+        """Meters the frame last rendered (weighted by what the eye looks at with abi.METER_GAZE), moves the renderer's exposure
+        towards it and tone-maps the frame at that exposure, all on the device; cfg.mode = abi.EXPOSE_FIXED tone-maps at
+        cfg.exposure and leaves the state alone.  in_color: device pointer of a float4 frame (None: the accum buffer; typically
+        post_buffers()[0]).  out_color / out_rgba: device pointers (out_color may be in_color), or None for the renderer's own
+        buffers (downloadExposedColor / downloadExposedPixels).  Enqueued on the renderer's stream, not synchronised (the
+        downloads and expose_state() synchronise)."""
+        cfg = cfg if cfg is not None else self.expose_defaults()
+        self._check(self._L.fovpt_expose(self._ctx, C.byref(self.launchParams), C.byref(cfg), in_color, out_color, out_rgba))
+
+    def expose_buffers(self):
+        """Device addresses of the renderer's own exposed outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_expose_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def expose_state(self) -> abi.ExposeState:
+        """The exposure state after everything enqueued so far (synchronises the renderer's stream)."""
+        s = abi.ExposeState()
+        self._check(self._L.fovpt_expose_state(self._ctx, C.byref(s)))
+        return s
+
+    def expose_reset(self):
+        """The next AUTO expose() is a first step: its exposure is the metered one."""
+        self._check(self._L.fovpt_expose_reset(self._ctx))
+
+    def downloadExposedPixels(self):
+        """The rgba8 output of the last expose() into the renderer's own buffer, shaped like downloadPixels()."""
+        return self._download_frame(self.expose_buffers()[1], 1)
+
+    def downloadExposedColor(self):
+        """The float4 output of the last expose() into the renderer's own buffer."""
+        return self._download_frame(self.expose_buffers()[0], 4)
+
     # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
     def update_vertices(self, updates, rebuild=False):
         """New vertex positions for meshes of the scene: updates maps a mesh index to an (n, 3) float32 numpy array, or to a

@@ -196,6 +196,43 @@ public:
         check(fovpt_post_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- gaze-metered auto-exposure and tone map (include/fovpt.h, fovpt_expose): meters in_color (null: the accum buffer; by
+    // default weighted by what the eye looks at), moves the renderer's exposure towards it and tone-maps the frame at that exposure
+    // into the renderer's own exposed buffers, then a device sync like render().  Typically behind post(): exposePost()
+    void expose()
+    {
+        fovpt_expose_config ec;
+        check(fovpt_expose_defaults(&ec));
+        expose(ec);
+    }
+    void expose(const fovpt_expose_config& ec, const fovpt_float4* in_color = nullptr)
+    {
+        check(fovpt_expose(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &ec, in_color, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // expose() of the colour the last post() left in the renderer's own post buffers
+    void exposePost(const fovpt_expose_config& ec)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_post_buffers(ctx, &color, &rgba));
+        expose(ec, color);
+    }
+    struct fovpt_expose_state exposeState()
+    {
+        struct fovpt_expose_state s;
+        check(fovpt_expose_state(ctx, &s));
+        return s;
+    }
+    void exposeReset() { check(fovpt_expose_reset(ctx)); }
+    // the exposed rgba8 pixels, like downloadPixels
+    void downloadExposedPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_expose_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
     // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
     // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true
