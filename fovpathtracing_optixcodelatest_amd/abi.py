@@ -172,6 +172,27 @@ class SkinPose(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("num_joints", C.c_uint32), ("matrices", C.c_void_p)]
 
 
+MORPH_MAX_TARGETS = 256                         # FOVPT_MORPH_MAX_TARGETS
+
+
+class MorphTarget(C.Structure):
+    """fovpt_morph_target: the vertices one target moves and their deltas; index null: dense, entry i is vertex i."""
+    _fields_ = [("count", C.c_uint32), ("_reserved", C.c_uint32), ("index", C.c_void_p), ("delta", C.c_void_p)]
+
+
+class MeshMorph(C.Structure):
+    """fovpt_mesh_morph: the morph targets of one mesh (fovpt_set_morphs); num_targets 0 and a null pointer remove them."""
+    _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("num_targets", C.c_uint32), ("_reserved", C.c_uint32),
+                ("targets", C.POINTER(MorphTarget))]
+
+
+class MorphPose(C.Structure):
+    """fovpt_morph_pose: one weight per target of a morphed mesh and, with num_joints > 0, its skin's palette
+    (fovpt_update_morphed)."""
+    _fields_ = [("mesh", C.c_int32), ("num_targets", C.c_uint32), ("weights", C.c_void_p), ("num_joints", C.c_uint32),
+                ("_reserved", C.c_uint32), ("matrices", C.c_void_p)]
+
+
 class TextureDesc(C.Structure):
     _fields_ = [("pixel", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -360,6 +381,9 @@ assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4
 assert C.sizeof(HierarchyCost) == 32 and HierarchyCost.updates.offset == 16
 assert C.sizeof(MeshSkin) == 32 and (MeshSkin.joints.offset, MeshSkin.weights.offset) == (16, 24)
 assert C.sizeof(SkinPose) == 16 and SkinPose.matrices.offset == 8
+assert C.sizeof(MorphTarget) == 24 and (MorphTarget.index.offset, MorphTarget.delta.offset) == (8, 16)
+assert C.sizeof(MeshMorph) == 24 and MeshMorph.targets.offset == 16
+assert C.sizeof(MorphPose) == 32 and (MorphPose.weights.offset, MorphPose.num_joints.offset, MorphPose.matrices.offset) == (8, 16, 24)
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232
 assert _Frame.c.offset == 72 and _Frame.offset.offset == 88 and _Frame.size.offset == 40

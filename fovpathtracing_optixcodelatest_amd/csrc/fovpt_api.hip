@@ -145,6 +145,8 @@ void free_scene(fovpt_ctx* c)
     c->has_scene = false;
     c->skins.clear();                               // fovpt_set_skins: the skins are the scene's
     c->skin_joints.release(); c->skin_weights.release(); c->skin_pal.release();
+    c->morphs.clear();                              // fovpt_set_morphs: and so are the morph targets
+    c->morph_off.release(); c->morph_ent.release(); c->morph_w.release();
 }
 
 // A queue shard receives the appends of the blocks whose index is congruent to it modulo FOVPT_SHARDS.  The
@@ -658,7 +660,9 @@ int check_updatable(fovpt_ctx* c, const char* who)
 // Where the new positions of update_scene come from: `up` (host arrays through a staging buffer, `floats` of them in all, or
 // device arrays by a gather kernel), `tf` (the rest positions through per-mesh matrices) or `sk` (the rest positions through
 // per-vertex blends of per-mesh joint palettes: host palettes through the staging buffer, `floats` of them in all, or device
-// palettes in place); all `num` validated.
+// palettes in place) or `mo` (the rest positions plus their weighted morph deltas, and through the skin where a pose has a
+// palette: host weights and palettes through the staging buffer, `floats` of them in all, or device ones in place); all `num`
+// validated.
 struct UpdateSource {
     const fovpt_vertex_update* up;
     bool device;
@@ -666,7 +670,8 @@ struct UpdateSource {
     const fovpt_mesh_transform* tf;
     int num;
     const fovpt_skin_pose* sk;
-    int mesh(int k) const { return up ? up[k].mesh : tf ? tf[k].mesh : sk[k].mesh; }
+    const fovpt_morph_pose* mo;
+    int mesh(int k) const { return up ? up[k].mesh : tf ? tf[k].mesh : sk ? sk[k].mesh : mo[k].mesh; }
 };
 
 // The next of the two pinned staging buffers, with room for `bytes`, once the copies it last fed have run
@@ -697,7 +702,7 @@ void ensure_absmax(fovpt_ctx* c)
     }
 }
 
-// The update itself, shared by fovpt_update_vertices, fovpt_update_transforms and fovpt_update_skinned: fovpt_temporal_motion's copy of the positions
+// The update itself, shared by fovpt_update_vertices, fovpt_update_transforms, fovpt_update_skinned and fovpt_update_morphed: fovpt_temporal_motion's copy of the positions
 // about to be overwritten, the new positions into up_vtx on fovpt_stream(), and either the refit, enqueued behind them on the
 // same stream (the stream every job's resolve, and so every job's last traversal launch, is ordered on) with the event the next
 // job waits for, or a rebuild.
@@ -740,12 +745,69 @@ int update_scene(fovpt_ctx* c, const UpdateSource& s, bool rebuild)
         }
         HIPCHK(c, hipGetLastError());
     }
-    if ((s.tf || s.sk) && !c->rest_vtx.p) {
+    if ((s.tf || s.sk || s.mo) && !c->rest_vtx.p) {
         // the first transforms or poses of the scene: the rest positions stay on the device
         HIPCHK(c, c->rest_vtx.reserve(c->h_vtx.size() * 4));
         HIPCHK(c, hipMemcpyAsync(c->rest_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
     }
-    if (s.sk) {
+    if (s.mo) {
+        if (!s.device && s.floats) {
+            // host weights, then host palettes: staged in call order, each copied to its mesh's place in morph_w / skin_pal
+            // (neighbours in one copy)
+            fovpt_ctx::Staging* S = nullptr;
+            { const int rc_ = take_stage(c, s.floats * 4, &S); if (rc_) return rc_; }
+            float* h = (float*)S->p;
+            for (int k = 0; k < s.num;) {
+                const uint32_t first = c->morphs[s.mo[k].mesh].w_first;
+                size_t nw = 0;
+                do {
+                    memcpy(h + nw, s.mo[k].weights, 4 * (size_t)s.mo[k].num_targets);
+                    nw += s.mo[k].num_targets;
+                } while (++k < s.num && c->morphs[s.mo[k].mesh].w_first == first + nw);
+                HIPCHK(c, hipMemcpyAsync((float*)c->morph_w.p + first, h, 4 * nw, hipMemcpyHostToDevice, st));
+                h += nw;
+            }
+            for (int k = 0; k < s.num;) {
+                if (!s.mo[k].num_joints) { k++; continue; }
+                const uint32_t first = c->skins[s.mo[k].mesh].pal_first;
+                size_t joints = 0;
+                do {
+                    memcpy(h + 12 * joints, s.mo[k].matrices, 48 * (size_t)s.mo[k].num_joints);
+                    joints += s.mo[k].num_joints;
+                } while (++k < s.num && s.mo[k].num_joints && c->skins[s.mo[k].mesh].pal_first == first + joints);
+                HIPCHK(c, hipMemcpyAsync((float*)c->skin_pal.p + 12 * (size_t)first, h, 48 * joints, hipMemcpyHostToDevice, st));
+                h += 12 * joints;
+            }
+            HIPCHK(c, hipEventRecord(S->ev, st));
+            S->pending = true;
+        }
+        // two batches side by side: the poses without a palette (k_morph_vertices) and those with one (k_morph_skin_vertices)
+        VertexMorph g[2];
+        memset(g, 0, sizeof(g));
+        for (int k = 0; k < s.num; k++) {
+            const fovpt_morph_pose& P = s.mo[k];
+            const fovpt_ctx::Morph& M = c->morphs[P.mesh];
+            const uint32_t nv = c->mesh_nv[P.mesh];
+            VertexMorph& b = g[P.num_joints ? 1 : 0];
+            b.w[b.count] = s.device ? P.weights : (const float*)c->morph_w.p + M.w_first;
+            b.first[b.count] = c->mesh_vbase[P.mesh]; b.n[b.count] = nv; b.off[b.count] = M.off_first;
+            if (P.num_joints) {
+                const fovpt_ctx::Skin& K = c->skins[P.mesh];
+                b.pal[b.count] = s.device ? P.matrices : (const float*)c->skin_pal.p + 12 * (size_t)K.pal_first;
+                b.skin[b.count] = K.first;
+            }
+            b.max_n = nv > b.max_n ? nv : b.max_n;
+            b.count++;
+            for (int v = 0; v < 2; v++) {
+                if (!(g[v].count == FOVPT_GATHER_BATCH || (k + 1 == s.num && g[v].count))) continue;
+                if (v) fovpt_launch_morph_skin_vertices(st, g[v], (const float*)c->rest_vtx.p, (const uint32_t*)c->morph_off.p, (const MorphEntry*)c->morph_ent.p,
+                                                        (const uint2*)c->skin_joints.p, (const float4*)c->skin_weights.p, vtx);
+                else fovpt_launch_morph_vertices(st, g[v], (const float*)c->rest_vtx.p, (const uint32_t*)c->morph_off.p, (const MorphEntry*)c->morph_ent.p, vtx);
+                memset(&g[v], 0, sizeof(g[v]));
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+    } else if (s.sk) {
         if (!s.device && s.floats) {
             // host palettes: staged in call order, each copied to its mesh's place in skin_pal (neighbours in one copy)
             fovpt_ctx::Staging* S = nullptr;
@@ -1101,7 +1163,7 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
     }
     { const int rc_ = check_updatable(c, "fovpt_update_vertices"); if (rc_) return rc_; }
     if (num_updates == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {up, device, floats, nullptr, num_updates, nullptr};
+    const UpdateSource src = {up, device, floats, nullptr, num_updates, nullptr, nullptr};
     return update_scene(c, src, rebuild);
 }
 
@@ -1133,7 +1195,7 @@ int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int nu
     { const int rc_ = check_updatable(c, "fovpt_update_transforms"); if (rc_) return rc_; }
     const bool rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
     if (num == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {nullptr, false, 0, tf, num, nullptr};
+    const UpdateSource src = {nullptr, false, 0, tf, num, nullptr, nullptr};
     return update_scene(c, src, rebuild);
 }
 
@@ -1250,7 +1312,176 @@ int fovpt_update_skinned(fovpt_ctx* c, const fovpt_skin_pose* poses, int num, in
     }
     { const int rc_ = check_updatable(c, "fovpt_update_skinned"); if (rc_) return rc_; }
     if (num == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {nullptr, device, floats, nullptr, num, poses};
+    const UpdateSource src = {nullptr, device, floats, nullptr, num, poses, nullptr};
+    return update_scene(c, src, rebuild);
+}
+
+// The morph targets are kept on the host per mesh, transposed into a per-vertex list of {delta, target} records sorted by
+// target (what the kernel walks: the order of the definition is the order in memory, and one launch does a whole pose; a pass per
+// active target would need ordering between passes).  Every call lays the device copies out anew (the morphed meshes' offsets,
+// entries and weights in mesh order), so a mesh's places in morph_off / morph_ent / morph_w are fixed until the next call.
+int fovpt_set_morphs(fovpt_ctx* c, const fovpt_mesh_morph* morphs, int num)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_set_morphs without a scene");
+    if (num < 0 || (num > 0 && !morphs)) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: %d morphs at %p", num, (const void*)morphs);
+    const int nmesh = (int)c->mesh_nv.size();
+    std::vector<char> seen((size_t)nmesh, 0);
+    std::vector<size_t> entries((size_t)(num > 0 ? num : 0), 0);
+    for (int k = 0; k < num; k++) {
+        const fovpt_mesh_morph& K = morphs[k];
+        if (K.mesh < 0 || K.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d of %d", K.mesh, nmesh);
+        if (seen[K.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d is listed twice", K.mesh);
+        seen[K.mesh] = 1;
+        if (K._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: _reserved is %u", K.mesh, K._reserved);
+        const uint32_t nv = c->mesh_nv[K.mesh];
+        if (K.num_vertices != nv) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d has %u vertices, not %u", K.mesh, nv, K.num_vertices);
+        if (K.num_targets > FOVPT_MORPH_MAX_TARGETS) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: %u targets (at most %d)", K.mesh, K.num_targets, FOVPT_MORPH_MAX_TARGETS);
+        if (K.num_targets == 0) {
+            if (K.targets) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: no targets, but a pointer (removing morphs takes a null pointer)", K.mesh);
+            continue;
+        }
+        if (!K.targets) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: null targets", K.mesh);
+        for (uint32_t t = 0; t < K.num_targets; t++) {
+            const fovpt_morph_target& T = K.targets[t];
+            if (T._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: _reserved is %u", K.mesh, t, T._reserved);
+            if (T.count > nv) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: %u entries for %u vertices", K.mesh, t, T.count, nv);
+            if (!T.index && T.count != 0 && T.count != nv)
+                return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: no indices, but %u entries for %u vertices", K.mesh, t, T.count, nv);
+            if (!T.delta && T.count) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: null delta", K.mesh, t);
+            entries[k] += T.count;
+        }
+    }
+    if (num == 0) return FOVPT_OK;
+    // the new layout (its size is known from the counts alone: checked before the entries themselves are read)
+    std::vector<uint32_t> nt((size_t)nmesh, 0);
+    std::vector<size_t> ne((size_t)nmesh, 0);
+    for (int m = 0; m < nmesh && !c->morphs.empty(); m++) { nt[m] = c->morphs[m].num_targets; ne[m] = c->morphs[m].ent.size(); }
+    for (int k = 0; k < num; k++) { nt[morphs[k].mesh] = morphs[k].num_targets; ne[morphs[k].mesh] = entries[k]; }
+    size_t offs = 0, ents = 0, targets = 0;
+    for (int m = 0; m < nmesh; m++)
+        if (nt[m]) { offs += (size_t)c->mesh_nv[m] + 1; ents += ne[m]; targets += nt[m]; }
+    if (ents >= (1ull << 32) || offs >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: more than 2^32 - 1 entries (%zu) or offsets (%zu)", ents, offs);
+    for (int k = 0; k < num; k++) {
+        const fovpt_mesh_morph& K = morphs[k];
+        for (uint32_t t = 0; t < K.num_targets; t++) {
+            const fovpt_morph_target& T = K.targets[t];
+            for (uint32_t i = 0; T.index && i < T.count; i++) {
+                if (T.index[i] >= K.num_vertices) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u entry %u: vertex %u of %u", K.mesh, t, i, T.index[i], K.num_vertices);
+                if (i && T.index[i] <= T.index[i - 1]) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u entry %u: indices are not strictly ascending", K.mesh, t, i);
+            }
+            for (size_t i = 0; i < 3 * (size_t)T.count; i++)
+                if (!std::isfinite(T.delta[i])) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u entry %zu: a delta is not finite", K.mesh, t, i / 3);
+        }
+    }
+    // the named meshes' targets, transposed: a count per vertex, its running sum, then the targets in ascending order
+    std::vector<fovpt_ctx::Morph> fresh((size_t)num);
+    for (int k = 0; k < num; k++) {
+        const fovpt_mesh_morph& K = morphs[k];
+        fovpt_ctx::Morph& D = fresh[k];
+        D.num_targets = K.num_targets;
+        if (!K.num_targets) continue;
+        const uint32_t nv = K.num_vertices;
+        D.D.assign(K.num_targets, 0.0);
+        D.off.assign((size_t)nv + 1, 0);
+        for (uint32_t t = 0; t < K.num_targets; t++)
+            for (uint32_t i = 0; i < K.targets[t].count; i++) D.off[(K.targets[t].index ? K.targets[t].index[i] : i) + 1]++;
+        for (uint32_t i = 0; i < nv; i++) D.off[i + 1] += D.off[i];
+        D.ent.resize(entries[k]);
+        std::vector<uint32_t> fill(D.off.begin(), D.off.end() - 1);
+        for (uint32_t t = 0; t < K.num_targets; t++) {
+            const fovpt_morph_target& T = K.targets[t];
+            for (uint32_t i = 0; i < T.count; i++) {
+                const float* d = T.delta + 3 * (size_t)i;
+                D.ent[fill[T.index ? T.index[i] : i]++] = MorphEntry{d[0], d[1], d[2], t};
+                D.D[t] = std::fmax(D.D[t], std::fmax(std::fabs((double)d[0]), std::fmax(std::fabs((double)d[1]), std::fabs((double)d[2]))));
+            }
+        }
+    }
+    // the device buffers before anything changes
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf d_off, d_ent, d_w;
+    if (targets) {
+        HIPCHK(c, d_off.reserve(offs * 4));
+        HIPCHK(c, d_ent.reserve(ents ? ents * 16 : 16));
+        HIPCHK(c, d_w.reserve(targets * 4));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_morphed in flight reads the buffers about to go
+    if (c->morphs.empty()) c->morphs.resize((size_t)nmesh);
+    for (int k = 0; k < num; k++) c->morphs[morphs[k].mesh] = std::move(fresh[k]);
+    uint32_t off_first = 0, ent_first = 0, w_first = 0;
+    std::vector<uint32_t> abs_off;
+    for (int m = 0; m < nmesh; m++) {
+        fovpt_ctx::Morph& D = c->morphs[m];
+        D.off_first = off_first; D.ent_first = ent_first; D.w_first = w_first;
+        if (!D.num_targets) continue;
+        abs_off.resize(D.off.size());
+        for (size_t i = 0; i < D.off.size(); i++) abs_off[i] = ent_first + D.off[i];
+        HIPCHK(c, hipMemcpy((uint32_t*)d_off.p + off_first, abs_off.data(), 4 * abs_off.size(), hipMemcpyHostToDevice));
+        if (!D.ent.empty()) HIPCHK(c, hipMemcpy((MorphEntry*)d_ent.p + ent_first, D.ent.data(), 16 * D.ent.size(), hipMemcpyHostToDevice));
+        off_first += (uint32_t)D.off.size(); ent_first += (uint32_t)D.ent.size(); w_first += D.num_targets;
+    }
+    std::swap(c->morph_off.p, d_off.p); std::swap(c->morph_off.bytes, d_off.bytes);
+    std::swap(c->morph_ent.p, d_ent.p); std::swap(c->morph_ent.bytes, d_ent.bytes);
+    std::swap(c->morph_w.p, d_w.p); std::swap(c->morph_w.bytes, d_w.bytes);
+    return FOVPT_OK;
+}
+
+// The rest positions of the named meshes plus their weighted deltas (k_morph_vertices), through the skin where a pose has a
+// palette (k_morph_skin_vertices), then fovpt_update_vertices' refit or rebuild.  For host data the overflow rules keep every
+// intermediate value finite.
+int fovpt_update_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, int flags)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_morphed without a scene");
+    if (num < 0 || (num > 0 && !poses)) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: %d poses at %p", num, (const void*)poses);
+    if (flags & ~(FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD)) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: unknown flag bits %d", flags);
+    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    const int nmesh = (int)c->mesh_nv.size();
+    if (num > 0 && !device) ensure_absmax(c);
+    std::vector<char> seen((size_t)nmesh, 0);
+    size_t floats = 0;
+    for (int k = 0; k < num; k++) {
+        const fovpt_morph_pose& P = poses[k];
+        if (P.mesh < 0 || P.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d of %d", P.mesh, nmesh);
+        if (seen[P.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d is listed twice", P.mesh);
+        seen[P.mesh] = 1;
+        if (P._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: _reserved is %u", P.mesh, P._reserved);
+        if (c->morphs.empty() || !c->morphs[P.mesh].num_targets) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d has no morph targets", P.mesh);
+        const fovpt_ctx::Morph& M = c->morphs[P.mesh];
+        if (P.num_targets != M.num_targets) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: %u targets, the mesh has %u", P.mesh, P.num_targets, M.num_targets);
+        if (!P.weights) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: null weights", P.mesh);
+        if ((P.matrices == nullptr) != (P.num_joints == 0))
+            return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: %u joints with matrices at %p", P.mesh, P.num_joints, (const void*)P.matrices);
+        const fovpt_ctx::Skin* K = nullptr;
+        if (P.num_joints) {
+            if (c->skins.empty() || !c->skins[P.mesh].num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d has no skin", P.mesh);
+            K = &c->skins[P.mesh];
+            if (P.num_joints != K->num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: %u joints, its skin has %u", P.mesh, P.num_joints, K->num_joints);
+        }
+        floats += (size_t)P.num_targets + 12 * (size_t)P.num_joints;
+        if (device) continue;
+        double B = c->mesh_absmax[P.mesh];
+        for (uint32_t t = 0; t < P.num_targets; t++) {
+            if (!std::isfinite(P.weights[t])) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: weight %u is not finite", P.mesh, t);
+            B += std::fabs((double)P.weights[t]) * M.D[t];
+        }
+        if (B > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d could overflow (bound %g > 2^127)", P.mesh, B);
+        if (!K) continue;
+        for (size_t i = 0; i < 12 * (size_t)P.num_joints; i++)
+            if (!std::isfinite(P.matrices[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d joint %zu entry %zu is not finite", P.mesh, i / 12, i % 12);
+        for (size_t r = 0; r < 3 * (size_t)P.num_joints; r++) {
+            // fovpt_update_skinned's two rules, with the morphed positions' bound B in A's place
+            const float* row = P.matrices + 4 * r;
+            const double bound = K->S * ((std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * B + std::fabs((double)row[3]));
+            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d joint %zu row %zu could overflow (bound %g > 2^127)", P.mesh, r / 3, r % 3, bound);
+            const double entry = K->S * std::fmax(std::fmax(std::fabs((double)row[0]), std::fabs((double)row[1])), std::fabs((double)row[2]));
+            if (entry > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d joint %zu row %zu: a blended entry could overflow (%g > 2^127)", P.mesh, r / 3, r % 3, entry);
+        }
+    }
+    { const int rc_ = check_updatable(c, "fovpt_update_morphed"); if (rc_) return rc_; }
+    if (num == 0 && !rebuild) return FOVPT_OK;
+    const UpdateSource src = {nullptr, device, floats, nullptr, num, nullptr, poses};
     return update_scene(c, src, rebuild);
 }
 

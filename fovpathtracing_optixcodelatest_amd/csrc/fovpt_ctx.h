@@ -102,6 +102,15 @@ struct fovpt_ctx {
     struct Skin { uint32_t num_joints = 0, first = 0, pal_first = 0; double S = 0.0; std::vector<uint16_t> joints; std::vector<float> weights; };
     std::vector<Skin> skins;
     DevBuf skin_joints, skin_weights, skin_pal;
+    // fovpt_set_morphs / fovpt_update_morphed.  morphs: empty until a scene's first fovpt_set_morphs, then one entry per mesh
+    // (num_targets 0: no morphs) with the host copy of the targets transposed into a per-vertex list -- off: num_vertices + 1
+    // offsets into ent, relative to the mesh's first entry; ent: 16-byte records {dx, dy, dz, target}, sorted by target within
+    // a vertex --, D[t] the largest |delta component| of target t (the overflow rule), the mesh's first offset in morph_off
+    // (the morphed meshes in mesh order, num_vertices + 1 each, absolute into morph_ent), its first entry in morph_ent and its
+    // first weight in morph_w (where host weights go).  Laid out anew by every fovpt_set_morphs; dropped by fovpt_set_scene.
+    struct Morph { uint32_t num_targets = 0, off_first = 0, ent_first = 0, w_first = 0; std::vector<double> D; std::vector<uint32_t> off; std::vector<MorphEntry> ent; };
+    std::vector<Morph> morphs;
+    DevBuf morph_off, morph_ent, morph_w;
     // fovpt_hierarchy_cost.  cost_built / cost_current / cost_updates / cost_measured: the caller's record.  cost_partial: the
     // block sums of k_tree_cost, sized when a hierarchy is adopted.  cost_slot: result records in pinned host memory the final
     // kernel writes, each with the event recorded behind it and the update number it measures; a slot is free once its event has

@@ -350,6 +350,25 @@ struct VertexSkin {
     uint32_t max_n;
 };
 void fovpt_launch_skin_vertices(hipStream_t st, const VertexSkin& g, const float* rest, const uint2* joints, const float4* weights, float* vtx);
+// fovpt_update_morphed: up to FOVPT_GATHER_BATCH meshes, each the n vertices from `first` on of rest through their morph entries
+// into vtx.  Vertex i of mesh u has the entries ent[off[o + i]] .. ent[off[o + i + 1]), o = this->off[u], sorted by target; an
+// entry {dx, dy, dz, target} whose weight w[u][target] is not zero adds w * d to the position (unfused binary32, ascending
+// targets).  pal[u], in a batch given to fovpt_launch_morph_skin_vertices, is the mesh's palette and skin[u] its first vertex
+// in joints and weights: the morphed position then goes through VertexSkin's expression.
+struct MorphEntry { float dx, dy, dz; uint32_t target; };     // 16 bytes
+struct VertexMorph {
+    const float* w[FOVPT_GATHER_BATCH];     // the mesh's weights, one per target
+    const float* pal[FOVPT_GATHER_BATCH];   // (morph and skin only)
+    uint32_t first[FOVPT_GATHER_BATCH];     // first vertex in rest and vtx
+    uint32_t n[FOVPT_GATHER_BATCH];         // vertices
+    uint32_t off[FOVPT_GATHER_BATCH];       // the mesh's first offset in morph_off (n + 1 of them)
+    uint32_t skin[FOVPT_GATHER_BATCH];      // (morph and skin only)
+    int32_t count;
+    uint32_t max_n;
+};
+void fovpt_launch_morph_vertices(hipStream_t st, const VertexMorph& g, const float* rest, const uint32_t* off, const MorphEntry* ent, float* vtx);
+void fovpt_launch_morph_skin_vertices(hipStream_t st, const VertexMorph& g, const float* rest, const uint32_t* off, const MorphEntry* ent,
+                                      const uint2* joints, const float4* weights, float* vtx);
 // fovpt_hierarchy_cost: the SAH cost of the num_nodes wide nodes in binary64, the same value from run to run.  partial: two
 // doubles per block of fovpt_tree_cost_blocks(num_nodes); rec: where the result goes (device-visible memory).
 struct TreeCostRecord { double cost, root, node, leaf; };     // (root + node + 2.7 leaf) / root and its three terms

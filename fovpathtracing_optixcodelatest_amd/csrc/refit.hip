@@ -11,7 +11,9 @@
 //
 // Also here: fovpt_update_transforms' k_transform_vertices (rest positions through per-mesh 3 x 4 matrices into the vertex array,
 // ahead of the same refit), fovpt_update_skinned's k_skin_vertices (the same with a matrix blended per vertex from its mesh's joint
-// palette) and fovpt_hierarchy_cost's k_tree_cost / k_tree_cost_final (the SAH cost of the nodes in binary64).
+// palette), fovpt_update_morphed's k_morph_vertices / k_morph_skin_vertices (the rest positions plus their weighted morph deltas,
+// the second then through the skin) and fovpt_hierarchy_cost's k_tree_cost / k_tree_cost_final (the SAH cost of the nodes in
+// binary64).
 #include "fovpt_device.h"
 
 namespace {
@@ -100,6 +102,66 @@ __global__ void k_skin_vertices(VertexSkin g, const float* __restrict__ rest, co
             dst[3 * i + 2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
         }
     }
+}
+
+// fovpt_update_morphed: k_skin_vertices' launch shape.  Per vertex 12 B of rest and its two offsets into the entries; per entry
+// the record's target word, that target's weight (at most 1 KB per mesh, read by every thread: cache resident), and only where
+// the weight is not zero the 16-byte record itself: p = p + w * d per coordinate in ascending targets, every operation unfused
+// (-ffp-contract=off); a vertex none of whose targets is active is stored as it was loaded, -0 included.  With SKIN the morphed
+// position goes through k_skin_vertices' blend (restated here: that kernel stays as it is) instead of to memory; 12 B written.
+// Offsets, targets and joint indices were laid out or checked by fovpt_set_morphs / fovpt_set_skins.
+template <bool SKIN>
+__device__ inline void morph_vertices(const VertexMorph& g, const float* __restrict__ rest, const uint32_t* __restrict__ off,
+                                      const MorphEntry* __restrict__ ent, const uint2* __restrict__ joints, const float4* __restrict__ weights,
+                                      float* __restrict__ vtx)
+{
+    for (int u = blockIdx.y; u < g.count; u += gridDim.y) {
+        const float* __restrict__ mw = g.w[u];
+        const float* __restrict__ src = rest + 3 * (size_t)g.first[u];
+        float* __restrict__ dst = vtx + 3 * (size_t)g.first[u];
+        const uint32_t* __restrict__ ov = off + g.off[u];
+        const size_t n = g.n[u];
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+            float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+            const uint32_t end = ov[i + 1];
+            for (uint32_t k = ov[i]; k < end; k++) {
+                const float t = mw[ent[k].target];
+                if (t != 0.0f) {                                          // +0 and -0 skip the entry: its record is not fetched
+                    const float4 d = reinterpret_cast<const float4*>(ent)[k];
+                    x = x + t * d.x; y = y + t * d.y; z = z + t * d.z;
+                }
+            }
+            if constexpr (SKIN) {
+                const float* __restrict__ pal = g.pal[u];
+                const uint2 j = joints[g.skin[u] + i];
+                const float4 w = weights[g.skin[u] + i];
+                const float* __restrict__ j0 = pal + 12 * (j.x & 0xffffu);
+                const float* __restrict__ j1 = pal + 12 * (j.x >> 16);
+                const float* __restrict__ j2 = pal + 12 * (j.y & 0xffffu);
+                const float* __restrict__ j3 = pal + 12 * (j.y >> 16);
+                float m[12];
+#pragma unroll
+                for (int e = 0; e < 12; e++) m[e] = ((w.x * j0[e] + w.y * j1[e]) + w.z * j2[e]) + w.w * j3[e];
+                dst[3 * i] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+                dst[3 * i + 1] = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+                dst[3 * i + 2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+            } else {
+                dst[3 * i] = x; dst[3 * i + 1] = y; dst[3 * i + 2] = z;
+            }
+        }
+    }
+}
+
+__global__ void k_morph_vertices(VertexMorph g, const float* __restrict__ rest, const uint32_t* __restrict__ off, const MorphEntry* __restrict__ ent,
+                                 float* __restrict__ vtx)
+{
+    morph_vertices<false>(g, rest, off, ent, nullptr, nullptr, vtx);
+}
+
+__global__ void k_morph_skin_vertices(VertexMorph g, const float* __restrict__ rest, const uint32_t* __restrict__ off, const MorphEntry* __restrict__ ent,
+                                      const uint2* __restrict__ joints, const float4* __restrict__ weights, float* __restrict__ vtx)
+{
+    morph_vertices<true>(g, rest, off, ent, joints, weights, vtx);
 }
 
 // fovpt_hierarchy_cost: dx dy + dy dz + dz dx of a box in binary64
@@ -245,6 +307,23 @@ void fovpt_launch_skin_vertices(hipStream_t st, const VertexSkin& g, const float
     const uint64_t n = g.max_n;
     const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
     hipLaunchKernelGGL(k_skin_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, joints, weights, vtx);
+}
+
+void fovpt_launch_morph_vertices(hipStream_t st, const VertexMorph& g, const float* rest, const uint32_t* off, const MorphEntry* ent, float* vtx)
+{
+    if (g.count <= 0 || g.max_n == 0) return;
+    const uint64_t n = g.max_n;
+    const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
+    hipLaunchKernelGGL(k_morph_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, off, ent, vtx);
+}
+
+void fovpt_launch_morph_skin_vertices(hipStream_t st, const VertexMorph& g, const float* rest, const uint32_t* off, const MorphEntry* ent,
+                                      const uint2* joints, const float4* weights, float* vtx)
+{
+    if (g.count <= 0 || g.max_n == 0) return;
+    const uint64_t n = g.max_n;
+    const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
+    hipLaunchKernelGGL(k_morph_skin_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, off, ent, joints, weights, vtx);
 }
 
 void fovpt_launch_tree_cost(hipStream_t st, const BvhNode4* nodes, uint32_t num_nodes, double* partial, TreeCostRecord* rec)

@@ -22,6 +22,7 @@ EXPORTS = [
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
     "fovpt_temporal_defaults", "fovpt_temporal", "fovpt_temporal_motion", "fovpt_temporal_buffers", "fovpt_temporal_reset", "fovpt_update_vertices",
     "fovpt_update_transforms", "fovpt_hierarchy_cost", "fovpt_set_skins", "fovpt_update_skinned",
+    "fovpt_set_morphs", "fovpt_update_morphed",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
@@ -178,6 +179,8 @@ def load():
     L.fovpt_hierarchy_cost.argtypes = [vp, i32, C.POINTER(abi.HierarchyCost)]
     L.fovpt_set_skins.argtypes = [vp, C.POINTER(abi.MeshSkin), i32]
     L.fovpt_update_skinned.argtypes = [vp, C.POINTER(abi.SkinPose), i32, i32]
+    L.fovpt_set_morphs.argtypes = [vp, C.POINTER(abi.MeshMorph), i32]
+    L.fovpt_update_morphed.argtypes = [vp, C.POINTER(abi.MorphPose), i32, i32]
     L.fovpt_comm_get_unique_id.argtypes = [vp]
     L.fovpt_comm_init.argtypes = [vp, vp, i32, i32]
     L.fovpt_comm_destroy.argtypes = [vp]

@@ -554,6 +554,88 @@ class SampleRenderer:
         if device:
             self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
 
+    # -- morph targets (include/fovpt.h, fovpt_set_morphs / fovpt_update_morphed)
+    def set_morphs(self, morphs):
+        """Sets, replaces or removes the morph targets of meshes: morphs maps a mesh index to a list of targets or to None
+        (remove).  A target is a dense (n, 3) float32 array of deltas, n the mesh's vertex count, or a pair (index (k,) unsigned
+        integers, strictly ascending, delta (k, 3) float32) that moves k of the vertices; k may be 0.  Set-up-time state of the
+        scene: copied before the call returns, geometry does not move.  Bad shapes raise ValueError."""
+        items = sorted(morphs.items())
+        mm = (abi.MeshMorph * max(1, len(items)))()
+        keep = []
+        for k, (mesh, targets) in enumerate(items):
+            if not 0 <= int(mesh) < len(self.model.meshes):
+                raise ValueError("set_morphs: mesh %d of %d" % (mesh, len(self.model.meshes)))
+            nv = int(self.model.meshes[mesh].vertex.shape[0])
+            mm[k].mesh, mm[k].num_vertices = int(mesh), nv
+            if targets is None:
+                continue
+            if len(targets) == 0:
+                raise ValueError("set_morphs: mesh %d: an empty list of targets (None removes them)" % mesh)
+            ts = (abi.MorphTarget * len(targets))()
+            for t, target in enumerate(targets):
+                if isinstance(target, tuple):
+                    idx, d = np.asarray(target[0]), np.ascontiguousarray(target[1], np.float32).reshape(-1, 3)
+                    if idx.ndim != 1 or (idx.size and (idx.dtype.kind not in "ui" or idx.min() < 0 or idx.max() > 0xffffffff)) or idx.shape[0] != d.shape[0]:
+                        raise ValueError("set_morphs: mesh %d target %d needs (k,) vertex indices and (k, 3) deltas" % (mesh, t))
+                    idx = np.ascontiguousarray(idx, np.uint32)
+                    keep.append(idx)
+                    ts[t].index = idx.ctypes.data
+                else:
+                    d = np.ascontiguousarray(target, np.float32)
+                    if d.ndim != 2 or d.shape != (nv, 3):
+                        raise ValueError("set_morphs: mesh %d target %d: a dense target needs (%d, 3) deltas" % (mesh, t, nv))
+                keep.append(d)
+                ts[t].count, ts[t].delta = d.shape[0], (d.ctypes.data if d.shape[0] else None)
+            keep.append(ts)
+            mm[k].num_targets, mm[k].targets = len(targets), ts
+        self._check(self._L.fovpt_set_morphs(self._ctx, mm, len(items)))
+
+    def update_morphed(self, poses, rebuild=False):
+        """Poses of morphed meshes: poses maps a mesh index to its weights, a (T,) float32 array, T the mesh's target count, or to
+        a pair (weights, palette) whose palette is what update_skinned() takes for the mesh's skin; or to contiguous float32 CUDA
+        torch tensors, (T,) and (J, 3, 4) (read in stream order on the renderer's stream, not validated).  All host or all
+        device.  Every vertex's rest position takes w[t] * delta of each of its targets whose weight is not zero, in ascending
+        targets, and then goes through the skin where a palette is given; absolute, not cumulative; then update_vertices()'
+        refit (or, rebuild=True, rebuild) with the same ordering.  Bad shapes raise ValueError.  The renderer's Model is not
+        changed."""
+        items = [(mesh, v if isinstance(v, tuple) else (v, None)) for mesh, v in sorted(poses.items())]
+        on_device = [hasattr(x, "is_cuda") and bool(x.is_cuda) for _, v in items for x in v if x is not None]
+        if any(on_device) and not all(on_device):
+            raise ValueError("update_morphed: mixes host arrays and device tensors")
+        device = bool(on_device) and all(on_device)
+        ps = (abi.MorphPose * max(1, len(items)))()
+        keep = []
+        for k, (mesh, (w, m)) in enumerate(items):
+            if device:
+                import torch
+                if w.dtype != torch.float32 or w.dim() != 1 or not w.is_contiguous():
+                    raise ValueError("update_morphed: mesh %d needs a contiguous (T,) float32 tensor of weights" % mesh)
+                if m is not None and (m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (3, 4) or not m.is_contiguous()):
+                    raise ValueError("update_morphed: mesh %d needs a contiguous (J, 3, 4) float32 tensor" % mesh)
+                wp, mp = w.data_ptr(), (None if m is None else m.data_ptr())
+            else:
+                w = np.ascontiguousarray(w, np.float32)
+                if w.ndim != 1:
+                    raise ValueError("update_morphed: mesh %d needs a (T,) array of weights" % mesh)
+                if m is not None:
+                    m = np.asarray(m, np.float32)
+                    if m.ndim == 3 and m.shape[1:] == (4, 4):
+                        if not (m[:, 3] == np.float32([0, 0, 0, 1])).all():
+                            raise ValueError("update_morphed: mesh %d: the last row of a (4, 4) matrix must be 0 0 0 1" % mesh)
+                        m = m[:, :3]
+                    if m.ndim != 3 or m.shape[1:] != (3, 4):
+                        raise ValueError("update_morphed: mesh %d needs a (J, 3, 4) or (J, 4, 4) palette" % mesh)
+                    m = np.ascontiguousarray(m)
+                wp, mp = w.ctypes.data, (None if m is None else m.ctypes.data)
+            keep += [w, m]
+            ps[k].mesh, ps[k].num_targets, ps[k].weights = int(mesh), int(w.shape[0]), wp
+            ps[k].num_joints, ps[k].matrices = (0 if m is None else int(m.shape[0])), mp
+        flags = (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)
+        self._check(self._L.fovpt_update_morphed(self._ctx, ps, len(items), flags))
+        if device:
+            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

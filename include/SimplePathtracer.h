@@ -275,6 +275,16 @@ public:
     {
         check(fovpt_update_skinned(ctx, poses.data(), (int)poses.size(), (rebuild ? FOVPT_UPDATE_REBUILD : 0) | (device ? FOVPT_UPDATE_DEVICE : 0)));
     }
+    // morph targets: setMorphs uploads, replaces or removes (num_targets 0, null pointer) the targets of the listed meshes,
+    // once; updateMorphed sends one weight per target and, with num_joints > 0, the mesh's skin palette (device = true: device
+    // pointers, read in stream order), adds the weighted deltas to the rest positions on the device and sends the result
+    // through the skin, absolute not cumulative, then updateAccel()'s refit or rebuild (include/fovpt.h, fovpt_set_morphs /
+    // fovpt_update_morphed).  The Model is not changed.
+    void setMorphs(const std::vector<fovpt_mesh_morph>& morphs) { check(fovpt_set_morphs(ctx, morphs.data(), (int)morphs.size())); }
+    void updateMorphed(const std::vector<fovpt_morph_pose>& poses, bool rebuild = false, bool device = false)
+    {
+        check(fovpt_update_morphed(ctx, poses.data(), (int)poses.size(), (rebuild ? FOVPT_UPDATE_REBUILD : 0) | (device ? FOVPT_UPDATE_DEVICE : 0)));
+    }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

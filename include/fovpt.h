@@ -353,6 +353,82 @@ typedef struct fovpt_skin_pose {
 } fovpt_skin_pose;               /* 16 bytes */
 int fovpt_update_skinned(fovpt_ctx* ctx, const fovpt_skin_pose* poses, int num, int flags);   /* FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD */
 
+/* ---- morph targets: per-mesh blend shapes weighted on the device --------------------------------------------------------------
+ * fovpt_update_vertices for morphed meshes (blend shapes: a face, a muscle corrective, cloth keyframes): the targets are
+ * uploaded once per mesh with fovpt_set_morphs, and every frame carries one weight per target, a few hundred bytes instead of
+ * 12 bytes per vertex.  With a palette the morphed positions go through the mesh's skin in the same pass (glTF's order: morph,
+ * then skin).
+ *   geometry   for a vertex of a named mesh with REST position p = (x, y, z) -- the one fovpt_set_scene received --, the mesh's
+ *              targets t = 0, 1, ... in ascending order: for every target that lists the vertex, with delta d, and whose weight
+ *              has w[t] != 0.0f,
+ *                  p.x = p.x + w[t] * d.x        p.y, p.z likewise
+ *              every * and + one unfused binary32 operation.  A target whose weight is +0 or -0 is SKIPPED, not applied: a pose
+ *              of all zeros leaves rest bit for bit, a coordinate of -0 included.  Zero deltas are applied like any other entry;
+ *              weights may be negative or above 1.  With matrices the morphed p then goes through fovpt_update_skinned's
+ *              expression unchanged, with the mesh's skin from fovpt_set_skins: the blended M[e], then
+ *              x' = ((M[0] * x + M[1] * y) + M[2] * z) + M[3].  Poses are absolute and start from rest; meshes not named keep
+ *              what they last had, through any of the four calls; a morphed mesh may still be given to the other three, and
+ *              fovpt_update_skinned of a morphed mesh is rest through the skin.
+ *   contract   after the call every frame, G-buffer, debug trace, "scene_vertices" buffer and hierarchy byte is what
+ *              fovpt_update_vertices gives on the same context with those positions as host arrays.  Stream ordering, the
+ *              refit, fovpt_temporal_motion's tracking, fovpt_hierarchy_cost's counting and FOVPT_UPDATE_REBUILD are that call's
+ *              own.
+ *   set_morphs set-up-time state of the scene: each entry sets, replaces or (num_targets == 0, targets null) removes the morphs
+ *              of its mesh; the morphs of other meshes stay; fovpt_set_scene drops them all.  Everything is copied before the
+ *              call returns; it may synchronise fovpt_stream(); it does not move geometry.  Per target the library keeps D_t,
+ *              the largest |delta component| (in binary64; 0 for an empty target), for the overflow rule below.
+ *              All or nothing.  FOVPT_E_NO_SCENE: no scene.  FOVPT_E_INVALID: null ctx, null morphs with num > 0, num < 0, a
+ *              mesh out of range or listed twice, num_vertices other than the mesh's, num_targets above
+ *              FOVPT_MORPH_MAX_TARGETS, targets null with num_targets > 0 or non-null with num_targets == 0, a non-zero
+ *              _reserved of either struct, count > num_vertices, a null index with 0 < count < num_vertices, a null delta with
+ *              count > 0, indices not strictly ascending or >= num_vertices, a non-finite delta, more than 2^32 - 1 entries
+ *              (index, delta pairs) in the scene's morphs together.
+ *   poses      fovpt_update_morphed: weights and matrices are host memory, copied before the call returns (through a pinned
+ *              staging buffer into arrays the context owns), or with FOVPT_UPDATE_DEVICE both are device memory read in place
+ *              in stream order on fovpt_stream() and not validated.
+ *              All or nothing, checked before anything changes.  FOVPT_E_NO_SCENE: no scene.  FOVPT_E_INVALID: null ctx, null
+ *              poses with num > 0, num < 0, a mesh out of range or listed twice, a mesh without morphs, num_targets other than
+ *              the mesh's, null weights, unknown flag bits, non-zero _reserved, matrices or num_joints on a mesh without a skin
+ *              or with a num_joints other than the skin's, exactly one of matrices == NULL and num_joints == 0, and for host
+ *              data a non-finite weight or matrix entry or a pose that could overflow: with A the largest |coordinate| of the
+ *              mesh's rest positions,
+ *                  B = A + sum over ascending t of |w[t]| * D_t        (in binary64)
+ *              must not exceed 2^127; every partial sum of a morphed coordinate and every product w * d is within B.  With
+ *              matrices, fovpt_update_skinned's two rules hold with B in A's place: no row with
+ *              S * ((|m0| + |m1| + |m2|) * B + |m3|) > 2^127 and no entry of the first three columns with S * |m| > 2^127.
+ *              Within the rules every intermediate value is finite.  num == 0 without FOVPT_UPDATE_REBUILD: FOVPT_OK, nothing
+ *              happens.
+ * Memory: 16 bytes per (vertex, target) entry and 4 bytes per vertex of a morphed mesh (+ 4 per mesh) on the device and the same
+ * on the host, 4 bytes per target of weights, and the device copy of the rest positions shared with fovpt_update_transforms
+ * and fovpt_update_skinned (12 bytes per vertex, made on the first call of any of the three).  A context that never calls these
+ * functions pays nothing.                                                                                                     */
+#define FOVPT_MORPH_MAX_TARGETS 256
+typedef struct fovpt_morph_target {
+    uint32_t count;              /* vertices this target moves, 0 .. num_vertices                                           */
+    uint32_t _reserved;          /* 0                                                                                       */
+    const uint32_t* index;       /* count vertex indices, host, strictly ascending, each < num_vertices; NULL = dense:
+                                    count == num_vertices (or 0), entry i is vertex i                                       */
+    const float* delta;          /* count xyz triples, host, finite; NULL only with count == 0                              */
+} fovpt_morph_target;            /* 24 bytes */
+typedef struct fovpt_mesh_morph {
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    uint32_t num_vertices;       /* must equal that mesh's num_vertices                                                     */
+    uint32_t num_targets;        /* 1 .. FOVPT_MORPH_MAX_TARGETS; 0 with targets == NULL: remove                            */
+    uint32_t _reserved;          /* 0                                                                                       */
+    const fovpt_morph_target* targets;   /* num_targets of them                                                             */
+} fovpt_mesh_morph;              /* 24 bytes */
+int fovpt_set_morphs(fovpt_ctx* ctx, const fovpt_mesh_morph* morphs, int num);
+
+typedef struct fovpt_morph_pose {
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    uint32_t num_targets;        /* must equal the mesh's                                                                   */
+    const float* weights;        /* num_targets floats (host, or device with FOVPT_UPDATE_DEVICE)                           */
+    uint32_t num_joints;         /* 0: morph alone; else must equal the mesh's skin's                                       */
+    uint32_t _reserved;          /* 0                                                                                       */
+    const float* matrices;       /* NULL with num_joints 0; else the mesh's skin palette, as fovpt_skin_pose.matrices       */
+} fovpt_morph_pose;              /* 32 bytes */
+int fovpt_update_morphed(fovpt_ctx* ctx, const fovpt_morph_pose* poses, int num, int flags);   /* FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD */
+
 /* ---- the cost of the hierarchy, measured on the device -----------------------------------------------------------------------
  * A refit keeps the tree's shape, so traversal slows as the motion grows (sections 13 and 16).  What to watch is
  * the SAH cost of the nodes, in binary64: with d = hi - lo of a live child entry and area = dx * dy + dy * dz + dz * dx,
@@ -879,6 +955,10 @@ static_assert(sizeof(fovpt_mesh_transform) == 52 && offsetof(fovpt_mesh_transfor
 static_assert(sizeof(fovpt_hierarchy_cost_info) == 32 && offsetof(fovpt_hierarchy_cost_info, updates) == 16, "hierarchy cost ABI");
 static_assert(sizeof(fovpt_mesh_skin) == 32 && offsetof(fovpt_mesh_skin, joints) == 16 && offsetof(fovpt_mesh_skin, weights) == 24, "mesh skin ABI");
 static_assert(sizeof(fovpt_skin_pose) == 16 && offsetof(fovpt_skin_pose, matrices) == 8, "skin pose ABI");
+static_assert(sizeof(fovpt_morph_target) == 24 && offsetof(fovpt_morph_target, index) == 8 && offsetof(fovpt_morph_target, delta) == 16, "morph target ABI");
+static_assert(sizeof(fovpt_mesh_morph) == 24 && offsetof(fovpt_mesh_morph, targets) == 16, "mesh morph ABI");
+static_assert(sizeof(fovpt_morph_pose) == 32 && offsetof(fovpt_morph_pose, weights) == 8 && offsetof(fovpt_morph_pose, num_joints) == 16 &&
+              offsetof(fovpt_morph_pose, matrices) == 24, "morph pose ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

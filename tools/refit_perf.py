@@ -16,7 +16,14 @@ device's current / built ratio polled after every frame's refit, beside the fram
 --skin: fovpt_update_skinned instead.  Every mesh gets a procedural skin of 2 .. 64 joints (skin_ref.bend) and one pose; on one
 context, --rounds rounds of three updates to the same positions in turn: update_skinned with host matrices, update_vertices with
 device pointers to the positions skinned beforehand, update_vertices with the same positions as host arrays (ms per call, device
-time on the library's stream; the median over the rounds and every round)."""
+time on the library's stream; the median over the rounds and every round).
+
+--morph: fovpt_update_morphed instead.  Every mesh gets --morph-dense dense and --morph-sparse sparse procedural targets
+(morph_ref.bumps; a sparse one lists --morph-fraction of the mesh's vertices) and one pose with --morph-active weights that are
+not zero; the mix is recorded in the output.  On one context, --rounds rounds of three updates to the same positions in turn:
+update_morphed with host weights, update_vertices with device pointers to the positions morphed beforehand, update_vertices with
+the same positions as host arrays.  Then every mesh gets --skin's skin as well, and update_morphed with weights and matrices
+alternates with update_skinned of the same matrices."""
 import argparse
 import ctypes as C
 import json
@@ -245,6 +252,64 @@ def run_skin(name, calls, warmup, rounds):
     print(json.dumps(out), flush=True)
 
 
+def alternate(r, fns, calls, warmup, rounds, out):
+    """--rounds rounds of the calls of fns in turn: per call the median device ms over the rounds, every round, the host ms."""
+    ms, host_ms = {k: [] for k in fns}, {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            d, h = device_ms(r, fn, calls, warmup)
+            ms[k].append(d)
+            host_ms[k].append(h)
+    for k in fns:
+        out[k + "_ms"] = round(float(np.median(ms[k])), 4)
+        out[k + "_ms_rounds"] = [round(x, 4) for x in ms[k]]
+        out[k + "_host_ms"] = round(float(np.median(host_ms[k])), 4)
+
+
+def run_morph(name, calls, warmup, rounds, dense, sparse, fraction, active):
+    import morph_ref as mr
+    import skin_ref as sk
+    model, r = make_renderer(name)
+    st0 = r.stats()
+    nt = dense + sparse
+    morphs = {k: mr.bumps(m.vertex, dense, sparse, fraction) for k, m in enumerate(model.meshes)}
+    w = np.zeros(nt, np.float32)
+    on = np.unique(np.round(np.linspace(0, nt - 1, min(active, nt))).astype(np.int64))       # spread over the dense and the sparse ones
+    w[on] = np.random.default_rng(5).uniform(0.2, 1.0, len(on)).astype(np.float32)
+    weights = {k: w.copy() for k in morphs}
+    t = time.perf_counter()
+    r.set_morphs(morphs)
+    set_morphs_ms = (time.perf_counter() - t) * 1e3
+    host = mr.restate(model, morphs, weights)
+    dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+    torch.cuda.synchronize()
+    vertices = int(sum(m.vertex.shape[0] for m in model.meshes))
+    entries = int(sum(len(mr.split(t_, model.meshes[k].vertex.shape[0])[0]) for k, ts in morphs.items() for t_ in ts))
+    out = dict(scene=name, triangles=model.num_triangles, meshes=len(model.meshes), bvh_nodes=int(st0.num_bvh_nodes), vertices=vertices,
+               targets_dense=dense, targets_sparse=sparse, sparse_fraction=fraction, targets_active=int((w != 0).sum()),
+               active_dense=int((w[:dense] != 0).sum()), entries=entries, entries_per_vertex=round(entries / max(1, vertices), 2),
+               rounds=rounds, calls=calls, set_morphs_host_ms=round(set_morphs_ms, 3))
+    alternate(r, dict(update_morphed=lambda: r.update_morphed(weights), update_vertices_device=lambda: r.update_vertices(dev),
+                      update_vertices_host=lambda: r.update_vertices(host)), calls, warmup, rounds, out)
+    p, n = C.c_void_p(), C.c_size_t()
+    r._check(r._L.fovpt_debug_buffer(r._ctx, b"scene_vertices", C.byref(p), C.byref(n)))
+    want = np.concatenate([host[k] for k in range(len(model.meshes))]).view(np.uint32).reshape(-1)
+    r.update_morphed(weights)
+    out["positions_match_restatement"] = bool(np.array_equal(r.download(p.value, np.empty(n.value // 4, np.uint32)), want))
+    # morph and skin in one pass against the skin alone
+    skins = {k: sk.bend(m.vertex, 2 + (7 * k) % 63) for k, m in enumerate(model.meshes)}
+    pal = {k: sk.bend_pose(m.vertex, skins[k][2], 12.0, (0.0, 0.02 * (k % 5), 0.0)) for k, m in enumerate(model.meshes)}
+    r.set_skins(skins)
+    both = {k: (weights[k], pal[k]) for k in morphs}
+    alternate(r, dict(update_morphed_skinned=lambda: r.update_morphed(both), update_skinned=lambda: r.update_skinned(pal)), calls, warmup, rounds, out)
+    want = mr.restate(model, morphs, both, skins)
+    want = np.concatenate([want[k] for k in range(len(model.meshes))]).view(np.uint32).reshape(-1)
+    r.update_morphed(both)
+    out["skinned_positions_match_restatement"] = bool(np.array_equal(r.download(p.value, np.empty(n.value // 4, np.uint32)), want))
+    r.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c3,street")
@@ -253,10 +318,17 @@ def main():
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--transforms", action="store_true", help="fovpt_update_transforms and fovpt_hierarchy_cost instead of fovpt_update_vertices")
     ap.add_argument("--skin", action="store_true", help="fovpt_update_skinned against fovpt_update_vertices with device pointers and with host arrays")
-    ap.add_argument("--rounds", type=int, default=5, help="--transforms, --skin: rounds of the alternated timings (at least 5)")
+    ap.add_argument("--morph", action="store_true", help="fovpt_update_morphed against fovpt_update_vertices with device pointers and with host arrays, and with matrices against fovpt_update_skinned")
+    ap.add_argument("--morph-dense", type=int, default=8)
+    ap.add_argument("--morph-sparse", type=int, default=44)
+    ap.add_argument("--morph-fraction", type=float, default=0.05)
+    ap.add_argument("--morph-active", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=5, help="--transforms, --skin, --morph: rounds of the alternated timings (at least 5)")
     a = ap.parse_args()
     for s in a.scenes.split(","):
-        if a.skin:
+        if a.morph:
+            run_morph(s, a.calls, a.warmup, max(5, a.rounds), a.morph_dense, a.morph_sparse, a.morph_fraction, a.morph_active)
+        elif a.skin:
             run_skin(s, a.calls, a.warmup, max(5, a.rounds))
         elif a.transforms:
             run_transforms(s, a.calls, a.warmup, a.frames, max(5, a.rounds))
