@@ -349,6 +349,32 @@ class ExposeState(C.Structure):
     ]
 
 
+PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS = 0x4b505646, 1, 4      # FOVPT_PACKET_*
+PACKET_NEAREST, PACKET_SMOOTH = 0, 1
+
+
+class PacketPass(C.Structure):
+    """fovpt_packet_pass: a pass's launch grid, factor, fill and offset, and the byte offset of its texel array in the packet."""
+    _fields_ = [
+        ("gw", C.c_uint32), ("gh", C.c_uint32), ("factor", C.c_uint32), ("fill", C.c_uint32),
+        ("offx", C.c_uint32), ("offy", C.c_uint32), ("texels", C.c_uint32), ("_reserved", C.c_uint32),
+    ]
+
+
+class PacketHeader(C.Structure):
+    """fovpt_packet_header: the first 128 bytes of a foveated frame packet."""
+    _fields_ = [
+        ("magic", C.c_uint32), ("version", C.c_uint32), ("bytes", C.c_uint32), ("sequence", C.c_uint32),
+        ("width", C.c_int32), ("height", C.c_int32), ("npass", C.c_uint32), ("_reserved", C.c_uint32),
+        ("passes", PacketPass * 3),
+    ]
+
+    @classmethod
+    def from_packet(cls, data):
+        """The header of a packet's bytes (unchecked: fovpt_packet_check checks)."""
+        return cls.from_buffer_copy(bytes(data[:C.sizeof(cls)]))
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
@@ -376,6 +402,8 @@ assert C.sizeof(TemporalConfig) == 32
 assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.reconstruct.offset, PostConfig.temporal.offset) == (16, 48, 80)
 assert C.sizeof(ExposeConfig) == 80 and (ExposeConfig.low_permille.offset, ExposeConfig.key.offset) == (32, 48)
 assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
+assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
+assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeader.passes.offset) == (16, 32)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4
 assert C.sizeof(HierarchyCost) == 32 and HierarchyCost.updates.offset == 16

@@ -3,7 +3,8 @@
 // One context = one device = one stream, like the reference's SampleRenderer
 // (PT_sv5_/SimplePathtracer.cpp:331-340).  Calls on a context are not thread-safe.
 //
-// The post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip; fovpt_ctx.h is what the three share.
+// The post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip, the frame packets in api_packet.hip;
+// fovpt_ctx.h is what they share.
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -939,6 +940,15 @@ fovpt_ctx::~fovpt_ctx()
     for (auto& S : cost_slot) {
         if (S.rec) (void)hipHostFree(S.rec);
         if (S.ev) (void)hipEventDestroy(S.ev);
+    }
+    if (pk_stream) {                                     // (fovpt_destroy's sync_all does not know the packets' copy stream)
+        (void)hipStreamSynchronize(pk_stream);
+        (void)hipStreamDestroy(pk_stream);
+    }
+    for (PacketSlot& S : pk_slot) {
+        if (S.host) (void)hipHostFree(S.host);
+        if (S.ev_encoded) (void)hipEventDestroy(S.ev_encoded);
+        if (S.ev_done) (void)hipEventDestroy(S.ev_done);
     }
     for (StateSet& S : set) {
         for (ChainEvents& ch : S.chain)

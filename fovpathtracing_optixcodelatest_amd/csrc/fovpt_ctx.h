@@ -1,4 +1,4 @@
-// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_post.hip, api_gather.hip): the context, the buffers it
+// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_post.hip, api_gather.hip, api_packet.hip): the context, the buffers it
 // owns, and the helpers more than one of the three files uses.  Host only: no kernel file includes it.
 #pragma once
 #include <string>
@@ -172,6 +172,15 @@ struct fovpt_ctx {
     // AUTO step is a first step; the host never reads it outside fovpt_expose_state), the meter's per-block histogram rows and
     // the histogram of the last metered step, and the context's own outputs; all allocated on first use
     DevBuf ex_state, ex_rows, ex_hist, ex_color, ex_rgba;
+    // fovpt_packet_submit / fovpt_packet_wait (api_packet.hip), all made by a context's first submit: the copy stream, and per slot
+    // the device buffer an encode writes (one each, so that an encode never overwrites a packet that is still being copied), the
+    // pinned host buffer its copy fills (grown on demand), the event recorded on fovpt_stream() behind the encode, which the copy
+    // stream waits for, and the event behind the copy, which fovpt_packet_wait and a later submit into the slot wait for.
+    // pk_next: submits so far; submit k uses slot k % FOVPT_PACKET_SLOTS
+    struct PacketSlot { DevBuf dev; void* host = nullptr; size_t host_bytes = 0, bytes = 0; hipEvent_t ev_encoded = nullptr, ev_done = nullptr; bool submitted = false; };
+    PacketSlot pk_slot[FOVPT_PACKET_SLOTS];
+    hipStream_t pk_stream = nullptr;
+    unsigned pk_next = 0;
     // RCCL transport of the packed gather (fovpt_comm_init / fovpt_gather_frame)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;

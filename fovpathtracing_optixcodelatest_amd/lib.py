@@ -25,6 +25,8 @@ EXPORTS = [
     "fovpt_set_morphs", "fovpt_update_morphed",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
+    "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
+    "fovpt_packet_check", "fovpt_packet_decode_host",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
     "fovpt_model_load_obj", "fovpt_model_load_gltf", "fovpt_model_destroy", "fovpt_model_counts", "fovpt_model_get_mesh", "fovpt_model_get_texture",
     "fovpt_image_load_float4", "fovpt_image_free", "fovpt_image_load_rgba8", "fovpt_image_free_rgba8",
@@ -122,6 +124,14 @@ def _declare_loader(L):
     L.fovpt_image_free_rgba8.restype = None
 
 
+def _declare_packet_host(L):
+    """The packet entry points both libraries share: the checks and the decoder for a client (csrc/packet_host.cpp)."""
+    L.fovpt_packet_check.argtypes = [C.c_void_p, C.c_size_t]
+    L.fovpt_packet_decode_host.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    for name in PACKET_HOST_EXPORTS:
+        getattr(L, name).restype = C.c_int
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -174,6 +184,11 @@ def load():
     L.fovpt_expose_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_expose_state.argtypes = [vp, C.POINTER(abi.ExposeState)]
     L.fovpt_expose_reset.argtypes = [vp]
+    L.fovpt_packet_describe.argtypes = [vp, C.POINTER(abi.LaunchParams), u32, C.POINTER(abi.PacketHeader)]
+    L.fovpt_packet_encode.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, vp]
+    L.fovpt_packet_submit.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, C.POINTER(i32)]
+    L.fovpt_packet_wait.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
+    L.fovpt_packet_decode.argtypes = [vp, C.POINTER(abi.PacketHeader), vp, i32, vp]
     L.fovpt_update_vertices.argtypes = [vp, C.POINTER(abi.VertexUpdate), i32, i32]
     L.fovpt_update_transforms.argtypes = [vp, C.POINTER(abi.MeshTransform), i32, i32]
     L.fovpt_hierarchy_cost.argtypes = [vp, i32, C.POINTER(abi.HierarchyCost)]
@@ -189,6 +204,7 @@ def load():
     L.fovpt_debug_buffer.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(sz)]
     L.fovpt_debug_trace.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     _declare_loader(L)
+    _declare_packet_host(L)
     for name in EXPORTS:
         if name not in ("fovpt_destroy", "fovpt_last_error", "fovpt_stream", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8"):
             getattr(L, name).restype = i32
@@ -198,11 +214,13 @@ def load():
 
 LOADER_SO_PATH = os.path.join(CSRC, "libfovpt_loader.so")
 LOADER_EXPORTS = [n for n in EXPORTS if n.startswith("fovpt_model_") or n.startswith("fovpt_image_")] + ["fovpt_last_error"]
+PACKET_HOST_EXPORTS = ["fovpt_packet_check", "fovpt_packet_decode_host"]      # in both libraries too
 _loader = None
 
 
 def load_loader():
-    """The scene / image ingestion of the C ABI (fovpt_model_*, fovpt_image_*).  If libfovpt.so is already loaded, it; otherwise the
+    """The scene / image ingestion of the C ABI (fovpt_model_*, fovpt_image_*) and the packet decoder for a client
+    (PACKET_HOST_EXPORTS).  If libfovpt.so is already loaded, it; otherwise the
     HOST-ONLY libfovpt_loader.so (same code, g++, no HIP runtime), so that reading OBJ / glTF / JPEG / HDR files needs no GPU
     stack; FOVPT_SO (an A/B build of the whole library) takes precedence.  The render path never goes through here."""
     global _loader
@@ -212,6 +230,7 @@ def load_loader():
         return _loader
     L = C.CDLL(LOADER_SO_PATH)
     _declare_loader(L)
+    _declare_packet_host(L)
     for name in LOADER_EXPORTS:
         if name not in ("fovpt_last_error", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8"):
             getattr(L, name).restype = C.c_int

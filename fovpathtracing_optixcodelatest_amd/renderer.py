@@ -12,6 +12,30 @@ from . import abi, lib
 from .scenes import Model, pack_model
 
 
+def decode_packet(data, mode=abi.PACKET_NEAREST, size=None, out=None):
+    """A foveated frame packet (bytes-like, e.g. what waitPacket returned on the rendering machine) -> the (H, W) uint32 rgba8
+    image, abi.PACKET_NEAREST or abi.PACKET_SMOOTH (fovpt_packet_decode_host).  size: the (width, height) the caller expects
+    (None: the packet's); out: an (H, W) uint32 array to decode into -- pixels no texel reaches keep their contents -- or None
+    for a zeroed one.  Needs the host-only loader library alone: no GPU, no HIP runtime.  Raises lib.FovptError on bytes that
+    are not a valid packet."""
+    buf = bytes(data)
+    L = lib.load_loader()
+    if size is None:
+        if len(buf) < C.sizeof(abi.PacketHeader):
+            raise lib.FovptError(-1, "decode_packet: fewer than 128 bytes")
+        h = abi.PacketHeader.from_packet(buf)
+        size = (h.width, h.height)
+    w, h = int(size[0]), int(size[1])
+    if out is None:
+        if not (0 < w <= 16384 and 0 < h <= 16384):
+            raise lib.FovptError(-1, "decode_packet: width / height outside 1 .. 16384")
+        out = np.zeros((h, w), np.uint32)
+    elif out.shape != (h, w) or out.dtype != np.uint32 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("decode_packet: out must be a C-contiguous (%d, %d) uint32 array" % (h, w))
+    lib.check(None, L.fovpt_packet_decode_host(buf, len(buf), int(mode), out.ctypes.data, w, h), L)
+    return out
+
+
 class Camera:
     """sutil::Camera (sutil/Camera.h:40-100): eye, lookat, up, fovY (degrees), aspect ratio."""
 
@@ -430,6 +454,40 @@ class SampleRenderer:
     def downloadExposedColor(self):
         """The float4 output of the last expose() into the renderer's own buffer."""
         return self._download_frame(self.expose_buffers()[0], 4)
+
+    # -- foveated frame packets (include/fovpt.h, fovpt_packet_*): a frame off the device, small and without stopping the renderer
+    def describePacket(self, sequence=0) -> abi.PacketHeader:
+        """The header encodePacket / submitPacket would write for the frame last rendered (host only); .bytes sizes a buffer."""
+        h = abi.PacketHeader()
+        self._check(self._L.fovpt_packet_describe(self._ctx, C.byref(self.launchParams), sequence, C.byref(h)))
+        return h
+
+    def encodePacket(self, out_packet, sequence=0, in_rgba=None) -> abi.PacketHeader:
+        """Encodes the frame last rendered into out_packet, a device pointer with describePacket().bytes of room.  in_rgba: device
+        pointer of an rgba8 image of the frame's size (post_buffers()[1], expose_buffers()[1], ...), None: the frame buffer.
+        Enqueued on the renderer's stream, not synchronised.  Returns the header it writes."""
+        h = self.describePacket(sequence)
+        self._check(self._L.fovpt_packet_encode(self._ctx, C.byref(self.launchParams), in_rgba, sequence, out_packet))
+        return h
+
+    def submitPacket(self, sequence=0, in_rgba=None) -> int:
+        """encodePacket into the next of abi.PACKET_SLOTS slots and an asynchronous copy to the slot's pinned host buffer: does
+        not wait for the GPU (except for the slot's previous copy, if that is still running).  Returns the slot for waitPacket."""
+        slot = C.c_int(-1)
+        self._check(self._L.fovpt_packet_submit(self._ctx, C.byref(self.launchParams), in_rgba, sequence, C.byref(slot)))
+        return slot.value
+
+    def waitPacket(self, slot) -> bytes:
+        """Waits for that slot's copy alone (later frames keep running) and returns the packet's bytes: what a client hands to
+        decode_packet()."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.fovpt_packet_wait(self._ctx, slot, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value)
+
+    def decodePacket(self, header, packet, out_rgba, mode=abi.PACKET_NEAREST):
+        """The device decoder: header an abi.PacketHeader (host), packet and out_rgba device pointers (out_rgba: the header's
+        width x height rgba8 pixels; those no texel reaches keep their contents).  Enqueued on the renderer's stream."""
+        self._check(self._L.fovpt_packet_decode(self._ctx, C.byref(header), packet, int(mode), out_rgba))
 
     # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
     def update_vertices(self, updates, rebuild=False):

@@ -233,6 +233,31 @@ public:
         check(fovpt_expose_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- foveated frame packets (include/fovpt.h, fovpt_packet_*): the frame last rendered -- in_rgba null: the renderer's own
+    // frame buffer; or the rgba8 output of post() / expose() -- as a small self-describing packet in pinned host memory, without a
+    // device sync: submitPacket() returns at once with a slot, later frames keep rendering, waitPacket(slot) waits for that
+    // slot's copy alone.  A client decodes the bytes with fovpt_packet_decode_host (libfovpt_loader.so has it: no ROCm needed)
+    struct Packet { const void* data; size_t bytes; };
+    int submitPacket(uint32_t sequence, const uint32_t* in_rgba = nullptr)
+    {
+        int slot = -1;
+        check(fovpt_packet_submit(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), in_rgba, sequence, &slot));
+        return slot;
+    }
+    // valid until the slot is submitted again (FOVPT_PACKET_SLOTS submits later)
+    Packet waitPacket(int slot)
+    {
+        Packet p = {nullptr, 0};
+        check(fovpt_packet_wait(ctx, slot, &p.data, &p.bytes));
+        return p;
+    }
+    // the device decoder: header on the host, packet and out_rgba (the header's width x height pixels) on the device; enqueued on
+    // the renderer's stream, then a device sync like render()
+    void decodePacket(const fovpt_packet_header& header, const void* packet, uint32_t* out_rgba, int mode = FOVPT_PACKET_NEAREST)
+    {
+        check(fovpt_packet_decode(ctx, &header, packet, mode, out_rgba));
+        check(fovpt_synchronize(ctx));
+    }
     // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
     // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
     // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true

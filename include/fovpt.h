@@ -802,6 +802,91 @@ int fovpt_expose_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 int fovpt_expose_state(fovpt_ctx* ctx, struct fovpt_expose_state* out);
 int fovpt_expose_reset(fovpt_ctx* ctx);
 
+/* ---- foveated frame packets: a frame off the device, small and without stopping the renderer -----------------------------------
+ * New with this library.  fovpt_download drains every stream and copies a whole frame into pageable memory.  A foveated frame
+ * is described exactly by one value per launch index -- at the shipped radii 74 / 241 a 1920 x 1080 frame has 211 149 of them,
+ * 845 KB against 8.3 MB -- and the library knows which launch index wrote each pixel last (the resolve's writer search).  A
+ * packet is that description, self-contained: a 128-byte header and one rgba8 texel array per pass, little endian (the
+ * definition in integers: tests/packet_ref.py).  It is the last stage behind fovpt_post / fovpt_expose.
+ *   layout    fovpt_packet_header, then per pass (launch order: P, M, F; FOV_OFF: one) gw * gh texels, row-major ly * gw + lx,
+ *             back to back (the first at byte 128).  The header's pass records are those of the frame as rendered; it carries no
+ *             gaze and no radii, a decoder needs neither.
+ *   encode    a launch index OWNS the pixels whose last writer it is.  A texel with n owned pixels: n == 0 -> 0x00000000, else
+ *             each of r, g, b = (sum + n / 2) / n of the owned pixels' 8-bit codes (integer division), alpha 0xff.  On the raw
+ *             frame every owned pixel is equal, so the texel is that pixel.
+ *   NEAREST   a texel with alpha != 0 writes its value to its block, pixels min((l * factor + off + u) mod 2^32, dim - 1) for
+ *             u < fill on both axes; texels write in pass order, within a pass in ascending (ly, lx); later writes win; pixels
+ *             no texel reaches keep what the output held.  decode(encode(raw frame)) is the raw frame on every written pixel.
+ *   SMOOTH    a pixel whose NEAREST texel (lx, ly) has fill == factor > 1 and whose block anchor (ix, iy) satisfies
+ *             0 <= x - ix < fill and 0 <= y - iy < fill is regular: dx = 2 (x - ix) + 1 - fill, sx = dx > 0 ? 1 : -1, neighbour
+ *             weight |dx|, own weight 2 fill - |dx|, the same along y; the taps (lx, ly), (lx + sx, ly), (lx, ly + sy),
+ *             (lx + sx, ly + sy) of the same pass carry the products.  A tap counts inside the grid with alpha != 0 (the own one
+ *             always does); each channel is (sum w c + W / 2) / W over the counted taps, alpha 0xff.  Every other pixel gets its
+ *             NEAREST value.  Seams between passes stay as they are.
+ *   fovpt_packet_describe    host only: the header fovpt_packet_encode would write (header.bytes sizes the caller's buffer).
+ *   fovpt_packet_encode      works on the frame last issued with fovpt_render(ctx, lp) as it was rendered, like every post stage.
+ *                            in_rgba: any device rgba8 image of the frame's size (the post, expose or denoise outputs), NULL =
+ *                            frame_buffer.  out_packet: device memory, header.bytes large, 4-byte aligned; written whole -- header
+ *                            and zero texels included -- and nothing else is.  Enqueued on fovpt_stream(), not synchronised,
+ *                            ordered like fovpt_denoise.  One thread per texel, no atomics (k_packet_encode).
+ *   fovpt_packet_submit      encodes into the device buffer of the next of FOVPT_PACKET_SLOTS slots (round robin; *slot tells
+ *                            which) and copies it to the slot's pinned host buffer on a copy stream of the context's own, behind
+ *                            an event.  Never waits for the GPU, except for the copy of the slot it is about to reuse if that is
+ *                            still in flight.
+ *   fovpt_packet_wait        waits for that slot's copy alone -- frames and stages issued later keep running -- and returns the
+ *                            pinned host pointer, valid until the slot is submitted again (fovpt_resize and fovpt_set_scene leave
+ *                            it readable; fovpt_destroy frees it).
+ *   fovpt_packet_decode      device decoder (one thread per pixel, k_packet_decode): header on the host, packet and out_rgba
+ *                            (header's width x height) on the device.  Enqueued on fovpt_stream().  Needs no rendered frame.
+ *                            It searches each pixel's last texel the way the resolve searches its last writer, which asks that
+ *                            (gw - 1) * factor and (gh - 1) * factor stay below 2^31 - 8 (any packet the encoder makes; the host
+ *                            decoder takes every valid packet).
+ *   fovpt_packet_check       no context, both libraries (libfovpt_loader.so too): FOVPT_OK if the bytes are a valid packet.
+ *   fovpt_packet_decode_host no context, both libraries: the decoder for a client, plain C++.  out_rgba: width x height pixels,
+ *                            which must be the packet's.  The two never read outside [packet, packet + bytes) nor write outside
+ *                            the output.
+ * All or nothing, checked before anything is enqueued.  encode / submit / describe: FOVPT_E_INVALID for a null ctx / lp / output,
+ * a frame rendered with world > 1 (a shard does not see the frame) or one whose packet would not pass fovpt_packet_check (a side
+ * above 16384, more than 2^26 launch indices); FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size
+ * differs, or a null frame_buffer with in_rgba NULL.  wait: FOVPT_E_INVALID for a slot out of range or never submitted.  check /
+ * decode_host / decode: FOVPT_E_INVALID for a wrong magic or version; a bytes field above the bytes given or below 128; width /
+ * height outside 1 .. 16384 or other than the output's; npass outside 1 .. 3; a non-zero reserved field or unused pass entry; gw
+ * or gh 0; more than 2^26 texels in total; factor 0; fill outside 1 .. 8; a texel offset below 128 or not a multiple of 4;
+ * offset + 4 gw gh above the bytes field (in 64 bits); a mode other than 0 / 1; null pointers.
+ * A context that never calls these allocates nothing for them and creates no stream.
+ * On an MI355X at 1920 x 1080, radii 148 / 482 (C3, two frames in flight): render + fovpt_packet_submit / _wait takes 0.831 ms
+ * per frame, render + fovpt_download of the frame 0.988 ms, render alone 0.699 ms; 1 810 768 bytes reach the host per frame
+ * instead of 8 294 400; k_packet_encode takes 0.039 ms, k_packet_decode 0.013 ms (NEAREST) / 0.021 ms (SMOOTH).  Against
+ * fovpt_post's rgba8 output the decoded frame is exact in the fovea and 13 .. 17 codes RMSE off in the other levels with NEAREST,
+ * 20 .. 27 with SMOOTH.                                                                                   */
+#define FOVPT_PACKET_MAGIC   0x4b505646u   /* "FVPK" */
+#define FOVPT_PACKET_VERSION 1
+#define FOVPT_PACKET_SLOTS   4
+#define FOVPT_PACKET_NEAREST 0
+#define FOVPT_PACKET_SMOOTH  1
+typedef struct fovpt_packet_pass {      /* 32 bytes */
+    uint32_t gw, gh;                    /* the pass's launch grid: one texel per launch index, row-major, ly * gw + lx */
+    uint32_t factor, fill;              /* pixel index of a launch = l * factor + off (uint32, wraps); block of fill x fill */
+    uint32_t offx, offy;
+    uint32_t texels;                    /* byte offset of the texel array from the start of the packet, multiple of 4 */
+    uint32_t _reserved;                 /* 0 */
+} fovpt_packet_pass;
+typedef struct fovpt_packet_header {    /* 128 bytes */
+    uint32_t magic, version, bytes, sequence;   /* bytes: the whole packet; sequence: the caller's, copied through */
+    int32_t width, height;
+    uint32_t npass, _reserved;          /* 1 .. 3 passes in launch order (P, M, F; FOV_OFF: one) */
+    fovpt_packet_pass pass[3];          /* unused entries all zero */
+} fovpt_packet_header;
+int fovpt_packet_describe(fovpt_ctx* ctx, const fovpt_launch_params* lp, uint32_t sequence, fovpt_packet_header* out);
+int fovpt_packet_encode(fovpt_ctx* ctx, const fovpt_launch_params* lp, const uint32_t* in_rgba /* NULL = frame_buffer */,
+                        uint32_t sequence, void* out_packet /* device, header.bytes large */);
+int fovpt_packet_submit(fovpt_ctx* ctx, const fovpt_launch_params* lp, const uint32_t* in_rgba, uint32_t sequence, int* slot);
+int fovpt_packet_wait(fovpt_ctx* ctx, int slot, const void** packet, size_t* bytes);      /* pinned host memory */
+int fovpt_packet_decode(fovpt_ctx* ctx, const fovpt_packet_header* header /* host */, const void* packet /* device */,
+                        int mode, uint32_t* out_rgba /* device, header's width x height */);
+int fovpt_packet_check(const void* packet, size_t bytes);
+int fovpt_packet_decode_host(const void* packet, size_t bytes, int mode, uint32_t* out_rgba, int width, int height);
+
 /* ---- multi-GPU: packed gather of the final framebuffer ----------------------------------
  * New with this library: the reference is single-GPU (SimplePathtracer.cpp:331-340).  With
  * fovpt_config.rank/world every handle renders the launch-index tiles it owns -- interleaved
@@ -950,6 +1035,9 @@ static_assert(sizeof(fovpt_post_config) == 112 && offsetof(fovpt_post_config, de
 static_assert(sizeof(fovpt_expose_config) == 80 && offsetof(fovpt_expose_config, low_permille) == 32 && offsetof(fovpt_expose_config, key) == 48,
               "expose config ABI");
 static_assert(sizeof(struct fovpt_expose_state) == 32 && offsetof(struct fovpt_expose_state, weight_total) == 16, "expose state ABI");
+static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");
+static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header, width) == 16 && offsetof(fovpt_packet_header, pass) == 32,
+              "packet header ABI");
 static_assert(sizeof(fovpt_vertex_update) == 16 && offsetof(fovpt_vertex_update, vertex) == 8, "vertex update ABI");
 static_assert(sizeof(fovpt_mesh_transform) == 52 && offsetof(fovpt_mesh_transform, m) == 4, "mesh transform ABI");
 static_assert(sizeof(fovpt_hierarchy_cost_info) == 32 && offsetof(fovpt_hierarchy_cost_info, updates) == 16, "hierarchy cost ABI");

@@ -1,0 +1,156 @@
+"""Foveated frame packets at BASELINE C3 (262,144-triangle atrium, 1920 x 1080, radii 148 / 482, spp 1 / 2 / 8) with two frames
+in flight.  In one process, alternately, --reps times each, --frames frames after a warm-up, by the host clock around a loop
+that ends in a device synchronise:
+    DOWNLOAD  (a) render + downloadPixels per frame: today's way to see a frame (drains the pipeline, 8.3 MB to pageable memory)
+    PACKET    (b) render + fovpt_packet_submit per frame, waiting for the slot submitted two frames earlier
+    RENDER    (c) render alone: what nobody looking at a frame pays
+and by HIP events on the library's stream around --calls calls back to back:
+    ENCODE    (d) k_packet_encode alone (fovpt_packet_encode of the frame buffer)
+    NEAREST / SMOOTH  k_packet_decode alone
+Prints one JSON line: the median over the repetitions and the spread (min, max) of each, PACKET - RENDER beside RENDER's spread,
+the bytes that cross to the host per frame, and the RMSE (8-bit codes, r g b) of decode(encode(x)) against x per foveation level
+for x = fovpt_post's rgba8 output.  Kernel statistics are a separate run:
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/packet_perf.py --frames 20 --calls 20 --reps 1"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from fovpathtracing_optixcodelatest_amd import abi, renderer, scenes  # noqa: E402
+
+
+def level_map(packet, size):
+    """The fill of the texel each pixel decodes from (0: none), from the packet alone: its texels replaced by their pass's fill."""
+    h = abi.PacketHeader.from_packet(packet)
+    b = bytearray(packet)
+    for p in range(h.npass):
+        P = h.passes[p]
+        tex = np.frombuffer(packet, "<u4", P.gw * P.gh, P.texels)
+        b[P.texels:P.texels + 4 * P.gw * P.gh] = np.where(tex >> 24, 0xff000000 | P.fill, 0).astype("<u4").tobytes()
+    return renderer.decode_packet(bytes(b), abi.PACKET_NEAREST, size) & 0xff
+
+
+def main(frames, warmup, calls, reps):
+    size = (1920, 1080)
+    cfg = abi.Config.reference_default()
+    cfg.r_inner, cfg.r_outer = 148, 482
+    cfg.spp_periphery, cfg.spp_middle, cfg.spp_fovea = 1, 2, 8
+    cfg.write_guides = 1
+    cfg.frames_in_flight = 2
+    r = renderer.SampleRenderer(scenes.atrium(262144))
+    r.resize(size)
+    cam = scenes.ATRIUM_CAMERA
+    r.setCamera(renderer.Camera(cam["eye"], cam["lookat"], cam["up"], cam["fovy"], size[0] / size[1]))
+    r.setProbe(renderer.ProbeData(scenes.ambient_probe(size[0], size[1], 2.5)).BuildCDF())
+    r.config = cfg
+    r.launchParams.frame.c.x, r.launchParams.frame.c.y = size[0] // 2, size[1] // 2
+    r.render()
+    header = r.describePacket()
+
+    def leg_download(n):
+        for _ in range(n):
+            r.render_async()
+            r.downloadPixels()
+
+    def leg_packet(n):
+        slots = []
+        for k in range(n):
+            r.render_async()
+            slots.append(r.submitPacket(k))
+            if k >= 2:
+                r.waitPacket(slots[k - 2])
+        for s in slots[-2:]:
+            r.waitPacket(s)
+
+    def leg_render(n):
+        for _ in range(n):
+            r.render_async()
+
+    legs = dict(DOWNLOAD=leg_download, PACKET=leg_packet, RENDER=leg_render)
+
+    def per_frame(fn):
+        fn(warmup)
+        r.synchronize()
+        t0 = time.perf_counter()
+        fn(frames)
+        r.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / frames
+
+    # (d) the kernels alone
+    dev = torch.empty(header.bytes, dtype=torch.uint8, device="cuda")
+    out = torch.zeros((size[1], size[0]), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    kernels = dict(ENCODE=lambda: r.encodePacket(dev.data_ptr()),
+                   NEAREST=lambda: r.decodePacket(header, dev.data_ptr(), out.data_ptr(), abi.PACKET_NEAREST),
+                   SMOOTH=lambda: r.decodePacket(header, dev.data_ptr(), out.data_ptr(), abi.PACKET_SMOOTH))
+    st = torch.cuda.ExternalStream(r.stream)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def per_call(fn):
+        for _ in range(max(1, warmup // 4)):
+            fn()
+        r.synchronize()
+        a.record(st)
+        for _ in range(calls):
+            fn()
+        b.record(st)
+        b.synchronize()
+        return a.elapsed_time(b) / calls
+
+    ms = {k: [] for k in list(legs) + list(kernels)}
+    for _ in range(reps):                                     # alternately
+        for k, fn in legs.items():
+            ms[k].append(per_frame(fn))
+        for k, fn in kernels.items():
+            ms[k].append(per_call(fn))
+    res = dict(config="C3", size=list(size), frames_in_flight=2, frames=frames, calls=calls, reps=reps, device=torch.cuda.get_device_name(0))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    for k, v in ms.items():
+        res["ms_" + k] = round(med[k], 4)
+        res["spread_" + k] = [round(min(v), 4), round(max(v), 4)]
+    res["PACKET_minus_RENDER"] = round(med["PACKET"] - med["RENDER"], 4)
+    res["DOWNLOAD_minus_RENDER"] = round(med["DOWNLOAD"] - med["RENDER"], 4)
+    res["PACKET_below_DOWNLOAD"] = bool(max(ms["PACKET"]) < min(ms["DOWNLOAD"]))
+    res["bytes_packet"], res["bytes_frame"] = int(header.bytes), size[0] * size[1] * 4
+    res["bytes_ratio"] = round(res["bytes_frame"] / res["bytes_packet"], 2)
+
+    # what the packet costs in quality: decode(encode(x)) against x = fovpt_post's rgba8 output, per level
+    r.post()
+    x = r.downloadPostPixels()
+    r.encodePacket(dev.data_ptr(), 0, r.post_buffers()[1])
+    r.synchronize()
+    packet = dev.cpu().numpy().tobytes()
+    level = level_map(packet, size)
+    rgb = lambda v: np.stack([(v >> (8 * k)) & 0xff for k in range(3)], axis=-1).astype(np.float64)
+    rmse = {}
+    for name, mode in (("NEAREST", abi.PACKET_NEAREST), ("SMOOTH", abi.PACKET_SMOOTH)):
+        out.zero_()
+        torch.cuda.synchronize()
+        r.decodePacket(header, dev.data_ptr(), out.data_ptr(), mode)
+        r.synchronize()
+        y = out.cpu().numpy().view(np.uint32)
+        assert np.array_equal(y, renderer.decode_packet(packet, mode, size)), "device and host decoders differ"
+        d2 = ((rgb(y) - rgb(x)) ** 2).mean(axis=-1)
+        rmse[name] = {("fill%d" % f): round(float(np.sqrt(d2[level == f].mean())), 3) for f in (1, 2, 4) if (level == f).any()}
+        rmse[name]["frame"] = round(float(np.sqrt(d2[level > 0].mean())), 3)
+    res["rmse"] = rmse
+    res["pixels_per_level"] = {("fill%d" % f): int((level == f).sum()) for f in (0, 1, 2, 4)}
+    print(json.dumps(res), flush=True)
+    r.close()
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=1000)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    main(args.frames, args.warmup, args.calls, args.reps)
