@@ -1,0 +1,387 @@
+"""Seed -> the script of one animated application (tests/test_app_fuzz_gpu.py runs it through tests/app_model.py).  Pure numpy,
+no GPU: tests/test_app_fuzz_cpu.py runs this generator alone and checks that the default seeds reach every operation and every
+situation listed there, so that an edit here cannot quietly drop one.
+
+A script is a dict: the scene, the frame size, the render config, the skins and morph targets registered before the first
+operation, and `ops`, a list of OPS operations with all their arguments.  The first five operations of every script are a
+frame whose post chain takes a temporal step with motion, three updates of one mesh by three different kinds (TRIPLES: over the
+eight residues of the seed every ordered pair of kinds) and a second such frame, so the three updates share one temporal
+interval; for seeds from 8 on the three kinds are drawn.  The other five operations are units (an operation, or a few that only mean
+something side by side) drawn from the seed and put in a drawn order, under two caps: at most two refused calls, at least
+three frame groups with a post chain.  The eight default seeds each carry some forced units (FORCED), so that together they
+hold everything the CPU test lists whatever else they draw; their order is drawn too."""
+import os
+
+import numpy as np
+
+import morph_ref as mr
+import post_ref as po
+import skin_ref as sk
+import transform_ref as tf
+from fovpathtracing_optixcodelatest_amd import abi, scenes
+
+DEFAULT_SEEDS = range(0, 8)
+SEEDS = range(int(os.environ.get("FOVPT_FUZZAPP_FROM", DEFAULT_SEEDS.start)), int(os.environ.get("FOVPT_FUZZAPP_TO", DEFAULT_SEEDS.stop)))  # widen for a sweep
+OPS = 10
+GATHER_BATCH = 32                                        # FOVPT_GATHER_BATCH
+KINDS = ("vertices", "transforms", "skinned", "morphed")
+# three kinds in turn on one mesh give the ordered pairs (a, b), (b, c), (a, c): the first six rows cover all twelve
+TRIPLES = [(0, 1, 2), (2, 1, 0), (0, 3, 2), (2, 3, 0), (1, 3, 2), (2, 3, 1), (3, 0, 1), (1, 0, 3)]
+# frame sizes, the families of postprocess_fuzz.EDGE_SHAPES within 130 x 90: one short of and one over a multiple of the 64-pixel
+# tile with heights that are no multiple of 4, a frame narrower than one 4 x 4 block, and two ordinary ones
+SIZES = [(63, 37), (65, 30), (127, 41), (129, 23), (3, 50), (96, 64), (64, 45)]
+BIG = (192, 128)                                         # chains_per_frame = 2 needs 16384 sample slots
+E_INVALID, E_NO_FRAME = -1, -5
+F = np.float32
+
+# The tail, operations 5 .. 9, is a shuffled list of UNITS: an operation, or a few that only mean something side by side.
+# u: an update (kind, form, rebuild, "many": more meshes than one batch, "all": every mesh the kind can move); f: a frame group
+# (frames, what runs between them, an update before the chain, the chain: None = drawn); x: a refused call; resize "same": to
+# the size the frame has (the history and the frame as rendered go all the same), "other": to another size that has a packet.
+U_SKINS = (("u", "skinned", "host", False), ("set_skins",), ("u", "skinned", "host", False, "all"))       # a pose, a new layout, every skin posed
+U_MORPHS = (("u", "morphed", "host", False), ("set_morphs",))
+U_RESIZE_SAME = (("resize", "same"), ("f", 1, (), False, "step"))
+U_RESIZE_OTHER = (("resize", "other"), ("x", "no_frame"), ("u", "morphed+", "host", False), ("f", 1, (), False, "step+packet"))
+U_RESIZE_FRAME = (("resize", "other"), ("f", 1, (), False, "step+packet"))
+U_SCENE = (("set_scene",), ("x", "no_skin"), ("set_skins",))
+U_RESET_FRAME = (("temporal_reset",), ("f", 1, (), True, None))
+U_EXPOSE_RESET_FRAME = (("expose_reset",), ("f", 1, (), False, "expose"))
+# the default seeds' units (the rest of their five operations is drawn like everybody's): together they hold every operation
+# and situation tests/test_app_fuzz_cpu.py lists.  Seeds from 8 on draw all of theirs.
+FORCED = [
+    [U_SKINS, U_RESIZE_SAME],
+    [(("f", 3, ("u", "x:overflow"), False, None),), (("expose_reset",),), U_RESET_FRAME, (("u", "morphed+", "host", True),)],
+    [(("u", "vertices", "host", False, "many"),), U_MORPHS, (("f", 2, (None,), False, None),), (("u", "vertices", "device", True),)],
+    [(("f", 2, ("x:mesh_range",), False, None),), U_SCENE],
+    [(("f", 1, (), True, "step"),), U_RESIZE_OTHER],
+    [(("u", "transforms", "host", True, "many"),), (("f", 2, ("u",), False, None),), (("x", "overflow"),), (("u", "morphed", "device", False),)],
+    [(("u", "skinned", "device", True),), (("f", 1, (), False, "packet"),), U_EXPOSE_RESET_FRAME, (("u", "morphed+", "device", False),)],
+    [(("u", "empty", "host", False),), (("set_morphs",),), (("u", "transforms", "host", True),), (("x", "overflow"),), (("f", 3, (None, "u"), True, None),)],
+]
+TAIL_OPS = 5
+MAX_REFUSED = 2
+
+
+def scene_of(s):
+    """(model, camera) of a script."""
+    if s["scene"][0] == "cornell":
+        return scenes.cornell_box(), scenes.CORNELL_CAMERA
+    return scenes.atrium(s["scene"][1]), scenes.ATRIUM_CAMERA
+
+
+class _Draw:
+    """The generator's state: what is registered, so that every pose drawn as valid fits the layout it will meet."""
+
+    def __init__(self, seed):
+        self.seed, self.m = seed, seed % 8
+        self.rng = np.random.default_rng(52000 + seed)
+        rng = self.rng
+        atrium = self.m in (2, 5)
+        self.s = dict(seed=seed, scene=("atrium", int(rng.integers(500, 2001))) if atrium else ("cornell",))
+        self.model, self.cam = scene_of(self.s)
+        self.nmesh = len(self.model.meshes)
+        self.nv = [m.vertex.shape[0] for m in self.model.meshes]
+        chains = self.m % 4 == 3
+        self.s["size"] = self.size = BIG if chains else SIZES[int(rng.integers(0, len(SIZES)))]
+        uniform = int(rng.random() < 0.25)
+        ri = int(rng.integers(0, 30))
+        cfg = dict(uniform=uniform, r_inner=ri, r_outer=ri + int(rng.integers(1, 50)), spp=tuple(int(x) for x in rng.integers(1, 5, 4)),
+                   max_depth=int(rng.integers(1, 4)), frames_in_flight=2 if self.m % 4 == 1 else 0, chains_per_frame=2 if chains else 0)
+        if chains:                                      # a fovea of 4 samples over more than 4096 pixels: >= 16384 sample slots
+            cfg.update(uniform=0, r_inner=40, r_outer=40 + int(rng.integers(1, 40)), spp=(int(rng.integers(1, 5)), int(rng.integers(1, 5)), 4, 4))
+        self.s["config"] = cfg
+        t = dict(zip(("history_fovea", "history_middle", "history_periphery", "history_uniform"), (int(x) for x in rng.choice([2, 3, 8, abi.TEMPORAL_MAX_HISTORY], 4))))
+        self.s["post"] = dict(denoise=dict(iterations_fovea=int(rng.integers(0, 2)), iterations_middle=int(rng.integers(0, 3)),
+                                           iterations_periphery=int(rng.integers(0, 3)), iterations_uniform=int(rng.integers(0, 3))),
+                              reconstruct=dict(levels=int(rng.integers(0, 3))), temporal=t)
+        # the meshes that pose: on the Cornell box the two blocks (3, 4), the floor and a wall; in the atrium the first 48
+        self.posable = [4, 3, 0, 5] if not atrium else list(range(48))
+        self.x = self.posable[0] if not atrium else int(rng.integers(0, 40))       # the mesh of the interval's three updates
+        self.skins = {k: self.skin(k) for k in self.posable}
+        self.morphs = {k: self.targets(k) for k in self.posable[:-1]}          # (one left for a set_morphs to add)
+        self.s["skins"], self.s["morphs"] = dict(self.skins), dict(self.morphs)
+        self.frames = 0
+
+    # ---- what gets registered
+    def skin(self, k):
+        return sk.random_skin(self.rng, self.nv[k], int(self.rng.integers(1, 6)))
+
+    def targets(self, k):
+        nt = int(self.rng.integers(1, 5))
+        t = mr.random_targets(self.rng, self.nv[k], nt, dense=int(self.rng.integers(0, 2)), fraction=0.5, scale=12.0)
+        if all(mr.split(x, self.nv[k])[1].size == 0 or not np.abs(mr.split(x, self.nv[k])[1]).max() >= 1 for x in t):
+            t[0] = np.full((self.nv[k], 3), 2.0, F)     # (some delta of at least 1: a weight of 3e38 then overflows)
+        return t
+
+    # ---- poses
+    def centre(self, k):
+        return self.model.meshes[k].vertex.astype(np.float64).mean(axis=0)
+
+    def pose(self, kind, k):
+        rng, v = self.rng, self.model.meshes[k].vertex
+        if kind == "vertices":
+            return (v + rng.uniform(-6.0, 6.0, v.shape).astype(F)).astype(F)
+        if kind == "transforms":
+            return tf.rotation_translation(rng.uniform(-25, 25), self.centre(k), rng.uniform(-12, 12, 3))
+        if kind == "skinned":
+            return sk.random_pose(rng, v, self.skins[k][2])
+        w = mr.random_weights(rng, len(self.morphs[k]), active=0.7)
+        return (w, sk.random_pose(rng, v, self.skins[k][2])) if kind == "morphed+" else w
+
+    def meshes_for(self, kind, many=False):
+        """The meshes one call moves: a random subset of those the kind can move, more than GATHER_BATCH with many."""
+        rng = self.rng
+        if kind in ("vertices", "transforms"):
+            pool = list(range(self.nmesh))
+        elif kind == "skinned":
+            pool = sorted(self.skins)
+        elif kind == "morphed":
+            pool = sorted(self.morphs)
+        else:
+            pool = sorted(set(self.skins) & set(self.morphs))
+        if many == "all":
+            return pool
+        if many and len(pool) > GATHER_BATCH:
+            n = int(rng.integers(GATHER_BATCH + 1, min(len(pool), 2 * GATHER_BATCH + 8) + 1))
+        else:
+            n = int(rng.integers(1, min(len(pool), 5) + 1)) if pool else 0
+        return sorted(int(k) for k in rng.choice(pool, n, replace=False)) if n else []
+
+    def update(self, kind, form="host", rebuild=False, many=False, meshes=None):
+        if kind == "empty":
+            kind, meshes = KINDS[int(self.rng.integers(0, 4))], []
+        meshes = self.meshes_for(kind, many) if meshes is None else meshes
+        base = "morphed" if kind == "morphed+" else kind
+        return dict(op="update", kind=base, poses={k: self.pose(kind, k) for k in meshes}, rebuild=bool(rebuild),
+                    device=form == "device" and base != "transforms")
+
+    def refused(self, which):
+        rng = self.rng
+        if which == "overflow":
+            kinds = [k for k in KINDS[1:] if k == "transforms" or (self.skins if k == "skinned" else self.morphs)]
+            kind = kinds[int(rng.integers(0, len(kinds)))]
+            k = self.meshes_for(kind)[0]
+            p = self.pose(kind, k)
+            if kind == "morphed":
+                p = p.copy()
+                t = int(np.argmax(mr.target_max(self.morphs[k], self.nv[k])))
+                p[t] = F(3e38)
+            else:
+                p = np.array(p, F)
+                p[..., int(rng.integers(0, 3)), 3] = F(-3e38)
+            good = self.meshes_for(kind)
+            poses = {g: self.pose(kind, g) for g in good if g != k}             # good poses beside the bad one: all or nothing
+            poses[k] = p
+            return dict(op="refused", which=which, kind=kind, poses=poses, bad=k, code=E_INVALID)
+        if which == "mesh_range":
+            kinds = [k for k in KINDS if k in ("vertices", "transforms") or (self.skins if k == "skinned" else self.morphs)]
+            kind = kinds[int(rng.integers(0, len(kinds)))]
+            k = self.meshes_for(kind)[0]
+            bad = self.nmesh if rng.random() < 0.5 else -1
+            return dict(op="refused", which=which, kind=kind, poses={bad: self.pose(kind, k)}, bad=bad, code=E_INVALID)
+        if which == "no_skin":
+            bare = [k for k in range(self.nmesh) if k not in self.skins]
+            k = int(rng.choice(bare))
+            return dict(op="refused", which=which, kind="skinned", poses={k: np.stack([tf.IDENTITY] * 2)}, bad=k, code=E_INVALID)
+        assert which == "no_frame"
+        return dict(op="refused", which=which, calls=("post", "expose", "packet"), code=E_NO_FRAME)      # each of the three
+
+    # ---- registration
+    def set_skins(self):
+        """One call that replaces, removes and adds: the lowest skinned mesh gets a skin of more joints (every later mesh's place
+        in the palette buffer moves up), the highest but one another joint count, the highest goes (three or more skinned), and
+        one mesh without a skin gets one."""
+        rng, new = self.rng, {}
+        have = sorted(self.skins)
+        bare = [k for k in self.posable if k not in self.skins]
+        if len(have) >= 3 and have[-1] != self.x:
+            new[have.pop()] = None
+        if have:
+            k = have[0]
+            new[k] = sk.random_skin(rng, self.nv[k], self.skins[k][2] + int(rng.integers(1, 3)))
+        if len(have) >= 2:
+            k = have[-1]
+            new[k] = self.skin(k)
+            while new[k][2] == self.skins[k][2]:
+                new[k] = self.skin(k)
+        if bare:
+            k = bare[int(rng.integers(0, len(bare)))]
+            new[k] = self.skin(k)
+        for k, v in new.items():
+            if v is None:
+                self.skins.pop(k, None)
+            else:
+                self.skins[k] = v
+        return dict(op="set_skins", skins=new)
+
+    def set_morphs(self):
+        rng, new = self.rng, {}
+        have = sorted(self.morphs)
+        bare = [k for k in self.posable if k not in self.morphs]
+        if have:
+            new[have[int(rng.integers(0, len(have)))]] = "replace"
+        rest = [k for k in have if k not in new and k != self.x]
+        if rest:
+            new[rest[int(rng.integers(0, len(rest)))]] = None
+        if bare:
+            new[bare[int(rng.integers(0, len(bare)))]] = "add"
+        for k, v in list(new.items()):
+            if v is not None:
+                old = self.morphs.get(k)
+                new[k] = self.targets(k)
+                while old is not None and len(new[k]) == len(old):
+                    new[k] = self.targets(k)
+        for k, v in new.items():
+            if v is None:
+                self.morphs.pop(k, None)
+            else:
+                self.morphs[k] = v
+        return dict(op="set_morphs", morphs=new)
+
+    # ---- frames
+    def expose_config(self):
+        rng = self.rng
+        lo = int(rng.integers(0, 1000))
+        ev = np.sort(rng.uniform(-16, 16, 2)).astype(F)
+        d = dict(mode=int(rng.random() < 0.85), metering=int(rng.integers(0, 2)), tone=int(rng.integers(0, 2)),
+                 low_permille=lo, high_permille=int(rng.integers(lo + 1, 1001)), ev_min=float(ev[0]), ev_max=float(ev[1]),
+                 key=float(F(np.exp2(rng.uniform(-8, 8)))), exposure=float(F(np.exp2(rng.uniform(-8, 8)))), white=float(F(np.exp2(rng.uniform(-4, 19)))),
+                 adapt_brighter=float(F(rng.uniform(0.01, 1.0))), adapt_darker=float(F(rng.uniform(0.01, 1.0))))
+        for k in ("weight_fovea", "weight_middle", "weight_periphery", "weight_uniform"):
+            d[k] = int(rng.choice([0, 1, 255, int(rng.integers(0, 256))]))
+        return d
+
+    def chain(self, want=None):
+        """dict(post=stage mask or None, expose=config or None, packet=bool): want "step" forces a temporal step with motion,
+        "packet" / "expose" that stage alone; otherwise each stage is there or not, at least one."""
+        rng = self.rng
+        if want == "packet":
+            return dict(post=None, expose=None, packet=True)
+        if want == "expose":
+            return dict(post=None, expose=self.expose_config(), packet=False)
+        step = want in ("step", "step+packet")
+        masks = [s for s in po.VALID_STAGES if not step or (s & po.TEMPORAL and s & po.MOTION)]
+        c = dict(post=masks[int(rng.integers(0, len(masks)))] if step or rng.random() < 0.8 else None,
+                 expose=self.expose_config() if rng.random() < 0.6 else None, packet=bool(want == "step+packet" or rng.random() < 0.6))
+        if c["post"] is None and c["expose"] is None and not c["packet"]:
+            c["post"] = masks[int(rng.integers(0, len(masks)))]
+        return c
+
+    def frame(self, n=1, between=(), pre_chain=False, want=None):
+        rng = self.rng
+        w, h = self.size
+        views = [dict(gaze=(int(rng.integers(-10, w + 11)), int(rng.integers(-10, h + 11))), subframe_index=int(rng.integers(0, 4)),
+                      eye=tuple(float(x) for x in rng.uniform(-0.02, 0.02, 3))) for _ in range(n)]
+        mid = []
+        for b in between:
+            if b is None:
+                mid.append(None)
+            elif b == "u":
+                kind = ("vertices", "transforms", "skinned", "morphed", "morphed+")[int(rng.integers(0, 5))]
+                mid.append(self.update(kind, "device" if rng.random() < 0.4 else "host"))
+            else:
+                mid.append(self.refused(b[2:]))
+        pre = self.update(KINDS[int(rng.integers(0, 4))], "host") if pre_chain else None
+        self.frames += 1
+        # the caller's next gaze and subframe index, written into the launch parameters between the render and its chain
+        moved_on = dict(gaze=(int(rng.integers(-10, w + 11)), int(rng.integers(-10, h + 11))), subframe_index=int(rng.integers(4, 9))) \
+            if pre_chain or rng.random() < 0.5 else None
+        return dict(op="frame", views=views, between=mid, pre_chain=pre, chain=self.chain(want), moved_on=moved_on,
+                    sync=bool(n == 1 and (self.seed + self.frames) % 2 == 0))
+
+    def resize(self, how=None):
+        rng = self.rng
+        if how is None:
+            how = "same" if rng.random() < 0.25 else "any"
+        pool = [x for x in SIZES if (x == self.size) == (how == "same") and (how != "other" or x[0] >= 4)] or [self.size]
+        self.size = pool[int(rng.integers(0, len(pool)))]
+        return dict(op="resize", size=self.size)
+
+    def set_scene(self):
+        self.skins, self.morphs = {}, {}
+        return dict(op="set_scene")
+
+    def expose_reset(self):
+        return dict(op="expose_reset")
+
+    def temporal_reset(self):
+        return dict(op="temporal_reset")
+
+    def draw_unit(self, room):
+        """One unit of at most `room` operations, drawn."""
+        rng = self.rng
+        while True:
+            u = rng.random()
+            if u < 0.30:
+                kind = ("vertices", "transforms", "skinned", "morphed", "morphed+", "empty")[int(rng.integers(0, 6))]
+                unit = (("u", kind, "device" if rng.random() < 0.4 else "host", bool(rng.random() < 0.3)) + (("many",) if rng.random() < 0.2 else ()),)
+            elif u < 0.55:
+                n = int(rng.integers(1, 4))
+                between = tuple((None, "u", "u", "x:overflow", "x:mesh_range")[int(rng.integers(0, 5))] for _ in range(n - 1))
+                unit = (("f", n, between, bool(rng.random() < 0.4), None),)
+            elif u < 0.70:
+                unit = (U_SKINS, U_MORPHS, (("set_skins",),), (("set_morphs",),))[int(rng.integers(0, 4))]
+            elif u < 0.85:
+                unit = (U_RESIZE_SAME, U_RESIZE_OTHER, U_RESIZE_FRAME, U_RESIZE_FRAME, (("resize",),))[int(rng.integers(0, 5))]
+            elif u < 0.90:
+                unit = U_SCENE if rng.random() < 0.5 else (("set_scene",),)
+            elif u < 0.95:
+                unit = ((("x", "overflow"),), (("x", "mesh_range"),), (("x", "no_skin"),))[int(rng.integers(0, 3))]
+            else:
+                unit = (U_RESET_FRAME, U_EXPOSE_RESET_FRAME, (("temporal_reset",),), (("expose_reset",),))[int(rng.integers(0, 4))]
+            if len(unit) <= room:
+                return unit
+
+    def realize(self, t):
+        """One operation of a unit, with its arguments drawn against the state the operations before it leave."""
+        if t[0] == "x" or (t[0] == "f" and any(b and b.startswith("x:") for b in t[2])):
+            if t[0] == "x":
+                if self.refusals >= MAX_REFUSED or (t[1] == "no_frame" and not self.resized):
+                    return self.temporal_reset()                 # (the cap is reached: something harmless in its place)
+                self.refusals += 1
+                return self.refused(t[1])
+            between = []
+            for b in t[2]:
+                if b and b.startswith("x:") and self.refusals >= MAX_REFUSED:
+                    b = None
+                self.refusals += bool(b and b.startswith("x:"))
+                between.append(b)
+            t = t[:2] + (tuple(between),) + t[3:]
+        self.resized = t[0] == "resize"
+        if t[0] == "u":
+            return self.update(t[1], t[2], t[3], many=t[4] if len(t) > 4 else False)
+        if t[0] == "f":
+            return self.frame(t[1], t[2], t[3], t[4])
+        return getattr(self, t[0])(*t[1:])
+
+    def script(self):
+        rng = self.rng
+        default = self.seed in DEFAULT_SEEDS
+        a, b, c = (KINDS[k] for k in (TRIPLES[self.seed] if default else rng.permutation(4)[:3]))
+
+        def burst(kind, last):
+            form = "device" if kind != "transforms" and rng.random() < 0.4 else "host"
+            k = "morphed+" if kind == "morphed" and rng.random() < 0.5 else kind
+            others = [g for g in self.meshes_for(k) if g != self.x][:2]
+            return self.update(k, form, rebuild=last and (self.m % 2 == 0 if default else rng.random() < 0.5), meshes=sorted([self.x] + others))
+        self.refusals, self.resized = 0, False
+        ops = [self.frame(want="step"), burst(a, False), burst(b, False), burst(c, True), self.frame(want="step")]
+        # the tail: the forced units of a default seed, drawn ones up to five operations, a frame group among them, in drawn order
+        units = list(FORCED[self.seed]) if default else []
+        room = TAIL_OPS - sum(len(u) for u in units)
+        if not any(t[0] == "f" for u in units for t in u):
+            n = int(rng.integers(1, 4))
+            units.append((("f", n, (None,) * (n - 1), bool(rng.random() < 0.4), None),))
+            room -= 1
+        while room > 0:
+            units.append(self.draw_unit(room))
+            room -= len(units[-1])
+        for k in rng.permutation(len(units)):
+            ops += [self.realize(t) for t in units[k]]
+        assert len(ops) == OPS
+        self.s["ops"] = ops
+        return self.s
+
+
+def script(seed):
+    return _Draw(int(seed)).script()

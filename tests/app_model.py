@@ -1,0 +1,496 @@
+"""The state of an animated application, restated: AppModel drives one SampleRenderer through updates of all four kinds, skin and
+morph registration, frames (also several in flight), the post chain (fovpt_post, fovpt_expose, fovpt_packet_*), resizes, scene
+reloads, resets and refused calls, keeps on the host everything the context is specified to keep (include/fovpt.h, DESIGN
+sections 12 to 20) and checks after every operation what that operation defines.  It never reads state back from the library to
+decide what to expect.  tests/app_fuzz.py writes the scripts run() takes; tests/test_app_fuzz_gpu.py runs them.
+
+What it keeps: the rest positions (the renderer's Model, never changed), the current positions, the registered skins and morph
+targets, MotionChecker's tracking bookkeeping (through PostChecker), the exposure state (test_expose_gpu.Checker), the frame
+size, whether a frame has been rendered at this size, the updates counted since the scene was set, and the packets submitted.
+
+The hierarchy is compared with a twin context built from the same model that is only ever given fovpt_update_vertices of the
+model's positions for the meshes just moved, with a rebuild at the same moments.  The build hands out node slots with atomic
+counters, so two builds of one model number their nodes differently, and now and then (one rebuild in a few hundred) they group
+the primitives differently: same_tree() compares the records always and canonical() forms, the tree with its boxes, leaves and
+records but without the numbering, where the two shapes agree.  Whatever the shape, every record and box must be a fixed point
+of refit_ref over the model's positions, and the link words a refit must not touch are compared on the context itself.
+
+dry_run() is the part of the model that needs no renderer: the positions.  (oracle.OracleScene exposes trace() and no tree,
+so there is no hierarchy for refit_ref to follow without a GPU.)"""
+import hashlib
+
+import numpy as np
+
+import packet_ref as pk
+import refit_ref as rf
+import transform_ref as tf
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
+
+from common import cfg_foveated, cfg_uniform, make_gpu
+from post_common import PostChecker
+from postprocess_common import bits
+from temporal_motion_common import debug_buffer, restate, vertex_arrays
+
+F = np.float32
+E_INVALID, E_NO_FRAME = -1, -5
+SEQUENCE0 = 7000                                         # packet k carries sequence SEQUENCE0 + k
+
+
+# ---- without a renderer ----------------------------------------------------------------------------------------------------
+def config_of(s):
+    """abi.Config of a script."""
+    c = s["config"]
+    p, m, f, u = c["spp"]
+    cfg = cfg_uniform(u, c["max_depth"]) if c["uniform"] else cfg_foveated(c["r_inner"], c["r_outer"], (p, m, f), c["max_depth"])
+    cfg.r_inner, cfg.r_outer = c["r_inner"], c["r_outer"]
+    cfg.write_guides = 1
+    cfg.frames_in_flight, cfg.chains_per_frame = c["frames_in_flight"], c["chains_per_frame"]
+    return cfg
+
+
+def updates_of(op):
+    """The updates an operation issues, in order: (update operation, where: "alone", "between" or "pre_chain")."""
+    if op["op"] == "update":
+        return [(op, "alone")]
+    if op["op"] == "frame":
+        out = [(b, "between") for b in op["between"] if b is not None and b["op"] == "update"]
+        return out + ([(op["pre_chain"], "pre_chain")] if op["pre_chain"] is not None else [])
+    return []
+
+
+def register(have, new):
+    for k, v in new.items():
+        if v is None:
+            have.pop(k, None)
+        else:
+            have[k] = v
+
+
+def dry_run(s, model):
+    """The positions a script leaves, through the three position restatements alone -> (V, 3) float32; every intermediate
+    position array is checked to be finite."""
+    _, vtx, _, first = vertex_arrays(model)
+    vtx = vtx.copy()
+    skins, morphs = dict(s["skins"]), dict(s["morphs"])
+    for op in s["ops"]:
+        if op["op"] == "set_skins":
+            register(skins, op["skins"])
+        elif op["op"] == "set_morphs":
+            register(morphs, op["morphs"])
+        elif op["op"] == "set_scene":
+            skins, morphs = {}, {}
+            vtx = vertex_arrays(model)[1].copy()
+        for u, _ in updates_of(op):
+            for k, v in restate(model, u["kind"], u["poses"], skins, morphs)[1].items():
+                assert np.isfinite(v).all(), (s["seed"], u["kind"], k)
+                vtx[first[k]:first[k + 1]] = v
+    return vtx
+
+
+# ---- the hierarchy without its numbering -----------------------------------------------------------------------------------
+def canonical(nodes, tris, shape_only=False):
+    """A digest of the wide tree that does not depend on how its nodes, child slots and records are numbered: an entry is its
+    box and, for a leaf, the sorted records it holds, for a node, the sorted digests of the child's live entries.  shape_only:
+    the grouping of the primitives alone, without boxes and vertices."""
+    nodes = np.asarray(nodes, np.uint32).reshape(-1, 4, 8)
+    ni, nf = nodes.view(np.int32), nodes.view(F)
+    tris = np.asarray(tris, np.uint32).reshape(-1, 12)
+
+    def node(i):
+        out = []
+        for k in range(4):
+            if not nf[i, k, 0] < np.inf:
+                continue
+            code = int(ni[i, k, 6])
+            if code < 0:
+                t0, n = rf.leaf_range(code)
+                body = b"".join(sorted(tris[t, 9:11].tobytes() if shape_only else tris[t].tobytes() for t in range(t0, t0 + n)))
+            else:
+                body = node(code)
+            out.append(hashlib.sha1((b"" if shape_only else nodes[i, k, :6].tobytes()) + body).digest())
+        return b"".join(sorted(out))
+    return node(0)
+
+
+def same_tree(a, b):
+    """Two contexts' hierarchies of the same positions.  Always: the same triangle records, whatever their order.  Two builds
+    of one scene usually choose the same tree and sometimes do not (the builder's parallel passes break ties by arrival), which
+    nothing specifies; where they did, every entry's box is the same too.  -> whether the shapes agree."""
+    (na, ta), (nb, tb) = a, b
+    ra, rb = (np.asarray(t, np.uint32).reshape(-1, 12)[:, :11] for t in (ta, tb))
+    assert ra.shape == rb.shape and np.array_equal(ra[np.lexsort(ra.T[::-1])], rb[np.lexsort(rb.T[::-1])]), "triangle records"
+    if canonical(na, ta, shape_only=True) != canonical(nb, tb, shape_only=True):
+        return False
+    assert canonical(na, ta) == canonical(nb, tb), "hierarchy"
+    return True
+
+
+def links(nodes):
+    """The words of the nodes a refit leaves alone: the code and rank of every child record."""
+    return np.asarray(nodes, np.uint32).reshape(-1, 4, 8)[:, :, 6:8].copy()
+
+
+def expected_cost(n):
+    levels = rf.levels_of(n)
+    return rf.sah_cost(n, levels), tf.cost_tolerance(tf.live_entries(n, levels))
+
+
+def hierarchy(r):
+    from test_refit_gpu import hierarchy as h
+    return h(r)
+
+
+# ---- the model ---------------------------------------------------------------------------------------------------------------
+class AppModel(PostChecker):
+    def __init__(self, oracle, s, model, cam, probe):
+        """s: a script of app_fuzz (its scene already made: model, cam), or any dict with size, config, post, skins, morphs."""
+        self.s, self.cam, self.probe, self.cfg_frame = s, dict(cam), probe, config_of(s)
+        self.size = tuple(s["size"])
+        r = make_gpu(model, probe, cam, self.size, self.cfg_frame)
+        super().__init__(oracle, r, cfg=s["post"])
+        self.twin = renderer.SampleRenderer(model)
+        self.rest = self.vtx.copy()
+        self.updates = 0                                  # fovpt_hierarchy_cost's counter
+        self.rendered = False                             # a frame exists at this size
+        self.packets = 0
+        from test_expose_gpu import Checker as ExposeChecker
+        self.ex = ExposeChecker(oracle, r)
+        self._bufs = []
+        self.log = []
+        self.fb = self.zero_frame()                       # the context's own frame buffers: zero after a resize
+        assert r.hierarchy_cost().updates == 0            # (switches the watching on)
+        self.tree_agrees = same_tree(hierarchy(r), hierarchy(self.twin))
+        self.log.append(("tree", self.tree_agrees))
+        if s["skins"]:
+            self.set_skins(s["skins"])
+        if s["morphs"]:
+            self.set_morphs(s["morphs"])
+
+    def close(self):
+        self.r.close()
+        self.twin.close()
+
+    def zero_frame(self):
+        w, h = self.size
+        return dict(frame=np.zeros((h, w), np.uint32), **{k: np.zeros((h, w, 4), F) for k in ("accum", "normal", "color", "albedo")})
+
+    # ---- positions and the tree
+    def current(self, meshes=None):
+        """{mesh: its current positions} of the meshes named (default: all that differ from rest)."""
+        if meshes is None:
+            meshes = [k for k in range(len(self.first) - 1) if not np.array_equal(bits(self.vtx[self.first[k]:self.first[k + 1]]), bits(self.rest[self.first[k]:self.first[k + 1]]))]
+        return {k: self.vtx[self.first[k]:self.first[k + 1]].copy() for k in meshes}
+
+    def scene_vertices(self):
+        p, n = debug_buffer(self.r, "scene_vertices")
+        return self.r.download(p, np.empty((n // 12, 3), F))
+
+    def check_scene(self, rebuilt=False, before=None):
+        """After an update (and everything enqueued): positions, previous positions of the marked meshes, the tree against the
+        twin's, the cost counters and the cost."""
+        r = self.r
+        # (the position buffer exists from a scene's first update on; before that, and so right after fovpt_set_scene, the
+        # positions are held through the triangle records below, which must be refit_ref's of the model's positions)
+        if self.updates:
+            assert np.array_equal(bits(self.scene_vertices()), bits(self.vtx)), "scene_vertices"
+        if self.tracking and self.moved.any():
+            p, n = debug_buffer(r, "scene_vertices_prev")
+            prev = r.download(p, np.empty((n // 12, 3), F))
+            for k in np.flatnonzero(self.moved):
+                a, b = self.first[k], self.first[k + 1]
+                assert np.array_equal(bits(prev[a:b]), bits(self.vtx_step[a:b])), "previous positions of mesh %d" % k
+        n, t = hierarchy(r)
+        agrees = same_tree((n, t), hierarchy(self.twin))
+        if not rebuilt:                                       # a refit changes no shape: what agreed before still does
+            assert agrees == self.tree_agrees, "the shapes of the two trees %s after a refit" % ("differ" if self.tree_agrees else "agree")
+        self.tree_agrees = agrees
+        self.log.append(("tree", agrees))
+        levels = rf.levels_of(n)
+        wn, wt = rf.refit(n, t, levels, self.tri_vidx, self.vtx)          # every record and box is the restatement's of the
+        assert np.array_equal(wt, t), "records against refit_ref"         # model's positions: refitting changes nothing
+        assert np.array_equal(wn, n), "boxes against refit_ref"
+        if rebuilt:
+            rf.check_conservative(n, t, levels)
+        elif before is not None:
+            assert np.array_equal(links(n), before), "a refit changed the tree's links"
+        c = r.hierarchy_cost(wait=True)
+        assert (c.updates, c.measured) == (self.updates, self.updates), (c.updates, c.measured, self.updates)
+        want, tol = expected_cost(n)
+        assert abs(c.current - want) <= tol * want, (c.current, want)
+        if rebuilt or self.updates == 0:
+            assert c.built == c.current
+
+    def update(self, poses, rebuild=False, device=False, kind="vertices", check=True):
+        before = links(hierarchy(self.r)[0]) if check and not rebuild else None
+        super().update(poses, rebuild=rebuild, device=device, kind=kind)
+        self.twin.update_vertices(self.current(sorted(poses)), rebuild=rebuild)
+        if poses or rebuild:
+            self.updates += 1
+        if check:
+            self.check_scene(rebuild, before)
+
+    def refused(self, op, check=True):
+        r = self.r
+        if op["which"] == "no_frame":                         # straight after a resize: nothing of the chain has a frame to work on
+            assert not self.rendered
+            for call in op["calls"]:
+                with_pytest_code(op["code"], dict(post=r.post, expose=r.expose, packet=lambda: r.submitPacket(1))[call])
+            return
+        with_pytest_code(op["code"], lambda: self.refused_call(op))
+        if check:
+            self.check_scene()
+
+    def refused_call(self, op):
+        r = self.r
+        give = restate_refused(r.model, op, self.skins, self.morphs)
+        getattr(r, dict(vertices="update_vertices", transforms="update_transforms", skinned="update_skinned", morphed="update_morphed")[op["kind"]])(give)
+
+    # ---- registration
+    def set_skins(self, new):
+        self.r.set_skins(new)
+        register(self.skins, new)
+        if self.updates:
+            assert np.array_equal(bits(self.scene_vertices()), bits(self.vtx)), "set_skins moved geometry"
+
+    def set_morphs(self, new):
+        self.r.set_morphs(new)
+        register(self.morphs, new)
+        if self.updates:
+            assert np.array_equal(bits(self.scene_vertices()), bits(self.vtx)), "set_morphs moved geometry"
+
+    # ---- frames
+    def view(self, v):
+        r, (w, h) = self.r, self.size
+        eye = tuple(float(x) for x in (np.array(self.cam["eye"], np.float64) * (1.0 + np.array(v["eye"]))).astype(F))
+        cam = dict(self.cam, eye=eye)
+        r.setCamera(renderer.Camera(cam["eye"], cam["lookat"], cam["up"], cam["fovy"], w / float(h)))
+        f = r.launchParams.frame
+        f.c.x, f.c.y = v["gaze"][0] & 0xffffffff, v["gaze"][1] & 0xffffffff
+        f.subframe_index = v["subframe_index"]
+        return cam
+
+    def frames(self, op):
+        """The frames of one group, each compared with the oracle's frame of the positions at issue time."""
+        import torch
+        from test_refit_gpu import moved
+        r, (w, h) = self.r, self.size
+        f = r.launchParams.frame
+        n = len(op["views"])
+        r.synchronize()
+        r.reset_stats()
+        issued = []
+        for k, v in enumerate(op["views"]):
+            cam = self.view(v)
+            if n > 1:
+                b = (torch.zeros((h, w, 4), dtype=torch.float32, device="cuda"), torch.zeros((h, w), dtype=torch.int32, device="cuda"))
+                torch.cuda.synchronize()
+                f.accum_buffer, f.frame_buffer = b[0].data_ptr(), b[1].data_ptr()
+            else:
+                b = None
+                f.accum_buffer, f.frame_buffer = r._frame_ptrs.accum_buffer, r._frame_ptrs.frame_buffer
+            if op["sync"]:
+                r.render()
+            else:
+                r.render_async()
+            issued.append((cam, (f.c.x, f.c.y), v["subframe_index"], self.current(), b))
+            if k + 1 < n and op["between"][k] is not None:
+                u = op["between"][k]
+                if u["op"] == "update":
+                    self.update(u["poses"], u["rebuild"], u["device"], u["kind"], check=False)
+                else:
+                    self.refused(u, check=False)
+        r.synchronize()
+        self._bufs = [x[4] for x in issued]
+        paths = rad = shadow = 0
+        for k, (cam, gaze, sub, pos, b) in enumerate(issued):
+            # the buffers a frame is resolved into keep what no pass of it writes: the context's own from the frames before
+            # (zero after a resize), a caller's buffers here zero; the guides are always the context's own
+            S = self.oracle.OracleScene(moved(r.model, pos))
+            Fr = self.oracle.OracleFrame(w, h, self.oracle.HostProbe(self.probe), cam, gaze=gaze, subframe_index=sub)
+            for name in ("normal", "color", "albedo") + (("accum", "frame") if b is None else ()):
+                getattr(Fr, name)[...] = self.fb[name]
+            cnt = self.oracle.render(S, Fr, self.cfg_frame, nthreads=16)
+            for name in ("normal", "color", "albedo") + (("accum", "frame") if b is None else ()):
+                self.fb[name] = getattr(Fr, name).copy()
+            acc = r.downloadAccum() if b is None else b[0].cpu().numpy()
+            px = r.downloadPixels() if b is None else b[1].cpu().numpy().view(np.uint32)
+            assert np.array_equal(bits(acc), bits(Fr.accum)), "frame %d of %d: accum, %d pixels" % (k, n, (bits(acc) != bits(Fr.accum)).any(axis=-1).sum())
+            assert np.array_equal(px, Fr.frame), "frame %d of %d: rgba8" % (k, n)
+            paths, rad, shadow = paths + cnt[2], rad + cnt.lib_radiance, shadow + cnt.lib_shadow
+        st = r.stats()
+        assert (st.paths, st.radiance_rays, st.shadow_rays) == (paths, rad, shadow), ((st.paths, st.radiance_rays, st.shadow_rays), (paths, rad, shadow))
+        for name in ("normal", "albedo", "color"):            # the guides after the last frame issued
+            g = r.download(getattr(f, name + "_buffer"), np.empty((h, w, 4), F))
+            assert np.array_equal(bits(g), bits(self.fb[name])), name
+        self.rendered = True
+        self.last_rgba = px
+        self.frame_as_rendered = ((w, h), issued[-1][1], (self.cfg_frame.r_inner, self.cfg_frame.r_outer), bool(self.cfg_frame.uniform))
+        self.gaze_rendered = issued[-1][1]
+        if any(b is not None and b["op"] == "update" for b in op["between"]):
+            self.check_scene(rebuilt=any(b is not None and b["op"] == "update" and b["rebuild"] for b in op["between"]))                               # what the updates between the frames left, now that all has run
+
+    def chain(self, c, moved_on=None):
+        """The post chain of the frame rendered last.  moved_on: the caller's next gaze and subframe index, written into the
+        launch parameters first: every stage works on the frame as it was rendered all the same."""
+        r = self.r
+        if moved_on is not None:
+            f = r.launchParams.frame
+            f.c.x, f.c.y = moved_on["gaze"][0] & 0xffffffff, moved_on["gaze"][1] & 0xffffffff
+            f.subframe_index = moved_on["subframe_index"]
+        color = ptr = None                                    # the colour the next stage is given: numpy, device pointer
+        rgba, rgba_ptr = self.last_rgba, None if not self._bufs or self._bufs[-1] is None else self._bufs[-1][1].data_ptr()
+        if c["post"] is not None:
+            had = self.prev is not None
+            out = self.step(stages=c["post"])
+            color, ptr = out["color"], r.post_buffers()[0]
+            rgba, rgba_ptr = r.downloadPostPixels(), r.post_buffers()[1]
+            self.log.append(("post", c["post"], had))
+        if c["expose"] is not None:
+            before = dict(self.ex.state)
+            out = self.expose(c["expose"], r.downloadAccum() if color is None else color, ptr)
+            rgba, rgba_ptr = out["rgba"], r.expose_buffers()[1]
+            self.log.append(("expose", before["steps"], self.ex.state["steps"]))
+        if c["packet"]:
+            self.packet(rgba, rgba_ptr)
+
+    def expose(self, d, inp, in_ptr):
+        """test_expose_gpu.Checker.step with the frame as rendered where that reads the launch parameters."""
+        import expose_ref as ex
+        import reconstruct_ref as rr
+        from test_expose_gpu import ecfg, histogram, same_state, usable
+        r, ck = self.r, self.ex
+        c, full = ecfg(d)
+        r.expose(c, in_ptr)
+        got_c, got_px = r.downloadExposedColor(), r.downloadExposedPixels()
+        (w, h), gaze, (ri, ro), uniform = self.frame_as_rendered
+        fill, uni = (rr.writers(w, h, gaze, ri, ro, int(uniform))[0], int(uniform)) if full["metering"] == ex.GAZE and full["mode"] == ex.AUTO else (None, 0)
+        want_c, want_px, want_h, ck.state = ex.expose(self.oracle, inp, full, ck.state, fill, uni)
+        if want_h is not None:
+            assert np.array_equal(histogram(r), want_h), "expose: histogram"
+        if ck.state["steps"]:
+            same_state(r.expose_state(), ck.state, "expose")
+        ok = usable(inp)
+        assert np.array_equal(bits(got_c[ok]), bits(want_c[ok])), "expose: colour"
+        assert np.array_equal(got_px[ok], want_px[ok]), "expose: rgba8"
+        return dict(color=got_c, rgba=got_px)
+
+    def packet(self, rgba, rgba_ptr):
+        import torch
+        from packet_cases import junk_canvas
+        from test_packet_gpu import decode_on_device, host_decode
+        r, seq = self.r, SEQUENCE0 + self.packets
+        want = pk.encode(rgba, *self.frame_as_rendered, sequence=seq)
+        if not pk.check(want):                                # (a pass without a launch index: a frame side below 4, say)
+            with_pytest_code(E_INVALID, lambda: r.submitPacket(seq, rgba_ptr))
+            self.log.append(("packet", None))
+            return
+        slot = r.submitPacket(seq, rgba_ptr)
+        assert slot == self.packets % abi.PACKET_SLOTS       # slots in submit order, over resizes and scene reloads too
+        self.packets += 1
+        got = r.waitPacket(slot)
+        assert got == want, "packet %d" % seq
+        self.log.append(("packet", slot))
+        h = abi.PacketHeader.from_packet(got)
+        dev = torch.frombuffer(bytearray(got), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        for mode in (abi.PACKET_NEAREST, abi.PACKET_SMOOTH):
+            ref = pk.decode(got, mode, junk_canvas(self.size))
+            assert np.array_equal(decode_on_device(r, dev, h, mode), ref), mode
+            assert np.array_equal(host_decode(got, mode, self.size), ref), mode
+
+    # ---- context events
+    def resize(self, size):
+        r = self.r
+        state = bytes(r.expose_state())
+        r.resize(size)
+        self.size = tuple(size)
+        self.rendered, self.prev = False, None               # the frame as rendered and the temporal history go
+        self._bufs = []
+        self.fb = self.zero_frame()
+        f = r.launchParams.frame
+        w, h = self.size
+        assert not r.download(f.frame_buffer, np.empty((h, w), np.uint32)).any()
+        for name in ("accum", "normal", "color", "albedo"):
+            assert not r.download(getattr(f, name + "_buffer"), np.empty((h, w, 4), F)).view(np.uint32).any(), name
+        if self.updates:                                      # positions stay (skins, morphs and tracking: the next pose and step show)
+            assert np.array_equal(bits(self.scene_vertices()), bits(self.vtx))
+        assert bytes(r.expose_state()) == state              # the exposure state stays
+        if self.ex.state["steps"]:
+            from test_expose_gpu import same_state
+            same_state(r.expose_state(), self.ex.state, "after a resize")
+
+    def set_scene(self):
+        from test_temporal_gpu import _scene_again
+        r = self.r
+        _scene_again(r)
+        _scene_again(self.twin)
+        self.vtx, self.vtx_step = self.rest.copy(), self.rest.copy()
+        self.moved[:] = False
+        self.prev, self.tracking, self.untracked = None, False, False
+        self.skins.clear()
+        self.morphs.clear()
+        self.updates = 0
+        self.ex.reset()
+        for call in (lambda: r.update_skinned({0: np.stack([tf.IDENTITY])}), lambda: r.update_morphed({0: np.zeros(1, F)})):
+            with_pytest_code(E_INVALID, call)                 # refused until a skin or morph is set again
+        with_pytest_code(E_INVALID, lambda: debug_buffer(r, "scene_vertices_prev"))     # tracking is off: its buffers are gone
+        assert r.expose_state().steps == 0                    # a fresh exposure state
+        c = r.hierarchy_cost()
+        assert (c.updates, c.measured) == (0, 0) and c.built == c.current
+        self.check_scene(rebuilt=True)                        # the tree is the twin's, of the rest positions
+
+    # ---- a script
+    def run_op(self, op):
+        kind = op["op"]
+        if kind == "update":
+            self.update(op["poses"], op["rebuild"], op["device"], op["kind"])
+        elif kind == "set_skins":
+            self.set_skins(op["skins"])
+        elif kind == "set_morphs":
+            self.set_morphs(op["morphs"])
+        elif kind == "frame":
+            self.frames(op)
+            if op["pre_chain"] is not None:
+                u = op["pre_chain"]
+                self.update(u["poses"], u["rebuild"], u["device"], u["kind"])
+            self.chain(op["chain"], op.get("moved_on"))
+        elif kind == "resize":
+            self.resize(op["size"])
+        elif kind == "set_scene":
+            self.set_scene()
+        elif kind == "temporal_reset":
+            self.r.temporal_reset()
+            self.reset()
+        elif kind == "expose_reset":
+            self.r.expose_reset()
+            self.ex.reset()
+        else:
+            assert kind == "refused", kind
+            self.refused(op)
+
+    def run(self):
+        for k, op in enumerate(self.s["ops"]):
+            try:
+                self.run_op(op)
+            except Exception as e:
+                raise AssertionError("seed %s, operation %d (%s): %s: %s" % (self.s.get("seed"), k, op["op"], type(e).__name__, e)) from e
+
+
+def restate_refused(model, op, skins, morphs):
+    """What a refused update is given: the poses as drawn, those of meshes that do not exist or have no skin included."""
+    ok = {k: v for k, v in op["poses"].items() if 0 <= k < len(model.meshes) and (op["kind"] != "skinned" or k in skins)}
+    give, _ = restate(model, op["kind"], ok, skins, morphs)
+    for k, v in op["poses"].items():
+        if k not in ok:
+            give[k] = v
+    return give
+
+
+def with_pytest_code(code, call):
+    """call() raises lib.FovptError with that code."""
+    try:
+        call()
+    except lib.FovptError as e:
+        assert e.code == code, (e.code, code, str(e))
+        return
+    raise AssertionError("a call that must be refused with %d was accepted" % code)

@@ -72,11 +72,11 @@ def same(a, b, stages, label, motion=True, stepped=None, a_posts=False):
     return cb
 
 
-def rendered_frame(r, inp, gb, uv):
+def rendered_frame(r, inp, gb, uv, gaze=None):
     """post_ref's description of the frame r rendered last, from the GPU's own buffers (r.launchParams and r.config as they
-    were at render time)."""
+    were at render time; gaze: the rendered frame's, where the caller has written the next one into r.launchParams since)."""
     f, cfg = r.launchParams.frame, r.config
-    fill, pas, ax, ay = rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)
+    fill, pas, ax, ay = rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y) if gaze is None else gaze, cfg.r_inner, cfg.r_outer, cfg.uniform)
     color, normal, albedo = guides(r) if cfg.write_guides else (None, None, None)
     return dict(inp=inp, color=color, normal=normal, albedo=albedo, gb=gb, uv=uv, fill=fill, pas=pas, ax=ax, ay=ay,
                 uniform=cfg.uniform, cam=camera(r))
@@ -88,11 +88,12 @@ class PostChecker(MotionChecker):
 
     def __init__(self, oracle, r, stages=po.DEFAULT_STAGES, cfg=None):
         self.stages, self.cfg = stages, dict(cfg or {})
+        self.gaze_rendered = None                                # set where r.launchParams no longer hold the rendered frame's gaze
         super().__init__(oracle, r, self.cfg.get("temporal"))
 
     def step(self, inp=None, in_ptr=None, out=None, with_motion=True, stages=None):
         """r.post() on the frame just rendered.  inp: the colour input as numpy (None: the accum buffer); out: None (the
-        renderer's own buffers) or (colour, rgba) device pointers.  -> dict(color, history, motion, fill)"""
+        renderer's own buffers) or (colour, rgba) device pointers.  -> dict(color, history, motion, fill, gb, frame)"""
         r, st = self.r, self.stages if stages is None else stages
         inp = r.downloadAccum() if inp is None else inp
         mo_ptr = r.motion_buffer() if st & M and with_motion else None
@@ -108,7 +109,7 @@ class PostChecker(MotionChecker):
         got_d = r.downloadDenoisedColor() if st & D and st & (R | T) else None
         gb = r.downloadGBuffer()                                  # (the same rays as the step's own trace)
         uv = download_hits(r)[..., 1:3]
-        frame = rendered_frame(r, inp, gb, uv)
+        frame = rendered_frame(r, inp, gb, uv, self.gaze_rendered)
         if st & M:
             if self.untracked:
                 self.prev = None
@@ -128,4 +129,4 @@ class PostChecker(MotionChecker):
             self.prev = dict(gb=gb, cam=frame["cam"], history=got_h)
             self.vtx_step = self.vtx.copy()
             self.moved[:] = False
-        return dict(color=got_c, history=got_h, motion=got_m, fill=frame["fill"], gb=gb)
+        return dict(color=got_c, history=got_h, motion=got_m, fill=frame["fill"], gb=gb, frame=frame)

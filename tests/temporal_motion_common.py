@@ -8,11 +8,17 @@ import ctypes as C
 
 import numpy as np
 
+import morph_ref as mr
+import skin_ref as sk
 import temporal_motion_ref as tm
 import temporal_ref as tr
+import transform_ref as tf
 
 from postprocess_common import bits
 from temporal_common import camera, cap_map, tcfg
+
+KINDS = ("vertices", "transforms", "skinned", "morphed")
+METHODS = dict(vertices="update_vertices", transforms="update_transforms", skinned="update_skinned", morphed="update_morphed")
 
 
 def vertex_arrays(model):
@@ -42,6 +48,26 @@ def download_hits(r):
     return r.download(p, np.empty((f.size.y, f.size.x, 4), np.float32))
 
 
+def restate(model, kind, updates, skins=None, morphs=None):
+    """One update of `kind` (KINDS) restated -> (what the renderer's method of that kind is given, {mesh: new positions}).
+    updates maps a mesh to its vertices, its matrix, its palette, or its weights / (weights, palette); the new positions are
+    transform_ref's, skin_ref's and morph_ref's over the model's rest positions and the registered skins and morphs."""
+    if kind == "vertices":
+        give = ups = {k: np.ascontiguousarray(v, np.float32) for k, v in updates.items()}
+    elif kind == "transforms":
+        give = {k: tf.matrix(m) for k, m in updates.items()}
+        ups = tf.restate(model, give)
+    elif kind == "skinned":
+        give = {k: np.ascontiguousarray(sk.palette(p).reshape(-1, 3, 4)) for k, p in updates.items()}
+        ups = sk.restate(model, skins, give)
+    else:
+        assert kind == "morphed", kind
+        give = {k: ((np.ascontiguousarray(p[0], np.float32), np.ascontiguousarray(sk.palette(p[1]).reshape(-1, 3, 4))) if isinstance(p, tuple)
+                    else np.ascontiguousarray(p, np.float32)) for k, p in updates.items()}
+        ups = mr.restate(model, morphs, give, skins)
+    return give, ups
+
+
 class MotionChecker:
     """Follows one renderer's updates and temporal steps.  update() moves meshes and remembers it; step() runs
     fovpt_temporal_motion (or, plain=True, fovpt_temporal) and compares colour, rgba8, history and motion vectors with the
@@ -58,19 +84,25 @@ class MotionChecker:
         self.prev = None
         self.tracking = self.untracked = False
         self._keep = None
+        self.skins, self.morphs = {}, {}                    # what update(kind="skinned" / "morphed") restates over
 
     def reset(self):
         self.prev = None
 
-    def update(self, updates, rebuild=False, device=False):
-        ups = {k: np.ascontiguousarray(v, np.float32) for k, v in updates.items()}
+    def update(self, updates, rebuild=False, device=False, kind="vertices"):
+        """Moves meshes through the entry point of `kind` (KINDS): updates maps a mesh to what the renderer's method of that kind
+        takes for it.  The positions the checker goes on with are restate()'s over self.skins / self.morphs, which the caller
+        keeps equal to what it registered.  device: as CUDA tensors (not for transforms, which have no such form)."""
+        give, ups = restate(self.r.model, kind, updates, self.skins, self.morphs)
         if device:
             import torch
-            self._keep = dev = {k: torch.from_numpy(v).cuda() for k, v in ups.items()}
+            assert kind != "transforms"
+
+            def dev(x):
+                return tuple(dev(y) for y in x) if isinstance(x, tuple) else torch.from_numpy(x).cuda()
+            self._keep = give = {k: dev(v) for k, v in give.items()}
             torch.cuda.synchronize()
-            self.r.update_vertices(dev, rebuild=rebuild)
-        else:
-            self.r.update_vertices(ups, rebuild=rebuild)
+        getattr(self.r, METHODS[kind])(give, rebuild=rebuild)
         for k, v in ups.items():
             self.vtx[self.first[k]:self.first[k + 1]] = v
             self.moved[k] = True
