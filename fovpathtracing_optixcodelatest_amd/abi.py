@@ -149,6 +149,8 @@ class MeshTransform(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("m", C.c_float * 12)]
 
 
+DEBUG_PROBE_PLAIN = 1                           # fovpt_debug_probe_sample / _probe_eval flag (FOVPT_DEBUG_PROBE_PLAIN)
+PROBE_PATH_GUIDED, PROBE_PATH_RECORDS, PROBE_PATH_ONE_ROW = 1, 2, 4   # their *path_out bits (FOVPT_PROBE_PATH_*)
 COST_WAIT = 1                                   # fovpt_hierarchy_cost flag (FOVPT_COST_WAIT)
 
 

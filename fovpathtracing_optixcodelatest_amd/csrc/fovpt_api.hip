@@ -274,6 +274,25 @@ int run_passes(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passe
     return run_job(c, lp, full, npass, 0, whole_frame);
 }
 
+// How a launch searches and reads the caller's probe: the guide tables, the packed records and the one-row layout belong to the
+// probe this context uploaded.  One function for run_job and for the debug entry points, so that a test sees the path a frame takes.
+struct ProbePath { const uint32_t *guide_x, *guide_y; const float4* rec; int32_t row_mul; };
+ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe)
+{
+    ProbePath pp;
+    // the guide tables belong to the probe this context uploaded; a caller-supplied foreign probe is searched plainly
+    const bool own_probe = c->guide_ok && probe.cdfValuesX == (float*)c->pr_cdfx.p && probe.cdfValuesY == (float*)c->pr_cdfy.p
+                           && probe.width == c->guide_w && probe.height == c->guide_h;
+    pp.guide_x = own_probe ? (const uint32_t*)c->pr_guidex.p : nullptr;
+    pp.guide_y = own_probe ? (const uint32_t*)c->pr_guidey.p : nullptr;
+    // (a probe whose rows are all alike is served from ONE row of the split arrays, which stays in L1; its 32-byte records would not)
+    pp.rec = (own_probe && !c->rows_identical && probe.data == (fovpt_float4*)c->pr_data.p && probe.pdfValuesX == (float*)c->pr_pdfx.p)
+             ? (const float4*)c->pr_rec.p : nullptr;
+    pp.row_mul = (c->rows_identical && probe.data == (fovpt_float4*)c->pr_data.p && probe.pdfValuesX == (float*)c->pr_pdfx.p
+                  && probe.cdfValuesX == (float*)c->pr_cdfx.p && probe.width == c->guide_w && probe.height == c->guide_h) ? 0 : 1;
+    return pp;
+}
+
 // One wavefront job: generate -> (closest, shade, occlusion) x depth -> resolve over the given passes / row ranges.
 int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame)
 {
@@ -296,16 +315,8 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     fd.cx = lp->frame.c.x; fd.cy = lp->frame.c.y;
     set_camera(fd, lp);
     fd.probe = lp->probe;
-    // the guide tables belong to the probe this context uploaded; a caller-supplied foreign probe is searched plainly
-    const bool own_probe = c->guide_ok && lp->probe.cdfValuesX == (float*)c->pr_cdfx.p && lp->probe.cdfValuesY == (float*)c->pr_cdfy.p
-                           && lp->probe.width == c->guide_w && lp->probe.height == c->guide_h;
-    fd.guide_x = own_probe ? (const uint32_t*)c->pr_guidex.p : nullptr;
-    fd.guide_y = own_probe ? (const uint32_t*)c->pr_guidey.p : nullptr;
-    // (a probe whose rows are all alike is served from ONE row of the split arrays, which stays in L1; its 32-byte records would not)
-    fd.probe_rec = (own_probe && !c->rows_identical && lp->probe.data == (fovpt_float4*)c->pr_data.p && lp->probe.pdfValuesX == (float*)c->pr_pdfx.p)
-                   ? (const float4*)c->pr_rec.p : nullptr;
-    fd.probe_row_mul = (c->rows_identical && lp->probe.data == (fovpt_float4*)c->pr_data.p && lp->probe.pdfValuesX == (float*)c->pr_pdfx.p
-                        && lp->probe.cdfValuesX == (float*)c->pr_cdfx.p && lp->probe.width == c->guide_w && lp->probe.height == c->guide_h) ? 0 : 1;
+    const ProbePath pp = probe_path(c, lp->probe);
+    fd.guide_x = pp.guide_x; fd.guide_y = pp.guide_y; fd.probe_rec = pp.rec; fd.probe_row_mul = pp.row_mul;
     fd.accum = lp->frame.accum_buffer;
     fd.accum_prev = (chunked && c->use_accum_before) ? (const fovpt_float4*)c->accum_before.p : lp->frame.accum_buffer;
     fd.frame = lp->frame.frame_buffer;
@@ -1843,6 +1854,105 @@ int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* d
             occluded_out[i] = v == 2.f ? 1 : 0;
         }
     }
+    return FOVPT_OK;
+}
+
+// test hooks: the device functions of a shaded hit on chosen inputs (shade_debug.hip), so that ProbeSample, ProbeEval, the
+// Disney BSDF and tex2D can be compared with the oracle input by input, not only through frames.  The probe entry points take
+// the caller's fovpt_probe the way a launch does and search it the way a launch would (probe_path).
+static int debug_probe_args(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const void* in, const char* who)
+{
+    if (!c || !probe || n < 0 || (flags & ~FOVPT_DEBUG_PROBE_PLAIN) || (n && !in)) return FOVPT_E_INVALID;
+    if (!probe->data || !probe->cdfValuesX || !probe->cdfValuesY || !probe->pdfValuesX || !probe->pdfValuesY || probe->width <= 0 || probe->height <= 0)
+        return fail(c, FOVPT_E_NO_PROBE, "%s with an incomplete probe", who);
+    return FOVPT_OK;
+}
+static ProbePath debug_probe_path(const fovpt_ctx* c, const fovpt_probe& probe, int flags, int* path_out)
+{
+    ProbePath pp = probe_path(c, probe);
+    if (flags & FOVPT_DEBUG_PROBE_PLAIN) { pp.guide_x = pp.guide_y = nullptr; pp.rec = nullptr; pp.row_mul = 1; }
+    if (path_out) *path_out = (pp.guide_x ? FOVPT_PROBE_PATH_GUIDED : 0) | (pp.rec ? FOVPT_PROBE_PATH_RECORDS : 0) | (pp.row_mul == 0 ? FOVPT_PROBE_PATH_ONE_ROW : 0);
+    return pp;
+}
+
+int fovpt_debug_probe_sample(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const float* r12, int32_t* rowcol_out2, float* out7, int* path_out)
+{
+    { const int rc_ = debug_probe_args(c, probe, flags, n, r12, "fovpt_debug_probe_sample"); if (rc_) return rc_; }
+    // Randf's range (maths.h:199-210): what the searches may be handed
+    for (size_t i = 0; i < 2 * (size_t)n; i++)
+        if (!(r12[i] >= 0.0f && r12[i] <= 0.999999f)) return fail(c, FOVPT_E_INVALID, "fovpt_debug_probe_sample: number %zu (%g) is outside [0, 0.999999]", i, (double)r12[i]);
+    const ProbePath pp = debug_probe_path(c, *probe, flags, path_out);
+    if (n == 0) return FOVPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    DevBuf in, rowcol, out;
+    HIPCHK(c, in.reserve((size_t)n * 8)); HIPCHK(c, rowcol.reserve((size_t)n * 8)); HIPCHK(c, out.reserve((size_t)n * 28));
+    HIPCHK(c, hipMemcpy(in.p, r12, (size_t)n * 8, hipMemcpyHostToDevice));
+    fovpt_launch_debug_probe_sample(c->stream, *probe, pp.guide_x, pp.guide_y, pp.rec, pp.row_mul, n, (const float2*)in.p, (int2*)rowcol.p, (float*)out.p);
+    HIPCHK(c, hipGetLastError());
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    if (rowcol_out2) HIPCHK(c, hipMemcpy(rowcol_out2, rowcol.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (out7) HIPCHK(c, hipMemcpy(out7, out.p, (size_t)n * 28, hipMemcpyDeviceToHost));
+    return FOVPT_OK;
+}
+
+int fovpt_debug_probe_eval(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const float* dirs3, float* out6, int* path_out)
+{
+    { const int rc_ = debug_probe_args(c, probe, flags, n, dirs3, "fovpt_debug_probe_eval"); if (rc_) return rc_; }
+    const ProbePath pp = debug_probe_path(c, *probe, flags, path_out);
+    if (n == 0) return FOVPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    DevBuf in, out;
+    HIPCHK(c, in.reserve((size_t)n * 12)); HIPCHK(c, out.reserve((size_t)n * 24));
+    HIPCHK(c, hipMemcpy(in.p, dirs3, (size_t)n * 12, hipMemcpyHostToDevice));
+    fovpt_launch_debug_probe_eval(c->stream, *probe, pp.row_mul, n, (const float*)in.p, (float*)out.p);
+    HIPCHK(c, hipGetLastError());
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    if (out6) HIPCHK(c, hipMemcpy(out6, out.p, (size_t)n * 24, hipMemcpyDeviceToHost));
+    return FOVPT_OK;
+}
+
+int fovpt_debug_bsdf(fovpt_ctx* c, const fovpt_material* material, int n, const float* N3, const float* view3, const float* albedo3, const float* etaI,
+                     const float* etaO, const int32_t* seeds, const float* L_given3, float* out14)
+{
+    if (!c || !material || n < 0 || (n && (!N3 || !view3 || !albedo3 || !etaI || !etaO || !seeds || !L_given3))) return FOVPT_E_INVALID;
+    if (n == 0) return FOVPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    std::vector<float> rows((size_t)n * 16, 0.f), res((size_t)n * 16);
+    for (int i = 0; i < n; i++) {
+        float* r = &rows[16 * (size_t)i];
+        for (int k = 0; k < 3; k++) { r[k] = N3[3 * (size_t)i + k]; r[3 + k] = view3[3 * (size_t)i + k]; r[6 + k] = albedo3[3 * (size_t)i + k]; r[12 + k] = L_given3[3 * (size_t)i + k]; }
+        r[9] = etaI[i]; r[10] = etaO[i];
+        memcpy(&r[11], &seeds[i], 4);
+    }
+    DevBuf in, out;
+    HIPCHK(c, in.reserve((size_t)n * 64)); HIPCHK(c, out.reserve((size_t)n * 64));
+    HIPCHK(c, hipMemcpy(in.p, rows.data(), (size_t)n * 64, hipMemcpyHostToDevice));
+    fovpt_launch_debug_bsdf(c->stream, *material, n, (const float*)in.p, (float*)out.p);
+    HIPCHK(c, hipGetLastError());
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    HIPCHK(c, hipMemcpy(res.data(), out.p, (size_t)n * 64, hipMemcpyDeviceToHost));
+    if (out14) for (int i = 0; i < n; i++) memcpy(out14 + 14 * (size_t)i, &res[16 * (size_t)i], 56);
+    return FOVPT_OK;
+}
+
+int fovpt_debug_tex2d(fovpt_ctx* c, int texture, int n, const float* uv2, float* rgba_out4)
+{
+    if (!c || n < 0 || (n && !uv2)) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_tex2d without a scene");
+    if (texture < 0 || (size_t)texture >= c->tex_pixels.size()) return fail(c, FOVPT_E_INVALID, "fovpt_debug_tex2d: texture %d of %zu", texture, c->tex_pixels.size());
+    if (n == 0) return FOVPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    DevBuf in, out;
+    HIPCHK(c, in.reserve((size_t)n * 8)); HIPCHK(c, out.reserve((size_t)n * 16));
+    HIPCHK(c, hipMemcpy(in.p, uv2, (size_t)n * 8, hipMemcpyHostToDevice));
+    fovpt_launch_debug_tex2d(c->stream, (const TexDev*)c->textures.p, texture, n, (const float2*)in.p, (float4*)out.p);
+    HIPCHK(c, hipGetLastError());
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    if (rgba_out4) HIPCHK(c, hipMemcpy(rgba_out4, out.p, (size_t)n * 16, hipMemcpyDeviceToHost));
     return FOVPT_OK;
 }
 

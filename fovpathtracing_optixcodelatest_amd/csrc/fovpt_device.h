@@ -383,3 +383,9 @@ void fovpt_launch_build_guide(hipStream_t st, const float* cdf, int n, int segme
 void fovpt_launch_probe_records(hipStream_t st, size_t n, const float* cdfX, const float* pdfX, const float4* data, float4* rec);
 void fovpt_launch_build_cdf(hipStream_t st, int w, int h, const float4* data, float* pdfX, float* cdfX, float* pdfY, float* cdfY, float* row_total);
 void fovpt_launch_math(hipStream_t st, int op, const float* a, const float* b, float* out, size_t n);
+// shade_debug.hip: the device functions of a shaded hit (fovpt_shade_fn.h, tex2d) on n chosen inputs, one thread each
+void fovpt_launch_debug_probe_sample(hipStream_t st, const fovpt_probe& pr, const uint32_t* guide_x, const uint32_t* guide_y, const float4* rec, int row_mul,
+                                     int n, const float2* r12, int2* rowcol, float* out7);
+void fovpt_launch_debug_probe_eval(hipStream_t st, const fovpt_probe& pr, int row_mul, int n, const float* dir3, float* out6);
+void fovpt_launch_debug_bsdf(hipStream_t st, const fovpt_material& mat, int n, const float* in16, float* out16);
+void fovpt_launch_debug_tex2d(hipStream_t st, const TexDev* textures, int texture, int n, const float2* uv, float4* out);

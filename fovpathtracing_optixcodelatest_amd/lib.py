@@ -17,6 +17,7 @@ EXPORTS = [
     "fovpt_resize", "fovpt_get_config", "fovpt_set_config", "fovpt_launch", "fovpt_render",
     "fovpt_synchronize", "fovpt_download", "fovpt_get_stats", "fovpt_reset_stats", "fovpt_stream",
     "fovpt_probe_build_cdf", "fovpt_camera_uvw", "fovpt_debug_math", "fovpt_debug_buffer", "fovpt_debug_trace",
+    "fovpt_debug_probe_sample", "fovpt_debug_probe_eval", "fovpt_debug_bsdf", "fovpt_debug_tex2d",
     "fovpt_gather_plan", "fovpt_gather_pack", "fovpt_gather_unpack",
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
@@ -203,6 +204,10 @@ def load():
     L.fovpt_debug_math.argtypes = [vp, i32, vp, vp, vp, sz]
     L.fovpt_debug_buffer.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(sz)]
     L.fovpt_debug_trace.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.fovpt_debug_probe_sample.argtypes = [vp, C.POINTER(abi.Probe), i32, i32, vp, vp, vp, C.POINTER(i32)]
+    L.fovpt_debug_probe_eval.argtypes = [vp, C.POINTER(abi.Probe), i32, i32, vp, vp, C.POINTER(i32)]
+    L.fovpt_debug_bsdf.argtypes = [vp, C.POINTER(abi.Material), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fovpt_debug_tex2d.argtypes = [vp, i32, i32, vp, vp]
     _declare_loader(L)
     _declare_packet_host(L)
     for name in EXPORTS:

@@ -753,6 +753,49 @@ class SampleRenderer:
         self._check(self._L.fovpt_debug_trace(self._ctx, n, o.ctypes.data, d.ctypes.data, prim.ctypes.data, tuv.ctypes.data, occ.ctypes.data))
         return prim, tuv, occ
 
+    def debug_probe_sample(self, r12, plain=False, probe=None):
+        """The production probe_sample with its two random numbers given (pairs in [0, 0.999999]) on `probe` (default: the launch
+        parameters' probe), searched the way a launch would, or plainly -> dict(row, col, dir, color, pdf, path): path = the
+        abi.PROBE_PATH_* bits of the layout that ran."""
+        r = np.ascontiguousarray(r12, np.float32).reshape(-1, 2)
+        n = r.shape[0]
+        rowcol, out, path = np.empty((n, 2), np.int32), np.empty((n, 7), np.float32), C.c_int(0)
+        self._check(self._L.fovpt_debug_probe_sample(self._ctx, C.byref(probe if probe is not None else self.launchParams.probe),
+                                                     abi.DEBUG_PROBE_PLAIN if plain else 0, n, r.ctypes.data, rowcol.ctypes.data,
+                                                     out.ctypes.data, C.byref(path)))
+        return dict(row=rowcol[:, 0].copy(), col=rowcol[:, 1].copy(), dir=out[:, 0:3].copy(), color=out[:, 3:6].copy(),
+                    pdf=out[:, 6].copy(), path=path.value)
+
+    def debug_probe_eval(self, dirs, plain=False, probe=None):
+        """probe_dir_to_uv + probe_eval, the backplate of a camera ray -> dict(uv, texel, path)."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = d.shape[0]
+        out, path = np.empty((n, 6), np.float32), C.c_int(0)
+        self._check(self._L.fovpt_debug_probe_eval(self._ctx, C.byref(probe if probe is not None else self.launchParams.probe),
+                                                   abi.DEBUG_PROBE_PLAIN if plain else 0, n, d.ctypes.data, out.ctypes.data, C.byref(path)))
+        return dict(uv=out[:, 0:2].copy(), texel=out[:, 2:6].copy(), path=path.value)
+
+    def debug_bsdf(self, material, N, view, albedo, etaI, etaO, seeds, L_given):
+        """Per row: bsdf_sample with Random(seed), bsdf_eval / bsdf_pdf at the sampled direction when its pdf is above 0, and
+        bsdf_pdf / bsdf_eval at L_given -> the columns of oracle.bsdf_table_given (without `type`)."""
+        N, view, albedo, L_given = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (N, view, albedo, L_given))
+        etaI, etaO = np.ascontiguousarray(etaI, np.float32), np.ascontiguousarray(etaO, np.float32)
+        seeds = np.ascontiguousarray(seeds, np.int32)
+        n = N.shape[0]
+        assert view.shape[0] == albedo.shape[0] == L_given.shape[0] == etaI.size == etaO.size == seeds.size == n
+        out = np.empty((n, 14), np.float32)
+        self._check(self._L.fovpt_debug_bsdf(self._ctx, C.byref(material), n, N.ctypes.data, view.ctypes.data, albedo.ctypes.data,
+                                             etaI.ctypes.data, etaO.ctypes.data, seeds.ctypes.data, L_given.ctypes.data, out.ctypes.data))
+        return dict(light=out[:, 0:3].copy(), pdf=out[:, 3].copy(), eval=out[:, 4:7].copy(), pdf_again=out[:, 7].copy(),
+                    rng_after=out[:, 8:10].copy().view(np.uint32), eval_given=out[:, 10:13].copy(), pdf_given=out[:, 13].copy())
+
+    def debug_tex2d(self, texture, uv):
+        """tex2d of texture `texture` of the scene at (u, v) pairs -> (n, 4) float32."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.empty((uv.shape[0], 4), np.float32)
+        self._check(self._L.fovpt_debug_tex2d(self._ctx, int(texture), uv.shape[0], uv.ctypes.data, out.ctypes.data))
+        return out
+
     def debug_math(self, op, a, b=None):
         a = np.ascontiguousarray(a, np.float32)
         bb = np.ascontiguousarray(b, np.float32) if b is not None else None

@@ -1010,6 +1010,31 @@ int fovpt_debug_math(fovpt_ctx* ctx, int op, const float* a, const float* b, flo
  * hit -> global primitive id (0xffffffff = miss) and (t, u, v); occlusion ray (deviceProgram.cu:224-248) -> 0 / 1.
  * Any output may be NULL.  Synchronises.                                                                              */
 int fovpt_debug_trace(fovpt_ctx* ctx, int n, const float* origins3, const float* dirs3, uint32_t* prim_out, float* tuv_out3, uint8_t* occluded_out);
+/* tests only: the device functions of a shaded hit on n inputs the caller chose (host arrays), so that the probe lookup, the
+ * Disney BSDF and the texture fetch can be compared with the oracle input by input.  All synchronise; any output may be NULL.
+ *
+ * fovpt_debug_probe_sample: ProbeSample (Probe.cuh:138-169) with its two random numbers given, r12 = n pairs in Randf's range
+ *   [0, 0.999999] -> the row and column the two searches found (rowcol_out2) and direction.xyz, colour.xyz, pdf (out7).
+ *   As for a launch, the last entry of cdfValuesY and of every row of cdfValuesX must be at least 0.999999 (BuildCDF ends
+ *   them at 1): a search for a number above a row's last entry returns the row's length, and the lookup reads past the row.
+ * fovpt_debug_probe_eval: ProbeDirToUV + ProbeEval, the backplate of the raygen program -> u, v, texel.xyzw (out6).
+ *   `probe` is what a launch takes (device pointers).  The arrays are searched and read the way a launch of this context
+ *   would: *path_out tells how (FOVPT_PROBE_PATH_* bits; 0 = the reference's plain binary search over all rows).
+ *   flags = FOVPT_DEBUG_PROBE_PLAIN forces that plain path on the same arrays.
+ * fovpt_debug_bsdf: per row BasisFromVector(N), then with Random(seed) BSDFSample and -- if its pdf is above 0 -- BSDFEval and
+ *   BSDFPdf at the sampled direction, then BSDFPdf and BSDFEval at L_given (the next-event branch: a direction from the
+ *   probe, which may lie below the surface) -> out14 = light.xyz, pdf, eval.xyz, pdf_again, the generator's two state words
+ *   afterwards (as bits), eval_given.xyz, pdf_given.
+ * fovpt_debug_tex2d: the bilinear wrap-addressed fetch of texture `texture` of the current scene at n (u, v) -> rgba.       */
+#define FOVPT_DEBUG_PROBE_PLAIN   1
+#define FOVPT_PROBE_PATH_GUIDED   1   /* both searches go through the guide tables                                  */
+#define FOVPT_PROBE_PATH_RECORDS  2   /* column search, pdf and colour from the packed 32-byte records               */
+#define FOVPT_PROBE_PATH_ONE_ROW  4   /* all rows alike: served from row 0 (row_mul = 0)                             */
+int fovpt_debug_probe_sample(fovpt_ctx* ctx, const fovpt_probe* probe, int flags, int n, const float* r12, int32_t* rowcol_out2, float* out7, int* path_out);
+int fovpt_debug_probe_eval(fovpt_ctx* ctx, const fovpt_probe* probe, int flags, int n, const float* dirs3, float* out6, int* path_out);
+int fovpt_debug_bsdf(fovpt_ctx* ctx, const fovpt_material* material, int n, const float* N3, const float* view3, const float* albedo3, const float* etaI,
+                     const float* etaO, const int32_t* seeds, const float* L_given3, float* out14);
+int fovpt_debug_tex2d(fovpt_ctx* ctx, int texture, int n, const float* uv2, float* rgba_out4);
 /* tests/diagnostics only: device address and size of an internal buffer ("sq_occ", "counters", "hit", "bvh_nodes", "bvh_tris"
  * -- the 48-byte triangle records of the hierarchy, stats.tri_bytes --, "scene_vertices" -- fovpt_update_vertices' vertex
  * array, once made --, "scene_vertices_prev" -- fovpt_temporal_motion's previous positions, once made --, "gbuffer_hit" -- the

@@ -228,12 +228,11 @@ inline int LowerBound(const float* array, int lower, int upper, const float valu
     }
     return lower;
 }
-inline void ProbeSample(const ProbeH& image, f3& dir, f3& color, float& pdf, Random& rand)   // Probe.cuh:138-169
+// ProbeSample behind its two draws (Probe.cuh:141-169): what orc_probe_sample_at hands chosen numbers; row, col: what the searches found
+inline void ProbeSampleAt(const ProbeH& image, float r1, float r2, f3& dir, f3& color, float& pdf, int& row, int& col)
 {
-    float r1, r2;
-    Sample2D(rand, r1, r2);
-    int row = LowerBound(image.cdfY, 0, image.height, r1);
-    int col = LowerBound(image.cdfX, row * image.width, (row + 1) * image.width, r2) - row * image.width;
+    row = LowerBound(image.cdfY, 0, image.height, r1);
+    col = LowerBound(image.cdfX, row * image.width, (row + 1) * image.width, r2) - row * image.width;
     color = mk3(image.data[row * image.width + col]);
     pdf = image.pdfX[row * image.width + col] * image.pdfY[row];
     float u = col / float(image.width);
@@ -243,6 +242,13 @@ inline void ProbeSample(const ProbeH& image, f3& dir, f3& color, float& pdf, Ran
     else pdf *= image.width * image.height / (2.0f * kPi * kPi * sinTheta);
     f2 uv = {u, v};
     dir = ProbeUVToDir(uv);
+}
+inline void ProbeSample(const ProbeH& image, f3& dir, f3& color, float& pdf, Random& rand)   // Probe.cuh:138-169
+{
+    float r1, r2;
+    Sample2D(rand, r1, r2);
+    int row, col;
+    ProbeSampleAt(image, r1, r2, dir, color, pdf, row, col);
 }
 inline float ProbePdf(const ProbeH& image, const f3& d)                       // Probe.cuh:69-93 (used by FOVPT_OPT_SKY_MISS only)
 {
@@ -1267,6 +1273,32 @@ void orc_probe_sample(const fovpt_probe* p, int seed, int n, float* dir3, float*
         pdf[i] = pd;
     }
 }
+/* ProbeSample with its two random numbers given (n pairs): the row and column of the two searches, direction, colour, pdf */
+void orc_probe_sample_at(const fovpt_probe* p, int n, const float* r12, int* rowcol2, float* dir3, float* color3, float* pdf)
+{
+    ProbeH P; P.width = p->width; P.height = p->height; P.data = (const f4*)p->data;
+    P.pdfX = p->pdfValuesX; P.cdfX = p->cdfValuesX; P.pdfY = p->pdfValuesY; P.cdfY = p->cdfValuesY;
+    for (int i = 0; i < n; i++) {
+        f3 d, c; float pd; int row, col;
+        ProbeSampleAt(P, r12[2 * i], r12[2 * i + 1], d, c, pd, row, col);
+        rowcol2[2 * i] = row; rowcol2[2 * i + 1] = col;
+        dir3[3 * i] = d.x; dir3[3 * i + 1] = d.y; dir3[3 * i + 2] = d.z;
+        color3[3 * i] = c.x; color3[3 * i + 1] = c.y; color3[3 * i + 2] = c.z;
+        pdf[i] = pd;
+    }
+}
+/* the backplate of the raygen program: ProbeDirToUV, then ProbeEval */
+void orc_probe_eval_dir(const fovpt_probe* p, int n, const float* dir3, float* uv2, float* rgba4)
+{
+    ProbeH P; P.width = p->width; P.height = p->height; P.data = (const f4*)p->data;
+    P.pdfX = P.cdfX = P.pdfY = P.cdfY = nullptr;
+    for (int i = 0; i < n; i++) {
+        const f2 uv = ProbeDirToUV(mk3(dir3[3 * i], dir3[3 * i + 1], dir3[3 * i + 2]));
+        const f4 c = ProbeEval(P, uv);
+        uv2[2 * i] = uv.x; uv2[2 * i + 1] = uv.y;
+        rgba4[4 * i] = c.x; rgba4[4 * i + 1] = c.y; rgba4[4 * i + 2] = c.z; rgba4[4 * i + 3] = c.w;
+    }
+}
 void orc_probe_dir_to_uv(int n, const float* dir3, float* uv2)
 {
     for (int i = 0; i < n; i++) {
@@ -1298,6 +1330,24 @@ void orc_bsdf_table(const fovpt_material* mat, int n, const float* N3, const flo
         eval3[3 * i] = f.x; eval3[3 * i + 1] = f.y; eval3[3 * i + 2] = f.z;
         pdf_again[i] = p2;
         rng_after[2 * i] = r.seed1; rng_after[2 * i + 1] = r.seed2;
+    }
+}
+/* the same rows, and BSDFPdf and BSDFEval at a given light direction: the next-event estimate of SampleLights, whose direction
+ * comes from the probe and may lie below the surface */
+void orc_bsdf_table_given(const fovpt_material* mat, int n, const float* N3, const float* view3, const float* albedo3,
+                          const float* etaI, const float* etaO, const int* seeds, const float* Lgiven3,
+                          float* light3, float* pdf, int* type, float* eval3, float* pdf_again, uint32_t* rng_after,
+                          float* eval_given3, float* pdf_given)
+{
+    orc_bsdf_table(mat, n, N3, view3, albedo3, etaI, etaO, seeds, light3, pdf, type, eval3, pdf_again, rng_after);
+    for (int i = 0; i < n; i++) {
+        const f3 N = mk3(N3[3 * i], N3[3 * i + 1], N3[3 * i + 2]);
+        const f3 view = mk3(view3[3 * i], view3[3 * i + 1], view3[3 * i + 2]);
+        const f3 alb = mk3(albedo3[3 * i], albedo3[3 * i + 1], albedo3[3 * i + 2]);
+        const f3 L = mk3(Lgiven3[3 * i], Lgiven3[3 * i + 1], Lgiven3[3 * i + 2]);
+        pdf_given[i] = BSDFPdf(*mat, etaI[i], etaO[i], N, view, L);
+        const f3 f = BSDFEval(*mat, alb, etaI[i], etaO[i], N, view, L);
+        eval_given3[3 * i] = f.x; eval_given3[3 * i + 1] = f.y; eval_given3[3 * i + 2] = f.z;
     }
 }
 void orc_make_color(int n, const float* rgb3, uint32_t* out)

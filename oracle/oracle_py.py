@@ -225,6 +225,27 @@ def probe_sample(probe: "HostProbe", seed, n):
     return d, c, p
 
 
+def probe_sample_at(probe: "HostProbe", r12):
+    """ProbeSample with its two random numbers given -> dict(row, col, dir, color, pdf)."""
+    r = np.ascontiguousarray(r12, np.float32).reshape(-1, 2)
+    n = r.shape[0]
+    rc = np.empty((n, 2), np.int32)
+    d = np.empty((n, 3), np.float32)
+    c = np.empty((n, 3), np.float32)
+    p = np.empty(n, np.float32)
+    lib().orc_probe_sample_at(C.byref(probe.struct), n, _p(r), _p(rc), _p(d), _p(c), _p(p))
+    return dict(row=rc[:, 0].copy(), col=rc[:, 1].copy(), dir=d, color=c, pdf=p)
+
+
+def probe_eval(probe: "HostProbe", dirs):
+    """ProbeDirToUV + ProbeEval (the backplate of a camera ray) -> dict(uv, texel)."""
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    uv = np.empty((d.shape[0], 2), np.float32)
+    t = np.empty((d.shape[0], 4), np.float32)
+    lib().orc_probe_eval_dir(C.byref(probe.struct), d.shape[0], _p(d), _p(uv), _p(t))
+    return dict(uv=uv, texel=t)
+
+
 def probe_dir_to_uv(dirs):
     d = np.ascontiguousarray(dirs, np.float32)
     uv = np.empty((d.shape[0], 2), np.float32)
@@ -246,6 +267,25 @@ def bsdf_table(material, N, view, albedo, etaI, etaO, seeds):
     lib().orc_bsdf_table(C.byref(material), n, _p(N), _p(view), _p(albedo), _p(etaI), _p(etaO), _p(seeds),
                          _p(light), _p(pdf), _p(typ), _p(ev), _p(pdf2), _p(rng))
     return dict(light=light, pdf=pdf, type=typ, eval=ev, pdf_again=pdf2, rng_after=rng)
+
+
+def bsdf_table_given(material, N, view, albedo, etaI, etaO, seeds, L_given):
+    """bsdf_table's columns, and eval_given / pdf_given: BSDFEval and BSDFPdf at the light direction L_given of each row."""
+    n = len(seeds)
+    N, view, albedo, L_given = (np.ascontiguousarray(x, np.float32) for x in (N, view, albedo, L_given))
+    etaI, etaO = np.ascontiguousarray(etaI, np.float32), np.ascontiguousarray(etaO, np.float32)
+    seeds = np.ascontiguousarray(seeds, np.int32)
+    light = np.empty((n, 3), np.float32)
+    pdf = np.empty(n, np.float32)
+    typ = np.empty(n, np.int32)
+    ev = np.empty((n, 3), np.float32)
+    pdf2 = np.empty(n, np.float32)
+    rng = np.empty((n, 2), np.uint32)
+    evg = np.empty((n, 3), np.float32)
+    pdfg = np.empty(n, np.float32)
+    lib().orc_bsdf_table_given(C.byref(material), n, _p(N), _p(view), _p(albedo), _p(etaI), _p(etaO), _p(seeds), _p(L_given),
+                               _p(light), _p(pdf), _p(typ), _p(ev), _p(pdf2), _p(rng), _p(evg), _p(pdfg))
+    return dict(light=light, pdf=pdf, type=typ, eval=ev, pdf_again=pdf2, rng_after=rng, eval_given=evg, pdf_given=pdfg)
 
 
 def make_color(rgb):

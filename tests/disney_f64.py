@@ -117,6 +117,26 @@ def bsdf_eval(mat, albedo, eta_i, eta_o, N, V, L):
     return _lerp(brdf, bsdf, mat.transmission), near
 
 
+# ---- two more closeness masks, for callers that hand bsdf_eval / bsdf_pdf chosen geometry instead of sampled directions
+# (tests/test_shade_units_cpu.py); in the style of `near` above, each stated once here.
+def near_grazing_view(N, V):
+    """N.V within 1e-3 of 0 (or below it): the bound `near` puts on N.L, for the view.  Fr and SmithGGX of a cosine that binary32
+    only knows to 1e-7 absolutely are not comparable across precisions."""
+    return _dot(N, V) < 1e-3
+
+
+def near_clearcoat_peak(mat, N, V, L):
+    """N.H within the clearcoat lobe's width a = lerp(0.1, 0.001, clearcoatGloss) of 1, for a material that has a clearcoat:
+    GTR1's denominator 1 + (a^2 - 1) (N.H)^2 falls to a^2 there and amplifies the binary32 rounding of N.H by ~1 / a^2, which the
+    tolerance rule of test_bsdf_against_an_independent_binary64_restatement allows for the GGX lobe's roughness only."""
+    if not mat.clearcoat > 0.0:
+        return np.zeros(len(N), bool)
+    h = L + V
+    with np.errstate(all="ignore"):
+        H = h / np.linalg.norm(h, axis=1, keepdims=True)
+    return 1.0 - np.abs(_dot(N, H)) < _lerp(0.1, 0.001, mat.clearcoatGloss)
+
+
 # ---- BSDFSample (Disney.cuh:197-315) as scalar Python: the order of the random draws and the branch structure -------
 M32 = 0xFFFFFFFF
 TWO_PI = 2.0 * float(PI)
