@@ -351,6 +351,34 @@ class ExposeState(C.Structure):
     ]
 
 
+WARP_COLOR, WARP_RGBA = 1, 2                   # FOVPT_WARP_*
+WARP_MAX_RADIUS = 4                            # FOVPT_WARP_MAX_RADIUS
+WARP_DIRECT, WARP_FILLED, WARP_EMPTY = 0, 1, 2  # the class in bits 30 .. 31 of a warp map entry
+
+
+class WarpCamera(C.Structure):
+    """fovpt_warp_camera: the camera fovpt_warp re-aims the frame at, in LaunchParams.camera's layout."""
+    _fields_ = [("eye", Float3), ("U", Float3), ("V", Float3), ("W", Float3)]
+
+
+class WarpConfig(C.Structure):
+    """fovpt_warp_config: the images to warp (WARP_* bits) and the radius of the hole fill (defaults: fovpt_warp_defaults)."""
+    _fields_ = [("images", C.c_int32), ("fill_radius", C.c_int32), ("_reserved", C.c_int32 * 6)]
+
+    def copy(self):
+        m = WarpConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(WarpConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class WarpCounts(C.Structure):
+    """struct fovpt_warp_counts: the source pixels of the last warp that landed in the frame, and its destination pixels by class."""
+    _fields_ = [("splatted", C.c_uint64), ("direct", C.c_uint64), ("filled", C.c_uint64), ("empty", C.c_uint64)]
+
+
 PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS = 0x4b505646, 1, 4      # FOVPT_PACKET_*
 PACKET_NEAREST, PACKET_SMOOTH = 0, 1
 
@@ -404,6 +432,7 @@ assert C.sizeof(TemporalConfig) == 32
 assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.reconstruct.offset, PostConfig.temporal.offset) == (16, 48, 80)
 assert C.sizeof(ExposeConfig) == 80 and (ExposeConfig.low_permille.offset, ExposeConfig.key.offset) == (32, 48)
 assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
+assert C.sizeof(WarpCamera) == 48 and C.sizeof(WarpConfig) == 32 and C.sizeof(WarpCounts) == 32
 assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
 assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeader.passes.offset) == (16, 32)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8

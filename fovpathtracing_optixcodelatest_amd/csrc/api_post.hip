@@ -1,6 +1,6 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
-// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), and
-// their defaults.
+// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), fovpt_warp
+// (warp.hip), and their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -670,6 +670,121 @@ int fovpt_expose(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_expose
         fovpt_launch_expose_adapt(st, a, (const uint32_t*)c->ex_rows.p, nrows, (uint64_t*)c->ex_hist.p, (ExposeState*)c->ex_state.p);
     }
     fovpt_launch_expose_apply(st, npix, a, aut ? (const ExposeState*)c->ex_state.p : nullptr, in, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- late reprojection of the finished frame to a newer camera (warp.hip; its definition: tests/warp_ref.py) ------------------
+// (fill_radius: a convention, not a measurement: include/fovpt.h)
+int fovpt_warp_defaults(fovpt_warp_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->images = FOVPT_WARP_COLOR | FOVPT_WARP_RGBA;
+    out->fill_radius = 2;
+    return FOVPT_OK;
+}
+
+int fovpt_warp_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_warp_buffers", c->wp_color, c->wp_rgba, *color, *rgba);
+}
+
+int fovpt_warp_counts(fovpt_ctx* c, struct fovpt_warp_counts* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "fovpt_warp_counts: null argument");
+    memset(out, 0, sizeof(*out));
+    if (!c->wp_counts.p) return FOVPT_OK;                                  // no warp yet
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));
+    std::vector<uint64_t> part(FOVPT_WARP_COUNT_BYTES / sizeof(uint64_t));
+    HIPCHK(c, hipMemcpy(part.data(), c->wp_counts.p, FOVPT_WARP_COUNT_BYTES, hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < FOVPT_WARP_COUNT_SLOTS; s++) {                  // the waves' partial records
+        const uint64_t* p = &part[s * FOVPT_WARP_COUNT_STRIDE];
+        out->splatted += p[0]; out->direct += p[1]; out->filled += p[2]; out->empty += p[3];
+    }
+    return FOVPT_OK;
+}
+
+int fovpt_temporal_gbuffer(fovpt_ctx* c, fovpt_gbuffer_ptrs* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "fovpt_temporal_gbuffer: null argument");
+    if (!c->tp_valid) return fail(c, FOVPT_E_NO_FRAME, "fovpt_temporal_gbuffer: no temporal step since create / reset / resize / set_scene");
+    const GBufferDev g = temporal_set(c, c->tp_last);
+    out->prim = g.prim;
+    out->position = (fovpt_float4*)g.pos; out->normal = (fovpt_float4*)g.nrm; out->albedo = (fovpt_float4*)g.alb;
+    out->width = c->tp_w; out->height = c->tp_h;
+    return FOVPT_OK;
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  Without a caller's G-buffer the rendered frame's first (the
+// same stream, into fovpt_gbuffer's buffers); then the keys and counts are cleared, k_warp_scatter, k_warp_resolve.
+int fovpt_warp(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, const fovpt_warp_config* wc, const fovpt_gbuffer_ptrs* gbuffer,
+               const fovpt_float4* in_color, const uint32_t* in_rgba, fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map)
+{
+    const char* who = "fovpt_warp";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !to || !wc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (wc->images == 0 || (wc->images & ~(FOVPT_WARP_COLOR | FOVPT_WARP_RGBA)))
+        return fail(c, FOVPT_E_INVALID, "%s: images %d names no image or an unknown one", who, wc->images);
+    if (wc->fill_radius < 0 || wc->fill_radius > FOVPT_WARP_MAX_RADIUS)
+        return fail(c, FOVPT_E_INVALID, "%s: fill_radius %d outside 0 .. %d", who, wc->fill_radius, FOVPT_WARP_MAX_RADIUS);
+    for (int32_t r : wc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    const float* cam = &to->eye.x;                                         // eye, U, V, W: 12 floats
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(cam[k])) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to has a non-finite entry", who);
+    WarpArgs a;
+    memset(&a, 0, sizeof(a));
+    if (!camera_inverse(&to->U.x, &to->V.x, &to->W.x, a.inv)) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to is singular", who);
+    memcpy(a.eye, &to->eye.x, sizeof(a.eye));
+    if (!gbuffer && (!c->has_scene || lp->traversable != c->scene_id)) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    { const int rc_ = check_rendered_frame(c, lp, who, "warp", nullptr); if (rc_) return rc_; }
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    if (npix >= (1ull << 30)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
+    if (gbuffer && (gbuffer->width != c->dn_w || gbuffer->height != c->dn_h || !gbuffer->prim || !gbuffer->position))
+        return fail(c, FOVPT_E_INVALID, "%s: the G-buffer is not of the frame's size %d x %d, or has a null prim or position", who, c->dn_w, c->dn_h);
+    const bool C_ = wc->images & FOVPT_WARP_COLOR, R_ = wc->images & FOVPT_WARP_RGBA;
+    const fovpt_float4* in = C_ ? (in_color ? in_color : lp->frame.accum_buffer) : nullptr;
+    const uint32_t* rin = R_ ? (in_rgba ? in_rgba : lp->frame.frame_buffer) : nullptr;
+    if ((C_ && !in) || (R_ && !rin)) return fail(c, FOVPT_E_INVALID, "%s: an enabled image has a null input", who);
+
+    // buffers: the context's own outputs where an enabled image has none, the keys, the counts
+    HIPCHK(c, hipSetDevice(c->device));
+    if (C_ && !out_color) { HIPCHK(c, c->wp_color.reserve(npix * 16)); out_color = (fovpt_float4*)c->wp_color.p; }
+    if (R_ && !out_rgba) { HIPCHK(c, c->wp_rgba.reserve(npix * 4)); out_rgba = (uint32_t*)c->wp_rgba.p; }
+    if (!C_) out_color = nullptr;
+    if (!R_) out_rgba = nullptr;
+    HIPCHK(c, c->wp_keys.reserve(npix * 8));
+    if (!c->wp_counts.p) {
+        HIPCHK(c, c->wp_counts.reserve(FOVPT_WARP_COUNT_BYTES));
+        HIPCHK(c, hipMemset(c->wp_counts.p, 0, FOVPT_WARP_COUNT_BYTES));
+    }
+    // the resolve reads other pixels' inputs and keys while it writes: no output is an input, the keys or another output
+    GBufferDev g;
+    if (gbuffer) { g.prim = gbuffer->prim; g.pos = (float4*)gbuffer->position; g.nrm = (float4*)gbuffer->normal; g.alb = (float4*)gbuffer->albedo; }
+    else { g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = nullptr; g.alb = nullptr; }      // (null until the first trace)
+    const void* outs[3] = {out_color, out_rgba, out_map};
+    const void* ins[5] = {in, rin, g.prim, g.pos, c->wp_keys.p};
+    for (int i = 0; i < 3; i++) {
+        if (!outs[i]) continue;
+        for (const void* p : ins)
+            if (p == outs[i]) return fail(c, FOVPT_E_INVALID, "%s: an output is an input of the call (the resolve reads across pixels)", who);
+        for (int j = 0; j < i; j++)
+            if (outs[j] == outs[i]) return fail(c, FOVPT_E_INVALID, "%s: two outputs are the same buffer", who);
+    }
+
+    if (!gbuffer) { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, who); if (rc_) return rc_; }   // the rendered frame's camera
+    const hipStream_t st = c->shadow_stream;
+    HIPCHK(c, hipMemsetAsync(c->wp_keys.p, 0xff, npix * 8, st));
+    HIPCHK(c, hipMemsetAsync(c->wp_counts.p, 0, FOVPT_WARP_COUNT_BYTES, st));
+    fovpt_launch_warp_scatter(st, c->dn_frame, a, g.prim, g.pos, (uint64_t*)c->wp_keys.p, (uint64_t*)c->wp_counts.p);
+    fovpt_launch_warp_resolve(st, c->dn_w, c->dn_h, wc->fill_radius, (const uint64_t*)c->wp_keys.p, in, rin, out_color, out_rgba, out_map,
+                              (uint64_t*)c->wp_counts.p);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }

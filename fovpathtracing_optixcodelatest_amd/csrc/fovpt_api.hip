@@ -1603,6 +1603,9 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->tp_hist[0].p) { const int rc_ = reserve_temporal(c, n); if (rc_) return rc_; }               // and fovpt_temporal's
     if (c->po_color.p) { HIPCHK(c, c->po_color.reserve(n * 16)); HIPCHK(c, c->po_rgba.reserve(n * 4)); }   // and fovpt_post's
     if (c->ex_color.p) { HIPCHK(c, c->ex_color.reserve(n * 16)); HIPCHK(c, c->ex_rgba.reserve(n * 4)); }   // and fovpt_expose's (its state stays)
+    if (c->wp_keys.p) HIPCHK(c, c->wp_keys.reserve(n * 8));                                                // and fovpt_warp's keys and outputs
+    if (c->wp_color.p) HIPCHK(c, c->wp_color.reserve(n * 16));
+    if (c->wp_rgba.p) HIPCHK(c, c->wp_rgba.reserve(n * 4));
     c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
@@ -1776,6 +1779,7 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "post_color") == 0 && c->po_color.p) { *ptr = c->po_color.p; *bytes = c->po_color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
     if (strcmp(name, "expose_histogram") == 0 && c->ex_hist.p) { *ptr = c->ex_hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
     if (strcmp(name, "expose_state") == 0 && c->ex_state.p) { *ptr = c->ex_state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
+    if (strcmp(name, "warp_keys") == 0 && c->wp_keys.p) { *ptr = c->wp_keys.p; *bytes = c->wp_keys.bytes; return FOVPT_OK; }   // fovpt_warp's keys, once made
     if (strcmp(name, "gbuffer_hit") == 0 && c->gb_hit.p) { *ptr = c->gb_hit.p; *bytes = c->gb_pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {

@@ -172,6 +172,10 @@ struct fovpt_ctx {
     // AUTO step is a first step; the host never reads it outside fovpt_expose_state), the meter's per-block histogram rows and
     // the histogram of the last metered step, and the context's own outputs; all allocated on first use
     DevBuf ex_state, ex_rows, ex_hist, ex_color, ex_rgba;
+    // fovpt_warp: the scatter's keys (8 bytes per pixel), the device counts (FOVPT_WARP_COUNT_SLOTS partial records, zeroed on the stream
+    // ahead of every warp; the host reads and adds them nowhere but in fovpt_warp_counts) and the context's own outputs; all allocated on
+    // first use
+    DevBuf wp_keys, wp_counts, wp_color, wp_rgba;
     // fovpt_packet_submit / fovpt_packet_wait (api_packet.hip), all made by a context's first submit: the copy stream, and per slot
     // the device buffer an encode writes (one each, so that an encode never overwrites a packet that is still being copied), the
     // pinned host buffer its copy fills (grown on demand), the event recorded on fovpt_stream() behind the encode, which the copy

@@ -306,6 +306,25 @@ void fovpt_launch_expose_meter(hipStream_t st, const FrameDev& fd, const ExposeA
 void fovpt_launch_expose_adapt(hipStream_t st, const ExposeArgs& a, const uint32_t* rows, uint32_t nrows, uint64_t* hist, ExposeState* state);
 void fovpt_launch_expose_apply(hipStream_t st, size_t npix, const ExposeArgs& a, const ExposeState* state, const fovpt_float4* in,
                                fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_warp (warp.hip): the depth-tested scatter of fd's pixels (its camera: the directions of miss pixels) into `keys` -- one
+// 64-bit key per pixel, all ones before the launch -- seen from the camera of a, then the resolve of the keys into the outputs.
+// counts: FOVPT_WARP_COUNT_SLOTS copies of a struct fovpt_warp_counts on the device, FOVPT_WARP_COUNT_STRIDE 64-bit words apart
+// (256 bytes: no two share a cache line), all zero before the scatter; a wave adds to the copy of its number, the sum over the
+// copies is the record.  WarpCounts: the struct shares its name with the entry point, which hides it in C++.
+typedef struct fovpt_warp_counts WarpCounts;
+#define FOVPT_WARP_COUNT_SLOTS 256
+#define FOVPT_WARP_COUNT_STRIDE 32
+#define FOVPT_WARP_COUNT_BYTES ((size_t)FOVPT_WARP_COUNT_SLOTS * FOVPT_WARP_COUNT_STRIDE * sizeof(uint64_t))
+struct WarpArgs {
+    float inv[9];                       // rows of the `to` camera's inverse [U V W]^-1 (binary64 on the host, rounded to fp32)
+    float eye[3];                       // the `to` camera's eye
+};
+void fovpt_launch_warp_scatter(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const uint32_t* prim, const float4* pos, uint64_t* keys,
+                               uint64_t* counts);
+// in_color / out_color, in_rgba / out_rgba: both null where that image is not warped; out_map: may be null.  No output is an
+// input or another output (a pixel reads other pixels' inputs)
+void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,
+                               fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map, uint64_t* counts);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32

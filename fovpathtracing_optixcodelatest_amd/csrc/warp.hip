@@ -1,0 +1,128 @@
+// warp.hip -- fovpt_warp: late reprojection of a finished frame to a newer camera.  fovpt_temporal pulls
+// old colours into a frame whose depth is known: a gather.  Here only the OLD frame's depth is known, so the pixels are pushed:
+//
+//   k_warp_scatter   per source pixel: its G-buffer point (a hit) or its camera-ray direction (a miss) projected into the `to`
+//                    camera with fovpt_temporal's expression, rounded to the nearest pixel, and one 64-bit atomic minimum of
+//                    (depth bits << 32 | source index) on that pixel's key.  Nearest depth wins, equal depths go to the lower
+//                    source index: the keys do not depend on the order in which the atomics arrive
+//   k_warp_resolve   per destination pixel: the key's source; for an empty key the farthest key of the nearest non-empty
+//                    Chebyshev ring within fill_radius; else the pixel itself.  Copies the enabled images from the source,
+//                    bit for bit, and writes the map
+//
+// One thread per pixel, 64 x 4 pixel tiles (a wave is 64 pixels of a row), no LDS.  The four counts are per wave: a ballot, a
+// popcount and one atomic add by the wave's first lane, into one of 256 copies of the record that the host adds up.  The
+// definition, operation by operation, is tests/warp_ref.py; -ffp-contract=off keeps every product and sum of it a separate
+// binary32 op.
+#include "fovpt_device.h"
+#include "fovpt_pixel.h"
+#include "fovpt_post_pixel.h"
+
+namespace {
+
+#define WARP_EMPTY 0xffffffffffffffffull
+
+// The counts record of this wave: one of FOVPT_WARP_COUNT_SLOTS copies, FOVPT_WARP_COUNT_STRIDE words apart (the host adds
+// them up).  With one copy every wave of the frame adds to the same four words, and those atomics are carried out one after
+// the other: at 1920 x 1080 that was 0.9 ms of a call.
+__device__ inline unsigned long long* count_slot(unsigned long long* counts)
+{
+    const uint32_t wave = (blockIdx.y * gridDim.x + blockIdx.x) * (FOVPT_BLOCK / FOVPT_WAVE) + threadIdx.x / FOVPT_WAVE;
+    return counts + (size_t)(wave % FOVPT_WARP_COUNT_SLOTS) * FOVPT_WARP_COUNT_STRIDE;
+}
+
+// lanes of the wave for which p holds, counted once into *n (every lane of the wave calls this)
+__device__ inline void count_wave(bool p, unsigned long long* n)
+{
+    const unsigned long long m = __ballot(p);
+    if ((threadIdx.x & (FOVPT_WAVE - 1)) == 0 && m) atomicAdd(n, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter(const FrameDev fd, const WarpArgs a, const uint32_t* __restrict__ prim,
+                                                              const float4* __restrict__ pos, unsigned long long* __restrict__ keys,
+                                                              unsigned long long* __restrict__ counts)
+{
+    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    bool landed = false;
+    if (x < (uint32_t)fd.w && y < (uint32_t)fd.h) {
+        const uint32_t s = y * (uint32_t)fd.w + x;
+        const bool miss = prim[s] == 0xffffffffu;
+        V3 v;
+        if (!miss) v = v3(pos[s]) - v3(a.eye[0], a.eye[1], a.eye[2]);
+        else v = pixel_ray(fd, x, y);                                    // the sky is at infinity: only rotation moves it
+        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
+        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
+        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
+        const float fw = (float)fd.w, fh = (float)fd.h;
+        const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
+        const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
+        const float fx = floorf(px + 0.5f), fy = floorf(py + 0.5f);
+        landed = az > 0.0f && fx >= 0.0f && fx < fw && fy >= 0.0f && fy < fh;    // (in float, before converting: NaN fails)
+        if (landed) {
+            const uint32_t d = miss ? 0x7fffffffu : __float_as_uint(az);  // (az > 0: its bits order as its value does)
+            const uint32_t q = (uint32_t)fy * (uint32_t)fd.w + (uint32_t)fx;
+            (void)atomicMin(&keys[q], ((unsigned long long)d << 32) | (unsigned long long)s);
+        }
+    }
+    count_wave(landed, &count_slot(counts)[0]);
+}
+
+// the largest non-empty key, or 0
+__device__ inline unsigned long long farthest(unsigned long long best, unsigned long long k) { return k != WARP_EMPTY && k > best ? k : best; }
+
+// in_color / out_color and in_rgba / out_rgba: both null where the image is not warped; out_map: may be null
+__global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_resolve(int w, int h, int radius, const unsigned long long* __restrict__ keys,
+                                                              const fovpt_float4* __restrict__ in_color, const uint32_t* __restrict__ in_rgba,
+                                                              fovpt_float4* __restrict__ out_color, uint32_t* __restrict__ out_rgba,
+                                                              uint32_t* __restrict__ out_map, unsigned long long* __restrict__ counts)
+{
+    const int x = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), y = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const bool in = x < w && y < h;
+    uint32_t cls = 3u;                                                   // (outside the frame: no class)
+    if (in) {
+        const uint32_t q = (uint32_t)y * (uint32_t)w + (uint32_t)x;
+        unsigned long long k = keys[q];
+        cls = 0u;
+        if (k == WARP_EMPTY) {
+            unsigned long long best = 0ull;                              // (no key is 0: a landed depth word is not)
+            for (int r = 1; r <= radius && best == 0ull; r++) {
+                const int x0 = max(x - r, 0), x1 = min(x + r, w - 1);
+                if (y - r >= 0)
+                    for (int qx = x0; qx <= x1; qx++) best = farthest(best, keys[(size_t)(y - r) * (size_t)w + (size_t)qx]);
+                if (y + r < h)
+                    for (int qx = x0; qx <= x1; qx++) best = farthest(best, keys[(size_t)(y + r) * (size_t)w + (size_t)qx]);
+                const int y0 = max(y - r + 1, 0), y1 = min(y + r - 1, h - 1);
+                if (x - r >= 0)
+                    for (int qy = y0; qy <= y1; qy++) best = farthest(best, keys[(size_t)qy * (size_t)w + (size_t)(x - r)]);
+                if (x + r < w)
+                    for (int qy = y0; qy <= y1; qy++) best = farthest(best, keys[(size_t)qy * (size_t)w + (size_t)(x + r)]);
+            }
+            cls = best != 0ull ? 1u : 2u;
+            k = best;
+        }
+        const uint32_t src = cls == 2u ? q : (uint32_t)k;                // (a key's low word is a source pixel: below w * h)
+        if (out_color) out_color[q] = in_color[src];
+        if (out_rgba) out_rgba[q] = in_rgba[src];
+        if (out_map) out_map[q] = src | (cls << 30);
+    }
+    unsigned long long* slot = count_slot(counts);
+    count_wave(cls == 0u, &slot[1]);
+    count_wave(cls == 1u, &slot[2]);
+    count_wave(cls == 2u, &slot[3]);
+}
+
+}  // namespace
+
+void fovpt_launch_warp_scatter(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const uint32_t* prim, const float4* pos, uint64_t* keys,
+                               uint64_t* counts)
+{
+    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
+    hipLaunchKernelGGL(k_warp_scatter, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, prim, pos, (unsigned long long*)keys, (unsigned long long*)counts);
+}
+
+void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,
+                               fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map, uint64_t* counts)
+{
+    const dim3 grid((w + 63) / 64, (h + 3) / 4);
+    hipLaunchKernelGGL(k_warp_resolve, grid, dim3(FOVPT_BLOCK), 0, st, w, h, radius, (const unsigned long long*)keys, in_color, in_rgba, out_color,
+                       out_rgba, out_map, (unsigned long long*)counts);
+}

@@ -26,6 +26,7 @@ EXPORTS = [
     "fovpt_set_morphs", "fovpt_update_morphed",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
+    "fovpt_warp_defaults", "fovpt_warp", "fovpt_warp_buffers", "fovpt_warp_counts", "fovpt_temporal_gbuffer",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
     "fovpt_packet_check", "fovpt_packet_decode_host",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
@@ -185,6 +186,12 @@ def load():
     L.fovpt_expose_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_expose_state.argtypes = [vp, C.POINTER(abi.ExposeState)]
     L.fovpt_expose_reset.argtypes = [vp]
+    L.fovpt_warp_defaults.argtypes = [C.POINTER(abi.WarpConfig)]
+    L.fovpt_warp.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.WarpCamera), C.POINTER(abi.WarpConfig), C.POINTER(abi.GBufferPtrs),
+                             vp, vp, vp, vp, vp]
+    L.fovpt_warp_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_warp_counts.argtypes = [vp, C.POINTER(abi.WarpCounts)]
+    L.fovpt_temporal_gbuffer.argtypes = [vp, C.POINTER(abi.GBufferPtrs)]
     L.fovpt_packet_describe.argtypes = [vp, C.POINTER(abi.LaunchParams), u32, C.POINTER(abi.PacketHeader)]
     L.fovpt_packet_encode.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, vp]
     L.fovpt_packet_submit.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, C.POINTER(i32)]

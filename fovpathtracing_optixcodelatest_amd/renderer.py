@@ -455,6 +455,67 @@ class SampleRenderer:
         """The float4 output of the last expose() into the renderer's own buffer."""
         return self._download_frame(self.expose_buffers()[0], 4)
 
+    # -- late reprojection of the finished frame to a newer camera (include/fovpt.h, fovpt_warp)
+    @staticmethod
+    def warp_defaults() -> abi.WarpConfig:
+        d = abi.WarpConfig()
+        lib.check(None, lib.load().fovpt_warp_defaults(C.byref(d)))
+        return d
+
+    @staticmethod
+    def warp_camera(camera) -> abi.WarpCamera:
+        """An abi.WarpCamera from a Camera (its aspect ratio as set), a dict of eye / U / V / W triples, an abi.WarpCamera or a
+        launchParams.camera."""
+        to = abi.WarpCamera()
+        if isinstance(camera, Camera):
+            to.U, to.V, to.W = camera.UVWFrame()
+            to.eye.set(camera.eye())
+        elif isinstance(camera, dict):
+            for k in ("eye", "U", "V", "W"):
+                getattr(to, k).set(camera[k])
+        else:
+            C.memmove(C.byref(to), C.byref(camera), C.sizeof(abi.WarpCamera))
+        return to
+
+    def warp(self, to, cfg=None, gbuffer=None, in_color=None, in_rgba=None, out_color=None, out_rgba=None, out_map=None):
+        """Re-aims the frame last rendered at the camera `to` (what warp_camera() takes): a depth-tested forward scatter of its
+        pixels and a fill of the holes, on the device; pixels are copied, never blended.  gbuffer: an abi.GBufferPtrs of the
+        rendered frame (temporal_gbuffer() after a post() / temporal() step saves the trace), None: traced by the call.  in_color /
+        in_rgba: device pointers of a float4 / rgba8 frame (None: the accum / frame buffer; typically expose_buffers()).
+        out_color / out_rgba: device pointers, or None for the renderer's own buffers (downloadWarpedColor /
+        downloadWarpedPixels); out_map: device pointer of a uint32 frame (source | class << 30) or None.  Enqueued on the
+        renderer's stream, not synchronised (the downloads and warp_counts() synchronise)."""
+        cfg = cfg if cfg is not None else self.warp_defaults()
+        to = self.warp_camera(to)
+        self._check(self._L.fovpt_warp(self._ctx, C.byref(self.launchParams), C.byref(to), C.byref(cfg), C.byref(gbuffer) if gbuffer is not None else None,
+                                       in_color, in_rgba, out_color, out_rgba, out_map))
+
+    def warp_buffers(self):
+        """Device addresses of the renderer's own warped outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_warp_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def warp_counts(self) -> abi.WarpCounts:
+        """The counts of the last warp() (synchronises the renderer's stream); zeros before any."""
+        s = abi.WarpCounts()
+        self._check(self._L.fovpt_warp_counts(self._ctx, C.byref(s)))
+        return s
+
+    def temporal_gbuffer(self) -> abi.GBufferPtrs:
+        """The G-buffer set the last temporal step (temporal(), temporal_motion(), post()) traced: the rendered frame's."""
+        g = abi.GBufferPtrs()
+        self._check(self._L.fovpt_temporal_gbuffer(self._ctx, C.byref(g)))
+        return g
+
+    def downloadWarpedPixels(self):
+        """The rgba8 output of the last warp() into the renderer's own buffer, shaped like downloadPixels()."""
+        return self._download_frame(self.warp_buffers()[1], 1)
+
+    def downloadWarpedColor(self):
+        """The float4 output of the last warp() into the renderer's own buffer."""
+        return self._download_frame(self.warp_buffers()[0], 4)
+
     # -- foveated frame packets (include/fovpt.h, fovpt_packet_*): a frame off the device, small and without stopping the renderer
     def describePacket(self, sequence=0) -> abi.PacketHeader:
         """The header encodePacket / submitPacket would write for the frame last rendered (host only); .bytes sizes a buffer."""

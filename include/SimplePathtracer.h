@@ -233,6 +233,57 @@ public:
         check(fovpt_expose_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- late reprojection (include/fovpt.h, fovpt_warp): re-aims the frame just rendered at a newer camera -- its aspect ratio is
+    // set from the frame size, as setCamera does -- into the renderer's own warped buffers, then a device sync like render().
+    // in_color / in_rgba: null = the accum / frame buffer, or e.g. the exposed outputs (fovpt_expose_buffers).  reuse_gbuffer: take the
+    // G-buffer of the last post() / temporal() step (fovpt_temporal_gbuffer) in place of tracing one
+    void warp(const sutil::Camera& to, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr, const uint32_t* in_rgba = nullptr)
+    {
+        fovpt_warp_config wc;
+        check(fovpt_warp_defaults(&wc));
+        warp(to, wc, reuse_gbuffer, in_color, in_rgba);
+    }
+    void warp(const sutil::Camera& to, const fovpt_warp_config& wc, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr,
+              const uint32_t* in_rgba = nullptr)
+    {
+        sutil::Camera cam = to;
+        cam.setAspectRatio(launchParams.frame.size.x / float(launchParams.frame.size.y));
+        float3 U, V, W;
+        cam.UVWFrame(U, V, W);
+        const float3 eye = cam.eye();
+        fovpt_warp_camera wcam;
+        wcam.eye.x = eye.x; wcam.eye.y = eye.y; wcam.eye.z = eye.z;
+        wcam.U.x = U.x; wcam.U.y = U.y; wcam.U.z = U.z;
+        wcam.V.x = V.x; wcam.V.y = V.y; wcam.V.z = V.z;
+        wcam.W.x = W.x; wcam.W.y = W.y; wcam.W.z = W.z;
+        fovpt_gbuffer_ptrs g;
+        if (reuse_gbuffer) check(fovpt_temporal_gbuffer(ctx, &g));
+        check(fovpt_warp(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &wcam, &wc, reuse_gbuffer ? &g : nullptr, in_color, in_rgba,
+                         nullptr, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // warp() of the images the last expose() left in the renderer's own exposed buffers
+    void warpExposed(const sutil::Camera& to, bool reuse_gbuffer = false)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_expose_buffers(ctx, &color, &rgba));
+        warp(to, reuse_gbuffer, color, rgba);
+    }
+    struct fovpt_warp_counts warpCounts()
+    {
+        struct fovpt_warp_counts s;
+        check(fovpt_warp_counts(ctx, &s));
+        return s;
+    }
+    // the warped rgba8 pixels, like downloadPixels
+    void downloadWarpedPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_warp_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- foveated frame packets (include/fovpt.h, fovpt_packet_*): the frame last rendered -- in_rgba null: the renderer's own
     // frame buffer; or the rgba8 output of post() / expose() -- as a small self-describing packet in pinned host memory, without a
     // device sync: submitPacket() returns at once with a slot, later frames keep rendering, waitPacket(slot) waits for that

@@ -802,6 +802,89 @@ int fovpt_expose_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 int fovpt_expose_state(fovpt_ctx* ctx, struct fovpt_expose_state* out);
 int fovpt_expose_reset(fovpt_ctx* ctx);
 
+/* ---- late reprojection ("timewarp") of a finished frame to a newer camera ----------------------------------------------------
+ * New with this library.  A head-mounted or gaze-tracked client learns its newest camera pose after fovpt_render was issued (with
+ * two frames in flight it is two poses behind): fovpt_warp re-aims the finished image at that pose just before display.
+ * fovpt_temporal pulls old colours into a new frame whose depth is known, a gather; here only the OLD frame's depth is known, so
+ * the stage is a depth-tested forward scatter (k_warp_scatter) followed by a resolve that closes cracks and disocclusions from the
+ * farthest surface nearby (k_warp_resolve).  No arithmetic touches a colour: a pixel is copied, so the result is defined bit for bit.
+ *   fovpt_warp               works on the frame last issued with fovpt_render(ctx, lp) as it was rendered: its size and camera (the
+ *                            camera is needed only for the directions of miss pixels).  `to`: the camera to warp to, in
+ *                            LaunchParams.camera's layout.  gbuffer NULL: the call traces the rendered camera's G-buffer into
+ *                            fovpt_gbuffer's buffers, exactly as fovpt_reconstruct does (so it needs the scene); non-NULL: the
+ *                            pointers are used as given, only prim and position are read, and the caller vouches that they belong
+ *                            to the frame -- with fovpt_temporal_gbuffer's set the loop render -> post -> expose ->
+ *                            temporal_gbuffer -> warp traces one G-buffer per frame, not two.  in_color NULL = accum_buffer,
+ *                            in_rgba NULL = frame_buffer (typically fovpt_expose's outputs); out_color / out_rgba NULL = the
+ *                            context's own (fovpt_warp_buffers: allocated on first use together with an 8-byte-per-pixel key
+ *                            buffer, reallocated by fovpt_resize, freed by fovpt_destroy; a context that never warps pays
+ *                            nothing); out_map (may be NULL): uint32 per pixel, source | class << 30.  Only the images of
+ *                            cfg.images are read and written.  The outputs are written whole.  Enqueued on fovpt_stream(), not
+ *                            synchronised, ordered like fovpt_denoise.  The definition, operation by operation
+ *                            (tests/warp_ref.py), every fp32 *, +, - and / one unfused operation; w, h the frame size,
+ *                            s = y * w + x a source pixel, M the rows of inverse(U V W) of `to` as fovpt_temporal computes the
+ *                            previous camera's (binary64, entries rounded to fp32):
+ *                              scatter     v = X_s - eye_to for a hit (prim != 0xffffffff), (dx U + dy V) + W of the rendered
+ *                                          camera for a miss (the sky is at infinity: only rotation moves it);
+ *                                          a_k = (M_k.x v.x + M_k.y v.y) + M_k.z v.z;
+ *                                          px = (((a.x / a.z) + 1) * 0.5) * w - 0.5, py likewise with h;
+ *                                          fx = floor(px + 0.5f), fy likewise; the pixel lands iff a.z > 0, 0 <= fx < w and
+ *                                          0 <= fy < h (compared in float: NaNs fall out); depth word d = the bits of a.z for a
+ *                                          hit, 0x7fffffff for a miss; key = d << 32 | s;
+ *                                          keys[fy * w + fx] = min(keys[...], key), keys all ones before.  Nearest depth wins,
+ *                                          equal depths go to the lower source index, whatever the arrival order
+ *                              resolve     per destination pixel q.  Key not empty: class direct (0), the source is the key's
+ *                                          low word.  Empty: for r = 1 .. fill_radius the pixels at Chebyshev distance exactly r
+ *                                          inside the frame; the first r with a non-empty key ends the search, the source is
+ *                                          the low word of the LARGEST key of that ring -- the farthest surface, which is what a
+ *                                          disocclusion uncovers; the smallest ring keeps a crack's fill local --, class filled
+ *                                          (1).  Still empty: class empty (2), the source is q itself.
+ *                                          out_color[q] = in_color[src] (all four components), out_rgba[q] = in_rgba[src],
+ *                                          out_map[q] = src | class << 30
+ *                            All or nothing, checked before anything is enqueued.  FOVPT_E_INVALID: null ctx / lp / to / wc;
+ *                            images 0 or with unknown bits; fill_radius outside 0 .. FOVPT_WARP_MAX_RADIUS; non-zero reserved
+ *                            fields; a non-finite entry of `to`, or a `to` whose [U V W] has a determinant of 0 or a non-finite
+ *                            one; a gbuffer whose size is not the frame's or with a null prim or position; width * height >=
+ *                            2^30 (the map's class bits); an enabled image with a null input; any output equal to any input or
+ *                            to another output (the resolve gathers across pixels; base addresses are compared: buffers that
+ *                            overlap part of the way are the caller's to avoid); a frame rendered with world > 1.
+ *                            FOVPT_E_NO_FRAME, FOVPT_E_NO_SCENE: as fovpt_reconstruct (the scene only where the call traces).
+ *   fovpt_warp_defaults      host only, no context: both images, fill_radius 2 (a convention, not a measurement).
+ *   fovpt_warp_buffers       addresses of the context's own warped outputs (allocated for the last frame if not yet).
+ *   fovpt_warp_counts        synchronises fovpt_stream() and copies the counts of the last fovpt_warp out; zeros before any warp.
+ *                            The struct and the function share their name, so the struct has no typedef: write
+ *                            `struct fovpt_warp_counts` (C and C++ alike).
+ *   fovpt_temporal_gbuffer   the G-buffer set the last temporal step (fovpt_temporal, fovpt_temporal_motion, fovpt_post) wrote;
+ *                            FOVPT_E_NO_FRAME when there is none (no step yet, or fovpt_temporal_reset / fovpt_resize /
+ *                            fovpt_set_scene since).  The next temporal step leaves it alone and overwrites the other set.
+ * Out of scope.  Moving meshes: they are warped as if static (extrapolating them by fovpt_temporal_motion's vectors is a later
+ * step).  Resampling: a pixel is copied, not interpolated.  Packets: a packet's texel ownership belongs to the rendered camera, so
+ * the warp is the last stage on the server, or a client's job after decoding.
+ * On an MI355X at 1920 x 1080, both images, fill_radius 2, a call takes 0.050 .. 0.054 ms with a caller's G-buffer and 0.262 .. 0.265 ms with
+ * its own trace over a slide, a turn and a dolly-in (fovpt_expose FIXED, a plain full-frame pass: 0.020 ms; one fovpt_render: 0.70 ms)
+ * (DESIGN.md, section 21).                                                                                                      */
+typedef struct fovpt_warp_camera { fovpt_float3 eye, U, V, W; } fovpt_warp_camera;        /* 48 bytes: LaunchParams.camera's layout */
+#define FOVPT_WARP_COLOR 1          /* warp the float4 image   */
+#define FOVPT_WARP_RGBA  2          /* warp the rgba8 image    */
+#define FOVPT_WARP_MAX_RADIUS 4
+typedef struct fovpt_warp_config {  /* 32 bytes */
+    int32_t images;                 /* FOVPT_WARP_* bits, at least one; default 3 */
+    int32_t fill_radius;            /* 0 .. FOVPT_WARP_MAX_RADIUS; default 2 (a convention, not a measurement) */
+    int32_t _reserved[6];           /* 0 */
+} fovpt_warp_config;
+struct fovpt_warp_counts {          /* 32 bytes, of the last fovpt_warp */
+    uint64_t splatted;              /* source pixels that landed inside the frame */
+    uint64_t direct, filled, empty; /* destination pixels by class; they sum to width * height */
+};
+int fovpt_warp_defaults(fovpt_warp_config* out);
+int fovpt_warp(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_warp_camera* to, const fovpt_warp_config* wc,
+               const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, const fovpt_float4* in_color /* NULL: accum_buffer */,
+               const uint32_t* in_rgba /* NULL: frame_buffer */, fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */,
+               uint32_t* out_map /* may be NULL */);
+int fovpt_warp_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+int fovpt_warp_counts(fovpt_ctx* ctx, struct fovpt_warp_counts* out);
+int fovpt_temporal_gbuffer(fovpt_ctx* ctx, fovpt_gbuffer_ptrs* out);
+
 /* ---- foveated frame packets: a frame off the device, small and without stopping the renderer -----------------------------------
  * New with this library.  fovpt_download drains every stream and copies a whole frame into pageable memory.  A foveated frame
  * is described exactly by one value per launch index -- at the shipped radii 74 / 241 a 1920 x 1080 frame has 211 149 of them,
@@ -1040,7 +1123,8 @@ int fovpt_debug_tex2d(fovpt_ctx* ctx, int texture, int n, const float* uv2, floa
  * array, once made --, "scene_vertices_prev" -- fovpt_temporal_motion's previous positions, once made --, "gbuffer_hit" -- the
  * hit records of the last G-buffer trace (fovpt_gbuffer, fovpt_reconstruct, a temporal step): float4 (t, u, v, record offset
  * as bits, 0xffffffff on a miss) per pixel --, "expose_histogram" -- fovpt_expose's last metered histogram, FOVPT_EXPOSE_BINS
- * uint64_t --, "expose_state" -- its device state record: a struct fovpt_expose_state --, ...)                                  */
+ * uint64_t --, "expose_state" -- its device state record: a struct fovpt_expose_state --, "warp_keys" -- fovpt_warp's key
+ * buffer, once made: the keys of the last warp in its first width * height uint64_t --, ...)                                   */
 int fovpt_debug_buffer(fovpt_ctx* ctx, const char* name, void** ptr, size_t* bytes);
 
 #ifdef __cplusplus
@@ -1060,6 +1144,9 @@ static_assert(sizeof(fovpt_post_config) == 112 && offsetof(fovpt_post_config, de
 static_assert(sizeof(fovpt_expose_config) == 80 && offsetof(fovpt_expose_config, low_permille) == 32 && offsetof(fovpt_expose_config, key) == 48,
               "expose config ABI");
 static_assert(sizeof(struct fovpt_expose_state) == 32 && offsetof(struct fovpt_expose_state, weight_total) == 16, "expose state ABI");
+static_assert(sizeof(fovpt_warp_camera) == 48 && offsetof(fovpt_warp_camera, W) == 36, "warp camera ABI");
+static_assert(sizeof(fovpt_warp_config) == 32 && offsetof(fovpt_warp_config, fill_radius) == 4, "warp config ABI");
+static_assert(sizeof(struct fovpt_warp_counts) == 32 && offsetof(struct fovpt_warp_counts, direct) == 8, "warp counts ABI");
 static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");
 static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header, width) == 16 && offsetof(fovpt_packet_header, pass) == 32,
               "packet header ABI");
