@@ -3,8 +3,8 @@
 // One context = one device = one stream, like the reference's SampleRenderer
 // (PT_sv5_/SimplePathtracer.cpp:331-340).  Calls on a context are not thread-safe.
 //
-// The post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip, the frame packets in api_packet.hip;
-// fovpt_ctx.h is what they share.
+// Animated geometry is in api_animate.hip, the post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip, the
+// frame packets in api_packet.hip; fovpt_ctx.h is what they share.
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -144,10 +144,7 @@ void free_scene(fovpt_ctx* c)
     for (void* p : c->tex_pixels) (void)hipFree(p);
     c->tex_pixels.clear();
     c->has_scene = false;
-    c->skins.clear();                               // fovpt_set_skins: the skins are the scene's
-    c->skin_joints.release(); c->skin_weights.release(); c->skin_pal.release();
-    c->morphs.clear();                              // fovpt_set_morphs: and so are the morph targets
-    c->morph_off.release(); c->morph_ent.release(); c->morph_w.release();
+    drop_animation(c);                              // what the update calls keep of it (api_animate.hip)
 }
 
 // A queue shard receives the appends of the blocks whose index is congruent to it modulo FOVPT_SHARDS.  The
@@ -519,6 +516,8 @@ int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P)
     return 3;
 }
 
+}  // namespace
+
 // The hierarchy over d_flat (9 floats per triangle) on stream st, as fovpt_set_scene builds it: FOVPT_BVH, FOVPT_SPLIT, and a
 // second build without reinsertion when reinsertion made the tree too deep; *ms = its device time.  On success br holds the
 // new hierarchy (adopt_hierarchy takes it); on failure nothing is kept.
@@ -559,6 +558,8 @@ int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uin
     return FOVPT_OK;
 }
 
+namespace {
+
 // What fovpt_set_probe and fovpt_set_probe_data share once the probe's arrays are on the device: whether the CDFs (host copies
 // cdfX, cdfY) are sorted, the guide tables and packed records if so, whether all rows are alike (texels, cdfX, and pdfX where
 // the caller has it on the host), and the caller's fovpt_probe.
@@ -598,6 +599,8 @@ int finish_probe(fovpt_ctx* c, int width, int height, const fovpt_float4* data, 
     return FOVPT_OK;
 }
 
+}  // namespace
+
 // the hierarchy build_hierarchy made becomes the scene's, with its scene facts
 void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms)
 {
@@ -611,7 +614,7 @@ void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms)
 
 // ---- fovpt_hierarchy_cost: measurements (refit.hip) ------------------------------------------------------------------------
 // The completed measurements: the newest becomes (cost_current, cost_measured), and their slots are free again.
-void take_costs(fovpt_ctx* c)
+static void take_costs(fovpt_ctx* c)
 {
     bool not_ready = false;
     for (auto& S : c->cost_slot) {
@@ -659,269 +662,6 @@ int measure_built(fovpt_ctx* c)
     c->cost_measured = c->cost_updates;
     return FOVPT_OK;
 }
-
-// ---- animated geometry (refit.hip) ---------------------------------------------------------------------------------------
-// What both entry points check of the scene once their own arguments are in order
-int check_updatable(fovpt_ctx* c, const char* who)
-{
-    if (c->h_vtx.size() / 3 >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "%s: more than 2^32 - 1 vertices", who);
-    if (c->bvh_num_levels == 0) return fail(c, FOVPT_E_INVALID, "%s: the hierarchy has more than %d levels", who, FOVPT_BVH_MAX_LEVELS);
-    return FOVPT_OK;
-}
-
-// Where the new positions of update_scene come from: `up` (host arrays through a staging buffer, `floats` of them in all, or
-// device arrays by a gather kernel), `tf` (the rest positions through per-mesh matrices) or `sk` (the rest positions through
-// per-vertex blends of per-mesh joint palettes: host palettes through the staging buffer, `floats` of them in all, or device
-// palettes in place) or `mo` (the rest positions plus their weighted morph deltas, and through the skin where a pose has a
-// palette: host weights and palettes through the staging buffer, `floats` of them in all, or device ones in place); all `num`
-// validated.
-struct UpdateSource {
-    const fovpt_vertex_update* up;
-    bool device;
-    size_t floats;
-    const fovpt_mesh_transform* tf;
-    int num;
-    const fovpt_skin_pose* sk;
-    const fovpt_morph_pose* mo;
-    int mesh(int k) const { return up ? up[k].mesh : tf ? tf[k].mesh : sk ? sk[k].mesh : mo[k].mesh; }
-};
-
-// The next of the two pinned staging buffers, with room for `bytes`, once the copies it last fed have run
-int take_stage(fovpt_ctx* c, size_t bytes, fovpt_ctx::Staging** out)
-{
-    auto& S = c->up_stage[c->up_next];
-    c->up_next ^= 1;
-    if (S.pending) { HIPCHK(c, hipEventSynchronize(S.ev)); S.pending = false; }      // its previous copy has run
-    if (S.bytes < bytes) {
-        if (S.p) (void)hipHostFree(S.p);
-        S.p = nullptr; S.bytes = 0;
-        HIPCHK(c, hipHostMalloc(&S.p, bytes, hipHostMallocDefault));
-        S.bytes = bytes;
-    }
-    *out = &S;
-    return FOVPT_OK;
-}
-
-// Once per scene, for the overflow rules: the largest |coordinate| of every mesh's rest positions
-void ensure_absmax(fovpt_ctx* c)
-{
-    if (!c->mesh_absmax.empty()) return;
-    const int nmesh = (int)c->mesh_nv.size();
-    c->mesh_absmax.assign((size_t)nmesh, 0.0);
-    for (int m = 0; m < nmesh; m++) {
-        const float* v = c->h_vtx.data() + 3 * (size_t)c->mesh_vbase[m];
-        for (size_t i = 0; i < 3 * (size_t)c->mesh_nv[m]; i++) c->mesh_absmax[m] = std::fmax(c->mesh_absmax[m], std::fabs((double)v[i]));
-    }
-}
-
-// The update itself, shared by fovpt_update_vertices, fovpt_update_transforms, fovpt_update_skinned and fovpt_update_morphed: fovpt_temporal_motion's copy of the positions
-// about to be overwritten, the new positions into up_vtx on fovpt_stream(), and either the refit, enqueued behind them on the
-// same stream (the stream every job's resolve, and so every job's last traversal launch, is ordered on) with the event the next
-// job waits for, or a rebuild.
-int update_scene(fovpt_ctx* c, const UpdateSource& s, bool rebuild)
-{
-    const int nmesh = (int)c->mesh_nv.size();
-    HIPCHK(c, hipSetDevice(c->device));
-    if (rebuild) { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    const hipStream_t st = c->shadow_stream;
-    if (!c->up_vtx.p) {
-        // the first update: the device copies of what fovpt_set_scene kept (ordered on the stream like everything below)
-        if (!c->ev_scene) HIPCHK(c, hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
-        for (auto& S : c->up_stage)
-            if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-        HIPCHK(c, c->up_vidx.reserve(c->h_tri_vidx.size() * 4));
-        HIPCHK(c, c->up_vtx.reserve(c->h_vtx.size() * 4));
-        HIPCHK(c, hipMemcpyAsync(c->up_vidx.p, c->h_tri_vidx.data(), c->h_tri_vidx.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    float* vtx = (float*)c->up_vtx.p;
-    if (!c->tm_tracking) c->tm_untracked = c->tm_untracked || s.num > 0;
-    else {
-        // fovpt_temporal_motion's previous positions: what a mesh holds now, ahead of the interval's first overwrite of it
-        HIPCHK(c, c->vtx_prev.reserve(c->h_vtx.size() * 4));
-        VertexTrack g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < s.num; k++) {
-            const int mesh = s.mesh(k);
-            const uint32_t nv = c->mesh_nv[mesh];
-            if (c->tm_mesh_epoch[mesh] != c->tm_epoch) {
-                c->tm_mesh_epoch[mesh] = c->tm_epoch;
-                g.first[g.count] = c->mesh_vbase[mesh]; g.n[g.count] = nv; g.mesh[g.count] = (uint32_t)mesh;
-                g.max_n = nv > g.max_n ? nv : g.max_n;
-                g.count++;
-            }
-            if (g.count == FOVPT_GATHER_BATCH || (k + 1 == s.num && g.count)) {
-                fovpt_launch_gather_vertices_prev(st, g, vtx, (float*)c->vtx_prev.p, (uint64_t*)c->tm_mark.p, c->tm_epoch);
-                memset(&g, 0, sizeof(g));
-            }
-        }
-        HIPCHK(c, hipGetLastError());
-    }
-    if ((s.tf || s.sk || s.mo) && !c->rest_vtx.p) {
-        // the first transforms or poses of the scene: the rest positions stay on the device
-        HIPCHK(c, c->rest_vtx.reserve(c->h_vtx.size() * 4));
-        HIPCHK(c, hipMemcpyAsync(c->rest_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    if (s.mo) {
-        if (!s.device && s.floats) {
-            // host weights, then host palettes: staged in call order, each copied to its mesh's place in morph_w / skin_pal
-            // (neighbours in one copy)
-            fovpt_ctx::Staging* S = nullptr;
-            { const int rc_ = take_stage(c, s.floats * 4, &S); if (rc_) return rc_; }
-            float* h = (float*)S->p;
-            for (int k = 0; k < s.num;) {
-                const uint32_t first = c->morphs[s.mo[k].mesh].w_first;
-                size_t nw = 0;
-                do {
-                    memcpy(h + nw, s.mo[k].weights, 4 * (size_t)s.mo[k].num_targets);
-                    nw += s.mo[k].num_targets;
-                } while (++k < s.num && c->morphs[s.mo[k].mesh].w_first == first + nw);
-                HIPCHK(c, hipMemcpyAsync((float*)c->morph_w.p + first, h, 4 * nw, hipMemcpyHostToDevice, st));
-                h += nw;
-            }
-            for (int k = 0; k < s.num;) {
-                if (!s.mo[k].num_joints) { k++; continue; }
-                const uint32_t first = c->skins[s.mo[k].mesh].pal_first;
-                size_t joints = 0;
-                do {
-                    memcpy(h + 12 * joints, s.mo[k].matrices, 48 * (size_t)s.mo[k].num_joints);
-                    joints += s.mo[k].num_joints;
-                } while (++k < s.num && s.mo[k].num_joints && c->skins[s.mo[k].mesh].pal_first == first + joints);
-                HIPCHK(c, hipMemcpyAsync((float*)c->skin_pal.p + 12 * (size_t)first, h, 48 * joints, hipMemcpyHostToDevice, st));
-                h += 12 * joints;
-            }
-            HIPCHK(c, hipEventRecord(S->ev, st));
-            S->pending = true;
-        }
-        // two batches side by side: the poses without a palette (k_morph_vertices) and those with one (k_morph_skin_vertices)
-        VertexMorph g[2];
-        memset(g, 0, sizeof(g));
-        for (int k = 0; k < s.num; k++) {
-            const fovpt_morph_pose& P = s.mo[k];
-            const fovpt_ctx::Morph& M = c->morphs[P.mesh];
-            const uint32_t nv = c->mesh_nv[P.mesh];
-            VertexMorph& b = g[P.num_joints ? 1 : 0];
-            b.w[b.count] = s.device ? P.weights : (const float*)c->morph_w.p + M.w_first;
-            b.first[b.count] = c->mesh_vbase[P.mesh]; b.n[b.count] = nv; b.off[b.count] = M.off_first;
-            if (P.num_joints) {
-                const fovpt_ctx::Skin& K = c->skins[P.mesh];
-                b.pal[b.count] = s.device ? P.matrices : (const float*)c->skin_pal.p + 12 * (size_t)K.pal_first;
-                b.skin[b.count] = K.first;
-            }
-            b.max_n = nv > b.max_n ? nv : b.max_n;
-            b.count++;
-            for (int v = 0; v < 2; v++) {
-                if (!(g[v].count == FOVPT_GATHER_BATCH || (k + 1 == s.num && g[v].count))) continue;
-                if (v) fovpt_launch_morph_skin_vertices(st, g[v], (const float*)c->rest_vtx.p, (const uint32_t*)c->morph_off.p, (const MorphEntry*)c->morph_ent.p,
-                                                        (const uint2*)c->skin_joints.p, (const float4*)c->skin_weights.p, vtx);
-                else fovpt_launch_morph_vertices(st, g[v], (const float*)c->rest_vtx.p, (const uint32_t*)c->morph_off.p, (const MorphEntry*)c->morph_ent.p, vtx);
-                memset(&g[v], 0, sizeof(g[v]));
-            }
-        }
-        HIPCHK(c, hipGetLastError());
-    } else if (s.sk) {
-        if (!s.device && s.floats) {
-            // host palettes: staged in call order, each copied to its mesh's place in skin_pal (neighbours in one copy)
-            fovpt_ctx::Staging* S = nullptr;
-            { const int rc_ = take_stage(c, s.floats * 4, &S); if (rc_) return rc_; }
-            float* h = (float*)S->p;
-            for (int k = 0; k < s.num;) {
-                const uint32_t first = c->skins[s.sk[k].mesh].pal_first;
-                size_t joints = 0;
-                do {
-                    memcpy(h + 12 * joints, s.sk[k].matrices, 48 * (size_t)s.sk[k].num_joints);
-                    joints += s.sk[k].num_joints;
-                } while (++k < s.num && c->skins[s.sk[k].mesh].pal_first == first + joints);
-                HIPCHK(c, hipMemcpyAsync((float*)c->skin_pal.p + 12 * (size_t)first, h, 48 * joints, hipMemcpyHostToDevice, st));
-                h += 12 * joints;
-            }
-            HIPCHK(c, hipEventRecord(S->ev, st));
-            S->pending = true;
-        }
-        VertexSkin g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < s.num; k++) {
-            const fovpt_ctx::Skin& K = c->skins[s.sk[k].mesh];
-            const uint32_t nv = c->mesh_nv[s.sk[k].mesh];
-            g.pal[g.count] = s.device ? s.sk[k].matrices : (const float*)c->skin_pal.p + 12 * (size_t)K.pal_first;
-            g.first[g.count] = c->mesh_vbase[s.sk[k].mesh]; g.n[g.count] = nv; g.skin[g.count] = K.first;
-            g.max_n = nv > g.max_n ? nv : g.max_n;
-            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == s.num) {
-                fovpt_launch_skin_vertices(st, g, (const float*)c->rest_vtx.p, (const uint2*)c->skin_joints.p, (const float4*)c->skin_weights.p, vtx);
-                memset(&g, 0, sizeof(g));
-            }
-        }
-        HIPCHK(c, hipGetLastError());
-    } else if (s.tf) {
-        VertexTransform g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < s.num; k++) {
-            const uint32_t nv = c->mesh_nv[s.tf[k].mesh];
-            memcpy(g.m[g.count], s.tf[k].m, sizeof(g.m[0]));
-            g.first[g.count] = c->mesh_vbase[s.tf[k].mesh]; g.n[g.count] = nv;
-            g.max_n = nv > g.max_n ? nv : g.max_n;
-            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == s.num) { fovpt_launch_transform_vertices(st, g, (const float*)c->rest_vtx.p, vtx); memset(&g, 0, sizeof(g)); }
-        }
-        HIPCHK(c, hipGetLastError());
-    } else if (s.device) {
-        VertexGather g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < s.num; k++) {
-            g.src[g.count] = s.up[k].vertex; g.dst[g.count] = c->mesh_vbase[s.up[k].mesh]; g.n[g.count] = s.up[k].num_vertices;
-            g.max_n = s.up[k].num_vertices > g.max_n ? s.up[k].num_vertices : g.max_n;
-            if (++g.count == FOVPT_GATHER_BATCH || k + 1 == s.num) { fovpt_launch_gather_vertices(st, g, vtx); memset(&g, 0, sizeof(g)); }
-        }
-        HIPCHK(c, hipGetLastError());
-    } else if (s.floats) {
-        fovpt_ctx::Staging* S = nullptr;
-        { const int rc_ = take_stage(c, s.floats * 4, &S); if (rc_) return rc_; }
-        float* h = (float*)S->p;
-        for (int k = 0; k < s.num; k++) {
-            const size_t n = 3 * (size_t)s.up[k].num_vertices;
-            memcpy(h, s.up[k].vertex, n * 4);
-            HIPCHK(c, hipMemcpyAsync(vtx + 3 * (size_t)c->mesh_vbase[s.up[k].mesh], h, n * 4, hipMemcpyHostToDevice, st));
-            h += n;
-        }
-        HIPCHK(c, hipEventRecord(S->ev, st));
-        S->pending = true;
-    }
-    if (!rebuild) {
-        fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, vtx);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_scene, st));
-        c->refit_pending = true;
-        c->cost_updates++;
-        if (c->cost_watching) {
-            // fovpt_hierarchy_cost is watching: the refit tree's cost, behind the event the next job waits for
-            fovpt_ctx::CostSlot* S = nullptr;
-            return enqueue_cost(c, st, c->cost_updates, &S);
-        }
-        return FOVPT_OK;
-    }
-    // FOVPT_UPDATE_REBUILD: fovpt_set_scene's build over the current vertices; the old hierarchy stays if it fails
-    const uint32_t ntri = (uint32_t)c->stats.num_triangles;
-    DevBuf t_flat, t_mesh_of;
-    HIPCHK(c, t_flat.reserve((size_t)ntri * 36));
-    HIPCHK(c, t_mesh_of.reserve((size_t)ntri * 4));
-    std::vector<uint32_t> mesh_of((size_t)ntri);
-    for (int m = 0; m < nmesh; m++) {
-        const uint32_t end = m + 1 < nmesh ? c->mesh_prim0[m + 1] : ntri;
-        for (uint32_t t = c->mesh_prim0[m]; t < end; t++) mesh_of[t] = (uint32_t)m;
-    }
-    HIPCHK(c, hipMemcpyAsync(t_mesh_of.p, mesh_of.data(), mesh_of.size() * 4, hipMemcpyHostToDevice, st));
-    fovpt_launch_flatten(st, ntri, (const uint3*)c->up_vidx.p, vtx, (float*)t_flat.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(st));
-    BvhBuildResult br;
-    float ms = 0.f;
-    { const int rc_ = build_hierarchy(c, st, (const float*)t_flat.p, (const uint32_t*)t_mesh_of.p, ntri, br, ms); if (rc_) return rc_; }
-    (void)hipFree(c->nodes);                           // (the device is idle: sync_all above, and the build synchronised)
-    adopt_hierarchy(c, br, ms);
-    c->cost_updates++;
-    return measure_built(c);
-}
-
-}  // namespace
 
 // The passes fovpt_render ran for the frame lp describes under cfg, whole (rows 0 .. gh) and on one rank: what
 // find_last_writer needs to give every pixel its writing pass and launch index; and lp's camera.  Computed on a copy: the
@@ -1062,12 +802,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     { const int rc_ = sync_all(c); if (rc_) return rc_; }
     free_scene(c);
     c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
-    c->up_vtx.release(); c->up_vidx.release();       // fovpt_update_vertices' device copies: made again on the scene's first update
-    c->refit_pending = false;
-    c->tm_tracking = c->tm_untracked = false;        // fovpt_temporal_motion's tracking: switched on again by its next call
-    c->tm_mark.release(); c->vtx_prev.release();
     { const int rc_ = expose_reset(c, nullptr); if (rc_) return rc_; }   // fovpt_expose adapts to another scene from scratch
-    c->rest_vtx.release(); c->mesh_absmax.clear();   // fovpt_update_transforms' rest positions: made again on the scene's first call
     take_costs(c);                                   // fovpt_hierarchy_cost: (the device is idle) no measurement of the old scene stays in flight
     c->cost_updates = c->cost_measured = 0;
     uint64_t ntri = 0;
@@ -1155,355 +890,6 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     c->scene_id |= 0x464f565000000000ull;          // 'FOVP' tag so a stale/foreign handle is recognisable
     if (traversable_out) *traversable_out = c->scene_id;
     return measure_built(c);
-}
-
-// ---- animated geometry (refit.hip) ---------------------------------------------------------------------------------------
-// Both entry points validate everything first (all or nothing); update_scene does the rest.
-int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_updates, int flags)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_vertices without a scene");
-    if (num_updates < 0 || (num_updates > 0 && !up)) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: %d updates at %p", num_updates, (const void*)up);
-    if (flags & ~(FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD)) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: unknown flag bits %d", flags);
-    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
-    const int nmesh = (int)c->mesh_nv.size();
-    std::vector<char> seen((size_t)nmesh, 0);
-    size_t floats = 0;
-    for (int k = 0; k < num_updates; k++) {
-        const fovpt_vertex_update& U = up[k];
-        if (U.mesh < 0 || U.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d of %d", U.mesh, nmesh);
-        if (seen[U.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d is listed twice", U.mesh);
-        seen[U.mesh] = 1;
-        if (U.num_vertices != c->mesh_nv[U.mesh])
-            return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d has %u vertices, the update %u", U.mesh, c->mesh_nv[U.mesh], U.num_vertices);
-        if (!U.vertex) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d has a null vertex pointer", U.mesh);
-        if (!device)
-            for (size_t i = 0; i < 3 * (size_t)U.num_vertices; i++)
-                if (!std::isfinite(U.vertex[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_vertices: mesh %d vertex %zu is not finite", U.mesh, i / 3);
-        floats += 3 * (size_t)U.num_vertices;
-    }
-    { const int rc_ = check_updatable(c, "fovpt_update_vertices"); if (rc_) return rc_; }
-    if (num_updates == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {up, device, floats, nullptr, num_updates, nullptr, nullptr};
-    return update_scene(c, src, rebuild);
-}
-
-// The rest positions of the named meshes through their matrices (k_transform_vertices), then fovpt_update_vertices' refit or
-// rebuild.  The overflow rule keeps every intermediate value finite, so no device memory has to be read to know the
-// coordinates are.
-int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int num, int flags)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_transforms without a scene");
-    if (num < 0 || (num > 0 && !tf)) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: %d transforms at %p", num, (const void*)tf);
-    if (flags & ~FOVPT_UPDATE_REBUILD) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: flag bits %d (FOVPT_UPDATE_REBUILD is the only one accepted)", flags);
-    const int nmesh = (int)c->mesh_nv.size();
-    if (num > 0) ensure_absmax(c);
-    std::vector<char> seen((size_t)nmesh, 0);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_transform& T = tf[k];
-        if (T.mesh < 0 || T.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d of %d", T.mesh, nmesh);
-        if (seen[T.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d is listed twice", T.mesh);
-        seen[T.mesh] = 1;
-        for (int i = 0; i < 12; i++)
-            if (!std::isfinite(T.m[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d matrix entry %d is not finite", T.mesh, i);
-        for (int r = 0; r < 3; r++) {
-            const float* row = T.m + 4 * r;
-            const double bound = (std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * c->mesh_absmax[T.mesh] + std::fabs((double)row[3]);
-            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_transforms: mesh %d row %d could overflow (bound %g > 2^127)", T.mesh, r, bound);
-        }
-    }
-    { const int rc_ = check_updatable(c, "fovpt_update_transforms"); if (rc_) return rc_; }
-    const bool rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
-    if (num == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {nullptr, false, 0, tf, num, nullptr, nullptr};
-    return update_scene(c, src, rebuild);
-}
-
-// The skins are kept on the host per mesh; every call lays the device copies out anew (the skinned meshes' vertices and joints
-// in mesh order), so a mesh's places in skin_joints / skin_weights / skin_pal are fixed until the next call.
-int fovpt_set_skins(fovpt_ctx* c, const fovpt_mesh_skin* skins, int num)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_set_skins without a scene");
-    if (num < 0 || (num > 0 && !skins)) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: %d skins at %p", num, (const void*)skins);
-    const int nmesh = (int)c->mesh_nv.size();
-    std::vector<char> seen((size_t)nmesh, 0);
-    std::vector<double> sums((size_t)(num > 0 ? num : 0), 0.0);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_skin& K = skins[k];
-        if (K.mesh < 0 || K.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d of %d", K.mesh, nmesh);
-        if (seen[K.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d is listed twice", K.mesh);
-        seen[K.mesh] = 1;
-        if (K._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: _reserved is %u", K.mesh, K._reserved);
-        if (K.num_vertices != c->mesh_nv[K.mesh])
-            return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d has %u vertices, not %u", K.mesh, c->mesh_nv[K.mesh], K.num_vertices);
-        if (K.num_joints > FOVPT_SKIN_MAX_JOINTS) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: %u joints (at most %d)", K.mesh, K.num_joints, FOVPT_SKIN_MAX_JOINTS);
-        if (K.num_joints == 0) {
-            if (K.joints || K.weights) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: no joints, but a pointer (removing a skin takes two null pointers)", K.mesh);
-            continue;
-        }
-        if (!K.joints || !K.weights) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d: null joints or weights", K.mesh);
-        for (size_t i = 0; i < 4 * (size_t)K.num_vertices; i++) {
-            if (K.joints[i] >= K.num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d vertex %zu: joint %u of %u", K.mesh, i / 4, (unsigned)K.joints[i], K.num_joints);
-            if (!(K.weights[i] >= 0.0f && K.weights[i] <= 1.0f)) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: mesh %d vertex %zu: weight %g is not in [0, 1]", K.mesh, i / 4, (double)K.weights[i]);
-        }
-        for (size_t i = 0; i < (size_t)K.num_vertices; i++) {
-            const float* w = K.weights + 4 * i;
-            sums[k] = std::fmax(sums[k], (((double)w[0] + (double)w[1]) + (double)w[2]) + (double)w[3]);
-        }
-    }
-    if (num == 0) return FOVPT_OK;
-    // the new layout, and its device buffers before anything changes
-    std::vector<uint32_t> nj((size_t)nmesh, 0);
-    for (int m = 0; m < nmesh; m++) nj[m] = c->skins.empty() ? 0 : c->skins[m].num_joints;
-    for (int k = 0; k < num; k++) nj[skins[k].mesh] = skins[k].num_joints;
-    size_t verts = 0, joints = 0;
-    for (int m = 0; m < nmesh; m++)
-        if (nj[m]) { verts += c->mesh_nv[m]; joints += nj[m]; }
-    if (verts >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "fovpt_set_skins: more than 2^32 - 1 skinned vertices");
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf d_joints, d_weights, d_pal;
-    if (joints) {
-        HIPCHK(c, d_joints.reserve(verts ? verts * 8 : 8));
-        HIPCHK(c, d_weights.reserve(verts ? verts * 16 : 16));
-        HIPCHK(c, d_pal.reserve(joints * 48));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_skinned in flight reads the buffers about to go
-    if (c->skins.empty()) c->skins.resize((size_t)nmesh);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_skin& K = skins[k];
-        fovpt_ctx::Skin& D = c->skins[K.mesh];
-        D.num_joints = K.num_joints; D.S = sums[k];
-        if (K.num_joints) { D.joints.assign(K.joints, K.joints + 4 * (size_t)K.num_vertices); D.weights.assign(K.weights, K.weights + 4 * (size_t)K.num_vertices); }
-        else { std::vector<uint16_t>().swap(D.joints); std::vector<float>().swap(D.weights); }
-    }
-    uint32_t first = 0, pal_first = 0;
-    for (int m = 0; m < nmesh; m++) {
-        fovpt_ctx::Skin& D = c->skins[m];
-        D.first = first; D.pal_first = pal_first;
-        if (!D.num_joints) continue;
-        if (c->mesh_nv[m]) {
-            HIPCHK(c, hipMemcpy((char*)d_joints.p + 8 * (size_t)first, D.joints.data(), 8 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy((char*)d_weights.p + 16 * (size_t)first, D.weights.data(), 16 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
-        }
-        first += c->mesh_nv[m]; pal_first += D.num_joints;
-    }
-    std::swap(c->skin_joints.p, d_joints.p); std::swap(c->skin_joints.bytes, d_joints.bytes);
-    std::swap(c->skin_weights.p, d_weights.p); std::swap(c->skin_weights.bytes, d_weights.bytes);
-    std::swap(c->skin_pal.p, d_pal.p); std::swap(c->skin_pal.bytes, d_pal.bytes);
-    return FOVPT_OK;
-}
-
-// The rest positions of the named meshes through the blends of their palettes (k_skin_vertices), then fovpt_update_vertices'
-// refit or rebuild.  For host palettes the overflow rule keeps every intermediate value finite, as fovpt_update_transforms' does.
-int fovpt_update_skinned(fovpt_ctx* c, const fovpt_skin_pose* poses, int num, int flags)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_skinned without a scene");
-    if (num < 0 || (num > 0 && !poses)) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: %d poses at %p", num, (const void*)poses);
-    if (flags & ~(FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD)) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: unknown flag bits %d", flags);
-    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
-    const int nmesh = (int)c->mesh_nv.size();
-    if (num > 0 && !device) ensure_absmax(c);
-    std::vector<char> seen((size_t)nmesh, 0);
-    size_t floats = 0;
-    for (int k = 0; k < num; k++) {
-        const fovpt_skin_pose& P = poses[k];
-        if (P.mesh < 0 || P.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d of %d", P.mesh, nmesh);
-        if (seen[P.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d is listed twice", P.mesh);
-        seen[P.mesh] = 1;
-        if (c->skins.empty() || !c->skins[P.mesh].num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d has no skin", P.mesh);
-        const fovpt_ctx::Skin& K = c->skins[P.mesh];
-        if (P.num_joints != K.num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d: %u joints, its skin has %u", P.mesh, P.num_joints, K.num_joints);
-        if (!P.matrices) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d: null matrices", P.mesh);
-        floats += 12 * (size_t)P.num_joints;
-        if (device) continue;
-        for (size_t i = 0; i < 12 * (size_t)P.num_joints; i++)
-            if (!std::isfinite(P.matrices[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d joint %zu entry %zu is not finite", P.mesh, i / 12, i % 12);
-        for (size_t r = 0; r < 3 * (size_t)P.num_joints; r++) {
-            const float* row = P.matrices + 4 * r;
-            const double bound = K.S * ((std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * c->mesh_absmax[P.mesh] + std::fabs((double)row[3]));
-            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d joint %zu row %zu could overflow (bound %g > 2^127)", P.mesh, r / 3, r % 3, bound);
-            // (the blended matrix is formed first: its entries are within S times the palette's, which the row's bound covers
-            // for the fourth column and, for the others, only when A >= 1)
-            const double entry = K.S * std::fmax(std::fmax(std::fabs((double)row[0]), std::fabs((double)row[1])), std::fabs((double)row[2]));
-            if (entry > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_skinned: mesh %d joint %zu row %zu: a blended entry could overflow (%g > 2^127)", P.mesh, r / 3, r % 3, entry);
-        }
-    }
-    { const int rc_ = check_updatable(c, "fovpt_update_skinned"); if (rc_) return rc_; }
-    if (num == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {nullptr, device, floats, nullptr, num, poses, nullptr};
-    return update_scene(c, src, rebuild);
-}
-
-// The morph targets are kept on the host per mesh, transposed into a per-vertex list of {delta, target} records sorted by
-// target (what the kernel walks: the order of the definition is the order in memory, and one launch does a whole pose; a pass per
-// active target would need ordering between passes).  Every call lays the device copies out anew (the morphed meshes' offsets,
-// entries and weights in mesh order), so a mesh's places in morph_off / morph_ent / morph_w are fixed until the next call.
-int fovpt_set_morphs(fovpt_ctx* c, const fovpt_mesh_morph* morphs, int num)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_set_morphs without a scene");
-    if (num < 0 || (num > 0 && !morphs)) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: %d morphs at %p", num, (const void*)morphs);
-    const int nmesh = (int)c->mesh_nv.size();
-    std::vector<char> seen((size_t)nmesh, 0);
-    std::vector<size_t> entries((size_t)(num > 0 ? num : 0), 0);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_morph& K = morphs[k];
-        if (K.mesh < 0 || K.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d of %d", K.mesh, nmesh);
-        if (seen[K.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d is listed twice", K.mesh);
-        seen[K.mesh] = 1;
-        if (K._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: _reserved is %u", K.mesh, K._reserved);
-        const uint32_t nv = c->mesh_nv[K.mesh];
-        if (K.num_vertices != nv) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d has %u vertices, not %u", K.mesh, nv, K.num_vertices);
-        if (K.num_targets > FOVPT_MORPH_MAX_TARGETS) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: %u targets (at most %d)", K.mesh, K.num_targets, FOVPT_MORPH_MAX_TARGETS);
-        if (K.num_targets == 0) {
-            if (K.targets) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: no targets, but a pointer (removing morphs takes a null pointer)", K.mesh);
-            continue;
-        }
-        if (!K.targets) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d: null targets", K.mesh);
-        for (uint32_t t = 0; t < K.num_targets; t++) {
-            const fovpt_morph_target& T = K.targets[t];
-            if (T._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: _reserved is %u", K.mesh, t, T._reserved);
-            if (T.count > nv) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: %u entries for %u vertices", K.mesh, t, T.count, nv);
-            if (!T.index && T.count != 0 && T.count != nv)
-                return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: no indices, but %u entries for %u vertices", K.mesh, t, T.count, nv);
-            if (!T.delta && T.count) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u: null delta", K.mesh, t);
-            entries[k] += T.count;
-        }
-    }
-    if (num == 0) return FOVPT_OK;
-    // the new layout (its size is known from the counts alone: checked before the entries themselves are read)
-    std::vector<uint32_t> nt((size_t)nmesh, 0);
-    std::vector<size_t> ne((size_t)nmesh, 0);
-    for (int m = 0; m < nmesh && !c->morphs.empty(); m++) { nt[m] = c->morphs[m].num_targets; ne[m] = c->morphs[m].ent.size(); }
-    for (int k = 0; k < num; k++) { nt[morphs[k].mesh] = morphs[k].num_targets; ne[morphs[k].mesh] = entries[k]; }
-    size_t offs = 0, ents = 0, targets = 0;
-    for (int m = 0; m < nmesh; m++)
-        if (nt[m]) { offs += (size_t)c->mesh_nv[m] + 1; ents += ne[m]; targets += nt[m]; }
-    if (ents >= (1ull << 32) || offs >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: more than 2^32 - 1 entries (%zu) or offsets (%zu)", ents, offs);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_morph& K = morphs[k];
-        for (uint32_t t = 0; t < K.num_targets; t++) {
-            const fovpt_morph_target& T = K.targets[t];
-            for (uint32_t i = 0; T.index && i < T.count; i++) {
-                if (T.index[i] >= K.num_vertices) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u entry %u: vertex %u of %u", K.mesh, t, i, T.index[i], K.num_vertices);
-                if (i && T.index[i] <= T.index[i - 1]) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u entry %u: indices are not strictly ascending", K.mesh, t, i);
-            }
-            for (size_t i = 0; i < 3 * (size_t)T.count; i++)
-                if (!std::isfinite(T.delta[i])) return fail(c, FOVPT_E_INVALID, "fovpt_set_morphs: mesh %d target %u entry %zu: a delta is not finite", K.mesh, t, i / 3);
-        }
-    }
-    // the named meshes' targets, transposed: a count per vertex, its running sum, then the targets in ascending order
-    std::vector<fovpt_ctx::Morph> fresh((size_t)num);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_morph& K = morphs[k];
-        fovpt_ctx::Morph& D = fresh[k];
-        D.num_targets = K.num_targets;
-        if (!K.num_targets) continue;
-        const uint32_t nv = K.num_vertices;
-        D.D.assign(K.num_targets, 0.0);
-        D.off.assign((size_t)nv + 1, 0);
-        for (uint32_t t = 0; t < K.num_targets; t++)
-            for (uint32_t i = 0; i < K.targets[t].count; i++) D.off[(K.targets[t].index ? K.targets[t].index[i] : i) + 1]++;
-        for (uint32_t i = 0; i < nv; i++) D.off[i + 1] += D.off[i];
-        D.ent.resize(entries[k]);
-        std::vector<uint32_t> fill(D.off.begin(), D.off.end() - 1);
-        for (uint32_t t = 0; t < K.num_targets; t++) {
-            const fovpt_morph_target& T = K.targets[t];
-            for (uint32_t i = 0; i < T.count; i++) {
-                const float* d = T.delta + 3 * (size_t)i;
-                D.ent[fill[T.index ? T.index[i] : i]++] = MorphEntry{d[0], d[1], d[2], t};
-                D.D[t] = std::fmax(D.D[t], std::fmax(std::fabs((double)d[0]), std::fmax(std::fabs((double)d[1]), std::fabs((double)d[2]))));
-            }
-        }
-    }
-    // the device buffers before anything changes
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf d_off, d_ent, d_w;
-    if (targets) {
-        HIPCHK(c, d_off.reserve(offs * 4));
-        HIPCHK(c, d_ent.reserve(ents ? ents * 16 : 16));
-        HIPCHK(c, d_w.reserve(targets * 4));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_morphed in flight reads the buffers about to go
-    if (c->morphs.empty()) c->morphs.resize((size_t)nmesh);
-    for (int k = 0; k < num; k++) c->morphs[morphs[k].mesh] = std::move(fresh[k]);
-    uint32_t off_first = 0, ent_first = 0, w_first = 0;
-    std::vector<uint32_t> abs_off;
-    for (int m = 0; m < nmesh; m++) {
-        fovpt_ctx::Morph& D = c->morphs[m];
-        D.off_first = off_first; D.ent_first = ent_first; D.w_first = w_first;
-        if (!D.num_targets) continue;
-        abs_off.resize(D.off.size());
-        for (size_t i = 0; i < D.off.size(); i++) abs_off[i] = ent_first + D.off[i];
-        HIPCHK(c, hipMemcpy((uint32_t*)d_off.p + off_first, abs_off.data(), 4 * abs_off.size(), hipMemcpyHostToDevice));
-        if (!D.ent.empty()) HIPCHK(c, hipMemcpy((MorphEntry*)d_ent.p + ent_first, D.ent.data(), 16 * D.ent.size(), hipMemcpyHostToDevice));
-        off_first += (uint32_t)D.off.size(); ent_first += (uint32_t)D.ent.size(); w_first += D.num_targets;
-    }
-    std::swap(c->morph_off.p, d_off.p); std::swap(c->morph_off.bytes, d_off.bytes);
-    std::swap(c->morph_ent.p, d_ent.p); std::swap(c->morph_ent.bytes, d_ent.bytes);
-    std::swap(c->morph_w.p, d_w.p); std::swap(c->morph_w.bytes, d_w.bytes);
-    return FOVPT_OK;
-}
-
-// The rest positions of the named meshes plus their weighted deltas (k_morph_vertices), through the skin where a pose has a
-// palette (k_morph_skin_vertices), then fovpt_update_vertices' refit or rebuild.  For host data the overflow rules keep every
-// intermediate value finite.
-int fovpt_update_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, int flags)
-{
-    if (!c) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_update_morphed without a scene");
-    if (num < 0 || (num > 0 && !poses)) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: %d poses at %p", num, (const void*)poses);
-    if (flags & ~(FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD)) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: unknown flag bits %d", flags);
-    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
-    const int nmesh = (int)c->mesh_nv.size();
-    if (num > 0 && !device) ensure_absmax(c);
-    std::vector<char> seen((size_t)nmesh, 0);
-    size_t floats = 0;
-    for (int k = 0; k < num; k++) {
-        const fovpt_morph_pose& P = poses[k];
-        if (P.mesh < 0 || P.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d of %d", P.mesh, nmesh);
-        if (seen[P.mesh]) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d is listed twice", P.mesh);
-        seen[P.mesh] = 1;
-        if (P._reserved) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: _reserved is %u", P.mesh, P._reserved);
-        if (c->morphs.empty() || !c->morphs[P.mesh].num_targets) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d has no morph targets", P.mesh);
-        const fovpt_ctx::Morph& M = c->morphs[P.mesh];
-        if (P.num_targets != M.num_targets) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: %u targets, the mesh has %u", P.mesh, P.num_targets, M.num_targets);
-        if (!P.weights) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: null weights", P.mesh);
-        if ((P.matrices == nullptr) != (P.num_joints == 0))
-            return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: %u joints with matrices at %p", P.mesh, P.num_joints, (const void*)P.matrices);
-        const fovpt_ctx::Skin* K = nullptr;
-        if (P.num_joints) {
-            if (c->skins.empty() || !c->skins[P.mesh].num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d has no skin", P.mesh);
-            K = &c->skins[P.mesh];
-            if (P.num_joints != K->num_joints) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: %u joints, its skin has %u", P.mesh, P.num_joints, K->num_joints);
-        }
-        floats += (size_t)P.num_targets + 12 * (size_t)P.num_joints;
-        if (device) continue;
-        double B = c->mesh_absmax[P.mesh];
-        for (uint32_t t = 0; t < P.num_targets; t++) {
-            if (!std::isfinite(P.weights[t])) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d: weight %u is not finite", P.mesh, t);
-            B += std::fabs((double)P.weights[t]) * M.D[t];
-        }
-        if (B > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d could overflow (bound %g > 2^127)", P.mesh, B);
-        if (!K) continue;
-        for (size_t i = 0; i < 12 * (size_t)P.num_joints; i++)
-            if (!std::isfinite(P.matrices[i])) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d joint %zu entry %zu is not finite", P.mesh, i / 12, i % 12);
-        for (size_t r = 0; r < 3 * (size_t)P.num_joints; r++) {
-            // fovpt_update_skinned's two rules, with the morphed positions' bound B in A's place
-            const float* row = P.matrices + 4 * r;
-            const double bound = K->S * ((std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * B + std::fabs((double)row[3]));
-            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d joint %zu row %zu could overflow (bound %g > 2^127)", P.mesh, r / 3, r % 3, bound);
-            const double entry = K->S * std::fmax(std::fmax(std::fabs((double)row[0]), std::fabs((double)row[1])), std::fabs((double)row[2]));
-            if (entry > 0x1p127) return fail(c, FOVPT_E_INVALID, "fovpt_update_morphed: mesh %d joint %zu row %zu: a blended entry could overflow (%g > 2^127)", P.mesh, r / 3, r % 3, entry);
-        }
-    }
-    { const int rc_ = check_updatable(c, "fovpt_update_morphed"); if (rc_) return rc_; }
-    if (num == 0 && !rebuild) return FOVPT_OK;
-    const UpdateSource src = {nullptr, device, floats, nullptr, num, nullptr, poses};
-    return update_scene(c, src, rebuild);
 }
 
 int fovpt_hierarchy_cost(fovpt_ctx* c, int flags, fovpt_hierarchy_cost_info* out)

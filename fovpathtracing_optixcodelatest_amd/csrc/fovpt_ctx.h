@@ -1,5 +1,5 @@
-// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_post.hip, api_gather.hip, api_packet.hip): the context, the buffers it
-// owns, and the helpers more than one of the three files uses.  Host only: no kernel file includes it.
+// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_animate.hip, api_post.hip, api_gather.hip, api_packet.hip): the
+// context, the buffers it owns, and the helpers more than one of those files uses.  Host only: no kernel file includes it.
 #pragma once
 #include <string>
 #include <vector>
@@ -25,6 +25,7 @@ struct DevBuf {
         return e;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    void swap(DevBuf& o) { void* q = p; p = o.p; o.p = q; const size_t n = bytes; bytes = o.bytes; o.bytes = n; }
 };
 
 enum TimedKind { T_GENERATE, T_TRACE, T_SHADE, T_SHADOW, T_RESOLVE };    // what a timed launch adds to in fovpt_stats
@@ -215,6 +216,13 @@ int sync_all(fovpt_ctx* c);
 SceneView scene_view(const fovpt_ctx* c);
 void set_camera(FrameDev& fd, const fovpt_launch_params* lp);
 void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd);
+// fovpt_api.hip: the hierarchy build of fovpt_set_scene and the measurements of fovpt_hierarchy_cost, which a rebuild and a refit use
+int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br, float& ms);
+void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms);
+int enqueue_cost(fovpt_ctx* c, hipStream_t st, uint64_t update, fovpt_ctx::CostSlot** out);
+int measure_built(fovpt_ctx* c);
+// api_animate.hip (fovpt_set_scene and the context's destructor drop what the update calls keep of a scene)
+void drop_animation(fovpt_ctx* c);
 // api_post.hip (fovpt_resize keeps the buffers of the post-processing calls at the frame's size)
 int reserve_gbuffer(fovpt_ctx* c, size_t n);
 int reserve_temporal(fovpt_ctx* c, size_t n);

@@ -550,6 +550,40 @@ class SampleRenderer:
         width x height rgba8 pixels; those no texel reaches keep their contents).  Enqueued on the renderer's stream."""
         self._check(self._L.fovpt_packet_decode(self._ctx, C.byref(header), packet, int(mode), out_rgba))
 
+    # -- what update_vertices, update_skinned and update_morphed share
+    @staticmethod
+    def _all_device(who, values):
+        """All host or all device: True when there are values and every one is a CUDA tensor; a mix raises ValueError."""
+        on_device = [hasattr(v, "is_cuda") and bool(v.is_cuda) for v in values]
+        if any(on_device) and not all(on_device):
+            raise ValueError("%s: mixes host arrays and device tensors" % who)
+        return bool(on_device) and all(on_device)
+
+    @staticmethod
+    def _host_palette(who, mesh, m, noun):
+        """A (J, 3, 4) array, or a (J, 4, 4) one whose last rows are 0 0 0 1, as contiguous (J, 3, 4) float32."""
+        m = np.asarray(m, np.float32)
+        if m.ndim == 3 and m.shape[1:] == (4, 4):
+            if not (m[:, 3] == np.float32([0, 0, 0, 1])).all():
+                raise ValueError("%s: mesh %d: the last row of a (4, 4) matrix must be 0 0 0 1" % (who, mesh))
+            m = m[:, :3]
+        if m.ndim != 3 or m.shape[1:] != (3, 4):
+            raise ValueError("%s: mesh %d needs a (J, 3, 4) or (J, 4, 4) %s" % (who, mesh, noun))
+        return np.ascontiguousarray(m)
+
+    @staticmethod
+    def _device_palette(who, mesh, m):
+        """The device pointer of a contiguous float32 (J, 3, 4) CUDA tensor."""
+        import torch
+        if m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (3, 4) or not m.is_contiguous():
+            raise ValueError("%s: mesh %d needs a contiguous (J, 3, 4) float32 tensor" % (who, mesh))
+        return m.data_ptr()
+
+    def _update(self, fn, entries, num, device, rebuild, keep):
+        self._check(fn(self._ctx, entries, num, (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)))
+        if device:
+            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+
     # -- animated geometry (include/fovpt.h, fovpt_update_vertices): optixAccelBuild(OPERATION_UPDATE) over the same build inputs
     def update_vertices(self, updates, rebuild=False):
         """New vertex positions for meshes of the scene: updates maps a mesh index to an (n, 3) float32 numpy array, or to a
@@ -557,10 +591,7 @@ class SampleRenderer:
         before the call).  All host or all device.  rebuild=False refits the hierarchy asynchronously; True builds it anew
         (synchronous).  The renderer's Model is not changed."""
         items = sorted(updates.items())
-        on_device = [hasattr(v, "is_cuda") and bool(v.is_cuda) for _, v in items]
-        if any(on_device) and not all(on_device):
-            raise ValueError("update_vertices: mixes host arrays and device tensors")
-        device = bool(items) and all(on_device)
+        device = self._all_device("update_vertices", updates.values())
         ups = (abi.VertexUpdate * max(1, len(items)))()
         keep = []
         for k, (mesh, v) in enumerate(items):
@@ -577,10 +608,7 @@ class SampleRenderer:
                 ptr, n = v.ctypes.data, v.shape[0]
             keep.append(v)
             ups[k].mesh, ups[k].num_vertices, ups[k].vertex = int(mesh), int(n), ptr
-        flags = (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)
-        self._check(self._L.fovpt_update_vertices(self._ctx, ups, len(items), flags))
-        if device:
-            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+        self._update(self._L.fovpt_update_vertices, ups, len(items), device, rebuild, keep)
 
     # -- rigid motion and the cost of the refit tree (include/fovpt.h, fovpt_update_transforms / fovpt_hierarchy_cost)
     def update_transforms(self, transforms, rebuild=False):
@@ -644,34 +672,18 @@ class SampleRenderer:
         weighted sum of its four joints' matrices on the device; absolute, not cumulative; then update_vertices()' refit (or,
         rebuild=True, rebuild) with the same ordering.  Bad shapes raise ValueError.  The renderer's Model is not changed."""
         items = sorted(poses.items())
-        on_device = [hasattr(v, "is_cuda") and bool(v.is_cuda) for _, v in items]
-        if any(on_device) and not all(on_device):
-            raise ValueError("update_skinned: mixes host arrays and device tensors")
-        device = bool(items) and all(on_device)
+        device = self._all_device("update_skinned", poses.values())
         ps = (abi.SkinPose * max(1, len(items)))()
         keep = []
         for k, (mesh, m) in enumerate(items):
             if device:
-                import torch
-                if m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (3, 4) or not m.is_contiguous():
-                    raise ValueError("update_skinned: mesh %d needs a contiguous (J, 3, 4) float32 tensor" % mesh)
-                ptr = m.data_ptr()
+                ptr = self._device_palette("update_skinned", mesh, m)
             else:
-                m = np.asarray(m, np.float32)
-                if m.ndim == 3 and m.shape[1:] == (4, 4):
-                    if not (m[:, 3] == np.float32([0, 0, 0, 1])).all():
-                        raise ValueError("update_skinned: mesh %d: the last row of a (4, 4) matrix must be 0 0 0 1" % mesh)
-                    m = m[:, :3]
-                if m.ndim != 3 or m.shape[1:] != (3, 4):
-                    raise ValueError("update_skinned: mesh %d needs a (J, 3, 4) or (J, 4, 4) array" % mesh)
-                m = np.ascontiguousarray(m)
+                m = self._host_palette("update_skinned", mesh, m, "array")
                 ptr = m.ctypes.data
             keep.append(m)
             ps[k].mesh, ps[k].num_joints, ps[k].matrices = int(mesh), int(m.shape[0]), ptr
-        flags = (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)
-        self._check(self._L.fovpt_update_skinned(self._ctx, ps, len(items), flags))
-        if device:
-            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+        self._update(self._L.fovpt_update_skinned, ps, len(items), device, rebuild, keep)
 
     # -- morph targets (include/fovpt.h, fovpt_set_morphs / fovpt_update_morphed)
     def set_morphs(self, morphs):
@@ -719,10 +731,7 @@ class SampleRenderer:
         refit (or, rebuild=True, rebuild) with the same ordering.  Bad shapes raise ValueError.  The renderer's Model is not
         changed."""
         items = [(mesh, v if isinstance(v, tuple) else (v, None)) for mesh, v in sorted(poses.items())]
-        on_device = [hasattr(x, "is_cuda") and bool(x.is_cuda) for _, v in items for x in v if x is not None]
-        if any(on_device) and not all(on_device):
-            raise ValueError("update_morphed: mixes host arrays and device tensors")
-        device = bool(on_device) and all(on_device)
+        device = self._all_device("update_morphed", [x for _, v in items for x in v if x is not None])
         ps = (abi.MorphPose * max(1, len(items)))()
         keep = []
         for k, (mesh, (w, m)) in enumerate(items):
@@ -730,30 +739,18 @@ class SampleRenderer:
                 import torch
                 if w.dtype != torch.float32 or w.dim() != 1 or not w.is_contiguous():
                     raise ValueError("update_morphed: mesh %d needs a contiguous (T,) float32 tensor of weights" % mesh)
-                if m is not None and (m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (3, 4) or not m.is_contiguous()):
-                    raise ValueError("update_morphed: mesh %d needs a contiguous (J, 3, 4) float32 tensor" % mesh)
-                wp, mp = w.data_ptr(), (None if m is None else m.data_ptr())
+                wp, mp = w.data_ptr(), (None if m is None else self._device_palette("update_morphed", mesh, m))
             else:
                 w = np.ascontiguousarray(w, np.float32)
                 if w.ndim != 1:
                     raise ValueError("update_morphed: mesh %d needs a (T,) array of weights" % mesh)
                 if m is not None:
-                    m = np.asarray(m, np.float32)
-                    if m.ndim == 3 and m.shape[1:] == (4, 4):
-                        if not (m[:, 3] == np.float32([0, 0, 0, 1])).all():
-                            raise ValueError("update_morphed: mesh %d: the last row of a (4, 4) matrix must be 0 0 0 1" % mesh)
-                        m = m[:, :3]
-                    if m.ndim != 3 or m.shape[1:] != (3, 4):
-                        raise ValueError("update_morphed: mesh %d needs a (J, 3, 4) or (J, 4, 4) palette" % mesh)
-                    m = np.ascontiguousarray(m)
+                    m = self._host_palette("update_morphed", mesh, m, "palette")
                 wp, mp = w.ctypes.data, (None if m is None else m.ctypes.data)
             keep += [w, m]
             ps[k].mesh, ps[k].num_targets, ps[k].weights = int(mesh), int(w.shape[0]), wp
             ps[k].num_joints, ps[k].matrices = (0 if m is None else int(m.shape[0])), mp
-        flags = (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)
-        self._check(self._L.fovpt_update_morphed(self._ctx, ps, len(items), flags))
-        if device:
-            self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
+        self._update(self._L.fovpt_update_morphed, ps, len(items), device, rebuild, keep)
 
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
