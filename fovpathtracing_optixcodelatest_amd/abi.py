@@ -152,6 +152,29 @@ class MeshTransform(C.Structure):
 DEBUG_PROBE_PLAIN = 1                           # fovpt_debug_probe_sample / _probe_eval flag (FOVPT_DEBUG_PROBE_PLAIN)
 PROBE_PATH_GUIDED, PROBE_PATH_RECORDS, PROBE_PATH_ONE_ROW = 1, 2, 4   # their *path_out bits (FOVPT_PROBE_PATH_*)
 COST_WAIT = 1                                   # fovpt_hierarchy_cost flag (FOVPT_COST_WAIT)
+STATE_DONE, STATE_SECONDARY, STATE_ALPHA_ONE, STATE_ALPHA_SET = 1, 2, 4, 8   # a sample slot's flags, below depth << 8 (fovpt_debug_resolve)
+
+
+class DebugPass(C.Structure):
+    """struct fovpt_debug_pass: one pass of the frame fovpt_debug_resolve resolves, and its place in the caller's arrays."""
+    _fields_ = [("gw", C.c_uint32), ("rows", C.c_uint32), ("spp", C.c_uint32), ("slot_base", C.c_uint32), ("launch_base", C.c_uint32)]
+
+
+DEBUG_SHADE_FILL = 0xcd                         # FOVPT_DEBUG_SHADE_FILL: the byte fovpt_debug_shade fills every output buffer with
+
+
+class DebugShadeLaunch(C.Structure):
+    """struct fovpt_debug_shade_launch."""
+    _fields_ = [("n", C.c_int32), ("depth_iter", C.c_int32), ("grid", C.c_int32), ("partition", C.c_int32), ("sel", C.c_uint32),
+                ("shard_count", C.c_uint32 * 8)]
+
+
+class DebugShadeResult(C.Structure):
+    """struct fovpt_debug_shade_result: host arrays of the caller's, and what the call counted."""
+    _fields_ = [(k, C.c_void_p) for k in ("rng4", "thr4", "rad4", "alpha4", "guide_n4", "guide_a4", "next_place2", "next_o4", "next_d4",
+                                          "shadow_place2", "shadow_o4", "shadow_d4", "shadow_vis4", "shadow_occ4")] + [
+        ("next_count", C.c_uint32 * 8), ("shadow_count", C.c_uint32 * 8),
+        ("next_found", C.c_uint32), ("shadow_found", C.c_uint32), ("counters_changed", C.c_uint32), ("cap", C.c_uint32)]
 
 
 class HierarchyCost(C.Structure):

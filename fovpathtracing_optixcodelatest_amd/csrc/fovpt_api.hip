@@ -290,14 +290,16 @@ ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe)
     return pp;
 }
 
-// One wavefront job: generate -> (closest, shade, occlusion) x depth -> resolve over the given passes / row ranges.
-int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame)
+// What the kernels see of a frame: the passes (with their places in the job's sample slots and launch records), the camera, the
+// probe and how it is searched, the caller's frame buffers and the configuration.  One function for run_job and for
+// fovpt_debug_resolve, so that the test hook resolves the frame a job of the same parameters would.
+int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame, FrameDev& fd,
+              uint64_t& slots, uint64_t& launches)
 {
-    FrameDev fd;
     memset(&fd, 0, sizeof(fd));
     fd.chunked = chunked;
     fd.zero_holes = (whole_frame && !chunked && c->cfg.world > 1 && c->cfg.rank != 0) ? 1 : 0;
-    uint64_t slots = 0, launches = 0;
+    slots = 0; launches = 0;
     for (int p = 0; p < npass; p++) {
         PassDev P = passes_in[p];
         const uint64_t rows = P.row1 - P.row0;
@@ -328,6 +330,15 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     fd.partition = !c->cfg.uniform;      // direction classes in k_shade's appends: foveated frames gain, uniform ones lose
     fd.rank = c->cfg.rank; fd.world = c->cfg.world < 1 ? 1 : c->cfg.world;
     fd.tile_w = c->cfg.tile_w > 0 ? c->cfg.tile_w : 8; fd.tile_h = c->cfg.tile_h > 0 ? c->cfg.tile_h : 4;
+    return FOVPT_OK;
+}
+
+// One wavefront job: generate -> (closest, shade, occlusion) x depth -> resolve over the given passes / row ranges.
+int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame)
+{
+    FrameDev fd;
+    uint64_t slots = 0, launches = 0;
+    { const int rc_ = frame_dev(c, lp, passes_in, npass, chunked, whole_frame, fd, slots, launches); if (rc_) return rc_; }
 
     if (slots == 0) return FOVPT_OK;
     // a refit enqueued on fovpt_stream() since the last job (fovpt_update_vertices): every stream that may trace the scene or read
@@ -1244,6 +1255,231 @@ int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* d
             occluded_out[i] = v == 2.f ? 1 : 0;
         }
     }
+    return FOVPT_OK;
+}
+
+// test hook: the PRODUCTION shading kernel on caller-made hits -- one launch of fovpt_launch_shade (k_shade<false> or <true> by the
+// configured options, as run_job launches it) over an input queue the caller laid out, and everything the kernel left: the slots'
+// state, the counters and the occupied entries of the next radiance queue and of the shadow queue.  Every buffer the kernel may
+// write is filled with the byte FOVPT_DEBUG_SHADE_FILL first, so that "not written" can be told from "written with zero".
+int fovpt_debug_shade(fovpt_ctx* c, const fovpt_probe* probe, const fovpt_debug_shade_launch* in, const float* origin3, const float* dir4,
+                      const uint32_t* prim, const float* tuv3, const uint32_t* rng3, const float* thr4, fovpt_debug_shade_result* out)
+{
+    if (!c || !probe || !in || !out || in->n < 0 || (in->n && (!origin3 || !dir4 || !prim || !tuv3 || !rng3 || !thr4))) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_shade without a scene");
+    if (!probe->data || !probe->cdfValuesX || !probe->cdfValuesY || !probe->pdfValuesX || !probe->pdfValuesY || probe->width <= 0 || probe->height <= 0)
+        return fail(c, FOVPT_E_NO_PROBE, "fovpt_debug_shade with an incomplete probe");
+    const int n = in->n;
+    if (in->sel > 2u || in->grid < 1 || in->grid > 4096 || in->depth_iter < 0 || in->depth_iter + 1 >= FOVPT_MAX_ITERS)
+        return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: sel %u, grid %d, depth_iter %d", in->sel, in->grid, in->depth_iter);
+    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
+    if (c->cfg.write_guides && c->any_catcher) return fail(c, FOVPT_E_INVALID, "write_guides is not available with shadow-catcher materials");
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+        const bool selected = in->sel == 0u || (in->sel == 1u) == (s < 4u);
+        if (in->shard_count[s] && !selected) return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: input in shard %u outside the selection %u", s, in->sel);
+        total += in->shard_count[s];
+    }
+    if (total != (uint64_t)n) return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: the shards hold %llu inputs, n = %d", (unsigned long long)total, n);
+    const size_t D = (size_t)c->cfg.max_depth, un = (size_t)n;
+    const bool guides = c->cfg.write_guides != 0;
+    if (n && (!out->rng4 || !out->thr4 || !out->rad4 || !out->alpha4 || (guides && (!out->guide_n4 || !out->guide_a4)) || !out->next_place2
+              || !out->next_o4 || !out->next_d4 || !out->shadow_place2 || !out->shadow_o4 || !out->shadow_d4 || !out->shadow_vis4 || !out->shadow_occ4))
+        return FOVPT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    StateSet& S = c->set[(c->last_set + 1u) % 2u];                  // (the device is idle: any set will do)
+    const size_t slots = (un ? un : 1u) * FOVPT_SHARDS;             // any one shard can hold everything
+    hipStream_t st = c->stream;
+    { const int rc_ = ensure_state(c, S, slots, 1, st); if (rc_) return rc_; }
+    const uint32_t cap = shard_capacity(slots);
+    const size_t qn = (size_t)cap * FOVPT_SHARDS, v = 16;
+    // leaf-order record of a primitive: the first one when spatial splits made several (the inverse of fovpt_debug_trace's map)
+    std::vector<TriRec> tris(c->num_tris);
+    HIPCHK(c, hipMemcpy(tris.data(), c->tris, sizeof(TriRec) * (size_t)c->num_tris, hipMemcpyDeviceToHost));
+    uint32_t nprim = 0;
+    for (const TriRec& T : tris) nprim = T.prim + 1u > nprim ? T.prim + 1u : nprim;
+    std::vector<uint32_t> first(nprim, 0xffffffffu);
+    for (size_t k = tris.size(); k-- > 0;) first[tris[k].prim] = (uint32_t)k;
+    // the input queue: shard s holds the next shard_count[s] hits, in order; slot of hit i = i
+    std::vector<float> qo(qn * 4, 0.f), qd(qn * 4, 0.f), hit(qn * 4, 0.f);
+    std::vector<uint32_t> rng(un * 4, 0u);
+    size_t i = 0;
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++)
+        for (uint32_t k = 0; k < in->shard_count[s]; k++, i++) {
+            const size_t ph = (size_t)s * cap + k;
+            const uint32_t slot = (uint32_t)i;
+            for (int a = 0; a < 3; a++) { qo[4 * ph + a] = origin3[3 * i + a]; hit[4 * ph + a] = tuv3[3 * i + a]; }
+            memcpy(&qo[4 * ph + 3], &slot, 4);
+            for (int a = 0; a < 4; a++) qd[4 * ph + a] = dir4[4 * i + a];
+            uint32_t tpos = 0xffffffffu;
+            if (prim[i] != 0xffffffffu) {
+                if (prim[i] >= nprim || first[prim[i]] == 0xffffffffu) return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: hit %zu names primitive %u", i, prim[i]);
+                tpos = first[prim[i]] * 3u;                                   // offset in 16-byte units, a record is 48 bytes
+            }
+            memcpy(&hit[4 * ph + 3], &tpos, 4);
+            rng[4 * i] = rng3[3 * i]; rng[4 * i + 1] = rng3[3 * i + 1]; rng[4 * i + 2] = rng3[3 * i + 2]; rng[4 * i + 3] = 0u;
+        }
+    const int fill = FOVPT_DEBUG_SHADE_FILL;
+    HIPCHK(c, hipMemcpyAsync(S.q_o[0].p, qo.data(), qn * v, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.q_d[0].p, qd.data(), qn * v, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.s_hit.p, hit.data(), qn * v, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(S.s_rng.p, fill, slots * v, st));
+    HIPCHK(c, hipMemsetAsync(S.s_thr.p, fill, slots * v, st));
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(S.s_rng.p, rng.data(), un * v, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(S.s_thr.p, thr4, un * v, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipMemsetAsync(S.s_rad.p, fill, slots * v * D, st));
+    HIPCHK(c, hipMemsetAsync(S.s_alpha.p, fill, slots * v, st));
+    if (guides) { HIPCHK(c, hipMemsetAsync(S.s_guide_n.p, fill, slots * v, st)); HIPCHK(c, hipMemsetAsync(S.s_guide_a.p, fill, slots * v, st)); }
+    HIPCHK(c, hipMemsetAsync(S.q_o[1].p, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(S.q_d[1].p, fill, qn * v, st));
+    HIPCHK(c, hipMemsetAsync(S.sq_o[0].p, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(S.sq_d[0].p, fill, qn * v, st));
+    HIPCHK(c, hipMemsetAsync(S.sq_vis[0].p, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(S.sq_occ[0].p, fill, qn * v, st));
+    const size_t cnt_bytes = offsetof(Counters, stat_radiance);
+    std::vector<uint32_t> cw(cnt_bytes / 4, 0u);
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(in->depth_iter)] = in->shard_count[s];
+    HIPCHK(c, hipMemcpyAsync(S.counters.p, cw.data(), cnt_bytes, hipMemcpyHostToDevice, st));
+    // what k_shade reads of a frame: the probe and how it is searched, the depth cap, the options, the partition
+    FrameDev fd;
+    memset(&fd, 0, sizeof(fd));
+    fd.w = fd.h = 1;
+    fd.probe = *probe;
+    const ProbePath pp = probe_path(c, *probe);
+    fd.guide_x = pp.guide_x; fd.guide_y = pp.guide_y; fd.probe_rec = pp.rec; fd.probe_row_mul = pp.row_mul;
+    fd.max_depth = c->cfg.max_depth; fd.options = c->cfg.options; fd.partition = in->partition ? 1 : 0;
+    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
+    PathState ps = path_state(c, S);
+    if (guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
+    RayQueue qa, qb;
+    qa.o = (float4*)S.q_o[0].p; qa.d = (float4*)S.q_d[0].p;
+    qb.o = (float4*)S.q_o[1].p; qb.d = (float4*)S.q_d[1].p;
+    fovpt_launch_shade(st, fd, scene_view(c), ps, qa, qb, shadow_queue(S, 0), cap, (Counters*)S.counters.p, in->depth_iter, in->grid, nullptr, in->sel);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> nq_o(qn * 4), nq_d(qn * 4), s_o(qn * 4), s_d(qn * 4), s_vis(qn * 4), s_occ(qn * 4);
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(out->rng4, S.s_rng.p, un * v, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->thr4, S.s_thr.p, un * v, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->rad4, S.s_rad.p, un * v * D, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->alpha4, S.s_alpha.p, un * v, hipMemcpyDeviceToHost, st));
+        if (guides) {
+            HIPCHK(c, hipMemcpyAsync(out->guide_n4, S.s_guide_n.p, un * v, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(out->guide_a4, S.s_guide_a.p, un * v, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(nq_o.data(), S.q_o[1].p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(nq_d.data(), S.q_d[1].p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(s_o.data(), S.sq_o[0].p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(s_d.data(), S.sq_d[0].p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(s_vis.data(), S.sq_vis[0].p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(s_occ.data(), S.sq_occ[0].p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(cw.data(), S.counters.p, cnt_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    // leave the set as a job expects to find it (resolve zeroes the queue counters at the end of every job)
+    HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
+    out->cap = cap;
+    out->counters_changed = 0;
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+        out->next_count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(in->depth_iter + 1)];
+        out->shadow_count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_SQ(in->depth_iter)];
+        for (int w = 0; w < FOVPT_SHARD_STRIDE; w++) {              // every other counter word is as it was
+            const uint32_t was = w == FOVPT_CNT_Q(in->depth_iter) ? in->shard_count[s] : 0u;
+            if (w != FOVPT_CNT_Q(in->depth_iter + 1) && w != FOVPT_CNT_SQ(in->depth_iter) && cw[(size_t)s * FOVPT_SHARD_STRIDE + w] != was) out->counters_changed++;
+        }
+    }
+    // the occupied entries: any word of the entry differs from the fill, in ascending physical order; at most n are handed out
+    const uint32_t fw = 0x01010101u * (uint32_t)fill;
+    auto occupied = [&](const std::vector<uint32_t>& a, size_t e) { return a[4 * e] != fw || a[4 * e + 1] != fw || a[4 * e + 2] != fw || a[4 * e + 3] != fw; };
+    uint32_t nn = 0, ns = 0;
+    for (size_t e = 0; e < qn; e++) {
+        if (occupied(nq_o, e) || occupied(nq_d, e)) {
+            if (nn < (uint32_t)n) {
+                out->next_place2[2 * nn] = (uint32_t)(e / cap); out->next_place2[2 * nn + 1] = (uint32_t)(e % cap);
+                memcpy(out->next_o4 + 4 * (size_t)nn, &nq_o[4 * e], 16); memcpy(out->next_d4 + 4 * (size_t)nn, &nq_d[4 * e], 16);
+            }
+            nn++;
+        }
+        if (occupied(s_o, e) || occupied(s_d, e) || occupied(s_vis, e) || occupied(s_occ, e)) {
+            if (ns < (uint32_t)n) {
+                out->shadow_place2[2 * ns] = (uint32_t)(e / cap); out->shadow_place2[2 * ns + 1] = (uint32_t)(e % cap);
+                memcpy(out->shadow_o4 + 4 * (size_t)ns, &s_o[4 * e], 16); memcpy(out->shadow_d4 + 4 * (size_t)ns, &s_d[4 * e], 16);
+                memcpy(out->shadow_vis4 + 4 * (size_t)ns, &s_vis[4 * e], 16); memcpy(out->shadow_occ4 + 4 * (size_t)ns, &s_occ[4 * e], 16);
+            }
+            ns++;
+        }
+    }
+    out->next_found = nn; out->shadow_found = ns;
+    return FOVPT_OK;
+}
+
+// test hook: the PRODUCTION resolve kernel on a caller-made path state.  The frame is the one a fovpt_launch (render = 0, a
+// width x height grid) or a fovpt_render (render = 1: the passes of frame_passes) of these parameters would resolve -- frame_dev()
+// is shared with run_job -- and the state of every sample slot and launch record is the caller's: what generate, shade and the
+// occlusion launches would have left.  Called with state = NULL it only hands out the pass table, which the caller needs to lay
+// the arrays out.  lp is not changed (a render's subframe_index is not advanced).
+int fovpt_debug_resolve(fovpt_ctx* c, const fovpt_launch_params* lp, int render, uint32_t width, uint32_t height, fovpt_debug_pass* passes_out,
+                        int* npass_out, const uint32_t* state, const float* cells4, const float* alpha4, const float* guide_n4, const float* guide_a4,
+                        const float* backplate4, uint32_t* counters_left_out)
+{
+    if (!c || !lp || !passes_out || !npass_out) return FOVPT_E_INVALID;
+    if (!lp->frame.accum_buffer || !lp->frame.frame_buffer) return fail(c, FOVPT_E_NO_FRAME, "fovpt_debug_resolve with null frame buffers");
+    if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
+    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
+    PassDev P[FOVPT_MAX_PASSES];
+    int npass = 1;
+    if (render) { fovpt_launch_params L = *lp; npass = frame_passes(c->cfg, L, P); }
+    else P[0] = pass_from_lp(lp, width, height);
+    uint64_t all_slots = 0;
+    for (int p = 0; p < npass; p++) {
+        if (P[p].spp == 0) return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
+        P[p].row0 = 0; P[p].row1 = P[p].gh; P[p].frame_pass = (uint32_t)p;                     // as run_passes hands an unchunked frame to run_job
+        all_slots += (uint64_t)P[p].gw * P[p].gh * P[p].spp;
+    }
+    if (all_slots > c->slot_budget) return fail(c, FOVPT_E_INVALID, "fovpt_debug_resolve: %llu sample slots would run as several jobs", (unsigned long long)all_slots);
+    FrameDev fd;
+    uint64_t slots = 0, launches = 0;
+    { const int rc_ = frame_dev(c, lp, P, npass, 0, render ? 1 : 0, fd, slots, launches); if (rc_) return rc_; }
+    *npass_out = npass;
+    for (int p = 0; p < npass; p++) {
+        const PassDev& D = fd.pass[p];
+        passes_out[p].gw = D.gw; passes_out[p].rows = D.row1 - D.row0; passes_out[p].spp = D.spp;
+        passes_out[p].slot_base = D.slot_base; passes_out[p].launch_base = D.launch_base;
+    }
+    if (!state) return FOVPT_OK;
+    if (counters_left_out) *counters_left_out = 0u;
+    if (slots == 0) return FOVPT_OK;                                  // (a job of no sample slots launches nothing)
+    if (!cells4 || !alpha4 || !backplate4 || (c->cfg.write_guides && (!guide_n4 || !guide_a4))) return FOVPT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    StateSet& S = c->set[(c->last_set + 1u) % 2u];                    // (the device is idle: any set will do)
+    hipStream_t st = c->stream;
+    { const int rc_ = ensure_state(c, S, (size_t)slots, (size_t)launches, st); if (rc_) return rc_; }
+    std::vector<uint32_t> rng((size_t)slots * 4, 0xdeadbeefu);        // the generator's words: nothing in a resolve reads them
+    for (size_t i = 0; i < (size_t)slots; i++) rng[4 * i + 2] = state[i];
+    const size_t v = 16, D = (size_t)c->cfg.max_depth;
+    HIPCHK(c, hipMemcpyAsync(S.s_rng.p, rng.data(), (size_t)slots * v, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.s_rad.p, cells4, (size_t)slots * v * D, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.s_alpha.p, alpha4, (size_t)slots * v, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.s_backplate.p, backplate4, (size_t)launches * v, hipMemcpyHostToDevice, st));
+    PathState ps = path_state(c, S);
+    if (c->cfg.write_guides) {
+        ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p;
+        HIPCHK(c, hipMemcpyAsync(S.s_guide_n.p, guide_n4, (size_t)slots * v, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(S.s_guide_a.p, guide_a4, (size_t)slots * v, hipMemcpyHostToDevice, st));
+    }
+    // the queue sizes a job's launches leave behind, here a pattern: the resolve must leave zeros for the set's next job
+    const size_t cnt_bytes = offsetof(Counters, stat_radiance);
+    HIPCHK(c, hipMemsetAsync(S.counters.p, 0xa5, cnt_bytes, st));
+    fovpt_launch_resolve(st, fd, ps, (Counters*)S.counters.p);       // as run_job launches it
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> left(cnt_bytes / 4);
+    HIPCHK(c, hipMemcpyAsync(left.data(), S.counters.p, cnt_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    uint32_t nonzero = 0;
+    for (uint32_t w : left) nonzero += w != 0u;
+    if (counters_left_out) *counters_left_out = nonzero;
+    // leave the set as a job expects to find it, whatever the kernel did
+    if (nonzero) HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
     return FOVPT_OK;
 }
 

@@ -854,6 +854,79 @@ class SampleRenderer:
         self._check(self._L.fovpt_debug_tex2d(self._ctx, int(texture), uv.shape[0], uv.ctypes.data, out.ctypes.data))
         return out
 
+    def debug_shade(self, origin, dir4, prim, tuv, rng3, thr4, depth_iter=0, sel=0, grid=1, partition=0, shard_count=None, probe=None):
+        """The production k_shade on n chosen hits, one launch under the current config (max_depth, options, write_guides) ->
+        dict: per slot rng (n, 4) uint32, thr, rad (n, max_depth, 4), alpha, guide_n, guide_a (float32; the fill pattern where
+        nothing was written); next_count / shadow_count (8,); next / shadow = dict(shard, pos, o, d[, vis, occ]) of the queue
+        entries found, in ascending physical order; next_found / shadow_found, counters_changed, cap."""
+        o = np.ascontiguousarray(origin, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        d = np.ascontiguousarray(dir4, np.float32).reshape(n, 4)
+        prim = np.ascontiguousarray(prim, np.uint32).reshape(n)
+        tuv = np.ascontiguousarray(tuv, np.float32).reshape(n, 3)
+        rng3 = np.ascontiguousarray(rng3, np.uint32).reshape(n, 3)
+        thr4 = np.ascontiguousarray(thr4, np.float32).reshape(n, 4)
+        depth = self.config.max_depth
+        L = abi.DebugShadeLaunch()
+        L.n, L.depth_iter, L.grid, L.partition, L.sel = n, depth_iter, grid, partition, sel
+        if shard_count is None:
+            shard_count = [0] * 8
+            shard_count[4 if sel == 2 else 0] = n
+        for s in range(8):
+            L.shard_count[s] = int(shard_count[s])
+        f4 = lambda *shape: np.empty(shape + (4,), np.float32)
+        a = dict(rng4=np.empty((n, 4), np.uint32), thr4=f4(n), rad4=f4(n, depth), alpha4=f4(n), guide_n4=f4(n), guide_a4=f4(n),
+                 next_place2=np.empty((n, 2), np.uint32), next_o4=f4(n), next_d4=f4(n), shadow_place2=np.empty((n, 2), np.uint32),
+                 shadow_o4=f4(n), shadow_d4=f4(n), shadow_vis4=f4(n), shadow_occ4=f4(n))
+        for v in a.values():
+            v.view(np.uint8)[...] = abi.DEBUG_SHADE_FILL
+        R = abi.DebugShadeResult()
+        for k, v in a.items():
+            setattr(R, k, v.ctypes.data)
+        self._check(self._L.fovpt_debug_shade(self._ctx, C.byref(probe if probe is not None else self.launchParams.probe), C.byref(L),
+                                              o.ctypes.data, d.ctypes.data, prim.ctypes.data, tuv.ctypes.data, rng3.ctypes.data, thr4.ctypes.data,
+                                              C.byref(R)))
+        nn, ns = min(R.next_found, n), min(R.shadow_found, n)
+        return dict(rng=a["rng4"], thr=a["thr4"], rad=a["rad4"], alpha=a["alpha4"], guide_n=a["guide_n4"], guide_a=a["guide_a4"],
+                    next_count=np.array(R.next_count[:], np.uint32), shadow_count=np.array(R.shadow_count[:], np.uint32),
+                    next=dict(shard=a["next_place2"][:nn, 0], pos=a["next_place2"][:nn, 1], o=a["next_o4"][:nn], d=a["next_d4"][:nn]),
+                    shadow=dict(shard=a["shadow_place2"][:ns, 0], pos=a["shadow_place2"][:ns, 1], o=a["shadow_o4"][:ns], d=a["shadow_d4"][:ns],
+                                vis=a["shadow_vis4"][:ns], occ=a["shadow_occ4"][:ns]),
+                    next_found=int(R.next_found), shadow_found=int(R.shadow_found), counters_changed=int(R.counters_changed), cap=int(R.cap))
+
+    def debug_resolve_passes(self, render=True, width=0, height=0):
+        """The pass table of the frame a render() (or a launch(width, height)) of the current launch parameters would resolve:
+        a list of abi.DebugPass.  Sample slot of (pass, launch index li, sample s) = slot_base + li * spp + s."""
+        passes, n = (abi.DebugPass * 3)(), C.c_int(0)
+        self._check(self._L.fovpt_debug_resolve(self._ctx, C.byref(self.launchParams), 1 if render else 0, int(width), int(height), passes,
+                                                C.byref(n), None, None, None, None, None, None, None))
+        return [passes[i] for i in range(n.value)]
+
+    def debug_resolve(self, state, cells, alpha, backplate, guide_n=None, guide_a=None, render=True, width=0, height=0):
+        """The production resolve kernel on a path state in slot order (debug_resolve_passes): state (slots,) uint32 =
+        flags | depth << 8, cells (slots, max_depth, 4), alpha (slots, 4), backplate (launch records, 4), guides (slots, 4) under
+        write_guides.  The results are in the frame buffers (downloadAccum, downloadPixels, ...).  Returns the number of
+        queue-counter words the kernel left non-zero."""
+        passes = self.debug_resolve_passes(render, width, height)
+        slots = sum(p.gw * p.rows * p.spp for p in passes)
+        launches = sum(p.gw * p.rows for p in passes)
+        depth = self.config.max_depth
+        state = np.ascontiguousarray(state, np.uint32)
+        cells, alpha, backplate = (np.ascontiguousarray(x, np.float32) for x in (cells, alpha, backplate))
+        assert state.shape == (slots,) and cells.shape == (slots, depth, 4) and alpha.shape == (slots, 4) and backplate.shape == (launches, 4)
+        guides = []
+        for g in (guide_n, guide_a):
+            if g is not None:
+                g = np.ascontiguousarray(g, np.float32)
+                assert g.shape == (slots, 4)
+            guides.append(g)
+        out, n, left = (abi.DebugPass * 3)(), C.c_int(0), C.c_uint32(0)
+        self._check(self._L.fovpt_debug_resolve(self._ctx, C.byref(self.launchParams), 1 if render else 0, int(width), int(height), out, C.byref(n),
+                                                state.ctypes.data, cells.ctypes.data, alpha.ctypes.data,
+                                                guides[0].ctypes.data if guides[0] is not None else None,
+                                                guides[1].ctypes.data if guides[1] is not None else None, backplate.ctypes.data, C.byref(left)))
+        return left.value
+
     def debug_math(self, op, a, b=None):
         a = np.ascontiguousarray(a, np.float32)
         bb = np.ascontiguousarray(b, np.float32) if b is not None else None

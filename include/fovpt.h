@@ -1118,6 +1118,57 @@ int fovpt_debug_probe_eval(fovpt_ctx* ctx, const fovpt_probe* probe, int flags, 
 int fovpt_debug_bsdf(fovpt_ctx* ctx, const fovpt_material* material, int n, const float* N3, const float* view3, const float* albedo3, const float* etaI,
                      const float* etaO, const int32_t* seeds, const float* L_given3, float* out14);
 int fovpt_debug_tex2d(fovpt_ctx* ctx, int texture, int n, const float* uv2, float* rgba_out4);
+/* tests only: the production shading kernel on n hits the caller made (host arrays), launched once as a job launches it -- with
+ * the configured max_depth, options (which pick the kernel's build) and write_guides --, and what it left.
+ *
+ * Per hit i (= sample slot i): origin3, dir4 = ray direction and, in .w, the pdf of the sample that sent the ray; prim = global
+ * primitive id or 0xffffffff for a miss, with tuv3 = (t, u, v); rng3 = the slot's generator words s1, s2 and flags | depth << 8;
+ * thr4 = pathThroughput.xyz and rayEta.  `probe` is what a launch takes (device pointers) and is searched as a launch would.
+ * The launch: depth_iter = the iteration whose queue the hits are (they are appended to the queues of depth_iter + 1 and of
+ * depth_iter's shadow rays), sel = 0 (all eight queue shards) or 1 / 2 (the first / second four), grid = blocks,
+ * partition = the direction classes of foveated frames, shard_count[s] = how many of the hits, taken in order, lie in input
+ * shard s.  The state is sized so that any one shard can hold all n entries: cap = the capacity of a shard.
+ * Out, per slot: rng4, thr4, rad4 (max_depth cells), alpha4, guide_n4 / guide_a4 (under write_guides).  The counters of the next
+ * queue and of the shadow queue per shard; *_found = the entries of those queues that differ from the fill pattern (every byte
+ * FOVPT_DEBUG_SHADE_FILL), wherever they lie; the first n of them in ascending physical order with (shard, position) in
+ * *_place2.  counters_changed = other counter words that changed.  Every out array has room for n entries.
+ * Errors: FOVPT_E_NO_SCENE, FOVPT_E_NO_PROBE, FOVPT_E_INVALID.                                                              */
+#define FOVPT_DEBUG_SHADE_FILL 0xcd
+typedef struct fovpt_debug_shade_launch {
+    int32_t n, depth_iter, grid, partition;
+    uint32_t sel;
+    uint32_t shard_count[8];
+} fovpt_debug_shade_launch;
+typedef struct fovpt_debug_shade_result {
+    uint32_t *rng4;
+    float *thr4, *rad4, *alpha4, *guide_n4, *guide_a4;
+    uint32_t *next_place2;
+    float *next_o4, *next_d4;
+    uint32_t *shadow_place2;
+    float *shadow_o4, *shadow_d4, *shadow_vis4, *shadow_occ4;
+    uint32_t next_count[8], shadow_count[8];
+    uint32_t next_found, shadow_found, counters_changed, cap;
+} fovpt_debug_shade_result;
+int fovpt_debug_shade(fovpt_ctx* ctx, const fovpt_probe* probe, const fovpt_debug_shade_launch* launch, const float* origin3, const float* dir4,
+                      const uint32_t* prim, const float* tuv3, const uint32_t* rng3, const float* thr4, fovpt_debug_shade_result* out);
+/* tests only: the production resolve kernel on a path state the caller made, so that the last-writer search, the ordered sums,
+ * the alpha flags, the backplate mix, accumulate mode, the tone map and the tile ownership of a sharded frame can be compared
+ * with a restatement pixel by pixel and case by case, not only through rendered frames.
+ *
+ * The frame is the one fovpt_launch(lp, width, height) (render = 0) or fovpt_render(lp) (render = 1; width and height unused)
+ * would resolve under the current configuration; lp is not changed.  passes_out (room for 3) / npass_out: the passes in launch
+ * order with their places in the arrays -- sample slot of (pass, launch index li = ly * gw + lx, sample s) =
+ * slot_base + li * spp + s, launch record = launch_base + li.  With state = NULL the call returns after filling them.
+ * Otherwise, host arrays in slot order: state = flags | depth << 8 (DONE 1, SECONDARY 2, ALPHA_ONE 4, ALPHA_SET 8), cells4 =
+ * max_depth float4 radiance cells per slot, alpha4 = float4 per slot, guide_n4 / guide_a4 = float4 per slot (read under
+ * write_guides only, may be NULL otherwise), backplate4 = float4 per launch record.  The call uploads them, runs the kernel
+ * and synchronises; the caller reads its own frame buffers.  *counters_left_out: how many words of the state set's queue
+ * counters -- filled with a pattern before the launch -- the kernel left non-zero (a resolve zeroes them for the next job).
+ * Errors: FOVPT_E_NO_FRAME, FOVPT_E_INVALID (also: a frame that would run as several jobs).                              */
+typedef struct fovpt_debug_pass { uint32_t gw, rows, spp, slot_base, launch_base; } fovpt_debug_pass;
+int fovpt_debug_resolve(fovpt_ctx* ctx, const fovpt_launch_params* lp, int render, uint32_t width, uint32_t height, fovpt_debug_pass* passes_out,
+                        int* npass_out, const uint32_t* state, const float* cells4, const float* alpha4, const float* guide_n4, const float* guide_a4,
+                        const float* backplate4, uint32_t* counters_left_out);
 /* tests/diagnostics only: device address and size of an internal buffer ("sq_occ", "counters", "hit", "bvh_nodes", "bvh_tris"
  * -- the 48-byte triangle records of the hierarchy, stats.tri_bytes --, "scene_vertices" -- fovpt_update_vertices' vertex
  * array, once made --, "scene_vertices_prev" -- fovpt_temporal_motion's previous positions, once made --, "gbuffer_hit" -- the

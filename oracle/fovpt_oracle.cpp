@@ -778,6 +778,14 @@ struct Counters {
 std::atomic<uint64_t> g_lib_radiance{0}, g_lib_shadow{0}, g_occluded{0};      // g_occluded: diagnostics, occluded shadow rays (all)
 int g_options = 0;         // fovpt_config.options for the launches that follow (orc_render sets it from its cfg)
 int g_count_lib = 1;       // 0: skip the extra BSDF evaluation the counting needs on occluded rays (timed CPU baseline)
+// Per-sample terms of the launches that follow (orc_record_samples), for tests of the resolve: one row of ORC_SAMPLE_ROW floats
+// per traced sample, in the order the samples run (launches then run single-threaded): launch number since the recording began,
+// lx, ly, sample, number of terms, prd.alpha.xyz, the sample's normal.xyz and albedo.xyz guide terms, the backplate.xyz of its
+// camera ray, then the terms added to directLight (the first, :523) and indirectLight (:526) in order, xyz each.
+const int ORC_SAMPLE_TERMS = 32, ORC_SAMPLE_ROW = 17 + 3 * ORC_SAMPLE_TERMS;
+float* g_rec_rows = nullptr;
+size_t g_rec_cap = 0, g_rec_n = 0;
+int g_rec_launch = -1;
 
 struct Ctx {
     const Scene* S;
@@ -791,13 +799,15 @@ struct Ctx {
 // deviceProgram.cu:303-344 (SampleLights) and :347-387 (SampleShadow, want_occluded = true)
 f3 SampleLightsOrShadow(const Ctx& C, const Material& material, f3 albedo, float etaI, float etaO,
                         const f3& surfacePos, const f3& surfaceNormal, const f3& wo, Random& rand,
-                        bool want_occluded, uint64_t& nshadow, f3* sum_if_taken = nullptr)
+                        bool want_occluded, uint64_t& nshadow, f3* sum_if_taken = nullptr, int given_occluded = -1, f3* wi_out = nullptr)
 {
     f3 sum = mk3(0.0f);
     f3 skyColor; float skyPdf; f3 wi;
     ProbeSample(C.probe, wi, skyColor, skyPdf, rand);
+    if (wi_out) *wi_out = wi;
     nshadow++;
-    const bool occluded = trace_occluded(*C.S, surfacePos, wi, kTmin, kTmax, C.opt.brute);
+    // (given_occluded >= 0: the outcome of the occlusion test is the caller's, orc_shade_hit)
+    const bool occluded = given_occluded >= 0 ? given_occluded != 0 : trace_occluded(*C.S, surfacePos, wi, kTmin, kTmax, C.opt.brute);
     if (occluded) g_occluded++;
     // the branch below is a pure function of the hit and wi (no random numbers): evaluated once, used if taken
     f3 taken = mk3(0.0f);
@@ -821,11 +831,24 @@ f3 SampleLightsOrShadow(const Ctx& C, const Material& material, f3 albedo, float
 }
 
 // optixTrace(RAY_TYPE_RADIANCE) + __closesthit__radiance (:619-732) / __miss__radiance (:253-282)
+// What a hit record tells a test about the reference's branch (orc_shade_hit): 0 miss, 1 shadow-catcher pass-through, 2 shaded,
+// 3 shaded on a shadow catcher; the hit point and the direction of the next-event sample (of a shaded hit).
+struct HitNote { int kind = 0; f3 P = {0, 0, 0}, wi = {0, 0, 0}; };
+
+// traceRadiance from just behind the closest-hit search: the hit `h` is given; given_occluded >= 0 also gives the outcome of
+// the next-event occlusion test.
+void shadeRadiance(const Ctx& C, const f3& ray_origin, const f3& ray_dir, const Hit& h, RadiancePRD* prd, uint64_t& nshadow,
+                   int given_occluded = -1, HitNote* note = nullptr);
 void traceRadiance(const Ctx& C, const f3& ray_origin, const f3& ray_dir, RadiancePRD* prd, uint64_t& nrad, uint64_t& nshadow)
 {
-    const Scene& S = *C.S;
     nrad++;
-    Hit h = trace_closest(S, ray_origin, ray_dir, kTmin, kTmax, C.opt.brute);
+    const Hit h = trace_closest(*C.S, ray_origin, ray_dir, kTmin, kTmax, C.opt.brute);
+    shadeRadiance(C, ray_origin, ray_dir, h, prd, nshadow);
+}
+void shadeRadiance(const Ctx& C, const f3& ray_origin, const f3& ray_dir, const Hit& h, RadiancePRD* prd, uint64_t& nshadow, int given_occluded,
+                   HitNote* note)
+{
+    const Scene& S = *C.S;
     prd->sky_added = false; prd->rr_kill = false;
     if (h.prim == NO_HIT) {                                         // __miss__radiance
         if ((C.opt.options & FOVPT_OPT_SKY_MISS) && (prd->stateFlags & RAY_STATE_FLAGS_SECONDARY_RAY)) {
@@ -849,6 +872,7 @@ void traceRadiance(const Ctx& C, const f3& ray_origin, const f3& ray_dir, Radian
     const float t = h.t;
     const f3 P = ray_origin + t * ray_dir;                          // :638
     float outEta; f3 outAbsorption;
+    if (note) { note->P = P; note->kind = 1; }
 
     if ((mat.flags & FOVPT_MATERIAL_FLAG_SHADOW_CATCHER) != 0 && (prd->stateFlags & RAY_STATE_FLAGS_SECONDARY_RAY) != 0) {   // :646-651
         prd->origin = P;
@@ -875,14 +899,16 @@ void traceRadiance(const Ctx& C, const f3& ray_origin, const f3& ray_dir, Radian
         outAbsorption = mk3(0.0f);
     }
     const bool catcher = (mat.flags & FOVPT_MATERIAL_FLAG_SHADOW_CATCHER) != 0;
+    if (note) note->kind = catcher ? 3 : 2;
+    f3* const wi_note = note ? &note->wi : nullptr;
     const bool lib_shades = prd->depth < C.opt.max_depth;           // the library does not shade the discarded segment's hit
     f3 sum_taken;                                                   // what SampleLights/SampleShadow returns when its visibility test passes
     if (!catcher) {                                                 // :686-694
-        f3 lightSample = SampleLightsOrShadow(C, mat, prd->albedo, prd->rayEta, outEta, P, N, -ray_dir, prd->rand, false, nshadow, &sum_taken);
+        f3 lightSample = SampleLightsOrShadow(C, mat, prd->albedo, prd->rayEta, outEta, P, N, -ray_dir, prd->rand, false, nshadow, &sum_taken, given_occluded, wi_note);
         prd->radiance += prd->pathThroughput * lightSample;
         prd->alpha = mk3(1.0f);
     } else {
-        f3 shadowSample = SampleLightsOrShadow(C, mat, prd->albedo, prd->rayEta, outEta, P, N, -ray_dir, prd->rand, true, nshadow, &sum_taken);
+        f3 shadowSample = SampleLightsOrShadow(C, mat, prd->albedo, prd->rayEta, outEta, P, N, -ray_dir, prd->rand, true, nshadow, &sum_taken, given_occluded, wi_note);
         prd->alpha += prd->pathThroughput * shadowSample;
     }
     // does the outcome of the occlusion test change a single bit?  (radiance / alpha were zero before this hit)
@@ -990,6 +1016,17 @@ void raygen(const Ctx& C, uint32_t lx, uint32_t ly)
         f3 ray_origin = eye;
         backplate = mk3(ProbeEval(C.probe, ProbeDirToUV(ray_direction)));           // :495
         npaths++;
+        float* rec = nullptr;                                                       // (orc_record_samples)
+        if (g_rec_rows) {
+            if (g_rec_n < g_rec_cap) { rec = g_rec_rows + (size_t)ORC_SAMPLE_ROW * g_rec_n; std::fill(rec, rec + ORC_SAMPLE_ROW, 0.0f); }
+            g_rec_n++;
+        }
+        auto rec_term = [&](const f3& v) {
+            if (!rec) return;
+            const int k = (int)rec[4];
+            if (k < ORC_SAMPLE_TERMS) { rec[17 + 3 * k] = v.x; rec[18 + 3 * k] = v.y; rec[19 + 3 * k] = v.z; }
+            rec[4] = (float)(k + 1);
+        };
         for (;;) {
             prd.radiance = mk3(0.f);
             if (prd.depth < C.opt.max_depth || C.S->any_catcher) nlib++;            // (the library skips the discarded segment)
@@ -997,14 +1034,16 @@ void raygen(const Ctx& C, uint32_t lx, uint32_t ly)
             if (prd.depth == 0.f) {                                                 // :509-512
                 normal += prd.normal;
                 albedo += prd.albedo;
+                if (rec) { rec[8] += prd.normal.x; rec[9] += prd.normal.y; rec[10] += prd.normal.z; rec[11] += prd.albedo.x; rec[12] += prd.albedo.y; rec[13] += prd.albedo.z; }
             }
             if ((prd.stateFlags & RAY_STATE_FLAGS_DONE) || prd.depth >= C.opt.max_depth) {   // :515
                 // FOVPT_OPT_SKY_MISS: an escaped secondary ray's sky radiance counts (depth >= 1 here: secondary)
-                if (prd.sky_added && prd.depth < C.opt.max_depth) indirectLight += prd.radiance;
+                if (prd.sky_added && prd.depth < C.opt.max_depth) { indirectLight += prd.radiance; rec_term(prd.radiance); }
                 break;
             }
             if (prd.depth == 0) directLight += prd.radiance;
             else indirectLight += prd.radiance;
+            rec_term(prd.radiance);
             ++prd.depth;
             if (prd.rr_kill) break;                                                // FOVPT_OPT_RUSSIAN_ROULETTE
             ray_origin = prd.origin;
@@ -1012,6 +1051,11 @@ void raygen(const Ctx& C, uint32_t lx, uint32_t ly)
         }
         result += directLight + indirectLight;                                      // :536
         alpha += prd.alpha;
+        if (rec) {
+            rec[0] = (float)g_rec_launch; rec[1] = (float)lx; rec[2] = (float)ly; rec[3] = (float)(samples_per_launch - i);
+            rec[5] = prd.alpha.x; rec[6] = prd.alpha.y; rec[7] = prd.alpha.z;
+            rec[14] = backplate.x; rec[15] = backplate.y; rec[16] = backplate.z;
+        }
     } while (--i);
     C.cnt->radiance_rays += nrad; C.cnt->shadow_rays += nshadow; C.cnt->paths += npaths;
     g_lib_radiance += nlib;
@@ -1070,6 +1114,7 @@ void launch(const Scene& S, const fovpt_launch_params& lp, uint32_t width, uint3
     }
     int nt = std::max(1, opt.nthreads);
     if (clamps) nt = 1;
+    if (g_rec_rows) { nt = 1; g_rec_launch++; }                   // rows in the order the samples run
     // Accumulate mode (PT_sv4_vmv2 :545-553) reads accum_buffer[pixel] and writes it back.  When several launch
     // indices of ONE launch write the same pixel (clamped or overlapping fills) that is a data race in the
     // reference.  It is resolved here the way a GPU resolves it when the reads precede the conflicting writes:
@@ -1230,6 +1275,59 @@ int orc_render(void* scene, fovpt_launch_params* lp, const fovpt_config* cfg, in
     return rc;
 }
 
+/* traceRadiance from just behind trace_closest, hit by hit, with the outcome of the occlusion test given: n hits -- ray origin,
+ * direction and (dir4.w) the pdf that sent the ray, global primitive id (0xffffffff: a miss) with (t, u, v), the generator's two
+ * words and stateFlags | depth << 8, pathThroughput and rayEta -- through the reference's closest-hit / miss program.
+ * out: n rows of orc_shade_hit_row_floats() floats: kind (HitNote), stateFlags, depth, radiance.xyz, alpha.xyz, origin.xyz,
+ * direction.xyz, bsdfPdf, pathThroughput.xyz, rayEta, the generator's words (as bits), normal.xyz, albedo.xyz, sky_added, rr_kill,
+ * the hit point P.xyz, the next-event direction wi.xyz.                                                                    */
+int orc_shade_hit_row_floats(void) { return 40; }
+int orc_shade_hit(void* scene, const fovpt_probe* probe, int max_depth, int options, int n, const float* origin3, const float* dir4,
+                  const uint32_t* prim, const float* tuv3, const uint32_t* rng3, const float* thr4, int occluded, float* out)
+{
+    if (!scene || !probe || !probe->data || n < 0) return FOVPT_E_INVALID;
+    const Scene& S = *(Scene*)scene;
+    Ctx C;
+    Counters cnt;
+    fovpt_launch_params lp;
+    memset(&lp, 0, sizeof(lp));
+    C.S = &S; C.lp = &lp; C.cnt = &cnt;
+    C.opt.max_depth = max_depth; C.opt.accumulate = 0; C.opt.brute = 0; C.opt.nthreads = 1; C.opt.write_guides = 0; C.opt.options = options;
+    C.probe.width = probe->width; C.probe.height = probe->height;
+    C.probe.data = (const f4*)probe->data;
+    C.probe.pdfX = probe->pdfValuesX; C.probe.cdfX = probe->cdfValuesX;
+    C.probe.pdfY = probe->pdfValuesY; C.probe.cdfY = probe->cdfValuesY;
+    for (int i = 0; i < n; i++) {
+        if (prim[i] != NO_HIT && prim[i] >= S.tris.size()) return FOVPT_E_INVALID;
+        RadiancePRD prd;
+        prd.radiance = mk3(0.f); prd.alpha = mk3(0.f);
+        prd.origin = mk3(0.f); prd.direction = mk3(0.f); prd.normal = mk3(0.f); prd.albedo = mk3(0.f);
+        prd.rayAbsorption = mk3(0.f);
+        prd.rand.seed1 = rng3[3 * i]; prd.rand.seed2 = rng3[3 * i + 1];
+        prd.stateFlags = (int)(rng3[3 * i + 2] & 0xffu); prd.depth = (int)(rng3[3 * i + 2] >> 8);
+        prd.pathThroughput = mk3(thr4[4 * i], thr4[4 * i + 1], thr4[4 * i + 2]); prd.rayEta = thr4[4 * i + 3];
+        prd.bsdfPdf = dir4[4 * i + 3];
+        Hit h; h.t = tuv3[3 * i]; h.u = tuv3[3 * i + 1]; h.v = tuv3[3 * i + 2]; h.prim = prim[i];
+        HitNote note;
+        uint64_t nshadow = 0;
+        shadeRadiance(C, mk3(origin3[3 * i], origin3[3 * i + 1], origin3[3 * i + 2]), mk3(dir4[4 * i], dir4[4 * i + 1], dir4[4 * i + 2]), h, &prd,
+                      nshadow, occluded ? 1 : 0, &note);
+        float* r = out + 40 * (size_t)i;
+        r[0] = (float)note.kind; r[1] = (float)prd.stateFlags; r[2] = (float)prd.depth;
+        const f3 v[] = {prd.radiance, prd.alpha, prd.origin, prd.direction};
+        for (int k = 0; k < 4; k++) { r[3 + 3 * k] = v[k].x; r[4 + 3 * k] = v[k].y; r[5 + 3 * k] = v[k].z; }
+        r[15] = prd.bsdfPdf;
+        r[16] = prd.pathThroughput.x; r[17] = prd.pathThroughput.y; r[18] = prd.pathThroughput.z; r[19] = prd.rayEta;
+        memcpy(&r[20], &prd.rand.seed1, 4); memcpy(&r[21], &prd.rand.seed2, 4);
+        const f3 w[] = {prd.normal, prd.albedo};
+        for (int k = 0; k < 2; k++) { r[22 + 3 * k] = w[k].x; r[23 + 3 * k] = w[k].y; r[24 + 3 * k] = w[k].z; }
+        r[28] = prd.sky_added ? 1.f : 0.f; r[29] = prd.rr_kill ? 1.f : 0.f;
+        r[30] = note.P.x; r[31] = note.P.y; r[32] = note.P.z; r[33] = note.wi.x; r[34] = note.wi.y; r[35] = note.wi.z;
+        r[36] = r[37] = r[38] = r[39] = 0.f;
+    }
+    return 0;
+}
+
 /* rays libfovpt traces for the frames rendered since the last reset (see g_lib_radiance above) */
 void orc_lib_counts(uint64_t* out2, int reset)
 {
@@ -1237,6 +1335,15 @@ void orc_lib_counts(uint64_t* out2, int reset)
     if (reset) { g_lib_radiance = 0; g_lib_shadow = 0; }
 }
 void orc_set_options(int options) { g_options = options; }
+/* Record the per-sample terms of the launches that follow into rows[capacity][orc_sample_row_floats()] (see g_rec_rows); rows =
+ * NULL ends the recording.  Returns the number of samples traced since the recording began (may exceed capacity). */
+int orc_sample_row_floats(void) { return ORC_SAMPLE_ROW; }
+uint64_t orc_record_samples(float* rows, uint64_t capacity)
+{
+    const uint64_t n = g_rec_n;
+    g_rec_rows = rows; g_rec_cap = (size_t)capacity; g_rec_n = 0; g_rec_launch = -1;
+    return n;
+}
 void orc_set_lib_counting(int on) { g_count_lib = on ? 1 : 0; }
 uint64_t orc_occluded_count(int reset)
 {

@@ -46,6 +46,9 @@ def lib():
         L.orc_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_math.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_lib_counts.argtypes = [C.c_void_p, C.c_int]
+        L.orc_shade_hit.argtypes = [C.c_void_p, C.POINTER(abi.Probe), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+        L.orc_record_samples.restype = C.c_uint64
+        L.orc_record_samples.argtypes = [C.c_void_p, C.c_uint64]
         L.orc_camera_uvw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
@@ -187,6 +190,53 @@ def launch(scene: OracleScene, frame: OracleFrame, width, height, max_depth=4, a
     if rc != 0:
         raise RuntimeError("orc_launch failed: %d" % rc)
     return _counts(cnt)
+
+
+def shade_hit(scene: OracleScene, probe: "HostProbe", max_depth, options, origin, dir4, prim, tuv, rng3, thr4, occluded):
+    """traceRadiance from just behind trace_closest on given hits, the outcome of the occlusion test given -> dict of the
+    RadiancePRD afterwards (flags, depth, radiance, alpha, origin, direction, bsdfPdf, thr, eta, rng (n, 2) uint32, normal, albedo,
+    sky_added, rr_kill) and kind (0 miss, 1 catcher pass-through, 2 shaded, 3 shaded on a catcher), P, wi."""
+    o = np.ascontiguousarray(origin, np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    d = np.ascontiguousarray(dir4, np.float32).reshape(n, 4)
+    prim = np.ascontiguousarray(prim, np.uint32).reshape(n)
+    tuv = np.ascontiguousarray(tuv, np.float32).reshape(n, 3)
+    rng3 = np.ascontiguousarray(rng3, np.uint32).reshape(n, 3)
+    thr4 = np.ascontiguousarray(thr4, np.float32).reshape(n, 4)
+    out = np.empty((n, lib().orc_shade_hit_row_floats()), np.float32)
+    rc = lib().orc_shade_hit(scene._h, C.byref(probe.struct), int(max_depth), int(options), n, _p(o), _p(d), _p(prim), _p(tuv), _p(rng3), _p(thr4),
+                             1 if occluded else 0, _p(out))
+    if rc != 0:
+        raise RuntimeError("orc_shade_hit failed: %d" % rc)
+    ints = lambda k: out[:, k].astype(np.int64)
+    return dict(kind=ints(0), flags=ints(1), depth=ints(2), radiance=out[:, 3:6].copy(), alpha=out[:, 6:9].copy(), origin=out[:, 9:12].copy(),
+                direction=out[:, 12:15].copy(), bsdfPdf=out[:, 15].copy(), thr=out[:, 16:19].copy(), eta=out[:, 19].copy(),
+                rng=out[:, 20:22].copy().view(np.uint32), normal=out[:, 22:25].copy(), albedo=out[:, 25:28].copy(),
+                sky_added=ints(28), rr_kill=ints(29), P=out[:, 30:33].copy(), wi=out[:, 33:36].copy())
+
+
+class SampleRecording:
+    """with SampleRecording(capacity) as rec: render(...) / launch(...) -- afterwards rec.rows holds the per-sample terms of those
+    launches, one row per traced sample in the order they ran: dict(launch, lx, ly, sample, nterm, alpha, normal, albedo,
+    backplate, terms): `terms` (n, 32, 3) are what the sample added to directLight (the first) and indirectLight, in order."""
+
+    def __init__(self, capacity):
+        self._buf = np.zeros((capacity, lib().orc_sample_row_floats()), np.float32)
+        self.rows = None
+
+    def __enter__(self):
+        lib().orc_record_samples(_p(self._buf), self._buf.shape[0])
+        return self
+
+    def __exit__(self, *exc):
+        n = int(lib().orc_record_samples(None, 0))
+        assert n <= self._buf.shape[0], "recorded %d samples, room for %d" % (n, self._buf.shape[0])
+        b = self._buf[:n]
+        ints = lambda k: b[:, k].astype(np.int64)
+        self.rows = dict(launch=ints(0), lx=ints(1), ly=ints(2), sample=ints(3), nterm=ints(4), alpha=b[:, 5:8].copy(),
+                         normal=b[:, 8:11].copy(), albedo=b[:, 11:14].copy(), backplate=b[:, 14:17].copy(),
+                         terms=b[:, 17:].reshape(n, -1, 3).copy())
+        return False
 
 
 def math_op(op, a, b=None):
