@@ -177,6 +177,19 @@ class DebugShadeResult(C.Structure):
         ("next_found", C.c_uint32), ("shadow_found", C.c_uint32), ("counters_changed", C.c_uint32), ("cap", C.c_uint32)]
 
 
+class DebugGenerateLaunch(C.Structure):
+    """struct fovpt_debug_generate_launch."""
+    _fields_ = [("render", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32), ("row0", C.c_uint32), ("row1", C.c_uint32),
+                ("sel", C.c_uint32), ("slot_begin", C.c_uint32), ("slot_end", C.c_uint32), ("grid", C.c_int32)]
+
+
+class DebugGenerateResult(C.Structure):
+    """struct fovpt_debug_generate_result: host arrays of the caller's, and what the call counted."""
+    _fields_ = [(k, C.c_void_p) for k in ("rng4", "backplate4", "guide_n4", "guide_a4", "place2", "o4", "d4")] + [
+        ("count", C.c_uint32 * 8), ("found", C.c_uint32), ("counters_changed", C.c_uint32), ("cap", C.c_uint32), ("kernel", C.c_uint32),
+        ("guides", C.c_uint32), ("slot_begin", C.c_uint32), ("slot_end", C.c_uint32), ("grid", C.c_uint32)]
+
+
 class HierarchyCost(C.Structure):
     """fovpt_hierarchy_cost_info: the SAH cost of the hierarchy as built and as last measured, and the update counters."""
     _fields_ = [("built", C.c_double), ("current", C.c_double), ("updates", C.c_uint64), ("measured", C.c_uint64)]

@@ -200,6 +200,20 @@ ShadowQueue shadow_queue(const StateSet& S, int k)
 
 int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame);
 
+// The two chains of a job that run_job splits (chains_per_frame = 2): chain k takes the sample slots [slot_begin, slot_end) -- the
+// first chain a whole number of 256-slot block iterations, the second the rest -- through the queue shards of sel = k + 1.  One
+// function for run_job and for fovpt_debug_generate, so that a test runs the chains a job would issue.
+struct ChainSplit { uint32_t sel, slot_begin, slot_end; };
+ChainSplit chain_split(uint64_t slots, int k)
+{
+    const uint32_t half = (uint32_t)(slots / 2 / FOVPT_BLOCK * FOVPT_BLOCK);
+    ChainSplit s;
+    s.sel = k == 0 ? 1u : 2u;
+    s.slot_begin = k == 0 ? 0u : half;
+    s.slot_end = k == 0 ? half : (uint32_t)slots;
+    return s;
+}
+
 // The engine: all passes of one frame as one wavefront job (or several, for very large launches).
 // whole_frame: the passes are a complete frame (fovpt_render), so with world > 1 the pixels nobody writes are
 // cleared on the ranks other than 0 (rank 0 keeps them, as the reference's frame buffer keeps what no launch
@@ -422,7 +436,7 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
         qa.o = (float4*)S.q_o[0].p; qa.d = (float4*)S.q_d[0].p;
         qb.o = (float4*)S.q_o[1].p; qb.d = (float4*)S.q_d[1].p;
         const int g_gen = c->grid / div, g_trace = c->grid_trace / div, g_shadow = c->grid_shadow / div, g_shade = c->grid_shade / div;
-        { Timed t(c, T_GENERATE, st); fovpt_launch_generate(st, fd, ps, qa, cap, cnt, slot_begin, slot_end, g_gen, sel); }
+        { Timed t(c, T_GENERATE, st); (void)fovpt_launch_generate(st, fd, ps, qa, cap, cnt, slot_begin, slot_end, g_gen, sel); }
         { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, sc, ps, qa, sq[0], cap, cnt, 0, -1, g_trace, nullptr, sel); }
         for (int it = 0; it < iters; it++) {
             if (it >= nsq) HIPCHK(c, hipStreamWaitEvent(st, ev.shadow[it - nsq], 0));
@@ -441,10 +455,10 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
         return FOVPT_OK;
     };
     if (two_chains) {
-        const uint32_t half = (uint32_t)(slots / 2 / FOVPT_BLOCK * FOVPT_BLOCK);      // (a whole number of 256-slot block iterations)
-        rc = issue_chain(c->lane_main[0], c->lane_shadow[0], 1u, 0u, half, 2, S.chain[0]);
+        const ChainSplit c0 = chain_split(slots, 0), c1 = chain_split(slots, 1);
+        rc = issue_chain(c->lane_main[0], c->lane_shadow[0], c0.sel, c0.slot_begin, c0.slot_end, 2, S.chain[0]);
         if (rc) return rc;
-        rc = issue_chain(c->lane_main[1], c->lane_shadow[1], 2u, half, (uint32_t)slots, 2, S.chain[1]);
+        rc = issue_chain(c->lane_main[1], c->lane_shadow[1], c1.sel, c1.slot_begin, c1.slot_end, 2, S.chain[1]);
         if (rc) return rc;
         HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[1].shadow[iters - 1], 0));      // (the first chain's last occlusion launch IS on shadow_stream)
     } else {
@@ -1480,6 +1494,124 @@ int fovpt_debug_resolve(fovpt_ctx* c, const fovpt_launch_params* lp, int render,
     if (counters_left_out) *counters_left_out = nonzero;
     // leave the set as a job expects to find it, whatever the kernel did
     if (nonzero) HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
+    return FOVPT_OK;
+}
+
+// test hook: the PRODUCTION generate launcher (fovpt_launch_generate: k_generate, or k_generate_owned for a rank of a sharded
+// frame) on the frame a fovpt_launch (render = 0; with row1 > 0 the chunk [row0, row1) of it, as run_passes hands a chunk to
+// run_job) or a fovpt_render (render = 1) of these parameters would run -- frame_dev() is shared with run_job -- and everything
+// the launch left: the generator words, the backplates, the guides, the queue counters and the occupied entries of queue 0.
+// The state is a job's (ensure_state, shard_capacity) except queue 0: the launch gets a scratch queue of 8 * cap + slots + 256
+// entries with the same cap, so that a shard that overflows lands in memory this function owns and shows in the result (the
+// appends of one launch number at most `slots`, and the last shard begins at 7 * cap).  Everything the kernel may write is
+// filled with the byte FOVPT_DEBUG_SHADE_FILL first.  lp is not changed.
+int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_debug_generate_launch* in, fovpt_debug_pass* passes_out,
+                         int* npass_out, fovpt_debug_generate_result* out)
+{
+    if (!c || !lp || !in || !passes_out || !npass_out) return FOVPT_E_INVALID;
+    if (!lp->frame.accum_buffer || !lp->frame.frame_buffer) return fail(c, FOVPT_E_NO_FRAME, "fovpt_debug_generate with null frame buffers");
+    if (!lp->probe.data || !lp->probe.cdfValuesX || !lp->probe.cdfValuesY || !lp->probe.pdfValuesX || !lp->probe.pdfValuesY
+        || lp->probe.width <= 0 || lp->probe.height <= 0)
+        return fail(c, FOVPT_E_NO_PROBE, "fovpt_debug_generate with an incomplete probe");
+    if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
+    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
+    const bool chunk = !in->render && in->row1 > 0u;
+    if (in->render ? (in->row0 || in->row1) : (chunk && (in->row0 >= in->row1 || in->row1 > in->height)))
+        return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: launch rows [%u, %u) of %u", in->row0, in->row1, in->height);
+    PassDev P[FOVPT_MAX_PASSES];
+    int npass = 1;
+    if (in->render) { fovpt_launch_params L = *lp; npass = frame_passes(c->cfg, L, P); }
+    else P[0] = pass_from_lp(lp, in->width, in->height);
+    uint64_t all_slots = 0;
+    for (int p = 0; p < npass; p++) {
+        if (P[p].spp == 0) return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
+        P[p].row0 = 0; P[p].row1 = P[p].gh; P[p].frame_pass = (uint32_t)p;                     // as run_passes hands an unchunked frame to run_job
+        if (chunk) { P[p].row0 = in->row0; P[p].row1 = in->row1; }                             // ... and a chunk of a launch
+        all_slots += (uint64_t)P[p].gw * (P[p].row1 - P[p].row0) * P[p].spp;
+    }
+    if (all_slots > c->slot_budget) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: %llu sample slots would run as several jobs", (unsigned long long)all_slots);
+    FrameDev fd;
+    uint64_t slots = 0, launches = 0;
+    { const int rc_ = frame_dev(c, lp, P, npass, chunk ? 1 : 0, in->render ? 1 : 0, fd, slots, launches); if (rc_) return rc_; }
+    *npass_out = npass;
+    for (int p = 0; p < npass; p++) {
+        const PassDev& D = fd.pass[p];
+        passes_out[p].gw = D.gw; passes_out[p].rows = D.row1 - D.row0; passes_out[p].spp = D.spp;
+        passes_out[p].slot_base = D.slot_base; passes_out[p].launch_base = D.launch_base;
+    }
+    if (!out) return FOVPT_OK;
+    // the launch: what run_job would give a launch of this `sel`, unless the caller says otherwise
+    const uint32_t sel = in->sel;
+    if (sel > 2u) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: sel %u", sel);
+    const int grid = in->grid ? in->grid : (sel ? c->grid / 2 : c->grid);
+    if (grid <= 0 || grid > (1 << 20) || grid % (sel ? FOVPT_SHARDS / 2 : FOVPT_SHARDS))
+        return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: a grid of %d blocks (a positive multiple of %d)", grid, sel ? FOVPT_SHARDS / 2 : FOVPT_SHARDS);
+    uint32_t slot_begin = in->slot_begin, slot_end = in->slot_end;
+    if (slot_begin == 0u && slot_end == 0u) {
+        slot_end = (uint32_t)slots;
+        if (sel) { const ChainSplit cs = chain_split(slots, (int)sel - 1); slot_begin = cs.slot_begin; slot_end = cs.slot_end; }
+    }
+    if (slot_begin > slot_end || (uint64_t)slot_end > slots) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: sample slots [%u, %u) of %llu", slot_begin, slot_end, (unsigned long long)slots);
+    const bool guides = c->cfg.write_guides != 0;
+    out->found = out->counters_changed = 0u; out->kernel = 0u; out->guides = guides ? 1u : 0u;
+    out->cap = shard_capacity((size_t)slots); out->slot_begin = slot_begin; out->slot_end = slot_end; out->grid = (uint32_t)grid;
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) out->count[s] = 0u;
+    if (slots == 0) return FOVPT_OK;                                  // (a job of no sample slots launches nothing)
+    if (!out->rng4 || !out->backplate4 || (guides && (!out->guide_n4 || !out->guide_a4)) || !out->place2 || !out->o4 || !out->d4) return FOVPT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    StateSet& S = c->set[(c->last_set + 1u) % 2u];                    // (the device is idle: any set will do)
+    hipStream_t st = c->stream;
+    { const int rc_ = ensure_state(c, S, (size_t)slots, (size_t)launches, st); if (rc_) return rc_; }
+    const uint32_t cap = shard_capacity((size_t)slots);
+    const size_t v = 16, qn = (size_t)cap * FOVPT_SHARDS + (size_t)slots + 256u;
+    struct Scratch { void *o = nullptr, *d = nullptr; ~Scratch() { if (o) (void)hipFree(o); if (d) (void)hipFree(d); } } scratch;      // freed on every return path
+    HIPCHK(c, hipMalloc(&scratch.o, qn * v)); HIPCHK(c, hipMalloc(&scratch.d, qn * v));
+    const int fill = FOVPT_DEBUG_SHADE_FILL;
+    HIPCHK(c, hipMemsetAsync(S.s_rng.p, fill, (size_t)slots * v, st));
+    HIPCHK(c, hipMemsetAsync(S.s_backplate.p, fill, (size_t)launches * v, st));
+    if (guides) { HIPCHK(c, hipMemsetAsync(S.s_guide_n.p, fill, (size_t)slots * v, st)); HIPCHK(c, hipMemsetAsync(S.s_guide_a.p, fill, (size_t)slots * v, st)); }
+    HIPCHK(c, hipMemsetAsync(scratch.o, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(scratch.d, fill, qn * v, st));
+    const size_t cnt_bytes = offsetof(Counters, stat_radiance);
+    HIPCHK(c, hipMemsetAsync(S.counters.p, 0, cnt_bytes, st));       // as a job finds them
+    PathState ps = path_state(c, S);
+    if (guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
+    RayQueue q0;
+    q0.o = (float4*)scratch.o; q0.d = (float4*)scratch.d;
+    out->kernel = (uint32_t)fovpt_launch_generate(st, fd, ps, q0, cap, (Counters*)S.counters.p, slot_begin, slot_end, grid, sel);   // as run_job launches it
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> qo(qn * 4), qd(qn * 4), cw(cnt_bytes / 4);
+    HIPCHK(c, hipMemcpyAsync(out->rng4, S.s_rng.p, (size_t)slots * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out->backplate4, S.s_backplate.p, (size_t)launches * v, hipMemcpyDeviceToHost, st));
+    if (guides) {
+        HIPCHK(c, hipMemcpyAsync(out->guide_n4, S.s_guide_n.p, (size_t)slots * v, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->guide_a4, S.s_guide_a.p, (size_t)slots * v, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipMemcpyAsync(qo.data(), scratch.o, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(qd.data(), scratch.d, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(cw.data(), S.counters.p, cnt_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    // leave the set as a job expects to find it (resolve zeroes the queue counters at the end of every job)
+    HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+        out->count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(0)];
+        for (int w = 0; w < FOVPT_SHARD_STRIDE; w++)
+            if (w != FOVPT_CNT_Q(0) && cw[(size_t)s * FOVPT_SHARD_STRIDE + w] != 0u) out->counters_changed++;
+    }
+    // the occupied entries: any word of the entry differs from the fill, in ascending physical order (an entry of the guard
+    // region behind the eight shards reports a shard of 8 or more); at most `slots` are handed out
+    const uint32_t fw = 0x01010101u * (uint32_t)fill;
+    auto occupied = [&](const std::vector<uint32_t>& a, size_t e) { return a[4 * e] != fw || a[4 * e + 1] != fw || a[4 * e + 2] != fw || a[4 * e + 3] != fw; };
+    uint32_t n = 0;
+    for (size_t e = 0; e < qn; e++)
+        if (occupied(qo, e) || occupied(qd, e)) {
+            if ((uint64_t)n < slots) {
+                out->place2[2 * (size_t)n] = (uint32_t)(e / cap); out->place2[2 * (size_t)n + 1] = (uint32_t)(e % cap);
+                memcpy(out->o4 + 4 * (size_t)n, &qo[4 * e], 16); memcpy(out->d4 + 4 * (size_t)n, &qd[4 * e], 16);
+            }
+            n++;
+        }
+    out->found = n;
     return FOVPT_OK;
 }
 

@@ -210,8 +210,9 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
 
 // cap = shard capacity (in items) of the radiance queues and of the shadow queue.
 // sel: 0 = all eight queue shards (a whole job); 1 / 2 = the first / second four (one of the two chains of a frame)
-void fovpt_launch_generate(hipStream_t st, const FrameDev& fd, PathState ps, RayQueue queue0, uint32_t cap, Counters* cnt, uint32_t slot_begin,
-                           uint32_t slot_end, int grid, uint32_t sel = 0);
+// Returns the kernel it launched: 0 = k_generate, 1 = k_generate_owned.
+int fovpt_launch_generate(hipStream_t st, const FrameDev& fd, PathState ps, RayQueue queue0, uint32_t cap, Counters* cnt, uint32_t slot_begin,
+                          uint32_t slot_end, int grid, uint32_t sel = 0);
 // One launch that traces the radiance queue of iteration it_closest (closest hit) OR the shadow queue of iteration
 // it_shadow (occlusion): the other one is < 0 (traverse.hip).
 void fovpt_launch_traverse(hipStream_t st, SceneView sc, PathState ps, RayQueue queue, ShadowQueue sq, uint32_t cap,

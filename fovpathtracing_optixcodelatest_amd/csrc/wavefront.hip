@@ -847,8 +847,8 @@ __global__ void k_math(int op, const float* a, const float* b, float* out, size_
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
-void fovpt_launch_generate(hipStream_t st, const FrameDev& fd, PathState ps, RayQueue queue0, uint32_t cap, Counters* cnt, uint32_t slot_begin,
-                           uint32_t slot_end, int grid, uint32_t sel)
+int fovpt_launch_generate(hipStream_t st, const FrameDev& fd, PathState ps, RayQueue queue0, uint32_t cap, Counters* cnt, uint32_t slot_begin,
+                          uint32_t slot_end, int grid, uint32_t sel)
 {
     // a rank of a tile-sharded frame walks its own tiles only (one chain: a half-frame chain is a range of sample slots).
     // Its index space is padded (tiles beyond a row's end, launch indices beyond the grid's edge): a queue shard holds
@@ -860,10 +860,12 @@ void fovpt_launch_generate(hipStream_t st, const FrameDev& fd, PathState ps, Ray
         o.init(fd, fd.pass[p]);
         space += ((unsigned long long)o.tile_rows * o.per_row * o.tile_lis * fd.pass[p].spp + FOVPT_BLOCK - 1u) / FOVPT_BLOCK * FOVPT_BLOCK;   // (64-bit: o.count may have wrapped)
     }
-    if (fd.world > 1 && sel == 0u && slot_begin == 0u && slot_end == fd.total_slots && space <= (unsigned long long)fd.total_slots)
+    const bool owned = fd.world > 1 && sel == 0u && slot_begin == 0u && slot_end == fd.total_slots && space <= (unsigned long long)fd.total_slots;
+    if (owned)
         hipLaunchKernelGGL(k_generate_owned, dim3(grid), dim3(FOVPT_BLOCK), 0, st, fd, ps, queue0, cap, cnt);
     else
         hipLaunchKernelGGL(k_generate, dim3(grid), dim3(FOVPT_BLOCK), 0, st, fd, ps, queue0, cap, cnt, slot_begin, slot_end, sel);
+    return owned ? 1 : 0;               // which kernel ran (fovpt_debug_generate hands it on)
 }
 void fovpt_launch_shade(hipStream_t st, const FrameDev& fd, SceneView sc, PathState ps, RayQueue queue_in, RayQueue queue_out,
                         ShadowQueue sq, uint32_t cap, Counters* cnt, int depth, int grid, hipEvent_t done, uint32_t sel)

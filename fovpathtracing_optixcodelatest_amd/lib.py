@@ -18,6 +18,7 @@ EXPORTS = [
     "fovpt_synchronize", "fovpt_download", "fovpt_get_stats", "fovpt_reset_stats", "fovpt_stream",
     "fovpt_probe_build_cdf", "fovpt_camera_uvw", "fovpt_debug_math", "fovpt_debug_buffer", "fovpt_debug_trace",
     "fovpt_debug_probe_sample", "fovpt_debug_probe_eval", "fovpt_debug_bsdf", "fovpt_debug_tex2d", "fovpt_debug_resolve", "fovpt_debug_shade",
+    "fovpt_debug_generate",
     "fovpt_gather_plan", "fovpt_gather_pack", "fovpt_gather_unpack",
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
@@ -218,6 +219,8 @@ def load():
     L.fovpt_debug_shade.argtypes = [vp, C.POINTER(abi.Probe), C.POINTER(abi.DebugShadeLaunch), vp, vp, vp, vp, vp, vp, C.POINTER(abi.DebugShadeResult)]
     L.fovpt_debug_resolve.argtypes = [vp, C.POINTER(abi.LaunchParams), i32, u32, u32, C.POINTER(abi.DebugPass), C.POINTER(i32), vp, vp, vp, vp, vp, vp,
                                       C.POINTER(u32)]
+    L.fovpt_debug_generate.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.DebugGenerateLaunch), C.POINTER(abi.DebugPass), C.POINTER(i32),
+                                       C.POINTER(abi.DebugGenerateResult)]
     _declare_loader(L)
     _declare_packet_host(L)
     for name in EXPORTS:

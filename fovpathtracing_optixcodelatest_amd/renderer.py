@@ -927,6 +927,40 @@ class SampleRenderer:
                                                 guides[1].ctypes.data if guides[1] is not None else None, backplate.ctypes.data, C.byref(left)))
         return left.value
 
+    def debug_generate(self, render=True, width=0, height=0, rows=None, sel=0, slot_begin=0, slot_end=0, grid=0):
+        """The production generate launch on the frame a render() (or a launch(width, height), or its chunk of launch rows
+        rows = (row0, row1)) of the current launch parameters would run, as a job launches it: sel = 0 or a chain's 1 / 2, the
+        sample slots [slot_begin, slot_end) (0, 0: a job's own), grid blocks (0: a job's own) -> dict: passes (list of
+        abi.DebugPass), rng (slots, 4) uint32, backplate (launch records, 4), guide_n / guide_a (slots, 4) or None without
+        write_guides -- the fill pattern abi.DEBUG_SHADE_FILL where nothing was written --, count (8,), found, counters_changed,
+        cap, kernel (0 k_generate, 1 k_generate_owned), slot_begin, slot_end, grid as launched, and the queue entries found in
+        ascending physical order: shard, pos, o (n, 4), d (n, 4)."""
+        L = abi.DebugGenerateLaunch()
+        L.render, L.width, L.height = 1 if render else 0, int(width), int(height)
+        L.row0, L.row1 = (int(rows[0]), int(rows[1])) if rows is not None else (0, 0)
+        L.sel, L.slot_begin, L.slot_end, L.grid = int(sel), int(slot_begin), int(slot_end), int(grid)
+        passes, n = (abi.DebugPass * 3)(), C.c_int(0)
+        self._check(self._L.fovpt_debug_generate(self._ctx, C.byref(self.launchParams), C.byref(L), passes, C.byref(n), None))
+        table = [passes[i] for i in range(n.value)]
+        slots = sum(p.gw * p.rows * p.spp for p in table)
+        launches = sum(p.gw * p.rows for p in table)
+        guides = bool(self.config.write_guides)
+        a = dict(rng4=np.empty((slots, 4), np.uint32), backplate4=np.empty((launches, 4), np.float32), place2=np.empty((slots, 2), np.uint32),
+                 o4=np.empty((slots, 4), np.float32), d4=np.empty((slots, 4), np.float32))
+        if guides:
+            a.update(guide_n4=np.empty((slots, 4), np.float32), guide_a4=np.empty((slots, 4), np.float32))
+        R = abi.DebugGenerateResult()
+        for k, v in a.items():
+            v.view(np.uint8)[...] = abi.DEBUG_SHADE_FILL
+            setattr(R, k, v.ctypes.data)
+        self._check(self._L.fovpt_debug_generate(self._ctx, C.byref(self.launchParams), C.byref(L), passes, C.byref(n), C.byref(R)))
+        assert bool(R.guides) == guides
+        m = min(R.found, slots)
+        return dict(passes=table, rng=a["rng4"], backplate=a["backplate4"], guide_n=a.get("guide_n4"), guide_a=a.get("guide_a4"),
+                    count=np.array(R.count[:], np.uint32), found=int(R.found), counters_changed=int(R.counters_changed), cap=int(R.cap),
+                    kernel=int(R.kernel), slot_begin=int(R.slot_begin), slot_end=int(R.slot_end), grid=int(R.grid),
+                    shard=a["place2"][:m, 0], pos=a["place2"][:m, 1], o=a["o4"][:m], d=a["d4"][:m])
+
     def debug_math(self, op, a, b=None):
         a = np.ascontiguousarray(a, np.float32)
         bb = np.ascontiguousarray(b, np.float32) if b is not None else None

@@ -1169,6 +1169,45 @@ typedef struct fovpt_debug_pass { uint32_t gw, rows, spp, slot_base, launch_base
 int fovpt_debug_resolve(fovpt_ctx* ctx, const fovpt_launch_params* lp, int render, uint32_t width, uint32_t height, fovpt_debug_pass* passes_out,
                         int* npass_out, const uint32_t* state, const float* cells4, const float* alpha4, const float* guide_n4, const float* guide_a4,
                         const float* backplate4, uint32_t* counters_left_out);
+/* tests only: the production generate launch -- k_generate, or k_generate_owned for a rank of a tile-sharded frame, whichever the
+ * library's launcher picks -- so that seeding, jitter, camera rays, backplates, the slot-to-launch decode, the ring test, tile
+ * ownership and the sharded queue can be compared with the oracle and a restatement slot by slot, not only through frames.
+ *
+ * The frame is the one fovpt_launch(lp, width, height) (render = 0) or fovpt_render(lp) (render = 1; width, height, row0, row1
+ * unused and 0) would run under the current configuration (world, rank, tile_w, tile_h, write_guides, uniform, max_depth); lp is
+ * not changed.  With render = 0 and row1 > 0 the job is the chunk of launch rows [row0, row1) of that launch, as an oversized
+ * launch is cut: sample slots and launch records are then relative to the chunk.  passes_out (room for 3) / npass_out are
+ * fovpt_debug_resolve's; with out = NULL the call returns after filling them.
+ * The launch: sel = 0 (all eight queue shards) or 1 / 2 (the first / second four: one of the two chains of a job), the sample
+ * slots [slot_begin, slot_end) -- 0 / 0: all of them for sel = 0, the half that a job's chain of that sel takes otherwise --
+ * and grid = blocks, a positive multiple of 8 (of 4 with sel != 0), or 0: what a job uses.  What ran is reported in out.
+ * The state is sized as a job sizes it (cap = the capacity of a queue shard), except that queue 0 is a scratch queue of
+ * 8 * cap + slots + 256 entries: a shard that overflows shows in the result and nothing else is overwritten.  The generator
+ * words, the backplates, the guides and the scratch queue are filled with the byte FOVPT_DEBUG_SHADE_FILL before the launch and
+ * the queue counters are zero, as a job finds them.
+ * Out, host arrays of the caller's: rng4 per sample slot, backplate4 per launch record, guide_n4 / guide_a4 per slot (under
+ * write_guides only: guides = 1; otherwise they are not touched and may be NULL), count[s] = the counter of queue 0 in shard
+ * s, counters_changed = other counter words that are not zero, found = the entries of the scratch queue that differ from the
+ * fill pattern, wherever they lie; the first `slots` of them in ascending physical order with (shard, position) in place2 (an
+ * entry behind the eighth shard reports a shard of 8 or more), origin and slot in o4, direction in d4 (room for `slots` entries
+ * each).  kernel = 0: k_generate ran, 1: k_generate_owned.
+ * Errors: FOVPT_E_NO_FRAME, FOVPT_E_NO_PROBE, FOVPT_E_INVALID (also: a frame that would run as several jobs).             */
+typedef struct fovpt_debug_generate_launch {
+    int32_t render;
+    uint32_t width, height, row0, row1;
+    uint32_t sel, slot_begin, slot_end;
+    int32_t grid;
+} fovpt_debug_generate_launch;
+typedef struct fovpt_debug_generate_result {
+    uint32_t *rng4;
+    float *backplate4, *guide_n4, *guide_a4;
+    uint32_t *place2;
+    float *o4, *d4;
+    uint32_t count[8];
+    uint32_t found, counters_changed, cap, kernel, guides, slot_begin, slot_end, grid;
+} fovpt_debug_generate_result;
+int fovpt_debug_generate(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_debug_generate_launch* launch, fovpt_debug_pass* passes_out,
+                         int* npass_out, fovpt_debug_generate_result* out);
 /* tests/diagnostics only: device address and size of an internal buffer ("sq_occ", "counters", "hit", "bvh_nodes", "bvh_tris"
  * -- the 48-byte triangle records of the hierarchy, stats.tri_bytes --, "scene_vertices" -- fovpt_update_vertices' vertex
  * array, once made --, "scene_vertices_prev" -- fovpt_temporal_motion's previous positions, once made --, "gbuffer_hit" -- the

@@ -971,24 +971,79 @@ inline uint32_t make_color(const f3& c)                             // cuda/help
     return quantizeUnsigned8Bits(srgb.x) | (quantizeUnsigned8Bits(srgb.y) << 8) | (quantizeUnsigned8Bits(srgb.z) << 16) | (255u << 24);
 }
 
+// The head of __raygen__renderFrame (:411-495) in two steps, shared by the launch loop below and by orc_camera_rays: the per-ray
+// reference of the camera-ray tests is the code every frame runs.
+// VARIANT is a compile-time argument: a launch instantiates RAYGEN_REFERENCE alone, so the code a frame runs holds none of the
+// branches below.  orc_camera_rays -- the one place that names another variant -- may ask for ONE deliberate deviation, so that
+// a test can show that its cases tell the reference from it (tests/test_generate_cpu.py).
+enum {
+    RAYGEN_REFERENCE = 0,
+    RAYGEN_JY_FIRST = 1,          // jy drawn before jx
+    RAYGEN_RANDOM_LATE = 2,       // Random(seed) taken after the jitter draws
+    RAYGEN_SIGNED_INDEX = 3,      // the pixel index converted as a signed number: no wrap of a negative offset
+    RAYGEN_INNER_EDGE_DEAD = 4,   // range <= r_inner does not pass the ring test
+    RAYGEN_SKIP_ONE_DRAW = 5,     // one draw skipped per earlier sample, not two    (these two concern the loop over the samples,
+    RAYGEN_FIRST_BACKPLATE = 6,   // the launch index keeps its FIRST sample's backplate   which orc_camera_rays has for itself)
+};
+struct RaygenIndex { uint32_t seed; uint32_t idx[3]; float range; bool alive; };
+template <int VARIANT> inline float raygen_index_as_float(uint32_t i) { return VARIANT == RAYGEN_SIGNED_INDEX ? (float)(int32_t)i : (float)i; }
+// the seed, the pixel index and the ring test of launch index (lx, ly), :411-437
+template <int VARIANT = RAYGEN_REFERENCE> inline RaygenIndex raygen_index(const fovpt_launch_params& params, uint32_t lx, uint32_t ly)
+{
+    RaygenIndex R;
+    const int w = params.frame.size.x;
+    uint32_t idx[3] = {lx, ly, 0};
+    R.seed = tea4(idx[1] * (uint32_t)w + idx[0], params.frame.subframe_index);        // :411
+    idx[0] = idx[0] * params.frame.factor.x + params.frame.offset.x;               // :433 (uint, wraps)
+    idx[1] = idx[1] * params.frame.factor.y + params.frame.offset.y;
+    idx[2] = idx[2] * params.frame.factor.z + 0;
+    float range = length(mk3(raygen_index_as_float<VARIANT>(idx[0]), raygen_index_as_float<VARIANT>(idx[1]), (float)idx[2])
+                         - mk3((float)params.frame.c.x, (float)params.frame.c.y, 0.0f));   // :435
+    R.alive = !(range < params.frame.r_inner || range > params.frame.r_outer);      // :437
+    if (VARIANT == RAYGEN_INNER_EDGE_DEAD && range <= params.frame.r_inner) R.alive = false;
+    R.range = range;
+    R.idx[0] = idx[0]; R.idx[1] = idx[1]; R.idx[2] = idx[2];
+    return R;
+}
+struct RaygenSample { Random rand; float jx, jy; f3 direction, backplate; };
+// one sample of it: Random(seed), the two jitter draws (they advance `seed`), the camera ray and its backplate, :464-495
+template <int VARIANT = RAYGEN_REFERENCE>
+inline RaygenSample raygen_sample(const fovpt_launch_params& params, const ProbeH& probe, const uint32_t idx[3], uint32_t& seed)
+{
+    RaygenSample R;
+    const int w = params.frame.size.x;
+    const int h = params.frame.size.y;
+    const f3 U = mk3(params.camera.U), V = mk3(params.camera.V), W = mk3(params.camera.W);
+    R.rand = Random((int)seed);                                                 // :464
+    float jx, jy;
+    if (VARIANT == RAYGEN_JY_FIRST) { jy = rnd(seed); jx = rnd(seed); }
+    else {
+        jx = rnd(seed);                                                         // :479, x drawn first
+        jy = rnd(seed);
+    }
+    if (VARIANT == RAYGEN_RANDOM_LATE) R.rand = Random((int)seed);
+    const float dx = 2.0f * ((raygen_index_as_float<VARIANT>(idx[0]) + jx) / static_cast<float>(w)) - 1.0f;   // :483-486
+    const float dy = 2.0f * ((raygen_index_as_float<VARIANT>(idx[1]) + jy) / static_cast<float>(h)) - 1.0f;
+    R.jx = jx; R.jy = jy;
+    R.direction = normalize(dx * U + dy * V + W);                               // :491
+    R.backplate = mk3(ProbeEval(probe, ProbeDirToUV(R.direction)));             // :495
+    return R;
+}
+
 // __raygen__renderFrame for one launch index (:392-617)
 void raygen(const Ctx& C, uint32_t lx, uint32_t ly)
 {
     const fovpt_launch_params& params = *C.lp;
     const int w = params.frame.size.x;
     const int h = params.frame.size.y;
-    const f3 eye = mk3(params.camera.eye), U = mk3(params.camera.U), V = mk3(params.camera.V), W = mk3(params.camera.W);
-    uint32_t idx[3] = {lx, ly, 0};
+    const f3 eye = mk3(params.camera.eye);
     const uint32_t subframe_index = params.frame.subframe_index;
     int samples_per_launch = (int)params.samples_per_launch;
     int i = samples_per_launch;
-    uint32_t seed = tea4(idx[1] * (uint32_t)w + idx[0], subframe_index);            // :411
+    const RaygenIndex head = raygen_index<RAYGEN_REFERENCE>(params, lx, ly);         // :411-437
+    uint32_t seed = head.seed;
     f3 result = mk3(0.0f);
-    idx[0] = idx[0] * params.frame.factor.x + params.frame.offset.x;               // :433 (uint, wraps)
-    idx[1] = idx[1] * params.frame.factor.y + params.frame.offset.y;
-    idx[2] = idx[2] * params.frame.factor.z + 0;
-    float range = length(mk3((float)idx[0], (float)idx[1], (float)idx[2]) - mk3((float)params.frame.c.x, (float)params.frame.c.y, 0.0f));   // :435
-    if (range < params.frame.r_inner || range > params.frame.r_outer) return;       // :437
+    if (!head.alive) return;                                                        // :437
     f3 normal = mk3(0.f);                                                           // :443-444 denoiser guides
     f3 albedo = mk3(0.f);
     f3 alpha = mk3(0.f);
@@ -999,7 +1054,8 @@ void raygen(const Ctx& C, uint32_t lx, uint32_t ly)
         RadiancePRD prd;
         prd.radiance = mk3(0.f);
         prd.alpha = mk3(0.f);
-        prd.rand = Random((int)seed);                                               // :464
+        const RaygenSample cam = raygen_sample<RAYGEN_REFERENCE>(params, C.probe, head.idx, seed);   // :464-495
+        prd.rand = cam.rand;
         prd.rayEta = 1.0f;
         prd.pathThroughput = mk3(1.f);
         prd.rayAbsorption = mk3(0.f);
@@ -1008,13 +1064,9 @@ void raygen(const Ctx& C, uint32_t lx, uint32_t ly)
         prd.albedo = mk3(0.0f);
         prd.stateFlags = 0;
         prd.depth = 0;
-        const float jx = rnd(seed);                                                 // :479, x drawn first
-        const float jy = rnd(seed);
-        const float dx = 2.0f * ((static_cast<float>(idx[0]) + jx) / static_cast<float>(w)) - 1.0f;   // :483-486
-        const float dy = 2.0f * ((static_cast<float>(idx[1]) + jy) / static_cast<float>(h)) - 1.0f;
-        f3 ray_direction = normalize(dx * U + dy * V + W);                          // :491
+        f3 ray_direction = cam.direction;
         f3 ray_origin = eye;
-        backplate = mk3(ProbeEval(C.probe, ProbeDirToUV(ray_direction)));           // :495
+        backplate = cam.backplate;
         npaths++;
         float* rec = nullptr;                                                       // (orc_record_samples)
         if (g_rec_rows) {
@@ -1393,6 +1445,55 @@ void orc_probe_sample_at(const fovpt_probe* p, int n, const float* r12, int* row
         color3[3 * i] = c.x; color3[3 * i + 1] = c.y; color3[3 * i + 2] = c.z;
         pdf[i] = pd;
     }
+}
+/* The camera rays of n launch indices (lxy2) of ONE optixLaunch with these parameters (frame size, factor, offset, r_inner,
+ * r_outer, c, subframe_index, camera, probe with host pointers, samples_per_launch): raygen_index / raygen_sample, the head of
+ * raygen().  Per launch index: alive (0 / 1), pixel2 = the wrapped pixel index, range = its distance from the gaze as the ring
+ * test computed it; per sample (alive or not -- the ring test comes after the seed): rand2 = the two words of Random(seed),
+ * jitter2 = jx, jy, dir3; backplate3 = the last sample's.
+ * variant 0 is the reference; 1..6 are the RAYGEN_* deviations, one at a time: for tests that show which cases tell them apart. */
+}  // extern "C"
+namespace {
+template <int VARIANT>
+void camera_rays(const fovpt_launch_params& lp, int n, const uint32_t* lxy2, uint8_t* alive, uint32_t* pixel2, float* range, uint32_t* rand2,
+                 float* jitter2, float* dir3, float* backplate3)
+{
+    // (the loop's own deviations run the reference's two functions)
+    const int HEAD = VARIANT == RAYGEN_SKIP_ONE_DRAW || VARIANT == RAYGEN_FIRST_BACKPLATE ? RAYGEN_REFERENCE : VARIANT;
+    ProbeH P; P.width = lp.probe.width; P.height = lp.probe.height; P.data = (const f4*)lp.probe.data;
+    P.pdfX = P.cdfX = P.pdfY = P.cdfY = nullptr;
+    const size_t spp = lp.samples_per_launch;
+    for (int i = 0; i < n; i++) {
+        const RaygenIndex head = raygen_index<HEAD>(lp, lxy2[2 * i], lxy2[2 * i + 1]);
+        alive[i] = head.alive ? 1 : 0;
+        pixel2[2 * i] = head.idx[0]; pixel2[2 * i + 1] = head.idx[1];
+        range[i] = head.range;
+        uint32_t seed = head.seed;
+        for (size_t s = 0; s < spp; s++) {
+            const uint32_t before = seed;
+            const RaygenSample cam = raygen_sample<HEAD>(lp, P, head.idx, seed);
+            if (VARIANT == RAYGEN_SKIP_ONE_DRAW) { seed = before; (void)rnd(seed); }
+            const size_t k = (size_t)i * spp + s;
+            rand2[2 * k] = cam.rand.seed1; rand2[2 * k + 1] = cam.rand.seed2;
+            jitter2[2 * k] = cam.jx; jitter2[2 * k + 1] = cam.jy;
+            dir3[3 * k] = cam.direction.x; dir3[3 * k + 1] = cam.direction.y; dir3[3 * k + 2] = cam.direction.z;
+            if (VARIANT != RAYGEN_FIRST_BACKPLATE || s == 0) { backplate3[3 * i] = cam.backplate.x; backplate3[3 * i + 1] = cam.backplate.y; backplate3[3 * i + 2] = cam.backplate.z; }
+        }
+    }
+}
+}  // namespace
+extern "C" {
+int orc_camera_rays(const fovpt_launch_params* lp, int n, const uint32_t* lxy2, int variant, uint8_t* alive, uint32_t* pixel2, float* range,
+                    uint32_t* rand2, float* jitter2, float* dir3, float* backplate3)
+{
+    if (!lp || n < 0 || (n && !lxy2) || !lp->probe.data || lp->samples_per_launch == 0) return FOVPT_E_INVALID;
+#define ORC_CAMERA_RAYS(V) case V: camera_rays<V>(*lp, n, lxy2, alive, pixel2, range, rand2, jitter2, dir3, backplate3); return 0
+    switch (variant) {
+        ORC_CAMERA_RAYS(RAYGEN_REFERENCE); ORC_CAMERA_RAYS(RAYGEN_JY_FIRST); ORC_CAMERA_RAYS(RAYGEN_RANDOM_LATE); ORC_CAMERA_RAYS(RAYGEN_SIGNED_INDEX);
+        ORC_CAMERA_RAYS(RAYGEN_INNER_EDGE_DEAD); ORC_CAMERA_RAYS(RAYGEN_SKIP_ONE_DRAW); ORC_CAMERA_RAYS(RAYGEN_FIRST_BACKPLATE);
+    }
+#undef ORC_CAMERA_RAYS
+    return FOVPT_E_INVALID;
 }
 /* the backplate of the raygen program: ProbeDirToUV, then ProbeEval */
 void orc_probe_eval_dir(const fovpt_probe* p, int n, const float* dir3, float* uv2, float* rgba4)

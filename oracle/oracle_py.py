@@ -50,6 +50,7 @@ def lib():
         L.orc_record_samples.restype = C.c_uint64
         L.orc_record_samples.argtypes = [C.c_void_p, C.c_uint64]
         L.orc_camera_uvw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_camera_rays.argtypes = [C.POINTER(abi.LaunchParams), C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib = L
     return _lib
 
@@ -294,6 +295,25 @@ def probe_eval(probe: "HostProbe", dirs):
     t = np.empty((d.shape[0], 4), np.float32)
     lib().orc_probe_eval_dir(C.byref(probe.struct), d.shape[0], _p(d), _p(uv), _p(t))
     return dict(uv=uv, texel=t)
+
+
+CAMERA_VARIANTS = dict(reference=0, jy_first=1, random_late=2, signed_index=3, inner_edge_dead=4, skip_one_draw=5, first_backplate=6)
+
+
+def camera_rays(lp, launch_indices, variant="reference"):
+    """The head of the raygen program for the launch indices (n, 2) = (lx, ly) of ONE launch with the parameters lp (host probe):
+    -> dict(alive (n,) bool, pixel (n, 2) uint32, range (n,) = the distance the ring test compared, rand (n, spp, 2) uint32 = Random(seed) of every sample, jitter (n, spp, 2),
+    dir (n, spp, 3), backplate (n, 3) = the last sample's).  `variant` other than "reference": one deliberate deviation
+    (CAMERA_VARIANTS), for tests that show their cases can tell."""
+    li = np.ascontiguousarray(launch_indices, np.uint32).reshape(-1, 2)
+    n, spp = li.shape[0], int(lp.samples_per_launch)
+    alive, pixel, rng = np.zeros(n, np.uint8), np.zeros((n, 2), np.uint32), np.zeros(n, np.float32)
+    rand, jitter = np.zeros((n, spp, 2), np.uint32), np.zeros((n, spp, 2), np.float32)
+    d, bp = np.zeros((n, spp, 3), np.float32), np.zeros((n, 3), np.float32)
+    rc = lib().orc_camera_rays(C.byref(lp), n, _p(li), CAMERA_VARIANTS[variant], _p(alive), _p(pixel), _p(rng), _p(rand), _p(jitter), _p(d), _p(bp))
+    if rc != 0:
+        raise RuntimeError("orc_camera_rays failed: %d" % rc)
+    return dict(alive=alive.astype(bool), pixel=pixel, range=rng, rand=rand, jitter=jitter, dir=d, backplate=bp)
 
 
 def probe_dir_to_uv(dirs):

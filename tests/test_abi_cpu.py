@@ -97,6 +97,25 @@ def test_config_mirror_matches_the_header(tmp_path):
     assert got[1:] == [getattr(abi.Config, n).offset for n in names]
 
 
+def test_debug_hook_structs_mirror_the_header(tmp_path):
+    """The structs of the test hooks (fovpt_debug_pass, fovpt_debug_shade_*, fovpt_debug_generate_*) member for member."""
+    pairs = (("fovpt_debug_pass", abi.DebugPass), ("fovpt_debug_shade_launch", abi.DebugShadeLaunch), ("fovpt_debug_shade_result", abi.DebugShadeResult),
+             ("fovpt_debug_generate_launch", abi.DebugGenerateLaunch), ("fovpt_debug_generate_result", abi.DebugGenerateResult))
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
+    for cname, mirror in pairs:
+        src += 'printf("%%zu", sizeof(%s));' % cname + "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_) + 'printf("\\n");'
+    src += "return 0;}\n"
+    exe = str(tmp_path / "hook_layout")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    lines = subprocess.check_output([exe]).decode().splitlines()
+    assert len(lines) == len(pairs)
+    for line, (cname, mirror) in zip(lines, pairs):
+        got = [int(x) for x in line.split()]
+        assert got[0] == C.sizeof(mirror), cname
+        assert got[1:] == [getattr(mirror, f[0]).offset for f in mirror._fields_], cname
+    assert C.sizeof(abi.DebugGenerateLaunch) == 36 and C.sizeof(abi.DebugGenerateResult) == 120 and abi.DebugGenerateResult.count.offset == 56
+
+
 def test_default_config_is_the_shipped_reference(so):
     c = abi.Config.reference_default()
     assert (c.uniform, c.r_inner, c.r_outer) == (0, 74, 241)                 # SimplePathtracer.cpp:20-23
