@@ -1076,7 +1076,11 @@ void fovpt_image_free_rgba8(uint32_t* pixels);
 void fovpt_image_free(fovpt_float4* texels);
 
 /* ---- device self-test hook (tests only): evaluates one scalar function on the GPU
- * for n inputs; op codes FOVPT_OP_*.  a,b host arrays (b may be NULL), out host.  */
+ * for n inputs; op codes FOVPT_OP_*.  a,b host arrays (b may be NULL), out host.
+ * The functions of fovpt_detmath.h keep their domains here (nothing is checked): SIN / COS |a| <= 2^20; ACOS a in [-1, 1];
+ * ATAN2 (y = a, x = b) finite operands; LOG every binary32; POW (x = a, y = b) a >= 0 finite or NaN, any b, a = +inf
+ * excluded.  Outside them the result is undefined and need not equal the host's.  SQRT and DIV are the hardware's IEEE
+ * operations on every binary32.                                                     */
 #define FOVPT_OP_SIN    1
 #define FOVPT_OP_COS    2
 #define FOVPT_OP_ACOS   3

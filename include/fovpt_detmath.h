@@ -6,9 +6,31 @@
  * off an NVIDIA device.  libfovpt defines its results in terms of the functions below:
  * every one is evaluated in IEEE binary64 with +,-,*,/ and sqrt only (no fused
  * multiply-add: build with -ffp-contract=off) and rounded once to binary32, so the same
- * source gives the same bits under g++ on the host and under hipcc on gfx950.  The double
- * intermediate keeps each result within 0.5 ulp + 1e-9 ulp of the true value, i.e. it
- * agrees with a correctly rounded libm in all but a vanishing fraction of arguments.
+ * source gives the same bits under g++ on the host and under hipcc on gfx950.
+ *
+ * Accuracy.  Over its domain every function is within 0.5 + 2^-20 binary32 ulp of the true
+ * value (the final rounding's half ulp plus the binary64 evaluation's error; an ulp below
+ * 2^-126 counts as 2^-149), i.e. it agrees with a correctly rounded libm in all but a
+ * vanishing fraction of arguments.  That bound is what tests/test_detmath_cpu.py and
+ * tests/test_detmath_gpu.py assert against a high-precision reference; the measured maxima
+ * are about 0.5 + 2^-23.
+ *
+ * Domains, and what is undefined (no function below checks for it -- they are inlined into
+ * kernels and carry no branch for inputs the library never passes):
+ *   fovpt_dm_sincos/sinf/cosf  |x| <= 2^20.  Larger or non-finite x: undefined.
+ *   fovpt_dm_acosf             [-1, 1].  Outside (and NaN): undefined.
+ *   fovpt_dm_atan2f            finite operands, signed zeros as C99 (atan2(+-0, -0) = +-pi).
+ *                              An infinite or NaN operand: undefined.
+ *   fovpt_dm_logf              every binary32: x < 0 -> NaN, +-0 -> -inf, +inf -> +inf, NaN -> NaN.
+ *   fovpt_dm_powf              x >= 0 finite, any y.  In this order: a NaN operand -> NaN (also for
+ *                              y = 0 or x = 1, unlike C99); y = 0 -> 1; x = +-0 -> +0 for y > 0, +inf
+ *                              for y < 0 (-0 counts as +0); x < 0 -> NaN for every y (no integer-
+ *                              exponent case); x = 1 -> 1; y = +-inf -> 0 or +inf as C99.  Results
+ *                              overflow to +inf and underflow through the subnormals to +0.
+ *                              x = +inf: undefined.
+ *   fovpt_dm_floor             |x| < 2^51 (the callers above stay below 2^21 and 2^11).
+ * "Undefined" means what it does in C: the conversions to integer inside differ between x86
+ * and gfx950 there, so not even host/device agreement holds.
  *
  * Call sites in the reference: Probe.cuh:40-41,53-55,161 (acosf, atan2, sinf, cosf),
  * Disney.cuh:63 (logf), :216-217,293-294 (sinf, cosf), maths.h:250-251,261 (cosf, sinf),
@@ -29,21 +51,28 @@ FOVPT_HD double fovpt_dm_bits2d(uint64_t u) { double d; __builtin_memcpy(&d, &u,
 FOVPT_HD uint64_t fovpt_dm_d2bits(double d) { uint64_t u; __builtin_memcpy(&u, &d, 8); return u; }
 FOVPT_HD uint32_t fovpt_dm_f2bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 
-/* floor for |x| < 2^51 without libm */
+/* floor for |x| < 2^51 without libm (beyond 2^63, and for NaN, the cast is undefined) */
 FOVPT_HD double fovpt_dm_floor(double x)
 {
     double t = (double)(long long)x;      /* truncation toward zero */
     return (t > x) ? t - 1.0 : t;
 }
 
-/* sin and cos of a binary32 argument, |x| < 1e6 */
+/* sin and cos of a binary32 argument, |x| <= 2^20 */
 FOVPT_HD void fovpt_dm_sincos(float xf, float* s_out, float* c_out)
 {
     const double x = (double)xf;
     const double kd = fovpt_dm_floor(x * 0.63661977236758138 + 0.5);
     const long long k = (long long)kd;
-    /* x - k*pi/2 with pi/2 split in two doubles */
-    const double r = (x - kd * 1.5707963267948966) - kd * 6.123233995736766e-17;
+    /* x - k*pi/2 with pi/2 = P1 + P2 + P3 (to 2^-122): P1 and P2 carry 33 significant bits each, so kd*P1 and
+     * kd*P2 are exact for kd < 2^20, x - kd*P1 is exact (a 24-bit and a 53-bit number that nearly cancel), and what
+     * rounds after that is of the order 2^-53 |r|.  A 53-bit head instead makes the first product round and r wrong
+     * by up to 2^-53 |x|: 12 ulp of the result at |x| = 256.  For every binary32 x in [0, 2 pi] the two reductions
+     * give the same sin and cos bits. */
+    const double p1 = 1.5707963267341256;          /* 0x1.921fb544p+0 (decimal: C++14 has no hexadecimal literals) */
+    const double p2 = 6.077100506303966e-11;       /* 0x1.0b4611a6p-34 */
+    const double p3 = 2.0222662487959506e-21;      /* 0x1.3198a2e037073p-69 */
+    const double r = ((x - kd * p1) - kd * p2) - kd * p3;
     const double z = r * r;
     /* Taylor, |r| <= pi/4: truncation < 3e-14 relative */
     double ps = -1.0 / 1307674368000.0;            /* -1/15! */
@@ -70,7 +99,8 @@ FOVPT_HD void fovpt_dm_sincos(float xf, float* s_out, float* c_out)
     case 2:  s = -sr; c = -cr; break;
     default: s = -cr; c = sr;  break;
     }
-    *s_out = (float)s;
+    /* sin(-0) = -0 (a select, not a branch): above, r + r*(z*ps) adds two zeros of opposite sign, which gives +0 */
+    *s_out = (xf == 0.0f) ? xf : (float)s;
     *c_out = (float)c;
 }
 
