@@ -415,7 +415,39 @@ class WarpCounts(C.Structure):
     _fields_ = [("splatted", C.c_uint64), ("direct", C.c_uint64), ("filled", C.c_uint64), ("empty", C.c_uint64)]
 
 
-PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS = 0x4b505646, 1, 4      # FOVPT_PACKET_*
+FOCUS_FIXED, FOCUS_AUTO = 0, 1                 # FOVPT_FOCUS_*
+FOCUS_MAX_RADIUS, FOCUS_MAX_METER_RADIUS, FOCUS_BINS = 8, 64, 256
+
+
+class FocusConfig(C.Structure):
+    """fovpt_focus_config: mode, the gaze disc and rank of the meter, the blur's cap and strength, the fixed and the default focus
+    distance and the adaptation rates (defaults: fovpt_focus_defaults)."""
+    _fields_ = [
+        ("mode", C.c_int32), ("meter_radius", C.c_int32), ("rank_permille", C.c_int32), ("max_radius", C.c_int32),
+        ("strength", C.c_float), ("focus_distance", C.c_float), ("focus_default", C.c_float),
+        ("adapt_nearer", C.c_float), ("adapt_farther", C.c_float),
+        ("_reserved", C.c_int32 * 7),
+    ]
+
+    def copy(self):
+        m = FocusConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(FocusConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class FocusState(C.Structure):
+    """struct fovpt_focus_state: the metered distance, the adapted reciprocal distance and distance, the pixels the last meter
+    counted and the AUTO steps since create / reset."""
+    _fields_ = [
+        ("focus_metered", C.c_float), ("inv_focus", C.c_float), ("focus", C.c_float), ("_pad", C.c_float),
+        ("count", C.c_uint64), ("steps", C.c_uint64),
+    ]
+
+
+PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS =0x4b505646, 1, 4      # FOVPT_PACKET_*
 PACKET_NEAREST, PACKET_SMOOTH = 0, 1
 
 
@@ -469,6 +501,8 @@ assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.re
 assert C.sizeof(ExposeConfig) == 80 and (ExposeConfig.low_permille.offset, ExposeConfig.key.offset) == (32, 48)
 assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
 assert C.sizeof(WarpCamera) == 48 and C.sizeof(WarpConfig) == 32 and C.sizeof(WarpCounts) == 32
+assert C.sizeof(FocusConfig) == 64 and (FocusConfig.strength.offset, FocusConfig._reserved.offset) == (16, 36)
+assert C.sizeof(FocusState) == 32 and FocusState.count.offset == 16
 assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
 assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeader.passes.offset) == (16, 32)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8

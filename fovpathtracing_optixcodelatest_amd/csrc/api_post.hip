@@ -1,6 +1,6 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
 // fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), fovpt_warp
-// (warp.hip), and their defaults.
+// (warp.hip), fovpt_focus (focus.hip), and their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -292,6 +292,24 @@ int expose_reset(fovpt_ctx* c, hipStream_t st)
     if (!c->ex_state.p) return FOVPT_OK;
     if (st) HIPCHK(c, hipMemsetAsync(c->ex_state.p, 0, sizeof(ExposeState), st));
     else HIPCHK(c, hipMemset(c->ex_state.p, 0, sizeof(ExposeState)));
+    return FOVPT_OK;
+}
+
+// fovpt_focus's state record, made (zeroed) on first use
+static int reserve_focus_state(fovpt_ctx* c)
+{
+    if (c->fc_state.p) return FOVPT_OK;
+    HIPCHK(c, c->fc_state.reserve(sizeof(FocusState)));
+    HIPCHK(c, hipMemset(c->fc_state.p, 0, sizeof(FocusState)));
+    return FOVPT_OK;
+}
+
+// steps = 0: the next AUTO step is a first step (no record yet: it will be made that way)
+int focus_reset(fovpt_ctx* c, hipStream_t st)
+{
+    if (!c->fc_state.p) return FOVPT_OK;
+    if (st) HIPCHK(c, hipMemsetAsync(c->fc_state.p, 0, sizeof(FocusState), st));
+    else HIPCHK(c, hipMemset(c->fc_state.p, 0, sizeof(FocusState)));
     return FOVPT_OK;
 }
 
@@ -785,6 +803,124 @@ int fovpt_warp(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_cam
     fovpt_launch_warp_scatter(st, c->dn_frame, a, g.prim, g.pos, (uint64_t*)c->wp_keys.p, (uint64_t*)c->wp_counts.p);
     fovpt_launch_warp_resolve(st, c->dn_w, c->dn_h, wc->fill_radius, (const uint64_t*)c->wp_keys.p, in, rin, out_color, out_rgba, out_map,
                               (uint64_t*)c->wp_counts.p);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- gaze-metered focus distance and depth of field (focus.hip; its definition: tests/focus_ref.py) ---------------------------
+// (conventions, not measurements: include/fovpt.h)
+int fovpt_focus_defaults(fovpt_focus_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->mode = FOVPT_FOCUS_AUTO;
+    out->meter_radius = 12;
+    out->rank_permille = 250;
+    out->max_radius = 6;
+    out->strength = 8.0f;
+    out->focus_distance = 1.0f;
+    out->focus_default = 1.0f;
+    out->adapt_nearer = 1.0f; out->adapt_farther = 1.0f;
+    return FOVPT_OK;
+}
+
+int fovpt_focus_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_focus_buffers", c->fc_color, c->fc_rgba, *color, *rgba);
+}
+
+int fovpt_focus_state(fovpt_ctx* c, struct fovpt_focus_state* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "fovpt_focus_state: null argument");
+    memset(out, 0, sizeof(*out));
+    if (!c->fc_state.p) return FOVPT_OK;                                   // no AUTO step yet
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));
+    HIPCHK(c, hipMemcpy(out, c->fc_state.p, sizeof(*out), hipMemcpyDeviceToHost));
+    return FOVPT_OK;
+}
+
+int fovpt_focus_reset(fovpt_ctx* c)
+{
+    if (!c) return FOVPT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    return focus_reset(c, c->shadow_stream);
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  Without a caller's G-buffer the rendered frame's first (the
+// same stream, into fovpt_gbuffer's buffers).  AUTO: k_focus_meter, k_focus_radius, k_focus_gather; the focus goes from the first to
+// the second through the state record, never through the host.  FIXED: the last two.
+int fovpt_focus(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_focus_config* fc, const fovpt_gbuffer_ptrs* gbuffer,
+                const fovpt_float4* in_color, fovpt_float4* out_color, uint32_t* out_rgba, float* out_coc)
+{
+    const char* who = "fovpt_focus";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !fc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (fc->mode != FOVPT_FOCUS_FIXED && fc->mode != FOVPT_FOCUS_AUTO) return fail(c, FOVPT_E_INVALID, "%s: unknown mode %d", who, fc->mode);
+    if (fc->meter_radius < 0 || fc->meter_radius > FOVPT_FOCUS_MAX_METER_RADIUS)
+        return fail(c, FOVPT_E_INVALID, "%s: meter_radius %d outside 0 .. %d", who, fc->meter_radius, FOVPT_FOCUS_MAX_METER_RADIUS);
+    if (fc->rank_permille < 0 || fc->rank_permille > 1000) return fail(c, FOVPT_E_INVALID, "%s: rank_permille %d outside 0 .. 1000", who, fc->rank_permille);
+    if (fc->max_radius < 0 || fc->max_radius > FOVPT_FOCUS_MAX_RADIUS)
+        return fail(c, FOVPT_E_INVALID, "%s: max_radius %d outside 0 .. %d", who, fc->max_radius, FOVPT_FOCUS_MAX_RADIUS);
+    if (!(fc->strength >= 0.0f && fc->strength <= FOVPT_SIGMA_MAX)) return fail(c, FOVPT_E_INVALID, "%s: strength %g outside [0, %g]", who, (double)fc->strength, (double)FOVPT_SIGMA_MAX);
+    const float dist[2] = {fc->focus_distance, fc->focus_default};
+    for (float v : dist)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "%s: focus distance %g outside [%g, %g]", who, (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    const float rates[2] = {fc->adapt_nearer, fc->adapt_farther};
+    for (float v : rates)
+        if (!(v > 0.0f && v <= 1.0f)) return fail(c, FOVPT_E_INVALID, "%s: adapt rate %g outside (0, 1]", who, (double)v);
+    for (int32_t r : fc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    if (!gbuffer && (!c->has_scene || lp->traversable != c->scene_id)) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    { const int rc_ = check_rendered_frame(c, lp, who, "gather from", nullptr); if (rc_) return rc_; }
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    if (npix >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
+    if (gbuffer && (gbuffer->width != c->dn_w || gbuffer->height != c->dn_h || !gbuffer->prim || !gbuffer->position))
+        return fail(c, FOVPT_E_INVALID, "%s: the G-buffer is not of the frame's size %d x %d, or has a null prim or position", who, c->dn_w, c->dn_h);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+
+    // buffers: the context's own outputs where the caller gave none, the (r, tp) pairs, the state
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = own_outputs(c, who, c->fc_color, c->fc_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    HIPCHK(c, c->fc_rt.reserve(npix * 8));
+    const bool aut = fc->mode == FOVPT_FOCUS_AUTO;
+    if (aut) { const int rc_ = reserve_focus_state(c); if (rc_) return rc_; }
+    // the gather reads other pixels' colours and pairs while it writes, the radius pass the G-buffer: no output is one of them
+    GBufferDev g;
+    if (gbuffer) { g.prim = gbuffer->prim; g.pos = (float4*)gbuffer->position; g.nrm = (float4*)gbuffer->normal; g.alb = (float4*)gbuffer->albedo; }
+    else { g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = nullptr; g.alb = nullptr; }      // (null until the first trace)
+    const void* outs[3] = {out_color, out_rgba, out_coc};
+    const void* ins[4] = {in, g.prim, g.pos, c->fc_rt.p};
+    for (int i = 0; i < 3; i++) {
+        if (!outs[i]) continue;
+        for (const void* p : ins)
+            if (p == outs[i]) return fail(c, FOVPT_E_INVALID, "%s: an output is an input of the call (the gather reads across pixels)", who);
+        for (int j = 0; j < i; j++)
+            if (outs[j] == outs[i]) return fail(c, FOVPT_E_INVALID, "%s: two outputs are the same buffer", who);
+    }
+
+    if (!gbuffer) { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, who); if (rc_) return rc_; }   // the rendered frame's camera
+    FocusArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cx = (int64_t)c->dn_frame.cx; a.cy = (int64_t)c->dn_frame.cy;       // (frame.c is unsigned: no difference below wraps)
+    const int64_t R = fc->meter_radius;
+    const int64_t x0 = a.cx - R > 0 ? a.cx - R : 0, x1 = a.cx + R < c->dn_w - 1 ? a.cx + R : c->dn_w - 1;
+    const int64_t y0 = a.cy - R > 0 ? a.cy - R : 0, y1 = a.cy + R < c->dn_h - 1 ? a.cy + R : c->dn_h - 1;
+    if (x0 <= x1 && y0 <= y1) { a.x0 = (int32_t)x0; a.x1 = (int32_t)x1; a.y0 = (int32_t)y0; a.y1 = (int32_t)y1; }
+    else { a.x0 = a.y0 = 0; a.x1 = a.y1 = -1; }                            // the disc's square misses the frame
+    a.meter_radius = fc->meter_radius; a.rank_permille = fc->rank_permille; a.max_radius = fc->max_radius;
+    a.strength = fc->strength; a.focus_default = fc->focus_default;
+    a.adapt_nearer = fc->adapt_nearer; a.adapt_farther = fc->adapt_farther;
+    a.inv_focus = 1.0f / fc->focus_distance;
+    const hipStream_t st = c->shadow_stream;
+    FocusState* state = aut ? (FocusState*)c->fc_state.p : nullptr;
+    if (aut) fovpt_launch_focus_meter(st, c->dn_w, a, g.prim, g.pos, state);
+    fovpt_launch_focus_radius(st, npix, a, state, g.prim, g.pos, (float2*)c->fc_rt.p, out_coc);
+    fovpt_launch_focus_gather(st, c->dn_w, c->dn_h, fc->max_radius, in, (const float2*)c->fc_rt.p, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }

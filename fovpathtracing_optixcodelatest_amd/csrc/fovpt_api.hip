@@ -828,6 +828,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     free_scene(c);
     c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
     { const int rc_ = expose_reset(c, nullptr); if (rc_) return rc_; }   // fovpt_expose adapts to another scene from scratch
+    { const int rc_ = focus_reset(c, nullptr); if (rc_) return rc_; }    // and fovpt_focus meters it from scratch
     take_costs(c);                                   // fovpt_hierarchy_cost: (the device is idle) no measurement of the old scene stays in flight
     c->cost_updates = c->cost_measured = 0;
     uint64_t ntri = 0;
@@ -1017,6 +1018,8 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->wp_keys.p) HIPCHK(c, c->wp_keys.reserve(n * 8));                                                // and fovpt_warp's keys and outputs
     if (c->wp_color.p) HIPCHK(c, c->wp_color.reserve(n * 16));
     if (c->wp_rgba.p) HIPCHK(c, c->wp_rgba.reserve(n * 4));
+    if (c->fc_rt.p) HIPCHK(c, c->fc_rt.reserve(n * 8));                                                    // and fovpt_focus's pairs and outputs (its state stays)
+    if (c->fc_color.p) { HIPCHK(c, c->fc_color.reserve(n * 16)); HIPCHK(c, c->fc_rgba.reserve(n * 4)); }
     c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
@@ -1191,6 +1194,8 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "expose_histogram") == 0 && c->ex_hist.p) { *ptr = c->ex_hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
     if (strcmp(name, "expose_state") == 0 && c->ex_state.p) { *ptr = c->ex_state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
     if (strcmp(name, "warp_keys") == 0 && c->wp_keys.p) { *ptr = c->wp_keys.p; *bytes = c->wp_keys.bytes; return FOVPT_OK; }   // fovpt_warp's keys, once made
+    if (strcmp(name, "focus_state") == 0 && c->fc_state.p) { *ptr = c->fc_state.p; *bytes = sizeof(FocusState); return FOVPT_OK; }   // fovpt_focus's state record
+    if (strcmp(name, "focus_scratch") == 0 && c->fc_rt.p) { *ptr = c->fc_rt.p; *bytes = c->fc_rt.bytes; return FOVPT_OK; }   // and its (r, tp) pairs, once made
     if (strcmp(name, "gbuffer_hit") == 0 && c->gb_hit.p) { *ptr = c->gb_hit.p; *bytes = c->gb_pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {

@@ -177,6 +177,10 @@ struct fovpt_ctx {
     // ahead of every warp; the host reads and adds them nowhere but in fovpt_warp_counts) and the context's own outputs; all allocated on
     // first use
     DevBuf wp_keys, wp_counts, wp_color, wp_rgba;
+    // fovpt_focus: the device state record (a struct fovpt_focus_state, zeroed when made and by a reset: steps 0 = the next AUTO
+    // step is a first step; the host never reads it outside fovpt_focus_state), the (r, tp) pairs of the last call (8 bytes per
+    // pixel) and the context's own outputs; all allocated on first use
+    DevBuf fc_state, fc_rt, fc_color, fc_rgba;
     // fovpt_packet_submit / fovpt_packet_wait (api_packet.hip), all made by a context's first submit: the copy stream, and per slot
     // the device buffer an encode writes (one each, so that an encode never overwrites a packet that is still being copied), the
     // pinned host buffer its copy fills (grown on demand), the event recorded on fovpt_stream() behind the encode, which the copy
@@ -227,5 +231,6 @@ void drop_animation(fovpt_ctx* c);
 int reserve_gbuffer(fovpt_ctx* c, size_t n);
 int reserve_temporal(fovpt_ctx* c, size_t n);
 int expose_reset(fovpt_ctx* c, hipStream_t st);      // (st null: the device is idle, reset now)
+int focus_reset(fovpt_ctx* c, hipStream_t st);       // (likewise)
 int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
                     const GBufferDev* target = nullptr);

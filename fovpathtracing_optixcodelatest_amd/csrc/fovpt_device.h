@@ -326,6 +326,26 @@ void fovpt_launch_warp_scatter(hipStream_t st, const FrameDev& fd, const WarpArg
 // input or another output (a pixel reads other pixels' inputs)
 void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,
                                fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map, uint64_t* counts);
+// fovpt_focus (focus.hip): the meter over the gaze disc's bounding square [x0, x1] x [y0, y1] (clipped to the frame on the host;
+// x1 < x0 or y1 < y0: nothing to meter) with the rank search and the adapt step in its one block (AUTO), the per-pixel (r, tp)
+// pairs into `rt` (state null: at a.inv_focus) and the gather.  No output of the gather is `in` or `rt` (a pixel reads other
+// pixels').  FocusState: the struct shares its name with the entry point, which hides it in C++.
+typedef struct fovpt_focus_state FocusState;
+#define FOVPT_FOCUS_BLOCK 1024           // threads of the meter's one block
+#define FOVPT_FOCUS_TILE_W 32            // outputs of a block of the gather: a thread each
+#define FOVPT_FOCUS_TILE_H 16
+struct FocusArgs {
+    int32_t x0, x1, y0, y1;             // the meter's square
+    int64_t cx, cy;                     // the rendered gaze
+    int32_t meter_radius, rank_permille, max_radius;
+    float strength, focus_default, adapt_nearer, adapt_farther;
+    float inv_focus;                    // FIXED: 1.0f / focus_distance
+};
+void fovpt_launch_focus_meter(hipStream_t st, int w, const FocusArgs& a, const uint32_t* prim, const float4* pos, FocusState* state);
+void fovpt_launch_focus_radius(hipStream_t st, size_t npix, const FocusArgs& a, const FocusState* state, const uint32_t* prim, const float4* pos,
+                               float2* rt, float* out_coc);
+void fovpt_launch_focus_gather(hipStream_t st, int w, int h, int max_radius, const fovpt_float4* in, const float2* rt, fovpt_float4* out_color,
+                               uint32_t* out_rgba);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32

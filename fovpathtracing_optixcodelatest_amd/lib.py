@@ -28,6 +28,7 @@ EXPORTS = [
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
     "fovpt_warp_defaults", "fovpt_warp", "fovpt_warp_buffers", "fovpt_warp_counts", "fovpt_temporal_gbuffer",
+    "fovpt_focus_defaults", "fovpt_focus", "fovpt_focus_buffers", "fovpt_focus_state", "fovpt_focus_reset",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
     "fovpt_packet_check", "fovpt_packet_decode_host",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
@@ -193,7 +194,12 @@ def load():
     L.fovpt_warp_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_warp_counts.argtypes = [vp, C.POINTER(abi.WarpCounts)]
     L.fovpt_temporal_gbuffer.argtypes = [vp, C.POINTER(abi.GBufferPtrs)]
-    L.fovpt_packet_describe.argtypes = [vp, C.POINTER(abi.LaunchParams), u32, C.POINTER(abi.PacketHeader)]
+    L.fovpt_focus_defaults.argtypes = [C.POINTER(abi.FocusConfig)]
+    L.fovpt_focus.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.FocusConfig), C.POINTER(abi.GBufferPtrs), vp, vp, vp, vp]
+    L.fovpt_focus_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_focus_state.argtypes = [vp, C.POINTER(abi.FocusState)]
+    L.fovpt_focus_reset.argtypes = [vp]
+    L.fovpt_packet_describe.argtypes =[vp, C.POINTER(abi.LaunchParams), u32, C.POINTER(abi.PacketHeader)]
     L.fovpt_packet_encode.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, vp]
     L.fovpt_packet_submit.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, C.POINTER(i32)]
     L.fovpt_packet_wait.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]

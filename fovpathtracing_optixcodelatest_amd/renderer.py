@@ -5,6 +5,7 @@ types it consumes (sutil::Camera, ProbeData), on top of the C ABI in include/fov
 compute happens in libfovpt.so (HIP, gfx950); nothing here touches pixels.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -515,6 +516,55 @@ class SampleRenderer:
     def downloadWarpedColor(self):
         """The float4 output of the last warp() into the renderer's own buffer."""
         return self._download_frame(self.warp_buffers()[0], 4)
+
+    # -- gaze-metered focus distance and depth of field (include/fovpt.h, fovpt_focus)
+    @staticmethod
+    def focus_defaults() -> abi.FocusConfig:
+        d = abi.FocusConfig()
+        lib.check(None, lib.load().fovpt_focus_defaults(C.byref(d)))
+        return d
+
+    def focus_strength(self, lens_radius) -> float:
+        """cfg.strength of a thin lens of radius lens_radius (scene units) at the current camera and frame height: the blur
+        radius in pixels per unit of |1 / t - 1 / focus|, lens_radius * (h / 2) * |W| / |V|.  Host only."""
+        cam = self.launchParams.camera
+        norm = lambda v: math.sqrt(float(v.x) ** 2 + float(v.y) ** 2 + float(v.z) ** 2)
+        return float(lens_radius) * (self.launchParams.frame.size.y / 2.0) * norm(cam.W) / norm(cam.V)
+
+    def focus(self, cfg=None, gbuffer=None, in_color=None, out_color=None, out_rgba=None, out_coc=None):
+        """Meters the distance of what the eye looks at in the frame last rendered (the cfg.rank_permille rank of the hit
+        distances inside the gaze disc), moves the renderer's focus towards it in 1 / distance and blurs the frame by a per-pixel
+        radius cfg.strength * |1 / t - 1 / focus| (at most cfg.max_radius pixels), all on the device; cfg.mode = abi.FOCUS_FIXED
+        focuses at cfg.focus_distance and leaves the state alone.  gbuffer: an abi.GBufferPtrs of the rendered frame
+        (temporal_gbuffer() after a post() / temporal() step saves the trace), None: traced by the call.  in_color: device pointer
+        of a float4 frame (None: the accum buffer; typically post_buffers()[0]).  out_color / out_rgba: device pointers, or None
+        for the renderer's own buffers (downloadFocus); out_coc: device pointer of a float frame (the radii) or None.  Enqueued on
+        the renderer's stream, not synchronised (downloadFocus and focus_state() synchronise)."""
+        cfg = cfg if cfg is not None else self.focus_defaults()
+        self._check(self._L.fovpt_focus(self._ctx, C.byref(self.launchParams), C.byref(cfg), C.byref(gbuffer) if gbuffer is not None else None,
+                                        in_color, out_color, out_rgba, out_coc))
+
+    def focus_buffers(self):
+        """Device addresses of the renderer's own focused outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_focus_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def focus_state(self) -> abi.FocusState:
+        """The focus state after everything enqueued so far (synchronises the renderer's stream); zeros before any AUTO step."""
+        s = abi.FocusState()
+        self._check(self._L.fovpt_focus_state(self._ctx, C.byref(s)))
+        return s
+
+    def focus_reset(self):
+        """The next AUTO focus() is a first step: its focus is the metered one."""
+        self._check(self._L.fovpt_focus_reset(self._ctx))
+
+    def downloadFocus(self):
+        """The outputs of the last focus() into the renderer's own buffers: ((H, W, 4) float32 colour, rgba8 shaped like
+        downloadPixels())."""
+        col, rgba = self.focus_buffers()
+        return self._download_frame(col, 4), self._download_frame(rgba, 1)
 
     # -- foveated frame packets (include/fovpt.h, fovpt_packet_*): a frame off the device, small and without stopping the renderer
     def describePacket(self, sequence=0) -> abi.PacketHeader:

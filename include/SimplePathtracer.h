@@ -4,6 +4,7 @@
 // OptiX.  Header-only; link with -lfovpt.  Errors become std::runtime_error like the reference's
 // sutil::Exception (sutil/Exception.h:245).
 #pragma once
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -283,6 +284,55 @@ public:
         uint32_t* rgba = nullptr;
         check(fovpt_warp_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
+    // ---- gaze-metered focus distance and depth of field (include/fovpt.h, fovpt_focus): meters the distance of what the eye looks
+    // at, moves the renderer's focus towards it and blurs in_color (null: the accum buffer) by a per-pixel radius around that
+    // distance into the renderer's own focused buffers, then a device sync like render().  reuse_gbuffer: take the G-buffer of the
+    // last post() / temporal() step (fovpt_temporal_gbuffer) in place of tracing one.  Typically behind post(): focusPost()
+    void focus(bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr)
+    {
+        fovpt_focus_config fc;
+        check(fovpt_focus_defaults(&fc));
+        focus(fc, reuse_gbuffer, in_color);
+    }
+    void focus(const fovpt_focus_config& fc, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr)
+    {
+        fovpt_gbuffer_ptrs g;
+        if (reuse_gbuffer) check(fovpt_temporal_gbuffer(ctx, &g));
+        check(fovpt_focus(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &fc, reuse_gbuffer ? &g : nullptr, in_color, nullptr, nullptr,
+                          nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // focus() of the colour the last post() left in the renderer's own post buffers, with that step's G-buffer
+    void focusPost(const fovpt_focus_config& fc)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_post_buffers(ctx, &color, &rgba));
+        focus(fc, true, color);
+    }
+    // cfg.strength of a thin lens of radius lens_radius (scene units) at the current camera and frame height
+    float focusStrength(float lens_radius) const
+    {
+        const float3 V = launchParams.camera.V, W = launchParams.camera.W;
+        return lens_radius * (launchParams.frame.size.y * 0.5f) * sqrtf(W.x * W.x + W.y * W.y + W.z * W.z) / sqrtf(V.x * V.x + V.y * V.y + V.z * V.z);
+    }
+    struct fovpt_focus_state focusState()
+    {
+        struct fovpt_focus_state s;
+        check(fovpt_focus_state(ctx, &s));
+        return s;
+    }
+    void focusReset() { check(fovpt_focus_reset(ctx)); }
+    // the focused float4 colour (may be null) and rgba8 pixels (may be null), like downloadPixels
+    void downloadFocus(fovpt_float4 h_color[], uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_focus_buffers(ctx, &color, &rgba));
+        const size_t n = (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y;
+        if (h_color) check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * n));
+        if (h_pixels) check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * n));
     }
     // ---- foveated frame packets (include/fovpt.h, fovpt_packet_*): the frame last rendered -- in_rgba null: the renderer's own
     // frame buffer; or the rgba8 output of post() / expose() -- as a small self-describing packet in pinned host memory, without a

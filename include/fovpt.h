@@ -885,6 +885,100 @@ int fovpt_warp_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 int fovpt_warp_counts(fovpt_ctx* ctx, struct fovpt_warp_counts* out);
 int fovpt_temporal_gbuffer(fovpt_ctx* ctx, fovpt_gbuffer_ptrs* out);
 
+/* ---- gaze-metered focus distance and depth of field ----------------------------------------------------------------------------
+ * New with this library.  Every other stage leaves the image sharp at all depths.  fovpt_focus meters the distance of what the eye
+ * looks at from the G-buffer (meter -> adapt -> apply, the pattern of fovpt_expose: device state, no host synchronisation) and blurs
+ * the frame by a per-pixel radius around that distance; fovpt_focus_state hands the metered distance to a varifocal or
+ * vergence-aware client.  The stage is meant behind fovpt_post and ahead of fovpt_expose.
+ *   fovpt_focus              works on the frame last issued with fovpt_render(ctx, lp) as it was rendered: its size, camera and
+ *                            gaze.  gbuffer NULL: the call traces the rendered camera's G-buffer into fovpt_gbuffer's buffers (so it
+ *                            needs the scene); non-NULL: the pointers are used as given, only prim and position are read, and the
+ *                            caller vouches that they belong to the frame (fovpt_temporal_gbuffer's set saves the trace).
+ *                            in_color NULL = accum_buffer; out_color / out_rgba NULL = the context's own (fovpt_focus_buffers:
+ *                            allocated on first use together with an 8-byte-per-pixel scratch, reallocated by fovpt_resize, freed by
+ *                            fovpt_destroy; a context that never calls the stage pays nothing); out_coc (may be NULL): the blur
+ *                            radius per pixel, float.  Enqueued on fovpt_stream(), not synchronised, ordered like fovpt_denoise.
+ *                            The definition, operation by operation (tests/focus_ref.py), every fp32 +, -, * and / one unfused
+ *                            operation; w, h the frame size, a pixel is a hit iff prim != 0xffffffff, t = position.w,
+ *                            min(a, b) = a < b ? a : b:
+ *                              1 meter (AUTO)  cx, cy the rendered gaze (frame.c, unsigned 32 bits) as signed 64-bit integers.  A
+ *                                          pixel (x, y) of the frame counts iff (x-cx)^2 + (y-cy)^2 <= meter_radius^2 in integers,
+ *                                          it is a hit and t > 0 (in float).  With u the bits of t, bin = clamp((u >> 20) - 888,
+ *                                          0, 255): fovpt_expose's bins, 8 per octave over 2^-16 .. 2^16.  h[bin] += 1, T = sum h.
+ *                                          T == 0: focus_metered = the present focus, on a first step focus_default.  Otherwise
+ *                                          k = min(T * rank_permille / 1000, T - 1) (integer division), b the smallest bin with
+ *                                          h[0] + .. + h[b] > k, focus_metered the float with the bits ((b + 888) << 20) | 0x80000
+ *                              2 adapt     in reciprocal distance.  D_m = 1.0f / focus_metered.  First step after create / reset:
+ *                                          D = D_m; otherwise D = D + a * (D_m - D), a = adapt_nearer if D_m > D else adapt_farther;
+ *                                          a later step with T == 0 leaves D as it is (D_m = D).  focus = 1.0f / D.  The state
+ *                                          record gets focus_metered, inv_focus = D, focus, count = T, steps + 1.
+ *                                          FOCUS_FIXED: D = 1.0f / focus_distance; nothing is metered, the state is untouched
+ *                              3 radius    per pixel: i = 1.0f / t for a hit, 0.0f for a miss; s = strength * fabsf(i - D);
+ *                                          r = s < (float)max_radius ? s : (float)max_radius; out_coc[p] = r
+ *                              4 gather    per pixel p = (x, y): tp = t for a hit, +inf for a miss.  The taps q = (x + dx, y + dy),
+ *                                          dy = -max_radius .. max_radius the outer loop, dx likewise the inner one; taps outside
+ *                                          the frame are skipped.  re = (tq > tp) ? min(rq, rp) : rq -- a surface behind p does
+ *                                          not bleed over p further than p itself is blurred, a surface in front spreads by its
+ *                                          own radius --, e = re + 0.5f; the tap covers iff (float)(dx*dx + dy*dy) <= e * e.
+ *                                          Only covering taps are added, in visiting order, into one running sum each:
+ *                                          g = 1.0f / (e * e), den += g, num.c += g * in.c for c = r, g, b.  The centre always
+ *                                          covers.  If it is the only covering tap out_color[p] = in_color[p], all four components
+ *                                          bit for bit; otherwise (num.r / den, num.g / den, num.b / den, in_color[p].w).
+ *                                          out_rgba[p] = make_color(reinhard(out_color[p].rgb * 16, 1)) as in every other stage.
+ *                                          Outputs for non-finite or negative input colours, or for a caller's G-buffer with
+ *                                          non-finite t, are unspecified.
+ *                            So strength = 0, max_radius = 0 or a scene entirely at the focus distance returns the input bit for
+ *                            bit, and an in-focus object keeps its pixels exactly, whatever lies behind it.
+ *                            The state survives fovpt_resize and fovpt_set_probe; fovpt_focus_reset and fovpt_set_scene reset it.
+ *                            All or nothing, checked before anything is enqueued.  FOVPT_E_INVALID: null ctx / lp / fc; an unknown
+ *                            mode; meter_radius outside 0 .. FOVPT_FOCUS_MAX_METER_RADIUS; rank_permille outside 0 .. 1000;
+ *                            max_radius outside 0 .. FOVPT_FOCUS_MAX_RADIUS; strength NaN, negative or above FOVPT_SIGMA_MAX;
+ *                            focus_distance or focus_default outside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX] or NaN; an adapt rate
+ *                            outside (0, 1] or NaN; non-zero reserved fields; a gbuffer whose size is not the frame's or with a
+ *                            null prim or position; a null input; width * height >= 2^31; any output equal to an input (the colour,
+ *                            the G-buffer's prim or position, the scratch: the kernels gather across pixels; base addresses are
+ *                            compared) or to another output; a frame rendered with world > 1.  FOVPT_E_NO_FRAME,
+ *                            FOVPT_E_NO_SCENE: as fovpt_warp (the scene only where the call traces).
+ *   fovpt_focus_defaults     host only, no context.  CONVENTIONS, NOT MEASUREMENTS: AUTO, meter_radius 12, rank_permille 250 (the
+ *                            nearer quartile: the eye settles on the nearer surface under the gaze), max_radius 6, strength 8,
+ *                            focus_distance 1, focus_default 1, both adapt rates 1 (the caller derives 1 - exp(-dt / tau) from its
+ *                            own frame time).  A thin lens of radius a in scene units has strength a * (h / 2) * |W| / |V|.
+ *   fovpt_focus_buffers      addresses of the context's own focused outputs (allocated for the last frame if not yet).
+ *   fovpt_focus_state        synchronises fovpt_stream() and copies the state record out; zeros before any AUTO step.  The struct
+ *                            and the function share their name, so the struct has no typedef: write `struct fovpt_focus_state`.
+ *   fovpt_focus_reset        the next AUTO step is a first step.  Enqueued on fovpt_stream().
+ * Out of scope.  Bokeh shapes; partial occlusion (what a blurred foreground hides stays hidden); per-level radii; the periphery's
+ * block copies are blurred as the pixels they are.
+ * On an MI355X at 1920 x 1080 with a caller's G-buffer a call takes 0.049 ms where every tile is a copy (strength 0; 2.6 times
+ * fovpt_expose FIXED, a plain full-frame pass: 0.019 ms), 0.153 ms with the defaults' cap of 6 on the atrium (mean radius 3.9 pixels;
+ * with its own trace 0.355 ms) and 0.306 ms with every pixel at max_radius 8, the worst case (one fovpt_render of that frame:
+ * 0.516 ms); the AUTO meter alone 0.004 ms at meter_radius 12 and 0.017 ms at 64.                        */
+#define FOVPT_FOCUS_FIXED 0          /* focus at cfg.focus_distance; nothing is metered, the state is untouched */
+#define FOVPT_FOCUS_AUTO  1
+#define FOVPT_FOCUS_MAX_RADIUS 8         /* blur radius cap, pixels */
+#define FOVPT_FOCUS_MAX_METER_RADIUS 64  /* gaze disc, pixels */
+#define FOVPT_FOCUS_BINS 256
+typedef struct fovpt_focus_config {  /* 64 bytes */
+    int32_t mode, meter_radius, rank_permille, max_radius;
+    float strength;            /* pixels of blur radius per unit of |1/t - 1/focus| (scene units); 0 = off */
+    float focus_distance;      /* FIXED */
+    float focus_default;       /* AUTO, first step with nothing to meter */
+    float adapt_nearer, adapt_farther;   /* share of the way per step, in 1/distance, (0, 1] */
+    int32_t _reserved[7];
+} fovpt_focus_config;
+struct fovpt_focus_state {     /* 32 bytes */
+    float focus_metered, inv_focus, focus, _pad;
+    uint64_t count;            /* T of the last metered step */
+    uint64_t steps;            /* AUTO steps since create / reset */
+};
+int fovpt_focus_defaults(fovpt_focus_config* out);
+int fovpt_focus(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_focus_config* fc,
+                const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, const fovpt_float4* in_color /* NULL: accum_buffer */,
+                fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */, float* out_coc /* may be NULL */);
+int fovpt_focus_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+int fovpt_focus_state(fovpt_ctx* ctx, struct fovpt_focus_state* out);   /* synchronises fovpt_stream() */
+int fovpt_focus_reset(fovpt_ctx* ctx);                                  /* enqueued */
+
 /* ---- foveated frame packets: a frame off the device, small and without stopping the renderer -----------------------------------
  * New with this library.  fovpt_download drains every stream and copies a whole frame into pageable memory.  A foveated frame
  * is described exactly by one value per launch index -- at the shipped radii 74 / 241 a 1920 x 1080 frame has 211 149 of them,
@@ -1218,7 +1312,8 @@ int fovpt_debug_generate(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fo
  * hit records of the last G-buffer trace (fovpt_gbuffer, fovpt_reconstruct, a temporal step): float4 (t, u, v, record offset
  * as bits, 0xffffffff on a miss) per pixel --, "expose_histogram" -- fovpt_expose's last metered histogram, FOVPT_EXPOSE_BINS
  * uint64_t --, "expose_state" -- its device state record: a struct fovpt_expose_state --, "warp_keys" -- fovpt_warp's key
- * buffer, once made: the keys of the last warp in its first width * height uint64_t --, ...)                                   */
+ * buffer, once made: the keys of the last warp in its first width * height uint64_t --, "focus_state" -- fovpt_focus's device
+ * state record: a struct fovpt_focus_state --, "focus_scratch" -- its (r, tp) pairs, float2 per pixel, once made --, ...)       */
 int fovpt_debug_buffer(fovpt_ctx* ctx, const char* name, void** ptr, size_t* bytes);
 
 #ifdef __cplusplus
@@ -1241,6 +1336,9 @@ static_assert(sizeof(struct fovpt_expose_state) == 32 && offsetof(struct fovpt_e
 static_assert(sizeof(fovpt_warp_camera) == 48 && offsetof(fovpt_warp_camera, W) == 36, "warp camera ABI");
 static_assert(sizeof(fovpt_warp_config) == 32 && offsetof(fovpt_warp_config, fill_radius) == 4, "warp config ABI");
 static_assert(sizeof(struct fovpt_warp_counts) == 32 && offsetof(struct fovpt_warp_counts, direct) == 8, "warp counts ABI");
+static_assert(sizeof(fovpt_focus_config) == 64 && offsetof(fovpt_focus_config, strength) == 16 && offsetof(fovpt_focus_config, _reserved) == 36,
+              "focus config ABI");
+static_assert(sizeof(struct fovpt_focus_state) == 32 && offsetof(struct fovpt_focus_state, count) == 16, "focus state ABI");
 static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");
 static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header, width) == 16 && offsetof(fovpt_packet_header, pass) == 32,
               "packet header ABI");
