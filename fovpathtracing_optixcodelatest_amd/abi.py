@@ -231,6 +231,41 @@ class MorphPose(C.Structure):
                 ("_reserved", C.c_uint32), ("matrices", C.c_void_p)]
 
 
+RIG_MAX_NODES, RIG_MAX_CLIPS, RIG_MAX_KEYS = 1024, 64, 1 << 20           # FOVPT_RIG_MAX_NODES / _CLIPS / _KEYS
+RIG_TRANSLATION, RIG_ROTATION, RIG_SCALE, RIG_WEIGHTS = 0, 1, 2, 3        # FOVPT_RIG_TRANSLATION ..: a channel's path
+RIG_STEP, RIG_LINEAR = 0, 1                                               # FOVPT_RIG_STEP / _LINEAR: its interpolation
+
+
+class RigNode(C.Structure):
+    """fovpt_rig_node: a node's parent (-1: a root; otherwise below its own index) and rest pose, rotation as x y z w."""
+    _fields_ = [("parent", C.c_int32), ("translation", C.c_float * 3), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
+
+
+class RigBinding(C.Structure):
+    """fovpt_rig_binding: one mesh the rig drives: rigidly by a node, through its skin by joint nodes and inverse bind matrices,
+    or (node -1, no joints) by morph weights alone."""
+    _fields_ = [("mesh", C.c_int32), ("node", C.c_int32), ("num_joints", C.c_uint32), ("_reserved", C.c_uint32),
+                ("joint_nodes", C.c_void_p), ("inverse_bind", C.c_void_p)]
+
+
+class RigChannel(C.Structure):
+    """fovpt_rig_channel: the keys of one path of one node (WEIGHTS: of one mesh)."""
+    _fields_ = [("target", C.c_int32), ("path", C.c_int32), ("interpolation", C.c_int32), ("num_keys", C.c_uint32),
+                ("times", C.c_void_p), ("values", C.c_void_p)]
+
+
+class RigClip(C.Structure):
+    """fovpt_rig_clip: the channels of one clip."""
+    _fields_ = [("num_channels", C.c_uint32), ("_reserved", C.c_uint32), ("channels", C.POINTER(RigChannel))]
+
+
+class RigDesc(C.Structure):
+    """fovpt_rig_desc: nodes, bindings and clips (fovpt_set_rig)."""
+    _fields_ = [("nodes", C.POINTER(RigNode)), ("num_nodes", C.c_uint32), ("_reserved0", C.c_uint32),
+                ("bindings", C.POINTER(RigBinding)), ("num_bindings", C.c_uint32), ("_reserved1", C.c_uint32),
+                ("clips", C.POINTER(RigClip)), ("num_clips", C.c_uint32), ("_reserved2", C.c_uint32)]
+
+
 class TextureDesc(C.Structure):
     _fields_ = [("pixel", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -512,6 +547,7 @@ assert C.sizeof(MeshSkin) == 32 and (MeshSkin.joints.offset, MeshSkin.weights.of
 assert C.sizeof(SkinPose) == 16 and SkinPose.matrices.offset == 8
 assert C.sizeof(MorphTarget) == 24 and (MorphTarget.index.offset, MorphTarget.delta.offset) == (8, 16)
 assert C.sizeof(MeshMorph) == 24 and MeshMorph.targets.offset == 16
+assert C.sizeof(RigNode) == 44 and C.sizeof(RigBinding) == 32 and C.sizeof(RigChannel) == 32 and C.sizeof(RigClip) == 16 and C.sizeof(RigDesc) == 48
 assert C.sizeof(MorphPose) == 32 and (MorphPose.weights.offset, MorphPose.num_joints.offset, MorphPose.matrices.offset) == (8, 16, 24)
 assert LaunchParams.camera.offset == 104 and LaunchParams.traversable.offset == 160
 assert LaunchParams.probe.offset == 168 and LaunchParams.viewportSize.offset == 232

@@ -1,5 +1,6 @@
 // api_animate.hip -- animated geometry over the C ABI (include/fovpt.h; kernels: refit.hip): fovpt_update_vertices,
-// fovpt_update_transforms, fovpt_set_skins / fovpt_update_skinned, fovpt_set_morphs / fovpt_update_morphed.
+// fovpt_update_transforms, fovpt_set_skins / fovpt_update_skinned, fovpt_set_morphs / fovpt_update_morphed, fovpt_set_rig /
+// fovpt_update_animated (kernel: rig.hip).
 //
 // Every entry point validates all of its arguments first (all or nothing; Listed is the part they share).  An update is then
 // three steps on fovpt_stream(), the stream every job's resolve, and so every job's last traversal launch, is ordered on:
@@ -14,7 +15,7 @@
 
 namespace {
 
-// What the six entry points check first, in this order: open() the context, the scene, the count and the array (`what`: the
+// What the entry points check first, in this order: open() the context, the scene, the count and the array (`what`: the
 // caller's word for its entries) and the flags (flag_text: the caller's wording); then mesh(), entry by entry between the
 // caller's own checks, that the mesh exists and is not listed twice (check(); mesh() also adds it to `meshes`, the list an update
 // goes on with).
@@ -231,7 +232,7 @@ int finish_update(fovpt_ctx* c, bool rebuild)
     return measure_built(c);
 }
 
-// What the four update calls do once everything is validated
+// What the update calls do once everything is validated
 template <class Write> int update(const Listed& L, bool rebuild, bool from_rest, Write write)
 {
     CHK(check_updatable(L.c, L.who));
@@ -241,7 +242,7 @@ template <class Write> int update(const Listed& L, bool rebuild, bool from_rest,
     return finish_update(L.c, rebuild);
 }
 
-// ---- the five sources: validated entries to new positions in up_vtx -------------------------------------------------------
+// ---- the six sources: validated entries to new positions in up_vtx -------------------------------------------------------
 // host arrays: through the staging buffer, one copy per mesh
 int write_host(fovpt_ctx* c, const fovpt_vertex_update* up, int num, size_t floats)
 {
@@ -343,13 +344,84 @@ int write_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, bool dev
     return FOVPT_OK;
 }
 
+// a rig's clip at a time: k_rig_pose leaves the palettes in skin_pal, the weights in morph_w and the rigid matrices in the rig's
+// own array, all on this stream; then every bound mesh through the batch of its kind, reading those places
+int write_animated(fovpt_ctx* c, int clip, float time)
+{
+    const fovpt_ctx::Rig& R = c->rig;
+    const hipStream_t st = c->shadow_stream;
+    RigDev d = R.dev;
+    d.node_chan += 3 * (size_t)d.num_nodes * (size_t)clip;
+    d.w_chan += (size_t)d.num_wjobs * (size_t)clip;
+    d.skin_pal = (float*)c->skin_pal.p;
+    d.morph_w = (float*)c->morph_w.p;
+    fovpt_launch_rig_pose(st, d, time, R.threads);
+    const float* rest = (const float*)c->rest_vtx.p;
+    const uint32_t* off = (const uint32_t*)c->morph_off.p;
+    const MorphEntry* ent = (const MorphEntry*)c->morph_ent.p;
+    const uint2* joints = (const uint2*)c->skin_joints.p;
+    const float4* weights = (const float4*)c->skin_weights.p;
+    float* vtx = (float*)c->up_vtx.p;
+    auto rigid = batch_of<VertexTransformDev>([&](const VertexTransformDev& g) { fovpt_launch_transform_vertices_dev(st, g, rest, vtx); });
+    auto skinned = batch_of<VertexSkin>([&](const VertexSkin& g) { fovpt_launch_skin_vertices(st, g, rest, joints, weights, vtx); });
+    auto morphed = batch_of<VertexMorph>([&](const VertexMorph& g) { fovpt_launch_morph_vertices(st, g, rest, off, ent, vtx); });
+    auto both = batch_of<VertexMorph>([&](const VertexMorph& g) { fovpt_launch_morph_skin_vertices(st, g, rest, off, ent, joints, weights, vtx); });
+    for (const fovpt_ctx::RigBound& B : R.bound) {
+        const uint32_t n = c->mesh_nv[B.mesh], first = c->mesh_vbase[B.mesh];
+        if (B.is_rigid) rigid.add(n, [&](VertexTransformDev& g, int i) { g.m[i] = d.rigid + 12 * (size_t)B.rigid; g.first[i] = first; });
+        else if (!B.morphed)
+            skinned.add(n, [&](VertexSkin& g, int i) {
+                g.pal[i] = d.skin_pal + 12 * (size_t)c->skins[B.mesh].pal_first; g.first[i] = first; g.skin[i] = c->skins[B.mesh].first;
+            });
+        else {
+            auto fill = [&](VertexMorph& g, int i) {
+                const fovpt_ctx::Morph& M = c->morphs[B.mesh];
+                g.w[i] = d.morph_w + M.w_first; g.first[i] = first; g.off[i] = M.off_first;
+                if (!B.skinned) return;
+                g.pal[i] = d.skin_pal + 12 * (size_t)c->skins[B.mesh].pal_first; g.skin[i] = c->skins[B.mesh].first;
+            };
+            if (B.skinned) both.add(n, fill); else morphed.add(n, fill);
+        }
+    }
+    rigid.flush(); skinned.flush(); morphed.flush(); both.flush();
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// the rig goes (the caller has seen to it that nothing on the device still reads it)
+void drop_rig(fovpt_ctx* c)
+{
+    c->rig.set = false;
+    c->rig.num_clips = 0;
+    c->rig.bound.clear();
+    c->rig.in.release(); c->rig.out.release();
+    c->rig.dev = RigDev{};
+}
+
+// the squared norm of a quaternion in binary64, as fovpt_set_rig's rule reads it
+bool rig_norm_ok(const float* q)
+{
+    const double n2 = (((double)q[0] * (double)q[0] + (double)q[1] * (double)q[1]) + (double)q[2] * (double)q[2]) + (double)q[3] * (double)q[3];
+    return n2 >= 0.25 && n2 <= 4.0;
+}
+
+// one section of the rig's device allocation: appended to `blob` at a 16-byte boundary, its offset returned
+template <class T> size_t rig_place(std::vector<char>& blob, const std::vector<T>& v)
+{
+    const size_t at = (blob.size() + 15) & ~(size_t)15;
+    blob.resize(at + sizeof(T) * v.size());
+    if (!v.empty()) memcpy(blob.data() + at, v.data(), sizeof(T) * v.size());
+    return at;
+}
+
 }  // namespace
 
 // What the calls of this file keep of a scene, dropped with it (fovpt_set_scene and the context's destructor; the device is
 // idle): the device copies an update makes and the refit it may have left for the next job to wait for, fovpt_temporal_motion's
-// tracking (switched on again by its next call), the rest positions and their bounds, the skins and the morph targets.
+// tracking (switched on again by its next call), the rest positions and their bounds, the skins, the morph targets and the rig.
 void drop_animation(fovpt_ctx* c)
 {
+    drop_rig(c);
     c->up_vtx.release(); c->up_vidx.release();
     c->refit_pending = false;
     c->tm_tracking = c->tm_untracked = false;
@@ -452,6 +524,7 @@ int fovpt_set_skins(fovpt_ctx* c, const fovpt_mesh_skin* skins, int num)
         HIPCHK(c, d_pal.reserve(joints * 48));
     }
     HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_skinned in flight reads the buffers about to go
+    drop_rig(c);                                           // its joint counts were checked against the skins about to change
     if (c->skins.empty()) c->skins.resize((size_t)nmesh);
     for (int k = 0; k < num; k++) {
         const fovpt_mesh_skin& K = skins[k];
@@ -585,6 +658,7 @@ int fovpt_set_morphs(fovpt_ctx* c, const fovpt_mesh_morph* morphs, int num)
         HIPCHK(c, d_w.reserve(targets * 4));
     }
     HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_morphed in flight reads the buffers about to go
+    drop_rig(c);                                           // its target counts were checked against the morphs about to change
     if (c->morphs.empty()) c->morphs.resize((size_t)nmesh);
     for (int k = 0; k < num; k++) c->morphs[morphs[k].mesh] = std::move(fresh[k]);
     uint32_t off_first = 0, ent_first = 0, w_first = 0;
@@ -639,6 +713,190 @@ int fovpt_update_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, i
         if (K) CHK(check_palette(c, who, P.mesh, P.matrices, P.num_joints, K->S, B));
     }
     return update(L, rebuild, poses != nullptr, [&] { return write_morphed(c, poses, num, device, floats); });
+}
+
+// Validated in the order of the description: the counts, the nodes, the bindings, then clip by clip the channels.  Then the
+// device copy is laid out and uploaded whole before the previous rig goes.
+int fovpt_set_rig(fovpt_ctx* c, const fovpt_rig_desc* rig)
+{
+    const char* who = "fovpt_set_rig";
+    if (!c) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    if (!rig) {
+        if (!c->rig.set) return FOVPT_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_animated in flight reads the buffers about to go
+        drop_rig(c);
+        return FOVPT_OK;
+    }
+    const int nmesh = (int)c->mesh_nv.size();
+    const uint32_t nn = rig->num_nodes;
+    if (rig->_reserved0 || rig->_reserved1 || rig->_reserved2) return fail(c, FOVPT_E_INVALID, "%s: a reserved field is not 0", who);
+    if (nn == 0 || nn > FOVPT_RIG_MAX_NODES) return fail(c, FOVPT_E_INVALID, "%s: %u nodes (1 .. %d)", who, nn, FOVPT_RIG_MAX_NODES);
+    if (rig->num_clips > FOVPT_RIG_MAX_CLIPS) return fail(c, FOVPT_E_INVALID, "%s: %u clips (at most %d)", who, rig->num_clips, FOVPT_RIG_MAX_CLIPS);
+    if (rig->num_bindings > (uint32_t)nmesh) return fail(c, FOVPT_E_INVALID, "%s: %u bindings for %d meshes", who, rig->num_bindings, nmesh);
+    if (!rig->nodes || (rig->num_bindings && !rig->bindings) || (rig->num_clips && !rig->clips))
+        return fail(c, FOVPT_E_INVALID, "%s: a null array with a count above 0", who);
+    // nodes
+    std::vector<int32_t> parent(nn);
+    std::vector<uint32_t> level(nn);
+    std::vector<float> rest(10 * (size_t)nn);
+    uint32_t num_levels = 0;
+    for (uint32_t i = 0; i < nn; i++) {
+        const fovpt_rig_node& N = rig->nodes[i];
+        if (N.parent < -1 || N.parent >= (int32_t)i) return fail(c, FOVPT_E_INVALID, "%s: node %u: parent %d (-1, or below the node's own index)", who, i, N.parent);
+        float* r = rest.data() + 10 * (size_t)i;
+        memcpy(r, N.translation, 12); memcpy(r + 3, N.rotation, 16); memcpy(r + 7, N.scale, 12);
+        for (int e = 0; e < 10; e++)
+            if (!std::isfinite(r[e])) return fail(c, FOVPT_E_INVALID, "%s: node %u: a rest value is not finite", who, i);
+        if (!rig_norm_ok(N.rotation)) return fail(c, FOVPT_E_INVALID, "%s: node %u: the rest rotation's squared norm is outside [1/4, 4]", who, i);
+        parent[i] = N.parent;
+        level[i] = N.parent < 0 ? 0u : level[N.parent] + 1u;
+        num_levels = level[i] + 1 > num_levels ? level[i] + 1 : num_levels;
+    }
+    // bindings
+    std::vector<fovpt_ctx::RigBound> bound;
+    std::vector<int> bound_at((size_t)nmesh, -1);           // per mesh its RigWeights, -2: bound without morphs, -1: not bound
+    std::vector<uint32_t> pal_node, pal_dst, rigid_node;
+    std::vector<float> inv_bind;
+    std::vector<RigWeights> wjobs;
+    for (uint32_t k = 0; k < rig->num_bindings; k++) {
+        const fovpt_rig_binding& B = rig->bindings[k];
+        if (B.mesh < 0 || B.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "%s: binding %u: mesh %d of %d", who, k, B.mesh, nmesh);
+        if (bound_at[B.mesh] != -1) return fail(c, FOVPT_E_INVALID, "%s: binding %u: mesh %d is bound twice", who, k, B.mesh);
+        if (B._reserved) return fail(c, FOVPT_E_INVALID, "%s: binding %u: _reserved is %u", who, k, B._reserved);
+        if (B.node < -1 || B.node >= (int32_t)nn) return fail(c, FOVPT_E_INVALID, "%s: binding %u: node %d of %u", who, k, B.node, nn);
+        if (B.node >= 0 && B.num_joints) return fail(c, FOVPT_E_INVALID, "%s: binding %u: both a node and joints", who, k);
+        const uint32_t skin_joints = c->skins.empty() ? 0u : c->skins[B.mesh].num_joints;
+        const uint32_t targets = c->morphs.empty() ? 0u : c->morphs[B.mesh].num_targets;
+        if (B.num_joints && B.num_joints != skin_joints)
+            return fail(c, FOVPT_E_INVALID, "%s: binding %u: %u joints, the skin of mesh %d has %u", who, k, B.num_joints, B.mesh, skin_joints);
+        if (B.node >= 0 && targets) return fail(c, FOVPT_E_INVALID, "%s: binding %u: a rigid binding of mesh %d, which has morphs", who, k, B.mesh);
+        if (B.node < 0 && !B.num_joints && !targets) return fail(c, FOVPT_E_INVALID, "%s: binding %u: neither a node, joints nor morphs on mesh %d", who, k, B.mesh);
+        if (B.num_joints && (!B.joint_nodes || !B.inverse_bind)) return fail(c, FOVPT_E_INVALID, "%s: binding %u: null joint_nodes or inverse_bind", who, k);
+        for (uint32_t j = 0; j < B.num_joints; j++) {
+            if (B.joint_nodes[j] >= nn) return fail(c, FOVPT_E_INVALID, "%s: binding %u joint %u: node %u of %u", who, k, j, (unsigned)B.joint_nodes[j], nn);
+            for (int e = 0; e < 12; e++)
+                if (!std::isfinite(B.inverse_bind[12 * (size_t)j + e])) return fail(c, FOVPT_E_INVALID, "%s: binding %u joint %u: an inverse bind entry is not finite", who, k, j);
+            pal_node.push_back(B.joint_nodes[j]);
+            pal_dst.push_back(c->skins[B.mesh].pal_first + j);
+        }
+        inv_bind.insert(inv_bind.end(), B.inverse_bind, B.inverse_bind + (B.num_joints ? 12 * (size_t)B.num_joints : 0));
+        fovpt_ctx::RigBound D{B.mesh, 0u, B.num_joints != 0, targets != 0, B.node >= 0};
+        if (D.is_rigid) { D.rigid = (uint32_t)rigid_node.size(); rigid_node.push_back((uint32_t)B.node); }
+        bound_at[B.mesh] = targets ? (int)wjobs.size() : -2;
+        if (targets) wjobs.push_back(RigWeights{c->morphs[B.mesh].w_first, targets});
+        bound.push_back(D);
+    }
+    // clips
+    std::vector<int32_t> node_chan(3 * (size_t)nn * rig->num_clips, -1), w_chan(wjobs.size() * (size_t)rig->num_clips, -1);
+    std::vector<RigChannel> chan;
+    size_t num_times = 0, num_values = 0;
+    for (uint32_t k = 0; k < rig->num_clips; k++) {
+        const fovpt_rig_clip& K = rig->clips[k];
+        if (K._reserved) return fail(c, FOVPT_E_INVALID, "%s: clip %u: _reserved is %u", who, k, K._reserved);
+        if (K.num_channels && !K.channels) return fail(c, FOVPT_E_INVALID, "%s: clip %u: null channels", who, k);
+        if (K.num_channels > 3 * (size_t)nn + (size_t)nmesh) return fail(c, FOVPT_E_INVALID, "%s: clip %u: %u channels name a (target, path) twice", who, k, K.num_channels);
+        int32_t* nc = node_chan.data() + 3 * (size_t)nn * k;
+        int32_t* wc = w_chan.data() + wjobs.size() * (size_t)k;
+        std::vector<char> weights_seen((size_t)nmesh, 0);
+        for (uint32_t h = 0; h < K.num_channels; h++) {
+            const fovpt_rig_channel& H = K.channels[h];
+            if (H.path < FOVPT_RIG_TRANSLATION || H.path > FOVPT_RIG_WEIGHTS) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: path %d", who, k, h, H.path);
+            if (H.interpolation != FOVPT_RIG_STEP && H.interpolation != FOVPT_RIG_LINEAR)
+                return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: interpolation %d", who, k, h, H.interpolation);
+            size_t width;
+            int32_t* slot;
+            if (H.path == FOVPT_RIG_WEIGHTS) {
+                if (H.target < 0 || H.target >= nmesh) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: mesh %d of %d", who, k, h, H.target, nmesh);
+                if (bound_at[H.target] < 0) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: mesh %d is not bound or has no morphs", who, k, h, H.target);
+                if (weights_seen[H.target]) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: the weights of mesh %d twice", who, k, h, H.target);
+                weights_seen[H.target] = 1;
+                slot = wc + bound_at[H.target];
+                width = wjobs[bound_at[H.target]].num_targets;
+            } else {
+                if (H.target < 0 || H.target >= (int32_t)nn) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: node %d of %u", who, k, h, H.target, nn);
+                slot = nc + 3 * (size_t)H.target + H.path;
+                if (*slot >= 0) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: node %d path %d twice", who, k, h, H.target, H.path);
+                width = H.path == FOVPT_RIG_ROTATION ? 4 : 3;
+            }
+            if (H.num_keys < 1 || H.num_keys > FOVPT_RIG_MAX_KEYS) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: %u keys (1 .. %u)", who, k, h, H.num_keys, FOVPT_RIG_MAX_KEYS);
+            if (!H.times || !H.values) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: null times or values", who, k, h);
+            for (uint32_t i = 0; i < H.num_keys; i++) {
+                if (!std::isfinite(H.times[i])) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: time %u is not finite", who, k, h, i);
+                if (i && !(H.times[i] > H.times[i - 1])) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: times are not strictly ascending at key %u", who, k, h, i);
+            }
+            for (size_t i = 0; i < width * H.num_keys; i++)
+                if (!std::isfinite(H.values[i])) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: value %zu is not finite", who, k, h, i);
+            if (H.path == FOVPT_RIG_ROTATION)
+                for (uint32_t i = 0; i < H.num_keys; i++)
+                    if (!rig_norm_ok(H.values + 4 * (size_t)i)) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: key %u's squared norm is outside [1/4, 4]", who, k, h, i);
+            *slot = (int32_t)chan.size();
+            chan.push_back(RigChannel{(uint32_t)num_times, (uint32_t)num_values, H.num_keys, (uint32_t)H.interpolation});
+            num_times += H.num_keys; num_values += width * H.num_keys;
+            if (num_times >= (1ull << 32) || num_values >= (1ull << 32) || chan.size() >= (1ull << 31))
+                return fail(c, FOVPT_E_INVALID, "%s: more than 2^32 - 1 key times or values", who);
+        }
+    }
+    // the device copy: the keys in channel order, then one allocation
+    std::vector<float> times(num_times), values(num_values);
+    {
+        size_t h = 0;
+        for (uint32_t k = 0; k < rig->num_clips; k++)
+            for (uint32_t i = 0; i < rig->clips[k].num_channels; i++, h++) {
+                const fovpt_rig_channel& H = rig->clips[k].channels[i];
+                const size_t end = h + 1 < chan.size() ? chan[h + 1].v_first : num_values;
+                memcpy(times.data() + chan[h].t_first, H.times, 4 * (size_t)H.num_keys);
+                memcpy(values.data() + chan[h].v_first, H.values, 4 * (end - chan[h].v_first));
+            }
+    }
+    std::vector<char> blob;
+    const size_t o_parent = rig_place(blob, parent), o_level = rig_place(blob, level), o_rest = rig_place(blob, rest),
+                 o_nc = rig_place(blob, node_chan), o_wc = rig_place(blob, w_chan), o_chan = rig_place(blob, chan),
+                 o_times = rig_place(blob, times), o_values = rig_place(blob, values), o_pn = rig_place(blob, pal_node),
+                 o_pd = rig_place(blob, pal_dst), o_ib = rig_place(blob, inv_bind), o_rn = rig_place(blob, rigid_node),
+                 o_wj = rig_place(blob, wjobs);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf d_in, d_out;
+    const size_t outs = 12 * ((size_t)nn + rigid_node.size() + pal_node.size());
+    HIPCHK(c, d_in.reserve(blob.size() + 16));
+    HIPCHK(c, d_out.reserve(4 * outs));
+    HIPCHK(c, hipMemcpy(d_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_out.p, 0, 4 * outs));
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_animated in flight reads the buffers about to go
+    drop_rig(c);
+    fovpt_ctx::Rig& R = c->rig;
+    R.in.swap(d_in); R.out.swap(d_out);
+    R.bound.swap(bound);
+    R.num_clips = rig->num_clips;
+    const char* in = (const char*)R.in.p;
+    RigDev& D = R.dev;
+    D.num_nodes = nn; D.num_levels = num_levels; D.num_pal = (uint32_t)pal_node.size(); D.num_rigid = (uint32_t)rigid_node.size();
+    D.num_wjobs = (uint32_t)wjobs.size();
+    D.parent = (const int32_t*)(in + o_parent); D.level = (const uint32_t*)(in + o_level); D.rest = (const float*)(in + o_rest);
+    D.node_chan = (const int32_t*)(in + o_nc); D.w_chan = (const int32_t*)(in + o_wc); D.chan = (const RigChannel*)(in + o_chan);
+    D.times = (const float*)(in + o_times); D.values = (const float*)(in + o_values);
+    D.pal_node = (const uint32_t*)(in + o_pn); D.pal_dst = (const uint32_t*)(in + o_pd); D.inv_bind = (const float*)(in + o_ib);
+    D.rigid_node = (const uint32_t*)(in + o_rn); D.wjobs = (const RigWeights*)(in + o_wj);
+    D.world = (float*)R.out.p; D.rigid = D.world + 12 * (size_t)nn; D.palette = D.rigid + 12 * rigid_node.size();
+    size_t most = nn > D.num_pal ? nn : D.num_pal;
+    for (const RigWeights& w : wjobs) most = w.num_targets > most ? w.num_targets : most;
+    R.threads = (uint32_t)(most >= FOVPT_RIG_MAX_NODES ? FOVPT_RIG_MAX_NODES : (most + 63) / 64 * 64);
+    R.set = true;
+    return FOVPT_OK;
+}
+
+// The composed matrices are made on the device and not validated, as FOVPT_UPDATE_DEVICE pointers are not.
+int fovpt_update_animated(fovpt_ctx* c, int clip, float time, int flags)
+{
+    const char* who = "fovpt_update_animated";
+    Listed L;
+    CHK(L.open(c, who, 0, nullptr, "clips", flags, FOVPT_UPDATE_REBUILD, "%s: flag bits %d (FOVPT_UPDATE_REBUILD is the only one accepted)"));
+    if (!c->rig.set) return fail(c, FOVPT_E_INVALID, "%s: no rig (fovpt_set_rig; fovpt_set_skins, fovpt_set_morphs and fovpt_set_scene drop it)", who);
+    if (clip < 0 || (uint32_t)clip >= c->rig.num_clips) return fail(c, FOVPT_E_INVALID, "%s: clip %d of %u", who, clip, c->rig.num_clips);
+    if (!std::isfinite(time)) return fail(c, FOVPT_E_INVALID, "%s: the time is not finite", who);
+    for (const fovpt_ctx::RigBound& B : c->rig.bound) CHK(L.mesh(B.mesh));
+    return update(L, (flags & FOVPT_UPDATE_REBUILD) != 0, true, [&] { return write_animated(c, clip, time); });
 }
 
 }  // extern "C"

@@ -1190,6 +1190,9 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "bvh_tris") == 0 && c->has_scene) { *ptr = c->tris; *bytes = (size_t)c->stats.tri_bytes; return FOVPT_OK; }
     if (strcmp(name, "scene_vertices") == 0 && c->up_vtx.p) { *ptr = c->up_vtx.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_update_vertices
     if (strcmp(name, "scene_vertices_prev") == 0 && c->vtx_prev.p) { *ptr = c->vtx_prev.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_temporal_motion
+    if (strcmp(name, "rig_world") == 0 && c->rig.set) { *ptr = c->rig.dev.world; *bytes = 48 * (size_t)c->rig.dev.num_nodes; return FOVPT_OK; }   // what k_rig_pose last wrote
+    if (strcmp(name, "rig_rigid") == 0 && c->rig.set) { *ptr = c->rig.dev.rigid; *bytes = 48 * (size_t)c->rig.dev.num_rigid; return FOVPT_OK; }
+    if (strcmp(name, "rig_palette") == 0 && c->rig.set) { *ptr = c->rig.dev.palette; *bytes = 48 * (size_t)c->rig.dev.num_pal; return FOVPT_OK; }
     if (strcmp(name, "post_color") == 0 && c->po_color.p) { *ptr = c->po_color.p; *bytes = c->po_color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
     if (strcmp(name, "expose_histogram") == 0 && c->ex_hist.p) { *ptr = c->ex_hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
     if (strcmp(name, "expose_state") == 0 && c->ex_state.p) { *ptr = c->ex_state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }

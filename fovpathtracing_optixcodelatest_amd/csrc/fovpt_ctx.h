@@ -112,6 +112,21 @@ struct fovpt_ctx {
     struct Morph { uint32_t num_targets = 0, off_first = 0, ent_first = 0, w_first = 0; std::vector<double> D; std::vector<uint32_t> off; std::vector<MorphEntry> ent; };
     std::vector<Morph> morphs;
     DevBuf morph_off, morph_ent, morph_w;
+    // fovpt_set_rig / fovpt_update_animated.  rig.set: a rig is there (made by fovpt_set_rig; dropped by a later fovpt_set_skins,
+    // fovpt_set_morphs, fovpt_set_scene or fovpt_set_rig(NULL)).  bound: the bindings in their order, each with what its mesh goes
+    // through and its place among the rigid matrices.  in: everything k_rig_pose reads, one allocation (the nodes' parents,
+    // levels and rest poses, per clip the nodes' channel table and the weights' channels, the channels, key times and key values,
+    // and per palette entry its node, its place in skin_pal and its inverse bind matrix); out: what it writes beside skin_pal and
+    // morph_w (the worlds, the rigid matrices and the palettes in binding order: fovpt_debug_buffer "rig_world", "rig_rigid",
+    // "rig_palette").  dev: the kernel's arguments, node_chan / w_chan those of clip 0 (a clip's tables follow its predecessor's).
+    struct RigBound { int32_t mesh; uint32_t rigid; bool skinned, morphed, is_rigid; };
+    struct Rig {
+        bool set = false;
+        uint32_t num_clips = 0, threads = 64;
+        std::vector<RigBound> bound;
+        DevBuf in, out;
+        RigDev dev{};
+    } rig;
     // fovpt_hierarchy_cost.  cost_built / cost_current / cost_updates / cost_measured: the caller's record.  cost_partial: the
     // block sums of k_tree_cost, sized when a hierarchy is adopted.  cost_slot: result records in pinned host memory the final
     // kernel writes, each with the event recorded behind it and the update number it measures; a slot is free once its event has

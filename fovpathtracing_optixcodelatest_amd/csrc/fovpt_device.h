@@ -377,6 +377,43 @@ struct VertexTransform {
     uint32_t max_n;
 };
 void fovpt_launch_transform_vertices(hipStream_t st, const VertexTransform& g, const float* rest, float* vtx);
+// fovpt_update_animated's rigid bindings: VertexTransform with the matrices in device memory (k_rig_pose wrote them)
+struct VertexTransformDev {
+    const float* m[FOVPT_GATHER_BATCH]; // 12 floats each
+    uint32_t first[FOVPT_GATHER_BATCH]; // first vertex in rest and vtx
+    uint32_t n[FOVPT_GATHER_BATCH];     // vertices
+    int32_t count;
+    uint32_t max_n;
+};
+void fovpt_launch_transform_vertices_dev(hipStream_t st, const VertexTransformDev& g, const float* rest, float* vtx);
+// fovpt_update_animated (rig.hip): one clip of a rig sampled at `time`, the nodes' world matrices composed level by level, and from
+// them the palettes of the bound skinned meshes (into their places in skin_pal), the matrices of the rigid bindings and the
+// weights of the bound morphed meshes (into their places in morph_w).  One workgroup of `threads` (a multiple of 64, at least
+// num_nodes, at most FOVPT_RIG_MAX_NODES).  The definition is include/fovpt.h's, operation by operation.
+struct RigChannel { uint32_t t_first, v_first, num_keys, interp; };      // its keys' places in times / values
+struct RigWeights { uint32_t w_first, num_targets; };                   // a bound morphed mesh's place in morph_w
+struct RigDev {
+    uint32_t num_nodes, num_levels, num_pal, num_rigid, num_wjobs;
+    const int32_t* parent;          // per node
+    const uint32_t* level;          // per node: 0 for a root, its parent's + 1 otherwise
+    const float* rest;              // per node 10 floats: translation, rotation, scale
+    const int32_t* node_chan;       // the clip's: per node the channels of its translation, rotation and scale (-1: rest)
+    const int32_t* w_chan;          // the clip's: per RigWeights its channel (-1: zeros)
+    const RigChannel* chan;
+    const float* times;
+    const float* values;
+    const uint32_t* pal_node;       // per palette entry (the joints of the bindings, in binding order) its node,
+    const uint32_t* pal_dst;        // its joint's place in skin_pal
+    const float* inv_bind;          // and its inverse bind matrix, 12 floats
+    const uint32_t* rigid_node;     // per rigid binding its node
+    const RigWeights* wjobs;
+    float* skin_pal;
+    float* morph_w;
+    float* world;                   // out: num_nodes x 12
+    float* rigid;                   // out: num_rigid x 12
+    float* palette;                 // out: num_pal x 12, what went to skin_pal, in binding order
+};
+void fovpt_launch_rig_pose(hipStream_t st, const RigDev& r, float time, uint32_t threads);
 // fovpt_update_skinned: up to FOVPT_GATHER_BATCH meshes, each the n vertices from `first` on of rest through the blend of its
 // four joints' matrices into vtx (M[e] = ((w0 J[j0][e] + w1 J[j1][e]) + w2 J[j2][e]) + w3 J[j3][e], then VertexTransform's
 // expression with M; unfused binary32).  Vertex i of mesh u has its four joint indices at joints[skin[u] + i] and its weights at

@@ -10,7 +10,7 @@
 // build's boxes bit for bit (without spatial splits: a split reference's clipped box becomes its whole triangle's box).
 //
 // Also here: fovpt_update_transforms' k_transform_vertices (rest positions through per-mesh 3 x 4 matrices into the vertex array,
-// ahead of the same refit), fovpt_update_skinned's k_skin_vertices (the same with a matrix blended per vertex from its mesh's joint
+// ahead of the same refit; k_transform_vertices_dev: the same for fovpt_update_animated's rigid bindings), fovpt_update_skinned's k_skin_vertices (the same with a matrix blended per vertex from its mesh's joint
 // palette), fovpt_update_morphed's k_morph_vertices / k_morph_skin_vertices (the rest positions plus their weighted morph deltas,
 // the second then through the skin) and fovpt_hierarchy_cost's k_tree_cost / k_tree_cost_final (the SAH cost of the nodes in
 // binary64).
@@ -60,6 +60,27 @@ __global__ void k_transform_vertices(VertexTransform g, const float* __restrict_
 {
     for (int u = blockIdx.y; u < g.count; u += gridDim.y) {
         const float* m = g.m[u];
+        const float* __restrict__ src = rest + 3 * (size_t)g.first[u];
+        float* __restrict__ dst = vtx + 3 * (size_t)g.first[u];
+        const size_t n = g.n[u];
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+            const float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+            dst[3 * i] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+            dst[3 * i + 1] = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+            dst[3 * i + 2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+        }
+    }
+}
+
+// fovpt_update_animated's rigid bindings: k_transform_vertices with each mesh's matrix read from device memory (k_rig_pose wrote
+// it earlier on the stream); the arithmetic is the same expression.
+__global__ void k_transform_vertices_dev(VertexTransformDev g, const float* __restrict__ rest, float* __restrict__ vtx)
+{
+    for (int u = blockIdx.y; u < g.count; u += gridDim.y) {
+        const float* __restrict__ gm = g.m[u];
+        float m[12];
+#pragma unroll
+        for (int e = 0; e < 12; e++) m[e] = gm[e];
         const float* __restrict__ src = rest + 3 * (size_t)g.first[u];
         float* __restrict__ dst = vtx + 3 * (size_t)g.first[u];
         const size_t n = g.n[u];
@@ -299,6 +320,14 @@ void fovpt_launch_transform_vertices(hipStream_t st, const VertexTransform& g, c
     const uint64_t n = g.max_n;
     const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
     hipLaunchKernelGGL(k_transform_vertices, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, vtx);
+}
+
+void fovpt_launch_transform_vertices_dev(hipStream_t st, const VertexTransformDev& g, const float* rest, float* vtx)
+{
+    if (g.count <= 0 || g.max_n == 0) return;
+    const uint64_t n = g.max_n;
+    const uint32_t gx = (uint32_t)(n < 1024ull * FOVPT_BLOCK ? (n + FOVPT_BLOCK - 1) / FOVPT_BLOCK : 1024ull);
+    hipLaunchKernelGGL(k_transform_vertices_dev, dim3(gx, (uint32_t)g.count), dim3(FOVPT_BLOCK), 0, st, g, rest, vtx);
 }
 
 void fovpt_launch_skin_vertices(hipStream_t st, const VertexSkin& g, const float* rest, const uint2* joints, const float4* weights, float* vtx)

@@ -24,7 +24,7 @@ EXPORTS = [
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
     "fovpt_temporal_defaults", "fovpt_temporal", "fovpt_temporal_motion", "fovpt_temporal_buffers", "fovpt_temporal_reset", "fovpt_update_vertices",
     "fovpt_update_transforms", "fovpt_hierarchy_cost", "fovpt_set_skins", "fovpt_update_skinned",
-    "fovpt_set_morphs", "fovpt_update_morphed",
+    "fovpt_set_morphs", "fovpt_update_morphed", "fovpt_set_rig", "fovpt_update_animated",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
     "fovpt_warp_defaults", "fovpt_warp", "fovpt_warp_buffers", "fovpt_warp_counts", "fovpt_temporal_gbuffer",
@@ -211,6 +211,8 @@ def load():
     L.fovpt_update_skinned.argtypes = [vp, C.POINTER(abi.SkinPose), i32, i32]
     L.fovpt_set_morphs.argtypes = [vp, C.POINTER(abi.MeshMorph), i32]
     L.fovpt_update_morphed.argtypes = [vp, C.POINTER(abi.MorphPose), i32, i32]
+    L.fovpt_set_rig.argtypes = [vp, C.POINTER(abi.RigDesc)]
+    L.fovpt_update_animated.argtypes = [vp, i32, C.c_float, i32]
     L.fovpt_comm_get_unique_id.argtypes = [vp]
     L.fovpt_comm_init.argtypes = [vp, vp, i32, i32]
     L.fovpt_comm_destroy.argtypes = [vp]

@@ -802,6 +802,81 @@ class SampleRenderer:
             ps[k].num_joints, ps[k].matrices = (0 if m is None else int(m.shape[0])), mp
         self._update(self._L.fovpt_update_morphed, ps, len(items), device, rebuild, keep)
 
+    # -- rigs (include/fovpt.h, fovpt_set_rig / fovpt_update_animated)
+    @staticmethod
+    def pack_rig(rig):
+        """(abi.RigDesc, what it points to) of a rig: a dict with parent (N,) integers, translation (N, 3), rotation (N, 4)
+        (x y z w) and scale (N, 3) float32, the nodes' parents and rest poses; bindings, a list of dicts with mesh and either
+        node (rigid), or joint_nodes (J,) and inverse_bind (J, 3, 4), or neither (morph weights only); clips, a list of lists of
+        channels, each a dict with target, path and interpolation (abi.RIG_*), times (K,) and values (K, 3 / 4 / 3 / targets).
+        Bad shapes raise ValueError; the values themselves are the library's to check."""
+        keep = []
+
+        def arr(a, dtype, shape, what):
+            a = np.ascontiguousarray(a, dtype)
+            if a.ndim != len(shape) or any(s is not None and s != d for s, d in zip(shape, a.shape)):
+                raise ValueError("set_rig: %s needs shape %s, not %s" % (what, shape, a.shape))
+            keep.append(a)
+            return a
+
+        parent = arr(rig["parent"], np.int32, (None,), "parent")
+        n = parent.shape[0]
+        t, q, s = arr(rig["translation"], np.float32, (n, 3), "translation"), arr(rig["rotation"], np.float32, (n, 4), "rotation"), \
+            arr(rig["scale"], np.float32, (n, 3), "scale")
+        nodes = (abi.RigNode * max(1, n))()
+        for i in range(n):
+            nodes[i].parent = int(parent[i])
+            nodes[i].translation[:], nodes[i].rotation[:], nodes[i].scale[:] = t[i].tolist(), q[i].tolist(), s[i].tolist()
+        bindings = list(rig.get("bindings", ()))
+        bs = (abi.RigBinding * max(1, len(bindings)))()
+        for k, b in enumerate(bindings):
+            bs[k].mesh, bs[k].node = int(b["mesh"]), int(b.get("node", -1))
+            if b.get("joint_nodes") is not None:
+                j = np.asarray(b["joint_nodes"])
+                if j.ndim != 1 or j.dtype.kind not in "ui" or (j.size and (j.min() < 0 or j.max() > 0xffff)):
+                    raise ValueError("set_rig: binding %d needs (J,) joint nodes that fit uint16" % k)
+                j = arr(j, np.uint16, (None,), "joint_nodes")
+                ib = SampleRenderer._host_palette("set_rig", int(b["mesh"]), b["inverse_bind"], "inverse bind palette")
+                if ib.shape[0] != j.shape[0]:
+                    raise ValueError("set_rig: binding %d needs one inverse bind matrix per joint node" % k)
+                keep.append(ib)
+                bs[k].num_joints, bs[k].joint_nodes, bs[k].inverse_bind = j.shape[0], j.ctypes.data, ib.ctypes.data
+        clips = list(rig.get("clips", ()))
+        cs = (abi.RigClip * max(1, len(clips)))()
+        for k, clip in enumerate(clips):
+            ch = (abi.RigChannel * max(1, len(clip)))()
+            for h, c in enumerate(clip):
+                times = arr(c["times"], np.float32, (None,), "clip %d channel %d: times" % (k, h))
+                values = arr(c["values"], np.float32, (times.shape[0], None), "clip %d channel %d: values" % (k, h))
+                width = {abi.RIG_TRANSLATION: 3, abi.RIG_ROTATION: 4, abi.RIG_SCALE: 3}.get(int(c["path"]))
+                if width is not None and values.shape[1] != width:
+                    raise ValueError("set_rig: clip %d channel %d needs (K, %d) values" % (k, h, width))
+                ch[h].target, ch[h].path, ch[h].interpolation, ch[h].num_keys = int(c["target"]), int(c["path"]), int(c["interpolation"]), times.shape[0]
+                ch[h].times, ch[h].values = times.ctypes.data, values.ctypes.data
+            keep.append(ch)
+            cs[k].num_channels, cs[k].channels = len(clip), ch
+        desc = abi.RigDesc()
+        desc.nodes, desc.num_nodes, desc.bindings, desc.num_bindings, desc.clips, desc.num_clips = nodes, n, bs, len(bindings), cs, len(clips)
+        keep += [nodes, bs, cs]
+        return desc, keep
+
+    def set_rig(self, rig):
+        """Sets, replaces or (None) removes the scene's rig: see pack_rig() for the form.  Called after set_skins() / set_morphs(),
+        either of which drops it.  Set-up-time state of the scene: copied before the call returns, geometry does not move."""
+        if rig is None:
+            self._check(self._L.fovpt_set_rig(self._ctx, None))
+            return
+        desc, keep = self.pack_rig(rig)
+        self._check(self._L.fovpt_set_rig(self._ctx, C.byref(desc)))
+        del keep
+
+    def update_animated(self, clip, time, rebuild=False):
+        """Poses every mesh the rig binds from clip `clip` at `time`: the keys are sampled, the hierarchy composed and the
+        palettes, weights and rigid matrices applied on the device; absolute, not cumulative; then update_vertices()' refit (or,
+        rebuild=True, rebuild) with the same ordering.  The caller wraps its own time to loop.  The renderer's Model is not
+        changed."""
+        self._check(self._L.fovpt_update_animated(self._ctx, int(clip), float(time), abi.UPDATE_REBUILD if rebuild else 0))
+
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""
         self.lastSetCamera = camera

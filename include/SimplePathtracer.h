@@ -411,6 +411,12 @@ public:
     {
         check(fovpt_update_morphed(ctx, poses.data(), (int)poses.size(), (rebuild ? FOVPT_UPDATE_REBUILD : 0) | (device ? FOVPT_UPDATE_DEVICE : 0)));
     }
+    // rigs: setRig uploads the node hierarchy, the bindings of meshes to it and the keyframe clips, once (after setSkins /
+    // setMorphs, either of which drops the rig; nullptr removes it); updateAnimated samples clip `clip` at `time`, composes the
+    // hierarchy and poses every bound mesh on the device, absolute not cumulative, then updateAccel()'s refit or rebuild
+    // (include/fovpt.h, fovpt_set_rig / fovpt_update_animated).  The caller wraps its own time to loop.  The Model is not changed.
+    void setRig(const fovpt_rig_desc* rig) { check(fovpt_set_rig(ctx, rig)); }
+    void updateAnimated(int clip, float time, bool rebuild = false) { check(fovpt_update_animated(ctx, clip, time, rebuild ? FOVPT_UPDATE_REBUILD : 0)); }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

@@ -429,6 +429,102 @@ typedef struct fovpt_morph_pose {
 } fovpt_morph_pose;              /* 32 bytes */
 int fovpt_update_morphed(fovpt_ctx* ctx, const fovpt_morph_pose* poses, int num, int flags);   /* FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD */
 
+/* ---- rigs: keyframe clips sampled and composed on the device ------------------------------------------------------------------
+ * fovpt_update_skinned / fovpt_update_morphed / fovpt_update_transforms without the caller's animation system: the node hierarchy,
+ * the bindings of meshes to it and the keyframe clips are uploaded once with fovpt_set_rig, and every frame carries one number,
+ * the time.  The layout maps onto glTF's nodes, skins and animation samplers one to one.
+ *   sample     a channel with keys t_0 < ... < t_{n-1} at time T: T <= t_0 gives v_0, T >= t_{n-1} gives v_{n-1}; otherwise
+ *              k is the largest index with t_k <= T.  FOVPT_RIG_STEP gives v_k.  FOVPT_RIG_LINEAR: u = (T - t_k) / (t_{k+1} - t_k)
+ *              and, for translation, scale and weights, v = v_k + u * (v_{k+1} - v_k) per component (at a key, u = 0: the key,
+ *              a component of -0 becoming +0).  For rotation, with a = v_k, b = v_{k+1}:
+ *                  d = ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w;   if d < 0: b = -b, d = -d
+ *                  d > 0.9995f:  q = a + u * (b - a)                                              per component
+ *                  otherwise:    th = fovpt_dm_acosf(d), s = fovpt_dm_sinf(th), wa = fovpt_dm_sinf((1.0f - u) * th) / s,
+ *                                wb = fovpt_dm_sinf(u * th) / s, q = wa * a + wb * b              per component
+ *                  then q = q / sqrtf(((x * x + y * y) + z * z) + w * w)                          per component
+ *              (include/fovpt_detmath.h: host and device agree bit for bit).  Every *, +, -, / and square root is one unfused
+ *              binary32 operation.  Values that were not interpolated -- rest values, STEP, either end of a clip -- are used as
+ *              given, NOT normalised (glTF's rule).  A path no channel of the clip names takes the node's rest value; a bound
+ *              morphed mesh without a WEIGHTS channel in the clip gets all-zero weights (rest, through the skin where skinned).
+ *   local      from (t, q = (x, y, z, w), s):  r00 = 1.0f - 2.0f * (y * y + z * z)   r01 = 2.0f * (x * y - z * w)   r02 = 2.0f * (x * z + y * w)
+ *                                              r10 = 2.0f * (x * y + z * w)   r11 = 1.0f - 2.0f * (x * x + z * z)   r12 = 2.0f * (y * z - x * w)
+ *                                              r20 = 2.0f * (x * z - y * w)   r21 = 2.0f * (y * z + x * w)   r22 = 1.0f - 2.0f * (x * x + y * y)
+ *              L[r][c] = r_rc * s[c], L[r][3] = t[r].
+ *   world      W = L for a root, otherwise W = P o L, P the parent's world:
+ *                  (P o L)[r][c] = (P[r][0] * L[0][c] + P[r][1] * L[1][c]) + P[r][2] * L[2][c]                   c < 3
+ *                  (P o L)[r][3] = ((P[r][0] * L[0][3] + P[r][1] * L[1][3]) + P[r][2] * L[2][3]) + P[r][3]
+ *   palette    J[j] = W[joint_nodes[j]] o inverse_bind[j], the same product; a rigid binding's matrix is M = W[node].
+ *   apply      a binding with joints goes through fovpt_update_skinned's expression with J (through fovpt_update_morphed's with the
+ *              sampled weights and J where the mesh has morphs), a binding without joints on a morphed mesh through
+ *              fovpt_update_morphed's with the weights alone, a rigid one through fovpt_update_transforms' with M.
+ *   contract   after fovpt_update_animated every frame, G-buffer, debug trace, "scene_vertices" buffer and hierarchy byte is what
+ *              fovpt_update_vertices gives on the same context with those positions of all bound meshes as host arrays in one
+ *              call.  It is one update: stream ordering, the refit, fovpt_temporal_motion's tracking, fovpt_hierarchy_cost's
+ *              counting (+1) and FOVPT_UPDATE_REBUILD (the only flag) are that call's own.  Meshes that are not bound keep what
+ *              they last had; poses are absolute and start from rest; a bound mesh may still be given to the other four calls.
+ *              Nothing but the kernel arguments crosses the bus.  The composed matrices are computed on the device and NOT
+ *              validated (the rule for FOVPT_UPDATE_DEVICE pointers): overflow along a hierarchy is the caller's responsibility.
+ *   set_rig    set-up-time state of the scene, called after fovpt_set_skins / fovpt_set_morphs: everything is validated first and
+ *              copied before the call returns; it may synchronise fovpt_stream(); it does not move geometry; it replaces a
+ *              previous rig as a whole (NULL: removes it).  A later fovpt_set_skins, fovpt_set_morphs or fovpt_set_scene drops
+ *              the rig: its joint and target counts were checked against those.  All or nothing.  FOVPT_E_NO_SCENE: no scene.
+ *              FOVPT_E_INVALID: null ctx; counts above the limits; num_nodes 0; a null array with a count > 0; a non-zero
+ *              reserved field; a parent >= the node's own index or < -1; a non-finite rest value; a rest rotation whose squared
+ *              norm (binary64) is outside [1/4, 4]; a binding's mesh out of range or bound twice; both node >= 0 and
+ *              num_joints > 0; a node (< -1 or >= num_nodes) or joint node out of range; num_joints > 0 other than the mesh's
+ *              skin's, or on a mesh without a skin; a rigid binding on a mesh that has morphs; a binding with neither node,
+ *              joints nor morphs on its mesh; a null joint_nodes or inverse_bind with num_joints > 0; a non-finite inverse bind
+ *              entry; a channel with an unknown path or interpolation, a target out of range, WEIGHTS on a mesh that is not
+ *              bound or has no morphs, the same (target, path) twice in one clip, num_keys outside 1 .. FOVPT_RIG_MAX_KEYS,
+ *              null times or values, times not finite or not strictly ascending, a non-finite value, a rotation key whose
+ *              squared norm is outside [1/4, 4]; more than 2^32 - 1 key times or values in the rig together.
+ *   animated   fovpt_update_animated poses every bound mesh from clip `clip` at `time`.  All or nothing.  FOVPT_E_NO_SCENE: no
+ *              scene.  FOVPT_E_INVALID: null ctx, no rig, clip out of range, a non-finite time, flag bits other than
+ *              FOVPT_UPDATE_REBUILD.  A rig without bindings: FOVPT_OK, nothing happens (unless a rebuild is asked for).
+ * Memory: on the device 44 + 12 bytes per node and clip-table entries of 12 bytes per node and clip, 4 bytes per key time and per
+ * key value, 56 bytes per joint of a binding, and 48 bytes per node, joint and rigid binding of results; nothing on the host
+ * beyond the list of bindings.  One k_rig_pose launch (one workgroup, a thread per node, a barrier per level of the hierarchy)
+ * ahead of the skinning, morph and transform launches: DESIGN.md, section 24.  Measured there on an MI355X, 103 meshes of 139 594
+ * vertices bound over 3020 joints to a rig of 1024 nodes in 8 levels: 0.144 ms per fovpt_update_animated against 0.220 ms per
+ * fovpt_update_skinned with host palettes made beforehand; k_rig_pose alone 0.004 ms for 1024 nodes on one level and 0.285 ms for
+ * 1024 nodes in one chain (about 0.28 us per level).  A context that never calls these functions pays nothing.                */
+#define FOVPT_RIG_MAX_NODES 1024
+#define FOVPT_RIG_MAX_CLIPS 64
+#define FOVPT_RIG_MAX_KEYS  (1u << 20)      /* per channel */
+#define FOVPT_RIG_TRANSLATION 0
+#define FOVPT_RIG_ROTATION    1
+#define FOVPT_RIG_SCALE       2
+#define FOVPT_RIG_WEIGHTS     3
+#define FOVPT_RIG_STEP   0
+#define FOVPT_RIG_LINEAR 1
+typedef struct fovpt_rig_node {
+    int32_t parent;              /* -1: a root; otherwise < this node's own index                                           */
+    float translation[3], rotation[4] /* x y z w */, scale[3];   /* the rest pose                                          */
+} fovpt_rig_node;                /* 44 bytes */
+typedef struct fovpt_rig_binding {   /* one mesh the rig drives */
+    int32_t mesh;                /* index into the meshes given to fovpt_set_scene                                          */
+    int32_t node;                /* >= 0: the mesh follows this node rigidly (num_joints 0); -1 otherwise                   */
+    uint32_t num_joints;         /* > 0: must equal the mesh's skin's (fovpt_set_skins)                                     */
+    uint32_t _reserved;          /* 0                                                                                       */
+    const uint16_t* joint_nodes; /* num_joints node indices, host                                                           */
+    const float* inverse_bind;   /* num_joints row-major 3 x 4 matrices, host                                               */
+} fovpt_rig_binding;             /* 32 bytes; node -1 and num_joints 0: morph weights only */
+typedef struct fovpt_rig_channel {
+    int32_t target;              /* node index; for FOVPT_RIG_WEIGHTS a mesh index                                          */
+    int32_t path, interpolation; /* FOVPT_RIG_TRANSLATION .. FOVPT_RIG_WEIGHTS; FOVPT_RIG_STEP or FOVPT_RIG_LINEAR          */
+    uint32_t num_keys;           /* 1 .. FOVPT_RIG_MAX_KEYS                                                                 */
+    const float* times;          /* num_keys, host, finite, strictly ascending                                              */
+    const float* values;         /* per key 3 / 4 / 3 floats; WEIGHTS: the mesh's num_targets; host, finite                 */
+} fovpt_rig_channel;             /* 32 bytes */
+typedef struct fovpt_rig_clip { uint32_t num_channels, _reserved; const fovpt_rig_channel* channels; } fovpt_rig_clip;   /* 16 bytes */
+typedef struct fovpt_rig_desc {
+    const fovpt_rig_node* nodes;       uint32_t num_nodes, _reserved0;        /* 1 .. FOVPT_RIG_MAX_NODES                  */
+    const fovpt_rig_binding* bindings; uint32_t num_bindings, _reserved1;
+    const fovpt_rig_clip* clips;       uint32_t num_clips, _reserved2;        /* 0 .. FOVPT_RIG_MAX_CLIPS                  */
+} fovpt_rig_desc;                /* 48 bytes */
+int fovpt_set_rig(fovpt_ctx* ctx, const fovpt_rig_desc* rig /* NULL: remove */);
+int fovpt_update_animated(fovpt_ctx* ctx, int clip, float time, int flags /* FOVPT_UPDATE_REBUILD */);
+
 /* ---- the cost of the hierarchy, measured on the device -----------------------------------------------------------------------
  * A refit keeps the tree's shape, so traversal slows as the motion grows (sections 13 and 16).  What to watch is
  * the SAH cost of the nodes, in binary64: with d = hi - lo of a live child entry and area = dx * dy + dy * dz + dz * dx,

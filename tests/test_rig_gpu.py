@@ -1,0 +1,633 @@
+"""fovpt_set_rig and fovpt_update_animated on the GPU: the bits k_rig_pose writes against tests/rig_ref.py, positions and hierarchy
+bytes against fovpt_update_vertices with the restated positions on the same context, a frame against the CPU oracle, the node
+counts around the wave and block sizes as flat rigs and as chains, morph weights, absolute semantics and mixing with the other
+update calls, rebuild and the cost counters, fovpt_temporal_motion's tracking, frames in flight, the life cycle of a rig, every
+rejection, a seeded sweep, and the C++ drop-in.  FOVPT_FUZZRG_TO widens the sweep."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import morph_ref as mr
+import rig_ref as rg
+import skin_ref as sk
+import transform_ref as tf
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+
+from common import cfg_foveated, make_gpu
+from postprocess_common import bits
+from temporal_motion_common import MotionChecker, debug_buffer
+from test_refit_gpu import assert_frame_is_oracle, hierarchy, jitter, moved, oracle_frame, render
+from test_skin_gpu import all_vertices, rest_of, same, scene_vertices
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_INVALID, E_NO_SCENE = -1, -3
+CORNELL = scenes.CORNELL_CAMERA
+PROBE = scenes.ambient_probe(64, 32, 2.0)
+F = np.float32
+SEEDS = range(0, int(os.environ.get("FOVPT_FUZZRG_TO", "8")))
+TALL, SHORT = 4, 3
+TIMES = (-1.0, 0.0, 0.25, 0.5, 0.75, 1.0, 1.25, 1.5, 1.75, 2.0, 3.0)      # before, at, between and after the keys below
+
+
+# ---- the fixture --------------------------------------------------------------------------------------------------------------
+def cornell_skins(model):
+    return {TALL: sk.bend(model.meshes[TALL].vertex, 3)}
+
+
+def cornell_rig(model):
+    """The tall block on a chain of three joints up its height, the short block rigid on node 4, which hangs from a pivot (node
+    3) at the block's centre.  Clip 0 has translation, rotation and scale channels of 2 to 4 keys, STEP and LINEAR, with rotation
+    keys 20 degrees apart (the sine branch), 2 degrees apart (the linear one) and on opposite hemispheres (the flip); clip 1
+    moves the short block alone."""
+    rig = rg.empty_rig(5)
+    rig["parent"] = np.array([-1, 0, 1, -1, 3], np.int32)
+    rig["translation"] = F([[368, 0, 351], [0, 110, 0], [0, 110, 0], [186, 82, 168], [-186, -82, -168]])
+    rig["rotation"][0] = rg.quat((0, 1, 0), 15.0)
+    z = (0.1, 0.0, 1.0)
+    rig["clips"] = [[
+        rg.channel(0, rg.ROTATION, [0.0, 1.0, 2.0], [rg.quat(z, 0.0), rg.quat(z, 20.0), rg.quat(z, 22.0)]),
+        rg.channel(1, rg.TRANSLATION, [0.5, 1.5], [[0, 110, 0], [12, 100, -6]]),
+        rg.channel(1, rg.ROTATION, [0.0, 0.5, 1.0, 1.5], [rg.quat((1, 0, 0), 0.0), -rg.quat((1, 0, 0), 14.0), rg.quat((1, 0, 0.3), 15.0, 1.3), rg.quat((1, 0, 0.3), 16.5, 0.8)]),
+        rg.channel(2, rg.SCALE, [0.25, 1.75], [[1, 1, 1], [1.2, 0.9, 1.1]]),
+        rg.channel(2, rg.ROTATION, [0.5, 1.0, 2.0], [rg.quat((0, 0, 1), -10.0), rg.quat((0, 0, 1), 10.0), rg.quat((0, 1, 0), 30.0)], rg.STEP),
+        rg.channel(3, rg.TRANSLATION, [0.0, 1.0, 2.0], [[186, 82, 168], [150, 95, 190], [160, 120, 150]], rg.STEP),
+        rg.channel(3, rg.ROTATION, [0.0, 2.0], [rg.quat((0, 1, 0), 0.0), rg.quat((0, 1, 0), 50.0)]),
+        rg.channel(3, rg.SCALE, [0.0, 1.0, 1.25, 2.0], [[1, 1, 1], [1.1, 0.8, 1], [1.1, 0.8, 1.2], [0.9, 1, 1]]),
+    ], [rg.channel(3, rg.TRANSLATION, [0.0, 1.0], [[186, 82, 168], [200, 82, 140]])]]
+    rig["bindings"] = [dict(mesh=TALL, joint_nodes=np.array([0, 1, 2], np.uint16), inverse_bind=rg.inverse_bind_of(rig, [0, 1, 2])), dict(mesh=SHORT, node=4)]
+    return rig
+
+
+def rig_buffers(r):
+    out = []
+    for name in ("rig_world", "rig_palette", "rig_rigid"):
+        p, n = debug_buffer(r, name)
+        out.append(r.download(p, np.empty((n // 48, 3, 4), F)) if n else np.empty((0, 3, 4), F))
+    return out
+
+
+def assert_pose_bits(oracle, r, rig, clip, T, morphs=None):
+    world, pal, rigid = rig_buffers(r)
+    P = rg.pose(oracle, rig, clip, T, morphs)
+    assert np.array_equal(bits(world), bits(P["world"])), T
+    assert np.array_equal(bits(pal), bits(np.concatenate(P["palettes"]) if P["palettes"] else np.empty((0, 3, 4), F))), T
+    assert np.array_equal(bits(rigid), bits(np.stack(P["rigid"]) if P["rigid"] else np.empty((0, 3, 4), F))), T
+    return P
+
+
+def cornell():
+    model = scenes.cornell_box()
+    r = renderer.SampleRenderer(model)
+    skins, rig = cornell_skins(model), cornell_rig(model)
+    r.set_skins(skins)
+    r.set_rig(rig)
+    return model, r, skins, rig
+
+
+# ---- 1. the bits of the pose ---------------------------------------------------------------------------------------------------
+def test_pose_bits_are_the_restatement(oracle):
+    model, r, skins, rig = cornell()
+    assert rg.accepted(rig, len(model.meshes), skins={TALL: 3})
+    branches = set()
+    for ch in rig["clips"][0]:                                            # the fixture does take both slerp branches, and the flip
+        v = ch["values"].astype(np.float64)
+        if ch["path"] == rg.ROTATION and ch["interpolation"] == rg.LINEAR:
+            for a, b in zip(v[:-1], v[1:]):
+                branches.add(("flip" if a @ b < 0 else "same", "linear" if abs(a @ b) > 0.9995 else "sine"))
+    assert {b for _, b in branches} == {"linear", "sine"} and "flip" in {f for f, _ in branches}
+    for T in TIMES:
+        r.update_animated(0, T)
+        P = assert_pose_bits(oracle, r, rig, 0, T)
+        assert np.isfinite(P["world"]).all()
+    r.update_animated(1, 0.5)
+    assert_pose_bits(oracle, r, rig, 1, 0.5)
+    r.close()
+
+
+# ---- 2. the contract -----------------------------------------------------------------------------------------------------------
+def test_positions_and_hierarchy_are_update_vertices_of_the_restatement(oracle):
+    model, r, skins, rig = cornell()
+    h0 = hierarchy(r)
+    first = np.cumsum([0] + [m.vertex.shape[0] for m in model.meshes])
+    for T in (0.0, 0.75, 1.25, 3.0):
+        new = rg.restate(oracle, model, rig, 0, T, skins)
+        assert sorted(new) == [SHORT, TALL]
+        r.update_vertices(new)
+        want = hierarchy(r)
+        r.update_vertices(rest_of(model))
+        assert same(hierarchy(r), h0)
+        r.update_animated(0, T)
+        got = scene_vertices(r)
+        assert np.array_equal(bits(got), bits(all_vertices(model, new))), T
+        assert same(hierarchy(r), want) and not same(want, h0), T
+        for k in (0, 1, 2, 5):                                            # the meshes that are not bound keep their bits
+            assert np.array_equal(bits(got[first[k]:first[k + 1]]), bits(model.meshes[k].vertex))
+    r.close()
+
+
+def test_a_frame_after_an_animated_update_is_the_oracle(oracle):
+    size, cfg = (96, 64), cfg_foveated(10, 24, (1, 2, 4))
+    base = scenes.cornell_box()
+    skins, rig = cornell_skins(base), cornell_rig(base)
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    _, px0, _ = render(r)
+    r.set_skins(skins)
+    r.set_rig(rig)
+    _, px1, _ = render(r)
+    assert np.array_equal(px0, px1)                                       # a rig alone moves nothing
+    r.update_animated(0, 1.25)
+    _, px = assert_frame_is_oracle(oracle, r, moved(base, rg.restate(oracle, base, rig, 0, 1.25, skins)), CORNELL, size, cfg)
+    assert not np.array_equal(px, px0)
+    r.close()
+
+
+# ---- 3. node counts ------------------------------------------------------------------------------------------------------------
+def _one_joint(model, rig):
+    n = len(rig["parent"])
+    rig["bindings"] = [dict(mesh=TALL, joint_nodes=np.array([n - 1], np.uint16), inverse_bind=np.eye(3, 4, dtype=F)[None])]
+    return rig
+
+
+@pytest.mark.parametrize("shape", ["flat", "chain"])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 256, 257, 1024])
+def test_node_count_edges(oracle, n, shape):
+    model = scenes.cornell_box()
+    rig = _one_joint(model, rg.flat_rig(n) if shape == "flat" else rg.chain_rig(n))
+    assert (max(rig["parent"]) == -1) if shape == "flat" else (list(rig["parent"]) == list(range(-1, n - 1)))
+    r = renderer.SampleRenderer(model)
+    r.set_skins({TALL: sk.bend(model.meshes[TALL].vertex, 1)})
+    r.set_rig(rig)
+    r.update_animated(0, 0.625)
+    P = assert_pose_bits(oracle, r, rig, 0, 0.625)
+    assert np.isfinite(P["world"]).all() and not np.array_equal(P["world"][n - 1], np.eye(3, 4, dtype=F))
+    r.close()
+
+
+def test_more_than_the_most_nodes_is_refused():
+    model = scenes.cornell_box()
+    r = renderer.SampleRenderer(model)
+    r.set_skins({TALL: sk.bend(model.meshes[TALL].vertex, 1)})
+    r.set_rig(_one_joint(model, rg.flat_rig(rg.MAX_NODES)))
+    with pytest.raises(lib.FovptError):
+        r.set_rig(_one_joint(model, rg.flat_rig(rg.MAX_NODES + 1)))
+    with pytest.raises(lib.FovptError):
+        r.set_rig(_one_joint(model, rg.chain_rig(rg.MAX_NODES + 1)))
+    r.update_animated(0, 0.5)                                             # the rig of 1024 is still there
+    r.close()
+
+
+# ---- 4. morphs -----------------------------------------------------------------------------------------------------------------
+def morph_fixture(model):
+    """The tall block skinned and morphed (4 targets), the short block morphed alone (3 targets), the left wall rigid."""
+    rng = np.random.default_rng(7)
+    skins = cornell_skins(model)
+    morphs = {TALL: mr.random_targets(rng, model.meshes[TALL].vertex.shape[0], 4, dense=1, scale=30.0),
+              SHORT: mr.random_targets(rng, model.meshes[SHORT].vertex.shape[0], 3, dense=3, scale=20.0)}
+    rig = cornell_rig(model)
+    rig["bindings"][1] = dict(mesh=SHORT)
+    rig["bindings"].append(dict(mesh=2, node=3))
+    rig["clips"][0] += [rg.channel(TALL, rg.WEIGHTS, [0.0, 1.0, 2.0], [[0, 0, 0, 0], [1, -0.5, 0, 2], [0, 0.25, 0, 1]]),
+                        rg.channel(SHORT, rg.WEIGHTS, [0.5, 1.5], [[0, 1, 0], [1, 0, -1]], rg.STEP)]
+    rig["clips"][1] = [rg.channel(0, rg.ROTATION, [0.0, 1.0], [rg.quat((0, 0, 1), 0.0), rg.quat((0, 0, 1), 25.0)])]       # no WEIGHTS channel
+    return skins, morphs, rig
+
+
+def test_morph_weights_and_a_clip_without_them(oracle):
+    model = scenes.cornell_box()
+    skins, morphs, rig = morph_fixture(model)
+    counts = {k: len(v) for k, v in morphs.items()}
+    assert rg.accepted(rig, len(model.meshes), skins={TALL: 3}, morphs=counts)
+    r = renderer.SampleRenderer(model)
+    r.set_skins(skins)
+    r.set_morphs(morphs)
+    r.set_rig(rig)
+    for T in (0.0, 0.5, 0.7, 1.0, 1.6, 2.5):
+        skinned, morphed, rigid = rg.drives(oracle, rig, 0, T, morphs)
+        assert not skinned and sorted(morphed) == [SHORT, TALL] and sorted(rigid) == [2] and isinstance(morphed[TALL], tuple)
+        r.update_vertices(rest_of(model))
+        r.update_morphed({TALL: morphed[TALL]})                           # the restated weights and palette through fovpt_update_morphed
+        r.update_morphed({SHORT: morphed[SHORT]})
+        r.update_transforms(rigid)
+        want_v, want_h = scene_vertices(r), hierarchy(r)
+        r.update_vertices(rest_of(model))
+        r.update_animated(0, T)
+        assert_pose_bits(oracle, r, rig, 0, T, counts)
+        assert np.array_equal(bits(scene_vertices(r)), bits(want_v)) and same(hierarchy(r), want_h), T
+        assert np.array_equal(bits(want_v), bits(all_vertices(model, rg.restate(oracle, model, rig, 0, T, skins, morphs)))), T
+    # clip 1 names no weights: all zero, so the tall block is rest through the skin and the short block is rest
+    r.update_animated(1, 0.5)
+    got = scene_vertices(r)
+    pal = rg.pose(oracle, rig, 1, 0.5)["palettes"][0]
+    new = rg.restate(oracle, model, rig, 1, 0.5, skins, morphs)
+    assert np.array_equal(bits(new[TALL]), bits(sk.apply(model.meshes[TALL].vertex, skins[TALL][0], skins[TALL][1], pal)))
+    assert np.array_equal(bits(new[SHORT]), bits(model.meshes[SHORT].vertex))
+    assert np.array_equal(bits(got), bits(all_vertices(model, new)))
+    r.close()
+
+
+# ---- 5. semantics ----------------------------------------------------------------------------------------------------------------
+def test_poses_are_absolute_and_mix_with_the_other_calls(oracle):
+    model, r, skins, rig = cornell()
+    new = lambda T, clip=0: rg.restate(oracle, model, rig, clip, T, skins)
+    r.update_animated(0, 0.75)
+    r.update_animated(0, 1.75)                                            # the second pose of rest, not of the first
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, new(1.75))))
+    # a mesh the other calls have moved starts from rest again; an unbound mesh they moved stays
+    j2 = jitter(model.meshes[2].vertex, 3, 9.0)
+    r.update_vertices({2: j2, TALL: jitter(model.meshes[TALL].vertex, 4, 9.0)})
+    r.update_transforms({SHORT: sk.dense_matrix()})
+    r.update_animated(0, 0.3)
+    want = new(0.3)
+    want[2] = j2
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, want)))
+    # a bound mesh through fovpt_update_skinned and fovpt_update_transforms, and back under the rig
+    pal = sk.bend_pose(model.meshes[TALL].vertex, 3, 40.0, (5.0, 0.0, -3.0))
+    r.update_skinned({TALL: pal})
+    want[TALL] = sk.apply(model.meshes[TALL].vertex, skins[TALL][0], skins[TALL][1], pal)
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, want)))
+    r.update_transforms({SHORT: sk.dense_matrix((186.0, 0.0, 168.0))})
+    want[SHORT] = tf.apply(model.meshes[SHORT].vertex, sk.dense_matrix((186.0, 0.0, 168.0)))
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, want)))
+    r.update_animated(1, 0.5)
+    want.update(new(0.5, 1))
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, want)))
+    r.close()
+
+
+def test_rebuild_and_the_cost_counters(oracle):
+    base = scenes.cornell_box()
+    size, cfg = (96, 64), cfg_foveated(10, 24, (1, 2, 4))
+    skins, rig = cornell_skins(base), cornell_rig(base)
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    trav = r.launchParams.traversable
+    r.set_skins(skins)
+    r.set_rig(rig)
+    assert r.hierarchy_cost().updates == 0                                # a rig is no update
+    r.update_animated(0, 1.25)
+    c1 = r.hierarchy_cost(wait=True)
+    assert (c1.updates, c1.measured) == (1, 1)                            # one update per call, whatever it binds
+    refit = render(r)
+    r.update_animated(0, 1.25, rebuild=True)
+    c2 = r.hierarchy_cost()
+    assert (c2.updates, c2.measured) == (2, 2) and c2.current == c2.built
+    assert r.launchParams.traversable == trav
+    rebuilt = render(r)
+    assert np.array_equal(bits(refit[0]), bits(rebuilt[0])) and np.array_equal(refit[1], rebuilt[1])
+    fresh = make_gpu(moved(base, rg.restate(oracle, base, rig, 0, 1.25, skins)), PROBE, CORNELL, size, cfg)
+    want = render(fresh)
+    assert np.array_equal(bits(rebuilt[0]), bits(want[0])) and np.array_equal(rebuilt[1], want[1])
+    r.update_animated(1, 0.0)
+    r.update_animated(1, 1.0)
+    assert r.hierarchy_cost(wait=True).updates == 4
+    assert r._L.fovpt_update_animated(r._ctx, 0, C.c_float(0.5), 4) == E_INVALID        # a refused call is not counted
+    assert r.hierarchy_cost().updates == 4
+    fresh.close()
+    r.close()
+
+
+def test_temporal_motion_sees_an_animated_update_as_a_vertex_update(oracle):
+    size = (96, 60)                                                       # (the restatement of a step is python: a small frame)
+    cfg = cfg_foveated(8, 20, (1, 2, 4))
+    cfg.write_guides = 1
+    base = scenes.cornell_box()
+    skins, rig = cornell_skins(base), cornell_rig(base)
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    r.set_skins(skins)
+    r.set_rig(rig)
+    ck = MotionChecker(oracle, r, dict(history_fovea=3, history_middle=5, history_periphery=8, history_uniform=6))
+    r.render()
+    ck.step()
+    for T in (0.6,):
+        r.update_animated(0, T)
+        for k, v in rg.restate(oracle, base, rig, 0, T, skins).items():   # the checker's own record of the update
+            ck.vtx[ck.first[k]:ck.first[k + 1]] = v
+            ck.moved[k] = True
+        r.launchParams.frame.subframe_index = 0
+        r.render()
+        _, h, _, mv = ck.step()
+    assert (h[..., 3] > 1).mean() > 0.3 and mv is not None            # the walls keep their history, and so do the blocks that moved
+    r.close()
+
+
+# ---- 6. frames in flight ---------------------------------------------------------------------------------------------------------
+def test_an_animated_update_between_frames_in_flight(oracle):
+    import torch
+    size = (96, 64)
+    cfg = cfg_foveated(10, 24, (1, 2, 4))
+    cfg.frames_in_flight = 2
+    base = scenes.cornell_box()
+    skins, rig = cornell_skins(base), cornell_rig(base)
+    shape = (size[1], size[0])
+    r = make_gpu(base, PROBE, CORNELL, size, cfg)
+    r.set_skins(skins)
+    r.set_rig(rig)
+    outs = [(torch.zeros(shape + (4,), dtype=torch.float32, device="cuda"), torch.zeros(shape, dtype=torch.int32, device="cuda")) for _ in range(2)]
+    torch.cuda.synchronize()
+    for k, b in enumerate(outs):                                          # render, update, render: no synchronisation
+        if k:
+            r.update_animated(0, 1.25)
+        f = r.launchParams.frame
+        f.accum_buffer, f.frame_buffer = b[0].data_ptr(), b[1].data_ptr()
+        f.subframe_index = 0
+        r.render_async()
+    r.synchronize()
+    models = [base, moved(base, rg.restate(oracle, base, rig, 0, 1.25, skins))]
+    for k, (m, b) in enumerate(zip(models, outs)):
+        Fr, _ = oracle_frame(oracle, m, CORNELL, size, cfg)
+        acc, px = b[0].cpu().numpy(), b[1].cpu().numpy()
+        assert np.array_equal(bits(acc), bits(Fr.accum)) and np.array_equal(px.view(np.uint32), Fr.frame), "frame %d" % k
+    assert not np.array_equal(outs[0][1].cpu().numpy(), outs[1][1].cpu().numpy())
+    r.close()
+
+
+# ---- 7. the life cycle of a rig ---------------------------------------------------------------------------------------------------
+def test_set_rig_replaces_removes_and_ends_with_skins_morphs_and_the_scene(oracle):
+    model, r, skins, rig = cornell()
+
+    def refused():
+        with pytest.raises(lib.FovptError) as e:
+            r.update_animated(0, 0.5)
+        assert e.value.code == E_INVALID and "no rig" in str(e.value)
+        assert b"no rig" in r._L.fovpt_last_error(r._ctx)
+
+    r.update_animated(0, 0.5)
+    r.set_skins({TALL: skins[TALL]})                                      # the same skin again: the rig goes all the same
+    refused()
+    r.set_rig(rig)
+    r.update_animated(0, 0.5)
+    r.set_morphs({2: mr.random_targets(np.random.default_rng(1), model.meshes[2].vertex.shape[0], 2)})
+    refused()
+    r.set_rig(rig)
+    r.update_animated(0, 0.5)
+    want = all_vertices(model, rg.restate(oracle, model, rig, 0, 0.5, skins))
+    assert np.array_equal(bits(scene_vertices(r)), bits(want))
+    r.set_rig(None)                                                       # NULL removes it; geometry does not move
+    refused()
+    r.set_rig(None)                                                       # nothing to remove: fine
+    assert np.array_equal(bits(scene_vertices(r)), bits(want))
+    # a second set_rig replaces the first as a whole
+    r.set_rig(rig)
+    other = cornell_rig(model)
+    other["clips"] = [other["clips"][1]]
+    other["bindings"] = other["bindings"][1:]                             # the short block alone
+    r.set_rig(other)
+    with pytest.raises(lib.FovptError):
+        r.update_animated(1, 0.5)                                         # the first rig's second clip is gone
+    r.update_vertices(rest_of(model))
+    r.update_animated(0, 0.5)
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, rg.restate(oracle, model, other, 0, 0.5, skins))))
+    assert debug_buffer(r, "rig_palette")[1] == 0 and debug_buffer(r, "rig_rigid")[1] == 48 and debug_buffer(r, "rig_world")[1] == 5 * 48
+    # fovpt_set_scene drops it
+    md, n, td, nt, keep = scenes.pack_model(model)
+    trav = C.c_uint64()
+    r._check(r._L.fovpt_set_scene(r._ctx, C.cast(md, C.c_void_p), n, C.cast(td, C.c_void_p), nt, C.byref(trav)))
+    refused()
+    with pytest.raises(lib.FovptError):
+        r.set_rig(rig)                                                    # the skins went with the scene: joints on a mesh without a skin
+    r.set_skins(skins)
+    r.set_rig(rig)
+    r.update_animated(0, 0.5)
+    assert np.array_equal(bits(scene_vertices(r)), bits(want))
+    r.close()
+
+
+# ---- 8. rejections -----------------------------------------------------------------------------------------------------------------
+def test_rejections_change_nothing(oracle):
+    model = scenes.cornell_box()
+    skins, morphs, rig = morph_fixture(model)
+    morphs[5] = mr.random_targets(np.random.default_rng(2), model.meshes[5].vertex.shape[0], 1)      # morphs, and not bound
+    skins[1] = sk.bend(model.meshes[1].vertex, 2)                         # a skin, and not bound
+    r = renderer.SampleRenderer(model)
+    L = r._L
+    r.set_skins(skins)
+    r.set_morphs(morphs)
+    r.set_rig(rig)
+    r.update_animated(0, 0.7)
+    before_v, before_h = scene_vertices(r), hierarchy(r)
+    before_w = rig_buffers(r)[0]
+
+    def unchanged():
+        return np.array_equal(bits(scene_vertices(r)), bits(before_v)) and same(hierarchy(r), before_h)
+
+    def refused(change, what):
+        desc, keep = r.pack_rig(rig)
+        keep.append(change(desc))
+        assert L.fovpt_set_rig(r._ctx, C.byref(desc)) == E_INVALID, what
+        assert b"fovpt_set_rig" in L.fovpt_last_error(r._ctx), what
+        assert unchanged(), what
+        r.update_animated(0, 0.7)                                         # the previous rig is still the rig
+        assert unchanged() and np.array_equal(bits(rig_buffers(r)[0]), bits(before_w)), what
+
+    def field(path, value):
+        """Sets desc.<path> = value; path like 'bindings[1].node' or 'clips[0].channels[2].times'."""
+        def change(desc):
+            v = value(desc) if callable(value) else value
+            exec("desc.%s = v" % path, dict(desc=desc, v=v))
+            return v
+        return change
+
+    def floats(get, index, value):
+        """A copy of the float array a pointer field holds, with one entry changed."""
+        def change(desc):
+            a = np.array(get(rig), F).copy()
+            a.reshape(-1)[index] = value
+            return a
+        return change
+
+    def ptr(path, make):
+        def change(desc):
+            a = np.ascontiguousarray(make(desc))
+            exec("desc.%s = p" % path, dict(desc=desc, p=a.ctypes.data))
+            return a
+        return change
+
+    nan, inf = np.nan, np.inf
+    below, above = (lambda x: np.nextafter(F(x), F(0))), (lambda x: np.nextafter(F(x), F(inf)))
+    B, CH = "bindings[%d].%s", "clips[0].channels[%d].%s"
+    # clip 0's channels: 0 R(node 0) 1 T(1) 2 R(1) 3 S(2) 4 R(2) 5 T(3) 6 R(3) 7 S(3) 8 W(TALL) 9 W(SHORT)
+    cases = [
+        # the description as a whole
+        ("reserved0", field("_reserved0", 1)), ("reserved1", field("_reserved1", 1)), ("reserved2", field("_reserved2", 7)),
+        ("no nodes", field("num_nodes", 0)), ("too many nodes", field("num_nodes", rg.MAX_NODES + 1)), ("too many clips", field("num_clips", rg.MAX_CLIPS + 1)),
+        ("null nodes", field("nodes", lambda d: C.POINTER(abi.RigNode)())), ("null bindings", field("bindings", lambda d: C.POINTER(abi.RigBinding)())),
+        ("null clips", field("clips", lambda d: C.POINTER(abi.RigClip)())),
+        ("clip reserved", field("clips[1]._reserved", 1)), ("null channels", field("clips[0].channels", lambda d: C.POINTER(abi.RigChannel)())),
+        # nodes
+        ("parent is itself", field("nodes[2].parent", 2)), ("parent above", field("nodes[1].parent", 3)), ("parent below -1", field("nodes[0].parent", -2)),
+        ("rest translation nan", field("nodes[1].translation[2]", nan)), ("rest rotation inf", field("nodes[4].rotation[0]", inf)),
+        ("rest scale -inf", field("nodes[3].scale[1]", -inf)),
+        ("rest rotation too short", field("nodes[2].rotation[3]", below(0.5))), ("rest rotation too long", field("nodes[2].rotation[3]", above(2.0))),
+        # bindings
+        ("mesh above", field(B % (0, "mesh"), 6)), ("mesh below", field(B % (0, "mesh"), -1)), ("bound twice", field(B % (2, "mesh"), TALL)),
+        ("binding reserved", field(B % (1, "_reserved"), 1)),
+        ("node and joints", field(B % (0, "node"), 1)), ("node above", field(B % (2, "node"), 5)), ("node below -1", field(B % (2, "node"), -2)),
+        ("joint node above", ptr(B % (0, "joint_nodes"), lambda d: np.array([0, 5, 2], np.uint16))),
+        ("fewer joints than the skin", field(B % (0, "num_joints"), 2)), ("more joints than the skin", field(B % (0, "num_joints"), 4)),
+        ("joints on a mesh without a skin", lambda d: [field(B % (2, "node"), -1)(d), field(B % (2, "num_joints"), 3)(d),
+                                                       field(B % (2, "joint_nodes"), d.bindings[0].joint_nodes)(d), field(B % (2, "inverse_bind"), d.bindings[0].inverse_bind)(d)]),
+        ("rigid and morphs", field(B % (1, "node"), 2)),
+        ("neither node, joints nor morphs", field(B % (2, "node"), -1)),
+        ("null joint_nodes", field(B % (0, "joint_nodes"), None)), ("null inverse_bind", field(B % (0, "inverse_bind"), None)),
+        ("inverse bind nan", ptr(B % (0, "inverse_bind"), floats(lambda g: g["bindings"][0]["inverse_bind"], 17, nan))),
+        ("inverse bind inf", ptr(B % (0, "inverse_bind"), floats(lambda g: g["bindings"][0]["inverse_bind"], 35, -inf))),
+        # clips and channels
+        ("path above", field(CH % (1, "path"), 4)), ("path below", field(CH % (1, "path"), -1)),
+        ("interpolation above", field(CH % (1, "interpolation"), 2)), ("interpolation below", field(CH % (1, "interpolation"), -1)),
+        ("node target above", field(CH % (1, "target"), 5)), ("node target below", field(CH % (1, "target"), -1)),
+        ("mesh target above", field(CH % (8, "target"), 6)), ("mesh target below", field(CH % (8, "target"), -1)),
+        ("weights of a mesh that is not bound", field(CH % (9, "target"), 5)), ("weights of a bound mesh without morphs", field(CH % (9, "target"), 2)),
+        ("weights of a mesh with neither", field(CH % (9, "target"), 0)),
+        ("the same node and path twice", field(CH % (3, "target"), 3)), ("the same weights twice", lambda d: [field(CH % (1, "path"), rg.WEIGHTS)(d), field(CH % (1, "target"), SHORT)(d)]),
+        ("no keys", field(CH % (1, "num_keys"), 0)), ("too many keys", field(CH % (1, "num_keys"), rg.MAX_KEYS + 1)),
+        ("null times", field(CH % (1, "times"), None)), ("null values", field(CH % (1, "values"), None)),
+        ("time nan", ptr(CH % (0, "times"), lambda d: F([0, nan, 2]))), ("time inf", ptr(CH % (0, "times"), lambda d: F([0, 1, inf]))),
+        ("time -inf", ptr(CH % (0, "times"), lambda d: F([-inf, 1, 2]))),
+        ("times equal", ptr(CH % (0, "times"), lambda d: F([0, 1, 1]))), ("times descending", ptr(CH % (0, "times"), lambda d: F([0, 2, 1]))),
+        ("value nan", ptr(CH % (1, "values"), floats(lambda g: g["clips"][0][1]["values"], 4, nan))),
+        ("value inf", ptr(CH % (3, "values"), floats(lambda g: g["clips"][0][3]["values"], 0, inf))),
+        ("weight nan", ptr(CH % (8, "values"), floats(lambda g: g["clips"][0][8]["values"], 11, nan))),
+        ("rotation key too short", ptr(CH % (0, "values"), lambda d: np.array([[0, 0, 0, 1], [0, below(0.5), 0, 0], [0, 0, 0, 1]], F))),
+        ("rotation key too long", ptr(CH % (0, "values"), lambda d: np.array([[0, 0, 0, 1], [0, 0, 0, 1], [above(1.0), 1, 1, 1]], F))),
+    ]
+    assert len(rig["clips"][0]) == 10 and rig["clips"][0][8]["path"] == rig["clips"][0][9]["path"] == rg.WEIGHTS
+    for what, change in cases:
+        refused(change, what)
+    # the other side of the norm rule: exactly 1/4 and exactly 4 are taken
+    desc, keep = r.pack_rig(rig)
+    keep.append(ptr(CH % (0, "values"), lambda d: np.array([[0, 0, 0, 0.5], [0, 2, 0, 0], [1, 1, 1, 1]], F))(desc))
+    desc.nodes[2].rotation[3] = 0.5
+    assert L.fovpt_set_rig(r._ctx, C.byref(desc)) == 0
+    r.set_rig(rig)
+    assert L.fovpt_set_rig(None, None) == E_INVALID
+    # fovpt_update_animated
+    for clip, T, flags in ((-1, 0.5, 0), (2, 0.5, 0), (0, nan, 0), (0, inf, 0), (0, -inf, abi.UPDATE_REBUILD), (0, 0.5, 1), (0, 0.5, 4), (0, 0.5, 8 | abi.UPDATE_REBUILD)):
+        assert L.fovpt_update_animated(r._ctx, clip, C.c_float(T), flags) == E_INVALID, (clip, T, flags)
+        assert unchanged()
+    assert L.fovpt_update_animated(None, 0, C.c_float(0.5), 0) == E_INVALID
+    for bad in (dict(rig, translation=np.zeros((4, 3), F)), dict(rig, rotation=np.zeros((5, 3), F)),       # the wrapper's own checks
+                dict(rig, bindings=[dict(mesh=TALL, joint_nodes=np.array([0, 1, 2]), inverse_bind=np.zeros((2, 3, 4), F))]),
+                dict(rig, clips=[[dict(rig["clips"][0][0], values=np.zeros((3, 3), F))]])):
+        with pytest.raises(ValueError):
+            r.set_rig(bad)
+    r.update_animated(0, 0.7)
+    assert unchanged()
+    r.close()
+    ctx = C.c_void_p()                                                    # no scene
+    lib.check(None, L.fovpt_create(C.byref(ctx), 0))
+    desc, keep = renderer.SampleRenderer.pack_rig(rig)
+    assert L.fovpt_set_rig(ctx, C.byref(desc)) == E_NO_SCENE and L.fovpt_set_rig(ctx, None) == E_NO_SCENE
+    assert L.fovpt_update_animated(ctx, 0, C.c_float(0.0), 0) == E_NO_SCENE
+    L.fovpt_destroy(ctx)
+
+
+# ---- 9. a seeded sweep -------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sweep_scene():
+    model = scenes.atrium(2000)
+    r = renderer.SampleRenderer(model)
+    yield model, r, hierarchy(r)
+    r.close()
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_seeded_rigs(oracle, sweep_scene, seed):
+    """Random hierarchies of up to 64 nodes over the atrium: skinned, skinned and morphed, morphed and rigid bindings, about a
+    third of the meshes left alone."""
+    model, r, h0 = sweep_scene
+    nmesh = len(model.meshes)
+    rng = np.random.default_rng(3000 + seed)
+    n = int(rng.integers(1, 65)) if seed else 64
+    rig = rg.random_rig(rng, n, max_depth=(None, 3, 12)[seed % 3], scales=bool(seed % 2), chains=0.5 * (seed % 2))
+    for i in range(n):                                                    # small carries and near-unit scales: the atrium stays in one piece
+        rig["translation"][i] *= F(0.3)
+    skins, morphs, bindings = {}, {}, []
+    for k in range(nmesh):
+        kind = rng.choice(["skin", "both", "morph", "rigid", "none"], p=[0.3, 0.1, 0.1, 0.2, 0.3])
+        nv = model.meshes[k].vertex.shape[0]
+        if kind in ("skin", "both"):
+            skins[k] = sk.random_skin(rng, nv, int(rng.integers(1, 9)))
+            nodes = rng.integers(0, n, skins[k][2]).astype(np.uint16)
+            bindings.append(dict(mesh=k, joint_nodes=nodes, inverse_bind=rg.inverse_bind_of(rig, nodes)))
+        if kind in ("both", "morph"):
+            morphs[k] = mr.random_targets(rng, nv, int(rng.integers(1, 5)), scale=0.5)
+            if kind == "morph":
+                bindings.append(dict(mesh=k))
+            if rng.uniform() < 0.8:
+                keys = int(rng.integers(1, 4))
+                rig["clips"][0].append(rg.channel(k, rg.WEIGHTS, np.cumsum(rng.uniform(0.2, 1.0, keys)), rng.uniform(-1, 2, (keys, len(morphs[k]))),
+                                                  rg.STEP if rng.uniform() < 0.3 else rg.LINEAR))
+        if kind == "rigid":
+            bindings.append(dict(mesh=k, node=int(rng.integers(0, n))))
+    order = rng.permutation(len(bindings))
+    rig["bindings"] = [bindings[i] for i in order]                        # binding order is not mesh order
+    assert rg.accepted(rig, nmesh, skins={k: s[2] for k, s in skins.items()}, morphs={k: len(t) for k, t in morphs.items()})
+    r.set_skins({k: skins.get(k) for k in range(nmesh)})                  # (the others lose what an earlier seed gave them)
+    r.set_morphs({k: morphs.get(k) for k in range(nmesh)})
+    r.set_rig(rig)
+    T = F(rng.uniform(0.0, 2.5))
+    want_v = rg.restate(oracle, model, rig, 0, T, skins, morphs)
+    assert sorted(want_v) == sorted(b["mesh"] for b in bindings) and all(np.isfinite(v).all() for v in want_v.values())
+    r.update_vertices(rest_of(model))
+    assert same(hierarchy(r), h0)
+    r.update_vertices(want_v)
+    want_h = hierarchy(r)
+    r.update_vertices(rest_of(model))
+    r.update_animated(0, T)
+    assert_pose_bits(oracle, r, rig, 0, T, {k: len(t) for k, t in morphs.items()})
+    assert np.array_equal(bits(scene_vertices(r)), bits(all_vertices(model, want_v)))
+    assert same(hierarchy(r), want_h) and not same(want_h, h0)
+
+
+# ---- 10. C++ -----------------------------------------------------------------------------------------------------------------------
+def test_cpp_set_rig_and_update_animated(oracle, tmp_path):
+    """SampleRenderer::setRig / updateAnimated of include/SimplePathtracer.h: the hashes of the frame and of the vertex bytes the
+    program prints are those of the same rig through the python wrapper."""
+    exe = str(tmp_path / "rig_gpu_test")
+    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "rig_gpu_test.cpp"), "-o", exe,
+                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    got = re.search(r"frame ([0-9a-f]{16}) vertices ([0-9a-f]{16})", res.stdout)
+    assert got and res.stdout.rstrip().endswith("ok"), res.stdout
+
+    def fnv1a(b):
+        h = 1469598103934665603
+        for x in b:
+            h = ((h ^ x) * 1099511628211) & 0xffffffffffffffff
+        return "%016x" % h
+
+    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
+    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
+    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
+    model = scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 2, 0.5), red)])
+    cam = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
+    size = (160, 96)
+    r = make_gpu(model, scenes.ambient_probe(160, 96, 2.5), cam, size, cfg_foveated(12, 36, (1, 2, 8)))
+    v = model.meshes[1].vertex
+    up = v[:, 1] > 0.5
+    j, w = np.zeros((len(v), 4), np.uint16), np.zeros((len(v), 4), F)
+    j[up, 1] = 1
+    w[up, 0], w[up, 1], w[~up, 0] = 0.25, 0.75, 1.0
+    rig = rg.empty_rig(3)
+    rig["parent"] = np.array([-1, 0, -1], np.int32)
+    rig["translation"] = F([[0, -0.5, 0], [0, 2, 0], [0, 0, 0]])
+    rig["bindings"] = [dict(mesh=1, joint_nodes=np.array([0, 1], np.uint16), inverse_bind=F([[1, 0, 0, 0, 0, 1, 0, 0.5, 0, 0, 1, 0], [1, 0, 0, 0, 0, 1, 0, -1.5, 0, 0, 1, 0]]).reshape(2, 3, 4)),
+                       dict(mesh=0, node=2)]
+    rig["clips"] = [[rg.channel(1, rg.ROTATION, [0.0, 1.0], [[0, 0, 0, 1], [0, 0, 0.5, 0.8660254]]), rg.channel(0, rg.SCALE, [0.0, 2.0], [[1, 1, 1], [1.5, 1, 0.5]]),
+                     rg.channel(2, rg.TRANSLATION, [0.0, 1.0], [[0, 0, 0], [0, -0.25, 0]], rg.STEP)]]
+    skins = {1: (j, w)}
+    r.set_skins(skins)
+    r.set_rig(rig)
+    r.update_animated(0, 0.75)
+    _, px, _ = render(r)
+    verts = scene_vertices(r)
+    assert np.array_equal(bits(verts), bits(all_vertices(model, rg.restate(oracle, model, rig, 0, 0.75, skins))))
+    assert (fnv1a(px.tobytes()), fnv1a(verts.tobytes())) == got.groups()
+    r.close()

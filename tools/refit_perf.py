@@ -23,7 +23,13 @@ time on the library's stream; the median over the rounds and every round).
 not zero; the mix is recorded in the output.  On one context, --rounds rounds of three updates to the same positions in turn:
 update_morphed with host weights, update_vertices with device pointers to the positions morphed beforehand, update_vertices with
 the same positions as host arrays.  Then every mesh gets --skin's skin as well, and update_morphed with weights and matrices
-alternates with update_skinned of the same matrices."""
+alternates with update_skinned of the same matrices.
+
+--rig: fovpt_update_animated instead.  Every mesh gets --skin's skin and is bound to a rig of 1024 nodes (8 levels, a rotation
+channel of four keys on every node, one clip).  On one context, --rounds rounds of three updates to the same positions in turn:
+update_animated, update_skinned with host palettes computed beforehand (rig_ref.pose), update_vertices with device pointers.
+Then, on a scene of a few vertices, k_rig_pose by itself for 64 and 1024 nodes, flat and as one chain: what update_animated
+takes beyond update_skinned with a device palette, which issues the same launches but for k_rig_pose."""
 import argparse
 import ctypes as C
 import json
@@ -310,6 +316,79 @@ def run_morph(name, calls, warmup, rounds, dense, sparse, fraction, active):
     print(json.dumps(out), flush=True)
 
 
+def run_rig(name, calls, warmup, rounds):
+    """--rig: see the module docstring."""
+    import rig_ref as rg
+    import skin_ref as sk
+    from oracle import oracle_py as orc
+    orc.build()
+    orc.set_math_mode(True)
+    model, r = make_renderer(name)
+    st0 = r.stats()
+    rng = np.random.default_rng(11)
+    n = rg.MAX_NODES
+    rig = rg.random_rig(rng, n, max_depth=8, scales=False, clip_channels=0.0)
+    for i in range(n):                                                    # a rotation channel of four keys on every node: small turns
+        rig["translation"][i] *= np.float32(0.02)
+        base = rig["rotation"][i].astype(np.float64)
+        keys = [base]
+        for _ in range(3):
+            x1, y1, z1, w1 = keys[-1]
+            x2, y2, z2, w2 = rg.quat(rng.standard_normal(3), 3.0).astype(np.float64)
+            keys.append(np.array([w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2,
+                                  w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2, w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2]))
+        rig["clips"][0].append(rg.channel(i, rg.ROTATION, [0.0, 1.0, 2.0, 3.0], np.stack(keys)))
+    skins = {k: sk.bend(m.vertex, 2 + (7 * k) % 63) for k, m in enumerate(model.meshes)}
+    for k in skins:
+        nodes = ((37 * k + np.arange(skins[k][2])) % n).astype(np.uint16)
+        rig["bindings"].append(dict(mesh=k, joint_nodes=nodes, inverse_bind=rg.inverse_bind_of(rig, nodes)))
+    r.set_skins(skins)
+    t = time.perf_counter()
+    r.set_rig(rig)
+    set_rig_ms = (time.perf_counter() - t) * 1e3
+    T = 1.4
+    pals = dict(zip(sorted(skins), rg.pose(orc, rig, 0, T)["palettes"]))   # the host's animation system, beforehand
+    host = sk.restate(model, skins, pals)
+    dev = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+    torch.cuda.synchronize()
+    out = dict(scene=name, triangles=model.num_triangles, meshes=len(model.meshes), bvh_nodes=int(st0.num_bvh_nodes),
+               vertices=int(sum(m.vertex.shape[0] for m in model.meshes)), joints=int(sum(s[2] for s in skins.values())),
+               rig_nodes=n, rig_levels=int(max(_levels(rig["parent"]))), rounds=rounds, calls=calls, set_rig_host_ms=round(set_rig_ms, 3))
+    alternate(r, dict(update_animated=lambda: r.update_animated(0, T), update_skinned=lambda: r.update_skinned(pals),
+                      update_vertices_device=lambda: r.update_vertices(dev)), calls, warmup, rounds, out)
+    p, nb = C.c_void_p(), C.c_size_t()
+    r._check(r._L.fovpt_debug_buffer(r._ctx, b"scene_vertices", C.byref(p), C.byref(nb)))
+    r.update_animated(0, T)
+    got = r.download(p.value, np.empty(nb.value // 4, np.uint32))
+    out["positions_match_restatement"] = bool(np.array_equal(got, np.concatenate([host[k] for k in range(len(model.meshes))]).view(np.uint32).reshape(-1)))
+    r.close()
+    print(json.dumps(out), flush=True)
+    # k_rig_pose by itself: a scene of a few vertices, one joint; what update_animated takes beyond update_skinned with a device
+    # palette (the same launches but for k_rig_pose) on the same context, in turn
+    small = scenes.cornell_box()
+    for nodes in (64, 1024):
+        for shape, make in (("flat", rg.flat_rig), ("chain", rg.chain_rig)):
+            q = renderer.SampleRenderer(small)
+            q.set_skins({4: sk.bend(small.meshes[4].vertex, 1)})
+            g = make(nodes)
+            g["bindings"] = [dict(mesh=4, joint_nodes=np.array([nodes - 1], np.uint16), inverse_bind=np.eye(3, 4, dtype=np.float32)[None])]
+            q.set_rig(g)
+            pal = {4: torch.from_numpy(np.eye(3, 4, dtype=np.float32)[None].copy()).cuda()}
+            torch.cuda.synchronize()
+            o = dict(scene="cornell", rig_nodes=nodes, rig_shape=shape, rig_levels=1 if shape == "flat" else nodes, rounds=rounds, calls=calls)
+            alternate(q, dict(update_animated=lambda: q.update_animated(0, 0.625), update_skinned_device=lambda: q.update_skinned(pal)), calls, warmup, rounds, o)
+            o["k_rig_pose_ms"] = round(o["update_animated_ms"] - o["update_skinned_device_ms"], 4)
+            q.close()
+            print(json.dumps(o), flush=True)
+
+
+def _levels(parent):
+    lv = []
+    for p in parent:
+        lv.append(1 if p < 0 else lv[int(p)] + 1)
+    return lv
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c3,street")
@@ -319,14 +398,17 @@ def main():
     ap.add_argument("--transforms", action="store_true", help="fovpt_update_transforms and fovpt_hierarchy_cost instead of fovpt_update_vertices")
     ap.add_argument("--skin", action="store_true", help="fovpt_update_skinned against fovpt_update_vertices with device pointers and with host arrays")
     ap.add_argument("--morph", action="store_true", help="fovpt_update_morphed against fovpt_update_vertices with device pointers and with host arrays, and with matrices against fovpt_update_skinned")
+    ap.add_argument("--rig", action="store_true", help="fovpt_update_animated against fovpt_update_skinned with host palettes and fovpt_update_vertices with device pointers, and k_rig_pose by itself")
     ap.add_argument("--morph-dense", type=int, default=8)
     ap.add_argument("--morph-sparse", type=int, default=44)
     ap.add_argument("--morph-fraction", type=float, default=0.05)
     ap.add_argument("--morph-active", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5, help="--transforms, --skin, --morph: rounds of the alternated timings (at least 5)")
+    ap.add_argument("--rounds", type=int, default=5, help="--transforms, --skin, --morph, --rig: rounds of the alternated timings (at least 5)")
     a = ap.parse_args()
     for s in a.scenes.split(","):
-        if a.morph:
+        if a.rig:
+            run_rig(s, a.calls, a.warmup, max(5, a.rounds))
+        elif a.morph:
             run_morph(s, a.calls, a.warmup, max(5, a.rounds), a.morph_dense, a.morph_sparse, a.morph_fraction, a.morph_active)
         elif a.skin:
             run_skin(s, a.calls, a.warmup, max(5, a.rounds))
