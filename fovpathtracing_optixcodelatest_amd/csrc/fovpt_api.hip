@@ -4,7 +4,7 @@
 // (PT_sv5_/SimplePathtracer.cpp:331-340).  Calls on a context are not thread-safe.
 //
 // Animated geometry is in api_animate.hip, the post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip, the
-// frame packets in api_packet.hip; fovpt_ctx.h is what they share.
+// frame packets in api_packet.hip, the test hooks (fovpt_debug_*) in api_debug.hip; fovpt_ctx.h is what they share.
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -147,6 +147,8 @@ void free_scene(fovpt_ctx* c)
     drop_animation(c);                              // what the update calls keep of it (api_animate.hip)
 }
 
+}  // namespace
+
 // A queue shard receives the appends of the blocks whose index is congruent to it modulo FOVPT_SHARDS.  The
 // producing kernels walk their index space in 256-wide block iterations m = 0, 1, 2, ... with a grid that is
 // a multiple of FOVPT_SHARDS, so shard s gets the iterations m = s (mod 8): at most ceil(M / 8) + 1 of them,
@@ -180,15 +182,19 @@ int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipSt
     return FOVPT_OK;
 }
 
-// What the kernels see of a state set: its path state (the guide pointers null: run_job sets them under write_guides) ...
+// What the kernels see of a state set: its path state (the guide pointers null unless write_guides is on: ensure_state's rule) ...
 PathState path_state(const fovpt_ctx* c, const StateSet& S)
 {
     PathState ps;
     memset(&ps, 0, sizeof(ps));
     ps.thr = (float4*)S.s_thr.p; ps.rng = (uint4*)S.s_rng.p; ps.hit = (float4*)S.s_hit.p; ps.rad = (float4*)S.s_rad.p;
     ps.stride = (size_t)c->cfg.max_depth; ps.alpha = (float4*)S.s_alpha.p; ps.backplate = (float4*)S.s_backplate.p;
+    if (c->cfg.write_guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
     return ps;
 }
+
+// ... its k-th radiance-ray queue ...
+RayQueue ray_queue(const StateSet& S, int k) { return RayQueue{(float4*)S.q_o[k].p, (float4*)S.q_d[k].p}; }
 
 // ... and its k-th shadow queue
 ShadowQueue shadow_queue(const StateSet& S, int k)
@@ -198,12 +204,11 @@ ShadowQueue shadow_queue(const StateSet& S, int k)
     return sq;
 }
 
-int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame);
+static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame);
 
 // The two chains of a job that run_job splits (chains_per_frame = 2): chain k takes the sample slots [slot_begin, slot_end) -- the
 // first chain a whole number of 256-slot block iterations, the second the rest -- through the queue shards of sel = k + 1.  One
-// function for run_job and for fovpt_debug_generate, so that a test runs the chains a job would issue.
-struct ChainSplit { uint32_t sel, slot_begin, slot_end; };
+// function for run_job and for the generate hook of api_debug.hip, so that a test runs the chains a job would issue.
 ChainSplit chain_split(uint64_t slots, int k)
 {
     const uint32_t half = (uint32_t)(slots / 2 / FOVPT_BLOCK * FOVPT_BLOCK);
@@ -219,13 +224,11 @@ ChainSplit chain_split(uint64_t slots, int k)
 // cleared on the ranks other than 0 (rank 0 keeps them, as the reference's frame buffer keeps what no launch
 // overwrites): the sum over the ranks is then the single-GPU frame.  A single fovpt_launch leaves them alone on
 // every rank -- it may be one of several launches that make up the caller's frame.
-int run_passes(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int whole_frame)
+static int run_passes(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int whole_frame)
 {
     if (!c->has_scene || lp->traversable != c->scene_id) return fail(c, FOVPT_E_NO_SCENE, "launch without a scene (traversable %llu, current %llu)",
                                                                      (unsigned long long)lp->traversable, (unsigned long long)c->scene_id);
-    if (!lp->probe.data || !lp->probe.cdfValuesX || !lp->probe.cdfValuesY || !lp->probe.pdfValuesX || !lp->probe.pdfValuesY
-        || lp->probe.width <= 0 || lp->probe.height <= 0)
-        return fail(c, FOVPT_E_NO_PROBE, "launch with an incomplete probe");
+    if (!probe_complete(lp->probe)) return fail(c, FOVPT_E_NO_PROBE, "launch with an incomplete probe");
     if (!lp->frame.accum_buffer || !lp->frame.frame_buffer) return fail(c, FOVPT_E_NO_FRAME, "launch with null frame buffers");
     if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
     if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
@@ -287,7 +290,6 @@ int run_passes(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passe
 
 // How a launch searches and reads the caller's probe: the guide tables, the packed records and the one-row layout belong to the
 // probe this context uploaded.  One function for run_job and for the debug entry points, so that a test sees the path a frame takes.
-struct ProbePath { const uint32_t *guide_x, *guide_y; const float4* rec; int32_t row_mul; };
 ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe)
 {
     ProbePath pp;
@@ -306,7 +308,7 @@ ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe)
 
 // What the kernels see of a frame: the passes (with their places in the job's sample slots and launch records), the camera, the
 // probe and how it is searched, the caller's frame buffers and the configuration.  One function for run_job and for
-// fovpt_debug_resolve, so that the test hook resolves the frame a job of the same parameters would.
+// the resolve and generate hooks of api_debug.hip, so that a test hook runs the frame a job of the same parameters would.
 int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame, FrameDev& fd,
               uint64_t& slots, uint64_t& launches)
 {
@@ -348,7 +350,7 @@ int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes
 }
 
 // One wavefront job: generate -> (closest, shade, occlusion) x depth -> resolve over the given passes / row ranges.
-int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame)
+static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame)
 {
     FrameDev fd;
     uint64_t slots = 0, launches = 0;
@@ -396,8 +398,7 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     c->last_set = set_index;
     S.used = true;
 
-    PathState ps = path_state(c, S);
-    if (c->cfg.write_guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
+    const PathState ps = path_state(c, S);
     ShadowQueue sq[FOVPT_NSQ];
     for (int k = 0; k < FOVPT_NSQ; k++) sq[k] = shadow_queue(S, k);
     const SceneView sc = scene_view(c);
@@ -432,9 +433,7 @@ int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_i
     // One chain: the sample slots [slot_begin, slot_end) through the queue shards of `sel` (0: all eight; 1 / 2: one half), with
     // 1 / div of the usual grids.
     auto issue_chain = [&](hipStream_t st, hipStream_t ss, uint32_t sel, uint32_t slot_begin, uint32_t slot_end, int div, const ChainEvents& ev) -> int {
-        RayQueue qa, qb;
-        qa.o = (float4*)S.q_o[0].p; qa.d = (float4*)S.q_d[0].p;
-        qb.o = (float4*)S.q_o[1].p; qb.d = (float4*)S.q_d[1].p;
+        RayQueue qa = ray_queue(S, 0), qb = ray_queue(S, 1);
         const int g_gen = c->grid / div, g_trace = c->grid_trace / div, g_shadow = c->grid_shadow / div, g_shade = c->grid_shade / div;
         { Timed t(c, T_GENERATE, st); (void)fovpt_launch_generate(st, fd, ps, qa, cap, cnt, slot_begin, slot_end, g_gen, sel); }
         { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, sc, ps, qa, sq[0], cap, cnt, 0, -1, g_trace, nullptr, sel); }
@@ -540,8 +539,6 @@ int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P)
     P[2] = pass_from_lp(&L, (uint32_t)(L.frame.r_outer * 2), (uint32_t)(L.frame.r_outer * 2));
     return 3;
 }
-
-}  // namespace
 
 // The hierarchy over d_flat (9 floats per triangle) on stream st, as fovpt_set_scene builds it: FOVPT_BVH, FOVPT_SPLIT, and a
 // second build without reinsertion when reinsertion made the tree too deep; *ms = its device time.  On success br holds the
@@ -1179,563 +1176,6 @@ int fovpt_camera_uvw(const fovpt_float3* eye, const fovpt_float3* lookat, const 
     const float ulen = vlen * aspect;
     ux *= ulen; uy *= ulen; uz *= ulen;
     U->x = ux; U->y = uy; U->z = uz; V->x = vx; V->y = vy; V->z = vz; W->x = wx; W->y = wy; W->z = wz;
-    return FOVPT_OK;
-}
-
-// test/diagnostic hook: device address and size of an internal buffer
-int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes)
-{
-    if (!c || !name || !ptr || !bytes) return FOVPT_E_INVALID;
-    if (strcmp(name, "bvh_nodes") == 0 && c->has_scene) { *ptr = c->nodes; *bytes = (size_t)c->stats.bvh_bytes; return FOVPT_OK; }   // tools/bvhstat.py
-    if (strcmp(name, "bvh_tris") == 0 && c->has_scene) { *ptr = c->tris; *bytes = (size_t)c->stats.tri_bytes; return FOVPT_OK; }
-    if (strcmp(name, "scene_vertices") == 0 && c->up_vtx.p) { *ptr = c->up_vtx.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_update_vertices
-    if (strcmp(name, "scene_vertices_prev") == 0 && c->vtx_prev.p) { *ptr = c->vtx_prev.p; *bytes = c->h_vtx.size() * 4; return FOVPT_OK; }   // fovpt_temporal_motion
-    if (strcmp(name, "rig_world") == 0 && c->rig.set) { *ptr = c->rig.dev.world; *bytes = 48 * (size_t)c->rig.dev.num_nodes; return FOVPT_OK; }   // what k_rig_pose last wrote
-    if (strcmp(name, "rig_rigid") == 0 && c->rig.set) { *ptr = c->rig.dev.rigid; *bytes = 48 * (size_t)c->rig.dev.num_rigid; return FOVPT_OK; }
-    if (strcmp(name, "rig_palette") == 0 && c->rig.set) { *ptr = c->rig.dev.palette; *bytes = 48 * (size_t)c->rig.dev.num_pal; return FOVPT_OK; }
-    if (strcmp(name, "post_color") == 0 && c->po_color.p) { *ptr = c->po_color.p; *bytes = c->po_color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
-    if (strcmp(name, "expose_histogram") == 0 && c->ex_hist.p) { *ptr = c->ex_hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
-    if (strcmp(name, "expose_state") == 0 && c->ex_state.p) { *ptr = c->ex_state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
-    if (strcmp(name, "warp_keys") == 0 && c->wp_keys.p) { *ptr = c->wp_keys.p; *bytes = c->wp_keys.bytes; return FOVPT_OK; }   // fovpt_warp's keys, once made
-    if (strcmp(name, "focus_state") == 0 && c->fc_state.p) { *ptr = c->fc_state.p; *bytes = sizeof(FocusState); return FOVPT_OK; }   // fovpt_focus's state record
-    if (strcmp(name, "focus_scratch") == 0 && c->fc_rt.p) { *ptr = c->fc_rt.p; *bytes = c->fc_rt.bytes; return FOVPT_OK; }   // and its (r, tp) pairs, once made
-    if (strcmp(name, "gbuffer_hit") == 0 && c->gb_hit.p) { *ptr = c->gb_hit.p; *bytes = c->gb_pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
-    StateSet& S = c->set[c->last_set];                    // the set the most recent job used
-    struct { const char* n; DevBuf* b; } tab[] = {
-        {"sq_o", &S.sq_o[0]}, {"sq_d", &S.sq_d[0]}, {"sq_vis", &S.sq_vis[0]}, {"sq_occ", &S.sq_occ[0]}, {"counters", &S.counters},
-        {"hit", &S.s_hit}, {"queue_a_o", &S.q_o[0]}, {"queue_a_d", &S.q_d[0]}, {"queue_b_o", &S.q_o[1]}, {"queue_b_d", &S.q_d[1]},
-    };
-    for (auto& t : tab)
-        if (strcmp(t.n, name) == 0) { *ptr = t.b->p; *bytes = t.b->bytes; return FOVPT_OK; }
-    return fail(c, FOVPT_E_INVALID, "unknown debug buffer %s", name);
-}
-
-// test hook: the PRODUCTION traversal kernel on a caller-supplied batch of rays -- closest hit (global primitive id, t, u, v)
-// and the occlusion predicate of the shadow rays (any front-facing candidate in (0.01, 1e16), deviceProgram.cu:224-248,
-// 284-300) -- so that optixTrace's two ray types can be compared with the oracle ray by ray, not only through frames.
-int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* dirs3, uint32_t* prim_out, float* tuv_out3, uint8_t* occluded_out)
-{
-    if (!c || n < 0 || (n && (!origins3 || !dirs3))) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_trace without a scene");
-    if (n == 0) return FOVPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    StateSet& S = c->set[(c->last_set + 1u) % 2u];                  // (the device is idle: any set will do)
-    const size_t slots = (size_t)n * FOVPT_SHARDS;                  // all rays go to shard 0: its capacity must hold them
-    int rc = ensure_state(c, S, slots, 1, c->stream);
-    if (rc) return rc;
-    const uint32_t cap = shard_capacity(slots);
-    hipStream_t st = c->stream;
-    std::vector<float> o4((size_t)n * 4), d4((size_t)n * 4), d4s((size_t)n * 4), vis((size_t)n * 4, 0.f), occ((size_t)n * 4, 0.f);
-    for (int i = 0; i < n; i++) {
-        const uint32_t slot = (uint32_t)i, cell = 0u;
-        for (int k = 0; k < 3; k++) { o4[4 * (size_t)i + k] = origins3[3 * (size_t)i + k]; d4[4 * (size_t)i + k] = d4s[4 * (size_t)i + k] = dirs3[3 * (size_t)i + k]; }
-        memcpy(&o4[4 * (size_t)i + 3], &slot, 4);                   // origin.w = sample slot
-        d4[4 * (size_t)i + 3] = 0.f;
-        memcpy(&d4s[4 * (size_t)i + 3], &cell, 4);                  // shadow record: direction.w = target cell of the slot
-        vis[4 * (size_t)i] = 1.f; occ[4 * (size_t)i] = 2.f;         // what store_shadow leaves in the cell: 1 visible, 2 occluded
-    }
-    const size_t bytes = (size_t)n * 16;
-    HIPCHK(c, hipMemcpyAsync(S.q_o[0].p, o4.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.q_d[0].p, d4.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_o[0].p, o4.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_d[0].p, d4s.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_vis[0].p, vis.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_occ[0].p, occ.data(), bytes, hipMemcpyHostToDevice, st));
-    // queue sizes: n entries in shard 0 of the radiance queue of iteration 0 and of the shadow queue of iteration 0
-    HIPCHK(c, hipMemsetAsync(S.counters.p, 0, offsetof(Counters, stat_radiance), st));
-    const uint32_t un = (uint32_t)n;
-    Counters* cnt = (Counters*)S.counters.p;
-    HIPCHK(c, hipMemcpyAsync(&cnt->shard[0][FOVPT_CNT_Q(0)], &un, 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(&cnt->shard[0][FOVPT_CNT_SQ(0)], &un, 4, hipMemcpyHostToDevice, st));
-    const PathState ps = path_state(c, S);
-    RayQueue q; q.o = (float4*)S.q_o[0].p; q.d = (float4*)S.q_d[0].p;
-    const ShadowQueue sq = shadow_queue(S, 0);
-    const SceneView sc = scene_view(c);
-    fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, 0, -1, c->grid_trace);        // closest hit, as run_job launches it
-    fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, -1, 0, c->grid_shadow);       // occlusion, as run_job launches it
-    HIPCHK(c, hipGetLastError());
-    std::vector<float> hit((size_t)n * 4), cell((size_t)n * 4 * (size_t)c->cfg.max_depth);
-    HIPCHK(c, hipMemcpyAsync(hit.data(), S.s_hit.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(cell.data(), S.s_rad.p, bytes * (size_t)c->cfg.max_depth, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    std::vector<TriRec> tris(c->num_tris);                           // leaf order -> global primitive id
-    HIPCHK(c, hipMemcpy(tris.data(), c->tris, sizeof(TriRec) * (size_t)c->num_tris, hipMemcpyDeviceToHost));
-    // leave the set as a job expects to find it (resolve zeroes the queue counters at the end of every job)
-    HIPCHK(c, hipMemset(S.counters.p, 0, offsetof(Counters, stat_radiance)));
-    for (int i = 0; i < n; i++) {
-        uint32_t pos;
-        memcpy(&pos, &hit[4 * (size_t)i + 3], 4);
-        const bool miss = pos == 0xffffffffu;
-        const size_t tri = miss ? 0 : (size_t)pos / 3;               // pos: offset in 16-byte units, a record is 48 bytes
-        if (!miss && (pos % 3u != 0u || tri >= tris.size())) return fail(c, FOVPT_E_DEVICE, "hit record %d points at 16-byte unit %u", i, pos);
-        if (prim_out) prim_out[i] = miss ? 0xffffffffu : tris[tri].prim;
-        if (tuv_out3) for (int k = 0; k < 3; k++) tuv_out3[3 * (size_t)i + k] = hit[4 * (size_t)i + k];
-        if (occluded_out) {
-            const float v = cell[4 * (size_t)i * (size_t)c->cfg.max_depth];
-            if (v != 1.f && v != 2.f) return fail(c, FOVPT_E_DEVICE, "shadow ray %d left %g in its cell", i, (double)v);
-            occluded_out[i] = v == 2.f ? 1 : 0;
-        }
-    }
-    return FOVPT_OK;
-}
-
-// test hook: the PRODUCTION shading kernel on caller-made hits -- one launch of fovpt_launch_shade (k_shade<false> or <true> by the
-// configured options, as run_job launches it) over an input queue the caller laid out, and everything the kernel left: the slots'
-// state, the counters and the occupied entries of the next radiance queue and of the shadow queue.  Every buffer the kernel may
-// write is filled with the byte FOVPT_DEBUG_SHADE_FILL first, so that "not written" can be told from "written with zero".
-int fovpt_debug_shade(fovpt_ctx* c, const fovpt_probe* probe, const fovpt_debug_shade_launch* in, const float* origin3, const float* dir4,
-                      const uint32_t* prim, const float* tuv3, const uint32_t* rng3, const float* thr4, fovpt_debug_shade_result* out)
-{
-    if (!c || !probe || !in || !out || in->n < 0 || (in->n && (!origin3 || !dir4 || !prim || !tuv3 || !rng3 || !thr4))) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_shade without a scene");
-    if (!probe->data || !probe->cdfValuesX || !probe->cdfValuesY || !probe->pdfValuesX || !probe->pdfValuesY || probe->width <= 0 || probe->height <= 0)
-        return fail(c, FOVPT_E_NO_PROBE, "fovpt_debug_shade with an incomplete probe");
-    const int n = in->n;
-    if (in->sel > 2u || in->grid < 1 || in->grid > 4096 || in->depth_iter < 0 || in->depth_iter + 1 >= FOVPT_MAX_ITERS)
-        return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: sel %u, grid %d, depth_iter %d", in->sel, in->grid, in->depth_iter);
-    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
-    if (c->cfg.write_guides && c->any_catcher) return fail(c, FOVPT_E_INVALID, "write_guides is not available with shadow-catcher materials");
-    uint64_t total = 0;
-    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
-        const bool selected = in->sel == 0u || (in->sel == 1u) == (s < 4u);
-        if (in->shard_count[s] && !selected) return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: input in shard %u outside the selection %u", s, in->sel);
-        total += in->shard_count[s];
-    }
-    if (total != (uint64_t)n) return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: the shards hold %llu inputs, n = %d", (unsigned long long)total, n);
-    const size_t D = (size_t)c->cfg.max_depth, un = (size_t)n;
-    const bool guides = c->cfg.write_guides != 0;
-    if (n && (!out->rng4 || !out->thr4 || !out->rad4 || !out->alpha4 || (guides && (!out->guide_n4 || !out->guide_a4)) || !out->next_place2
-              || !out->next_o4 || !out->next_d4 || !out->shadow_place2 || !out->shadow_o4 || !out->shadow_d4 || !out->shadow_vis4 || !out->shadow_occ4))
-        return FOVPT_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    StateSet& S = c->set[(c->last_set + 1u) % 2u];                  // (the device is idle: any set will do)
-    const size_t slots = (un ? un : 1u) * FOVPT_SHARDS;             // any one shard can hold everything
-    hipStream_t st = c->stream;
-    { const int rc_ = ensure_state(c, S, slots, 1, st); if (rc_) return rc_; }
-    const uint32_t cap = shard_capacity(slots);
-    const size_t qn = (size_t)cap * FOVPT_SHARDS, v = 16;
-    // leaf-order record of a primitive: the first one when spatial splits made several (the inverse of fovpt_debug_trace's map)
-    std::vector<TriRec> tris(c->num_tris);
-    HIPCHK(c, hipMemcpy(tris.data(), c->tris, sizeof(TriRec) * (size_t)c->num_tris, hipMemcpyDeviceToHost));
-    uint32_t nprim = 0;
-    for (const TriRec& T : tris) nprim = T.prim + 1u > nprim ? T.prim + 1u : nprim;
-    std::vector<uint32_t> first(nprim, 0xffffffffu);
-    for (size_t k = tris.size(); k-- > 0;) first[tris[k].prim] = (uint32_t)k;
-    // the input queue: shard s holds the next shard_count[s] hits, in order; slot of hit i = i
-    std::vector<float> qo(qn * 4, 0.f), qd(qn * 4, 0.f), hit(qn * 4, 0.f);
-    std::vector<uint32_t> rng(un * 4, 0u);
-    size_t i = 0;
-    for (uint32_t s = 0; s < FOVPT_SHARDS; s++)
-        for (uint32_t k = 0; k < in->shard_count[s]; k++, i++) {
-            const size_t ph = (size_t)s * cap + k;
-            const uint32_t slot = (uint32_t)i;
-            for (int a = 0; a < 3; a++) { qo[4 * ph + a] = origin3[3 * i + a]; hit[4 * ph + a] = tuv3[3 * i + a]; }
-            memcpy(&qo[4 * ph + 3], &slot, 4);
-            for (int a = 0; a < 4; a++) qd[4 * ph + a] = dir4[4 * i + a];
-            uint32_t tpos = 0xffffffffu;
-            if (prim[i] != 0xffffffffu) {
-                if (prim[i] >= nprim || first[prim[i]] == 0xffffffffu) return fail(c, FOVPT_E_INVALID, "fovpt_debug_shade: hit %zu names primitive %u", i, prim[i]);
-                tpos = first[prim[i]] * 3u;                                   // offset in 16-byte units, a record is 48 bytes
-            }
-            memcpy(&hit[4 * ph + 3], &tpos, 4);
-            rng[4 * i] = rng3[3 * i]; rng[4 * i + 1] = rng3[3 * i + 1]; rng[4 * i + 2] = rng3[3 * i + 2]; rng[4 * i + 3] = 0u;
-        }
-    const int fill = FOVPT_DEBUG_SHADE_FILL;
-    HIPCHK(c, hipMemcpyAsync(S.q_o[0].p, qo.data(), qn * v, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.q_d[0].p, qd.data(), qn * v, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.s_hit.p, hit.data(), qn * v, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(S.s_rng.p, fill, slots * v, st));
-    HIPCHK(c, hipMemsetAsync(S.s_thr.p, fill, slots * v, st));
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(S.s_rng.p, rng.data(), un * v, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(S.s_thr.p, thr4, un * v, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(c, hipMemsetAsync(S.s_rad.p, fill, slots * v * D, st));
-    HIPCHK(c, hipMemsetAsync(S.s_alpha.p, fill, slots * v, st));
-    if (guides) { HIPCHK(c, hipMemsetAsync(S.s_guide_n.p, fill, slots * v, st)); HIPCHK(c, hipMemsetAsync(S.s_guide_a.p, fill, slots * v, st)); }
-    HIPCHK(c, hipMemsetAsync(S.q_o[1].p, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(S.q_d[1].p, fill, qn * v, st));
-    HIPCHK(c, hipMemsetAsync(S.sq_o[0].p, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(S.sq_d[0].p, fill, qn * v, st));
-    HIPCHK(c, hipMemsetAsync(S.sq_vis[0].p, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(S.sq_occ[0].p, fill, qn * v, st));
-    const size_t cnt_bytes = offsetof(Counters, stat_radiance);
-    std::vector<uint32_t> cw(cnt_bytes / 4, 0u);
-    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(in->depth_iter)] = in->shard_count[s];
-    HIPCHK(c, hipMemcpyAsync(S.counters.p, cw.data(), cnt_bytes, hipMemcpyHostToDevice, st));
-    // what k_shade reads of a frame: the probe and how it is searched, the depth cap, the options, the partition
-    FrameDev fd;
-    memset(&fd, 0, sizeof(fd));
-    fd.w = fd.h = 1;
-    fd.probe = *probe;
-    const ProbePath pp = probe_path(c, *probe);
-    fd.guide_x = pp.guide_x; fd.guide_y = pp.guide_y; fd.probe_rec = pp.rec; fd.probe_row_mul = pp.row_mul;
-    fd.max_depth = c->cfg.max_depth; fd.options = c->cfg.options; fd.partition = in->partition ? 1 : 0;
-    fd.world = 1; fd.tile_w = 8; fd.tile_h = 4;
-    PathState ps = path_state(c, S);
-    if (guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
-    RayQueue qa, qb;
-    qa.o = (float4*)S.q_o[0].p; qa.d = (float4*)S.q_d[0].p;
-    qb.o = (float4*)S.q_o[1].p; qb.d = (float4*)S.q_d[1].p;
-    fovpt_launch_shade(st, fd, scene_view(c), ps, qa, qb, shadow_queue(S, 0), cap, (Counters*)S.counters.p, in->depth_iter, in->grid, nullptr, in->sel);
-    HIPCHK(c, hipGetLastError());
-    std::vector<uint32_t> nq_o(qn * 4), nq_d(qn * 4), s_o(qn * 4), s_d(qn * 4), s_vis(qn * 4), s_occ(qn * 4);
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(out->rng4, S.s_rng.p, un * v, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->thr4, S.s_thr.p, un * v, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->rad4, S.s_rad.p, un * v * D, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->alpha4, S.s_alpha.p, un * v, hipMemcpyDeviceToHost, st));
-        if (guides) {
-            HIPCHK(c, hipMemcpyAsync(out->guide_n4, S.s_guide_n.p, un * v, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipMemcpyAsync(out->guide_a4, S.s_guide_a.p, un * v, hipMemcpyDeviceToHost, st));
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync(nq_o.data(), S.q_o[1].p, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(nq_d.data(), S.q_d[1].p, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(s_o.data(), S.sq_o[0].p, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(s_d.data(), S.sq_d[0].p, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(s_vis.data(), S.sq_vis[0].p, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(s_occ.data(), S.sq_occ[0].p, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(cw.data(), S.counters.p, cnt_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    // leave the set as a job expects to find it (resolve zeroes the queue counters at the end of every job)
-    HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
-    out->cap = cap;
-    out->counters_changed = 0;
-    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
-        out->next_count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(in->depth_iter + 1)];
-        out->shadow_count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_SQ(in->depth_iter)];
-        for (int w = 0; w < FOVPT_SHARD_STRIDE; w++) {              // every other counter word is as it was
-            const uint32_t was = w == FOVPT_CNT_Q(in->depth_iter) ? in->shard_count[s] : 0u;
-            if (w != FOVPT_CNT_Q(in->depth_iter + 1) && w != FOVPT_CNT_SQ(in->depth_iter) && cw[(size_t)s * FOVPT_SHARD_STRIDE + w] != was) out->counters_changed++;
-        }
-    }
-    // the occupied entries: any word of the entry differs from the fill, in ascending physical order; at most n are handed out
-    const uint32_t fw = 0x01010101u * (uint32_t)fill;
-    auto occupied = [&](const std::vector<uint32_t>& a, size_t e) { return a[4 * e] != fw || a[4 * e + 1] != fw || a[4 * e + 2] != fw || a[4 * e + 3] != fw; };
-    uint32_t nn = 0, ns = 0;
-    for (size_t e = 0; e < qn; e++) {
-        if (occupied(nq_o, e) || occupied(nq_d, e)) {
-            if (nn < (uint32_t)n) {
-                out->next_place2[2 * nn] = (uint32_t)(e / cap); out->next_place2[2 * nn + 1] = (uint32_t)(e % cap);
-                memcpy(out->next_o4 + 4 * (size_t)nn, &nq_o[4 * e], 16); memcpy(out->next_d4 + 4 * (size_t)nn, &nq_d[4 * e], 16);
-            }
-            nn++;
-        }
-        if (occupied(s_o, e) || occupied(s_d, e) || occupied(s_vis, e) || occupied(s_occ, e)) {
-            if (ns < (uint32_t)n) {
-                out->shadow_place2[2 * ns] = (uint32_t)(e / cap); out->shadow_place2[2 * ns + 1] = (uint32_t)(e % cap);
-                memcpy(out->shadow_o4 + 4 * (size_t)ns, &s_o[4 * e], 16); memcpy(out->shadow_d4 + 4 * (size_t)ns, &s_d[4 * e], 16);
-                memcpy(out->shadow_vis4 + 4 * (size_t)ns, &s_vis[4 * e], 16); memcpy(out->shadow_occ4 + 4 * (size_t)ns, &s_occ[4 * e], 16);
-            }
-            ns++;
-        }
-    }
-    out->next_found = nn; out->shadow_found = ns;
-    return FOVPT_OK;
-}
-
-// test hook: the PRODUCTION resolve kernel on a caller-made path state.  The frame is the one a fovpt_launch (render = 0, a
-// width x height grid) or a fovpt_render (render = 1: the passes of frame_passes) of these parameters would resolve -- frame_dev()
-// is shared with run_job -- and the state of every sample slot and launch record is the caller's: what generate, shade and the
-// occlusion launches would have left.  Called with state = NULL it only hands out the pass table, which the caller needs to lay
-// the arrays out.  lp is not changed (a render's subframe_index is not advanced).
-int fovpt_debug_resolve(fovpt_ctx* c, const fovpt_launch_params* lp, int render, uint32_t width, uint32_t height, fovpt_debug_pass* passes_out,
-                        int* npass_out, const uint32_t* state, const float* cells4, const float* alpha4, const float* guide_n4, const float* guide_a4,
-                        const float* backplate4, uint32_t* counters_left_out)
-{
-    if (!c || !lp || !passes_out || !npass_out) return FOVPT_E_INVALID;
-    if (!lp->frame.accum_buffer || !lp->frame.frame_buffer) return fail(c, FOVPT_E_NO_FRAME, "fovpt_debug_resolve with null frame buffers");
-    if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
-    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
-    PassDev P[FOVPT_MAX_PASSES];
-    int npass = 1;
-    if (render) { fovpt_launch_params L = *lp; npass = frame_passes(c->cfg, L, P); }
-    else P[0] = pass_from_lp(lp, width, height);
-    uint64_t all_slots = 0;
-    for (int p = 0; p < npass; p++) {
-        if (P[p].spp == 0) return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
-        P[p].row0 = 0; P[p].row1 = P[p].gh; P[p].frame_pass = (uint32_t)p;                     // as run_passes hands an unchunked frame to run_job
-        all_slots += (uint64_t)P[p].gw * P[p].gh * P[p].spp;
-    }
-    if (all_slots > c->slot_budget) return fail(c, FOVPT_E_INVALID, "fovpt_debug_resolve: %llu sample slots would run as several jobs", (unsigned long long)all_slots);
-    FrameDev fd;
-    uint64_t slots = 0, launches = 0;
-    { const int rc_ = frame_dev(c, lp, P, npass, 0, render ? 1 : 0, fd, slots, launches); if (rc_) return rc_; }
-    *npass_out = npass;
-    for (int p = 0; p < npass; p++) {
-        const PassDev& D = fd.pass[p];
-        passes_out[p].gw = D.gw; passes_out[p].rows = D.row1 - D.row0; passes_out[p].spp = D.spp;
-        passes_out[p].slot_base = D.slot_base; passes_out[p].launch_base = D.launch_base;
-    }
-    if (!state) return FOVPT_OK;
-    if (counters_left_out) *counters_left_out = 0u;
-    if (slots == 0) return FOVPT_OK;                                  // (a job of no sample slots launches nothing)
-    if (!cells4 || !alpha4 || !backplate4 || (c->cfg.write_guides && (!guide_n4 || !guide_a4))) return FOVPT_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    StateSet& S = c->set[(c->last_set + 1u) % 2u];                    // (the device is idle: any set will do)
-    hipStream_t st = c->stream;
-    { const int rc_ = ensure_state(c, S, (size_t)slots, (size_t)launches, st); if (rc_) return rc_; }
-    std::vector<uint32_t> rng((size_t)slots * 4, 0xdeadbeefu);        // the generator's words: nothing in a resolve reads them
-    for (size_t i = 0; i < (size_t)slots; i++) rng[4 * i + 2] = state[i];
-    const size_t v = 16, D = (size_t)c->cfg.max_depth;
-    HIPCHK(c, hipMemcpyAsync(S.s_rng.p, rng.data(), (size_t)slots * v, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.s_rad.p, cells4, (size_t)slots * v * D, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.s_alpha.p, alpha4, (size_t)slots * v, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.s_backplate.p, backplate4, (size_t)launches * v, hipMemcpyHostToDevice, st));
-    PathState ps = path_state(c, S);
-    if (c->cfg.write_guides) {
-        ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p;
-        HIPCHK(c, hipMemcpyAsync(S.s_guide_n.p, guide_n4, (size_t)slots * v, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(S.s_guide_a.p, guide_a4, (size_t)slots * v, hipMemcpyHostToDevice, st));
-    }
-    // the queue sizes a job's launches leave behind, here a pattern: the resolve must leave zeros for the set's next job
-    const size_t cnt_bytes = offsetof(Counters, stat_radiance);
-    HIPCHK(c, hipMemsetAsync(S.counters.p, 0xa5, cnt_bytes, st));
-    fovpt_launch_resolve(st, fd, ps, (Counters*)S.counters.p);       // as run_job launches it
-    HIPCHK(c, hipGetLastError());
-    std::vector<uint32_t> left(cnt_bytes / 4);
-    HIPCHK(c, hipMemcpyAsync(left.data(), S.counters.p, cnt_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    uint32_t nonzero = 0;
-    for (uint32_t w : left) nonzero += w != 0u;
-    if (counters_left_out) *counters_left_out = nonzero;
-    // leave the set as a job expects to find it, whatever the kernel did
-    if (nonzero) HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
-    return FOVPT_OK;
-}
-
-// test hook: the PRODUCTION generate launcher (fovpt_launch_generate: k_generate, or k_generate_owned for a rank of a sharded
-// frame) on the frame a fovpt_launch (render = 0; with row1 > 0 the chunk [row0, row1) of it, as run_passes hands a chunk to
-// run_job) or a fovpt_render (render = 1) of these parameters would run -- frame_dev() is shared with run_job -- and everything
-// the launch left: the generator words, the backplates, the guides, the queue counters and the occupied entries of queue 0.
-// The state is a job's (ensure_state, shard_capacity) except queue 0: the launch gets a scratch queue of 8 * cap + slots + 256
-// entries with the same cap, so that a shard that overflows lands in memory this function owns and shows in the result (the
-// appends of one launch number at most `slots`, and the last shard begins at 7 * cap).  Everything the kernel may write is
-// filled with the byte FOVPT_DEBUG_SHADE_FILL first.  lp is not changed.
-int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_debug_generate_launch* in, fovpt_debug_pass* passes_out,
-                         int* npass_out, fovpt_debug_generate_result* out)
-{
-    if (!c || !lp || !in || !passes_out || !npass_out) return FOVPT_E_INVALID;
-    if (!lp->frame.accum_buffer || !lp->frame.frame_buffer) return fail(c, FOVPT_E_NO_FRAME, "fovpt_debug_generate with null frame buffers");
-    if (!lp->probe.data || !lp->probe.cdfValuesX || !lp->probe.cdfValuesY || !lp->probe.pdfValuesX || !lp->probe.pdfValuesY
-        || lp->probe.width <= 0 || lp->probe.height <= 0)
-        return fail(c, FOVPT_E_NO_PROBE, "fovpt_debug_generate with an incomplete probe");
-    if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
-    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
-    const bool chunk = !in->render && in->row1 > 0u;
-    if (in->render ? (in->row0 || in->row1) : (chunk && (in->row0 >= in->row1 || in->row1 > in->height)))
-        return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: launch rows [%u, %u) of %u", in->row0, in->row1, in->height);
-    PassDev P[FOVPT_MAX_PASSES];
-    int npass = 1;
-    if (in->render) { fovpt_launch_params L = *lp; npass = frame_passes(c->cfg, L, P); }
-    else P[0] = pass_from_lp(lp, in->width, in->height);
-    uint64_t all_slots = 0;
-    for (int p = 0; p < npass; p++) {
-        if (P[p].spp == 0) return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
-        P[p].row0 = 0; P[p].row1 = P[p].gh; P[p].frame_pass = (uint32_t)p;                     // as run_passes hands an unchunked frame to run_job
-        if (chunk) { P[p].row0 = in->row0; P[p].row1 = in->row1; }                             // ... and a chunk of a launch
-        all_slots += (uint64_t)P[p].gw * (P[p].row1 - P[p].row0) * P[p].spp;
-    }
-    if (all_slots > c->slot_budget) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: %llu sample slots would run as several jobs", (unsigned long long)all_slots);
-    FrameDev fd;
-    uint64_t slots = 0, launches = 0;
-    { const int rc_ = frame_dev(c, lp, P, npass, chunk ? 1 : 0, in->render ? 1 : 0, fd, slots, launches); if (rc_) return rc_; }
-    *npass_out = npass;
-    for (int p = 0; p < npass; p++) {
-        const PassDev& D = fd.pass[p];
-        passes_out[p].gw = D.gw; passes_out[p].rows = D.row1 - D.row0; passes_out[p].spp = D.spp;
-        passes_out[p].slot_base = D.slot_base; passes_out[p].launch_base = D.launch_base;
-    }
-    if (!out) return FOVPT_OK;
-    // the launch: what run_job would give a launch of this `sel`, unless the caller says otherwise
-    const uint32_t sel = in->sel;
-    if (sel > 2u) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: sel %u", sel);
-    const int grid = in->grid ? in->grid : (sel ? c->grid / 2 : c->grid);
-    if (grid <= 0 || grid > (1 << 20) || grid % (sel ? FOVPT_SHARDS / 2 : FOVPT_SHARDS))
-        return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: a grid of %d blocks (a positive multiple of %d)", grid, sel ? FOVPT_SHARDS / 2 : FOVPT_SHARDS);
-    uint32_t slot_begin = in->slot_begin, slot_end = in->slot_end;
-    if (slot_begin == 0u && slot_end == 0u) {
-        slot_end = (uint32_t)slots;
-        if (sel) { const ChainSplit cs = chain_split(slots, (int)sel - 1); slot_begin = cs.slot_begin; slot_end = cs.slot_end; }
-    }
-    if (slot_begin > slot_end || (uint64_t)slot_end > slots) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: sample slots [%u, %u) of %llu", slot_begin, slot_end, (unsigned long long)slots);
-    const bool guides = c->cfg.write_guides != 0;
-    out->found = out->counters_changed = 0u; out->kernel = 0u; out->guides = guides ? 1u : 0u;
-    out->cap = shard_capacity((size_t)slots); out->slot_begin = slot_begin; out->slot_end = slot_end; out->grid = (uint32_t)grid;
-    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) out->count[s] = 0u;
-    if (slots == 0) return FOVPT_OK;                                  // (a job of no sample slots launches nothing)
-    if (!out->rng4 || !out->backplate4 || (guides && (!out->guide_n4 || !out->guide_a4)) || !out->place2 || !out->o4 || !out->d4) return FOVPT_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    StateSet& S = c->set[(c->last_set + 1u) % 2u];                    // (the device is idle: any set will do)
-    hipStream_t st = c->stream;
-    { const int rc_ = ensure_state(c, S, (size_t)slots, (size_t)launches, st); if (rc_) return rc_; }
-    const uint32_t cap = shard_capacity((size_t)slots);
-    const size_t v = 16, qn = (size_t)cap * FOVPT_SHARDS + (size_t)slots + 256u;
-    struct Scratch { void *o = nullptr, *d = nullptr; ~Scratch() { if (o) (void)hipFree(o); if (d) (void)hipFree(d); } } scratch;      // freed on every return path
-    HIPCHK(c, hipMalloc(&scratch.o, qn * v)); HIPCHK(c, hipMalloc(&scratch.d, qn * v));
-    const int fill = FOVPT_DEBUG_SHADE_FILL;
-    HIPCHK(c, hipMemsetAsync(S.s_rng.p, fill, (size_t)slots * v, st));
-    HIPCHK(c, hipMemsetAsync(S.s_backplate.p, fill, (size_t)launches * v, st));
-    if (guides) { HIPCHK(c, hipMemsetAsync(S.s_guide_n.p, fill, (size_t)slots * v, st)); HIPCHK(c, hipMemsetAsync(S.s_guide_a.p, fill, (size_t)slots * v, st)); }
-    HIPCHK(c, hipMemsetAsync(scratch.o, fill, qn * v, st)); HIPCHK(c, hipMemsetAsync(scratch.d, fill, qn * v, st));
-    const size_t cnt_bytes = offsetof(Counters, stat_radiance);
-    HIPCHK(c, hipMemsetAsync(S.counters.p, 0, cnt_bytes, st));       // as a job finds them
-    PathState ps = path_state(c, S);
-    if (guides) { ps.guide_n = (float4*)S.s_guide_n.p; ps.guide_a = (float4*)S.s_guide_a.p; }
-    RayQueue q0;
-    q0.o = (float4*)scratch.o; q0.d = (float4*)scratch.d;
-    out->kernel = (uint32_t)fovpt_launch_generate(st, fd, ps, q0, cap, (Counters*)S.counters.p, slot_begin, slot_end, grid, sel);   // as run_job launches it
-    HIPCHK(c, hipGetLastError());
-    std::vector<uint32_t> qo(qn * 4), qd(qn * 4), cw(cnt_bytes / 4);
-    HIPCHK(c, hipMemcpyAsync(out->rng4, S.s_rng.p, (size_t)slots * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(out->backplate4, S.s_backplate.p, (size_t)launches * v, hipMemcpyDeviceToHost, st));
-    if (guides) {
-        HIPCHK(c, hipMemcpyAsync(out->guide_n4, S.s_guide_n.p, (size_t)slots * v, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->guide_a4, S.s_guide_a.p, (size_t)slots * v, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(c, hipMemcpyAsync(qo.data(), scratch.o, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(qd.data(), scratch.d, qn * v, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(cw.data(), S.counters.p, cnt_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    // leave the set as a job expects to find it (resolve zeroes the queue counters at the end of every job)
-    HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
-    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
-        out->count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(0)];
-        for (int w = 0; w < FOVPT_SHARD_STRIDE; w++)
-            if (w != FOVPT_CNT_Q(0) && cw[(size_t)s * FOVPT_SHARD_STRIDE + w] != 0u) out->counters_changed++;
-    }
-    // the occupied entries: any word of the entry differs from the fill, in ascending physical order (an entry of the guard
-    // region behind the eight shards reports a shard of 8 or more); at most `slots` are handed out
-    const uint32_t fw = 0x01010101u * (uint32_t)fill;
-    auto occupied = [&](const std::vector<uint32_t>& a, size_t e) { return a[4 * e] != fw || a[4 * e + 1] != fw || a[4 * e + 2] != fw || a[4 * e + 3] != fw; };
-    uint32_t n = 0;
-    for (size_t e = 0; e < qn; e++)
-        if (occupied(qo, e) || occupied(qd, e)) {
-            if ((uint64_t)n < slots) {
-                out->place2[2 * (size_t)n] = (uint32_t)(e / cap); out->place2[2 * (size_t)n + 1] = (uint32_t)(e % cap);
-                memcpy(out->o4 + 4 * (size_t)n, &qo[4 * e], 16); memcpy(out->d4 + 4 * (size_t)n, &qd[4 * e], 16);
-            }
-            n++;
-        }
-    out->found = n;
-    return FOVPT_OK;
-}
-
-// test hooks: the device functions of a shaded hit on chosen inputs (shade_debug.hip), so that ProbeSample, ProbeEval, the
-// Disney BSDF and tex2D can be compared with the oracle input by input, not only through frames.  The probe entry points take
-// the caller's fovpt_probe the way a launch does and search it the way a launch would (probe_path).
-static int debug_probe_args(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const void* in, const char* who)
-{
-    if (!c || !probe || n < 0 || (flags & ~FOVPT_DEBUG_PROBE_PLAIN) || (n && !in)) return FOVPT_E_INVALID;
-    if (!probe->data || !probe->cdfValuesX || !probe->cdfValuesY || !probe->pdfValuesX || !probe->pdfValuesY || probe->width <= 0 || probe->height <= 0)
-        return fail(c, FOVPT_E_NO_PROBE, "%s with an incomplete probe", who);
-    return FOVPT_OK;
-}
-static ProbePath debug_probe_path(const fovpt_ctx* c, const fovpt_probe& probe, int flags, int* path_out)
-{
-    ProbePath pp = probe_path(c, probe);
-    if (flags & FOVPT_DEBUG_PROBE_PLAIN) { pp.guide_x = pp.guide_y = nullptr; pp.rec = nullptr; pp.row_mul = 1; }
-    if (path_out) *path_out = (pp.guide_x ? FOVPT_PROBE_PATH_GUIDED : 0) | (pp.rec ? FOVPT_PROBE_PATH_RECORDS : 0) | (pp.row_mul == 0 ? FOVPT_PROBE_PATH_ONE_ROW : 0);
-    return pp;
-}
-
-int fovpt_debug_probe_sample(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const float* r12, int32_t* rowcol_out2, float* out7, int* path_out)
-{
-    { const int rc_ = debug_probe_args(c, probe, flags, n, r12, "fovpt_debug_probe_sample"); if (rc_) return rc_; }
-    // Randf's range (maths.h:199-210): what the searches may be handed
-    for (size_t i = 0; i < 2 * (size_t)n; i++)
-        if (!(r12[i] >= 0.0f && r12[i] <= 0.999999f)) return fail(c, FOVPT_E_INVALID, "fovpt_debug_probe_sample: number %zu (%g) is outside [0, 0.999999]", i, (double)r12[i]);
-    const ProbePath pp = debug_probe_path(c, *probe, flags, path_out);
-    if (n == 0) return FOVPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    DevBuf in, rowcol, out;
-    HIPCHK(c, in.reserve((size_t)n * 8)); HIPCHK(c, rowcol.reserve((size_t)n * 8)); HIPCHK(c, out.reserve((size_t)n * 28));
-    HIPCHK(c, hipMemcpy(in.p, r12, (size_t)n * 8, hipMemcpyHostToDevice));
-    fovpt_launch_debug_probe_sample(c->stream, *probe, pp.guide_x, pp.guide_y, pp.rec, pp.row_mul, n, (const float2*)in.p, (int2*)rowcol.p, (float*)out.p);
-    HIPCHK(c, hipGetLastError());
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    if (rowcol_out2) HIPCHK(c, hipMemcpy(rowcol_out2, rowcol.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (out7) HIPCHK(c, hipMemcpy(out7, out.p, (size_t)n * 28, hipMemcpyDeviceToHost));
-    return FOVPT_OK;
-}
-
-int fovpt_debug_probe_eval(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const float* dirs3, float* out6, int* path_out)
-{
-    { const int rc_ = debug_probe_args(c, probe, flags, n, dirs3, "fovpt_debug_probe_eval"); if (rc_) return rc_; }
-    const ProbePath pp = debug_probe_path(c, *probe, flags, path_out);
-    if (n == 0) return FOVPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    DevBuf in, out;
-    HIPCHK(c, in.reserve((size_t)n * 12)); HIPCHK(c, out.reserve((size_t)n * 24));
-    HIPCHK(c, hipMemcpy(in.p, dirs3, (size_t)n * 12, hipMemcpyHostToDevice));
-    fovpt_launch_debug_probe_eval(c->stream, *probe, pp.row_mul, n, (const float*)in.p, (float*)out.p);
-    HIPCHK(c, hipGetLastError());
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    if (out6) HIPCHK(c, hipMemcpy(out6, out.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-    return FOVPT_OK;
-}
-
-int fovpt_debug_bsdf(fovpt_ctx* c, const fovpt_material* material, int n, const float* N3, const float* view3, const float* albedo3, const float* etaI,
-                     const float* etaO, const int32_t* seeds, const float* L_given3, float* out14)
-{
-    if (!c || !material || n < 0 || (n && (!N3 || !view3 || !albedo3 || !etaI || !etaO || !seeds || !L_given3))) return FOVPT_E_INVALID;
-    if (n == 0) return FOVPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    std::vector<float> rows((size_t)n * 16, 0.f), res((size_t)n * 16);
-    for (int i = 0; i < n; i++) {
-        float* r = &rows[16 * (size_t)i];
-        for (int k = 0; k < 3; k++) { r[k] = N3[3 * (size_t)i + k]; r[3 + k] = view3[3 * (size_t)i + k]; r[6 + k] = albedo3[3 * (size_t)i + k]; r[12 + k] = L_given3[3 * (size_t)i + k]; }
-        r[9] = etaI[i]; r[10] = etaO[i];
-        memcpy(&r[11], &seeds[i], 4);
-    }
-    DevBuf in, out;
-    HIPCHK(c, in.reserve((size_t)n * 64)); HIPCHK(c, out.reserve((size_t)n * 64));
-    HIPCHK(c, hipMemcpy(in.p, rows.data(), (size_t)n * 64, hipMemcpyHostToDevice));
-    fovpt_launch_debug_bsdf(c->stream, *material, n, (const float*)in.p, (float*)out.p);
-    HIPCHK(c, hipGetLastError());
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    HIPCHK(c, hipMemcpy(res.data(), out.p, (size_t)n * 64, hipMemcpyDeviceToHost));
-    if (out14) for (int i = 0; i < n; i++) memcpy(out14 + 14 * (size_t)i, &res[16 * (size_t)i], 56);
-    return FOVPT_OK;
-}
-
-int fovpt_debug_tex2d(fovpt_ctx* c, int texture, int n, const float* uv2, float* rgba_out4)
-{
-    if (!c || n < 0 || (n && !uv2)) return FOVPT_E_INVALID;
-    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_tex2d without a scene");
-    if (texture < 0 || (size_t)texture >= c->tex_pixels.size()) return fail(c, FOVPT_E_INVALID, "fovpt_debug_tex2d: texture %d of %zu", texture, c->tex_pixels.size());
-    if (n == 0) return FOVPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    DevBuf in, out;
-    HIPCHK(c, in.reserve((size_t)n * 8)); HIPCHK(c, out.reserve((size_t)n * 16));
-    HIPCHK(c, hipMemcpy(in.p, uv2, (size_t)n * 8, hipMemcpyHostToDevice));
-    fovpt_launch_debug_tex2d(c->stream, (const TexDev*)c->textures.p, texture, n, (const float2*)in.p, (float4*)out.p);
-    HIPCHK(c, hipGetLastError());
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    if (rgba_out4) HIPCHK(c, hipMemcpy(rgba_out4, out.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-    return FOVPT_OK;
-}
-
-int fovpt_debug_math(fovpt_ctx* c, int op, const float* a, const float* b, float* out, size_t n)
-{
-    if (!c || !a || !out) return FOVPT_E_INVALID;
-    if (n == 0) return FOVPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf ba, bb, bo;
-    HIPCHK(c, ba.reserve(n * 4)); HIPCHK(c, bb.reserve(n * 4)); HIPCHK(c, bo.reserve(n * 4));
-    float *da = (float*)ba.p, *db = (float*)bb.p, *dout = (float*)bo.p;
-    HIPCHK(c, hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice));
-    if (b) HIPCHK(c, hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice));
-    else HIPCHK(c, hipMemset(db, 0, n * 4));
-    fovpt_launch_math(c->stream, op, da, db, dout, n);
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
-    HIPCHK(c, hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
     return FOVPT_OK;
 }
 

@@ -1,5 +1,6 @@
-// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_animate.hip, api_post.hip, api_gather.hip, api_packet.hip): the
-// context, the buffers it owns, and the helpers more than one of those files uses.  Host only: no kernel file includes it.
+// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_animate.hip, api_post.hip, api_gather.hip, api_packet.hip,
+// api_debug.hip): the context, the buffers it owns, and the helpers more than one of those files uses.  Host only: no kernel file
+// includes it.
 #pragma once
 #include <string>
 #include <vector>
@@ -240,6 +241,27 @@ int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uin
 void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms);
 int enqueue_cost(fovpt_ctx* c, hipStream_t st, uint64_t update, fovpt_ctx::CostSlot** out);
 int measure_built(fovpt_ctx* c);
+// fovpt_api.hip: the pieces of the frame engine (run_passes / run_job) that the test hooks of api_debug.hip run a launch through.
+// Hidden: the library does not export them.
+#pragma GCC visibility push(hidden)
+struct ProbePath { const uint32_t *guide_x, *guide_y; const float4* rec; int32_t row_mul; };
+struct ChainSplit { uint32_t sel, slot_begin, slot_end; };
+inline bool probe_complete(const fovpt_probe& p)              // what a launch needs of a probe: the texels, the four tables and a size
+{
+    return p.data && p.cdfValuesX && p.cdfValuesY && p.pdfValuesX && p.pdfValuesY && p.width > 0 && p.height > 0;
+}
+uint32_t shard_capacity(size_t slots);                        // entries of one queue shard of a job of `slots` sample slots
+int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipStream_t st);   // S holds a job of that size (st: the stream about to use it)
+PathState path_state(const fovpt_ctx* c, const StateSet& S);  // what the kernels see of a state set: its path state ...
+RayQueue ray_queue(const StateSet& S, int k);                 // ... its k-th radiance-ray queue (0, 1) ...
+ShadowQueue shadow_queue(const StateSet& S, int k);           // ... and its k-th shadow queue (0 .. FOVPT_NSQ - 1)
+ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe);   // how a launch searches and reads the caller's probe
+ChainSplit chain_split(uint64_t slots, int k);                // chain k (0, 1) of a job of two chains: its shards and sample slots
+PassDev pass_from_lp(const fovpt_launch_params* lp, uint32_t gw, uint32_t gh);   // the pass of one fovpt_launch of a gw x gh grid
+int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P);   // the passes of one fovpt_render; sets L's per-pass members
+int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame, FrameDev& fd,
+              uint64_t& slots, uint64_t& launches);           // what the kernels see of a job's frame, and its sample slots and launch records
+#pragma GCC visibility pop
 // api_animate.hip (fovpt_set_scene and the context's destructor drop what the update calls keep of a scene)
 void drop_animation(fovpt_ctx* c);
 // api_post.hip (fovpt_resize keeps the buffers of the post-processing calls at the frame's size)

@@ -169,7 +169,7 @@ def test_a_frames_probe_samples_are_the_entry_points(oracle):
     debug_probe_sample returns for those two numbers, which is also the oracle's ProbeSample for that seed.  This ties the
     seeding, the order of the draws and the probe the launch read to the unit level.  It cannot tell which layout the launch
     searched -- every layout returns the same sample, which is what the tests above hold -- that the launch and the entry
-    point choose the same one is the shared probe_path() of fovpt_api.hip."""
+    point choose the same one is the shared probe_path() of fovpt_api.hip, which the entry points of api_debug.hip call."""
     w = h = 32
     data = scenes.sky_probe(96, 40)
     r = make_gpu(scenes.cornell_box(), data, scenes.CORNELL_CAMERA, (w, h), cfg_uniform(1, 1))
