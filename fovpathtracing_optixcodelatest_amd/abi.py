@@ -482,6 +482,32 @@ class FocusState(C.Structure):
     ]
 
 
+LENS_NEAREST, LENS_BILINEAR, LENS_BICUBIC = 0, 1, 2    # FOVPT_LENS_*
+LENS_ENCODE_DISPLAY, LENS_ENCODE_RESOLVE = 0, 1
+
+
+class LensConfig(C.Structure):
+    """fovpt_lens_config: the filter and the rgba8 encoding, the lens axis and scale in destination NDC, the radial polynomial and
+    its per-channel factors, the lens's clip radius, the map from lens units to source NDC and the border colour (defaults:
+    fovpt_lens_defaults)."""
+    _fields_ = [
+        ("filter", C.c_int32), ("encode", C.c_int32), ("_reserved0", C.c_int32 * 2),
+        ("center", C.c_float * 2), ("scale", C.c_float * 2), ("k", C.c_float * 4), ("chroma", C.c_float * 3), ("clip_r2", C.c_float),
+        ("src_center", C.c_float * 2), ("src_scale", C.c_float * 2), ("border", C.c_float * 4),
+        ("_reserved", C.c_int32 * 8),
+    ]
+
+    def copy(self):
+        m = LensConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(LensConfig))
+        return m
+
+    def as_dict(self):
+        """The public fields; the float arrays as tuples."""
+        get = lambda n: getattr(self, n)
+        return {n: (tuple(get(n)) if isinstance(get(n), C.Array) else get(n)) for n, _ in self._fields_ if not n.startswith("_")}
+
+
 PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS =0x4b505646, 1, 4      # FOVPT_PACKET_*
 PACKET_NEAREST, PACKET_SMOOTH = 0, 1
 
@@ -538,6 +564,7 @@ assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
 assert C.sizeof(WarpCamera) == 48 and C.sizeof(WarpConfig) == 32 and C.sizeof(WarpCounts) == 32
 assert C.sizeof(FocusConfig) == 64 and (FocusConfig.strength.offset, FocusConfig._reserved.offset) == (16, 36)
 assert C.sizeof(FocusState) == 32 and FocusState.count.offset == 16
+assert C.sizeof(LensConfig) == 128 and (LensConfig.k.offset, LensConfig.clip_r2.offset, LensConfig.border.offset, LensConfig._reserved.offset) == (32, 60, 80, 96)
 assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
 assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeader.passes.offset) == (16, 32)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8

@@ -1,6 +1,6 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
 // fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), fovpt_warp
-// (warp.hip), fovpt_focus (focus.hip), and their defaults.
+// (warp.hip), fovpt_focus (focus.hip), fovpt_lens (lens.hip), and their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -921,6 +921,90 @@ int fovpt_focus(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_focus_c
     if (aut) fovpt_launch_focus_meter(st, c->dn_w, a, g.prim, g.pos, state);
     fovpt_launch_focus_radius(st, npix, a, state, g.prim, g.pos, (float2*)c->fc_rt.p, out_coc);
     fovpt_launch_focus_gather(st, c->dn_w, c->dn_h, fc->max_radius, in, (const float2*)c->fc_rt.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- head-mounted display lens pre-distortion (lens.hip; its definition: tests/lens_ref.py) ---------------------------------------
+// (conventions, not measurements: include/fovpt.h)
+int fovpt_lens_defaults(fovpt_lens_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->filter = FOVPT_LENS_BILINEAR;
+    out->encode = FOVPT_LENS_ENCODE_DISPLAY;
+    out->scale[0] = out->scale[1] = 1.0f;
+    out->k[0] = 1.0f; out->k[1] = 0.22f; out->k[2] = 0.24f; out->k[3] = 0.0f;
+    out->chroma[0] = 0.996f; out->chroma[1] = 1.0f; out->chroma[2] = 1.014f;
+    out->clip_r2 = INFINITY;
+    out->src_scale[0] = out->src_scale[1] = 1.0f;
+    out->border[3] = 1.0f;
+    return FOVPT_OK;
+}
+
+int fovpt_lens_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    if (!c || !color || !rgba) return FOVPT_E_INVALID;
+    *color = nullptr; *rgba = nullptr;
+    return own_outputs(c, "fovpt_lens_buffers", c->ln_color, c->ln_rgba, *color, *rgba);
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: one launch of k_lens.
+int fovpt_lens(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_lens_config* lc, const fovpt_warp_camera* to, const fovpt_float4* in_color,
+               fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    const char* who = "fovpt_lens";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !lc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (lc->filter != FOVPT_LENS_NEAREST && lc->filter != FOVPT_LENS_BILINEAR && lc->filter != FOVPT_LENS_BICUBIC)
+        return fail(c, FOVPT_E_INVALID, "%s: unknown filter %d", who, lc->filter);
+    if (lc->encode != FOVPT_LENS_ENCODE_DISPLAY && lc->encode != FOVPT_LENS_ENCODE_RESOLVE) return fail(c, FOVPT_E_INVALID, "%s: unknown encode %d", who, lc->encode);
+    for (int32_t r : lc->_reserved0)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    for (int32_t r : lc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    const float fields[19] = {lc->center[0], lc->center[1], lc->scale[0], lc->scale[1], lc->k[0], lc->k[1], lc->k[2], lc->k[3], lc->chroma[0], lc->chroma[1],
+                              lc->chroma[2], lc->src_center[0], lc->src_center[1], lc->src_scale[0], lc->src_scale[1], lc->border[0], lc->border[1],
+                              lc->border[2], lc->border[3]};
+    for (float v : fields)
+        if (!std::isfinite(v)) return fail(c, FOVPT_E_INVALID, "%s: a non-finite center, scale, k, chroma, src_* or border entry", who);
+    if (!(lc->clip_r2 > 0.0f)) return fail(c, FOVPT_E_INVALID, "%s: clip_r2 %g is not above 0", who, (double)lc->clip_r2);
+    if (to) {
+        const float* cam = &to->eye.x;                                     // eye, U, V, W: 12 floats
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(cam[k])) return fail(c, FOVPT_E_INVALID, "%s: the camera to re-aim at has a non-finite entry", who);
+    }
+    { const int rc_ = check_rendered_frame(c, lp, who, "resample", nullptr); if (rc_) return rc_; }
+    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    if (npix >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
+    LensArgs a;
+    memset(&a, 0, sizeof(a));
+    if (to) {                                                              // H = M [U_to V_to W_to], M of the rendered camera
+        float M[9];
+        if (!camera_inverse(c->dn_frame.U, c->dn_frame.V, c->dn_frame.W, M)) return fail(c, FOVPT_E_INVALID, "%s: the rendered camera is singular", who);
+        const float* B[3] = {&to->U.x, &to->V.x, &to->W.x};               // the columns
+        for (int k = 0; k < 3; k++)
+            for (int j = 0; j < 3; j++)
+                a.H[3 * k + j] = (float)(((double)M[3 * k] * (double)B[j][0] + (double)M[3 * k + 1] * (double)B[j][1]) + (double)M[3 * k + 2] * (double)B[j][2]);
+        a.reaim = 1;
+    }
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc_ = own_outputs(c, who, c->ln_color, c->ln_rgba, out_color, out_rgba); if (rc_) return rc_; }
+    if ((const void*)out_color == (const void*)in || (const void*)out_rgba == (const void*)in)
+        return fail(c, FOVPT_E_INVALID, "%s: an output is the input of the call (the gather reads across pixels)", who);
+    if ((const void*)out_color == (const void*)out_rgba) return fail(c, FOVPT_E_INVALID, "%s: two outputs are the same buffer", who);
+
+    a.filter = lc->filter; a.encode = lc->encode;
+    a.mono = memcmp(&lc->chroma[0], &lc->chroma[1], 4) == 0 && memcmp(&lc->chroma[0], &lc->chroma[2], 4) == 0;
+    memcpy(a.center, lc->center, sizeof(a.center)); memcpy(a.scale, lc->scale, sizeof(a.scale));
+    memcpy(a.k, lc->k, sizeof(a.k)); memcpy(a.chroma, lc->chroma, sizeof(a.chroma));
+    a.clip_r2 = lc->clip_r2;
+    memcpy(a.src_center, lc->src_center, sizeof(a.src_center)); memcpy(a.src_scale, lc->src_scale, sizeof(a.src_scale));
+    memcpy(a.border, lc->border, sizeof(a.border));
+    fovpt_launch_lens(c->shadow_stream, c->dn_w, c->dn_h, a, in, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }

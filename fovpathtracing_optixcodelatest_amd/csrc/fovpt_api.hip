@@ -1017,6 +1017,7 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->wp_rgba.p) HIPCHK(c, c->wp_rgba.reserve(n * 4));
     if (c->fc_rt.p) HIPCHK(c, c->fc_rt.reserve(n * 8));                                                    // and fovpt_focus's pairs and outputs (its state stays)
     if (c->fc_color.p) { HIPCHK(c, c->fc_color.reserve(n * 16)); HIPCHK(c, c->fc_rgba.reserve(n * 4)); }
+    if (c->ln_color.p) { HIPCHK(c, c->ln_color.reserve(n * 16)); HIPCHK(c, c->ln_rgba.reserve(n * 4)); }   // and fovpt_lens's
     c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;

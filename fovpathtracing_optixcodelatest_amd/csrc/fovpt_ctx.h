@@ -197,6 +197,8 @@ struct fovpt_ctx {
     // step is a first step; the host never reads it outside fovpt_focus_state), the (r, tp) pairs of the last call (8 bytes per
     // pixel) and the context's own outputs; all allocated on first use
     DevBuf fc_state, fc_rt, fc_color, fc_rgba;
+    // fovpt_lens: the context's own outputs, allocated on first use (the stage keeps nothing else)
+    DevBuf ln_color, ln_rgba;
     // fovpt_packet_submit / fovpt_packet_wait (api_packet.hip), all made by a context's first submit: the copy stream, and per slot
     // the device buffer an encode writes (one each, so that an encode never overwrites a packet that is still being copied), the
     // pinned host buffer its copy fills (grown on demand), the event recorded on fovpt_stream() behind the encode, which the copy

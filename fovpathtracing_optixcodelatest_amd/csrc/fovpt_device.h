@@ -346,6 +346,15 @@ void fovpt_launch_focus_radius(hipStream_t st, size_t npix, const FocusArgs& a, 
                                float2* rt, float* out_coc);
 void fovpt_launch_focus_gather(hipStream_t st, int w, int h, int max_radius, const fovpt_float4* in, const float2* rt, fovpt_float4* out_color,
                                uint32_t* out_rgba);
+// fovpt_lens (lens.hip): the pre-distortion of `in` into the outputs.  `in` is neither output (a pixel reads other pixels').
+struct LensArgs {
+    float H[9];                         // reaim: rows of M [U_to V_to W_to], M the rendered camera's inverse (binary64 on the host, rounded to fp32)
+    int32_t reaim;                      // a `to` camera was given
+    int32_t filter, encode;             // FOVPT_LENS_*
+    int32_t mono;                       // the three chroma factors have equal bits: one lookup serves the three channels
+    float center[2], scale[2], k[4], chroma[3], clip_r2, src_center[2], src_scale[2], border[4];
+};
+void fovpt_launch_lens(hipStream_t st, int w, int h, const LensArgs& a, const fovpt_float4* in, fovpt_float4* out_color, uint32_t* out_rgba);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32

@@ -29,6 +29,7 @@ EXPORTS = [
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
     "fovpt_warp_defaults", "fovpt_warp", "fovpt_warp_buffers", "fovpt_warp_counts", "fovpt_temporal_gbuffer",
     "fovpt_focus_defaults", "fovpt_focus", "fovpt_focus_buffers", "fovpt_focus_state", "fovpt_focus_reset",
+    "fovpt_lens_defaults", "fovpt_lens", "fovpt_lens_buffers",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
     "fovpt_packet_check", "fovpt_packet_decode_host",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
@@ -199,6 +200,9 @@ def load():
     L.fovpt_focus_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_focus_state.argtypes = [vp, C.POINTER(abi.FocusState)]
     L.fovpt_focus_reset.argtypes = [vp]
+    L.fovpt_lens_defaults.argtypes = [C.POINTER(abi.LensConfig)]
+    L.fovpt_lens.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.LensConfig), C.POINTER(abi.WarpCamera), vp, vp, vp]
+    L.fovpt_lens_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_packet_describe.argtypes =[vp, C.POINTER(abi.LaunchParams), u32, C.POINTER(abi.PacketHeader)]
     L.fovpt_packet_encode.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, vp]
     L.fovpt_packet_submit.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, C.POINTER(i32)]

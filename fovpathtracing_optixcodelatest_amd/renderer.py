@@ -566,6 +566,52 @@ class SampleRenderer:
         col, rgba = self.focus_buffers()
         return self._download_frame(col, 4), self._download_frame(rgba, 1)
 
+    # -- head-mounted display lens pre-distortion with chromatic correction (include/fovpt.h, fovpt_lens)
+    @staticmethod
+    def lens_defaults() -> abi.LensConfig:
+        d = abi.LensConfig()
+        lib.check(None, lib.load().fovpt_lens_defaults(C.byref(d)))
+        return d
+
+    @staticmethod
+    def lens_for_frame(cfg, width, height) -> abi.LensConfig:
+        """A copy of cfg fitted to a width x height frame: scale.y = height / width and src_scale.y = width / height (the lens is
+        round, the NDC square is not), then both src_scale entries divided by f(1) = k0 + k1 + k2 + k3, so that the mid-point of the
+        left and right edges maps to itself.  Host only."""
+        c = cfg.copy()
+        f1 = float(c.k[0]) + (float(c.k[1]) + (float(c.k[2]) + float(c.k[3])))
+        c.scale[1] = float(height) / float(width)
+        c.src_scale[1] = float(width) / float(height)
+        c.src_scale[0] = float(c.src_scale[0]) / f1
+        c.src_scale[1] = float(c.src_scale[1]) / f1
+        return c
+
+    def lens(self, cfg=None, to=None, in_color=None, out_color=None, out_rgba=None):
+        """Pre-distorts the frame last rendered for a head-mounted display's lens: for every display pixel and colour channel the
+        position cfg's radial polynomial (times cfg.chroma[c]) maps it to is read from in_color with cfg.filter, on the device.
+        cfg None: lens_for_frame(lens_defaults()) of the frame's size.  to: a late camera (what warp_camera() takes) whose ROTATION
+        re-aims the rays in the same gather, None: no re-aim.  in_color: device pointer of a float4 frame (None: the accum buffer;
+        typically expose_buffers()[0]).  out_color / out_rgba: device pointers, or None for the renderer's own buffers
+        (downloadLens).  Enqueued on the renderer's stream, not synchronised (downloadLens synchronises)."""
+        if cfg is None:
+            f = self.launchParams.frame
+            cfg = self.lens_for_frame(self.lens_defaults(), f.size.x, f.size.y)
+        to = self.warp_camera(to) if to is not None else None
+        self._check(self._L.fovpt_lens(self._ctx, C.byref(self.launchParams), C.byref(cfg), C.byref(to) if to is not None else None,
+                                       in_color, out_color, out_rgba))
+
+    def lens_buffers(self):
+        """Device addresses of the renderer's own pre-distorted outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_lens_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def downloadLens(self):
+        """The outputs of the last lens() into the renderer's own buffers: ((H, W, 4) float32 colour, rgba8 shaped like
+        downloadPixels())."""
+        col, rgba = self.lens_buffers()
+        return self._download_frame(col, 4), self._download_frame(rgba, 1)
+
     # -- foveated frame packets (include/fovpt.h, fovpt_packet_*): a frame off the device, small and without stopping the renderer
     def describePacket(self, sequence=0) -> abi.PacketHeader:
         """The header encodePacket / submitPacket would write for the frame last rendered (host only); .bytes sizes a buffer."""

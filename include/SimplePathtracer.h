@@ -334,6 +334,58 @@ public:
         if (h_color) check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * n));
         if (h_pixels) check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * n));
     }
+    // ---- head-mounted display lens pre-distortion with chromatic correction (include/fovpt.h, fovpt_lens): resamples in_color (null:
+    // the accum buffer; typically expose()'s colour) through the lens polynomial, one position per colour channel, into the
+    // renderer's own lens buffers, then a device sync like render().  `to` (may be null): a late camera whose ROTATION re-aims the
+    // rays in the same gather.  lens() without a configuration: lensForFrame(lensDefaults())
+    static fovpt_lens_config lensDefaults()
+    {
+        fovpt_lens_config lc;
+        if (fovpt_lens_defaults(&lc) != FOVPT_OK) throw std::runtime_error("fovpt_lens_defaults failed");
+        return lc;
+    }
+    // lc fitted to the renderer's frame size: scale.y = h / w, src_scale.y = w / h, both src_scale entries divided by f(1), so that
+    // the mid-point of the left and right edges maps to itself
+    fovpt_lens_config lensForFrame(const fovpt_lens_config& lc) const
+    {
+        fovpt_lens_config c = lc;
+        const double w = launchParams.frame.size.x, h = launchParams.frame.size.y;
+        const double f1 = (double)c.k[0] + ((double)c.k[1] + ((double)c.k[2] + (double)c.k[3]));
+        c.scale[1] = (float)(h / w);
+        c.src_scale[1] = (float)(w / h);
+        c.src_scale[0] = (float)((double)c.src_scale[0] / f1);
+        c.src_scale[1] = (float)((double)c.src_scale[1] / f1);
+        return c;
+    }
+    void lens(const sutil::Camera* to = nullptr, const fovpt_float4* in_color = nullptr) { lens(lensForFrame(lensDefaults()), to, in_color); }
+    void lens(const fovpt_lens_config& lc, const sutil::Camera* to = nullptr, const fovpt_float4* in_color = nullptr)
+    {
+        fovpt_warp_camera wcam;
+        if (to) {
+            sutil::Camera cam = *to;
+            cam.setAspectRatio(launchParams.frame.size.x / float(launchParams.frame.size.y));
+            float3 U, V, W;
+            cam.UVWFrame(U, V, W);
+            const float3 eye = cam.eye();
+            wcam.eye.x = eye.x; wcam.eye.y = eye.y; wcam.eye.z = eye.z;
+            wcam.U.x = U.x; wcam.U.y = U.y; wcam.U.z = U.z;
+            wcam.V.x = V.x; wcam.V.y = V.y; wcam.V.z = V.z;
+            wcam.W.x = W.x; wcam.W.y = W.y; wcam.W.z = W.z;
+        }
+        check(fovpt_lens(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &lc, to ? &wcam : nullptr, in_color, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    void lensBuffers(fovpt_float4** color, uint32_t** rgba) { check(fovpt_lens_buffers(ctx, color, rgba)); }
+    // the pre-distorted float4 colour (may be null) and rgba8 pixels (may be null), like downloadPixels
+    void downloadLens(fovpt_float4 h_color[], uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_lens_buffers(ctx, &color, &rgba));
+        const size_t n = (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y;
+        if (h_color) check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * n));
+        if (h_pixels) check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * n));
+    }
     // ---- foveated frame packets (include/fovpt.h, fovpt_packet_*): the frame last rendered -- in_rgba null: the renderer's own
     // frame buffer; or the rgba8 output of post() / expose() -- as a small self-describing packet in pinned host memory, without a
     // device sync: submitPacket() returns at once with a slot, later frames keep rendering, waitPacket(slot) waits for that

@@ -1075,6 +1075,94 @@ int fovpt_focus_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 int fovpt_focus_state(fovpt_ctx* ctx, struct fovpt_focus_state* out);   /* synchronises fovpt_stream() */
 int fovpt_focus_reset(fovpt_ctx* ctx);                                  /* enqueued */
 
+/* ---- head-mounted display lens pre-distortion with chromatic correction ---------------------------------------------------------
+ * New with this library.  fovpt_warp is a compositor's timewarp; its other half is the pre-distortion that cancels the headset's
+ * lens, one radial polynomial per colour channel so that the lens's chromatic aberration cancels too.  fovpt_lens is that pass, for
+ * a caller that drives a panel directly: an inverse-mapped resampling stage.  For every display pixel it computes where, per channel,
+ * the rendered image is to be read, optionally re-aims that ray by a rotation-only late camera ("rotate and distort in one
+ * gather"), and filters with nearest, bilinear or Catmull-Rom taps.  The stage is the last one ahead of the display (or of
+ * fovpt_packet_*): render -> fovpt_post -> fovpt_focus -> fovpt_expose -> fovpt_lens.
+ *   fovpt_lens               works on the frame last issued with fovpt_render(ctx, lp): its size and, only with `to`, its camera.
+ *                            It needs no scene.  in_color NULL = accum_buffer; out_color / out_rgba NULL = the context's own
+ *                            (fovpt_lens_buffers: allocated on first use, reallocated by fovpt_resize, freed by fovpt_destroy; a
+ *                            context that never calls the stage pays nothing).  Enqueued on fovpt_stream(), not synchronised,
+ *                            ordered like fovpt_denoise.
+ *                            The definition, operation by operation (tests/lens_ref.py), every fp32 +, -, * and / one unfused
+ *                            operation; w, h the frame size, (x, y) a destination pixel:
+ *                              1  nx = (float)(2x + 1) / (float)w - 1.0f, ny likewise with h
+ *                              2  px = (nx - center.x) * scale.x, py likewise; r2 = px * px + py * py
+ *                              3  if !(r2 <= clip_r2) the pixel is outside the lens: out_color = border, all four components
+ *                                 (NaNs fall here)
+ *                              4  f = k0 + r2 * (k1 + r2 * (k2 + r2 * k3)).  Per channel c: fc = f * chroma[c],
+ *                                 sx = (px * fc) * src_scale.x + src_center.x, sy likewise
+ *                              5  only with `to`: a_k = (H[k][0] * sx + H[k][1] * sy) + H[k][2] for k = 0, 1, 2; the channel is
+ *                                 valid iff a.z > 0; then sx = a.x / a.z, sy = a.y / a.z.  H = M [U_to V_to W_to], computed on the
+ *                                 host in binary64 and rounded to fp32: M the rows of inverse(U V W) of the rendered camera (each
+ *                                 entry rounded to fp32, as fovpt_warp and fovpt_temporal compute them), each entry of the product
+ *                                 (m0 * b0 + m1 * b1) + m2 * b2.  to.eye is ignored: the re-aim is rotational (translation needs
+ *                                 depth: that is fovpt_warp, ahead of this stage)
+ *                              6  fx = ((sx + 1.0f) * 0.5f) * (float)w - 0.5f, fy likewise with h (fovpt_warp's pixel convention)
+ *                              7  an invalid channel has the value border[c] exactly and reads no tap.  A channel is invalid if
+ *                                 step 5 said so, or if !(fx >= -2.0f && fx <= (float)w + 1.0f), or the same for fy and h
+ *                              8  otherwise the filter; a tap outside the frame reads border[c], and a window with no tap inside
+ *                                 the frame gives border[c] exactly (the sums below would round).
+ *                                 NEAREST   the tap (floor(fx + 0.5f), floor(fy + 0.5f))
+ *                                 BILINEAR  x0 = floor(fx), tx = fx - x0, likewise in y; taps a = (x0, y0), b = (x0 + 1, y0) and
+ *                                           the row below: top = (1.0f - tx) * a + tx * b, bottom likewise,
+ *                                           v = (1.0f - ty) * top + ty * bottom
+ *                                 BICUBIC   taps x0 - 1 .. x0 + 2, weights of t = tx (and of ty for the rows)
+ *                                           w0 = ((-0.5f * t + 1.0f) * t - 0.5f) * t,  w1 = ((1.5f * t - 2.5f) * t) * t + 1.0f,
+ *                                           w2 = ((-1.5f * t + 2.0f) * t + 0.5f) * t,  w3 = ((0.5f * t - 0.5f) * t) * t;
+ *                                           a row is ((w0 * a0 + w1 * a1) + w2 * a2) + w3 * a3, the four rows y0 - 1 .. y0 + 2
+ *                                           are combined the same way with the y weights; then v = v < 0.0f ? 0.0f : v
+ *                              9  out_color = (v_r, v_g, v_b, 1.0f); out_rgba by `encode`, of out_color's rgb (a pixel outside
+ *                                 the lens: of the border's), with make_color and reinhard of the resolve.  Outputs for non-finite
+ *                                 input colours are unspecified
+ *                            When the three chroma entries have equal bits the channels share one position, and the kernel does
+ *                            one lookup in place of three: the same results by construction.
+ *                            All or nothing, checked before anything is enqueued.  FOVPT_E_INVALID: null ctx / lp / lc; an unknown
+ *                            filter or encode; non-zero reserved fields; a non-finite center, scale, k, chroma, src_center,
+ *                            src_scale or border entry; a clip_r2 that is NaN or <= 0 (+inf is allowed); with `to`, a non-finite
+ *                            entry of `to`, or a rendered camera whose [U V W] has a determinant of 0 or a non-finite one; a null
+ *                            input; an output equal to the input or to the other output (the kernel gathers across pixels; base
+ *                            addresses are compared); width * height >= 2^31; a frame rendered with world > 1.
+ *                            FOVPT_E_NO_FRAME: as fovpt_focus.
+ *   fovpt_lens_defaults      host only, no context.  CONVENTIONS, NOT MEASUREMENTS: BILINEAR, ENCODE_DISPLAY, center 0, both
+ *                            scales (1, 1), src_center 0, clip_r2 +inf, border (0, 0, 0, 1), k = (1, 0.22, 0.24, 0) and
+ *                            chroma = (0.996, 1, 1.014): the publicly documented coefficients of a first-generation
+ *                            development-kit lens.  The defaults know no frame size: a caller sets scale.y = h / w and
+ *                            src_scale.y = w / h (the lens is round, the NDC square is not) and divides both src_scale entries by
+ *                            f(1), so that the mid-point of the left and right edges maps to itself (lens_for_frame of the Python
+ *                            binding, lensForFrame of SimplePathtracer.h).
+ *   fovpt_lens_buffers       addresses of the context's own outputs (allocated for the last frame if not yet).
+ * Out of scope.  Mesh-based or look-up-table distortion; positional re-aim (fovpt_warp); resampling the rgba8 image; vignetting
+ * compensation; distortion of packets on a client.
+ * On an MI355X at 1920 x 1080 a call takes, as a multiple of fovpt_expose FIXED (a plain full-frame pass: 0.020 ms) measured beside it:
+ * NEAREST 1.19 (equal chroma: one lookup) / 1.34 (distinct chroma: three), BILINEAR 1.46 / 1.76 (0.030 / 0.036 ms), BICUBIC 1.85 /
+ * 3.86 (0.038 / 0.078 ms), BILINEAR with distinct chroma and a re-aim 1.89 (one fovpt_render of that frame: 0.655 ms) (DESIGN.md,
+ * section 25).                                                                                                                     */
+#define FOVPT_LENS_NEAREST  0
+#define FOVPT_LENS_BILINEAR 1
+#define FOVPT_LENS_BICUBIC  2          /* Catmull-Rom, 4 x 4 taps */
+#define FOVPT_LENS_ENCODE_DISPLAY 0    /* out_rgba = make_color(o): the input is display-referred (fovpt_expose's colour) */
+#define FOVPT_LENS_ENCODE_RESOLVE 1    /* out_rgba = make_color(reinhard(o * 16, 1)) as every other stage */
+typedef struct fovpt_lens_config {     /* 128 bytes */
+    int32_t filter, encode, _reserved0[2];
+    float center[2];       /* lens axis in destination NDC */
+    float scale[2];        /* destination NDC -> lens radius units */
+    float k[4];            /* f = k0 + r2 * (k1 + r2 * (k2 + r2 * k3)) */
+    float chroma[3];       /* per-channel factor on f: red, green, blue */
+    float clip_r2;         /* r2 above it is outside the lens; +inf = none */
+    float src_center[2], src_scale[2];   /* lens units -> source NDC */
+    float border[4];       /* what lies outside the source image or the lens */
+    int32_t _reserved[8];
+} fovpt_lens_config;
+int fovpt_lens_defaults(fovpt_lens_config* out);          /* host only, no context */
+int fovpt_lens(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_lens_config* lc,
+               const fovpt_warp_camera* to /* NULL: no re-aim */, const fovpt_float4* in_color /* NULL: accum_buffer */,
+               fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */);
+int fovpt_lens_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+
 /* ---- foveated frame packets: a frame off the device, small and without stopping the renderer -----------------------------------
  * New with this library.  fovpt_download drains every stream and copies a whole frame into pageable memory.  A foveated frame
  * is described exactly by one value per launch index -- at the shipped radii 74 / 241 a 1920 x 1080 frame has 211 149 of them,
@@ -1435,6 +1523,8 @@ static_assert(sizeof(struct fovpt_warp_counts) == 32 && offsetof(struct fovpt_wa
 static_assert(sizeof(fovpt_focus_config) == 64 && offsetof(fovpt_focus_config, strength) == 16 && offsetof(fovpt_focus_config, _reserved) == 36,
               "focus config ABI");
 static_assert(sizeof(struct fovpt_focus_state) == 32 && offsetof(struct fovpt_focus_state, count) == 16, "focus state ABI");
+static_assert(sizeof(fovpt_lens_config) == 128 && offsetof(fovpt_lens_config, k) == 32 && offsetof(fovpt_lens_config, clip_r2) == 60 &&
+              offsetof(fovpt_lens_config, border) == 80 && offsetof(fovpt_lens_config, _reserved) == 96, "lens config ABI");
 static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");
 static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header, width) == 16 && offsetof(fovpt_packet_header, pass) == 32,
               "packet header ABI");
