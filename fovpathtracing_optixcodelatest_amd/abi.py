@@ -445,6 +445,23 @@ class WarpConfig(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+WARP_MAX_ADVANCE = 4.0                         # FOVPT_WARP_MAX_ADVANCE
+
+
+class WarpMotionConfig(C.Structure):
+    """fovpt_warp_motion_config: WarpConfig's images and fill radius, and how far past the rendered frame the moved meshes are
+    extrapolated, in intervals between the last two temporal steps (defaults: fovpt_warp_motion_defaults)."""
+    _fields_ = [("images", C.c_int32), ("fill_radius", C.c_int32), ("advance", C.c_float), ("_reserved", C.c_int32 * 5)]
+
+    def copy(self):
+        m = WarpMotionConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(WarpMotionConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
 class WarpCounts(C.Structure):
     """struct fovpt_warp_counts: the source pixels of the last warp that landed in the frame, and its destination pixels by class."""
     _fields_ = [("splatted", C.c_uint64), ("direct", C.c_uint64), ("filled", C.c_uint64), ("empty", C.c_uint64)]
@@ -562,6 +579,7 @@ assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.re
 assert C.sizeof(ExposeConfig) == 80 and (ExposeConfig.low_permille.offset, ExposeConfig.key.offset) == (32, 48)
 assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
 assert C.sizeof(WarpCamera) == 48 and C.sizeof(WarpConfig) == 32 and C.sizeof(WarpCounts) == 32
+assert C.sizeof(WarpMotionConfig) == 32 and WarpMotionConfig.advance.offset == 8
 assert C.sizeof(FocusConfig) == 64 and (FocusConfig.strength.offset, FocusConfig._reserved.offset) == (16, 36)
 assert C.sizeof(FocusState) == 32 and FocusState.count.offset == 16
 assert C.sizeof(LensConfig) == 128 and (LensConfig.k.offset, LensConfig.clip_r2.offset, LensConfig.border.offset, LensConfig._reserved.offset) == (32, 60, 80, 96)

@@ -159,6 +159,7 @@ int begin_update(fovpt_ctx* c, const std::vector<int>& meshes, bool rebuild, boo
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (rebuild) CHK(sync_all(c));
+    c->seq_update = ++c->seq;                          // fovpt_warp_motion: the last temporal step and trace are of the geometry before
     const hipStream_t st = c->shadow_stream;
     if (!c->up_vtx.p) {
         // the first update: the device copies of what fovpt_set_scene kept (ordered on the stream like everything below)

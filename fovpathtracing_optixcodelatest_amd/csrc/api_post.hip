@@ -1,6 +1,6 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
-// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), fovpt_warp
-// (warp.hip), fovpt_focus (focus.hip), fovpt_lens (lens.hip), and their defaults.
+// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), fovpt_warp /
+// fovpt_warp_motion (warp.hip), fovpt_focus (focus.hip), fovpt_lens (lens.hip), and their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -228,6 +228,8 @@ int temporal_enqueue(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_te
     memcpy(c->tp_eye, fd.eye, sizeof(c->tp_eye)); memcpy(c->tp_U, fd.U, sizeof(c->tp_U));
     memcpy(c->tp_V, fd.V, sizeof(c->tp_V)); memcpy(c->tp_W, fd.W, sizeof(c->tp_W));
     c->tm_epoch++;                                                         // the marks of this interval no longer hold
+    c->tm_step_blind = c->tm_untracked;                                    // fovpt_warp_motion: what this step knew of the interval it ended
+    c->seq_step = ++c->seq;
     c->tm_untracked = false;
     return FOVPT_OK;
 }
@@ -352,8 +354,13 @@ int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev&
     const size_t n = (size_t)w * (size_t)h;
     if (n >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, w, h);
     HIPCHK(c, hipSetDevice(c->device));
+    c->gb_stamp = 0;
     { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }
     c->gb_pixels = n;
+    // fovpt_warp_motion: whose hit records these are -- the rendered frame's when this is its size and camera
+    if (w == c->dn_w && h == c->dn_h && !memcmp(view.eye, c->dn_frame.eye, sizeof(view.eye)) && !memcmp(view.U, c->dn_frame.U, sizeof(view.U)) &&
+        !memcmp(view.V, c->dn_frame.V, sizeof(view.V)) && !memcmp(view.W, c->dn_frame.W, sizeof(view.W)))
+        c->gb_stamp = ++c->seq;
     FrameDev fd;
     memset(&fd, 0, sizeof(fd));
     fd.w = w; fd.h = h;
@@ -739,55 +746,67 @@ int fovpt_temporal_gbuffer(fovpt_ctx* c, fovpt_gbuffer_ptrs* out)
     return FOVPT_OK;
 }
 
-// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  Without a caller's G-buffer the rendered frame's first (the
-// same stream, into fovpt_gbuffer's buffers); then the keys and counts are cleared, k_warp_scatter, k_warp_resolve.
-int fovpt_warp(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, const fovpt_warp_config* wc, const fovpt_gbuffer_ptrs* gbuffer,
-               const fovpt_float4* in_color, const uint32_t* in_rgba, fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map)
+// What fovpt_warp and fovpt_warp_motion (`who`) share.  A checked call: the scatter's camera, the enabled images and their inputs,
+// the G-buffer the scatter reads.
+struct WarpCall {
+    WarpArgs a;
+    size_t npix;
+    bool C_, R_;
+    const fovpt_float4* in;
+    const uint32_t* rin;
+    GBufferDev g;
+};
+
+// the validation up to the inputs, in fovpt_warp's order (nothing allocated, enqueued or changed).  reserved: the config's nres words
+static int warp_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, int32_t images, int32_t fill_radius, const int32_t* reserved,
+                      int nres, const fovpt_gbuffer_ptrs* gbuffer, const fovpt_float4* in_color, const uint32_t* in_rgba, const char* who, WarpCall& w)
 {
-    const char* who = "fovpt_warp";
-    if (!c) return FOVPT_E_INVALID;
-    if (!lp || !to || !wc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
-    if (wc->images == 0 || (wc->images & ~(FOVPT_WARP_COLOR | FOVPT_WARP_RGBA)))
-        return fail(c, FOVPT_E_INVALID, "%s: images %d names no image or an unknown one", who, wc->images);
-    if (wc->fill_radius < 0 || wc->fill_radius > FOVPT_WARP_MAX_RADIUS)
-        return fail(c, FOVPT_E_INVALID, "%s: fill_radius %d outside 0 .. %d", who, wc->fill_radius, FOVPT_WARP_MAX_RADIUS);
-    for (int32_t r : wc->_reserved)
-        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    if (images == 0 || (images & ~(FOVPT_WARP_COLOR | FOVPT_WARP_RGBA)))
+        return fail(c, FOVPT_E_INVALID, "%s: images %d names no image or an unknown one", who, images);
+    if (fill_radius < 0 || fill_radius > FOVPT_WARP_MAX_RADIUS)
+        return fail(c, FOVPT_E_INVALID, "%s: fill_radius %d outside 0 .. %d", who, fill_radius, FOVPT_WARP_MAX_RADIUS);
+    for (int k = 0; k < nres; k++)
+        if (reserved[k] != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
     const float* cam = &to->eye.x;                                         // eye, U, V, W: 12 floats
     for (int k = 0; k < 12; k++)
         if (!std::isfinite(cam[k])) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to has a non-finite entry", who);
-    WarpArgs a;
-    memset(&a, 0, sizeof(a));
-    if (!camera_inverse(&to->U.x, &to->V.x, &to->W.x, a.inv)) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to is singular", who);
-    memcpy(a.eye, &to->eye.x, sizeof(a.eye));
+    memset(&w.a, 0, sizeof(w.a));
+    if (!camera_inverse(&to->U.x, &to->V.x, &to->W.x, w.a.inv)) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to is singular", who);
+    memcpy(w.a.eye, &to->eye.x, sizeof(w.a.eye));
     if (!gbuffer && (!c->has_scene || lp->traversable != c->scene_id)) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
     { const int rc_ = check_rendered_frame(c, lp, who, "warp", nullptr); if (rc_) return rc_; }
-    const size_t npix = (size_t)c->dn_w * (size_t)c->dn_h;
-    if (npix >= (1ull << 30)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
+    w.npix = (size_t)c->dn_w * (size_t)c->dn_h;
+    if (w.npix >= (1ull << 30)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
     if (gbuffer && (gbuffer->width != c->dn_w || gbuffer->height != c->dn_h || !gbuffer->prim || !gbuffer->position))
         return fail(c, FOVPT_E_INVALID, "%s: the G-buffer is not of the frame's size %d x %d, or has a null prim or position", who, c->dn_w, c->dn_h);
-    const bool C_ = wc->images & FOVPT_WARP_COLOR, R_ = wc->images & FOVPT_WARP_RGBA;
-    const fovpt_float4* in = C_ ? (in_color ? in_color : lp->frame.accum_buffer) : nullptr;
-    const uint32_t* rin = R_ ? (in_rgba ? in_rgba : lp->frame.frame_buffer) : nullptr;
-    if ((C_ && !in) || (R_ && !rin)) return fail(c, FOVPT_E_INVALID, "%s: an enabled image has a null input", who);
+    w.C_ = images & FOVPT_WARP_COLOR; w.R_ = images & FOVPT_WARP_RGBA;
+    w.in = w.C_ ? (in_color ? in_color : lp->frame.accum_buffer) : nullptr;
+    w.rin = w.R_ ? (in_rgba ? in_rgba : lp->frame.frame_buffer) : nullptr;
+    if ((w.C_ && !w.in) || (w.R_ && !w.rin)) return fail(c, FOVPT_E_INVALID, "%s: an enabled image has a null input", who);
+    return FOVPT_OK;
+}
 
-    // buffers: the context's own outputs where an enabled image has none, the keys, the counts
+// the buffers of a checked call -- the context's own outputs where an enabled image has none, the keys, the counts -- and the last
+// of the validation, which needs them: no output is an input, the keys or another output (the resolve reads other pixels' inputs
+// and keys while it writes)
+static int warp_buffers(fovpt_ctx* c, const fovpt_gbuffer_ptrs* gbuffer, WarpCall& w, fovpt_float4*& out_color, uint32_t*& out_rgba, uint32_t* out_map,
+                        const char* who)
+{
     HIPCHK(c, hipSetDevice(c->device));
-    if (C_ && !out_color) { HIPCHK(c, c->wp_color.reserve(npix * 16)); out_color = (fovpt_float4*)c->wp_color.p; }
-    if (R_ && !out_rgba) { HIPCHK(c, c->wp_rgba.reserve(npix * 4)); out_rgba = (uint32_t*)c->wp_rgba.p; }
-    if (!C_) out_color = nullptr;
-    if (!R_) out_rgba = nullptr;
-    HIPCHK(c, c->wp_keys.reserve(npix * 8));
+    if (w.C_ && !out_color) { HIPCHK(c, c->wp_color.reserve(w.npix * 16)); out_color = (fovpt_float4*)c->wp_color.p; }
+    if (w.R_ && !out_rgba) { HIPCHK(c, c->wp_rgba.reserve(w.npix * 4)); out_rgba = (uint32_t*)c->wp_rgba.p; }
+    if (!w.C_) out_color = nullptr;
+    if (!w.R_) out_rgba = nullptr;
+    HIPCHK(c, c->wp_keys.reserve(w.npix * 8));
     if (!c->wp_counts.p) {
         HIPCHK(c, c->wp_counts.reserve(FOVPT_WARP_COUNT_BYTES));
         HIPCHK(c, hipMemset(c->wp_counts.p, 0, FOVPT_WARP_COUNT_BYTES));
     }
-    // the resolve reads other pixels' inputs and keys while it writes: no output is an input, the keys or another output
-    GBufferDev g;
+    GBufferDev& g = w.g;
     if (gbuffer) { g.prim = gbuffer->prim; g.pos = (float4*)gbuffer->position; g.nrm = (float4*)gbuffer->normal; g.alb = (float4*)gbuffer->albedo; }
     else { g.prim = (uint32_t*)c->gb_prim.p; g.pos = (float4*)c->gb_pos.p; g.nrm = nullptr; g.alb = nullptr; }      // (null until the first trace)
     const void* outs[3] = {out_color, out_rgba, out_map};
-    const void* ins[5] = {in, rin, g.prim, g.pos, c->wp_keys.p};
+    const void* ins[5] = {w.in, w.rin, g.prim, g.pos, c->wp_keys.p};
     for (int i = 0; i < 3; i++) {
         if (!outs[i]) continue;
         for (const void* p : ins)
@@ -795,16 +814,88 @@ int fovpt_warp(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_cam
         for (int j = 0; j < i; j++)
             if (outs[j] == outs[i]) return fail(c, FOVPT_E_INVALID, "%s: two outputs are the same buffer", who);
     }
+    return FOVPT_OK;
+}
 
-    if (!gbuffer) { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, g, who); if (rc_) return rc_; }   // the rendered frame's camera
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  Without a caller's G-buffer the rendered frame's first (the
+// same stream, into fovpt_gbuffer's buffers); then the keys and counts are cleared, k_warp_scatter (motion null) or
+// k_warp_scatter_motion (motion: its advance; the rest is filled in here, behind the trace), k_warp_resolve.
+static int warp_enqueue(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_gbuffer_ptrs* gbuffer, WarpCall& w, int32_t fill_radius,
+                        const float* motion, fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map, const char* who)
+{
+    if (!gbuffer) { const int rc_ = enqueue_gbuffer(c, lp, c->dn_frame, w.g, who); if (rc_) return rc_; }   // the rendered frame's camera
     const hipStream_t st = c->shadow_stream;
-    HIPCHK(c, hipMemsetAsync(c->wp_keys.p, 0xff, npix * 8, st));
+    HIPCHK(c, hipMemsetAsync(c->wp_keys.p, 0xff, w.npix * 8, st));
     HIPCHK(c, hipMemsetAsync(c->wp_counts.p, 0, FOVPT_WARP_COUNT_BYTES, st));
-    fovpt_launch_warp_scatter(st, c->dn_frame, a, g.prim, g.pos, (uint64_t*)c->wp_keys.p, (uint64_t*)c->wp_counts.p);
-    fovpt_launch_warp_resolve(st, c->dn_w, c->dn_h, wc->fill_radius, (const uint64_t*)c->wp_keys.p, in, rin, out_color, out_rgba, out_map,
+    if (!motion) fovpt_launch_warp_scatter(st, c->dn_frame, w.a, w.g.prim, w.g.pos, (uint64_t*)c->wp_keys.p, (uint64_t*)c->wp_counts.p);
+    else {
+        WarpMotionArgs m;
+        memset(&m, 0, sizeof(m));
+        m.hit = (const float4*)c->gb_hit.p; m.tris = c->tris;
+        m.mark = (const uint64_t*)c->tm_mark.p; m.epoch = c->tm_epoch - 1;     // the step that ended the last interval
+        m.tri_vidx = (const uint3*)c->up_vidx.p; m.vtx_prev = (const float*)c->vtx_prev.p;
+        m.tri_bytes = (uint64_t)c->num_tris * sizeof(TriRec);
+        m.num_prims = (uint32_t)(c->h_tri_vidx.size() / 3); m.num_meshes = (uint32_t)c->mesh_nv.size();
+        m.advance = *motion;
+        fovpt_launch_warp_scatter_motion(st, c->dn_frame, w.a, m, w.g.prim, w.g.pos, (uint64_t*)c->wp_keys.p, (uint64_t*)c->wp_counts.p);
+    }
+    fovpt_launch_warp_resolve(st, c->dn_w, c->dn_h, fill_radius, (const uint64_t*)c->wp_keys.p, w.in, w.rin, out_color, out_rgba, out_map,
                               (uint64_t*)c->wp_counts.p);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
+}
+
+int fovpt_warp(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, const fovpt_warp_config* wc, const fovpt_gbuffer_ptrs* gbuffer,
+               const fovpt_float4* in_color, const uint32_t* in_rgba, fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map)
+{
+    const char* who = "fovpt_warp";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !to || !wc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    WarpCall w;
+    { const int rc_ = warp_check(c, lp, to, wc->images, wc->fill_radius, wc->_reserved, 6, gbuffer, in_color, in_rgba, who, w); if (rc_) return rc_; }
+    { const int rc_ = warp_buffers(c, gbuffer, w, out_color, out_rgba, out_map, who); if (rc_) return rc_; }
+    return warp_enqueue(c, lp, gbuffer, w, wc->fill_radius, nullptr, out_color, out_rgba, out_map, who);
+}
+
+// ---- fovpt_warp in which the meshes that moved in the last interval go on moving (warp.hip, k_warp_scatter_motion; its definition:
+// tests/warp_motion_ref.py) ----------------------------------------------------------------------------
+// (advance: a convention, not a measurement: include/fovpt.h)
+int fovpt_warp_motion_defaults(fovpt_warp_motion_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->images = FOVPT_WARP_COLOR | FOVPT_WARP_RGBA;
+    out->fill_radius = 2;
+    out->advance = 1.0f;
+    return FOVPT_OK;
+}
+
+int fovpt_warp_motion(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, const fovpt_warp_motion_config* mc,
+                      const fovpt_gbuffer_ptrs* gbuffer, const fovpt_float4* in_color, const uint32_t* in_rgba, fovpt_float4* out_color,
+                      uint32_t* out_rgba, uint32_t* out_map)
+{
+    const char* who = "fovpt_warp_motion";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !to || !mc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (!(mc->advance >= 0.0f && mc->advance <= FOVPT_WARP_MAX_ADVANCE))   // (NaN fails)
+        return fail(c, FOVPT_E_INVALID, "%s: advance %g outside 0 .. %g", who, (double)mc->advance, (double)FOVPT_WARP_MAX_ADVANCE);
+    WarpCall w;
+    { const int rc_ = warp_check(c, lp, to, mc->images, mc->fill_radius, mc->_reserved, 5, gbuffer, in_color, in_rgba, who, w); if (rc_) return rc_; }
+    // the last temporal step, the previous positions and the hit records describe the rendered frame
+    if (!c->tp_valid) return fail(c, FOVPT_E_NO_FRAME, "%s: no temporal step since create / reset / resize / set_scene", who);
+    if (!c->tm_tracking)
+        return fail(c, FOVPT_E_NO_FRAME, "%s: previous positions are not tracked yet (no fovpt_temporal_motion or fovpt_post with MOTION on this scene)", who);
+    if (c->seq_update > c->seq_step)
+        return fail(c, FOVPT_E_NO_FRAME, "%s: a geometry update has been issued since the last temporal step", who);
+    if (gbuffer && !(c->gb_stamp > c->seq_frame && c->gb_stamp > c->seq_update))
+        return fail(c, FOVPT_E_NO_FRAME, "%s: the context's last G-buffer trace is not of the rendered frame and the current geometry "
+                                         "(its hit records go with the caller's G-buffer)", who);
+    { const int rc_ = warp_buffers(c, gbuffer, w, out_color, out_rgba, out_map, who); if (rc_) return rc_; }
+    // what the host knows: with no mesh moved in the interval, a step that did not see its updates, or no advance, fovpt_warp's scatter
+    bool moved = false;
+    if (!c->tm_step_blind && mc->advance != 0.0f)
+        for (const uint64_t e : c->tm_mesh_epoch) moved = moved || e == c->tm_epoch - 1;
+    return warp_enqueue(c, lp, gbuffer, w, mc->fill_radius, moved ? &mc->advance : nullptr, out_color, out_rgba, out_map, who);
 }
 
 // ---- gaze-metered focus distance and depth of field (focus.hip; its definition: tests/focus_ref.py) ---------------------------

@@ -824,6 +824,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     { const int rc_ = sync_all(c); if (rc_) return rc_; }
     free_scene(c);
     c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
+    c->seq_frame = ++c->seq;                         // fovpt_warp_motion: the hit records of the last trace are another scene's
     { const int rc_ = expose_reset(c, nullptr); if (rc_) return rc_; }   // fovpt_expose adapts to another scene from scratch
     { const int rc_ = focus_reset(c, nullptr); if (rc_) return rc_; }    // and fovpt_focus meters it from scratch
     take_costs(c);                                   // fovpt_hierarchy_cost: (the device is idle) no measurement of the old scene stays in flight
@@ -1020,6 +1021,7 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->ln_color.p) { HIPCHK(c, c->ln_color.reserve(n * 16)); HIPCHK(c, c->ln_rgba.reserve(n * 4)); }   // and fovpt_lens's
     c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
+    c->seq_frame = ++c->seq;                                                                  // (fovpt_warp_motion: nor traced)
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
     out->color_buffer = (fovpt_float4*)c->fb_color.p; out->normal_buffer = (fovpt_float4*)c->fb_normal.p;
     out->albedo_buffer = (fovpt_float4*)c->fb_albedo.p;
@@ -1066,6 +1068,7 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
     const int rc = run_passes(c, lp, P, npass, 1);
     lp->frame.subframe_index = temp_frame;                                                   // :128-129 / :210-211
     lp->frame.subframe_index++;
+    c->seq_frame = ++c->seq;                                                                  // fovpt_warp_motion: the last trace is an earlier frame's
     if (rc == FOVPT_OK) {                                                                     // what post-processing may filter
         c->dn_w = lp->frame.size.x; c->dn_h = lp->frame.size.y;
         frame_levels(c->cfg, lp, c->dn_frame);

@@ -229,6 +229,14 @@ struct fovpt_ctx {
     fovpt_stats stats;
     std::vector<EventPair> pending;
     std::vector<hipEvent_t> free_events;
+    // fovpt_warp_motion: what it asks of the last temporal step and of the last G-buffer trace, all on the host.  tm_step_blind
+    // (set by every temporal step): the step ended an interval with an update the tracking did not see, so no mesh counts as
+    // moved in it.  seq: one counter, incremented at each of the events below, whose value then is the event's stamp (0: never)
+    // -- seq_frame: the last fovpt_render, fovpt_resize or fovpt_set_scene; seq_update: the last geometry update; seq_step: the
+    // last temporal step; gb_stamp: the last G-buffer trace, 0 when it was not of the rendered frame's size and camera.  The hit
+    // records (gb_hit) describe the rendered frame and the current geometry when gb_stamp is above seq_frame and seq_update.
+    bool tm_step_blind = false;
+    uint64_t seq = 0, seq_frame = 0, seq_update = 0, seq_step = 0, gb_stamp = 0;
     ~fovpt_ctx();                          // what no DevBuf owns; fovpt_destroy synchronises first
 };
 

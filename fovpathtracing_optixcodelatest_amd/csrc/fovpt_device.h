@@ -322,6 +322,23 @@ struct WarpArgs {
 };
 void fovpt_launch_warp_scatter(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const uint32_t* prim, const float4* pos, uint64_t* keys,
                                uint64_t* counts);
+// fovpt_warp_motion (warp.hip, k_warp_scatter_motion): what its scatter reads beside k_warp_scatter's inputs -- fovpt_temporal_motion's
+// per-pixel reads.  A hit pixel's mesh moved in the interval the last temporal step ended when mark[mesh] == epoch (that step's
+// number); only then are tri_vidx and vtx_prev read, and the pixel scatters X* = X_s + advance * (X_s - X').  tri_bytes, num_prims
+// and num_meshes bound what a hit record and a G-buffer entry may address: an entry outside them counts as not moved.
+struct WarpMotionArgs {
+    const float4* hit;                  // the last G-buffer trace's hit records: t, u, v, record position in 16-byte units as bits
+    const TriRec* tris;
+    const uint64_t* mark;               // per mesh: the step before which it last moved
+    const uint3* tri_vidx;              // per global primitive id its three vertices in vtx_prev
+    const float* vtx_prev;              // the positions the marked meshes had when the step before the last one ran
+    uint64_t epoch;                     // the number of the last step
+    uint64_t tri_bytes;                 // the triangle records' bytes
+    uint32_t num_prims, num_meshes;
+    float advance;
+};
+void fovpt_launch_warp_scatter_motion(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const WarpMotionArgs& m, const uint32_t* prim,
+                                      const float4* pos, uint64_t* keys, uint64_t* counts);
 // in_color / out_color, in_rgba / out_rgba: both null where that image is not warped; out_map: may be null.  No output is an
 // input or another output (a pixel reads other pixels' inputs)
 void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,

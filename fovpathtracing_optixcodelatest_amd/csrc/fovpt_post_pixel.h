@@ -176,6 +176,21 @@ __device__ inline void temporal_history(const FrameDev& fd, const TemporalArgs& 
     }
 }
 
+// The previous positions a', b', c' of primitive prim's vertices (tri_vidx: its index triple into vtx_prev), and the point
+// X' = (w0 a' + u b') + v c', w0 = (1 - u) - v, of a hit record (t, u, v, record) over them: what fovpt_temporal_motion and
+// fovpt_warp_motion take for where a moved surface was at the previous step.
+__device__ inline void previous_vertices(const uint3* tri_vidx, const float* vtx_prev, uint32_t prim, V3& A, V3& B, V3& Cc)
+{
+    const uint3 iv = tri_vidx[prim];
+    const float* pa = vtx_prev + 3 * (size_t)iv.x, *pb = vtx_prev + 3 * (size_t)iv.y, *pc = vtx_prev + 3 * (size_t)iv.z;
+    A = v3(pa[0], pa[1], pa[2]); B = v3(pb[0], pb[1], pb[2]); Cc = v3(pc[0], pc[1], pc[2]);
+}
+__device__ inline V3 previous_point(const float4& hit, const V3& A, const V3& B, const V3& Cc)
+{
+    const float w0 = (1.0f - hit.y) - hit.z;
+    return (w0 * A + hit.y * B) + hit.z * Cc;
+}
+
 // k_temporal_motion's: temporal_history in which a hit pixel whose mesh is marked (m.mark[mesh] == m.epoch) gets
 // X' = (w0 a' + u b') + v c' and N' = normalize(cross(b' - a', c' - a')) * s from its triangle's previous vertices a', b', c' and
 // its hit's (u, v), s the sign k_gbuffer_fill gave the current normal; every other pixel takes temporal_history's operations.
@@ -200,11 +215,9 @@ __device__ inline void temporal_motion_history(const FrameDev& fd, const Tempora
             const uint32_t mesh = __float_as_uint(tr[2].z);
             if (m.mark[mesh] == m.epoch) {
                 const float4 hit = m.hit[idx];
-                const uint3 iv = m.tri_vidx[prim];
-                const float* pa = m.vtx_prev + 3 * (size_t)iv.x, *pb = m.vtx_prev + 3 * (size_t)iv.y, *pc = m.vtx_prev + 3 * (size_t)iv.z;
-                const V3 A = v3(pa[0], pa[1], pa[2]), B = v3(pb[0], pb[1], pb[2]), Cc = v3(pc[0], pc[1], pc[2]);
-                const float w0 = (1.0f - hit.y) - hit.z;
-                Xp = (w0 * A + hit.y * B) + hit.z * Cc;
+                V3 A, B, Cc;
+                previous_vertices(m.tri_vidx, m.vtx_prev, prim, A, B, Cc);
+                Xp = previous_point(hit, A, B, Cc);
                 // s: k_gbuffer_fill's copysignf(1, dot(wo, N_0)) over the current record's edges and k_gbuffer_rays' direction
                 const float4 t0 = tr[0], t1 = tr[1];
                 const V3 N_0 = normalize(cross(v3(t0.w, t1.x, t1.y), v3(t1.z, t1.w, tr[2].x)));

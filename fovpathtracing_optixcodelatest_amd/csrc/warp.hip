@@ -5,6 +5,8 @@
 //                    camera with fovpt_temporal's expression, rounded to the nearest pixel, and one 64-bit atomic minimum of
 //                    (depth bits << 32 | source index) on that pixel's key.  Nearest depth wins, equal depths go to the lower
 //                    source index: the keys do not depend on the order in which the atomics arrive
+//   k_warp_scatter_motion   fovpt_warp_motion's scatter: k_warp_scatter in which a hit pixel of a mesh that moved in the last
+//                    interval lands where its own motion, extrapolated by `advance` intervals, takes it
 //   k_warp_resolve   per destination pixel: the key's source; for an empty key the farthest key of the nearest non-empty
 //                    Chebyshev ring within fill_radius; else the pixel itself.  Copies the enabled images from the source,
 //                    bit for bit, and writes the map
@@ -66,6 +68,54 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter(const FrameDev fd,
     count_wave(landed, &count_slot(counts)[0]);
 }
 
+// fovpt_warp_motion's scatter (tests/warp_motion_ref.py): k_warp_scatter, statement for statement, in which
+// a hit pixel of a mesh that moved in the interval the last temporal step ended scatters X* = X_s + advance * (X_s - X') for X_s, X'
+// where its hit (u, v) was on the triangle's previous vertices (fovpt_post_pixel.h, as k_temporal_motion's).  The common case -- an
+// unmarked mesh -- pays for the hit record, one word of the triangle record and the mark; the branch is per lane.
+__global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter_motion(const FrameDev fd, const WarpArgs a, const WarpMotionArgs m,
+                                                                     const uint32_t* __restrict__ prim, const float4* __restrict__ pos,
+                                                                     unsigned long long* __restrict__ keys, unsigned long long* __restrict__ counts)
+{
+    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    bool landed = false;
+    if (x < (uint32_t)fd.w && y < (uint32_t)fd.h) {
+        const uint32_t s = y * (uint32_t)fd.w + x;
+        const uint32_t p = prim[s];
+        const bool miss = p == 0xffffffffu;
+        V3 v;
+        if (!miss) {
+            V3 X = v3(pos[s]);
+            const float4 hit = m.hit[s];
+            const uint64_t rec = (uint64_t)__float_as_uint(hit.w) << 4;   // byte offset of the triangle record, as k_gbuffer_fill's
+            if (rec + sizeof(TriRec) <= m.tri_bytes && p < m.num_prims) { // (a G-buffer of this frame's trace: always)
+                const float4* tr = (const float4*)((const char*)m.tris + rec);
+                const uint32_t mesh = __float_as_uint(tr[2].z);
+                if (mesh < m.num_meshes && m.mark[mesh] == m.epoch) {
+                    V3 A, B, Cc;
+                    previous_vertices(m.tri_vidx, m.vtx_prev, p, A, B, Cc);
+                    const V3 d = X - previous_point(hit, A, B, Cc);
+                    X = X + m.advance * d;
+                }
+            }
+            v = X - v3(a.eye[0], a.eye[1], a.eye[2]);
+        } else v = pixel_ray(fd, x, y);                                  // the sky is at infinity: only rotation moves it
+        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
+        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
+        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
+        const float fw = (float)fd.w, fh = (float)fd.h;
+        const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
+        const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
+        const float fx = floorf(px + 0.5f), fy = floorf(py + 0.5f);
+        landed = az > 0.0f && fx >= 0.0f && fx < fw && fy >= 0.0f && fy < fh;    // (in float, before converting: a non-finite X* fails)
+        if (landed) {
+            const uint32_t d = miss ? 0x7fffffffu : __float_as_uint(az);
+            const uint32_t q = (uint32_t)fy * (uint32_t)fd.w + (uint32_t)fx;
+            (void)atomicMin(&keys[q], ((unsigned long long)d << 32) | (unsigned long long)s);
+        }
+    }
+    count_wave(landed, &count_slot(counts)[0]);
+}
+
 // the largest non-empty key, or 0
 __device__ inline unsigned long long farthest(unsigned long long best, unsigned long long k) { return k != WARP_EMPTY && k > best ? k : best; }
 
@@ -117,6 +167,14 @@ void fovpt_launch_warp_scatter(hipStream_t st, const FrameDev& fd, const WarpArg
 {
     const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
     hipLaunchKernelGGL(k_warp_scatter, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, prim, pos, (unsigned long long*)keys, (unsigned long long*)counts);
+}
+
+void fovpt_launch_warp_scatter_motion(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const WarpMotionArgs& m, const uint32_t* prim,
+                                      const float4* pos, uint64_t* keys, uint64_t* counts)
+{
+    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
+    hipLaunchKernelGGL(k_warp_scatter_motion, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, m, prim, pos, (unsigned long long*)keys,
+                       (unsigned long long*)counts);
 }
 
 void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,

@@ -28,6 +28,7 @@ EXPORTS = [
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
     "fovpt_warp_defaults", "fovpt_warp", "fovpt_warp_buffers", "fovpt_warp_counts", "fovpt_temporal_gbuffer",
+    "fovpt_warp_motion_defaults", "fovpt_warp_motion",
     "fovpt_focus_defaults", "fovpt_focus", "fovpt_focus_buffers", "fovpt_focus_state", "fovpt_focus_reset",
     "fovpt_lens_defaults", "fovpt_lens", "fovpt_lens_buffers",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
@@ -195,6 +196,9 @@ def load():
     L.fovpt_warp_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_warp_counts.argtypes = [vp, C.POINTER(abi.WarpCounts)]
     L.fovpt_temporal_gbuffer.argtypes = [vp, C.POINTER(abi.GBufferPtrs)]
+    L.fovpt_warp_motion_defaults.argtypes = [C.POINTER(abi.WarpMotionConfig)]
+    L.fovpt_warp_motion.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.WarpCamera), C.POINTER(abi.WarpMotionConfig),
+                                    C.POINTER(abi.GBufferPtrs), vp, vp, vp, vp, vp]
     L.fovpt_focus_defaults.argtypes = [C.POINTER(abi.FocusConfig)]
     L.fovpt_focus.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.FocusConfig), C.POINTER(abi.GBufferPtrs), vp, vp, vp, vp]
     L.fovpt_focus_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]

@@ -491,6 +491,22 @@ class SampleRenderer:
         self._check(self._L.fovpt_warp(self._ctx, C.byref(self.launchParams), C.byref(to), C.byref(cfg), C.byref(gbuffer) if gbuffer is not None else None,
                                        in_color, in_rgba, out_color, out_rgba, out_map))
 
+    @staticmethod
+    def warp_motion_defaults() -> abi.WarpMotionConfig:
+        d = abi.WarpMotionConfig()
+        lib.check(None, lib.load().fovpt_warp_motion_defaults(C.byref(d)))
+        return d
+
+    def warp_motion(self, to, cfg=None, gbuffer=None, in_color=None, in_rgba=None, out_color=None, out_rgba=None, out_map=None):
+        """warp() in which the meshes that moved in the interval the last temporal step ended (temporal(), temporal_motion() or
+        post()) go on moving: their pixels are scattered cfg.advance intervals further along their own motion.  Everything else,
+        the buffers and warp_counts() included, is warp()'s.  gbuffer: as warp()'s; the hit records that go with it are the
+        renderer's last G-buffer trace, which must be of the frame last rendered and of the current geometry (the library checks)."""
+        cfg = cfg if cfg is not None else self.warp_motion_defaults()
+        to = self.warp_camera(to)
+        self._check(self._L.fovpt_warp_motion(self._ctx, C.byref(self.launchParams), C.byref(to), C.byref(cfg),
+                                              C.byref(gbuffer) if gbuffer is not None else None, in_color, in_rgba, out_color, out_rgba, out_map))
+
     def warp_buffers(self):
         """Device addresses of the renderer's own warped outputs: (float4 colour, rgba8)."""
         col, rgba = C.c_void_p(), C.c_void_p()

@@ -244,8 +244,8 @@ public:
         check(fovpt_warp_defaults(&wc));
         warp(to, wc, reuse_gbuffer, in_color, in_rgba);
     }
-    void warp(const sutil::Camera& to, const fovpt_warp_config& wc, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr,
-              const uint32_t* in_rgba = nullptr)
+    // `to` with the frame's aspect ratio, in the layout fovpt_warp, fovpt_warp_motion and fovpt_lens take
+    fovpt_warp_camera warpCamera(const sutil::Camera& to) const
     {
         sutil::Camera cam = to;
         cam.setAspectRatio(launchParams.frame.size.x / float(launchParams.frame.size.y));
@@ -257,11 +257,47 @@ public:
         wcam.U.x = U.x; wcam.U.y = U.y; wcam.U.z = U.z;
         wcam.V.x = V.x; wcam.V.y = V.y; wcam.V.z = V.z;
         wcam.W.x = W.x; wcam.W.y = W.y; wcam.W.z = W.z;
+        return wcam;
+    }
+    void warp(const sutil::Camera& to, const fovpt_warp_config& wc, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr,
+              const uint32_t* in_rgba = nullptr)
+    {
+        const fovpt_warp_camera wcam = warpCamera(to);
         fovpt_gbuffer_ptrs g;
         if (reuse_gbuffer) check(fovpt_temporal_gbuffer(ctx, &g));
         check(fovpt_warp(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &wcam, &wc, reuse_gbuffer ? &g : nullptr, in_color, in_rgba,
                          nullptr, nullptr, nullptr));
         check(fovpt_synchronize(ctx));
+    }
+    // ---- fovpt_warp_motion: warp() in which the meshes that moved in the interval the last post() / temporal step ended go on moving,
+    // `advance` intervals past the rendered frame; into the same warped buffers, so downloadWarpedPixels and warpCounts serve both.
+    // reuse_gbuffer: as warp()'s -- the hit records that go with the step's G-buffer are the context's last trace, which the library
+    // checks to be of this frame
+    void warpMotion(const sutil::Camera& to, float advance, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr,
+                    const uint32_t* in_rgba = nullptr)
+    {
+        fovpt_warp_motion_config mc;
+        check(fovpt_warp_motion_defaults(&mc));
+        mc.advance = advance;
+        warpMotion(to, mc, reuse_gbuffer, in_color, in_rgba);
+    }
+    void warpMotion(const sutil::Camera& to, const fovpt_warp_motion_config& mc, bool reuse_gbuffer = false, const fovpt_float4* in_color = nullptr,
+                    const uint32_t* in_rgba = nullptr)
+    {
+        const fovpt_warp_camera wcam = warpCamera(to);
+        fovpt_gbuffer_ptrs g;
+        if (reuse_gbuffer) check(fovpt_temporal_gbuffer(ctx, &g));
+        check(fovpt_warp_motion(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &wcam, &mc, reuse_gbuffer ? &g : nullptr, in_color,
+                                in_rgba, nullptr, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // warpMotion() of the images the last expose() left in the renderer's own exposed buffers
+    void warpMotionExposed(const sutil::Camera& to, float advance, bool reuse_gbuffer = false)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_expose_buffers(ctx, &color, &rgba));
+        warpMotion(to, advance, reuse_gbuffer, color, rgba);
     }
     // warp() of the images the last expose() left in the renderer's own exposed buffers
     void warpExposed(const sutil::Camera& to, bool reuse_gbuffer = false)
@@ -361,17 +397,7 @@ public:
     void lens(const fovpt_lens_config& lc, const sutil::Camera* to = nullptr, const fovpt_float4* in_color = nullptr)
     {
         fovpt_warp_camera wcam;
-        if (to) {
-            sutil::Camera cam = *to;
-            cam.setAspectRatio(launchParams.frame.size.x / float(launchParams.frame.size.y));
-            float3 U, V, W;
-            cam.UVWFrame(U, V, W);
-            const float3 eye = cam.eye();
-            wcam.eye.x = eye.x; wcam.eye.y = eye.y; wcam.eye.z = eye.z;
-            wcam.U.x = U.x; wcam.U.y = U.y; wcam.U.z = U.z;
-            wcam.V.x = V.x; wcam.V.y = V.y; wcam.V.z = V.z;
-            wcam.W.x = W.x; wcam.W.y = W.y; wcam.W.z = W.z;
-        }
+        if (to) wcam = warpCamera(*to);
         check(fovpt_lens(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &lc, to ? &wcam : nullptr, in_color, nullptr, nullptr));
         check(fovpt_synchronize(ctx));
     }

@@ -953,12 +953,50 @@ int fovpt_expose_reset(fovpt_ctx* ctx);
  *   fovpt_temporal_gbuffer   the G-buffer set the last temporal step (fovpt_temporal, fovpt_temporal_motion, fovpt_post) wrote;
  *                            FOVPT_E_NO_FRAME when there is none (no step yet, or fovpt_temporal_reset / fovpt_resize /
  *                            fovpt_set_scene since).  The next temporal step leaves it alone and overwrites the other set.
- * Out of scope.  Moving meshes: they are warped as if static (extrapolating them by fovpt_temporal_motion's vectors is a later
- * step).  Resampling: a pixel is copied, not interpolated.  Packets: a packet's texel ownership belongs to the rendered camera, so
+ *   fovpt_warp_motion        fovpt_warp in which the meshes that moved go on moving.  fovpt_warp re-aims the
+ *                            static world; every skinned, morphed, rigged or rigidly moving mesh stays where it was at render time.
+ *                            This call is fovpt_warp, operation for operation -- inputs and outputs, the context's warp buffers and
+ *                            keys, fovpt_warp_counts, the stream and the ordering, images, fill_radius, the map and the classes, the
+ *                            validation and the resolve -- with one difference: a source pixel that hits a mesh moved in the last
+ *                            interval scatters an extrapolated point X* instead of X_s.  The last interval is the one ended by the
+ *                            context's last temporal step (fovpt_temporal, fovpt_temporal_motion or fovpt_post, whichever ran
+ *                            last).  With (u, v) the pixel's hit record and a', b', c' the positions its triangle's vertices had
+ *                            when the step before the last one ran (fovpt_temporal_motion's quantities), every *, +, - one unfused
+ *                            binary32 operation per component (tests/warp_motion_ref.py):
+ *                              w0 = (1 - u) - v          X' = (w0 a' + u b') + v c'
+ *                              d  = X_s - X'             X* = X_s + advance * d
+ *                              v  = X* - eye_to          then fovpt_warp's a_k, px, py, fx, fy, landing test, depth word and key
+ *                            X_s is the G-buffer position as stored.  A non-finite X* lands nowhere.  Hits on meshes that did not
+ *                            move in that interval, every miss, every pixel when no mesh moved or advance is 0 (the call then
+ *                            launches fovpt_warp's own scatter kernel), and every pixel when the last step knew nothing of the
+ *                            motion (an update ran while the tracking of previous positions was still off: the first
+ *                            fovpt_temporal_motion of a scene) are fovpt_warp's, bit for bit.  advance: how far past the rendered
+ *                            frame the image is shown, in units of the interval between the last two temporal steps.
+ *                            The hit records are not part of fovpt_gbuffer_ptrs: they are the context's, written by its last
+ *                            G-buffer trace, whichever call made it.  gbuffer NULL: the call traces, as fovpt_warp does.  Non-NULL:
+ *                            the pointers are used as fovpt_warp uses them, and the call checks on the host (one counter, stamped
+ *                            at every trace; no device work) that the context's last trace was of the rendered frame's size and
+ *                            camera and is newer than the last fovpt_render, geometry update, fovpt_resize and fovpt_set_scene.
+ *                            With fovpt_temporal_gbuffer's set the loop update -> render -> post(MOTION) -> expose ->
+ *                            temporal_gbuffer -> warp_motion -> update ... traces one G-buffer per frame.
+ *                            All or nothing.  Everything fovpt_warp returns for the same arguments; FOVPT_E_INVALID: advance NaN,
+ *                            infinite, below 0 or above FOVPT_WARP_MAX_ADVANCE, a non-zero reserved field; FOVPT_E_NO_FRAME: no
+ *                            temporal step since create / fovpt_temporal_reset / fovpt_resize / fovpt_set_scene; tracking of
+ *                            previous positions off (no fovpt_temporal_motion and no fovpt_post with MOTION on this scene yet); a
+ *                            geometry update issued since the last temporal step (the previous positions and the step's G-buffer
+ *                            no longer describe one frame); with a caller's gbuffer, the stamp check above.
+ *   fovpt_warp_motion_defaults   host only, no context: both images, fill_radius 2, advance 1 (conventions, not measurements).
+ * Out of scope.  Moving meshes in fovpt_warp itself: it warps them as if static; fovpt_warp_motion extrapolates them by one
+ * interval's difference (no acceleration, and not their reflections and shadows).  Its resolve is fovpt_warp's: a strip that a mesh
+ * vacates, if it is wider than fill_radius rings, stays class empty and keeps showing the source pixel -- the mesh's old image (on the
+ * wall scene of tests/test_warp_motion_cpu.py already at advance 1 with a move of 8 px).  Resampling: a pixel is copied, not interpolated.  Packets: a packet's texel ownership belongs to the rendered camera, so
  * the warp is the last stage on the server, or a client's job after decoding.
  * On an MI355X at 1920 x 1080, both images, fill_radius 2, a call takes 0.050 .. 0.054 ms with a caller's G-buffer and 0.262 .. 0.265 ms with
  * its own trace over a slide, a turn and a dolly-in (fovpt_expose FIXED, a plain full-frame pass: 0.020 ms; one fovpt_render: 0.70 ms)
- * (DESIGN.md, section 21).                                                                                                      */
+ * (DESIGN.md, section 21).  fovpt_warp_motion, same frame, a slide, advance 1, alternated with fovpt_warp in one process: 0.050 ms with
+ * nothing moved (fovpt_warp's launches); 0.060 ms with a quarter of the meshes turning (62 % of the source pixels on moved meshes) and
+ * 0.063 ms with all of them, against fovpt_warp's 0.050 ms, with the step's G-buffer; 0.279 and 0.284 ms against 0.267 and 0.269 ms
+ * with its own trace; direct / filled / empty 92.2 / 3.4 / 4.4 % against fovpt_warp's 94.2 / 1.5 / 4.4 %.     */
 typedef struct fovpt_warp_camera { fovpt_float3 eye, U, V, W; } fovpt_warp_camera;        /* 48 bytes: LaunchParams.camera's layout */
 #define FOVPT_WARP_COLOR 1          /* warp the float4 image   */
 #define FOVPT_WARP_RGBA  2          /* warp the rgba8 image    */
@@ -979,6 +1017,20 @@ int fovpt_warp(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_warp_c
                uint32_t* out_map /* may be NULL */);
 int fovpt_warp_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 int fovpt_warp_counts(fovpt_ctx* ctx, struct fovpt_warp_counts* out);
+#define FOVPT_WARP_MAX_ADVANCE 4.0f
+typedef struct fovpt_warp_motion_config {   /* 32 bytes */
+    int32_t images;                 /* FOVPT_WARP_* bits, at least one; default 3 */
+    int32_t fill_radius;            /* 0 .. FOVPT_WARP_MAX_RADIUS; default 2 */
+    float   advance;                /* 0 .. FOVPT_WARP_MAX_ADVANCE, finite; default 1.0f: how far past the rendered frame the image is
+                                       shown, in units of the interval between the last two temporal steps (a convention, not a
+                                       measurement) */
+    int32_t _reserved[5];           /* 0 */
+} fovpt_warp_motion_config;
+int fovpt_warp_motion_defaults(fovpt_warp_motion_config* out);
+int fovpt_warp_motion(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_warp_camera* to, const fovpt_warp_motion_config* mc,
+                      const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, const fovpt_float4* in_color /* NULL: accum_buffer */,
+                      const uint32_t* in_rgba /* NULL: frame_buffer */, fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */,
+                      uint32_t* out_map /* may be NULL */);
 int fovpt_temporal_gbuffer(fovpt_ctx* ctx, fovpt_gbuffer_ptrs* out);
 
 /* ---- gaze-metered focus distance and depth of field ----------------------------------------------------------------------------
@@ -1520,6 +1572,7 @@ static_assert(sizeof(struct fovpt_expose_state) == 32 && offsetof(struct fovpt_e
 static_assert(sizeof(fovpt_warp_camera) == 48 && offsetof(fovpt_warp_camera, W) == 36, "warp camera ABI");
 static_assert(sizeof(fovpt_warp_config) == 32 && offsetof(fovpt_warp_config, fill_radius) == 4, "warp config ABI");
 static_assert(sizeof(struct fovpt_warp_counts) == 32 && offsetof(struct fovpt_warp_counts, direct) == 8, "warp counts ABI");
+static_assert(sizeof(fovpt_warp_motion_config) == 32 && offsetof(fovpt_warp_motion_config, advance) == 8, "warp motion config ABI");
 static_assert(sizeof(fovpt_focus_config) == 64 && offsetof(fovpt_focus_config, strength) == 16 && offsetof(fovpt_focus_config, _reserved) == 36,
               "focus config ABI");
 static_assert(sizeof(struct fovpt_focus_state) == 32 && offsetof(struct fovpt_focus_state, count) == 16, "focus state ABI");

@@ -1,0 +1,138 @@
+"""A seeded fuzz of fovpt_warp_motion on the GPU: a random loop of 4 to 6 frames on the box scene -- per frame a random subset of
+the four update kinds (vertices, transforms, skinned, morphed; refit or rebuild), a temporal step through one of the three calls
+(fovpt_temporal, fovpt_temporal_motion, fovpt_post), a random camera to render and one to warp to, a random advance in [0, 4],
+fill radius and image choice, the call's own trace or the step's G-buffer -- with every frame's warp bit for bit against
+tests/warp_motion_ref.py on the GPU's own inputs, and fovpt_warp_motion's refusal where the tracking is not on yet.
+FOVPT_FUZZW_FROM / FOVPT_FUZZW_TO widen the sweep."""
+import os
+
+import numpy as np
+import pytest
+
+import skin_ref as sk
+import transform_ref as tf
+import warp_ref as wr
+from fovpathtracing_optixcodelatest_amd import lib, renderer, scenes
+
+from common import cfg_foveated, cfg_uniform, make_gpu
+from postprocess_common import BOX_CAMERA, box_model
+from temporal_motion_common import KINDS
+from test_warp_gpu import to_camera
+from warp_motion_common import STEPS, Intervals, check, frame_data, mcfg
+
+pytestmark = pytest.mark.gpu
+DEFAULT_SEEDS = range(0, 6)
+SEEDS = range(int(os.environ.get("FOVPT_FUZZW_FROM", DEFAULT_SEEDS.start)), int(os.environ.get("FOVPT_FUZZW_TO", DEFAULT_SEEDS.stop)))
+E_NO_FRAME = -5
+SLAB, BOX = 0, 1
+CAM = BOX_CAMERA
+
+
+def params(seed):
+    rng = np.random.default_rng(41000 + seed)
+    frames = int(rng.integers(4, 7))
+    w, h = 129 + int(rng.integers(-20, 21)), 75 + int(rng.integers(-10, 11))
+    p = dict(frames=frames, size=(w, h), uniform=int(rng.random() < 0.25))
+    r_in = int(rng.integers(0, 30))
+    p["radii"] = (r_in, r_in + int(rng.integers(0, 50)))
+    p["gaze"] = [(int(rng.integers(0, w)), int(rng.integers(0, h))) for _ in range(frames)]
+    p["camera"] = [tuple(float(x) for x in rng.normal(0, 0.15, 6)) for _ in range(frames)]
+    p["to"] = [tuple(float(x) for x in rng.normal(0, 0.3, 6)) for _ in range(frames)]
+    # per frame: the kinds that move the box, in call order, each with (turn in degrees, carry, morph weight, rebuild); whether the slab moves too
+    p["kinds"] = [[KINDS[i] for i in rng.permutation(4)[:int(rng.integers(0, 4))]] for _ in range(frames)]
+    p["slab"] = [bool(rng.random() < 0.25) for _ in range(frames)]
+    p["step"] = [STEPS[int(rng.integers(0, 3))] for _ in range(frames)]
+    p["advance"] = [0.0 if rng.random() < 0.1 else 4.0 if rng.random() < 0.1 else float(np.float32(rng.uniform(0.0, 4.0))) for _ in range(frames)]
+    # so that every seed reaches the kernel's moved branch beside its unmoved one: tracking is on by the second step, and the third
+    # frame moves the box alone and is extrapolated
+    if p["step"][1] == "temporal":
+        p["step"][1] = "temporal_motion"
+    p["kinds"][2] = p["kinds"][2] or [KINDS[seed % 4]]
+    p["slab"][2] = False
+    p["advance"][2] = p["advance"][2] or 1.0
+    p["moves"] = [[(float(rng.uniform(-30, 30)), tuple(float(x) for x in rng.uniform(-0.6, 0.6, 3)), float(np.float32(rng.uniform(0.2, 1.2))),
+                    bool(rng.random() < 0.25)) for _ in ks] for ks in p["kinds"]]
+    p["radius"] = [int(rng.integers(0, 5)) for _ in range(frames)]
+    p["images"] = [int(rng.integers(1, 4)) for _ in range(frames)]
+    p["reuse"] = [bool(rng.random() < 0.5) for _ in range(frames)]
+    return p
+
+
+def box_update(model, kind, deg, t, weight):
+    """What MotionChecker.update(kind=...) takes for the box: a turn about its axis by deg and a carry by t, as positions, a matrix
+    or a two-joint palette; for `morphed` the weight of its one target and that palette."""
+    v = model.meshes[BOX].vertex
+    m = tf.rotation_translation(deg, (0.0, 0.5, 0.0), t)
+    if kind == "vertices":
+        return tf.apply(v, m)
+    if kind == "transforms":
+        return m
+    pose = sk.bend_pose(v, 2, deg, t)
+    return pose if kind == "skinned" else (np.float32([weight]), pose)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_random_warp_motion(seed):
+    p = params(seed)
+    w, h = p["size"]
+    model = box_model()
+    cfg = cfg_uniform(1) if p["uniform"] else cfg_foveated(p["radii"][0], p["radii"][1], (1, 1, 2))
+    cfg.write_guides = 1
+    r = make_gpu(model, scenes.ambient_probe(48, 27, 2.5), CAM, p["size"], cfg, gaze=p["gaze"][0])
+    ck = Intervals(r)
+    rng = np.random.default_rng(seed)
+    box = model.meshes[BOX].vertex
+    ck.skins = {BOX: sk.bend(box, 2)}
+    ck.morphs = {BOX: [rng.uniform(-0.2, 0.2, box.shape).astype(np.float32)]}
+    r.set_skins(ck.skins)
+    r.set_morphs(ck.morphs)
+    eye, look = np.array(CAM["eye"], np.float64), np.array(CAM["lookat"], np.float64)
+    took_moved = took_unmoved = took_plain = 0
+    for k in range(p["frames"]):
+        for kind, (deg, t, weight, rebuild) in zip(p["kinds"][k], p["moves"][k]):
+            ck.update({BOX: box_update(model, kind, deg, t, weight)}, rebuild=rebuild, kind=kind)
+        if p["slab"][k]:
+            ck.update({SLAB: tf.rotation_translation(3.0 * k, (0.0, -1.0, 0.0), (0.0, 0.05 * k, 0.0))}, kind="transforms")
+        mv = np.array(p["camera"][k])
+        at, lk = eye + mv[:3], look + mv[3:]
+        r.setCamera(renderer.Camera(tuple(at), tuple(lk), CAM["up"], CAM["fovy"], w / float(h)))
+        r.launchParams.frame.c.x, r.launchParams.frame.c.y = p["gaze"][k]
+        r.launchParams.frame.subframe_index = k
+        r.render()
+        ck.end_interval(p["step"][k])
+        tv = np.array(p["to"][k])
+        to, want_cam = to_camera((tuple(at + tv[:3]), tuple(lk + tv[3:])), p["size"])
+        label = (seed, k, p["step"][k], p["kinds"][k], p["advance"][k])
+        if not ck.tracking:
+            with pytest.raises(lib.FovptError) as e:         # only plain fovpt_temporal steps so far
+                r.warp_motion(to, mcfg(advance=p["advance"][k]))
+            assert e.value.code == E_NO_FRAME, label
+            continue
+        gb, uv = frame_data(r)
+        want = check(r, ck, to, want_cam, gb, uv, r.downloadAccum(), r.downloadPixels(), p["advance"][k], p["radius"][k], p["images"][k],
+                     r.temporal_gbuffer() if p["reuse"][k] else None, label)
+        if ck.moved_last() and p["advance"][k] != 0.0:       # the motion kernel ran
+            hit = gb["prim"] != wr.MISS
+            on_moved = hit & ck.last["moved"][ck.mesh_of_prim[np.where(hit, gb["prim"], 0).astype(np.int64)]]
+            took_moved += int(on_moved.sum())
+            took_unmoved += int((hit & ~on_moved).sum())
+        else:
+            took_plain += 1
+    print("seed %d: %d frames, moved-branch pixels %d, unmoved hit pixels beside them %d, frames through fovpt_warp's scatter %d" %
+          (seed, p["frames"], took_moved, took_unmoved, took_plain))
+    assert took_moved > 0 and took_unmoved > 0
+    r.close()
+
+
+def test_the_seeds_reach_the_paths():
+    ps = [params(s) for s in DEFAULT_SEEDS]
+    assert all(4 <= q["frames"] <= 6 for q in ps) and len({q["frames"] for q in ps}) >= 2
+    assert {k for q in ps for f in q["kinds"] for k in f} == set(KINDS)
+    assert {s for q in ps for s in q["step"]} == set(STEPS)
+    assert any(len(f) == 0 for q in ps for f in q["kinds"]) and any(len(f) >= 2 for q in ps for f in q["kinds"])
+    assert any(m[3] for q in ps for f in q["moves"] for m in f) and any(not m[3] for q in ps for f in q["moves"] for m in f)
+    assert any(x for q in ps for x in q["slab"]) and any(x for q in ps for x in q["reuse"]) and any(not x for q in ps for x in q["reuse"])
+    assert {x for q in ps for x in q["images"]} == {1, 2, 3} and {x for q in ps for x in q["radius"]} >= {0, 4}
+    adv = [x for q in ps for x in q["advance"]]
+    assert min(adv) == 0.0 and max(adv) <= 4.0 and any(0.0 < x < 4.0 for x in adv)
+    assert any(q["step"][0] == "temporal" for q in ps)       # a frame that fovpt_warp_motion refuses
