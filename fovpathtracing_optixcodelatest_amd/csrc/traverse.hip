@@ -14,6 +14,7 @@
 #include <assert.h>
 #include "fovpt_pixel.h"            // V3, cross, dot
 #include "fovpt_queue.h"            // ShardMap
+#include "fovpt_stream.h"           // ld_stream, st_stream: the once-touched state
 
 // waves per SIMD the traversal kernel is compiled for (caps VGPRs at 64); measured best
 #ifndef FOVPT_V_WAVES
@@ -268,16 +269,16 @@ __device__ inline void store_hit(const PathState& ps, uint32_t ph, const QuadTra
     uint32_t mp = cand ? T.bprim : 0xffffffffu;
     mp = min(mp, quad_rot2(mp));
     mp = min(mp, quad_rot1(mp));
-    if (cand && T.bprim == mp) ps.hit[ph] = make_float4(T.bt, T.bu, T.bv, __uint_as_float(T.bpos));
+    if (cand && T.bprim == mp) st_stream<FOVPT_STREAM_HIT>(ps.hit + ph, make_float4(T.bt, T.bu, T.bv, __uint_as_float(T.bpos)));
 }
 // any-hit: the deferred NEE add of SampleLights / SampleShadow (deviceProgram.cu:323-341,367-385).
 // Every (slot, depth) cell has exactly one writer, so this is a plain store and the shadow rays of a
 // bounce may run at any time before resolve (own stream, see fovpt_api.hip)
 __device__ inline void store_shadow(const PathState& ps, const ShadowQueue& sq, uint32_t ph, uint32_t slot, uint32_t target, bool occluded)
 {
-    const float4 val = occluded ? sq.val_occ[ph] : sq.val_vis[ph];
+    const float4 val = occluded ? ld_stream<FOVPT_STREAM_SHADOWQ>(sq.val_occ + ph) : ld_stream<FOVPT_STREAM_SHADOWQ>(sq.val_vis + ph);
     float4* cell = target == 0xffffffffu ? ps.alpha + slot : ps.rad + ((size_t)slot * ps.stride + target);
-    *cell = make_float4(val.x, val.y, val.z, 0.f);
+    st_stream<FOVPT_STREAM_CELLS>(cell, make_float4(val.x, val.y, val.z, 0.f));
 }
 
 // na live lanes of the wave, nn of them at a node: does the node phase end here?  (FOVPT_VOTE_C = 64: never -- the phases of rounds 1-3)
@@ -370,14 +371,15 @@ __device__ inline void traverse_shadow_pool(const SceneView& sc, const PathState
         const uint32_t n_idle = (uint32_t)__builtin_popcountll(idle) >> 2;
         if (n_idle == 16u || (n_idle >= (uint32_t)FOVPT_REFILL && next < end)) {
             if (T.cur == TRAV_DONE) {
-                if (pending && q.j == 0) store_shadow(ps, sq, ph, __float_as_uint(sq.o[ph].w), __float_as_uint(sq.d[ph].w), occluded);
+                if (pending && q.j == 0) store_shadow(ps, sq, ph, __float_as_uint(ld_stream<FOVPT_STREAM_SHADOWQ>(&sq.o[ph].w)),
+                                                          __float_as_uint(ld_stream<FOVPT_STREAM_SHADOWQ>(&sq.d[ph].w)), occluded);
                 pending = false;
                 // idle quads below mine (all four lanes of an idle quad are set in the mask)
                 const uint32_t rank = (__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u)) - q.j) >> 2;
                 const uint32_t idx = next + rank;
                 if (idx < end) {
                     ph = map.phys16(idx, next, cap);
-                    ray_setup(r, sq.o[ph], sq.d[ph]);
+                    ray_setup(r, ld_stream<FOVPT_STREAM_SHADOWQ>(sq.o + ph), ld_stream<FOVPT_STREAM_SHADOWQ>(sq.d + ph));
                     T.start(stack, q);
                     pending = true; occluded = false;
                 }
@@ -441,7 +443,7 @@ __global__ __launch_bounds__(FOVPT_TBLOCK, FOVPT_V_WAVES) void k_traverse(SceneV
         RayT r;
         QuadTrav T;
         const uint32_t ph = map.phys16(i, i0, cap);
-        const float4 o = queue.o[ph], d = queue.d[ph];
+        const float4 o = ld_stream<FOVPT_STREAM_RAYQ>(queue.o + ph), d = ld_stream<FOVPT_STREAM_RAYQ>(queue.d + ph);
         ray_setup(r, o, d);
         traverse_quad(sc, r, stack, q, T, cnt->diag[0]);
         store_hit(ps, ph, T);

@@ -26,6 +26,7 @@
 #include "fovpt_pixel.h"            // V3, ring_alive, find_last_writer, the tone map (shared with denoise.hip)
 #include "fovpt_scene.h"            // load_tri_off, tex2d (shared with reconstruct.hip)
 #include "fovpt_queue.h"            // sel_first, sel_mask, ShardMap (shared with traverse.hip)
+#include "fovpt_stream.h"           // ld_stream, st_stream: the once-touched state (shared with traverse.hip)
 #include "fovpt_shade_fn.h"         // Rng, the probe, the Disney BSDF (shared with shade_debug.hip)
 
 namespace {
@@ -184,21 +185,24 @@ __device__ inline void generate_rays(const FrameDev& fd, const PathState& ps, co
         const V3 U = v3(fd.U[0], fd.U[1], fd.U[2]), V = v3(fd.V[0], fd.V[1], fd.V[2]), W = v3(fd.W[0], fd.W[1], fd.W[2]);
         const V3 dir = normalize(dx * U + dy * V + W);                      // :491
         ray_dir = dir;
-        ps.rng[slot] = make_uint4(rng.s1, rng.s2, 0u, 0u);                  // stateFlags 0, depth 0
+        st_stream<FOVPT_STREAM_STATE>(ps.rng + slot, make_uint4(rng.s1, rng.s2, 0u, 0u));     // stateFlags 0, depth 0
         // Nothing else is initialised: pathThroughput / rayEta are (1,1,1) / 1 until the first shaded hit
         // (k_shade), the radiance cells [0, depth) and alpha are written exactly once before resolve
         // reads them (depth and FLAG_ALPHA_SET tell it which), :450-451
-        if (ps.guide_n) { ps.guide_n[slot] = make_float4(0.f, 0.f, 0.f, 0.f); ps.guide_a[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }
+        if (ps.guide_n) {
+            st_stream<FOVPT_STREAM_CELLS>(ps.guide_n + slot, make_float4(0.f, 0.f, 0.f, 0.f));
+            st_stream<FOVPT_STREAM_CELLS>(ps.guide_a + slot, make_float4(0.f, 0.f, 0.f, 0.f));
+        }
         if (s == P.spp - 1) {                                               // backplate of the last sample, :495
             float u, v;
             probe_dir_to_uv(dir, u, v);
-            ps.backplate[P.launch_base + (ly - P.row0) * P.gw + lx] = probe_eval(fd.probe, fd.probe_row_mul, u, v);
+            st_stream<FOVPT_STREAM_CELLS>(ps.backplate + (P.launch_base + (ly - P.row0) * P.gw + lx), probe_eval(fd.probe, fd.probe_row_mul, u, v));
         }
     }
     const uint32_t pos = block_append(cnt, FOVPT_CNT_Q(0), cap, live, s_scratch, sel);
     if (live) {
-        queue0.o[pos] = make_float4(fd.eye[0], fd.eye[1], fd.eye[2], __uint_as_float(slot));
-        queue0.d[pos] = f4(ray_dir, 0.f);
+        st_stream<FOVPT_STREAM_RAYQ>(queue0.o + pos, make_float4(fd.eye[0], fd.eye[1], fd.eye[2], __uint_as_float(slot)));
+        st_stream<FOVPT_STREAM_RAYQ>(queue0.d + pos, f4(ray_dir, 0.f));
     }
 }
 
@@ -285,11 +289,11 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
         sh_o = sh_d = sh_vis = sh_occ = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < n) {
             const uint32_t ph = mq.phys(i, cap);
-            const float4 o4 = queue_in.o[ph], d4 = queue_in.d[ph];
+            const float4 o4 = ld_stream<FOVPT_STREAM_RAYQ>(queue_in.o + ph), d4 = ld_stream<FOVPT_STREAM_RAYQ>(queue_in.d + ph);
             slot = __float_as_uint(o4.w);
-            const float4 hit = ps.hit[ph];
+            const float4 hit = ld_stream<FOVPT_STREAM_HIT>(ps.hit + ph);
             const uint32_t tpos = __float_as_uint(hit.w);
-            uint4 rs = ps.rng[slot];
+            uint4 rs = ld_stream<FOVPT_STREAM_STATE>(ps.rng + slot);
             uint32_t flags = rs.z & 0xffu;
             int depth = (int)(rs.z >> 8);
             if (tpos == 0xffffffffu) {
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                     // segment is counted (one more radiance cell), see include/fovpt.h
                     const V3 dir = v3(d4);
                     const float bsdfPdf = d4.w;                                            // pdf of the sample that sent this ray
-                    const V3 thr = v3(ps.thr[slot]);
+                    const V3 thr = v3(ld_stream<FOVPT_STREAM_STATE>(ps.thr + slot));
                     float u, v;
                     probe_dir_to_uv(dir, u, v);
                     const fovpt_probe& pr = fd.probe;                                      // ProbePdf, Probe.cuh:69-93
@@ -312,7 +316,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                     else skyPdf *= float(pr.width) * float(pr.height) / (2.0f * kPi * kPi * sinTheta);
                     const float weight = 0.5f * bsdfPdf / (0.5f * bsdfPdf + 0.5f * skyPdf);
                     const V3 rad = v3(0.f) + (weight * v3(probe_eval(pr, fd.probe_row_mul, u, v))) * thr;
-                    ps.rad[(size_t)slot * ps.stride + depth] = f4(rad, 0.f);
+                    st_stream<FOVPT_STREAM_CELLS>(ps.rad + ((size_t)slot * ps.stride + depth), f4(rad, 0.f));
                     depth += 1;
                 }
             } else {
@@ -323,7 +327,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                 Rng rng_probe; rng_probe.s1 = rs.x; rng_probe.s2 = rs.y;
                 V3 wi, skyColor; float skyPdf;
                 probe_sample(fd.probe, fd.guide_x, fd.guide_y, fd.probe_rec, fd.probe_row_mul, wi, skyColor, skyPdf, rng_probe);
-                const float4 thr_in = ps.thr[slot];                            // (unused garbage until the first shaded hit wrote it)
+                const float4 thr_in = ld_stream<FOVPT_STREAM_STATE>(ps.thr + slot);      // (unused garbage until the first shaded hit wrote it)
                 const TriRec T = load_tri_off(sc.tris, tpos << 4);            // tpos: offset in 16-byte units
                 const MeshDev M = sc.meshes[T.mesh];
                 const Mat& mat = M.material;
@@ -359,8 +363,8 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                         albedo = v3(tex2d(M.tex, tcx, tcy));
                     }
                     if (ps.guide_n && depth == 0 && (flags & FLAG_SECONDARY) == 0) {       // :509-512, :653-654
-                        ps.guide_n[slot] = f4(N, 0.f);
-                        ps.guide_a[slot] = f4(albedo, 0.f);
+                        st_stream<FOVPT_STREAM_CELLS>(ps.guide_n + slot, f4(N, 0.f));
+                        st_stream<FOVPT_STREAM_CELLS>(ps.guide_a + slot, f4(albedo, 0.f));
                     }
                     float outEta;
                     if (rayEta == 1.0f)                                                    // :673-683
@@ -409,7 +413,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                         // alpha += thr * shadowSample happens regardless of what follows (:693); alpha is still
                         // (0,0,0) here because only a primary hit gets this far on a catcher
                         flags |= FLAG_ALPHA_SET;
-                        if (same) ps.alpha[slot] = f4(v3(0.f) + alpha_occ, 0.f);
+                        if (same) st_stream<FOVPT_STREAM_CELLS>(ps.alpha + slot, f4(v3(0.f) + alpha_occ, 0.f));
                         else {
                             want_shadow = true;
                             sh_o = f4(P, __uint_as_float(slot)); sh_d = f4(wi, __uint_as_float(0xffffffffu));
@@ -427,7 +431,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                             sh_o = f4(P, __uint_as_float(slot)); sh_d = f4(wi, __uint_as_float((uint32_t)depth));
                             sh_vis = f4(rad_vis, 0.f); sh_occ = f4(rad_occ, 0.f);
                         } else {
-                            *cell = f4(rad_occ, 0.f);
+                            st_stream<FOVPT_STREAM_CELLS>(cell, f4(rad_occ, 0.f));
                         }
                         flags |= FLAG_SECONDARY;
                         depth += 1;                                                        // :529
@@ -447,7 +451,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                             }
                             if (!rr_kill) {
                                 next_o = P; next_d = bsdfDir; next_pdf = bsdfPdf;
-                                ps.thr[slot] = f4(thr, rayEta);
+                                st_stream<FOVPT_STREAM_STATE>(ps.thr + slot, f4(thr, rayEta));
                                 want_next = true;
                             }
                         }
@@ -456,7 +460,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
                 }
             }
             rs.z = flags | ((uint32_t)depth << 8);
-            ps.rng[slot] = rs;
+            st_stream<FOVPT_STREAM_STATE>(ps.rng + slot, rs);
         }
         // ---- wavefront-ballot compaction into the next queues
         uint32_t spos, qpos;
@@ -464,8 +468,14 @@ __global__ __launch_bounds__(FOVPT_BLOCK, FOVPT_V_SHADEWAVES) void k_shade(const
             block_append2d(cnt, FOVPT_CNT_SQ(depth_iter), want_shadow, FOVPT_CNT_Q(depth_iter + 1), want_next, next_d.y > 0.0f, cap, s_scratch, spos, qpos, sel);
         else
             block_append2(cnt, FOVPT_CNT_SQ(depth_iter), want_shadow, FOVPT_CNT_Q(depth_iter + 1), want_next, cap, s_scratch, spos, qpos, sel);
-        if (want_shadow) { sq.o[spos] = sh_o; sq.d[spos] = sh_d; sq.val_vis[spos] = sh_vis; sq.val_occ[spos] = sh_occ; }
-        if (want_next) { queue_out.o[qpos] = f4(next_o, __uint_as_float(slot)); queue_out.d[qpos] = f4(next_d, next_pdf); }
+        if (want_shadow) {
+            st_stream<FOVPT_STREAM_SHADOWQ>(sq.o + spos, sh_o); st_stream<FOVPT_STREAM_SHADOWQ>(sq.d + spos, sh_d);
+            st_stream<FOVPT_STREAM_SHADOWQ>(sq.val_vis + spos, sh_vis); st_stream<FOVPT_STREAM_SHADOWQ>(sq.val_occ + spos, sh_occ);
+        }
+        if (want_next) {
+            st_stream<FOVPT_STREAM_RAYQ>(queue_out.o + qpos, f4(next_o, __uint_as_float(slot)));
+            st_stream<FOVPT_STREAM_RAYQ>(queue_out.d + qpos, f4(next_d, next_pdf));
+        }
     }
 }
 
@@ -541,22 +551,22 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_resolve(const FrameDev fd, Path
         V3 result = v3(0.0f), alpha = v3(0.0f), gnorm = v3(0.0f), galb = v3(0.0f);
         for (uint32_t s = 0; s < P.spp; s++) {                                     // :536-537, in sample order
             const uint32_t slot = s0 + s;
-            if (ps.guide_n) { gnorm = gnorm + v3(ps.guide_n[slot]); galb = galb + v3(ps.guide_a[slot]); }   // :510-511
+            if (ps.guide_n) { gnorm = gnorm + v3(ld_stream<FOVPT_STREAM_CELLS>(ps.guide_n + slot)); galb = galb + v3(ld_stream<FOVPT_STREAM_CELLS>(ps.guide_a + slot)); }   // :510-511
             const float4* cells = ps.rad + (size_t)slot * ps.stride;                 // one 16*D-byte record per slot
             // the path's `depth` segments counted, cell dd holds prd.radiance of segment dd; the reference
             // adds nothing for a segment it never reached
-            const uint32_t st = ps.rng[slot].z;
+            const uint32_t st = ld_stream<FOVPT_STREAM_STATE>(&ps.rng[slot].z);
             const int nseg = min((int)(st >> 8), fd.max_depth);
-            const V3 direct = v3(0.0f) + (nseg > 0 ? v3(cells[0]) : v3(0.0f));          // :523
+            const V3 direct = v3(0.0f) + (nseg > 0 ? v3(ld_stream<FOVPT_STREAM_CELLS>(cells)) : v3(0.0f));          // :523
             V3 indirect = v3(0.0f);
             for (int dd = 1; dd < nseg; dd++)                                          // :526, in bounce order
-                indirect = indirect + v3(cells[dd]);
+                indirect = indirect + v3(ld_stream<FOVPT_STREAM_CELLS>(cells + dd));
             result = result + (direct + indirect);
-            alpha = alpha + ((st & FLAG_ALPHA_ONE) ? v3(1.0f) : (st & FLAG_ALPHA_SET) ? v3(ps.alpha[slot]) : v3(0.0f));
+            alpha = alpha + ((st & FLAG_ALPHA_ONE) ? v3(1.0f) : (st & FLAG_ALPHA_SET) ? v3(ld_stream<FOVPT_STREAM_CELLS>(ps.alpha + slot)) : v3(0.0f));
         }
         const float sppf = (float)P.spp;
         { const float inv = 1.0f / sppf; alpha = alpha * inv; gnorm = gnorm * inv; galb = galb * inv; }   // :541-543
-        const V3 backplate = v3(ps.backplate[P.launch_base + li]);
+        const V3 backplate = v3(ld_stream<FOVPT_STREAM_CELLS>(ps.backplate + (P.launch_base + li)));
         const V3 color = (backplate * sppf) * sub_sv(1.0f, alpha) + result;        // :558
         const V3 accum_color = div_vs(color, sppf);                                // :560
         s_gn[threadIdx.x] = f4(gnorm, 1.0f); s_ga[threadIdx.x] = f4(galb, 1.0f);

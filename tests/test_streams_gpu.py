@@ -1,0 +1,178 @@
+"""The once-touched wavefront state -- ray queues, hit records, rng / thr, shadow queues, radiance cells, alpha, backplate and
+guides (csrc/fovpt_stream.h) -- is read and written through ld_stream / st_stream, whose flavour says where a line lives and must
+never change a value.  Every case renders a small frame that runs one group of those accesses and compares frame and accum BIT FOR
+BIT with the CPU oracle: state sets and lanes reused over consecutive frames, probe and texture loads beside the state, the guide
+streams, the alpha cell and the target = 0xffffffff shadow record of a shadow catcher, a chunked accumulating frame, the two
+ranks of a tile-sharded frame (k_generate_owned, zero_holes), fewer and more bounces than shadow-queue buffers, and a frame whose
+last block and last 16-ray round are partly filled."""
+import numpy as np
+import pytest
+
+from fovpathtracing_optixcodelatest_amd import abi, scenes
+
+from common import cfg_foveated, make_gpu, make_oracle
+
+pytestmark = pytest.mark.gpu
+
+SIZE = (96, 64)
+
+
+def _cfg(max_depth=4):
+    return cfg_foveated(12, 28, (1, 2, 8), max_depth=max_depth)          # periphery 1, middle 2, fovea 8 spp
+
+
+def _bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def _catcher_box():
+    m = scenes.cornell_box()
+    m.meshes[0].material.flags = abi.MATERIAL_FLAG_SHADOW_CATCHER          # floor + ceiling + back wall
+    return m
+
+
+_SCENES = {
+    "cornell": (scenes.cornell_box, scenes.sky_probe, scenes.CORNELL_CAMERA),
+    "atrium": (lambda: scenes.atrium(2000), lambda: scenes.sky_probe(64, 32), scenes.ATRIUM_CAMERA),
+    "catcher": (_catcher_box, scenes.sky_probe, scenes.CORNELL_CAMERA),
+}
+_REFERENCE = {}
+
+
+def _reference(oracle, name, size=SIZE, max_depth=4, guides=0, spp=(1, 2, 8)):
+    """The oracle's frame of one case: computed once, shared by the tests that need it, never written to."""
+    key = (name, size, max_depth, guides, spp)
+    if key not in _REFERENCE:
+        model, probe, cam = _SCENES[name]
+        cfg = cfg_foveated(12, 28, spp, max_depth=max_depth)
+        cfg.write_guides = guides
+        S, F = make_oracle(oracle, model(), probe(), cam, size)
+        cnt = oracle.render(S, F, cfg)
+        out = {"accum": F.accum.copy(), "frame": F.frame.copy(), "paths": cnt[2]}
+        if guides:
+            out.update(normal=F.normal.copy(), color=F.color.copy(), albedo=F.albedo.copy())
+        for v in out.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _REFERENCE[key] = out
+    return _REFERENCE[key]
+
+
+def _gpu(name, cfg, size=SIZE):
+    model, probe, cam = _SCENES[name]
+    return make_gpu(model(), probe(), cam, size, cfg)
+
+
+def _same(r, ref):
+    return _bits(r.downloadAccum(), ref["accum"]) and np.array_equal(r.downloadPixels(), ref["frame"])
+
+
+def test_ten_frames_reuse_every_state_set_and_lane(oracle):
+    """Ten consecutive frames with two frames in flight (all four state sets, both lanes), then with one: the same frame every
+    time, the oracle's."""
+    ref = _reference(oracle, "cornell")
+    got = []
+    for fif in (2, 1):
+        cfg = _cfg()
+        cfg.frames_in_flight = fif
+        r = _gpu("cornell", cfg)
+        for _ in range(10):
+            r.launchParams.frame.subframe_index = 0
+            r.render_async()
+        r.synchronize()
+        got.append((r.downloadAccum(), r.downloadPixels()))
+        r.close()
+    assert _bits(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+    for a, f in got:
+        assert _bits(a, ref["accum"]) and np.array_equal(f, ref["frame"])
+
+
+def test_textured_scene_with_a_sky_probe(oracle):
+    """Probe, guide-table and texture loads (plain) beside the hinted state."""
+    ref = _reference(oracle, "atrium")
+    r = _gpu("atrium", _cfg())
+    r.render()
+    assert _same(r, ref)
+    assert r.stats().paths == ref["paths"]
+    r.close()
+
+
+def test_guide_streams(oracle):
+    ref = _reference(oracle, "atrium", guides=1)
+    cfg = _cfg()
+    cfg.write_guides = 1
+    r = _gpu("atrium", cfg)
+    r.render()
+    f = r.launchParams.frame
+    for ptr, want in ((f.normal_buffer, ref["normal"]), (f.color_buffer, ref["color"]), (f.albedo_buffer, ref["albedo"])):
+        assert _bits(r.download(ptr, np.empty((SIZE[1], SIZE[0], 4), np.float32)), want)
+    assert _same(r, ref)
+    r.close()
+
+
+def test_shadow_catcher_alpha_cell_and_record(oracle):
+    ref = _reference(oracle, "catcher")
+    r = _gpu("catcher", _cfg())
+    r.render()
+    assert _same(r, ref)
+    r.close()
+
+
+def test_chunked_accumulating_frame(oracle, monkeypatch):
+    """A slot budget that cuts the 96 x 64 frame into chunks (the accum_before path), accumulate on, subframes 0, 1, 2."""
+    monkeypatch.setenv("FOVPT_SLOT_BUDGET", "3000")
+    model, probe, cam = _SCENES["cornell"]
+    cfg = _cfg()
+    cfg.accumulate = 1
+    r = make_gpu(model(), probe(), cam, SIZE, cfg)
+    S, F = make_oracle(oracle, model(), probe(), cam, SIZE)
+    for k in range(3):
+        for lp in (r.launchParams, F.lp):
+            lp.frame.subframe_index = k
+        r.render()
+        oracle.render(S, F, cfg)
+        assert _bits(r.downloadAccum(), F.accum) and np.array_equal(r.downloadPixels(), F.frame), k
+    r.close()
+
+
+def test_two_ranks_on_one_gpu_sum_to_the_frame(oracle):
+    """world = 2: k_generate_owned and zero_holes; the two frames add up to the unsharded one."""
+    ref = _reference(oracle, "atrium")
+    sa = np.zeros(ref["accum"].shape, np.float32)
+    sf = np.zeros(ref["frame"].shape, np.uint64)
+    for rank in (0, 1):
+        cfg = _cfg()
+        cfg.rank, cfg.world = rank, 2
+        r = _gpu("atrium", cfg)
+        r.render()
+        sa += r.downloadAccum()
+        sf += r.downloadPixels()
+        r.close()
+    full = _gpu("atrium", _cfg())
+    full.render()
+    fa, ff = full.downloadAccum(), full.downloadPixels()
+    full.close()
+    assert _bits(sa, fa) and np.array_equal(sf.astype(np.uint32), ff)
+    assert _bits(fa, ref["accum"]) and np.array_equal(ff, ref["frame"])
+
+
+@pytest.mark.parametrize("depth", [1, 8])
+def test_fewer_and_more_bounces_than_shadow_queue_buffers(oracle, depth):
+    ref = _reference(oracle, "cornell", max_depth=depth)
+    r = _gpu("cornell", _cfg(depth))
+    r.render()
+    assert _same(r, ref)
+    r.close()
+
+
+def test_partial_blocks_and_a_partly_filled_last_round(oracle):
+    """70 x 45 at 1 / 2 / 3 spp: the width is no multiple of 64 (k_resolve's tiles), and the camera rays are neither a multiple
+    of 256 (the kernels' blocks) nor of 16 (k_traverse's rounds)."""
+    size, spp = (70, 45), (1, 2, 3)
+    ref = _reference(oracle, "cornell", size=size, spp=spp)
+    assert ref["paths"] % 256 != 0 and ref["paths"] % 16 != 0
+    r = _gpu("cornell", cfg_foveated(12, 28, spp), size)
+    r.render()
+    assert _same(r, ref)
+    assert r.stats().paths == ref["paths"]
+    r.close()
