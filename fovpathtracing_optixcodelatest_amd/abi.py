@@ -137,6 +137,9 @@ class ModelMesh(C.Structure):
 
 
 UPDATE_DEVICE, UPDATE_REBUILD = 1, 2            # fovpt_update_vertices flags (FOVPT_UPDATE_*)
+UPDATE_REBUILD_ASYNC = 16                       # FOVPT_UPDATE_REBUILD_ASYNC: all five fovpt_update_* calls
+REBUILD_IDLE, REBUILD_BUILDING, REBUILD_READY = 0, 1, 2     # fovpt_rebuild_info.state (FOVPT_REBUILD_*)
+REBUILD_WAIT, REBUILD_ADOPT = 1, 2              # fovpt_rebuild_state flags
 
 
 class VertexUpdate(C.Structure):
@@ -193,6 +196,12 @@ class DebugGenerateResult(C.Structure):
 class HierarchyCost(C.Structure):
     """fovpt_hierarchy_cost_info: the SAH cost of the hierarchy as built and as last measured, and the update counters."""
     _fields_ = [("built", C.c_double), ("current", C.c_double), ("updates", C.c_uint64), ("measured", C.c_uint64)]
+
+
+class RebuildInfo(C.Structure):
+    """fovpt_rebuild_info: the state of the background rebuild (FOVPT_UPDATE_REBUILD_ASYNC) and its counters."""
+    _fields_ = [("state", C.c_int32), ("last_error", C.c_int32), ("requested", C.c_uint64), ("started", C.c_uint64), ("adopted", C.c_uint64),
+                ("failed", C.c_uint64), ("discarded", C.c_uint64), ("snapshot_update", C.c_uint64), ("ms_build", C.c_double)]
 
 
 SKIN_MAX_JOINTS = 1024                          # FOVPT_SKIN_MAX_JOINTS
@@ -588,6 +597,7 @@ assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeade
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4
 assert C.sizeof(HierarchyCost) == 32 and HierarchyCost.updates.offset == 16
+assert C.sizeof(RebuildInfo) == 64 and (RebuildInfo.requested.offset, RebuildInfo.snapshot_update.offset, RebuildInfo.ms_build.offset) == (8, 48, 56)
 assert C.sizeof(MeshSkin) == 32 and (MeshSkin.joints.offset, MeshSkin.weights.offset) == (16, 24)
 assert C.sizeof(SkinPose) == 16 and SkinPose.matrices.offset == 8
 assert C.sizeof(MorphTarget) == 24 and (MorphTarget.index.offset, MorphTarget.delta.offset) == (8, 16)

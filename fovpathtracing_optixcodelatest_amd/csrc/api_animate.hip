@@ -6,8 +6,11 @@
 // three steps on fovpt_stream(), the stream every job's resolve, and so every job's last traversal launch, is ordered on:
 // begin_update (what has to happen ahead of any new position), the source's own write_* (the new positions into up_vtx) and
 // finish_update (the refit, with the event the next job waits for, or the rebuild).  A new source is a new write_*.
+#include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
+#include <thread>
 
 #include "fovpt_ctx.h"
 
@@ -30,6 +33,8 @@ struct Listed {
         if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
         if (num < 0 || (num > 0 && !at)) return fail(c, FOVPT_E_INVALID, "%s: %d %s at %p", who, num, what, at);
         if (flags & ~allowed) return fail(c, FOVPT_E_INVALID, flag_text, who, flags);
+        if ((flags & FOVPT_UPDATE_REBUILD) && (flags & FOVPT_UPDATE_REBUILD_ASYNC))
+            return fail(c, FOVPT_E_INVALID, "%s: FOVPT_UPDATE_REBUILD together with FOVPT_UPDATE_REBUILD_ASYNC", who);
         seen.assign((size_t)nmesh, 0);
         return FOVPT_OK;
     }
@@ -151,26 +156,209 @@ struct Stage {
     int done() { HIPCHK(c, hipEventRecord(S->ev, c->shadow_stream)); S->pending = true; return FOVPT_OK; }
 };
 
+// ---- FOVPT_UPDATE_REBUILD_ASYNC: the hierarchy built beside the frames ---------------------------------------------------------
+// The slot and its transitions are fovpt_bgjob.h's.  Here: what a request puts on fovpt_stream() (start_rebuild), what the
+// builder's thread does with it (run_rebuild: that function and what it calls touch no fovpt_ctx), how a finished hierarchy
+// becomes the scene's without a wait (adopt_ready) and how the one it replaces goes once nothing can read it (retire_poll).
+using RebuildJob = fovpt::BgJob<fovpt_ctx::RebuildDone>;
+int enqueue_refit(fovpt_ctx* c);
+
+void free_rebuild_result(fovpt_ctx::RebuildDone& d)
+{
+    if (d.br.nodes) (void)hipFree(d.br.nodes);
+    if (d.partial) (void)hipFree(d.partial);
+    d = fovpt_ctx::RebuildDone();
+}
+
+// Retired memory whose events have all completed is freed (hipFree waits for the device: DESIGN.md, section 27, has what that
+// costs where this is called); nothing here waits for an event.
+void retire_poll(fovpt_ctx* c)
+{
+    bool not_ready = false;
+    for (size_t i = 0; i < c->retired.size();) {
+        fovpt_ctx::Retired& T = c->retired[i];
+        bool done = true;
+        for (hipEvent_t e : T.ev)
+            if (hipEventQuery(e) != hipSuccess) { done = false; break; }
+        if (!done) { not_ready = true; i++; continue; }
+        for (void* p : T.p) if (p) (void)hipFree(p);
+        for (hipEvent_t e : T.ev) (void)hipEventDestroy(e);
+        c->retired.erase(c->retired.begin() + (long)i);
+    }
+    if (not_ready) (void)hipGetLastError();      // (hipErrorNotReady is an answer, not an error a later check should find)
+}
+
+// The same on an idle device (the caller has synchronised every stream): everything retired goes
+void retire_idle(fovpt_ctx* c)
+{
+    for (fovpt_ctx::Retired& T : c->retired) {
+        for (void* p : T.p) if (p) (void)hipFree(p);
+        for (hipEvent_t e : T.ev) (void)hipEventDestroy(e);
+    }
+    c->retired.clear();
+}
+
+// fovpt_set_scene, a synchronous rebuild and fovpt_destroy end a background build: its thread is joined, its result freed
+void end_background_rebuild(fovpt_ctx* c)
+{
+    if (!c->rb) return;
+    (void)c->rb->job.discard([&](fovpt_ctx::RebuildDone& d) { c->rb->ms_build = d.ms; free_rebuild_result(d); });
+}
+
+// A context's first flagged call: the builder's stream, of the lowest priority the device offers, the snapshot's event and the
+// pinned record the builder's cost measurement writes
+int ensure_rebuild(fovpt_ctx* c)
+{
+    if (c->rb) return FOVPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::unique_ptr<fovpt_ctx::Rebuild> R(new fovpt_ctx::Rebuild);
+    int least = 0, greatest = 0;
+    HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(c, hipStreamCreateWithPriority(&R->st, hipStreamNonBlocking, least));
+    HIPCHK(c, hipEventCreateWithFlags(&R->ev_snapshot, hipEventDisableTiming));
+    HIPCHK(c, hipHostMalloc((void**)&R->rec, sizeof(TreeCostRecord), hipHostMallocDefault));
+    R->job.on_destroy(free_rebuild_result);
+    c->rb = std::move(R);
+    return FOVPT_OK;
+}
+
+// On the builder's thread.  build_hierarchy as fovpt_set_scene runs it, over the snapshot, on the builder's stream behind the
+// snapshot's event; then what a refit needs of the result, and its cost with partial sums of its own.
+int run_rebuild(fovpt_ctx::Rebuild* R, fovpt_ctx::RebuildDone& out, std::string& text)
+{
+    const fovpt_ctx::Rebuild::In& in = R->in;
+    char err[384];
+    hipError_t e = hipSuccess;
+    const char* what = nullptr;
+#define TRY(x) do { if (e == hipSuccess && (e = (x)) != hipSuccess) what = #x; } while (0)
+    TRY(hipSetDevice(in.device));
+    TRY(hipStreamWaitEvent(R->st, R->ev_snapshot, 0));
+    TRY(hipMemcpyAsync(R->mesh_of.p, in.h_mesh_of.data(), 4 * (size_t)in.ntri, hipMemcpyHostToDevice, R->st));
+    if (e != hipSuccess) { text = std::string(what) + ": " + hipGetErrorString(e); return FOVPT_E_DEVICE; }
+    const int rc = build_hierarchy(R->st, in.sw, (const float*)R->flat.p, (const uint32_t*)R->mesh_of.p, in.ntri, out.br, out.ms, err, sizeof(err));
+    if (rc) { text = err; out = fovpt_ctx::RebuildDone(); return rc; }
+    if (out.br.num_levels == 0) {
+        // (a refit needs the levels, and an adopted hierarchy is refitted at once)
+        free_rebuild_result(out);
+        snprintf(err, sizeof(err), "the hierarchy has more than %d levels", FOVPT_BVH_MAX_LEVELS);
+        text = err;
+        return FOVPT_E_INVALID;
+    }
+    out.partial_bytes = 2 * sizeof(double) * (size_t)fovpt_tree_cost_blocks(out.br.num_nodes);
+    TreeCostRecord* d_rec = nullptr;
+    TRY(hipMalloc(&out.partial, out.partial_bytes ? out.partial_bytes : 16));
+    TRY(hipHostGetDevicePointer((void**)&d_rec, R->rec, 0));
+    if (e == hipSuccess) {
+        fovpt_launch_tree_cost(R->st, out.br.nodes, out.br.num_nodes, (double*)out.partial, d_rec);
+        TRY(hipGetLastError());
+        TRY(hipStreamSynchronize(R->st));
+    }
+#undef TRY
+    if (e != hipSuccess) { text = std::string(what) + ": " + hipGetErrorString(e); free_rebuild_result(out); return FOVPT_E_DEVICE; }
+    out.cost = R->rec->cost;
+    if (in.delay_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(in.delay_ms));      // FOVPT_ASYNC_BUILD_DELAY_MS (tests)
+    return FOVPT_OK;
+}
+
+// The snapshot of the current positions on fovpt_stream(), behind whatever the call has enqueued, and the build over it.  The
+// slot is idle (update() looked).  Never waits for the device.  The environment is read here, on the caller's thread.
+int start_rebuild(fovpt_ctx* c)
+{
+    fovpt_ctx::Rebuild* R = c->rb.get();
+    const hipStream_t st = c->shadow_stream;
+    const uint32_t ntri = (uint32_t)c->stats.num_triangles;
+    const int nmesh = (int)c->mesh_nv.size();
+    HIPCHK(c, R->flat.reserve((size_t)ntri * 36));
+    HIPCHK(c, R->mesh_of.reserve((size_t)ntri * 4));
+    if (R->in.h_mesh_of.size() != ntri) {
+        R->in.h_mesh_of.resize(ntri);
+        for (int m = 0; m < nmesh; m++) {
+            const uint32_t end = m + 1 < nmesh ? c->mesh_prim0[m + 1] : ntri;
+            for (uint32_t t = c->mesh_prim0[m]; t < end; t++) R->in.h_mesh_of[t] = (uint32_t)m;
+        }
+    }
+    fovpt_launch_flatten(st, ntri, (const uint3*)c->up_vidx.p, (const float*)c->up_vtx.p, (float*)R->flat.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(R->ev_snapshot, st));
+    R->in.device = c->device;
+    R->in.ntri = ntri;
+    R->in.sw = fovpt_bvh_switches();
+    const char* delay = getenv("FOVPT_ASYNC_BUILD_DELAY_MS");
+    R->in.delay_ms = delay ? atoi(delay) : 0;
+    R->snapshot_update = c->cost_updates;
+    (void)R->job.request([R](fovpt_ctx::RebuildDone& out, std::string& text) { return run_rebuild(R, out, text); });
+    return FOVPT_OK;
+}
+
+// READY: the finished hierarchy becomes the scene's, on fovpt_stream() and without a wait.  Frames already issued keep the old
+// one in their kernel arguments (nothing on the device holds a copy of the scene's pointers): it is retired with an event behind
+// everything enqueued so far on every stream that traces, and so are the partial sums a cost measurement in flight may use; the
+// builder's own become the context's, sized for the new tree.  Then a refit over the CURRENT positions -- the snapshot may be
+// several updates old -- with the event the next job waits for, counted as one update.  Any other state: nothing.
+int adopt_ready(fovpt_ctx* c)
+{
+    fovpt_ctx::Rebuild* R = c->rb.get();
+    if (!R || R->job.state() != RebuildJob::READY) return FOVPT_OK;
+    fovpt_ctx::Retired T;
+    T.p[0] = c->nodes; T.p[1] = c->cost_partial.p;
+    hipError_t e = hipSuccess;
+    auto behind = [&](hipStream_t s) {
+        hipEvent_t ev = nullptr;
+        if (!s || e != hipSuccess || (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return;
+        T.ev.push_back(ev);
+        e = hipEventRecord(ev, s);
+    };
+    behind(c->shadow_stream);
+    for (int l = 0; l < FOVPT_MAX_LANES; l++) {
+        behind(c->lane_main[l]);
+        if (c->lane_shadow[l] != c->shadow_stream) behind(c->lane_shadow[l]);
+    }
+    if (e != hipSuccess) {
+        // nothing has changed yet: the old hierarchy stays, the new one waits for the next call
+        for (hipEvent_t ev : T.ev) (void)hipEventDestroy(ev);
+        return fail(c, FOVPT_E_DEVICE, "adopting the rebuilt hierarchy: %s", hipGetErrorString(e));
+    }
+    fovpt_ctx::RebuildDone D;
+    (void)R->job.adopt(&D);
+    c->retired.push_back(T);
+    c->cost_partial.p = D.partial; c->cost_partial.bytes = D.partial_bytes ? D.partial_bytes : 16;
+    adopt_hierarchy(c, D.br, D.ms);
+    R->ms_build = D.ms;
+    c->cost_built = D.cost;
+    c->seq_adopt = ++c->seq;                           // fovpt_warp_motion: hit records traced before address the old triangle records
+    return enqueue_refit(c);
+}
+
 // ---- the three steps of an update -----------------------------------------------------------------------------------------
 // Ahead of the new positions of the listed meshes: a rebuild waits for the device; the scene's first update makes the device
 // copies of what fovpt_set_scene kept; fovpt_temporal_motion's tracking copies the positions about to be overwritten; from_rest
 // (the source reads the rest positions: its caller passed an array, if an empty one): the scene's first puts them on the device.
+// The scene's first update: the device copies of what fovpt_set_scene kept, ordered on fovpt_stream() like everything an update does
+int ensure_device_copies(fovpt_ctx* c)
+{
+    if (c->up_vtx.p) return FOVPT_OK;
+    const hipStream_t st = c->shadow_stream;
+    if (!c->ev_scene) HIPCHK(c, hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
+    for (auto& S : c->up_stage)
+        if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+    HIPCHK(c, c->up_vidx.reserve(c->h_tri_vidx.size() * 4));
+    HIPCHK(c, c->up_vtx.reserve(c->h_vtx.size() * 4));
+    HIPCHK(c, hipMemcpyAsync(c->up_vidx.p, c->h_tri_vidx.data(), c->h_tri_vidx.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
+    return FOVPT_OK;
+}
+
 int begin_update(fovpt_ctx* c, const std::vector<int>& meshes, bool rebuild, bool from_rest)
 {
     HIPCHK(c, hipSetDevice(c->device));
-    if (rebuild) CHK(sync_all(c));
+    if (rebuild) {
+        CHK(sync_all(c));
+        end_background_rebuild(c);                     // a synchronous rebuild ends a background one: joined, its result discarded
+        retire_idle(c);
+    }
     c->seq_update = ++c->seq;                          // fovpt_warp_motion: the last temporal step and trace are of the geometry before
     const hipStream_t st = c->shadow_stream;
-    if (!c->up_vtx.p) {
-        // the first update: the device copies of what fovpt_set_scene kept (ordered on the stream like everything below)
-        if (!c->ev_scene) HIPCHK(c, hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming));
-        for (auto& S : c->up_stage)
-            if (!S.ev) HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-        HIPCHK(c, c->up_vidx.reserve(c->h_tri_vidx.size() * 4));
-        HIPCHK(c, c->up_vtx.reserve(c->h_vtx.size() * 4));
-        HIPCHK(c, hipMemcpyAsync(c->up_vidx.p, c->h_tri_vidx.data(), c->h_tri_vidx.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->up_vtx.p, c->h_vtx.data(), c->h_vtx.size() * 4, hipMemcpyHostToDevice, st));
-    }
+    CHK(ensure_device_copies(c));
     if (!c->tm_tracking) c->tm_untracked = c->tm_untracked || !meshes.empty();
     else {
         // fovpt_temporal_motion's previous positions: what a mesh holds now, ahead of the interval's first overwrite of it
@@ -197,19 +385,23 @@ int begin_update(fovpt_ctx* c, const std::vector<int>& meshes, bool rebuild, boo
 // Behind the new positions: the refit, enqueued on the same stream, with the event the next job waits for (and the tree's cost
 // behind it when fovpt_hierarchy_cost is watching); or FOVPT_UPDATE_REBUILD, fovpt_set_scene's build over the current vertices
 // (the old hierarchy stays if it fails).
+int enqueue_refit(fovpt_ctx* c)
+{
+    const hipStream_t st = c->shadow_stream;
+    fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, (const float*)c->up_vtx.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_scene, st));
+    c->refit_pending = true;
+    c->cost_updates++;
+    fovpt_ctx::CostSlot* S = nullptr;
+    return c->cost_watching ? enqueue_cost(c, st, c->cost_updates, &S) : FOVPT_OK;
+}
+
 int finish_update(fovpt_ctx* c, bool rebuild)
 {
     const hipStream_t st = c->shadow_stream;
     const float* vtx = (const float*)c->up_vtx.p;
-    if (!rebuild) {
-        fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, vtx);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_scene, st));
-        c->refit_pending = true;
-        c->cost_updates++;
-        fovpt_ctx::CostSlot* S = nullptr;
-        return c->cost_watching ? enqueue_cost(c, st, c->cost_updates, &S) : FOVPT_OK;
-    }
+    if (!rebuild) return enqueue_refit(c);
     const int nmesh = (int)c->mesh_nv.size();
     const uint32_t ntri = (uint32_t)c->stats.num_triangles;
     DevBuf t_flat, t_mesh_of;
@@ -233,14 +425,36 @@ int finish_update(fovpt_ctx* c, bool rebuild)
     return measure_built(c);
 }
 
-// What the update calls do once everything is validated
-template <class Write> int update(const Listed& L, bool rebuild, bool from_rest, Write write)
+// What the update calls do once everything is validated.  With FOVPT_UPDATE_REBUILD_ASYNC the call is the one without the flag;
+// `start` (the slot was idle when the call came in) then adds the snapshot and the background build behind it.
+template <class Write> int update(const Listed& L, int flags, bool from_rest, Write write)
 {
-    CHK(check_updatable(L.c, L.who));
-    if (L.meshes.empty() && !rebuild) return FOVPT_OK;
-    CHK(begin_update(L.c, L.meshes, rebuild, from_rest));
+    fovpt_ctx* c = L.c;
+    const bool rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    CHK(check_updatable(c, L.who));
+    bool start = false;
+    if (flags & FOVPT_UPDATE_REBUILD_ASYNC) {
+        CHK(ensure_rebuild(c));
+        start = c->rb->job.state() == fovpt::BgJob<fovpt_ctx::RebuildDone>::IDLE;
+        if (!start) c->rb->job.count_ignored();
+    }
+    if (L.meshes.empty() && !rebuild) {
+        if (!start) return FOVPT_OK;
+        // a background rebuild alone: nothing moves, no refit, nothing is counted
+        HIPCHK(c, hipSetDevice(c->device));
+        retire_poll(c);
+        CHK(ensure_device_copies(c));
+        return start_rebuild(c);
+    }
+    if (c->rb && !rebuild) {
+        HIPCHK(c, hipSetDevice(c->device));
+        retire_poll(c);
+        CHK(adopt_ready(c));
+    }
+    CHK(begin_update(c, L.meshes, rebuild, from_rest));
     CHK(write());
-    return finish_update(L.c, rebuild);
+    CHK(finish_update(c, rebuild));
+    return start ? start_rebuild(c) : FOVPT_OK;
 }
 
 // ---- the six sources: validated entries to new positions in up_vtx -------------------------------------------------------
@@ -417,11 +631,24 @@ template <class T> size_t rig_place(std::vector<char>& blob, const std::vector<T
 
 }  // namespace
 
+// The builder's thread is joined first (the slot's destructor would do it too late for the stream it works on)
+fovpt_ctx::Rebuild::~Rebuild()
+{
+    (void)job.discard(free_rebuild_result);
+    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    if (ev_snapshot) (void)hipEventDestroy(ev_snapshot);
+    if (rec) (void)hipHostFree(rec);
+}
+
 // What the calls of this file keep of a scene, dropped with it (fovpt_set_scene and the context's destructor; the device is
 // idle): the device copies an update makes and the refit it may have left for the next job to wait for, fovpt_temporal_motion's
 // tracking (switched on again by its next call), the rest positions and their bounds, the skins, the morph targets and the rig.
 void drop_animation(fovpt_ctx* c)
 {
+    // a background rebuild of the scene that goes: joined and discarded; what adoptions retired; the snapshot's buffers
+    end_background_rebuild(c);
+    retire_idle(c);
+    if (c->rb) { c->rb->flat.release(); c->rb->mesh_of.release(); std::vector<uint32_t>().swap(c->rb->in.h_mesh_of); }
     drop_rig(c);
     c->up_vtx.release(); c->up_vidx.release();
     c->refit_pending = false;
@@ -440,8 +667,8 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
 {
     const char* who = "fovpt_update_vertices";
     Listed L;
-    CHK(L.open(c, who, num_updates, up, "updates", flags, FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD));
-    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    CHK(L.open(c, who, num_updates, up, "updates", flags, FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD | FOVPT_UPDATE_REBUILD_ASYNC));
+    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0;
     size_t floats = 0;
     for (int k = 0; k < num_updates; k++) {
         const fovpt_vertex_update& U = up[k];
@@ -454,7 +681,7 @@ int fovpt_update_vertices(fovpt_ctx* c, const fovpt_vertex_update* up, int num_u
                 if (!std::isfinite(U.vertex[i])) return fail(c, FOVPT_E_INVALID, "%s: mesh %d vertex %zu is not finite", who, U.mesh, i / 3);
         floats += 3 * (size_t)U.num_vertices;
     }
-    return update(L, rebuild, false, [&] { return device ? write_device(c, up, num_updates) : write_host(c, up, num_updates, floats); });
+    return update(L, flags, false, [&] { return device ? write_device(c, up, num_updates) : write_host(c, up, num_updates, floats); });
 }
 
 // The overflow rule keeps every intermediate value finite, so no device memory has to be read to know the coordinates are.
@@ -462,7 +689,8 @@ int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int nu
 {
     const char* who = "fovpt_update_transforms";
     Listed L;
-    CHK(L.open(c, who, num, tf, "transforms", flags, FOVPT_UPDATE_REBUILD, "%s: flag bits %d (FOVPT_UPDATE_REBUILD is the only one accepted)"));
+    CHK(L.open(c, who, num, tf, "transforms", flags, FOVPT_UPDATE_REBUILD | FOVPT_UPDATE_REBUILD_ASYNC,
+                "%s: flag bits %d (FOVPT_UPDATE_REBUILD and FOVPT_UPDATE_REBUILD_ASYNC are the only ones accepted)"));
     if (num > 0) ensure_absmax(c);
     for (int k = 0; k < num; k++) {
         const fovpt_mesh_transform& T = tf[k];
@@ -475,7 +703,7 @@ int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int nu
             if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "%s: mesh %d row %d could overflow (bound %g > 2^127)", who, T.mesh, r, bound);
         }
     }
-    return update(L, (flags & FOVPT_UPDATE_REBUILD) != 0, tf != nullptr, [&] { return write_transforms(c, tf, num); });
+    return update(L, flags, tf != nullptr, [&] { return write_transforms(c, tf, num); });
 }
 
 // The skins are kept on the host per mesh; every call lays the device copies out anew (the skinned meshes' vertices and joints
@@ -554,8 +782,8 @@ int fovpt_update_skinned(fovpt_ctx* c, const fovpt_skin_pose* poses, int num, in
 {
     const char* who = "fovpt_update_skinned";
     Listed L;
-    CHK(L.open(c, who, num, poses, "poses", flags, FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD));
-    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    CHK(L.open(c, who, num, poses, "poses", flags, FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD | FOVPT_UPDATE_REBUILD_ASYNC));
+    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0;
     if (num > 0 && !device) ensure_absmax(c);
     size_t floats = 0;
     for (int k = 0; k < num; k++) {
@@ -568,7 +796,7 @@ int fovpt_update_skinned(fovpt_ctx* c, const fovpt_skin_pose* poses, int num, in
         floats += 12 * (size_t)P.num_joints;
         if (!device) CHK(check_palette(c, who, P.mesh, P.matrices, P.num_joints, K.S, c->mesh_absmax[P.mesh]));
     }
-    return update(L, rebuild, poses != nullptr, [&] { return write_skinned(c, poses, num, device, floats); });
+    return update(L, flags, poses != nullptr, [&] { return write_skinned(c, poses, num, device, floats); });
 }
 
 // The morph targets are kept on the host per mesh, transposed into a per-vertex list of {delta, target} records sorted by
@@ -683,8 +911,8 @@ int fovpt_update_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, i
 {
     const char* who = "fovpt_update_morphed";
     Listed L;
-    CHK(L.open(c, who, num, poses, "poses", flags, FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD));
-    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0, rebuild = (flags & FOVPT_UPDATE_REBUILD) != 0;
+    CHK(L.open(c, who, num, poses, "poses", flags, FOVPT_UPDATE_DEVICE | FOVPT_UPDATE_REBUILD | FOVPT_UPDATE_REBUILD_ASYNC));
+    const bool device = (flags & FOVPT_UPDATE_DEVICE) != 0;
     if (num > 0 && !device) ensure_absmax(c);
     size_t floats = 0;
     for (int k = 0; k < num; k++) {
@@ -713,7 +941,7 @@ int fovpt_update_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, i
         if (B > 0x1p127) return fail(c, FOVPT_E_INVALID, "%s: mesh %d could overflow (bound %g > 2^127)", who, P.mesh, B);
         if (K) CHK(check_palette(c, who, P.mesh, P.matrices, P.num_joints, K->S, B));
     }
-    return update(L, rebuild, poses != nullptr, [&] { return write_morphed(c, poses, num, device, floats); });
+    return update(L, flags, poses != nullptr, [&] { return write_morphed(c, poses, num, device, floats); });
 }
 
 // Validated in the order of the description: the counts, the nodes, the bindings, then clip by clip the channels.  Then the
@@ -892,12 +1120,43 @@ int fovpt_update_animated(fovpt_ctx* c, int clip, float time, int flags)
 {
     const char* who = "fovpt_update_animated";
     Listed L;
-    CHK(L.open(c, who, 0, nullptr, "clips", flags, FOVPT_UPDATE_REBUILD, "%s: flag bits %d (FOVPT_UPDATE_REBUILD is the only one accepted)"));
+    CHK(L.open(c, who, 0, nullptr, "clips", flags, FOVPT_UPDATE_REBUILD | FOVPT_UPDATE_REBUILD_ASYNC,
+                "%s: flag bits %d (FOVPT_UPDATE_REBUILD and FOVPT_UPDATE_REBUILD_ASYNC are the only ones accepted)"));
     if (!c->rig.set) return fail(c, FOVPT_E_INVALID, "%s: no rig (fovpt_set_rig; fovpt_set_skins, fovpt_set_morphs and fovpt_set_scene drop it)", who);
     if (clip < 0 || (uint32_t)clip >= c->rig.num_clips) return fail(c, FOVPT_E_INVALID, "%s: clip %d of %u", who, clip, c->rig.num_clips);
     if (!std::isfinite(time)) return fail(c, FOVPT_E_INVALID, "%s: the time is not finite", who);
     for (const fovpt_ctx::RigBound& B : c->rig.bound) CHK(L.mesh(B.mesh));
-    return update(L, (flags & FOVPT_UPDATE_REBUILD) != 0, true, [&] { return write_animated(c, clip, time); });
+    return update(L, flags, true, [&] { return write_animated(c, clip, time); });
+}
+
+// Polls, and with the flags waits for the builder's thread (never for the device) and adopts.  The text of a build that failed
+// since the last call goes to the context here, on the caller's thread: the call itself succeeds.
+int fovpt_rebuild_state(fovpt_ctx* c, int flags, fovpt_rebuild_info* out)
+{
+    const char* who = "fovpt_rebuild_state";
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "%s: null out pointer", who);
+    if (flags & ~(FOVPT_REBUILD_WAIT | FOVPT_REBUILD_ADOPT)) return fail(c, FOVPT_E_INVALID, "%s: unknown flag bits %d", who, flags);
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    memset(out, 0, sizeof(*out));
+    fovpt_ctx::Rebuild* R = c->rb.get();
+    if (!R) return FOVPT_OK;                               // the context has never asked: idle, nothing counted
+    HIPCHK(c, hipSetDevice(c->device));
+    retire_poll(c);
+    if (flags & FOVPT_REBUILD_WAIT) (void)R->job.wait();
+    if (flags & FOVPT_REBUILD_ADOPT) CHK(adopt_ready(c));
+    out->state = (int32_t)R->job.state();
+    const RebuildJob::Counters& n = R->job.counters();
+    out->last_error = R->job.last_error();
+    out->requested = n.requested; out->started = n.started; out->adopted = n.adopted; out->failed = n.failed; out->discarded = n.discarded;
+    out->snapshot_update = R->snapshot_update;
+    const fovpt_ctx::RebuildDone* waiting = R->job.peek();
+    out->ms_build = waiting ? (double)waiting->ms : R->ms_build;
+    if (n.failed != R->failed_told) {
+        R->failed_told = n.failed;
+        (void)fail(c, R->job.last_error(), "background rebuild: %s", R->job.last_text().c_str());
+    }
+    return FOVPT_OK;
 }
 
 }  // extern "C"

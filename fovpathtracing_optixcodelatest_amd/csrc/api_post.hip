@@ -887,7 +887,7 @@ int fovpt_warp_motion(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_w
         return fail(c, FOVPT_E_NO_FRAME, "%s: previous positions are not tracked yet (no fovpt_temporal_motion or fovpt_post with MOTION on this scene)", who);
     if (c->seq_update > c->seq_step)
         return fail(c, FOVPT_E_NO_FRAME, "%s: a geometry update has been issued since the last temporal step", who);
-    if (gbuffer && !(c->gb_stamp > c->seq_frame && c->gb_stamp > c->seq_update))
+    if (gbuffer && !(c->gb_stamp > c->seq_frame && c->gb_stamp > c->seq_update && c->gb_stamp > c->seq_adopt))
         return fail(c, FOVPT_E_NO_FRAME, "%s: the context's last G-buffer trace is not of the rendered frame and the current geometry "
                                          "(its hit records go with the caller's G-buffer)", who);
     { const int rc_ = warp_buffers(c, gbuffer, w, out_color, out_rgba, out_map, who); if (rc_) return rc_; }

@@ -330,6 +330,9 @@ __device__ inline float merged_area(const Box& a, const Box& b) { return union_a
 struct Move { int out; int pivot; float gain; };
 
 #define FOVPT_REINSERT_STACK 96
+#ifndef FOVPT_SPLIT_BUDGET_DEFAULT
+#define FOVPT_SPLIT_BUDGET_DEFAULT 0.0f
+#endif
 #ifndef FOVPT_REINSERT_DEFAULT
 #define FOVPT_REINSERT_DEFAULT 12          // at most this many rounds; a round that lowers the cost by less than FOVPT_REINSERT_STOP ends them
 #endif
@@ -870,9 +873,28 @@ __global__ void k_split_emit(const float* __restrict__ flat, uint32_t n, const u
 
 }  // namespace
 
-hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n_prims, int use_ploc, float split_budget,
+BvhSwitches fovpt_bvh_switches()
+{
+    BvhSwitches sw;
+    const char* bvh_env = getenv("FOVPT_BVH");          // "lbvh" = plain Karras tree (A/B testing); default PLOC
+    sw.use_ploc = !(bvh_env && strcmp(bvh_env, "lbvh") == 0);
+    sw.split_budget = FOVPT_SPLIT_BUDGET_DEFAULT;       // references added by spatial splits, as a fraction of the triangles
+    if (const char* sb = getenv("FOVPT_SPLIT")) sw.split_budget = (float)atof(sb);
+    if (!(sw.split_budget >= 0.f) || sw.split_budget > 2.f) sw.split_budget = 0.f;
+    const char* order_env = getenv("FOVPT_BVH_ORDER");                            // 0: keep the collapse's child order (A/B)
+    sw.order_children = !order_env || atoi(order_env) != 0;
+    // reinsertion rounds on the PLOC tree (k_reinsert_find): FOVPT_REINSERT=<rounds>, 0 = off
+    const char* re_env = getenv("FOVPT_REINSERT");
+    sw.reinsert_rounds = re_env ? atoi(re_env) : FOVPT_REINSERT_DEFAULT;
+    sw.verbose = getenv("FOVPT_BVH_VERBOSE") != nullptr;
+    return sw;
+}
+
+hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n_prims, const BvhSwitches& sw,
                             int reinsert, BvhBuildResult* out, char* err, size_t errlen)
 {
+    const int use_ploc = sw.use_ploc;
+    const float split_budget = sw.split_budget;
     uint32_t n = n_prims;                      // build primitives: triangles, or references of triangles when splits are on
     uint32_t *ref_prim = nullptr, *split_cnt = nullptr, *split_first = nullptr;
     unsigned long long* split_total = nullptr;
@@ -895,13 +917,10 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
     DpCost* dp = nullptr;
     std::vector<uint32_t> round_end;           // PLOC: internal nodes created up to and including each round
     std::vector<uint32_t> level_first;         // wide tree: index of the first node of every level (+ the node count at the end)
-    const char* order_env = getenv("FOVPT_BVH_ORDER");                            // 0: keep the collapse's child order (A/B)
-    const bool order_children = !order_env || atoi(order_env) != 0;
+    const bool order_children = sw.order_children != 0;
     float2* order_pc = nullptr;
-    // reinsertion rounds on the PLOC tree (k_reinsert_find): FOVPT_REINSERT=<rounds>, 0 = off
-    const char* re_env = getenv("FOVPT_REINSERT");
-    const int reinsert_rounds = reinsert >= 0 ? reinsert : re_env ? atoi(re_env) : FOVPT_REINSERT_DEFAULT;
-    const bool verbose = getenv("FOVPT_BVH_VERBOSE") != nullptr;
+    const int reinsert_rounds = reinsert >= 0 ? reinsert : sw.reinsert_rounds;
+    const bool verbose = sw.verbose != 0;
     bool tree_changed = false;
     Move* re_moves = nullptr;
     unsigned long long* re_lock = nullptr;

@@ -13,9 +13,6 @@
 #include <cstring>
 
 #include "fovpt_ctx.h"
-#ifndef FOVPT_SPLIT_BUDGET_DEFAULT
-#define FOVPT_SPLIT_BUDGET_DEFAULT 0.0f
-#endif
 
 namespace {
 
@@ -540,44 +537,54 @@ int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P)
     return 3;
 }
 
-// The hierarchy over d_flat (9 floats per triangle) on stream st, as fovpt_set_scene builds it: FOVPT_BVH, FOVPT_SPLIT, and a
-// second build without reinsertion when reinsertion made the tree too deep; *ms = its device time.  On success br holds the
-// new hierarchy (adopt_hierarchy takes it); on failure nothing is kept.
-int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br, float& ms)
+// The hierarchy over d_flat (9 floats per triangle) on stream st, as fovpt_set_scene builds it: sw (FOVPT_BVH, FOVPT_SPLIT, ...,
+// read by the caller), and a second build without reinsertion when reinsertion made the tree too deep; *ms = its device time.
+// On success br holds the new hierarchy (adopt_hierarchy takes it); on failure nothing is kept, the code is returned and err
+// holds the text.  Touches no context: whoever sees the result on the context's own thread calls fail() with it (a background
+// rebuild runs this on a thread of its own).
+int build_hierarchy(hipStream_t st, const BvhSwitches& sw, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br,
+                    float& ms, char* err, size_t errlen)
 {
+#define BHCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #x, hipGetErrorString(e_)); return FOVPT_E_DEVICE; } } while (0)
     struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;    // destroyed on every return path
-    HIPCHK(c, hipEventCreate(&ev0.e)); HIPCHK(c, hipEventCreate(&ev1.e));
+    err[0] = 0;
+    BHCHK(hipEventCreate(&ev0.e)); BHCHK(hipEventCreate(&ev1.e));
     const hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    HIPCHK(c, hipEventRecord(e0, st));
+    BHCHK(hipEventRecord(e0, st));
+#undef BHCHK
     memset(&br, 0, sizeof(br));
     char errbuf[256];
-    const char* bvh_env = getenv("FOVPT_BVH");          // "lbvh" = plain Karras tree (A/B testing); default PLOC
-    const int use_ploc = !(bvh_env && strcmp(bvh_env, "lbvh") == 0);
-    float split_budget = FOVPT_SPLIT_BUDGET_DEFAULT;    // references added by spatial splits, as a fraction of the triangles
-    if (const char* sb = getenv("FOVPT_SPLIT")) split_budget = (float)atof(sb);
-    if (!(split_budget >= 0.f) || split_budget > 2.f) split_budget = 0.f;
-    hipError_t be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, use_ploc, split_budget, -1, &br, errbuf, sizeof(errbuf));
+    hipError_t be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, sw, -1, &br, errbuf, sizeof(errbuf));
     if (be == hipSuccess && br.reinserted && 3 * br.max_depth + 1 > FOVPT_STACK) {
         // reinsertion lowers the tree's cost, not its depth: a hierarchy it made too deep for the traversal stack is built again without it
         (void)hipFree(br.nodes);
         memset(&br, 0, sizeof(br));
-        be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, use_ploc, split_budget, 0, &br, errbuf, sizeof(errbuf));
+        be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, sw, 0, &br, errbuf, sizeof(errbuf));
     }
     (void)hipEventRecord(e1, st);
     (void)hipEventSynchronize(e1);
     ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
-    if (be != hipSuccess) return fail(c, FOVPT_E_DEVICE, "LBVH build: %s", errbuf);
+    if (be != hipSuccess) { snprintf(err, errlen, "LBVH build: %s", errbuf); return FOVPT_E_DEVICE; }
     if (3 * br.max_depth + 1 > FOVPT_STACK) {       // a wide node leaves at most 3 entries behind
         (void)hipFree(br.nodes);
-        return fail(c, FOVPT_E_BVH_DEPTH, "hierarchy depth %u needs more than the %d traversal stack entries", br.max_depth, FOVPT_STACK);
+        snprintf(err, errlen, "hierarchy depth %u needs more than the %d traversal stack entries", br.max_depth, FOVPT_STACK);
+        return FOVPT_E_BVH_DEPTH;
     }
     if ((size_t)((const char*)br.tris - (const char*)br.nodes) + br.tri_bytes + 64 >= (1ull << 32)) {
         (void)hipFree(br.nodes);
-        return fail(c, FOVPT_E_INVALID, "hierarchy of %llu bytes exceeds the 32-bit offsets of the traversal",
-                    (unsigned long long)(br.node_bytes + br.tri_bytes));
+        snprintf(err, errlen, "hierarchy of %llu bytes exceeds the 32-bit offsets of the traversal", (unsigned long long)(br.node_bytes + br.tri_bytes));
+        return FOVPT_E_INVALID;
     }
     return FOVPT_OK;
+}
+
+// build_hierarchy for a caller on the context's own thread: the switches are the environment's now, the text goes to the context
+int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br, float& ms)
+{
+    char err[384];
+    const int rc = build_hierarchy(st, fovpt_bvh_switches(), d_flat, d_mesh_of, ntri, br, ms, err, sizeof(err));
+    return rc ? fail(c, rc, "%s", err) : FOVPT_OK;
 }
 
 namespace {
@@ -705,6 +712,7 @@ void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameD
 fovpt_ctx::~fovpt_ctx()
 {
     free_scene(this);
+    rb.reset();                                          // (its thread is joined: free_scene ended a background rebuild)
     for (auto& S : up_stage) {
         if (S.p) (void)hipHostFree(S.p);
         if (S.ev) (void)hipEventDestroy(S.ev);

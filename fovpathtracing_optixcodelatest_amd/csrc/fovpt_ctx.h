@@ -2,9 +2,11 @@
 // api_debug.hip): the context, the buffers it owns, and the helpers more than one of those files uses.  Host only: no kernel file
 // includes it.
 #pragma once
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "fovpt_bgjob.h"
 #include "fovpt_device.h"
 #include <rccl/rccl.h>      // types only: the library is loaded at run time (fovpt_comm_*), libfovpt.so does not link it
 
@@ -137,6 +139,30 @@ struct fovpt_ctx {
     bool cost_watching = false;
     double cost_built = 0.0, cost_current = 0.0;
     uint64_t cost_updates = 0, cost_measured = 0;
+    // FOVPT_UPDATE_REBUILD_ASYNC (api_animate.hip).  rb: made by a context's first flagged call, with the builder's stream (lowest
+    // priority), the snapshot's event and the pinned record its cost measurement writes; a context that never passes the flag
+    // has none of it.  The builder's thread (fovpt_bgjob.h) touches nothing of the context but *rb's `in` members, which the
+    // requesting call fills before the thread starts and nobody else reads while it runs, and the RebuildDone it publishes:
+    // the hierarchy, its cost, and the partial sums the measurement used, sized for that hierarchy (they become cost_partial).
+    // flat / mesh_of: the snapshot (36 + 4 bytes per triangle), kept until the scene goes.  retired: hierarchies (and their
+    // partial sums) that frames issued before an adoption may still read, each with events recorded behind everything that can;
+    // freed once a poll finds them all complete (retire_poll), or when the device is idle.
+    struct RebuildDone { BvhBuildResult br{}; float ms = 0.f; double cost = 0.0; void* partial = nullptr; size_t partial_bytes = 0; };
+    struct Rebuild {
+        fovpt::BgJob<RebuildDone> job;
+        hipStream_t st = nullptr;
+        hipEvent_t ev_snapshot = nullptr;
+        TreeCostRecord* rec = nullptr;
+        DevBuf flat, mesh_of;
+        struct In { int device = 0; uint32_t ntri = 0; std::vector<uint32_t> h_mesh_of; BvhSwitches sw{}; int delay_ms = 0; } in;
+        uint64_t snapshot_update = 0;
+        double ms_build = 0.0;                 // of the last build that finished and has left the slot (one that waits there has its own)
+        uint64_t failed_told = 0;              // the failed builds whose text fovpt_rebuild_state has given
+        ~Rebuild();
+    };
+    std::unique_ptr<Rebuild> rb;
+    struct Retired { void* p[2]; std::vector<hipEvent_t> ev; };
+    std::vector<Retired> retired;
     // probe
     DevBuf pr_data, pr_pdfx, pr_cdfx, pr_pdfy, pr_cdfy, pr_guidex, pr_guidey, pr_rec;
     bool guide_ok = false;
@@ -237,6 +263,7 @@ struct fovpt_ctx {
     // records (gb_hit) describe the rendered frame and the current geometry when gb_stamp is above seq_frame and seq_update.
     bool tm_step_blind = false;
     uint64_t seq = 0, seq_frame = 0, seq_update = 0, seq_step = 0, gb_stamp = 0;
+    uint64_t seq_adopt = 0;                // the last adoption of a background rebuild: no position moves, but the hit records of an earlier trace address the old hierarchy's triangle records
     ~fovpt_ctx();                          // what no DevBuf owns; fovpt_destroy synchronises first
 };
 
@@ -248,6 +275,8 @@ void set_camera(FrameDev& fd, const fovpt_launch_params* lp);
 void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd);
 // fovpt_api.hip: the hierarchy build of fovpt_set_scene and the measurements of fovpt_hierarchy_cost, which a rebuild and a refit use
 int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br, float& ms);
+int build_hierarchy(hipStream_t st, const BvhSwitches& sw, const float* d_flat, const uint32_t* d_mesh_of, uint32_t ntri, BvhBuildResult& br,
+                    float& ms, char* err, size_t errlen);      // (no context: for a thread that is not the context's own)
 void adopt_hierarchy(fovpt_ctx* c, const BvhBuildResult& br, float ms);
 int enqueue_cost(fovpt_ctx* c, hipStream_t st, uint64_t update, fovpt_ctx::CostSlot** out);
 int measure_built(fovpt_ctx* c);

@@ -202,10 +202,16 @@ struct BvhBuildResult {
     uint32_t level_first[FOVPT_BVH_MAX_LEVELS + 1];   // level L is the contiguous nodes [level_first[L], level_first[L + 1])
 };
 
+// The environment switches of a build, read once by whoever asks for it (fovpt_bvh_switches), so that a build on a thread of its
+// own never reads the environment: FOVPT_BVH (use_ploc), FOVPT_SPLIT (split_budget: references added by spatial splits as a
+// fraction of the triangles, 0 = none, see bvh_build.hip), FOVPT_BVH_ORDER, FOVPT_REINSERT (rounds of reinsertion on the PLOC
+// tree, 0 = none) and FOVPT_BVH_VERBOSE.
+struct BvhSwitches { int use_ploc; float split_budget; int order_children, reinsert_rounds, verbose; };
+BvhSwitches fovpt_bvh_switches();
+
 // flat: 9 floats per triangle (v0,v1,v2), mesh_of_prim: mesh id per triangle.  All device pointers.
-// split_budget: references added by spatial splits as a fraction of the triangles (0 = none), see bvh_build.hip.
-// reinsert: rounds of reinsertion on the PLOC tree (0 = none, -1 = FOVPT_REINSERT or the build's default).
-hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n, int use_ploc, float split_budget,
+// reinsert: rounds of reinsertion on the PLOC tree (0 = none, -1 = sw.reinsert_rounds).
+hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n, const BvhSwitches& sw,
                             int reinsert, BvhBuildResult* out, char* err, size_t errlen);
 
 // cap = shard capacity (in items) of the radiance queues and of the shadow queue.

@@ -23,7 +23,7 @@ EXPORTS = [
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
     "fovpt_temporal_defaults", "fovpt_temporal", "fovpt_temporal_motion", "fovpt_temporal_buffers", "fovpt_temporal_reset", "fovpt_update_vertices",
-    "fovpt_update_transforms", "fovpt_hierarchy_cost", "fovpt_set_skins", "fovpt_update_skinned",
+    "fovpt_update_transforms", "fovpt_hierarchy_cost", "fovpt_rebuild_state", "fovpt_set_skins", "fovpt_update_skinned",
     "fovpt_set_morphs", "fovpt_update_morphed", "fovpt_set_rig", "fovpt_update_animated",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
@@ -215,6 +215,7 @@ def load():
     L.fovpt_update_vertices.argtypes = [vp, C.POINTER(abi.VertexUpdate), i32, i32]
     L.fovpt_update_transforms.argtypes = [vp, C.POINTER(abi.MeshTransform), i32, i32]
     L.fovpt_hierarchy_cost.argtypes = [vp, i32, C.POINTER(abi.HierarchyCost)]
+    L.fovpt_rebuild_state.argtypes = [vp, i32, C.POINTER(abi.RebuildInfo)]
     L.fovpt_set_skins.argtypes = [vp, C.POINTER(abi.MeshSkin), i32]
     L.fovpt_update_skinned.argtypes = [vp, C.POINTER(abi.SkinPose), i32, i32]
     L.fovpt_set_morphs.argtypes = [vp, C.POINTER(abi.MeshMorph), i32]

@@ -691,8 +691,17 @@ class SampleRenderer:
             raise ValueError("%s: mesh %d needs a contiguous (J, 3, 4) float32 tensor" % (who, mesh))
         return m.data_ptr()
 
+    @staticmethod
+    def _rebuild_flag(rebuild):
+        """rebuild=False / True / "async" as FOVPT_UPDATE_* bits (True: synchronous; "async": beside the frames, rebuild_state())."""
+        if isinstance(rebuild, str):
+            if rebuild != "async":
+                raise ValueError("rebuild is False, True or \"async\", not %r" % (rebuild,))
+            return abi.UPDATE_REBUILD_ASYNC
+        return abi.UPDATE_REBUILD if rebuild else 0
+
     def _update(self, fn, entries, num, device, rebuild, keep):
-        self._check(fn(self._ctx, entries, num, (abi.UPDATE_DEVICE if device else 0) | (abi.UPDATE_REBUILD if rebuild else 0)))
+        self._check(fn(self._ctx, entries, num, (abi.UPDATE_DEVICE if device else 0) | self._rebuild_flag(rebuild)))
         if device:
             self._keep_updates = keep          # (the tensors are read on the stream after the call returns)
 
@@ -739,7 +748,15 @@ class SampleRenderer:
                 raise ValueError("update_transforms: mesh %d needs a (3, 4) or (4, 4) matrix" % mesh)
             tfs[k].mesh = int(mesh)
             tfs[k].m[:] = [float(x) for x in m.reshape(-1)]
-        self._check(self._L.fovpt_update_transforms(self._ctx, tfs, len(items), abi.UPDATE_REBUILD if rebuild else 0))
+        self._check(self._L.fovpt_update_transforms(self._ctx, tfs, len(items), self._rebuild_flag(rebuild)))
+
+    def rebuild_state(self, wait=False, adopt=False) -> abi.RebuildInfo:
+        """The background rebuild an update with rebuild="async" starts (state REBUILD_IDLE / _BUILDING / _READY, the counters,
+        last_error, snapshot_update, ms_build).  Never waits for the device.  wait=True waits until the state is not BUILDING;
+        adopt=True makes a READY hierarchy the scene's now (otherwise the next update that enqueues something does)."""
+        out = abi.RebuildInfo()
+        self._check(self._L.fovpt_rebuild_state(self._ctx, (abi.REBUILD_WAIT if wait else 0) | (abi.REBUILD_ADOPT if adopt else 0), C.byref(out)))
+        return out
 
     def hierarchy_cost(self, wait=False) -> abi.HierarchyCost:
         """The SAH cost of the hierarchy as built and as last measured on the device (built, current, updates, measured).  The
@@ -937,7 +954,7 @@ class SampleRenderer:
         palettes, weights and rigid matrices applied on the device; absolute, not cumulative; then update_vertices()' refit (or,
         rebuild=True, rebuild) with the same ordering.  The caller wraps its own time to loop.  The renderer's Model is not
         changed."""
-        self._check(self._L.fovpt_update_animated(self._ctx, int(clip), float(time), abi.UPDATE_REBUILD if rebuild else 0))
+        self._check(self._L.fovpt_update_animated(self._ctx, int(clip), float(time), self._rebuild_flag(rebuild)))
 
     def setCamera(self, camera: Camera):
         """SimplePathtracer.cpp:282-289: aspect ratio is recomputed from the frame size."""

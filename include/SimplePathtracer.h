@@ -440,8 +440,19 @@ public:
     // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
     // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
     // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true
-    // builds it anew (synchronous; include/fovpt.h, fovpt_update_vertices)
-    void updateAccel(const std::vector<int>& meshes, bool rebuild = false)
+    // builds it anew (synchronous; include/fovpt.h, fovpt_update_vertices).  `rebuild` of the whole updateAccel family has a third
+    // choice, REBUILD_ASYNC: the call refits, and a new hierarchy is built beside the frames and adopted by a later update or by
+    // rebuildState(false, true) (include/fovpt.h, FOVPT_UPDATE_REBUILD_ASYNC)
+    enum { REFIT = 0, REBUILD = 1, REBUILD_ASYNC = 2 };        // (false and true still mean the first two)
+    static constexpr int rebuildFlag(int rebuild) { return rebuild == REBUILD_ASYNC ? FOVPT_UPDATE_REBUILD_ASYNC : rebuild ? FOVPT_UPDATE_REBUILD : 0; }
+    // the background rebuild's state and counters; wait: until it is not BUILDING (never for the device); adopt: now, if READY
+    fovpt_rebuild_info rebuildState(bool wait = false, bool adopt = false)
+    {
+        fovpt_rebuild_info info;
+        check(fovpt_rebuild_state(ctx, (wait ? FOVPT_REBUILD_WAIT : 0) | (adopt ? FOVPT_REBUILD_ADOPT : 0), &info));
+        return info;
+    }
+    void updateAccel(const std::vector<int>& meshes, int rebuild = REFIT)
     {
         std::vector<fovpt_vertex_update> up(meshes.size());
         for (size_t k = 0; k < meshes.size(); k++) {
@@ -451,14 +462,14 @@ public:
             up[k].num_vertices = (uint32_t)m.vertex.size();
             up[k].vertex = m.vertex.empty() ? nullptr : &m.vertex[0].x;
         }
-        check(fovpt_update_vertices(ctx, up.data(), (int)up.size(), rebuild ? FOVPT_UPDATE_REBUILD : 0));
+        check(fovpt_update_vertices(ctx, up.data(), (int)up.size(), rebuildFlag(rebuild)));
     }
     // rigid motion: the listed meshes' rest positions (the Model's, when this renderer was built) through row-major 3 x 4
     // matrices on the device, absolute not cumulative, then updateAccel()'s refit or rebuild (include/fovpt.h,
     // fovpt_update_transforms).  The Model is not changed.
-    void updateTransforms(const std::vector<fovpt_mesh_transform>& transforms, bool rebuild = false)
+    void updateTransforms(const std::vector<fovpt_mesh_transform>& transforms, int rebuild = REFIT)
     {
-        check(fovpt_update_transforms(ctx, transforms.data(), (int)transforms.size(), rebuild ? FOVPT_UPDATE_REBUILD : 0));
+        check(fovpt_update_transforms(ctx, transforms.data(), (int)transforms.size(), rebuildFlag(rebuild)));
     }
     // the SAH cost of the hierarchy as built and as last measured (include/fovpt.h, fovpt_hierarchy_cost): the first call
     // switches the measurements on; wait = false never blocks and may lag, wait = true returns measured == updates.  Rebuild
@@ -475,9 +486,9 @@ public:
     // updateAccel()'s refit or rebuild (include/fovpt.h, fovpt_set_skins / fovpt_update_skinned).  The Model is not changed.
     fovpt_ctx* context() const { return ctx; }       // the C ABI's context, for calls this class does not wrap (fovpt_debug_buffer)
     void setSkins(const std::vector<fovpt_mesh_skin>& skins) { check(fovpt_set_skins(ctx, skins.data(), (int)skins.size())); }
-    void updateSkinned(const std::vector<fovpt_skin_pose>& poses, bool rebuild = false, bool device = false)
+    void updateSkinned(const std::vector<fovpt_skin_pose>& poses, int rebuild = REFIT, bool device = false)
     {
-        check(fovpt_update_skinned(ctx, poses.data(), (int)poses.size(), (rebuild ? FOVPT_UPDATE_REBUILD : 0) | (device ? FOVPT_UPDATE_DEVICE : 0)));
+        check(fovpt_update_skinned(ctx, poses.data(), (int)poses.size(), rebuildFlag(rebuild) | (device ? FOVPT_UPDATE_DEVICE : 0)));
     }
     // morph targets: setMorphs uploads, replaces or removes (num_targets 0, null pointer) the targets of the listed meshes,
     // once; updateMorphed sends one weight per target and, with num_joints > 0, the mesh's skin palette (device = true: device
@@ -485,16 +496,16 @@ public:
     // through the skin, absolute not cumulative, then updateAccel()'s refit or rebuild (include/fovpt.h, fovpt_set_morphs /
     // fovpt_update_morphed).  The Model is not changed.
     void setMorphs(const std::vector<fovpt_mesh_morph>& morphs) { check(fovpt_set_morphs(ctx, morphs.data(), (int)morphs.size())); }
-    void updateMorphed(const std::vector<fovpt_morph_pose>& poses, bool rebuild = false, bool device = false)
+    void updateMorphed(const std::vector<fovpt_morph_pose>& poses, int rebuild = REFIT, bool device = false)
     {
-        check(fovpt_update_morphed(ctx, poses.data(), (int)poses.size(), (rebuild ? FOVPT_UPDATE_REBUILD : 0) | (device ? FOVPT_UPDATE_DEVICE : 0)));
+        check(fovpt_update_morphed(ctx, poses.data(), (int)poses.size(), rebuildFlag(rebuild) | (device ? FOVPT_UPDATE_DEVICE : 0)));
     }
     // rigs: setRig uploads the node hierarchy, the bindings of meshes to it and the keyframe clips, once (after setSkins /
     // setMorphs, either of which drops the rig; nullptr removes it); updateAnimated samples clip `clip` at `time`, composes the
     // hierarchy and poses every bound mesh on the device, absolute not cumulative, then updateAccel()'s refit or rebuild
     // (include/fovpt.h, fovpt_set_rig / fovpt_update_animated).  The caller wraps its own time to loop.  The Model is not changed.
     void setRig(const fovpt_rig_desc* rig) { check(fovpt_set_rig(ctx, rig)); }
-    void updateAnimated(int clip, float time, bool rebuild = false) { check(fovpt_update_animated(ctx, clip, time, rebuild ? FOVPT_UPDATE_REBUILD : 0)); }
+    void updateAnimated(int clip, float time, int rebuild = REFIT) { check(fovpt_update_animated(ctx, clip, time, rebuildFlag(rebuild))); }
     // ---- multi-GPU (new with this library; the reference is single-GPU): one SampleRenderer per GPU / process, rank and
     // world in fovpt_config, the framebuffer gathered over RCCL on the library's stream (include/fovpt.h, fovpt_comm_*)
     void renderAsync() { check(fovpt_render(ctx, reinterpret_cast<fovpt_launch_params*>(&launchParams))); }   // render() without the sync

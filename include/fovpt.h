@@ -549,6 +549,77 @@ typedef struct fovpt_hierarchy_cost_info {
 #define FOVPT_COST_WAIT 1
 int fovpt_hierarchy_cost(fovpt_ctx* ctx, int flags, fovpt_hierarchy_cost_info* out);
 
+/* ---- the hierarchy rebuilt beside the frames ------------------------------------------------------------------------------------
+ * FOVPT_UPDATE_REBUILD stops the frame loop for the length of a build (15.3 ms at C3, 103 ms on the street).
+ * FOVPT_UPDATE_REBUILD_ASYNC builds the new hierarchy on a thread and a stream of its own while frames go on over the refit one,
+ * and swaps it in later.  A hit is the minimum (t, primitive id) and occlusion is existence, so no pixel depends on which
+ * conservative tree is in use: the swap is invisible bit for bit.
+ *   the flag   accepted by all five fovpt_update_* calls, refused (FOVPT_E_INVALID) together with FOVPT_UPDATE_REBUILD.  The call
+ *              is the call without the flag: same validation, writes, refit, event, `updates` count and stream ordering.  If the
+ *              state is IDLE it then enqueues, on fovpt_stream() behind the refit, a snapshot of the current positions (9 floats
+ *              per triangle into a buffer the build owns), starts one background build over it and returns; it never waits for the
+ *              device.  With no entries it is a background rebuild alone (nothing moves, no refit, nothing counted; the device
+ *              copies of the indices and positions are made if the scene has not been updated yet).  In state BUILDING or READY no
+ *              second build starts: `requested` counts the request, `started` does not.  One build per context is in flight.
+ *              (Its value is 16: the bits 4 and 8 are refused as unknown, as they always were.)
+ *   the build  fovpt_set_scene's (FOVPT_BVH, FOVPT_SPLIT, FOVPT_REINSERT, FOVPT_BVH_ORDER, and the second build without
+ *              reinsertion when the first is too deep), on a host thread that owns a stream of the lowest priority the device
+ *              offers, which waits for the snapshot's event.  The environment is read by the requesting call, on its thread: a
+ *              caller may change it while a build runs.  The thread touches nothing of the context but its own job record; it
+ *              measures the new tree's cost with partial sums of its own and publishes hierarchy, levels, scene facts, cost and
+ *              build time together.  A hierarchy too deep for the traversal stack (FOVPT_E_BVH_DEPTH), of more than 64 levels or
+ *              beyond the 32-bit offsets (FOVPT_E_INVALID), or a device error (FOVPT_E_DEVICE) is a failed build: nothing is kept,
+ *              the present hierarchy stays, `failed` counts it, `last_error` holds the code, the state is IDLE again and a later
+ *              request starts a new build.  A failed build makes no update call fail; fovpt_last_error gives its text after the
+ *              next fovpt_rebuild_state.
+ *   adoption   only in state READY and only in two places: at the start of a later fovpt_update_* call that enqueues something
+ *              (not one that returns at "nothing happens", nor one with FOVPT_UPDATE_REBUILD), and in
+ *              fovpt_rebuild_state(FOVPT_REBUILD_ADOPT).  So what fovpt_debug_buffer shows of the hierarchy changes only inside
+ *              calls the caller makes.  It never synchronises: on fovpt_stream() the new hierarchy becomes the scene's (with
+ *              stats.num_bvh_nodes / bvh_max_depth / bvh_bytes / tri_bytes / ms_bvh_build), a refit of it over the CURRENT
+ *              positions is enqueued (the snapshot may be several updates old) with the event the next job waits for, `updates`
+ *              counts 1, `built` becomes the cost the builder measured and, if the context is watching, a measurement follows as
+ *              behind any refit.  Frames already issued keep reading the old hierarchy.  Its memory is retired with events
+ *              recorded behind everything that can read it and released once a poll finds them complete, at a later update call
+ *              that enqueues something, fovpt_rebuild_state, fovpt_set_scene or fovpt_destroy; no call waits for those events
+ *              (the release itself, hipFree, waits for the device: DESIGN.md, section 27).  Positions, primitive ids, the
+ *              traversable handle, the temporal history and the tracking of fovpt_temporal_motion / fovpt_warp_motion are
+ *              untouched; a caller's G-buffer traced before the adoption no longer goes with the context's hit records
+ *              (fovpt_warp_motion with that G-buffer: FOVPT_E_NO_FRAME, as after an update).
+ *   ended      fovpt_set_scene, a FOVPT_UPDATE_REBUILD and fovpt_destroy end a background build early: the thread is joined and
+ *              the result freed (`discarded` counts it).  These calls are host-synchronous already.
+ *   state      fovpt_rebuild_state never waits for the device.  flags 0: polls.  FOVPT_REBUILD_WAIT: waits until the state is not
+ *              BUILDING, for the builder's thread and nothing else.  FOVPT_REBUILD_ADOPT: adopts now if READY (after the wait, if
+ *              both are given); in any other state it does nothing.
+ *   errors     FOVPT_E_INVALID: null ctx or out, unknown flag bits.  FOVPT_E_NO_SCENE: no scene.
+ * A context that never passes the flag creates no thread and no stream and issues exactly the HIP calls it issued before.
+ * FOVPT_ASYNC_BUILD_DELAY_MS (tests and tuning only; read by the requesting call): the builder's thread sleeps that long before it
+ * publishes.  Default 0; it changes no result.
+ * Device memory: the snapshot, 40 bytes per triangle (36 of positions, 4 of the mesh index), from the first request until the next
+ * fovpt_set_scene.  While a build runs, the builder's scratch on top, the same as in fovpt_set_scene: for the default build (PLOC with
+ * reinsertion, no splits) about 460 bytes per triangle, added up from the sizes of its arrays (176 of them the result before it
+ * is packed, 128 per binary node and 48 per triangle record; the sort's temporary storage comes on top).  From READY until the old
+ * one is released, the second hierarchy (stats.bvh_bytes + stats.tri_bytes).
+ * Time (MI355X; two frames in flight, a quarter of the meshes turning 3 degrees per frame, a rebuild asked
+ * for at current / built > 2): an adoption is 0.12 ms of device time at C3 and 0.47 ms on the street.  A build beside the frames
+ * takes 250 .. 590 ms at C3 against 15 ms on a stalled device, because every host round trip of the builder waits for frames: the
+ * longest frame interval falls from 14 ms to 5 .. 7 ms, the mean rises from 2.1 to 2.5 ms (the refit tree serves longer), and a
+ * fovpt_render issued while a build runs took up to 4.5 ms on the host.  On the street the build (13.5 s) does not keep up with the
+ * degrading tree: there FOVPT_UPDATE_REBUILD, or a much earlier request, is the better choice.                                      */
+#define FOVPT_UPDATE_REBUILD_ASYNC 16  /* all five fovpt_update_* calls; refused together with FOVPT_UPDATE_REBUILD              */
+#define FOVPT_REBUILD_IDLE 0           /* nothing in flight                                                                      */
+#define FOVPT_REBUILD_BUILDING 1       /* a background build is running                                                          */
+#define FOVPT_REBUILD_READY 2          /* a finished hierarchy waits to be adopted                                               */
+#define FOVPT_REBUILD_WAIT 1           /* flag: wait until the state is not BUILDING (and for nothing else)                      */
+#define FOVPT_REBUILD_ADOPT 2          /* flag: adopt now if READY (after WAIT, if both are given)                               */
+typedef struct fovpt_rebuild_info {
+    int32_t state, last_error;   /* last_error: 0, or the FOVPT_E_* of the last background build that failed                */
+    uint64_t requested, started, adopted, failed, discarded;
+    uint64_t snapshot_update;    /* the value of fovpt_hierarchy_cost_info.updates the newest snapshot was taken at         */
+    double ms_build;             /* device time of the last finished background build, on its own stream                    */
+} fovpt_rebuild_info;
+int fovpt_rebuild_state(fovpt_ctx* ctx, int flags, fovpt_rebuild_info* out);
+
 /* CUDAProbeData::createBuffer (Probe.h:102-124): uploads the 5 arrays, fills *probe_out
  * with device pointers exactly as setProbe does (SimplePathtracer.cpp:292-308).   */
 int fovpt_set_probe(fovpt_ctx* ctx, int width, int height, const fovpt_float4* data,
@@ -1584,6 +1655,8 @@ static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header
 static_assert(sizeof(fovpt_vertex_update) == 16 && offsetof(fovpt_vertex_update, vertex) == 8, "vertex update ABI");
 static_assert(sizeof(fovpt_mesh_transform) == 52 && offsetof(fovpt_mesh_transform, m) == 4, "mesh transform ABI");
 static_assert(sizeof(fovpt_hierarchy_cost_info) == 32 && offsetof(fovpt_hierarchy_cost_info, updates) == 16, "hierarchy cost ABI");
+static_assert(sizeof(fovpt_rebuild_info) == 64 && offsetof(fovpt_rebuild_info, requested) == 8 && offsetof(fovpt_rebuild_info, snapshot_update) == 48 &&
+              offsetof(fovpt_rebuild_info, ms_build) == 56, "rebuild info ABI");
 static_assert(sizeof(fovpt_mesh_skin) == 32 && offsetof(fovpt_mesh_skin, joints) == 16 && offsetof(fovpt_mesh_skin, weights) == 24, "mesh skin ABI");
 static_assert(sizeof(fovpt_skin_pose) == 16 && offsetof(fovpt_skin_pose, matrices) == 8, "skin pose ABI");
 static_assert(sizeof(fovpt_morph_target) == 24 && offsetof(fovpt_morph_target, index) == 8 && offsetof(fovpt_morph_target, delta) == 16, "morph target ABI");

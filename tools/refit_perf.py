@@ -29,7 +29,17 @@ alternates with update_skinned of the same matrices.
 channel of four keys on every node, one clip).  On one context, --rounds rounds of three updates to the same positions in turn:
 update_animated, update_skinned with host palettes computed beforehand (rig_ref.pose), update_vertices with device pointers.
 Then, on a scene of a few vertices, k_rig_pose by itself for 64 and 1024 nodes, flat and as one chain: what update_animated
-takes beyond update_skinned with a device palette, which issues the same launches but for k_rig_pose."""
+takes beyond update_skinned with a device palette, which issues the same launches but for k_rig_pose.
+
+--async: FOVPT_UPDATE_REBUILD_ASYNC against FOVPT_UPDATE_REBUILD.  The quality experiment's motion (a quarter of the meshes turning
+3 degrees per frame), frames back to back with two in flight (the loop waits for frame f - 2 before it issues frame f, as an
+application's present would; nothing else waits), the cost polled after every frame and a rebuild asked for whenever
+current / built exceeds --threshold.  In one run, --rounds times in turn: a loop of --frames frames that rebuilds synchronously
+(the reference) and one that passes the new flag.  Per loop: the mean, median and longest frame interval (device events on the
+library's stream behind every frame), the longest and median host time of every kind of call, and for the new flag the longest
+host time of any call while a build runs, the time from request to READY, the build's device time on its own stream, the mean
+interval while a build runs against the interval otherwise, and the intervals of the frames whose update adopted.  Last, on an
+idle device: the device and host time of one adoption, and the host time of the poll that releases the retired hierarchy."""
 import argparse
 import ctypes as C
 import json
@@ -382,6 +392,123 @@ def run_rig(name, calls, warmup, rounds):
             print(json.dumps(o), flush=True)
 
 
+def run_async(name, frames, rounds, threshold):
+    """--async: see the module docstring."""
+    model, r = make_renderer(name)
+    cfg = r.config
+    cfg.frames_in_flight = 2
+    r.config = cfg
+    st0 = r.stats()
+    moving = list(range(0, len(model.meshes), 4))
+    identity = {k: np.eye(3, 4, dtype=np.float32) for k in range(len(model.meshes))}
+    poses = [{k: turn_matrix(model.meshes[k].vertex, 3.0 * (f + 1)) for k in moving} for f in range(frames)]
+    stream = torch.cuda.ExternalStream(r.stream)
+    r.hierarchy_cost()                                          # watching: the caller decides on current / built
+    out = dict(scene=name, triangles=model.num_triangles, meshes=len(model.meshes), moving_meshes=len(moving), frames=frames, rounds=rounds,
+               threshold=threshold, build_ms_set_scene=round(st0.ms_bvh_build, 3))
+
+    def timed(calls, key, fn, building):
+        t = time.perf_counter()
+        v = fn()
+        calls.append((key, (time.perf_counter() - t) * 1e3, building))
+        return v
+
+    def loop(mode):
+        r.update_transforms(identity, rebuild=True)             # from rest, on a fresh tree, the device idle
+        r.synchronize()
+        calls, marks, building_frames, adopt_frames, rebuilds = [], [], [], [], 0
+        request_t, ready_ms, build_ms = None, [], []
+        want, adopted = False, 0
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(frames + 1)]
+        ev[0].record(stream)
+        for f in range(frames):
+            if f >= 2:
+                ev[f - 1].synchronize()                         # two frames in flight, as an application's present would hold it: frame f - 2 is done
+            building = False
+            if mode == "async":
+                s = timed(calls, "rebuild_state", r.rebuild_state, request_t is not None)
+                building = s.state == abi.REBUILD_BUILDING
+                if request_t is not None and s.state != abi.REBUILD_BUILDING:
+                    ready_ms.append((time.perf_counter() - request_t) * 1e3)
+                    build_ms.append(s.ms_build)
+                    request_t = None
+                if s.adopted != adopted:
+                    adopted = s.adopted
+                    adopt_frames.append(f - 1)                  # the previous frame's update adopted
+                ask = want and s.state == abi.REBUILD_IDLE
+                flag = "async" if ask else False
+            else:
+                ask = want
+                flag = bool(want)
+            timed(calls, "update_rebuild" if (ask and mode == "sync") else "update", lambda: r.update_transforms(poses[f], rebuild=flag), building)
+            if ask:
+                want, rebuilds = False, rebuilds + 1
+                if mode == "async":
+                    request_t, building = time.perf_counter(), True
+            r.launchParams.frame.subframe_index = 0
+            timed(calls, "render", r.render_async, building)
+            c = timed(calls, "hierarchy_cost", r.hierarchy_cost, building)
+            if c.built > 0 and c.current / c.built > threshold and request_t is None:
+                want = True
+            ev[f + 1].record(stream)
+            marks.append(building)
+        late = None
+        if mode == "async":
+            if request_t is not None:                           # still BUILDING behind the last frame: how long the request has taken once it is READY
+                t_issued = time.perf_counter()
+                s = r.rebuild_state(wait=True)
+                late = dict(request_to_ready_ms=round((time.perf_counter() - request_t) * 1e3, 3),
+                            of_which_after_the_last_frame_was_issued_ms=round((time.perf_counter() - t_issued) * 1e3, 3),
+                            build_device_ms=round(s.ms_build, 3), state=int(s.state))
+            else:
+                r.rebuild_state(wait=True)
+        r.synchronize()
+        iv = np.array([ev[k].elapsed_time(ev[k + 1]) for k in range(frames)])
+        marks = np.array(marks)
+        res = dict(rebuilds=rebuilds, interval_mean_ms=round(float(iv.mean()), 4), interval_max_ms=round(float(iv.max()), 4),
+                   interval_median_ms=round(float(np.median(iv)), 4), total_ms=round(float(iv.sum()), 3))
+        for key in sorted(set(k for k, _, _ in calls)):
+            res["host_max_ms_" + key] = round(max(t for k, t, _ in calls if k == key), 4)
+            res["host_median_ms_" + key] = round(float(np.median([t for k, t, _ in calls if k == key])), 4)
+        if mode == "async":
+            during = [t for k, t, b in calls if b]
+            res["host_max_ms_any_call_while_building"] = round(max(during), 4) if during else None
+            res["request_to_ready_ms"] = [round(x, 3) for x in ready_ms]
+            res["build_device_ms"] = [round(x, 3) for x in build_ms]
+            res["frames_while_building"] = int(marks.sum())
+            res["interval_mean_ms_while_building"] = round(float(iv[marks].mean()), 4) if marks.any() else None
+            res["interval_mean_ms_otherwise"] = round(float(iv[~marks].mean()), 4) if (~marks).any() else None
+            res["interval_ms_of_adopting_frames"] = [round(float(iv[k]), 4) for k in adopt_frames if 0 <= k < frames]
+            res["adopted"] = int(adopted)
+            res["ready_only_after_the_loop"] = late
+        return res
+
+    out["loops"] = []
+    for k in range(rounds):
+        for mode in ("sync", "async"):
+            res = loop(mode)
+            res["mode"], res["round"] = mode, k
+            out["loops"].append(res)
+    # the device time of an adoption alone: an idle device, a finished build, events around rebuild_state(adopt)
+    r.update_transforms(identity, rebuild=True)
+    r.update_transforms({}, rebuild="async")
+    r.rebuild_state(wait=True)
+    r.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(stream)
+    t = time.perf_counter()
+    r.rebuild_state(adopt=True)
+    out["adopt_host_ms"] = round((time.perf_counter() - t) * 1e3, 4)
+    b.record(stream)
+    b.synchronize()
+    out["adopt_device_ms"] = round(a.elapsed_time(b), 4)
+    t = time.perf_counter()
+    r.rebuild_state()                                           # the poll that releases the retired hierarchy (hipFree)
+    out["release_poll_host_ms"] = round((time.perf_counter() - t) * 1e3, 4)
+    r.close()
+    print(json.dumps(out), flush=True)
+
+
 def _levels(parent):
     lv = []
     for p in parent:
@@ -399,6 +526,8 @@ def main():
     ap.add_argument("--skin", action="store_true", help="fovpt_update_skinned against fovpt_update_vertices with device pointers and with host arrays")
     ap.add_argument("--morph", action="store_true", help="fovpt_update_morphed against fovpt_update_vertices with device pointers and with host arrays, and with matrices against fovpt_update_skinned")
     ap.add_argument("--rig", action="store_true", help="fovpt_update_animated against fovpt_update_skinned with host palettes and fovpt_update_vertices with device pointers, and k_rig_pose by itself")
+    ap.add_argument("--async", dest="async_", action="store_true", help="FOVPT_UPDATE_REBUILD_ASYNC against FOVPT_UPDATE_REBUILD in a frame loop with large motion")
+    ap.add_argument("--threshold", type=float, default=2.0, help="--async: a rebuild is asked for when current / built exceeds it")
     ap.add_argument("--morph-dense", type=int, default=8)
     ap.add_argument("--morph-sparse", type=int, default=44)
     ap.add_argument("--morph-fraction", type=float, default=0.05)
@@ -406,7 +535,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="--transforms, --skin, --morph, --rig: rounds of the alternated timings (at least 5)")
     a = ap.parse_args()
     for s in a.scenes.split(","):
-        if a.rig:
+        if a.async_:
+            run_async(s, a.frames, a.rounds, a.threshold)
+        elif a.rig:
             run_rig(s, a.calls, a.warmup, max(5, a.rounds))
         elif a.morph:
             run_morph(s, a.calls, a.warmup, max(5, a.rounds), a.morph_dense, a.morph_sparse, a.morph_fraction, a.morph_active)
