@@ -536,6 +536,8 @@ class LensConfig(C.Structure):
 
 PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS =0x4b505646, 1, 4      # FOVPT_PACKET_*
 PACKET_NEAREST, PACKET_SMOOTH = 0, 1
+PACKET_MAGIC_CODED = 0x43505646                                   # "FVPC": a coded packet, a codec per pass
+PACKET_RAW, PACKET_BC1, PACKET_BY_FILL = 0, 1, 0xffffffff
 
 
 class PacketPass(C.Structure):
@@ -546,8 +548,14 @@ class PacketPass(C.Structure):
     ]
 
 
+class PacketConfig(C.Structure):
+    """fovpt_packet_config: the codec of every launch pass of a coded packet (PACKET_RAW, PACKET_BC1, PACKET_BY_FILL)."""
+    _fields_ = [("codec", C.c_uint32 * 3), ("_reserved", C.c_uint32)]
+
+
 class PacketHeader(C.Structure):
-    """fovpt_packet_header: the first 128 bytes of a foveated frame packet."""
+    """fovpt_packet_header: the first 128 bytes of a foveated frame packet, raw ("FVPK") or coded ("FVPC": a pass's _reserved is
+    its codec)."""
     _fields_ = [
         ("magic", C.c_uint32), ("version", C.c_uint32), ("bytes", C.c_uint32), ("sequence", C.c_uint32),
         ("width", C.c_int32), ("height", C.c_int32), ("npass", C.c_uint32), ("_reserved", C.c_uint32),
@@ -593,6 +601,7 @@ assert C.sizeof(FocusConfig) == 64 and (FocusConfig.strength.offset, FocusConfig
 assert C.sizeof(FocusState) == 32 and FocusState.count.offset == 16
 assert C.sizeof(LensConfig) == 128 and (LensConfig.k.offset, LensConfig.clip_r2.offset, LensConfig.border.offset, LensConfig._reserved.offset) == (32, 60, 80, 96)
 assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
+assert C.sizeof(PacketConfig) == 16 and PacketConfig._reserved.offset == 12
 assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeader.passes.offset) == (16, 32)
 assert C.sizeof(VertexUpdate) == 16 and VertexUpdate.vertex.offset == 8
 assert C.sizeof(MeshTransform) == 52 and MeshTransform.m.offset == 4

@@ -1,4 +1,4 @@
-// api_packet.hip -- foveated frame packets over the C ABI (include/fovpt.h, fovpt_packet_*): the header of the frame as rendered,
+// api_packet.hip -- foveated frame packets, raw and coded, over the C ABI (include/fovpt.h, fovpt_packet_*): the header of the frame as rendered,
 // the encoder (packet.hip) on fovpt_stream(), the slots that take a packet to pinned host memory on a copy stream of the
 // context's own, and the device decoder.  The decoder for a client and the checks are packet_host.cpp.
 #include <cstring>
@@ -9,22 +9,32 @@
 namespace {
 
 // What describe, encode and submit (`who`) ask: a frame was rendered, whole, at lp's size, and its packet is one the decoders
-// accept.  Fills the kernels' arguments; nothing is allocated, enqueued or changed.
-int packet_args(fovpt_ctx* c, const fovpt_launch_params* lp, uint32_t sequence, const char* who, PacketArgs& a)
+// accept.  Fills the kernels' arguments; nothing is allocated, enqueued or changed.  cfg: null for an "FVPK" packet, else the
+// codecs of a coded one, whose a.first[] counts k_packet_encode_coded's threads.
+int packet_args(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, uint32_t sequence, const char* who, PacketArgs& a)
 {
     if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "%s: no frame rendered yet", who);
     if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "%s: a tile shard (world = %d) does not see the frame", who, c->dn_world);
     if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
         return fail(c, FOVPT_E_NO_FRAME, "%s: frame size %d x %d differs from the last frame's %d x %d", who, lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
     const FrameDev& fd = c->dn_frame;
+    if (cfg) {
+        if (cfg->_reserved) return fail(c, FOVPT_E_INVALID, "%s: non-zero reserved word in the packet config", who);
+        for (int p = 0; p < FOVPT_MAX_PASSES; p++) {
+            const uint32_t k = cfg->codec[p];
+            if (k == FOVPT_PACKET_BY_FILL) continue;
+            if (k > FOVPT_PACKET_BC1) return fail(c, FOVPT_E_INVALID, "%s: unknown codec %u for pass %d", who, k, p);
+            if (p >= fd.npass && k) return fail(c, FOVPT_E_INVALID, "%s: codec %u for pass %d of a frame of %d", who, k, p, fd.npass);
+        }
+    }
     memset(&a, 0, sizeof(a));
     fovpt_packet_header& h = a.h;
-    h.magic = FOVPT_PACKET_MAGIC; h.version = FOVPT_PACKET_VERSION; h.sequence = sequence;
+    h.magic = cfg ? FOVPT_PACKET_MAGIC_CODED : FOVPT_PACKET_MAGIC; h.version = FOVPT_PACKET_VERSION; h.sequence = sequence;
     h.width = fd.w; h.height = fd.h;
     h.npass = (uint32_t)fd.npass;
-    uint64_t at = FOVPT_PACKET_HEADER_BYTES, texels = 0;
+    uint64_t at = FOVPT_PACKET_HEADER_BYTES, texels = 0, threads = 0;
     for (int p = 0; p < FOVPT_MAX_PASSES; p++) {
-        a.first[p] = (uint32_t)texels;
+        a.first[p] = (uint32_t)(cfg ? threads : texels);
         if (p >= fd.npass) continue;
         const PassDev& P = fd.pass[p];
         const uint64_t n = (uint64_t)P.gw * (uint64_t)P.gh;
@@ -35,9 +45,12 @@ int packet_args(fovpt_ctx* c, const fovpt_launch_params* lp, uint32_t sequence, 
         fovpt_packet_pass& O = h.pass[p];
         O.gw = P.gw; O.gh = P.gh; O.factor = P.fx; O.fill = (uint32_t)P.fill; O.offx = P.offx; O.offy = P.offy;
         O.texels = (uint32_t)at;
-        at += 4 * n;
+        if (cfg) O._reserved = cfg->codec[p] == FOVPT_PACKET_BY_FILL ? (P.fill > 1 ? FOVPT_PACKET_BC1 : FOVPT_PACKET_RAW) : cfg->codec[p];
+        at += fovpt_packet_pass_bytes(P.gw, P.gh, O._reserved);
+        // a raw pass: a thread per texel; a BC1 pass: 16 per block; whole groups of 16 (<= 2^26 + 2^15 per pass)
+        threads += O._reserved == FOVPT_PACKET_BC1 ? 16ull * (((uint64_t)P.gw + 3u) >> 2) * (((uint64_t)P.gh + 3u) >> 2) : (n + 15u) & ~15ull;
     }
-    a.first[FOVPT_MAX_PASSES] = (uint32_t)texels;
+    a.first[FOVPT_MAX_PASSES] = (uint32_t)(cfg ? threads : texels);
     h.bytes = (uint32_t)at;                                           // (<= 128 + 2^28)
     if (const char* why = fovpt_packet_header_error(&h, at)) return fail(c, FOVPT_E_INVALID, "%s: the frame does not fit a packet: %s", who, why);
     return FOVPT_OK;
@@ -63,34 +76,37 @@ int packet_slots(fovpt_ctx* c)
     return FOVPT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fovpt_packet_describe(fovpt_ctx* c, const fovpt_launch_params* lp, uint32_t sequence, fovpt_packet_header* out)
+// The three entry points, raw (cfg null) and coded (coded: cfg must not be null).
+int packet_describe(const char* who, bool coded, fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, uint32_t sequence,
+                    fovpt_packet_header* out)
 {
-    const char* who = "fovpt_packet_describe";
     if (!c) return FOVPT_E_INVALID;
-    if (!lp || !out) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (!lp || !out || (coded && !cfg)) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
     PacketArgs a;
-    { const int rc_ = packet_args(c, lp, sequence, who, a); if (rc_) return rc_; }
+    { const int rc_ = packet_args(c, lp, cfg, sequence, who, a); if (rc_) return rc_; }
     *out = a.h;
     return FOVPT_OK;
 }
 
-// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: behind the frame's resolve, ahead of the next frame's.
-int fovpt_packet_encode(fovpt_ctx* c, const fovpt_launch_params* lp, const uint32_t* in_rgba, uint32_t sequence, void* out_packet)
+void launch_encode(fovpt_ctx* c, const PacketArgs& a, const uint32_t* in, uint32_t* out)
 {
-    const char* who = "fovpt_packet_encode";
+    if (a.h.magic == FOVPT_PACKET_MAGIC_CODED) fovpt_launch_packet_encode_coded(c->shadow_stream, c->dn_frame, a, in, out);
+    else fovpt_launch_packet_encode(c->shadow_stream, c->dn_frame, a, in, out);
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: behind the frame's resolve, ahead of the next frame's.
+int packet_encode(const char* who, bool coded, fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba,
+                  uint32_t sequence, void* out_packet)
+{
     if (!c) return FOVPT_E_INVALID;
-    if (!lp || !out_packet) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (!lp || !out_packet || (coded && !cfg)) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
     if (((uintptr_t)out_packet & 3u) != 0u) return fail(c, FOVPT_E_INVALID, "%s: the packet buffer is not 4-byte aligned", who);
     PacketArgs a;
-    { const int rc_ = packet_args(c, lp, sequence, who, a); if (rc_) return rc_; }
+    { const int rc_ = packet_args(c, lp, cfg, sequence, who, a); if (rc_) return rc_; }
     const uint32_t* in = packet_input(lp, in_rgba);
     if (!in) return fail(c, FOVPT_E_NO_FRAME, "%s: null frame_buffer", who);
     HIPCHK(c, hipSetDevice(c->device));
-    fovpt_launch_packet_encode(c->shadow_stream, c->dn_frame, a, in, (uint32_t*)out_packet);
+    launch_encode(c, a, in, (uint32_t*)out_packet);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }
@@ -98,13 +114,13 @@ int fovpt_packet_encode(fovpt_ctx* c, const fovpt_launch_params* lp, const uint3
 // The encode into the slot's own device buffer on fovpt_stream(), an event behind it, and on the copy stream -- which waits for
 // that event and for nothing else -- the copy into the slot's pinned buffer and the slot's done-event.  The host waits only for
 // the previous copy out of the slot it is about to reuse, if that is still running.
-int fovpt_packet_submit(fovpt_ctx* c, const fovpt_launch_params* lp, const uint32_t* in_rgba, uint32_t sequence, int* slot)
+int packet_submit(const char* who, bool coded, fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba,
+                  uint32_t sequence, int* slot)
 {
-    const char* who = "fovpt_packet_submit";
     if (!c) return FOVPT_E_INVALID;
-    if (!lp || !slot) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (!lp || !slot || (coded && !cfg)) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
     PacketArgs a;
-    { const int rc_ = packet_args(c, lp, sequence, who, a); if (rc_) return rc_; }
+    { const int rc_ = packet_args(c, lp, cfg, sequence, who, a); if (rc_) return rc_; }
     const uint32_t* in = packet_input(lp, in_rgba);
     if (!in) return fail(c, FOVPT_E_NO_FRAME, "%s: null frame_buffer", who);
     HIPCHK(c, hipSetDevice(c->device));
@@ -120,7 +136,7 @@ int fovpt_packet_submit(fovpt_ctx* c, const fovpt_launch_params* lp, const uint3
         S.host_bytes = bytes;
     }
     HIPCHK(c, S.dev.reserve(bytes));
-    fovpt_launch_packet_encode(c->shadow_stream, c->dn_frame, a, in, (uint32_t*)S.dev.p);
+    launch_encode(c, a, in, (uint32_t*)S.dev.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(S.ev_encoded, c->shadow_stream));
     HIPCHK(c, hipStreamWaitEvent(c->pk_stream, S.ev_encoded, 0));
@@ -131,6 +147,44 @@ int fovpt_packet_submit(fovpt_ctx* c, const fovpt_launch_params* lp, const uint3
     c->pk_next++;
     *slot = k;
     return FOVPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fovpt_packet_describe(fovpt_ctx* c, const fovpt_launch_params* lp, uint32_t sequence, fovpt_packet_header* out)
+{
+    return packet_describe("fovpt_packet_describe", false, c, lp, nullptr, sequence, out);
+}
+int fovpt_packet_encode(fovpt_ctx* c, const fovpt_launch_params* lp, const uint32_t* in_rgba, uint32_t sequence, void* out_packet)
+{
+    return packet_encode("fovpt_packet_encode", false, c, lp, nullptr, in_rgba, sequence, out_packet);
+}
+int fovpt_packet_submit(fovpt_ctx* c, const fovpt_launch_params* lp, const uint32_t* in_rgba, uint32_t sequence, int* slot)
+{
+    return packet_submit("fovpt_packet_submit", false, c, lp, nullptr, in_rgba, sequence, slot);
+}
+
+void fovpt_packet_defaults(fovpt_packet_config* cfg)
+{
+    if (!cfg) return;
+    for (uint32_t& k : cfg->codec) k = FOVPT_PACKET_BY_FILL;
+    cfg->_reserved = 0;
+}
+int fovpt_packet_describe_coded(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, uint32_t sequence, fovpt_packet_header* out)
+{
+    return packet_describe("fovpt_packet_describe_coded", true, c, lp, cfg, sequence, out);
+}
+int fovpt_packet_encode_coded(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba, uint32_t sequence,
+                              void* out_packet)
+{
+    return packet_encode("fovpt_packet_encode_coded", true, c, lp, cfg, in_rgba, sequence, out_packet);
+}
+int fovpt_packet_submit_coded(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba, uint32_t sequence,
+                              int* slot)
+{
+    return packet_submit("fovpt_packet_submit_coded", true, c, lp, cfg, in_rgba, sequence, slot);
 }
 
 int fovpt_packet_wait(fovpt_ctx* c, int slot, const void** packet, size_t* bytes)

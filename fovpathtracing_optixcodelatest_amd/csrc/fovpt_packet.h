@@ -14,6 +14,11 @@
 // The checks of fovpt_packet_check on a header alone, `avail` the bytes the caller holds (packet_host.cpp).  Null: the header is
 // valid; otherwise what is wrong with it.
 const char* fovpt_packet_header_error(const fovpt_packet_header* h, uint64_t avail);
+// the bytes of a pass's array under a codec (FOVPT_PACKET_RAW / _BC1), in 64 bits
+inline uint64_t fovpt_packet_pass_bytes(uint32_t gw, uint32_t gh, uint32_t codec)
+{
+    return codec == FOVPT_PACKET_BC1 ? 8ull * (((uint64_t)gw + 3u) >> 2) * (((uint64_t)gh + 3u) >> 2) : 4ull * (uint64_t)gw * (uint64_t)gh;
+}
 
 #ifdef __HIP__
 #include "fovpt_device.h"
@@ -27,5 +32,9 @@ struct PacketArgs {
 };
 // fd: the frame as rendered (fovpt_ctx::dn_frame), whose passes a.h describes.  in: the rgba8 image; out: the packet.
 void fovpt_launch_packet_encode(hipStream_t st, const FrameDev& fd, const PacketArgs& a, const uint32_t* in, uint32_t* out);
+// A coded packet ("FVPC", a.h.pass[p]._reserved the codec): first[p] is the first thread of pass p, a multiple of 16 -- a raw
+// pass takes one thread per texel, a BC1 pass 16 per block --, first[npass] their total; the arrays go by their byte offsets.
+void fovpt_launch_packet_encode_coded(hipStream_t st, const FrameDev& fd, const PacketArgs& a, const uint32_t* in, uint32_t* out);
+// (either magic: a coded header runs the CODED instantiation)
 void fovpt_launch_packet_decode(hipStream_t st, const PacketArgs& a, int mode, const uint32_t* packet, uint32_t* out);
 #endif

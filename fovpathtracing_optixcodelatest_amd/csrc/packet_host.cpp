@@ -1,5 +1,5 @@
 // packet_host.cpp -- the foveated frame packet for a client: fovpt_packet_check and fovpt_packet_decode_host (include/fovpt.h;
-// the definition in integers: tests/packet_ref.py).  Host-only C++ without a context, for untrusted bytes: compiled into
+// the definition in integers: tests/packet_ref.py, of a coded packet's BC1 passes tests/packet_bc_ref.py).  Host-only C++ without a context, for untrusted bytes: compiled into
 // libfovpt.so and into libfovpt_loader.so, the library for machines without ROCm.  Every read goes through memcpy inside
 // [packet, packet + header.bytes), which the checks have shown to lie inside the caller's bytes; every write is to a pixel
 // index clamped into the output.
@@ -16,7 +16,8 @@ static_assert(sizeof(fovpt_packet_header) == FOVPT_PACKET_HEADER_BYTES, "packet 
 
 const char* fovpt_packet_header_error(const fovpt_packet_header* h, uint64_t avail)
 {
-    if (h->magic != FOVPT_PACKET_MAGIC) return "wrong magic";
+    const bool coded = h->magic == FOVPT_PACKET_MAGIC_CODED;             // ("FVPC": the pass's eighth word is its codec)
+    if (h->magic != FOVPT_PACKET_MAGIC && !coded) return "wrong magic";
     if (h->version != FOVPT_PACKET_VERSION) return "unknown version";
     if (h->bytes > avail || h->bytes < FOVPT_PACKET_HEADER_BYTES) return "bytes field outside 128 .. the bytes given";
     if (h->width < 1 || h->width > FOVPT_PACKET_MAX_DIM || h->height < 1 || h->height > FOVPT_PACKET_MAX_DIM) return "width / height outside 1 .. 16384";
@@ -29,14 +30,14 @@ const char* fovpt_packet_header_error(const fovpt_packet_header* h, uint64_t ava
             if (P.gw | P.gh | P.factor | P.fill | P.offx | P.offy | P.texels | P._reserved) return "non-zero unused pass entry";
             continue;
         }
-        if (P._reserved) return "non-zero reserved field";
+        if (coded ? P._reserved > FOVPT_PACKET_BC1 : P._reserved != 0u) return coded ? "unknown codec" : "non-zero reserved field";
         if (P.gw == 0 || P.gh == 0) return "empty launch grid";
         const uint64_t n = (uint64_t)P.gw * (uint64_t)P.gh;               // (< 2^64)
         if (n > FOVPT_PACKET_MAX_TEXELS || (texels += n) > FOVPT_PACKET_MAX_TEXELS) return "more than 2^26 texels";
         if (P.factor == 0) return "factor 0";
         if (P.fill < 1 || P.fill > FOVPT_PACKET_MAX_FILL) return "fill outside 1 .. 8";
         if (P.texels < FOVPT_PACKET_HEADER_BYTES || (P.texels & 3u)) return "texel offset below 128 or not a multiple of 4";
-        if ((uint64_t)P.texels + 4ull * n > (uint64_t)h->bytes) return "texel array outside the packet";
+        if ((uint64_t)P.texels + fovpt_packet_pass_bytes(P.gw, P.gh, P._reserved) > (uint64_t)h->bytes) return "texel array outside the packet";
     }
     return nullptr;
 }
@@ -60,8 +61,29 @@ int read_header(const char* who, const void* packet, size_t bytes, fovpt_packet_
     return FOVPT_OK;
 }
 
+// one texel of a BC1 pass, decoded from its 8-byte block (include/fovpt.h; tests/packet_bc_ref.py)
+inline uint32_t bc1_texel(const unsigned char* blocks, uint32_t gw, uint32_t lx, uint32_t ly)
+{
+    const uint64_t bw = ((uint64_t)gw + 3u) >> 2;
+    uint32_t w[2];
+    memcpy(w, blocks + 8ull * ((uint64_t)(ly >> 2) * bw + (lx >> 2)), 8);
+    const uint32_t c0 = w[0] & 0xffffu, c1 = w[0] >> 16, j = (w[1] >> (2u * (4u * (ly & 3u) + (lx & 3u)))) & 3u;
+    const bool four = c0 > c1;
+    if (j == 3u && !four) return 0u;
+    const uint32_t e0[3] = {c0 >> 11, (c0 >> 5) & 63u, c0 & 31u}, e1[3] = {c1 >> 11, (c1 >> 5) & 63u, c1 & 31u};
+    uint32_t v = 0xff000000u;
+    for (int k = 0; k < 3; k++) {
+        const uint32_t x = k == 1 ? (e0[k] << 2 | e0[k] >> 4) : (e0[k] << 3 | e0[k] >> 2), y = k == 1 ? (e1[k] << 2 | e1[k] >> 4) : (e1[k] << 3 | e1[k] >> 2);
+        const uint32_t c = j == 0u ? x : j == 1u ? y : !four ? (x + y + 1u) / 2u : j == 2u ? (2u * x + y + 1u) / 3u : (x + 2u * y + 1u) / 3u;
+        v |= c << (8 * k);
+    }
+    return v;
+}
+
+// (an "FVPK" pass has _reserved 0 = FOVPT_PACKET_RAW)
 inline uint32_t texel(const unsigned char* base, const fovpt_packet_pass& P, uint32_t lx, uint32_t ly)
 {
+    if (P._reserved == FOVPT_PACKET_BC1) return bc1_texel(base + P.texels, P.gw, lx, ly);
     uint32_t v;
     memcpy(&v, base + P.texels + 4ull * ((uint64_t)ly * P.gw + lx), 4);
     return v;

@@ -33,6 +33,7 @@ EXPORTS = [
     "fovpt_lens_defaults", "fovpt_lens", "fovpt_lens_buffers",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
     "fovpt_packet_check", "fovpt_packet_decode_host",
+    "fovpt_packet_defaults", "fovpt_packet_describe_coded", "fovpt_packet_encode_coded", "fovpt_packet_submit_coded",
     "fovpt_comm_get_unique_id", "fovpt_comm_init", "fovpt_comm_destroy", "fovpt_gather_frame",
     "fovpt_model_load_obj", "fovpt_model_load_gltf", "fovpt_model_destroy", "fovpt_model_counts", "fovpt_model_get_mesh", "fovpt_model_get_texture",
     "fovpt_image_load_float4", "fovpt_image_free", "fovpt_image_load_rgba8", "fovpt_image_free_rgba8",
@@ -212,6 +213,11 @@ def load():
     L.fovpt_packet_submit.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, C.POINTER(i32)]
     L.fovpt_packet_wait.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz)]
     L.fovpt_packet_decode.argtypes = [vp, C.POINTER(abi.PacketHeader), vp, i32, vp]
+    L.fovpt_packet_defaults.argtypes = [C.POINTER(abi.PacketConfig)]
+    L.fovpt_packet_defaults.restype = None
+    L.fovpt_packet_describe_coded.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.PacketConfig), u32, C.POINTER(abi.PacketHeader)]
+    L.fovpt_packet_encode_coded.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.PacketConfig), vp, u32, vp]
+    L.fovpt_packet_submit_coded.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.PacketConfig), vp, u32, C.POINTER(i32)]
     L.fovpt_update_vertices.argtypes = [vp, C.POINTER(abi.VertexUpdate), i32, i32]
     L.fovpt_update_transforms.argtypes = [vp, C.POINTER(abi.MeshTransform), i32, i32]
     L.fovpt_hierarchy_cost.argtypes = [vp, i32, C.POINTER(abi.HierarchyCost)]

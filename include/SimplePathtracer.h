@@ -423,6 +423,14 @@ public:
         check(fovpt_packet_submit(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), in_rgba, sequence, &slot));
         return slot;
     }
+    // the same as a coded packet ("FVPC"): codec.codec[p] says whether launch pass p goes as raw texels or as BC1 blocks
+    // (fovpt_packet_defaults: BC1 where the pass's fill is above 1, so the fovea stays exact); the slots are the same
+    int submitPacket(uint32_t sequence, const fovpt_packet_config& codec, const uint32_t* in_rgba = nullptr)
+    {
+        int slot = -1;
+        check(fovpt_packet_submit_coded(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &codec, in_rgba, sequence, &slot));
+        return slot;
+    }
     // valid until the slot is submitted again (FOVPT_PACKET_SLOTS submits later)
     Packet waitPacket(int slot)
     {

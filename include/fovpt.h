@@ -1371,6 +1371,56 @@ int fovpt_packet_decode(fovpt_ctx* ctx, const fovpt_packet_header* header /* hos
 int fovpt_packet_check(const void* packet, size_t bytes);
 int fovpt_packet_decode_host(const void* packet, size_t bytes, int mode, uint32_t* out_rgba, int width, int height);
 
+/* ---- coded frame packets: levels as BC1 blocks, encoded on the device -----------------------------------------------------------
+ * New with this library (the definition in integers: tests/packet_bc_ref.py).  A coded packet has magic
+ * "FVPC", version 1 and the header above; the eighth word of a pass record (_reserved in the struct) is the pass's codec:
+ *   FOVPT_PACKET_RAW   4 * gw * gh bytes of texels, as in an "FVPK" packet
+ *   FOVPT_PACKET_BC1   8 * ceil(gw / 4) * ceil(gh / 4) bytes: BC1 / DXT1 blocks, row-major by * ceil(gw / 4) + bx, block (bx, by)
+ *                      over texels (4 bx .. 4 bx + 3, 4 by .. 4 by + 3); texels beyond the grid count as dead
+ * The arrays lie back to back from byte 128 at multiples of 4.  The texels that get coded are those of fovpt_packet_encode.
+ *   block     L: the block's texels with alpha != 0.  L empty: 00 00 00 00 ff ff ff ff.  Else per channel lo / hi = min / max over
+ *             L; ref = the channel with the largest hi - lo (ties: g, r, b); endpoint A takes hi_ref, B lo_ref; another channel k
+ *             gives A hi_k and B lo_k unless s_k = sum over L of (2 c_k - lo_k - hi_k)(2 c_ref - lo_ref - hi_ref) < 0, then A lo_k
+ *             and B hi_k.  565: q5(c) = (31 c + 127) / 255, q6(c) = (63 c + 127) / 255, a = q5(A_r) << 11 | q6(A_g) << 5 | q5(A_b).
+ *             a == b, or a dead texel in the block: color0 = min(a, b), color1 = max(a, b) -- the 3-colour mode, index 3
+ *             transparent; else color0 = max, color1 = min (4 colours).  Palette from e5(v) = v << 3 | v >> 2, e6(v) = v << 2 |
+ *             v >> 4: P2 = (2 P0 + P1 + 1) / 3, P3 = (P0 + 2 P1 + 1) / 3 (4 colours), P2 = (P0 + P1 + 1) / 2 (3 colours).  A live
+ *             texel's index: the opaque entry with the least squared distance, ties to the lowest; a dead texel's: 3.  Bytes:
+ *             color0, color1 (LE16), a 32-bit LE word with texel (x, y) at bits 2 (4 y + x).
+ *   decode    index 3 with color0 <= color1: 0x00000000; else 0xff000000 | b << 16 | g << 8 | r of the palette entry.  Liveness
+ *             survives texel by texel, so NEAREST writes exactly the pixels it writes for the raw packet.
+ * expand(coded packet) -- every BC1 pass replaced by its decoded texels -- is a valid "FVPK" packet, and NEAREST / SMOOTH of a
+ * coded packet are NEAREST / SMOOTH of that.  fovpt_packet_check, fovpt_packet_decode_host and fovpt_packet_decode take both
+ * magics; for "FVPC" the rejections are those above with the pass word a codec in {0, 1} and the array's end computed from
+ * the codec (in 64 bits).
+ *   fovpt_packet_defaults        codec[] = FOVPT_PACKET_BY_FILL: a pass is BC1 if its fill at describe time is above 1, else raw
+ *                                (the fovea, and the one pass of FOV_OFF, stay exact).
+ *   fovpt_packet_describe_coded / _encode_coded / _submit_coded   as their raw counterparts -- ordering, checks, error codes, the
+ *                                same four slots (raw and coded submits may alternate, fovpt_packet_wait serves both) --, with
+ *                                cfg->codec[p] the codec of launch pass p: FOVPT_PACKET_RAW, _BC1 or _BY_FILL.  Additionally
+ *                                FOVPT_E_INVALID for a null cfg, another codec, a non-zero entry beyond the frame's passes (other
+ *                                than _BY_FILL) or a non-zero _reserved.  k_packet_encode_coded: 16 lanes per block.
+ * At 1920 x 1080, radii 148 / 482: 537 752 bytes with P and M coded, 227 536 with all three, against 1 810 768.  On an MI355X
+ * k_packet_encode_coded takes 0.042 ms (k_packet_encode: 0.039), the coded decoders 0.015 ms (NEAREST) / 0.031 ms (SMOOTH); the
+ * frame loop with a coded submit per frame takes 0.817 ms against 0.812 ms with a raw one.  The block code is a range fit: on
+ * fovpt_post's output of a 1 / 2 spp periphery the decoded coded levels are 15 .. 16 codes RMSE off the decoded raw packet, and a
+ * coded fovea 17: keep the fovea raw.                                                                     */
+#define FOVPT_PACKET_MAGIC_CODED 0x43505646u   /* "FVPC" */
+#define FOVPT_PACKET_RAW     0u
+#define FOVPT_PACKET_BC1     1u
+#define FOVPT_PACKET_BY_FILL 0xffffffffu       /* in a config only: BC1 where the pass's fill > 1 */
+typedef struct fovpt_packet_config {    /* 16 bytes */
+    uint32_t codec[3];                  /* per launch pass (P, M, F; FOV_OFF: one) */
+    uint32_t _reserved;                 /* 0 */
+} fovpt_packet_config;
+void fovpt_packet_defaults(fovpt_packet_config* cfg);
+int fovpt_packet_describe_coded(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, uint32_t sequence,
+                                fovpt_packet_header* out);
+int fovpt_packet_encode_coded(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba,
+                              uint32_t sequence, void* out_packet);
+int fovpt_packet_submit_coded(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba,
+                              uint32_t sequence, int* slot);
+
 /* ---- multi-GPU: packed gather of the final framebuffer ----------------------------------
  * New with this library: the reference is single-GPU (SimplePathtracer.cpp:331-340).  With
  * fovpt_config.rank/world every handle renders the launch-index tiles it owns -- interleaved
@@ -1650,6 +1700,7 @@ static_assert(sizeof(struct fovpt_focus_state) == 32 && offsetof(struct fovpt_fo
 static_assert(sizeof(fovpt_lens_config) == 128 && offsetof(fovpt_lens_config, k) == 32 && offsetof(fovpt_lens_config, clip_r2) == 60 &&
               offsetof(fovpt_lens_config, border) == 80 && offsetof(fovpt_lens_config, _reserved) == 96, "lens config ABI");
 static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");
+static_assert(sizeof(fovpt_packet_config) == 16 && offsetof(fovpt_packet_config, _reserved) == 12, "packet config ABI");
 static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header, width) == 16 && offsetof(fovpt_packet_header, pass) == 32,
               "packet header ABI");
 static_assert(sizeof(fovpt_vertex_update) == 16 && offsetof(fovpt_vertex_update, vertex) == 8, "vertex update ABI");

@@ -1,0 +1,292 @@
+"""The coded frame packet ("FVPC": levels as BC1 blocks) without a GPU: sizes and blocks spelled out by hand, properties of the
+reference (tests/packet_bc_ref.py) with no pixel or block excluded, the host decoder of both libraries against it bit for bit, the
+wire format pinned by a golden packet, untrusted bytes -- every rejection by a one-field mutation, every truncation, and the
+stand-alone sanitizer build of csrc/packet_host.cpp fed those plus seeded random mutations -- and the ABI."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import packet_bc_ref as bc
+import packet_ref as pk
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
+from packet_bc_cases import coded_mutations, masks_for
+from packet_cases import IDS, JUNK, SHAPES, junk_canvas, random_frame, synthetic_raw
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+E_INVALID = -1
+
+
+@pytest.fixture(scope="module")
+def libs():
+    """(name, library) for the host-only loader library and for libfovpt.so: both carry the decoder."""
+    lib.build()
+    L = C.CDLL(lib.LOADER_SO_PATH)
+    lib._declare_loader(L)
+    lib._declare_packet_host(L)
+    return [("libfovpt_loader.so", L), ("libfovpt.so", lib.load())]
+
+
+def host_decode(L, packet, mode, out):
+    return L.fovpt_packet_decode_host(packet, len(packet), mode, out.ctypes.data, out.shape[1], out.shape[0])
+
+
+def block_bytes(tex):
+    return bc.encode_blocks(np.array(tex, np.int64)).astype("<u4").tobytes()
+
+
+# ---- 1. sizes and blocks by hand ------------------------------------------------------------------------------------------------------
+def test_sizes_by_hand():
+    for radii, want_pm, want_all, raw in (((148, 482), 537752, 227536, 1810768), ((74, 241), 185176, 106728, 844724)):
+        pas = pk.passes((1920, 1080), (960, 540), radii, False)
+        assert pk.header((1920, 1080), pas)[2] == raw
+        assert bc.default_codecs(pas) == (1, 1, 0)
+        assert bc.header((1920, 1080), pas, (1, 1, 0))[2] == want_pm
+        assert bc.header((1920, 1080), pas, (1, 1, 1))[2] == want_all
+        assert bc.header((1920, 1080), pas, (0, 0, 0))[2] == raw
+    # 128 + 8 (120 * 68 + 121 * 121) + 4 * 298^2
+    assert 537752 == 128 + 8 * (120 * 68 + 121 * 121) + 4 * 298 * 298
+    assert bc.default_codecs(pk.passes((33, 21), (16, 10), None, True)) == (0,)          # FOV_OFF: one raw pass
+
+
+def test_blocks_spelled_out():
+    # all dead
+    assert block_bytes(np.zeros((4, 4))) == bytes.fromhex("00000000ffffffff")
+    # flat: r 0x80, g 0x40, b 0x20 -> q5 16, q6 16, q5 4 -> 0x8204 twice, every index 0; decoded 132, 65, 33
+    flat = np.full((4, 4), 0xff204080)
+    assert block_bytes(flat) == bytes.fromhex("0482048200000000")
+    assert (bc.decode_blocks(bc.encode_blocks(flat), 4, 4) == 0xff214184).all()
+    # dead texels: black, white, black, white in the first row, twelve dead: color0 0 < color1 0xffff, the dead ones index 3
+    t = np.zeros((4, 4), np.int64)
+    t[0] = [0xff000000, 0xffffffff, 0xff000000, 0xffffffff]
+    assert block_bytes(t) == bytes.fromhex("0000ffff44ffffff")
+    assert np.array_equal(bc.decode_blocks(bc.encode_blocks(t), 4, 4), t)
+    # r rises while b falls, g constant: ref = r (ties after g: g's extent is 0), s_b < 0 flips b, so the endpoints are the
+    # two colours themselves and not (hi, hi, hi) / (lo, lo, lo).  247 = e5(30), 101 = e6(25)
+    c1, c2 = 0xff000000 | 247 << 16 | 101 << 8 | 0, 0xff000000 | 0 << 16 | 101 << 8 | 247
+    t = np.array([[c1] * 4, [c1] * 4, [c2] * 4, [c2] * 4], np.int64)
+    assert block_bytes(t) == struct.pack("<HHI", 30 << 11 | 25 << 5, 25 << 5 | 30, 0x00005555)       # color0 > color1: 4 colours
+    assert np.array_equal(bc.decode_blocks(bc.encode_blocks(t), 4, 4), t)
+    # a 5 x 3 grid of one colour: two blocks, row 3 and columns 5 .. 7 dead
+    g = np.full((3, 5), 0xff214184)
+    assert block_bytes(g) == bytes.fromhex("04820482000000ff") + bytes.fromhex("04820482fcfcfcff")
+    assert np.array_equal(bc.decode_blocks(bc.encode_blocks(g), 5, 3), g)
+    assert bc.pass_bytes(5, 3, bc.BC1) == 16 and bc.pass_bytes(5, 3, bc.RAW) == 60 and bc.pass_bytes(1, 1, bc.BC1) == 8
+
+
+# ---- 2. properties of the reference -----------------------------------------------------------------------------------------------------
+def test_two_565_colours_decode_exactly_and_liveness_survives():
+    rng = np.random.default_rng(77)
+    n = 4000
+    e5 = lambda v: v << 3 | v >> 2
+    e6 = lambda v: v << 2 | v >> 4
+    col = []
+    for _ in range(2):
+        r, g, b = rng.integers(0, 32, n), rng.integers(0, 64, n), rng.integers(0, 32, n)
+        col.append(0xff000000 | e5(b) << 16 | e6(g) << 8 | e5(r))
+    which = rng.integers(0, 2, (n, 16))
+    which[: n // 8] = 0                                                   # (one colour; both orders of the pair come up by chance)
+    live = rng.random((n, 16)) < rng.choice([0.2, 0.7, 1.0, 1.0], (n, 1))
+    t = np.where(live, np.where(which == 0, col[0][:, None], col[1][:, None]), 0)
+    tex = t.reshape(n, 4, 4).transpose(1, 0, 2).reshape(4, 4 * n)          # n blocks side by side
+    got = bc.decode_blocks(bc.encode_blocks(tex), 4 * n, 4)
+    assert np.array_equal(got, tex)
+    assert live.all(1).sum() > 100 and (~live.any(1)).sum() > 0
+    # any colours: liveness texel by texel, alpha 0xff on the live ones, on grids that are no multiple of 4 too
+    for gw, gh in ((64, 64), (13, 7), (1, 1), (3, 9), (4, 5)):
+        tex = rng.integers(0, 1 << 24, (gh, gw)) | 0xff000000
+        tex = np.where(rng.random((gh, gw)) < 0.4, 0, tex)
+        got = bc.decode_blocks(bc.encode_blocks(tex), gw, gh)
+        assert np.array_equal(got == 0, tex == 0) and ((got[tex != 0] >> 24) == 0xff).all()
+        words = bc.encode_blocks(tex).astype(np.int64)
+        mixed = np.array([not blk.all() for blk in _blocks_live(tex)])
+        assert ((words[mixed, 0] & 0xffff) <= (words[mixed, 0] >> 16)).all()        # a dead texel: the 3-colour order
+
+
+def _blocks_live(tex):
+    gh, gw = tex.shape
+    pad = np.zeros((4 * ((gh + 3) // 4), 4 * ((gw + 3) // 4)), np.int64)
+    pad[:gh, :gw] = tex
+    return [pad[y:y + 4, x:x + 4] != 0 for y in range(0, pad.shape[0], 4) for x in range(0, pad.shape[1], 4)]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_expand_is_a_raw_packet_with_the_same_pixel_set(shape):
+    size, gaze, radii, uniform = shape
+    npass = len(pk.passes(size, gaze, radii, uniform))
+    for img in (synthetic_raw(size, gaze, radii, uniform)[0], random_frame(size, 21)):
+        raw = pk.encode(img, size, gaze, radii, uniform, sequence=9)
+        wrote_raw = pk.decode(raw, pk.NEAREST, junk_canvas(size)) != JUNK
+        for mask in masks_for(npass):
+            packet = bc.encode(img, size, gaze, radii, uniform, mask, sequence=9)
+            hd = bc.parse(packet)
+            assert hd is not None and hd["codecs"] == list(mask) and len(packet) == hd["bytes"] and packet[:4] == b"FVPC"
+            assert not pk.check(packet) and bc.check(packet)
+            ex = bc.expand(packet)
+            assert pk.check(ex) and len(ex) == len(raw) and ex[:4] == b"FVPK" and pk.parse(ex)["sequence"] == 9
+            if not any(mask):
+                assert ex == raw and packet[128:] == raw[128:]
+            for P, k in zip(pk.parse(raw)["passes"], mask):              # raw passes are carried as they are, liveness everywhere
+                a, b = pk._texels(raw, P), pk._texels(ex, P)
+                assert np.array_equal(a == 0, b == 0)
+                if k == bc.RAW:
+                    assert np.array_equal(a, b)
+            assert np.array_equal(pk.decode(ex, pk.NEAREST, junk_canvas(size)) != JUNK, wrote_raw), mask
+
+
+# ---- 3. the host decoder against the reference ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_host_decoder_matches_the_reference(libs, shape):
+    size, gaze, radii, uniform = shape
+    npass = len(pk.passes(size, gaze, radii, uniform))
+    raw, written = synthetic_raw(size, gaze, radii, uniform)
+    for label, img in (("raw", raw), ("random", random_frame(size, 11))):
+        for mask in masks_for(npass):
+            packet = bc.encode(img, size, gaze, radii, uniform, mask, sequence=5)
+            for mode in (pk.NEAREST, pk.SMOOTH):
+                want = bc.decode(packet, mode, junk_canvas(size))
+                assert (want[~written] == JUNK).all() and ((want[written] >> 24) == 0xff).all()
+                for name, L in libs:
+                    assert L.fovpt_packet_check(packet, len(packet)) == 0, (name, mask)
+                    got = junk_canvas(size)
+                    assert host_decode(L, packet, mode, got) == 0, (name, label, mask, mode)
+                    assert np.array_equal(got, want), (name, label, mask, mode, int((got != want).sum()))
+            if label == "raw" and npass == 3 and mask[2] == 0:           # the fovea raw: exact on its pixels
+                fovea = pk.owners(size, gaze, radii, uniform)[0] == 2
+                assert fovea.any() and np.array_equal(bc.decode(packet, pk.NEAREST, junk_canvas(size))[fovea], raw[fovea])
+    assert np.array_equal(renderer.decode_packet(packet, abi.PACKET_SMOOTH, size, out=junk_canvas(size)), bc.decode(packet, pk.SMOOTH, junk_canvas(size)))
+
+
+# ---- 4. the wire format, pinned -------------------------------------------------------------------------------------------------------
+def test_golden_coded_packet(libs):
+    packet = open(os.path.join(GOLDEN, "packet_c1_64x48.bin"), "rb").read()
+    assert len(packet) == 128 + 8 * 4 * 3 + 8 * 4 * 4 + 4 * 14 * 14 == 1136
+    size, gaze, radii, uniform = SHAPES[0]
+    assert bc.encode(random_frame(size, 2024), size, gaze, radii, uniform, sequence=0x01020304) == packet      # (default codecs: 1, 1, 0)
+    h = abi.PacketHeader.from_packet(packet)
+    assert (h.magic, h.version, h.bytes, h.sequence, h.width, h.height, h.npass) == (abi.PACKET_MAGIC_CODED, 1, 1136, 0x01020304, 64, 48, 3)
+    assert [(p.gw, p.gh, p.factor, p.fill, p.texels, p._reserved) for p in h.passes] == [(16, 12, 4, 4, 128, 1), (16, 16, 2, 2, 224, 1), (14, 14, 1, 1, 352, 0)]
+    raw = open(os.path.join(GOLDEN, "packet_v1_64x48.bin"), "rb").read()
+    assert packet[352:] == raw[1920:]                                     # the fovea, as in the raw packet
+    for mode, name in ((pk.NEAREST, "nearest"), (pk.SMOOTH, "smooth")):
+        want = np.fromfile(os.path.join(GOLDEN, "packet_c1_64x48_%s.bin" % name), "<u4").reshape(48, 64)
+        assert np.array_equal(bc.decode(packet, mode, np.zeros((48, 64), np.uint32)), want)
+        for _, L in libs:
+            got = np.zeros((48, 64), np.uint32)
+            assert host_decode(L, packet, mode, got) == 0 and np.array_equal(got, want)
+
+
+# ---- 5. untrusted input ---------------------------------------------------------------------------------------------------------------
+CASES = [(0, (1, 1, 1)), (2, (1, 1, 0)), (5, (1,)), (4, (0, 1, 0))]      # (shape, mask): a coded last pass, a raw one, one pass
+
+
+def _cases():
+    """(valid packets, [(label, bytes, check must refuse, the size of the packet it was made from)])"""
+    valid, bad = [], []
+    for n, (k, mask) in enumerate(CASES):
+        size, gaze, radii, uniform = SHAPES[k]
+        packet = bc.encode(random_frame(size, 3 + k), size, gaze, radii, uniform, mask)
+        valid.append(packet)
+        bad += [("%d %s: %s" % (n, IDS[k], label), m, not label.startswith("another"), size) for label, m in coded_mutations(packet)]
+    p0 = valid[0]
+    bad += [("0 truncated to %d" % n, p0[:n], True, SHAPES[0][0]) for n in range(0, len(p0), 4)]
+    return valid, bad
+
+
+def test_every_rejection_of_a_coded_packet(libs):
+    valid, bad = _cases()
+    labels = " ".join(label for label, *_ in bad)
+    for must in ("codec 2", "array past bytes by one block", "one block row", "array past the end", "truncated to 124", "magic", "version 2"):
+        assert must in labels, must
+    assert len(valid[0]) == 480 and len(bad) >= 4 * 35 + 120              # (every mutation of four packets, 120 truncations)
+    for name, L in libs:
+        for packet in valid:
+            assert L.fovpt_packet_check(packet, len(packet)) == 0
+        for label, m, refused, size in bad:
+            assert bc.check(m) == (not refused), label
+            assert L.fovpt_packet_check(m, len(m)) == (E_INVALID if refused else 0), (name, label)
+            out = junk_canvas(size)
+            for mode in (0, 1):
+                assert host_decode(L, m, mode, out) == E_INVALID, (name, label, mode)      # ("another width": not the output's)
+            assert (out == JUNK).all(), (name, label)
+        packet, size = valid[0], SHAPES[0][0]
+        out = junk_canvas(size)
+        for mode in (-1, 2, 1 << 20):
+            assert host_decode(L, packet, mode, out) == E_INVALID
+        assert L.fovpt_packet_decode_host(packet, len(packet), 0, None, 64, 48) == E_INVALID
+        assert L.fovpt_packet_decode_host(packet, len(packet), 0, out.ctypes.data, 48, 64) == E_INVALID
+        assert (out == JUNK).all()
+        assert L.fovpt_packet_check(packet + bytes(100), len(packet) + 100) == 0
+        # a raw packet under the coded magic is a coded packet of raw passes; a coded one under the raw magic is refused
+        raw = pk.encode(random_frame(size, 3), *SHAPES[0])
+        assert L.fovpt_packet_check(b"FVPC" + raw[4:], len(raw)) == 0 and L.fovpt_packet_check(b"FVPK" + packet[4:], len(packet)) == E_INVALID
+    with pytest.raises(lib.FovptError):
+        renderer.decode_packet(valid[0][:-4])
+
+
+def test_untrusted_coded_packets_under_sanitizers(tmp_path):
+    """csrc/packet_host.cpp in the stand-alone program of tests/cpp/packet_host_main.cpp, built with AddressSanitizer and
+    UndefinedBehaviorSanitizer: the valid coded packets, every mutation and truncation above, and 3000 seeded random mutations per
+    packet.  Every call returns FOVPT_OK or FOVPT_E_INVALID and the sanitizers stay silent."""
+    exe = str(tmp_path / "packet_host_asan")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                           os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc", "packet_host.cpp"),
+                           os.path.join(ROOT, "tests", "cpp", "packet_host_main.cpp"), "-o", exe])
+    valid, bad = _cases()
+    files = []
+    for k, packet in enumerate(valid):                                    # a file per valid packet: it and the cases made from it
+        mine = [m for label, m, _, _ in bad if label.startswith("%d " % k)]
+        path = str(tmp_path / ("cases%d.bin" % k))
+        with open(path, "wb") as f:
+            for b in [packet] + mine:
+                f.write(struct.pack("<I", len(b)) + b)
+        files.append((path, 1 + len(mine)))
+    res = subprocess.run([exe, "3000"] + [p for p, _ in files], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
+    assert "runtime error" not in res.stderr and "Sanitizer" not in res.stderr, res.stderr[-3000:]
+    lines = res.stdout.splitlines()
+    assert len(lines) == len(files), res.stdout
+    for (path, n), line in zip(files, lines):
+        f = dict(kv.split("=") for kv in line.split()[1:])
+        assert int(f["packets"]) == n and int(f["bad"]) == 0 and int(f["fuzzed"]) == 3000, line
+        assert 1 <= int(f["valid"]) <= 3                                   # (the packet, and "another width / height")
+        assert 0 < int(f["fuzzed_valid"]) < 3000, line                     # (the fuzz reaches both outcomes)
+
+
+# ---- 6. the ABI -----------------------------------------------------------------------------------------------------------------------
+def test_struct_mirror_defines_prototypes_and_exports(libs, tmp_path):
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
+           'printf("%zu %zu %zu\\n", sizeof(fovpt_packet_config), offsetof(fovpt_packet_config, codec), offsetof(fovpt_packet_config, _reserved));'
+           'printf("%u %u %u %u %u %d\\n", FOVPT_PACKET_MAGIC_CODED, FOVPT_PACKET_RAW, FOVPT_PACKET_BC1, FOVPT_PACKET_BY_FILL, FOVPT_PACKET_MAGIC, FOVPT_PACKET_VERSION);'
+           'return 0;}\n')
+    exe = str(tmp_path / "packet_config_layout")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    lines = subprocess.check_output([exe]).decode().splitlines()
+    assert [int(x) for x in lines[0].split()] == [C.sizeof(abi.PacketConfig), abi.PacketConfig.codec.offset, abi.PacketConfig._reserved.offset] == [16, 0, 12]
+    assert [int(x) for x in lines[1].split()] == [abi.PACKET_MAGIC_CODED, abi.PACKET_RAW, abi.PACKET_BC1, abi.PACKET_BY_FILL, abi.PACKET_MAGIC, abi.PACKET_VERSION]
+    assert (bc.MAGIC_CODED, bc.RAW, bc.BC1, bc.BY_FILL) == (abi.PACKET_MAGIC_CODED, abi.PACKET_RAW, abi.PACKET_BC1, abi.PACKET_BY_FILL)
+    assert struct.pack("<I", abi.PACKET_MAGIC_CODED) == b"FVPC"
+    text = open(os.path.join(ROOT, "include", "fovpt.h")).read()
+    full = dict(libs)["libfovpt.so"]
+    names = ["fovpt_packet_describe_coded", "fovpt_packet_encode_coded", "fovpt_packet_submit_coded"]
+    for n in names:
+        assert ("int %s(" % n) in text and n in lib.EXPORTS and hasattr(full, n), n
+    assert "void fovpt_packet_defaults(" in text and "fovpt_packet_defaults" in lib.EXPORTS
+    cfg = abi.PacketConfig((7, 7, 7), 7)
+    full.fovpt_packet_defaults(C.byref(cfg))
+    assert list(cfg.codec) == [abi.PACKET_BY_FILL] * 3 and cfg._reserved == 0
+    full.fovpt_packet_defaults(None)
+    loader = C.CDLL(lib.LOADER_SO_PATH)
+    for n in lib.PACKET_HOST_EXPORTS:
+        assert hasattr(loader, n), n
+    for n in names:
+        assert not hasattr(loader, n), n                                  # (the context's entry points need the device)
+    assert "submitPacket(uint32_t sequence, const fovpt_packet_config& codec" in open(os.path.join(ROOT, "include", "SimplePathtracer.h")).read()
+    subprocess.check_call(["g++", "-std=c++14", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "packet_bc_shim_check.cpp")])
+    # the context's entry points without a context
+    assert full.fovpt_packet_describe_coded(None, None, None, 0, None) == E_INVALID and full.fovpt_packet_encode_coded(None, None, None, None, 0, None) == E_INVALID
+    assert full.fovpt_packet_submit_coded(None, None, None, None, 0, None) == E_INVALID

@@ -10,7 +10,11 @@ and by HIP events on the library's stream around --calls calls back to back:
 Prints one JSON line: the median over the repetitions and the spread (min, max) of each, PACKET - RENDER beside RENDER's spread,
 the bytes that cross to the host per frame, and the RMSE (8-bit codes, r g b) of decode(encode(x)) against x per foveation level
 for x = fovpt_post's rgba8 output.  Kernel statistics are a separate run:
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/packet_perf.py --frames 20 --calls 20 --reps 1"""
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/packet_perf.py --frames 20 --calls 20 --reps 1
+--coded measures coded packets ("FVPC") instead: the legs RENDER, PACKET, and render +
+fovpt_packet_submit_coded with P and M as BC1 (CODED_110) and with all three levels as BC1 (CODED_111); k_packet_encode_coded and
+the CODED decoders beside the raw kernels; the bytes per frame; and the RMSE per level of the decoded coded packet against
+fovpt_post's output and against the decoded raw packet."""
 import argparse
 import json
 import os
@@ -37,8 +41,7 @@ def level_map(packet, size):
     return renderer.decode_packet(bytes(b), abi.PACKET_NEAREST, size) & 0xff
 
 
-def main(frames, warmup, calls, reps):
-    size = (1920, 1080)
+def scene(size):
     cfg = abi.Config.reference_default()
     cfg.r_inner, cfg.r_outer = 148, 482
     cfg.spp_periphery, cfg.spp_middle, cfg.spp_fovea = 1, 2, 8
@@ -52,6 +55,124 @@ def main(frames, warmup, calls, reps):
     r.config = cfg
     r.launchParams.frame.c.x, r.launchParams.frame.c.y = size[0] // 2, size[1] // 2
     r.render()
+    return r
+
+
+def timers(r, frames, warmup, calls):
+    """per_frame(fn): ms per frame of fn(n) by the host clock; per_call(fn): ms per call by HIP events on the library's stream."""
+    def per_frame(fn):
+        fn(warmup)
+        r.synchronize()
+        t0 = time.perf_counter()
+        fn(frames)
+        r.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / frames
+
+    st = torch.cuda.ExternalStream(r.stream)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def per_call(fn):
+        for _ in range(max(1, warmup // 4)):
+            fn()
+        r.synchronize()
+        a.record(st)
+        for _ in range(calls):
+            fn()
+        b.record(st)
+        b.synchronize()
+        return a.elapsed_time(b) / calls
+
+    return per_frame, per_call
+
+
+def rgb(v):
+    return np.stack([(v >> (8 * k)) & 0xff for k in range(3)], axis=-1).astype(np.float64)
+
+
+def main_coded(frames, warmup, calls, reps):
+    size = (1920, 1080)
+    r = scene(size)
+    per_frame, per_call = timers(r, frames, warmup, calls)
+    codecs = {"PACKET": None, "CODED_110": (1, 1, 0), "CODED_111": (1, 1, 1)}
+    headers = {k: r.describePacket(0, c) for k, c in codecs.items()}
+
+    def leg_packet(codec):
+        def run(n):
+            slots = []
+            for k in range(n):
+                r.render_async()
+                slots.append(r.submitPacket(k, codec=codec))
+                if k >= 2:
+                    r.waitPacket(slots[k - 2])
+            for s in slots[-2:]:
+                r.waitPacket(s)
+        return run
+
+    def leg_render(n):
+        for _ in range(n):
+            r.render_async()
+
+    legs = dict(RENDER=leg_render)
+    legs.update({k: leg_packet(c) for k, c in codecs.items()})
+    dev = {k: torch.empty(h.bytes, dtype=torch.uint8, device="cuda") for k, h in headers.items()}
+    out = torch.zeros((size[1], size[0]), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    kernels = {}
+    for k, c in codecs.items():
+        kernels["ENCODE_" + k] = lambda k=k, c=c: r.encodePacket(dev[k].data_ptr(), 0, None, c)
+    for k in codecs:                                              # (every buffer holds its packet by the time a decoder runs)
+        for name, mode in (("NEAREST", abi.PACKET_NEAREST), ("SMOOTH", abi.PACKET_SMOOTH)):
+            kernels["%s_%s" % (name, k)] = lambda k=k, mode=mode: r.decodePacket(headers[k], dev[k].data_ptr(), out.data_ptr(), mode)
+    ms = {k: [] for k in list(legs) + list(kernels)}
+    for _ in range(reps):                                         # alternately
+        for k, fn in legs.items():
+            ms[k].append(per_frame(fn))
+        for k, fn in kernels.items():
+            ms[k].append(per_call(fn))
+    res = dict(config="C3", coded=True, size=list(size), frames_in_flight=2, frames=frames, calls=calls, reps=reps, device=torch.cuda.get_device_name(0))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    for k, v in ms.items():
+        res["ms_" + k] = round(med[k], 4)
+        res["spread_" + k] = [round(min(v), 4), round(max(v), 4)]
+    for k in codecs:
+        res[k + "_minus_RENDER"] = round(med[k] - med["RENDER"], 4)
+        res["bytes_" + k] = int(headers[k].bytes)
+    res["bytes_frame"] = size[0] * size[1] * 4
+
+    # quality: the decoded coded packet of x = fovpt_post's rgba8 output against x and against the decoded raw packet, per level
+    r.post()
+    x = r.downloadPostPixels()
+    decoded, rmse = {}, {}
+    level = None
+    for k, c in codecs.items():
+        r.encodePacket(dev[k].data_ptr(), 0, r.post_buffers()[1], c)
+        r.synchronize()
+        packet = dev[k].cpu().numpy().tobytes()
+        if c is None:
+            level = level_map(packet, size)
+        for name, mode in (("NEAREST", abi.PACKET_NEAREST), ("SMOOTH", abi.PACKET_SMOOTH)):
+            out.zero_()
+            torch.cuda.synchronize()
+            r.decodePacket(headers[k], dev[k].data_ptr(), out.data_ptr(), mode)
+            r.synchronize()
+            y = out.cpu().numpy().view(np.uint32).copy()
+            assert np.array_equal(y, renderer.decode_packet(packet, mode, size)), "device and host decoders differ"
+            assert np.array_equal(y != 0, level > 0), "the coded packet writes another pixel set"
+            decoded[k, name] = y
+            for against, z in (("post", x), ("raw_packet", decoded["PACKET", name])):
+                d2 = ((rgb(y) - rgb(z)) ** 2).mean(axis=-1)
+                e = {("fill%d" % f): round(float(np.sqrt(d2[level == f].mean())), 3) for f in (1, 2, 4) if (level == f).any()}
+                e["frame"] = round(float(np.sqrt(d2[level > 0].mean())), 3)
+                rmse["%s_%s_vs_%s" % (k, name, against)] = e
+    res["rmse"] = rmse
+    res["pixels_per_level"] = {("fill%d" % f): int((level == f).sum()) for f in (0, 1, 2, 4)}
+    print(json.dumps(res), flush=True)
+    r.close()
+
+
+def main(frames, warmup, calls, reps):
+    size = (1920, 1080)
+    r = scene(size)
     header = r.describePacket()
 
     def leg_download(n):
@@ -75,14 +196,7 @@ def main(frames, warmup, calls, reps):
 
     legs = dict(DOWNLOAD=leg_download, PACKET=leg_packet, RENDER=leg_render)
 
-    def per_frame(fn):
-        fn(warmup)
-        r.synchronize()
-        t0 = time.perf_counter()
-        fn(frames)
-        r.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / frames
-
+    per_frame, per_call = timers(r, frames, warmup, calls)
     # (d) the kernels alone
     dev = torch.empty(header.bytes, dtype=torch.uint8, device="cuda")
     out = torch.zeros((size[1], size[0]), dtype=torch.int32, device="cuda")
@@ -90,20 +204,6 @@ def main(frames, warmup, calls, reps):
     kernels = dict(ENCODE=lambda: r.encodePacket(dev.data_ptr()),
                    NEAREST=lambda: r.decodePacket(header, dev.data_ptr(), out.data_ptr(), abi.PACKET_NEAREST),
                    SMOOTH=lambda: r.decodePacket(header, dev.data_ptr(), out.data_ptr(), abi.PACKET_SMOOTH))
-    st = torch.cuda.ExternalStream(r.stream)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def per_call(fn):
-        for _ in range(max(1, warmup // 4)):
-            fn()
-        r.synchronize()
-        a.record(st)
-        for _ in range(calls):
-            fn()
-        b.record(st)
-        b.synchronize()
-        return a.elapsed_time(b) / calls
-
     ms = {k: [] for k in list(legs) + list(kernels)}
     for _ in range(reps):                                     # alternately
         for k, fn in legs.items():
@@ -128,7 +228,6 @@ def main(frames, warmup, calls, reps):
     r.synchronize()
     packet = dev.cpu().numpy().tobytes()
     level = level_map(packet, size)
-    rgb = lambda v: np.stack([(v >> (8 * k)) & 0xff for k in range(3)], axis=-1).astype(np.float64)
     rmse = {}
     for name, mode in (("NEAREST", abi.PACKET_NEAREST), ("SMOOTH", abi.PACKET_SMOOTH)):
         out.zero_()
@@ -152,5 +251,6 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--coded", action="store_true", help="coded packets (BC1 levels) beside raw ones")
     args = ap.parse_args()
-    main(args.frames, args.warmup, args.calls, args.reps)
+    (main_coded if args.coded else main)(args.frames, args.warmup, args.calls, args.reps)
