@@ -560,7 +560,9 @@ int fovpt_hierarchy_cost(fovpt_ctx* ctx, int flags, fovpt_hierarchy_cost_info* o
  *              per triangle into a buffer the build owns), starts one background build over it and returns; it never waits for the
  *              device.  With no entries it is a background rebuild alone (nothing moves, no refit, nothing counted; the device
  *              copies of the indices and positions are made if the scene has not been updated yet).  In state BUILDING or READY no
- *              second build starts: `requested` counts the request, `started` does not.  One build per context is in flight.
+ *              second build starts: `requested` counts the request, `started` does not.  The state is the one the call finds
+ *              when it comes in: a flagged call that finds READY and adopts (below) leaves IDLE behind and starts nothing.  One
+ *              build per context is in flight.
  *              (Its value is 16: the bits 4 and 8 are refused as unknown, as they always were.)
  *   the build  fovpt_set_scene's (FOVPT_BVH, FOVPT_SPLIT, FOVPT_REINSERT, FOVPT_BVH_ORDER, and the second build without
  *              reinsertion when the first is too deep), on a host thread that owns a stream of the lowest priority the device

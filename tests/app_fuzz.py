@@ -9,7 +9,14 @@ eight residues of the seed every ordered pair of kinds) and a second such frame,
 interval; for seeds from 8 on the three kinds are drawn.  The other five operations are units (an operation, or a few that only mean
 something side by side) drawn from the seed and put in a drawn order, under two caps: at most two refused calls, at least
 three frame groups with a post chain.  The eight default seeds each carry some forced units (FORCED), so that together they
-hold everything the CPU test lists whatever else they draw; their order is drawn too."""
+hold everything the CPU test lists whatever else they draw; their order is drawn too.
+
+script(seed, late=True) is a second family over the seeds LATE_SEEDS (FOVPT_FUZZLATE_FROM / FOVPT_FUZZLATE_TO widen it), for what
+the library has learnt since: the same scene, config, skins and morphs as the old script of that seed, a rig over them (make_rig),
+and ten operations out of the old units and the new ones at the end of this file -- updates of kind "animated", "async" rebuilds
+on all five kinds and with no entries, rebuild_state with its four flag values, set_rig, focus_reset, four more refused calls, and
+a chain post -> focus -> expose -> packet (raw or coded) -> warp | warp_motion | lens.  script(seed) itself returns what it
+always returned: tests/test_app_fuzz_cpu.py pins a digest of the scripts of seeds 0 .. 31."""
 import os
 
 import numpy as np
@@ -383,5 +390,347 @@ class _Draw:
         return self.s
 
 
-def script(seed):
-    return _Draw(int(seed)).script()
+# ---- the late family: rigs, background rebuilds, focus, warp, warp_motion, lens, coded packets -------------------------------
+# A late script has the shape of an old one and one entry more, the rig registered after the skins and morphs.  Its operations
+# are the old ones and: update of kind "animated" (poses = dict(clip, time)); rebuild "async" beside False and True on any update;
+# rebuild_state(wait, adopt); set_rig; focus_reset; the refusals no_rig, clip_range, async_with_rebuild, warp_motion_stale; and a
+# chain post -> focus -> expose -> packet (raw or coded, of the unwarped frame) -> warp | warp_motion | lens.
+LATE_DEFAULT_SEEDS = range(0, 8)
+LATE_SEEDS = range(int(os.environ.get("FOVPT_FUZZLATE_FROM", LATE_DEFAULT_SEEDS.start)), int(os.environ.get("FOVPT_FUZZLATE_TO", LATE_DEFAULT_SEEDS.stop)))
+LATE_KINDS = KINDS + ("animated",)
+# the three kinds of the head's interval: the first four rows hold the eight ordered pairs of "animated" (4) with another kind
+LATE_TRIPLES = [(0, 4, 1), (2, 4, 3), (1, 4, 0), (3, 4, 2), (4, 2, 1), (3, 1, 4), (0, 4, 3), (1, 2, 4)]
+# the flags of the head's three updates: background builds left in flight, and (4) one ended by FOVPT_UPDATE_REBUILD
+LATE_HEAD_FLAG = [(False, False, "async"), (False, False, "async"), (False, False, "async"), (False, False, "async"),
+                  (False, "async", True), (False, False, "async"), (False, False, False), (False, False, True)]
+ADVANCES = (0.0, 0.5, 1.0, 2.0)
+# clip times against the keys 0, 0.5, 1, 2: before the first, between (the lerp, the flipped slerp and the slerp segment of a
+# rotation channel), exactly a key, behind the last
+CLIP_TIMES = (-0.5, 0.25, 0.5, 0.75, 1.5, 3.0)
+ROT_KEYS = (0.0, 0.5, 1.0, 2.0)
+RAW, BC1, BY_FILL = 0, 1, 0xffffffff
+FIXED, AUTO = 0, 1
+T_, M_ = po.TEMPORAL, po.MOTION
+
+L_NO_RIG = lambda drop: ((drop,), ("x", "no_rig"), ("set_rig",), ("u", "animated", "host", False))
+# the late default seeds' units; a chain given as a dict is forced stage by stage (late_chain)
+LATE_FORCED = [
+    # 0: adoption by a later update after WAIT, inside a tracked interval; focus AUTO across a resize
+    [(("u", "empty", "host", "async"), ("rebuild_state", True, False), ("u", "vertices", "host", False)),
+     (("resize", "other"), ("f", 1, (), False, dict(step=True, focus=(AUTO, "temporal"), last=("warp_motion", "temporal", 2.0), codec=(BC1, RAW, BY_FILL))))],
+    # 1: set_skins drops the rig; a stale snapshot adopted by rebuild_state (the script widens the BUILDING window)
+    [L_NO_RIG("set_skins"),
+     (("f", 3, ("u:async", "u"), False, dict(step=True, adopt_first=True, focus=(FIXED, "own"), last=("lens", 0, True))),)],
+    # 2: a request while a build is in flight; an adopting update between two frames in flight
+    [(("u", "skinned", "host", "async"), ("u", "empty", "host", "async"), ("rebuild_state", True, False), ("f", 2, ("u",), False, dict(step=True, last=("lens", 1, False)))),],
+    # 3: set_morphs drops the rig
+    [L_NO_RIG("set_morphs"), (("f", 1, (), False, dict(step=True, focus=(AUTO, "own"), last=("warp",), codec=(BY_FILL, BY_FILL, BY_FILL))),)],
+    # 4: set_scene drops the rig and ends a build; the step after it did not know the motion
+    [(("u", "vertices", "host", "async"),) + L_NO_RIG("set_scene")[:3] + (("f", 1, (), "animated", dict(step=True, last=("warp_motion", "own", 1.0), codec=(BC1, BC1, BC1))),)],
+    # 5: warp_motion refused after an update; rebuild_state polled and with ADOPT alone
+    [(("f", 1, (), False, dict(step=True, last=("warp_motion", "own", 0.0))), ("u", "transforms", "host", False), ("x", "warp_motion_stale")),
+     (("rebuild_state", False, False),), (("rebuild_state", False, True),)],
+    # 6: both rebuild flags; a clip out of range; focus_reset
+    [(("x", "async_with_rebuild"),), (("focus_reset",), ("f", 1, (), False, dict(focus=(AUTO, "own"), last=("lens", 2, True)))),
+     (("x", "clip_range"),), (("f", 1, (), False, dict(last=("lens", 0, False), codec=(RAW, BC1, RAW))),)],
+    # 7: rebuild_state(WAIT | ADOPT) as an operation of its own
+    [(("u", "animated", "host", "async"), ("rebuild_state", True, True)), (("f", 1, (), False, dict(last=("lens", 1, True))),)],
+]
+# the chain of the head's second frame: the stale G-buffer (seeds whose head leaves a build in flight), every advance
+LATE_HEAD_CHAIN = [
+    dict(step=True, focus=(AUTO, "temporal"), last=("warp_motion", "temporal", 1.0, "adopt"), codec=(BY_FILL, BC1, RAW)),
+    dict(step=True, last=("warp_motion", "own", 0.5)),
+    dict(step=True, focus=(AUTO, "temporal"), last=("warp_motion", "temporal", 2.0)),
+    dict(step=True, focus=(FIXED, "temporal"), last=("warp_motion", "temporal", 1.0, "adopt"), codec=(BC1, BC1, RAW)),
+    dict(step=True, last=("warp_motion", "own", 2.0)),
+    dict(step=True, last=("lens", 2, False)),
+    dict(step=True, last=("warp_motion", "own", 0.0)),
+    dict(step=True, focus=(AUTO, "own"), last=("warp_motion", "temporal", 1.0)),
+]
+LATE_DELAY_MS = {1: 150}                                  # FOVPT_ASYNC_BUILD_DELAY_MS of a script: widens a window, decides nothing
+
+
+class _LateDraw(_Draw):
+    def __init__(self, seed):
+        super().__init__(seed)
+        self.rng = np.random.default_rng(53000 + seed)   # (the scene, config, skins and morphs are the old family's of this seed)
+        if seed in LATE_DEFAULT_SEEDS and self.s["config"]["chains_per_frame"] == 0:
+            self.s["size"] = self.size = SIZES[seed % len(SIZES)]     # every size of the pool, (3, 50) among them
+        self.s["late"] = True
+        self.s["delay_ms"] = LATE_DELAY_MS.get(seed, 0) if seed in LATE_DEFAULT_SEEDS else 0
+        self.rig = self.make_rig()
+        self.s["rig"] = self.rig
+        self.stepped = False                              # a temporal step at this size, on this scene, since the last reset
+        self.posed = 0                                    # animated updates so far
+
+    # ---- the rig
+    def make_rig(self):
+        """A rig over the registered skins and morphs: the mesh of the interval's updates morphed and skinned, one mesh by morph
+        weights alone, one skinned, one or two rigid; a root, a pivot per mesh at its centre and chains of joints below the pivots
+        (four levels and more); clip 0 with STEP and LINEAR channels of all four paths, rotation keys 2 degrees apart (the lerp),
+        on opposite hemispheres (the flip) and 20 degrees apart (the slerp); clip 1 carries the root alone."""
+        import rig_ref as rg
+        rng = self.rng
+        both = [k for k in sorted(self.skins) if k in self.morphs]
+        bind = [(self.x, "morph+skin")] if self.x in both else []
+        rest = [k for k in both if k != self.x]
+        bind += [(k, "morph") for k in rest[:1]] + [(k, "morph+skin") for k in rest[1:2]]
+        bind += [(k, "skin") for k in [k for k in sorted(self.skins) if k not in self.morphs][:1]]
+        bind += [(k, "morph") for k in [k for k in sorted(self.morphs) if k not in self.skins][:1]]
+        taken = {k for k, _ in bind}
+        bare = [k for k in range(self.nmesh) if k not in taken and k not in self.morphs and k not in self.skins]
+        bind += [(k, "rigid") for k in ([self.x] if self.x not in taken and self.x not in self.morphs else []) + bare[:1 if taken else 2]]
+        parent, trans = [-1], [np.zeros(3)]
+        bindings, clip, count = [], [], [0, 0, 0, 0]
+
+        def node(p, t):
+            parent.append(p)
+            trans.append(np.asarray(t, np.float64))
+            return len(parent) - 1
+
+        def chan(target, path, times, values):
+            count[path] += 1
+            clip.append(rg.channel(target, path, times, values, rg.STEP if count[path] % 3 == 2 else rg.LINEAR))
+
+        def turns(target):
+            axis, axis2 = rng.standard_normal(3), rng.standard_normal(3)
+            a = rng.uniform(-5, 5)
+            q = [rg.quat(axis, a), rg.quat(axis, a + 2.0), -rg.quat(axis2, a + 20.0), -rg.quat(axis2, a + 40.0)]
+            chan(target, rg.ROTATION, ROT_KEYS, q)
+
+        joints = {}
+        for k, how in bind:
+            c = self.centre(k)
+            p = node(0, c)
+            chan(p, rg.TRANSLATION, [0.0, 1.0, 2.0], c[None, :] + rng.uniform(-8, 8, (3, 3)))
+            if how == "rigid":
+                n = node(p, -c)
+                turns(p)
+                chan(n, rg.SCALE, [0.5, 1.5], rng.uniform(0.9, 1.1, (2, 3)))
+                bindings.append(dict(mesh=k, node=n))
+            elif how == "morph":
+                bindings.append(dict(mesh=k))
+            else:
+                js = []
+                for j in range(self.skins[k][2]):
+                    js.append(node(js[-1] if j % 3 else p, rng.uniform(-4, 4, 3)))
+                    if j < 3:
+                        turns(js[-1])
+                chan(js[0], rg.SCALE, [0.5, 1.5], rng.uniform(0.9, 1.1, (2, 3)))
+                joints[k] = js
+                bindings.append(dict(mesh=k, joint_nodes=np.array(js, np.uint16)))
+            if k in self.morphs:
+                chan(k, rg.WEIGHTS, ROT_KEYS, rng.uniform(-0.5, 1.0, (4, len(self.morphs[k]))))
+        rig = rg.empty_rig(len(parent))
+        rig["parent"] = np.array(parent, np.int32)
+        rig["translation"] = np.array(trans).astype(F)
+        for b in bindings:
+            if "joint_nodes" in b:
+                b["inverse_bind"] = rg.inverse_bind_of(rig, b["joint_nodes"])
+        rig["bindings"] = bindings
+        rig["clips"] = [clip, [rg.channel(0, rg.TRANSLATION, [0.0, 1.0], [[0, 0, 0], rng.uniform(-6, 6, 3)])]]
+        return rig
+
+    def set_rig(self):
+        self.rig = self.make_rig()
+        return dict(op="set_rig", rig=self.rig)
+
+    def set_skins(self):
+        self.rig = None
+        return super().set_skins()
+
+    def set_morphs(self):
+        self.rig = None
+        return super().set_morphs()
+
+    def set_scene(self):
+        self.rig, self.stepped = None, False
+        return super().set_scene()
+
+    def resize(self, how=None):
+        self.stepped = False
+        return super().resize(how)
+
+    def temporal_reset(self):
+        self.stepped = False
+        return super().temporal_reset()
+
+    def focus_reset(self):
+        return dict(op="focus_reset")
+
+    def rebuild_state(self, wait, adopt):
+        return dict(op="rebuild_state", wait=bool(wait), adopt=bool(adopt))
+
+    # ---- updates
+    def update(self, kind, form="host", rebuild=False, many=False, meshes=None):
+        rng = self.rng
+        flag = rebuild if rebuild == "async" else bool(rebuild)
+        if kind == "animated" and self.rig is None:
+            kind = "vertices"                             # (the rig went: something that still moves)
+        if kind == "animated":
+            clip = int(rng.random() < 0.2)
+            t = int(rng.integers(0, len(CLIP_TIMES)))
+            if self.seed in LATE_DEFAULT_SEEDS:           # the default seeds take the times in turn: every case of the sample rule
+                t, self.posed = (self.seed + self.posed) % len(CLIP_TIMES), self.posed + 1
+                clip = clip if self.posed > 1 else 0
+            return dict(op="update", kind="animated", poses=dict(clip=clip, time=float(CLIP_TIMES[t])),
+                        rebuild=flag, device=False)
+        u = super().update(kind, form, False, many, meshes)
+        u["rebuild"] = flag
+        return u
+
+    def refused(self, which):
+        rng = self.rng
+        T = float(rng.uniform(0.0, 2.0))
+        if which == "no_rig":
+            assert self.rig is None
+            return dict(op="refused", which=which, clip=0, time=T, code=E_INVALID)
+        if which == "clip_range":
+            return dict(op="refused", which=which, clip=len(self.rig["clips"]) if rng.random() < 0.5 else -1, time=T, code=E_INVALID)
+        if which == "async_with_rebuild":
+            return dict(op="refused", which=which, kind="animated" if self.rig is not None and rng.random() < 0.5 else "vertices", clip=0, time=T, code=E_INVALID)
+        if which == "warp_motion_stale":
+            return dict(op="refused", which=which, to=self.newer_camera(), code=E_NO_FRAME)
+        return super().refused(which)
+
+    # ---- the chain
+    def newer_camera(self):
+        """(how, eye, lookat) of a camera a little later: a slide, a turn or a dolly of the script's."""
+        rng = self.rng
+        eye, look = np.array(self.cam["eye"], np.float64), np.array(self.cam["lookat"], np.float64)
+        d = np.linalg.norm(look - eye)
+        how = ("slide", "turn", "dolly")[int(rng.integers(0, 3))]
+        off = rng.uniform(-1, 1, 3) * 0.04 * d
+        if how == "slide":
+            eye, look = eye + off, look + off
+        elif how == "turn":
+            look = look + 3 * off
+        else:
+            eye = eye + (look - eye) * rng.uniform(-0.15, 0.15)
+        return (how, tuple(float(x) for x in eye), tuple(float(x) for x in look))
+
+    def focus_config(self, mode, gbuffer):
+        rng = self.rng
+        d = float(np.linalg.norm(np.array(self.cam["lookat"], np.float64) - np.array(self.cam["eye"], np.float64)))
+        return dict(mode=int(mode), gbuffer=gbuffer, meter_radius=int(rng.integers(8, 41)), rank_permille=int(rng.integers(0, 1001)),
+                    max_radius=int(rng.integers(1, 6)), strength=float(F(d * rng.uniform(4, 30))), focus_distance=float(F(d * rng.uniform(0.6, 1.4))),
+                    focus_default=float(F(d)), adapt_nearer=float(F(rng.uniform(0.1, 1.0))), adapt_farther=float(F(rng.uniform(0.1, 1.0))))
+
+    def late_chain(self, want):
+        """dict(post, expose, packet, codec, focus, last) -- the stages in the order they run; want forces the entries it names:
+        step (a temporal step with motion), focus (mode, gbuffer), last (stage, ...), codec (a triple; "raw"; None: no packet)."""
+        rng = self.rng
+        want = dict(want or {})
+        draw_last = "last" not in want
+        if draw_last:
+            want["last"] = ((None,), ("warp",), ("warp_motion", "own" if rng.random() < 0.5 else "temporal", ADVANCES[int(rng.integers(0, 4))]),
+                            ("lens", int(rng.integers(0, 3)), bool(rng.random() < 0.5)))[int(rng.integers(0, 4))]
+        if "focus" not in want:
+            want["focus"] = (int(rng.integers(0, 2)), "own" if rng.random() < 0.5 else "temporal") if rng.random() < 0.4 else None
+        last, focus = want["last"], want["focus"]
+        step = bool(want.get("step") or last[0] == "warp_motion" or (focus and focus[1] == "temporal"))
+        masks = [s for s in po.VALID_STAGES if not step or (s & T_ and s & M_)]
+        post = masks[int(rng.integers(0, len(masks)))] if step or rng.random() < 0.8 else None
+        c = dict(post=post, expose=self.expose_config() if rng.random() < 0.5 else None, packet=False, codec=None, focus=None, last=None)
+        if "codec" not in want:
+            want["codec"] = (None, "raw", tuple(int(x) for x in rng.choice([RAW, BC1, BY_FILL], 3)))[int(rng.integers(0, 3))]
+        if want["codec"] is not None:
+            c["packet"] = True
+            c["codec"] = None if want["codec"] == "raw" else tuple(int(k) for k in want["codec"])
+        if focus:
+            c["focus"] = self.focus_config(*focus)
+        if last[0] in ("warp", "warp_motion"):
+            c["last"] = dict(stage=last[0], to=self.newer_camera(), images=int(rng.integers(1, 4)), fill_radius=int(rng.integers(0, 4)))
+            if last[0] == "warp_motion":
+                c["last"].update(gbuffer=last[1], advance=float(last[2]), adopt=len(last) > 3)
+        elif last[0] == "lens":
+            c["last"] = dict(stage="lens", filter=int(last[1]), to=self.newer_camera() if last[2] else None,
+                             chroma=tuple(float(F(x)) for x in (rng.uniform(0.95, 1.0), 1.0, rng.uniform(1.0, 1.05))))
+        if post is not None and post & T_:
+            self.stepped = True
+        return c
+
+    def frame(self, n=1, between=(), pre_chain=False, want=None):
+        flags = [b[2:] if isinstance(b, str) and b.startswith("u:") else None for b in between]
+        # (the old frame with the cheapest chain there is, "packet": its views, between and moved_on are kept, the chain it drew
+        # is thrown away on purpose and late_chain() draws the one that runs)
+        op = super().frame(n, tuple("u" if f else b for f, b in zip(flags, between)), False, "packet")
+        for k, f in enumerate(flags):
+            if f:
+                op["between"][k]["rebuild"] = f
+        if pre_chain:
+            kind = pre_chain if isinstance(pre_chain, str) else LATE_KINDS[int(self.rng.integers(0, 5))]
+            op["pre_chain"] = self.update(kind, "host")
+            if op["moved_on"] is None:
+                w, h = self.size
+                op["moved_on"] = dict(gaze=(int(self.rng.integers(-10, w + 11)), int(self.rng.integers(-10, h + 11))), subframe_index=int(self.rng.integers(4, 9)))
+        adopt_first = isinstance(want, dict) and want.pop("adopt_first", False)
+        op["chain"] = self.late_chain(want if isinstance(want, dict) else dict(step=True) if want in ("step", "step+packet") else None)
+        op["adopt_first"] = bool(adopt_first)             # rebuild_state(WAIT | ADOPT) between the frames and their chain
+        return op
+
+    def draw_unit(self, room):
+        rng = self.rng
+        while True:
+            u = rng.random()
+            if u < 0.45:
+                unit = super().draw_unit(room)
+            elif u < 0.65:
+                flag = (False, True, "async", "async")[int(rng.integers(0, 4))]
+                kind = ("animated", "animated", "vertices", "transforms", "skinned", "morphed", "empty")[int(rng.integers(0, 7))]
+                unit = (("u", kind, "host", flag),)
+            elif u < 0.80:
+                unit = (("rebuild_state", bool(rng.random() < 0.5), bool(rng.random() < 0.5)),)
+            elif u < 0.85:
+                unit = (("u", "animated", "host", "async"), ("rebuild_state", True, False), ("u", "animated", "host", False))
+            elif u < 0.90:
+                unit = (("focus_reset",),)
+            elif u < 0.95:
+                unit = ((("x", "clip_range"),), (("x", "async_with_rebuild"),), L_NO_RIG("set_skins"), L_NO_RIG("set_morphs"))[int(rng.integers(0, 4))]
+            else:
+                unit = (("f", 1, (), False, dict(step=True)), ("u", "vertices", "host", False), ("x", "warp_motion_stale"))
+            if len(unit) <= room:
+                return unit
+
+    def realize(self, t):
+        if t[0] == "x" and t[1] in ("no_rig", "clip_range", "warp_motion_stale") and self.refusals < MAX_REFUSED:
+            if (t[1] == "no_rig") != (self.rig is None) or (t[1] == "warp_motion_stale" and not self.stepped):
+                return self.temporal_reset()                 # (nothing to refuse here: something harmless in its place)
+        if t[0] == "set_rig" and self.rig is not None:
+            return self.focus_reset()
+        return super().realize(t)
+
+    def script(self):
+        rng = self.rng
+        default = self.seed in LATE_DEFAULT_SEEDS
+        a, b, c = (LATE_KINDS[k] for k in (LATE_TRIPLES[self.seed] if default else rng.permutation(5)[:3]))
+        flags = LATE_HEAD_FLAG[self.seed] if default else (False, False, (False, True, "async")[int(rng.integers(0, 3))])
+
+        def burst(kind, flag):
+            if kind == "animated":
+                return self.update("animated", "host", flag)
+            form = "device" if kind != "transforms" and rng.random() < 0.4 else "host"
+            k = "morphed+" if kind == "morphed" and rng.random() < 0.5 else kind
+            others = [g for g in self.meshes_for(k) if g != self.x][:2]
+            return self.update(k, form, rebuild=flag, meshes=sorted([self.x] + others))
+        self.refusals, self.resized = 0, False
+        ops = [self.frame(want=dict(step=True)), burst(a, flags[0]), burst(b, flags[1]), burst(c, flags[2]),
+               self.frame(want=dict(LATE_HEAD_CHAIN[self.seed]) if default else dict(step=True))]
+        units = [tuple(tuple(dict(x) if isinstance(x, dict) else x for x in t) for t in u) for u in LATE_FORCED[self.seed]] if default else []
+        room = TAIL_OPS - sum(len(u) for u in units)
+        assert room >= 0
+        if not any(t[0] == "f" for u in units for t in u):
+            units.append((("f", 1, (), bool(rng.random() < 0.4), None),))
+            room -= 1
+        while room > 0:
+            units.append(self.draw_unit(room))
+            room -= len(units[-1])
+        for k in rng.permutation(len(units)):
+            ops += [self.realize(t) for t in units[k]]
+        assert len(ops) == OPS
+        self.s["ops"] = ops
+        return self.s
+
+
+def script(seed, late=False):
+    return (_LateDraw if late else _Draw)(int(seed)).script()

@@ -15,6 +15,9 @@ the primitives differently: same_tree() compares the records always and canonica
 records but without the numbering, where the two shapes agree.  Whatever the shape, every record and box must be a fixed point
 of refit_ref over the model's positions, and the link words a refit must not touch are compared on the context itself.
 
+LateModel, at the end of this file, is the model of the late scripts (app_fuzz.script(seed, late=True)): the rig, the focus state,
+the record of the background build, what the last temporal step knew of its interval and the stamp of the last G-buffer trace.
+
 dry_run() is the part of the model that needs no renderer: the positions.  (oracle.OracleScene exposes trace() and no tree,
 so there is no hierarchy for refit_ref to follow without a GPU.)"""
 import hashlib
@@ -22,6 +25,7 @@ import hashlib
 import numpy as np
 
 import packet_ref as pk
+import post_ref as po
 import refit_ref as rf
 import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
@@ -66,22 +70,31 @@ def register(have, new):
             have[k] = v
 
 
-def dry_run(s, model):
-    """The positions a script leaves, through the three position restatements alone -> (V, 3) float32; every intermediate
-    position array is checked to be finite."""
+def dry_run(s, model, oracle=None):
+    """The positions a script leaves, through the position restatements alone -> (V, 3) float32; every intermediate position
+    array is checked to be finite.  oracle: for the scripts with a rig (rig_ref takes its sine and arc cosine from it)."""
+    import rig_ref as rg
     _, vtx, _, first = vertex_arrays(model)
     vtx = vtx.copy()
-    skins, morphs = dict(s["skins"]), dict(s["morphs"])
+    skins, morphs, rig = dict(s["skins"]), dict(s["morphs"]), s.get("rig")
     for op in s["ops"]:
         if op["op"] == "set_skins":
             register(skins, op["skins"])
+            rig = None
         elif op["op"] == "set_morphs":
             register(morphs, op["morphs"])
+            rig = None
+        elif op["op"] == "set_rig":
+            rig = op["rig"]
         elif op["op"] == "set_scene":
-            skins, morphs = {}, {}
+            skins, morphs, rig = {}, {}, None
             vtx = vertex_arrays(model)[1].copy()
         for u, _ in updates_of(op):
-            for k, v in restate(model, u["kind"], u["poses"], skins, morphs)[1].items():
+            if u["kind"] == "animated":
+                new = rg.restate(oracle, model, rig, u["poses"]["clip"], u["poses"]["time"], skins, morphs)
+            else:
+                new = restate(model, u["kind"], u["poses"], skins, morphs)[1]
+            for k, v in new.items():
                 assert np.isfinite(v).all(), (s["seed"], u["kind"], k)
                 vtx[first[k]:first[k + 1]] = v
     return vtx
@@ -185,9 +198,10 @@ class AppModel(PostChecker):
         p, n = debug_buffer(self.r, "scene_vertices")
         return self.r.download(p, np.empty((n // 12, 3), F))
 
-    def check_scene(self, rebuilt=False, before=None):
+    def check_scene(self, rebuilt=False, before=None, adopted=None):
         """After an update (and everything enqueued): positions, previous positions of the marked meshes, the tree against the
-        twin's, the cost counters and the cost."""
+        twin's, the cost counters and the cost.  adopted: the positions a background build's snapshot held, where the tree is
+        an adopted one that no synchronous rebuild has replaced since: `built` is the cost of the tree over those positions."""
         r = self.r
         # (the position buffer exists from a scene's first update on; before that, and so right after fovpt_set_scene, the
         # positions are held through the triangle records below, which must be refit_ref's of the model's positions)
@@ -217,7 +231,11 @@ class AppModel(PostChecker):
         assert (c.updates, c.measured) == (self.updates, self.updates), (c.updates, c.measured, self.updates)
         want, tol = expected_cost(n)
         assert abs(c.current - want) <= tol * want, (c.current, want)
-        if rebuilt or self.updates == 0:
+        if adopted is not None:
+            sn, _ = rf.refit(n, t, levels, self.tri_vidx, adopted)
+            want, tol = expected_cost(sn)
+            assert abs(c.built - want) <= tol * want, ("built of an adopted tree", c.built, want)
+        elif rebuilt or self.updates == 0:
             assert c.built == c.current
 
     def update(self, poses, rebuild=False, device=False, kind="vertices", check=True):
@@ -494,3 +512,431 @@ def with_pytest_code(code, call):
         assert e.code == code, (e.code, code, str(e))
         return
     raise AssertionError("a call that must be refused with %d was accepted" % code)
+
+
+# ---- the late family's model ---------------------------------------------------------------------------------------------------
+T_ = po.TEMPORAL
+IDLE, BUILDING, READY = abi.REBUILD_IDLE, abi.REBUILD_BUILDING, abi.REBUILD_READY
+DELAY = "FOVPT_ASYNC_BUILD_DELAY_MS"
+RAW, BC1, BY_FILL = abi.PACKET_RAW, abi.PACKET_BC1, abi.PACKET_BY_FILL
+
+
+class _Ptr:
+    """A device address where a helper asks for a tensor's data_ptr()."""
+
+    def __init__(self, p):
+        self.p = p
+
+    def data_ptr(self):
+        return self.p
+
+
+class LateModel(AppModel):
+    """AppModel for the scripts of app_fuzz.script(seed, late=True).  On top of AppModel it keeps: the rig (present or dropped:
+    fovpt_set_skins, fovpt_set_morphs and fovpt_set_scene drop it); the focus state (test_focus_gpu.Checker's, survives a resize,
+    reset by fovpt_focus_reset and fovpt_set_scene); the record of the background build (in flight or not, known to be READY after
+    a wait, the five counters, snapshot_update, the positions at the snapshot); what the last temporal step knew of its interval
+    (warp_motion_common.Intervals' `last`); and whether the context's last G-buffer trace is newer than every render, update,
+    resize, scene and adoption (the stamp fovpt_warp_motion checks for a caller's G-buffer).
+
+    Background builds stay deterministic.  No pixel depends on which conservative tree is in use, so frames, G-buffers and stages
+    are compared as ever.  An update that enqueues something while a build is in flight adopts the result if the state is READY:
+    after rebuild_state(WAIT) that is certain and expected; without it the model reads fovpt_rebuild_state(0).adopted once after
+    the call, accepts exactly "not adopted" and "adopted by one", goes on with what happened and logs it ("race")."""
+
+    def __init__(self, oracle, s, model, cam, probe):
+        from test_focus_gpu import Checker as FocusChecker
+        self.rig = None
+        self.rec = dict(flight=False, ready=False, requested=0, started=0, adopted=0, discarded=0, snapshot_update=0, snapshot=None)
+        self._pending = None                              # what the updates issued without a check (between frames) did to the tree
+        self.last = None
+        self.trace_fresh = False
+        self._late_keep = []
+        super().__init__(oracle, s, model, cam, probe)
+        self.fc = FocusChecker(oracle, self.r)
+        if s.get("rig") is not None:
+            self.set_rig(s["rig"])
+
+    def split(self, vtx):
+        return {k: vtx[self.first[k]:self.first[k + 1]].copy() for k in range(len(self.first) - 1)}
+
+    # ---- the background build
+    def check_info(self):
+        rec, info = self.rec, self.r.rebuild_state()
+        got = (info.requested, info.started, info.adopted, info.failed, info.discarded)
+        assert got == (rec["requested"], rec["started"], rec["adopted"], 0, rec["discarded"]), (got, rec["requested"], rec["started"], rec["adopted"], rec["discarded"])
+        assert info.last_error == 0
+        if rec["flight"]:
+            assert info.state in ((READY,) if rec["ready"] else (BUILDING, READY)), info.state
+            assert info.snapshot_update == rec["snapshot_update"], (info.snapshot_update, rec["snapshot_update"])
+        else:
+            assert info.state == IDLE, info.state
+
+    def adopt(self):
+        """The bookkeeping of an adoption -> the snapshot's positions.  The twin is brought to the same tree: a rebuild over the
+        snapshot, a refit over the present positions (the caller does both once the call's own update is in self.vtx)."""
+        rec = self.rec
+        snap = rec["snapshot"]
+        rec.update(flight=False, ready=False, snapshot=None)
+        rec["adopted"] += 1
+        self.updates += 1
+        self.trace_fresh = False                          # a caller's G-buffer no longer goes with the hit records
+        return snap
+
+    def twin_adopts(self, snap):
+        self.twin.update_vertices(self.split(snap), rebuild=True)
+        self.twin.update_vertices(self.split(self.vtx))
+
+    def rebuild_state(self, wait, adopt):
+        rec = self.rec
+        info = self.r.rebuild_state(wait=wait, adopt=adopt)
+        took = False
+        if rec["flight"]:
+            rec["ready"] = rec["ready"] or wait
+            if adopt and rec["ready"]:
+                took = True
+            elif adopt:
+                assert info.adopted in (rec["adopted"], rec["adopted"] + 1), info.adopted
+                took = info.adopted == rec["adopted"] + 1
+                self.log.append(("race", "rebuild_state", took))
+        if took:
+            at, now = rec["snapshot_update"], self.updates
+            snap = self.adopt()
+            self.twin_adopts(snap)
+            self.check_scene(True, None, snap)
+            self.log.append(("adopt", "rebuild_state", at, now, self.tree_agrees))
+        self.check_info()
+
+    def check_scene(self, rebuilt=False, before=None, adopted=None):
+        # AppModel.frames() ends with check_scene(rebuilt=any(b["rebuild"] ...)), which is true for "async" as well and knows
+        # nothing of adoptions.  What the updates between the frames really did to the tree is in _pending (update(check=False)
+        # fills it), and it replaces the arguments on purpose: keep this where frames() or its argument changes.
+        if self._pending is not None:
+            rebuilt, before, adopted = self._pending["shape"], None, self._pending["adopted"]
+            self._pending = None
+        super().check_scene(rebuilt, before, adopted)
+
+    # ---- updates
+    def update(self, poses, rebuild=False, device=False, kind="vertices", check=True):
+        import rig_ref as rg
+        from temporal_motion_common import MotionChecker
+        r, rec = self.r, self.rec
+        sync, asyn, animated = rebuild is True, rebuild == "async", kind == "animated"
+        moves = animated or bool(poses)
+        before = links(hierarchy(r)[0]) if check and not sync else None
+        if sync and rec["flight"]:                            # a synchronous rebuild ends the build
+            rec.update(flight=False, ready=False, snapshot=None)
+            rec["discarded"] += 1
+        idle = not rec["flight"]                              # when the call comes in: what a request looks at
+        may_adopt = moves and not sync and rec["flight"]
+        certain = may_adopt and rec["ready"]
+        if animated:
+            new = rg.restate(self.oracle, r.model, self.rig, poses["clip"], poses["time"], self.skins, self.morphs)
+            r.update_animated(poses["clip"], poses["time"], rebuild=rebuild)
+            for k, v in new.items():
+                self.vtx[self.first[k]:self.first[k + 1]] = v
+                self.moved[k] = True                          # one update for the tracking
+            self.untracked = self.untracked or (bool(new) and not self.tracking)
+            meshes = sorted(new)
+        else:
+            MotionChecker.update(self, poses, rebuild=rebuild, device=device, kind=kind)
+            meshes = sorted(poses)
+        snap = None
+        if may_adopt:
+            took = certain
+            if not certain:
+                n = r.rebuild_state().adopted
+                assert n in (rec["adopted"], rec["adopted"] + 1), n
+                took = n == rec["adopted"] + 1
+                self.log.append(("race", "update", took))
+            if took:
+                at, now = rec["snapshot_update"], self.updates
+                snap = self.adopt()                           # (counts one, before the call's own update)
+        if moves or sync:
+            self.updates += 1
+        if moves:
+            self.trace_fresh = False
+        if asyn:
+            rec["requested"] += 1
+            if idle:                                          # (a call that adopts counts its own request and starts nothing)
+                rec.update(flight=True, ready=False, snapshot_update=self.updates, snapshot=self.vtx.copy())
+                rec["started"] += 1
+        if snap is not None:
+            self.twin_adopts(snap)
+        else:
+            self.twin.update_vertices(self.current(meshes), rebuild=sync)
+        if check:
+            self.check_scene(sync or snap is not None, before if snap is None else None, snap)
+        else:
+            p = self._pending = self._pending or dict(shape=False, adopted=None)
+            if sync or snap is not None:
+                p.update(shape=True, adopted=snap)
+        if snap is not None:
+            self.log.append(("adopt", "update", at, now, self.tree_agrees if check else None))
+
+    def refused(self, op, check=True):
+        import ctypes as C
+        r, which = self.r, op["which"]
+        if which in ("no_rig", "clip_range"):
+            assert (self.rig is None) == (which == "no_rig")
+            with_pytest_code(op["code"], lambda: r.update_animated(op["clip"], op["time"]))
+        elif which == "async_with_rebuild":
+            both = abi.UPDATE_REBUILD | abi.UPDATE_REBUILD_ASYNC
+            if op["kind"] == "animated":
+                with_pytest_code(op["code"], lambda: r._check(r._L.fovpt_update_animated(r._ctx, op["clip"], C.c_float(op["time"]), both)))
+            else:
+                with_pytest_code(op["code"], lambda: r._check(r._L.fovpt_update_vertices(r._ctx, None, 0, both)))
+        elif which == "warp_motion_stale":
+            assert self.prev is not None and self.tracking and self.moved.any() and self.rendered      # an update since the step
+            to = self.to_camera(op["to"])[0]
+            with_pytest_code(op["code"], lambda: r.warp_motion(to))
+            return
+        else:
+            return super().refused(op, check)
+        if check:
+            self.check_scene()
+
+    # ---- registration
+    def set_skins(self, new):
+        super().set_skins(new)
+        self.rig = None
+
+    def set_morphs(self, new):
+        super().set_morphs(new)
+        self.rig = None
+
+    def set_rig(self, rig):
+        before = self.r.hierarchy_cost().updates
+        self.r.set_rig(rig)
+        self.rig = rig
+        assert self.r.hierarchy_cost().updates == before == self.updates      # a rig is no update
+        if self.updates:
+            assert np.array_equal(bits(self.scene_vertices()), bits(self.vtx)), "set_rig moved geometry"
+
+    # ---- context events
+    def resize(self, size):
+        from test_focus_gpu import state_tuple
+        super().resize(size)
+        self.last, self.trace_fresh, self._late_keep = None, False, []
+        if self.fc.state["steps"]:                            # the focus state stays
+            assert state_tuple(self.r.focus_state()) == state_tuple(self.fc.state), "focus state after a resize"
+
+    def set_scene(self):
+        rec = self.rec
+        if rec["flight"]:                                     # the scene ends the build
+            rec.update(flight=False, ready=False, snapshot=None)
+            rec["discarded"] += 1
+        self.rig, self.last, self.trace_fresh = None, None, False
+        self.fc.reset()
+        super().set_scene()
+        with_pytest_code(E_INVALID, lambda: self.r.update_animated(0, 0.5))        # the rig went with the scene
+        assert self.r.focus_state().steps == 0
+
+    # ---- the chain
+    def to_camera(self, to):
+        from test_warp_gpu import to_camera
+        return to_camera((to[1], to[2]), self.size, base=self.cam)
+
+    def step(self, inp=None, in_ptr=None, out=None, with_motion=True, stages=None):
+        st = self.stages if stages is None else stages
+        m, untracked = self.motion(), self.untracked
+        m = dict(m, vtx_prev=m["vtx_prev"].copy(), vtx=m["vtx"].copy())
+        res = super().step(inp, in_ptr, out, with_motion, stages)
+        if st & T_:
+            self.last = None if untracked else m              # what the step knew of the interval it ended
+        self.trace_fresh = True
+        return res
+
+    def focus(self, d, color, ptr):
+        """test_focus_gpu.Checker.step with the frame as rendered where that reads the launch parameters."""
+        import focus_ref as fr
+        from test_focus_gpu import device_outputs, fcfg, host, state_tuple
+        r = self.r
+        cfg, full = fcfg({k: v for k, v in d.items() if k != "gbuffer"})
+        g = r.temporal_gbuffer() if d["gbuffer"] == "temporal" else None
+        inp = r.downloadAccum() if color is None else color
+        oc, op, oz = device_outputs(self.size)
+        r.focus(cfg, g, ptr, oc.data_ptr(), op.data_ptr(), oz.data_ptr())
+        gb = r.downloadGBuffer()                              # (the same rays as the call's own trace, and as the step's)
+        self.trace_fresh = True
+        steps = self.fc.state["steps"]
+        want = fr.focus(self.oracle, gb, self.frame_as_rendered[1], inp, full, self.fc.state)
+        self.fc.state = want["state"]
+        if self.fc.state["steps"]:
+            got = r.focus_state()
+            assert state_tuple(got) == state_tuple(self.fc.state), ("focus: state", state_tuple(got), state_tuple(self.fc.state))
+        assert np.array_equal(bits(host(oz, "coc")), bits(want["coc"])), "focus: radius"
+        assert np.array_equal(bits(host(oc, "color")), bits(want["color"])), "focus: colour"
+        assert np.array_equal(host(op, "rgba"), want["rgba"]), "focus: rgba8"
+        self.log.append(("focus", full["mode"], int(want["state"]["count"]) if full["mode"] == abi.FOCUS_AUTO else None, int(want["acted"].sum()), steps))
+        self._late_keep += [oc, op, oz]
+        return want["color"], oc.data_ptr(), want["rgba"], op.data_ptr()
+
+    def warp(self, la, color, ptr, rgba, rgba_ptr):
+        """fovpt_warp through test_warp_gpu.check; fovpt_warp_motion as warp_motion_common.check does it, with the chain's images
+        as the inputs and `last` from the model's own steps."""
+        import warp_motion_ref as wm
+        import warp_ref as wr
+        from temporal_common import camera
+        from test_warp_gpu import check as warp_check, counts_of, device_outputs, host
+        from warp_motion_common import frame_data, mcfg
+        r = self.r
+        to, want_cam = self.to_camera(la["to"])
+        inp = r.downloadAccum() if color is None else color
+        images, radius = la["images"], la["fill_radius"]
+        if la["stage"] == "warp":
+            gb = r.downloadGBuffer()
+            self.trace_fresh = True
+            warp_check(r, to, want_cam, gb, inp, rgba, radius, images, (ptr, rgba_ptr), None, "warp")
+            self.log.append(("warp",))
+            return
+        cfg = mcfg(images=images, fill_radius=radius, advance=la["advance"])
+        g = r.temporal_gbuffer() if la["gbuffer"] == "temporal" else None
+        if la["adopt"]:                                       # an adoption between the step's trace and the warp
+            assert self.rec["flight"] and g is not None
+            self.rebuild_state(True, True)
+            assert not self.trace_fresh
+            with_pytest_code(E_NO_FRAME, lambda: r.warp_motion(to, cfg, g, ptr, rgba_ptr))
+            self.log.append(("stale", "refused"))
+            frame_data(r)                                     # a fresh trace: the caller's set goes with the hit records again
+            self.trace_fresh = True
+        assert self.prev is not None and self.tracking and not self.moved.any()     # legal: a step, tracking, no update since
+        assert g is None or self.trace_fresh                  # ... and with a caller's G-buffer, a trace newer than everything else
+        oc, op, om = device_outputs(self.size)
+        r.warp_motion(to, cfg, g, ptr, rgba_ptr, oc.data_ptr(), op.data_ptr(), om.data_ptr())
+        got_counts = counts_of(r)
+        gb, uv = frame_data(r)                                # (the same rays as the trace the call used, or made)
+        self.trace_fresh = True
+        d = dict(images=images, fill_radius=radius, advance=la["advance"])
+        want = wm.warp(gb, uv, self.last, camera(r), want_cam, d, inp, rgba)
+        plain = wr.warp(gb, camera(r), want_cam, dict(images=images, fill_radius=radius), inp, rgba)
+        assert np.array_equal(host(om, 1), want["map"]), "warp_motion: map"
+        assert got_counts == want["counts"] and sum(got_counts[1:]) == self.size[0] * self.size[1], (got_counts, want["counts"])
+        differs = not np.array_equal(want["map"], plain["map"])
+        if images & wr.COLOR:
+            assert np.array_equal(bits(host(oc, 4)), bits(want["color"])), "warp_motion: colour"
+            differs = differs or not np.array_equal(bits(want["color"]), bits(plain["color"]))
+        else:
+            assert (oc.cpu().numpy() == 0x5a).all()
+        if images & wr.RGBA:
+            assert np.array_equal(host(op, 1), want["rgba"]), "warp_motion: rgba8"
+            differs = differs or not np.array_equal(want["rgba"], plain["rgba"])
+        else:
+            assert (op.cpu().numpy() == 0x5a).all()
+        moving = self.last is not None and bool(self.last["moved"].any()) and la["advance"] > 0
+        if not moving:                                        # nothing known to move: fovpt_warp's bits
+            assert not differs, "warp_motion without motion is not fovpt_warp"
+        self.log.append(("warp_motion", moving, differs, self.last is None))
+        if la["adopt"]:
+            self.log.append(("stale", "accepted"))
+
+    def lens(self, la, color, ptr):
+        from test_lens_gpu import lcfg, run
+        r = self.r
+        inp = r.downloadAccum() if color is None else color
+        cfg, full = lcfg(self.size, filter=la["filter"], chroma=la["chroma"])
+        want = run(r, self.oracle, inp, _Ptr(ptr), cfg, full, self.to_camera(la["to"]) if la["to"] is not None else None, "lens")
+        self.log.append(("lens", not np.array_equal(bits(want["color"]), bits(inp))))
+
+    def packet(self, rgba, rgba_ptr, codec=None):
+        import torch
+        import packet_bc_ref as bc
+        from packet_cases import junk_canvas
+        from test_packet_gpu import decode_on_device
+        if codec is None:
+            return super().packet(rgba, rgba_ptr)
+        r, seq = self.r, SEQUENCE0 + self.packets
+        pas = pk.passes(*self.frame_as_rendered)
+        give = tuple(k if p < len(pas) or k == BY_FILL else RAW for p, k in enumerate(codec))      # nothing beyond the frame's passes
+        if not pk.check(pk.encode(rgba, *self.frame_as_rendered, sequence=seq)):    # as the raw packet: a pass without a launch index
+            with_pytest_code(E_INVALID, lambda: r.submitPacket(seq, rgba_ptr, codec=give))
+            self.log.append(("coded", None, 0))
+            return
+        resolved = tuple((BC1 if pas[p][3] > 1 else RAW) if codec[p] == BY_FILL else codec[p] for p in range(len(pas)))
+        want = bc.encode(rgba, *self.frame_as_rendered, resolved, sequence=seq)
+        slot = r.submitPacket(seq, rgba_ptr, codec=give)
+        assert slot == self.packets % abi.PACKET_SLOTS
+        self.packets += 1
+        got = r.waitPacket(slot)
+        assert got == want, "coded packet %d" % seq
+        hd = bc.parse(got)
+        two = 0
+        for (gw, gh, *_, off), k in zip(hd["passes"], hd["codecs"]):
+            if k == BC1:
+                w = np.frombuffer(got, "<u4", 2 * ((gw + 3) // 4) * ((gh + 3) // 4), off).reshape(-1, 2)
+                two += int(((w[:, 0] & 0xffff) != (w[:, 0] >> 16)).sum())
+        self.log.append(("coded", resolved, two))
+        h = abi.PacketHeader.from_packet(got)
+        dev = torch.frombuffer(bytearray(got), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        for mode in (abi.PACKET_NEAREST, abi.PACKET_SMOOTH):
+            ref = bc.decode(got, mode, junk_canvas(self.size))
+            assert np.array_equal(decode_on_device(r, dev, h, mode), ref), mode
+            assert np.array_equal(renderer.decode_packet(got, mode, self.size, out=junk_canvas(self.size)), ref), mode
+
+    def chain(self, c, moved_on=None):
+        """post -> focus -> expose -> packet (of the unwarped frame) -> warp | warp_motion | lens."""
+        if "focus" not in c:
+            return super().chain(c, moved_on)
+        r = self.r
+        if moved_on is not None:
+            f = r.launchParams.frame
+            f.c.x, f.c.y = moved_on["gaze"][0] & 0xffffffff, moved_on["gaze"][1] & 0xffffffff
+            f.subframe_index = moved_on["subframe_index"]
+        color = ptr = None
+        rgba, rgba_ptr = self.last_rgba, None if not self._bufs or self._bufs[-1] is None else self._bufs[-1][1].data_ptr()
+        if c["post"] is not None:
+            had = self.prev is not None
+            out = self.step(stages=c["post"])
+            color, ptr = out["color"], r.post_buffers()[0]
+            rgba, rgba_ptr = r.downloadPostPixels(), r.post_buffers()[1]
+            self.log.append(("post", c["post"], had))
+        if c["focus"] is not None:
+            color, ptr, rgba, rgba_ptr = self.focus(c["focus"], color, ptr)
+        if c["expose"] is not None:
+            out = self.expose(c["expose"], r.downloadAccum() if color is None else color, ptr)
+            color, ptr = out["color"], r.expose_buffers()[0]
+            rgba, rgba_ptr = out["rgba"], r.expose_buffers()[1]
+        if c["packet"]:
+            self.packet(rgba, rgba_ptr, c["codec"])
+        la = c["last"]
+        if la is not None and la["stage"] == "lens":
+            self.lens(la, color, ptr)
+        elif la is not None:
+            self.warp(la, color, ptr, rgba, rgba_ptr)
+
+    # ---- a script
+    def run_op(self, op):
+        kind = op["op"]
+        if kind == "frame":
+            self.frames(op)
+            self.trace_fresh, self._late_keep = False, []
+            if op.get("adopt_first"):
+                self.rebuild_state(True, True)
+            if op["pre_chain"] is not None:
+                u = op["pre_chain"]
+                self.update(u["poses"], u["rebuild"], u["device"], u["kind"])
+            self.chain(op["chain"], op.get("moved_on"))
+        elif kind == "set_rig":
+            self.set_rig(op["rig"])
+        elif kind == "rebuild_state":
+            self.rebuild_state(op["wait"], op["adopt"])
+        elif kind == "focus_reset":
+            self.r.focus_reset()
+            self.fc.reset()
+        else:
+            super().run_op(op)
+        self.check_info()
+
+    def run(self):
+        import os
+        had = os.environ.get(DELAY)
+        if self.s.get("delay_ms"):
+            os.environ[DELAY] = str(self.s["delay_ms"])      # (widens the BUILDING window; no assertion depends on it)
+        try:
+            super().run()
+        finally:
+            if had is None:
+                os.environ.pop(DELAY, None)
+            else:
+                os.environ[DELAY] = had
