@@ -193,6 +193,21 @@ class DebugGenerateResult(C.Structure):
         ("guides", C.c_uint32), ("slot_begin", C.c_uint32), ("slot_end", C.c_uint32), ("grid", C.c_uint32)]
 
 
+class DebugBuildSwitches(C.Structure):
+    """struct fovpt_debug_build_switches: the switches of one fovpt_debug_build, nothing from the environment."""
+    _fields_ = [("use_ploc", C.c_int32), ("split_budget", C.c_float), ("reinsert_rounds", C.c_int32), ("order_children", C.c_int32)]
+
+
+class DebugBuildTrace(C.Structure):
+    """struct fovpt_debug_build_trace: host arrays of the caller's for what every stage of a build left, and its scalars."""
+    _fields_ = [(k, C.c_void_p) for k in ("split_count", "split_first", "ref_prim", "boxes", "keys_s", "vals_s", "left0", "right0", "ibox0",
+                                          "round_end", "left1", "right1", "ibox1", "size_int", "node_first", "leaf_pos", "dp", "nodes_pre",
+                                          "nodes", "tris")] + [
+        (k, C.c_uint32) for k in ("cap_refs", "cap_rounds", "num_refs", "tiny", "have_count", "have_splits", "root", "num_rounds", "num_nodes",
+                                  "max_depth", "reinserted", "num_levels")] + [
+        ("s_cut", C.c_float), ("cbounds", C.c_float * 6), ("level_first", C.c_uint32 * 65)]
+
+
 class HierarchyCost(C.Structure):
     """fovpt_hierarchy_cost_info: the SAH cost of the hierarchy as built and as last measured, and the update counters."""
     _fields_ = [("built", C.c_double), ("current", C.c_double), ("updates", C.c_uint64), ("measured", C.c_uint64)]

@@ -230,6 +230,61 @@ int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* d
     return FOVPT_OK;
 }
 
+// test hook: the PRODUCTION hierarchy build -- fovpt_build_lbvh itself, the function fovpt_set_scene and the rebuilds call -- over
+// caller-supplied triangles under explicit switches, with a trace: what every stage left (fovpt_device.h, BvhBuildTrace).  The
+// triangles, the hierarchy and the trace are the call's own: no member of the context changes but the error text.
+int fovpt_debug_build(fovpt_ctx* c, uint32_t n, const float* tris9, const uint32_t* mesh_of_prim, const fovpt_debug_build_switches* sw,
+                      fovpt_debug_build_trace* out)
+{
+    if (!c || !tris9 || !sw || !out || n == 0 || n > (1u << 24)) return FOVPT_E_INVALID;
+    if (!(sw->split_budget >= 0.f) || sw->split_budget > 2.f || sw->reinsert_rounds < 0) return fail(c, FOVPT_E_INVALID, "fovpt_debug_build: switches out of range");
+    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    DevBuf d_flat, d_mesh;
+    HIPCHK(c, upload(d_flat, tris9, 36ull * n));
+    HIPCHK(c, d_mesh.reserve(4ull * n));
+    if (mesh_of_prim) HIPCHK(c, hipMemcpy(d_mesh.p, mesh_of_prim, 4ull * n, hipMemcpyHostToDevice));
+    else HIPCHK(c, hipMemset(d_mesh.p, 0, 4ull * n));
+    BvhSwitches bs;
+    bs.use_ploc = sw->use_ploc ? 1 : 0; bs.split_budget = sw->split_budget; bs.order_children = sw->order_children ? 1 : 0;
+    bs.reinsert_rounds = sw->reinsert_rounds; bs.verbose = 0;
+    BvhBuildResult br;
+    memset(&br, 0, sizeof(br));
+    BvhBuildTrace T;
+    char err[256];
+    const hipError_t be = fovpt_build_lbvh(c->stream, (const float*)d_flat.p, (const uint32_t*)d_mesh.p, n, bs, sw->reinsert_rounds, &br, err, sizeof(err), &T);
+    if (be != hipSuccess) return fail(c, FOVPT_E_DEVICE, "fovpt_debug_build: %s", err);
+    struct Free { void* p; ~Free() { (void)hipFree(p); } } free_nodes{br.nodes};          // (one allocation: nodes, then triangles)
+    const size_t R = br.num_refs, I = R - 1, N = br.num_nodes;
+    out->num_refs = br.num_refs;
+    if (R > out->cap_refs) return fail(c, FOVPT_E_INVALID, "fovpt_debug_build: %zu references, room for %u", R, out->cap_refs);
+    if (T.round_end.size() > out->cap_rounds && out->round_end) return fail(c, FOVPT_E_INVALID, "fovpt_debug_build: %zu PLOC rounds, room for %u", T.round_end.size(), out->cap_rounds);
+    if (br.num_levels == 0) return fail(c, FOVPT_E_INVALID, "fovpt_debug_build: the wide tree has more than %d levels", FOVPT_BVH_MAX_LEVELS);
+    // every array of the trace has the length its stage gives it
+    const bool tree = !T.tiny;
+    const size_t want_i = tree ? I : 0;
+    if (T.boxes.size() != 6 * R || T.vals_s.size() != R || T.leaf_pos.size() != R || T.nodes_pre.size() != 32 * N || T.keys_s.size() != (tree ? R : 0)
+        || T.left0.size() != want_i || T.right0.size() != want_i || T.ibox0.size() != 6 * want_i || T.left1.size() != want_i || T.right1.size() != want_i
+        || T.ibox1.size() != 6 * want_i || T.size_int.size() != want_i || T.node_first.size() != want_i || T.dp.size() != 4 * want_i
+        || (!T.split_count.empty() && T.split_count.size() != n) || (T.splits && (T.split_first.size() != n || T.ref_prim.size() != R)))
+        return fail(c, FOVPT_E_DEVICE, "fovpt_debug_build: a stage's arrays do not have the build's sizes");
+    auto put = [](auto* dst, const auto& v) { if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    put(out->split_count, T.split_count); put(out->split_first, T.split_first); put(out->ref_prim, T.ref_prim);
+    put(out->boxes, T.boxes); put(out->keys_s, T.keys_s); put(out->vals_s, T.vals_s);
+    put(out->left0, T.left0); put(out->right0, T.right0); put(out->ibox0, T.ibox0); put(out->round_end, T.round_end);
+    put(out->left1, T.left1); put(out->right1, T.right1); put(out->ibox1, T.ibox1);
+    put(out->size_int, T.size_int); put(out->node_first, T.node_first); put(out->leaf_pos, T.leaf_pos); put(out->dp, T.dp);
+    put(out->nodes_pre, T.nodes_pre);
+    if (out->nodes) HIPCHK(c, hipMemcpy(out->nodes, br.nodes, sizeof(BvhNode4) * N, hipMemcpyDeviceToHost));
+    if (out->tris) HIPCHK(c, hipMemcpy(out->tris, br.tris, sizeof(TriRec) * R, hipMemcpyDeviceToHost));
+    out->tiny = (uint32_t)T.tiny; out->have_count = T.split_count.empty() ? 0u : 1u; out->have_splits = (uint32_t)T.splits;
+    out->root = (uint32_t)T.root; out->num_rounds = (uint32_t)T.round_end.size();
+    out->num_nodes = br.num_nodes; out->max_depth = br.max_depth; out->reinserted = br.reinserted; out->num_levels = br.num_levels;
+    out->s_cut = T.s_cut;
+    for (int a = 0; a < 6; a++) out->cbounds[a] = T.cbounds[a];
+    for (uint32_t L = 0; L <= br.num_levels; L++) out->level_first[L] = br.level_first[L];
+    return debug_end(c);
+}
+
 // test hook: the PRODUCTION shading kernel on caller-made hits -- one launch of fovpt_launch_shade (k_shade<false> or <true> by the
 // configured options, as run_job launches it) over an input queue the caller laid out, and everything the kernel left: the slots'
 // state, the counters and the occupied entries of the next radiance queue and of the shadow queue.  Every buffer the kernel may

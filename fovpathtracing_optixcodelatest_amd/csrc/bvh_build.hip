@@ -227,20 +227,32 @@ __global__ void k_ploc_nn(int n, int force, const Box* __restrict__ c_box, int* 
     nn[i] = bj;
 }
 
-// children coded: >= 0 internal node id, < 0 ~sorted leaf position
-__global__ void k_ploc_merge(int n, const int* __restrict__ c_node, const Box* __restrict__ c_box, const int* __restrict__ nn,
-                             uint32_t* __restrict__ node_counter, int* __restrict__ left, int* __restrict__ right,
+// a cluster survives the round unless it is the higher index of a mutual pair
+__global__ void k_ploc_mark(int n, const int* __restrict__ nn, uint32_t* __restrict__ valid)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int j = nn[i];
+    valid[i] = (j != i && nn[j] == i && i > j) ? 0u : 1u;
+}
+
+// children coded: >= 0 internal node id, < 0 ~sorted leaf position.  pos = the exclusive scan of valid: a survivor's place in the
+// next round's list, and j - pos[j] = the dropped clusters in front of j, which numbers the round's pairs 0, 1, ... in the order of
+// their higher index: node ids are a function of the input alone, not of the order threads arrive in.  (Reinsertion breaks ties
+// between equal gains by node id -- move_key -- so ids from an atomic made the reinserted tree differ from build to build.)
+__global__ void k_ploc_merge(int n, int base, const int* __restrict__ c_node, const Box* __restrict__ c_box, const int* __restrict__ nn,
+                             const uint32_t* __restrict__ pos, int* __restrict__ left, int* __restrict__ right,
                              int* __restrict__ parent_int, int* __restrict__ parent_leaf, unsigned char* __restrict__ side_int,
                              unsigned char* __restrict__ side_leaf, Box* __restrict__ ibox, uint32_t* __restrict__ size_int,
-                             uint32_t* __restrict__ valid, int* __restrict__ t_node, Box* __restrict__ t_box)
+                             int* __restrict__ t_node, Box* __restrict__ t_box)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int j = nn[i];
     const bool mutual = j != i && nn[j] == i;
-    if (!mutual) { valid[i] = 1u; t_node[i] = c_node[i]; t_box[i] = c_box[i]; return; }
-    if (i > j) { valid[i] = 0u; return; }
-    const int node = (int)atomicAdd(node_counter, 1u);
+    if (!mutual) { t_node[pos[i]] = c_node[i]; t_box[pos[i]] = c_box[i]; return; }
+    if (i > j) return;
+    const int node = base + (j - (int)pos[j]);
     const int a = c_node[i], b = c_node[j];
     const Box ba = c_box[i], bb = c_box[j];
     Box u;
@@ -251,16 +263,7 @@ __global__ void k_ploc_merge(int n, const int* __restrict__ c_node, const Box* _
     parent_int[node] = -1;
     if (a < 0) { parent_leaf[~a] = node; side_leaf[~a] = 0; } else { parent_int[a] = node; side_int[a] = 0; }
     if (b < 0) { parent_leaf[~b] = node; side_leaf[~b] = 1; } else { parent_int[b] = node; side_int[b] = 1; }
-    valid[i] = 1u; t_node[i] = node; t_box[i] = u;
-}
-
-__global__ void k_ploc_compact(int n, const uint32_t* __restrict__ valid, const uint32_t* __restrict__ pos,
-                               const int* __restrict__ t_node, const Box* __restrict__ t_box, int* __restrict__ c_node, Box* __restrict__ c_box)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !valid[i]) return;
-    c_node[pos[i]] = t_node[i];
-    c_box[pos[i]] = t_box[i];
+    t_node[pos[i]] = node; t_box[pos[i]] = u;           // (the next round's list: the host swaps the two lists)
 }
 
 // depth-first position of every leaf and first position of every internal node: climb to the root,
@@ -891,7 +894,7 @@ BvhSwitches fovpt_bvh_switches()
 }
 
 hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n_prims, const BvhSwitches& sw,
-                            int reinsert, BvhBuildResult* out, char* err, size_t errlen)
+                            int reinsert, BvhBuildResult* out, char* err, size_t errlen, BvhBuildTrace* trace)
 {
     const int use_ploc = sw.use_ploc;
     const float split_budget = sw.split_budget;
@@ -908,7 +911,7 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
     // PLOC state
     int *c_node = nullptr, *t_node = nullptr, *nn = nullptr;
     Box *c_box = nullptr, *t_box = nullptr;
-    uint32_t *valid = nullptr, *pos = nullptr, *node_counter = nullptr, *size_int = nullptr, *leaf_pos = nullptr, *node_first = nullptr, *node_depth = nullptr;
+    uint32_t *valid = nullptr, *pos = nullptr, *size_int = nullptr, *leaf_pos = nullptr, *node_first = nullptr, *node_depth = nullptr;
     unsigned char *side_int = nullptr, *side_leaf = nullptr;
     void* scan_temp = nullptr;
     size_t scan_bytes = 0;
@@ -959,6 +962,16 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
         snprintf(err, errlen, "bottom-up sweeps did not reach the root");
         return false;
     };
+    // trace only (fovpt_debug_build): `count` elements of a stage's device array into a host vector, once the stage is through
+    auto grab = [&](auto& dst, const void* src, size_t count) -> bool {
+        dst.resize(count);
+        if (count == 0) return true;
+        if (hipMemcpyAsync(dst.data(), src, count * sizeof(dst[0]), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            snprintf(err, errlen, "copying a stage of the build out failed: %s", hipGetErrorString(hipGetLastError()));
+            return false;
+        }
+        return true;
+    };
     for (int a = 0; a < 3; a++) { h_bounds[a] = 0xffffffffu; h_bounds[3 + a] = 0u; }
     HC(hipMalloc(&bounds, 6 * 4));
     if (split_budget > 0.f && n_prims > FOVPT_LEAF_MAX) {
@@ -987,6 +1000,7 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
         hipLaunchKernelGGL(k_split_count, dim3(gp), dim3(B), 0, st, flat, n_prims, s_cut, split_cnt, split_total);
         HC(hipMemcpyAsync(&h_total, split_total, 8, hipMemcpyDeviceToHost, st));
         HC(hipStreamSynchronize(st));
+        if (trace) { trace->s_cut = s_cut; if (!grab(trace->split_count, split_cnt, n_prims)) goto fail; }
         if (h_total > n_prims && h_total < (1ull << 27)) {
             size_t tb = 0;
             HC(rocprim::exclusive_scan(nullptr, tb, split_cnt, split_first, 0u, (size_t)n_prims, rocprim::plus<uint32_t>(), st));
@@ -999,6 +1013,7 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
             hipLaunchKernelGGL(k_split_emit, dim3(gp), dim3(B), 0, st, flat, n_prims, split_cnt, split_first, boxes, ref_prim, bounds);
             HC(hipGetLastError());
             have_boxes = true;
+            if (trace) { trace->splits = 1; if (!grab(trace->split_first, split_first, n_prims) || !grab(trace->ref_prim, ref_prim, n)) goto fail; }
         }
     }
     ni = n > 1 ? n - 1 : 1;
@@ -1020,15 +1035,23 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
         HC(hipMemcpyAsync(bounds, h_bounds, sizeof(h_bounds), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_tri_bounds, dim3(gn), dim3(B), 0, st, flat, n, boxes, bounds);
     }
+    if (trace) {
+        std::vector<uint32_t> hb;
+        if (!grab(hb, bounds, 6) || !grab(trace->boxes, boxes, 6ull * n)) goto fail;
+        for (int a = 0; a < 6; a++) trace->cbounds[a] = ord2f(hb[a]);
+        trace->tiny = n <= FOVPT_LEAF_MAX ? 1 : 0;
+    }
     if (n <= FOVPT_LEAF_MAX) {
         hipLaunchKernelGGL(k_iota, dim3(1), dim3(64), 0, st, vals_s, n);
         hipLaunchKernelGGL(k_emit_tiny, dim3(1), dim3(1), 0, st, (int)n, boxes, nodes, stats, leaf_pos);
+        if (trace && (!grab(trace->vals_s, vals_s, n) || !grab(trace->leaf_pos, leaf_pos, n))) goto fail;
     } else {
         int root = 0;
         hipLaunchKernelGGL(k_morton, dim3(gn), dim3(B), 0, st, boxes, n, bounds, keys, vals);
         HC(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, keys_s, vals, vals_s, (size_t)n, 0, 63, st));
         HC(hipMalloc(&temp, temp_bytes));
         HC(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_s, vals, vals_s, (size_t)n, 0, 63, st));
+        if (trace && (!grab(trace->keys_s, keys_s, n) || !grab(trace->vals_s, vals_s, n))) goto fail;
         if (!use_ploc) {
             HC(hipMalloc(&arrive, 4ull * ni));
             HC(hipMalloc(&rfirst, 4ull * ni)); HC(hipMalloc(&rlast, 4ull * ni));
@@ -1037,39 +1060,48 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
             hipLaunchKernelGGL(k_refit, dim3(gn), dim3(B), 0, st, boxes, vals_s, (int)n, left, right, parent_int, parent_leaf, ibox, arrive);
             hipLaunchKernelGGL(k_lbvh_generic, dim3(gn), dim3(B), 0, st, (int)n, rfirst, rlast, size_int, node_first, leaf_pos);
             root = 0;
+            if (trace) {
+                trace->root = root;
+                if (!grab(trace->left0, left, ni) || !grab(trace->right0, right, ni) || !grab(trace->ibox0, ibox, 6ull * ni)) goto fail;
+            }
         } else {
             HC(hipMalloc(&c_node, 4ull * n)); HC(hipMalloc(&t_node, 4ull * n)); HC(hipMalloc(&nn, 4ull * n));
             HC(hipMalloc(&c_box, sizeof(Box) * n)); HC(hipMalloc(&t_box, sizeof(Box) * n));
             HC(hipMalloc(&valid, 4ull * n)); HC(hipMalloc(&pos, 4ull * n));
-            HC(hipMalloc(&node_counter, 4)); HC(hipMalloc(&node_depth, 4ull * ni));
+            HC(hipMalloc(&node_depth, 4ull * ni));
             HC(hipMalloc(&side_int, ni)); HC(hipMalloc(&side_leaf, n));
-            HC(hipMemsetAsync(node_counter, 0, 4, st));
             HC(hipMemsetAsync(side_int, 0, ni, st));
             HC(rocprim::exclusive_scan(nullptr, scan_bytes, valid, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
             HC(hipMalloc(&scan_temp, scan_bytes));
             hipLaunchKernelGGL(k_ploc_init, dim3(gn), dim3(B), 0, st, (int)n, boxes, vals_s, c_node, c_box);
-            uint32_t m = n;
+            uint32_t m = n, made = 0;
             int force = 0, rounds = 0;
             round_end.clear();
             while (m > 1) {
                 const uint32_t gm = (m + B - 1) / B;
                 hipLaunchKernelGGL(k_ploc_nn, dim3(gm), dim3(B), 0, st, (int)m, force, c_box, nn);
-                hipLaunchKernelGGL(k_ploc_merge, dim3(gm), dim3(B), 0, st, (int)m, c_node, c_box, nn, node_counter, left, right, parent_int,
-                                   parent_leaf, side_int, side_leaf, ibox, size_int, valid, t_node, t_box);
+                hipLaunchKernelGGL(k_ploc_mark, dim3(gm), dim3(B), 0, st, (int)m, nn, valid);
                 HC(rocprim::exclusive_scan(scan_temp, scan_bytes, valid, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
-                hipLaunchKernelGGL(k_ploc_compact, dim3(gm), dim3(B), 0, st, (int)m, valid, pos, t_node, t_box, c_node, c_box);
-                uint32_t last_pos = 0, last_valid = 0, made = 0;
-                HC(hipMemcpyAsync(&made, node_counter, 4, hipMemcpyDeviceToHost, st));
+                hipLaunchKernelGGL(k_ploc_merge, dim3(gm), dim3(B), 0, st, (int)m, (int)made, c_node, c_box, nn, pos, left, right, parent_int,
+                                   parent_leaf, side_int, side_leaf, ibox, size_int, t_node, t_box);
+                uint32_t last_pos = 0, last_valid = 0;
                 HC(hipMemcpyAsync(&last_pos, pos + (m - 1), 4, hipMemcpyDeviceToHost, st));
                 HC(hipMemcpyAsync(&last_valid, valid + (m - 1), 4, hipMemcpyDeviceToHost, st));
                 HC(hipStreamSynchronize(st));
-                round_end.push_back(made);
+                { int* tn = c_node; c_node = t_node; t_node = tn; Box* tb = c_box; c_box = t_box; t_box = tb; }
                 const uint32_t m2 = last_pos + last_valid;
+                made += m - m2;                                // every pair drops one cluster and makes one node
+                round_end.push_back(made);
                 // (Almost) no mutual pair this round -- coincident geometry: among equal boxes everybody picks the first
                 // candidate of its window and one pair merges per round -- so the next round pairs neighbours.
                 force = ((uint64_t)(m - m2) * 64u < m) ? 1 : 0;
                 m = m2;
                 if (++rounds > 4096) { snprintf(err, errlen, "PLOC did not converge"); goto fail; }
+            }
+            if (trace) {
+                trace->root = (int)n - 2;
+                trace->round_end = round_end;
+                if (!grab(trace->left0, left, ni) || !grab(trace->right0, right, ni) || !grab(trace->ibox0, ibox, 6ull * ni)) goto fail;
             }
             if (reinsert_rounds > 0 && n > 16) {
                 // ---- reinsertion rounds on the PLOC tree (see k_reinsert_find)
@@ -1118,6 +1150,8 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
                                leaf_pos, node_first, node_depth);
             root = (int)n - 2;                                 // the last merge created the root
         }
+        if (trace && (!grab(trace->left1, left, ni) || !grab(trace->right1, right, ni) || !grab(trace->ibox1, ibox, 6ull * ni)
+                      || !grab(trace->size_int, size_int, ni) || !grab(trace->node_first, node_first, ni) || !grab(trace->leaf_pos, leaf_pos, n))) goto fail;
         // ---- 2 -> 4 collapse: costs bottom-up, then one launch per level of the wide tree
         HC(hipMalloc(&dp, sizeof(DpCost) * ni));
         if (use_ploc && !tree_changed) {
@@ -1140,6 +1174,7 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
             hipLaunchKernelGGL(k_dp_collapse, dim3(gn), dim3(B), 0, st, (int)n, boxes, vals_s, left, right, parent_int, parent_leaf, size_int, ibox,
                                dp, dp_arrive);
         }
+        if (trace && !grab(trace->dp, dp, 4ull * ni)) goto fail;
         HC(hipMalloc(&work_a, sizeof(Work4) * ni)); HC(hipMalloc(&work_b, sizeof(Work4) * ni));
         Work4 w0; w0.node = root; w0.out = 0; w0.depth = 0;
         HC(hipMemcpyAsync(work_a, &w0, sizeof(w0), hipMemcpyHostToDevice, st));
@@ -1163,6 +1198,7 @@ hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* m
     }
     hipLaunchKernelGGL(k_emit_tris_generic, dim3(gn), dim3(B), 0, st, flat, mesh_of_prim, vals_s, ref_prim, leaf_pos, n, tris);
     HC(hipGetLastError());
+    if (trace && !grab(trace->nodes_pre, nodes, 32ull * (level_first.size() >= 2 ? level_first.back() : 1u))) goto fail;
     if (order_children && level_first.size() >= 2) {
         // children in the order that ends occlusion rays soonest: one launch per level, deepest first
         const uint32_t total = level_first.back();
@@ -1211,7 +1247,7 @@ fail:
     (void)hipFree(vals); (void)hipFree(vals_s); (void)hipFree(arrive); (void)hipFree(left); (void)hipFree(right); (void)hipFree(parent_int);
     (void)hipFree(parent_leaf); (void)hipFree(rfirst); (void)hipFree(rlast); (void)hipFree(temp); (void)hipFree(nodes); (void)hipFree(tris);
     (void)hipFree(c_node); (void)hipFree(t_node); (void)hipFree(nn); (void)hipFree(c_box); (void)hipFree(t_box); (void)hipFree(valid); (void)hipFree(pos);
-    (void)hipFree(node_counter); (void)hipFree(size_int); (void)hipFree(leaf_pos); (void)hipFree(node_first); (void)hipFree(node_depth);
+    (void)hipFree(size_int); (void)hipFree(leaf_pos); (void)hipFree(node_first); (void)hipFree(node_depth);
     (void)hipFree(dp); (void)hipFree(dp_arrive); (void)hipFree(order_pc);
     (void)hipFree(re_moves); (void)hipFree(re_lock); (void)hipFree(re_arrive); (void)hipFree(re_scalars); (void)hipFree(re_flags);
     (void)hipFree(side_int); (void)hipFree(side_leaf); (void)hipFree(scan_temp); (void)hipFree(work_a); (void)hipFree(work_b); (void)hipFree(counters);

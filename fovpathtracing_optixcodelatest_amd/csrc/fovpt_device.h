@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/fovpt.h"
 
 #define FOVPT_WAVE 64
@@ -209,10 +211,33 @@ struct BvhBuildResult {
 struct BvhSwitches { int use_ploc; float split_budget; int order_children, reinsert_rounds, verbose; };
 BvhSwitches fovpt_bvh_switches();
 
+// What every stage of a build left, for the test hook fovpt_debug_build (api_debug.hip): host copies of the build's own arrays,
+// taken before the build moves on.  n = build primitives (references), ni = n - 1 internal nodes of the binary tree.  A tiny
+// build (n <= FOVPT_LEAF_MAX) has no keys and no binary tree: only splits, boxes, bounds, vals_s, leaf_pos and nodes_pre.
+struct BvhBuildTrace {
+    int tiny = 0, splits = 0;                                 // splits: references were made (boxes come from k_split_emit)
+    float s_cut = 0.f;                                        // the bisection's cut length (0: no split budget)
+    std::vector<uint32_t> split_count, split_first, ref_prim; // per triangle (whenever the budget is on); per reference (splits only)
+    std::vector<float> boxes;                                 // 6 per build primitive: lo.xyz, hi.xyz
+    float cbounds[6] = {0, 0, 0, 0, 0, 0};                    // centroid bounds: min.xyz, max.xyz
+    std::vector<uint64_t> keys_s;
+    std::vector<uint32_t> vals_s;
+    int root = 0;                                             // the binary tree as PLOC or Karras left it
+    std::vector<int32_t> left0, right0;
+    std::vector<float> ibox0;
+    std::vector<uint32_t> round_end;                          // PLOC: internal nodes made up to and including each round
+    std::vector<int32_t> left1, right1;                       // ... and as the collapse saw it (after reinsertion)
+    std::vector<float> ibox1;
+    std::vector<uint32_t> size_int, node_first, leaf_pos;
+    std::vector<uint32_t> dp;                                 // 4 words per internal node: c1, c2, c3 (float bits), dec
+    std::vector<uint32_t> nodes_pre;                          // the wide nodes before k_order_children, 32 words each
+};
+
 // flat: 9 floats per triangle (v0,v1,v2), mesh_of_prim: mesh id per triangle.  All device pointers.
 // reinsert: rounds of reinsertion on the PLOC tree (0 = none, -1 = sw.reinsert_rounds).
+// trace: null for every production build; set, each stage's arrays are copied to the host (a synchronisation per stage).
 hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n, const BvhSwitches& sw,
-                            int reinsert, BvhBuildResult* out, char* err, size_t errlen);
+                            int reinsert, BvhBuildResult* out, char* err, size_t errlen, BvhBuildTrace* trace = nullptr);
 
 // cap = shard capacity (in items) of the radiance queues and of the shadow queue.
 // sel: 0 = all eight queue shards (a whole job); 1 / 2 = the first / second four (one of the two chains of a frame)

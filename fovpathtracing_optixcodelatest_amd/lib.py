@@ -18,7 +18,7 @@ EXPORTS = [
     "fovpt_synchronize", "fovpt_download", "fovpt_get_stats", "fovpt_reset_stats", "fovpt_stream",
     "fovpt_probe_build_cdf", "fovpt_camera_uvw", "fovpt_debug_math", "fovpt_debug_buffer", "fovpt_debug_trace",
     "fovpt_debug_probe_sample", "fovpt_debug_probe_eval", "fovpt_debug_bsdf", "fovpt_debug_tex2d", "fovpt_debug_resolve", "fovpt_debug_shade",
-    "fovpt_debug_generate",
+    "fovpt_debug_generate", "fovpt_debug_build",
     "fovpt_gather_plan", "fovpt_gather_pack", "fovpt_gather_unpack",
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
@@ -244,6 +244,7 @@ def load():
                                       C.POINTER(u32)]
     L.fovpt_debug_generate.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.DebugGenerateLaunch), C.POINTER(abi.DebugPass), C.POINTER(i32),
                                        C.POINTER(abi.DebugGenerateResult)]
+    L.fovpt_debug_build.argtypes = [vp, u32, vp, vp, C.POINTER(abi.DebugBuildSwitches), C.POINTER(abi.DebugBuildTrace)]
     _declare_loader(L)
     _declare_packet_host(L)
     for name in EXPORTS:

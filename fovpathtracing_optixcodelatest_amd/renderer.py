@@ -1123,6 +1123,43 @@ class SampleRenderer:
                                 vis=a["shadow_vis4"][:ns], occ=a["shadow_occ4"][:ns]),
                     next_found=int(R.next_found), shadow_found=int(R.shadow_found), counters_changed=int(R.counters_changed), cap=int(R.cap))
 
+    def debug_build(self, tri, mesh_of_prim=None, ploc=True, split_budget=0.0, reinsert_rounds=0, order_children=True):
+        """The production hierarchy build over `tri` (T, 9) float32 under explicit switches, and what every stage left -> dict of
+        the arrays and scalars of struct fovpt_debug_build_trace (include/fovpt.h), the arrays cut to the build's sizes; an array
+        its build did not make (no splits, a tiny build) is None.  Touches neither the scene nor the environment."""
+        tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
+        n = tri.shape[0]
+        mesh = None if mesh_of_prim is None else np.ascontiguousarray(mesh_of_prim, np.uint32).reshape(n)
+        sw = abi.DebugBuildSwitches(1 if ploc else 0, float(split_budget), int(reinsert_rounds), 1 if order_children else 0)
+        cap, rounds = int(n * (1.0 + float(split_budget))) + 1, 4097
+        ci = max(cap - 1, 1)
+        u32, i32, f32 = np.uint32, np.int32, np.float32
+        a = dict(split_count=np.zeros(n, u32), split_first=np.zeros(n, u32), ref_prim=np.zeros(cap, u32), boxes=np.zeros((cap, 6), f32),
+                 keys_s=np.zeros(cap, np.uint64), vals_s=np.zeros(cap, u32), left0=np.zeros(ci, i32), right0=np.zeros(ci, i32),
+                 ibox0=np.zeros((ci, 6), f32), round_end=np.zeros(rounds, u32), left1=np.zeros(ci, i32), right1=np.zeros(ci, i32),
+                 ibox1=np.zeros((ci, 6), f32), size_int=np.zeros(ci, u32), node_first=np.zeros(ci, u32), leaf_pos=np.zeros(cap, u32),
+                 dp=np.zeros((ci, 4), u32), nodes_pre=np.zeros((ci, 32), u32), nodes=np.zeros((ci, 32), u32), tris=np.zeros((cap, 12), u32))
+        T = abi.DebugBuildTrace()
+        for k, v in a.items():
+            setattr(T, k, v.ctypes.data)
+        T.cap_refs, T.cap_rounds = cap, rounds
+        self._check(self._L.fovpt_debug_build(self._ctx, n, tri.ctypes.data, mesh.ctypes.data if mesh is not None else None, C.byref(sw), C.byref(T)))
+        R, N = int(T.num_refs), int(T.num_nodes)
+        I = 0 if T.tiny else R - 1
+        size = dict(split_count=n if T.have_count else None, split_first=n if T.have_splits else None, ref_prim=R if T.have_splits else None,
+                    boxes=R, keys_s=None if T.tiny else R, vals_s=R, leaf_pos=R, round_end=int(T.num_rounds) if (ploc and not T.tiny) else None,
+                    nodes_pre=N, nodes=N, tris=R)
+        out = {}
+        for k, v in a.items():
+            m = size.get(k, None if T.tiny else I)
+            out[k] = None if m is None else v[:m].copy()
+        for k in ("num_refs", "tiny", "have_count", "have_splits", "root", "num_rounds", "num_nodes", "max_depth", "reinserted", "num_levels"):
+            out[k] = int(getattr(T, k))
+        out["s_cut"] = np.float32(T.s_cut)
+        out["cbounds"] = np.array(T.cbounds[:], np.float32)
+        out["level_first"] = [int(x) for x in T.level_first[:int(T.num_levels) + 1]]
+        return out
+
     def debug_resolve_passes(self, render=True, width=0, height=0):
         """The pass table of the frame a render() (or a launch(width, height)) of the current launch parameters would resolve:
         a list of abi.DebugPass.  Sample slot of (pass, launch index li, sample s) = slot_base + li * spp + s."""

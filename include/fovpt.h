@@ -1665,6 +1665,49 @@ typedef struct fovpt_debug_generate_result {
 } fovpt_debug_generate_result;
 int fovpt_debug_generate(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_debug_generate_launch* launch, fovpt_debug_pass* passes_out,
                          int* npass_out, fovpt_debug_generate_result* out);
+/* tests only: the production hierarchy build (the function fovpt_set_scene and every rebuild call) over n triangles the caller
+ * supplies (host array, 9 floats each; mesh_of_prim: a mesh id per triangle, NULL = all 0), under explicit switches -- nothing is
+ * read from the environment --, and what every stage of it left, so that splits, boxes, Morton keys, the sort, the binary tree,
+ * reinsertion, the collapse's dynamic programme, the emitted wide tree and the child order can each be held against a
+ * restatement, not only the rays a finished tree answers.  Needs no scene and leaves the context as it was.  Synchronises.
+ *
+ * Switches: use_ploc (0: the plain Karras tree), split_budget in [0, 2] (0: no spatial splits), reinsert_rounds >= 0 (PLOC only),
+ * order_children (0: keep the collapse's child order).
+ * The trace, arrays of the caller's (any may be NULL = not asked for).  R = num_refs, the build primitives: the triangles, or
+ * their references under splits; cap_refs (in) = the room of every per-reference array, R <= n * (1 + split_budget); when
+ * cap_refs < R the call sets num_refs, writes no array and returns FOVPT_E_INVALID.  I = R - 1 internal nodes of the binary
+ * tree, whose children are coded >= 0: internal node, < 0: ~(sorted position of a leaf).
+ *   split_count, split_first (n; written when split_budget > 0 and n > 4: have_count = 1), ref_prim (R; have_splits = 1 only),
+ *   boxes (R x 6: lo.xyz, hi.xyz), cbounds (the centroid bounds min.xyz, max.xyz), vals_s (R), leaf_pos (R), nodes_pre = the
+ *   wide nodes before the child order (num_nodes x 32 words), nodes and tris = the result (num_nodes x 32, R x 12 words),
+ *   level_first (num_levels + 1) -- always;
+ *   keys_s (R), left0 / right0 (I), ibox0 (I x 6), root, round_end (num_rounds <= cap_rounds (in) entries; PLOC only) = the
+ *   tree as PLOC or Karras left it, left1 / right1 / ibox1, size_int, node_first (I) = the tree the collapse saw, dp (I x 4
+ *   words: c1, c2, c3 as float bits, dec) -- unless tiny = 1 (R <= 4: one root with one leaf, no keys, no binary tree).       */
+typedef struct fovpt_debug_build_switches {
+    int32_t use_ploc;
+    float split_budget;
+    int32_t reinsert_rounds, order_children;
+} fovpt_debug_build_switches;
+typedef struct fovpt_debug_build_trace {
+    uint32_t *split_count, *split_first, *ref_prim;
+    float *boxes;
+    uint64_t *keys_s;
+    uint32_t *vals_s;
+    int32_t *left0, *right0;
+    float *ibox0;
+    uint32_t *round_end;
+    int32_t *left1, *right1;
+    float *ibox1;
+    uint32_t *size_int, *node_first, *leaf_pos, *dp, *nodes_pre, *nodes, *tris;
+    uint32_t cap_refs, cap_rounds;
+    uint32_t num_refs, tiny, have_count, have_splits, root, num_rounds, num_nodes, max_depth, reinserted, num_levels;
+    float s_cut;
+    float cbounds[6];
+    uint32_t level_first[65];
+} fovpt_debug_build_trace;
+int fovpt_debug_build(fovpt_ctx* ctx, uint32_t n, const float* tris9, const uint32_t* mesh_of_prim, const fovpt_debug_build_switches* switches,
+                      fovpt_debug_build_trace* trace);
 /* tests/diagnostics only: device address and size of an internal buffer ("sq_occ", "counters", "hit", "bvh_nodes", "bvh_tris"
  * -- the 48-byte triangle records of the hierarchy, stats.tri_bytes --, "scene_vertices" -- fovpt_update_vertices' vertex
  * array, once made --, "scene_vertices_prev" -- fovpt_temporal_motion's previous positions, once made --, "gbuffer_hit" -- the

@@ -100,7 +100,8 @@ def test_config_mirror_matches_the_header(tmp_path):
 def test_debug_hook_structs_mirror_the_header(tmp_path):
     """The structs of the test hooks (fovpt_debug_pass, fovpt_debug_shade_*, fovpt_debug_generate_*) member for member."""
     pairs = (("fovpt_debug_pass", abi.DebugPass), ("fovpt_debug_shade_launch", abi.DebugShadeLaunch), ("fovpt_debug_shade_result", abi.DebugShadeResult),
-             ("fovpt_debug_generate_launch", abi.DebugGenerateLaunch), ("fovpt_debug_generate_result", abi.DebugGenerateResult))
+             ("fovpt_debug_generate_launch", abi.DebugGenerateLaunch), ("fovpt_debug_generate_result", abi.DebugGenerateResult),
+             ("fovpt_debug_build_switches", abi.DebugBuildSwitches), ("fovpt_debug_build_trace", abi.DebugBuildTrace))
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
     for cname, mirror in pairs:
         src += 'printf("%%zu", sizeof(%s));' % cname + "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_) + 'printf("\\n");'
