@@ -180,6 +180,26 @@ class DebugShadeResult(C.Structure):
         ("next_found", C.c_uint32), ("shadow_found", C.c_uint32), ("counters_changed", C.c_uint32), ("cap", C.c_uint32)]
 
 
+DEBUG_TRACE_ALPHA = 0xffffffff                  # FOVPT_DEBUG_TRACE_ALPHA: a shadow record whose target is the slot's alpha
+DEBUG_TRACE_ITERS = 63                          # FOVPT_DEBUG_TRACE_ITERS: the iterations fovpt_debug_trace_queued may name
+
+
+class DebugTraceLaunch(C.Structure):
+    """struct fovpt_debug_trace_launch: host arrays of the caller's for the two ray sets, and the launch."""
+    _fields_ = [(k, C.c_void_p) for k in ("origins3", "dirs3", "slot", "target", "vis4", "occ4", "other_origins3", "other_dirs3", "other_slot",
+                                          "other_target", "other_vis4", "other_occ4")] + [
+        ("n", C.c_int32), ("n_other", C.c_int32), ("sel", C.c_uint32), ("both", C.c_uint32), ("it_closest", C.c_int32), ("it_shadow", C.c_int32),
+        ("grid_closest", C.c_int32), ("grid_shadow", C.c_int32), ("slots", C.c_uint32), ("q_count", C.c_uint32 * 8), ("sq_count", C.c_uint32 * 8),
+        ("other_q_count", C.c_uint32 * 8), ("other_sq_count", C.c_uint32 * 8), ("decoy", C.c_uint32 * 8)]
+
+
+class DebugTraceResult(C.Structure):
+    """struct fovpt_debug_trace_result: host arrays of the caller's, and what the call counted."""
+    _fields_ = [(k, C.c_void_p) for k in ("hit_place2", "hit4", "hit_prim", "cells4", "alpha4")] + [
+        ("stat_radiance", C.c_uint64), ("stat_shadow", C.c_uint64), ("stat_paths", C.c_uint64),
+        ("hit_found", C.c_uint32), ("counters_changed", C.c_uint32), ("queues_unchanged", C.c_uint32), ("cap", C.c_uint32)]
+
+
 class DebugGenerateLaunch(C.Structure):
     """struct fovpt_debug_generate_launch."""
     _fields_ = [("render", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32), ("row0", C.c_uint32), ("row1", C.c_uint32),

@@ -131,6 +131,187 @@ ProbePath debug_probe_path(const fovpt_ctx* c, const fovpt_probe& probe, int fla
     return pp;
 }
 
+static_assert(FOVPT_DEBUG_TRACE_ITERS == FOVPT_MAX_ITERS, "the iterations a traversal hook may name are the counter words there are");
+
+// One of the two ray sets of a traversal hook (the selected chain's, the other chain's) and where its rays lie: ray i of the
+// set is entry i - (the rays of the shards before) of the shard the counts put it in, in either queue
+struct TraceRays {
+    size_t n;
+    const float *o3, *d3;
+    const uint32_t *slot, *target;
+    const float *vis4, *occ4;
+    const uint32_t *q_count, *sq_count;
+};
+
+// What shard s of the six queue arrays holds for a traversal hook -- a[0 .. 6) = the radiance queue's o, d and the shadow queue's
+// o, d, vis, occ, `cap` entries each: the rays the counts put there, then the idle ray
+void trace_shard_image(const TraceRays* sets, int nsets, uint32_t s, uint32_t cap, const float* idle_o4, std::vector<float>* a)
+{
+    const float idle_d4[4] = {0.f, 1.f, 0.f, 0.f}, idle_vis4[4] = {3.f, 5.f, 7.f, 9.f}, idle_occ4[4] = {4.f, 6.f, 8.f, 10.f};
+    const float* const idle[6] = {idle_o4, idle_d4, idle_o4, idle_d4, idle_vis4, idle_occ4};       // (a shadow record's d.w: cell 0, as bits)
+    for (int k = 0; k < 6; k++) {
+        a[k].resize((size_t)cap * 4);
+        for (size_t e = 0; e < cap; e++) memcpy(&a[k][4 * e], idle[k], 16);
+    }
+    for (int t = 0; t < nsets; t++) {
+        const TraceRays& R = sets[t];
+        for (int shadow = 0; shadow < 2; shadow++) {
+            const uint32_t* count = shadow ? R.sq_count : R.q_count;
+            size_t i = 0;
+            for (uint32_t k = 0; k < s; k++) i += count[k];
+            for (uint32_t e = 0; e < count[s]; e++, i++) {
+                float* o = &a[shadow ? 2 : 0][4 * (size_t)e];
+                float* d = &a[shadow ? 3 : 1][4 * (size_t)e];
+                for (int k = 0; k < 3; k++) { o[k] = R.o3[3 * i + k]; d[k] = R.d3[3 * i + k]; }
+                memcpy(&o[3], &R.slot[i], 4);                            // origin.w = sample slot
+                d[3] = 0.f;
+                if (shadow) {
+                    memcpy(&d[3], &R.target[i], 4);                      // shadow record: direction.w = target cell of the slot
+                    memcpy(&a[4][4 * (size_t)e], &R.vis4[4 * i], 16);
+                    memcpy(&a[5][4 * (size_t)e], &R.occ4[4 * i], 16);
+                }
+            }
+        }
+    }
+}
+
+// The shared step of fovpt_debug_trace and fovpt_debug_trace_queued (include/fovpt.h has the contract)
+int trace_queued(fovpt_ctx* c, const fovpt_debug_trace_launch* in, fovpt_debug_trace_result* out, const char* who)
+{
+    if (!c || !in || !out || in->n < 0 || in->n_other < 0) return FOVPT_E_INVALID;
+    if (in->n && (!in->origins3 || !in->dirs3 || !in->slot || !in->target || !in->vis4 || !in->occ4)) return FOVPT_E_INVALID;
+    if (in->n_other && (!in->other_origins3 || !in->other_dirs3 || !in->other_slot || !in->other_target || !in->other_vis4 || !in->other_occ4)) return FOVPT_E_INVALID;
+    if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+    if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
+    const uint32_t sel = in->sel;
+    if (sel > 2u || ((in->n_other || in->both) && sel == 0u)) return fail(c, FOVPT_E_INVALID, "%s: sel %u with %d rays of another chain", who, sel, in->n_other);
+    if (in->it_closest < 0 || in->it_closest >= FOVPT_MAX_ITERS || in->it_shadow < 0 || in->it_shadow >= FOVPT_MAX_ITERS)
+        return fail(c, FOVPT_E_INVALID, "%s: iterations %d and %d", who, in->it_closest, in->it_shadow);
+    if (in->grid_closest < 0 || in->grid_closest > (1 << 20) || in->grid_shadow < 0 || in->grid_shadow > (1 << 20))
+        return fail(c, FOVPT_E_INVALID, "%s: grids %d and %d", who, in->grid_closest, in->grid_shadow);
+    const size_t n = (size_t)in->n, m = (size_t)in->n_other, N = n + m, D = (size_t)c->cfg.max_depth;
+    const size_t slots = in->slots ? (size_t)in->slots : (n ? n : 1u) * FOVPT_SHARDS;
+    const uint32_t cap = shard_capacity(slots);
+    const TraceRays sets[2] = {{n, in->origins3, in->dirs3, in->slot, in->target, in->vis4, in->occ4, in->q_count, in->sq_count},
+                               {m, in->other_origins3, in->other_dirs3, in->other_slot, in->other_target, in->other_vis4, in->other_occ4,
+                                in->other_q_count, in->other_sq_count}};
+    for (int t = 0; t < 2; t++) {
+        const TraceRays& R = sets[t];
+        uint64_t total[2] = {0, 0};
+        for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+            const bool selected = sel == 0u || (sel == 1u) == (s < 4u), mine = t == 0 ? selected : !selected;
+            if ((R.q_count[s] || R.sq_count[s]) && !mine) return fail(c, FOVPT_E_INVALID, "%s: rays in shard %u outside the selection %u", who, s, t == 0 ? sel : 3u - sel);
+            if (R.q_count[s] > cap || R.sq_count[s] > cap) return fail(c, FOVPT_E_INVALID, "%s: shard %u holds more than its capacity %u", who, s, cap);
+            total[0] += R.q_count[s]; total[1] += R.sq_count[s];
+        }
+        if (total[0] != R.n || total[1] != R.n)
+            return fail(c, FOVPT_E_INVALID, "%s: the shards hold %llu and %llu rays, n = %zu", who, (unsigned long long)total[0], (unsigned long long)total[1], R.n);
+        std::vector<uint8_t> seen(R.n, 0);
+        const size_t first = t == 0 ? 0 : n;
+        for (size_t i = 0; i < R.n; i++) {
+            const size_t k = (size_t)R.slot[i] - first;                  // (below `first`: wraps to a large number)
+            if (R.slot[i] < first || k >= R.n || seen[k]) return fail(c, FOVPT_E_INVALID, "%s: the slots are no permutation (ray %zu names slot %u)", who, i, R.slot[i]);
+            seen[k] = 1;
+            if (R.target[i] != FOVPT_DEBUG_TRACE_ALPHA && R.target[i] >= D) return fail(c, FOVPT_E_INVALID, "%s: ray %zu names cell %u of %zu", who, i, R.target[i], D);
+        }
+    }
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++)
+        if (in->decoy[s] > cap) return fail(c, FOVPT_E_INVALID, "%s: a decoy count above the capacity %u", who, cap);
+    if (!out->cells4 || !out->alpha4 || (N && (!out->hit_place2 || !out->hit4 || !out->hit_prim))) return FOVPT_E_INVALID;
+    // the state: the queues of a job of `slots` sample slots, the cells of all N + 1
+    StateSet* set = nullptr; uint32_t cap_state = 0;
+    { const int rc_ = debug_state(c, slots > N + 1 ? slots : N + 1, 1, set, cap_state); if (rc_) return rc_; }
+    StateSet& S = *set;
+    hipStream_t st = c->stream;
+    const size_t v = 16, qn = (size_t)cap * FOVPT_SHARDS;
+    const int fill = FOVPT_DEBUG_SHADE_FILL;
+    HIPCHK(c, hipMemsetAsync(S.s_hit.p, fill, qn * v, st));
+    HIPCHK(c, hipMemsetAsync(S.s_rad.p, fill, (N + 1) * v * D, st));
+    HIPCHK(c, hipMemsetAsync(S.s_alpha.p, fill, (N + 1) * v, st));
+    // the idle ray: from the middle of the scene's vertices, along +y, for the trap slot N
+    float idle_o4[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 3 && c->h_vtx.size() >= 3; k++) {
+        float lo = c->h_vtx[k], hi = lo;
+        for (size_t i = k; i < c->h_vtx.size(); i += 3) { lo = c->h_vtx[i] < lo ? c->h_vtx[i] : lo; hi = c->h_vtx[i] > hi ? c->h_vtx[i] : hi; }
+        idle_o4[k] = 0.5f * lo + 0.5f * hi;
+    }
+    const uint32_t trap = (uint32_t)N;
+    memcpy(&idle_o4[3], &trap, 4);
+    const DevBuf* const qbuf[6] = {&S.q_o[0], &S.q_d[0], &S.sq_o[0], &S.sq_d[0], &S.sq_vis[0], &S.sq_occ[0]};
+    std::vector<float> image[6];
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+        trace_shard_image(sets, m ? 2 : 1, s, cap, idle_o4, image);
+        for (int k = 0; k < 6; k++) HIPCHK(c, hipMemcpyAsync((char*)qbuf[k]->p + (size_t)s * cap * v, image[k].data(), (size_t)cap * v, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));                             // (the image is reused for the next shard)
+    }
+    // the counter words: the counts where the launches read them, the decoys in every word a neighbouring iteration would use
+    const int w_q = FOVPT_CNT_Q(in->it_closest), w_sq = FOVPT_CNT_SQ(in->it_shadow);
+    const int near[6] = {FOVPT_CNT_Q(in->it_closest - 1), FOVPT_CNT_Q(in->it_closest + 1), FOVPT_CNT_Q(in->it_shadow),
+                         FOVPT_CNT_SQ(in->it_shadow - 1), FOVPT_CNT_SQ(in->it_shadow + 1), FOVPT_CNT_SQ(in->it_closest)};
+    std::vector<uint32_t> was(cnt_words, 0u), cw;
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+        uint32_t* w = &was[(size_t)s * FOVPT_SHARD_STRIDE];
+        for (int k = 0; k < 6; k++) {
+            const bool radiance = k < 3;                                 // (it - 1 of iteration 0 names no word of its queue)
+            const int lo = radiance ? FOVPT_CNT_Q(0) : FOVPT_CNT_SQ(0), hi = lo + FOVPT_MAX_ITERS;
+            if (near[k] >= lo && near[k] <= hi) w[near[k]] = in->decoy[s];
+        }
+        w[w_q] = in->q_count[s] + in->other_q_count[s];
+        w[w_sq] = in->sq_count[s] + in->other_sq_count[s];
+    }
+    HIPCHK(c, put_counters(S, was, st));
+    Counters* cnt = (Counters*)S.counters.p;
+    unsigned long long stat0[3], stat1[3];
+    HIPCHK(c, hipMemcpyAsync(stat0, &cnt->stat_radiance, sizeof(stat0), hipMemcpyDeviceToHost, st));
+    // (under write_guides the path state carries the set's guide buffers, which ensure_state has made: k_traverse never reads them)
+    const PathState ps = path_state(c, S);
+    const RayQueue q = ray_queue(S, 0);
+    const ShadowQueue sq = shadow_queue(S, 0);
+    const SceneView sc = scene_view(c);
+    const int div = sel ? 2 : 1;                                         // a chain's launches get half the grids (run_job)
+    const int g_trace = in->grid_closest ? in->grid_closest : c->grid_trace / div, g_shadow = in->grid_shadow ? in->grid_shadow : c->grid_shadow / div;
+    for (int pass = 0; pass < (in->both ? 2 : 1); pass++) {
+        const uint32_t sel_now = pass == 0 ? sel : 3u - sel;
+        fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, in->it_closest, -1, g_trace, nullptr, sel_now);    // closest hit, as run_job launches it
+        fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, -1, in->it_shadow, g_shadow, nullptr, sel_now);    // occlusion, as run_job launches it
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> hit(qn * 4);
+    HIPCHK(c, hipMemcpyAsync(hit.data(), S.s_hit.p, qn * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out->cells4, S.s_rad.p, (N + 1) * v * D, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out->alpha4, S.s_alpha.p, (N + 1) * v, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(stat1, &cnt->stat_radiance, sizeof(stat1), hipMemcpyDeviceToHost, st));
+    { const int rc_ = take_counters(c, S, cw, st); if (rc_) return rc_; }
+    out->cap = cap;
+    out->stat_radiance = stat1[0] - stat0[0]; out->stat_shadow = stat1[1] - stat0[1]; out->stat_paths = stat1[2] - stat0[2];
+    out->counters_changed = counters_changed(cw, was, -1, -1);
+    // the product build never writes a queue
+    out->queues_unchanged = 1u;
+    std::vector<float> back((size_t)cap * 4);
+    for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
+        trace_shard_image(sets, m ? 2 : 1, s, cap, idle_o4, image);
+        for (int k = 0; k < 6; k++) {
+            HIPCHK(c, hipMemcpy(back.data(), (const char*)qbuf[k]->p + (size_t)s * cap * v, (size_t)cap * v, hipMemcpyDeviceToHost));
+            if (memcmp(back.data(), image[k].data(), (size_t)cap * v) != 0) out->queues_unchanged = 0u;
+        }
+    }
+    // the occupied entries of the hit buffer, and their primitives: leaf order -> global primitive id
+    float* const rec[1] = {out->hit4};
+    out->hit_found = occupied_entries(1, &hit, qn, fill, cap, N, out->hit_place2, rec);
+    std::vector<TriRec> tris(c->num_tris);
+    HIPCHK(c, hipMemcpy(tris.data(), c->tris, sizeof(TriRec) * (size_t)c->num_tris, hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < N && e < (size_t)out->hit_found; e++) {
+        uint32_t pos;
+        memcpy(&pos, &out->hit4[4 * e + 3], 4);
+        const bool miss = pos == 0xffffffffu;
+        const size_t tri = miss ? 0 : (size_t)pos / 3;               // pos: offset in 16-byte units, a record is 48 bytes
+        if (!miss && (pos % 3u != 0u || tri >= tris.size()))
+            return fail(c, FOVPT_E_DEVICE, "%s: the hit record at (%u, %u) points at 16-byte unit %u", who, out->hit_place2[2 * e], out->hit_place2[2 * e + 1], pos);
+        out->hit_prim[e] = miss ? 0xffffffffu : tris[tri].prim;
+    }
+    return FOVPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -171,63 +352,37 @@ int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* d
     if (!c || n < 0 || (n && (!origins3 || !dirs3))) return FOVPT_E_INVALID;
     if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_trace without a scene");
     if (n == 0) return FOVPT_OK;
-    const size_t slots = (size_t)n * FOVPT_SHARDS;                  // all rays go to shard 0: its capacity must hold them
-    StateSet* set = nullptr; uint32_t cap = 0;
-    { const int rc_ = debug_state(c, slots, 1, set, cap); if (rc_) return rc_; }
-    StateSet& S = *set;
-    hipStream_t st = c->stream;
-    std::vector<float> o4((size_t)n * 4), d4((size_t)n * 4), d4s((size_t)n * 4), vis((size_t)n * 4, 0.f), occ((size_t)n * 4, 0.f);
-    for (int i = 0; i < n; i++) {
-        const uint32_t slot = (uint32_t)i, cell = 0u;
-        for (int k = 0; k < 3; k++) { o4[4 * (size_t)i + k] = origins3[3 * (size_t)i + k]; d4[4 * (size_t)i + k] = d4s[4 * (size_t)i + k] = dirs3[3 * (size_t)i + k]; }
-        memcpy(&o4[4 * (size_t)i + 3], &slot, 4);                   // origin.w = sample slot
-        d4[4 * (size_t)i + 3] = 0.f;
-        memcpy(&d4s[4 * (size_t)i + 3], &cell, 4);                  // shadow record: direction.w = target cell of the slot
-        vis[4 * (size_t)i] = 1.f; occ[4 * (size_t)i] = 2.f;         // what store_shadow leaves in the cell: 1 visible, 2 occluded
-    }
-    const size_t bytes = (size_t)n * 16;
-    HIPCHK(c, hipMemcpyAsync(S.q_o[0].p, o4.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.q_d[0].p, d4.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_o[0].p, o4.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_d[0].p, d4s.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_vis[0].p, vis.data(), bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.sq_occ[0].p, occ.data(), bytes, hipMemcpyHostToDevice, st));
-    // queue sizes: n entries in shard 0 of the radiance queue of iteration 0 and of the shadow queue of iteration 0
-    std::vector<uint32_t> cw(cnt_words, 0u);
-    cw[FOVPT_CNT_Q(0)] = cw[FOVPT_CNT_SQ(0)] = (uint32_t)n;
-    HIPCHK(c, put_counters(S, cw, st));
-    Counters* cnt = (Counters*)S.counters.p;
-    // (under write_guides the path state carries the set's guide buffers, which ensure_state has made: k_traverse never reads them)
-    const PathState ps = path_state(c, S);
-    const RayQueue q = ray_queue(S, 0);
-    const ShadowQueue sq = shadow_queue(S, 0);
-    const SceneView sc = scene_view(c);
-    fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, 0, -1, c->grid_trace);        // closest hit, as run_job launches it
-    fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, -1, 0, c->grid_shadow);       // occlusion, as run_job launches it
-    HIPCHK(c, hipGetLastError());
-    std::vector<float> hit((size_t)n * 4), cell((size_t)n * 4 * (size_t)c->cfg.max_depth);
-    HIPCHK(c, hipMemcpyAsync(hit.data(), S.s_hit.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(cell.data(), S.s_rad.p, bytes * (size_t)c->cfg.max_depth, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    std::vector<TriRec> tris(c->num_tris);                           // leaf order -> global primitive id
-    HIPCHK(c, hipMemcpy(tris.data(), c->tris, sizeof(TriRec) * (size_t)c->num_tris, hipMemcpyDeviceToHost));
-    // leave the set as a job expects to find it (resolve zeroes the queue counters at the end of every job)
-    HIPCHK(c, hipMemset(S.counters.p, 0, cnt_bytes));
-    for (int i = 0; i < n; i++) {
-        uint32_t pos;
-        memcpy(&pos, &hit[4 * (size_t)i + 3], 4);
-        const bool miss = pos == 0xffffffffu;
-        const size_t tri = miss ? 0 : (size_t)pos / 3;               // pos: offset in 16-byte units, a record is 48 bytes
-        if (!miss && (pos % 3u != 0u || tri >= tris.size())) return fail(c, FOVPT_E_DEVICE, "hit record %d points at 16-byte unit %u", i, pos);
-        if (prim_out) prim_out[i] = miss ? 0xffffffffu : tris[tri].prim;
-        if (tuv_out3) for (int k = 0; k < 3; k++) tuv_out3[3 * (size_t)i + k] = hit[4 * (size_t)i + k];
+    // fovpt_debug_trace_queued with every ray in shard 0 of both queues, slot = index, cell 0, iteration 0 and the production grids
+    const size_t un = (size_t)n, D = (size_t)c->cfg.max_depth;
+    std::vector<uint32_t> slot(un), target(un, 0u), place(2 * un), prim(un);
+    std::vector<float> vis(un * 4, 0.f), occ(un * 4, 0.f), hit(un * 4), cells((un + 1) * 4 * D), alpha((un + 1) * 4);
+    for (size_t i = 0; i < un; i++) { slot[i] = (uint32_t)i; vis[4 * i] = 1.f; occ[4 * i] = 2.f; }      // what store_shadow leaves in the cell: 1 visible, 2 occluded
+    fovpt_debug_trace_launch L;
+    memset(&L, 0, sizeof(L));
+    L.origins3 = origins3; L.dirs3 = dirs3; L.slot = slot.data(); L.target = target.data(); L.vis4 = vis.data(); L.occ4 = occ.data();
+    L.n = n; L.q_count[0] = L.sq_count[0] = (uint32_t)n;
+    fovpt_debug_trace_result R;
+    memset(&R, 0, sizeof(R));
+    R.hit_place2 = place.data(); R.hit4 = hit.data(); R.hit_prim = prim.data(); R.cells4 = cells.data(); R.alpha4 = alpha.data();
+    { const int rc_ = trace_queued(c, &L, &R, "fovpt_debug_trace"); if (rc_) return rc_; }
+    if (R.hit_found != (uint32_t)n) return fail(c, FOVPT_E_DEVICE, "fovpt_debug_trace: %u hit records for %d rays", R.hit_found, n);
+    for (size_t i = 0; i < un; i++) {
+        if (place[2 * i] != 0u || place[2 * i + 1] != (uint32_t)i) return fail(c, FOVPT_E_DEVICE, "fovpt_debug_trace: a hit record at (%u, %u)", place[2 * i], place[2 * i + 1]);
+        if (prim_out) prim_out[i] = prim[i];
+        if (tuv_out3) for (int k = 0; k < 3; k++) tuv_out3[3 * i + k] = hit[4 * i + k];
         if (occluded_out) {
-            const float v = cell[4 * (size_t)i * (size_t)c->cfg.max_depth];
-            if (v != 1.f && v != 2.f) return fail(c, FOVPT_E_DEVICE, "shadow ray %d left %g in its cell", i, (double)v);
+            const float v = cells[4 * i * D];
+            if (v != 1.f && v != 2.f) return fail(c, FOVPT_E_DEVICE, "shadow ray %zu left %g in its cell", i, (double)v);
             occluded_out[i] = v == 2.f ? 1 : 0;
         }
     }
     return FOVPT_OK;
+}
+
+// test hook: the PRODUCTION traversal launches on a caller-made queue state (include/fovpt.h), and everything they left
+int fovpt_debug_trace_queued(fovpt_ctx* c, const fovpt_debug_trace_launch* launch, fovpt_debug_trace_result* out)
+{
+    return trace_queued(c, launch, out, "fovpt_debug_trace_queued");
 }
 
 // test hook: the PRODUCTION hierarchy build -- fovpt_build_lbvh itself, the function fovpt_set_scene and the rebuilds call -- over

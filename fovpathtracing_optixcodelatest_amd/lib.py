@@ -18,7 +18,7 @@ EXPORTS = [
     "fovpt_synchronize", "fovpt_download", "fovpt_get_stats", "fovpt_reset_stats", "fovpt_stream",
     "fovpt_probe_build_cdf", "fovpt_camera_uvw", "fovpt_debug_math", "fovpt_debug_buffer", "fovpt_debug_trace",
     "fovpt_debug_probe_sample", "fovpt_debug_probe_eval", "fovpt_debug_bsdf", "fovpt_debug_tex2d", "fovpt_debug_resolve", "fovpt_debug_shade",
-    "fovpt_debug_generate", "fovpt_debug_build",
+    "fovpt_debug_generate", "fovpt_debug_build", "fovpt_debug_trace_queued",
     "fovpt_gather_plan", "fovpt_gather_pack", "fovpt_gather_unpack",
     "fovpt_denoise_defaults", "fovpt_denoise", "fovpt_denoise_buffers",
     "fovpt_gbuffer", "fovpt_reconstruct_defaults", "fovpt_reconstruct", "fovpt_reconstruct_buffers",
@@ -235,6 +235,7 @@ def load():
     L.fovpt_debug_math.argtypes = [vp, i32, vp, vp, vp, sz]
     L.fovpt_debug_buffer.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(sz)]
     L.fovpt_debug_trace.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.fovpt_debug_trace_queued.argtypes = [vp, C.POINTER(abi.DebugTraceLaunch), C.POINTER(abi.DebugTraceResult)]
     L.fovpt_debug_probe_sample.argtypes = [vp, C.POINTER(abi.Probe), i32, i32, vp, vp, vp, C.POINTER(i32)]
     L.fovpt_debug_probe_eval.argtypes = [vp, C.POINTER(abi.Probe), i32, i32, vp, vp, C.POINTER(i32)]
     L.fovpt_debug_bsdf.argtypes = [vp, C.POINTER(abi.Material), i32, vp, vp, vp, vp, vp, vp, vp, vp]

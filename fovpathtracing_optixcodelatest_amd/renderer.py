@@ -1040,6 +1040,53 @@ class SampleRenderer:
         self._check(self._L.fovpt_debug_trace(self._ctx, n, o.ctypes.data, d.ctypes.data, prim.ctypes.data, tuv.ctypes.data, occ.ctypes.data))
         return prim, tuv, occ
 
+    def debug_trace_queued(self, rays, q_count, sq_count, sel=0, it_closest=0, it_shadow=0, grid_closest=0, grid_shadow=0, slots=0,
+                           decoy=None, other=None, both=False):
+        """The production traversal launches (closest hit, then occlusion) on a queue state laid out here (include/fovpt.h,
+        fovpt_debug_trace_queued).  rays = dict(o (n, 3), d (n, 3), slot (n,), target (n,), vis (n, 4), occ (n, 4)); q_count /
+        sq_count (8,) = the rays per shard of the radiance / shadow queue; other = the other chain's rays with q_count and
+        sq_count among its keys (sel != 0 only); both: run the other chain's launches behind this one's.
+        -> dict: cap; hit = dict(shard, pos, rec (k, 4) float32, prim) of the hit-buffer entries found, in ascending physical
+        order; hit_found; cells (N + 1, max_depth, 4) and alpha (N + 1, 4) float32 of all N = n + n_other slots and the trap
+        slot, the fill pattern abi.DEBUG_SHADE_FILL where nothing was written; stat_radiance, stat_shadow, stat_paths (what the
+        launches added); counters_changed; queues_unchanged."""
+        L = abi.DebugTraceLaunch()
+        keep = []                                                   # (the arrays the struct points into)
+
+        def put(prefix, r):
+            o = np.ascontiguousarray(r["o"], np.float32).reshape(-1, 3)
+            k = o.shape[0]
+            a = dict(origins3=o, dirs3=np.ascontiguousarray(r["d"], np.float32).reshape(k, 3),
+                     slot=np.ascontiguousarray(r["slot"], np.uint32).reshape(k), target=np.ascontiguousarray(r["target"], np.uint32).reshape(k),
+                     vis4=np.ascontiguousarray(r["vis"], np.float32).reshape(k, 4), occ4=np.ascontiguousarray(r["occ"], np.float32).reshape(k, 4))
+            for key, arr in a.items():
+                keep.append(arr)
+                setattr(L, prefix + key, arr.ctypes.data)
+            return k
+
+        n = put("", rays)
+        m = put("other_", other) if other is not None else 0
+        L.n, L.n_other, L.sel, L.both = n, m, sel, 1 if both else 0
+        L.it_closest, L.it_shadow, L.grid_closest, L.grid_shadow, L.slots = it_closest, it_shadow, grid_closest, grid_shadow, slots
+        for s in range(8):
+            L.q_count[s], L.sq_count[s] = int(q_count[s]), int(sq_count[s])
+            L.other_q_count[s] = int(other["q_count"][s]) if other is not None else 0
+            L.other_sq_count[s] = int(other["sq_count"][s]) if other is not None else 0
+            L.decoy[s] = int(decoy[s]) if decoy is not None else 0
+        N, depth = n + m, self.config.max_depth
+        a = dict(hit_place2=np.empty((N, 2), np.uint32), hit4=np.empty((N, 4), np.float32), hit_prim=np.empty(N, np.uint32),
+                 cells4=np.empty((N + 1, depth, 4), np.float32), alpha4=np.empty((N + 1, 4), np.float32))
+        R = abi.DebugTraceResult()
+        for k, v in a.items():
+            v.view(np.uint8)[...] = abi.DEBUG_SHADE_FILL
+            setattr(R, k, v.ctypes.data)
+        self._check(self._L.fovpt_debug_trace_queued(self._ctx, C.byref(L), C.byref(R)))
+        k = min(int(R.hit_found), N)
+        return dict(cap=int(R.cap), hit=dict(shard=a["hit_place2"][:k, 0], pos=a["hit_place2"][:k, 1], rec=a["hit4"][:k], prim=a["hit_prim"][:k]),
+                    hit_found=int(R.hit_found), cells=a["cells4"], alpha=a["alpha4"], stat_radiance=int(R.stat_radiance),
+                    stat_shadow=int(R.stat_shadow), stat_paths=int(R.stat_paths), counters_changed=int(R.counters_changed),
+                    queues_unchanged=int(R.queues_unchanged))
+
     def debug_probe_sample(self, r12, plain=False, probe=None):
         """The production probe_sample with its two random numbers given (pairs in [0, 0.999999]) on `probe` (default: the launch
         parameters' probe), searched the way a launch would, or plainly -> dict(row, col, dir, color, pdf, path): path = the

@@ -1550,6 +1550,58 @@ int fovpt_debug_math(fovpt_ctx* ctx, int op, const float* a, const float* b, flo
  * hit -> global primitive id (0xffffffff = miss) and (t, u, v); occlusion ray (deviceProgram.cu:224-248) -> 0 / 1.
  * Any output may be NULL.  Synchronises.                                                                              */
 int fovpt_debug_trace(fovpt_ctx* ctx, int n, const float* origins3, const float* dirs3, uint32_t* prim_out, float* tuv_out3, uint8_t* occluded_out);
+/* tests only: the production traversal launches -- closest hit, then occlusion, each as a job launches it -- on a queue state the
+ * caller lays out, and everything they left, so that the kernel's QUEUE side (which shards a launch reads, the map from a queue
+ * index to its place, where a hit record and a shadow result go, which counter words are read) can be held against the oracle
+ * ray by ray.  fovpt_debug_trace is this call with every ray in shard 0, slot = index, cell 0 and the production grids.
+ *
+ * In (host arrays): n rays (origins3, dirs3); per ray its sample slot (slot: a permutation of 0 .. n-1), the target of its shadow
+ * record (target: a radiance cell 0 .. max_depth-1, or FOVPT_DEBUG_TRACE_ALPHA: the slot's alpha) and the two records of the
+ * shadow queue (vis4, occ4: four floats each; the launch stores .xyz of one of them and +0).  Every ray is in BOTH queues, at the
+ * same index: q_count[s] / sq_count[s] = how many of the rays, taken in order, lie in shard s of the radiance / the shadow queue.
+ * sel = 0 (all eight shards) or 1 / 2 (the first / second four: a chain of a job); with sel != 0 the other four shards may hold
+ * the other chain's live rays, other_* (n_other of them, slots a permutation of n .. n+n_other-1), whose counts stand in the same
+ * counter words; both != 0 runs the other chain's two launches behind this one's, on the same stream and the same state.
+ * it_closest / it_shadow = the iterations whose counter words hold the counts (0 .. FOVPT_DEBUG_TRACE_ITERS-1); decoy[s] is
+ * written into every other word of shard s that a neighbouring iteration would use -- radiance it_closest +- 1 and it_shadow,
+ * shadow it_shadow +- 1 and it_closest.  grid_closest / grid_shadow = the launcher's grid argument (units of 256 threads), 0 =
+ * what a job of this sel uses.  slots sizes the queues as a job of that many sample slots would (0 = 8 * max(n, 1)): cap = the
+ * capacity of a shard.
+ * Before the launch the hit buffer (8 * cap entries) and the cells and alpha of n + n_other + 1 sample slots hold the byte
+ * FOVPT_DEBUG_SHADE_FILL, and every queue entry no ray occupies holds one fixed ray (from the middle of the scene along +y) whose
+ * shadow record names cell 0 of the last slot, n + n_other: the trap slot no ray owns.
+ * Out (host arrays of the caller's): the hit-buffer entries that differ from the fill, wherever they lie -- hit_found of them,
+ * the first n + n_other in ascending physical order as (shard, position) in hit_place2, the record in hit4 and its global
+ * primitive id (0xffffffff = miss) in hit_prim; cells4 = max_depth float4 per slot and alpha4 = one, of all n + n_other + 1
+ * slots; the rise of the three ray statistics; counters_changed = queue counter words that are not what was written;
+ * queues_unchanged = 1 when all six queue arrays are byte for byte what was uploaded; cap.
+ * Errors: FOVPT_E_NO_SCENE, FOVPT_E_INVALID (counts that do not sum to n or n_other, exceed cap or lie outside their selection;
+ * slots that are no permutation; a target, an iteration, a grid or sel out of range), FOVPT_E_DEVICE (a hit record that names
+ * no triangle).  Synchronises.                                                                                             */
+#define FOVPT_DEBUG_TRACE_ALPHA 0xffffffffu
+#define FOVPT_DEBUG_TRACE_ITERS 63
+typedef struct fovpt_debug_trace_launch {
+    const float *origins3, *dirs3;
+    const uint32_t *slot, *target;
+    const float *vis4, *occ4;
+    const float *other_origins3, *other_dirs3;
+    const uint32_t *other_slot, *other_target;
+    const float *other_vis4, *other_occ4;
+    int32_t n, n_other;
+    uint32_t sel, both;
+    int32_t it_closest, it_shadow, grid_closest, grid_shadow;
+    uint32_t slots;
+    uint32_t q_count[8], sq_count[8], other_q_count[8], other_sq_count[8], decoy[8];
+} fovpt_debug_trace_launch;
+typedef struct fovpt_debug_trace_result {
+    uint32_t *hit_place2;
+    float *hit4;
+    uint32_t *hit_prim;
+    float *cells4, *alpha4;
+    uint64_t stat_radiance, stat_shadow, stat_paths;
+    uint32_t hit_found, counters_changed, queues_unchanged, cap;
+} fovpt_debug_trace_result;
+int fovpt_debug_trace_queued(fovpt_ctx* ctx, const fovpt_debug_trace_launch* launch, fovpt_debug_trace_result* out);
 /* tests only: the device functions of a shaded hit on n inputs the caller chose (host arrays), so that the probe lookup, the
  * Disney BSDF and the texture fetch can be compared with the oracle input by input.  All synchronise; any output may be NULL.
  *

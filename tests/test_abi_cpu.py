@@ -98,10 +98,12 @@ def test_config_mirror_matches_the_header(tmp_path):
 
 
 def test_debug_hook_structs_mirror_the_header(tmp_path):
-    """The structs of the test hooks (fovpt_debug_pass, fovpt_debug_shade_*, fovpt_debug_generate_*) member for member."""
+    """The structs of the test hooks (fovpt_debug_pass, fovpt_debug_shade_*, fovpt_debug_generate_*, fovpt_debug_trace_*) member for
+    member."""
     pairs = (("fovpt_debug_pass", abi.DebugPass), ("fovpt_debug_shade_launch", abi.DebugShadeLaunch), ("fovpt_debug_shade_result", abi.DebugShadeResult),
              ("fovpt_debug_generate_launch", abi.DebugGenerateLaunch), ("fovpt_debug_generate_result", abi.DebugGenerateResult),
-             ("fovpt_debug_build_switches", abi.DebugBuildSwitches), ("fovpt_debug_build_trace", abi.DebugBuildTrace))
+             ("fovpt_debug_build_switches", abi.DebugBuildSwitches), ("fovpt_debug_build_trace", abi.DebugBuildTrace),
+             ("fovpt_debug_trace_launch", abi.DebugTraceLaunch), ("fovpt_debug_trace_result", abi.DebugTraceResult))
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
     for cname, mirror in pairs:
         src += 'printf("%%zu", sizeof(%s));' % cname + "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, f[0]) for f in mirror._fields_) + 'printf("\\n");'
@@ -115,6 +117,16 @@ def test_debug_hook_structs_mirror_the_header(tmp_path):
         assert got[0] == C.sizeof(mirror), cname
         assert got[1:] == [getattr(mirror, f[0]).offset for f in mirror._fields_], cname
     assert C.sizeof(abi.DebugGenerateLaunch) == 36 and C.sizeof(abi.DebugGenerateResult) == 120 and abi.DebugGenerateResult.count.offset == 56
+    assert C.sizeof(abi.DebugTraceLaunch) == 296 and abi.DebugTraceLaunch.n.offset == 96 and abi.DebugTraceLaunch.decoy.offset == 260
+    assert C.sizeof(abi.DebugTraceResult) == 80 and abi.DebugTraceResult.stat_radiance.offset == 40
+
+
+def test_debug_trace_constants_mirror_the_header(tmp_path):
+    """FOVPT_DEBUG_TRACE_ALPHA and FOVPT_DEBUG_TRACE_ITERS as the header compiled by gcc has them."""
+    src = '#include <stdio.h>\n#include "fovpt.h"\nint main(void){printf("%u %d", FOVPT_DEBUG_TRACE_ALPHA, FOVPT_DEBUG_TRACE_ITERS);return 0;}\n'
+    exe = str(tmp_path / "trace_constants")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    assert [int(x) for x in subprocess.check_output([exe]).split()] == [abi.DEBUG_TRACE_ALPHA, abi.DEBUG_TRACE_ITERS]
 
 
 def test_default_config_is_the_shipped_reference(so):
