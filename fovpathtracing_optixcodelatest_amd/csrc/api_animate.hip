@@ -165,7 +165,7 @@ int enqueue_refit(fovpt_ctx* c);
 
 void free_rebuild_result(fovpt_ctx::RebuildDone& d)
 {
-    if (d.br.nodes) (void)hipFree(d.br.nodes);
+    free_hierarchy(d.br);
     if (d.partial) (void)hipFree(d.partial);
     d = fovpt_ctx::RebuildDone();
 }

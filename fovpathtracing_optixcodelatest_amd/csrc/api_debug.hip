@@ -408,7 +408,7 @@ int fovpt_debug_build(fovpt_ctx* c, uint32_t n, const float* tris9, const uint32
     char err[256];
     const hipError_t be = fovpt_build_lbvh(c->stream, (const float*)d_flat.p, (const uint32_t*)d_mesh.p, n, bs, sw->reinsert_rounds, &br, err, sizeof(err), &T);
     if (be != hipSuccess) return fail(c, FOVPT_E_DEVICE, "fovpt_debug_build: %s", err);
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } free_nodes{br.nodes};          // (one allocation: nodes, then triangles)
+    struct Free { BvhBuildResult& b; ~Free() { free_hierarchy(b); } } free_nodes{br};     // (on every return below)
     const size_t R = br.num_refs, I = R - 1, N = br.num_nodes;
     out->num_refs = br.num_refs;
     if (R > out->cap_refs) return fail(c, FOVPT_E_INVALID, "fovpt_debug_build: %zu references, room for %u", R, out->cap_refs);

@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "fovpt_device.h"
+#include "fovpt_scratch.h"
 
 namespace {
 
@@ -872,7 +873,329 @@ __global__ void k_split_emit(const float* __restrict__ flat, uint32_t n, const u
     }
 }
 
-#define HC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(err, errlen, "%s failed: %s", #x, hipGetErrorString(e_)); goto fail; } } while (0)
+// ---- the host side: the state the stages of a build share, and one function per stage ----------------------------------------
+struct Build {
+    hipStream_t st; const float* flat; const uint32_t* mesh_of_prim; uint32_t n_prims;      // what the caller asked for
+    BvhSwitches sw; int reinsert_rounds; char* err; size_t errlen; BvhBuildTrace* trace;
+    Scratch mem;                               // every device array below and in the stages is its (fovpt_scratch.h)
+    uint32_t n = 0, ni = 1;                    // build primitives (triangles, or references when splits are on); internal nodes
+    Box* boxes = nullptr; uint64_t* keys_s = nullptr;
+    uint32_t *ref_prim = nullptr, *bounds = nullptr, *vals_s = nullptr;      // ref_prim: null unless references were made
+    TreeView T = {}; int root = 0;             // the binary tree: internal nodes 0 .. n-2, of which `root` is the root
+    uint32_t *size_int = nullptr, *node_first = nullptr, *leaf_pos = nullptr;
+    unsigned char *side_int = nullptr, *side_leaf = nullptr;                 // PLOC only
+    unsigned short* sweep_done = nullptr;      // sweep_up's flags: the sweep that finished each node, + 1 (reinsertion's to allocate)
+    DpCost* dp = nullptr; BvhNode4* nodes = nullptr; TriRec* tris = nullptr;
+    uint32_t* stats = nullptr;                 // [0] depth, [1] wide nodes emitted
+    std::vector<uint32_t> round_end;           // PLOC: internal nodes created up to and including each round
+    std::vector<uint32_t> level_first;         // wide tree: index of the first node of every level (+ the node count at the end)
+    bool tree_changed = false;                 // reinsertion moved something
+};
+constexpr int B = 256;
+const uint32_t EMPTY_BOUNDS[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+// a stage returns false with the text in S.err; ARRAY: `count` elements of TYPE from the build's owner, or the stage fails there
+#define HC_(x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(S.err, S.errlen, "%s failed: %s", what, hipGetErrorString(e_)); return false; } } while (0)
+#define HC(x) HC_(x, #x)
+#define ARRAY(TYPE, count) ({ TYPE* p_; HC_(S.mem.array(&p_, (count)), "hipMalloc(" #TYPE " x " #count ")"); p_; })
+// `kernel` with one thread per item, in blocks of B
+template <class K, class... A> void launch(const Build& S, K kernel, uint32_t items, A... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((items + B - 1) / B), dim3(B), 0, S.st, args...);
+}
+// trace only (fovpt_debug_build): `count` elements of a stage's device array into a host vector, once the stage is through
+template <class V> bool grab(Build& S, V& dst, const void* src, size_t count)
+{
+    dst.resize(count);
+    if (count == 0 || (hipMemcpyAsync(dst.data(), src, count * sizeof(dst[0]), hipMemcpyDeviceToHost, S.st) == hipSuccess && hipStreamSynchronize(S.st) == hipSuccess)) return true;
+    snprintf(S.err, S.errlen, "copying a stage of the build out failed: %s", hipGetErrorString(hipGetLastError()));
+    return false;
+}
+
+// Split references: the cut length by bisection, the count per triangle, its scan, the references' boxes.  Leaves S.n, and with
+// references S.boxes, S.ref_prim and their centroid bounds.  Its own arrays do not outlive it: the trace gets them from here.
+bool split_references(Build& S)
+{
+    const uint32_t n_prims = S.n = S.n_prims;                   // (S.n changes once references are made)
+    S.bounds = ARRAY(uint32_t, 6);
+    if (!(S.sw.split_budget > 0.f && n_prims > FOVPT_LEAF_MAX)) return true;
+    // how long may a box be before it is cut: bisection on s for (1 + budget) x n_prims references
+    unsigned long long h_total = 0, want = (unsigned long long)((double)n_prims * (1.0 + (double)S.sw.split_budget));
+    unsigned long long* total = ARRAY(unsigned long long, 1);
+    HC(hipMemcpyAsync(S.bounds, EMPTY_BOUNDS, sizeof(EMPTY_BOUNDS), hipMemcpyHostToDevice, S.st));
+    launch(S, k_scene_extent, n_prims, S.flat, n_prims, S.bounds);
+    uint32_t hb[6];
+    HC(hipMemcpyAsync(hb, S.bounds, sizeof(hb), hipMemcpyDeviceToHost, S.st)); HC(hipStreamSynchronize(S.st));
+    float hi_s = 0.f;
+    for (int a = 0; a < 3; a++) hi_s = fmaxf(hi_s, ord2f(hb[3 + a]) - ord2f(hb[a]));
+    float lo_s = hi_s * 1e-7f, s_cut = hi_s;
+    for (int it = 0; it < 24 && hi_s > 0.f; it++) {
+        const float mid = sqrtf(lo_s * hi_s);                   // the extents span orders of magnitude
+        HC(hipMemsetAsync(total, 0, 8, S.st));
+        launch(S, k_split_count, n_prims, S.flat, n_prims, mid, (uint32_t*)nullptr, total);
+        HC(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, S.st)); HC(hipStreamSynchronize(S.st));
+        if (h_total > want) lo_s = mid; else { hi_s = mid; s_cut = mid; }       // (the count falls as s grows)
+    }
+    uint32_t *count = ARRAY(uint32_t, n_prims), *first = ARRAY(uint32_t, n_prims);
+    HC(hipMemsetAsync(total, 0, 8, S.st));
+    launch(S, k_split_count, n_prims, S.flat, n_prims, s_cut, count, total);
+    HC(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, S.st)); HC(hipStreamSynchronize(S.st));
+    if (S.trace) { S.trace->s_cut = s_cut; if (!grab(S, S.trace->split_count, count, n_prims)) return false; }
+    if (!(h_total > n_prims && h_total < (1ull << 27))) return true;        // no reference to add: the triangles' own boxes
+    size_t tb = 0;
+    HC(rocprim::exclusive_scan(nullptr, tb, count, first, 0u, (size_t)n_prims, rocprim::plus<uint32_t>(), S.st));
+    char* temp = ARRAY(char, tb);
+    HC(rocprim::exclusive_scan(temp, tb, count, first, 0u, (size_t)n_prims, rocprim::plus<uint32_t>(), S.st));
+    S.n = (uint32_t)h_total;
+    S.boxes = ARRAY(Box, S.n); S.ref_prim = ARRAY(uint32_t, S.n);
+    HC(hipMemcpyAsync(S.bounds, EMPTY_BOUNDS, sizeof(EMPTY_BOUNDS), hipMemcpyHostToDevice, S.st));
+    launch(S, k_split_emit, n_prims, S.flat, n_prims, count, first, S.boxes, S.ref_prim, S.bounds);
+    HC(hipGetLastError());
+    if (S.trace) { S.trace->splits = 1; if (!grab(S, S.trace->split_first, first, n_prims) || !grab(S, S.trace->ref_prim, S.ref_prim, S.n)) return false; }
+    return true;
+}
+// Boxes and centroid bounds of the build primitives (unless the references brought theirs), and the arrays of the binary and the
+// wide tree, which every later stage reaches through S
+bool boxes_and_bounds(Build& S)
+{
+    const uint32_t n = S.n, ni = n > 1 ? n - 1 : 1;
+    const bool have_boxes = S.boxes != nullptr;
+    TreeView& T = S.T;
+    if (!have_boxes) S.boxes = ARRAY(Box, n);
+    T.ibox = ARRAY(Box, ni); S.stats = ARRAY(uint32_t, 2);
+    S.keys_s = ARRAY(uint64_t, n); S.vals_s = ARRAY(uint32_t, n);
+    T.left = ARRAY(int, ni); T.right = ARRAY(int, ni); T.parent_int = ARRAY(int, ni); T.parent_leaf = ARRAY(int, n);
+    S.size_int = ARRAY(uint32_t, ni); S.leaf_pos = ARRAY(uint32_t, n); S.node_first = ARRAY(uint32_t, ni);
+    S.nodes = ARRAY(BvhNode4, ni); S.tris = ARRAY(TriRec, n);              // (a wide node replaces >= 1 binary node)
+    S.ni = ni; T.n = (int)n; T.boxes = S.boxes; T.vals = S.vals_s;
+    HC(hipMemsetAsync(S.stats, 0, 8, S.st));
+    if (!have_boxes) {
+        HC(hipMemcpyAsync(S.bounds, EMPTY_BOUNDS, sizeof(EMPTY_BOUNDS), hipMemcpyHostToDevice, S.st));
+        launch(S, k_tri_bounds, n, S.flat, n, S.boxes, S.bounds);
+    }
+    return true;
+}
+// at most FOVPT_LEAF_MAX primitives: the root alone, with one leaf
+bool build_tiny(Build& S)
+{
+    hipLaunchKernelGGL(k_iota, dim3(1), dim3(64), 0, S.st, S.vals_s, S.n);
+    hipLaunchKernelGGL(k_emit_tiny, dim3(1), dim3(1), 0, S.st, (int)S.n, S.boxes, S.nodes, S.stats, S.leaf_pos);
+    return true;
+}
+// Morton keys of the boxes' centres and the sort of (key, primitive): S.keys_s, S.vals_s
+bool morton_sort(Build& S)
+{
+    uint64_t* keys = ARRAY(uint64_t, S.n); uint32_t* vals = ARRAY(uint32_t, S.n);
+    size_t temp_bytes = 0;
+    launch(S, k_morton, S.n, S.boxes, S.n, S.bounds, keys, vals);
+    HC(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, S.keys_s, vals, S.vals_s, (size_t)S.n, 0, 63, S.st));
+    char* temp = ARRAY(char, temp_bytes);
+    HC(rocprim::radix_sort_pairs(temp, temp_bytes, keys, S.keys_s, vals, S.vals_s, (size_t)S.n, 0, 63, S.st));
+    return true;
+}
+// FOVPT_BVH=lbvh: the Karras radix tree (its root is node 0), its boxes bottom-up, sizes and positions from the nodes' key ranges
+bool karras_tree(Build& S)
+{
+    const TreeView& T = S.T;
+    uint32_t* arrive = ARRAY(uint32_t, S.ni);
+    int *rfirst = ARRAY(int, S.ni), *rlast = ARRAY(int, S.ni);
+    HC(hipMemsetAsync(arrive, 0, 4ull * S.ni, S.st));
+    launch(S, k_hierarchy, S.ni, S.keys_s, T.n, T.left, T.right, T.parent_int, T.parent_leaf, rfirst, rlast);
+    launch(S, k_refit, S.n, S.boxes, S.vals_s, T.n, T.left, T.right, T.parent_int, T.parent_leaf, T.ibox, arrive);
+    launch(S, k_lbvh_generic, S.n, T.n, rfirst, rlast, S.size_int, S.node_first, S.leaf_pos);
+    return true;
+}
+// PLOC: rounds of nearest-neighbour search, mutual pairs, scan and merge until one cluster is left; S.round_end
+bool ploc_tree(Build& S)
+{
+    const TreeView& T = S.T;
+    const uint32_t n = S.n;
+    int *c_node = ARRAY(int, n), *t_node = ARRAY(int, n), *nn = ARRAY(int, n);
+    Box *c_box = ARRAY(Box, n), *t_box = ARRAY(Box, n);
+    uint32_t *valid = ARRAY(uint32_t, n), *pos = ARRAY(uint32_t, n);
+    S.side_int = ARRAY(unsigned char, S.ni); S.side_leaf = ARRAY(unsigned char, n);
+    size_t scan_bytes = 0;
+    HC(hipMemsetAsync(S.side_int, 0, S.ni, S.st));
+    HC(rocprim::exclusive_scan(nullptr, scan_bytes, valid, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), S.st));
+    char* scan_temp = ARRAY(char, scan_bytes);
+    launch(S, k_ploc_init, n, (int)n, S.boxes, S.vals_s, c_node, c_box);
+    uint32_t m = n, made = 0, last_pos = 0, last_valid = 0;
+    for (int force = 0, rounds = 0; m > 1;) {
+        launch(S, k_ploc_nn, m, (int)m, force, c_box, nn);
+        launch(S, k_ploc_mark, m, (int)m, nn, valid);
+        HC(rocprim::exclusive_scan(scan_temp, scan_bytes, valid, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), S.st));
+        launch(S, k_ploc_merge, m, (int)m, (int)made, c_node, c_box, nn, pos, T.left, T.right, T.parent_int, T.parent_leaf, S.side_int, S.side_leaf,
+               T.ibox, S.size_int, t_node, t_box);
+        HC(hipMemcpyAsync(&last_pos, pos + (m - 1), 4, hipMemcpyDeviceToHost, S.st));
+        HC(hipMemcpyAsync(&last_valid, valid + (m - 1), 4, hipMemcpyDeviceToHost, S.st));
+        HC(hipStreamSynchronize(S.st));
+        { int* tn = c_node; c_node = t_node; t_node = tn; Box* tb = c_box; c_box = t_box; t_box = tb; }
+        const uint32_t m2 = last_pos + last_valid;
+        made += m - m2;                                // every pair drops one cluster and makes one node
+        S.round_end.push_back(made);
+        // (Almost) no mutual pair this round -- coincident geometry: among equal boxes everybody picks the first
+        // candidate of its window and one pair merges per round -- so the next round pairs neighbours.
+        force = ((uint64_t)(m - m2) * 64u < m) ? 1 : 0;
+        m = m2;
+        if (++rounds > 4096) { snprintf(S.err, S.errlen, "PLOC did not converge"); return false; }
+    }
+    S.root = (int)n - 2;                               // the last merge created the root
+    return true;
+}
+// bottom-up sweeps (k_sweep_up) until the root is finished: mode 0 sums the internal nodes' areas into *cost, mode 1 runs the collapse's programme
+bool sweep_up(Build& S, int mode, float* cost)
+{
+    unsigned short* done = S.sweep_done;
+    if (hipMemsetAsync(done, 0, 2ull * S.ni, S.st) != hipSuccess) { snprintf(S.err, S.errlen, "hipMemsetAsync failed (sweep flags)"); return false; }
+    for (uint32_t sweep = 0; sweep < 65000u;) {
+        for (int k = 0; k < 16; k++, sweep++) {
+            if (mode == 0) launch(S, k_sweep_up<0>, S.ni, S.T, sweep, done, S.size_int, S.side_int, S.side_leaf, cost, (DpCost*)nullptr);
+            else launch(S, k_sweep_up<1>, S.ni, S.T, sweep, done, S.size_int, S.side_int, S.side_leaf, (float*)nullptr, S.dp);
+        }
+        unsigned short root_done = 0;
+        if (hipMemcpyAsync(&root_done, done + (S.ni - 1u), 2, hipMemcpyDeviceToHost, S.st) != hipSuccess || hipStreamSynchronize(S.st) != hipSuccess) {
+            snprintf(S.err, S.errlen, "bottom-up sweep failed: %s", hipGetErrorString(hipGetLastError()));
+            return false;
+        }
+        if (root_done) return true;
+    }
+    snprintf(S.err, S.errlen, "bottom-up sweeps did not reach the root");
+    return false;
+}
+// Reinsertion rounds on the PLOC tree (see k_reinsert_find) for as long as a round lowers the cost; S.tree_changed
+bool reinsert_rounds(Build& S)
+{
+    const TreeView& T = S.T;
+    const uint32_t n = S.n, nall = 2 * n - 1;
+    if (!(S.reinsert_rounds > 0 && n > 16)) return true;
+    Move* moves = ARRAY(Move, nall); unsigned long long* lock = ARRAY(unsigned long long, nall);
+    S.sweep_done = ARRAY(unsigned short, S.ni);
+    uint32_t* scalars = ARRAY(uint32_t, 4);                    // [0] moves applied, [1] sum of internal areas (float), [2] candidates
+    unsigned char* flags = ARRAY(unsigned char, 2ull * nall);  // [0, nall): a surviving move moves the node; [nall, 2 nall): the move yields
+    float cost_prev = 0.f;                     // the cost of the tree as PLOC left it (what the first round's gain is measured against)
+    HC(hipMemsetAsync(scalars, 0, 16, S.st));
+    if (!sweep_up(S, 0, (float*)(scalars + 1))) return false;
+    HC(hipMemcpyAsync(&cost_prev, scalars + 1, 4, hipMemcpyDeviceToHost, S.st)); HC(hipStreamSynchronize(S.st));
+    if (S.sw.verbose) fprintf(stderr, "[fovpt bvh] PLOC tree: sum of internal areas %.6g\n", (double)cost_prev);
+    for (int round = 0; round < S.reinsert_rounds; round++) {
+        uint32_t applied = 0, candidates = 0; float cost = 0.f;
+        launch(S, k_reinsert_find, nall, T, (int)n - 2, moves, 0u, 1u);
+        HC(hipMemsetAsync(lock, 0, 8ull * nall, S.st));
+        HC(hipMemsetAsync(flags, 0, 2ull * nall, S.st));
+        HC(hipMemsetAsync(scalars, 0, 16, S.st));
+        launch(S, k_reinsert_lock, nall, T, moves, lock, scalars);
+        launch(S, k_reinsert_check, nall, T, moves, lock, flags);
+        launch(S, k_reinsert_check2, nall, T, moves, lock, flags, flags + nall, scalars);
+        launch(S, k_reinsert_apply, nall, T, moves, flags + nall);
+        if (!sweep_up(S, 0, (float*)(scalars + 1))) return false;
+        HC(hipMemcpyAsync(&applied, scalars, 4, hipMemcpyDeviceToHost, S.st));
+        HC(hipMemcpyAsync(&cost, scalars + 1, 4, hipMemcpyDeviceToHost, S.st));
+        HC(hipMemcpyAsync(&candidates, scalars + 2, 4, hipMemcpyDeviceToHost, S.st));
+        HC(hipStreamSynchronize(S.st)); HC(hipGetLastError());
+        S.tree_changed = S.tree_changed || applied > 0;
+        if (S.sw.verbose) fprintf(stderr, "[fovpt bvh] reinsertion round %d: %u of %u candidate moves, sum of internal areas %.6g\n", round, applied, candidates, (double)cost);
+        if (applied == 0 || !(cost_prev - cost > FOVPT_REINSERT_STOP * cost_prev)) break;      // (nothing much left to gain)
+        cost_prev = cost;
+    }
+    return true;
+}
+// PLOC: subtree sizes and sides to depth-first positions (S.leaf_pos, S.node_first)
+bool dfs_offsets(Build& S)
+{
+    const TreeView& T = S.T;
+    uint32_t* node_depth = ARRAY(uint32_t, S.ni);
+    launch(S, k_dfs_offsets, 2 * S.n - 1, T.n, T.left, T.parent_int, T.parent_leaf, S.side_int, S.side_leaf, S.size_int, S.leaf_pos, S.node_first, node_depth);
+    return true;
+}
+// The costs of the 2 -> 4 collapse, bottom-up, into S.dp: one programme (dp_node) under the driver the tree allows
+bool collapse_costs(Build& S)
+{
+    const TreeView& T = S.T;
+    S.dp = ARRAY(DpCost, S.ni);
+    if (S.sw.use_ploc && !S.tree_changed) {
+        uint32_t first = 0;                    // the PLOC tree as it was made: a round's nodes have their children in earlier rounds
+        for (uint32_t end : S.round_end) {
+            if (end > first) launch(S, k_dp_range, end - first, (int)first, (int)(end - first), S.boxes, S.vals_s, T.left, T.right, S.size_int, T.ibox, S.dp);
+            first = end;
+        }
+    } else if (S.sw.use_ploc) {
+        return sweep_up(S, 1, nullptr);        // a reinserted tree: the same programme in bottom-up sweeps
+    } else {
+        uint32_t* arrive = ARRAY(uint32_t, S.ni);                  // the Karras tree: the second arrival at a node computes it
+        HC(hipMemsetAsync(arrive, 0, 4ull * S.ni, S.st));
+        launch(S, k_dp_collapse, S.n, T.n, S.boxes, S.vals_s, T.left, T.right, T.parent_int, T.parent_leaf, S.size_int, T.ibox, S.dp, arrive);
+    }
+    return true;
+}
+// The wide tree, one launch per level, breadth-first from the root: S.nodes, S.level_first
+bool collapse_levels(Build& S)
+{
+    const TreeView& T = S.T;
+    uint32_t* counters = ARRAY(uint32_t, 2);
+    Work4 *work_a = ARRAY(Work4, S.ni), *work_b = ARRAY(Work4, S.ni);
+    uint32_t h_counters[2] = {1, 0}, nwork = 1;
+    Work4 w0; w0.node = S.root; w0.out = 0; w0.depth = 0;
+    HC(hipMemcpyAsync(work_a, &w0, sizeof(w0), hipMemcpyHostToDevice, S.st));
+    HC(hipMemcpyAsync(counters, h_counters, 8, hipMemcpyHostToDevice, S.st));
+    S.level_first.assign({0u, 1u});            // the root is node 0; the nodes of level L + 1 are allocated by the launch of level L
+    for (int levels = 0; nwork > 0;) {
+        launch(S, k_collapse4, nwork, (int)nwork, work_a, work_b, counters, T.left, T.right, S.size_int, S.node_first, S.leaf_pos, S.boxes, S.vals_s,
+               T.ibox, S.dp, S.nodes, S.stats);
+        HC(hipMemcpyAsync(h_counters, counters, 8, hipMemcpyDeviceToHost, S.st)); HC(hipStreamSynchronize(S.st));
+        nwork = h_counters[1];
+        if (nwork > 0) S.level_first.push_back(h_counters[0]);
+        h_counters[1] = 0;
+        HC(hipMemcpyAsync(counters + 1, &h_counters[1], 4, hipMemcpyHostToDevice, S.st));
+        Work4* t = work_a; work_a = work_b; work_b = t;
+        if (++levels > 4096) { snprintf(S.err, S.errlen, "BVH collapse did not terminate"); return false; }
+    }
+    return true;
+}
+// The triangle records in depth-first leaf order; then the children of every wide node in the order that ends occlusion rays
+// soonest, one launch per level, deepest first.  The trace gets the nodes as they were in between.
+bool records_and_child_order(Build& S)
+{
+    const std::vector<uint32_t>& lf = S.level_first;
+    const uint32_t total = lf.size() >= 2 ? lf.back() : 1u;
+    launch(S, k_emit_tris_generic, S.n, S.flat, S.mesh_of_prim, S.vals_s, S.ref_prim, S.leaf_pos, S.n, S.tris);
+    HC(hipGetLastError());
+    if (S.trace && !grab(S, S.trace->nodes_pre, S.nodes, 32ull * total)) return false;
+    if (!(S.sw.order_children && lf.size() >= 2)) return true;
+    float2* pc = ARRAY(float2, total);
+    for (size_t L = lf.size() - 1; L-- > 0;) {
+        const uint32_t first = lf[L], count = lf[L + 1] - first;
+        if (count) launch(S, k_order_children, count, first, count, S.nodes, S.tris, pc);
+    }
+    HC(hipGetLastError());
+    return true;
+}
+// The hierarchy that stays: ONE allocation, the nodes actually emitted (the build array is sized for the binary tree, ~8 x as
+// many) followed by the triangles, so the traversal reaches both through one base register and a 32-bit offset, and the build's
+// slack goes back to the allocator.
+bool pack_result(Build& S, BvhBuildResult* out)
+{
+    uint32_t h_stats[2] = {0, 0};
+    HC(hipMemcpyAsync(h_stats, S.stats, 8, hipMemcpyDeviceToHost, S.st)); HC(hipStreamSynchronize(S.st));
+    const size_t node_bytes = sizeof(BvhNode4) * (size_t)h_stats[1], tri_bytes = sizeof(TriRec) * (size_t)S.n;
+    const size_t tri_off = (node_bytes + 255) & ~(size_t)255;
+    char* scene = ARRAY(char, tri_off + tri_bytes + 64);          // + slack: a lane may fetch 16 bytes past its record
+    if (hipMemcpyAsync(scene, S.nodes, node_bytes, hipMemcpyDeviceToDevice, S.st) != hipSuccess
+        || hipMemcpyAsync(scene + tri_off, S.tris, tri_bytes, hipMemcpyDeviceToDevice, S.st) != hipSuccess
+        || hipMemsetAsync(scene + tri_off + tri_bytes, 0, 64, S.st) != hipSuccess
+        || hipStreamSynchronize(S.st) != hipSuccess) {
+        snprintf(S.err, S.errlen, "copying the hierarchy failed");
+        return false;
+    }
+    S.mem.keep(scene);                                            // the caller's from here (free_hierarchy)
+    out->nodes = (BvhNode4*)scene; out->tris = (TriRec*)(scene + tri_off);          // tris is INSIDE the nodes allocation
+    out->num_nodes = h_stats[1]; out->num_refs = S.n; out->max_depth = h_stats[0]; out->reinserted = S.tree_changed ? 1u : 0u;
+    out->node_bytes = node_bytes; out->tri_bytes = tri_bytes;
+    // the levels of the wide tree, for the refit (refit.hip); a tiny scene is its root alone
+    std::vector<uint32_t>& lf = S.level_first;
+    if (lf.size() < 2) lf.assign({0u, 1u});
+    out->num_levels = lf.size() - 1 <= FOVPT_BVH_MAX_LEVELS ? (uint32_t)(lf.size() - 1) : 0u;
+    for (uint32_t L = 0; out->num_levels && L <= out->num_levels; L++) out->level_first[L] = lf[L];
+    return true;
+}
 
 }  // namespace
 
@@ -893,363 +1216,40 @@ BvhSwitches fovpt_bvh_switches()
     return sw;
 }
 
+// The stages in order; with a trace (fovpt_debug_build only), what each left is copied out before the next one runs
 hipError_t fovpt_build_lbvh(hipStream_t st, const float* flat, const uint32_t* mesh_of_prim, uint32_t n_prims, const BvhSwitches& sw,
-                            int reinsert, BvhBuildResult* out, char* err, size_t errlen, BvhBuildTrace* trace)
+                            int reinsert, BvhBuildResult* out, char* err, size_t errlen, BvhBuildTrace* tr)
 {
-    const int use_ploc = sw.use_ploc;
-    const float split_budget = sw.split_budget;
-    uint32_t n = n_prims;                      // build primitives: triangles, or references of triangles when splits are on
-    uint32_t *ref_prim = nullptr, *split_cnt = nullptr, *split_first = nullptr;
-    unsigned long long* split_total = nullptr;
-    void* split_temp = nullptr;
-    Box *boxes = nullptr, *ibox = nullptr;
-    uint32_t *bounds = nullptr, *vals = nullptr, *vals_s = nullptr, *arrive = nullptr, *stats = nullptr;
-    uint64_t *keys = nullptr, *keys_s = nullptr;
-    int *left = nullptr, *right = nullptr, *parent_int = nullptr, *parent_leaf = nullptr, *rfirst = nullptr, *rlast = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
-    // PLOC state
-    int *c_node = nullptr, *t_node = nullptr, *nn = nullptr;
-    Box *c_box = nullptr, *t_box = nullptr;
-    uint32_t *valid = nullptr, *pos = nullptr, *size_int = nullptr, *leaf_pos = nullptr, *node_first = nullptr, *node_depth = nullptr;
-    unsigned char *side_int = nullptr, *side_leaf = nullptr;
-    void* scan_temp = nullptr;
-    size_t scan_bytes = 0;
-    // collapse state
-    Work4 *work_a = nullptr, *work_b = nullptr;
-    DpCost* dp = nullptr;
-    std::vector<uint32_t> round_end;           // PLOC: internal nodes created up to and including each round
-    std::vector<uint32_t> level_first;         // wide tree: index of the first node of every level (+ the node count at the end)
-    const bool order_children = sw.order_children != 0;
-    float2* order_pc = nullptr;
-    const int reinsert_rounds = reinsert >= 0 ? reinsert : sw.reinsert_rounds;
-    const bool verbose = sw.verbose != 0;
-    bool tree_changed = false;
-    Move* re_moves = nullptr;
-    unsigned long long* re_lock = nullptr;
-    uint32_t *re_arrive = nullptr, *re_scalars = nullptr;      // re_scalars: [0] moves applied, [1] sum of internal areas (float), [2] candidates
-    unsigned char* re_flags = nullptr;                         // [0, nall): the node is moved by a surviving move; [nall, 2 nall): the move yields
-    uint32_t* dp_arrive = nullptr;
-    uint32_t* counters = nullptr;
-    BvhNode4* nodes = nullptr;
-    TriRec* tris = nullptr;
-    const int B = 256;
-    uint32_t ni = 1, gn = 1, gi = 1;           // (assigned once the number of build primitives is known)
-    bool have_boxes = false;
-    uint32_t h_bounds[6];
-    uint32_t h_stats[2] = {0, 0};
-    uint32_t h_counters[2] = {1, 0};
-    hipError_t rc = hipSuccess;
+#define STAGE(x) do { if (!(x)) return hipErrorUnknown; } while (0)
+    Build S{st, flat, mesh_of_prim, n_prims, sw, reinsert >= 0 ? reinsert : sw.reinsert_rounds, err, errlen, tr};
+    const TreeView& T = S.T;
     err[0] = 0;
-    // bottom-up sweeps over the binary tree until the root is finished (k_sweep_up); false + err on failure
-    auto sweep_up = [&](int mode, const TreeView& T, float* cost) -> bool {
-        const uint32_t nint = (uint32_t)T.n - 1u, g = (nint + 255u) / 256u;
-        if (!re_arrive && hipMalloc(&re_arrive, 2ull * nint) != hipSuccess) { snprintf(err, errlen, "hipMalloc failed (sweep flags)"); return false; }
-        if (hipMemsetAsync(re_arrive, 0, 2ull * nint, st) != hipSuccess) { snprintf(err, errlen, "hipMemsetAsync failed (sweep flags)"); return false; }
-        unsigned short* done = (unsigned short*)re_arrive;
-        for (uint32_t sweep = 0; sweep < 65000u;) {
-            for (int k = 0; k < 16; k++, sweep++) {
-                if (mode == 0) hipLaunchKernelGGL(k_sweep_up<0>, dim3(g), dim3(256), 0, st, T, sweep, done, size_int, side_int, side_leaf, cost, (DpCost*)nullptr);
-                else hipLaunchKernelGGL(k_sweep_up<1>, dim3(g), dim3(256), 0, st, T, sweep, done, size_int, side_int, side_leaf, (float*)nullptr, dp);
-            }
-            unsigned short root_done = 0;
-            if (hipMemcpyAsync(&root_done, done + (nint - 1u), 2, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                snprintf(err, errlen, "bottom-up sweep failed: %s", hipGetErrorString(hipGetLastError()));
-                return false;
-            }
-            if (root_done) return true;
-        }
-        snprintf(err, errlen, "bottom-up sweeps did not reach the root");
-        return false;
-    };
-    // trace only (fovpt_debug_build): `count` elements of a stage's device array into a host vector, once the stage is through
-    auto grab = [&](auto& dst, const void* src, size_t count) -> bool {
-        dst.resize(count);
-        if (count == 0) return true;
-        if (hipMemcpyAsync(dst.data(), src, count * sizeof(dst[0]), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            snprintf(err, errlen, "copying a stage of the build out failed: %s", hipGetErrorString(hipGetLastError()));
-            return false;
-        }
-        return true;
-    };
-    for (int a = 0; a < 3; a++) { h_bounds[a] = 0xffffffffu; h_bounds[3 + a] = 0u; }
-    HC(hipMalloc(&bounds, 6 * 4));
-    if (split_budget > 0.f && n_prims > FOVPT_LEAF_MAX) {
-        // how long may a box be before it is cut: bisection on s for (1 + budget) x n_prims references
-        const uint32_t gp = (n_prims + B - 1) / B;
-        unsigned long long h_total = 0, want = (unsigned long long)((double)n_prims * (1.0 + (double)split_budget));
-        HC(hipMalloc(&split_total, 8));
-        HC(hipMemcpyAsync(bounds, h_bounds, sizeof(h_bounds), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_scene_extent, dim3(gp), dim3(B), 0, st, flat, n_prims, bounds);
-        uint32_t hb[6];
-        HC(hipMemcpyAsync(hb, bounds, sizeof(hb), hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-        float hi_s = 0.f;
-        for (int a = 0; a < 3; a++) hi_s = fmaxf(hi_s, ord2f(hb[3 + a]) - ord2f(hb[a]));
-        float lo_s = hi_s * 1e-7f, s_cut = hi_s;
-        for (int it = 0; it < 24 && hi_s > 0.f; it++) {
-            const float mid = sqrtf(lo_s * hi_s);                   // the extents span orders of magnitude
-            HC(hipMemsetAsync(split_total, 0, 8, st));
-            hipLaunchKernelGGL(k_split_count, dim3(gp), dim3(B), 0, st, flat, n_prims, mid, (uint32_t*)nullptr, split_total);
-            HC(hipMemcpyAsync(&h_total, split_total, 8, hipMemcpyDeviceToHost, st));
-            HC(hipStreamSynchronize(st));
-            if (h_total > want) lo_s = mid; else { hi_s = mid; s_cut = mid; }       // (the count falls as s grows)
-        }
-        HC(hipMalloc(&split_cnt, 4ull * n_prims)); HC(hipMalloc(&split_first, 4ull * n_prims));
-        HC(hipMemsetAsync(split_total, 0, 8, st));
-        hipLaunchKernelGGL(k_split_count, dim3(gp), dim3(B), 0, st, flat, n_prims, s_cut, split_cnt, split_total);
-        HC(hipMemcpyAsync(&h_total, split_total, 8, hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-        if (trace) { trace->s_cut = s_cut; if (!grab(trace->split_count, split_cnt, n_prims)) goto fail; }
-        if (h_total > n_prims && h_total < (1ull << 27)) {
-            size_t tb = 0;
-            HC(rocprim::exclusive_scan(nullptr, tb, split_cnt, split_first, 0u, (size_t)n_prims, rocprim::plus<uint32_t>(), st));
-            HC(hipMalloc(&split_temp, tb));
-            HC(rocprim::exclusive_scan(split_temp, tb, split_cnt, split_first, 0u, (size_t)n_prims, rocprim::plus<uint32_t>(), st));
-            n = (uint32_t)h_total;
-            HC(hipMalloc(&boxes, sizeof(Box) * n));
-            HC(hipMalloc(&ref_prim, 4ull * n));
-            HC(hipMemcpyAsync(bounds, h_bounds, sizeof(h_bounds), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_split_emit, dim3(gp), dim3(B), 0, st, flat, n_prims, split_cnt, split_first, boxes, ref_prim, bounds);
-            HC(hipGetLastError());
-            have_boxes = true;
-            if (trace) { trace->splits = 1; if (!grab(trace->split_first, split_first, n_prims) || !grab(trace->ref_prim, ref_prim, n)) goto fail; }
-        }
-    }
-    ni = n > 1 ? n - 1 : 1;
-    gn = (n + B - 1) / B; gi = (ni + B - 1) / B;
-
-    if (!have_boxes) HC(hipMalloc(&boxes, sizeof(Box) * n));
-    HC(hipMalloc(&ibox, sizeof(Box) * ni));
-    HC(hipMalloc(&stats, 2 * 4));
-    HC(hipMalloc(&counters, 2 * 4));
-    HC(hipMalloc(&keys, 8ull * n)); HC(hipMalloc(&keys_s, 8ull * n));
-    HC(hipMalloc(&vals, 4ull * n)); HC(hipMalloc(&vals_s, 4ull * n));
-    HC(hipMalloc(&left, 4ull * ni)); HC(hipMalloc(&right, 4ull * ni));
-    HC(hipMalloc(&parent_int, 4ull * ni)); HC(hipMalloc(&parent_leaf, 4ull * n));
-    HC(hipMalloc(&size_int, 4ull * ni)); HC(hipMalloc(&leaf_pos, 4ull * n)); HC(hipMalloc(&node_first, 4ull * ni));
-    HC(hipMalloc(&nodes, sizeof(BvhNode4) * ni));              // a wide node replaces >= 1 binary node
-    HC(hipMalloc(&tris, sizeof(TriRec) * n));
-    HC(hipMemsetAsync(stats, 0, 8, st));
-    if (!have_boxes) {
-        HC(hipMemcpyAsync(bounds, h_bounds, sizeof(h_bounds), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_tri_bounds, dim3(gn), dim3(B), 0, st, flat, n, boxes, bounds);
-    }
-    if (trace) {
+    STAGE(split_references(S));
+    STAGE(boxes_and_bounds(S));
+    const uint32_t n = S.n, ni = S.ni;
+    if (tr) {
         std::vector<uint32_t> hb;
-        if (!grab(hb, bounds, 6) || !grab(trace->boxes, boxes, 6ull * n)) goto fail;
-        for (int a = 0; a < 6; a++) trace->cbounds[a] = ord2f(hb[a]);
-        trace->tiny = n <= FOVPT_LEAF_MAX ? 1 : 0;
+        STAGE(grab(S, hb, S.bounds, 6) && grab(S, tr->boxes, S.boxes, 6ull * n));
+        for (int a = 0; a < 6; a++) tr->cbounds[a] = ord2f(hb[a]);
+        tr->tiny = n <= FOVPT_LEAF_MAX ? 1 : 0;
     }
     if (n <= FOVPT_LEAF_MAX) {
-        hipLaunchKernelGGL(k_iota, dim3(1), dim3(64), 0, st, vals_s, n);
-        hipLaunchKernelGGL(k_emit_tiny, dim3(1), dim3(1), 0, st, (int)n, boxes, nodes, stats, leaf_pos);
-        if (trace && (!grab(trace->vals_s, vals_s, n) || !grab(trace->leaf_pos, leaf_pos, n))) goto fail;
+        STAGE(build_tiny(S));
+        if (tr) STAGE(grab(S, tr->vals_s, S.vals_s, n) && grab(S, tr->leaf_pos, S.leaf_pos, n));
     } else {
-        int root = 0;
-        hipLaunchKernelGGL(k_morton, dim3(gn), dim3(B), 0, st, boxes, n, bounds, keys, vals);
-        HC(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, keys_s, vals, vals_s, (size_t)n, 0, 63, st));
-        HC(hipMalloc(&temp, temp_bytes));
-        HC(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_s, vals, vals_s, (size_t)n, 0, 63, st));
-        if (trace && (!grab(trace->keys_s, keys_s, n) || !grab(trace->vals_s, vals_s, n))) goto fail;
-        if (!use_ploc) {
-            HC(hipMalloc(&arrive, 4ull * ni));
-            HC(hipMalloc(&rfirst, 4ull * ni)); HC(hipMalloc(&rlast, 4ull * ni));
-            HC(hipMemsetAsync(arrive, 0, 4ull * ni, st));
-            hipLaunchKernelGGL(k_hierarchy, dim3(gi), dim3(B), 0, st, keys_s, (int)n, left, right, parent_int, parent_leaf, rfirst, rlast);
-            hipLaunchKernelGGL(k_refit, dim3(gn), dim3(B), 0, st, boxes, vals_s, (int)n, left, right, parent_int, parent_leaf, ibox, arrive);
-            hipLaunchKernelGGL(k_lbvh_generic, dim3(gn), dim3(B), 0, st, (int)n, rfirst, rlast, size_int, node_first, leaf_pos);
-            root = 0;
-            if (trace) {
-                trace->root = root;
-                if (!grab(trace->left0, left, ni) || !grab(trace->right0, right, ni) || !grab(trace->ibox0, ibox, 6ull * ni)) goto fail;
-            }
-        } else {
-            HC(hipMalloc(&c_node, 4ull * n)); HC(hipMalloc(&t_node, 4ull * n)); HC(hipMalloc(&nn, 4ull * n));
-            HC(hipMalloc(&c_box, sizeof(Box) * n)); HC(hipMalloc(&t_box, sizeof(Box) * n));
-            HC(hipMalloc(&valid, 4ull * n)); HC(hipMalloc(&pos, 4ull * n));
-            HC(hipMalloc(&node_depth, 4ull * ni));
-            HC(hipMalloc(&side_int, ni)); HC(hipMalloc(&side_leaf, n));
-            HC(hipMemsetAsync(side_int, 0, ni, st));
-            HC(rocprim::exclusive_scan(nullptr, scan_bytes, valid, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-            HC(hipMalloc(&scan_temp, scan_bytes));
-            hipLaunchKernelGGL(k_ploc_init, dim3(gn), dim3(B), 0, st, (int)n, boxes, vals_s, c_node, c_box);
-            uint32_t m = n, made = 0;
-            int force = 0, rounds = 0;
-            round_end.clear();
-            while (m > 1) {
-                const uint32_t gm = (m + B - 1) / B;
-                hipLaunchKernelGGL(k_ploc_nn, dim3(gm), dim3(B), 0, st, (int)m, force, c_box, nn);
-                hipLaunchKernelGGL(k_ploc_mark, dim3(gm), dim3(B), 0, st, (int)m, nn, valid);
-                HC(rocprim::exclusive_scan(scan_temp, scan_bytes, valid, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
-                hipLaunchKernelGGL(k_ploc_merge, dim3(gm), dim3(B), 0, st, (int)m, (int)made, c_node, c_box, nn, pos, left, right, parent_int,
-                                   parent_leaf, side_int, side_leaf, ibox, size_int, t_node, t_box);
-                uint32_t last_pos = 0, last_valid = 0;
-                HC(hipMemcpyAsync(&last_pos, pos + (m - 1), 4, hipMemcpyDeviceToHost, st));
-                HC(hipMemcpyAsync(&last_valid, valid + (m - 1), 4, hipMemcpyDeviceToHost, st));
-                HC(hipStreamSynchronize(st));
-                { int* tn = c_node; c_node = t_node; t_node = tn; Box* tb = c_box; c_box = t_box; t_box = tb; }
-                const uint32_t m2 = last_pos + last_valid;
-                made += m - m2;                                // every pair drops one cluster and makes one node
-                round_end.push_back(made);
-                // (Almost) no mutual pair this round -- coincident geometry: among equal boxes everybody picks the first
-                // candidate of its window and one pair merges per round -- so the next round pairs neighbours.
-                force = ((uint64_t)(m - m2) * 64u < m) ? 1 : 0;
-                m = m2;
-                if (++rounds > 4096) { snprintf(err, errlen, "PLOC did not converge"); goto fail; }
-            }
-            if (trace) {
-                trace->root = (int)n - 2;
-                trace->round_end = round_end;
-                if (!grab(trace->left0, left, ni) || !grab(trace->right0, right, ni) || !grab(trace->ibox0, ibox, 6ull * ni)) goto fail;
-            }
-            if (reinsert_rounds > 0 && n > 16) {
-                // ---- reinsertion rounds on the PLOC tree (see k_reinsert_find)
-                TreeView T;
-                T.n = (int)n; T.left = left; T.right = right; T.parent_int = parent_int; T.parent_leaf = parent_leaf;
-                T.ibox = ibox; T.boxes = boxes; T.vals = vals_s;
-                const uint32_t nall = 2 * n - 1, gall2 = (nall + B - 1) / B;
-                HC(hipMalloc(&re_moves, sizeof(Move) * (size_t)nall));
-                HC(hipMalloc(&re_lock, 8ull * nall));
-                HC(hipMalloc(&re_arrive, 2ull * ni));                     // (the sweep that finished each node, + 1)
-                HC(hipMalloc(&re_scalars, 16));
-                HC(hipMalloc(&re_flags, 2ull * nall));
-                // the cost of the tree as PLOC left it (what the first round's gain is measured against)
-                float cost_prev = 0.f;
-                HC(hipMemsetAsync(re_scalars, 0, 16, st));
-                if (!sweep_up(0, T, (float*)(re_scalars + 1))) goto fail;
-                HC(hipMemcpyAsync(&cost_prev, re_scalars + 1, 4, hipMemcpyDeviceToHost, st));
-                HC(hipStreamSynchronize(st));
-                if (verbose) fprintf(stderr, "[fovpt bvh] PLOC tree: sum of internal areas %.6g\n", (double)cost_prev);
-                for (int round = 0; round < reinsert_rounds; round++) {
-                    uint32_t applied = 0;
-                    float cost = 0.f;
-                    hipLaunchKernelGGL(k_reinsert_find, dim3(gall2), dim3(B), 0, st, T, (int)n - 2, re_moves, 0u, 1u);
-                    HC(hipMemsetAsync(re_lock, 0, 8ull * nall, st));
-                    HC(hipMemsetAsync(re_flags, 0, 2ull * nall, st));
-                    HC(hipMemsetAsync(re_scalars, 0, 16, st));
-                    hipLaunchKernelGGL(k_reinsert_lock, dim3(gall2), dim3(B), 0, st, T, re_moves, re_lock, re_scalars);
-                    hipLaunchKernelGGL(k_reinsert_check, dim3(gall2), dim3(B), 0, st, T, re_moves, re_lock, re_flags);
-                    hipLaunchKernelGGL(k_reinsert_check2, dim3(gall2), dim3(B), 0, st, T, re_moves, re_lock, re_flags, re_flags + nall, re_scalars);
-                    hipLaunchKernelGGL(k_reinsert_apply, dim3(gall2), dim3(B), 0, st, T, re_moves, re_flags + nall);
-                    if (!sweep_up(0, T, (float*)(re_scalars + 1))) goto fail;
-                    uint32_t candidates = 0;
-                    HC(hipMemcpyAsync(&applied, re_scalars, 4, hipMemcpyDeviceToHost, st));
-                    HC(hipMemcpyAsync(&cost, re_scalars + 1, 4, hipMemcpyDeviceToHost, st));
-                    HC(hipMemcpyAsync(&candidates, re_scalars + 2, 4, hipMemcpyDeviceToHost, st));
-                    HC(hipStreamSynchronize(st));
-                    HC(hipGetLastError());
-                    tree_changed = tree_changed || applied > 0;
-                    if (verbose) fprintf(stderr, "[fovpt bvh] reinsertion round %d: %u of %u candidate moves, sum of internal areas %.6g\n", round, applied, candidates, (double)cost);
-                    if (applied == 0 || !(cost_prev - cost > FOVPT_REINSERT_STOP * cost_prev)) break;      // (nothing much left to gain)
-                    cost_prev = cost;
-                }
-            }
-            const uint32_t gall = (2 * n - 1 + B - 1) / B;
-            hipLaunchKernelGGL(k_dfs_offsets, dim3(gall), dim3(B), 0, st, (int)n, left, parent_int, parent_leaf, side_int, side_leaf, size_int,
-                               leaf_pos, node_first, node_depth);
-            root = (int)n - 2;                                 // the last merge created the root
-        }
-        if (trace && (!grab(trace->left1, left, ni) || !grab(trace->right1, right, ni) || !grab(trace->ibox1, ibox, 6ull * ni)
-                      || !grab(trace->size_int, size_int, ni) || !grab(trace->node_first, node_first, ni) || !grab(trace->leaf_pos, leaf_pos, n))) goto fail;
-        // ---- 2 -> 4 collapse: costs bottom-up, then one launch per level of the wide tree
-        HC(hipMalloc(&dp, sizeof(DpCost) * ni));
-        if (use_ploc && !tree_changed) {
-            uint32_t first = 0;
-            for (uint32_t end : round_end) {
-                if (end > first)
-                    hipLaunchKernelGGL(k_dp_range, dim3((end - first + B - 1) / B), dim3(B), 0, st, (int)first, (int)(end - first), boxes, vals_s,
-                                       left, right, size_int, ibox, dp);
-                first = end;
-            }
-        } else if (use_ploc) {
-            // a reinserted tree: the same programme in bottom-up sweeps (k_sweep_up)
-            TreeView T;
-            T.n = (int)n; T.left = left; T.right = right; T.parent_int = parent_int; T.parent_leaf = parent_leaf;
-            T.ibox = ibox; T.boxes = boxes; T.vals = vals_s;
-            if (!sweep_up(1, T, nullptr)) goto fail;
-        } else {
-            HC(hipMalloc(&dp_arrive, 4ull * ni));
-            HC(hipMemsetAsync(dp_arrive, 0, 4ull * ni, st));
-            hipLaunchKernelGGL(k_dp_collapse, dim3(gn), dim3(B), 0, st, (int)n, boxes, vals_s, left, right, parent_int, parent_leaf, size_int, ibox,
-                               dp, dp_arrive);
-        }
-        if (trace && !grab(trace->dp, dp, 4ull * ni)) goto fail;
-        HC(hipMalloc(&work_a, sizeof(Work4) * ni)); HC(hipMalloc(&work_b, sizeof(Work4) * ni));
-        Work4 w0; w0.node = root; w0.out = 0; w0.depth = 0;
-        HC(hipMemcpyAsync(work_a, &w0, sizeof(w0), hipMemcpyHostToDevice, st));
-        HC(hipMemcpyAsync(counters, h_counters, 8, hipMemcpyHostToDevice, st));
-        uint32_t nwork = 1;
-        int levels = 0;
-        level_first.push_back(0u);
-        level_first.push_back(1u);             // the root is node 0; the nodes of level L + 1 are allocated by the launch of level L
-        while (nwork > 0) {
-            hipLaunchKernelGGL(k_collapse4, dim3((nwork + B - 1) / B), dim3(B), 0, st, (int)nwork, work_a, work_b, counters, left, right,
-                               size_int, node_first, leaf_pos, boxes, vals_s, ibox, dp, nodes, stats);
-            HC(hipMemcpyAsync(h_counters, counters, 8, hipMemcpyDeviceToHost, st));
-            HC(hipStreamSynchronize(st));
-            nwork = h_counters[1];
-            if (nwork > 0) level_first.push_back(h_counters[0]);
-            h_counters[1] = 0;
-            HC(hipMemcpyAsync(counters + 1, &h_counters[1], 4, hipMemcpyHostToDevice, st));
-            Work4* t = work_a; work_a = work_b; work_b = t;
-            if (++levels > 4096) { snprintf(err, errlen, "BVH collapse did not terminate"); goto fail; }
-        }
+        STAGE(morton_sort(S));
+        if (tr) STAGE(grab(S, tr->keys_s, S.keys_s, n) && grab(S, tr->vals_s, S.vals_s, n));
+        if (sw.use_ploc) STAGE(ploc_tree(S)); else STAGE(karras_tree(S));
+        if (tr) { tr->root = S.root; tr->round_end = S.round_end; }
+        if (tr) STAGE(grab(S, tr->left0, T.left, ni) && grab(S, tr->right0, T.right, ni) && grab(S, tr->ibox0, T.ibox, 6ull * ni));
+        if (sw.use_ploc) { STAGE(reinsert_rounds(S)); STAGE(dfs_offsets(S)); }
+        if (tr) STAGE(grab(S, tr->left1, T.left, ni) && grab(S, tr->right1, T.right, ni) && grab(S, tr->ibox1, T.ibox, 6ull * ni)
+                      && grab(S, tr->size_int, S.size_int, ni) && grab(S, tr->node_first, S.node_first, ni) && grab(S, tr->leaf_pos, S.leaf_pos, n));
+        STAGE(collapse_costs(S));
+        if (tr) STAGE(grab(S, tr->dp, S.dp, 4ull * ni));
+        STAGE(collapse_levels(S));
     }
-    hipLaunchKernelGGL(k_emit_tris_generic, dim3(gn), dim3(B), 0, st, flat, mesh_of_prim, vals_s, ref_prim, leaf_pos, n, tris);
-    HC(hipGetLastError());
-    if (trace && !grab(trace->nodes_pre, nodes, 32ull * (level_first.size() >= 2 ? level_first.back() : 1u))) goto fail;
-    if (order_children && level_first.size() >= 2) {
-        // children in the order that ends occlusion rays soonest: one launch per level, deepest first
-        const uint32_t total = level_first.back();
-        HC(hipMalloc(&order_pc, sizeof(float2) * (size_t)total));
-        for (size_t L = level_first.size() - 1; L-- > 0;) {
-            const uint32_t first = level_first[L], count = level_first[L + 1] - first;
-            if (count) hipLaunchKernelGGL(k_order_children, dim3((count + B - 1) / B), dim3(B), 0, st, first, count, nodes, tris, order_pc);
-        }
-        HC(hipGetLastError());
-    }
-    HC(hipMemcpyAsync(h_stats, stats, 8, hipMemcpyDeviceToHost, st));
-    HC(hipStreamSynchronize(st));
-
-    {
-        // The hierarchy that stays: ONE allocation, the nodes actually emitted (the build array is sized for the binary
-        // tree, ~8 x as many) followed by the triangles, so the traversal reaches both through one base register and a
-        // 32-bit offset, and the build's slack goes back to the allocator.
-        const size_t node_bytes = sizeof(BvhNode4) * (size_t)h_stats[1], tri_bytes = sizeof(TriRec) * (size_t)n;
-        const size_t tri_off = (node_bytes + 255) & ~(size_t)255;
-        char* scene = nullptr;
-        HC(hipMalloc(&scene, tri_off + tri_bytes + 64));          // + slack: a lane may fetch 16 bytes past its record
-        if (hipMemcpyAsync(scene, nodes, node_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess
-            || hipMemcpyAsync(scene + tri_off, tris, tri_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess
-            || hipMemsetAsync(scene + tri_off + tri_bytes, 0, 64, st) != hipSuccess
-            || hipStreamSynchronize(st) != hipSuccess) {
-            (void)hipFree(scene);
-            snprintf(err, errlen, "copying the hierarchy failed");
-            goto fail;
-        }
-        out->nodes = (BvhNode4*)scene; out->tris = (TriRec*)(scene + tri_off);      // tris is INSIDE the nodes allocation
-        out->num_nodes = h_stats[1];
-        out->num_refs = n;
-        out->max_depth = h_stats[0];
-        out->reinserted = tree_changed ? 1u : 0u;
-        out->node_bytes = node_bytes;
-        out->tri_bytes = tri_bytes;
-        // the levels of the wide tree, for the refit (refit.hip); a tiny scene is its root alone
-        if (level_first.size() < 2) level_first.assign({0u, 1u});
-        out->num_levels = level_first.size() - 1 <= FOVPT_BVH_MAX_LEVELS ? (uint32_t)(level_first.size() - 1) : 0u;
-        for (uint32_t L = 0; out->num_levels && L <= out->num_levels; L++) out->level_first[L] = level_first[L];
-    }
-fail:
-    if (err[0]) rc = hipErrorUnknown;
-    (void)hipFree(ref_prim); (void)hipFree(split_cnt); (void)hipFree(split_first); (void)hipFree(split_total); (void)hipFree(split_temp);
-    (void)hipFree(boxes); (void)hipFree(ibox); (void)hipFree(bounds); (void)hipFree(stats); (void)hipFree(keys); (void)hipFree(keys_s);
-    (void)hipFree(vals); (void)hipFree(vals_s); (void)hipFree(arrive); (void)hipFree(left); (void)hipFree(right); (void)hipFree(parent_int);
-    (void)hipFree(parent_leaf); (void)hipFree(rfirst); (void)hipFree(rlast); (void)hipFree(temp); (void)hipFree(nodes); (void)hipFree(tris);
-    (void)hipFree(c_node); (void)hipFree(t_node); (void)hipFree(nn); (void)hipFree(c_box); (void)hipFree(t_box); (void)hipFree(valid); (void)hipFree(pos);
-    (void)hipFree(size_int); (void)hipFree(leaf_pos); (void)hipFree(node_first); (void)hipFree(node_depth);
-    (void)hipFree(dp); (void)hipFree(dp_arrive); (void)hipFree(order_pc);
-    (void)hipFree(re_moves); (void)hipFree(re_lock); (void)hipFree(re_arrive); (void)hipFree(re_scalars); (void)hipFree(re_flags);
-    (void)hipFree(side_int); (void)hipFree(side_leaf); (void)hipFree(scan_temp); (void)hipFree(work_a); (void)hipFree(work_b); (void)hipFree(counters);
-    return rc;
+    STAGE(records_and_child_order(S));
+    STAGE(pack_result(S, out));
+    return hipSuccess;
 }

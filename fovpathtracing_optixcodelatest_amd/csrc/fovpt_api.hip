@@ -557,8 +557,7 @@ int build_hierarchy(hipStream_t st, const BvhSwitches& sw, const float* d_flat, 
     hipError_t be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, sw, -1, &br, errbuf, sizeof(errbuf));
     if (be == hipSuccess && br.reinserted && 3 * br.max_depth + 1 > FOVPT_STACK) {
         // reinsertion lowers the tree's cost, not its depth: a hierarchy it made too deep for the traversal stack is built again without it
-        (void)hipFree(br.nodes);
-        memset(&br, 0, sizeof(br));
+        free_hierarchy(br);
         be = fovpt_build_lbvh(st, d_flat, d_mesh_of, ntri, sw, 0, &br, errbuf, sizeof(errbuf));
     }
     (void)hipEventRecord(e1, st);
@@ -567,13 +566,13 @@ int build_hierarchy(hipStream_t st, const BvhSwitches& sw, const float* d_flat, 
     (void)hipEventElapsedTime(&ms, e0, e1);
     if (be != hipSuccess) { snprintf(err, errlen, "LBVH build: %s", errbuf); return FOVPT_E_DEVICE; }
     if (3 * br.max_depth + 1 > FOVPT_STACK) {       // a wide node leaves at most 3 entries behind
-        (void)hipFree(br.nodes);
         snprintf(err, errlen, "hierarchy depth %u needs more than the %d traversal stack entries", br.max_depth, FOVPT_STACK);
+        free_hierarchy(br);
         return FOVPT_E_BVH_DEPTH;
     }
     if ((size_t)((const char*)br.tris - (const char*)br.nodes) + br.tri_bytes + 64 >= (1ull << 32)) {
-        (void)hipFree(br.nodes);
         snprintf(err, errlen, "hierarchy of %llu bytes exceeds the 32-bit offsets of the traversal", (unsigned long long)(br.node_bytes + br.tri_bytes));
+        free_hierarchy(br);
         return FOVPT_E_INVALID;
     }
     return FOVPT_OK;

@@ -203,6 +203,8 @@ struct BvhBuildResult {
     uint32_t num_levels;          // levels of the wide tree (0: more than FOVPT_BVH_MAX_LEVELS)
     uint32_t level_first[FOVPT_BVH_MAX_LEVELS + 1];   // level L is the contiguous nodes [level_first[L], level_first[L + 1])
 };
+// a result nobody adopted: the allocation goes, br is left zeroed
+inline void free_hierarchy(BvhBuildResult& br) { if (br.nodes) (void)hipFree(br.nodes); br = BvhBuildResult{}; }
 
 // The environment switches of a build, read once by whoever asks for it (fovpt_bvh_switches), so that a build on a thread of its
 // own never reads the environment: FOVPT_BVH (use_ploc), FOVPT_SPLIT (split_budget: references added by spatial splits as a

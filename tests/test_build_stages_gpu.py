@@ -29,6 +29,9 @@ CONFIGS = {
     "lbvh": (False, 0.0, 0, True),
     "ploc_split_reinsert": (True, 1.0, REINSERT_DEFAULT, True),
     "lbvh_split_noorder": (False, 1.0, 0, False),
+    # a budget too small for one extra reference of the lattice's 216 triangles (< 1 / 216): the split stage counts, makes no
+    # reference, and the build goes on over the triangles' own boxes
+    "ploc_split_none": (True, 1.0 / 256.0, 0, True),
 }
 SCENES = {
     "soup1": lambda: tc.soup(1, 1), "soup4": lambda: tc.soup(4, 2), "soup5": lambda: tc.soup(5, 3), "soup17": lambda: tc.soup(17, 4),
@@ -41,6 +44,7 @@ CASES = [("soup1", "ploc"), ("soup4", "ploc"), ("soup4", "ploc_split_reinsert"),
 CASES += [(s, c) for s in ("soup5", "soup17", "soup64", "soup65", "soup256", "soup257", "soup300", "soup2000", "duplicates", "lattice", "cards") for c in _three]
 CASES += [(s, "ploc_split_reinsert") for s in ("soup5", "soup17", "soup65", "soup300", "soup2000", "cards")]
 CASES += [(s, "lbvh_split_noorder") for s in ("soup300", "cards")]
+CASES += [("lattice", "ploc_split_none")]
 
 _scene_cache, _ref_cache = {}, {}
 
@@ -108,7 +112,7 @@ def check_splits(p, budget, T):
     total = int(count.sum())
     assert total <= (1.0 + budget) * n
     if total == n:
-        assert not T["have_splits"] and T["num_refs"] == n
+        assert not T["have_splits"] and T["num_refs"] == n and (T["split_count"] == 1).all()
         return np.arange(n), np.zeros(n, bool)
     assert T["have_splits"] and T["num_refs"] == total
     ref_prim, first, slabs = br.split_references(p, count)
