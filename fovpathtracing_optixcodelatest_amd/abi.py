@@ -569,6 +569,40 @@ class LensConfig(C.Structure):
         return {n: (tuple(get(n)) if isinstance(get(n), C.Array) else get(n)) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+QUALITY_SSIM, QUALITY_PROFILE = 1, 2                   # FOVPT_QUALITY_* flags
+QUALITY_CLASSES, QUALITY_RINGS, QUALITY_MAX_RING_WIDTH = 5, 64, 65536
+QUALITY_FOVEA, QUALITY_MIDDLE, QUALITY_PERIPHERY, QUALITY_UNIFORM, QUALITY_UNWRITTEN = 0, 1, 2, 3, 4   # a pixel's class
+QUALITY_CLASS_NAMES = ("fovea", "middle", "periphery", "uniform", "unwritten")
+
+
+class QualityConfig(C.Structure):
+    """fovpt_quality_config: which sums beside the per-class errors, and the width of a ring of the eccentricity profile
+    (defaults: fovpt_quality_defaults)."""
+    _fields_ = [("flags", C.c_int32), ("ring_width", C.c_int32), ("_reserved", C.c_int32 * 6)]
+
+    def copy(self):
+        m = QualityConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(QualityConfig))
+        return m
+
+
+class QualitySums(C.Structure):
+    """fovpt_quality_sums: the exact integer sums of one measurement, per class (QUALITY_FOVEA ..) and per ring."""
+    _fields_ = [
+        ("pixels", C.c_uint64 * 5), ("differing", C.c_uint64 * 5), ("sq_err", (C.c_uint64 * 3) * 5),
+        ("max_err", C.c_uint32 * 5), ("_pad", C.c_uint32),
+        ("windows", C.c_uint64 * 5), ("ssim_q20", C.c_int64 * 5),
+        ("ring_pixels", C.c_uint64 * 64), ("ring_sq_err", C.c_uint64 * 64),
+        ("width", C.c_uint32), ("height", C.c_uint32), ("ring_width", C.c_uint32), ("flags", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        """Every field: the arrays as (nested) lists of Python integers."""
+        def val(v):
+            return [val(x) for x in v] if isinstance(v, C.Array) else int(v)
+        return {n: val(getattr(self, n)) for n, _ in self._fields_}
+
+
 PACKET_MAGIC, PACKET_VERSION, PACKET_SLOTS =0x4b505646, 1, 4      # FOVPT_PACKET_*
 PACKET_NEAREST, PACKET_SMOOTH = 0, 1
 PACKET_MAGIC_CODED = 0x43505646                                   # "FVPC": a coded packet, a codec per pass
@@ -634,6 +668,8 @@ assert C.sizeof(WarpCamera) == 48 and C.sizeof(WarpConfig) == 32 and C.sizeof(Wa
 assert C.sizeof(WarpMotionConfig) == 32 and WarpMotionConfig.advance.offset == 8
 assert C.sizeof(FocusConfig) == 64 and (FocusConfig.strength.offset, FocusConfig._reserved.offset) == (16, 36)
 assert C.sizeof(FocusState) == 32 and FocusState.count.offset == 16
+assert C.sizeof(QualityConfig) == 32 and QualityConfig._reserved.offset == 8
+assert C.sizeof(QualitySums) == 1344 and (QualitySums.max_err.offset, QualitySums.windows.offset, QualitySums.ring_pixels.offset, QualitySums.width.offset) == (200, 224, 304, 1328)
 assert C.sizeof(LensConfig) == 128 and (LensConfig.k.offset, LensConfig.clip_r2.offset, LensConfig.border.offset, LensConfig._reserved.offset) == (32, 60, 80, 96)
 assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
 assert C.sizeof(PacketConfig) == 16 and PacketConfig._reserved.offset == 12

@@ -1,6 +1,6 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI: fovpt_denoise (denoise.hip), fovpt_gbuffer /
 // fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_expose (expose.hip), fovpt_warp /
-// fovpt_warp_motion (warp.hip), fovpt_focus (focus.hip), fovpt_lens (lens.hip), and their defaults.
+// fovpt_warp_motion (warp.hip), fovpt_focus (focus.hip), fovpt_lens (lens.hip), fovpt_quality (quality.hip), and their defaults.
 #include <cmath>
 #include <cstring>
 
@@ -259,6 +259,39 @@ int expose_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_expose
     { const int rc_ = check_rendered_frame(c, lp, who, "meter", nullptr); if (rc_) return rc_; }
     if ((size_t)c->dn_w * (size_t)c->dn_h >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
     if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+    return FOVPT_OK;
+}
+
+// fovpt_quality's validation (nothing allocated, enqueued or changed).  test: its test image
+int quality_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_quality_config* qc, const uint32_t* test, const uint32_t* ref, const char* who)
+{
+    if (qc->flags & ~(FOVPT_QUALITY_SSIM | FOVPT_QUALITY_PROFILE)) return fail(c, FOVPT_E_INVALID, "%s: unknown flag bits 0x%x", who, (unsigned)qc->flags);
+    if (qc->ring_width < 1 || qc->ring_width > FOVPT_QUALITY_MAX_RING_WIDTH)
+        return fail(c, FOVPT_E_INVALID, "%s: ring_width %d outside 1 .. %d", who, qc->ring_width, FOVPT_QUALITY_MAX_RING_WIDTH);
+    for (int32_t r : qc->_reserved)
+        if (r != 0) return fail(c, FOVPT_E_INVALID, "%s: reserved fields must be 0", who);
+    { const int rc_ = check_rendered_frame(c, lp, who, "measure", nullptr); if (rc_) return rc_; }
+    if ((size_t)c->dn_w * (size_t)c->dn_h >= (1ull << 31)) return fail(c, FOVPT_E_INVALID, "%s: frame too large (%d x %d)", who, c->dn_w, c->dn_h);
+    if (!ref) return fail(c, FOVPT_E_INVALID, "%s: null reference image", who);
+    if (!test) return fail(c, FOVPT_E_INVALID, "%s: null frame_buffer", who);
+    return FOVPT_OK;
+}
+
+// the measurement's buffers and launches for a checked call (out_sums null: the context's own record)
+int quality_enqueue(fovpt_ctx* c, const fovpt_quality_config* qc, const uint32_t* test, const uint32_t* ref, fovpt_quality_sums* out_sums, uint8_t* out_class)
+{
+    if (!out_sums) {
+        HIPCHK(c, c->q_sums.reserve(sizeof(fovpt_quality_sums)));           // (made here, and the launch below writes every byte of it)
+        out_sums = (fovpt_quality_sums*)c->q_sums.p;
+    }
+    HIPCHK(c, c->q_rows.reserve((size_t)fovpt_quality_rows(c->dn_w, c->dn_h) * FOVPT_QUALITY_COLUMNS * sizeof(uint64_t)));
+    QualityArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cx = (int64_t)(int32_t)c->dn_frame.cx; a.cy = (int64_t)(int32_t)c->dn_frame.cy;      // the rendered gaze
+    a.flags = qc->flags; a.ring_width = qc->ring_width;
+    a.uniform = c->dn_uniform != 0;
+    fovpt_launch_quality(c->shadow_stream, c->dn_frame, a, test, ref, (uint64_t*)c->q_rows.p, out_sums, out_class);
+    HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }
 
@@ -1097,6 +1130,43 @@ int fovpt_lens(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_lens_con
     memcpy(a.border, lc->border, sizeof(a.border));
     fovpt_launch_lens(c->shadow_stream, c->dn_w, c->dn_h, a, in, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
+}
+
+// ---- image quality of the rendered frame (quality.hip; its definition: tests/quality_ref.py) -----------------------------------
+// (ring_width: a convention, not a measurement: include/fovpt.h)
+int fovpt_quality_defaults(fovpt_quality_config* out)
+{
+    if (!out) return FOVPT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->flags = FOVPT_QUALITY_SSIM | FOVPT_QUALITY_PROFILE;
+    out->ring_width = 16;
+    return FOVPT_OK;
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: k_quality_tile, k_quality_sum.  The rows between them are
+// the context's; calls in flight use them one after the other, in stream order.
+int fovpt_quality(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_quality_config* qc, const uint32_t* test_rgba, const uint32_t* ref_rgba,
+                  fovpt_quality_sums* out_sums, uint8_t* out_class)
+{
+    const char* who = "fovpt_quality";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !qc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const uint32_t* test = test_rgba ? test_rgba : lp->frame.frame_buffer;
+    { const int rc_ = quality_check(c, lp, qc, test, ref_rgba, who); if (rc_) return rc_; }
+    HIPCHK(c, hipSetDevice(c->device));
+    return quality_enqueue(c, qc, test, ref_rgba, out_sums, out_class);
+}
+
+int fovpt_quality_read(fovpt_ctx* c, fovpt_quality_sums* out)
+{
+    if (!c) return FOVPT_E_INVALID;
+    if (!out) return fail(c, FOVPT_E_INVALID, "fovpt_quality_read: null argument");
+    memset(out, 0, sizeof(*out));
+    if (!c->q_sums.p) return FOVPT_OK;                                     // no measurement into the context's record yet
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));
+    HIPCHK(c, hipMemcpy(out, c->q_sums.p, sizeof(*out), hipMemcpyDeviceToHost));
     return FOVPT_OK;
 }
 

@@ -1026,6 +1026,7 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (c->fc_rt.p) HIPCHK(c, c->fc_rt.reserve(n * 8));                                                    // and fovpt_focus's pairs and outputs (its state stays)
     if (c->fc_color.p) { HIPCHK(c, c->fc_color.reserve(n * 16)); HIPCHK(c, c->fc_rgba.reserve(n * 4)); }
     if (c->ln_color.p) { HIPCHK(c, c->ln_color.reserve(n * 16)); HIPCHK(c, c->ln_rgba.reserve(n * 4)); }   // and fovpt_lens's
+    if (c->q_rows.p) HIPCHK(c, c->q_rows.reserve((size_t)fovpt_quality_rows(width, height) * FOVPT_QUALITY_COLUMNS * sizeof(uint64_t)));   // and fovpt_quality's rows (its record stays)
     c->tp_valid = false;                                                                      // (its history is of another size)
     c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
     c->seq_frame = ++c->seq;                                                                  // (fovpt_warp_motion: nor traced)

@@ -225,6 +225,10 @@ struct fovpt_ctx {
     DevBuf fc_state, fc_rt, fc_color, fc_rgba;
     // fovpt_lens: the context's own outputs, allocated on first use (the stage keeps nothing else)
     DevBuf ln_color, ln_rgba;
+    // fovpt_quality: the context's own record (a fovpt_quality_sums, made by the first call that measures into it, which writes
+    // every byte; the host reads it nowhere but in fovpt_quality_read) and the tile kernel's rows of partial sums
+    // (fovpt_quality_rows of the frame's size); both allocated on first use
+    DevBuf q_sums, q_rows;
     // fovpt_packet_submit / fovpt_packet_wait (api_packet.hip), all made by a context's first submit: the copy stream, and per slot
     // the device buffer an encode writes (one each, so that an encode never overwrites a packet that is still being copied), the
     // pinned host buffer its copy fills (grown on demand), the event recorded on fovpt_stream() behind the encode, which the copy

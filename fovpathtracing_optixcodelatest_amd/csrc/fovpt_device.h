@@ -405,6 +405,25 @@ struct LensArgs {
     float center[2], scale[2], k[4], chroma[3], clip_r2, src_center[2], src_scale[2], border[4];
 };
 void fovpt_launch_lens(hipStream_t st, int w, int h, const LensArgs& a, const fovpt_float4* in, fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_quality (quality.hip): k_quality_tile over the frame's 32 x 32 pixel tiles into `rows` -- one row of FOVPT_QUALITY_COLUMNS
+// 64-bit partial sums per block of fovpt_quality_rows(w, h), a block striding over the tiles --, then the one block of
+// k_quality_sum, which adds the columns (the maximum for max_err) and writes every byte of the record.  test and ref may be the
+// same image; out_class may be null.
+#define FOVPT_QUALITY_TILE 32            // pixels along a side of a tile
+#define FOVPT_QUALITY_BLOCK 256          // threads of k_quality_tile: 4 pixels of the tile each
+#define FOVPT_QUALITY_SUM_BLOCK 1024     // threads of k_quality_sum's one block
+#define FOVPT_QUALITY_COLUMNS (8 * FOVPT_QUALITY_CLASSES + 2 * FOVPT_QUALITY_RINGS)
+#ifndef FOVPT_QUALITY_MAX_ROWS
+#define FOVPT_QUALITY_MAX_ROWS 1024      // blocks of k_quality_tile: 4 per CU; every row goes through the one block of k_quality_sum
+#endif
+struct QualityArgs {
+    int64_t cx, cy;                     // the rendered gaze: (int64)(int32)frame.c
+    int32_t flags, ring_width;
+    int32_t uniform;                    // the frame was rendered FOV_OFF
+};
+uint32_t fovpt_quality_rows(int w, int h);
+void fovpt_launch_quality(hipStream_t st, const FrameDev& fd, const QualityArgs& a, const uint32_t* test, const uint32_t* ref, uint64_t* rows,
+                          fovpt_quality_sums* out_sums, uint8_t* out_class);
 // fovpt_update_vertices (refit.hip).  vtx: the scene's vertex positions, xyz per vertex, all meshes one after the other;
 // tri_vidx: per global primitive id the three indices of its vertices in vtx.
 #define FOVPT_GATHER_BATCH 32

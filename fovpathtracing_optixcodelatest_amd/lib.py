@@ -31,6 +31,8 @@ EXPORTS = [
     "fovpt_warp_motion_defaults", "fovpt_warp_motion",
     "fovpt_focus_defaults", "fovpt_focus", "fovpt_focus_buffers", "fovpt_focus_state", "fovpt_focus_reset",
     "fovpt_lens_defaults", "fovpt_lens", "fovpt_lens_buffers",
+    "fovpt_quality_defaults", "fovpt_quality", "fovpt_quality_read", "fovpt_quality_host",
+    "fovpt_quality_mse", "fovpt_quality_psnr", "fovpt_quality_ssim", "fovpt_quality_score",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
     "fovpt_packet_check", "fovpt_packet_decode_host",
     "fovpt_packet_defaults", "fovpt_packet_describe_coded", "fovpt_packet_encode_coded", "fovpt_packet_submit_coded",
@@ -139,6 +141,17 @@ def _declare_packet_host(L):
         getattr(L, name).restype = C.c_int
 
 
+def _declare_quality_host(L):
+    """The quality entry points both libraries share: the measurement on host images and the scores of a record
+    (csrc/quality_host.cpp)."""
+    sums = C.POINTER(abi.QualitySums)
+    L.fovpt_quality_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(abi.QualityConfig), sums]
+    L.fovpt_quality_host.restype = C.c_int
+    for name in QUALITY_SCORE_EXPORTS:
+        getattr(L, name).argtypes = [sums, C.POINTER(C.c_double) if name == "fovpt_quality_score" else C.c_int]
+        getattr(L, name).restype = C.c_double
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -208,6 +221,9 @@ def load():
     L.fovpt_lens_defaults.argtypes = [C.POINTER(abi.LensConfig)]
     L.fovpt_lens.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.LensConfig), C.POINTER(abi.WarpCamera), vp, vp, vp]
     L.fovpt_lens_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_quality_defaults.argtypes = [C.POINTER(abi.QualityConfig)]
+    L.fovpt_quality.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.QualityConfig), vp, vp, vp, vp]
+    L.fovpt_quality_read.argtypes = [vp, C.POINTER(abi.QualitySums)]
     L.fovpt_packet_describe.argtypes =[vp, C.POINTER(abi.LaunchParams), u32, C.POINTER(abi.PacketHeader)]
     L.fovpt_packet_encode.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, vp]
     L.fovpt_packet_submit.argtypes = [vp, C.POINTER(abi.LaunchParams), vp, u32, C.POINTER(i32)]
@@ -249,8 +265,9 @@ def load():
     _declare_loader(L)
     _declare_packet_host(L)
     for name in EXPORTS:
-        if name not in ("fovpt_destroy", "fovpt_last_error", "fovpt_stream", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8"):
+        if name not in ("fovpt_destroy", "fovpt_last_error", "fovpt_stream", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8") + QUALITY_SCORE_EXPORTS:
             getattr(L, name).restype = i32
+    _declare_quality_host(L)
     _lib = L
     return L
 
@@ -258,12 +275,14 @@ def load():
 LOADER_SO_PATH = os.path.join(CSRC, "libfovpt_loader.so")
 LOADER_EXPORTS = [n for n in EXPORTS if n.startswith("fovpt_model_") or n.startswith("fovpt_image_")] + ["fovpt_last_error"]
 PACKET_HOST_EXPORTS = ["fovpt_packet_check", "fovpt_packet_decode_host"]      # in both libraries too
+QUALITY_SCORE_EXPORTS = ("fovpt_quality_mse", "fovpt_quality_psnr", "fovpt_quality_ssim", "fovpt_quality_score")   # return a double
+QUALITY_HOST_EXPORTS = ["fovpt_quality_host"] + list(QUALITY_SCORE_EXPORTS)   # in both libraries too
 _loader = None
 
 
 def load_loader():
-    """The scene / image ingestion of the C ABI (fovpt_model_*, fovpt_image_*) and the packet decoder for a client
-    (PACKET_HOST_EXPORTS).  If libfovpt.so is already loaded, it; otherwise the
+    """The scene / image ingestion of the C ABI (fovpt_model_*, fovpt_image_*), the packet decoder for a client
+    (PACKET_HOST_EXPORTS) and the quality measurement on host images (QUALITY_HOST_EXPORTS).  If libfovpt.so is already loaded, it; otherwise the
     HOST-ONLY libfovpt_loader.so (same code, g++, no HIP runtime), so that reading OBJ / glTF / JPEG / HDR files needs no GPU
     stack; FOVPT_SO (an A/B build of the whole library) takes precedence.  The render path never goes through here."""
     global _loader
@@ -274,6 +293,7 @@ def load_loader():
     L = C.CDLL(LOADER_SO_PATH)
     _declare_loader(L)
     _declare_packet_host(L)
+    _declare_quality_host(L)
     for name in LOADER_EXPORTS:
         if name not in ("fovpt_last_error", "fovpt_model_destroy", "fovpt_image_free", "fovpt_image_free_rgba8"):
             getattr(L, name).restype = C.c_int

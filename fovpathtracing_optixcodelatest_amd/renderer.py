@@ -628,6 +628,83 @@ class SampleRenderer:
         col, rgba = self.lens_buffers()
         return self._download_frame(col, 4), self._download_frame(rgba, 1)
 
+    # -- image quality of the rendered frame (include/fovpt.h, fovpt_quality): per-level error, SSIM and eccentricity profile
+    @staticmethod
+    def quality_defaults() -> abi.QualityConfig:
+        d = abi.QualityConfig()
+        lib.check(None, lib.load().fovpt_quality_defaults(C.byref(d)))
+        return d
+
+    @staticmethod
+    def quality_scores(sums) -> dict:
+        """The derived scores of an abi.QualitySums (fovpt_quality_mse / _psnr / _ssim, host only): {"mse": {class name: value, ...,
+        "all": every class but unwritten}, "psnr": ..., "ssim": ..., "profile_mse": the 64 rings' mean squared error}; NaN where a
+        class or ring is empty."""
+        L = lib.load_loader()
+        keys = list(enumerate(abi.QUALITY_CLASS_NAMES)) + [(-1, "all")]
+        out = {what: {name: float(getattr(L, "fovpt_quality_" + what)(C.byref(sums), k)) for k, name in keys} for what in ("mse", "psnr", "ssim")}
+        out["profile_mse"] = [float(s) / (3.0 * float(n)) if n else float("nan") for s, n in zip(sums.ring_sq_err, sums.ring_pixels)]
+        return out
+
+    @staticmethod
+    def quality_score(sums, weights) -> float:
+        """fovpt_quality_score: the mean squared error with the five classes weighted (fovea, middle, periphery, uniform, unwritten)."""
+        w = (C.c_double * abi.QUALITY_CLASSES)(*[float(v) for v in weights])
+        return float(lib.load_loader().fovpt_quality_score(C.byref(sums), w))
+
+    def _quality_image(self, who, image):
+        """A device pointer as it is; an (H, W) uint32 numpy image of the frame's size uploaded (kept until the next read)."""
+        if image is None or isinstance(image, int):
+            return image
+        import torch
+        f = self.launchParams.frame
+        a = np.ascontiguousarray(image)
+        if a.dtype != np.uint32 or a.shape != (f.size.y, f.size.x):
+            raise ValueError("%s: a host image must be a (%d, %d) uint32 array" % (who, f.size.y, f.size.x))
+        t = torch.from_numpy(a.view(np.int32)).to("cuda:%d" % self._device)
+        torch.cuda.synchronize(self._device)
+        self._quality_keep.append(t)
+        return t.data_ptr()
+
+    def qualityAsync(self, ref_rgba, test_rgba=None, config=None, out_sums=None, out_class=None):
+        """Enqueues one measurement of the frame last rendered on the renderer's stream, not synchronised: test_rgba (None: the
+        frame buffer) against ref_rgba, each a device pointer of an rgba8 image of the frame's size or an (H, W) uint32 numpy array.
+        config None: quality_defaults().  out_sums: device pointer of an abi.QualitySums record, None: the renderer's own
+        (readQuality); with records of the caller's any number of measurements may be in flight.  out_class: device pointer of one
+        byte per pixel for the pixels' classes, or None."""
+        if not hasattr(self, "_quality_keep"):
+            self._quality_keep = []
+        cfg = config if config is not None else self.quality_defaults()
+        ref, test = self._quality_image("qualityAsync", ref_rgba), self._quality_image("qualityAsync", test_rgba)
+        self._check(self._L.fovpt_quality(self._ctx, C.byref(self.launchParams), C.byref(cfg), test, ref, out_sums, out_class))
+
+    def readQuality(self, sums=False):
+        """Waits for the renderer's stream and returns the renderer's own record as a dict: the fields of abi.QualitySums as Python
+        integers and lists, and the derived scores of quality_scores().  sums=True: the abi.QualitySums itself."""
+        s = abi.QualitySums()
+        self._check(self._L.fovpt_quality_read(self._ctx, C.byref(s)))
+        self._quality_keep = []
+        if sums:
+            return s
+        out = s.as_dict()
+        out.update(self.quality_scores(s))
+        return out
+
+    def measureQuality(self, ref_rgba, test_rgba=None, config=None, classes=False):
+        """qualityAsync into the renderer's own record, then readQuality: the dict of the sums and the derived scores.
+        classes=True: also "classes", the (H, W) uint8 class of every pixel (abi.QUALITY_FOVEA ..)."""
+        cls = None
+        if classes:
+            import torch
+            f = self.launchParams.frame
+            cls = torch.zeros((f.size.y, f.size.x), dtype=torch.uint8, device="cuda:%d" % self._device)
+            torch.cuda.synchronize(self._device)
+        self.qualityAsync(ref_rgba, test_rgba, config, None, cls.data_ptr() if cls is not None else None)
+        out = self.readQuality()
+        if cls is not None:
+            out["classes"] = cls.cpu().numpy()
+        return out
+
     # -- foveated frame packets (include/fovpt.h, fovpt_packet_*): a frame off the device, small and without stopping the renderer
     def packetConfig(self, codec=True) -> abi.PacketConfig:
         """The fovpt_packet_config of a codec= argument: True -> fovpt_packet_defaults (BC1 where a pass's fill is above 1), a

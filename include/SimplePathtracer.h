@@ -412,6 +412,35 @@ public:
         if (h_color) check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * n));
         if (h_pixels) check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * n));
     }
+    // ---- image quality of the frame last rendered (include/fovpt.h, fovpt_quality): test_rgba (null: the frame buffer) against
+    // ref_rgba, device rgba8 images of the frame's size -> per-class error sums, SSIM sums and the eccentricity profile; the scores
+    // of a record are fovpt_quality_mse / _psnr / _ssim / _score.  measureQuality() measures into the renderer's own record and
+    // reads it (a device sync); qualityAsync() only enqueues (out_sums: a device record of the caller's, null: the renderer's own,
+    // which readQuality() returns); out_class (device, may be null): one byte per pixel, its class
+    static fovpt_quality_config qualityDefaults()
+    {
+        fovpt_quality_config qc;
+        if (fovpt_quality_defaults(&qc) != FOVPT_OK) throw std::runtime_error("fovpt_quality_defaults failed");
+        return qc;
+    }
+    void qualityAsync(const uint32_t* ref_rgba, const uint32_t* test_rgba = nullptr, const fovpt_quality_config* qc = nullptr,
+                      fovpt_quality_sums* out_sums = nullptr, uint8_t* out_class = nullptr)
+    {
+        const fovpt_quality_config d = qc ? *qc : qualityDefaults();
+        check(fovpt_quality(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &d, test_rgba, ref_rgba, out_sums, out_class));
+    }
+    fovpt_quality_sums readQuality()
+    {
+        fovpt_quality_sums s;
+        check(fovpt_quality_read(ctx, &s));
+        return s;
+    }
+    fovpt_quality_sums measureQuality(const uint32_t* ref_rgba, const uint32_t* test_rgba = nullptr, const fovpt_quality_config* qc = nullptr,
+                                      uint8_t* out_class = nullptr)
+    {
+        qualityAsync(ref_rgba, test_rgba, qc, nullptr, out_class);
+        return readQuality();
+    }
     // ---- foveated frame packets (include/fovpt.h, fovpt_packet_*): the frame last rendered -- in_rgba null: the renderer's own
     // frame buffer; or the rgba8 output of post() / expose() -- as a small self-describing packet in pinned host memory, without a
     // device sync: submitPacket() returns at once with a slot, later frames keep rendering, waitPacket(slot) waits for that

@@ -1288,6 +1288,97 @@ int fovpt_lens(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_lens_c
                fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */);
 int fovpt_lens_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 
+/* ---- image quality of a foveated frame: per-level error, SSIM and eccentricity profile -------------------------------------------
+ * New with this library.  Choosing radii, spp, denoiser iterations, history caps or BC1 for a level asks one question: how good is
+ * the frame, and where in the visual field does its error sit?  fovpt_quality answers it on the device, in stream order, with no
+ * host synchronisation: it compares two display-referred rgba8 images of the frame last rendered (a test image against a
+ * reference: a converged render, the uncoded frame, ...) and leaves exact integer sums in a small device record.  Everything in it
+ * is an integer, or one binary64 quotient of exact integers, so the result does not depend on grid, block or summation order.
+ *   fovpt_quality            works on the frame last issued with fovpt_render(ctx, lp) as it was rendered (its passes, its gaze
+ *                            frame.c and its FOV_OFF flag).  test_rgba NULL = lp->frame.frame_buffer; out_sums NULL = the context's
+ *                            own record (fovpt_quality_read; made on first use, freed by fovpt_destroy); out_class: one byte per
+ *                            pixel, or NULL.  test_rgba may be ref_rgba (all errors zero).  Enqueued on fovpt_stream(), not
+ *                            synchronised, ordered like fovpt_denoise; with caller-provided out_sums records any number of
+ *                            measurements may be in flight.  Writes out_sums (every byte), out_class if given and its own scratch,
+ *                            nothing else.  The definition, operation by operation (tests/quality_ref.py), with R, G, B the low
+ *                            three bytes of a pixel (alpha is ignored), T the test and F the reference image:
+ *                              1 class       of pixel (x, y): UNWRITTEN where no pass of the frame writes the pixel; otherwise
+ *                                            UNIFORM on a FOV_OFF frame; otherwise by the fill of the pixel's last writer (as
+ *                                            fovpt_expose's METER_GAZE): 4 PERIPHERY, 2 MIDDLE, anything else FOVEA.
+ *                                            out_class[y * w + x] = that class
+ *                              2 error sums  per class k: pixels[k] += 1; sq_err[k][c] += (T_c - F_c)^2 for c = r, g, b;
+ *                                            differing[k] += 1 if any channel differs; max_err[k] = max(max_err[k], max_c |T_c - F_c|)
+ *                              3 profile     (QUALITY_PROFILE, else both arrays 0) dx = x - (int64)(int32)frame.c.x, dy likewise,
+ *                                            d2 = dx^2 + dy^2, ring = min(63, isqrt(d2) / ring_width) with isqrt the floor integer
+ *                                            square root; ring_pixels[ring] += 1, ring_sq_err[ring] += the three channels' squared
+ *                                            differences.  Every pixel counts, whatever its class
+ *                              4 SSIM        (QUALITY_SSIM, else windows and ssim_q20 0) luma Y = (54 R + 183 G + 19 B + 128) >> 8.
+ *                                            Windows are 8 x 8 pixels with origins (4i, 4j), 4i + 8 <= w, 4j + 8 <= h (a frame
+ *                                            narrower or lower than 8 has none).  With the integer sums sx, sy, sxx, syy, sxy of a
+ *                                            window's test (x) and reference (y) luma and C1 = 26634, C2 = 239708 ((0.01 * 255)^2
+ *                                            * 4096 and (0.03 * 255)^2 * 4096, rounded), in int64:
+ *                                              A = 2 sx sy + C1, B = 2 (64 sxy - sx sy) + C2, C = sx^2 + sy^2 + C1,
+ *                                              D = (64 sxx - sx^2) + (64 syy - sy^2) + C2, N = A B, M = C D (|N|, M < 2^57),
+ *                                              q = (int64)rint(((double)N / (double)M) * 1048576.0)
+ *                                            every operation one IEEE binary64 operation, the conversions round to nearest even.
+ *                                            The window's class k is that of pixel (x0 + 4, y0 + 4): windows[k] += 1, ssim_q20[k] += q
+ *                              5 header      width, height, ring_width, flags echo the call; _pad = 0
+ *                            All or nothing, checked before anything is enqueued.  FOVPT_E_INVALID: null ctx / lp / cfg / ref_rgba;
+ *                            unknown flag bits; ring_width outside 1 .. FOVPT_QUALITY_MAX_RING_WIDTH; non-zero reserved fields; a
+ *                            frame rendered with world > 1 (a shard does not see the frame); width * height >= 2^31; test_rgba NULL
+ *                            with a null frame_buffer.  FOVPT_E_NO_FRAME: nothing rendered since create / resize, or
+ *                            lp->frame.size differs.
+ *   fovpt_quality_defaults   host only, no context.  SSIM | PROFILE; ring_width 16 is A CONVENTION, NOT A MEASUREMENT.
+ *   fovpt_quality_read       synchronises fovpt_stream() and copies the context's own record out (all zero before the first
+ *                            fovpt_quality with out_sums NULL).
+ *   fovpt_quality_host       the same definition on host images, host only, no context, no device (also in libfovpt_loader.so):
+ *                            the classes are handed in (one byte per pixel, each below FOVPT_QUALITY_CLASSES; NULL: all UNIFORM),
+ *                            and the gaze as two integers.  FOVPT_E_INVALID: null test / ref / cfg / out, w or h < 1,
+ *                            w * h >= 2^31, a bad config, a class byte out of range.
+ *   fovpt_quality_mse / _psnr / _ssim / _score   host only, binary64, of a record (cls -1: every class but UNWRITTEN):
+ *                            mse = sum_c sq_err / (3 pixels); psnr = 10 log10(65025 / mse), +inf at mse 0; ssim = ssim_q20 /
+ *                            (1048576 windows); score = sum_k w_k sum_c sq_err[k] / (3 sum_k w_k pixels[k]), a weighted mse over the
+ *                            five classes.  NaN for an empty class (no pixels, no windows, no weight), a null record or a cls
+ *                            outside -1 .. 4.
+ * On an MI355X at 1920 x 1080 a call takes 0.054 ms with no flags, 0.061 ms with SSIM, 0.059 ms with PROFILE and 0.079 ms with both,
+ * measured beside fovpt_expose AUTO / METER_GAZE (one writer search per pixel and a two-kernel reduction too: 0.063 ms), fovpt_expose
+ * FIXED (0.021 ms) and one fovpt_render of that frame (0.633 ms): 0.86, 0.96, 0.94 and 1.26 times AUTO / GAZE. */
+#define FOVPT_QUALITY_SSIM     1   /* also the SSIM sums            */
+#define FOVPT_QUALITY_PROFILE  2   /* also the eccentricity profile */
+#define FOVPT_QUALITY_CLASSES  5
+#define FOVPT_QUALITY_FOVEA     0
+#define FOVPT_QUALITY_MIDDLE    1
+#define FOVPT_QUALITY_PERIPHERY 2
+#define FOVPT_QUALITY_UNIFORM   3
+#define FOVPT_QUALITY_UNWRITTEN 4
+#define FOVPT_QUALITY_RINGS    64
+#define FOVPT_QUALITY_MAX_RING_WIDTH 65536
+typedef struct fovpt_quality_config {     /* 32 bytes */
+    int32_t flags;                        /* FOVPT_QUALITY_SSIM | FOVPT_QUALITY_PROFILE */
+    int32_t ring_width;                   /* pixels per ring of the profile, 1 .. FOVPT_QUALITY_MAX_RING_WIDTH */
+    int32_t _reserved[6];
+} fovpt_quality_config;
+typedef struct fovpt_quality_sums {       /* 1344 bytes */
+    uint64_t pixels[FOVPT_QUALITY_CLASSES], differing[FOVPT_QUALITY_CLASSES], sq_err[FOVPT_QUALITY_CLASSES][3];
+    uint32_t max_err[FOVPT_QUALITY_CLASSES], _pad;
+    uint64_t windows[FOVPT_QUALITY_CLASSES];
+    int64_t ssim_q20[FOVPT_QUALITY_CLASSES];
+    uint64_t ring_pixels[FOVPT_QUALITY_RINGS], ring_sq_err[FOVPT_QUALITY_RINGS];
+    uint32_t width, height, ring_width, flags;
+} fovpt_quality_sums;
+int fovpt_quality_defaults(fovpt_quality_config* out);
+int fovpt_quality(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_quality_config* qc,
+                  const uint32_t* test_rgba /* NULL: lp->frame.frame_buffer */, const uint32_t* ref_rgba,
+                  fovpt_quality_sums* out_sums /* device; NULL: the context's own record */,
+                  uint8_t* out_class /* device, one byte per pixel, or NULL */);
+int fovpt_quality_read(fovpt_ctx* ctx, fovpt_quality_sums* out /* host */);
+int fovpt_quality_host(const uint32_t* test, const uint32_t* ref, int w, int h, const uint8_t* classes /* NULL: all UNIFORM */,
+                       int64_t gaze_x, int64_t gaze_y, const fovpt_quality_config* qc, fovpt_quality_sums* out);
+double fovpt_quality_mse(const fovpt_quality_sums* s, int cls /* -1: all classes but UNWRITTEN */);
+double fovpt_quality_psnr(const fovpt_quality_sums* s, int cls);
+double fovpt_quality_ssim(const fovpt_quality_sums* s, int cls);
+double fovpt_quality_score(const fovpt_quality_sums* s, const double weights[FOVPT_QUALITY_CLASSES]);
+
 /* ---- foveated frame packets: a frame off the device, small and without stopping the renderer -----------------------------------
  * New with this library.  fovpt_download drains every stream and copies a whole frame into pageable memory.  A foveated frame
  * is described exactly by one value per launch index -- at the shipped radii 74 / 241 a 1920 x 1080 frame has 211 149 of them,
@@ -1796,6 +1887,9 @@ static_assert(sizeof(fovpt_focus_config) == 64 && offsetof(fovpt_focus_config, s
 static_assert(sizeof(struct fovpt_focus_state) == 32 && offsetof(struct fovpt_focus_state, count) == 16, "focus state ABI");
 static_assert(sizeof(fovpt_lens_config) == 128 && offsetof(fovpt_lens_config, k) == 32 && offsetof(fovpt_lens_config, clip_r2) == 60 &&
               offsetof(fovpt_lens_config, border) == 80 && offsetof(fovpt_lens_config, _reserved) == 96, "lens config ABI");
+static_assert(sizeof(fovpt_quality_config) == 32 && offsetof(fovpt_quality_config, _reserved) == 8, "quality config ABI");
+static_assert(sizeof(fovpt_quality_sums) == 1344 && offsetof(fovpt_quality_sums, max_err) == 200 && offsetof(fovpt_quality_sums, windows) == 224 &&
+              offsetof(fovpt_quality_sums, ring_pixels) == 304 && offsetof(fovpt_quality_sums, width) == 1328, "quality sums ABI");
 static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");
 static_assert(sizeof(fovpt_packet_config) == 16 && offsetof(fovpt_packet_config, _reserved) == 12, "packet config ABI");
 static_assert(sizeof(fovpt_packet_header) == 128 && offsetof(fovpt_packet_header, width) == 16 && offsetof(fovpt_packet_header, pass) == 32,
