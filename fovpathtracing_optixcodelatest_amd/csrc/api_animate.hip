@@ -14,8 +14,6 @@
 
 #include "fovpt_ctx.h"
 
-#define CHK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
-
 namespace {
 
 // What the entry points check first, in this order: open() the context, the scene, the count and the array (`what`: the

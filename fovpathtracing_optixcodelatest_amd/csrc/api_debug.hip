@@ -32,7 +32,7 @@ hipError_t download(void* dst, const DevBuf& b, size_t n) { return dst ? hipMemc
 // An idle state set for a hook, as a job of `slots` sample slots and `launches` launch records sizes it, and its shard capacity
 int debug_state(fovpt_ctx* c, size_t slots, size_t launches, StateSet*& S, uint32_t& cap)
 {
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     S = &c->set[(c->last_set + 1u) % 2u];                           // (the device is idle: any set will do)
     cap = shard_capacity(slots);
     return ensure_state(c, *S, slots, launches, c->stream);
@@ -57,7 +57,7 @@ int debug_frame(fovpt_ctx* c, const fovpt_launch_params* lp, int render, uint32_
         all_slots += (uint64_t)P[p].gw * (P[p].row1 - P[p].row0) * P[p].spp;
     }
     if (all_slots > c->slot_budget) return fail(c, FOVPT_E_INVALID, "%s: %llu sample slots would run as several jobs", who, (unsigned long long)all_slots);
-    { const int rc_ = frame_dev(c, lp, P, npass, chunk ? 1 : 0, render ? 1 : 0, fd, slots, launches); if (rc_) return rc_; }
+    CHK(frame_dev(c, lp, P, npass, chunk ? 1 : 0, render ? 1 : 0, fd, slots, launches));
     *npass_out = npass;
     for (int p = 0; p < npass; p++) {
         const PassDev& D = fd.pass[p];
@@ -220,7 +220,7 @@ int trace_queued(fovpt_ctx* c, const fovpt_debug_trace_launch* in, fovpt_debug_t
     if (!out->cells4 || !out->alpha4 || (N && (!out->hit_place2 || !out->hit4 || !out->hit_prim))) return FOVPT_E_INVALID;
     // the state: the queues of a job of `slots` sample slots, the cells of all N + 1
     StateSet* set = nullptr; uint32_t cap_state = 0;
-    { const int rc_ = debug_state(c, slots > N + 1 ? slots : N + 1, 1, set, cap_state); if (rc_) return rc_; }
+    CHK(debug_state(c, slots > N + 1 ? slots : N + 1, 1, set, cap_state));
     StateSet& S = *set;
     hipStream_t st = c->stream;
     const size_t v = 16, qn = (size_t)cap * FOVPT_SHARDS;
@@ -281,7 +281,7 @@ int trace_queued(fovpt_ctx* c, const fovpt_debug_trace_launch* in, fovpt_debug_t
     HIPCHK(c, hipMemcpyAsync(out->cells4, S.s_rad.p, (N + 1) * v * D, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(out->alpha4, S.s_alpha.p, (N + 1) * v, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(stat1, &cnt->stat_radiance, sizeof(stat1), hipMemcpyDeviceToHost, st));
-    { const int rc_ = take_counters(c, S, cw, st); if (rc_) return rc_; }
+    CHK(take_counters(c, S, cw, st));
     out->cap = cap;
     out->stat_radiance = stat1[0] - stat0[0]; out->stat_shadow = stat1[1] - stat0[1]; out->stat_paths = stat1[2] - stat0[2];
     out->counters_changed = counters_changed(cw, was, -1, -1);
@@ -327,13 +327,13 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "rig_world") == 0 && c->rig.set) { *ptr = c->rig.dev.world; *bytes = 48 * (size_t)c->rig.dev.num_nodes; return FOVPT_OK; }   // what k_rig_pose last wrote
     if (strcmp(name, "rig_rigid") == 0 && c->rig.set) { *ptr = c->rig.dev.rigid; *bytes = 48 * (size_t)c->rig.dev.num_rigid; return FOVPT_OK; }
     if (strcmp(name, "rig_palette") == 0 && c->rig.set) { *ptr = c->rig.dev.palette; *bytes = 48 * (size_t)c->rig.dev.num_pal; return FOVPT_OK; }
-    if (strcmp(name, "post_color") == 0 && c->po_color.p) { *ptr = c->po_color.p; *bytes = c->po_color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
-    if (strcmp(name, "expose_histogram") == 0 && c->ex_hist.p) { *ptr = c->ex_hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
-    if (strcmp(name, "expose_state") == 0 && c->ex_state.p) { *ptr = c->ex_state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
-    if (strcmp(name, "warp_keys") == 0 && c->wp_keys.p) { *ptr = c->wp_keys.p; *bytes = c->wp_keys.bytes; return FOVPT_OK; }   // fovpt_warp's keys, once made
-    if (strcmp(name, "focus_state") == 0 && c->fc_state.p) { *ptr = c->fc_state.p; *bytes = sizeof(FocusState); return FOVPT_OK; }   // fovpt_focus's state record
-    if (strcmp(name, "focus_scratch") == 0 && c->fc_rt.p) { *ptr = c->fc_rt.p; *bytes = c->fc_rt.bytes; return FOVPT_OK; }   // and its (r, tp) pairs, once made
-    if (strcmp(name, "gbuffer_hit") == 0 && c->gb_hit.p) { *ptr = c->gb_hit.p; *bytes = c->gb_pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
+    if (strcmp(name, "post_color") == 0 && c->post.out.color.p) { *ptr = c->post.out.color.p; *bytes = c->post.out.color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
+    if (strcmp(name, "expose_histogram") == 0 && c->expose.hist.p) { *ptr = c->expose.hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
+    if (strcmp(name, "expose_state") == 0 && c->expose.state.p) { *ptr = c->expose.state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
+    if (strcmp(name, "warp_keys") == 0 && c->warp.keys.p) { *ptr = c->warp.keys.p; *bytes = c->warp.keys.bytes; return FOVPT_OK; }   // fovpt_warp's keys, once made
+    if (strcmp(name, "focus_state") == 0 && c->focus.state.p) { *ptr = c->focus.state.p; *bytes = sizeof(FocusState); return FOVPT_OK; }   // fovpt_focus's state record
+    if (strcmp(name, "focus_scratch") == 0 && c->focus.rt.p) { *ptr = c->focus.rt.p; *bytes = c->focus.rt.bytes; return FOVPT_OK; }   // and its (r, tp) pairs, once made
+    if (strcmp(name, "gbuffer_hit") == 0 && c->gbuffer.hit.p) { *ptr = c->gbuffer.hit.p; *bytes = c->gbuffer.pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
     StateSet& S = c->set[c->last_set];                    // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {
         {"sq_o", &S.sq_o[0]}, {"sq_d", &S.sq_d[0]}, {"sq_vis", &S.sq_vis[0]}, {"sq_occ", &S.sq_occ[0]}, {"counters", &S.counters},
@@ -364,7 +364,7 @@ int fovpt_debug_trace(fovpt_ctx* c, int n, const float* origins3, const float* d
     fovpt_debug_trace_result R;
     memset(&R, 0, sizeof(R));
     R.hit_place2 = place.data(); R.hit4 = hit.data(); R.hit_prim = prim.data(); R.cells4 = cells.data(); R.alpha4 = alpha.data();
-    { const int rc_ = trace_queued(c, &L, &R, "fovpt_debug_trace"); if (rc_) return rc_; }
+    CHK(trace_queued(c, &L, &R, "fovpt_debug_trace"));
     if (R.hit_found != (uint32_t)n) return fail(c, FOVPT_E_DEVICE, "fovpt_debug_trace: %u hit records for %d rays", R.hit_found, n);
     for (size_t i = 0; i < un; i++) {
         if (place[2 * i] != 0u || place[2 * i + 1] != (uint32_t)i) return fail(c, FOVPT_E_DEVICE, "fovpt_debug_trace: a hit record at (%u, %u)", place[2 * i], place[2 * i + 1]);
@@ -393,7 +393,7 @@ int fovpt_debug_build(fovpt_ctx* c, uint32_t n, const float* tris9, const uint32
 {
     if (!c || !tris9 || !sw || !out || n == 0 || n > (1u << 24)) return FOVPT_E_INVALID;
     if (!(sw->split_budget >= 0.f) || sw->split_budget > 2.f || sw->reinsert_rounds < 0) return fail(c, FOVPT_E_INVALID, "fovpt_debug_build: switches out of range");
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     DevBuf d_flat, d_mesh;
     HIPCHK(c, upload(d_flat, tris9, 36ull * n));
     HIPCHK(c, d_mesh.reserve(4ull * n));
@@ -469,7 +469,7 @@ int fovpt_debug_shade(fovpt_ctx* c, const fovpt_probe* probe, const fovpt_debug_
         return FOVPT_E_INVALID;
     const size_t slots = (un ? un : 1u) * FOVPT_SHARDS;             // any one shard can hold everything
     StateSet* set = nullptr; uint32_t cap = 0;
-    { const int rc_ = debug_state(c, slots, 1, set, cap); if (rc_) return rc_; }
+    CHK(debug_state(c, slots, 1, set, cap));
     StateSet& S = *set;
     hipStream_t st = c->stream;
     const size_t qn = (size_t)cap * FOVPT_SHARDS, v = 16;
@@ -542,7 +542,7 @@ int fovpt_debug_shade(fovpt_ctx* c, const fovpt_probe* probe, const fovpt_debug_
         }
     }
     for (int k = 0; k < 6; k++) { back[k].resize(qn * 4); HIPCHK(c, hipMemcpyAsync(back[k].data(), outq[k]->p, qn * v, hipMemcpyDeviceToHost, st)); }
-    { const int rc_ = take_counters(c, S, cw, st); if (rc_) return rc_; }
+    CHK(take_counters(c, S, cw, st));
     out->cap = cap;
     for (uint32_t s = 0; s < FOVPT_SHARDS; s++) {
         out->next_count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + w_next];
@@ -572,13 +572,13 @@ int fovpt_debug_resolve(fovpt_ctx* c, const fovpt_launch_params* lp, int render,
     if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
     FrameDev fd;
     uint64_t slots = 0, launches = 0;
-    { const int rc_ = debug_frame(c, lp, render, width, height, 0u, 0u, "fovpt_debug_resolve", fd, slots, launches, passes_out, npass_out); if (rc_) return rc_; }
+    CHK(debug_frame(c, lp, render, width, height, 0u, 0u, "fovpt_debug_resolve", fd, slots, launches, passes_out, npass_out));
     if (!state) return FOVPT_OK;
     if (counters_left_out) *counters_left_out = 0u;
     if (slots == 0) return FOVPT_OK;                                  // (a job of no sample slots launches nothing)
     if (!cells4 || !alpha4 || !backplate4 || (c->cfg.write_guides && (!guide_n4 || !guide_a4))) return FOVPT_E_INVALID;
     StateSet* set = nullptr; uint32_t cap = 0;
-    { const int rc_ = debug_state(c, (size_t)slots, (size_t)launches, set, cap); if (rc_) return rc_; }
+    CHK(debug_state(c, (size_t)slots, (size_t)launches, set, cap));
     StateSet& S = *set;
     hipStream_t st = c->stream;
     std::vector<uint32_t> rng((size_t)slots * 4, 0xdeadbeefu);        // the generator's words: nothing in a resolve reads them
@@ -597,7 +597,7 @@ int fovpt_debug_resolve(fovpt_ctx* c, const fovpt_launch_params* lp, int render,
     HIPCHK(c, put_counters(S, left, st));
     fovpt_launch_resolve(st, fd, path_state(c, S), (Counters*)S.counters.p);       // as run_job launches it
     HIPCHK(c, hipGetLastError());
-    { const int rc_ = take_counters(c, S, left, st); if (rc_) return rc_; }          // (zeros from here on, whatever the kernel did)
+    CHK(take_counters(c, S, left, st));          // (zeros from here on, whatever the kernel did)
     uint32_t nonzero = 0;
     for (uint32_t w : left) nonzero += w != 0u;
     if (counters_left_out) *counters_left_out = nonzero;
@@ -625,7 +625,7 @@ int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovp
         return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: launch rows [%u, %u) of %u", in->row0, in->row1, in->height);
     FrameDev fd;
     uint64_t slots = 0, launches = 0;
-    { const int rc_ = debug_frame(c, lp, in->render, in->width, in->height, in->row0, in->row1, "fovpt_debug_generate", fd, slots, launches, passes_out, npass_out); if (rc_) return rc_; }
+    CHK(debug_frame(c, lp, in->render, in->width, in->height, in->row0, in->row1, "fovpt_debug_generate", fd, slots, launches, passes_out, npass_out));
     if (!out) return FOVPT_OK;
     // the launch: what run_job would give a launch of this `sel`, unless the caller says otherwise
     const uint32_t sel = in->sel;
@@ -646,7 +646,7 @@ int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovp
     if (slots == 0) return FOVPT_OK;                                  // (a job of no sample slots launches nothing)
     if (!out->rng4 || !out->backplate4 || (guides && (!out->guide_n4 || !out->guide_a4)) || !out->place2 || !out->o4 || !out->d4) return FOVPT_E_INVALID;
     StateSet* set = nullptr; uint32_t cap = 0;
-    { const int rc_ = debug_state(c, (size_t)slots, (size_t)launches, set, cap); if (rc_) return rc_; }
+    CHK(debug_state(c, (size_t)slots, (size_t)launches, set, cap));
     StateSet& S = *set;
     hipStream_t st = c->stream;
     const size_t v = 16, qn = (size_t)cap * FOVPT_SHARDS + (size_t)slots + 256u;
@@ -673,7 +673,7 @@ int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovp
     }
     HIPCHK(c, hipMemcpyAsync(q[0].data(), scratch.o, qn * v, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(q[1].data(), scratch.d, qn * v, hipMemcpyDeviceToHost, st));
-    { const int rc_ = take_counters(c, S, cw, st); if (rc_) return rc_; }
+    CHK(take_counters(c, S, cw, st));
     for (uint32_t s = 0; s < FOVPT_SHARDS; s++) out->count[s] = cw[(size_t)s * FOVPT_SHARD_STRIDE + FOVPT_CNT_Q(0)];
     out->counters_changed = counters_changed(cw, was, FOVPT_CNT_Q(0), -1);
     // the occupied entries of the scratch queue (an entry of the guard region behind the eight shards reports a shard of 8 or
@@ -685,31 +685,31 @@ int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovp
 
 int fovpt_debug_probe_sample(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const float* r12, int32_t* rowcol_out2, float* out7, int* path_out)
 {
-    { const int rc_ = debug_probe_args(c, probe, flags, n, r12, "fovpt_debug_probe_sample"); if (rc_) return rc_; }
+    CHK(debug_probe_args(c, probe, flags, n, r12, "fovpt_debug_probe_sample"));
     // Randf's range (maths.h:199-210): what the searches may be handed
     for (size_t i = 0; i < 2 * (size_t)n; i++)
         if (!(r12[i] >= 0.0f && r12[i] <= 0.999999f)) return fail(c, FOVPT_E_INVALID, "fovpt_debug_probe_sample: number %zu (%g) is outside [0, 0.999999]", i, (double)r12[i]);
     const ProbePath pp = debug_probe_path(c, *probe, flags, path_out);
     if (n == 0) return FOVPT_OK;
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     DevBuf in, rowcol, out;
     HIPCHK(c, upload(in, r12, (size_t)n * 8)); HIPCHK(c, rowcol.reserve((size_t)n * 8)); HIPCHK(c, out.reserve((size_t)n * 28));
     fovpt_launch_debug_probe_sample(c->stream, *probe, pp.guide_x, pp.guide_y, pp.rec, pp.row_mul, n, (const float2*)in.p, (int2*)rowcol.p, (float*)out.p);
-    { const int rc_ = debug_end(c); if (rc_) return rc_; }
+    CHK(debug_end(c));
     HIPCHK(c, download(rowcol_out2, rowcol, (size_t)n * 8)); HIPCHK(c, download(out7, out, (size_t)n * 28));
     return FOVPT_OK;
 }
 
 int fovpt_debug_probe_eval(fovpt_ctx* c, const fovpt_probe* probe, int flags, int n, const float* dirs3, float* out6, int* path_out)
 {
-    { const int rc_ = debug_probe_args(c, probe, flags, n, dirs3, "fovpt_debug_probe_eval"); if (rc_) return rc_; }
+    CHK(debug_probe_args(c, probe, flags, n, dirs3, "fovpt_debug_probe_eval"));
     const ProbePath pp = debug_probe_path(c, *probe, flags, path_out);
     if (n == 0) return FOVPT_OK;
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     DevBuf in, out;
     HIPCHK(c, upload(in, dirs3, (size_t)n * 12)); HIPCHK(c, out.reserve((size_t)n * 24));
     fovpt_launch_debug_probe_eval(c->stream, *probe, pp.row_mul, n, (const float*)in.p, (float*)out.p);
-    { const int rc_ = debug_end(c); if (rc_) return rc_; }
+    CHK(debug_end(c));
     HIPCHK(c, download(out6, out, (size_t)n * 24));
     return FOVPT_OK;
 }
@@ -719,7 +719,7 @@ int fovpt_debug_bsdf(fovpt_ctx* c, const fovpt_material* material, int n, const 
 {
     if (!c || !material || n < 0 || (n && (!N3 || !view3 || !albedo3 || !etaI || !etaO || !seeds || !L_given3))) return FOVPT_E_INVALID;
     if (n == 0) return FOVPT_OK;
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     std::vector<float> rows((size_t)n * 16, 0.f), res((size_t)n * 16);
     for (int i = 0; i < n; i++) {
         float* r = &rows[16 * (size_t)i];
@@ -730,7 +730,7 @@ int fovpt_debug_bsdf(fovpt_ctx* c, const fovpt_material* material, int n, const 
     DevBuf in, out;
     HIPCHK(c, upload(in, rows.data(), (size_t)n * 64)); HIPCHK(c, out.reserve((size_t)n * 64));
     fovpt_launch_debug_bsdf(c->stream, *material, n, (const float*)in.p, (float*)out.p);
-    { const int rc_ = debug_end(c); if (rc_) return rc_; }
+    CHK(debug_end(c));
     HIPCHK(c, download(res.data(), out, (size_t)n * 64));
     if (out14) for (int i = 0; i < n; i++) memcpy(out14 + 14 * (size_t)i, &res[16 * (size_t)i], 56);
     return FOVPT_OK;
@@ -742,11 +742,11 @@ int fovpt_debug_tex2d(fovpt_ctx* c, int texture, int n, const float* uv2, float*
     if (!c->has_scene) return fail(c, FOVPT_E_NO_SCENE, "fovpt_debug_tex2d without a scene");
     if (texture < 0 || (size_t)texture >= c->tex_pixels.size()) return fail(c, FOVPT_E_INVALID, "fovpt_debug_tex2d: texture %d of %zu", texture, c->tex_pixels.size());
     if (n == 0) return FOVPT_OK;
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     DevBuf in, out;
     HIPCHK(c, upload(in, uv2, (size_t)n * 8)); HIPCHK(c, out.reserve((size_t)n * 16));
     fovpt_launch_debug_tex2d(c->stream, (const TexDev*)c->textures.p, texture, n, (const float2*)in.p, (float4*)out.p);
-    { const int rc_ = debug_end(c); if (rc_) return rc_; }
+    CHK(debug_end(c));
     HIPCHK(c, download(rgba_out4, out, (size_t)n * 16));
     return FOVPT_OK;
 }
@@ -755,12 +755,12 @@ int fovpt_debug_math(fovpt_ctx* c, int op, const float* a, const float* b, float
 {
     if (!c || !a || !out) return FOVPT_E_INVALID;
     if (n == 0) return FOVPT_OK;
-    { const int rc_ = debug_begin(c); if (rc_) return rc_; }
+    CHK(debug_begin(c));
     DevBuf ba, bb, bo;
     HIPCHK(c, upload(ba, a, n * 4)); HIPCHK(c, b ? upload(bb, b, n * 4) : bb.reserve(n * 4)); HIPCHK(c, bo.reserve(n * 4));
     if (!b) HIPCHK(c, hipMemset(bb.p, 0, n * 4));
     fovpt_launch_math(c->stream, op, (const float*)ba.p, (const float*)bb.p, (float*)bo.p, n);
-    { const int rc_ = debug_end(c); if (rc_) return rc_; }
+    CHK(debug_end(c));
     HIPCHK(c, download(out, bo, n * 4));
     return FOVPT_OK;
 }

@@ -13,11 +13,8 @@ namespace {
 // codecs of a coded one, whose a.first[] counts k_packet_encode_coded's threads.
 int packet_args(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, uint32_t sequence, const char* who, PacketArgs& a)
 {
-    if (c->dn_w <= 0 || c->dn_h <= 0) return fail(c, FOVPT_E_NO_FRAME, "%s: no frame rendered yet", who);
-    if (c->dn_world > 1) return fail(c, FOVPT_E_INVALID, "%s: a tile shard (world = %d) does not see the frame", who, c->dn_world);
-    if (lp->frame.size.x != c->dn_w || lp->frame.size.y != c->dn_h)
-        return fail(c, FOVPT_E_NO_FRAME, "%s: frame size %d x %d differs from the last frame's %d x %d", who, lp->frame.size.x, lp->frame.size.y, c->dn_w, c->dn_h);
-    const FrameDev& fd = c->dn_frame;
+    CHK(check_rendered_frame(c, lp, who, nullptr, nullptr, 0));
+    const FrameDev& fd = c->rendered.frame;
     if (cfg) {
         if (cfg->_reserved) return fail(c, FOVPT_E_INVALID, "%s: non-zero reserved word in the packet config", who);
         for (int p = 0; p < FOVPT_MAX_PASSES; p++) {
@@ -83,15 +80,15 @@ int packet_describe(const char* who, bool coded, fovpt_ctx* c, const fovpt_launc
     if (!c) return FOVPT_E_INVALID;
     if (!lp || !out || (coded && !cfg)) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
     PacketArgs a;
-    { const int rc_ = packet_args(c, lp, cfg, sequence, who, a); if (rc_) return rc_; }
+    CHK(packet_args(c, lp, cfg, sequence, who, a));
     *out = a.h;
     return FOVPT_OK;
 }
 
 void launch_encode(fovpt_ctx* c, const PacketArgs& a, const uint32_t* in, uint32_t* out)
 {
-    if (a.h.magic == FOVPT_PACKET_MAGIC_CODED) fovpt_launch_packet_encode_coded(c->shadow_stream, c->dn_frame, a, in, out);
-    else fovpt_launch_packet_encode(c->shadow_stream, c->dn_frame, a, in, out);
+    if (a.h.magic == FOVPT_PACKET_MAGIC_CODED) fovpt_launch_packet_encode_coded(c->shadow_stream, c->rendered.frame, a, in, out);
+    else fovpt_launch_packet_encode(c->shadow_stream, c->rendered.frame, a, in, out);
 }
 
 // Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: behind the frame's resolve, ahead of the next frame's.
@@ -102,7 +99,7 @@ int packet_encode(const char* who, bool coded, fovpt_ctx* c, const fovpt_launch_
     if (!lp || !out_packet || (coded && !cfg)) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
     if (((uintptr_t)out_packet & 3u) != 0u) return fail(c, FOVPT_E_INVALID, "%s: the packet buffer is not 4-byte aligned", who);
     PacketArgs a;
-    { const int rc_ = packet_args(c, lp, cfg, sequence, who, a); if (rc_) return rc_; }
+    CHK(packet_args(c, lp, cfg, sequence, who, a));
     const uint32_t* in = packet_input(lp, in_rgba);
     if (!in) return fail(c, FOVPT_E_NO_FRAME, "%s: null frame_buffer", who);
     HIPCHK(c, hipSetDevice(c->device));
@@ -120,11 +117,11 @@ int packet_submit(const char* who, bool coded, fovpt_ctx* c, const fovpt_launch_
     if (!c) return FOVPT_E_INVALID;
     if (!lp || !slot || (coded && !cfg)) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
     PacketArgs a;
-    { const int rc_ = packet_args(c, lp, cfg, sequence, who, a); if (rc_) return rc_; }
+    CHK(packet_args(c, lp, cfg, sequence, who, a));
     const uint32_t* in = packet_input(lp, in_rgba);
     if (!in) return fail(c, FOVPT_E_NO_FRAME, "%s: null frame_buffer", who);
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = packet_slots(c); if (rc_) return rc_; }
+    CHK(packet_slots(c));
     const int k = (int)(c->pk_next % FOVPT_PACKET_SLOTS);
     fovpt_ctx::PacketSlot& S = c->pk_slot[k];
     if (S.submitted) HIPCHK(c, hipEventSynchronize(S.ev_done));

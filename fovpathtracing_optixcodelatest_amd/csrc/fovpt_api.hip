@@ -3,7 +3,7 @@
 // One context = one device = one stream, like the reference's SampleRenderer
 // (PT_sv5_/SimplePathtracer.cpp:331-340).  Calls on a context are not thread-safe.
 //
-// Animated geometry is in api_animate.hip, the post-processing calls are in api_post.hip, the multi-GPU gather in api_gather.hip, the
+// Animated geometry is in api_animate.hip, the post-processing calls are in api_post.hip and api_view.hip, the multi-GPU gather in api_gather.hip, the
 // frame packets in api_packet.hip, the test hooks (fovpt_debug_*) in api_debug.hip; fovpt_ctx.h is what they share.
 #include <climits>
 #include <cmath>
@@ -351,7 +351,7 @@ static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* p
 {
     FrameDev fd;
     uint64_t slots = 0, launches = 0;
-    { const int rc_ = frame_dev(c, lp, passes_in, npass, chunked, whole_frame, fd, slots, launches); if (rc_) return rc_; }
+    CHK(frame_dev(c, lp, passes_in, npass, chunked, whole_frame, fd, slots, launches));
 
     if (slots == 0) return FOVPT_OK;
     // a refit enqueued on fovpt_stream() since the last job (fovpt_update_vertices): every stream that may trace the scene or read
@@ -682,7 +682,7 @@ int measure_built(fovpt_ctx* c)
 {
     HIPCHK(c, c->cost_partial.reserve(2 * sizeof(double) * (size_t)fovpt_tree_cost_blocks((uint32_t)c->stats.num_bvh_nodes)));
     fovpt_ctx::CostSlot* S = nullptr;
-    { const int rc_ = enqueue_cost(c, c->shadow_stream, c->cost_updates, &S); if (rc_) return rc_; }
+    CHK(enqueue_cost(c, c->shadow_stream, c->cost_updates, &S));
     if (!S) return fail(c, FOVPT_E_DEVICE, "no free cost slot on an idle device");
     HIPCHK(c, hipEventSynchronize(S->ev));
     S->pending = false;
@@ -693,7 +693,7 @@ int measure_built(fovpt_ctx* c)
 
 // The passes fovpt_render ran for the frame lp describes under cfg, whole (rows 0 .. gh) and on one rank: what
 // find_last_writer needs to give every pixel its writing pass and launch index; and lp's camera.  Computed on a copy: the
-// caller's parameters stay as they are.  fovpt_render keeps this for the frame it issued (fovpt_ctx::dn_frame).
+// caller's parameters stay as they are.  fovpt_render keeps this for the frame it issued (fovpt_ctx::rendered).
 void frame_levels(const fovpt_config& cfg, const fovpt_launch_params* lp, FrameDev& fd)
 {
     fovpt_launch_params L = *lp;
@@ -828,12 +828,9 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
     if (!c) return FOVPT_E_INVALID;
     if (!meshes || num_meshes <= 0) return fail(c, FOVPT_E_INVALID, "scene needs at least one mesh");
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     free_scene(c);
-    c->tp_valid = false;                             // fovpt_temporal's history: primitive ids change
-    c->seq_frame = ++c->seq;                         // fovpt_warp_motion: the hit records of the last trace are another scene's
-    { const int rc_ = expose_reset(c, nullptr); if (rc_) return rc_; }   // fovpt_expose adapts to another scene from scratch
-    { const int rc_ = focus_reset(c, nullptr); if (rc_) return rc_; }    // and fovpt_focus meters it from scratch
+    CHK(post_scene_changed(c));
     take_costs(c);                                   // fovpt_hierarchy_cost: (the device is idle) no measurement of the old scene stays in flight
     c->cost_updates = c->cost_measured = 0;
     uint64_t ntri = 0;
@@ -913,7 +910,7 @@ int fovpt_set_scene(fovpt_ctx* c, const fovpt_mesh_desc* meshes, int num_meshes,
 
     BvhBuildResult br;
     float ms = 0.f;
-    { const int rc_ = build_hierarchy(c, c->stream, d_flat, d_mesh_of, (uint32_t)ntri, br, ms); if (rc_) return rc_; }
+    CHK(build_hierarchy(c, c->stream, d_flat, d_mesh_of, (uint32_t)ntri, br, ms));
     adopt_hierarchy(c, br, ms);
     c->stats.num_triangles = ntri;
     c->has_scene = true;
@@ -938,12 +935,11 @@ int fovpt_hierarchy_cost(fovpt_ctx* c, int flags, fovpt_hierarchy_cost_info* out
         fovpt_ctx::CostSlot* S = nullptr;
         for (auto& X : c->cost_slot)
             if (X.pending && X.update == c->cost_updates) S = &X;
-        if (!S) { const int rc_ = enqueue_cost(c, c->shadow_stream, c->cost_updates, &S); if (rc_) return rc_; }
+        if (!S) CHK(enqueue_cost(c, c->shadow_stream, c->cost_updates, &S));
         if (!S && wait) {
             // every slot is in flight with an older tree's measurement: one of them first
             HIPCHK(c, hipEventSynchronize(c->cost_slot[0].ev));
-            const int rc_ = enqueue_cost(c, c->shadow_stream, c->cost_updates, &S);
-            if (rc_) return rc_;
+            CHK(enqueue_cost(c, c->shadow_stream, c->cost_updates, &S));
             if (!S) return fail(c, FOVPT_E_DEVICE, "fovpt_hierarchy_cost: no free slot behind a completed measurement");
         }
         if (wait) { HIPCHK(c, hipEventSynchronize(S->ev)); take_costs(c); }
@@ -961,7 +957,7 @@ int fovpt_set_probe(fovpt_ctx* c, int width, int height, const fovpt_float4* dat
     if (!data || !pdfX || !cdfX || !pdfY || !cdfY || width <= 0 || height <= 0 || !out)
         return fail(c, FOVPT_E_INVALID, "Probe Data is not valid");                         // Probe.h:104-105
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     const size_t n = (size_t)width * height;
     HIPCHK(c, c->pr_pdfx.reserve(n * 4)); HIPCHK(c, c->pr_cdfx.reserve(n * 4));
     HIPCHK(c, c->pr_pdfy.reserve((size_t)height * 4)); HIPCHK(c, c->pr_cdfy.reserve((size_t)height * 4));
@@ -979,7 +975,7 @@ int fovpt_set_probe_data(fovpt_ctx* c, int width, int height, const fovpt_float4
     if (!c) return FOVPT_E_INVALID;
     if (!data || width <= 0 || height <= 0 || !out) return fail(c, FOVPT_E_INVALID, "Probe Data is not valid");
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     const size_t n = (size_t)width * height;
     HIPCHK(c, c->pr_pdfx.reserve(n * 4)); HIPCHK(c, c->pr_cdfx.reserve(n * 4));
     HIPCHK(c, c->pr_pdfy.reserve((size_t)height * 4)); HIPCHK(c, c->pr_cdfy.reserve((size_t)height * 4));
@@ -1005,7 +1001,7 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     if (width == 0 || height == 0) return FOVPT_OK;                                          // :231
     if (width < 0 || height < 0 || !out) return fail(c, FOVPT_E_INVALID, "bad resize arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     const size_t n = (size_t)width * height;
     HIPCHK(c, c->fb_frame.reserve(n * 4)); HIPCHK(c, c->fb_accum.reserve(n * 16));
     HIPCHK(c, c->fb_color.reserve(n * 16)); HIPCHK(c, c->fb_normal.reserve(n * 16)); HIPCHK(c, c->fb_albedo.reserve(n * 16));
@@ -1014,22 +1010,7 @@ int fovpt_resize(fovpt_ctx* c, int width, int height, fovpt_frame_ptrs* out)
     HIPCHK(c, hipMemset(c->fb_color.p, 0, n * 16));
     HIPCHK(c, hipMemset(c->fb_normal.p, 0, n * 16));
     HIPCHK(c, hipMemset(c->fb_albedo.p, 0, n * 16));
-    if (c->dn_color.p) { HIPCHK(c, c->dn_color.reserve(n * 16)); HIPCHK(c, c->dn_rgba.reserve(n * 4)); }   // fovpt_denoise's own outputs follow the frame
-    if (c->gb_prim.p) { const int rc_ = reserve_gbuffer(c, n); if (rc_) return rc_; }                   // so do the G-buffer's
-    if (c->rc_color.p) { HIPCHK(c, c->rc_color.reserve(n * 16)); HIPCHK(c, c->rc_rgba.reserve(n * 4)); }   // and fovpt_reconstruct's
-    if (c->tp_hist[0].p) { const int rc_ = reserve_temporal(c, n); if (rc_) return rc_; }               // and fovpt_temporal's
-    if (c->po_color.p) { HIPCHK(c, c->po_color.reserve(n * 16)); HIPCHK(c, c->po_rgba.reserve(n * 4)); }   // and fovpt_post's
-    if (c->ex_color.p) { HIPCHK(c, c->ex_color.reserve(n * 16)); HIPCHK(c, c->ex_rgba.reserve(n * 4)); }   // and fovpt_expose's (its state stays)
-    if (c->wp_keys.p) HIPCHK(c, c->wp_keys.reserve(n * 8));                                                // and fovpt_warp's keys and outputs
-    if (c->wp_color.p) HIPCHK(c, c->wp_color.reserve(n * 16));
-    if (c->wp_rgba.p) HIPCHK(c, c->wp_rgba.reserve(n * 4));
-    if (c->fc_rt.p) HIPCHK(c, c->fc_rt.reserve(n * 8));                                                    // and fovpt_focus's pairs and outputs (its state stays)
-    if (c->fc_color.p) { HIPCHK(c, c->fc_color.reserve(n * 16)); HIPCHK(c, c->fc_rgba.reserve(n * 4)); }
-    if (c->ln_color.p) { HIPCHK(c, c->ln_color.reserve(n * 16)); HIPCHK(c, c->ln_rgba.reserve(n * 4)); }   // and fovpt_lens's
-    if (c->q_rows.p) HIPCHK(c, c->q_rows.reserve((size_t)fovpt_quality_rows(width, height) * FOVPT_QUALITY_COLUMNS * sizeof(uint64_t)));   // and fovpt_quality's rows (its record stays)
-    c->tp_valid = false;                                                                      // (its history is of another size)
-    c->dn_w = c->dn_h = 0;                                                                    // (nothing rendered at this size yet)
-    c->seq_frame = ++c->seq;                                                                  // (fovpt_warp_motion: nor traced)
+    CHK(post_resize(c, width, height));                                                       // the post-frame stages follow the frame
     out->frame_buffer = (uint32_t*)c->fb_frame.p; out->accum_buffer = (fovpt_float4*)c->fb_accum.p;
     out->color_buffer = (fovpt_float4*)c->fb_color.p; out->normal_buffer = (fovpt_float4*)c->fb_normal.p;
     out->albedo_buffer = (fovpt_float4*)c->fb_albedo.p;
@@ -1078,11 +1059,11 @@ int fovpt_render(fovpt_ctx* c, fovpt_launch_params* lp)
     lp->frame.subframe_index++;
     c->seq_frame = ++c->seq;                                                                  // fovpt_warp_motion: the last trace is an earlier frame's
     if (rc == FOVPT_OK) {                                                                     // what post-processing may filter
-        c->dn_w = lp->frame.size.x; c->dn_h = lp->frame.size.y;
-        frame_levels(c->cfg, lp, c->dn_frame);
-        c->dn_uniform = c->cfg.uniform;
-        c->dn_guides = c->cfg.write_guides;
-        c->dn_world = c->cfg.world;
+        c->rendered.w = lp->frame.size.x; c->rendered.h = lp->frame.size.y;
+        frame_levels(c->cfg, lp, c->rendered.frame);
+        c->rendered.uniform = c->cfg.uniform;
+        c->rendered.guides = c->cfg.write_guides;
+        c->rendered.world = c->cfg.world;
     }
     return rc;
 }
@@ -1091,7 +1072,7 @@ int fovpt_synchronize(fovpt_ctx* c)
 {
     if (!c) return FOVPT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     return FOVPT_OK;
 }
 
@@ -1099,7 +1080,7 @@ int fovpt_download(fovpt_ctx* c, const void* device_src, void* host_dst, size_t 
 {
     if (!c || !device_src || !host_dst) return FOVPT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     HIPCHK(c, hipMemcpy(host_dst, device_src, n_bytes, hipMemcpyDeviceToHost));
     return FOVPT_OK;
 }
@@ -1108,7 +1089,7 @@ int fovpt_get_stats(fovpt_ctx* c, fovpt_stats* out)
 {
     if (!c || !out) return FOVPT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     drain_events(c);
     c->stats.radiance_rays = c->stats.shadow_rays = c->stats.paths = 0;
     for (StateSet& S : c->set) {
@@ -1125,7 +1106,7 @@ int fovpt_reset_stats(fovpt_ctx* c)
 {
     if (!c) return FOVPT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc_ = sync_all(c); if (rc_) return rc_; }
+    CHK(sync_all(c));
     drain_events(c);
     for (StateSet& S : c->set)
         if (S.counters.p) HIPCHK(c, hipMemset((char*)S.counters.p + offsetof(Counters, stat_radiance), 0, sizeof(Counters) - offsetof(Counters, stat_radiance)));

@@ -1,7 +1,9 @@
-// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_animate.hip, api_post.hip, api_gather.hip, api_packet.hip,
-// api_debug.hip): the context, the buffers it owns, and the helpers more than one of those files uses.  Host only: no kernel file
-// includes it.
+// fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_animate.hip, api_post.hip, api_view.hip, api_gather.hip,
+// api_packet.hip, api_debug.hip): the context, the buffers it owns, and the helpers more than one of those files uses.  The
+// post-frame stages' state is grouped: the record of the rendered frame (fovpt_ctx::rendered) and one struct per stage.  Host
+// only: no kernel file includes it.
 #pragma once
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -29,6 +31,14 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     void swap(DevBuf& o) { void* q = p; p = o.p; o.p = q; const size_t n = bytes; bytes = o.bytes; o.bytes = n; }
+};
+
+#define FOVPT_LOCAL __attribute__((visibility("hidden")))      // a type whose members the library does not export
+
+// A post-frame stage's own outputs: a float4 colour and an rgba8 image per pixel.
+struct FOVPT_LOCAL OutPair {
+    DevBuf color, rgba;
+    hipError_t reserve(size_t n) { const hipError_t e = color.reserve(n * 16); return e != hipSuccess ? e : rgba.reserve(n * 4); }   // both, for n pixels
 };
 
 enum TimedKind { T_GENERATE, T_TRACE, T_SHADE, T_SHADOW, T_RESOLVE };    // what a timed launch adds to in fovpt_stats
@@ -176,59 +186,65 @@ struct fovpt_ctx {
     std::vector<uint32_t> plan_off;        // host copy: rank r owns plan_idx[plan_off[r] .. plan_off[r + 1])
     std::string plan_key;                  // what the plan was built for
     bool use_accum_before = false;
-    // fovpt_denoise / fovpt_reconstruct: the frame last issued with fovpt_render as it was rendered (dn_w x dn_h; 0 x 0: none
-    // since create / resize): its passes, gaze and camera (dn_frame), and the FOV_OFF flag, guides and shard count of its config.
-    // Post-processing reads these, never the caller's current config, gaze or camera.  Then the level map, the ping-pong
-    // filter buffers and the context's own outputs (allocated on first use)
-    int dn_w = 0, dn_h = 0;
-    FrameDev dn_frame{};
-    int32_t dn_uniform = 0, dn_guides = 0, dn_world = 1;
-    DevBuf dn_level, dn_i0, dn_i1, dn_color, dn_rgba;
+    // ---- the post-frame stages (api_post.hip, api_view.hip): the record of the rendered frame they all read, then one struct per
+    // stage with what that stage owns, `out` being its own outputs.  post_resize keeps what exists of them at the frame's size.
+    // The frame last issued with fovpt_render as it was rendered (w x h; 0 x 0: none since create / resize): its passes, gaze
+    // and camera (frame), and the FOV_OFF flag, guides and shard count of its config.  Post-processing, the packet encoder and
+    // the quality metric read these, never the caller's current config, gaze or camera.  Set by fovpt_render, cleared by
+    // post_resize, and by nothing else.
+    struct FOVPT_LOCAL Rendered {
+        int w = 0, h = 0;
+        FrameDev frame{};
+        int32_t uniform = 0, guides = 0, world = 1;
+        size_t pixels() const { return (size_t)w * (size_t)h; }
+    } rendered;
+    // fovpt_denoise: the level map, the ping-pong filter buffers and the context's own outputs (allocated on first use)
+    struct FOVPT_LOCAL Denoise { DevBuf level, i0, i1; OutPair out; } denoise;
     // fovpt_gbuffer / fovpt_reconstruct: the G-buffer's own ray queue, hit records, counters and outputs (never a render state
-    // set: a frame in flight may be using those), and the context's own reconstruction outputs; all allocated on first use
-    DevBuf gb_o, gb_d, gb_hit, gb_cnt, gb_prim, gb_pos, gb_nrm, gb_alb, rc_color, rc_rgba;
-    // fovpt_temporal: two G-buffer sets and two histories (rgb, n), used in turn by consecutive calls (tp_last: the set the
+    // set: a frame in flight may be using those); all allocated on first use.  pixels: the pixels of the last G-buffer trace
+    // (fovpt_debug_buffer "gbuffer_hit")
+    struct FOVPT_LOCAL GBuffer { DevBuf o, d, hit, cnt, prim, pos, nrm, alb; size_t pixels = 0; } gbuffer;
+    // fovpt_reconstruct, fovpt_post (the chain's last stage) and fovpt_lens: the context's own outputs, allocated on first use
+    // (the stages keep nothing else; everything else the chain uses is the stages' own: the denoiser's buffers, the temporal
+    // step's sets, histories and state)
+    struct FOVPT_LOCAL OwnOutputs { OutPair out; } reconstruct, post, lens;
+    // fovpt_temporal: two G-buffer sets and two histories (rgb, n), used in turn by consecutive calls (last: the set the
     // last call wrote), the previous step's camera and size, and the context's own outputs; all allocated on first use.
-    // tp_valid: a previous step exists (dropped by fovpt_temporal_reset, fovpt_resize and fovpt_set_scene)
-    DevBuf tp_prim[2], tp_pos[2], tp_nrm[2], tp_alb[2], tp_hist[2], tp_color, tp_rgba;
-    int tp_last = 0;
-    bool tp_valid = false;
-    int tp_w = 0, tp_h = 0;
-    float tp_eye[3] = {}, tp_U[3] = {}, tp_V[3] = {}, tp_W[3] = {};
+    // valid: a previous step exists (dropped by fovpt_temporal_reset, fovpt_resize and fovpt_set_scene)
+    struct FOVPT_LOCAL Temporal {
+        DevBuf prim[2], pos[2], nrm[2], alb[2], hist[2];
+        OutPair out;
+        int last = 0, w = 0, h = 0;
+        bool valid = false;
+        float eye[3] = {}, U[3] = {}, V[3] = {}, W[3] = {};
+    } temporal;
     // fovpt_temporal_motion: tracking of the positions meshes had at the previous temporal step.  Switched on by a context's
     // first fovpt_temporal_motion (tm_tracking; off again after fovpt_set_scene), which makes tm_mark: per mesh the number of the
     // step (tm_epoch, counted over both entry points) before which fovpt_update_vertices last moved it, 0 = never; the host's
     // copy is tm_mesh_epoch.  A mesh has moved since the previous step when its mark equals tm_epoch, so ending an interval is
     // tm_epoch++ on the host and nothing on the device.  vtx_prev (12 B per vertex, made by the first tracked update) holds, for
     // the marked meshes, what up_vtx held before the interval's first update of them.  tm_untracked: an update ran since the
-    // previous step while tracking was off (the next fovpt_temporal_motion step has no history).  gb_pixels: the pixels of the
-    // last G-buffer trace (fovpt_debug_buffer "gbuffer_hit")
+    // previous step while tracking was off (the next fovpt_temporal_motion step has no history).
     bool tm_tracking = false, tm_untracked = false;
     uint64_t tm_epoch = 1;                 // (64 bits: never wraps)
     std::vector<uint64_t> tm_mesh_epoch;
     DevBuf tm_mark, vtx_prev;
-    size_t gb_pixels = 0;
-    // fovpt_post: the context's own outputs of the chain's last stage, allocated on first use (everything else the chain uses
-    // is the stages' own: the denoiser's buffers, the temporal step's sets, histories and state)
-    DevBuf po_color, po_rgba;
     // fovpt_expose: the device state record (a struct fovpt_expose_state, zeroed when made and by a reset: steps 0 = the next
     // AUTO step is a first step; the host never reads it outside fovpt_expose_state), the meter's per-block histogram rows and
     // the histogram of the last metered step, and the context's own outputs; all allocated on first use
-    DevBuf ex_state, ex_rows, ex_hist, ex_color, ex_rgba;
+    struct FOVPT_LOCAL Expose { DevBuf state, rows, hist; OutPair out; } expose;
     // fovpt_warp: the scatter's keys (8 bytes per pixel), the device counts (FOVPT_WARP_COUNT_SLOTS partial records, zeroed on the stream
     // ahead of every warp; the host reads and adds them nowhere but in fovpt_warp_counts) and the context's own outputs; all allocated on
     // first use
-    DevBuf wp_keys, wp_counts, wp_color, wp_rgba;
+    struct FOVPT_LOCAL Warp { DevBuf keys, counts; OutPair out; } warp;
     // fovpt_focus: the device state record (a struct fovpt_focus_state, zeroed when made and by a reset: steps 0 = the next AUTO
     // step is a first step; the host never reads it outside fovpt_focus_state), the (r, tp) pairs of the last call (8 bytes per
     // pixel) and the context's own outputs; all allocated on first use
-    DevBuf fc_state, fc_rt, fc_color, fc_rgba;
-    // fovpt_lens: the context's own outputs, allocated on first use (the stage keeps nothing else)
-    DevBuf ln_color, ln_rgba;
+    struct FOVPT_LOCAL Focus { DevBuf state, rt; OutPair out; } focus;
     // fovpt_quality: the context's own record (a fovpt_quality_sums, made by the first call that measures into it, which writes
     // every byte; the host reads it nowhere but in fovpt_quality_read) and the tile kernel's rows of partial sums
     // (fovpt_quality_rows of the frame's size); both allocated on first use
-    DevBuf q_sums, q_rows;
+    struct FOVPT_LOCAL Quality { DevBuf sums, rows; } quality;
     // fovpt_packet_submit / fovpt_packet_wait (api_packet.hip), all made by a context's first submit: the copy stream, and per slot
     // the device buffer an encode writes (one each, so that an encode never overwrites a packet that is still being copied), the
     // pinned host buffer its copy fills (grown on demand), the event recorded on fovpt_stream() behind the encode, which the copy
@@ -264,7 +280,7 @@ struct fovpt_ctx {
     // moved in it.  seq: one counter, incremented at each of the events below, whose value then is the event's stamp (0: never)
     // -- seq_frame: the last fovpt_render, fovpt_resize or fovpt_set_scene; seq_update: the last geometry update; seq_step: the
     // last temporal step; gb_stamp: the last G-buffer trace, 0 when it was not of the rendered frame's size and camera.  The hit
-    // records (gb_hit) describe the rendered frame and the current geometry when gb_stamp is above seq_frame and seq_update.
+    // records (gbuffer.hit) describe the rendered frame and the current geometry when gb_stamp is above seq_frame and seq_update.
     bool tm_step_blind = false;
     uint64_t seq = 0, seq_frame = 0, seq_update = 0, seq_step = 0, gb_stamp = 0;
     uint64_t seq_adopt = 0;                // the last adoption of a background rebuild: no position moves, but the hit records of an earlier trace address the old hierarchy's triangle records
@@ -273,6 +289,7 @@ struct fovpt_ctx {
 
 int fail(fovpt_ctx* c, int code, const char* fmt, ...);       // sets the error text (c null: the text fovpt_last_error(NULL) returns), returns code
 #define HIPCHK(c, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail((c), FOVPT_E_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+#define CHK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)      // a step that has set the error text: its code goes up
 int sync_all(fovpt_ctx* c);
 SceneView scene_view(const fovpt_ctx* c);
 void set_camera(FrameDev& fd, const fovpt_launch_params* lp);
@@ -307,10 +324,28 @@ int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes
 #pragma GCC visibility pop
 // api_animate.hip (fovpt_set_scene and the context's destructor drop what the update calls keep of a scene)
 void drop_animation(fovpt_ctx* c);
-// api_post.hip (fovpt_resize keeps the buffers of the post-processing calls at the frame's size)
-int reserve_gbuffer(fovpt_ctx* c, size_t n);
-int reserve_temporal(fovpt_ctx* c, size_t n);
-int expose_reset(fovpt_ctx* c, hipStream_t st);      // (st null: the device is idle, reset now)
-int focus_reset(fovpt_ctx* c, hipStream_t st);       // (likewise)
+// api_post.hip
 int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev& view, GBufferDev& g, const char* who,
                     const GBufferDev* target = nullptr);
+// api_post.hip: what fovpt_resize and fovpt_set_scene ask of the post-frame stages, and the steps the stages of api_post.hip and
+// api_view.hip (and, for the first, api_packet.hip) share; `who` is the entry point's name, for the error text.  Hidden: the
+// library does not export them.
+#pragma GCC visibility push(hidden)
+int post_resize(fovpt_ctx* c, int w, int h);         // what exists of the stages' buffers follows the frame; nothing is rendered at this size yet
+int post_scene_changed(fovpt_ctx* c);                // (the device is idle) no history, the last trace is another scene's, exposure and focus start from scratch
+int check_rendered_frame(fovpt_ctx* c, const fovpt_launch_params* lp, const char* who, const char* to_what, const char* need_guides, size_t limit);
+int check_reserved(fovpt_ctx* c, const int32_t* words, int n, const char* who);
+int check_aliases(fovpt_ctx* c, std::initializer_list<const void*> outs, std::initializer_list<const void*> ins, const char* who, const char* fmt_input);
+// an edge-stopping scale of fovpt_denoise / fovpt_reconstruct: inside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX], so that 1 / sigma^2
+// is a normal float and the denoiser's colour scale (1 / sigma^2) * 4^(FOVPT_DENOISE_MAX_ITERATIONS - 1) / 1e-4 stays finite
+// (an infinite scale makes the centre tap 0 * inf: every weight 0, the output 0 / 0)
+inline bool sigma_ok(float v) { return v >= FOVPT_SIGMA_MIN && v <= FOVPT_SIGMA_MAX; }
+template <class T> bool zeroed(T* out) { if (out) memset(out, 0, sizeof(*out)); return out != nullptr; }      // how every fovpt_*_defaults begins
+bool camera_inverse(const float* U, const float* V, const float* W, float* inv);
+GBufferDev gbuffer_dev(const fovpt_ctx* c, const fovpt_gbuffer_ptrs* given);
+int own_outputs(fovpt_ctx* c, const char* who, OutPair& own, fovpt_float4*& out_color, uint32_t*& out_rgba);
+int own_buffers(fovpt_ctx* c, const char* who, OutPair& own, fovpt_float4** color, uint32_t** rgba);
+int record_make(fovpt_ctx* c, DevBuf& rec, size_t bytes);
+int record_reset(fovpt_ctx* c, DevBuf& rec, size_t bytes, hipStream_t st);
+int record_read(fovpt_ctx* c, const DevBuf& rec, void* out, size_t bytes, const char* null_text);
+#pragma GCC visibility pop
