@@ -307,10 +307,7 @@ int adopt_ready(fovpt_ctx* c)
         e = hipEventRecord(ev, s);
     };
     behind(c->shadow_stream);
-    for (int l = 0; l < FOVPT_MAX_LANES; l++) {
-        behind(c->lane_main[l]);
-        if (c->lane_shadow[l] != c->shadow_stream) behind(c->lane_shadow[l]);
-    }
+    for (int k = 0; k < c->engine.num_trace_streams; k++) behind(c->engine.trace_stream[k]);
     if (e != hipSuccess) {
         // nothing has changed yet: the old hierarchy stays, the new one waits for the next call
         for (hipEvent_t ev : T.ev) (void)hipEventDestroy(ev);
@@ -389,7 +386,7 @@ int enqueue_refit(fovpt_ctx* c)
     fovpt_launch_refit(st, c->nodes, c->tris, c->bvh_levels, c->bvh_num_levels, (const uint3*)c->up_vidx.p, (const float*)c->up_vtx.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_scene, st));
-    c->refit_pending = true;
+    c->engine.refit_pending = true;
     c->cost_updates++;
     fovpt_ctx::CostSlot* S = nullptr;
     return c->cost_watching ? enqueue_cost(c, st, c->cost_updates, &S) : FOVPT_OK;
@@ -649,7 +646,7 @@ void drop_animation(fovpt_ctx* c)
     if (c->rb) { c->rb->flat.release(); c->rb->mesh_of.release(); std::vector<uint32_t>().swap(c->rb->in.h_mesh_of); }
     drop_rig(c);
     c->up_vtx.release(); c->up_vidx.release();
-    c->refit_pending = false;
+    c->engine.refit_pending = false;
     c->tm_tracking = c->tm_untracked = false;
     c->tm_mark.release(); c->vtx_prev.release();
     c->rest_vtx.release(); c->mesh_absmax.clear();

@@ -33,7 +33,7 @@ hipError_t download(void* dst, const DevBuf& b, size_t n) { return dst ? hipMemc
 int debug_state(fovpt_ctx* c, size_t slots, size_t launches, StateSet*& S, uint32_t& cap)
 {
     CHK(debug_begin(c));
-    S = &c->set[(c->last_set + 1u) % 2u];                           // (the device is idle: any set will do)
+    S = &c->engine.set[(c->engine.rot.last_set + 1u) % 2u];         // (the device is idle: any set will do)
     cap = shard_capacity(slots);
     return ensure_state(c, *S, slots, launches, c->stream);
 }
@@ -49,15 +49,10 @@ int debug_frame(fovpt_ctx* c, const fovpt_launch_params* lp, int render, uint32_
     if (render) { fovpt_launch_params L = *lp; npass = frame_passes(c->cfg, L, P); }
     else P[0] = pass_from_lp(lp, width, height);
     const bool chunk = row1 > 0u;
-    uint64_t all_slots = 0;
-    for (int p = 0; p < npass; p++) {
-        if (P[p].spp == 0) return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
-        P[p].row0 = 0; P[p].row1 = P[p].gh; P[p].frame_pass = (uint32_t)p;                     // as run_passes hands an unchunked frame to run_job
-        if (chunk) { P[p].row0 = row0; P[p].row1 = row1; }                                     // ... and a chunk of a launch
-        all_slots += (uint64_t)P[p].gw * (P[p].row1 - P[p].row0) * P[p].spp;
-    }
-    if (all_slots > c->slot_budget) return fail(c, FOVPT_E_INVALID, "%s: %llu sample slots would run as several jobs", who, (unsigned long long)all_slots);
-    CHK(frame_dev(c, lp, P, npass, chunk ? 1 : 0, render ? 1 : 0, fd, slots, launches));
+    uint64_t over = 0;
+    CHK(job_passes(c, P, npass, 0u, row0, row1, P, &over));                                    // as run_passes hands a frame, or a chunk of a launch, to run_job
+    if (over) return fail(c, FOVPT_E_INVALID, "%s: %llu sample slots would run as several jobs", who, (unsigned long long)over);
+    CHK(frame_dev(c, lp, P, npass, chunk ? 1 : 0, render ? 1 : 0, nullptr, fd, slots, launches));
     *npass_out = npass;
     for (int p = 0; p < npass; p++) {
         const PassDev& D = fd.pass[p];
@@ -269,7 +264,7 @@ int trace_queued(fovpt_ctx* c, const fovpt_debug_trace_launch* in, fovpt_debug_t
     const ShadowQueue sq = shadow_queue(S, 0);
     const SceneView sc = scene_view(c);
     const int div = sel ? 2 : 1;                                         // a chain's launches get half the grids (run_job)
-    const int g_trace = in->grid_closest ? in->grid_closest : c->grid_trace / div, g_shadow = in->grid_shadow ? in->grid_shadow : c->grid_shadow / div;
+    const int g_trace = in->grid_closest ? in->grid_closest : c->engine.grid_trace / div, g_shadow = in->grid_shadow ? in->grid_shadow : c->engine.grid_shadow / div;
     for (int pass = 0; pass < (in->both ? 2 : 1); pass++) {
         const uint32_t sel_now = pass == 0 ? sel : 3u - sel;
         fovpt_launch_traverse(st, sc, ps, q, sq, cap, cnt, in->it_closest, -1, g_trace, nullptr, sel_now);    // closest hit, as run_job launches it
@@ -334,7 +329,7 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "focus_state") == 0 && c->focus.state.p) { *ptr = c->focus.state.p; *bytes = sizeof(FocusState); return FOVPT_OK; }   // fovpt_focus's state record
     if (strcmp(name, "focus_scratch") == 0 && c->focus.rt.p) { *ptr = c->focus.rt.p; *bytes = c->focus.rt.bytes; return FOVPT_OK; }   // and its (r, tp) pairs, once made
     if (strcmp(name, "gbuffer_hit") == 0 && c->gbuffer.hit.p) { *ptr = c->gbuffer.hit.p; *bytes = c->gbuffer.pixels * 16; return FOVPT_OK; }   // the last G-buffer trace
-    StateSet& S = c->set[c->last_set];                    // the set the most recent job used
+    StateSet& S = c->engine.set[c->engine.rot.last_set];  // the set the most recent job used
     struct { const char* n; DevBuf* b; } tab[] = {
         {"sq_o", &S.sq_o[0]}, {"sq_d", &S.sq_d[0]}, {"sq_vis", &S.sq_vis[0]}, {"sq_occ", &S.sq_occ[0]}, {"counters", &S.counters},
         {"hit", &S.s_hit}, {"queue_a_o", &S.q_o[0]}, {"queue_a_d", &S.q_d[0]}, {"queue_b_o", &S.q_o[1]}, {"queue_b_d", &S.q_d[1]},
@@ -630,7 +625,7 @@ int fovpt_debug_generate(fovpt_ctx* c, const fovpt_launch_params* lp, const fovp
     // the launch: what run_job would give a launch of this `sel`, unless the caller says otherwise
     const uint32_t sel = in->sel;
     if (sel > 2u) return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: sel %u", sel);
-    const int grid = in->grid ? in->grid : (sel ? c->grid / 2 : c->grid);
+    const int grid = in->grid ? in->grid : (sel ? c->engine.grid / 2 : c->engine.grid);
     if (grid <= 0 || grid > (1 << 20) || grid % (sel ? FOVPT_SHARDS / 2 : FOVPT_SHARDS))
         return fail(c, FOVPT_E_INVALID, "fovpt_debug_generate: a grid of %d blocks (a positive multiple of %d)", grid, sel ? FOVPT_SHARDS / 2 : FOVPT_SHARDS);
     uint32_t slot_begin = in->slot_begin, slot_end = in->slot_end;

@@ -232,7 +232,7 @@ int enqueue_gbuffer(fovpt_ctx* c, const fovpt_launch_params* lp, const FrameDev&
     g = target ? *target : gbuffer_dev(c, nullptr);
     hipStream_t st = c->shadow_stream;
     fovpt_launch_gbuffer_rays(st, fd, q, cnt);
-    fovpt_launch_traverse(st, scene_view(c), ps, q, sq, (uint32_t)n, cnt, 0, -1, c->grid_trace);   // shard 0 holds all n rays
+    fovpt_launch_traverse(st, scene_view(c), ps, q, sq, (uint32_t)n, cnt, 0, -1, c->engine.grid_trace);   // shard 0 holds all n rays
     fovpt_launch_gbuffer_fill(st, fd, scene_view(c), q, ps.hit, g);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;

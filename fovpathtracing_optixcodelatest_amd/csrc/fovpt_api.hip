@@ -36,10 +36,7 @@ int fail(fovpt_ctx* c, int code, const char* fmt, ...)
 
 int sync_all(fovpt_ctx* c)
 {
-    for (int l = 0; l < FOVPT_MAX_LANES; l++) {
-        if (c->lane_main[l]) HIPCHK(c, hipStreamSynchronize(c->lane_main[l]));
-        if (c->lane_shadow[l]) HIPCHK(c, hipStreamSynchronize(c->lane_shadow[l]));
-    }
+    for (int k = 0; k < c->engine.num_trace_streams; k++) HIPCHK(c, hipStreamSynchronize(c->engine.trace_stream[k]));
     if (c->shadow_stream) HIPCHK(c, hipStreamSynchronize(c->shadow_stream));      // last: the resolves wait for the lanes
     return FOVPT_OK;
 }
@@ -92,7 +89,7 @@ bool env_int(const char* name, int lo, int hi, int* dst)
 
 hipEvent_t get_event(fovpt_ctx* c)
 {
-    if (!c->free_events.empty()) { hipEvent_t e = c->free_events.back(); c->free_events.pop_back(); return e; }
+    if (!c->engine.free_events.empty()) { hipEvent_t e = c->engine.free_events.back(); c->engine.free_events.pop_back(); return e; }
     hipEvent_t e = nullptr;
     if (hipEventCreate(&e) != hipSuccess) return nullptr;      // (Timed skips the measurement)
     return e;
@@ -106,19 +103,19 @@ struct Timed {
         if (c->cfg.profile) {
             a = get_event(c); b = get_event(c);
             if (a && b) (void)hipEventRecord(a, st);
-            else { if (a) c->free_events.push_back(a); if (b) c->free_events.push_back(b); a = b = nullptr; }
+            else { if (a) c->engine.free_events.push_back(a); if (b) c->engine.free_events.push_back(b); a = b = nullptr; }
         }
     }
     ~Timed()
     {
-        if (a && b) { (void)hipEventRecord(b, st); EventPair p = {a, b, kind}; c->pending.push_back(p); }
+        if (a && b) { (void)hipEventRecord(b, st); EventPair p = {a, b, kind}; c->engine.pending.push_back(p); }
         if (c->cfg.profile == 2) (void)hipStreamSynchronize(st);
     }
 };
 
 void drain_events(fovpt_ctx* c)
 {
-    for (auto& p : c->pending) {
+    for (auto& p : c->engine.pending) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
             switch (p.kind) {
@@ -129,9 +126,9 @@ void drain_events(fovpt_ctx* c)
             case T_RESOLVE: c->stats.ms_resolve += ms; break;
             }
         }
-        c->free_events.push_back(p.a); c->free_events.push_back(p.b);
+        c->engine.free_events.push_back(p.a); c->engine.free_events.push_back(p.b);
     }
-    c->pending.clear();
+    c->engine.pending.clear();
 }
 
 void free_scene(fovpt_ctx* c)
@@ -144,13 +141,59 @@ void free_scene(fovpt_ctx* c)
     drop_animation(c);                              // what the update calls keep of it (api_animate.hip)
 }
 
-}  // namespace
+// The engine of a new context (c->num_cus is set): the launch grids, the knobs of the environment switches (tuning and A/B only;
+// none changes a result), the streams of every lane and the events of every state set.  Returns the first HIP error; what was
+// made until then is the destructor's.
+hipError_t make_engine(fovpt_ctx* c)
+{
+    Engine& E = c->engine;
+    // Blocks per CU, each a default that the switch of that name replaces when it lies in range; every grid a multiple of
+    // FOVPT_SHARDS (shard_grid).
+    //   generate: 8 blocks of 256 = 32 waves per CU, grid-stride
+    //   closest-hit launches, in units of 256 threads (k_traverse's own blocks are FOVPT_TBLOCK threads)
+    //   occlusion launches (measured best of 2..8 with per-wave ray pools)
+    //   shading: the kernel holds 4 waves per SIMD (104 VGPRs) = 4 blocks per CU; twice the resident number of blocks is
+    //   measured best (blocks per CU 2 / 3 / 4 / 6 / 8: shading 0.307 / 0.274 / 0.261 / 0.263 / 0.244 ms per C3 frame)
+    const struct { const char* name; int hi, per_cu; int* grid; } grids[4] = {
+        {"FOVPT_GRID_GEN", 64, 8, &E.grid}, {"FOVPT_GRID", 64, FOVPT_GRID_PER_CU, &E.grid_trace},
+        {"FOVPT_GRID_SHADOW", 16, FOVPT_GRID_SHADOW_PER_CU, &E.grid_shadow}, {"FOVPT_GRID_SHADE", 16, 8, &E.grid_shade}};
+    for (const auto& g : grids) {
+        int per_cu = g.per_cu;
+        (void)env_int(g.name, 1, g.hi, &per_cu);
+        *g.grid = shard_grid(c->num_cus * per_cu);
+    }
+    if (const char* sb = getenv("FOVPT_SLOT_BUDGET")) { const long long v = atoll(sb); if (v > 0) E.slot_budget = (uint64_t)v; }   // tests: force chunking
+    (void)env_int("FOVPT_LANES", 1, FOVPT_MAX_LANES, &E.knobs.lanes);
+    (void)env_int("FOVPT_SPREAD_OCCLUSION", INT_MIN, INT_MAX, &E.knobs.spread_occlusion);      // 0 off, 1 the last occlusion launch, 2 the second (A/B); not range-checked
+    (void)env_int("FOVPT_CHAINS", 1, 2, &E.knobs.chains_default);
+    int nsets = 2 * E.knobs.lanes;
+    (void)env_int("FOVPT_SETS", 2, 2 * FOVPT_MAX_LANES, &nsets);
+    E.knobs.nsets = (unsigned)nsets;
+    // the main chain is the critical path: give it the higher priority so occlusion waves only fill gaps
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    hipError_t e = hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_hi);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->shadow_stream, hipStreamDefault, prio_lo);
+    E.lane_main[0] = c->stream; E.lane_shadow[0] = c->shadow_stream;
+    for (int l = 1; l < E.knobs.lanes; l++) {
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&E.lane_main[l], hipStreamDefault, prio_hi);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&E.lane_shadow[l], hipStreamDefault, prio_lo);
+    }
+    for (int l = 0; l < FOVPT_MAX_LANES; l++)
+        for (hipStream_t s : {E.lane_main[l], E.lane_shadow[l]})
+            if (s && s != c->shadow_stream) E.trace_stream[E.num_trace_streams++] = s;
+    for (StateSet& S : E.set) {
+        for (ChainEvents& ch : S.chain)
+            for (int k = 0; k <= FOVPT_MAX_ITERS && e == hipSuccess; k++) {
+                e = hipEventCreateWithFlags(&ch.shade[k], hipEventDefault);
+                if (e == hipSuccess) e = hipEventCreateWithFlags(&ch.shadow[k], hipEventDefault);
+            }
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_done, hipEventDefault);
+    }
+    return e;
+}
 
-// A queue shard receives the appends of the blocks whose index is congruent to it modulo FOVPT_SHARDS.  The
-// producing kernels walk their index space in 256-wide block iterations m = 0, 1, 2, ... with a grid that is
-// a multiple of FOVPT_SHARDS, so shard s gets the iterations m = s (mod 8): at most ceil(M / 8) + 1 of them,
-// each appending at most 256 entries.  Nothing can overflow a shard of slots / 8 + 512 entries.
-uint32_t shard_capacity(size_t slots) { return (uint32_t)(slots / FOVPT_SHARDS + 512); }
+}  // namespace
 
 int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipStream_t st)
 {
@@ -179,6 +222,21 @@ int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipSt
     return FOVPT_OK;
 }
 
+// The other sets of a rotation through nrot sets, grown to the job's size now rather than one per job: an allocation waits for
+// the device, and the first jobs of a caller that keeps several frames in flight would each stop for one.  Only a set too small
+// for the job's sample slots: ensure_state would also give a set that is large enough a longer backplate, guide buffers the
+// configuration has since switched on, or more shadow queues (a scene that has gained a catcher) -- allocations, and a wait
+// each, that this job does not need; the set gets them when its own job comes.
+int grow_rotation(fovpt_ctx* c, unsigned nrot, unsigned set_index, size_t slots, size_t launches, hipStream_t st)
+{
+    for (unsigned k = 0; k < nrot; k++) {
+        const StateSet& S = c->engine.set[k];
+        if (k != set_index && (S.s_thr.bytes < slots * 16 || S.s_rad.bytes < slots * 16 * (size_t)c->cfg.max_depth))
+            CHK(ensure_state(c, c->engine.set[k], slots, launches, st));
+    }
+    return FOVPT_OK;
+}
+
 // What the kernels see of a state set: its path state (the guide pointers null unless write_guides is on: ensure_state's rule) ...
 PathState path_state(const fovpt_ctx* c, const StateSet& S)
 {
@@ -201,19 +259,19 @@ ShadowQueue shadow_queue(const StateSet& S, int k)
     return sq;
 }
 
-static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame);
+static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes, int npass, int chunked, int whole_frame, const fovpt_float4* accum_prev);
 
-// The two chains of a job that run_job splits (chains_per_frame = 2): chain k takes the sample slots [slot_begin, slot_end) -- the
-// first chain a whole number of 256-slot block iterations, the second the rest -- through the queue shards of sel = k + 1.  One
-// function for run_job and for the generate hook of api_debug.hip, so that a test runs the chains a job would issue.
-ChainSplit chain_split(uint64_t slots, int k)
+// The pass table of one job (pass_table, fovpt_jobplan.h), for run_passes (a whole frame, a chunk) and for the hooks of
+// api_debug.hip, so that a test runs the frame a job would: every pass of `in` whole (row1 = 0) or its launch rows [row0, row1), as
+// the passes first_pass, first_pass + 1, ... of the caller's frame -- ownership rotates with a pass's place in the frame, also when
+// it runs as a job of its own.  *over: 0, or the job's sample slots when they exceed the budget of one job.
+int job_passes(fovpt_ctx* c, const PassDev* in, int npass, uint32_t first_pass, uint32_t row0, uint32_t row1, PassDev* out, uint64_t* over)
 {
-    const uint32_t half = (uint32_t)(slots / 2 / FOVPT_BLOCK * FOVPT_BLOCK);
-    ChainSplit s;
-    s.sel = k == 0 ? 1u : 2u;
-    s.slot_begin = k == 0 ? 0u : half;
-    s.slot_end = k == 0 ? half : (uint32_t)slots;
-    return s;
+    uint64_t slots = 0;
+    if (!pass_table(in, npass, first_pass, row0, row1, out, &slots))
+        return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
+    *over = slots > c->engine.slot_budget ? slots : 0;      // (a job without sample slots fits)
+    return FOVPT_OK;
 }
 
 // The engine: all passes of one frame as one wavefront job (or several, for very large launches).
@@ -230,59 +288,46 @@ static int run_passes(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev
     if (lp->frame.size.x <= 0 || lp->frame.size.y <= 0) return fail(c, FOVPT_E_INVALID, "bad frame size");
     if (c->cfg.max_depth < 1 || c->cfg.max_depth > 32) return fail(c, FOVPT_E_INVALID, "max_depth out of range");
 
+    PassDev job[FOVPT_MAX_PASSES];
+    uint64_t over = 0;
+    CHK(job_passes(c, passes_in, npass, 0u, 0u, 0u, job, &over));
+    c->stats.frames++;
+    if (!over) return run_job(c, lp, job, npass, 0, whole_frame, nullptr);
+
     // A launch whose sample slots would not fit the per-job budget is cut into chunks of launch rows and
     // run as several jobs in the reference's order (pass by pass, rows ascending): later jobs overwrite
     // earlier ones exactly as later launch indices overwrite earlier ones in the reference.
-    uint64_t all_slots = 0;
+    const uint64_t budget = c->engine.slot_budget;
+    const size_t npix = (size_t)lp->frame.size.x * lp->frame.size.y;
     for (int p = 0; p < npass; p++) {
-        if (passes_in[p].spp == 0) return fail(c, FOVPT_E_INVALID, "samples_per_launch must be >= 1 (do{}while(--i), deviceProgram.cu:448,539)");
-        all_slots += (uint64_t)passes_in[p].gw * passes_in[p].gh * passes_in[p].spp;
-    }
-    const uint64_t budget = c->slot_budget;
-    if (all_slots > budget) {
-        c->stats.frames++;
-        const size_t npix = (size_t)lp->frame.size.x * lp->frame.size.y;
-        // Accumulate mode blends with the pixel's value from BEFORE the launch (a pass of render() = one
-        // optixLaunch).  The chunks of a pass are separate jobs, so a pixel that two of them write (clamped
-        // or overlapping fills) would otherwise be blended twice: keep a copy for the chunks to read.  The copy
-        // of the FIRST pass is taken here, before anything of this frame touches the buffer (the clearing below
-        // included); render() blends in pass P only, which is the first.
-        auto blends = [&](const PassDev& P) { return c->cfg.accumulate && P.subframe > 0 && !P.redraw; };
-        auto snapshot = [&]() -> int {
-            HIPCHK(c, c->accum_before.reserve(npix * 16));
-            HIPCHK(c, hipMemcpyAsync(c->accum_before.p, lp->frame.accum_buffer, npix * 16, hipMemcpyDeviceToDevice, c->shadow_stream));
-            return FOVPT_OK;
-        };
-        if (npass > 0 && blends(passes_in[0])) { int rc = snapshot(); if (rc) return rc; }
-        if (whole_frame && c->cfg.world > 1 && c->cfg.rank != 0) {
+        const PassDev& P = passes_in[p];
+        // Accumulate mode blends with the pixel's value from BEFORE the launch (a pass of render() = one optixLaunch).  The
+        // chunks of a pass are separate jobs, so a pixel that two of them write (clamped or overlapping fills) would otherwise
+        // be blended twice: a pass that blends gets a copy, taken before its first chunk, for its chunks to read.  For the first
+        // pass that is before anything of this frame touches the buffer, the clearing below included.  (render() blends in pass
+        // P only, which is the first: no caller of this library takes the copy for a later pass.)
+        const bool blends = c->cfg.accumulate && P.subframe > 0 && !P.redraw;
+        if (blends) {
+            HIPCHK(c, c->engine.accum_before.reserve(npix * 16));
+            HIPCHK(c, hipMemcpyAsync(c->engine.accum_before.p, lp->frame.accum_buffer, npix * 16, hipMemcpyDeviceToDevice, c->shadow_stream));
+        }
+        if (p == 0 && whole_frame && c->cfg.world > 1 && c->cfg.rank != 0) {
             // The chunk jobs zero the pixels whose last writer (within the chunk) belongs to another rank; pixels no
             // chunk writes must not keep this rank's stale values (rank 0 keeps its own, like the unchunked path)
             // (on the stream the resolves run on: after the previous frame's, before this frame's)
             HIPCHK(c, hipMemsetAsync(lp->frame.frame_buffer, 0, npix * 4, c->shadow_stream));
             HIPCHK(c, hipMemsetAsync(lp->frame.accum_buffer, 0, npix * 16, c->shadow_stream));
         }
-        for (int p = 0; p < npass; p++) {
-            const PassDev& P = passes_in[p];
-            c->use_accum_before = blends(P);
-            if (p > 0 && c->use_accum_before) { int rc = snapshot(); if (rc) return rc; }      // (no caller of this library gets here)
-            const uint64_t per_row = (uint64_t)P.gw * P.spp;
-            if (per_row == 0 || P.gh == 0) continue;
-            if (per_row > budget) return fail(c, FOVPT_E_INVALID, "one launch row needs %llu sample slots (budget %llu)", (unsigned long long)per_row, (unsigned long long)budget);
-            const uint32_t rows_per = (uint32_t)(budget / per_row);
-            for (uint32_t y0 = 0; y0 < P.gh; y0 += rows_per) {
-                PassDev Q = P;
-                Q.frame_pass = (uint32_t)p;        // the job holds ONE pass; ownership still rotates with its place in the frame
-                Q.row0 = y0; Q.row1 = y0 + rows_per < P.gh ? y0 + rows_per : P.gh;
-                int rc = run_job(c, lp, &Q, 1, 1, 0);
-                if (rc) return rc;
-            }
+        if (P.gw == 0 || P.gh == 0) continue;
+        const ChunkRows cr = chunk_rows(budget, P.gw, P.spp);
+        if (cr.rows == 0) return fail(c, FOVPT_E_INVALID, "one launch row needs %llu sample slots (budget %llu)", (unsigned long long)cr.per_row, (unsigned long long)budget);
+        for (uint32_t y0 = 0; y0 < P.gh; y0 += cr.rows) {
+            PassDev Q;                         // the job holds ONE pass
+            CHK(job_passes(c, &P, 1, (uint32_t)p, y0, y0 + cr.rows < P.gh ? y0 + cr.rows : P.gh, &Q, &over));
+            CHK(run_job(c, lp, &Q, 1, 1, 0, blends ? (const fovpt_float4*)c->engine.accum_before.p : nullptr));
         }
-        return FOVPT_OK;
     }
-    PassDev full[FOVPT_MAX_PASSES];
-    for (int p = 0; p < npass; p++) { full[p] = passes_in[p]; full[p].row0 = 0; full[p].row1 = passes_in[p].gh; full[p].frame_pass = (uint32_t)p; }
-    c->stats.frames++;
-    return run_job(c, lp, full, npass, 0, whole_frame);
+    return FOVPT_OK;
 }
 
 // How a launch searches and reads the caller's probe: the guide tables, the packed records and the one-row layout belong to the
@@ -306,8 +351,9 @@ ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe)
 // What the kernels see of a frame: the passes (with their places in the job's sample slots and launch records), the camera, the
 // probe and how it is searched, the caller's frame buffers and the configuration.  One function for run_job and for
 // the resolve and generate hooks of api_debug.hip, so that a test hook runs the frame a job of the same parameters would.
-int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame, FrameDev& fd,
-              uint64_t& slots, uint64_t& launches)
+// accum_prev: what an accumulating resolve blends with when that is not the accum buffer itself (the chunks of a pass: run_passes).
+int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame,
+              const fovpt_float4* accum_prev, FrameDev& fd, uint64_t& slots, uint64_t& launches)
 {
     memset(&fd, 0, sizeof(fd));
     fd.chunked = chunked;
@@ -330,7 +376,7 @@ int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes
     const ProbePath pp = probe_path(c, lp->probe);
     fd.guide_x = pp.guide_x; fd.guide_y = pp.guide_y; fd.probe_rec = pp.rec; fd.probe_row_mul = pp.row_mul;
     fd.accum = lp->frame.accum_buffer;
-    fd.accum_prev = (chunked && c->use_accum_before) ? (const fovpt_float4*)c->accum_before.p : lp->frame.accum_buffer;
+    fd.accum_prev = accum_prev ? accum_prev : lp->frame.accum_buffer;
     fd.frame = lp->frame.frame_buffer;
     if (c->cfg.write_guides) {
         if (c->any_catcher) return fail(c, FOVPT_E_INVALID, "write_guides is not available with shadow-catcher materials");
@@ -346,127 +392,103 @@ int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes
     return FOVPT_OK;
 }
 
-// One wavefront job: generate -> (closest, shade, occlusion) x depth -> resolve over the given passes / row ranges.
-static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame)
-{
+// What every chain of a job shares: the frame, the set's path state, queues and counters, the scene, and the plan's iterations
+struct JobShared {
     FrameDev fd;
-    uint64_t slots = 0, launches = 0;
-    CHK(frame_dev(c, lp, passes_in, npass, chunked, whole_frame, fd, slots, launches));
+    PathState ps;
+    SceneView sc;
+    RayQueue q[2];
+    ShadowQueue sq[FOVPT_NSQ];
+    Counters* cnt;
+    uint32_t cap;
+    int iters, nsq, spread_it;
+};
 
-    if (slots == 0) return FOVPT_OK;
-    // a refit enqueued on fovpt_stream() since the last job (fovpt_update_vertices): every stream that may trace the scene or read
-    // its triangle records -- the lanes' main and shadow streams, both chains' -- waits for it, once
-    if (c->refit_pending) {
-        for (int l = 0; l < FOVPT_MAX_LANES; l++) {
-            if (c->lane_main[l]) HIPCHK(c, hipStreamWaitEvent(c->lane_main[l], c->ev_scene, 0));
-            if (c->lane_shadow[l] && c->lane_shadow[l] != c->shadow_stream) HIPCHK(c, hipStreamWaitEvent(c->lane_shadow[l], c->ev_scene, 0));
-        }
-        c->refit_pending = false;
+// One chain of a job (ChainPlan, fovpt_jobplan.h) on its lane's streams, its launches' completion events in ev:
+// Main chain (stream `st`):    generate, closest(0), shade(0), closest(1), shade(1), ... shade(D-1)
+// Shadow chain (stream `ss`):  occlusion(it) as soon as shade(it) has queued its rays; then resolve.
+// Every radiance cell has one writer, so the only joins are: shade(it+2) reuses the shadow queue
+// buffer of bounce it, and resolve needs everything -- it runs on the shadow stream, behind the last
+// occlusion launch (which waited for the last shade), so the main chain is free for the next job.
+static int issue_chain(fovpt_ctx* c, const JobShared& J, const ChainPlan& ch, const ChainEvents& ev)
+{
+    const Engine& E = c->engine;
+    const hipStream_t st = E.lane_main[ch.lane], ss = E.lane_shadow[ch.lane];
+    const uint32_t sel = ch.sel, cap = J.cap;
+    const int iters = J.iters, nsq = J.nsq;
+    RayQueue qa = J.q[0], qb = J.q[1];
+    const int g_gen = E.grid / ch.div, g_trace = E.grid_trace / ch.div, g_shadow = E.grid_shadow / ch.div, g_shade = E.grid_shade / ch.div;
+    { Timed t(c, T_GENERATE, st); (void)fovpt_launch_generate(st, J.fd, J.ps, qa, cap, J.cnt, ch.slot_begin, ch.slot_end, g_gen, sel); }
+    { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, J.sc, J.ps, qa, J.sq[0], cap, J.cnt, 0, -1, g_trace, nullptr, sel); }
+    for (int it = 0; it < iters; it++) {
+        if (it >= nsq) HIPCHK(c, hipStreamWaitEvent(st, ev.shadow[it - nsq], 0));
+        // the events ride on the kernels' own completion signals (hipExtLaunchKernel): a separate
+        // hipEventRecord would put a marker packet between shade(it) and closest(it+1), ~6 us on the critical path
+        { Timed t(c, T_SHADE, st); fovpt_launch_shade(st, J.fd, J.sc, J.ps, qa, qb, J.sq[it % nsq], cap, J.cnt, it, g_shade, ev.shade[it], sel); }
+        // (a sharded frame on the first lane: bounce spread_it's occlusion rays run on the OTHER lane's shadow stream -- the
+        // completion stream carries every job's resolve as well; the resolve waits for it)
+        const hipStream_t so = it == J.spread_it ? E.lane_shadow[1] : ss;
+        HIPCHK(c, hipStreamWaitEvent(ss, ev.shade[it], 0));
+        if (so != ss) HIPCHK(c, hipStreamWaitEvent(so, ev.shade[it], 0));
+        { Timed t(c, T_SHADOW, so); fovpt_launch_traverse(so, J.sc, J.ps, qb, J.sq[it % nsq], cap, J.cnt, -1, it, g_shadow, ev.shadow[it], sel); }
+        if (it + 1 < iters) { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, J.sc, J.ps, qb, J.sq[0], cap, J.cnt, it + 1, -1, g_trace, nullptr, sel); }
+        const RayQueue tmp = qa; qa = qb; qb = tmp;
     }
-    // the chunk jobs of an oversized launch all run on lane 0 (their memsets / snapshot copies are ordered on shadow_stream,
-    // as before round 3) and, like every job of more than FOVPT_SETS_SLOT_LIMIT sample slots (~330 B of state each), rotate
-    // through no more sets than before round 4
-    const unsigned few = c->lanes < 2 ? 2u : (unsigned)c->lanes;
-    const unsigned nrot = (chunked || (unsigned long long)slots > FOVPT_SETS_SLOT_LIMIT || c->nsets < few) ? few : c->nsets;
-    const unsigned set_index = c->jobs == 0 ? 0u : (c->last_set + 1u) % nrot;
-    StateSet& S = c->set[set_index];
-    const int fif = c->cfg.frames_in_flight > 0 ? c->cfg.frames_in_flight : c->lanes;
-    const unsigned lanes = (unsigned)(fif < c->lanes ? fif : c->lanes);
-    // chains_per_frame = 2: the job is TWO chains -- the halves of its sample slots, each with four of the eight queue shards, on
-    // the two lanes -- and one resolve behind both.  (Not for chunk jobs, nor for jobs too small to split.)
-    const int chains = c->cfg.chains_per_frame > 0 ? c->cfg.chains_per_frame : c->chains_default;
-    const bool two_chains = chains == 2 && c->lanes >= 2 && !chunked && slots >= 16384;
-    const unsigned lane = two_chains ? 0u : (lanes > 1u && !chunked) ? c->jobs % lanes : 0u;
-    hipStream_t st = c->lane_main[lane], ss = c->lane_shadow[lane];
-    // the set is free once the resolve of the job that used it last has run (reserve() may also free and
-    // reallocate its buffers, which the runtime orders after all device work)
-    if (S.used) HIPCHK(c, hipStreamWaitEvent(st, S.ev_done, 0));
-    if (S.used && two_chains) HIPCHK(c, hipStreamWaitEvent(c->lane_main[1], S.ev_done, 0));
-    int rc = ensure_state(c, S, (size_t)slots, (size_t)launches, st);
-    if (rc) return rc;
-    // the other sets of the rotation now rather than one per job: an allocation waits for the device, and the first jobs of a
-    // caller that keeps several frames in flight would each stop for one
-    for (unsigned k = 0; k < nrot && !chunked; k++)
-        if (k != set_index && (c->set[k].s_thr.bytes < (size_t)slots * 16 || c->set[k].s_rad.bytes < (size_t)slots * 16 * (size_t)c->cfg.max_depth)) {
-            rc = ensure_state(c, c->set[k], (size_t)slots, (size_t)launches, st);
-            if (rc) return rc;
-        }
-    c->jobs++;
-    c->last_set = set_index;
+    return FOVPT_OK;
+}
+
+// One wavefront job: generate -> (closest, shade, occlusion) x depth -> resolve over the given passes / row ranges.
+static int run_job(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes, int npass, int chunked, int whole_frame, const fovpt_float4* accum_prev)
+{
+    Engine& E = c->engine;
+    JobShared J;
+    uint64_t slots = 0, launches = 0;
+    CHK(frame_dev(c, lp, passes, npass, chunked, whole_frame, accum_prev, J.fd, slots, launches));
+    if (slots == 0) return FOVPT_OK;
+    const PlanJob job = {c->cfg.frames_in_flight, c->cfg.chains_per_frame, c->cfg.max_depth, c->cfg.world, c->any_catcher, slots, chunked};
+    const JobPlan plan = plan_job(E.knobs, E.rot, job);
+
+    // wait for the scene.  A refit enqueued on fovpt_stream() since the last job (fovpt_update_vertices): every stream that may
+    // trace the scene or read its triangle records -- the lanes' main and shadow streams, both chains' -- waits for it, once
+    // (what runs on shadow_stream itself is behind it already)
+    if (E.refit_pending) {
+        for (int k = 0; k < E.num_trace_streams; k++) HIPCHK(c, hipStreamWaitEvent(E.trace_stream[k], c->ev_scene, 0));
+        E.refit_pending = false;
+    }
+
+    // take the set.  It is free once the resolve of the job that used it last has run (reserve() may also free and
+    // reallocate its buffers, which the runtime orders after all device work); its counters are made and cleared on the
+    // stream about to use it
+    StateSet& S = E.set[plan.set_index];
+    const hipStream_t st = E.lane_main[plan.chain[0].lane];
+    for (int k = 0; k < plan.nchains && S.used; k++) HIPCHK(c, hipStreamWaitEvent(E.lane_main[plan.chain[k].lane], S.ev_done, 0));
+    CHK(ensure_state(c, S, (size_t)slots, (size_t)launches, st));
+    if (!chunked) CHK(grow_rotation(c, plan.nrot, plan.set_index, (size_t)slots, (size_t)launches, st));
+    E.rot.jobs++;
+    E.rot.last_set = plan.set_index;
     S.used = true;
 
-    const PathState ps = path_state(c, S);
-    ShadowQueue sq[FOVPT_NSQ];
-    for (int k = 0; k < FOVPT_NSQ; k++) sq[k] = shadow_queue(S, k);
-    const SceneView sc = scene_view(c);
-    Counters* cnt = (Counters*)S.counters.p;
+    J.ps = path_state(c, S);
+    J.sc = scene_view(c);
+    for (int k = 0; k < 2; k++) J.q[k] = ray_queue(S, k);
+    for (int k = 0; k < FOVPT_NSQ; k++) J.sq[k] = shadow_queue(S, k);
+    J.cnt = (Counters*)S.counters.p;
     // (the queue counters are zero: at allocation, and again by the resolve of the set's previous job)
 #if FOVPT_V_STEPSTAT
-    HIPCHK(c, hipMemsetAsync(cnt, 0, offsetof(Counters, stat_radiance), st));      // the diagnostic build keeps them after the job
+    HIPCHK(c, hipMemsetAsync(J.cnt, 0, offsetof(Counters, stat_radiance), st));      // the diagnostic build keeps them after the job
 #endif
-    const uint32_t cap = shard_capacity((size_t)slots);
-    // iterations: depth 0 .. max_depth-1, plus the reference's discarded segment and shadow-catcher
-    // pass-throughs (which do not advance depth) when the scene holds a catcher
-    int iters = c->cfg.max_depth + (c->any_catcher ? 1 + 24 : 0);
-    if (iters > FOVPT_MAX_ITERS) iters = FOVPT_MAX_ITERS;
-    const int nsq = iters < FOVPT_NSQ ? iters : FOVPT_NSQ;        // (only that many shadow queue buffers are allocated)
-    // Main chain (stream `st`):    generate, closest(0), shade(0), closest(1), shade(1), ... shade(D-1)
-    // Shadow chain (stream `ss`):  occlusion(it) as soon as shade(it) has queued its rays; then resolve.
-    // Every radiance cell has one writer, so the only joins are: shade(it+2) reuses the shadow queue
-    // buffer of bounce it, and resolve needs everything -- it runs on the shadow stream, behind the last
-    // occlusion launch (which waited for the last shade), so the main chain is free for the next job.
-    // Sharded frames (world > 1): the completion stream -- the first lane's shadow stream -- carries every job's resolve (whose
-    // writer search and clearing cover the whole frame on every rank) on top of that lane's occlusion launches and is then as
-    // long as the main chains (kernel trace, round 4).  One occlusion launch of a first-lane job moves to the second lane's
-    // shadow stream: occlusion launches depend on their shading launch only, and the resolve waits for all of them.
-    int spread_it = (c->spread_occlusion && fd.world > 1 && lanes > 1u && lane == 0u && !two_chains && !chunked
-                           && c->cfg.max_depth >= 2) ? (c->spread_occlusion == 2 ? 1 : -2) : -1;      // -2: the job's LAST one (below)
-    // Which one: a launch is queued when the job is issued and holds the stream's later entries back until its own shading launch
-    // has run.  The job's last occlusion launch is the smallest and the resolve waits for it anyway -- but behind it the other
-    // lane's next job would find its occlusion launches held back for a whole chain, and with more bounces than shadow queue
-    // buffers (iters > FOVPT_NSQ) that job's main chain waits for them (measured: C5, depth 8, 1/8 shard 0.76 -> 1.0 ms).  So:
-    // the last launch when no main chain can depend on an occlusion launch, else the second (held back for one bounce only).
-    if (spread_it == -2) spread_it = iters <= nsq ? iters - 1 : 1;
-    // One chain: the sample slots [slot_begin, slot_end) through the queue shards of `sel` (0: all eight; 1 / 2: one half), with
-    // 1 / div of the usual grids.
-    auto issue_chain = [&](hipStream_t st, hipStream_t ss, uint32_t sel, uint32_t slot_begin, uint32_t slot_end, int div, const ChainEvents& ev) -> int {
-        RayQueue qa = ray_queue(S, 0), qb = ray_queue(S, 1);
-        const int g_gen = c->grid / div, g_trace = c->grid_trace / div, g_shadow = c->grid_shadow / div, g_shade = c->grid_shade / div;
-        { Timed t(c, T_GENERATE, st); (void)fovpt_launch_generate(st, fd, ps, qa, cap, cnt, slot_begin, slot_end, g_gen, sel); }
-        { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, sc, ps, qa, sq[0], cap, cnt, 0, -1, g_trace, nullptr, sel); }
-        for (int it = 0; it < iters; it++) {
-            if (it >= nsq) HIPCHK(c, hipStreamWaitEvent(st, ev.shadow[it - nsq], 0));
-            // the events ride on the kernels' own completion signals (hipExtLaunchKernel): a separate
-            // hipEventRecord would put a marker packet between shade(it) and closest(it+1), ~6 us on the critical path
-            { Timed t(c, T_SHADE, st); fovpt_launch_shade(st, fd, sc, ps, qa, qb, sq[it % nsq], cap, cnt, it, g_shade, ev.shade[it], sel); }
-            // (a sharded frame on the first lane: bounce spread_it's occlusion rays run on the OTHER lane's shadow stream -- the
-            // completion stream carries every job's resolve as well; the resolve below waits for it)
-            const hipStream_t so = it == spread_it ? c->lane_shadow[1] : ss;
-            HIPCHK(c, hipStreamWaitEvent(ss, ev.shade[it], 0));
-            if (so != ss) HIPCHK(c, hipStreamWaitEvent(so, ev.shade[it], 0));
-            { Timed t(c, T_SHADOW, so); fovpt_launch_traverse(so, sc, ps, qb, sq[it % nsq], cap, cnt, -1, it, g_shadow, ev.shadow[it], sel); }
-            if (it + 1 < iters) { Timed t(c, T_TRACE, st); fovpt_launch_traverse(st, sc, ps, qb, sq[0], cap, cnt, it + 1, -1, g_trace, nullptr, sel); }
-            const RayQueue tmp = qa; qa = qb; qb = tmp;
-        }
-        return FOVPT_OK;
-    };
-    if (two_chains) {
-        const ChainSplit c0 = chain_split(slots, 0), c1 = chain_split(slots, 1);
-        rc = issue_chain(c->lane_main[0], c->lane_shadow[0], c0.sel, c0.slot_begin, c0.slot_end, 2, S.chain[0]);
-        if (rc) return rc;
-        rc = issue_chain(c->lane_main[1], c->lane_shadow[1], c1.sel, c1.slot_begin, c1.slot_end, 2, S.chain[1]);
-        if (rc) return rc;
-        HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[1].shadow[iters - 1], 0));      // (the first chain's last occlusion launch IS on shadow_stream)
-    } else {
-        rc = issue_chain(st, ss, 0u, 0u, (uint32_t)slots, 1, S.chain[0]);
-        if (rc) return rc;
-        // Every resolve runs on shadow_stream, whatever the lane: in job order (a later job's pixels overwrite, or blend with, an
-        // earlier one's), behind whatever the caller has queued on fovpt_stream() since the previous frame, and in front of what it
-        // queues next.  A job of the second lane joins it behind its last occlusion launch (which waited for its last shade).
-        if (ss != c->shadow_stream) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[0].shadow[iters - 1], 0));
-        if (spread_it >= 0 && spread_it < iters) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[0].shadow[spread_it], 0));
-    }
-    { Timed t(c, T_RESOLVE, c->shadow_stream); fovpt_launch_resolve(c->shadow_stream, fd, ps, cnt, S.ev_done); }
+    J.cap = shard_capacity(slots);
+    J.iters = plan.iters; J.nsq = plan.nsq; J.spread_it = plan.spread_it;
+    for (int k = 0; k < plan.nchains; k++) CHK(issue_chain(c, J, plan.chain[k], S.chain[k]));
+
+    // join and resolve.  Every resolve runs on shadow_stream, whatever the lane: in job order (a later job's pixels overwrite, or
+    // blend with, an earlier one's), behind whatever the caller has queued on fovpt_stream() since the previous frame, and in front
+    // of what it queues next.  A chain of another lane joins it behind its last occlusion launch (which waited for its last
+    // shade; the first lane's last occlusion launch IS on shadow_stream), and so does the occlusion launch that was moved there.
+    for (int k = 0; k < plan.nchains; k++)
+        if (E.lane_shadow[plan.chain[k].lane] != c->shadow_stream) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[k].shadow[plan.iters - 1], 0));
+    if (plan.spread_it >= 0) HIPCHK(c, hipStreamWaitEvent(c->shadow_stream, S.chain[0].shadow[plan.spread_it], 0));
+    { Timed t(c, T_RESOLVE, c->shadow_stream); fovpt_launch_resolve(c->shadow_stream, J.fd, J.ps, J.cnt, S.ev_done); }
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }
@@ -587,6 +609,16 @@ int build_hierarchy(fovpt_ctx* c, hipStream_t st, const float* d_flat, const uin
 }
 
 namespace {
+
+// The device arrays of a width x height probe (the device is idle): the texels and the four tables
+int reserve_probe(fovpt_ctx* c, int width, int height)
+{
+    const size_t n = (size_t)width * height;
+    HIPCHK(c, c->pr_pdfx.reserve(n * 4)); HIPCHK(c, c->pr_cdfx.reserve(n * 4));
+    HIPCHK(c, c->pr_pdfy.reserve((size_t)height * 4)); HIPCHK(c, c->pr_cdfy.reserve((size_t)height * 4));
+    HIPCHK(c, c->pr_data.reserve(n * 16));
+    return FOVPT_OK;
+}
 
 // What fovpt_set_probe and fovpt_set_probe_data share once the probe's arrays are on the device: whether the CDFs (host copies
 // cdfX, cdfY) are sorted, the guide tables and packed records if so, whether all rows are alike (texels, cdfX, and pdfX where
@@ -730,7 +762,7 @@ fovpt_ctx::~fovpt_ctx()
         if (S.ev_encoded) (void)hipEventDestroy(S.ev_encoded);
         if (S.ev_done) (void)hipEventDestroy(S.ev_done);
     }
-    for (StateSet& S : set) {
+    for (StateSet& S : engine.set) {
         for (ChainEvents& ch : S.chain)
             for (int k = 0; k <= FOVPT_MAX_ITERS; k++) {
                 if (ch.shade[k]) (void)hipEventDestroy(ch.shade[k]);
@@ -738,10 +770,10 @@ fovpt_ctx::~fovpt_ctx()
             }
         if (S.ev_done) (void)hipEventDestroy(S.ev_done);
     }
-    for (hipEvent_t e : free_events) (void)hipEventDestroy(e);
+    for (hipEvent_t e : engine.free_events) (void)hipEventDestroy(e);
     for (int l = 1; l < FOVPT_MAX_LANES; l++) {          // ([0] are stream and shadow_stream)
-        if (lane_main[l]) (void)hipStreamDestroy(lane_main[l]);
-        if (lane_shadow[l]) (void)hipStreamDestroy(lane_shadow[l]);
+        if (engine.lane_main[l]) (void)hipStreamDestroy(engine.lane_main[l]);
+        if (engine.lane_shadow[l]) (void)hipStreamDestroy(engine.lane_shadow[l]);
     }
     if (stream) (void)hipStreamDestroy(stream);
     if (shadow_stream) (void)hipStreamDestroy(shadow_stream);
@@ -765,46 +797,7 @@ int fovpt_create(fovpt_ctx** out, int device)
     memset(&c->stats, 0, sizeof(c->stats));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
-    c->grid = c->num_cus * 8;                 // generate: 8 blocks of 256 = 32 waves per CU, grid-stride; a multiple of FOVPT_SHARDS
-    c->grid_trace = c->num_cus * FOVPT_GRID_PER_CU;   // closest-hit launches, in units of 256 threads (k_traverse's own blocks are FOVPT_TBLOCK threads)
-    c->grid_shadow = c->num_cus * FOVPT_GRID_SHADOW_PER_CU;   // occlusion launches (measured best of 2..8 with per-wave ray pools)
-    int v = 0;                                // tuning: blocks per CU
-    if (env_int("FOVPT_GRID_GEN", 1, 64, &v)) c->grid = c->num_cus * v;
-    if (env_int("FOVPT_GRID", 1, 64, &v)) c->grid_trace = c->num_cus * v;
-    if (env_int("FOVPT_GRID_SHADOW", 1, 16, &v)) c->grid_shadow = c->num_cus * v;
-    c->grid = (c->grid + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;      // shard_capacity() relies on it
-    c->grid_trace = (c->grid_trace + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;
-    c->grid_shadow = (c->grid_shadow + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;      // the work fetch of k_traverse relies on equal shard groups
-    // the shading kernel holds 4 waves per SIMD (104 VGPRs) = 4 blocks per CU; twice the resident number of blocks is
-    // measured best (blocks per CU 2 / 3 / 4 / 6 / 8: shading 0.307 / 0.274 / 0.261 / 0.263 / 0.244 ms per C3 frame)
-    c->grid_shade = c->num_cus * 8;
-    if (env_int("FOVPT_GRID_SHADE", 1, 16, &v)) c->grid_shade = c->num_cus * v;
-    c->grid_shade = (c->grid_shade + FOVPT_SHARDS - 1) / FOVPT_SHARDS * FOVPT_SHARDS;
-    if (const char* sb = getenv("FOVPT_SLOT_BUDGET")) { const long long v = atoll(sb); if (v > 0) c->slot_budget = (uint64_t)v; }   // tests: force chunking
-    // the main chain is the critical path: give it the higher priority so occlusion waves only fill gaps
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    e = hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_hi);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->shadow_stream, hipStreamDefault, prio_lo);
-    (void)env_int("FOVPT_LANES", 1, FOVPT_MAX_LANES, &c->lanes);
-    (void)env_int("FOVPT_SPREAD_OCCLUSION", INT_MIN, INT_MAX, &c->spread_occlusion);      // 0 off, 1 the last occlusion launch, 2 the second (A/B); not range-checked
-    (void)env_int("FOVPT_CHAINS", 1, 2, &c->chains_default);
-    v = 2 * c->lanes;
-    (void)env_int("FOVPT_SETS", 2, 2 * FOVPT_MAX_LANES, &v);
-    c->nsets = (unsigned)v;
-    c->lane_main[0] = c->stream; c->lane_shadow[0] = c->shadow_stream;
-    for (int l = 1; l < c->lanes; l++) {
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->lane_main[l], hipStreamDefault, prio_hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->lane_shadow[l], hipStreamDefault, prio_lo);
-    }
-    for (StateSet& S : c->set) {
-        for (ChainEvents& ch : S.chain)
-            for (int k = 0; k <= FOVPT_MAX_ITERS && e == hipSuccess; k++) {
-                e = hipEventCreateWithFlags(&ch.shade[k], hipEventDefault);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&ch.shadow[k], hipEventDefault);
-            }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev_done, hipEventDefault);
-    }
+    e = make_engine(c);
     if (e != hipSuccess) { fovpt_destroy(c); return fail(nullptr, FOVPT_E_DEVICE, "stream/event creation: %s", hipGetErrorString(e)); }
     *out = c;
     return FOVPT_OK;
@@ -959,9 +952,7 @@ int fovpt_set_probe(fovpt_ctx* c, int width, int height, const fovpt_float4* dat
     HIPCHK(c, hipSetDevice(c->device));
     CHK(sync_all(c));
     const size_t n = (size_t)width * height;
-    HIPCHK(c, c->pr_pdfx.reserve(n * 4)); HIPCHK(c, c->pr_cdfx.reserve(n * 4));
-    HIPCHK(c, c->pr_pdfy.reserve((size_t)height * 4)); HIPCHK(c, c->pr_cdfy.reserve((size_t)height * 4));
-    HIPCHK(c, c->pr_data.reserve(n * 16));
+    CHK(reserve_probe(c, width, height));
     HIPCHK(c, hipMemcpy(c->pr_pdfx.p, pdfX, n * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->pr_cdfx.p, cdfX, n * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->pr_pdfy.p, pdfY, (size_t)height * 4, hipMemcpyHostToDevice));
@@ -977,9 +968,7 @@ int fovpt_set_probe_data(fovpt_ctx* c, int width, int height, const fovpt_float4
     HIPCHK(c, hipSetDevice(c->device));
     CHK(sync_all(c));
     const size_t n = (size_t)width * height;
-    HIPCHK(c, c->pr_pdfx.reserve(n * 4)); HIPCHK(c, c->pr_cdfx.reserve(n * 4));
-    HIPCHK(c, c->pr_pdfy.reserve((size_t)height * 4)); HIPCHK(c, c->pr_cdfy.reserve((size_t)height * 4));
-    HIPCHK(c, c->pr_data.reserve(n * 16));
+    CHK(reserve_probe(c, width, height));
     HIPCHK(c, hipMemcpy(c->pr_data.p, data, n * 16, hipMemcpyHostToDevice));
     DevBuf row_total;
     HIPCHK(c, row_total.reserve((size_t)height * 4));
@@ -1092,7 +1081,7 @@ int fovpt_get_stats(fovpt_ctx* c, fovpt_stats* out)
     CHK(sync_all(c));
     drain_events(c);
     c->stats.radiance_rays = c->stats.shadow_rays = c->stats.paths = 0;
-    for (StateSet& S : c->set) {
+    for (StateSet& S : c->engine.set) {
         if (!S.counters.p) continue;
         unsigned long long h[3];                          // stat_radiance, stat_shadow, stat_paths
         HIPCHK(c, hipMemcpy(h, (const char*)S.counters.p + offsetof(Counters, stat_radiance), sizeof(h), hipMemcpyDeviceToHost));
@@ -1108,7 +1097,7 @@ int fovpt_reset_stats(fovpt_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     CHK(sync_all(c));
     drain_events(c);
-    for (StateSet& S : c->set)
+    for (StateSet& S : c->engine.set)
         if (S.counters.p) HIPCHK(c, hipMemset((char*)S.counters.p + offsetof(Counters, stat_radiance), 0, sizeof(Counters) - offsetof(Counters, stat_radiance)));
     c->stats.radiance_rays = c->stats.shadow_rays = c->stats.paths = c->stats.frames = 0;
     c->stats.ms_generate = c->stats.ms_trace = c->stats.ms_shade = c->stats.ms_shadow = c->stats.ms_resolve = 0.0;

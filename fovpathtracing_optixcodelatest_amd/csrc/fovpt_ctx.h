@@ -1,7 +1,8 @@
 // fovpt_ctx.h -- private to the host half of libfovpt (fovpt_api.hip, api_animate.hip, api_post.hip, api_view.hip, api_gather.hip,
 // api_packet.hip, api_debug.hip): the context, the buffers it owns, and the helpers more than one of those files uses.  The
-// post-frame stages' state is grouped: the record of the rendered frame (fovpt_ctx::rendered) and one struct per stage.  Host
-// only: no kernel file includes it.
+// frame engine's state is grouped (fovpt_ctx::engine: lanes, state sets, rotation, grids, knobs, timing events), and so is the
+// post-frame stages': the record of the rendered frame (fovpt_ctx::rendered) and one struct per stage.  Host only: no kernel file
+// includes it.
 #pragma once
 #include <cstring>
 #include <memory>
@@ -10,6 +11,7 @@
 
 #include "fovpt_bgjob.h"
 #include "fovpt_device.h"
+#include "fovpt_jobplan.h"      // the engine's constants and decisions (plan_job, chunk_rows, shard_capacity, chain_split)
 #include <rccl/rccl.h>      // types only: the library is loaded at run time (fovpt_comm_*), libfovpt.so does not link it
 
 // Device memory with one owner: freed by release(), by a growing reserve() and when the holder goes away.
@@ -44,10 +46,6 @@ struct FOVPT_LOCAL OutPair {
 enum TimedKind { T_GENERATE, T_TRACE, T_SHADE, T_SHADOW, T_RESOLVE };    // what a timed launch adds to in fovpt_stats
 struct EventPair { hipEvent_t a, b; TimedKind kind; };
 
-// Shadow-queue buffers per state set: bounce it writes buffer it % FOVPT_NSQ, so with max_depth <= FOVPT_NSQ the
-// main chain never has to wait for an occlusion launch inside a job.
-#define FOVPT_NSQ 4
-
 // The completion events of one chain's shading and occlusion launches, per iteration
 struct ChainEvents { hipEvent_t shade[FOVPT_MAX_ITERS + 1], shadow[FOVPT_MAX_ITERS + 1]; };
 
@@ -60,26 +58,42 @@ struct StateSet {
     bool used = false;
 };
 
-#ifndef FOVPT_LANES_DEFAULT
-#define FOVPT_LANES_DEFAULT 2
-#endif
-#define FOVPT_MAX_LANES 4
-#ifndef FOVPT_SETS_SLOT_LIMIT
-#define FOVPT_SETS_SLOT_LIMIT (16ull << 20)    // (~330 B of state and queues per slot and set)
-#endif
+// The frame engine (run_passes / run_job, fovpt_api.hip): everything a job is issued with.  Filled by fovpt_create (make_engine),
+// which reads the environment switches once.
+struct FOVPT_LOCAL Engine {
+    // Second LANE (round 3): consecutive jobs alternate between two (main, shadow) stream pairs, so the main chain of job k+1
+    // -- generate, closest-hit, shade, strictly one after the other -- runs BESIDE the main chain of job k instead of behind it:
+    // the launch gaps, ramps and tails of one chain are filled by the other.  Resolves stay in job order (each waits for the
+    // previous job's), and `shadow_stream` remains the one stream every finished frame is ordered on (fovpt_stream()).
+    hipStream_t lane_main[FOVPT_MAX_LANES] = {}, lane_shadow[FOVPT_MAX_LANES] = {};   // [0] = the context's stream / shadow_stream
+    // Every stream beside shadow_stream that may trace the scene or read its triangle records: the lanes' main streams and the
+    // later lanes' shadow streams, once each, in lane order.  Whoever waits for, or records behind, "everything that traces"
+    // walks these and names shadow_stream itself: first or last, as its order asks.
+    hipStream_t trace_stream[2 * FOVPT_MAX_LANES - 1] = {};
+    int num_trace_streams = 0;
+    // Wavefront state, several sets used in rotation by consecutive jobs: the tail of job k (its last occlusion
+    // rays and its resolve, on the shadow stream) runs beside the head of job k+1 (generate, camera rays).
+    // Round 4: TWICE as many sets as lanes, so that the job which follows job k on the same lane (job k + lanes) does not
+    // wait for job k's resolve before it may overwrite the path state: its main chain starts as soon as job k's has ended,
+    // and k's tail runs beside it.  (What a 1/N shard of a frame needs: its launches are short, and last occlusion launch +
+    // resolve were a third of a lane's cycle.)
+    StateSet set[2 * FOVPT_MAX_LANES];
+    PlanKnobs knobs;                       // lanes, nsets, chains_default, spread_occlusion (fovpt_jobplan.h)
+    PlanRotation rot;                      // jobs issued so far and the set the last one used
+    int grid = 2048, grid_trace = 2048, grid_shadow = 1024, grid_shade = 1024;   // blocks of generate, closest-hit, occlusion and shading launches
+    uint64_t slot_budget = 64ull << 20;    // sample slots per wavefront job (~330 B of state and queues each and per set; jobs above FOVPT_SETS_SLOT_LIMIT rotate through one set per lane)
+    DevBuf accum_before;                   // accumulate mode, chunked launch: the accum buffer as it was before the pass
+    bool refit_pending = false;            // a refit has recorded fovpt_ctx::ev_scene since the last job: the trace streams wait for it, once
+    std::vector<EventPair> pending;        // profile: the timed launches not yet read (drain_events), and events free for reuse
+    std::vector<hipEvent_t> free_events;
+};
 
 struct fovpt_ctx {
     int device = 0;
     int num_cus = 256;
     hipStream_t stream = nullptr;          // main chain: generate, closest-hit traversal, shade
     hipStream_t shadow_stream = nullptr;   // occlusion rays of every bounce and the resolve: off the critical path
-    // Second LANE (round 3): consecutive jobs alternate between two (main, shadow) stream pairs, so the main chain of job k+1
-    // -- generate, closest-hit, shade, strictly one after the other -- runs BESIDE the main chain of job k instead of behind it:
-    // the launch gaps, ramps and tails of one chain are filled by the other.  Resolves stay in job order (each waits for the
-    // previous job's), and `shadow_stream` remains the one stream every finished frame is ordered on (fovpt_stream()).
-    hipStream_t lane_main[FOVPT_MAX_LANES] = {}, lane_shadow[FOVPT_MAX_LANES] = {};   // [0] = stream / shadow_stream
-    int lanes = FOVPT_LANES_DEFAULT;
-    int chains_default = 1;                // what fovpt_config.chains_per_frame = 0 means (FOVPT_CHAINS)
+    Engine engine;                         // the frame engine: lanes, state sets, rotation, grids, knobs, timing events
     std::string err;
     fovpt_config cfg;
     // scene
@@ -96,14 +110,13 @@ struct fovpt_ctx {
     // concatenated vertex array and vertex count; per primitive the indices of its three vertices in that array; the positions.
     // Made on the first update: their device copies (up_vtx 12 B per vertex, up_vidx 12 B per primitive), two pinned staging
     // buffers for host updates used in turn (each reused once its previous copy has run: ev), and the event a refit records on
-    // fovpt_stream(), which every lane stream waits for before the next job traces the scene (refit_pending).
+    // fovpt_stream(), which every lane stream waits for before the next job traces the scene (engine.refit_pending).
     std::vector<uint32_t> mesh_prim0, mesh_vbase, mesh_nv, h_tri_vidx;
     std::vector<float> h_vtx;
     DevBuf up_vtx, up_vidx;
     struct Staging { void* p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } up_stage[2];
     int up_next = 0;
     hipEvent_t ev_scene = nullptr;
-    bool refit_pending = false;
     // fovpt_update_transforms.  Made on a scene's first call and dropped by fovpt_set_scene: the device copy of h_vtx (12 B per
     // vertex) and, per mesh, the largest |coordinate| of its rest positions (the overflow rule)
     DevBuf rest_vtx;
@@ -180,12 +193,10 @@ struct fovpt_ctx {
     bool rows_identical = false;           // every row of data / pdfX / cdfX equals row 0 bit for bit
     // frame buffers (resize)
     DevBuf fb_frame, fb_accum, fb_color, fb_normal, fb_albedo;
-    DevBuf accum_before;                   // accumulate mode, chunked launch: the accum buffer as it was before the launch
     // multi-GPU gather plan (fovpt_gather_plan): pixel indices grouped by owning rank
     DevBuf plan_owner, plan_blocks, plan_total, plan_base, plan_idx;
     std::vector<uint32_t> plan_off;        // host copy: rank r owns plan_idx[plan_off[r] .. plan_off[r + 1])
     std::string plan_key;                  // what the plan was built for
-    bool use_accum_before = false;
     // ---- the post-frame stages (api_post.hip, api_view.hip): the record of the rendered frame they all read, then one struct per
     // stage with what that stage owns, `out` being its own outputs.  post_resize keeps what exists of them at the frame's size.
     // The frame last issued with fovpt_render as it was rendered (w x h; 0 x 0: none since create / resize): its passes, gaze
@@ -258,23 +269,8 @@ struct fovpt_ctx {
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
     DevBuf comm_packed, comm_gathered;
-    // Wavefront state, several sets used in rotation by consecutive jobs: the tail of job k (its last occlusion
-    // rays and its resolve, on the shadow stream) runs beside the head of job k+1 (generate, camera rays).
-    // Round 4: TWICE as many sets as lanes, so that the job which follows job k on the same lane (job k + lanes) does not
-    // wait for job k's resolve before it may overwrite the path state: its main chain starts as soon as job k's has ended,
-    // and k's tail runs beside it.  (What a 1/N shard of a frame needs: its launches are short, and last occlusion launch +
-    // resolve were a third of a lane's cycle.)
-    StateSet set[2 * FOVPT_MAX_LANES];
-    unsigned nsets = 4;                    // sets in rotation for ordinary jobs = 2 * lanes (FOVPT_SETS: 2 .. 2 * FOVPT_MAX_LANES)
-    unsigned last_set = 0;                 // the set the most recent job used
-    unsigned jobs = 0;                     // jobs issued so far; job j runs on lane j % lanes
-    int grid = 2048, grid_trace = 2048, grid_shadow = 1024, grid_shade = 1024;
-    int spread_occlusion = 1;              // sharded frames: one occlusion launch of a first-lane job runs on the second lane's shadow stream (FOVPT_SPREAD_OCCLUSION)
-    uint64_t slot_budget = 64ull << 20;    // sample slots per wavefront job (~330 B of state and queues each and per set; jobs above FOVPT_SETS_SLOT_LIMIT rotate through one set per lane)
     // stats
     fovpt_stats stats;
-    std::vector<EventPair> pending;
-    std::vector<hipEvent_t> free_events;
     // fovpt_warp_motion: what it asks of the last temporal step and of the last G-buffer trace, all on the host.  tm_step_blind
     // (set by every temporal step): the step ended an interval with an update the tracking did not see, so no mesh counts as
     // moved in it.  seq: one counter, incremented at each of the events below, whose value then is the event's stamp (0: never)
@@ -305,22 +301,25 @@ int measure_built(fovpt_ctx* c);
 // Hidden: the library does not export them.
 #pragma GCC visibility push(hidden)
 struct ProbePath { const uint32_t *guide_x, *guide_y; const float4* rec; int32_t row_mul; };
-struct ChainSplit { uint32_t sel, slot_begin, slot_end; };
 inline bool probe_complete(const fovpt_probe& p)              // what a launch needs of a probe: the texels, the four tables and a size
 {
     return p.data && p.cdfValuesX && p.cdfValuesY && p.pdfValuesX && p.pdfValuesY && p.width > 0 && p.height > 0;
 }
-uint32_t shard_capacity(size_t slots);                        // entries of one queue shard of a job of `slots` sample slots
 int ensure_state(fovpt_ctx* c, StateSet& S, size_t slots, size_t launches, hipStream_t st);   // S holds a job of that size (st: the stream about to use it)
 PathState path_state(const fovpt_ctx* c, const StateSet& S);  // what the kernels see of a state set: its path state ...
 RayQueue ray_queue(const StateSet& S, int k);                 // ... its k-th radiance-ray queue (0, 1) ...
 ShadowQueue shadow_queue(const StateSet& S, int k);           // ... and its k-th shadow queue (0 .. FOVPT_NSQ - 1)
 ProbePath probe_path(const fovpt_ctx* c, const fovpt_probe& probe);   // how a launch searches and reads the caller's probe
-ChainSplit chain_split(uint64_t slots, int k);                // chain k (0, 1) of a job of two chains: its shards and sample slots
 PassDev pass_from_lp(const fovpt_launch_params* lp, uint32_t gw, uint32_t gh);   // the pass of one fovpt_launch of a gw x gh grid
 int frame_passes(const fovpt_config& cfg, fovpt_launch_params& L, PassDev* P);   // the passes of one fovpt_render; sets L's per-pass members
-int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame, FrameDev& fd,
-              uint64_t& slots, uint64_t& launches);           // what the kernels see of a job's frame, and its sample slots and launch records
+// the pass table of one job: `in` whole (row1 = 0: the rows 0 .. gh of each pass) or the launch rows [row0, row1) of each, as
+// the passes first_pass, first_pass + 1, ... of the caller's frame (out may be in); *over: 0, or the job's sample slots when they
+// exceed the budget of one job
+int job_passes(fovpt_ctx* c, const PassDev* in, int npass, uint32_t first_pass, uint32_t row0, uint32_t row1, PassDev* out, uint64_t* over);
+// what the kernels see of a job's frame, and its sample slots and launch records (accum_prev: what an accumulating resolve
+// blends with when that is not the accum buffer itself -- the chunks of a pass --, else null)
+int frame_dev(fovpt_ctx* c, const fovpt_launch_params* lp, const PassDev* passes_in, int npass, int chunked, int whole_frame,
+              const fovpt_float4* accum_prev, FrameDev& fd, uint64_t& slots, uint64_t& launches);
 #pragma GCC visibility pop
 // api_animate.hip (fovpt_set_scene and the context's destructor drop what the update calls keep of a scene)
 void drop_animation(fovpt_ctx* c);

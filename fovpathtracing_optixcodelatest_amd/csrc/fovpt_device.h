@@ -10,9 +10,9 @@
 #include <vector>
 
 #include "../../include/fovpt.h"
+#include "fovpt_jobplan.h"      // FOVPT_BLOCK, FOVPT_MAX_PASSES, FOVPT_MAX_ITERS, FOVPT_SHARDS and the engine's other constants
 
 #define FOVPT_WAVE 64
-#define FOVPT_BLOCK 256
 #ifndef FOVPT_V_STEPSTAT
 #define FOVPT_V_STEPSTAT 0         // 1: diagnostic build: k_traverse counts steps (tools/stepstat.py, raystat.py, stepcount.py, raytrace_dump.py)
 #endif
@@ -35,9 +35,6 @@
 #ifndef FOVPT_GRID_SHADOW_PER_CU
 #define FOVPT_GRID_SHADOW_PER_CU 6
 #endif
-#define FOVPT_MAX_PASSES 3
-#define FOVPT_MAX_ITERS 63         // wavefront iterations per frame (max_depth + catcher pass-throughs)
-#define FOVPT_SHARDS 8            // queue shards: one append counter per blockIdx % 8 (~ per XCD)
 
 // One triangle in BVH leaf order, pre-subtracted edges (exactly v1-v0 and v2-v0 in fp32,
 // so Moeller-Trumbore gives the same bits as the contract in include/fovpt.h / oracle).

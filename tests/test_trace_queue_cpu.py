@@ -19,7 +19,7 @@ DEFINES = {"FOVPT_BLOCK": 256, "FOVPT_TBLOCK": 64, "FOVPT_GRID_PER_CU": 24, "FOV
 BLOCK, TBLOCK, SHARDS = DEFINES["FOVPT_BLOCK"], DEFINES["FOVPT_TBLOCK"], DEFINES["FOVPT_SHARDS"]
 TQUADS, REFILL = TBLOCK // 4, DEFINES["FOVPT_REFILL"]                          # rays per wave and round; idle quads that trigger a refill
 STRIDE, MAX_ITERS = DEFINES["FOVPT_SHARD_STRIDE"], DEFINES["FOVPT_MAX_ITERS"]  # counter words per shard; iterations
-CAP_SLACK = 512                     # shard_capacity(slots) = slots / FOVPT_SHARDS + 512 (csrc/fovpt_api.hip)
+CAP_SLACK = 512                     # shard_capacity(slots) = slots / FOVPT_SHARDS + 512 (csrc/fovpt_jobplan.h)
 
 
 def _capacity(run):
@@ -27,22 +27,24 @@ def _capacity(run):
 
 
 def test_the_walk_has_the_sources_constants():
-    """The defines of csrc/fovpt_device.h and csrc/traverse.hip, and the capacity rule of csrc/fovpt_api.hip, are what the walk
+    """The defines of csrc/fovpt_device.h, csrc/fovpt_jobplan.h and csrc/traverse.hip, the capacity rule of csrc/fovpt_jobplan.h and
+    the grids per CU that csrc/fovpt_api.hip gives the traversal launches are what the walk
     assumes: a change of the block size, the refill threshold, the grids per CU or the counter layout fails here, not silently in
     the reach shown below.  One wave per block, eight shards and two chains of four are built into the walk's shape."""
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fovpathtracing_optixcodelatest_amd", "csrc")
-    text = "".join(open(os.path.join(csrc, f)).read() for f in ("fovpt_device.h", "traverse.hip"))
+    text = "".join(open(os.path.join(csrc, f)).read() for f in ("fovpt_device.h", "fovpt_jobplan.h", "traverse.hip"))
     for name, value in DEFINES.items():
         found = re.findall(r"^\s*#define\s+%s\s+(\d+)\b" % name, text, flags=re.M)
         assert found and all(int(x) == value for x in found), (name, found, value)
     assert TBLOCK == 64 and SHARDS == 8
     assert re.search(r"#define\s+FOVPT_TQUADS\s+\(FOVPT_TBLOCK\s*/\s*4\)", text)
     assert re.search(r"#define\s+FOVPT_CNT_SQ\(it\)\s+\(FOVPT_MAX_ITERS \+ 1 \+ \(it\)\)", text) and re.search(r"#define\s+FOVPT_CNT_Q\(it\)\s+\(it\)", text)
+    assert "return (uint32_t)(slots / FOVPT_SHARDS + %d);" % CAP_SLACK in text
     api = open(os.path.join(csrc, "fovpt_api.hip")).read()
-    assert "return (uint32_t)(slots / FOVPT_SHARDS + %d);" % CAP_SLACK in api
-    assert "c->grid_trace = c->num_cus * FOVPT_GRID_PER_CU;" in api and "c->grid_shadow = c->num_cus * FOVPT_GRID_SHADOW_PER_CU;" in api
+    assert '{"FOVPT_GRID", 64, FOVPT_GRID_PER_CU, &E.grid_trace}' in api and '{"FOVPT_GRID_SHADOW", 16, FOVPT_GRID_SHADOW_PER_CU, &E.grid_shadow}' in api
+    assert "*g.grid = shard_grid(c->num_cus * per_cu);" in api
 
 
 # ---- the oracle alone: the rays of every case hit and miss, are occluded and are not -----------------------------------------
