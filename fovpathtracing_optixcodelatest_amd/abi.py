@@ -569,6 +569,43 @@ class LensConfig(C.Structure):
         return {n: (tuple(get(n)) if isinstance(get(n), C.Array) else get(n)) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+class VarianceConfig(C.Structure):
+    """fovpt_variance_config: the cap of the moment history, the history length below which the spatial estimate is taken, that
+    estimate's radius and the tolerances of the history taps and the window (defaults: fovpt_variance_defaults)."""
+    _fields_ = [
+        ("history_cap", C.c_int32), ("spatial_below", C.c_int32), ("spatial_radius", C.c_int32),
+        ("depth_tolerance", C.c_float), ("normal_tolerance", C.c_float),
+        ("_reserved", C.c_int32 * 3),
+    ]
+
+    def copy(self):
+        m = VarianceConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(VarianceConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class VarianceFilterConfig(C.Structure):
+    """fovpt_variance_filter_config: a-trous iterations per foveation level, the luminance (in standard deviations), normal and
+    plane-distance edge-stopping scales and the albedo demodulation (defaults: fovpt_variance_filter_defaults)."""
+    _fields_ = [
+        ("iterations_fovea", C.c_int32), ("iterations_middle", C.c_int32), ("iterations_periphery", C.c_int32), ("iterations_uniform", C.c_int32),
+        ("luminance_sigma", C.c_float), ("normal_sigma", C.c_float), ("depth_sigma", C.c_float),
+        ("demodulate", C.c_int32),
+        ("_reserved", C.c_int32 * 4),
+    ]
+
+    def copy(self):
+        m = VarianceFilterConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(VarianceFilterConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
 QUALITY_SSIM, QUALITY_PROFILE = 1, 2                   # FOVPT_QUALITY_* flags
 QUALITY_CLASSES, QUALITY_RINGS, QUALITY_MAX_RING_WIDTH = 5, 64, 65536
 QUALITY_FOVEA, QUALITY_MIDDLE, QUALITY_PERIPHERY, QUALITY_UNIFORM, QUALITY_UNWRITTEN = 0, 1, 2, 3, 4   # a pixel's class
@@ -671,6 +708,8 @@ assert C.sizeof(FocusState) == 32 and FocusState.count.offset == 16
 assert C.sizeof(QualityConfig) == 32 and QualityConfig._reserved.offset == 8
 assert C.sizeof(QualitySums) == 1344 and (QualitySums.max_err.offset, QualitySums.windows.offset, QualitySums.ring_pixels.offset, QualitySums.width.offset) == (200, 224, 304, 1328)
 assert C.sizeof(LensConfig) == 128 and (LensConfig.k.offset, LensConfig.clip_r2.offset, LensConfig.border.offset, LensConfig._reserved.offset) == (32, 60, 80, 96)
+assert C.sizeof(VarianceConfig) == 32 and (VarianceConfig.depth_tolerance.offset, VarianceConfig._reserved.offset) == (12, 20)
+assert C.sizeof(VarianceFilterConfig) == 48 and (VarianceFilterConfig.luminance_sigma.offset, VarianceFilterConfig.demodulate.offset, VarianceFilterConfig._reserved.offset) == (16, 28, 32)
 assert C.sizeof(PacketPass) == 32 and PacketPass.texels.offset == 24
 assert C.sizeof(PacketConfig) == 16 and PacketConfig._reserved.offset == 12
 assert C.sizeof(PacketHeader) == 128 and (PacketHeader.width.offset, PacketHeader.passes.offset) == (16, 32)

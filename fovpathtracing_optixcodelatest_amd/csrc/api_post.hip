@@ -1,11 +1,13 @@
 // api_post.hip -- post-processing of the rendered frame over the C ABI, first half: the steps every post-frame stage shares (declared
 // in fovpt_ctx.h; api_view.hip and api_packet.hip use them too), what fovpt_resize and fovpt_set_scene ask of the stages
 // (post_resize, post_scene_changed), and the stages that rebuild the image: fovpt_denoise (denoise.hip), fovpt_gbuffer /
-// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_post (post_fused.hip), and their
-// defaults.  Every stage has the same parts -- *_check (nothing allocated, enqueued or changed), the kernel's arguments from the
-// config and the rendered frame's record (*_args where more than one place needs them) and *_enqueue (reservations and launches of
-// a checked call) -- and its entry point is: null checks, check, hipSetDevice, own outputs, alias check, enqueue.  fovpt_post
-// checks every enabled stage, then enqueues them.  The state is fovpt_ctx::rendered and one struct per stage (fovpt_ctx.h).
+// fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_post (post_fused.hip),
+// fovpt_variance / fovpt_variance_filter (variance.hip), and their defaults.  Every stage has the same parts -- *_check (nothing
+// allocated, enqueued or changed), the kernel's arguments from the config and the rendered frame's record (*_args where more than
+// one place needs them) and *_enqueue (reservations and launches of a checked call; the two variance calls, which nothing else
+// enqueues, have theirs in the entry point) -- and its entry point is: null checks, check, hipSetDevice, own outputs, alias check,
+// enqueue.  fovpt_post checks every enabled stage, then enqueues them.  The state is fovpt_ctx::rendered and one struct per stage
+// (fovpt_ctx.h).
 #include <cmath>
 #include <cstring>
 
@@ -158,6 +160,14 @@ static int reserve_temporal(fovpt_ctx* c, size_t n)
     return FOVPT_OK;
 }
 
+// fovpt_variance's moment histories and variance image for n pixels
+static int reserve_variance(fovpt_ctx* c, size_t n)
+{
+    fovpt_ctx::Variance& V = c->variance;
+    HIPCHK(c, V.hist[0].reserve(n * 16)); HIPCHK(c, V.hist[1].reserve(n * 16)); HIPCHK(c, V.image.reserve(n * 16));
+    return FOVPT_OK;
+}
+
 // fovpt_resize: what exists of the stages' buffers follows the frame (nothing is made here); the states of fovpt_expose and
 // fovpt_focus and the record of fovpt_quality stay
 int post_resize(fovpt_ctx* c, int w, int h)
@@ -176,6 +186,10 @@ int post_resize(fovpt_ctx* c, int w, int h)
     if (c->focus.rt.p) HIPCHK(c, c->focus.rt.reserve(n * 8));
     HIPCHK(c, follow(c->focus.out));
     HIPCHK(c, follow(c->lens.out));
+    if (c->variance.hist[0].p) CHK(reserve_variance(c, n));
+    HIPCHK(c, follow(c->variance.out));
+    c->variance.valid = false;                                             // (its history is of another size, and so is its image)
+    c->variance.own_w = c->variance.own_h = 0;
     if (c->quality.rows.p) HIPCHK(c, c->quality.rows.reserve((size_t)fovpt_quality_rows(w, h) * FOVPT_QUALITY_COLUMNS * sizeof(uint64_t)));
     c->temporal.valid = false;                                             // (its history is of another size)
     c->rendered.w = c->rendered.h = 0;                                     // (nothing rendered at this size yet)
@@ -186,6 +200,7 @@ int post_resize(fovpt_ctx* c, int w, int h)
 int post_scene_changed(fovpt_ctx* c)
 {
     c->temporal.valid = false;                       // fovpt_temporal's history: primitive ids change
+    c->variance.valid = false;                       // fovpt_variance's moments: of another scene's surfaces
     c->seq_frame = ++c->seq;                         // fovpt_warp_motion: the hit records of the last trace are another scene's
     CHK(record_reset(c, c->expose.state, sizeof(ExposeState), nullptr));   // fovpt_expose adapts to another scene from scratch
     return record_reset(c, c->focus.state, sizeof(FocusState), nullptr);   // and fovpt_focus meters it from scratch
@@ -431,6 +446,66 @@ int temporal_step(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_tempo
     return temporal_enqueue(c, lp, tc, in, out_color, out_rgba, out_motion, motion, who);
 }
 
+// what fovpt_variance and fovpt_variance_filter ask of the scene, the rendered frame and a caller's G-buffer (need_albedo: the
+// filter demodulates), after their configs are checked.  in: the colour input
+int variance_frame_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_gbuffer_ptrs* gbuffer, bool need_albedo, const fovpt_float4* in,
+                         const char* who, const char* to_what)
+{
+    if (!gbuffer && (!c->has_scene || lp->traversable != c->scene_id)) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
+#if FOVPT_V_STEPSTAT
+    if (!gbuffer) return fail(c, FOVPT_E_INVALID, "%s: the G-buffer is not available in a diagnostic (FOVPT_V_STEPSTAT) build", who);
+#endif
+    CHK(check_rendered_frame(c, lp, who, to_what, nullptr, 1ull << 31));
+    if (gbuffer && (gbuffer->width != c->rendered.w || gbuffer->height != c->rendered.h || !gbuffer->position || !gbuffer->normal))
+        return fail(c, FOVPT_E_INVALID, "%s: the G-buffer is not of the frame's size %d x %d, or has a null position or normal", who, c->rendered.w, c->rendered.h);
+    if (gbuffer && need_albedo && !gbuffer->albedo) return fail(c, FOVPT_E_INVALID, "%s: demodulate = 1 with a G-buffer that has a null albedo", who);
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+    return FOVPT_OK;
+}
+
+// fovpt_variance's validation; makes the kernel's arguments but has_history
+int variance_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_variance_config* vc, const fovpt_gbuffer_ptrs* gbuffer, const fovpt_float4* in,
+                   const char* who, VarianceArgs& a)
+{
+    if (vc->history_cap < 1 || vc->history_cap > FOVPT_TEMPORAL_MAX_HISTORY)
+        return fail(c, FOVPT_E_INVALID, "%s: history_cap %d outside 1 .. %d", who, vc->history_cap, FOVPT_TEMPORAL_MAX_HISTORY);
+    if (vc->spatial_below < 0 || vc->spatial_below > vc->history_cap + 1)
+        return fail(c, FOVPT_E_INVALID, "%s: spatial_below %d outside 0 .. history_cap + 1", who, vc->spatial_below);
+    if (vc->spatial_radius < 1 || vc->spatial_radius > 3) return fail(c, FOVPT_E_INVALID, "%s: spatial_radius %d outside 1 .. 3", who, vc->spatial_radius);
+    if (!(vc->depth_tolerance >= 0.0f && vc->depth_tolerance <= 1.0f))
+        return fail(c, FOVPT_E_INVALID, "%s: depth_tolerance %g outside [0, 1]", who, (double)vc->depth_tolerance);
+    if (!(vc->normal_tolerance >= 0.0f && vc->normal_tolerance <= 4.0f))
+        return fail(c, FOVPT_E_INVALID, "%s: normal_tolerance %g outside [0, 4]", who, (double)vc->normal_tolerance);
+    CHK(check_reserved(c, vc->_reserved, sizeof(vc->_reserved) / 4, who));
+    CHK(variance_frame_check(c, lp, gbuffer, false, in, who, "estimate variance from"));
+    const FrameDev& fd = c->rendered.frame;
+    float M[9];
+    if (!camera_inverse(fd.U, fd.V, fd.W, M)) return fail(c, FOVPT_E_INVALID, "%s: the rendered camera is singular", who);
+    memset(&a, 0, sizeof(a));
+    memcpy(a.eye, fd.eye, sizeof(a.eye)); memcpy(a.m2, M + 6, sizeof(a.m2));
+    a.depth_tol = vc->depth_tolerance; a.normal_tol = vc->normal_tolerance;
+    a.cap = vc->history_cap; a.spatial_below = vc->spatial_below; a.radius = vc->spatial_radius;
+    return FOVPT_OK;
+}
+
+// fovpt_variance_filter's validation.  variance: the caller's, or null for the context's own image
+int variance_filter_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_variance_filter_config* fc, const fovpt_gbuffer_ptrs* gbuffer,
+                          const fovpt_float4* in, const fovpt_float4* variance, const char* who)
+{
+    const int32_t its[4] = {fc->iterations_fovea, fc->iterations_middle, fc->iterations_periphery, fc->iterations_uniform};
+    for (int32_t n : its)
+        if (n < 0 || n > FOVPT_DENOISE_MAX_ITERATIONS) return fail(c, FOVPT_E_INVALID, "%s: iteration count %d outside 0 .. %d", who, n, FOVPT_DENOISE_MAX_ITERATIONS);
+    const float sig[3] = {fc->luminance_sigma, fc->normal_sigma, fc->depth_sigma};
+    for (float v : sig)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "%s: sigma %g outside [%g, %g]", who, (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    if (fc->demodulate != 0 && fc->demodulate != 1) return fail(c, FOVPT_E_INVALID, "%s: demodulate %d is neither 0 nor 1", who, fc->demodulate);
+    CHK(check_reserved(c, fc->_reserved, sizeof(fc->_reserved) / 4, who));
+    CHK(variance_frame_check(c, lp, gbuffer, fc->demodulate != 0, in, who, "filter with"));
+    if (!variance && (c->variance.own_w != c->rendered.w || c->variance.own_h != c->rendered.h))
+        return fail(c, FOVPT_E_NO_FRAME, "%s: no fovpt_variance has written the context's variance image at this frame size", who);
+    return FOVPT_OK;
+}
+
 }  // namespace
 
 // fovpt_reconstruct_defaults (chosen by measurement: DESIGN.md, section 11)
@@ -653,6 +728,128 @@ int fovpt_post(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_post_con
         if (R) ra = reconstruct_args(&pc->reconstruct);
         return temporal_enqueue(c, lp, &pc->temporal, in, out_color, out_rgba, out_motion, M, who, R ? &ra : nullptr);
     }
+    return FOVPT_OK;
+}
+
+// ---- luminance moment history and variance-guided a-trous filter (variance.hip; their definition: tests/variance_ref.py) ----------
+// (conventions, not measurements: SVGF's history, threshold and window, fovpt_temporal's tolerances)
+int fovpt_variance_defaults(fovpt_variance_config* out)
+{
+    if (!zeroed(out)) return FOVPT_E_INVALID;
+    out->history_cap = 16;
+    out->spatial_below = 4;
+    out->spatial_radius = 3;
+    out->depth_tolerance = FOVPT_TEMPORAL_DEPTH_TOLERANCE;
+    out->normal_tolerance = FOVPT_TEMPORAL_NORMAL_TOLERANCE;
+    return FOVPT_OK;
+}
+
+int fovpt_variance_buffers(fovpt_ctx* c, fovpt_float4** variance, const fovpt_float4** moments)
+{
+    if (!c || !variance || !moments) return FOVPT_E_INVALID;
+    *variance = nullptr; *moments = nullptr;
+    fovpt_ctx::Variance& V = c->variance;
+    if (!V.image.p) {
+        if (c->rendered.w <= 0 || c->rendered.h <= 0) return fail(c, FOVPT_E_NO_FRAME, "fovpt_variance_buffers: no frame rendered yet");
+        HIPCHK(c, hipSetDevice(c->device));
+    }
+    CHK(reserve_variance(c, c->rendered.pixels()));
+    *variance = (fovpt_float4*)V.image.p;
+    *moments = (const fovpt_float4*)V.hist[V.last].p;
+    return FOVPT_OK;
+}
+
+int fovpt_variance_reset(fovpt_ctx* c)
+{
+    if (!c) return FOVPT_E_INVALID;
+    c->variance.valid = false;
+    return FOVPT_OK;
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  Without a caller's G-buffer the rendered frame's first (the same
+// stream, into fovpt_gbuffer's buffers); then one launch of k_variance_moments, from the history the last call wrote into the other.
+int fovpt_variance(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_variance_config* vc, const fovpt_gbuffer_ptrs* gbuffer,
+                   const fovpt_float4* in_sample, const fovpt_float4* motion, fovpt_float4* out_variance)
+{
+    const char* who = "fovpt_variance";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !vc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const fovpt_float4* in = in_sample ? in_sample : lp->frame.accum_buffer;
+    VarianceArgs a;
+    CHK(variance_check(c, lp, vc, gbuffer, in, who, a));
+    HIPCHK(c, hipSetDevice(c->device));
+    fovpt_ctx::Variance& V = c->variance;
+    const fovpt_ctx::Rendered& R = c->rendered;
+    CHK(reserve_variance(c, R.pixels()));
+    const bool own = !out_variance;
+    if (own) out_variance = (fovpt_float4*)V.image.p;
+    GBufferDev g = gbuffer_dev(c, gbuffer);                                // (the context's own: null until the first trace)
+    CHK(check_aliases(c, {out_variance}, {in, g.pos, g.nrm, motion, V.hist[0].p, V.hist[1].p}, who,
+                      "%s: the output is an input of the call or a moment history (the kernel reads across pixels)"));
+    if (!gbuffer) CHK(enqueue_gbuffer(c, lp, R.frame, g, who));           // the rendered frame's camera
+    const int cur = V.last ^ 1, prev = V.last;
+    a.has_history = V.valid && V.w == R.w && V.h == R.h;
+    fovpt_launch_variance(c->shadow_stream, R.frame, a, in, g.pos, g.nrm, motion, (const float4*)V.hist[prev].p, (float4*)V.hist[cur].p, out_variance);
+    HIPCHK(c, hipGetLastError());
+    V.last = cur;                                                          // this step is the next one's previous step
+    V.valid = true;
+    V.w = R.w; V.h = R.h;
+    if (own) { V.own_w = R.w; V.own_h = R.h; }
+    return FOVPT_OK;
+}
+
+// (conventions, not measurements: SVGF's luminance scale, fovpt_reconstruct's normal and depth scales)
+int fovpt_variance_filter_defaults(fovpt_variance_filter_config* out)
+{
+    if (!zeroed(out)) return FOVPT_E_INVALID;
+    out->iterations_fovea = 0;
+    out->iterations_middle = 2;
+    out->iterations_periphery = 4;
+    out->iterations_uniform = 4;
+    out->luminance_sigma = 4.0f;
+    out->normal_sigma = FOVPT_RECONSTRUCT_NORMAL_SIGMA;
+    out->depth_sigma = FOVPT_RECONSTRUCT_DEPTH_SIGMA;
+    out->demodulate = 1;
+    return FOVPT_OK;
+}
+
+int fovpt_variance_filter_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    return c ? own_buffers(c, "fovpt_variance_filter_buffers", c->variance.out, color, rgba) : FOVPT_E_INVALID;
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it.  Without a caller's G-buffer the rendered frame's first; then
+// k_vfilter_prep and one k_vfilter_step per iteration.
+int fovpt_variance_filter(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_variance_filter_config* fc, const fovpt_gbuffer_ptrs* gbuffer,
+                          const fovpt_float4* in_color, const fovpt_float4* variance, fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    const char* who = "fovpt_variance_filter";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !fc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    CHK(variance_filter_check(c, lp, fc, gbuffer, in, variance, who));
+    HIPCHK(c, hipSetDevice(c->device));
+    fovpt_ctx::Variance& V = c->variance;
+    const fovpt_ctx::Rendered& R = c->rendered;
+    CHK(own_outputs(c, who, V.out, out_color, out_rgba));
+    if (!variance) variance = (const fovpt_float4*)V.image.p;
+    GBufferDev g = gbuffer_dev(c, gbuffer);                                // (the context's own: null until the first trace)
+    CHK(check_aliases(c, {out_color, out_rgba}, {in, variance, g.pos, g.nrm, fc->demodulate ? g.alb : nullptr}, who,
+                      "%s: an output is an input of the call (the kernels gather across pixels)"));
+    const size_t npix = R.pixels();
+    HIPCHK(c, V.level.reserve(npix));
+    HIPCHK(c, V.j0.reserve(npix * 16));
+    HIPCHK(c, V.j1.reserve(npix * 16));
+    if (!gbuffer) CHK(enqueue_gbuffer(c, lp, R.frame, g, who));           // the rendered frame's camera
+    VFilterArgs a;
+    memset(&a, 0, sizeof(a));
+    if (R.uniform) a.n_pass[0] = fc->iterations_uniform;
+    else { a.n_pass[0] = fc->iterations_periphery; a.n_pass[1] = fc->iterations_middle; a.n_pass[2] = fc->iterations_fovea; }
+    for (int p = 0; p < R.frame.npass; p++) a.iterations = a.n_pass[p] > a.iterations ? a.n_pass[p] : a.iterations;
+    a.demodulate = fc->demodulate;
+    a.sl2 = fc->luminance_sigma * fc->luminance_sigma; a.inv_n = inv_sq(fc->normal_sigma); a.inv_z = inv_sq(fc->depth_sigma);
+    fovpt_launch_vfilter(c->shadow_stream, R.frame, a, in, variance, g, (float4*)V.j0.p, (float4*)V.j1.p, (uint8_t*)V.level.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
 }
 

@@ -252,7 +252,19 @@ struct fovpt_ctx {
     // step is a first step; the host never reads it outside fovpt_focus_state), the (r, tp) pairs of the last call (8 bytes per
     // pixel) and the context's own outputs; all allocated on first use
     struct FOVPT_LOCAL Focus { DevBuf state, rt; OutPair out; } focus;
-    // fovpt_quality: the context's own record (a fovpt_quality_sums, made by the first call that measures into it, which writes
+    // fovpt_variance: two moment histories (M1, M2, n, z), used in turn by consecutive calls (last: the one the last call wrote), and
+    // the context's own variance image; valid: a previous step exists, of size w x h (dropped by fovpt_variance_reset, fovpt_resize
+    // and fovpt_set_scene); own_w x own_h: the frame size at which a step last wrote the context's own image (0: none since create /
+    // resize).  fovpt_variance_filter: the level map, the ping-pong (I, v) buffers and the context's own outputs.  All allocated on
+    // first use
+    struct FOVPT_LOCAL Variance {
+        DevBuf hist[2], image;
+        int last = 0, w = 0, h = 0, own_w = 0, own_h = 0;
+        bool valid = false;
+        DevBuf level, j0, j1;
+        OutPair out;
+    } variance;
+    // fovpt_quality: the context's own record(a fovpt_quality_sums, made by the first call that measures into it, which writes
     // every byte; the host reads it nowhere but in fovpt_quality_read) and the tile kernel's rows of partial sums
     // (fovpt_quality_rows of the frame's size); both allocated on first use
     struct FOVPT_LOCAL Quality { DevBuf sums, rows; } quality;

@@ -402,6 +402,26 @@ struct LensArgs {
     float center[2], scale[2], k[4], chroma[3], clip_r2, src_center[2], src_scale[2], border[4];
 };
 void fovpt_launch_lens(hipStream_t st, int w, int h, const LensArgs& a, const fovpt_float4* in, fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_variance (variance.hip): one launch of k_variance_moments.  pos / nrm: the rendered frame's G-buffer; motion may be null;
+// hist_prev is read only with has_history; out_variance is none of the inputs and neither history (a pixel reads other pixels').
+struct VarianceArgs {
+    float eye[3], m2[3];                // the rendered camera's eye and the third row of its inverse [U V W]^-1 (binary64 on the host, rounded to fp32)
+    float depth_tol, normal_tol;
+    int32_t cap, spatial_below, radius;
+    int32_t has_history;                // a previous step of this frame size exists
+};
+void fovpt_launch_variance(hipStream_t st, const FrameDev& fd, const VarianceArgs& a, const fovpt_float4* in, const float4* pos, const float4* nrm,
+                           const fovpt_float4* motion, const float4* hist_prev, float4* hist_out, fovpt_float4* out_variance);
+// fovpt_variance_filter (variance.hip): level map + demodulation + the initial variance, then `iterations` a-trous launches (the
+// last writes the outputs).  J0 / J1: ping-pong float4 per pixel (I, v); level: one byte per pixel, as the denoiser's.
+struct VFilterArgs {
+    int32_t n_pass[FOVPT_MAX_PASSES];   // iterations of the pixels whose last writer is pass p
+    int32_t iterations;                 // max over the passes present
+    int32_t demodulate;
+    float sl2, inv_n, inv_z;            // luminance_sigma^2, 1 / normal_sigma^2, 1 / depth_sigma^2 (fp32, host)
+};
+void fovpt_launch_vfilter(hipStream_t st, const FrameDev& fd, const VFilterArgs& a, const fovpt_float4* color, const fovpt_float4* variance,
+                          GBufferDev g, float4* J0, float4* J1, uint8_t* level, fovpt_float4* out_color, uint32_t* out_rgba);
 // fovpt_quality (quality.hip): k_quality_tile over the frame's 32 x 32 pixel tiles into `rows` -- one row of FOVPT_QUALITY_COLUMNS
 // 64-bit partial sums per block of fovpt_quality_rows(w, h), a block striding over the tiles --, then the one block of
 // k_quality_sum, which adds the columns (the maximum for max_err) and writes every byte of the record.  test and ref may be the

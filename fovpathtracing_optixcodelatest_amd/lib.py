@@ -31,6 +31,8 @@ EXPORTS = [
     "fovpt_warp_motion_defaults", "fovpt_warp_motion",
     "fovpt_focus_defaults", "fovpt_focus", "fovpt_focus_buffers", "fovpt_focus_state", "fovpt_focus_reset",
     "fovpt_lens_defaults", "fovpt_lens", "fovpt_lens_buffers",
+    "fovpt_variance_defaults", "fovpt_variance", "fovpt_variance_buffers", "fovpt_variance_reset",
+    "fovpt_variance_filter_defaults", "fovpt_variance_filter", "fovpt_variance_filter_buffers",
     "fovpt_quality_defaults", "fovpt_quality", "fovpt_quality_read", "fovpt_quality_host",
     "fovpt_quality_mse", "fovpt_quality_psnr", "fovpt_quality_ssim", "fovpt_quality_score",
     "fovpt_packet_describe", "fovpt_packet_encode", "fovpt_packet_submit", "fovpt_packet_wait", "fovpt_packet_decode",
@@ -221,6 +223,13 @@ def load():
     L.fovpt_lens_defaults.argtypes = [C.POINTER(abi.LensConfig)]
     L.fovpt_lens.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.LensConfig), C.POINTER(abi.WarpCamera), vp, vp, vp]
     L.fovpt_lens_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_variance_defaults.argtypes = [C.POINTER(abi.VarianceConfig)]
+    L.fovpt_variance.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.VarianceConfig), C.POINTER(abi.GBufferPtrs), vp, vp, vp]
+    L.fovpt_variance_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fovpt_variance_reset.argtypes = [vp]
+    L.fovpt_variance_filter_defaults.argtypes = [C.POINTER(abi.VarianceFilterConfig)]
+    L.fovpt_variance_filter.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.VarianceFilterConfig), C.POINTER(abi.GBufferPtrs), vp, vp, vp, vp]
+    L.fovpt_variance_filter_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_quality_defaults.argtypes = [C.POINTER(abi.QualityConfig)]
     L.fovpt_quality.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.QualityConfig), vp, vp, vp, vp]
     L.fovpt_quality_read.argtypes = [vp, C.POINTER(abi.QualitySums)]

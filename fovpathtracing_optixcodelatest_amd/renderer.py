@@ -628,6 +628,67 @@ class SampleRenderer:
         col, rgba = self.lens_buffers()
         return self._download_frame(col, 4), self._download_frame(rgba, 1)
 
+    # -- luminance moment history and variance-guided a-trous filter (include/fovpt.h, fovpt_variance / fovpt_variance_filter)
+    @staticmethod
+    def variance_defaults() -> abi.VarianceConfig:
+        d = abi.VarianceConfig()
+        lib.check(None, lib.load().fovpt_variance_defaults(C.byref(d)))
+        return d
+
+    def variance(self, cfg=None, gbuffer=None, in_sample=None, motion=None, out_variance=None):
+        """One step of the luminance moment history of the frame last rendered, and its variance image (rel, var, mean, n) per pixel:
+        the history is read where `motion` says the pixel was (device pointer of a float4 frame as temporal_motion() / post() write
+        it; None: at the pixel itself), a short history takes a spatial estimate instead.  gbuffer: an abi.GBufferPtrs of the
+        rendered frame (temporal_gbuffer() after a post() / temporal() step saves the trace), None: traced by the call.  in_sample:
+        device pointer of a float4 frame (None: the accum buffer); out_variance: device pointer, or None for the renderer's own image
+        (downloadVariance).  Enqueued on the renderer's stream, not synchronised."""
+        cfg = cfg if cfg is not None else self.variance_defaults()
+        self._check(self._L.fovpt_variance(self._ctx, C.byref(self.launchParams), C.byref(cfg), C.byref(gbuffer) if gbuffer is not None else None,
+                                           in_sample, motion, out_variance))
+
+    def variance_buffers(self):
+        """Device addresses of the renderer's own variance image and of the moment history the last variance() wrote."""
+        var, mom = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_variance_buffers(self._ctx, C.byref(var), C.byref(mom)))
+        return var.value, mom.value
+
+    def variance_reset(self):
+        """The next variance() has no history."""
+        self._check(self._L.fovpt_variance_reset(self._ctx))
+
+    def downloadVariance(self):
+        """((H, W, 4) float32 variance image (rel, var, mean, n), (H, W, 4) float32 moment history (M1, M2, n, z)) of the last
+        variance() into the renderer's own image."""
+        var, mom = self.variance_buffers()
+        return self._download_frame(var, 4), self._download_frame(mom, 4)
+
+    @staticmethod
+    def variance_filter_defaults() -> abi.VarianceFilterConfig:
+        d = abi.VarianceFilterConfig()
+        lib.check(None, lib.load().fovpt_variance_filter_defaults(C.byref(d)))
+        return d
+
+    def variance_filter(self, cfg=None, gbuffer=None, in_color=None, variance=None, out_color=None, out_rgba=None):
+        """Filters in_color (device pointer of a float4 frame; None: the accum buffer; typically post_buffers()[0]) with an a-trous
+        filter whose luminance edge-stop is scaled by `variance` (device pointer of a variance image; None: the renderer's own, from
+        the last variance()) and whose normal and plane-distance stops read the G-buffer (as variance()).  out_color / out_rgba:
+        device pointers, or None for the renderer's own buffers (downloadVarianceFiltered).  Enqueued, not synchronised."""
+        cfg = cfg if cfg is not None else self.variance_filter_defaults()
+        self._check(self._L.fovpt_variance_filter(self._ctx, C.byref(self.launchParams), C.byref(cfg), C.byref(gbuffer) if gbuffer is not None else None,
+                                                  in_color, variance, out_color, out_rgba))
+
+    def variance_filter_buffers(self):
+        """Device addresses of the renderer's own filtered outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_variance_filter_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def downloadVarianceFiltered(self):
+        """The outputs of the last variance_filter() into the renderer's own buffers: ((H, W, 4) float32 colour, rgba8 shaped like
+        downloadPixels())."""
+        col, rgba = self.variance_filter_buffers()
+        return self._download_frame(col, 4), self._download_frame(rgba, 1)
+
     # -- image quality of the rendered frame (include/fovpt.h, fovpt_quality): per-level error, SSIM and eccentricity profile
     @staticmethod
     def quality_defaults() -> abi.QualityConfig:

@@ -412,6 +412,69 @@ public:
         if (h_color) check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * n));
         if (h_pixels) check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * n));
     }
+    // ---- luminance moment history and variance-guided a-trous filter (include/fovpt.h, fovpt_variance / fovpt_variance_filter).
+    // variance(): one step of the moment history of the frame last rendered into the renderer's own variance image (or
+    // out_variance); gbuffer null: traced by the call; in_sample null: the accum buffer; motion (may be null): the motion vectors
+    // post() / temporalMotion() write.  varianceFilter(): filters in_color (null: the accum buffer; typically post()'s colour) by
+    // `variance` (null: the renderer's own image) into the renderer's own buffers (or the caller's).  Both are only enqueued;
+    // downloadVarianceFiltered() synchronises
+    static fovpt_variance_config varianceDefaults()
+    {
+        fovpt_variance_config vc;
+        if (fovpt_variance_defaults(&vc) != FOVPT_OK) throw std::runtime_error("fovpt_variance_defaults failed");
+        return vc;
+    }
+    void variance() { variance(varianceDefaults()); }
+    void variance(const fovpt_variance_config& vc, const fovpt_gbuffer_ptrs* gbuffer = nullptr, const fovpt_float4* in_sample = nullptr,
+                  const fovpt_float4* motion = nullptr, fovpt_float4* out_variance = nullptr)
+    {
+        check(fovpt_variance(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &vc, gbuffer, in_sample, motion, out_variance));
+    }
+    void varianceBuffers(fovpt_float4** variance, const fovpt_float4** moments) { check(fovpt_variance_buffers(ctx, variance, moments)); }
+    void varianceReset() { check(fovpt_variance_reset(ctx)); }
+    // the renderer's own variance image, (rel, var, mean, n) per pixel
+    void downloadVariance(fovpt_float4 h_variance[])
+    {
+        fovpt_float4* var = nullptr;
+        const fovpt_float4* moments = nullptr;
+        check(fovpt_variance_buffers(ctx, &var, &moments));
+        check(fovpt_download(ctx, var, h_variance, sizeof(fovpt_float4) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
+    static fovpt_variance_filter_config varianceFilterDefaults()
+    {
+        fovpt_variance_filter_config fc;
+        if (fovpt_variance_filter_defaults(&fc) != FOVPT_OK) throw std::runtime_error("fovpt_variance_filter_defaults failed");
+        return fc;
+    }
+    void varianceFilter() { varianceFilter(varianceFilterDefaults()); }
+    void varianceFilter(const fovpt_variance_filter_config& fc, const fovpt_gbuffer_ptrs* gbuffer = nullptr, const fovpt_float4* in_color = nullptr,
+                        const fovpt_float4* variance = nullptr, fovpt_float4* out_color = nullptr, uint32_t* out_rgba = nullptr)
+    {
+        check(fovpt_variance_filter(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &fc, gbuffer, in_color, variance, out_color, out_rgba));
+    }
+    void varianceFilterBuffers(fovpt_float4** color, uint32_t** rgba) { check(fovpt_variance_filter_buffers(ctx, color, rgba)); }
+    // behind post(pc, nullptr, motion): a moment step on the raw samples (the accum buffer) and the filter of the colour post() left
+    // in the renderer's own post buffers, both with that step's G-buffer (no trace of their own); motion: what post() wrote, or null
+    void variancePost(const fovpt_variance_config& vc, const fovpt_variance_filter_config& fc, const fovpt_float4* motion = nullptr)
+    {
+        fovpt_gbuffer_ptrs g;
+        check(fovpt_temporal_gbuffer(ctx, &g));
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_post_buffers(ctx, &color, &rgba));
+        variance(vc, &g, nullptr, motion);
+        varianceFilter(fc, &g, color);
+    }
+    // the filtered rgba8 pixels (may be null) and float4 colour (may be null), like downloadPixels
+    void downloadVarianceFiltered(uint32_t h_pixels[], fovpt_float4 h_color[] = nullptr)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_variance_filter_buffers(ctx, &color, &rgba));
+        const size_t n = (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y;
+        if (h_color) check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * n));
+        if (h_pixels) check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * n));
+    }
     // ---- image quality of the frame last rendered (include/fovpt.h, fovpt_quality): test_rgba (null: the frame buffer) against
     // ref_rgba, device rgba8 images of the frame's size -> per-class error sums, SSIM sums and the eccentricity profile; the scores
     // of a record are fovpt_quality_mse / _psnr / _ssim / _score.  measureQuality() measures into the renderer's own record and

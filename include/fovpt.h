@@ -1288,6 +1288,126 @@ int fovpt_lens(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_lens_c
                fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */);
 int fovpt_lens_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 
+/* ---- luminance moment history and variance-guided a-trous filter ------------------------------------------------------------------
+ * New with this library.  fovpt_denoise's colour edge-stop is a guess that knows nothing of how noisy a pixel is, and the temporal
+ * step carries no second moment.  This stage closes that gap the way SVGF does (Schied et al. 2017): fovpt_variance keeps temporally
+ * reprojected first and second luminance moments per pixel (a spatial estimate where the history is short) and writes a variance
+ * image; fovpt_variance_filter is an a-trous filter over a per-pixel G-buffer whose luminance edge-stop is scaled by that variance,
+ * which it pushes through its iterations.  Neither reads the frame's guides, so both run on fovpt_reconstruct's or fovpt_post's
+ * per-pixel output.  The loop they are meant for, tracing one G-buffer per frame:
+ *   render -> fovpt_post(RECONSTRUCT | TEMPORAL | MOTION, out_motion) -> fovpt_temporal_gbuffer
+ *          -> fovpt_variance(in_sample = accum_buffer, motion) -> fovpt_variance_filter(in_color = post's colour) -> focus / expose / lens
+ * Both calls work on the frame last issued with fovpt_render(ctx, lp): its size, its passes and its camera.  Both are enqueued on
+ * fovpt_stream(), not synchronised, ordered like fovpt_denoise, and all or nothing: every argument is checked before anything is
+ * enqueued or any state moves.  Both are defined operation by operation (tests/variance_ref.py): every fp32 +, -, * and / one unfused
+ * operation, beyond those only floor, min, max and comparisons -- no transcendental function, no square root.  w, h the frame size,
+ * (x, y) a pixel, idx = y * w + x; lum(c) = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; sq3(a) = (a.x * a.x + a.y * a.y) + a.z * a.z,
+ * dot likewise; edge(d) = max(0, 1 - d)^2; a pixel's fill is that of its last writer among the frame's passes, 1 where no pass writes.
+ *   fovpt_variance           the moment step (one kernel).  gbuffer NULL = the rendered frame's G-buffer is traced by the call, as
+ *                            fovpt_warp does (into fovpt_gbuffer's buffers; needs the scene); of a caller's G-buffer only position and
+ *                            normal are read, never prim.  in_sample NULL = accum_buffer; motion NULL = the history is read at the
+ *                            pixel itself; out_variance NULL = the context's own image.  The context owns two moment histories, used in
+ *                            turn like the temporal step's, and the variance image, float4 per pixel each (allocated on first use,
+ *                            reallocated by fovpt_resize, freed by fovpt_destroy; a context that never calls the stage pays nothing).
+ *                            M: the rows of inverse(U V W) of the rendered camera as fovpt_lens step 5 takes them (binary64, each
+ *                            entry rounded to fp32).
+ *                              1  l = lum(in_sample[idx]), l2 = l * l
+ *                              2  the pixel is a miss iff gbuffer.position[idx].w < 0.  A hit: v = X - eye,
+ *                                 z_p = (M[2].x * v.x + M[2].y * v.y) + M[2].z * v.z; a miss: z_p = -1
+ *                              3  mv = motion ? motion[idx] : (0, 0, z_p, 1); no history if mv.w == 0; px = (float)x + mv.x, py
+ *                                 likewise, zr = mv.z; no history unless px >= -1 && px < w && py >= -1 && py < h (a NaN fails)
+ *                              4  x0 = floor(px), fx = px - x0, likewise in y; the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *                                 (x0 + 1, y0 + 1) with weights (1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy.  A tap q
+ *                                 inside the frame is kept iff the previous record's (z_q < 0) equals the pixel's miss class and, for
+ *                                 hits, fabsf(z_q - zr) <= depth_tolerance * zr.  sw = sum of the kept weights in tap order; if
+ *                                 sw >= 1 / 64: m1 = (sum M1_q * w) / sw, m2 and n_h likewise; otherwise n_h = 0.  The first step,
+ *                                 and the first after fovpt_variance_reset, fovpt_resize or fovpt_set_scene, has no history anywhere
+ *                              5  n = min(n_h + 1, (float)history_cap).  n == 1: M1 = l, M2 = l2 bit for bit; otherwise
+ *                                 M1 = m1 + (1 / n) * (l - m1), M2 = m2 + (1 / n) * (l2 - m2).  The new record is (M1, M2, n, z_p)
+ *                              6  n >= (float)spatial_below: mean = M1, var = max(0, M2 - M1 * M1).  Otherwise the spatial estimate
+ *                                 over the current frame: taps q = clamp(p + fill * (i, j)), i, j in -R .. R (rows outer),
+ *                                 R = spatial_radius; the centre has weight 1, another tap weight 1 iff its class equals the pixel's
+ *                                 and, for hits, sq3(N_q - N_p) <= normal_tolerance and fabsf(dot(N_p, X_q - X_p)) <=
+ *                                 depth_tolerance * t_p, else 0.  s0 = sum w, s1 = sum w * l_q, s2 = sum w * (l_q * l_q);
+ *                                 mean = s1 / s0, var = max(0, s2 / s0 - mean * mean).  (Stepping by the fill: a block-filled pixel
+ *                                 never counts its own copies)
+ *                              7  out_variance[idx] = (rel, var, mean, n), rel = var / (mean * mean + 1e-8f): the squared coefficient
+ *                                 of variation, the same for a colour and for that colour divided by its albedo
+ *                            FOVPT_E_INVALID: null ctx / lp / vc; a value out of range (NaN included); non-zero reserved fields; a
+ *                            G-buffer of another size or with a null position or normal; an output that is an input or a history
+ *                            (base addresses are compared); a rendered camera whose [U V W] is singular; width * height >= 2^31; a
+ *                            frame rendered with world > 1.  FOVPT_E_NO_FRAME, FOVPT_E_NO_SCENE: as fovpt_reconstruct (the scene only
+ *                            where the call traces).  Outputs for non-finite colours are unspecified.  fovpt_set_probe keeps the
+ *                            history: a caller who changes the lighting resets.
+ *   fovpt_variance_defaults  host only, no context.  CONVENTIONS, NOT MEASUREMENTS: history_cap 16, spatial_below 4 and
+ *                            spatial_radius 3 (a 7 x 7 window) are SVGF's; the tolerances 0.02 and 0.1 are fovpt_temporal's.
+ *   fovpt_variance_buffers   the context's own variance image and the moment history the last step wrote (allocated for the last
+ *                            frame if not yet).
+ *   fovpt_variance_reset     the next step has no history (takes effect in call order).
+ *   fovpt_variance_filter    gbuffer NULL = traced by the call; position, normal and (with demodulate) albedo of a caller's are
+ *                            read.  in_color NULL = accum_buffer; variance NULL = the context's own image as the last fovpt_variance
+ *                            into it left it; out_color / out_rgba NULL = the context's own (fovpt_variance_filter_buffers).
+ *                              prep   the level byte is fovpt_denoise's: iterations n by the fill of the last writer (0 where no pass
+ *                                     writes), and log2(fill).  D = demodulate ? demod(albedo[idx]) : 1, demod the denoiser's;
+ *                                     I = C / D; v0 = variance[idx].x * (lum(I) * lum(I)); J = (I, v0).  A pixel with n = 0 gets
+ *                                     out_color = (C.rgb, 1) and its tone map here
+ *                              iteration it = 0 .. max n - 1, for the pixels with it < n (the others keep J); s = fill * 2^it:
+ *                                1  g = sum G_ij * J.w(clamp(p + fill * (i, j))), i, j in -1 .. 1 (rows outer),
+ *                                   G = [1/16 1/8 1/16; 1/8 1/4 1/8; 1/16 1/8 1/16]
+ *                                2  kl = 1 / ((luminance_sigma * luminance_sigma) * g + 1e-6f) (the scale is the same in every
+ *                                   iteration: the variance shrinks instead)
+ *                                3  25 taps q = clamp(p + s * (dx, dy)), dy outer, B3 weights H = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *                                   d = lum(I_q) - lum(I_p), wl = edge((d * d) * kl); a class mismatch: wn = wz = 0; both misses: 1;
+ *                                   both hits: wn = edge(sq3(N_q - N_p) * inv_n), wz = edge(((dz * dz) * inv_z) / (t_p * t_p)),
+ *                                   dz = dot(N_p, X_q - X_p) (fovpt_reconstruct's expression), inv_n = 1 / normal_sigma^2 and
+ *                                   inv_z = 1 / depth_sigma^2 in fp32 on the host.  wt = (((H_dx * H_dy) * wl) * wn) * wz;
+ *                                   sw += wt, acc += I_q * wt, sv += (wt * wt) * v_q
+ *                                4  I' = acc / sw, v' = sv / (sw * sw) (the centre tap keeps sw >= 9 / 64)
+ *                              output of a pixel with n >= 1: I * D with alpha 1, rgba8 = make_color(reinhard(out * 16, 1))
+ *                            Errors as fovpt_variance's, with: an iteration count outside 0 .. FOVPT_DENOISE_MAX_ITERATIONS, a sigma
+ *                            outside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX], demodulate neither 0 nor 1, a null albedo with demodulate,
+ *                            an output equal to an input or to the other output (the kernels gather), and FOVPT_E_NO_FRAME when
+ *                            variance is NULL and no fovpt_variance has written the context's image at this frame size.
+ *   fovpt_variance_filter_defaults   host only.  CONVENTIONS, NOT MEASUREMENTS: iterations 0 / 2 / 4 / 4, luminance_sigma 4 (SVGF's),
+ *                            normal_sigma 0.5 and depth_sigma 0.05 (fovpt_reconstruct's), demodulate 1.
+ * What is SVGF here: the moment history with its length, the spatial fallback, the variance-scaled luminance stop, the 3 x 3 prefilter
+ * and the variance carried through the iterations.  What is not: the colour history stays fovpt_temporal's (with its own length), and
+ * the weights are this library's (squared-linear edge, plane distance), not exponentials.
+ * Out of scope.  A FOVPT_POST_* bit for this stage; a neighbourhood clamp of the colour history; variance of reflections and shadows
+ * under motion; resetting the moments when a pixel changes foveation level (the cap bounds it); world > 1.
+ * On an MI355X at 1920 x 1080, on fovpt_post's G-buffer, a call takes: fovpt_variance 0.258 ms as a first step (the window everywhere)
+ * and 0.034 ms in steady state, fovpt_variance_filter at its defaults 0.587 ms, measured beside fovpt_denoise at its defaults (0.341 ms:
+ * ratios 0.76 / 0.10 / 1.72) and one fovpt_render (0.687 ms).  On the 384 x 216 quality path the filter behind fovpt_post takes the
+ * periphery's RMSE from 0.0451 to 0.0386 and the middle ring's from 0.0433 to 0.0268; luminance_sigma 1 / 2 / 8 give 0.0390 / 0.0386 /
+ * 0.0387 and 0.0317 / 0.0281 / 0.0264.                                                                       */
+typedef struct fovpt_variance_config {            /* 32 bytes */
+    int32_t history_cap;           /* 1 .. FOVPT_TEMPORAL_MAX_HISTORY; default 16                                          */
+    int32_t spatial_below;         /* a history shorter than this takes the spatial estimate: 0 .. history_cap + 1; 4      */
+    int32_t spatial_radius;        /* 1 .. 3; default 3                                                                    */
+    float depth_tolerance;         /* 0 .. 1; default 0.02                                                                 */
+    float normal_tolerance;        /* 0 .. 4; default 0.1                                                                  */
+    int32_t _reserved[3];
+} fovpt_variance_config;
+typedef struct fovpt_variance_filter_config {     /* 48 bytes */
+    int32_t iterations_fovea, iterations_middle, iterations_periphery, iterations_uniform;   /* 0 .. FOVPT_DENOISE_MAX_ITERATIONS; 0 / 2 / 4 / 4 */
+    float luminance_sigma;         /* FOVPT_SIGMA_MIN .. MAX; default 4    */
+    float normal_sigma;            /* default 0.5                          */
+    float depth_sigma;             /* default 0.05                         */
+    int32_t demodulate;            /* 0 / 1; default 1                     */
+    int32_t _reserved[4];
+} fovpt_variance_filter_config;
+int fovpt_variance_defaults(fovpt_variance_config* out);          /* host only, no context */
+int fovpt_variance(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_variance_config* vc,
+                   const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, const fovpt_float4* in_sample /* NULL: accum_buffer */,
+                   const fovpt_float4* motion /* NULL: history read at the pixel itself */, fovpt_float4* out_variance /* NULL: the context's own */);
+int fovpt_variance_buffers(fovpt_ctx* ctx, fovpt_float4** variance, const fovpt_float4** moments);
+int fovpt_variance_reset(fovpt_ctx* ctx);
+int fovpt_variance_filter_defaults(fovpt_variance_filter_config* out);   /* host only, no context */
+int fovpt_variance_filter(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_variance_filter_config* fc,
+                          const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, const fovpt_float4* in_color /* NULL: accum_buffer */,
+                          const fovpt_float4* variance /* NULL: the context's own */, fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */);
+int fovpt_variance_filter_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+
 /* ---- image quality of a foveated frame: per-level error, SSIM and eccentricity profile -------------------------------------------
  * New with this library.  Choosing radii, spp, denoiser iterations, history caps or BC1 for a level asks one question: how good is
  * the frame, and where in the visual field does its error sit?  fovpt_quality answers it on the device, in stream order, with no
@@ -1887,7 +2007,12 @@ static_assert(sizeof(fovpt_focus_config) == 64 && offsetof(fovpt_focus_config, s
 static_assert(sizeof(struct fovpt_focus_state) == 32 && offsetof(struct fovpt_focus_state, count) == 16, "focus state ABI");
 static_assert(sizeof(fovpt_lens_config) == 128 && offsetof(fovpt_lens_config, k) == 32 && offsetof(fovpt_lens_config, clip_r2) == 60 &&
               offsetof(fovpt_lens_config, border) == 80 && offsetof(fovpt_lens_config, _reserved) == 96, "lens config ABI");
-static_assert(sizeof(fovpt_quality_config) == 32 && offsetof(fovpt_quality_config, _reserved) == 8, "quality config ABI");
+static_assert(sizeof(fovpt_variance_config) == 32 && offsetof(fovpt_variance_config, depth_tolerance) == 12 &&
+              offsetof(fovpt_variance_config, _reserved) == 20, "variance config ABI");
+static_assert(sizeof(fovpt_variance_filter_config) == 48 && offsetof(fovpt_variance_filter_config, luminance_sigma) == 16 &&
+              offsetof(fovpt_variance_filter_config, demodulate) == 28 && offsetof(fovpt_variance_filter_config, _reserved) == 32,
+              "variance filter config ABI");
+static_assert(sizeof(fovpt_quality_config) == 32 &&offsetof(fovpt_quality_config, _reserved) == 8, "quality config ABI");
 static_assert(sizeof(fovpt_quality_sums) == 1344 && offsetof(fovpt_quality_sums, max_err) == 200 && offsetof(fovpt_quality_sums, windows) == 224 &&
               offsetof(fovpt_quality_sums, ring_pixels) == 304 && offsetof(fovpt_quality_sums, width) == 1328, "quality sums ABI");
 static_assert(sizeof(fovpt_packet_pass) == 32 && offsetof(fovpt_packet_pass, texels) == 24, "packet pass ABI");

@@ -1,0 +1,578 @@
+"""fovpt_variance and fovpt_variance_filter on the GPU against tests/variance_ref.py, bit for bit: sequences of moment steps with no
+motion, with uploaded sub-pixel motion (w = 0, landings outside the frame and NaNs among it) and with the motion vectors of
+fovpt_temporal_motion over a camera slide, a cap reached within the sequence and both values of the spatial branch; the filter with
+every iteration mix, with and without demodulation, a caller's G-buffer and a traced one, the context's own buffers and the
+caller's; at frame sizes from 1 x 1 up, foveated and uniform.  Then the lifecycle, ordering with frames in flight, every rejection
+and the C++ drop-in.  The frame is a trivial render of the box scene; colour, variance and motion are synthetic where the case
+needs them.  The conditions that keep a case from being vacuous are asserted on the restatement's output."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import variance_ref as vr
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+
+from common import cfg_foveated, cfg_uniform, make_gpu
+from postprocess_common import BOX_CAMERA, bits, box_model
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
+SIZES = [(1, 1), (2, 1), (1, 3), (5, 4), (33, 17), (193, 109)]
+PROBE = scenes.ambient_probe(64, 32, 2.5)
+FOVEATED = ("foveated", lambda: cfg_foveated(10, 30, (1, 1, 2), max_depth=2))     # fovea 22 px, middle ring 64 px: all three fills at 193 x 109
+UNIFORM = ("uniform", lambda: cfg_uniform(1, max_depth=2))
+MOMENT_CONFIGS = (dict(), dict(history_cap=2, spatial_below=2, spatial_radius=1, depth_tolerance=0.1),
+                  dict(history_cap=3, spatial_below=0, spatial_radius=2, normal_tolerance=0.0))
+ITERATION_MIXES = ((0, 2, 4, 4), (1, 3, 5, 5), (5, 0, 1, 2), (2, 2, 0, 1), (0, 0, 0, 0), (3, 1, 2, 3))       # fovea, middle, periphery, uniform
+
+
+def _box(size, cfg=None):
+    return make_gpu(box_model(), PROBE, BOX_CAMERA, size, cfg if cfg is not None else UNIFORM[1]())
+
+
+def vcfg(**d):
+    c = renderer.SampleRenderer.variance_defaults()
+    for k, v in d.items():
+        setattr(c, k, v)
+    return c
+
+
+def fcfg(**d):
+    c = renderer.SampleRenderer.variance_filter_defaults()
+    for k, v in d.items():
+        setattr(c, k, v)
+    return c
+
+
+def camera_of(r):
+    cam = r.launchParams.camera
+    vec = lambda v: (float(v.x), float(v.y), float(v.z))
+    return dict(eye=vec(cam.eye), U=vec(cam.U), V=vec(cam.V), W=vec(cam.W))
+
+
+def frame_fills(r, cfg):
+    f = r.launchParams.frame
+    return vr.fills(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)
+
+
+def upload(a):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+def device_frame(size, channels=4, fill=0x5a):
+    import torch
+    t = torch.full((size[1], size[0], 4 * channels), fill, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    return t
+
+
+def host(t, kind="color"):
+    a = t.cpu().numpy()
+    if kind == "color":
+        return a.view(np.float32).reshape(a.shape[0], a.shape[1], 4)
+    return a.view(np.uint32).reshape(a.shape[0], a.shape[1])
+
+
+def synthetic(size, seed, lo=0.0, hi=1.5):
+    w, h = size
+    c = np.random.default_rng(seed).uniform(lo, hi, (h, w, 4)).astype(np.float32)
+    c[..., 3] = 0.5
+    return c
+
+
+def random_motion(size, z, seed):
+    """Sub-pixel motion whose reprojected depth is the pixel's own z (a fifth: half as far again), with w = 0, landings outside the
+    frame and NaNs among it."""
+    w, h = size
+    rng = np.random.default_rng(seed)
+    mv = np.zeros((h, w, 4), np.float32)
+    mv[..., :2] = rng.uniform(-1.4, 1.4, (h, w, 2))
+    mv[..., 2] = np.where(z < 0, -1.0, z * rng.choice([1.0, 1.0, 1.0, 1.0, 1.5], (h, w)))
+    mv[..., 3] = rng.choice([1.0, 1.0, 1.0, 1.0, 1.0, 0.0, 2.0], (h, w))
+    kind = rng.integers(0, 40, (h, w))
+    mv[..., 0][kind == 0] = np.nan
+    mv[..., 1][kind == 1] = np.nan
+    mv[..., 2][kind == 2] = np.nan
+    mv[..., 0][kind == 3] = 3.0 * w
+    mv[..., 1][kind == 4] = -2.0 * h
+    return mv
+
+
+class Moments:
+    """The device's moment history beside the restatement's."""
+
+    def __init__(self, r, cfg):
+        self.r, self.cfg, self.prev = r, cfg, None
+        self.fill, _ = frame_fills(r, cfg)
+
+    def step(self, d, gbuffer=None, sample=None, motion=None, own=True, label=None):
+        """One fovpt_variance (gbuffer: abi.GBufferPtrs or None; sample, motion: host arrays or None) compared with the restatement
+        -> (the restatement's history, its variance image, its record)."""
+        r = self.r
+        f = r.launchParams.frame
+        size = (f.size.x, f.size.y)
+        keep = [upload(a) if a is not None else None for a in (sample, motion)]
+        out = None if own else device_frame(size)
+        r.variance(vcfg(**d), gbuffer, keep[0].data_ptr() if sample is not None else None, keep[1].data_ptr() if motion is not None else None,
+                   out.data_ptr() if out is not None else None)
+        r.synchronize()
+        var_ptr, mom_ptr = r.variance_buffers()
+        got_hist = r._download_frame(mom_ptr, 4)
+        got_var = host(out) if out is not None else r._download_frame(var_ptr, 4)
+        gb = r.downloadGBuffer(gbuffer if gbuffer is not None else r.gbuffer())       # (the same camera: what the call traced)
+        rec = {}
+        full = dict(vr.MOMENT_DEFAULTS, **d)
+        hist, var = vr.moments(self.prev, sample if sample is not None else r.downloadAccum(), gb, camera_of(r), self.fill, motion, full, rec)
+        assert np.array_equal(bits(got_hist), bits(hist)), label
+        assert np.array_equal(bits(got_var), bits(var)), label
+        self.prev = hist
+        return hist, var, rec
+
+
+# ---- 1. the moment step, bit for bit ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fov", (FOVEATED, UNIFORM), ids=lambda f: f[0])
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+def test_moment_sequences_bit_for_bit(size, fov):
+    cfg = fov[1]()
+    r = _box(size, cfg)
+    seen = dict(spatial=0, temporal=0, depth=0, cls=0, capped=0)
+    for i, d in enumerate(MOMENT_CONFIGS):
+        r.variance_reset()
+        m = Moments(r, cfg)
+        for k in range(4):
+            r.launchParams.frame.subframe_index = 4 * i + k
+            r.render()
+            g = r.gbuffer() if (k + i) % 2 else None                        # a caller's G-buffer and a traced one in turn
+            motion = None
+            if k >= 2:
+                motion = random_motion(size, m.prev[..., 3], 7 * k + i)            # (a static camera: the last step's depths are this one's)
+            sample = synthetic(size, 11 * k + i, 0.1, 2.0) if k == 3 else None      # the accum buffer, and an uploaded sample
+            hist, var, rec = m.step(d, g, sample, motion, own=(k != 1), label=(size, fov[0], i, k))
+            assert (hist[..., 2] == 1).all() if k == 0 else True
+            seen["spatial"] += int(rec["spatial"].sum()); seen["temporal"] += int((~rec["spatial"]).sum())
+            seen["depth"] += int(rec["reject_depth"].sum()); seen["cls"] += int(rec["reject_class"].sum())
+            seen["capped"] += int((hist[..., 2] == dict(vr.MOMENT_DEFAULTS, **d)["history_cap"]).sum())
+    if size == SIZES[-1]:
+        assert all(v > 0 for v in seen.values()), seen                       # both branches, both rejections, a cap reached
+        if fov is FOVEATED:
+            assert set(np.unique(m.fill)) == {1, 2, 4}
+    r.close()
+
+
+def test_a_camera_slide_with_real_motion_vectors():
+    """render -> fovpt_temporal_motion(out_motion) -> fovpt_temporal_gbuffer -> fovpt_variance(motion): the loop the stage is for."""
+    size = SIZES[-1]
+    cfg = FOVEATED[1]()
+    r = _box(size, cfg)
+    m = Moments(r, cfg)
+    mv_dev = device_frame(size)
+    e = np.array(BOX_CAMERA["eye"], np.float64)
+    for k in range(4):
+        eye = tuple(e + np.array([0.35 * k, 0.0, -0.1 * k]))
+        r.setCamera(renderer.Camera(eye, BOX_CAMERA["lookat"], BOX_CAMERA["up"], BOX_CAMERA["fovy"], size[0] / float(size[1])))
+        r.launchParams.frame.subframe_index = k
+        r.render()
+        r.temporal_motion(None, None, None, None, mv_dev.data_ptr())
+        r.synchronize()
+        motion = host(mv_dev).copy()
+        hist, var, rec = m.step(dict(spatial_below=2), r.temporal_gbuffer(), None, motion, label=("slide", k))
+        n = hist[..., 2]
+        if k == 0:
+            assert (n == 1).all() and rec["spatial"].all()
+        if k >= 1:
+            assert (motion[..., 3] == 1).sum() > 1000 and np.abs(motion[..., 0]).max() > 1.0
+            assert (n == 1).sum() > 0 and (n >= 2).sum() > 1000              # disoccluded pixels, and pixels with a history
+            assert rec["spatial"].any() and not rec["spatial"].all()
+            assert rec["reject_depth"].sum() > 0 and rec["reject_class"].sum() > 0
+    assert set(np.unique(m.fill)) == {1, 2, 4}
+    r.close()
+
+
+# ---- 2. the filter, bit for bit --------------------------------------------------------------------------------------------------------
+def run_filter(oracle, r, cfg, d, color, variance, gbuffer, own, label, record=None):
+    f = r.launchParams.frame
+    size = (f.size.x, f.size.y)
+    dc, dv = upload(color), upload(variance)
+    if own:
+        r.variance_filter(fcfg(**d), gbuffer, dc.data_ptr(), dv.data_ptr())
+        got_c, got_p = r.downloadVarianceFiltered()
+    else:
+        oc, op = device_frame(size), device_frame(size, 1)
+        r.variance_filter(fcfg(**d), gbuffer, dc.data_ptr(), dv.data_ptr(), oc.data_ptr(), op.data_ptr())
+        r.synchronize()
+        got_c, got_p = host(oc), host(op, "rgba")
+    gb = r.downloadGBuffer(gbuffer if gbuffer is not None else r.gbuffer())
+    fill, pas = frame_fills(r, cfg)
+    full = dict(vr.FILTER_DEFAULTS, **d)
+    n = vr.iteration_map(fill, pas, full, cfg.uniform)
+    want, _ = vr.vfilter(color, variance, gb, fill, n, full, record)
+    assert np.array_equal(bits(got_c), bits(want)), label
+    assert np.array_equal(got_p, oracle.make_color(want[..., :3].reshape(-1, 3)).reshape(got_p.shape)), label
+    return want, n
+
+
+@pytest.mark.parametrize("fov", (FOVEATED, UNIFORM), ids=lambda f: f[0])
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+def test_filter_bit_for_bit(oracle, size, fov):
+    cfg = fov[1]()
+    r = _box(size, cfg)
+    r.render()
+    color = synthetic(size, size[0] + 1, 0.05, 1.5)
+    variance = synthetic(size, size[0] + 2, 0.0, 0.6)
+    variance[..., 0][np.random.default_rng(3).integers(0, 4, variance.shape[:2]) == 0] = 0.0      # some pixels with no variance at all
+    names = ("iterations_fovea", "iterations_middle", "iterations_periphery", "iterations_uniform")
+    wl_zero = wl_part = 0
+    for i, mix in enumerate(ITERATION_MIXES):
+        d = dict(zip(names, mix), demodulate=i % 2)
+        if i == 3:
+            d.update(luminance_sigma=1.5, normal_sigma=0.2, depth_sigma=0.01)
+        rec = [] if i == 0 else None
+        want, n = run_filter(oracle, r, cfg, d, color, variance, r.gbuffer() if i % 3 == 0 else None, own=(i % 2 == 0), label=(size, fov[0], mix), record=rec)
+        assert (want[..., 3] == 1).all() and np.array_equal(bits(want[..., :3][n == 0]), bits(color[..., :3][n == 0]))
+        if rec:
+            wl_zero += sum(int(((wl == 0) & act).sum()) for _, act, wl in rec)
+            wl_part += sum(int(((wl > 0) & (wl < 1) & act).sum()) for _, act, wl in rec)
+    if size == SIZES[-1]:
+        assert wl_zero > 0 and wl_part > 0
+    r.close()
+
+
+def test_the_stages_together_on_the_accum_buffer(oracle):
+    """in_color None and variance None: the accum buffer filtered by the context's own image, as the last fovpt_variance left it."""
+    size = (96, 64)
+    cfg = FOVEATED[1]()
+    r = _box(size, cfg)
+    with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
+        r.variance()
+    assert e.value.code == E_NO_FRAME
+    with pytest.raises(lib.FovptError) as e:
+        r.variance_filter_buffers()
+    assert e.value.code == E_NO_FRAME
+    r.render()
+    with pytest.raises(lib.FovptError) as e:                 # no variance image yet
+        r.variance_filter()
+    assert e.value.code == E_NO_FRAME
+    m = Moments(r, cfg)
+    m.step({}, None, None, None, own=False)                  # into a caller's image: the context's own is still unwritten
+    with pytest.raises(lib.FovptError) as e:
+        r.variance_filter()
+    assert e.value.code == E_NO_FRAME
+    _, var, _ = m.step({})
+    r.variance_filter()
+    got_c, got_p = r.downloadVarianceFiltered()
+    fill, pas = frame_fills(r, cfg)
+    n = vr.iteration_map(fill, pas, None, cfg.uniform)
+    want, _ = vr.vfilter(r.downloadAccum(), var, r.downloadGBuffer(r.gbuffer()), fill, n)
+    assert np.array_equal(bits(got_c), bits(want))
+    assert np.array_equal(got_p, oracle.make_color(want[..., :3].reshape(-1, 3)).reshape(got_p.shape))
+    assert (n > 0).any() and (n == 0).any() and len(np.unique(got_p)) > 20
+    r.close()
+
+
+# ---- 3. the lifecycle ------------------------------------------------------------------------------------------------------------------
+def _scene_again(r):
+    md, n, td, nt, keep = renderer.pack_model(r.model)
+    trav = C.c_uint64()
+    r._check(r._L.fovpt_set_scene(r._ctx, C.cast(md, C.c_void_p), n, C.cast(td, C.c_void_p), nt, C.byref(trav)))
+    r.launchParams.traversable = trav.value
+
+
+def test_reset_resize_and_set_scene_start_a_new_history():
+    small, large = (96, 64), (200, 120)
+    cfg = UNIFORM[1]()
+    r = _box(small, cfg)
+    r.render()
+    m = Moments(r, cfg)
+    m.step({})
+    hist, _, _ = m.step({})
+    assert (hist[..., 2] == 2).all()
+    r.variance_reset()
+    m.prev = None
+    hist, _, _ = m.step({})
+    assert (hist[..., 2] == 1).all()
+    hist, _, _ = m.step({})
+    assert (hist[..., 2] == 2).all()
+    _scene_again(r)
+    r.render()
+    m.prev = None
+    hist, _, _ = m.step({})
+    assert (hist[..., 2] == 1).all()
+    before = r.variance_buffers() + r.variance_filter_buffers()
+    r.resize(large)
+    r.setCamera(r.lastSetCamera)
+    with pytest.raises(lib.FovptError) as e:                 # nothing rendered at this size yet
+        r.variance()
+    assert e.value.code == E_NO_FRAME
+    r.render()
+    with pytest.raises(lib.FovptError) as e:                 # the context's image is of another size
+        r.variance_filter()
+    assert e.value.code == E_NO_FRAME
+    m = Moments(r, cfg)
+    hist, var, _ = m.step({})
+    assert hist.shape == (large[1], large[0], 4) and (hist[..., 2] == 1).all()
+    r.variance_filter()
+    got_c, _ = r.downloadVarianceFiltered()
+    assert got_c.shape == (large[1], large[0], 4) and all(before) and all(r.variance_buffers() + r.variance_filter_buffers())
+    r.close()
+
+
+def test_the_other_stages_buffers_stay_as_they_are():
+    size = (96, 64)
+    cfg = FOVEATED[1]()
+    cfg.write_guides = 1
+    r = _box(size, cfg)
+    r.render()
+    r.denoise()
+    r.temporal()
+    r.synchronize()
+    g = r.temporal_gbuffer()
+
+    def others():
+        col, rgba, hist = r.temporal_buffers()
+        out = [r._download_frame(p, 4).tobytes() for p in (col, hist, r.denoise_buffers()[0])]
+        out += [r._download_frame(p, 1).tobytes() for p in (rgba, r.denoise_buffers()[1])]
+        tg = r.downloadGBuffer(g)
+        return out + [tg[k].tobytes() for k in ("prim", "position", "normal", "albedo")] + [r.downloadAccum().tobytes(), r.downloadPixels().tobytes()]
+
+    before = others()
+    r.variance()
+    r.variance(None, g)
+    r.variance_filter()
+    r.variance_filter(None, g)
+    r.synchronize()
+    assert others() == before
+    assert len(np.unique(r.downloadVarianceFiltered()[1])) > 20
+    r.close()
+
+
+def test_the_stage_is_ordered_with_frames_in_flight():
+    """render_async, variance, filter, render_async, ... with no synchronisation in between: what the same sequence gives with a
+    synchronise after every call."""
+    import torch
+    size = (384, 216)
+    cfg = cfg_foveated(20, 60, (2, 4, 8))
+    cfg.frames_in_flight = 2
+    r = _box(size, cfg)
+    views = [((190, 108), 0), ((300, 40), 1), ((80, 60), 2)]
+    outs = [[(device_frame(size), device_frame(size), device_frame(size, 1)) for _ in views] for _ in range(2)]
+    for sync, out in zip((True, False), outs):
+        for g, k in views:                                   # the accum buffer's leftovers where no pass writes, as all views leave them
+            r.launchParams.frame.c.x, r.launchParams.frame.c.y = g
+            r.launchParams.frame.subframe_index = k
+            r.render()
+        r.variance_reset()
+        for (g, k), (ov, oc, op) in zip(views, out):
+            r.launchParams.frame.c.x, r.launchParams.frame.c.y = g
+            r.launchParams.frame.subframe_index = k
+            for call in (r.render_async, lambda: r.variance(None, None, None, None, ov.data_ptr()),
+                         lambda: r.variance_filter(None, None, None, ov.data_ptr(), oc.data_ptr(), op.data_ptr())):
+                call()
+                if sync:
+                    r.synchronize()
+        r.synchronize()
+    for want, got in zip(*outs):
+        for x, y in zip(want, got):
+            assert torch.equal(x, y)
+    a, b = host(outs[0][0][2], "rgba"), host(outs[0][2][2], "rgba")
+    assert (a != b).mean() > 0.1                             # (the frames differ: the comparison is not of copies)
+    n = host(outs[0][2][0])[..., 3]
+    assert (n == 3).any()                                    # (the third step has a history of three)
+    r.close()
+
+
+# ---- 4. rejections ---------------------------------------------------------------------------------------------------------------------
+def test_rejections_leave_everything_unchanged():
+    size = (96, 64)
+    r = _box(size)
+    L = lib.load()
+    r.render()
+    ov, oc, op = device_frame(size), device_frame(size), device_frame(size, 1)
+    mv = upload(np.tile(np.float32([0.25, -0.25, 5.0, 1.0]), (size[1], size[0], 1)))
+    g = r.gbuffer()
+    r.variance(None, g, None, mv.data_ptr(), ov.data_ptr())
+    r.variance()
+    r.variance_filter(None, g, None, None, oc.data_ptr(), op.data_ptr())
+    r.variance_filter()
+    r.synchronize()
+    own_var, own_mom = r.variance_buffers()
+    own_c, own_p = r.variance_filter_buffers()
+
+    def everything():
+        var, mom = r.variance_buffers()                                    # (mom: a rejected call does not turn the histories)
+        own = r.downloadVarianceFiltered()
+        return (mom, r._download_frame(var, 4).tobytes(), r._download_frame(mom, 4).tobytes(), own[0].tobytes(), own[1].tobytes()) + \
+            tuple(t.cpu().numpy().tobytes() for t in (ov, oc, op))
+
+    before = everything()
+    f = r.launchParams.frame
+
+    def refuse_v(code, label, **kw):
+        args = dict(cfg=None, gbuffer=g, in_sample=None, motion=mv.data_ptr(), out_variance=ov.data_ptr())
+        args.update(kw)
+        with pytest.raises(lib.FovptError) as e:
+            r.variance(**args)
+        assert e.value.code == code, label
+        assert everything() == before, label
+
+    def refuse_f(code, label, **kw):
+        args = dict(cfg=None, gbuffer=g, in_color=None, variance=None, out_color=oc.data_ptr(), out_rgba=op.data_ptr())
+        args.update(kw)
+        with pytest.raises(lib.FovptError) as e:
+            r.variance_filter(**args)
+        assert e.value.code == code, label
+        assert everything() == before, label
+
+    nan = float("nan")
+    for name, values in (("history_cap", (0, -1, 65)), ("spatial_below", (-1, 18)), ("spatial_radius", (0, 4, -1)),
+                         ("depth_tolerance", (-0.1, 1.5, nan)), ("normal_tolerance", (-0.1, 4.5, nan))):
+        for v in values:
+            refuse_v(E_INVALID, (name, v), cfg=vcfg(**{name: v}))
+    refuse_v(E_INVALID, "spatial_below above cap + 1", cfg=vcfg(history_cap=2, spatial_below=4))
+    for i in range(3):
+        c = vcfg()
+        c._reserved[i] = 1
+        refuse_v(E_INVALID, ("_reserved", i), cfg=c)
+    for name in ("iterations_fovea", "iterations_middle", "iterations_periphery", "iterations_uniform"):
+        for v in (-1, 6):
+            refuse_f(E_INVALID, (name, v), cfg=fcfg(**{name: v}))
+    for name in ("luminance_sigma", "normal_sigma", "depth_sigma"):
+        for v in (0.0, -1.0, 1e-7, 1e7, nan):
+            refuse_f(E_INVALID, (name, v), cfg=fcfg(**{name: v}))
+    for v in (-1, 2):
+        refuse_f(E_INVALID, ("demodulate", v), cfg=fcfg(demodulate=v))
+    for i in range(4):
+        c = fcfg()
+        c._reserved[i] = 1
+        refuse_f(E_INVALID, ("_reserved", i), cfg=c)
+    # null arguments
+    lp, vc, fc = C.byref(r.launchParams), vcfg(), fcfg()
+    assert L.fovpt_variance(None, lp, C.byref(vc), None, None, None, None) == E_INVALID
+    assert L.fovpt_variance(r._ctx, None, C.byref(vc), None, None, None, None) == E_INVALID
+    assert L.fovpt_variance(r._ctx, lp, None, None, None, None, None) == E_INVALID
+    assert L.fovpt_variance_filter(None, lp, C.byref(fc), None, None, None, None, None) == E_INVALID
+    assert L.fovpt_variance_filter(r._ctx, None, C.byref(fc), None, None, None, None, None) == E_INVALID
+    assert L.fovpt_variance_filter(r._ctx, lp, None, None, None, None, None, None) == E_INVALID
+    a_, b_ = C.c_void_p(), C.c_void_p()
+    assert L.fovpt_variance_buffers(r._ctx, None, C.byref(b_)) == E_INVALID and L.fovpt_variance_buffers(r._ctx, C.byref(a_), None) == E_INVALID
+    assert L.fovpt_variance_filter_buffers(r._ctx, None, C.byref(b_)) == E_INVALID and L.fovpt_variance_buffers(None, C.byref(a_), C.byref(b_)) == E_INVALID
+    assert L.fovpt_variance_reset(None) == E_INVALID
+    assert everything() == before
+    # a null input
+    keep = f.accum_buffer
+    f.accum_buffer = None
+    refuse_v(E_INVALID, "null accum_buffer")
+    refuse_f(E_INVALID, "null accum_buffer")
+    f.accum_buffer = keep
+    # a G-buffer of another size, or without a position or normal (and, demodulating, without an albedo)
+    for name, v in (("width", size[0] - 1), ("height", size[1] + 1), ("position", None), ("normal", None)):
+        bad = abi.GBufferPtrs.from_buffer_copy(bytes(g))
+        setattr(bad, name, v)
+        refuse_v(E_INVALID, ("gbuffer", name), gbuffer=bad)
+        refuse_f(E_INVALID, ("gbuffer", name), gbuffer=bad)
+    bad = abi.GBufferPtrs.from_buffer_copy(bytes(g))
+    bad.albedo = None
+    refuse_f(E_INVALID, "demodulate without an albedo", gbuffer=bad)
+    bad.prim = None                                                        # prim is never read
+    r.variance_filter(fcfg(demodulate=0), bad, None, None, oc.data_ptr(), op.data_ptr())
+    r.variance_filter(None, g, None, None, oc.data_ptr(), op.data_ptr())
+    r.synchronize()
+    assert everything() == before                                          # (the same call as before again)
+    # aliasing: the output of the moment step is an input or a history; an output of the filter is an input or the other output
+    refuse_v(E_INVALID, "out is in_sample", in_sample=ov.data_ptr())
+    refuse_v(E_INVALID, "out is accum", out_variance=keep)
+    refuse_v(E_INVALID, "out is the motion", out_variance=mv.data_ptr())
+    refuse_v(E_INVALID, "out is the position", out_variance=g.position)
+    refuse_v(E_INVALID, "out is the normal", out_variance=g.normal)
+    refuse_v(E_INVALID, "out is a history", out_variance=own_mom)
+    refuse_v(E_INVALID, "the own image is the input", out_variance=None, in_sample=own_var)
+    refuse_f(E_INVALID, "out_color is in_color", in_color=oc.data_ptr())
+    refuse_f(E_INVALID, "out_color is accum", out_color=keep)
+    refuse_f(E_INVALID, "out_rgba is in_color", in_color=op.data_ptr())
+    refuse_f(E_INVALID, "out_rgba is out_color", out_rgba=oc.data_ptr())
+    refuse_f(E_INVALID, "out_color is the variance", variance=oc.data_ptr())
+    refuse_f(E_INVALID, "out_color is the own variance", out_color=own_var)
+    refuse_f(E_INVALID, "out_color is the position", out_color=g.position)
+    refuse_f(E_INVALID, "out_color is the normal", out_color=g.normal)
+    refuse_f(E_INVALID, "out_color is the albedo", out_color=g.albedo)
+    refuse_f(E_INVALID, "the own colour is the input", out_color=None, in_color=own_c)
+    refuse_f(E_INVALID, "out_color is the own rgba", out_rgba=None, out_color=own_p)
+    # the frame: another size; no scene where the call traces; a singular rendered camera; a tile shard
+    f.size.x -= 4
+    for call in (lambda: r.variance(None, g, None, None, ov.data_ptr()), lambda: r.variance_filter(None, g, None, None, oc.data_ptr(), op.data_ptr())):
+        with pytest.raises(lib.FovptError) as e:
+            call()
+        assert e.value.code == E_NO_FRAME
+    f.size.x += 4                                            # (the downloads of everything() go by this size)
+    assert everything() == before
+    trav = r.launchParams.traversable
+    r.launchParams.traversable = trav + 1
+    refuse_v(E_NO_SCENE, "another scene", gbuffer=None)
+    refuse_f(E_NO_SCENE, "another scene", gbuffer=None)
+    r.variance_filter(None, g, None, None, oc.data_ptr(), op.data_ptr())   # with a G-buffer the scene is not needed
+    r.launchParams.traversable = trav
+    r.synchronize()
+    assert everything() == before
+    cam = r.launchParams.camera
+    keep_w = (cam.W.x, cam.W.y, cam.W.z)
+    cam.W.set((cam.U.x, cam.U.y, cam.U.z))                   # determinant 0
+    r.render()
+    before = everything()
+    refuse_v(E_INVALID, "a singular rendered camera")
+    cam.W.set(keep_w)
+    c = r.config
+    c.world, c.rank = 2, 0
+    r.config = c
+    r.render()
+    before = everything()
+    refuse_v(E_INVALID, "world 2")
+    refuse_f(E_INVALID, "world 2")
+    c.world, c.rank = 1, 0
+    r.config = c
+    r.render()
+    r.variance(None, g, None, mv.data_ptr(), ov.data_ptr())  # the valid calls after them
+    r.variance_filter(None, g, None, ov.data_ptr(), oc.data_ptr(), op.data_ptr())
+    r.synchronize()
+    assert everything() != before
+    r.close()
+
+
+# ---- 5. the C++ drop-in ----------------------------------------------------------------------------------------------------------------
+def test_cpp_dropin_variance(oracle, tmp_path):
+    """SampleRenderer::variance() / varianceFilter() / downloadVarianceFiltered() of include/SimplePathtracer.h: the same pixels as
+    Python."""
+    exe, out = str(tmp_path / "variance_gpu_test"), str(tmp_path / "variance_out.bin")
+    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "variance_gpu_test.cpp"), "-o", exe,
+                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
+    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    size = (160, 96)
+    n = size[0] * size[1]
+    raw = np.fromfile(out, np.uint8)
+    px = raw[:8 * n].view(np.uint32).reshape(2, size[1], size[0])
+    col = raw[8 * n:40 * n].view(np.float32).reshape(2, size[1], size[0], 4)
+    var = raw[40 * n:56 * n].view(np.float32).reshape(size[1], size[0], 4)
+    cfg = cfg_foveated(12, 36, (1, 2, 8))
+    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg)
+    m = Moments(r, cfg)
+    for k in range(2):
+        r.launchParams.frame.subframe_index = k
+        r.render()
+        _, want_var, _ = m.step({})
+    assert np.array_equal(bits(var), bits(want_var)) and (var[..., 3] == 2).all()
+    r.variance_filter()
+    got_c, got_p = r.downloadVarianceFiltered()
+    assert np.array_equal(px[0], got_p) and np.array_equal(bits(col[0]), bits(got_c))
+    r.variance_filter(fcfg(iterations_fovea=1, iterations_middle=3, iterations_periphery=5, demodulate=0))
+    got_c, got_p = r.downloadVarianceFiltered()
+    assert np.array_equal(px[1], got_p) and np.array_equal(bits(col[1]), bits(got_c))
+    assert (px[1] != px[0]).mean() > 0.05 and len(np.unique(px[0])) > 20
+    r.close()
