@@ -466,6 +466,30 @@ class ExposeState(C.Structure):
     ]
 
 
+BLOOM_MAX_LEVELS = 8                           # FOVPT_BLOOM_MAX_LEVELS
+BLOOM_KARIS, BLOOM_GAINS, BLOOM_EXPOSURE_STATE = 1, 2, 4     # FOVPT_BLOOM_* (flags)
+
+
+class BloomConfig(C.Structure):
+    """fovpt_bloom_config: flags, levels, the threshold and knee in exposed units, the exposure they are divided by, the intensity
+    of the composite, the spread between levels and the gains per foveation level (defaults: fovpt_bloom_defaults)."""
+    _fields_ = [
+        ("flags", C.c_int32), ("levels", C.c_int32),
+        ("threshold", C.c_float), ("knee", C.c_float), ("exposure", C.c_float),
+        ("intensity", C.c_float), ("spread", C.c_float),
+        ("gain_fovea", C.c_float), ("gain_middle", C.c_float), ("gain_periphery", C.c_float), ("gain_uniform", C.c_float),
+        ("_reserved", C.c_int32 * 5),
+    ]
+
+    def copy(self):
+        m = BloomConfig()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(BloomConfig))
+        return m
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
 WARP_COLOR, WARP_RGBA = 1, 2                   # FOVPT_WARP_*
 WARP_MAX_RADIUS = 4                            # FOVPT_WARP_MAX_RADIUS
 WARP_DIRECT, WARP_FILLED, WARP_EMPTY = 0, 1, 2  # the class in bits 30 .. 31 of a warp map entry
@@ -701,6 +725,7 @@ assert C.sizeof(TemporalConfig) == 32
 assert C.sizeof(PostConfig) == 112 and (PostConfig.denoise.offset, PostConfig.reconstruct.offset, PostConfig.temporal.offset) == (16, 48, 80)
 assert C.sizeof(ExposeConfig) == 80 and (ExposeConfig.low_permille.offset, ExposeConfig.key.offset) == (32, 48)
 assert C.sizeof(ExposeState) == 32 and ExposeState.weight_total.offset == 16
+assert C.sizeof(BloomConfig) == 64 and (BloomConfig.exposure.offset, BloomConfig.gain_fovea.offset, BloomConfig._reserved.offset) == (16, 28, 44)
 assert C.sizeof(WarpCamera) == 48 and C.sizeof(WarpConfig) == 32 and C.sizeof(WarpCounts) == 32
 assert C.sizeof(WarpMotionConfig) == 32 and WarpMotionConfig.advance.offset == 8
 assert C.sizeof(FocusConfig) == 64 and (FocusConfig.strength.offset, FocusConfig._reserved.offset) == (16, 36)

@@ -325,6 +325,7 @@ int fovpt_debug_buffer(fovpt_ctx* c, const char* name, void** ptr, size_t* bytes
     if (strcmp(name, "post_color") == 0 && c->post.out.color.p) { *ptr = c->post.out.color.p; *bytes = c->post.out.color.bytes; return FOVPT_OK; }   // fovpt_post's own output, once made
     if (strcmp(name, "expose_histogram") == 0 && c->expose.hist.p) { *ptr = c->expose.hist.p; *bytes = FOVPT_EXPOSE_BINS * sizeof(uint64_t); return FOVPT_OK; }   // fovpt_expose's last metered step
     if (strcmp(name, "expose_state") == 0 && c->expose.state.p) { *ptr = c->expose.state.p; *bytes = sizeof(ExposeState); return FOVPT_OK; }
+    if (strcmp(name, "bloom_pyramid") == 0 && c->bloom.pyramid.p) { *ptr = c->bloom.pyramid.p; *bytes = c->bloom.texels * 16; return FOVPT_OK; }   // fovpt_bloom's levels of the last call
     if (strcmp(name, "warp_keys") == 0 && c->warp.keys.p) { *ptr = c->warp.keys.p; *bytes = c->warp.keys.bytes; return FOVPT_OK; }   // fovpt_warp's keys, once made
     if (strcmp(name, "focus_state") == 0 && c->focus.state.p) { *ptr = c->focus.state.p; *bytes = sizeof(FocusState); return FOVPT_OK; }   // fovpt_focus's state record
     if (strcmp(name, "focus_scratch") == 0 && c->focus.rt.p) { *ptr = c->focus.rt.p; *bytes = c->focus.rt.bytes; return FOVPT_OK; }   // and its (r, tp) pairs, once made

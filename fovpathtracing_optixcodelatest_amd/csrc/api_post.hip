@@ -2,7 +2,7 @@
 // in fovpt_ctx.h; api_view.hip and api_packet.hip use them too), what fovpt_resize and fovpt_set_scene ask of the stages
 // (post_resize, post_scene_changed), and the stages that rebuild the image: fovpt_denoise (denoise.hip), fovpt_gbuffer /
 // fovpt_reconstruct (reconstruct.hip), fovpt_temporal / fovpt_temporal_motion (temporal.hip), fovpt_post (post_fused.hip),
-// fovpt_variance / fovpt_variance_filter (variance.hip), and their defaults.  Every stage has the same parts -- *_check (nothing
+// fovpt_variance / fovpt_variance_filter (variance.hip), fovpt_bloom (bloom.hip), and their defaults.  Every stage has the same parts -- *_check (nothing
 // allocated, enqueued or changed), the kernel's arguments from the config and the rendered frame's record (*_args where more than
 // one place needs them) and *_enqueue (reservations and launches of a checked call; the two variance calls, which nothing else
 // enqueues, have theirs in the entry point) -- and its entry point is: null checks, check, hipSetDevice, own outputs, alias check,
@@ -168,6 +168,15 @@ static int reserve_variance(fovpt_ctx* c, size_t n)
     return FOVPT_OK;
 }
 
+// the texels of fovpt_bloom's pyramid for a w x h frame, with every level a call may ask for
+static size_t bloom_pyramid_texels(int w, int h)
+{
+    int W, H;
+    size_t end;
+    fovpt_bloom_level(w, h, FOVPT_BLOOM_MAX_LEVELS, &W, &H, &end);
+    return end;
+}
+
 // fovpt_resize: what exists of the stages' buffers follows the frame (nothing is made here); the states of fovpt_expose and
 // fovpt_focus and the record of fovpt_quality stay
 int post_resize(fovpt_ctx* c, int w, int h)
@@ -180,6 +189,9 @@ int post_resize(fovpt_ctx* c, int w, int h)
     if (c->temporal.hist[0].p) CHK(reserve_temporal(c, n));
     HIPCHK(c, follow(c->post.out));
     HIPCHK(c, follow(c->expose.out));
+    HIPCHK(c, follow(c->bloom.out));
+    if (c->bloom.pyramid.p) HIPCHK(c, c->bloom.pyramid.reserve(bloom_pyramid_texels(w, h) * 16));
+    c->bloom.texels = 0;                                                   // (the levels in it are of another size)
     if (c->warp.keys.p) HIPCHK(c, c->warp.keys.reserve(n * 8));
     if (c->warp.out.color.p) HIPCHK(c, c->warp.out.color.reserve(n * 16));     // (a warp of one image makes only that one)
     if (c->warp.out.rgba.p) HIPCHK(c, c->warp.out.rgba.reserve(n * 4));
@@ -503,6 +515,49 @@ int variance_filter_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fov
     CHK(variance_frame_check(c, lp, gbuffer, fc->demodulate != 0, in, who, "filter with"));
     if (!variance && (c->variance.own_w != c->rendered.w || c->variance.own_h != c->rendered.h))
         return fail(c, FOVPT_E_NO_FRAME, "%s: no fovpt_variance has written the context's variance image at this frame size", who);
+    return FOVPT_OK;
+}
+
+// fovpt_bloom's validation.  in: its colour input
+int bloom_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_bloom_config* bc, const fovpt_float4* in, const char* who)
+{
+    if (bc->flags & ~(FOVPT_BLOOM_KARIS | FOVPT_BLOOM_GAINS | FOVPT_BLOOM_EXPOSURE_STATE)) return fail(c, FOVPT_E_INVALID, "%s: unknown flag bits in %d", who, bc->flags);
+    if (bc->levels < 1 || bc->levels > FOVPT_BLOOM_MAX_LEVELS) return fail(c, FOVPT_E_INVALID, "%s: levels %d outside 1 .. %d", who, bc->levels, FOVPT_BLOOM_MAX_LEVELS);
+    const float pos[2] = {bc->threshold, bc->exposure};
+    for (float v : pos)
+        if (!sigma_ok(v)) return fail(c, FOVPT_E_INVALID, "%s: threshold or exposure %g outside [%g, %g]", who, (double)v, (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX);
+    const float nonneg[2] = {bc->knee, bc->intensity};
+    for (float v : nonneg)
+        if (!(v >= 0.0f && v <= FOVPT_SIGMA_MAX)) return fail(c, FOVPT_E_INVALID, "%s: knee or intensity %g outside [0, %g]", who, (double)v, (double)FOVPT_SIGMA_MAX);
+    const float unit[5] = {bc->spread, bc->gain_fovea, bc->gain_middle, bc->gain_periphery, bc->gain_uniform};
+    for (float v : unit)
+        if (!(v >= 0.0f && v <= 1.0f)) return fail(c, FOVPT_E_INVALID, "%s: spread or gain %g outside [0, 1]", who, (double)v);
+    CHK(check_reserved(c, bc->_reserved, sizeof(bc->_reserved) / 4, who));
+    CHK(check_rendered_frame(c, lp, who, "spread light over", nullptr, 1ull << 31));
+    if (!in) return fail(c, FOVPT_E_INVALID, "%s: null accum_buffer", who);
+    return FOVPT_OK;
+}
+
+BloomArgs bloom_args(const fovpt_bloom_config* bc, const fovpt_ctx::Rendered& R)
+{
+    BloomArgs a;
+    memset(&a, 0, sizeof(a));
+    a.flags = bc->flags; a.uniform = R.uniform != 0;
+    a.threshold = bc->threshold; a.knee = bc->knee; a.exposure = bc->exposure; a.intensity = bc->intensity; a.spread = bc->spread;
+    a.gain[0] = bc->gain_fovea; a.gain[1] = bc->gain_middle; a.gain[2] = bc->gain_periphery; a.gain[3] = bc->gain_uniform;
+    return a;
+}
+
+// the launches of a checked call with its outputs set and the pyramid reserved
+int bloom_enqueue(fovpt_ctx* c, const fovpt_bloom_config* bc, const fovpt_float4* in, fovpt_float4* out_color, uint32_t* out_rgba)
+{
+    const fovpt_ctx::Rendered& R = c->rendered;
+    // the exposure record where fovpt_expose has made one (none yet: no AUTO step has run, E = cfg.exposure)
+    const ExposeState* state = (bc->flags & FOVPT_BLOOM_EXPOSURE_STATE) ? (const ExposeState*)c->expose.state.p : nullptr;
+    fovpt_launch_bloom(c->shadow_stream, R.frame, bloom_args(bc, R), bc->levels, state, in, (float4*)c->bloom.pyramid.p, out_color, out_rgba);
+    HIPCHK(c, hipGetLastError());
+    int W, H;
+    fovpt_bloom_level(R.w, R.h, bc->levels, &W, &H, &c->bloom.texels);
     return FOVPT_OK;
 }
 
@@ -851,6 +906,47 @@ int fovpt_variance_filter(fovpt_ctx* c, const fovpt_launch_params* lp, const fov
     fovpt_launch_vfilter(c->shadow_stream, R.frame, a, in, variance, g, (float4*)V.j0.p, (float4*)V.j1.p, (uint8_t*)V.level.p, out_color, out_rgba);
     HIPCHK(c, hipGetLastError());
     return FOVPT_OK;
+}
+
+// ---- HDR glare ahead of the tone map (bloom.hip; its definition: tests/bloom_ref.py) ----------------------------------------
+// (conventions, not measurements: the usual threshold, knee and levels of a dual-filter bloom, the shipped app's exposure)
+int fovpt_bloom_defaults(fovpt_bloom_config* out)
+{
+    if (!zeroed(out)) return FOVPT_E_INVALID;
+    out->flags = FOVPT_BLOOM_KARIS;
+    out->levels = 6;
+    out->threshold = 1.0f;
+    out->knee = 0.5f;
+    out->exposure = 16.0f;
+    out->intensity = 0.05f;
+    out->spread = 0.7f;
+    out->gain_fovea = out->gain_middle = out->gain_periphery = out->gain_uniform = 1.0f;
+    return FOVPT_OK;
+}
+
+int fovpt_bloom_buffers(fovpt_ctx* c, fovpt_float4** color, uint32_t** rgba)
+{
+    return c ? own_buffers(c, "fovpt_bloom_buffers", c->bloom.out, color, rgba) : FOVPT_E_INVALID;
+}
+
+// Enqueued on fovpt_stream() like fovpt_denoise, and ordered like it: k_bloom_prefilter, the levels down and back up (one launch
+// each), k_bloom_composite.  With EXPOSURE_STATE the exposure goes from fovpt_expose's record into the first kernel, never through
+// the host.
+int fovpt_bloom(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_bloom_config* bc, const fovpt_float4* in_color, fovpt_float4* out_color,
+                uint32_t* out_rgba)
+{
+    const char* who = "fovpt_bloom";
+    if (!c) return FOVPT_E_INVALID;
+    if (!lp || !bc) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    const fovpt_float4* in = in_color ? in_color : lp->frame.accum_buffer;
+    CHK(bloom_check(c, lp, bc, in, who));
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(own_outputs(c, who, c->bloom.out, out_color, out_rgba));
+    HIPCHK(c, c->bloom.pyramid.reserve(bloom_pyramid_texels(c->rendered.w, c->rendered.h) * 16));
+    const void* pyr = c->bloom.pyramid.p;
+    CHK(check_aliases(c, {out_color, out_rgba}, {pyr}, who, "%s: an output is the pyramid"));
+    CHK(check_aliases(c, {out_rgba, pyr}, {in}, who, "%s: the rgba output or the pyramid is the input (only out_color may be)"));
+    return bloom_enqueue(c, bc, in, out_color, out_rgba);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 """Build guard (Makefile): reads the -Rpass-analysis=kernel-resource-usage remarks of a device compile and fails when a
 per-frame kernel (k_generate, k_traverse, k_shade, k_resolve, the denoiser's k_denoise_*, the reconstruction's k_gbuffer_* and
 k_reconstruct, the temporal reprojection's k_temporal, the refit's k_gather_vertices / k_refit_level / k_flatten,
-the transforms' k_transform_vertices*, the rig's k_rig_pose, the skinning's k_skin_vertices, the morph targets' k_morph_vertices / k_morph_skin_vertices, the cost measurement's k_tree_cost*, the exposure's k_expose_*, the warp's k_warp_* (k_warp_scatter_motion of fovpt_warp_motion among them), the frame packets' k_packet_*, the focus stage's k_focus_*, the lens pre-distortion's k_lens, the variance stage's k_variance_moments and k_vfilter_*, the quality measurement's k_quality_*) uses scratch memory, when k_rig_pose's LDS is not the 48 KiB it is designed for, or when k_traverse drops below the waves per
+the transforms' k_transform_vertices*, the rig's k_rig_pose, the skinning's k_skin_vertices, the morph targets' k_morph_vertices / k_morph_skin_vertices, the cost measurement's k_tree_cost*, the exposure's k_expose_*, the bloom stage's k_bloom_*, the warp's k_warp_* (k_warp_scatter_motion of fovpt_warp_motion among them), the frame packets' k_packet_*, the focus stage's k_focus_*, the lens pre-distortion's k_lens, the variance stage's k_variance_moments and k_vfilter_*, the quality measurement's k_quality_*) uses scratch memory, when k_rig_pose's LDS is not the 48 KiB it is designed for, or when k_traverse drops below the waves per
 SIMD it is written for.  (The one-off kernels of the BVH build -- k_collapse4, rocPRIM's radix sort -- do use scratch, and run.)
 
 Why: every hot kernel here is tuned to a register budget; a compiler or flag change that makes one spill would silently
@@ -11,7 +11,7 @@ HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION; the product must never get there unn
 import re, sys
 
 HOT = ("k_generate", "k_traverse", "k_shade", "k_resolve", "k_denoise", "k_gbuffer", "k_reconstruct", "k_temporal", "k_gather_vertices",
-       "k_refit_level", "k_flatten", "k_transform_vertices", "k_rig_pose", "k_skin_vertices", "k_morph_vertices", "k_morph_skin_vertices", "k_tree_cost", "k_expose", "k_warp", "k_packet", "k_focus", "k_lens", "k_quality", "k_variance", "k_vfilter")
+       "k_refit_level", "k_flatten", "k_transform_vertices", "k_rig_pose", "k_skin_vertices", "k_morph_vertices", "k_morph_skin_vertices", "k_tree_cost", "k_expose", "k_bloom", "k_warp", "k_packet", "k_focus", "k_lens", "k_quality", "k_variance", "k_vfilter")
 text = open(sys.argv[1]).read()
 bad = []
 name = None

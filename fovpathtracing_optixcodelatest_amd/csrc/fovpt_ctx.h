@@ -244,6 +244,9 @@ struct fovpt_ctx {
     // AUTO step is a first step; the host never reads it outside fovpt_expose_state), the meter's per-block histogram rows and
     // the histogram of the last metered step, and the context's own outputs; all allocated on first use
     struct FOVPT_LOCAL Expose { DevBuf state, rows, hist; OutPair out; } expose;
+    // fovpt_bloom: the pyramid (float4 texels, the levels packed one after the other; texels: those of the last call's levels,
+    // fovpt_debug_buffer "bloom_pyramid") and the context's own outputs; all allocated on first use
+    struct FOVPT_LOCAL Bloom { DevBuf pyramid; size_t texels = 0; OutPair out; } bloom;
     // fovpt_warp: the scatter's keys (8 bytes per pixel), the device counts (FOVPT_WARP_COUNT_SLOTS partial records, zeroed on the stream
     // ahead of every warp; the host reads and adds them nowhere but in fovpt_warp_counts) and the context's own outputs; all allocated on
     // first use

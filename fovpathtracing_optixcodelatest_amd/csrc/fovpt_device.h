@@ -337,6 +337,18 @@ void fovpt_launch_expose_meter(hipStream_t st, const FrameDev& fd, const ExposeA
 void fovpt_launch_expose_adapt(hipStream_t st, const ExposeArgs& a, const uint32_t* rows, uint32_t nrows, uint64_t* hist, ExposeState* state);
 void fovpt_launch_expose_apply(hipStream_t st, size_t npix, const ExposeArgs& a, const ExposeState* state, const fovpt_float4* in,
                                fovpt_float4* out_color, uint32_t* out_rgba);
+// fovpt_bloom (bloom.hip): the bright pass into level 0 of the pyramid (state: fovpt_expose's record where the exposure comes
+// from it, else null), the levels down and back up, one launch each, then the composite.  pyramid: the levels packed one after
+// the other (fovpt_bloom_level: the size of level k of a w x h frame and its first texel); it is none of the call's other buffers.
+struct BloomArgs {
+    int32_t flags;                      // FOVPT_BLOOM_*
+    int32_t uniform;                    // the frame was rendered FOV_OFF
+    float threshold, knee, exposure, intensity, spread;
+    float gain[4];                      // GAINS: fill 1, fill 2, fill 4, FOV_OFF
+};
+void fovpt_bloom_level(int w, int h, int k, int* W, int* H, size_t* first);
+void fovpt_launch_bloom(hipStream_t st, const FrameDev& fd, const BloomArgs& a, int levels, const ExposeState* state, const fovpt_float4* in,
+                        float4* pyramid, fovpt_float4* out_color, uint32_t* out_rgba);
 // fovpt_warp (warp.hip): the depth-tested scatter of fd's pixels (its camera: the directions of miss pixels) into `keys` -- one
 // 64-bit key per pixel, all ones before the launch -- seen from the camera of a, then the resolve of the keys into the outputs.
 // counts: FOVPT_WARP_COUNT_SLOTS copies of a struct fovpt_warp_counts on the device, FOVPT_WARP_COUNT_STRIDE 64-bit words apart

@@ -27,6 +27,7 @@ EXPORTS = [
     "fovpt_set_morphs", "fovpt_update_morphed", "fovpt_set_rig", "fovpt_update_animated",
     "fovpt_post_defaults", "fovpt_post", "fovpt_post_buffers",
     "fovpt_expose_defaults", "fovpt_expose", "fovpt_expose_buffers", "fovpt_expose_state", "fovpt_expose_reset",
+    "fovpt_bloom_defaults", "fovpt_bloom", "fovpt_bloom_buffers",
     "fovpt_warp_defaults", "fovpt_warp", "fovpt_warp_buffers", "fovpt_warp_counts", "fovpt_temporal_gbuffer",
     "fovpt_warp_motion_defaults", "fovpt_warp_motion",
     "fovpt_focus_defaults", "fovpt_focus", "fovpt_focus_buffers", "fovpt_focus_state", "fovpt_focus_reset",
@@ -206,6 +207,9 @@ def load():
     L.fovpt_expose_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_expose_state.argtypes = [vp, C.POINTER(abi.ExposeState)]
     L.fovpt_expose_reset.argtypes = [vp]
+    L.fovpt_bloom_defaults.argtypes = [C.POINTER(abi.BloomConfig)]
+    L.fovpt_bloom.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.BloomConfig), vp, vp, vp]
+    L.fovpt_bloom_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.fovpt_warp_defaults.argtypes = [C.POINTER(abi.WarpConfig)]
     L.fovpt_warp.argtypes = [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.WarpCamera), C.POINTER(abi.WarpConfig), C.POINTER(abi.GBufferPtrs),
                              vp, vp, vp, vp, vp]

@@ -456,6 +456,37 @@ class SampleRenderer:
         """The float4 output of the last expose() into the renderer's own buffer."""
         return self._download_frame(self.expose_buffers()[0], 4)
 
+    # -- HDR glare ahead of the tone map (include/fovpt.h, fovpt_bloom)
+    @staticmethod
+    def bloom_defaults() -> abi.BloomConfig:
+        d = abi.BloomConfig()
+        lib.check(None, lib.load().fovpt_bloom_defaults(C.byref(d)))
+        return d
+
+    def bloom(self, config=None, in_color=None, out_color=None, out_rgba=None):
+        """Adds the glare of the frame's highlights to it, in HDR (fovpt_bloom): a bright pass whose threshold follows the exposure
+        (config.flags & abi.BLOOM_EXPOSURE_STATE: the one expose() last adapted to, read on the device), a pyramid of
+        config.levels levels, and the composite.  in_color: device pointer of a float4 frame (None: the accum buffer; typically
+        focus_buffers()[0] or post_buffers()[0]), out_color / out_rgba: device pointers, or None for the renderer's own buffers
+        (downloadBloomColor / downloadBloomPixels); out_color may be in_color.  Meant ahead of expose().  Enqueued on the
+        renderer's stream, not synchronised (the downloads synchronise)."""
+        config = config if config is not None else self.bloom_defaults()
+        self._check(self._L.fovpt_bloom(self._ctx, C.byref(self.launchParams), C.byref(config), in_color, out_color, out_rgba))
+
+    def bloomBuffers(self):
+        """Device addresses of the renderer's own bloom outputs: (float4 colour, rgba8)."""
+        col, rgba = C.c_void_p(), C.c_void_p()
+        self._check(self._L.fovpt_bloom_buffers(self._ctx, C.byref(col), C.byref(rgba)))
+        return col.value, rgba.value
+
+    def downloadBloomPixels(self):
+        """The rgba8 output of the last bloom() into the renderer's own buffer, shaped like downloadPixels()."""
+        return self._download_frame(self.bloomBuffers()[1], 1)
+
+    def downloadBloomColor(self):
+        """The float4 output of the last bloom() into the renderer's own buffer."""
+        return self._download_frame(self.bloomBuffers()[0], 4)
+
     # -- late reprojection of the finished frame to a newer camera (include/fovpt.h, fovpt_warp)
     @staticmethod
     def warp_defaults() -> abi.WarpConfig:

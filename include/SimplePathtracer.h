@@ -234,6 +234,50 @@ public:
         check(fovpt_expose_buffers(ctx, &color, &rgba));
         check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
     }
+    // ---- HDR glare ahead of the tone map (include/fovpt.h, fovpt_bloom): adds the glare of in_color's highlights (null: the accum
+    // buffer) to it, into the renderer's own bloom buffers, then a device sync like render().  Meant ahead of expose(): exposeBloom()
+    void bloom()
+    {
+        fovpt_bloom_config bc;
+        check(fovpt_bloom_defaults(&bc));
+        bloom(bc);
+    }
+    void bloom(const fovpt_bloom_config& bc, const fovpt_float4* in_color = nullptr)
+    {
+        check(fovpt_bloom(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &bc, in_color, nullptr, nullptr));
+        check(fovpt_synchronize(ctx));
+    }
+    // bloom() of the colour the last post() left in the renderer's own post buffers
+    void bloomPost(const fovpt_bloom_config& bc)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_post_buffers(ctx, &color, &rgba));
+        bloom(bc, color);
+    }
+    // expose() of the colour the last bloom() left in the renderer's own bloom buffers
+    void exposeBloom(const fovpt_expose_config& ec)
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_bloom_buffers(ctx, &color, &rgba));
+        expose(ec, color);
+    }
+    // the bloom stage's float4 colour and rgba8 pixels, like downloadPixels
+    void downloadBloomColor(fovpt_float4 h_color[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_bloom_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, color, h_color, sizeof(fovpt_float4) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
+    void downloadBloomPixels(uint32_t h_pixels[])
+    {
+        fovpt_float4* color = nullptr;
+        uint32_t* rgba = nullptr;
+        check(fovpt_bloom_buffers(ctx, &color, &rgba));
+        check(fovpt_download(ctx, rgba, h_pixels, sizeof(uint32_t) * (size_t)launchParams.frame.size.x * (size_t)launchParams.frame.size.y));
+    }
     // ---- late reprojection (include/fovpt.h, fovpt_warp): re-aims the frame just rendered at a newer camera -- its aspect ratio is
     // set from the frame size, as setCamera does -- into the renderer's own warped buffers, then a device sync like render().
     // in_color / in_rgba: null = the accum / frame buffer, or e.g. the exposed outputs (fovpt_expose_buffers).  reuse_gbuffer: take the

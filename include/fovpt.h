@@ -971,6 +971,79 @@ int fovpt_expose_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
 int fovpt_expose_state(fovpt_ctx* ctx, struct fovpt_expose_state* out);
 int fovpt_expose_reset(fovpt_ctx* ctx);
 
+/* ---- HDR glare ("bloom") ahead of the tone map ----------------------------------------------------------------------------------
+ * New with this library.  fovpt_expose compresses everything above the display range to white; fovpt_bloom is the stage ahead of it
+ * (behind fovpt_focus) that lets a highlight say how far above white it was: a thresholded, downsampled and re-expanded copy of the
+ * frame added onto it, in HDR.  Two things are this renderer's own: the bright pass can weight its samples by 1 / (1 + L) (KARIS: a
+ * block-filled 1-spp firefly of the periphery does not become a blob) and by a gain per foveation level (GAINS), and the threshold
+ * follows the exposure, which with EXPOSURE_STATE is read from fovpt_expose's device record on the device, in stream order.
+ *   fovpt_bloom              works on the frame last issued with fovpt_render(ctx, lp) as it was rendered (its size, passes, gaze and
+ *                            FOV_OFF flag).  in_color NULL = accum_buffer; out_color / out_rgba NULL = the context's own buffers
+ *                            (fovpt_bloom_buffers: allocated on first use with the pyramid, reallocated by fovpt_resize, freed by
+ *                            fovpt_destroy).  out_color may be in_color (the pyramid is finished before any pixel is written, and the
+ *                            composite reads only its own input pixel).  Enqueued on fovpt_stream(), not synchronised, ordered like
+ *                            fovpt_denoise.  Writes its outputs and the pyramid, nothing else.  The definition, operation by
+ *                            operation (tests/bloom_ref.py), every fp32 + - * / one unfused operation, min(a, b) = a < b ? a : b and
+ *                            max likewise; w x h the frame, n = levels, level k of W_k x H_k texels with W_k = ceil(W_{k-1} / 2),
+ *                            W_{-1} = w (never below 1: a 1 x 1 level is downsampled to 1 x 1 by the same rule):
+ *                              0 constants   E = cfg.exposure; with EXPOSURE_STATE the exposure of fovpt_expose's state record if its
+ *                                            steps != 0.  T = threshold / E, K = knee / E, K2 = 2.0f * K, K4 = 4.0f * K
+ *                              1 bright pass d_0(X, Y) from the source pixels (min(2X + i, w - 1), min(2Y + j, h - 1)), j = 0, 1
+ *                                            outer, i = 0, 1 inner; with c the pixel's rgb:
+ *                                              L = (0.2126f * r + 0.7152f * g) + 0.0722f * b
+ *                                              s = max(0, min(L - (T - K), K2));  q = K > 0 ? (s * s) / K4 : 0
+ *                                              m = max(max(q, L - T), 0) / max(L, 1e-6f)
+ *                                              kw = KARIS ? 1.0f / (1.0f + L) : 1.0f
+ *                                              g = 1; with GAINS gain_fovea / _middle / _periphery by the fill (1 / 2 / 4) of the
+ *                                                  pixel's last writer, gain_uniform on a FOV_OFF frame, 0 where no pass writes
+ *                                              wt = g * kw;  num.c = num.c + wt * (c.c * m);  den = den + kw
+ *                                            then d_0.c = num.c / den
+ *                              2 downsample  d_k(X, Y), k = 1 .. n - 1: taps j = 0 .. 3 outer, i = 0 .. 3 inner, of
+ *                                            d_{k-1}(clamp(2X - 1 + i, 0, W_{k-1} - 1), clamp(2Y - 1 + j, 0, H_{k-1} - 1)) with weight
+ *                                            (float)(b_j * b_i) * 0.015625f, b = {1, 3, 3, 1}: acc.c = acc.c + weight * S.c from 0
+ *                              3 upsample    up(S)(x, y) of a level S (Ws x Hs) onto a grid twice as fine: ax = x >> 1,
+ *                                            bx = clamp((x & 1) ? ax + 1 : ax - 1, 0, Ws - 1), the same in y;
+ *                                            r0 = 0.75f * S(ax, ay) + 0.25f * S(bx, ay), r1 = 0.75f * S(ax, by) + 0.25f * S(bx, by),
+ *                                            up = 0.75f * r0 + 0.25f * r1, per channel
+ *                              4 combine     u_{n-1} = d_{n-1}; k = n - 2 .. 0: u_k.c = d_k.c + spread * up(u_{k+1})(x, y).c
+ *                              5 composite   B = up(u_0)(x, y); out_color = (in.r + intensity * B.r, in.g + intensity * B.g,
+ *                                            in.b + intensity * B.b, in.w); out_rgba = make_color(reinhard(out.rgb * 16, 1)), as in
+ *                                            every stage
+ *                            Outputs for input colours that are non-finite or negative are unspecified.  A non-negative frame whose
+ *                            every L <= T - K comes back bit for bit, at any intensity.  The pyramid is one allocation of float4
+ *                            texels (the fourth channel 0), the levels packed one after the other; u_k overwrites d_k, and after a
+ *                            call every level's u_k is in memory (fovpt_debug_buffer "bloom_pyramid").
+ *                            All or nothing, checked before anything is enqueued.  FOVPT_E_INVALID: null ctx / lp / bc; unknown
+ *                            flag bits; levels outside 1 .. FOVPT_BLOOM_MAX_LEVELS; threshold or exposure outside [FOVPT_SIGMA_MIN,
+ *                            FOVPT_SIGMA_MAX] or NaN; knee or intensity outside [0, FOVPT_SIGMA_MAX] or NaN; spread or a gain outside
+ *                            [0, 1] or NaN; non-zero reserved fields; a null input; width * height >= 2^31; out_color or out_rgba
+ *                            the pyramid or each other, out_rgba or the pyramid the input; a frame rendered with world > 1 (a shard
+ *                            does not see the frame).  FOVPT_E_NO_FRAME: nothing rendered since create / resize, or lp->frame.size
+ *                            differs.
+ *   fovpt_bloom_defaults     host only, no context.  CONVENTIONS, NOT MEASUREMENTS: KARIS only, 6 levels, threshold 1, knee 0.5,
+ *                            exposure 16 (the shipped app's constant), intensity 0.05, spread 0.7, all gains 1.
+ *   fovpt_bloom_buffers      addresses of the context's own outputs (allocated for the last frame if not yet).
+ * On an MI355X at 1920 x 1080 a call at the defaults takes 0.067 ms, 3.3 times fovpt_expose FIXED (a plain full-frame pass: 0.020 ms)
+ * measured beside it; with GAINS 0.088 ms (four writer searches per texel of the first level), with 8 levels 0.075 ms; one
+ * fovpt_render 0.68 ms.  Every level is one launch: one workgroup making the small levels in LDS measured slower at the defaults, and
+ * the composite's once-written outputs are nt stores, which measured no worse (EXPERIMENTS.md).               */
+#define FOVPT_BLOOM_MAX_LEVELS 8
+#define FOVPT_BLOOM_KARIS          1   /* flags: weight the first downsample's samples by 1 / (1 + L) */
+#define FOVPT_BLOOM_GAINS          2   /* per-level gains by the last writer's fill; off: gain 1 everywhere, no writer search */
+#define FOVPT_BLOOM_EXPOSURE_STATE 4   /* E from fovpt_expose's device record (steps != 0), else cfg.exposure */
+typedef struct fovpt_bloom_config {    /* 64 bytes */
+    int32_t flags, levels;             /* levels 1 .. FOVPT_BLOOM_MAX_LEVELS */
+    float threshold, knee;             /* in exposed units: compared against L * E */
+    float exposure;                    /* E unless EXPOSURE_STATE applies */
+    float intensity, spread;
+    float gain_fovea, gain_middle, gain_periphery, gain_uniform;
+    int32_t _reserved[5];
+} fovpt_bloom_config;
+int fovpt_bloom_defaults(fovpt_bloom_config* out);
+int fovpt_bloom(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_bloom_config* bc, const fovpt_float4* in_color /* NULL: accum_buffer */,
+                fovpt_float4* out_color, uint32_t* out_rgba /* NULL: the context's own */);
+int fovpt_bloom_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
+
 /* ---- late reprojection ("timewarp") of a finished frame to a newer camera ----------------------------------------------------
  * New with this library.  A head-mounted or gaze-tracked client learns its newest camera pose after fovpt_render was issued (with
  * two frames in flight it is two poses behind): fovpt_warp re-aims the finished image at that pose just before display.
@@ -1978,7 +2051,8 @@ int fovpt_debug_build(fovpt_ctx* ctx, uint32_t n, const float* tris9, const uint
  * as bits, 0xffffffff on a miss) per pixel --, "expose_histogram" -- fovpt_expose's last metered histogram, FOVPT_EXPOSE_BINS
  * uint64_t --, "expose_state" -- its device state record: a struct fovpt_expose_state --, "warp_keys" -- fovpt_warp's key
  * buffer, once made: the keys of the last warp in its first width * height uint64_t --, "focus_state" -- fovpt_focus's device
- * state record: a struct fovpt_focus_state --, "focus_scratch" -- its (r, tp) pairs, float2 per pixel, once made --, ...)       */
+ * state record: a struct fovpt_focus_state --, "focus_scratch" -- its (r, tp) pairs, float2 per pixel, once made --,
+ * "bloom_pyramid" -- fovpt_bloom's pyramid, once made: the levels of the last call, float4 texels packed one after the other --, ...) */
 int fovpt_debug_buffer(fovpt_ctx* ctx, const char* name, void** ptr, size_t* bytes);
 
 #ifdef __cplusplus
@@ -1998,6 +2072,8 @@ static_assert(sizeof(fovpt_post_config) == 112 && offsetof(fovpt_post_config, de
 static_assert(sizeof(fovpt_expose_config) == 80 && offsetof(fovpt_expose_config, low_permille) == 32 && offsetof(fovpt_expose_config, key) == 48,
               "expose config ABI");
 static_assert(sizeof(struct fovpt_expose_state) == 32 && offsetof(struct fovpt_expose_state, weight_total) == 16, "expose state ABI");
+static_assert(sizeof(fovpt_bloom_config) == 64 && offsetof(fovpt_bloom_config, exposure) == 16 && offsetof(fovpt_bloom_config, gain_fovea) == 28 &&
+              offsetof(fovpt_bloom_config, _reserved) == 44, "bloom config ABI");
 static_assert(sizeof(fovpt_warp_camera) == 48 && offsetof(fovpt_warp_camera, W) == 36, "warp camera ABI");
 static_assert(sizeof(fovpt_warp_config) == 32 && offsetof(fovpt_warp_config, fill_radius) == 4, "warp config ABI");
 static_assert(sizeof(struct fovpt_warp_counts) == 32 && offsetof(struct fovpt_warp_counts, direct) == 8, "warp counts ABI");

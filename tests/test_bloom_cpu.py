@@ -1,0 +1,347 @@
+"""fovpt_bloom without a GPU: the restatement (tests/bloom_ref.py) held against an independent binary64 statement within bounds
+derived from the roundings, its properties, the level sizes, the defaults through ctypes, the struct mirror against the header,
+the prototypes and the C++ drop-in."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import bloom_ref as br
+from fovpathtracing_optixcodelatest_amd import abi, lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+U = 2.0 ** -24                           # the unit roundoff of binary32
+
+
+@pytest.fixture(scope="module")
+def so():
+    lib.build()
+    return lib.load()
+
+
+def cfg(**kw):
+    return dict(br.DEFAULTS, **kw)
+
+
+def hdr_frame(w, h, seed, top=10):
+    """Seeded HDR image: values from 0 to 2^top with isolated spikes and black pixels, alpha a ramp."""
+    rng = np.random.default_rng(seed)
+    img = np.exp2(rng.uniform(-6, 3, (h, w, 4))).astype(np.float32)
+    n = w * h
+    flat = img.reshape(-1, 4)
+    flat[rng.permutation(n)[:max(1, n // 16)], :3] = 0.0
+    spikes = rng.permutation(n)[:max(1, n // 24)]
+    flat[spikes, :3] = np.exp2(rng.uniform(4, top, (len(spikes), 3))).astype(np.float32)
+    flat[:, 3] = np.linspace(0.0, 1.0, n, dtype=np.float32)
+    return img
+
+
+# ---- an independent binary64 statement ------------------------------------------------------------------------------------------
+# Not the restatement's loops: the downsample as two passes of the 1-D binomial (1, 3, 3, 1) / 8 over an edge-padded array, the
+# upsample as two passes of 1-D interpolation (3/4 of the near texel, 1/4 of the neighbour on the sample's side), level by level.
+def _down1(a, axis):
+    a = np.moveaxis(a, axis, 0)
+    n = a.shape[0]
+    m = (n + 1) // 2
+    pad = np.concatenate([a[:1], a, a[-1:], a[-1:], a[-1:]], axis=0)          # index i of a is i + 1 of pad; beyond the end: the last
+    out = sum(wt * pad[k:k + 2 * m:2][:m] for k, wt in enumerate((0.125, 0.375, 0.375, 0.125)))
+    return np.moveaxis(out, 0, axis)
+
+
+def _up1(a, n, axis):
+    a = np.moveaxis(a, axis, 0)
+    idx = np.arange(n)
+    near = idx // 2
+    other = np.clip(near + np.where(idx % 2 == 1, 1, -1), 0, a.shape[0] - 1)
+    out = 0.75 * a[near] + 0.25 * a[other]
+    return np.moveaxis(out, 0, axis)
+
+
+def pyramid64(d0, color, d):
+    """Steps 2 to 5 in binary64 from an fp32 d_0 -> (the u_k, out rgb)."""
+    n = d["levels"]
+    ds = [np.asarray(d0, np.float64)[..., :3]]
+    for _ in range(1, n):
+        ds.append(_down1(_down1(ds[-1], 1), 0))
+    us = [None] * n
+    us[-1] = ds[-1]
+    sp = float(f32(d["spread"]))
+    for k in range(n - 2, -1, -1):
+        H, W = ds[k].shape[:2]
+        us[k] = ds[k] + sp * _up1(_up1(us[k + 1], W, 1), H, 0)
+    h, w = color.shape[:2]
+    out = np.asarray(color, np.float64)[..., :3] + float(f32(d["intensity"])) * _up1(_up1(us[0], w, 1), h, 0)
+    return us, out
+
+
+def roundings_on_the_longest_path(n):
+    """Counted from the definition.  A downsample: the product of a tap (the weight itself is exact) and the 16 additions of the
+    accumulator chain, 17.  An upsample: product and sum in r0 / r1, product and sum in the result, 4.  A combine: the upsample,
+    spread * up and d + ..., 6.  The composite: the upsample, intensity * B and in + ..., 6.  The path goes down n - 1 levels, back
+    up n - 1 combines, and through the composite."""
+    down = 1 + 16
+    up = 2 + 2
+    return (n - 1) * down + (n - 1) * (up + 2) + (up + 2)
+
+
+@pytest.mark.parametrize("size,levels", [((37, 23), 1), ((37, 23), 2), ((64, 48), 5), ((17, 9), 8), ((1, 1), 3), ((5, 1), 4)], ids=str)
+def test_steps_2_to_5_against_binary64(size, levels):
+    """Every term is non-negative (a non-negative frame, d_0 >= 0, weights, spread and intensity >= 0), so nothing cancels and each
+    rounding adds at most a relative 2^-24: the relative bound is the rounding count of the longest dependency path times that."""
+    w, h = size
+    img = hdr_frame(w, h, 5)
+    d = cfg(levels=levels, intensity=0.3)
+    d0 = br.prefilter(img, d, d["exposure"])
+    assert (d0 >= 0).all() and d0[..., :3].max() > 1
+    ds, us = br.pyramid(d0, levels, d["spread"])
+    got = br.composite(img, us[0], d["intensity"])
+    want_u, want = pyramid64(d0, img, d)
+    bound = roundings_on_the_longest_path(levels) * U
+    assert bound == {1: 6, 2: 29, 5: 98, 8: 167, 3: 52, 4: 75}[levels] * U
+    for k in range(levels):
+        assert us[k].shape[:2] == want_u[k].shape[:2] and not us[k][..., 3].any()
+        err = np.abs(us[k][..., :3].astype(np.float64) - want_u[k])
+        assert (err <= bound * want_u[k]).all(), (k, float((err / np.maximum(want_u[k], 1e-300)).max()) / U)
+    err = np.abs(got[..., :3].astype(np.float64) - want)
+    print("steps 2-5", size, levels, "worst error in units of 2^-24:", float((err / np.maximum(want, 1e-300)).max()) / U, "bound", bound / U)
+    assert (err <= bound * want).all()
+    assert np.array_equal(got[..., 3], img[..., 3])
+
+
+def prefilter64(img, d, E, g_px=None):
+    """Step 1 in binary64 from the fp32 inputs -> (d_0 rgb, the bound on |fp32 d_0 - it|).
+
+    The bound, to first order in u = 2^-24, with A = L + T + K per source pixel (all non-negative):
+      L has 3 roundings on its path: |dL| <= 3u L.  T and K are one division each.  L - T: 3u L + u T + u |L - T| <= 4u A.
+      L - (T - K): 3u L + (u T + u K + u |T - K|) + u |..| <= 6u A; clamping to [0, K2] (dK2 <= 2u K) keeps that.
+      q = s s / K4 with s <= 2K: (2 s ds + u s^2) / 4K + 2u q <= 6u A + u K + 2u K <= 9u A.
+      h = max(q, L - T, 0): <= 9u A (a maximum moves by at most what its arguments move).
+      One sample's term wt (c h / max(L, 1e-6)): relative 3u (L) + u (/) + u (c m) + 6u (wt: 1 + L is 4u, 1 / is u, g kw is u) + u
+      (the product) = 12u, plus absolute wt (c / max(L, 1e-6)) 9u A from h: the cancellation in L - T, relative to L.
+      The sum of four: 4u; den: 5u per kw and 4 additions, 9u; the quotient: u.  So
+        |d d_0.c| <= sum_samples(wt (c / Lmax) 9u A) / den + 26u d_0.c,
+    used here as 10u and 27u: the rounding up pays for the terms of second order."""
+    img = np.asarray(img, np.float64)
+    h, w = img.shape[:2]
+    E = float(f32(E))
+    T, K = float(f32(d["threshold"])) / E, float(f32(d["knee"])) / E
+    W0, H0 = (w + 1) // 2, (h + 1) // 2
+    num, den, slack = np.zeros((H0, W0, 3)), np.zeros((H0, W0)), np.zeros((H0, W0, 3))
+    ys, xs = np.arange(H0), np.arange(W0)
+    for j in (0, 1):
+        py = np.minimum(2 * ys + j, h - 1)
+        for i in (0, 1):
+            px = np.minimum(2 * xs + i, w - 1)
+            c = img[py][:, px, :3]
+            L = c @ np.array([float(f32(0.2126)), float(f32(0.7152)), float(f32(0.0722))])
+            soft = np.clip(L - T + K, 0.0, 2.0 * K) ** 2 / (4.0 * K) if K > 0 else 0.0 * L
+            hh = np.maximum(np.maximum(soft, L - T), 0.0)
+            Lmax = np.maximum(L, float(f32(1e-6)))
+            kw = 1.0 / (1.0 + L) if d["flags"] & br.KARIS else np.ones_like(L)
+            wt = kw * (1.0 if g_px is None else g_px[py][:, px].astype(np.float64))
+            num += (wt * hh / Lmax)[..., None] * c
+            den += kw
+            slack += (wt * 10 * U * (L + T + K) / Lmax)[..., None] * c
+    d0 = num / den[..., None]
+    return d0, slack / den[..., None] + 27 * U * d0 + 1e-37
+
+
+@pytest.mark.parametrize("flags", [0, br.KARIS, br.GAINS, br.KARIS | br.GAINS])
+@pytest.mark.parametrize("knee", [0.5, 0.0])
+def test_step_1_against_binary64(flags, knee):
+    w, h = 41, 27
+    img = hdr_frame(w, h, 8)
+    d = cfg(flags=flags, knee=knee, threshold=1.5, exposure=3.0, gain_fovea=1.0, gain_middle=0.5, gain_periphery=0.125)
+    rng = np.random.default_rng(2)
+    fill = rng.choice([0, 1, 2, 4], (h, w))
+    got = br.prefilter(img, d, d["exposure"], fill, 0)
+    want, bound = prefilter64(img, d, d["exposure"], br.gains(fill, d, 0) if flags & br.GAINS else None)
+    err = np.abs(got[..., :3].astype(np.float64) - want)
+    T, K = 1.5 / 3.0, knee / 3.0
+    L = br.luminance(img)
+    assert (L == 0).any() and (L > T + K).any() and (K == 0 or ((L > T - K) & (L < T + K)).any())     # zero, the hard branch and the knee all occur
+    print("step 1", flags, knee, "worst error / bound:", float((err / bound).max()))
+    assert (err <= bound).all() and want.max() > 1
+    assert not got[..., 3].any()
+
+
+# ---- properties -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags", [0, br.KARIS, br.KARIS | br.GAINS])
+def test_a_frame_below_the_knee_comes_back_bit_for_bit(flags):
+    """Every L <= T - K: s = 0, q = 0, L - T < 0, so m = 0, every num is +0, the pyramid is +0 and c + intensity * 0 = c."""
+    w, h = 33, 18
+    d = cfg(flags=flags, threshold=1.0, knee=0.5, exposure=2.0, intensity=1e6, levels=4)
+    T, K, _, _ = br.constants(d, d["exposure"])
+    rng = np.random.default_rng(4)
+    img = (rng.random((h, w, 4)) * 0.24).astype(np.float32)
+    img[0, 0, :3] = T - K                                                       # L = (T - K) times the sum of the three coefficients, at most T - K
+    assert (br.luminance(img) <= T - K).all()
+    out = br.bloom(None, img, d, fill=np.ones((h, w), np.int64))
+    assert np.array_equal(out["color"].view(np.uint32), img.view(np.uint32))
+    assert not out["pyramid"].any()
+    img[2, 3, :3] = 1.0                                                         # (not vacuous: one pixel above it changes the frame)
+    assert not np.array_equal(br.bloom(None, img, d, fill=np.ones((h, w), np.int64))["color"], img)
+
+
+def test_a_constant_level_stays_constant_through_the_downsample():
+    """The 16 weights sum to exactly 1 (64 / 64) and every product weight * v is within u of exact, so the exact sum is within
+    16 * (1/64..9/64) u v -- in all u v -- of v, and the 15 real additions (the first adds to 0) of partial sums <= v add at most
+    u v each: |acc - v| <= 16 u v, also at the clamped edges, where the same taps repeat."""
+    for v in (1.0, 0.1, 3.3e4, 1e-3):
+        S = np.zeros((9, 13, 4), np.float32)
+        S[..., :3] = f32(v)
+        D = br.downsample(S)
+        assert D.shape == (5, 7, 4)
+        err = np.abs(D[..., :3].astype(np.float64) - float(f32(v)))
+        assert (err <= 16 * U * float(f32(v))).all(), v
+    S[..., :3] = 1.0                                                            # powers of two: exact
+    assert (br.downsample(S)[..., :3] == 1.0).all()
+
+
+def test_outputs_are_monotone_in_intensity():
+    img = hdr_frame(29, 17, 6)
+    prev = None
+    for intensity in (0.0, 1e-3, 0.05, 0.0500001, 0.3, 1.0, 50.0, 1e6):
+        out = br.bloom(None, img, cfg(intensity=intensity, levels=3))["color"]
+        if prev is not None:
+            assert (out >= prev).all(), intensity
+        else:
+            assert np.array_equal(out.view(np.uint32), img.view(np.uint32))          # c + 0 * B = c
+        prev = out
+    assert (prev > img)[..., :3].any()
+
+
+def test_karis_holds_an_outlier_down():
+    """A 2 x 2 block of three grey samples at 0.5 and one at 1e4, threshold far below both (m is about 1).  Without the outlier
+    d_0's luminance is 0.5 m(0.5).  With KARIS the outlier's share is kw(1e4) 1e4 / den with kw = 1 / (1 + L), den >=
+    3 / 1.5 = 2: below 1e4 / 1e4 / 2 = 0.5; the three others contribute at most (3 / 1.5) 0.5 / den <= 0.5.  So the ratio to the
+    block without the outlier is below (0.5 + 0.5) / (0.5 m(0.5)) = 2 / m(0.5), where a plain average gives about 5000."""
+    d = cfg(flags=br.KARIS, threshold=1e-3, knee=0.0, exposure=1.0, levels=1)
+    grey = lambda v: [v, v, v, 1.0]
+    base = np.array([[grey(0.5), grey(0.5)], [grey(0.5), grey(0.5)]], np.float32)
+    spike = base.copy()
+    spike[1, 0, :3] = 1e4
+    T, K, K2, K4 = br.constants(d, 1.0)
+    m_half = float(br.bright(base[0, 0, :3], T, K, K2, K4)[1])
+    assert 0.99 < m_half <= 1.0
+    lum = lambda img, dd: float(br.luminance(br.prefilter(img, dd, 1.0))[0, 0])
+    factor = 2.0 / m_half
+    assert lum(spike, d) < factor * lum(base, d)
+    assert lum(spike, dict(d, flags=0)) > 1000 * lum(base, dict(d, flags=0))           # the plain average does not
+
+
+def test_gains_of_zero_give_the_input_back():
+    img = hdr_frame(21, 14, 7)
+    rng = np.random.default_rng(1)
+    fill = rng.choice([0, 1, 2, 4], (14, 21))
+    d = cfg(flags=br.KARIS | br.GAINS, gain_fovea=0.0, gain_middle=0.0, gain_periphery=0.0, gain_uniform=0.0, intensity=10.0, levels=3)
+    for uniform in (0, 1):
+        out = br.bloom(None, img, d, fill=fill, uniform=uniform)
+        assert np.array_equal(out["color"].view(np.uint32), img.view(np.uint32))
+    assert not np.array_equal(br.bloom(None, img, dict(d, gain_middle=1.0), fill=fill)["color"], img)
+
+
+def test_gains_go_by_the_fill_of_the_last_writer():
+    d = cfg(gain_fovea=0.9, gain_middle=0.5, gain_periphery=0.25, gain_uniform=0.125)
+    fill = np.array([[0, 1, 2, 4]])
+    assert br.gains(fill, d, 0).tolist() == [[0.0, f32(0.9), 0.5, 0.25]]
+    assert br.gains(fill, d, 1).tolist() == [[0.0, 0.125, 0.125, 0.125]]
+
+
+def test_level_sizes_and_the_packed_layout():
+    assert br.level_sizes(17, 9, 8) == [(9, 5), (5, 3), (3, 2), (2, 1), (1, 1), (1, 1), (1, 1), (1, 1)]
+    assert br.level_sizes(1, 1, 3) == [(1, 1)] * 3
+    assert br.level_sizes(1, 6, 4) == [(1, 3), (1, 2), (1, 1), (1, 1)]
+    assert br.level_sizes(1920, 1080, 6) == [(960, 540), (480, 270), (240, 135), (120, 68), (60, 34), (30, 17)]
+    assert br.level_offsets(17, 9, 4) == [0, 45, 60, 66, 68]
+    out = br.bloom(None, hdr_frame(17, 9, 3), cfg(levels=8))
+    assert [u.shape[:2] for u in out["u"]] == [(h, w) for w, h in br.level_sizes(17, 9, 8)]
+    assert out["pyramid"].shape == (br.level_offsets(17, 9, 8)[-1], 4) == (72, 4)
+    assert np.array_equal(out["pyramid"][45:60], out["u"][1].reshape(-1, 4))
+    assert np.array_equal(out["u"][7], out["d"][7])                             # u_{n-1} = d_{n-1}
+    one = br.bloom(None, hdr_frame(1, 1, 3), cfg(levels=2))
+    assert one["pyramid"].shape == (2, 4)
+
+
+def test_the_upsample_takes_the_neighbour_on_its_own_side():
+    S = np.zeros((1, 3, 4), np.float32)
+    S[0, :, 0] = [0.0, 4.0, 8.0]
+    up = br.upsample(S, 5, 1)[0, :, 0]                                          # rows: by clamps onto ay, 0.75 v + 0.25 v
+    assert up.tolist() == [0.0, 1.0, 3.0, 5.0, 7.0]
+
+
+# ---- the ABI --------------------------------------------------------------------------------------------------------------------
+def test_the_mirror_has_the_documented_size():
+    assert C.sizeof(abi.BloomConfig) == 64
+    assert (abi.BloomConfig.exposure.offset, abi.BloomConfig.gain_fovea.offset, abi.BloomConfig._reserved.offset) == (16, 28, 44)
+    assert (abi.BLOOM_KARIS, abi.BLOOM_GAINS, abi.BLOOM_EXPOSURE_STATE, abi.BLOOM_MAX_LEVELS) == (br.KARIS, br.GAINS, br.EXPOSURE_STATE, br.MAX_LEVELS) == (1, 2, 4, 8)
+
+
+def test_bloom_defaults_are_the_documented_ones(so):
+    d = abi.BloomConfig()
+    C.memset(C.byref(d), 0xff, C.sizeof(d))
+    assert so.fovpt_bloom_defaults(C.byref(d)) == 0
+    assert (d.flags, d.levels) == (abi.BLOOM_KARIS, 6)
+    assert (d.threshold, d.knee, d.exposure, d.intensity, d.spread) == (1.0, 0.5, 16.0, f32(0.05), f32(0.7))
+    assert (d.gain_fovea, d.gain_middle, d.gain_periphery, d.gain_uniform) == (1.0, 1.0, 1.0, 1.0)
+    assert list(d._reserved) == [0] * 5
+    got = d.as_dict()
+    assert set(got) == set(br.DEFAULTS)
+    for k, v in br.DEFAULTS.items():
+        assert f32(got[k]) == f32(v), k
+    assert so.fovpt_bloom_defaults(None) == -1
+
+
+def test_bloom_rejects_a_null_context(so):
+    d, lp = abi.BloomConfig(), abi.LaunchParams()
+    so.fovpt_bloom_defaults(C.byref(d))
+    assert so.fovpt_bloom(None, C.byref(lp), C.byref(d), None, None, None) == -1
+    col, rgba = C.c_void_p(), C.c_void_p()
+    assert so.fovpt_bloom_buffers(None, C.byref(col), C.byref(rgba)) == -1
+
+
+def _args(hdr, name):
+    m = re.search(r"\bint %s\(([^;]*)\);" % name, hdr)
+    assert m, name
+    text = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+    return [" ".join(a.split()) for a in text.split(",")]
+
+
+def test_the_prototypes_agree_everywhere(so):
+    hdr = open(os.path.join(ROOT, "include", "fovpt.h")).read()
+    assert _args(hdr, "fovpt_bloom_defaults") == ["fovpt_bloom_config* out"]
+    assert _args(hdr, "fovpt_bloom") == ["fovpt_ctx* ctx", "const fovpt_launch_params* lp", "const fovpt_bloom_config* bc",
+                                         "const fovpt_float4* in_color", "fovpt_float4* out_color", "uint32_t* out_rgba"]
+    assert _args(hdr, "fovpt_bloom_buffers") == ["fovpt_ctx* ctx", "fovpt_float4** color", "uint32_t** rgba"]
+    vp = C.c_void_p
+    assert list(so.fovpt_bloom.argtypes) == [vp, C.POINTER(abi.LaunchParams), C.POINTER(abi.BloomConfig), vp, vp, vp]
+    names = subprocess.check_output(["nm", "-D", "--defined-only", lib.SO_PATH], text=True)
+    for sym in ("fovpt_bloom_defaults", "fovpt_bloom", "fovpt_bloom_buffers"):
+        assert re.search(r"\bT %s\b" % sym, names), sym
+        assert getattr(so, sym).restype == C.c_int
+    kernels = subprocess.check_output(["strings", lib.SO_PATH], text=True)
+    for k in ("k_bloom_prefilter", "k_bloom_down", "k_bloom_up", "k_bloom_composite"):
+        assert k in kernels, k
+
+
+def test_the_struct_mirror_matches_the_header(tmp_path):
+    names = [f[0] for f in abi.BloomConfig._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu", sizeof(fovpt_bloom_config));' + "".join(
+        'printf(" %%zu", offsetof(fovpt_bloom_config, %s));' % n for n in names) + "return 0;}\n"
+    exe = str(tmp_path / "layout")
+    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert got[0] == C.sizeof(abi.BloomConfig) == 64
+    assert got[1:] == [getattr(abi.BloomConfig, n).offset for n in names]
+
+
+def test_the_dropin_header_compiles():
+    src = '#include "SimplePathtracer.h"\nvoid f(SampleRenderer& s, fovpt_float4* m, uint32_t* h) { s.bloom(); fovpt_bloom_config bc; ' \
+          'fovpt_bloom_defaults(&bc); bc.flags = FOVPT_BLOOM_KARIS | FOVPT_BLOOM_GAINS | FOVPT_BLOOM_EXPOSURE_STATE; bc.levels = FOVPT_BLOOM_MAX_LEVELS; ' \
+          's.bloom(bc); s.bloom(bc, m); s.bloomPost(bc); fovpt_expose_config ec; fovpt_expose_defaults(&ec); s.exposeBloom(ec); ' \
+          's.downloadBloomColor(m); s.downloadBloomPixels(h); }\n'
+    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
