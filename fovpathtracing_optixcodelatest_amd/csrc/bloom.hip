@@ -99,7 +99,7 @@ __global__ __launch_bounds__(BLOOM_TX * BLOOM_TY) void k_bloom_prefilter(const F
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const float4 p = c[2 * j + i];
-            const float L = (0.2126f * p.x + 0.7152f * p.y) + 0.0722f * p.z;
+            const float L = luma(p.x, p.y, p.z);
             const float s = fmax2(0.0f, fmin2(L - TK, K2));
             const float q = K > 0.0f ? (s * s) / K4 : 0.0f;
             const float m = fmax2(fmax2(q, L - T), 0.0f) / fmax2(L, 1e-6f);
@@ -109,10 +109,7 @@ __global__ __launch_bounds__(BLOOM_TX * BLOOM_TY) void k_bloom_prefilter(const F
                 int wp = 0;
                 uint32_t wlx, wly;
                 if (!find_last_writer(fd, (uint32_t)min(2 * X + i, w - 1), (uint32_t)min(2 * Y + j, h - 1), wp, wlx, wly)) g = 0.0f;
-                else {
-                    const int f = fd.pass[wp].fill;
-                    g = a.uniform ? a.gain[3] : f == 4 ? a.gain[2] : f == 2 ? a.gain[1] : a.gain[0];
-                }
+                else g = by_level(a.gain, a.uniform, fd.pass[wp].fill);
             }
             const float wt = g * kw;
             nr = nr + wt * (p.x * m); ng = ng + wt * (p.y * m); nb = nb + wt * (p.z * m);
@@ -152,7 +149,7 @@ __global__ __launch_bounds__(BLOOM_TX * BLOOM_TY) void k_bloom_composite(int w, 
     const V3 B = up_texel(u0, (w + 1) >> 1, (h + 1) >> 1, x, y);
     const V3 o = v3(c.x + intensity * B.x, c.y + intensity * B.y, c.z + intensity * B.z);
     st_stream<FOVPT_BLOOM_OUT>(&out_color[idx], make_float4(o.x, o.y, o.z, c.w));
-    st_stream<FOVPT_BLOOM_OUT>(&out_rgba[idx], make_color(reinhard(o * 16.0f, 1.0f)));
+    st_stream<FOVPT_BLOOM_OUT>(&out_rgba[idx], resolved_rgba(o));      // (c.w kept and streaming stores: not store_resolved)
 }
 
 dim3 tile_grid(int W, int H)

@@ -20,9 +20,7 @@ namespace {
 #define EXPOSE_UNROLL 4                 // pixels a thread of the meter has in flight
 static_assert(EXPOSE_BINS <= FOVPT_EXPOSE_BLOCK && FOVPT_EXPOSE_BLOCK % EXPOSE_BINS == 0 && EXPOSE_BINS == 4 * FOVPT_WAVE, "a thread per bin, a wave per row");
 
-__device__ inline float luminance(const fovpt_float4& c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-
-// GAZE: a pixel's weight by the foveation level of its last writer (as the temporal step's history cap picks its level)
+// GAZE: a pixel's weight by the foveation level of its last writer (by_level, fovpt_pixel.h)
 template <bool GAZE>
 __global__ __launch_bounds__(FOVPT_EXPOSE_BLOCK) void k_expose_meter(const FrameDev fd, const ExposeArgs a, uint32_t npix,
                                                                      const fovpt_float4* __restrict__ in, uint32_t* __restrict__ rows)
@@ -38,7 +36,7 @@ __global__ __launch_bounds__(FOVPT_EXPOSE_BLOCK) void k_expose_meter(const Frame
 #pragma unroll
         for (int j = 0; j < EXPOSE_UNROLL; j++) {                     // the loads first: EXPOSE_UNROLL of them in flight
             const uint32_t idx = i0 + (uint32_t)j * stride;
-            L[j] = idx < npix ? luminance(in[idx]) : 0.0f;
+            L[j] = idx < npix ? luma(v3(in[idx])) : 0.0f;
         }
 #pragma unroll
         for (int j = 0; j < EXPOSE_UNROLL; j++) {
@@ -50,8 +48,7 @@ __global__ __launch_bounds__(FOVPT_EXPOSE_BLOCK) void k_expose_meter(const Frame
                 int wp = 0;
                 uint32_t wlx, wly;
                 if (!find_last_writer(fd, x, y, wp, wlx, wly)) continue;
-                const int f = fd.pass[wp].fill;
-                wgt = (uint32_t)(a.uniform ? a.weight[3] : f == 4 ? a.weight[2] : f == 2 ? a.weight[1] : a.weight[0]);
+                wgt = (uint32_t)by_level(a.weight, a.uniform, fd.pass[wp].fill);
                 if (!wgt) continue;
             }
             const int bin = min(max((int)(__float_as_uint(L[j]) >> 20) - 888, 0), EXPOSE_BINS - 1);

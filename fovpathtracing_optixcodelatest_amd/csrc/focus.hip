@@ -190,7 +190,7 @@ __global__ __launch_bounds__(FOCUS_TW * FOCUS_TH) void k_focus_gather(int w, int
         if (covering > 1) o = v3(nr / den, ng / den, nb / den);
     }
     out_color[idx] = fovpt_float4{o.x, o.y, o.z, ow};
-    out_rgba[idx] = make_color(reinhard(o * 16.0f, 1.0f));
+    out_rgba[idx] = resolved_rgba(o);                                    // (the pixel keeps its own w: not store_resolved)
 }
 
 }  // namespace

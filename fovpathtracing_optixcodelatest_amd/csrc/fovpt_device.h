@@ -257,6 +257,20 @@ void fovpt_launch_plan_scan_fill(hipStream_t st, uint32_t npix, uint32_t nblocks
 void fovpt_launch_gather_pack(hipStream_t st, uint32_t n, const uint32_t* idx, const uint32_t* frame, uint32_t* packed);
 void fovpt_launch_gather_unpack(hipStream_t st, int world, uint32_t stride, uint32_t total, const uint32_t* base, const uint32_t* idx,
                                 const uint32_t* gathered, uint32_t* frame);
+// The post-frame kernels' tiling: one thread per pixel, a block a 64 x 4 pixel tile (a wave is 64 consecutive pixels of a row).
+// fovpt_tile_grid: the grid that covers w x h; a thread finds its pixel with tile_pixel (fovpt_pixel.h).
+#define FOVPT_TILE_W 64
+#define FOVPT_TILE_H 4
+static_assert(FOVPT_TILE_W == FOVPT_WAVE && FOVPT_TILE_W * FOVPT_TILE_H == FOVPT_BLOCK, "a wave per tile row, a block per tile");
+inline dim3 fovpt_tile_grid(int w, int h) { return dim3((w + FOVPT_TILE_W - 1) / FOVPT_TILE_W, (h + FOVPT_TILE_H - 1) / FOVPT_TILE_H); }
+// The launches of an a-trous filter after its prep kernel: iteration i reads the ping-pong buffer i & 1 and writes the other;
+// step(i, last, in, out) launches it, `last` on the one that writes the outputs (fovpt_denoise, fovpt_variance_filter).
+template <class Step>
+inline void fovpt_atrous_iterate(int iterations, float4* b0, float4* b1, Step step)
+{
+    float4* buf[2] = {b0, b1};
+    for (int i = 0; i < iterations; i++) step(i, i + 1 == iterations, buf[i & 1], buf[(i + 1) & 1]);
+}
 // fovpt_denoise (denoise.hip): level map + demodulation, then `iterations` a-trous launches (the last writes the outputs).
 // I0 / I1: ping-pong float4 per pixel; level: one byte per pixel.
 struct DenoiseArgs {
@@ -425,7 +439,7 @@ struct VarianceArgs {
 void fovpt_launch_variance(hipStream_t st, const FrameDev& fd, const VarianceArgs& a, const fovpt_float4* in, const float4* pos, const float4* nrm,
                            const fovpt_float4* motion, const float4* hist_prev, float4* hist_out, fovpt_float4* out_variance);
 // fovpt_variance_filter (variance.hip): level map + demodulation + the initial variance, then `iterations` a-trous launches (the
-// last writes the outputs).  J0 / J1: ping-pong float4 per pixel (I, v); level: one byte per pixel, as the denoiser's.
+// last writes the outputs).  J0 / J1: ping-pong float4 per pixel (I, v); level: one byte per pixel (AtrousLevel, fovpt_post_pixel.h).
 struct VFilterArgs {
     int32_t n_pass[FOVPT_MAX_PASSES];   // iterations of the pixels whose last writer is pass p
     int32_t iterations;                 // max over the passes present

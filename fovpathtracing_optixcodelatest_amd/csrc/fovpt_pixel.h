@@ -1,6 +1,7 @@
-// fovpt_pixel.h -- device helpers shared by the wavefront kernels (wavefront.hip), the denoiser (denoise.hip) and the
-// reconstruction (reconstruct.hip): the fp32
-// vector type, the ring test, the last-writer search over a frame's passes and the resolve's tone map.
+// fovpt_pixel.h -- device helpers of anything that works on a frame's pixels: the wavefront kernels (wavefront.hip) and every
+// post-frame stage.  The fp32 vector type, a thread's pixel in the 64 x 4 tiling, the ring test, the resolve's tone map and its
+// store, Rec. 709 luminance, the last-writer search over a frame's passes and the pick of a per-level value by the writer's fill.
+// What only post-frame stages share is in fovpt_post_pixel.h.
 #pragma once
 
 #include "fovpt_device.h"
@@ -16,6 +17,7 @@ __device__ inline V3 v3(float x, float y, float z) { V3 r = {x, y, z}; return r;
 __device__ inline V3 v3(float s) { return v3(s, s, s); }
 __device__ inline V3 v3(const float4& a) { return v3(a.x, a.y, a.z); }
 __device__ inline V3 v3(const fovpt_float3& a) { return v3(a.x, a.y, a.z); }
+__device__ inline V3 v3(const fovpt_float4& a) { return v3(a.x, a.y, a.z); }
 __device__ inline V3 neg(const V3& a) { return v3(-a.x, -a.y, -a.z); }
 __device__ inline V3 operator+(const V3& a, const V3& b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ inline V3 operator-(const V3& a, const V3& b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -36,6 +38,17 @@ __device__ inline V3 lerp3(const V3& a, const V3& b, float t) { return a + t * (
 __device__ inline float sqr(float a) { return a * a; }
 __device__ inline float4 f4(const V3& a, float w) { return make_float4(a.x, a.y, a.z, w); }
 
+// The pixel (x, y) and its index of the calling thread where a block is a 64 x 4 tile of a w x h image (the grid: fovpt_tile_grid);
+// false outside the image.  T: the coordinates' type, int or uint32_t, as the kernel's arithmetic on them wants.
+template <class T>
+__device__ inline bool tile_pixel(int w, int h, T& x, T& y, uint32_t& idx)
+{
+    x = (T)(blockIdx.x * FOVPT_TILE_W + threadIdx.x % FOVPT_TILE_W);
+    y = (T)(blockIdx.y * FOVPT_TILE_H + threadIdx.x / FOVPT_TILE_W);
+    idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
+    return x < (T)w && y < (T)h;
+}
+
 // ring test of deviceProgram.cu:433-440 on the block's top-left pixel (uint arithmetic wraps)
 __device__ inline bool ring_alive(const FrameDev& fd, const PassDev& P, uint32_t lx, uint32_t ly, uint32_t& ix, uint32_t& iy)
 {
@@ -47,10 +60,11 @@ __device__ inline bool ring_alive(const FrameDev& fd, const PassDev& P, uint32_t
 }
 
 // ---- tone map of the resolve ---------------------------------------------------------------
+__device__ inline float luma(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }   // Rec. 709
+__device__ inline float luma(const V3& c) { return luma(c.x, c.y, c.z); }
 __device__ inline V3 reinhard(const V3& color, float white)                    // :126-131
 {
-    const float luminance = 0.2126f * color.x + 0.7152f * color.y + 0.0722f * color.z;
-    return div_vs(color * 1.0f, 1.0f + luminance / white);
+    return div_vs(color * 1.0f, 1.0f + luma(color) / white);
 }
 __device__ inline float srgb1(float c)                                          // cuda/helpers.h:35-43
 {
@@ -67,6 +81,13 @@ __device__ inline uint32_t make_color(const V3& c)                              
 {
     const V3 cc = clamp3(c, 0.0f, 1.0f);
     return quant8(srgb1(cc.x)) | (quant8(srgb1(cc.y)) << 8) | (quant8(srgb1(cc.z)) << 16) | (255u << 24);
+}
+// a post-frame stage's outputs as the resolve stores a pixel: the rgba8 of colour c, and c with w = 1 beside it
+__device__ inline uint32_t resolved_rgba(const V3& c) { return make_color(reinhard(c * 16.0f, 1.0f)); }
+__device__ inline void store_resolved(fovpt_float4* out_color, uint32_t* out_rgba, uint32_t idx, const V3& c)
+{
+    out_color[idx] = fovpt_float4{c.x, c.y, c.z, 1.0f};
+    out_rgba[idx] = resolved_rgba(c);
 }
 
 // ---- last writer of a pixel -----------------------------------------------------------------
@@ -154,6 +175,14 @@ __device__ inline bool find_last_writer(const FrameDev& fd, uint32_t x, uint32_t
         }
     }
     return false;
+}
+
+// a per-level value for a pixel whose last writer has fill f: t = {fill 1, fill 2, fill 4, FOV_OFF}
+template <class T>
+__device__ inline T by_level(const T (&t)[4], bool uniform, int f)
+{
+    const T t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];       // (all four read first: the pick is selects, no branch)
+    return uniform ? t3 : f == 4 ? t2 : f == 2 ? t1 : t0;
 }
 
 }  // namespace

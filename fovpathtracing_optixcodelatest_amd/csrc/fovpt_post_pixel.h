@@ -1,8 +1,13 @@
-// fovpt_post_pixel.h -- the per-pixel bodies of the reconstruction and of the temporal step, each in one place: k_reconstruct
-// (reconstruct.hip), k_temporal / k_temporal_motion (temporal.hip) and k_reconstruct_temporal (post_fused.hip) are these
-// functions between their loads of the input pixel and their stores.  Their definitions, operation by operation, are
-// tests/reconstruct_ref.py, tests/temporal_ref.py and tests/temporal_motion_ref.py; -ffp-contract=off keeps every product and
-// sum a separate binary32 op.
+// fovpt_post_pixel.h -- what the post-frame stages share beyond fovpt_pixel.h, each step in one place:
+//   - albedo demodulation and the edge-stopping terms (demod, div3, sq3, edge) of the denoiser, the reconstruction and the
+//     variance-guided filter;
+//   - the a-trous filters' level byte, B3 weights and clamped taps (denoise.hip, variance.hip);
+//   - the projection of a point or direction into another camera's pixels (temporal.hip, warp.hip);
+//   - the per-pixel bodies of the reconstruction and of the temporal step: k_reconstruct (reconstruct.hip), k_temporal /
+//     k_temporal_motion (temporal.hip) and k_reconstruct_temporal (post_fused.hip) are these functions between their loads of the
+//     input pixel and their stores.  Their definitions, operation by operation, are tests/reconstruct_ref.py,
+//     tests/temporal_ref.py and tests/temporal_motion_ref.py.
+// -ffp-contract=off keeps every product and sum a separate binary32 op.
 //
 // A pixel's own G-buffer entry reaches the bodies through an accessor (prim() / pos() / nrm()): GLazy reads memory where the
 // body asks, which is where the separate kernels always read it; GRegs holds an entry that the fused kernel has read once.
@@ -28,7 +33,8 @@ struct GRegs {
     __device__ inline float4 nrm() const { return nrm_; }
 };
 
-__device__ inline V3 demod(const V3& a)                                    // as the denoiser's
+// ---- demodulation and edge stopping ----------------------------------------------------------
+__device__ inline V3 demod(const V3& a)                                    // the albedo to divide by: never below 1 / 64, 1 where black
 {
     const float s = a.x + a.y + a.z;
     if (s > 0.0f) return v3(fmaxf(a.x, 1.0f / 64.0f), fmaxf(a.y, 1.0f / 64.0f), fmaxf(a.z, 1.0f / 64.0f));
@@ -36,6 +42,53 @@ __device__ inline V3 demod(const V3& a)                                    // as
 }
 __device__ inline float edge(float d) { const float t = fmaxf(0.0f, 1.0f - d); return t * t; }
 __device__ inline float sq3(const V3& a) { return a.x * a.x + a.y * a.y + a.z * a.z; }
+__device__ inline V3 div3(const V3& a, const V3& b) { return v3(a.x / b.x, a.y / b.y, a.z / b.z); }
+__device__ inline V3 div3(const V3& a, float s) { return v3(a.x / s, a.y / s, a.z / s); }       // (three divisions: not div_vs)
+
+// ---- a-trous filters ---------------------------------------------------------------------------
+// A pixel's level: the iterations n of its last writer's pass and log2 of that pass's fill (1, 2, 4), kept between the prep and
+// the step kernels as one byte, n in bits 0-3 and the shift in bits 4-7.
+struct AtrousLevel {
+    int n, fill_shift;
+    __device__ inline uint8_t code() const { return (uint8_t)(n | (fill_shift << 4)); }
+};
+__device__ inline AtrousLevel atrous_decode(int code) { return AtrousLevel{code & 15, code >> 4}; }
+// the level of pixel (x, y): n_pass[p] iterations where pass p writes it last, 0 where no pass does
+__device__ inline AtrousLevel atrous_level(const FrameDev& fd, const int32_t* n_pass, uint32_t x, uint32_t y)
+{
+    int wp = 0;
+    AtrousLevel l = {0, 0};
+    uint32_t wlx, wly;
+    if (find_last_writer(fd, x, y, wp, wlx, wly)) {
+        l.n = n_pass[wp];
+        l.fill_shift = 31 - __clz(fd.pass[wp].fill);
+    }
+    return l;
+}
+// B3-spline weight of tap d = -2 .. 2 along an axis: b3_weight where d is a constant once its loop is unrolled, b3_weight_row where
+// it is a run-time value (compares: indexing the table would be a memory lookup per tap row)
+__device__ inline float b3_weight(int d)
+{
+    const float H[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    return H[d + 2];
+}
+__device__ inline float b3_weight_row(int d) { return d == 0 ? 3.0f / 8.0f : (d == 1 || d == -1) ? 1.0f / 4.0f : 1.0f / 16.0f; }
+// tap d at step s from coordinate p of an axis of n pixels, clamped to the image
+__device__ inline int tap_coord(int p, int s, int d, int n) { return min(max(p + s * d, 0), n - 1); }
+
+// ---- projection into another camera ----------------------------------------------------------
+// v (a point relative to that camera's eye, or a direction) in the camera whose inverse [U V W]^-1 has the rows inv: its depth
+// az along W and, meaningful where az > 0, its position (px, py) in pixels of an fw x fh image
+__device__ inline void project(const float* inv, const V3& v, float fw, float fh, float& az, float& px, float& py)
+{
+    const float ax = (inv[0] * v.x + inv[1] * v.y) + inv[2] * v.z;
+    const float ay = (inv[3] * v.x + inv[4] * v.y) + inv[5] * v.z;
+    az = (inv[6] * v.x + inv[7] * v.y) + inv[8] * v.z;
+    px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
+    py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
+}
+
+// ---- reconstruction and temporal step --------------------------------------------------------
 
 // whether the reconstruction is on for a pixel whose last writer has fill f
 __device__ inline bool reconstruct_level_on(const ReconstructArgs& a, int f) { return f > 1 && (a.levels & (f == 2 ? 1 : 2)); }
@@ -80,18 +133,17 @@ __device__ inline bool reconstruct_pixel(const FrameDev& fd, const ReconstructAr
                 }
                 const float wt = ((hx * hy) * wn) * wz;
                 const fovpt_float4 cq = in[q];
-                V3 Iq = v3(cq.x, cq.y, cq.z);
+                V3 Iq = v3(cq);
                 if (a.remodulate) {
                     const fovpt_float4 aq = albedo[q];
-                    const V3 D = demod(v3(aq.x, aq.y, aq.z));
-                    Iq = v3(Iq.x / D.x, Iq.y / D.y, Iq.z / D.z);
+                    Iq = div3(Iq, demod(v3(aq)));
                 }
                 sw = sw + wt;
                 acc = acc + Iq * wt;
             }
         }
         if (sw > 0.0f) {
-            o = v3(acc.x / sw, acc.y / sw, acc.z / sw);
+            o = div3(acc, sw);
             if (a.remodulate) o = o * demod(v3(g.alb[idx]));
             return true;
         }
@@ -103,7 +155,7 @@ __device__ inline bool reconstruct_pixel(const FrameDev& fd, const ReconstructAr
 __device__ inline int history_cap(const FrameDev& fd, const TemporalArgs& a, bool found, int wp)
 {
     if (!found) return 1;
-    const int f = fd.pass[wp].fill;
+    const int f = fd.pass[wp].fill;                                         // (not by_level: with it k_reconstruct_temporal needs 4 more SGPRs)
     return a.uniform ? a.cap[3] : f == 4 ? a.cap[2] : f == 2 ? a.cap[1] : a.cap[0];
 }
 
@@ -144,7 +196,7 @@ __device__ inline void history_taps(const FrameDev& fd, const TemporalArgs& a, c
         sn = sn + hq.w * wt[k];
     }
     if (sw >= 1.0f / 64.0f) {
-        H = v3(acc.x / sw, acc.y / sw, acc.z / sw);
+        H = div3(acc, sw);
         nh = sn / sw;
     }
 }
@@ -161,17 +213,12 @@ __device__ inline void temporal_history(const FrameDev& fd, const TemporalArgs& 
         V3 v;
         if (!miss_p) v = Xp - v3(a.eye_prev[0], a.eye_prev[1], a.eye_prev[2]);
         else v = pixel_ray(fd, x, y);
-        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
-        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
-        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
-        if (az > 0.0f) {
-            const float fw = (float)fd.w, fh = (float)fd.h;
-            const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
-            const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
-            if (px >= -1.0f && px < fw && py >= -1.0f && py < fh) {        // (NaN fails): x0 in [-1, w - 1], y0 in [-1, h - 1]
-                const V3 Np = v3(own.nrm());
-                history_taps(fd, a, gp, hist_prev, px, py, miss_p, Xp, Np, a.depth_tol * xp4.w, H, nh);
-            }
+        const float fw = (float)fd.w, fh = (float)fd.h;
+        float az, px, py;
+        project(a.inv, v, fw, fh, az, px, py);
+        if (az > 0.0f && px >= -1.0f && px < fw && py >= -1.0f && py < fh) {   // (NaN fails): x0 in [-1, w - 1], y0 in [-1, h - 1]
+            const V3 Np = v3(own.nrm());
+            history_taps(fd, a, gp, hist_prev, px, py, miss_p, Xp, Np, a.depth_tol * xp4.w, H, nh);
         }
     }
 }
@@ -226,17 +273,12 @@ __device__ inline void temporal_motion_history(const FrameDev& fd, const Tempora
             }
             v = Xp - v3(a.eye_prev[0], a.eye_prev[1], a.eye_prev[2]);
         } else v = pixel_ray(fd, x, y);
-        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
-        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
-        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
-        if (az > 0.0f) {
-            const float fw = (float)fd.w, fh = (float)fd.h;
-            const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
-            const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
-            if (px >= -1.0f && px < fw && py >= -1.0f && py < fh) {        // (NaN fails): x0 in [-1, w - 1], y0 in [-1, h - 1]
-                mv = make_float4(px - (float)x, py - (float)y, az, 1.0f);
-                if (cap > 1) history_taps(fd, a, gp, hist_prev, px, py, miss_p, Xp, Np, a.depth_tol * xp4.w, H, nh);
-            }
+        const float fw = (float)fd.w, fh = (float)fd.h;
+        float az, px, py;
+        project(a.inv, v, fw, fh, az, px, py);
+        if (az > 0.0f && px >= -1.0f && px < fw && py >= -1.0f && py < fh) {   // (NaN fails): x0 in [-1, w - 1], y0 in [-1, h - 1]
+            mv = make_float4(px - (float)x, py - (float)y, az, 1.0f);
+            if (cap > 1) history_taps(fd, a, gp, hist_prev, px, py, miss_p, Xp, Np, a.depth_tol * xp4.w, H, nh);
         }
     }
 }
@@ -249,13 +291,12 @@ __device__ inline void temporal_blend(const fovpt_float4& c, const V3& H, float 
     if (n == 1.0f) {                                                       // first step, disocclusion, cap 1: the input, bit for bit
         out_color[idx] = c;
         hist_out[idx] = make_float4(c.x, c.y, c.z, 1.0f);
-        out_rgba[idx] = make_color(reinhard(v3(c.x, c.y, c.z) * 16.0f, 1.0f));
+        out_rgba[idx] = resolved_rgba(v3(c));                              // (c keeps its own w: not store_resolved)
         return;
     }
-    const V3 o = lerp3(H, v3(c.x, c.y, c.z), 1.0f / n);
-    out_color[idx] = fovpt_float4{o.x, o.y, o.z, 1.0f};
+    const V3 o = lerp3(H, v3(c), 1.0f / n);
     hist_out[idx] = f4(o, n);
-    out_rgba[idx] = make_color(reinhard(o * 16.0f, 1.0f));
+    store_resolved(out_color, out_rgba, idx, o);
 }
 
 }  // namespace

@@ -107,9 +107,8 @@ template <int FILTER, bool MONO>
 __global__ __launch_bounds__(FOVPT_BLOCK) void k_lens(int w, int h, const LensArgs a, const fovpt_float4* __restrict__ in,
                                                       fovpt_float4* __restrict__ out_color, uint32_t* __restrict__ out_rgba)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)w || y >= (uint32_t)h) return;
-    const uint32_t p = y * (uint32_t)w + x;
+    uint32_t x, y, p;
+    if (!tile_pixel(w, h, x, y, p)) return;
     const float nx = (float)(2u * x + 1u) / (float)w - 1.0f;
     const float ny = (float)(2u * y + 1u) / (float)h - 1.0f;
     const float px = (nx - a.center[0]) * a.scale[0];
@@ -130,13 +129,13 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_lens(int w, int h, const LensAr
     }
     out_color[p] = fovpt_float4{o[0], o[1], o[2], o[3]};
     const V3 c = v3(o[0], o[1], o[2]);
-    out_rgba[p] = a.encode == FOVPT_LENS_ENCODE_RESOLVE ? make_color(reinhard(c * 16.0f, 1.0f)) : make_color(c);
+    out_rgba[p] = a.encode == FOVPT_LENS_ENCODE_RESOLVE ? resolved_rgba(c) : make_color(c);   // (o[3] is the border's or 1: not store_resolved)
 }
 
 template <int FILTER>
 void launch(hipStream_t st, int w, int h, const LensArgs& a, const fovpt_float4* in, fovpt_float4* out_color, uint32_t* out_rgba)
 {
-    const dim3 grid((w + 63) / 64, (h + 3) / 4);
+    const dim3 grid = fovpt_tile_grid(w, h);
     if (a.mono) hipLaunchKernelGGL((k_lens<FILTER, true>), grid, dim3(FOVPT_BLOCK), 0, st, w, h, a, in, out_color, out_rgba);
     else hipLaunchKernelGGL((k_lens<FILTER, false>), grid, dim3(FOVPT_BLOCK), 0, st, w, h, a, in, out_color, out_rgba);
 }

@@ -22,9 +22,8 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_reconstruct_temporal(const Fram
                                                                       float4* __restrict__ hist_out, fovpt_float4* __restrict__ out_color,
                                                                       uint32_t* __restrict__ out_rgba)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
+    uint32_t x, y, idx;
+    if (!tile_pixel(fd.w, fd.h, x, y, idx)) return;
     int wp = 0;
     uint32_t wlx, wly;
     const bool found = find_last_writer(fd, x, y, wp, wlx, wly);           // the reconstruction's level and anchor, the step's cap
@@ -54,7 +53,7 @@ void fovpt_launch_reconstruct_temporal(hipStream_t st, const FrameDev& fd, const
                                        const TemporalMotionArgs* m, const fovpt_float4* in, const fovpt_float4* albedo, GBufferDev g,
                                        GBufferDev gp, const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
+    const dim3 grid = fovpt_tile_grid(fd.w, fd.h);
     if (m) hipLaunchKernelGGL(k_reconstruct_temporal<true>, grid, dim3(FOVPT_BLOCK), 0, st, fd, ra, ta, *m, in, albedo, g, gp, hist_prev, hist_out,
                               out_color, out_rgba);
     else {

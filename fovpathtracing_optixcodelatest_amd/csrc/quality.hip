@@ -37,6 +37,7 @@ static_assert(Q_TILE == 32 && Q_BLOCK == 256 && Q_BLOCK * 4 == Q_TILE * Q_TILE, 
 static_assert(Q_COLS <= Q_BLOCK && Q_COLS <= 3 * FOVPT_WAVE && Q_COLS + 1 <= FOVPT_QUALITY_SUM_BLOCK, "a thread per column");
 static_assert(COL_RING_SQ_ERR + Q_RINGS == Q_COLS && COL_MAX_ERR + Q_CLASSES <= FOVPT_WAVE, "the columns");
 
+// (not by_level, fovpt_pixel.h: a class table picked with it changes the machine code of every k_quality_tile)
 __device__ inline uint32_t quality_class(const FrameDev& fd, bool uniform, uint32_t x, uint32_t y)
 {
     int wp = 0;

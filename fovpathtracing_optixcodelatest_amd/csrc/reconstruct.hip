@@ -19,12 +19,12 @@ namespace {
 
 __global__ __launch_bounds__(FOVPT_BLOCK) void k_gbuffer_rays(const FrameDev fd, RayQueue q, Counters* __restrict__ cnt)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    uint32_t x, y, idx;
+    const bool inside = tile_pixel(fd.w, fd.h, x, y, idx);
     const uint32_t n = (uint32_t)fd.w * (uint32_t)fd.h;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < FOVPT_SHARDS)      // every ray in shard 0 of iteration 0's queue
         cnt->shard[threadIdx.x][FOVPT_CNT_Q(0)] = threadIdx.x == 0 ? n : 0u;
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
+    if (!inside) return;
     const float dx = 2.0f * (((float)x + 0.5f) / (float)fd.w) - 1.0f;       // generate_rays with jx = jy = 0.5
     const float dy = 2.0f * (((float)y + 0.5f) / (float)fd.h) - 1.0f;
     const V3 U = v3(fd.U[0], fd.U[1], fd.U[2]), V = v3(fd.V[0], fd.V[1], fd.V[2]), W = v3(fd.W[0], fd.W[1], fd.W[2]);
@@ -36,9 +36,8 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_gbuffer_rays(const FrameDev fd,
 __global__ __launch_bounds__(FOVPT_BLOCK) void k_gbuffer_fill(const FrameDev fd, SceneView sc, RayQueue q, const float4* __restrict__ hits,
                                                               GBufferDev g)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
+    uint32_t x, y, idx;
+    if (!tile_pixel(fd.w, fd.h, x, y, idx)) return;
     const float4 hit = hits[idx];
     const uint32_t tpos = __float_as_uint(hit.w);
     if (tpos == 0xffffffffu) {
@@ -75,41 +74,36 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_reconstruct(const FrameDev fd, 
                                                              const fovpt_float4* __restrict__ albedo, GBufferDev g,
                                                              fovpt_float4* __restrict__ out_color, uint32_t* __restrict__ out_rgba)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
+    uint32_t x, y, idx;
+    if (!tile_pixel(fd.w, fd.h, x, y, idx)) return;
     const fovpt_float4 c = in[idx];
     int wp = 0;
     uint32_t wlx, wly;
     if (find_last_writer(fd, x, y, wp, wlx, wly)) {
         V3 o;
         if (reconstruct_pixel(fd, a, in, albedo, g, GLazy{g, idx}, x, y, idx, wp, wlx, wly, o)) {   // (fovpt_post_pixel.h)
-            out_color[idx] = fovpt_float4{o.x, o.y, o.z, 1.0f};
-            out_rgba[idx] = make_color(reinhard(o * 16.0f, 1.0f));
+            store_resolved(out_color, out_rgba, idx, o);
             return;
         }
     }
     out_color[idx] = c;                                                     // unchanged, bit for bit
-    out_rgba[idx] = make_color(reinhard(v3(c.x, c.y, c.z) * 16.0f, 1.0f));
+    out_rgba[idx] = resolved_rgba(v3(c));                                   // (c keeps its own w: not store_resolved)
 }
 
 }  // namespace
 
 void fovpt_launch_gbuffer_rays(hipStream_t st, const FrameDev& fd, RayQueue q, Counters* cnt)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_gbuffer_rays, grid, dim3(FOVPT_BLOCK), 0, st, fd, q, cnt);
+    hipLaunchKernelGGL(k_gbuffer_rays, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, q, cnt);
 }
 
 void fovpt_launch_gbuffer_fill(hipStream_t st, const FrameDev& fd, SceneView sc, RayQueue q, const float4* hit, GBufferDev g)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_gbuffer_fill, grid, dim3(FOVPT_BLOCK), 0, st, fd, sc, q, hit, g);
+    hipLaunchKernelGGL(k_gbuffer_fill, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, sc, q, hit, g);
 }
 
 void fovpt_launch_reconstruct(hipStream_t st, const FrameDev& fd, const ReconstructArgs& a, const fovpt_float4* in, const fovpt_float4* albedo,
                               GBufferDev g, fovpt_float4* out_color, uint32_t* out_rgba)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_reconstruct, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, in, albedo, g, out_color, out_rgba);
+    hipLaunchKernelGGL(k_reconstruct, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, in, albedo, g, out_color, out_rgba);
 }

@@ -22,9 +22,8 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_temporal(const FrameDev fd, Tem
                                                           const float4* __restrict__ hist_prev, float4* __restrict__ hist_out,
                                                           fovpt_float4* out_color, uint32_t* __restrict__ out_rgba)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
+    uint32_t x, y, idx;
+    if (!tile_pixel(fd.w, fd.h, x, y, idx)) return;
     const fovpt_float4 c = in[idx];
     int wp = 0;
     uint32_t wlx, wly;
@@ -43,9 +42,8 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_temporal_motion(const FrameDev 
                                                                  float4* __restrict__ hist_out, fovpt_float4* out_color,
                                                                  uint32_t* __restrict__ out_rgba)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
+    uint32_t x, y, idx;
+    if (!tile_pixel(fd.w, fd.h, x, y, idx)) return;
     const fovpt_float4 c = in[idx];
     int wp = 0;
     uint32_t wlx, wly;
@@ -65,13 +63,12 @@ void fovpt_launch_temporal_motion(hipStream_t st, const FrameDev& fd, const Temp
                                   GBufferDev g, GBufferDev gp, const float4* hist_prev, float4* hist_out, fovpt_float4* out_color,
                                   uint32_t* out_rgba)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_temporal_motion, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, m, in, g, gp, hist_prev, hist_out, out_color, out_rgba);
+    hipLaunchKernelGGL(k_temporal_motion, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, m, in, g, gp, hist_prev, hist_out,
+                       out_color, out_rgba);
 }
 
 void fovpt_launch_temporal(hipStream_t st, const FrameDev& fd, const TemporalArgs& a, const fovpt_float4* in, GBufferDev g, GBufferDev gp,
                            const float4* hist_prev, float4* hist_out, fovpt_float4* out_color, uint32_t* out_rgba)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_temporal, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, in, g, gp, hist_prev, hist_out, out_color, out_rgba);
+    hipLaunchKernelGGL(k_temporal, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, in, g, gp, hist_prev, hist_out, out_color, out_rgba);
 }

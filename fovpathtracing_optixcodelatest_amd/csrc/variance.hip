@@ -5,7 +5,7 @@
 //   k_variance_moments  per pixel: luminance and its square, the four bilinear taps of the previous moment history where the motion
 //                       vector lands (kept by class and depth), the blend by history length, the variance -- from the moments, or
 //                       from a (2R + 1)^2 window of the current frame while the history is short -- and the new history record
-//   k_vfilter_prep      level map (as k_denoise_prep's), demodulation by the G-buffer's albedo, J = (I, rel * lum(I)^2); pixels that are
+//   k_vfilter_prep      level map (atrous_level, fovpt_post_pixel.h), demodulation by the G-buffer's albedo, J = (I, rel * lum(I)^2); pixels that are
 //                       not filtered get their output here (C itself, bit for bit)
 //   k_vfilter_step      one iteration over the pixels with i < n: the 3 x 3 prefilter of the variance, 5 x 5 taps at step fill * 2^i
 //                       with B3-spline weights and luminance / normal / plane-distance edge stopping, the filtered variance; the
@@ -15,16 +15,9 @@
 // is tests/variance_ref.py; -ffp-contract=off keeps every product and sum of it a separate binary32 op.
 #include "fovpt_device.h"
 #include "fovpt_pixel.h"
-#include "fovpt_post_pixel.h"      // demod, edge, sq3: the reconstruction's
+#include "fovpt_post_pixel.h"      // demod, edge, sq3, the a-trous level byte, weights and taps
 
 namespace {
-
-__device__ inline float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-__device__ inline void write_out(fovpt_float4* out_color, uint32_t* out_rgba, uint32_t idx, const V3& c)
-{
-    out_color[idx] = fovpt_float4{c.x, c.y, c.z, 1.0f};
-    out_rgba[idx] = make_color(reinhard(c * 16.0f, 1.0f));
-}
 
 // The spatial estimate's sums over the (2R + 1)^2 window of pixel (x, y), stepping by the fill f: one tap row per trip, its loads in
 // flight together (R is a template argument so that the row unrolls)
@@ -35,11 +28,10 @@ __device__ inline void window(const Window& d, const fovpt_float4* __restrict__ 
 {
 #pragma unroll 1
     for (int j = -R; j <= R; j++) {
-        const int qy = min(max(d.y + d.f * j, 0), d.h - 1);
+        const int qy = tap_coord(d.y, d.f, j, d.h);
 #pragma unroll
         for (int i = -R; i <= R; i++) {
-            const int qx = min(max(d.x + d.f * i, 0), d.w - 1);
-            const uint32_t q = (uint32_t)qy * (uint32_t)d.w + (uint32_t)qx;
+            const uint32_t q = (uint32_t)qy * (uint32_t)d.w + (uint32_t)tap_coord(d.x, d.f, i, d.w);
             const fovpt_float4 cq = in[q];
             const float4 xq4 = pos[q];
             float wq = 1.0f;
@@ -50,7 +42,7 @@ __device__ inline void window(const Window& d, const fovpt_float4* __restrict__ 
                     if (!(sq3(Nq - d.Np) <= d.ntol) || !(fabsf(dot(d.Np, v3(xq4) - d.Xp)) <= d.ztol)) wq = 0.0f;
                 }
             }
-            const float lq = lum(cq.x, cq.y, cq.z);
+            const float lq = luma(v3(cq));
             s0 = s0 + wq;
             s1 = s1 + wq * lq;
             s2 = s2 + wq * (lq * lq);
@@ -63,12 +55,11 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_variance_moments(const FrameDev
                                                                   const fovpt_float4* __restrict__ motion, const float4* __restrict__ hist_prev,
                                                                   float4* __restrict__ hist_out, fovpt_float4* __restrict__ out)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int w = fd.w, h = fd.h;
-    if (x >= w || y >= h) return;
-    const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
-    const fovpt_float4 c = in[idx];
-    const float l = lum(c.x, c.y, c.z), l2 = l * l;
+    int x, y;
+    uint32_t idx;
+    if (!tile_pixel(w, h, x, y, idx)) return;
+    const float l = luma(v3(in[idx])), l2 = l * l;
     const float4 xp4 = pos[idx];
     const bool miss_p = xp4.w < 0.0f;
     const V3 Xp = v3(xp4);
@@ -131,29 +122,21 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_variance_moments(const FrameDev
     out[idx] = fovpt_float4{var / (mean * mean + 1e-8f), var, mean, n};
 }
 
-// level byte: iterations n in bits 0-3, log2(fill) in bits 4-7 (fill 1, 2, 4), as k_denoise_prep's
 __global__ __launch_bounds__(FOVPT_BLOCK) void k_vfilter_prep(const FrameDev fd, VFilterArgs a, const fovpt_float4* __restrict__ color,
                                                               const fovpt_float4* __restrict__ variance, const float4* __restrict__ albedo,
                                                               float4* __restrict__ J0, uint8_t* __restrict__ level, fovpt_float4* __restrict__ out_color,
                                                               uint32_t* __restrict__ out_rgba)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= (uint32_t)fd.w || y >= (uint32_t)fd.h) return;
-    const uint32_t idx = y * (uint32_t)fd.w + x;
-    int wp = 0, n = 0, sh = 0;
-    uint32_t wlx, wly;
-    if (find_last_writer(fd, x, y, wp, wlx, wly)) {
-        n = a.n_pass[wp];
-        sh = 31 - __clz(fd.pass[wp].fill);
-    }
-    level[idx] = (uint8_t)(n | (sh << 4));
-    const fovpt_float4 c = color[idx];
-    const V3 C = v3(c.x, c.y, c.z);
+    uint32_t x, y, idx;
+    if (!tile_pixel(fd.w, fd.h, x, y, idx)) return;
+    const AtrousLevel l = atrous_level(fd, a.n_pass, x, y);
+    level[idx] = l.code();
+    const V3 C = v3(color[idx]);
     const V3 D = a.demodulate ? demod(v3(albedo[idx])) : v3(1.0f);
-    const V3 I = v3(C.x / D.x, C.y / D.y, C.z / D.z);
-    const float lI = lum(I.x, I.y, I.z);
+    const V3 I = v3(C.x / D.x, C.y / D.y, C.z / D.z);                      // (not div3: with this D it orders the kernel's code differently)
+    const float lI = luma(I);
     J0[idx] = f4(I, variance[idx].x * (lI * lI));
-    if (n == 0) write_out(out_color, out_rgba, idx, C);
+    if (l.n == 0) store_resolved(out_color, out_rgba, idx, C);
 }
 
 template <bool LAST>
@@ -163,27 +146,27 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_vfilter_step(int w, int h, int 
                                                               const float4* __restrict__ albedo, float4* __restrict__ Jout,
                                                               fovpt_float4* __restrict__ out_color, uint32_t* __restrict__ out_rgba)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    const uint32_t idx = (uint32_t)y * (uint32_t)w + (uint32_t)x;
-    const int code = level[idx], n = code & 15;
+    int x, y;
+    uint32_t idx;
+    if (!tile_pixel(w, h, x, y, idx)) return;
+    const AtrousLevel l = atrous_decode(level[idx]);
     const float4 Jp = Jin[idx];
     const V3 Ip = v3(Jp);
-    if (it >= n) {                                       // done (or never filtered): keep J; the last launch remodulates
+    if (it >= l.n) {                                     // done (or never filtered): keep J; the last launch remodulates
         if (!LAST) Jout[idx] = Jp;
-        else if (n >= 1) write_out(out_color, out_rgba, idx, demodulate ? Ip * demod(v3(albedo[idx])) : Ip);
+        else if (l.n >= 1) store_resolved(out_color, out_rgba, idx, demodulate ? Ip * demod(v3(albedo[idx])) : Ip);
         return;
     }
-    const int f = 1 << (code >> 4);
+    const int f = 1 << l.fill_shift;
     const int s = f << it;                               // fill * 2^it: a block-filled pixel never taps its own copies
     // the variance, prefiltered over the 3 x 3 neighbours one fill away
     float g = 0.0f;
 #pragma unroll
     for (int j = -1; j <= 1; j++) {
-        const int qy = min(max(y + f * j, 0), h - 1);
+        const int qy = tap_coord(y, f, j, h);
 #pragma unroll
         for (int i = -1; i <= 1; i++) {
-            const int qx = min(max(x + f * i, 0), w - 1);
+            const int qx = tap_coord(x, f, i, w);
             const float G = (i == 0 ? 0.5f : 0.25f) * (j == 0 ? 0.5f : 0.25f);       // 1/4, 1/8, 1/16: exact
             g = g + G * Jin[(uint32_t)qy * (uint32_t)w + (uint32_t)qx].w;
         }
@@ -193,22 +176,20 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_vfilter_step(int w, int h, int 
     const bool miss_p = xp4.w < 0.0f;
     const V3 Xp = v3(xp4), Np = v3(nrm[idx]);
     const float tp2 = xp4.w * xp4.w;
-    const float lp = lum(Ip.x, Ip.y, Ip.z);
-    const float H[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float lp = luma(Ip);
     float sw = 0.0f, sv = 0.0f;
     V3 acc = v3(0.0f);
     // one tap row per trip (its 15 loads in flight together), as k_denoise_step
 #pragma unroll 1
     for (int dy = -2; dy <= 2; dy++) {
-        const int qy = min(max(y + s * dy, 0), h - 1);
-        const float hy = dy == 0 ? 3.0f / 8.0f : (dy == 1 || dy == -1) ? 1.0f / 4.0f : 1.0f / 16.0f;
+        const int qy = tap_coord(y, s, dy, h);
+        const float hy = b3_weight_row(dy);
 #pragma unroll
         for (int dx = -2; dx <= 2; dx++) {
-            const int qx = min(max(x + s * dx, 0), w - 1);
-            const uint32_t q = (uint32_t)qy * (uint32_t)w + (uint32_t)qx;
+            const uint32_t q = (uint32_t)qy * (uint32_t)w + (uint32_t)tap_coord(x, s, dx, w);
             const float4 Jq = Jin[q], xq4 = pos[q], nq4 = nrm[q];
             const V3 Iq = v3(Jq);
-            const float d = lum(Iq.x, Iq.y, Iq.z) - lp;
+            const float d = luma(Iq) - lp;
             const float wl = edge((d * d) * kl);
             const bool miss_q = xq4.w < 0.0f;
             float wn = 1.0f, wz = 1.0f;
@@ -218,15 +199,15 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_vfilter_step(int w, int h, int 
                 const float dz = dot(Np, v3(xq4) - Xp);
                 wz = edge(((dz * dz) * inv_z) / tp2);
             }
-            const float wt = (((H[dx + 2] * hy) * wl) * wn) * wz;
+            const float wt = (((b3_weight(dx) * hy) * wl) * wn) * wz;
             sw = sw + wt;
             acc = acc + Iq * wt;
             sv = sv + (wt * wt) * Jq.w;
         }
     }
-    const V3 I = v3(acc.x / sw, acc.y / sw, acc.z / sw);   // sw >= 9/64: the centre tap
+    const V3 I = div3(acc, sw);                          // sw >= 9/64: the centre tap
     if (!LAST) Jout[idx] = f4(I, sv / (sw * sw));
-    else write_out(out_color, out_rgba, idx, demodulate ? I * demod(v3(albedo[idx])) : I);
+    else store_resolved(out_color, out_rgba, idx, demodulate ? I * demod(v3(albedo[idx])) : I);
 }
 
 }  // namespace
@@ -234,22 +215,17 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_vfilter_step(int w, int h, int 
 void fovpt_launch_variance(hipStream_t st, const FrameDev& fd, const VarianceArgs& a, const fovpt_float4* in, const float4* pos, const float4* nrm,
                            const fovpt_float4* motion, const float4* hist_prev, float4* hist_out, fovpt_float4* out_variance)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_variance_moments, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, in, pos, nrm, motion, hist_prev, hist_out, out_variance);
+    hipLaunchKernelGGL(k_variance_moments, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, in, pos, nrm, motion, hist_prev,
+                       hist_out, out_variance);
 }
 
 void fovpt_launch_vfilter(hipStream_t st, const FrameDev& fd, const VFilterArgs& a, const fovpt_float4* color, const fovpt_float4* variance,
                           GBufferDev g, float4* J0, float4* J1, uint8_t* level, fovpt_float4* out_color, uint32_t* out_rgba)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
+    const dim3 grid = fovpt_tile_grid(fd.w, fd.h);
     hipLaunchKernelGGL(k_vfilter_prep, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, color, variance, g.alb, J0, level, out_color, out_rgba);
-    float4* buf[2] = {J0, J1};
-    for (int i = 0; i < a.iterations; i++) {
-        if (i + 1 < a.iterations)
-            hipLaunchKernelGGL(k_vfilter_step<false>, grid, dim3(FOVPT_BLOCK), 0, st, fd.w, fd.h, i, a.demodulate, a.sl2, a.inv_n, a.inv_z, level,
-                               buf[i & 1], g.pos, g.nrm, g.alb, buf[(i + 1) & 1], out_color, out_rgba);
-        else
-            hipLaunchKernelGGL(k_vfilter_step<true>, grid, dim3(FOVPT_BLOCK), 0, st, fd.w, fd.h, i, a.demodulate, a.sl2, a.inv_n, a.inv_z, level,
-                               buf[i & 1], g.pos, g.nrm, g.alb, buf[(i + 1) & 1], out_color, out_rgba);
-    }
+    fovpt_atrous_iterate(a.iterations, J0, J1, [&](int i, bool last, const float4* Jin, float4* Jout) {
+        hipLaunchKernelGGL(!last ? k_vfilter_step<false> : k_vfilter_step<true>, grid, dim3(FOVPT_BLOCK), 0, st, fd.w, fd.h, i, a.demodulate, a.sl2,
+                           a.inv_n, a.inv_z, level, Jin, g.pos, g.nrm, g.alb, Jout, out_color, out_rgba);
+    });
 }

@@ -2,9 +2,9 @@
 // old colours into a frame whose depth is known: a gather.  Here only the OLD frame's depth is known, so the pixels are pushed:
 //
 //   k_warp_scatter   per source pixel: its G-buffer point (a hit) or its camera-ray direction (a miss) projected into the `to`
-//                    camera with fovpt_temporal's expression, rounded to the nearest pixel, and one 64-bit atomic minimum of
-//                    (depth bits << 32 | source index) on that pixel's key.  Nearest depth wins, equal depths go to the lower
-//                    source index: the keys do not depend on the order in which the atomics arrive
+//                    camera with fovpt_temporal's expression (project, fovpt_post_pixel.h), rounded to the nearest pixel, and one
+//                    64-bit atomic minimum of (depth bits << 32 | source index) on that pixel's key.  Nearest depth wins, equal
+//                    depths go to the lower source index: the keys do not depend on the order in which the atomics arrive
 //   k_warp_scatter_motion   fovpt_warp_motion's scatter: k_warp_scatter in which a hit pixel of a mesh that moved in the last
 //                    interval lands where its own motion, extrapolated by `advance` intervals, takes it
 //   k_warp_resolve   per destination pixel: the key's source; for an empty key the farthest key of the nearest non-empty
@@ -39,36 +39,42 @@ __device__ inline void count_wave(bool p, unsigned long long* n)
     if ((threadIdx.x & (FOVPT_WAVE - 1)) == 0 && m) atomicAdd(n, (unsigned long long)__popcll(m));
 }
 
+// The tail of a scatter: v (source pixel s's point relative to the `to` eye, or a miss's direction) projected with fovpt_temporal's
+// expression, rounded to the nearest pixel, and the atomic minimum on that pixel's key.  false: it lands outside the frame or behind
+// the camera
+__device__ inline bool scatter_key(const FrameDev& fd, const WarpArgs& a, const V3& v, bool miss, uint32_t s,
+                                   unsigned long long* __restrict__ keys)
+{
+    const float fw = (float)fd.w, fh = (float)fd.h;
+    float az, px, py;
+    project(a.inv, v, fw, fh, az, px, py);
+    const float fx = floorf(px + 0.5f), fy = floorf(py + 0.5f);
+    const bool landed = az > 0.0f && fx >= 0.0f && fx < fw && fy >= 0.0f && fy < fh;   // (in float, before converting: NaN fails)
+    if (landed) {
+        const uint32_t d = miss ? 0x7fffffffu : __float_as_uint(az);      // (az > 0: its bits order as its value does)
+        const uint32_t q = (uint32_t)fy * (uint32_t)fd.w + (uint32_t)fx;
+        (void)atomicMin(&keys[q], ((unsigned long long)d << 32) | (unsigned long long)s);
+    }
+    return landed;
+}
+
 __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter(const FrameDev fd, const WarpArgs a, const uint32_t* __restrict__ prim,
                                                               const float4* __restrict__ pos, unsigned long long* __restrict__ keys,
                                                               unsigned long long* __restrict__ counts)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    uint32_t x, y, s;
     bool landed = false;
-    if (x < (uint32_t)fd.w && y < (uint32_t)fd.h) {
-        const uint32_t s = y * (uint32_t)fd.w + x;
+    if (tile_pixel(fd.w, fd.h, x, y, s)) {                                // (lanes outside the frame go on to count_wave)
         const bool miss = prim[s] == 0xffffffffu;
         V3 v;
         if (!miss) v = v3(pos[s]) - v3(a.eye[0], a.eye[1], a.eye[2]);
         else v = pixel_ray(fd, x, y);                                    // the sky is at infinity: only rotation moves it
-        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
-        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
-        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
-        const float fw = (float)fd.w, fh = (float)fd.h;
-        const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
-        const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
-        const float fx = floorf(px + 0.5f), fy = floorf(py + 0.5f);
-        landed = az > 0.0f && fx >= 0.0f && fx < fw && fy >= 0.0f && fy < fh;    // (in float, before converting: NaN fails)
-        if (landed) {
-            const uint32_t d = miss ? 0x7fffffffu : __float_as_uint(az);  // (az > 0: its bits order as its value does)
-            const uint32_t q = (uint32_t)fy * (uint32_t)fd.w + (uint32_t)fx;
-            (void)atomicMin(&keys[q], ((unsigned long long)d << 32) | (unsigned long long)s);
-        }
+        landed = scatter_key(fd, a, v, miss, s, keys);
     }
     count_wave(landed, &count_slot(counts)[0]);
 }
 
-// fovpt_warp_motion's scatter (tests/warp_motion_ref.py): k_warp_scatter, statement for statement, in which
+// fovpt_warp_motion's scatter (tests/warp_motion_ref.py): k_warp_scatter in which
 // a hit pixel of a mesh that moved in the interval the last temporal step ended scatters X* = X_s + advance * (X_s - X') for X_s, X'
 // where its hit (u, v) was on the triangle's previous vertices (fovpt_post_pixel.h, as k_temporal_motion's).  The common case -- an
 // unmarked mesh -- pays for the hit record, one word of the triangle record and the mark; the branch is per lane.
@@ -76,10 +82,9 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter_motion(const Frame
                                                                      const uint32_t* __restrict__ prim, const float4* __restrict__ pos,
                                                                      unsigned long long* __restrict__ keys, unsigned long long* __restrict__ counts)
 {
-    const uint32_t x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    uint32_t x, y, s;
     bool landed = false;
-    if (x < (uint32_t)fd.w && y < (uint32_t)fd.h) {
-        const uint32_t s = y * (uint32_t)fd.w + x;
+    if (tile_pixel(fd.w, fd.h, x, y, s)) {                                // (lanes outside the frame go on to count_wave)
         const uint32_t p = prim[s];
         const bool miss = p == 0xffffffffu;
         V3 v;
@@ -99,19 +104,7 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter_motion(const Frame
             }
             v = X - v3(a.eye[0], a.eye[1], a.eye[2]);
         } else v = pixel_ray(fd, x, y);                                  // the sky is at infinity: only rotation moves it
-        const float ax = (a.inv[0] * v.x + a.inv[1] * v.y) + a.inv[2] * v.z;
-        const float ay = (a.inv[3] * v.x + a.inv[4] * v.y) + a.inv[5] * v.z;
-        const float az = (a.inv[6] * v.x + a.inv[7] * v.y) + a.inv[8] * v.z;
-        const float fw = (float)fd.w, fh = (float)fd.h;
-        const float px = (((ax / az) + 1.0f) * 0.5f) * fw - 0.5f;
-        const float py = (((ay / az) + 1.0f) * 0.5f) * fh - 0.5f;
-        const float fx = floorf(px + 0.5f), fy = floorf(py + 0.5f);
-        landed = az > 0.0f && fx >= 0.0f && fx < fw && fy >= 0.0f && fy < fh;    // (in float, before converting: a non-finite X* fails)
-        if (landed) {
-            const uint32_t d = miss ? 0x7fffffffu : __float_as_uint(az);
-            const uint32_t q = (uint32_t)fy * (uint32_t)fd.w + (uint32_t)fx;
-            (void)atomicMin(&keys[q], ((unsigned long long)d << 32) | (unsigned long long)s);
-        }
+        landed = scatter_key(fd, a, v, miss, s, keys);                    // (a non-finite X* does not land)
     }
     count_wave(landed, &count_slot(counts)[0]);
 }
@@ -125,11 +118,11 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_resolve(int w, int h, int 
                                                               fovpt_float4* __restrict__ out_color, uint32_t* __restrict__ out_rgba,
                                                               uint32_t* __restrict__ out_map, unsigned long long* __restrict__ counts)
 {
-    const int x = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), y = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
-    const bool in = x < w && y < h;
+    int x, y;
+    uint32_t q;
+    const bool in = tile_pixel(w, h, x, y, q);
     uint32_t cls = 3u;                                                   // (outside the frame: no class)
     if (in) {
-        const uint32_t q = (uint32_t)y * (uint32_t)w + (uint32_t)x;
         unsigned long long k = keys[q];
         cls = 0u;
         if (k == WARP_EMPTY) {
@@ -165,22 +158,20 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_resolve(int w, int h, int 
 void fovpt_launch_warp_scatter(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const uint32_t* prim, const float4* pos, uint64_t* keys,
                                uint64_t* counts)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_warp_scatter, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, prim, pos, (unsigned long long*)keys, (unsigned long long*)counts);
+    hipLaunchKernelGGL(k_warp_scatter, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, prim, pos, (unsigned long long*)keys,
+                       (unsigned long long*)counts);
 }
 
 void fovpt_launch_warp_scatter_motion(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const WarpMotionArgs& m, const uint32_t* prim,
                                       const float4* pos, uint64_t* keys, uint64_t* counts)
 {
-    const dim3 grid((fd.w + 63) / 64, (fd.h + 3) / 4);
-    hipLaunchKernelGGL(k_warp_scatter_motion, grid, dim3(FOVPT_BLOCK), 0, st, fd, a, m, prim, pos, (unsigned long long*)keys,
-                       (unsigned long long*)counts);
+    hipLaunchKernelGGL(k_warp_scatter_motion, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, m, prim, pos,
+                       (unsigned long long*)keys, (unsigned long long*)counts);
 }
 
 void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,
                                fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map, uint64_t* counts)
 {
-    const dim3 grid((w + 63) / 64, (h + 3) / 4);
-    hipLaunchKernelGGL(k_warp_resolve, grid, dim3(FOVPT_BLOCK), 0, st, w, h, radius, (const unsigned long long*)keys, in_color, in_rgba, out_color,
-                       out_rgba, out_map, (unsigned long long*)counts);
+    hipLaunchKernelGGL(k_warp_resolve, fovpt_tile_grid(w, h), dim3(FOVPT_BLOCK), 0, st, w, h, radius, (const unsigned long long*)keys, in_color,
+                       in_rgba, out_color, out_rgba, out_map, (unsigned long long*)counts);
 }
