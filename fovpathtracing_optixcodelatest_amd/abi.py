@@ -12,7 +12,26 @@ OPT_SKY_MISS, OPT_RUSSIAN_ROULETTE = 1, 2      # fovpt_config.options (include/f
 OP_SIN, OP_COS, OP_ACOS, OP_ATAN2, OP_LOG, OP_POW, OP_SQRT, OP_DIV, OP_RSQRTD, OP_UNORM8, OP_HALFPLUS = range(1, 12)
 
 
-class Float3(C.Structure):
+class Struct(C.Structure):
+    """What every mirror below shares (no _fields_ of its own, no C counterpart)."""
+
+    def copy(self):
+        """A new object of the same class with the same bytes."""
+        m = type(self)()
+        C.memmove(C.byref(m), C.byref(self), C.sizeof(self))
+        return m
+
+    def as_dict(self):
+        """The public fields (names that do not start with "_"); arrays as tuples."""
+        out = {}
+        for n, _ in self._fields_:
+            if not n.startswith("_"):
+                v = getattr(self, n)
+                out[n] = tuple(v) if isinstance(v, C.Array) else v
+        return out
+
+
+class Float3(Struct):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
 
     def set(self, v):
@@ -23,23 +42,23 @@ class Float3(C.Structure):
         return [self.x, self.y, self.z]
 
 
-class Float4(C.Structure):
+class Float4(Struct):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("w", C.c_float)]
 
 
-class Int2(C.Structure):
+class Int2(Struct):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32)]
 
 
-class UInt2(C.Structure):
+class UInt2(Struct):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32)]
 
 
-class UInt3(C.Structure):
+class UInt3(Struct):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("z", C.c_uint32)]
 
 
-class Material(C.Structure):
+class Material(Struct):
     """fovpt_material == Material (PT_sv5_/Material.h).  Construct with Material.reference_default()
     to get the non-trivial constructor defaults of Material.h:13-38."""
     _fields_ = [
@@ -74,13 +93,8 @@ class Material(C.Structure):
         m.flags = 0
         return m
 
-    def copy(self):
-        m = Material()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(Material))
-        return m
 
-
-class Probe(C.Structure):
+class Probe(Struct):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32),
         ("data", C.c_void_p),
@@ -90,7 +104,7 @@ class Probe(C.Structure):
     ]
 
 
-class _Frame(C.Structure):
+class _Frame(Struct):
     _fields_ = [
         ("accum_buffer", C.c_void_p), ("frame_buffer", C.c_void_p),
         ("color_buffer", C.c_void_p), ("normal_buffer", C.c_void_p), ("albedo_buffer", C.c_void_p),
@@ -101,11 +115,11 @@ class _Frame(C.Structure):
     ]
 
 
-class _Camera(C.Structure):
+class _Camera(Struct):
     _fields_ = [("eye", Float3), ("U", Float3), ("V", Float3), ("W", Float3)]
 
 
-class LaunchParams(C.Structure):
+class LaunchParams(Struct):
     _fields_ = [
         ("frame", _Frame), ("camera", _Camera),
         ("samples_per_launch", C.c_uint32), ("_pad2", C.c_uint32),
@@ -113,13 +127,8 @@ class LaunchParams(C.Structure):
         ("viewportSize", Int2), ("white", C.c_float), ("_pad3", C.c_uint32),
     ]
 
-    def copy(self):
-        m = LaunchParams()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(LaunchParams))
-        return m
 
-
-class MeshDesc(C.Structure):
+class MeshDesc(Struct):
     _fields_ = [
         ("vertex", C.c_void_p), ("normal", C.c_void_p), ("texcoord", C.c_void_p), ("index", C.c_void_p),
         ("num_vertices", C.c_uint32), ("num_triangles", C.c_uint32),
@@ -127,7 +136,7 @@ class MeshDesc(C.Structure):
     ]
 
 
-class ModelMesh(C.Structure):
+class ModelMesh(Struct):
     """fovpt_model_mesh: one TriangleMesh of a model loaded by fovpt_model_load_obj (arrays owned by the model)."""
     _fields_ = [
         ("vertex", C.c_void_p), ("normal", C.c_void_p), ("texcoord", C.c_void_p), ("index", C.c_void_p),
@@ -142,12 +151,12 @@ REBUILD_IDLE, REBUILD_BUILDING, REBUILD_READY = 0, 1, 2     # fovpt_rebuild_info
 REBUILD_WAIT, REBUILD_ADOPT = 1, 2              # fovpt_rebuild_state flags
 
 
-class VertexUpdate(C.Structure):
+class VertexUpdate(Struct):
     """fovpt_vertex_update: new xyz positions for one mesh of the scene (host, or device with UPDATE_DEVICE)."""
     _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("vertex", C.c_void_p)]
 
 
-class MeshTransform(C.Structure):
+class MeshTransform(Struct):
     """fovpt_mesh_transform: a row-major 3 x 4 matrix applied to the rest positions of one mesh (fovpt_update_transforms)."""
     _fields_ = [("mesh", C.c_int32), ("m", C.c_float * 12)]
 
@@ -158,7 +167,7 @@ COST_WAIT = 1                                   # fovpt_hierarchy_cost flag (FOV
 STATE_DONE, STATE_SECONDARY, STATE_ALPHA_ONE, STATE_ALPHA_SET = 1, 2, 4, 8   # a sample slot's flags, below depth << 8 (fovpt_debug_resolve)
 
 
-class DebugPass(C.Structure):
+class DebugPass(Struct):
     """struct fovpt_debug_pass: one pass of the frame fovpt_debug_resolve resolves, and its place in the caller's arrays."""
     _fields_ = [("gw", C.c_uint32), ("rows", C.c_uint32), ("spp", C.c_uint32), ("slot_base", C.c_uint32), ("launch_base", C.c_uint32)]
 
@@ -166,13 +175,13 @@ class DebugPass(C.Structure):
 DEBUG_SHADE_FILL = 0xcd                         # FOVPT_DEBUG_SHADE_FILL: the byte fovpt_debug_shade fills every output buffer with
 
 
-class DebugShadeLaunch(C.Structure):
+class DebugShadeLaunch(Struct):
     """struct fovpt_debug_shade_launch."""
     _fields_ = [("n", C.c_int32), ("depth_iter", C.c_int32), ("grid", C.c_int32), ("partition", C.c_int32), ("sel", C.c_uint32),
                 ("shard_count", C.c_uint32 * 8)]
 
 
-class DebugShadeResult(C.Structure):
+class DebugShadeResult(Struct):
     """struct fovpt_debug_shade_result: host arrays of the caller's, and what the call counted."""
     _fields_ = [(k, C.c_void_p) for k in ("rng4", "thr4", "rad4", "alpha4", "guide_n4", "guide_a4", "next_place2", "next_o4", "next_d4",
                                           "shadow_place2", "shadow_o4", "shadow_d4", "shadow_vis4", "shadow_occ4")] + [
@@ -184,7 +193,7 @@ DEBUG_TRACE_ALPHA = 0xffffffff                  # FOVPT_DEBUG_TRACE_ALPHA: a sha
 DEBUG_TRACE_ITERS = 63                          # FOVPT_DEBUG_TRACE_ITERS: the iterations fovpt_debug_trace_queued may name
 
 
-class DebugTraceLaunch(C.Structure):
+class DebugTraceLaunch(Struct):
     """struct fovpt_debug_trace_launch: host arrays of the caller's for the two ray sets, and the launch."""
     _fields_ = [(k, C.c_void_p) for k in ("origins3", "dirs3", "slot", "target", "vis4", "occ4", "other_origins3", "other_dirs3", "other_slot",
                                           "other_target", "other_vis4", "other_occ4")] + [
@@ -193,32 +202,32 @@ class DebugTraceLaunch(C.Structure):
         ("other_q_count", C.c_uint32 * 8), ("other_sq_count", C.c_uint32 * 8), ("decoy", C.c_uint32 * 8)]
 
 
-class DebugTraceResult(C.Structure):
+class DebugTraceResult(Struct):
     """struct fovpt_debug_trace_result: host arrays of the caller's, and what the call counted."""
     _fields_ = [(k, C.c_void_p) for k in ("hit_place2", "hit4", "hit_prim", "cells4", "alpha4")] + [
         ("stat_radiance", C.c_uint64), ("stat_shadow", C.c_uint64), ("stat_paths", C.c_uint64),
         ("hit_found", C.c_uint32), ("counters_changed", C.c_uint32), ("queues_unchanged", C.c_uint32), ("cap", C.c_uint32)]
 
 
-class DebugGenerateLaunch(C.Structure):
+class DebugGenerateLaunch(Struct):
     """struct fovpt_debug_generate_launch."""
     _fields_ = [("render", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32), ("row0", C.c_uint32), ("row1", C.c_uint32),
                 ("sel", C.c_uint32), ("slot_begin", C.c_uint32), ("slot_end", C.c_uint32), ("grid", C.c_int32)]
 
 
-class DebugGenerateResult(C.Structure):
+class DebugGenerateResult(Struct):
     """struct fovpt_debug_generate_result: host arrays of the caller's, and what the call counted."""
     _fields_ = [(k, C.c_void_p) for k in ("rng4", "backplate4", "guide_n4", "guide_a4", "place2", "o4", "d4")] + [
         ("count", C.c_uint32 * 8), ("found", C.c_uint32), ("counters_changed", C.c_uint32), ("cap", C.c_uint32), ("kernel", C.c_uint32),
         ("guides", C.c_uint32), ("slot_begin", C.c_uint32), ("slot_end", C.c_uint32), ("grid", C.c_uint32)]
 
 
-class DebugBuildSwitches(C.Structure):
+class DebugBuildSwitches(Struct):
     """struct fovpt_debug_build_switches: the switches of one fovpt_debug_build, nothing from the environment."""
     _fields_ = [("use_ploc", C.c_int32), ("split_budget", C.c_float), ("reinsert_rounds", C.c_int32), ("order_children", C.c_int32)]
 
 
-class DebugBuildTrace(C.Structure):
+class DebugBuildTrace(Struct):
     """struct fovpt_debug_build_trace: host arrays of the caller's for what every stage of a build left, and its scalars."""
     _fields_ = [(k, C.c_void_p) for k in ("split_count", "split_first", "ref_prim", "boxes", "keys_s", "vals_s", "left0", "right0", "ibox0",
                                           "round_end", "left1", "right1", "ibox1", "size_int", "node_first", "leaf_pos", "dp", "nodes_pre",
@@ -228,12 +237,12 @@ class DebugBuildTrace(C.Structure):
         ("s_cut", C.c_float), ("cbounds", C.c_float * 6), ("level_first", C.c_uint32 * 65)]
 
 
-class HierarchyCost(C.Structure):
+class HierarchyCost(Struct):
     """fovpt_hierarchy_cost_info: the SAH cost of the hierarchy as built and as last measured, and the update counters."""
     _fields_ = [("built", C.c_double), ("current", C.c_double), ("updates", C.c_uint64), ("measured", C.c_uint64)]
 
 
-class RebuildInfo(C.Structure):
+class RebuildInfo(Struct):
     """fovpt_rebuild_info: the state of the background rebuild (FOVPT_UPDATE_REBUILD_ASYNC) and its counters."""
     _fields_ = [("state", C.c_int32), ("last_error", C.c_int32), ("requested", C.c_uint64), ("started", C.c_uint64), ("adopted", C.c_uint64),
                 ("failed", C.c_uint64), ("discarded", C.c_uint64), ("snapshot_update", C.c_uint64), ("ms_build", C.c_double)]
@@ -242,14 +251,14 @@ class RebuildInfo(C.Structure):
 SKIN_MAX_JOINTS = 1024                          # FOVPT_SKIN_MAX_JOINTS
 
 
-class MeshSkin(C.Structure):
+class MeshSkin(Struct):
     """fovpt_mesh_skin: four joint indices and four weights per vertex of one mesh (fovpt_set_skins); num_joints 0 and two null
     pointers remove the mesh's skin."""
     _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("num_joints", C.c_uint32), ("_reserved", C.c_uint32),
                 ("joints", C.c_void_p), ("weights", C.c_void_p)]
 
 
-class SkinPose(C.Structure):
+class SkinPose(Struct):
     """fovpt_skin_pose: the palette of one skinned mesh, num_joints row-major 3 x 4 matrices (fovpt_update_skinned)."""
     _fields_ = [("mesh", C.c_int32), ("num_joints", C.c_uint32), ("matrices", C.c_void_p)]
 
@@ -257,18 +266,18 @@ class SkinPose(C.Structure):
 MORPH_MAX_TARGETS = 256                         # FOVPT_MORPH_MAX_TARGETS
 
 
-class MorphTarget(C.Structure):
+class MorphTarget(Struct):
     """fovpt_morph_target: the vertices one target moves and their deltas; index null: dense, entry i is vertex i."""
     _fields_ = [("count", C.c_uint32), ("_reserved", C.c_uint32), ("index", C.c_void_p), ("delta", C.c_void_p)]
 
 
-class MeshMorph(C.Structure):
+class MeshMorph(Struct):
     """fovpt_mesh_morph: the morph targets of one mesh (fovpt_set_morphs); num_targets 0 and a null pointer remove them."""
     _fields_ = [("mesh", C.c_int32), ("num_vertices", C.c_uint32), ("num_targets", C.c_uint32), ("_reserved", C.c_uint32),
                 ("targets", C.POINTER(MorphTarget))]
 
 
-class MorphPose(C.Structure):
+class MorphPose(Struct):
     """fovpt_morph_pose: one weight per target of a morphed mesh and, with num_joints > 0, its skin's palette
     (fovpt_update_morphed)."""
     _fields_ = [("mesh", C.c_int32), ("num_targets", C.c_uint32), ("weights", C.c_void_p), ("num_joints", C.c_uint32),
@@ -280,41 +289,41 @@ RIG_TRANSLATION, RIG_ROTATION, RIG_SCALE, RIG_WEIGHTS = 0, 1, 2, 3        # FOVP
 RIG_STEP, RIG_LINEAR = 0, 1                                               # FOVPT_RIG_STEP / _LINEAR: its interpolation
 
 
-class RigNode(C.Structure):
+class RigNode(Struct):
     """fovpt_rig_node: a node's parent (-1: a root; otherwise below its own index) and rest pose, rotation as x y z w."""
     _fields_ = [("parent", C.c_int32), ("translation", C.c_float * 3), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
 
 
-class RigBinding(C.Structure):
+class RigBinding(Struct):
     """fovpt_rig_binding: one mesh the rig drives: rigidly by a node, through its skin by joint nodes and inverse bind matrices,
     or (node -1, no joints) by morph weights alone."""
     _fields_ = [("mesh", C.c_int32), ("node", C.c_int32), ("num_joints", C.c_uint32), ("_reserved", C.c_uint32),
                 ("joint_nodes", C.c_void_p), ("inverse_bind", C.c_void_p)]
 
 
-class RigChannel(C.Structure):
+class RigChannel(Struct):
     """fovpt_rig_channel: the keys of one path of one node (WEIGHTS: of one mesh)."""
     _fields_ = [("target", C.c_int32), ("path", C.c_int32), ("interpolation", C.c_int32), ("num_keys", C.c_uint32),
                 ("times", C.c_void_p), ("values", C.c_void_p)]
 
 
-class RigClip(C.Structure):
+class RigClip(Struct):
     """fovpt_rig_clip: the channels of one clip."""
     _fields_ = [("num_channels", C.c_uint32), ("_reserved", C.c_uint32), ("channels", C.POINTER(RigChannel))]
 
 
-class RigDesc(C.Structure):
+class RigDesc(Struct):
     """fovpt_rig_desc: nodes, bindings and clips (fovpt_set_rig)."""
     _fields_ = [("nodes", C.POINTER(RigNode)), ("num_nodes", C.c_uint32), ("_reserved0", C.c_uint32),
                 ("bindings", C.POINTER(RigBinding)), ("num_bindings", C.c_uint32), ("_reserved1", C.c_uint32),
                 ("clips", C.POINTER(RigClip)), ("num_clips", C.c_uint32), ("_reserved2", C.c_uint32)]
 
 
-class TextureDesc(C.Structure):
+class TextureDesc(Struct):
     _fields_ = [("pixel", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
 
-class Config(C.Structure):
+class Config(Struct):
     _fields_ = [
         ("uniform", C.c_int32), ("r_inner", C.c_int32), ("r_outer", C.c_int32),
         ("spp_periphery", C.c_int32), ("spp_middle", C.c_int32), ("spp_fovea", C.c_int32),
@@ -338,17 +347,12 @@ class Config(C.Structure):
         c.tile_w, c.tile_h = 8, 4
         return c
 
-    def copy(self):
-        m = Config()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(Config))
-        return m
-
 
 DENOISE_MAX_ITERATIONS = 5                     # FOVPT_DENOISE_MAX_ITERATIONS
 SIGMA_MIN, SIGMA_MAX = 1e-6, 1e6               # FOVPT_SIGMA_MIN / MAX (binary32 1e-6f / 1e6f): accepted *_sigma of both configs
 
 
-class DenoiseConfig(C.Structure):
+class DenoiseConfig(Struct):
     """fovpt_denoise_config: iterations per foveation level and the edge-stopping scales (defaults: fovpt_denoise_defaults)."""
     _fields_ = [
         ("iterations_fovea", C.c_int32), ("iterations_middle", C.c_int32), ("iterations_periphery", C.c_int32),
@@ -357,16 +361,8 @@ class DenoiseConfig(C.Structure):
         ("_reserved", C.c_int32),
     ]
 
-    def copy(self):
-        m = DenoiseConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(DenoiseConfig))
-        return m
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class ReconstructConfig(C.Structure):
+class ReconstructConfig(Struct):
     """fovpt_reconstruct_config: tent support, edge-stopping scales, levels and remodulation (defaults: fovpt_reconstruct_defaults)."""
     _fields_ = [
         ("support", C.c_float), ("normal_sigma", C.c_float), ("depth_sigma", C.c_float),
@@ -374,16 +370,8 @@ class ReconstructConfig(C.Structure):
         ("_reserved", C.c_int32 * 3),
     ]
 
-    def copy(self):
-        m = ReconstructConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(ReconstructConfig))
-        return m
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class GBufferPtrs(C.Structure):
+class GBufferPtrs(Struct):
     """fovpt_gbuffer_ptrs: device pointers of the G-buffer fovpt_gbuffer filled."""
     _fields_ = [
         ("prim", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p),
@@ -394,7 +382,7 @@ class GBufferPtrs(C.Structure):
 TEMPORAL_MAX_HISTORY = 64                      # FOVPT_TEMPORAL_MAX_HISTORY
 
 
-class TemporalConfig(C.Structure):
+class TemporalConfig(Struct):
     """fovpt_temporal_config: history caps per foveation level and the reprojection tolerances (defaults: fovpt_temporal_defaults)."""
     _fields_ = [
         ("history_fovea", C.c_int32), ("history_middle", C.c_int32), ("history_periphery", C.c_int32),
@@ -403,30 +391,17 @@ class TemporalConfig(C.Structure):
         ("_reserved", C.c_int32 * 2),
     ]
 
-    def copy(self):
-        m = TemporalConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(TemporalConfig))
-        return m
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
 
 POST_DENOISE, POST_RECONSTRUCT, POST_TEMPORAL, POST_MOTION = 1, 2, 4, 8     # FOVPT_POST_*
 
 
-class PostConfig(C.Structure):
+class PostConfig(Struct):
     """fovpt_post_config: the stages of the post-frame chain (POST_* bits) and each stage's own config (defaults: fovpt_post_defaults)."""
     _fields_ = [
         ("stages", C.c_int32),
         ("_reserved", C.c_int32 * 3),
         ("denoise", DenoiseConfig), ("reconstruct", ReconstructConfig), ("temporal", TemporalConfig),
     ]
-
-    def copy(self):
-        m = PostConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(PostConfig))
-        return m
 
 
 EXPOSE_FIXED, EXPOSE_AUTO = 0, 1               # FOVPT_EXPOSE_*
@@ -435,7 +410,7 @@ TONE_REINHARD, TONE_ACES = 0, 1                # FOVPT_TONE_*
 EXPOSE_BINS = 256                              # FOVPT_EXPOSE_BINS
 
 
-class ExposeConfig(C.Structure):
+class ExposeConfig(Struct):
     """fovpt_expose_config: mode, metering, tone map, the meter's weights per foveation level and its trimmed mean, the key and
     the adaptation rates (defaults: fovpt_expose_defaults)."""
     _fields_ = [
@@ -448,16 +423,8 @@ class ExposeConfig(C.Structure):
         ("_reserved", C.c_int32 * 3),
     ]
 
-    def copy(self):
-        m = ExposeConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(ExposeConfig))
-        return m
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class ExposeState(C.Structure):
+class ExposeState(Struct):
     """struct fovpt_expose_state: the metered and the adapted log2 luminance, the exposure, the last meter's total weight and the
     AUTO steps since create / reset."""
     _fields_ = [
@@ -470,7 +437,7 @@ BLOOM_MAX_LEVELS = 8                           # FOVPT_BLOOM_MAX_LEVELS
 BLOOM_KARIS, BLOOM_GAINS, BLOOM_EXPOSURE_STATE = 1, 2, 4     # FOVPT_BLOOM_* (flags)
 
 
-class BloomConfig(C.Structure):
+class BloomConfig(Struct):
     """fovpt_bloom_config: flags, levels, the threshold and knee in exposed units, the exposure they are divided by, the intensity
     of the composite, the spread between levels and the gains per foveation level (defaults: fovpt_bloom_defaults)."""
     _fields_ = [
@@ -481,56 +448,32 @@ class BloomConfig(C.Structure):
         ("_reserved", C.c_int32 * 5),
     ]
 
-    def copy(self):
-        m = BloomConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(BloomConfig))
-        return m
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
 
 WARP_COLOR, WARP_RGBA = 1, 2                   # FOVPT_WARP_*
 WARP_MAX_RADIUS = 4                            # FOVPT_WARP_MAX_RADIUS
 WARP_DIRECT, WARP_FILLED, WARP_EMPTY = 0, 1, 2  # the class in bits 30 .. 31 of a warp map entry
 
 
-class WarpCamera(C.Structure):
+class WarpCamera(Struct):
     """fovpt_warp_camera: the camera fovpt_warp re-aims the frame at, in LaunchParams.camera's layout."""
     _fields_ = [("eye", Float3), ("U", Float3), ("V", Float3), ("W", Float3)]
 
 
-class WarpConfig(C.Structure):
+class WarpConfig(Struct):
     """fovpt_warp_config: the images to warp (WARP_* bits) and the radius of the hole fill (defaults: fovpt_warp_defaults)."""
     _fields_ = [("images", C.c_int32), ("fill_radius", C.c_int32), ("_reserved", C.c_int32 * 6)]
-
-    def copy(self):
-        m = WarpConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(WarpConfig))
-        return m
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
 
 
 WARP_MAX_ADVANCE = 4.0                         # FOVPT_WARP_MAX_ADVANCE
 
 
-class WarpMotionConfig(C.Structure):
+class WarpMotionConfig(Struct):
     """fovpt_warp_motion_config: WarpConfig's images and fill radius, and how far past the rendered frame the moved meshes are
     extrapolated, in intervals between the last two temporal steps (defaults: fovpt_warp_motion_defaults)."""
     _fields_ = [("images", C.c_int32), ("fill_radius", C.c_int32), ("advance", C.c_float), ("_reserved", C.c_int32 * 5)]
 
-    def copy(self):
-        m = WarpMotionConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(WarpMotionConfig))
-        return m
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class WarpCounts(C.Structure):
+class WarpCounts(Struct):
     """struct fovpt_warp_counts: the source pixels of the last warp that landed in the frame, and its destination pixels by class."""
     _fields_ = [("splatted", C.c_uint64), ("direct", C.c_uint64), ("filled", C.c_uint64), ("empty", C.c_uint64)]
 
@@ -539,7 +482,7 @@ FOCUS_FIXED, FOCUS_AUTO = 0, 1                 # FOVPT_FOCUS_*
 FOCUS_MAX_RADIUS, FOCUS_MAX_METER_RADIUS, FOCUS_BINS = 8, 64, 256
 
 
-class FocusConfig(C.Structure):
+class FocusConfig(Struct):
     """fovpt_focus_config: mode, the gaze disc and rank of the meter, the blur's cap and strength, the fixed and the default focus
     distance and the adaptation rates (defaults: fovpt_focus_defaults)."""
     _fields_ = [
@@ -549,16 +492,8 @@ class FocusConfig(C.Structure):
         ("_reserved", C.c_int32 * 7),
     ]
 
-    def copy(self):
-        m = FocusConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(FocusConfig))
-        return m
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class FocusState(C.Structure):
+class FocusState(Struct):
     """struct fovpt_focus_state: the metered distance, the adapted reciprocal distance and distance, the pixels the last meter
     counted and the AUTO steps since create / reset."""
     _fields_ = [
@@ -571,7 +506,7 @@ LENS_NEAREST, LENS_BILINEAR, LENS_BICUBIC = 0, 1, 2    # FOVPT_LENS_*
 LENS_ENCODE_DISPLAY, LENS_ENCODE_RESOLVE = 0, 1
 
 
-class LensConfig(C.Structure):
+class LensConfig(Struct):
     """fovpt_lens_config: the filter and the rgba8 encoding, the lens axis and scale in destination NDC, the radial polynomial and
     its per-channel factors, the lens's clip radius, the map from lens units to source NDC and the border colour (defaults:
     fovpt_lens_defaults)."""
@@ -582,18 +517,8 @@ class LensConfig(C.Structure):
         ("_reserved", C.c_int32 * 8),
     ]
 
-    def copy(self):
-        m = LensConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(LensConfig))
-        return m
 
-    def as_dict(self):
-        """The public fields; the float arrays as tuples."""
-        get = lambda n: getattr(self, n)
-        return {n: (tuple(get(n)) if isinstance(get(n), C.Array) else get(n)) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class VarianceConfig(C.Structure):
+class VarianceConfig(Struct):
     """fovpt_variance_config: the cap of the moment history, the history length below which the spatial estimate is taken, that
     estimate's radius and the tolerances of the history taps and the window (defaults: fovpt_variance_defaults)."""
     _fields_ = [
@@ -602,16 +527,8 @@ class VarianceConfig(C.Structure):
         ("_reserved", C.c_int32 * 3),
     ]
 
-    def copy(self):
-        m = VarianceConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(VarianceConfig))
-        return m
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
-
-class VarianceFilterConfig(C.Structure):
+class VarianceFilterConfig(Struct):
     """fovpt_variance_filter_config: a-trous iterations per foveation level, the luminance (in standard deviations), normal and
     plane-distance edge-stopping scales and the albedo demodulation (defaults: fovpt_variance_filter_defaults)."""
     _fields_ = [
@@ -621,14 +538,6 @@ class VarianceFilterConfig(C.Structure):
         ("_reserved", C.c_int32 * 4),
     ]
 
-    def copy(self):
-        m = VarianceFilterConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(VarianceFilterConfig))
-        return m
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
-
 
 QUALITY_SSIM, QUALITY_PROFILE = 1, 2                   # FOVPT_QUALITY_* flags
 QUALITY_CLASSES, QUALITY_RINGS, QUALITY_MAX_RING_WIDTH = 5, 64, 65536
@@ -636,18 +545,13 @@ QUALITY_FOVEA, QUALITY_MIDDLE, QUALITY_PERIPHERY, QUALITY_UNIFORM, QUALITY_UNWRI
 QUALITY_CLASS_NAMES = ("fovea", "middle", "periphery", "uniform", "unwritten")
 
 
-class QualityConfig(C.Structure):
+class QualityConfig(Struct):
     """fovpt_quality_config: which sums beside the per-class errors, and the width of a ring of the eccentricity profile
     (defaults: fovpt_quality_defaults)."""
     _fields_ = [("flags", C.c_int32), ("ring_width", C.c_int32), ("_reserved", C.c_int32 * 6)]
 
-    def copy(self):
-        m = QualityConfig()
-        C.memmove(C.byref(m), C.byref(self), C.sizeof(QualityConfig))
-        return m
 
-
-class QualitySums(C.Structure):
+class QualitySums(Struct):
     """fovpt_quality_sums: the exact integer sums of one measurement, per class (QUALITY_FOVEA ..) and per ring."""
     _fields_ = [
         ("pixels", C.c_uint64 * 5), ("differing", C.c_uint64 * 5), ("sq_err", (C.c_uint64 * 3) * 5),
@@ -670,7 +574,7 @@ PACKET_MAGIC_CODED = 0x43505646                                   # "FVPC": a co
 PACKET_RAW, PACKET_BC1, PACKET_BY_FILL = 0, 1, 0xffffffff
 
 
-class PacketPass(C.Structure):
+class PacketPass(Struct):
     """fovpt_packet_pass: a pass's launch grid, factor, fill and offset, and the byte offset of its texel array in the packet."""
     _fields_ = [
         ("gw", C.c_uint32), ("gh", C.c_uint32), ("factor", C.c_uint32), ("fill", C.c_uint32),
@@ -678,12 +582,12 @@ class PacketPass(C.Structure):
     ]
 
 
-class PacketConfig(C.Structure):
+class PacketConfig(Struct):
     """fovpt_packet_config: the codec of every launch pass of a coded packet (PACKET_RAW, PACKET_BC1, PACKET_BY_FILL)."""
     _fields_ = [("codec", C.c_uint32 * 3), ("_reserved", C.c_uint32)]
 
 
-class PacketHeader(C.Structure):
+class PacketHeader(Struct):
     """fovpt_packet_header: the first 128 bytes of a foveated frame packet, raw ("FVPK") or coded ("FVPC": a pass's _reserved is
     its codec)."""
     _fields_ = [
@@ -698,7 +602,7 @@ class PacketHeader(C.Structure):
         return cls.from_buffer_copy(bytes(data[:C.sizeof(cls)]))
 
 
-class Stats(C.Structure):
+class Stats(Struct):
     _fields_ = [
         ("radiance_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("frames", C.c_uint64),
         ("ms_generate", C.c_double), ("ms_trace", C.c_double), ("ms_shade", C.c_double),
@@ -709,7 +613,7 @@ class Stats(C.Structure):
     ]
 
 
-class FramePtrs(C.Structure):
+class FramePtrs(Struct):
     _fields_ = [
         ("frame_buffer", C.c_void_p), ("accum_buffer", C.c_void_p), ("color_buffer", C.c_void_p),
         ("normal_buffer", C.c_void_p), ("albedo_buffer", C.c_void_p),

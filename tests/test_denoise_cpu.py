@@ -1,16 +1,13 @@
 """fovpt_denoise without a GPU: the C ABI of the config (layout, defaults, argument checks) and properties of the filter's
 definition, the numpy restatement in tests/denoise_ref.py that the GPU kernels are checked against bit for bit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_layout
 import denoise_ref as dn
 from fovpathtracing_optixcodelatest_amd import abi, lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -19,13 +16,9 @@ def so():
     return lib.load()
 
 
-def test_denoise_config_mirror_matches_the_header(tmp_path):
+def test_denoise_config_mirror_matches_the_header():
     names = [f[0] for f in abi.DenoiseConfig._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu", sizeof(fovpt_denoise_config));' + "".join(
-        'printf(" %%zu", offsetof(fovpt_denoise_config, %s));' % n for n in names) + "return 0;}\n"
-    exe = str(tmp_path / "dn_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    got = header_layout.layout("fovpt_denoise_config", abi.DenoiseConfig)
     assert got[0] == C.sizeof(abi.DenoiseConfig) == 32
     assert got[1:] == [getattr(abi.DenoiseConfig, n).offset for n in names]
 
@@ -138,16 +131,12 @@ def test_level_map_follows_the_passes():
     assert pas[19, 29] == 2 and (pas[:-1, 28:] == -1).all() and (pas[:, :28] == 0).all() and (fill[:, :28] == 4).all()
 
 
-def test_sigma_bounds_are_the_header_constants(tmp_path):
+def test_sigma_bounds_are_the_header_constants():
     """abi.SIGMA_MIN / MAX are FOVPT_SIGMA_MIN / MAX (binary32) and abi.DENOISE_MAX_ITERATIONS is FOVPT_DENOISE_MAX_ITERATIONS."""
-    src = '#include <stdio.h>\n#include "fovpt.h"\nint main(void){printf("%a %a %d", (double)FOVPT_SIGMA_MIN, (double)FOVPT_SIGMA_MAX, ' \
-          'FOVPT_DENOISE_MAX_ITERATIONS); return 0;}\n'
-    exe = str(tmp_path / "sigma_bounds")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    lo, hi, its = subprocess.check_output([exe]).split()
-    assert float.fromhex(lo.decode()) == float(np.float32(abi.SIGMA_MIN))
-    assert float.fromhex(hi.decode()) == float(np.float32(abi.SIGMA_MAX))
-    assert int(its) == abi.DENOISE_MAX_ITERATIONS
+    lo, hi, its = header_layout.constants("FOVPT_SIGMA_MIN", "FOVPT_SIGMA_MAX", "FOVPT_DENOISE_MAX_ITERATIONS")
+    assert lo == float(np.float32(abi.SIGMA_MIN))
+    assert hi == float(np.float32(abi.SIGMA_MAX))
+    assert its == abi.DENOISE_MAX_ITERATIONS
 
 
 def test_the_sigma_bounds_keep_every_weight_finite():

@@ -3,16 +3,14 @@ scalar loop that rounds after every operation, hand-computed cases (the +-0 skip
 the empty target), the overflow rules on either side of 2^127; and of the ABI mirrors of fovpt_morph_target, fovpt_mesh_morph
 and fovpt_morph_pose."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import header_layout
 import morph_ref as mr
 import skin_ref as sk
 from fovpathtracing_optixcodelatest_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
@@ -188,19 +186,13 @@ def test_procedural_targets_are_what_they_say():
     assert (w == 0).any() and np.signbit(w[w == 0]).any() and not np.signbit(w[w == 0]).all() and (w < 0).any() and (w > 1).any()
 
 
-def test_abi_mirrors_match_the_header(tmp_path):
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu '
-           '%zu %zu %zu %zu %zu %zu %zu %d", '
-           'sizeof(fovpt_morph_target), offsetof(fovpt_morph_target, count), offsetof(fovpt_morph_target, _reserved), '
-           'offsetof(fovpt_morph_target, index), offsetof(fovpt_morph_target, delta), '
-           'sizeof(fovpt_mesh_morph), offsetof(fovpt_mesh_morph, mesh), offsetof(fovpt_mesh_morph, num_vertices), '
-           'offsetof(fovpt_mesh_morph, num_targets), offsetof(fovpt_mesh_morph, _reserved), offsetof(fovpt_mesh_morph, targets), '
-           'sizeof(fovpt_morph_pose), offsetof(fovpt_morph_pose, mesh), offsetof(fovpt_morph_pose, num_targets), '
-           'offsetof(fovpt_morph_pose, weights), offsetof(fovpt_morph_pose, num_joints), offsetof(fovpt_morph_pose, _reserved), '
-           'offsetof(fovpt_morph_pose, matrices), sizeof(void*), FOVPT_MORPH_MAX_TARGETS); return 0;}\n')
-    exe = str(tmp_path / "morph_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+def test_abi_mirrors_match_the_header():
+    (t, m, p), consts = header_layout.probe(
+        [("fovpt_morph_target", ("count", "_reserved", "index", "delta")),
+         ("fovpt_mesh_morph", ("mesh", "num_vertices", "num_targets", "_reserved", "targets")),
+         ("fovpt_morph_pose", ("mesh", "num_targets", "weights", "num_joints", "_reserved", "matrices"))],
+        ("sizeof(void*)", "FOVPT_MORPH_MAX_TARGETS"))
+    got = t + m + p + consts
     T, M, P = abi.MorphTarget, abi.MeshMorph, abi.MorphPose
     assert got == [ctypes.sizeof(T), T.count.offset, T._reserved.offset, T.index.offset, T.delta.offset,
                    ctypes.sizeof(M), M.mesh.offset, M.num_vertices.offset, M.num_targets.offset, M._reserved.offset, M.targets.offset,

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import header_layout
 import packet_bc_ref as bc
 import packet_ref as pk
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
@@ -258,16 +259,11 @@ def test_untrusted_coded_packets_under_sanitizers(tmp_path):
 
 
 # ---- 6. the ABI -----------------------------------------------------------------------------------------------------------------------
-def test_struct_mirror_defines_prototypes_and_exports(libs, tmp_path):
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
-           'printf("%zu %zu %zu\\n", sizeof(fovpt_packet_config), offsetof(fovpt_packet_config, codec), offsetof(fovpt_packet_config, _reserved));'
-           'printf("%u %u %u %u %u %d\\n", FOVPT_PACKET_MAGIC_CODED, FOVPT_PACKET_RAW, FOVPT_PACKET_BC1, FOVPT_PACKET_BY_FILL, FOVPT_PACKET_MAGIC, FOVPT_PACKET_VERSION);'
-           'return 0;}\n')
-    exe = str(tmp_path / "packet_config_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    lines = subprocess.check_output([exe]).decode().splitlines()
-    assert [int(x) for x in lines[0].split()] == [C.sizeof(abi.PacketConfig), abi.PacketConfig.codec.offset, abi.PacketConfig._reserved.offset] == [16, 0, 12]
-    assert [int(x) for x in lines[1].split()] == [abi.PACKET_MAGIC_CODED, abi.PACKET_RAW, abi.PACKET_BC1, abi.PACKET_BY_FILL, abi.PACKET_MAGIC, abi.PACKET_VERSION]
+def test_struct_mirror_defines_prototypes_and_exports(libs):
+    (lay,), consts = header_layout.probe([("fovpt_packet_config", ("codec", "_reserved"))],
+                                         ("FOVPT_PACKET_MAGIC_CODED", "FOVPT_PACKET_RAW", "FOVPT_PACKET_BC1", "FOVPT_PACKET_BY_FILL", "FOVPT_PACKET_MAGIC", "FOVPT_PACKET_VERSION"))
+    assert lay == [C.sizeof(abi.PacketConfig), abi.PacketConfig.codec.offset, abi.PacketConfig._reserved.offset] == [16, 0, 12]
+    assert consts == [abi.PACKET_MAGIC_CODED, abi.PACKET_RAW, abi.PACKET_BC1, abi.PACKET_BY_FILL, abi.PACKET_MAGIC, abi.PACKET_VERSION]
     assert (bc.MAGIC_CODED, bc.RAW, bc.BC1, bc.BY_FILL) == (abi.PACKET_MAGIC_CODED, abi.PACKET_RAW, abi.PACKET_BC1, abi.PACKET_BY_FILL)
     assert struct.pack("<I", abi.PACKET_MAGIC_CODED) == b"FVPC"
     text = open(os.path.join(ROOT, "include", "fovpt.h")).read()

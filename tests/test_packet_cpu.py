@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import header_layout
 import packet_ref as pk
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
 from packet_cases import IDS, JUNK, SHAPES, junk_canvas, mutations, random_frame, synthetic_raw
@@ -178,21 +179,15 @@ def test_untrusted_packets_under_sanitizers(tmp_path):
 
 
 # ---- 5. the ABI -----------------------------------------------------------------------------------------------------------------------
-def test_struct_mirrors_match_the_header(tmp_path):
+def test_struct_mirrors_match_the_header():
     fields = [("fovpt_packet_pass", abi.PacketPass, [n for n, _ in abi.PacketPass._fields_], {}),
               ("fovpt_packet_header", abi.PacketHeader, [n for n, _ in abi.PacketHeader._fields_], {"passes": "pass"})]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
-    for cname, _, names, ren in fields:
-        src += 'printf("%%zu", sizeof(%s));' % cname + "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, ren.get(n, n)) for n in names) + 'printf("\\n");'
-    src += 'printf("%u %d %d %d %d\\n", FOVPT_PACKET_MAGIC, FOVPT_PACKET_VERSION, FOVPT_PACKET_SLOTS, FOVPT_PACKET_NEAREST, FOVPT_PACKET_SMOOTH);return 0;}\n'
-    exe = str(tmp_path / "packet_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    lines = subprocess.check_output([exe]).decode().splitlines()
-    for (cname, T, names, _), line in zip(fields, lines):
-        got = [int(x) for x in line.split()]
+    lines, consts = header_layout.probe([(cname, names, ren) for cname, _, names, ren in fields],
+                                        ("FOVPT_PACKET_MAGIC", "FOVPT_PACKET_VERSION", "FOVPT_PACKET_SLOTS", "FOVPT_PACKET_NEAREST", "FOVPT_PACKET_SMOOTH"))
+    for (cname, T, names, _), got in zip(fields, lines):
         assert got[0] == C.sizeof(T) == {"fovpt_packet_pass": 32, "fovpt_packet_header": 128}[cname]
         assert got[1:] == [getattr(T, n).offset for n in names]
-    assert [int(x) for x in lines[2].split()] == [abi.PACKET_MAGIC, abi.PACKET_VERSION, abi.PACKET_SLOTS, abi.PACKET_NEAREST, abi.PACKET_SMOOTH]
+    assert consts == [abi.PACKET_MAGIC, abi.PACKET_VERSION, abi.PACKET_SLOTS, abi.PACKET_NEAREST, abi.PACKET_SMOOTH]
     assert (pk.MAGIC, pk.VERSION, pk.SLOTS, pk.NEAREST, pk.SMOOTH) == (abi.PACKET_MAGIC, abi.PACKET_VERSION, abi.PACKET_SLOTS, abi.PACKET_NEAREST, abi.PACKET_SMOOTH)
 
 

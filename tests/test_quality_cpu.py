@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import header_layout
 import quality_cases as qc
 import quality_ref as qr
 from fovpathtracing_optixcodelatest_amd import abi, lib
@@ -239,17 +240,9 @@ def test_host_under_the_sanitizers(cases, tmp_path):
 
 
 # ---- 5. the ABI ---------------------------------------------------------------------------------------------------------------------------
-def test_struct_mirrors_match_the_header(tmp_path):
+def test_struct_mirrors_match_the_header():
     structs = [("fovpt_quality_config", abi.QualityConfig), ("fovpt_quality_sums", abi.QualitySums)]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
-    for cname, cls in structs:
-        src += 'printf("%%zu", sizeof(%s));' % cname + "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, n) for n, _ in cls._fields_) + 'printf("\\n");'
-    src += "return 0;}\n"
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    lines = subprocess.check_output([exe], text=True).splitlines()
-    for (cname, cls), line in zip(structs, lines):
-        got = [int(x) for x in line.split()]
+    for (cname, cls), got in zip(structs, header_layout.layouts(*structs)):
         assert got[0] == C.sizeof(cls) and got[1:] == [getattr(cls, n).offset for n, _ in cls._fields_], cname
     assert C.sizeof(abi.QualityConfig) == 32 and C.sizeof(abi.QualitySums) == 1344
     hdr = open(os.path.join(ROOT, "include", "fovpt.h")).read()

@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import header_layout
 from fovpathtracing_optixcodelatest_amd import abi, lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,18 +19,12 @@ CONSTANTS = (("FOVPT_UPDATE_REBUILD_ASYNC", "UPDATE_REBUILD_ASYNC"), ("FOVPT_REB
              ("FOVPT_REBUILD_WAIT", "REBUILD_WAIT"), ("FOVPT_REBUILD_ADOPT", "REBUILD_ADOPT"))
 
 
-def test_constants_and_rebuild_info_mirror_the_header(tmp_path):
+def test_constants_and_rebuild_info_mirror_the_header():
     """abi.py's constants are the header's, and abi.RebuildInfo is fovpt_rebuild_info member for member (the header compiled by
     gcc says where each member lies)."""
     names = [f[0] for f in abi.RebuildInfo._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){'
-    src += "".join('printf("%%d ", %s);' % c for c, _ in CONSTANTS) + 'printf("\\n%zu", sizeof(fovpt_rebuild_info));'
-    src += "".join('printf(" %%zu", offsetof(fovpt_rebuild_info, %s));' % n for n in names) + "return 0;}\n"
-    exe = str(tmp_path / "rebuild_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", INCLUDE, "-", "-o", exe], input=src.encode(), check=True)
-    consts, layout = subprocess.check_output([exe]).decode().splitlines()
-    assert [int(x) for x in consts.split()] == [getattr(abi, a) for _, a in CONSTANTS]
-    got = [int(x) for x in layout.split()]
+    (got,), consts = header_layout.probe([("fovpt_rebuild_info", abi.RebuildInfo)], [c for c, _ in CONSTANTS])
+    assert consts == [getattr(abi, a) for _, a in CONSTANTS]
     assert got[0] == C.sizeof(abi.RebuildInfo) == 64
     assert got[1:] == [getattr(abi.RebuildInfo, n).offset for n in names]
     assert names == ["state", "last_error", "requested", "started", "adopted", "failed", "discarded", "snapshot_update", "ms_build"]

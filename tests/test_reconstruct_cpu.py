@@ -1,16 +1,13 @@
 """fovpt_reconstruct without a GPU: the C ABI of its structs (layout, defaults, argument checks) and properties of the
 reconstruction's definition, the numpy restatement in tests/reconstruct_ref.py that the GPU kernels are checked against."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_layout
 import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -21,13 +18,9 @@ def so():
 
 @pytest.mark.parametrize("struct, cname, size", [(abi.ReconstructConfig, "fovpt_reconstruct_config", 32),
                                                  (abi.GBufferPtrs, "fovpt_gbuffer_ptrs", 40)])
-def test_struct_mirrors_match_the_header(tmp_path, struct, cname, size):
+def test_struct_mirrors_match_the_header(struct, cname, size):
     names = [f[0] for f in struct._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%%zu", sizeof(%s));' % cname + "".join(
-        'printf(" %%zu", offsetof(%s, %s));' % (cname, n) for n in names) + "return 0;}\n"
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    got = header_layout.layout(cname, struct)
     assert got[0] == C.sizeof(struct) == size
     assert got[1:] == [getattr(struct, n).offset for n in names]
 

@@ -1,15 +1,13 @@
 """CPU tests of tests/refit_ref.py, the restatement the GPU refit of fovpt_update_vertices is checked against, on hand-built wide
 trees; and of the ABI mirror of fovpt_vertex_update."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_layout
 import refit_ref as rf
 from fovpathtracing_optixcodelatest_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 INF = F(np.inf)
 
@@ -156,13 +154,9 @@ def test_conservative_check_and_levels():
     assert rf.sah_cost(got_n, levels) >= 1.0
 
 
-def test_abi_mirror_matches_the_header(tmp_path):
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu %zu %zu %zu %d %d", '
-           'sizeof(fovpt_vertex_update), offsetof(fovpt_vertex_update, mesh), offsetof(fovpt_vertex_update, num_vertices), '
-           'offsetof(fovpt_vertex_update, vertex), FOVPT_UPDATE_DEVICE, FOVPT_UPDATE_REBUILD); return 0;}\n')
-    exe = str(tmp_path / "vu_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+def test_abi_mirror_matches_the_header():
+    (lay,), consts = header_layout.probe([("fovpt_vertex_update", ("mesh", "num_vertices", "vertex"))], ("FOVPT_UPDATE_DEVICE", "FOVPT_UPDATE_REBUILD"))
+    got = lay + consts
     V = abi.VertexUpdate
     assert got == [C_size(V), V.mesh.offset, V.num_vertices.offset, V.vertex.offset, abi.UPDATE_DEVICE, abi.UPDATE_REBUILD]
 

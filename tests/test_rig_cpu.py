@@ -5,16 +5,14 @@ statement, the validation rules on either side, and the ABI mirrors of the rig s
 Measured on this file's binary64 comparison (seeds 0 .. 11, depth up to 16, rotations and unit scales): the largest absolute error
 of a world or palette entry is 4.93e-7 of the rig's largest |entry|; the test asserts four times that."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_layout
 import rig_ref as rg
 from fovpathtracing_optixcodelatest_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 MEASURED_F64_ERROR = 4.93e-7
 
@@ -408,22 +406,16 @@ def test_accepted_on_either_side_of_every_rule():
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------
-def test_abi_mirrors_match_the_header(tmp_path):
+def test_abi_mirrors_match_the_header():
     fields = [("fovpt_rig_node", abi.RigNode, ("parent", "translation", "rotation", "scale")),
               ("fovpt_rig_binding", abi.RigBinding, ("mesh", "node", "num_joints", "_reserved", "joint_nodes", "inverse_bind")),
               ("fovpt_rig_channel", abi.RigChannel, ("target", "path", "interpolation", "num_keys", "times", "values")),
               ("fovpt_rig_clip", abi.RigClip, ("num_channels", "_reserved", "channels")),
               ("fovpt_rig_desc", abi.RigDesc, ("nodes", "num_nodes", "_reserved0", "bindings", "num_bindings", "_reserved1", "clips", "num_clips", "_reserved2"))]
-    exprs = []
-    for cname, _, names in fields:
-        exprs += ["sizeof(%s)" % cname] + ["offsetof(%s, %s)" % (cname, f) for f in names]
     consts = ["FOVPT_RIG_MAX_NODES", "FOVPT_RIG_MAX_CLIPS", "FOVPT_RIG_MAX_KEYS", "FOVPT_RIG_TRANSLATION", "FOVPT_RIG_ROTATION", "FOVPT_RIG_SCALE",
               "FOVPT_RIG_WEIGHTS", "FOVPT_RIG_STEP", "FOVPT_RIG_LINEAR"]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("' + "%zu " * len(exprs) + "%ld " * len(consts) + '", ' +
-           ", ".join(exprs) + ", " + ", ".join("(long)" + c for c in consts) + "); return 0;}\n")
-    exe = str(tmp_path / "rig_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    lays, values = header_layout.probe([(cname, names) for cname, _, names in fields], consts)
+    got = [x for lay in lays for x in lay] + values
     want = []
     for _, S, names in fields:
         want += [ctypes.sizeof(S)] + [getattr(S, f).offset for f in names]

@@ -2,17 +2,15 @@
 scalar loop that rounds after every operation, one joint against transform_ref, the overflow rule on either side of 2^127; and
 of the ABI mirrors of fovpt_mesh_skin and fovpt_skin_pose."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_layout
 import skin_ref as sk
 import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
@@ -158,15 +156,10 @@ def test_overflow_bound_on_either_side_of_two_to_the_127():
     assert 10 < n_accepted < 50
 
 
-def test_abi_mirrors_match_the_header(tmp_path):
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d", '
-           'sizeof(fovpt_mesh_skin), offsetof(fovpt_mesh_skin, mesh), offsetof(fovpt_mesh_skin, num_vertices), offsetof(fovpt_mesh_skin, num_joints), '
-           'offsetof(fovpt_mesh_skin, _reserved), offsetof(fovpt_mesh_skin, joints), offsetof(fovpt_mesh_skin, weights), '
-           'sizeof(fovpt_skin_pose), offsetof(fovpt_skin_pose, mesh), offsetof(fovpt_skin_pose, num_joints), offsetof(fovpt_skin_pose, matrices), '
-           'FOVPT_SKIN_MAX_JOINTS); return 0;}\n')
-    exe = str(tmp_path / "skin_layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+def test_abi_mirrors_match_the_header():
+    (s, p), consts = header_layout.probe([("fovpt_mesh_skin", ("mesh", "num_vertices", "num_joints", "_reserved", "joints", "weights")),
+                                          ("fovpt_skin_pose", ("mesh", "num_joints", "matrices"))], ("FOVPT_SKIN_MAX_JOINTS",))
+    got = s + p + consts
     S, P = abi.MeshSkin, abi.SkinPose
     assert got == [ctypes.sizeof(S), S.mesh.offset, S.num_vertices.offset, S.num_joints.offset, S._reserved.offset, S.joints.offset,
                    S.weights.offset, ctypes.sizeof(P), P.mesh.offset, P.num_joints.offset, P.matrices.offset, abi.SKIN_MAX_JOINTS]

@@ -1,17 +1,15 @@
 """fovpt_temporal without a GPU: the C ABI of its config (layout, defaults, null arguments) and properties of the definition, the
 numpy restatement in tests/temporal_ref.py that the GPU kernel is checked against."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_layout
 import reconstruct_ref as rr
 import temporal_ref as tr
 from fovpathtracing_optixcodelatest_amd import abi, lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
 
@@ -21,14 +19,11 @@ def so():
     return lib.load()
 
 
-def test_struct_mirror_matches_the_header(tmp_path):
+def test_struct_mirror_matches_the_header():
     cname, struct = "fovpt_temporal_config", abi.TemporalConfig
     names = [f[0] for f in struct._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "fovpt.h"\nint main(void){printf("%%zu %%d", sizeof(%s), FOVPT_TEMPORAL_MAX_HISTORY);' % cname + "".join(
-        'printf(" %%zu", offsetof(%s, %s));' % (cname, n) for n in names) + "return 0;}\n"
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-std=c99", "-x", "c", "-I", os.path.join(ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    (lay,), (max_history,) = header_layout.probe([(cname, struct)], ("FOVPT_TEMPORAL_MAX_HISTORY",))
+    got = [lay[0], max_history] + lay[1:]
     assert got[0] == C.sizeof(struct) == 32
     assert got[1] == abi.TEMPORAL_MAX_HISTORY == tr.MAX_HISTORY
     assert got[2:] == [getattr(struct, n).offset for n in names]
