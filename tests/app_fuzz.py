@@ -16,7 +16,11 @@ the library has learnt since: the same scene, config, skins and morphs as the ol
 and ten operations out of the old units and the new ones at the end of this file -- updates of kind "animated", "async" rebuilds
 on all five kinds and with no entries, rebuild_state with its four flag values, set_rig, focus_reset, four more refused calls, and
 a chain post -> focus -> expose -> packet (raw or coded) -> warp | warp_motion | lens.  script(seed) itself returns what it
-always returned: tests/test_app_fuzz_cpu.py pins a digest of the scripts of seeds 0 .. 31."""
+always returned: tests/test_app_fuzz_cpu.py pins a digest of the scripts of seeds 0 .. 31.
+
+script(seed, hdr=True) is a third family over HDR_SEEDS (FOVPT_FUZZHDR_FROM / FOVPT_FUZZHDR_TO widen it): the late script's scene,
+size, config, skins, morphs and rig of that seed, and ten operations that put fovpt_variance, fovpt_variance_filter, fovpt_bloom and
+fovpt_quality into the chain (see the section at the end of this file).  The late scripts and the hdr ones are pinned by digests too."""
 import os
 
 import numpy as np
@@ -700,11 +704,21 @@ class _LateDraw(_Draw):
             return self.focus_reset()
         return super().realize(t)
 
+    def tables(self):
+        """(the default seeds, the flags of their heads' updates, their forced units): what a family built on this one replaces."""
+        return LATE_DEFAULT_SEEDS, LATE_HEAD_FLAG, LATE_FORCED
+
+    def head_chains(self, default):
+        """What the chains of the head's two frames are asked to hold."""
+        return dict(step=True), dict(LATE_HEAD_CHAIN[self.seed]) if default else dict(step=True)
+
     def script(self):
         rng = self.rng
-        default = self.seed in LATE_DEFAULT_SEEDS
+        seeds, head_flag, forced = self.tables()
+        default = self.seed in seeds
         a, b, c = (LATE_KINDS[k] for k in (LATE_TRIPLES[self.seed] if default else rng.permutation(5)[:3]))
-        flags = LATE_HEAD_FLAG[self.seed] if default else (False, False, (False, True, "async")[int(rng.integers(0, 3))])
+        flags = head_flag[self.seed] if default else (False, False, (False, True, "async")[int(rng.integers(0, 3))])
+        heads = self.head_chains(default)
 
         def burst(kind, flag):
             if kind == "animated":
@@ -714,9 +728,8 @@ class _LateDraw(_Draw):
             others = [g for g in self.meshes_for(k) if g != self.x][:2]
             return self.update(k, form, rebuild=flag, meshes=sorted([self.x] + others))
         self.refusals, self.resized = 0, False
-        ops = [self.frame(want=dict(step=True)), burst(a, flags[0]), burst(b, flags[1]), burst(c, flags[2]),
-               self.frame(want=dict(LATE_HEAD_CHAIN[self.seed]) if default else dict(step=True))]
-        units = [tuple(tuple(dict(x) if isinstance(x, dict) else x for x in t) for t in u) for u in LATE_FORCED[self.seed]] if default else []
+        ops = [self.frame(want=heads[0]), burst(a, flags[0]), burst(b, flags[1]), burst(c, flags[2]), self.frame(want=heads[1])]
+        units = [tuple(tuple(dict(x) if isinstance(x, dict) else x for x in t) for t in u) for u in forced[self.seed]] if default else []
         room = TAIL_OPS - sum(len(u) for u in units)
         assert room >= 0
         if not any(t[0] == "f" for u in units for t in u):
@@ -732,5 +745,237 @@ class _LateDraw(_Draw):
         return self.s
 
 
-def script(seed, late=False):
-    return (_LateDraw if late else _Draw)(int(seed)).script()
+# ---- the hdr family: variance, variance filter, bloom, quality -----------------------------------------------------------------------
+# An hdr script is a late script's scene, size, config, skins, morphs and rig of the same seed with operations of its own, drawn from a
+# generator state seeded apart from both other families.  Its operations are the late ones and: variance_reset; the refusals
+# vfilter_no_image, variance_bad_config, bloom_bad_levels and quality_bad_ring; and a chain
+#     post -> variance -> vfilter -> focus -> bloom -> expose -> quality -> packet -> warp | warp_motion | lens
+# whose four new entries are dicts or None:
+#   variance  cfg (fovpt_variance_config's five fields), gbuffer "own" (NULL: traced by the call) | "temporal" (fovpt_temporal_gbuffer,
+#             only behind a temporal step of this chain), motion (the post step's vectors: exactly when the mask has MOTION), own (the
+#             context's image or a caller's), adopt (fovpt_rebuild_state(WAIT | ADOPT) between the step and the call)
+#   vfilter   cfg (four iteration counts 0 .. 3, demodulate, three sigmas), input "post" | "accum", variance "own" (NULL) | "given" (the
+#             pointer the variance call wrote), out_own; its G-buffer is the variance call's
+#   bloom     cfg (fovpt_bloom_config), in_place (out_color == in_color: only on the filter's or the focus step's output, which the
+#             chain does not read again), own
+#   quality   flags, ring_width, ref "post" | "frame", record_own, classes; the test image is the rgba8 the chain holds there, and the
+#             entry exists only where that is not the reference itself
+# The restatements of all four stages on a 192 x 128 frame take 0.3 s together (tests/test_app_fuzz_cpu.py measures it), so the BIG
+# scripts draw the filter's iteration counts like everybody.
+HDR_DEFAULT_SEEDS = range(0, 8)
+HDR_SEEDS = range(int(os.environ.get("FOVPT_FUZZHDR_FROM", HDR_DEFAULT_SEEDS.start)), int(os.environ.get("FOVPT_FUZZHDR_TO", HDR_DEFAULT_SEEDS.stop)))
+KARIS, GAINS, STATE = 1, 2, 4                            # FOVPT_BLOOM_*
+SSIM, PROFILE = 1, 2                                     # FOVPT_QUALITY_*
+BLOOM_MAX_LEVELS = 8
+HDR_VARIANCE_DEFAULTS = dict(history_cap=16, spatial_below=4, spatial_radius=3, depth_tolerance=0.02, normal_tolerance=0.1)      # variance_ref.MOMENT_DEFAULTS
+# what csrc/api_post.hip (variance_check, bloom_check) and csrc/api_view.hip (quality_check) refuse: one step outside each range
+VARIANCE_BAD = (("history_cap", 0), ("history_cap", 65), ("spatial_below", -1), ("spatial_radius", 0), ("spatial_radius", 4),
+                ("depth_tolerance", 1.5), ("normal_tolerance", 4.5))
+BLOOM_BAD_LEVELS = (0, BLOOM_MAX_LEVELS + 1)
+QUALITY_BAD_RING = (0, 65537)
+ITS = ("iterations_fovea", "iterations_middle", "iterations_periphery", "iterations_uniform")
+GAIN_NAMES = ("gain_fovea", "gain_middle", "gain_periphery", "gain_uniform")
+NO_MOTION = po.RECONSTRUCT | T_                          # a temporal step that writes no motion vectors
+# the kinds and flags of the head's three updates, and the chains of its two frames.  The first chain's bloom reads the exposure
+# state before any expose step, the second after the first chain's step (FIXED for seeds 1 and 6); "lit": knee >= threshold, so that
+# every pixel with any light passes the bright pass whatever the exposure (checked with bloom_ref on oracle frames of both scenes)
+HDR_HEAD_FLAG = [(False, False, "async"), (False, False, True), (False, False, False), (False, False, False),
+                 (False, False, True), (False, False, False), (False, False, False), (False, False, False)]
+HDR_HEAD_CHAIN = [
+    (dict(variance=dict(own=True), bloom=dict(flags=STATE | KARIS, lit=True), expose=("fixed" if s in (1, 6) else "auto")),
+     dict(variance=dict(gbuffer="temporal" if s % 2 == 0 else "own", adopt=(s == 0)), vfilter={}, bloom=dict(flags=STATE | (GAINS if s % 4 == 2 else 0), lit=True),
+          quality=dict(flags=s % 4), **(dict(last=("lens", 1, False)) if s == 0 else {})))
+    for s in range(8)]
+HDR_FORCED = [
+    # 0: variance_reset; a refused config between two steps of one history; a filter that does nothing; the context's own image
+    [(("variance_reset",), ("f", 1, (), False, dict(step=True, variance={}, vfilter=dict(iterations=(0, 0, 0, 0)), quality=dict(flags=0, record_own=False)))),
+     (("f", 1, (), False, dict(variance=dict(own=True))), ("x", "variance_bad_config"), ("f", 1, (), False, dict(variance=dict(own=True), vfilter=dict(variance="own"))))],
+    # 1: three views in flight with all four stages; temporal_reset, which leaves the moments: first a step with no motion, which
+    # reads the history at the pixel itself (a history that wrongly ended would show), then the tracked step whose motion is w = 0
+    # everywhere, on moments that are still there
+    [(("f", 3, (None, "u"), False, dict(step=True, variance={}, vfilter={}, bloom=dict(lit=True), quality={})),),
+     (("temporal_reset",), ("f", 1, (), False, dict(post="none", variance={})), ("f", 1, (), False, dict(step=True, variance={}))),
+     (("x", "bloom_bad_levels"),)],
+    # 2: expose_reset ahead of a bloom that reads the state; a rebuild between the frame and its chain
+    [(("expose_reset",), ("f", 1, (), False, dict(variance={}, bloom=dict(flags=STATE | GAINS, lit=True), expose="auto"))),
+     (("f", 1, (), ("vertices", True), dict(step=True, variance=dict(gbuffer="own"))),), (("x", "quality_bad_ring"),)],
+    # 3: a resize to the same size, then a step with no motion (with motion the step's w = 0 would hide a history that survived: the
+    # temporal history went too); a background build requested between the frame and its chain
+    [(("resize", "same"), ("f", 1, (), False, dict(post="none", variance=dict(gbuffer="own")))),
+     (("f", 1, (), ("transforms", "async"), dict(step=True, variance=dict(gbuffer="temporal"), quality=dict(flags=SSIM))),)],
+    # 4: another size: the filter refused before any variance step there, then accepted; bloom in place, 1 and 8 levels
+    [(("resize", "other"), ("f", 1, (), False, dict(variance=False, bloom=dict(levels=1, lit=True))), ("x", "vfilter_no_image"),
+      ("f", 1, (), False, dict(step=True, variance=dict(own=True), vfilter=dict(variance="own", out_own=True), bloom=dict(in_place=True, levels=BLOOM_MAX_LEVELS, lit=True))))],
+    # 5: set_scene; an adoption between the frame and its chain
+    [(("set_scene",), ("f", 1, (), False, dict(post=NO_MOTION, variance={}, bloom=dict(flags=STATE))), ("u", "empty", "host", "async"),
+      ("f", 1, (), False, dict(step=True, adopt_first=True, variance=dict(gbuffer="own"))))],
+    # 6: no post at all and a post without MOTION; a caller's variance image; the remaining quality flags; focus_reset, which
+    # leaves the moments, ahead of a step with no motion
+    [(("f", 1, (), False, dict(post="none", variance=dict(own=False), vfilter=dict(variance="given", input="accum"), bloom=dict(in_place=True, levels=1, lit=True),
+                               quality=dict(flags=PROFILE, ref="frame"))),),
+     (("f", 1, (), False, dict(post=NO_MOTION, variance={}, bloom=dict(flags=STATE), quality=dict(flags=SSIM | PROFILE))),),
+     (("focus_reset",), ("f", 1, (), False, dict(post="none", variance={})))],
+    # 7: the caller's gaze moved on ahead of everything that reads the frame as rendered
+    [(("f", 1, (), False, dict(step=True, moved_on=True, variance={}, vfilter={}, bloom=dict(flags=GAINS | KARIS, lit=True), quality=dict(classes=True, record_own=True))),),
+     (("expose_reset",), ("f", 1, (), False, dict(post=NO_MOTION, variance={}, bloom=dict(flags=STATE))))],       # (expose_reset leaves the moments too)
+]
+
+
+class _HdrDraw(_LateDraw):
+    def __init__(self, seed):
+        super().__init__(seed)                            # (the late script's scene, size, config, skins, morphs and rig)
+        self.rng = np.random.default_rng(54000 + seed)
+        self.s["hdr"] = True
+        self.s["delay_ms"] = 0
+        self.rendered = False                             # a frame at this size
+        self.var_own = None                               # the size the context's own variance image was written at
+
+    def variance_reset(self):
+        return dict(op="variance_reset")
+
+    def resize(self, how=None):
+        self.rendered, self.var_own = False, None
+        return super().resize(how)
+
+    def refused(self, which):
+        rng = self.rng
+        if which == "vfilter_no_image":
+            assert self.rendered and self.var_own != self.size
+            return dict(op="refused", which=which, code=E_NO_FRAME)
+        if which == "variance_bad_config":
+            name, v = VARIANCE_BAD[int(rng.integers(0, len(VARIANCE_BAD)))]
+            return dict(op="refused", which=which, field=name, value=v, code=E_INVALID)
+        if which == "bloom_bad_levels":
+            return dict(op="refused", which=which, value=int(BLOOM_BAD_LEVELS[int(rng.integers(0, 2))]), code=E_INVALID)
+        if which == "quality_bad_ring":
+            return dict(op="refused", which=which, value=int(QUALITY_BAD_RING[int(rng.integers(0, 2))]), code=E_INVALID)
+        return super().refused(which)
+
+    # ---- the chain
+    def hdr_chain(self, c, want):
+        """The late chain c with the four new entries; want forces what it names: post ("none" or a mask), expose ("auto", "fixed",
+        None), variance / vfilter / bloom / quality (False: absent; a dict: present, with these entries)."""
+        rng = self.rng
+        if "post" in want:
+            c["post"] = None if want["post"] == "none" else int(want["post"])
+        if "expose" in want:
+            c["expose"] = None if want["expose"] is None else dict(self.expose_config(), mode=AUTO if want["expose"] == "auto" else FIXED)
+        post = c["post"]
+        has_t, has_m = post is not None and bool(post & T_), post is not None and bool(post & M_)
+        present = lambda name, p: want.get(name) is not False and (want.get(name) is not None or rng.random() < p)
+        src = origin = "frame" if post is None else "post"
+
+        v = None
+        if present("variance", 0.7):
+            cap = int(rng.choice([2, 3, 16]))
+            below = int(rng.choice([0, 2, 4] if cap > 2 else [0, 2]))       # (spatial_below above history_cap + 1 is refused)
+            cfg = dict(history_cap=cap, spatial_below=below, spatial_radius=int(rng.integers(1, 4)),
+                       depth_tolerance=float(F(rng.uniform(0.005, 0.2))), normal_tolerance=float(F(rng.uniform(0.0, 1.0))))
+            v = dict(cfg=cfg, gbuffer="temporal" if has_t and rng.random() < 0.5 else "own", motion=has_m, own=bool(rng.random() < 0.6), adopt=False)
+            for k, x in (want.get("variance") or {}).items():
+                (cfg if k in cfg else v)[k] = x
+            assert v["gbuffer"] == "own" or has_t
+            if v["own"]:
+                self.var_own = self.size
+        f = None
+        if v is not None and present("vfilter", 0.7):
+            cfg = dict(zip(ITS, (int(x) for x in rng.integers(0, 4, 4))), demodulate=int(rng.integers(0, 2)),
+                       luminance_sigma=float(F(4.0 * np.exp2(rng.uniform(-1, 1)))), normal_sigma=float(F(0.5 * np.exp2(rng.uniform(-1, 1)))),
+                       depth_sigma=float(F(0.05 * np.exp2(rng.uniform(-1, 1)))))
+            f = dict(cfg=cfg, input="post" if post is not None and rng.random() < 0.6 else "accum",
+                     variance="own" if v["own"] and rng.random() < 0.5 else "given", out_own=bool(rng.random() < 0.5))
+            for k, x in (want.get("vfilter") or {}).items():
+                if k == "iterations":
+                    cfg.update(zip(ITS, x))
+                else:
+                    (cfg if k in cfg else f)[k] = x
+            assert (f["input"] == "accum" or post is not None) and (f["variance"] == "given" or v["own"])
+            src = origin = "vfilter"
+        if c["focus"] is not None:
+            src = origin = "focus"
+        b = None
+        if present("bloom", 0.6):
+            pick = lambda: float(F((0.0, 0.125, 1.0, rng.uniform(0, 1))[int(rng.integers(0, 4))]))
+            cfg = dict(flags=int(rng.integers(0, 8)), levels=int(rng.integers(1, BLOOM_MAX_LEVELS + 1)), threshold=float(F(np.exp2(rng.uniform(-6, 1)))),
+                       knee=float(F(np.exp2(rng.uniform(-6, 1)))) if rng.random() < 0.8 else 0.0, exposure=float(F(np.exp2(rng.uniform(0, 6)))),
+                       intensity=float(F(rng.uniform(0, 0.5))), spread=float(F(rng.uniform(0, 1))), **{g: pick() for g in GAIN_NAMES})
+            b = dict(cfg=cfg, in_place=bool(src in ("vfilter", "focus") and rng.random() < 0.4), own=bool(rng.random() < 0.5))
+            wb = dict(want.get("bloom") or {})
+            lit = wb.pop("lit", False)
+            for k, x in wb.items():
+                (cfg if k in cfg else b)[k] = x
+            if lit:
+                cfg["knee"] = max(cfg["knee"], cfg["threshold"])
+                cfg.update(gain_fovea=1.0, gain_uniform=1.0)
+            assert not b["in_place"] or src in ("vfilter", "focus")
+            origin = "bloom"
+        if c["expose"] is not None:
+            origin = "expose"
+        q = None
+        refs = [x for x in (("post",) if post is not None else ()) + ("frame",) if x != origin]
+        if refs and present("quality", 0.6):
+            q = dict(flags=int(rng.integers(0, 4)), ring_width=int(rng.choice([1, 3, 16])), ref=refs[int(rng.integers(0, len(refs)))],
+                     record_own=bool(rng.random() < 0.5), classes=bool(rng.random() < 0.5))
+            q.update(want.get("quality") or {})
+            assert q["ref"] in refs
+        c.update(variance=v, vfilter=f, bloom=b, quality=q)
+        return c
+
+    def frame(self, n=1, between=(), pre_chain=False, want=None):
+        want = dict(want) if isinstance(want, dict) else dict(step=True) if want in ("step", "step+packet") else {}
+        flag = False
+        if isinstance(pre_chain, tuple):
+            pre_chain, flag = pre_chain
+        late = {k: want[k] for k in ("step", "focus", "last", "codec", "adopt_first") if k in want}
+        if "post" in want and not (want["post"] != "none" and want["post"] & T_ and want["post"] & M_):
+            late.update(focus=None, last=(None,))         # (neither stage has a tracked step to lean on)
+        if (want.get("variance") or {}).get("adopt"):
+            late.setdefault("last", (None,))              # (a warp_motion on the step's G-buffer would be refused: the late family's case)
+        stepped = self.stepped
+        op = super().frame(n, between, pre_chain, late)
+        if flag:
+            op["pre_chain"]["rebuild"] = flag
+        if want.get("moved_on") and op["moved_on"] is None:
+            w, h = self.size
+            op["moved_on"] = dict(gaze=(int(self.rng.integers(-10, w + 11)), int(self.rng.integers(-10, h + 11))), subframe_index=int(self.rng.integers(4, 9)))
+        self.rendered = True
+        op["chain"] = self.hdr_chain(op["chain"], want)
+        post = op["chain"]["post"]
+        self.stepped = stepped or (post is not None and bool(post & T_))
+        return op
+
+    def draw_unit(self, room):
+        rng = self.rng
+        while True:
+            u = rng.random()
+            if u < 0.45:
+                unit = super().draw_unit(room)
+            elif u < 0.70:
+                n = int(rng.integers(1, 4))
+                unit = (("f", n, (None,) * (n - 1), bool(rng.random() < 0.3), None),)
+            elif u < 0.80:
+                unit = ((("variance_reset",),), (("variance_reset",), ("f", 1, (), False, dict(variance={}))))[int(rng.integers(0, 2))]
+            elif u < 0.90:
+                unit = ((("x", "bloom_bad_levels"),), (("x", "quality_bad_ring"),),
+                        (("f", 1, (), False, dict(variance={})), ("x", "variance_bad_config"), ("f", 1, (), False, dict(variance={}))),
+                        (("resize", "other"), ("f", 1, (), False, dict(variance=False)), ("x", "vfilter_no_image")))[int(rng.integers(0, 4))]
+            else:
+                unit = (("expose_reset",), ("f", 1, (), False, dict(bloom=dict(flags=STATE))))
+            if len(unit) <= room:
+                return unit
+
+    def realize(self, t):
+        if t[0] == "x" and t[1] == "vfilter_no_image" and self.refusals < MAX_REFUSED and not (self.rendered and self.var_own != self.size):
+            return self.temporal_reset()                  # (nothing to refuse here: something harmless in its place)
+        return super().realize(t)
+
+    def tables(self):
+        return HDR_DEFAULT_SEEDS, HDR_HEAD_FLAG, HDR_FORCED
+
+    def head_chains(self, default):
+        first, second = HDR_HEAD_CHAIN[self.seed] if default else (dict(variance={}), dict(variance={}))
+        return dict(first, step=True), dict(second, step=True)
+
+
+def script(seed, late=False, hdr=False):
+    return (_HdrDraw if hdr else _LateDraw if late else _Draw)(int(seed)).script()

@@ -17,6 +17,9 @@ of refit_ref over the model's positions, and the link words a refit must not tou
 
 LateModel, at the end of this file, is the model of the late scripts (app_fuzz.script(seed, late=True)): the rig, the focus state,
 the record of the background build, what the last temporal step knew of its interval and the stamp of the last G-buffer trace.
+HdrModel, behind it, is the model of the hdr scripts (app_fuzz.script(seed, hdr=True)): the moment history of fovpt_variance, the
+size of the context's own variance image and the rendered frame's camera, for the four stages variance, variance filter, bloom and
+quality inside the chain.
 
 dry_run() is the part of the model that needs no renderer: the positions.  (oracle.OracleScene exposes trace() and no tree,
 so there is no hierarchy for refit_ref to follow without a GPU.)"""
@@ -940,3 +943,236 @@ class LateModel(AppModel):
                 os.environ.pop(DELAY, None)
             else:
                 os.environ[DELAY] = had
+
+
+# ---- the hdr family's model ----------------------------------------------------------------------------------------------------
+M_ = po.MOTION
+B_KARIS, B_GAINS, B_STATE = abi.BLOOM_KARIS, abi.BLOOM_GAINS, abi.BLOOM_EXPOSURE_STATE
+
+
+class _Frame(_Ptr):
+    """A per-pixel device buffer at a known address where a helper asks for a tensor: data_ptr(), and cpu().numpy() as the bytes
+    of a frame of `channels` 32-bit words per pixel."""
+
+    def __init__(self, r, p, size, channels):
+        super().__init__(p)
+        self.r, self.shape = r, (size[1], size[0], 4 * channels)
+
+    def cpu(self):
+        return self
+
+    def numpy(self):
+        return self.r.download(self.p, np.empty(self.shape, np.uint8))
+
+
+class HdrModel(LateModel):
+    """LateModel for the scripts of app_fuzz.script(seed, hdr=True): fovpt_variance, fovpt_variance_filter, fovpt_bloom and
+    fovpt_quality inside the chain.  On top of LateModel it keeps on the host: the previous moment history (None: the next step
+    has none; fovpt_variance_reset, fovpt_resize -- to the same size too -- and fovpt_set_scene end it, fovpt_temporal_reset,
+    fovpt_expose_reset and fovpt_focus_reset do not), the size the context's own variance image was written at, the camera of the
+    frame as rendered, and the exposure state (AppModel's, which fovpt_bloom reads with EXPOSURE_STATE).  Every stage's passes,
+    gaze and FOV_OFF flag are those of self.frame_as_rendered, never the launch parameters' at call time.
+
+    Log entries, one per stage of a chain: ("variance", had_history, spatial_count, kept_count, reject_depth, reject_class, moved,
+    pixels) -- pixels that took the window, pixels with n >= 2, taps rejected by depth and by class, whether the step's interval
+    moved a mesh, and the frame's pixel count, which "the window on some pixels but not all" needs across resizes; ("vfilter",
+    changed_pixels); ("bloom", flags, steps of the exposure state it read or None without EXPOSURE_STATE, texels of pyramid level 0
+    that are not +0); ("quality", flags, differing_pixels)."""
+
+    def __init__(self, oracle, s, model, cam, probe):
+        from test_variance_gpu import Moments
+        self.var_own_size = None
+        self.cam_rendered = None
+        super().__init__(oracle, s, model, cam, probe)
+        self.mom = Moments(self.r, self.cfg_frame)            # (its `prev` is the model's history; fills and camera are given per step)
+
+    @property
+    def var_prev(self):
+        return self.mom.prev
+
+    @var_prev.setter
+    def var_prev(self, hist):
+        self.mom.prev = hist
+
+    def frames(self, op):
+        from test_variance_gpu import camera_of
+        super().frames(op)
+        self.cam_rendered = camera_of(self.r)             # (nothing below changes the camera: the chain's stages use the rendered one)
+
+    def rendered_fills(self):
+        """(fill with 1 where no pass writes, pass, fill with 0 there, FOV_OFF) of the frame as rendered."""
+        import reconstruct_ref as rr
+        import variance_ref as vr
+        (w, h), gaze, (ri, ro), uniform = self.frame_as_rendered
+        fill, pas = vr.fills(w, h, gaze, ri, ro, int(uniform))
+        return fill, pas, rr.writers(w, h, gaze, ri, ro, int(uniform))[0], int(uniform)
+
+    # ---- the four stages
+    def variance(self, v, motion, motion_ptr):
+        """One fovpt_variance on the accum buffer through test_variance_gpu.Moments.step, with the motion buffer the post step
+        wrote and the rendered frame's fills and camera -> (the restatement's variance image, the address the call wrote it to,
+        the G-buffer argument it was given)."""
+        r = self.r
+        g = r.temporal_gbuffer() if v["gbuffer"] == "temporal" else None
+        assert (motion is not None) == v["motion"]
+        had = self.mom.prev is not None
+        hist, var, rec = self.mom.step(v["cfg"], g, None, motion, own=v["own"], label="variance", motion_ptr=motion_ptr,
+                                       fill=self.rendered_fills()[0], cam=self.cam_rendered)
+        if g is None:
+            self.trace_fresh = True                           # (the call's own trace, and the same rays again for the comparison)
+        moved = motion is not None and self.last is not None and bool(self.last["moved"].any())
+        self.log.append(("variance", had, int(rec["spatial"].sum()), int((hist[..., 2] >= 2).sum()),
+                         int(rec["reject_depth"].sum()), int(rec["reject_class"].sum()), moved, int(hist[..., 2].size)))
+        if v["own"]:
+            self.var_own_size = self.size
+        self._late_keep.append(self.mom.out)
+        return var, self.mom.out.data_ptr() if self.mom.out is not None else r.variance_buffers()[0], g
+
+    def vfilter(self, f, var, var_ptr, g, color, ptr):
+        """One fovpt_variance_filter through test_variance_gpu.run_filter, on the device buffers the stages before it wrote."""
+        from test_variance_gpu import run_filter
+        r = self.r
+        inp, in_ptr = (color, ptr) if f["input"] == "post" else (r.downloadAccum(), None)
+        assert f["variance"] == "given" or self.var_own_size == self.size
+        fill, pas, _, _ = self.rendered_fills()
+        outs = {}
+        want, _ = run_filter(self.oracle, r, self.cfg_frame, f["cfg"], inp, var, g, f["out_own"], "vfilter", in_ptr=in_ptr,
+                             var_ptr=var_ptr if f["variance"] == "given" else None, fills=(fill, pas), outs=outs)
+        if g is None:
+            self.trace_fresh = True
+        self._late_keep += outs["keep"]
+        self.log.append(("vfilter", int((bits(want[..., :3]) != bits(np.asarray(inp, F)[..., :3])).any(axis=-1).sum())))
+        return want, outs["color"], outs["got_rgba"], outs["rgba"]
+
+    def bloom(self, b, color, ptr):
+        import bloom_ref as br
+        from test_bloom_gpu import check, device_outputs
+        r = self.r
+        d = b["cfg"]
+        inp = r.downloadAccum() if color is None else color
+        _, _, fill0, uniform = self.rendered_fills()
+        E, steps = None, None
+        if d["flags"] & B_STATE:                              # the record's exposure once a step has made one, else the config's
+            steps = int(self.ex.state["steps"])
+            E = self.ex.state["exposure"] if steps else d["exposure"]
+        if b["in_place"]:
+            assert ptr is not None
+            out = (_Frame(r, ptr, self.size, 4), device_outputs(self.size)[1])
+        else:
+            out = None if b["own"] else device_outputs(self.size)
+        want = check(self.oracle, r, d, inp, (fill0, uniform), in_ptr=ptr, out=out, E=E, label="bloom")
+        off = br.level_offsets(self.size[0], self.size[1], d["levels"])
+        lit = int((bits(want["pyramid"][:off[1]]) != 0).any(axis=-1).sum())
+        self.log.append(("bloom", d["flags"], steps, lit))
+        self._late_keep.append(out)
+        if out is None:
+            out_c, out_p = r.bloomBuffers()
+        else:
+            out_c, out_p = out[0].data_ptr(), out[1].data_ptr()
+        return want["color"], out_c, want["rgba"], out_p
+
+    def quality(self, q, test, test_ptr, ref, ref_ptr):
+        import ctypes as C
+        import quality_cases as qc
+        import quality_ref as qr
+        from test_quality_gpu import device_bytes, qcfg, sums_of
+        r = self.r
+        (w, h), gaze, (ri, ro), uniform = self.frame_as_rendered
+        cfg, full = qcfg(dict(flags=q["flags"], ring_width=q["ring_width"]))
+        n = C.sizeof(abi.QualitySums)
+        assert n == 1344
+        out = None if q["record_own"] else device_bytes(n)
+        cls = device_bytes(w * h, 0xee) if q["classes"] else None
+        r.qualityAsync(ref_ptr, test_ptr, cfg, out.data_ptr() if out is not None else None, cls.data_ptr() if cls is not None else None)
+        got = r.readQuality(sums=True) if out is None else None
+        r.synchronize()
+        got = sums_of(out) if out is not None else got
+        classes = qr.classes_of_frame(w, h, gaze, ri, ro, int(uniform))
+        want = qr.quality(test, ref, classes, gaze, full)
+        assert bytes(got) == bytes(qc.sums_of_dict(want)), "quality: record"
+        if cls is not None:
+            assert np.array_equal(cls.cpu().numpy().reshape(h, w), classes), "quality: class map"
+        self.log.append(("quality", q["flags"], int(sum(want["differing"]))))
+
+    def chain(self, c, moved_on=None):
+        """post -> variance -> vfilter -> focus -> bloom -> expose -> quality -> packet (of the unwarped frame) -> warp | warp_motion
+        | lens: every hand-over a device pointer into the stage before."""
+        if "variance" not in c:
+            return super().chain(c, moved_on)
+        r = self.r
+        f = r.launchParams.frame
+        if moved_on is not None:
+            f.c.x, f.c.y = moved_on["gaze"][0] & 0xffffffff, moved_on["gaze"][1] & 0xffffffff
+            f.subframe_index = moved_on["subframe_index"]
+        color = ptr = None
+        frame_ptr = int(f.frame_buffer)
+        rgba, rgba_ptr = self.last_rgba, None if not self._bufs or self._bufs[-1] is None else self._bufs[-1][1].data_ptr()
+        post_rgba = post_ptr = motion = motion_ptr = None
+        if c["post"] is not None:
+            had = self.prev is not None
+            out = self.step(stages=c["post"])
+            color, ptr = out["color"], r.post_buffers()[0]
+            rgba, rgba_ptr = r.downloadPostPixels(), r.post_buffers()[1]
+            post_rgba, post_ptr = rgba, rgba_ptr
+            if c["post"] & M_:
+                motion, motion_ptr = out["motion"], r.motion_buffer()
+            self.log.append(("post", c["post"], had))
+        if c["variance"] is not None:
+            if c["variance"]["adopt"]:                        # an adoption between the step's trace and the call that is handed it
+                assert self.rec["flight"]
+                self.rebuild_state(True, True)
+            var, var_ptr, g = self.variance(c["variance"], motion, motion_ptr)
+            if c["vfilter"] is not None:
+                color, ptr, rgba, rgba_ptr = self.vfilter(c["vfilter"], var, var_ptr, g, color, ptr)
+        if c["focus"] is not None:
+            color, ptr, rgba, rgba_ptr = self.focus(c["focus"], color, ptr)
+        if c["bloom"] is not None:
+            color, ptr, rgba, rgba_ptr = self.bloom(c["bloom"], color, ptr)
+        if c["expose"] is not None:
+            out = self.expose(c["expose"], r.downloadAccum() if color is None else color, ptr)
+            color, ptr = out["color"], r.expose_buffers()[0]
+            rgba, rgba_ptr = out["rgba"], r.expose_buffers()[1]
+        if c["quality"] is not None:
+            ref, ref_ptr = (post_rgba, post_ptr) if c["quality"]["ref"] == "post" else (self.last_rgba, frame_ptr)
+            self.quality(c["quality"], rgba, rgba_ptr, ref, ref_ptr)
+        if c["packet"]:
+            self.packet(rgba, rgba_ptr, c["codec"])
+        la = c["last"]
+        if la is not None and la["stage"] == "lens":
+            self.lens(la, color, ptr)
+        elif la is not None:
+            self.warp(la, color, ptr, rgba, rgba_ptr)
+
+    # ---- events
+    def resize(self, size):
+        super().resize(size)
+        self.var_prev, self.var_own_size = None, None         # (to the same size as well)
+
+    def set_scene(self):
+        super().set_scene()
+        self.var_prev = None
+
+    def refused(self, op, check=True):
+        from test_bloom_gpu import bcfg
+        from test_quality_gpu import qcfg
+        from test_variance_gpu import vcfg
+        r, which = self.r, op["which"]
+        if which == "vfilter_no_image":                       # a frame at this size, and no variance step into the context's image yet
+            assert self.rendered and self.var_own_size != self.size
+            with_pytest_code(op["code"], lambda: r.variance_filter())
+        elif which == "variance_bad_config":                  # refused before anything is enqueued: the history goes on
+            with_pytest_code(op["code"], lambda: r.variance(vcfg(**{op["field"]: op["value"]})))
+        elif which == "bloom_bad_levels":
+            with_pytest_code(op["code"], lambda: r.bloom(bcfg(dict(levels=op["value"]))[0]))
+        elif which == "quality_bad_ring":
+            with_pytest_code(op["code"], lambda: r.qualityAsync(int(r.launchParams.frame.frame_buffer), None, qcfg(dict(ring_width=op["value"]))[0]))
+        else:
+            return super().refused(op, check)
+
+    def run_op(self, op):
+        if op["op"] == "variance_reset":
+            self.r.variance_reset()
+            self.var_prev = None
+            self.check_info()
+        else:
+            super().run_op(op)

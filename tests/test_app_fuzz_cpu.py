@@ -27,7 +27,20 @@ result if the builder has finished, which no script can know without rebuild_sta
 happened (tests/app_model.LateModel), the walker counts a situation only where it is certain -- with one exception that cannot be
 made certain: "an update between snapshot and adoption" is counted where updates follow a request without a wait and
 rebuild_state(WAIT | ADOPT) follows them; whether the adoption then finds a snapshot older than the positions depends on whether
-those updates met the build still running (any of them that met it READY adopted it itself, with nothing in between)."""
+those updates met the build still running (any of them that met it READY adopted it itself, with nothing in between).
+
+The late scripts are pinned by a digest as well (seeds 0 .. 31, computed before the hdr family was added).  The hdr family
+(af.script(seed, hdr=True)) gets the same five tests and a digest through walk_hdr(), which follows the tracking and the interval,
+the events since the last variance step, the moment history, the context's variance image, the exposure state's last event and
+the background build, and checks every new chain entry against the ranges the library validates:
+  operations   HDR_OPERATIONS: the four stages, variance_reset, the four refusals, both G-buffers, both images, both filter inputs
+               and outputs, both quality references
+  situations   HDR_SITUATIONS, listed in test_the_hdr_default_seeds_reach_every_situation
+  own units    HDR_OWN: what each default seed's forced units and head chains are there for
+test_the_restatements_of_an_hdr_chain_stay_finite_and_quick runs the four restatements without a renderer on a synthetic frame for
+every size and chain config of the default scripts: moments twice, the filter, bloom and quality of one chain take 0.34 s at
+192 x 128 on the CPU (0.04 s at 64 x 45, 0.09 s at 96 x 64), beside post_ref.post's 0.21 s there, so the 192 x 128 scripts draw the
+filter's iteration counts like every other size."""
 import hashlib
 
 import numpy as np
@@ -666,3 +679,422 @@ def test_each_late_default_seed_holds_its_own_units(walked_late):
     for seed, want in LATE_OWN.items():
         missing = [w for w in want if w not in walked_late[seed][2][0]]
         assert not missing, (seed, missing)
+
+
+# sha256 over the late scripts of seeds 0 .. 31, computed with the generator as it was before the hdr family was added
+LATE_SCRIPTS_DIGEST = "b9dd2b1fbe149d781aa76f68c4196fa1e1ace7183cc1e9b409e72f73c8b2d502"
+
+
+def test_the_late_scripts_are_what_they_were():
+    h = hashlib.sha256()
+    for seed in range(32):
+        _feed(h, af.script(seed, late=True))
+    assert h.hexdigest() == LATE_SCRIPTS_DIGEST
+    assert not any("hdr" in af.script(seed, late=True) or "variance" in o["chain"] for seed in (0, 9) for o in af.script(seed, late=True)["ops"] if o["op"] == "frame")
+
+
+# ---- the hdr family ----------------------------------------------------------------------------------------------------------------
+# what the library accepts (csrc/api_post.hip: variance_check, variance_filter_check, bloom_check; csrc/api_view.hip: quality_check)
+def _variance_ok(c):
+    return (1 <= c["history_cap"] <= 64 and 0 <= c["spatial_below"] <= c["history_cap"] + 1 and 1 <= c["spatial_radius"] <= 3
+            and 0.0 <= c["depth_tolerance"] <= 1.0 and 0.0 <= c["normal_tolerance"] <= 4.0)
+
+
+def walk_hdr(s):
+    """walk() for an hdr script -> (set of names, refused operations, frames with a chain).  It follows on its own what decides
+    which situation a chain is in: the tracking and the interval, the events since the last variance step, whether a moment
+    history is alive, the size of the context's own variance image, the exposure state's last event and the background build
+    ("no", "yes", or "maybe" once an update that may have adopted it has run)."""
+    seen, refused, chained = set(), 0, 0
+    ops, size = s["ops"], tuple(s["size"])
+    # the head's mesh: the one all three updates of the first interval share
+    head = set.intersection(*(set(o["poses"]) if o["kind"] != "animated" else {b["mesh"] for b in s["rig"]["bindings"]} for o in ops[1:4]))
+    assert head
+    rig = s["rig"]
+    tracking = stepped = False
+    moved = set()                                         # the meshes moved since the last temporal step
+    events = set()                                        # what happened since the last variance step
+    var_live, var_own, rendered = False, None, False
+    ex_last, ex_any = None, False                         # the exposure state's last event; any step since the scene was set
+    flight = "no"
+
+    def update(u, where):
+        nonlocal flight
+        flag = u["rebuild"]
+        meshes = {b["mesh"] for b in rig["bindings"]} if u["kind"] == "animated" else set(u["poses"])
+        assert flag in (False, True, "async") and (u["kind"] != "animated" or rig is not None)
+        if flag is True:
+            flight = "no"
+        elif meshes and flight == "yes":
+            flight = "maybe"
+        if flag == "async" and flight == "no":
+            flight = "yes"
+        moved.update(meshes)
+        seen.add("update " + where)
+
+    for i, op in enumerate(ops):
+        kind = op["op"]
+        if kind == "update":
+            update(op, "alone")
+        elif kind == "refused":
+            refused += 1
+            which = op["which"]
+            seen.add("refused:" + which)
+            if which == "vfilter_no_image":
+                assert rendered and var_own != size and op["code"] == af.E_NO_FRAME
+                assert ops[i - 1]["op"] == "frame" and ops[i - 2]["op"] == "resize" and ops[i - 1]["chain"]["variance"] is None
+            elif which == "variance_bad_config":
+                assert not _variance_ok(dict(af.HDR_VARIANCE_DEFAULTS, **{op["field"]: op["value"]})) and op["code"] == af.E_INVALID
+                a, b = ops[i - 1], ops[i + 1] if i + 1 < len(ops) else None
+                if a["op"] == "frame" and a["chain"]["variance"] is not None and b is not None and b["op"] == "frame" and b["chain"]["variance"] is not None:
+                    seen.add("a refused config between two steps of one history")
+            elif which == "bloom_bad_levels":
+                assert not 1 <= op["value"] <= af.BLOOM_MAX_LEVELS and op["code"] == af.E_INVALID
+            elif which == "quality_bad_ring":
+                assert not 1 <= op["value"] <= 65536 and op["code"] == af.E_INVALID
+        elif kind in ("set_skins", "set_morphs"):
+            rig = None
+        elif kind == "set_rig":
+            rig = op["rig"]
+        elif kind == "rebuild_state":
+            if op["adopt"] and op["wait"] and flight == "yes":
+                flight = "no"
+            elif op["adopt"] and flight != "no":
+                flight = "maybe"
+        elif kind == "frame":
+            n = len(op["views"])
+            assert 1 <= n <= 3 and len(op["between"]) == n - 1
+            for b in op["between"]:
+                if b is not None and b["op"] == "update":
+                    update(b, "between")
+                elif b is not None:
+                    refused += 1
+            rendered = True
+            c = op["chain"]
+            v, f, bl, q = (c[k] for k in ("variance", "vfilter", "bloom", "quality"))
+            ahead = set()
+            if op["adopt_first"] and flight == "yes":
+                ahead.add("an adoption")
+                flight = "no"
+            elif op["adopt_first"]:
+                flight = "no" if flight == "no" else "maybe"
+            if op["pre_chain"] is not None:
+                u = op["pre_chain"]
+                update(u, "between a render and its post chain")
+                ahead.add({True: "a rebuild", "async": "a background build requested", False: "a refit"}[u["rebuild"]])
+            chained += any(c[k] is not None for k in ("post", "expose", "focus", "last", "variance", "bloom", "quality")) or c["packet"]
+            post = c["post"]
+            assert post is None or post in po.VALID_STAGES
+            has_t, has_m = post is not None and bool(post & po.TEMPORAL), post is not None and bool(post & po.MOTION)
+            untracked_step = has_m and not stepped
+            over_head = has_m and stepped and tracking and head <= moved
+            if has_t:
+                tracking = tracking or has_m
+                stepped, moved = True, set()
+            origin = src = "frame" if post is None else "post"
+            if v is not None:
+                seen.add("variance")
+                assert _variance_ok(v["cfg"]) and v["motion"] == has_m and (v["gbuffer"] == "own" or has_t)
+                assert v["cfg"]["history_cap"] in (2, 3, 16) and v["cfg"]["spatial_below"] in (0, 2, 4)
+                seen.add("variance on " + ("the temporal G-buffer" if v["gbuffer"] == "temporal" else "its own trace"))
+                seen.add("variance into " + ("the context's image" if v["own"] else "a caller's image"))
+                if v["adopt"]:
+                    assert flight == "yes" and v["gbuffer"] == "temporal"
+                    seen.add("an adoption between the step and the variance call that takes its G-buffer")
+                    flight = "no"
+                if over_head:
+                    seen.add("variance with motion over an interval that moved the head's mesh")
+                if untracked_step:
+                    seen.add("variance with motion from an untracked step")
+                if post is None:
+                    seen.add("variance with no post at all")
+                elif not has_m:
+                    seen.add("variance behind a post without MOTION")
+                if size == (3, 50):
+                    seen.add("variance on the (3, 50) frame")
+                if size == af.BIG and s["config"]["chains_per_frame"] == 2:
+                    seen.add("variance on the 192 x 128 two-chain frame")
+                for e in events:
+                    seen.add("variance after " + e)
+                    # read at the pixel itself: a history that wrongly survived a reset that ends it would show, and so would one
+                    # that wrongly ended at a reset that leaves it (which needs a history to be there)
+                    if not has_m and (var_live or e in ENDS_THE_MOMENTS):
+                        seen.add("variance without motion after " + e)
+                events = set()
+                for a in ahead:
+                    seen.add("%s between the frames and a chain with a variance step" % a)
+                    seen.add("an update or adoption ahead of a variance step on " + ("the temporal G-buffer" if v["gbuffer"] == "temporal" else "its own trace"))
+                if var_live:
+                    seen.add("a variance step that continues a history")
+                var_live = True
+                if v["own"]:
+                    var_own = size
+            if f is not None:
+                assert v is not None and all(0 <= f["cfg"][k] <= 3 for k in af.ITS) and f["cfg"]["demodulate"] in (0, 1)
+                assert all(1e-3 < f["cfg"][k] < 1e3 for k in ("luminance_sigma", "normal_sigma", "depth_sigma"))
+                assert (f["input"] == "accum" or post is not None) and (f["variance"] == "given" or v["own"])
+                seen.add("vfilter")
+                seen.add("a filter on " + ("the context's variance image" if f["variance"] == "own" else "a caller's variance image" if not v["own"] else "the context's image by its address"))
+                seen.add("a filter of " + ("the post colour" if f["input"] == "post" else "the accum buffer"))
+                seen.add("a filter into " + ("the context's buffers" if f["out_own"] else "a caller's buffers"))
+                if not any(f["cfg"][k] for k in af.ITS):
+                    seen.add("a filter with no iterations")
+                origin = src = "vfilter"
+            if c["focus"] is not None:
+                origin = src = "focus"
+            if bl is not None:
+                d = bl["cfg"]
+                assert 0 <= d["flags"] <= 7 and 1 <= d["levels"] <= af.BLOOM_MAX_LEVELS and all(0.0 <= d[g] <= 1.0 for g in af.GAIN_NAMES)
+                assert 1e-3 < d["threshold"] < 1e3 and 1e-3 < d["exposure"] < 1e3 and 0 <= d["knee"] < 1e3 and 0 <= d["intensity"] <= 1 and 0 <= d["spread"] <= 1
+                assert not bl["in_place"] or src in ("vfilter", "focus")
+                seen.add("bloom")
+                seen.add("bloom flags %d" % d["flags"])
+                seen.add("bloom levels %d" % d["levels"])
+                if bl["in_place"]:
+                    seen.add("bloom in place")
+                if d["flags"] & af.STATE:
+                    seen.add("bloom state " + {None: "before any expose step", "reset": "after expose_reset", "auto": "after an AUTO step", "fixed": "after a FIXED step"}[ex_last])
+                origin = "bloom"
+            if c["expose"] is not None:
+                ex_last = "auto" if c["expose"]["mode"] == af.AUTO else "fixed"
+                ex_any = True
+                origin = "expose"
+            if q is not None:
+                assert q["flags"] in (0, 1, 2, 3) and q["ring_width"] in (1, 3, 16) and q["ref"] != origin and (q["ref"] == "frame" or post is not None)
+                seen.add("quality")
+                seen.add("quality flags %d" % q["flags"])
+                seen.add("quality into " + ("the context's record" if q["record_own"] else "a caller's record"))
+                seen.add("quality against " + ("the post step's rgba8" if q["ref"] == "post" else "the frame buffer"))
+                if q["classes"]:
+                    seen.add("quality with a class map")
+            if v is not None and f is not None and bl is not None and q is not None:
+                if n == 3 and s["config"]["frames_in_flight"] == 2:
+                    seen.add("three views in flight ahead of all four stages")
+            if op["moved_on"] is not None and f is not None and bl is not None and bl["cfg"]["flags"] & af.GAINS and q is not None and q["classes"]:
+                seen.add("moved_on ahead of the variance filter, bloom with GAINS and quality with a class map")
+            la = c["last"]
+            if la is not None and la["stage"] == "warp_motion":
+                assert has_t and has_m
+        elif kind == "resize":
+            events.add("a resize to the same size" if tuple(op["size"]) == size else "a resize to another size")
+            size = tuple(op["size"])
+            stepped, var_live, var_own, rendered = False, False, None, False
+        elif kind == "set_scene":
+            events.add("set_scene")
+            rig, flight = None, "no"
+            tracking = stepped = var_live = False
+            moved = set()
+            ex_last, ex_any = None, False
+        elif kind == "temporal_reset":
+            events.add("temporal_reset")
+            stepped = False
+        elif kind == "expose_reset":
+            events.add("expose_reset")
+            ex_last = "reset" if ex_any else None
+        elif kind == "variance_reset":
+            seen.add("variance_reset")
+            events.add("variance_reset")
+            var_live = False
+        else:
+            assert kind == "focus_reset", kind
+            events.add("focus_reset")
+    return seen, refused, chained
+
+
+ENDS_THE_MOMENTS = ("variance_reset", "a resize to the same size", "a resize to another size", "set_scene")
+LEAVES_THE_MOMENTS = ("temporal_reset", "expose_reset", "focus_reset")
+HDR_OPERATIONS = ["variance", "vfilter", "bloom", "quality", "variance_reset", "refused:vfilter_no_image", "refused:variance_bad_config",
+                  "refused:bloom_bad_levels", "refused:quality_bad_ring", "variance on the temporal G-buffer", "variance on its own trace",
+                  "variance into the context's image", "variance into a caller's image", "a filter of the post colour", "a filter of the accum buffer",
+                  "a filter into the context's buffers", "a filter into a caller's buffers", "quality against the post step's rgba8",
+                  "quality against the frame buffer"]
+HDR_SITUATIONS = (["variance with motion over an interval that moved the head's mesh", "variance with motion from an untracked step",
+                   "variance behind a post without MOTION", "variance with no post at all", "variance on the (3, 50) frame",
+                   "variance on the 192 x 128 two-chain frame"]
+                  + ["variance after " + e for e in ("variance_reset", "temporal_reset", "expose_reset", "a resize to the same size", "a resize to another size", "set_scene")]
+                  + ["variance without motion after a resize to the same size", "variance without motion after set_scene"]
+                  + ["variance without motion after " + e for e in LEAVES_THE_MOMENTS]      # (on a live history: it must go on)
+                  + ["%s between the frames and a chain with a variance step" % a for a in ("a rebuild", "a background build requested", "an adoption")]
+                  + ["an update or adoption ahead of a variance step on its own trace", "an update or adoption ahead of a variance step on the temporal G-buffer",
+                     "an adoption between the step and the variance call that takes its G-buffer",
+                     "moved_on ahead of the variance filter, bloom with GAINS and quality with a class map", "three views in flight ahead of all four stages",
+                     "bloom state before any expose step", "bloom state after expose_reset", "bloom state after an AUTO step", "bloom state after a FIXED step",
+                     "bloom in place", "bloom levels 1", "bloom levels %d" % af.BLOOM_MAX_LEVELS, "a filter with no iterations",
+                     "a filter on the context's variance image", "a filter on a caller's variance image", "quality into the context's record",
+                     "quality into a caller's record", "quality with a class map", "a refused config between two steps of one history",
+                     "a variance step that continues a history"]
+                  + ["quality flags %d" % k for k in range(4)]
+                  + ["refused:" + k for k in ("vfilter_no_image", "variance_bad_config", "bloom_bad_levels", "quality_bad_ring")])
+
+
+@pytest.fixture(scope="module")
+def walked_hdr():
+    out = {}
+    for seed in af.HDR_DEFAULT_SEEDS:
+        s = af.script(seed, hdr=True)
+        model, _ = af.scene_of(s)
+        out[seed] = (s, model, walk_hdr(s))
+    return out
+
+
+def test_an_hdr_script_is_a_pure_function_of_the_seed():
+    for seed in (0, 2, 5):
+        assert _same(af.script(seed, hdr=True), af.script(seed, hdr=True))
+    for seed in (0, 3, 9):                               # the late script's scene, size, config, skins, morphs and rig; operations of its own
+        a, b = af.script(seed, hdr=True), af.script(seed, late=True)
+        assert all(_same(a[k], b[k]) for k in ("scene", "size", "config", "post", "skins", "morphs", "rig")) and not _same(a["ops"], b["ops"])
+    orders = {tuple(o["op"] for o in af.script(seed, hdr=True)["ops"][5:]) for seed in range(8, 32) if seed % 8 not in (2, 5)}
+    assert len(orders) >= 12, len(orders)
+
+
+def test_every_hdr_script_does_something(walked_hdr):
+    """Ten operations, at most 2 refused calls, a frame group in the tail, and every chain entry valid (walk_hdr asserts the
+    library's ranges): for the default seeds and the next 24, all drawn; every default script holds one of the new stages."""
+    more = {}
+    for seed in range(8, 32):
+        s = af.script(seed, hdr=True)
+        more[seed] = (s, None, walk_hdr(s))
+    for seed, (s, _, (seen, refused, chained)) in list(walked_hdr.items()) + list(more.items()):
+        assert len(s["ops"]) == af.OPS == 10
+        assert refused <= af.MAX_REFUSED and chained >= 3 and any(o["op"] == "frame" for o in s["ops"][5:]), (seed, refused, chained)
+        assert "variance" in seen, seed
+    drawn = set().union(*(w[2][0] for w in more.values()))
+    assert len({x for x in drawn if x.startswith("bloom flags")}) == 8       # every subset of KARIS, GAINS and EXPOSURE_STATE is drawn
+
+
+def test_the_hdr_default_seeds_reach_every_operation(walked_hdr):
+    seen = set().union(*(w[2][0] for w in walked_hdr.values()))
+    missing = [w for w in HDR_OPERATIONS if w not in seen]
+    assert not missing, missing
+
+
+def test_the_hdr_default_seeds_reach_every_situation(walked_hdr):
+    """A variance step with motion from an interval in which the head's mesh moved, from an untracked step (w = 0 everywhere), with
+    no motion (a post without MOTION, no post at all); on the (3, 50) frame and on the 192 x 128 two-chain frame; after each of
+    variance_reset, temporal_reset, expose_reset, a resize to the same size, to another size and set_scene, and with no motion (so
+    that the history is read at the pixel itself and a reset's effect on it shows) after a resize to the same size and set_scene,
+    which end the moments, and on a live history after temporal_reset, expose_reset and focus_reset, which leave them; an update with a
+    rebuild, one that requests a background build and an adoption, each between the frames and a chain with a variance step, on
+    its own trace and on the temporal G-buffer; moved_on ahead of the filter, bloom with GAINS and quality with a class map; three
+    views with two frames in flight ahead of all four stages; bloom with EXPOSURE_STATE before any expose step, after
+    expose_reset, after an AUTO and after a FIXED step; bloom in place, with 1 level and with 8; a filter with no iterations, one
+    on the context's image (variance = NULL) and one on a caller's; quality into the context's record and a caller's, with each
+    flag subset; each of the four refusals."""
+    seen = set().union(*(w[2][0] for w in walked_hdr.values()))
+    missing = [w for w in HDR_SITUATIONS if w not in seen]
+    assert not missing, missing
+
+
+def test_hdr_shapes_and_budgets(walked_hdr):
+    sizes = set()
+    for seed, (s, model, _) in walked_hdr.items():
+        c, (w, h) = s["config"], s["size"]
+        sizes.add((w, h))
+        assert max(c["spp"]) <= 4 and 1 <= c["max_depth"] <= 3
+        assert (w, h) == af.BIG if c["chains_per_frame"] == 2 else (w, h) in af.SIZES
+        assert all(tuple(o["size"]) in af.SIZES + [af.BIG] for o in s["ops"] if o["op"] == "resize")
+    assert (3, 50) in sizes and af.BIG in sizes and {s["scene"][0] for s, _, _ in walked_hdr.values()} == {"cornell", "atrium"}
+
+
+def test_hdr_dry_run_keeps_every_position_finite(walked_hdr, oracle):
+    for seed, (s, model, _) in walked_hdr.items():
+        vtx = am.dry_run(s, model, oracle)
+        assert np.isfinite(vtx).all() and vtx.shape[0] == sum(m.vertex.shape[0] for m in model.meshes)
+
+
+# what each hdr default seed's forced units and head chains (af.HDR_FORCED, af.HDR_HEAD_CHAIN) are there for
+HDR_OWN = {
+    0: ["variance after variance_reset", "a refused config between two steps of one history", "a filter with no iterations",
+        "a filter on the context's variance image", "an adoption between the step and the variance call that takes its G-buffer", "quality into a caller's record"],
+    1: ["three views in flight ahead of all four stages", "variance after temporal_reset", "variance without motion after temporal_reset",
+        "variance with motion from an untracked step", "refused:bloom_bad_levels", "bloom state after a FIXED step"],
+    2: ["variance after expose_reset", "bloom state after expose_reset", "a rebuild between the frames and a chain with a variance step", "refused:quality_bad_ring"],
+    3: ["variance after a resize to the same size", "variance without motion after a resize to the same size", "a background build requested between the frames and a chain with a variance step",
+        "an update or adoption ahead of a variance step on the temporal G-buffer", "variance on the 192 x 128 two-chain frame"],
+    4: ["variance on the (3, 50) frame", "variance after a resize to another size", "refused:vfilter_no_image", "bloom in place", "bloom levels 1",
+        "bloom levels %d" % af.BLOOM_MAX_LEVELS],
+    5: ["variance after set_scene", "variance without motion after set_scene", "an adoption between the frames and a chain with a variance step", "bloom state before any expose step"],
+    6: ["variance with no post at all", "variance behind a post without MOTION", "a filter on a caller's variance image", "quality flags 2", "quality flags 3",
+        "variance without motion after focus_reset"],
+    7: ["moved_on ahead of the variance filter, bloom with GAINS and quality with a class map", "quality into the context's record", "quality with a class map",
+        "variance without motion after expose_reset"],
+}
+
+
+def test_each_hdr_default_seed_holds_its_own_units(walked_hdr):
+    for seed, want in HDR_OWN.items():
+        missing = [w for w in want if w not in walked_hdr[seed][2][0]]
+        assert not missing, (seed, missing)
+
+
+# sha256 over the hdr scripts of seeds 0 .. 31
+HDR_SCRIPTS_DIGEST = "c98b0d9b11011f4e389da841ae8831b29acd7abc817c10a1484f869c349b53a5"
+
+
+def test_the_hdr_scripts_are_what_they_were():
+    h = hashlib.sha256()
+    for seed in range(32):
+        _feed(h, af.script(seed, hdr=True))
+    assert h.hexdigest() == HDR_SCRIPTS_DIGEST
+
+
+def test_the_restatements_of_an_hdr_chain_stay_finite_and_quick():
+    """No renderer: for every frame size and every chain config of the default hdr scripts, variance_ref.moments twice (the second
+    on the first's history, with motion), vfilter, bloom_ref.bloom and quality_ref.quality on a synthetic frame -- a tilted plane
+    with a hole of misses, a noisy colour with black pixels and spikes.  Finite inputs give finite outputs, and the slowest size's
+    time is printed and bounded: the model runs these after every chain."""
+    import time
+    import bloom_ref as br
+    import quality_ref as qr
+    import variance_ref as vr
+    cam = dict(eye=(0.0, 0.0, 0.0), U=(1.0, 0.0, 0.0), V=(0.0, 1.0, 0.0), W=(0.0, 0.0, -1.0))
+    slowest = {}
+    for seed in af.HDR_DEFAULT_SEEDS:
+        s = af.script(seed, hdr=True)
+        size, c = tuple(s["size"]), s["config"]
+        for op in s["ops"]:
+            if op["op"] == "resize":
+                size = tuple(op["size"])
+            ch = op["chain"] if op["op"] == "frame" else None
+            if ch is None or ch["variance"] is None:
+                continue
+            w, h = size
+            rng = np.random.default_rng(seed)
+            Y, X = np.mgrid[0:h, 0:w].astype(F)
+            z = (F(5.0) + F(0.05) * X + F(0.02) * Y).astype(F)
+            pos = np.stack([(X - w / 2) * z / w, (Y - h / 2) * z / w, -z, z], axis=-1).astype(F)
+            pos[h // 3:h // 2, w // 3:w // 2, 3] = -1.0
+            nrm = np.zeros((h, w, 4), F)
+            nrm[..., 2] = 1.0
+            gb = dict(position=pos, normal=nrm, albedo=rng.uniform(0, 1, (h, w, 4)).astype(F))
+            color = np.exp2(rng.uniform(-8, 2, (h, w, 4))).astype(F)
+            color[rng.random((h, w)) < 0.1, :3] = 0.0
+            color[rng.random((h, w)) < 0.02, :3] = 500.0
+            gaze = op["views"][-1]["gaze"]
+            fill, pas = vr.fills(w, h, gaze, c["r_inner"], c["r_outer"], c["uniform"])
+            t0 = time.perf_counter()
+            vc = dict(vr.MOMENT_DEFAULTS, **ch["variance"]["cfg"])
+            hist, var = vr.moments(None, color, gb, cam, fill, None, vc)
+            mv = np.zeros((h, w, 4), F)
+            mv[..., :2], mv[..., 2], mv[..., 3] = rng.uniform(-1.5, 1.5, (h, w, 2)), hist[..., 3], 1.0
+            hist, var = vr.moments(hist, color, gb, cam, fill, mv, vc)
+            assert np.isfinite(hist).all() and np.isfinite(var).all() and (hist[..., 2] >= 1).all()
+            out = color
+            if ch["vfilter"] is not None:
+                fc = dict(vr.FILTER_DEFAULTS, **ch["vfilter"]["cfg"])
+                out, _ = vr.vfilter(color, var, gb, fill, vr.iteration_map(fill, pas, fc, c["uniform"]), fc)
+                assert np.isfinite(out).all()
+            if ch["bloom"] is not None:
+                import reconstruct_ref as rr
+                got = br.bloom(None, out, ch["bloom"]["cfg"], None, rr.writers(w, h, gaze, c["r_inner"], c["r_outer"], c["uniform"])[0], c["uniform"])
+                assert np.isfinite(got["color"]).all() and np.isfinite(got["pyramid"]).all()
+                out = got["color"]
+            if ch["quality"] is not None:
+                code = lambda img: np.clip(np.asarray(img)[..., 0] * 255.0, 0, 255).astype(np.uint32) * np.uint32(0x010101)
+                q = qr.quality(code(out), code(color), qr.classes_of_frame(w, h, gaze, c["r_inner"], c["r_outer"], c["uniform"]), gaze,
+                               dict(flags=ch["quality"]["flags"], ring_width=ch["quality"]["ring_width"]))
+                assert sum(q["pixels"]) == w * h
+            slowest[size] = max(slowest.get(size, 0.0), time.perf_counter() - t0)
+    print("the restatements of one hdr chain, slowest per size:", {k: round(v, 3) for k, v in sorted(slowest.items())})
+    assert af.BIG in slowest and (3, 50) in slowest
+    assert slowest[af.BIG] < 5.0                          # (a few seconds at 192 x 128 would ask for fewer periphery iterations)

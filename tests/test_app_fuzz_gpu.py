@@ -22,7 +22,23 @@ as the only test of a process, where it also pays for loading the library, the o
 3.6 s inside the suite.  The restatements' share is small: post_ref.post with every stage takes 0.05 s at 127 x 41 and 0.21 s at
 192 x 128 on the CPU.  The late seeds and the old ones in one run of this module on an MI355X (the first test of the process
 carries 12 s of start-up): old seeds 0.04 ... 0.82 s (seed 2), late seeds 0.06 ... 0.76 s (seed 2, an atrium; seed 5: 0.68 s),
-the late directed test 0.39 s; inside the whole suite the slowest were old seed 2 with 0.90 s and late seed 5 with 0.68 s."""
+the late directed test 0.39 s; inside the whole suite the slowest were old seed 2 with 0.90 s and late seed 5 with 0.68 s.
+
+The hdr family (af.script(seed, hdr=True), app_model.HdrModel; FOVPT_FUZZHDR_FROM / FOVPT_FUZZHDR_TO widen it) puts fovpt_variance,
+fovpt_variance_filter, fovpt_bloom and fovpt_quality into the chain: post -> variance -> variance_filter -> focus -> bloom -> expose
+-> quality -> packet -> warp | warp_motion | lens, every hand-over a device pointer into the stage before, with the operation
+variance_reset and the refusals vfilter_no_image, variance_bad_config, bloom_bad_levels and quality_bad_ring (argument checks that
+return before anything is enqueued).  The model keeps the moment history, the size of the context's own variance image, the rendered
+frame's camera and the exposure state on the host and compares every stage bit for bit with variance_ref, bloom_ref and quality_ref,
+always with the passes and gaze of the frame as rendered.  What a drawn frame happens to show (a history carried over a moved mesh, a
+filter that changed pixels, a lit bloom level, an exposure taken from a state with steps, differing pixels under fovpt_quality) is
+printed per seed and asserted over the default seeds together.  Its directed case: the tall block of the Cornell box moved between
+two moment steps. Time, in one run of this module on an MI355X: the hdr seeds 0.14 ... 0.91 s (seed 5, an atrium at 96 x 64 with
+five chains; seed 2: 0.82 s, seeds 7 and 3 at 192 x 128: 0.69 and 0.64 s), the late seeds of the same run 0.06 ... 0.69 s (seed 2)
+and the old ones 0.05 ... 0.72 s behind the process's first test, test_moments_follow_a_moved_block 0.10 s, the summary test
+nothing it has not run already; three times the slowest late seed is 2.1 s, and no new test comes near it.  Inside the whole suite
+the slowest were hdr seed 5 with 0.91 s and hdr seed 2 with 0.84 s, beside late seed 2 with 0.73 s.  As the only test of a
+process an hdr seed takes 3.7 ... 4.7 s, the directed test 12 s, start-up included."""
 import numpy as np
 import pytest
 
@@ -222,5 +238,162 @@ def test_an_adoption_between_a_step_and_its_warp(oracle):
         on4 = (prim != 0xffffffff) & (m.mesh_of_prim[np.where(prim == 0xffffffff, 0, prim).astype(np.int64)] == 4)
         assert on4.sum() > 60 and (out["motion"][on4][:, :2] != 0).any()     # the tall block's own motion, from tracked positions
         m.check_info()
+    finally:
+        m.close()
+
+
+# ---- the hdr family ----------------------------------------------------------------------------------------------------------------
+HDR_LOGS = {}                                            # seed -> (script, the model's log)
+
+
+def _hdr(oracle, seed):
+    """Runs an hdr seed once per process; a run that raised is remembered and raises again from the record (see _late)."""
+    from app_model import HdrModel
+    if seed not in HDR_LOGS:
+        HDR_LOGS[seed] = None
+        s = af.script(seed, hdr=True)
+        model, cam = af.scene_of(s)
+        m = HdrModel(oracle, s, model, cam, PROBE)
+        try:
+            m.run()
+            HDR_LOGS[seed] = (s, m.log)
+        except Exception as e:
+            HDR_LOGS[seed] = e
+            raise
+        finally:
+            m.close()
+    got = HDR_LOGS[seed]
+    if got is None or isinstance(got, Exception):
+        raise AssertionError("hdr seed %d has failed in this process already, it is not run again: %r" % (seed, got))
+    return got
+
+
+HDR_STAGES = ("variance", "vfilter", "bloom", "quality")
+
+
+def _hdr_conditions(logs):
+    """What keeps the sweep from being vacuous, on the models' logs -> {condition: met}.  A variance entry is ("variance",
+    had_history, spatial_count, kept_count, reject_depth, reject_class, moved, pixels)."""
+    v = [x for x in logs if x[0] == "variance"]
+    return {
+        "a variance step with a history over a moved mesh: pixels kept, taps rejected, the window on some pixels and not on all":
+            any(x[1] and x[6] and x[3] > 0 and x[4] + x[5] > 0 and 0 < x[2] < x[7] for x in v),
+        "a filter changed pixels": any(x[0] == "vfilter" and x[1] > 0 for x in logs),
+        "a bloom lit level 0": any(x[0] == "bloom" and x[3] > 0 for x in logs),
+        "a bloom took the exposure of a state with steps": any(x[0] == "bloom" and x[2] for x in logs),
+        "a quality measurement saw differing pixels": any(x[0] == "quality" and x[2] > 0 for x in logs),
+    }
+
+
+@pytest.mark.parametrize("seed", af.HDR_SEEDS)
+def test_random_hdr_application(oracle, seed):
+    """An hdr script on one context (app_model.HdrModel compares every stage of every chain bit for bit with its restatement, the
+    state on the host): every chain entry of the script left exactly one log entry (the refusals are operations of their own and
+    leave none).  The conditions against vacuity depend on what a drawn frame shows; they are printed here for every seed and
+    asserted over the default seeds together (test_the_hdr_default_seeds_together)."""
+    s, log = _hdr(oracle, seed)
+    chains = [o["chain"] for o in s["ops"] if o["op"] == "frame"]
+    print("hdr seed %d:" % seed, [x for x in log if x[0] in HDR_STAGES + ("adopt", "race")])
+    print("hdr seed %d:" % seed, _hdr_conditions(log))
+    for stage in HDR_STAGES:
+        assert len([x for x in log if x[0] == stage]) == sum(c[stage] is not None for c in chains), stage
+    assert len([x for x in log if x[0] == "post"]) >= 2
+
+
+def test_the_hdr_default_seeds_together(oracle):
+    logs = [x for seed in af.HDR_DEFAULT_SEEDS for x in _hdr(oracle, seed)[1]]
+    missed = [k for k, met in _hdr_conditions(logs).items() if not met]
+    assert not missed, missed
+
+
+def test_moments_follow_a_moved_block(oracle):
+    """On the Cornell box at 64 x 45, three tracked steps, each followed by fovpt_variance with the step's motion vectors and
+    G-buffer; then the tall block (mesh 4) is moved sideways by fovpt_update_transforms and a fourth frame, step and variance call
+    follow.  On the restatement (which the device equals bit for bit: HdrModel.variance): the block's pixels carry their history
+    along by the block's own motion, the pixels it uncovered start again and take the window, taps are rejected by depth.  The
+    restatement with no motion and with the interval before's motion each differ from the device on the block: the test can tell.
+    Then fovpt_variance_reset ends the history; fovpt_temporal_reset does not: a call with motion = NULL behind it continues the
+    history (and differs from the restatement without one), while the step's own motion is w = 0 everywhere and starts every pixel
+    again."""
+    import variance_ref as vr
+    from app_model import HdrModel
+    model = scenes.cornell_box()
+    s = dict(seed="directed-hdr", size=(64, 45), ops=[], late=True, hdr=True, skins={}, morphs={}, rig=None,
+             config=dict(uniform=0, r_inner=8, r_outer=18, spp=(1, 2, 4, 1), max_depth=2, frames_in_flight=0, chains_per_frame=0),
+             post=dict(temporal=dict(history_fovea=3, history_middle=5, history_periphery=8, history_uniform=6)))
+    m = HdrModel(oracle, s, model, scenes.CORNELL_CAMERA, PROBE)
+    r = m.r
+    stages = po.RECONSTRUCT | po.TEMPORAL | po.MOTION
+    cfg = dict(vr.MOMENT_DEFAULTS, spatial_below=2)
+    vd = dict(cfg=cfg, gbuffer="temporal", motion=True, own=True, adopt=False)
+    view = dict(gaze=(28, 20), subframe_index=0, eye=(0.0, 0.0, 0.0))
+    chain = dict(post=stages, variance=vd, vfilter=None, focus=None, bloom=None, expose=None, quality=None, packet=False, codec=None, last=None)
+    frame = dict(op="frame", views=[view], between=[], pre_chain=None, chain=chain, sync=True, moved_on=None)
+
+    def on_block(gb):
+        prim = gb["prim"]
+        return (prim != 0xffffffff) & (m.mesh_of_prim[np.where(prim == 0xffffffff, 0, prim).astype(np.int64)] == 4)
+
+    def one(motion_of=None):
+        """A frame, a step and a variance call -> (step output, history before, history after, the restatement's record)."""
+        m.frames(frame)
+        out = m.step(stages=stages)
+        before = m.var_prev
+        m.variance(vd, out["motion"], r.motion_buffer())
+        rec = {}
+        hist, _ = vr.moments(before, r.downloadAccum(), out["gb"], m.cam_rendered, m.rendered_fills()[0], out["motion"], cfg, rec)
+        assert np.array_equal(bits(hist), bits(m.var_prev))
+        return out, before, hist, rec
+    try:
+        for _ in range(2):
+            m.run_op(frame)
+        out3, _, hist3, _ = one()
+        assert (hist3[..., 2] == 3).mean() > 0.9                             # a static scene: three steps of history
+        was = on_block(out3["gb"])
+        m.update({4: tf.rotation_translation(0.0, (368.0, 0.0, 351.0), (-45.0, 0.0, 0.0))}, kind="transforms")
+        out, before, hist, rec = one()
+        now = on_block(out["gb"])
+        n, mv = hist[..., 2], out["motion"]
+        back = now & (mv[..., 3] == 1)
+        assert now.sum() > 60 and back.sum() > 30 and (np.abs(mv[back][:, 0]) > 2.0).mean() > 0.9      # several pixels, by its own motion
+        # the block took its history along: of its 174 pixels the restatement keeps one on 139 (the rest are its leading edge,
+        # which lands on what was wall a frame ago and is rejected by depth, and the pixels whose landing lies outside the block)
+        assert (n[back] >= 2).sum() > 120 and (n[back] >= 2).mean() > 0.75
+        # what it uncovered starts again and takes the window: 39 of 41 pixels (two at its foot land within the depth tolerance
+        # of the floor beside it)
+        gone = was & ~now
+        assert gone.sum() > 30 and (n[gone] == 1).mean() > 0.9 and rec["spatial"][gone & (n == 1)].all()
+        assert rec["reject_depth"].sum() > 0 and rec["reject_depth"][gone].sum() > 0
+        print("moved block: %d pixels on it, %d with a history, %d uncovered, %d of them new; taps rejected by depth %d, by class %d"
+              % (now.sum(), (n[back] >= 2).sum(), gone.sum(), (n[gone] == 1).sum(), rec["reject_depth"].sum(), rec["reject_class"].sum()))
+        for label, other in (("no motion", None), ("the interval before's motion", out3["motion"])):
+            leak, _ = vr.moments(before, r.downloadAccum(), out["gb"], m.cam_rendered, m.rendered_fills()[0], other, cfg)
+            assert not np.array_equal(bits(leak[now]), bits(hist[now])), label
+        r.variance_reset()
+        m.var_prev = None
+        _, _, hist, _ = one()
+        assert (hist[..., 2] == 1).all()
+        one()
+        # fovpt_temporal_reset leaves the moments.  Read at the pixel itself (motion = NULL) the history of two steps goes on to
+        # three: a moment history that ended with the temporal one would give n == 1, which the restatement without a history shows
+        r.temporal_reset()
+        m.reset()
+        m.frames(frame)
+        out = m.step(stages=stages)
+        assert (out["motion"][..., 3] == 0).all()
+        before = m.var_prev
+        assert before is not None and (before[..., 2] == 2).mean() > 0.9
+        m.variance(dict(vd, motion=False), None, None)                       # (asserts device == restatement on the model's history)
+        hist = m.var_prev
+        assert np.array_equal(hist[..., 2], before[..., 2] + 1) and (hist[..., 2] == 3).mean() > 0.9      # a static scene: every pixel goes on
+        ended, _ = vr.moments(None, r.downloadAccum(), out["gb"], m.cam_rendered, m.rendered_fills()[0], None, cfg)
+        assert (ended[..., 2] == 1).all() and not np.array_equal(bits(ended), bits(hist))
+        # ... and the step right behind a temporal reset says of no pixel where it was (w = 0): with that motion the restatement
+        # starts every pixel again, on moments that are still there
+        r.temporal_reset()
+        m.reset()
+        out, before, hist, _ = one()
+        assert before is not None and (out["motion"][..., 3] == 0).all() and (hist[..., 2] == 1).all()
+        print("after temporal_reset, motion with w = 0: n == 1 on %d of %d pixels" % ((hist[..., 2] == 1).sum(), hist[..., 2].size))
     finally:
         m.close()

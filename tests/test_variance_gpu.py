@@ -112,15 +112,19 @@ class Moments:
         self.r, self.cfg, self.prev = r, cfg, None
         self.fill, _ = frame_fills(r, cfg)
 
-    def step(self, d, gbuffer=None, sample=None, motion=None, own=True, label=None):
+    def step(self, d, gbuffer=None, sample=None, motion=None, own=True, label=None, motion_ptr=None, fill=None, cam=None):
         """One fovpt_variance (gbuffer: abi.GBufferPtrs or None; sample, motion: host arrays or None) compared with the restatement
-        -> (the restatement's history, its variance image, its record)."""
+        -> (the restatement's history, its variance image, its record).  motion_ptr: the device buffer that holds `motion` already
+        (default: uploaded here); fill, cam: the rendered frame's, where r.launchParams no longer hold them (default: self.fill and
+        the launch parameters' camera).  self.out: the caller's image the call wrote (a device tensor), None for the context's own."""
         r = self.r
         f = r.launchParams.frame
         size = (f.size.x, f.size.y)
-        keep = [upload(a) if a is not None else None for a in (sample, motion)]
-        out = None if own else device_frame(size)
-        r.variance(vcfg(**d), gbuffer, keep[0].data_ptr() if sample is not None else None, keep[1].data_ptr() if motion is not None else None,
+        keep = [upload(a) if a is not None else None for a in (sample, motion if motion_ptr is None else None)]
+        out = self.out = None if own else device_frame(size)
+        if motion is not None and motion_ptr is None:
+            motion_ptr = keep[1].data_ptr()
+        r.variance(vcfg(**d), gbuffer, keep[0].data_ptr() if sample is not None else None, motion_ptr if motion is not None else None,
                    out.data_ptr() if out is not None else None)
         r.synchronize()
         var_ptr, mom_ptr = r.variance_buffers()
@@ -129,9 +133,10 @@ class Moments:
         gb = r.downloadGBuffer(gbuffer if gbuffer is not None else r.gbuffer())       # (the same camera: what the call traced)
         rec = {}
         full = dict(vr.MOMENT_DEFAULTS, **d)
-        hist, var = vr.moments(self.prev, sample if sample is not None else r.downloadAccum(), gb, camera_of(r), self.fill, motion, full, rec)
-        assert np.array_equal(bits(got_hist), bits(hist)), label
-        assert np.array_equal(bits(got_var), bits(var)), label
+        hist, var = vr.moments(self.prev, sample if sample is not None else r.downloadAccum(), gb, cam if cam is not None else camera_of(r),
+                               self.fill if fill is None else fill, motion, full, rec)
+        assert np.array_equal(bits(got_hist), bits(hist)), (label, "history", int((bits(got_hist) != bits(hist)).any(axis=-1).sum()))
+        assert np.array_equal(bits(got_var), bits(var)), (label, "image", int((bits(got_var) != bits(var)).any(axis=-1).sum()))
         self.prev = hist
         return hist, var, rec
 
@@ -196,20 +201,29 @@ def test_a_camera_slide_with_real_motion_vectors():
 
 
 # ---- 2. the filter, bit for bit --------------------------------------------------------------------------------------------------------
-def run_filter(oracle, r, cfg, d, color, variance, gbuffer, own, label, record=None):
+def run_filter(oracle, r, cfg, d, color, variance, gbuffer, own, label, record=None, in_ptr="upload", var_ptr="upload", fills=None, outs=None):
+    """One fovpt_variance_filter of color with variance (host arrays) compared with the restatement -> (its colour, the iteration
+    map).  in_ptr, var_ptr: the device pointers that hold the two already, or None for the call's NULL (the accum buffer, the
+    context's own image); default: both uploaded here.  fills: (fill, pass) of the rendered frame where r.launchParams no longer
+    hold its gaze.  outs: a dict that receives color and rgba, the addresses written, and keep, the tensors behind them."""
     f = r.launchParams.frame
     size = (f.size.x, f.size.y)
-    dc, dv = upload(color), upload(variance)
+    dc, dv = upload(color) if in_ptr == "upload" else None, upload(variance) if var_ptr == "upload" else None
+    in_ptr, var_ptr = dc.data_ptr() if dc is not None else in_ptr, dv.data_ptr() if dv is not None else var_ptr
     if own:
-        r.variance_filter(fcfg(**d), gbuffer, dc.data_ptr(), dv.data_ptr())
+        r.variance_filter(fcfg(**d), gbuffer, in_ptr, var_ptr)
         got_c, got_p = r.downloadVarianceFiltered()
+        ptrs, kept = r.variance_filter_buffers(), []
     else:
         oc, op = device_frame(size), device_frame(size, 1)
-        r.variance_filter(fcfg(**d), gbuffer, dc.data_ptr(), dv.data_ptr(), oc.data_ptr(), op.data_ptr())
+        r.variance_filter(fcfg(**d), gbuffer, in_ptr, var_ptr, oc.data_ptr(), op.data_ptr())
         r.synchronize()
         got_c, got_p = host(oc), host(op, "rgba")
+        ptrs, kept = (oc.data_ptr(), op.data_ptr()), [oc, op]
+    if outs is not None:
+        outs.update(color=ptrs[0], rgba=ptrs[1], keep=kept, got_rgba=got_p)
     gb = r.downloadGBuffer(gbuffer if gbuffer is not None else r.gbuffer())
-    fill, pas = frame_fills(r, cfg)
+    fill, pas = fills if fills is not None else frame_fills(r, cfg)
     full = dict(vr.FILTER_DEFAULTS, **d)
     n = vr.iteration_map(fill, pas, full, cfg.uniform)
     want, _ = vr.vfilter(color, variance, gb, fill, n, full, record)
