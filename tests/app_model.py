@@ -35,8 +35,8 @@ from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
 
 from common import cfg_foveated, cfg_uniform, make_gpu
 from post_common import PostChecker
-from postprocess_common import bits
-from temporal_motion_common import debug_buffer, restate, vertex_arrays
+from gpu_common import bits, camera, debug_buffer, device_filled, device_images, host_view
+from temporal_motion_common import restate, vertex_arrays
 
 F = np.float32
 E_INVALID, E_NO_FRAME = -1, -5
@@ -753,12 +753,12 @@ class LateModel(AppModel):
     def focus(self, d, color, ptr):
         """test_focus_gpu.Checker.step with the frame as rendered where that reads the launch parameters."""
         import focus_ref as fr
-        from test_focus_gpu import device_outputs, fcfg, host, state_tuple
+        from test_focus_gpu import fcfg, state_tuple
         r = self.r
         cfg, full = fcfg({k: v for k, v in d.items() if k != "gbuffer"})
         g = r.temporal_gbuffer() if d["gbuffer"] == "temporal" else None
         inp = r.downloadAccum() if color is None else color
-        oc, op, oz = device_outputs(self.size)
+        oc, op, oz = device_images(self.size, 16, 4, 4)
         r.focus(cfg, g, ptr, oc.data_ptr(), op.data_ptr(), oz.data_ptr())
         gb = r.downloadGBuffer()                              # (the same rays as the call's own trace, and as the step's)
         self.trace_fresh = True
@@ -768,9 +768,9 @@ class LateModel(AppModel):
         if self.fc.state["steps"]:
             got = r.focus_state()
             assert state_tuple(got) == state_tuple(self.fc.state), ("focus: state", state_tuple(got), state_tuple(self.fc.state))
-        assert np.array_equal(bits(host(oz, "coc")), bits(want["coc"])), "focus: radius"
-        assert np.array_equal(bits(host(oc, "color")), bits(want["color"])), "focus: colour"
-        assert np.array_equal(host(op, "rgba"), want["rgba"]), "focus: rgba8"
+        assert np.array_equal(bits(host_view(oz, "coc")), bits(want["coc"])), "focus: radius"
+        assert np.array_equal(bits(host_view(oc, "color")), bits(want["color"])), "focus: colour"
+        assert np.array_equal(host_view(op, "rgba"), want["rgba"]), "focus: rgba8"
         self.log.append(("focus", full["mode"], int(want["state"]["count"]) if full["mode"] == abi.FOCUS_AUTO else None, int(want["acted"].sum()), steps))
         self._late_keep += [oc, op, oz]
         return want["color"], oc.data_ptr(), want["rgba"], op.data_ptr()
@@ -780,8 +780,7 @@ class LateModel(AppModel):
         as the inputs and `last` from the model's own steps."""
         import warp_motion_ref as wm
         import warp_ref as wr
-        from temporal_common import camera
-        from test_warp_gpu import check as warp_check, counts_of, device_outputs, host
+        from test_warp_gpu import check as warp_check, counts_of
         from warp_motion_common import frame_data, mcfg
         r = self.r
         to, want_cam = self.to_camera(la["to"])
@@ -805,7 +804,7 @@ class LateModel(AppModel):
             self.trace_fresh = True
         assert self.prev is not None and self.tracking and not self.moved.any()     # legal: a step, tracking, no update since
         assert g is None or self.trace_fresh                  # ... and with a caller's G-buffer, a trace newer than everything else
-        oc, op, om = device_outputs(self.size)
+        oc, op, om = device_images(self.size, 16, 4, 4)
         r.warp_motion(to, cfg, g, ptr, rgba_ptr, oc.data_ptr(), op.data_ptr(), om.data_ptr())
         got_counts = counts_of(r)
         gb, uv = frame_data(r)                                # (the same rays as the trace the call used, or made)
@@ -813,16 +812,16 @@ class LateModel(AppModel):
         d = dict(images=images, fill_radius=radius, advance=la["advance"])
         want = wm.warp(gb, uv, self.last, camera(r), want_cam, d, inp, rgba)
         plain = wr.warp(gb, camera(r), want_cam, dict(images=images, fill_radius=radius), inp, rgba)
-        assert np.array_equal(host(om, 1), want["map"]), "warp_motion: map"
+        assert np.array_equal(host_view(om, "map"), want["map"]), "warp_motion: map"
         assert got_counts == want["counts"] and sum(got_counts[1:]) == self.size[0] * self.size[1], (got_counts, want["counts"])
         differs = not np.array_equal(want["map"], plain["map"])
         if images & wr.COLOR:
-            assert np.array_equal(bits(host(oc, 4)), bits(want["color"])), "warp_motion: colour"
+            assert np.array_equal(bits(host_view(oc, "color")), bits(want["color"])), "warp_motion: colour"
             differs = differs or not np.array_equal(bits(want["color"]), bits(plain["color"]))
         else:
             assert (oc.cpu().numpy() == 0x5a).all()
         if images & wr.RGBA:
-            assert np.array_equal(host(op, 1), want["rgba"]), "warp_motion: rgba8"
+            assert np.array_equal(host_view(op, "rgba"), want["rgba"]), "warp_motion: rgba8"
             differs = differs or not np.array_equal(want["rgba"], plain["rgba"])
         else:
             assert (op.cpu().numpy() == 0x5a).all()
@@ -995,9 +994,8 @@ class HdrModel(LateModel):
         self.mom.prev = hist
 
     def frames(self, op):
-        from test_variance_gpu import camera_of
         super().frames(op)
-        self.cam_rendered = camera_of(self.r)             # (nothing below changes the camera: the chain's stages use the rendered one)
+        self.cam_rendered = camera(self.r)             # (nothing below changes the camera: the chain's stages use the rendered one)
 
     def rendered_fills(self):
         """(fill with 1 where no pass writes, pass, fill with 0 there, FOV_OFF) of the frame as rendered."""
@@ -1046,7 +1044,7 @@ class HdrModel(LateModel):
 
     def bloom(self, b, color, ptr):
         import bloom_ref as br
-        from test_bloom_gpu import check, device_outputs
+        from test_bloom_gpu import check
         r = self.r
         d = b["cfg"]
         inp = r.downloadAccum() if color is None else color
@@ -1057,9 +1055,9 @@ class HdrModel(LateModel):
             E = self.ex.state["exposure"] if steps else d["exposure"]
         if b["in_place"]:
             assert ptr is not None
-            out = (_Frame(r, ptr, self.size, 4), device_outputs(self.size)[1])
+            out = (_Frame(r, ptr, self.size, 4), device_images(self.size, 16, 4)[1])
         else:
-            out = None if b["own"] else device_outputs(self.size)
+            out = None if b["own"] else device_images(self.size, 16, 4)
         want = check(self.oracle, r, d, inp, (fill0, uniform), in_ptr=ptr, out=out, E=E, label="bloom")
         off = br.level_offsets(self.size[0], self.size[1], d["levels"])
         lit = int((bits(want["pyramid"][:off[1]]) != 0).any(axis=-1).sum())
@@ -1075,14 +1073,14 @@ class HdrModel(LateModel):
         import ctypes as C
         import quality_cases as qc
         import quality_ref as qr
-        from test_quality_gpu import device_bytes, qcfg, sums_of
+        from test_quality_gpu import qcfg, sums_of
         r = self.r
         (w, h), gaze, (ri, ro), uniform = self.frame_as_rendered
         cfg, full = qcfg(dict(flags=q["flags"], ring_width=q["ring_width"]))
         n = C.sizeof(abi.QualitySums)
         assert n == 1344
-        out = None if q["record_own"] else device_bytes(n)
-        cls = device_bytes(w * h, 0xee) if q["classes"] else None
+        out = None if q["record_own"] else device_filled(n, 0xa5)
+        cls = device_filled(w * h, 0xee) if q["classes"] else None
         r.qualityAsync(ref_ptr, test_ptr, cfg, out.data_ptr() if out is not None else None, cls.data_ptr() if cls is not None else None)
         got = r.readQuality(sums=True) if out is None else None
         r.synchronize()

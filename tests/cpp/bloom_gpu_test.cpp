@@ -1,38 +1,19 @@
-// fovpt_bloom through the drop-in C++ API: the box scene of post_gpu_test.cpp rendered, stepped with SampleRenderer::post(), then
+// fovpt_bloom through the drop-in C++ API: the box scene of box_scene.h rendered, stepped with SampleRenderer::post(), then
 // bloomPost() with Karis weights, per-level gains and a lowered threshold, and exposeBloom() behind it; once more with the defaults
 // straight from the accum buffer.  Writes the two bloom colours (float4), their rgba8 and the exposed rgba8 to a file.
 #include <cstdio>
 #include <vector>
-#include "SimplePathtracer.h"
+#include "box_scene.h"
 
 int main(int argc, char** argv)
 {
     const char* out = argc > 1 ? argv[1] : "bloom_out.bin";
-    try {
-        Model* model = new Model;
-        Material grey; grey.color = make_float3(0.7f, 0.7f, 0.7f); grey.emission = make_float3(0.0f);
-        Material red; red.color = make_float3(0.8f, 0.1f, 0.1f); red.emission = make_float3(0.0f);
-        addBox(model, grey, make_float3(0, -1.0f, 0), make_float3(6, 0.5f, 6));
-        addBox(model, red, make_float3(0, 0.5f, 0), make_float3(1, 1, 1));
-        const int2 fbSize = make_int2(160, 96);
-        const size_t n = (size_t)fbSize.x * fbSize.y;
-        std::vector<float4> sky(n, make_float4(2.5f, 2.5f, 2.5f, 1.0f));
-        ProbeData probe;
-        probe.width = fbSize.x; probe.height = fbSize.y; probe.data = sky.data();
-        probe.BuildCDF();
-        sutil::Camera camera(make_float3(4, 3, 6), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, fbSize.x / float(fbSize.y));
+    return run_main([&]() -> int {
+        BoxScene scene;
+        const size_t n = scene.n;
 
-        SampleRenderer sample(model);
-        sample.resize(fbSize);
-        sample.setCamera(camera);
-        sample.setProbe(probe);
-        fovpt_config cfg = sample.config();
-        cfg.r_inner = 12; cfg.r_outer = 36; cfg.spp_periphery = 1; cfg.spp_middle = 2; cfg.spp_fovea = 8;
-        cfg.write_guides = 1;
-        sample.setConfig(cfg);
-        sample.launchParams.frame.c.x = fbSize.x / 2;
-        sample.launchParams.frame.c.y = fbSize.y / 2;
-        sample.launchParams.frame.subframe_index = 0;
+        SampleRenderer sample(scene.model);
+        scene.setup(sample, true);
         std::vector<fovpt_float4> color(n * 2);
         std::vector<uint32_t> pixels(n * 3);
         fovpt_bloom_config bc;
@@ -53,20 +34,14 @@ int main(int argc, char** argv)
         sample.bloom();
         sample.downloadBloomColor(color.data() + n);
         sample.downloadBloomPixels(pixels.data() + 2 * n);
-        FILE* f = fopen(out, "wb");
-        fwrite(color.data(), sizeof(fovpt_float4), color.size(), f);
-        fwrite(pixels.data(), 4, pixels.size(), f);
-        fclose(f);
+        OutFile f(out);
+        f.write(color.data(), sizeof(fovpt_float4), color.size());
+        f.write(pixels.data(), 4, pixels.size());
+        f.close();
         // more levels than the stage has are refused
-        bool threw = false;
         bc.levels = FOVPT_BLOOM_MAX_LEVELS + 1;
-        try { sample.bloom(bc); } catch (const std::runtime_error&) { threw = true; }
-        if (!threw) { printf("bloom(levels 9) did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.bloom(bc); }, "bloom(levels 9) did not throw")) return 2;
         printf("ok\n");
-        delete model;
-    } catch (const std::exception& e) {
-        printf("exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -1,40 +1,21 @@
-// fovpt_focus through the drop-in C++ API: the box scene of post_gpu_test.cpp rendered and stepped with SampleRenderer::post(), then
+// fovpt_focus through the drop-in C++ API: the box scene of box_scene.h rendered and stepped with SampleRenderer::post(), then
 // the post colour focused twice with the defaults' meter and a strength that blurs the slab -- once with the post step's G-buffer
 // (focusPost), once tracing its own -- and the raw frame focused at a fixed distance.  Writes the three rgba8 frames, the three
 // float4 frames and the two state records to a file.
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "SimplePathtracer.h"
+#include "box_scene.h"
 
 int main(int argc, char** argv)
 {
     const char* out = argc > 1 ? argv[1] : "focus_out.bin";
-    try {
-        Model* model = new Model;
-        Material grey; grey.color = make_float3(0.7f, 0.7f, 0.7f); grey.emission = make_float3(0.0f);
-        Material red; red.color = make_float3(0.8f, 0.1f, 0.1f); red.emission = make_float3(0.0f);
-        addBox(model, grey, make_float3(0, -1.0f, 0), make_float3(6, 0.5f, 6));
-        addBox(model, red, make_float3(0, 0.5f, 0), make_float3(1, 1, 1));
-        const int2 fbSize = make_int2(160, 96);
-        const size_t n = (size_t)fbSize.x * fbSize.y;
-        std::vector<float4> sky(n, make_float4(2.5f, 2.5f, 2.5f, 1.0f));
-        ProbeData probe;
-        probe.width = fbSize.x; probe.height = fbSize.y; probe.data = sky.data();
-        probe.BuildCDF();
-        sutil::Camera camera(make_float3(4, 3, 6), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, fbSize.x / float(fbSize.y));
+    return run_main([&]() -> int {
+        BoxScene scene;
+        const size_t n = scene.n;
 
-        SampleRenderer sample(model);
-        sample.resize(fbSize);
-        sample.setCamera(camera);
-        sample.setProbe(probe);
-        fovpt_config cfg = sample.config();
-        cfg.r_inner = 12; cfg.r_outer = 36; cfg.spp_periphery = 1; cfg.spp_middle = 2; cfg.spp_fovea = 8;
-        cfg.write_guides = 1;
-        sample.setConfig(cfg);
-        sample.launchParams.frame.c.x = fbSize.x / 2;
-        sample.launchParams.frame.c.y = fbSize.y / 2;
-        sample.launchParams.frame.subframe_index = 0;
+        SampleRenderer sample(scene.model);
+        scene.setup(sample, true);
         std::vector<uint32_t> pixels(n * 3);
         std::vector<fovpt_float4> colors(n * 3);
         struct fovpt_focus_state states[2];
@@ -67,24 +48,18 @@ int main(int argc, char** argv)
         sample.focus(fc);
         sample.downloadFocus(colors.data() + 2 * n, pixels.data() + 2 * n);
         if (sample.focusState().steps != 2) { printf("a FIXED call touched the state\n"); return 2; }
-        FILE* f = fopen(out, "wb");
-        fwrite(pixels.data(), 4, pixels.size(), f);
-        fwrite(colors.data(), 16, colors.size(), f);
-        fwrite(states, sizeof(states[0]), 2, f);
-        fwrite(&fc.strength, 4, 1, f);
-        fclose(f);
+        OutFile f(out);
+        f.write(pixels.data(), 4, pixels.size());
+        f.write(colors.data(), 16, colors.size());
+        f.write(states, sizeof(states[0]), 2);
+        f.write(&fc.strength, 4, 1);
+        f.close();
         sample.focusReset();
         if (sample.focusState().steps != 0) { printf("focusReset left the state\n"); return 2; }
         // an out-of-range configuration is an exception, like every other error of the shim
-        bool threw = false;
         fc.max_radius = FOVPT_FOCUS_MAX_RADIUS + 1;
-        try { sample.focus(fc); } catch (const std::runtime_error&) { threw = true; }
-        if (!threw) { printf("focus(max_radius %d) did not throw\n", FOVPT_FOCUS_MAX_RADIUS + 1); return 2; }
+        if (!must_throw([&] { sample.focus(fc); }, text("focus(max_radius %d) did not throw", FOVPT_FOCUS_MAX_RADIUS + 1))) return 2;
         printf("ok\n");
-        delete model;
-    } catch (const std::exception& e) {
-        printf("exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -1,11 +1,11 @@
-// Morph targets through the drop-in C++ API: the box scene of transform_gpu_test.cpp, the red box with three targets -- a dense
+// Morph targets through the drop-in C++ API: the tall-box scene of box_scene.h, the red box with three targets -- a dense
 // one that leans the box, a sparse one that lifts its upper vertices, an empty one -- set by SampleRenderer::setMorphs, posed by
 // updateMorphed, rendered.  Prints the FNV-1a hashes of the rgba8 frame and of the "scene_vertices" bytes for the python test
 // to compare with the same calls through the python wrapper, then poses again with rebuild = true (the hashes must come back
 // the same), checks that a pose of zero weights brings back the bytes of the zero pose made first and that an unmorphed mesh is an exception.
 #include <cstdio>
 #include <vector>
-#include "SimplePathtracer.h"
+#include "box_scene.h"
 
 namespace {
 unsigned long long fnv1a(const void* p, size_t n)
@@ -36,30 +36,13 @@ unsigned long long frame_hash(SampleRenderer& s, std::vector<uint32_t>& pixels)
 
 int main()
 {
-    try {
-        Model* model = new Model;
-        Material grey; grey.color = make_float3(0.7f, 0.7f, 0.7f); grey.emission = make_float3(0.0f);
-        Material red; red.color = make_float3(0.8f, 0.1f, 0.1f); red.emission = make_float3(0.0f);
-        addBox(model, grey, make_float3(0, -1.0f, 0), make_float3(6, 0.5f, 6));
-        addBox(model, red, make_float3(0, 0.5f, 0), make_float3(1, 2, 0.5f));
-        const int2 fbSize = make_int2(160, 96);
-        const size_t n = (size_t)fbSize.x * fbSize.y;
-        std::vector<float4> sky(n, make_float4(2.5f, 2.5f, 2.5f, 1.0f));
-        ProbeData probe;
-        probe.width = fbSize.x; probe.height = fbSize.y; probe.data = sky.data();
-        probe.BuildCDF();
-        sutil::Camera camera(make_float3(4, 3, 6), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, fbSize.x / float(fbSize.y));
-        SampleRenderer sample(model);
-        sample.resize(fbSize);
-        sample.setCamera(camera);
-        sample.setProbe(probe);
-        fovpt_config cfg = sample.config();
-        cfg.r_inner = 12; cfg.r_outer = 36; cfg.spp_periphery = 1; cfg.spp_middle = 2; cfg.spp_fovea = 8;
-        sample.setConfig(cfg);
-        sample.launchParams.frame.c.x = fbSize.x / 2;
-        sample.launchParams.frame.c.y = fbSize.y / 2;
+    return run_main([&]() -> int {
+        BoxScene scene(make_float3(1, 2, 0.5f));
+        const size_t n = scene.n;
+        SampleRenderer sample(scene.model);
+        scene.setup(sample);
 
-        const std::vector<float3>& v = model->meshes[1]->vertex;
+        const std::vector<float3>& v = scene.model->meshes[1]->vertex;
         std::vector<float> lean(3 * v.size(), 0.0f), lift;
         std::vector<uint32_t> upper;
         for (size_t i = 0; i < v.size(); i++) {
@@ -87,20 +70,12 @@ int main()
         if (f1 != f2 || v1 != v2) { printf("rebuild: frame %016llx vertices %016llx\n", f2, v2); return 2; }
         sample.updateMorphed({at_rest});
         if (vertex_hash(sample) != v0 || v1 == v0) { printf("a pose of zero weights did not bring the rest positions back\n"); return 2; }
-        bool threw = false;
         const fovpt_morph_pose bad = {0, 3, weights, 0, 0, nullptr};       // mesh 0 has no morph targets
-        try { sample.updateMorphed({bad}); } catch (const std::runtime_error&) { threw = true; }
-        if (!threw) { printf("updateMorphed of an unmorphed mesh did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.updateMorphed({bad}); }, "updateMorphed of an unmorphed mesh did not throw")) return 2;
         fovpt_mesh_morph none = {1, (uint32_t)v.size(), 0, 0, nullptr};
         sample.setMorphs({none});
-        threw = false;
-        try { sample.updateMorphed({pose}); } catch (const std::runtime_error&) { threw = true; }
-        if (!threw) { printf("updateMorphed after the targets were removed did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.updateMorphed({pose}); }, "updateMorphed after the targets were removed did not throw")) return 2;
         printf("ok\n");
-        delete model;
-    } catch (const std::exception& e) {
-        printf("exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -1,37 +1,21 @@
-// Foveated frame packets through the drop-in C++ API: the box scene of post_gpu_test.cpp rendered at three gazes, each frame
+// Foveated frame packets through the drop-in C++ API: the box scene of box_scene.h rendered at three gazes, each frame
 // submitted as a packet the moment it is issued and the next one rendered at once; then every slot is waited for, checked, decoded
 // on the host (fovpt_packet_decode_host, both modes) and compared with what downloadPixels gave for that frame.  Writes the
 // packets' sizes, the three downloaded frames and the three NEAREST decodes to a file.
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "SimplePathtracer.h"
+#include "box_scene.h"
 
 int main(int argc, char** argv)
 {
     const char* out = argc > 1 ? argv[1] : "packet_out.bin";
-    try {
-        Model* model = new Model;
-        Material grey; grey.color = make_float3(0.7f, 0.7f, 0.7f); grey.emission = make_float3(0.0f);
-        Material red; red.color = make_float3(0.8f, 0.1f, 0.1f); red.emission = make_float3(0.0f);
-        addBox(model, grey, make_float3(0, -1.0f, 0), make_float3(6, 0.5f, 6));
-        addBox(model, red, make_float3(0, 0.5f, 0), make_float3(1, 1, 1));
-        const int2 fbSize = make_int2(160, 96);
-        const size_t n = (size_t)fbSize.x * fbSize.y;
-        std::vector<float4> sky(n, make_float4(2.5f, 2.5f, 2.5f, 1.0f));
-        ProbeData probe;
-        probe.width = fbSize.x; probe.height = fbSize.y; probe.data = sky.data();
-        probe.BuildCDF();
-        sutil::Camera camera(make_float3(4, 3, 6), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, fbSize.x / float(fbSize.y));
+    return run_main([&]() -> int {
+        BoxScene scene;
+        const size_t n = scene.n;
 
-        SampleRenderer sample(model);
-        sample.resize(fbSize);
-        sample.setCamera(camera);
-        sample.setProbe(probe);
-        fovpt_config cfg = sample.config();
-        cfg.r_inner = 12; cfg.r_outer = 36; cfg.spp_periphery = 1; cfg.spp_middle = 2; cfg.spp_fovea = 8;
-        sample.setConfig(cfg);
-        sample.launchParams.frame.subframe_index = 0;
+        SampleRenderer sample(scene.model);
+        scene.setup(sample);
         const int gaze[3][2] = {{80, 48}, {150, 10}, {3, 90}};
         // the frames one by one, downloaded: what the packets must reproduce
         std::vector<uint32_t> frames(3 * n), decoded(3 * n, 0u), smooth(n);
@@ -58,8 +42,8 @@ int main(int argc, char** argv)
             fovpt_packet_header h;
             memcpy(&h, p.data, sizeof(h));
             if (fovpt_packet_check(p.data, p.bytes) != FOVPT_OK || h.sequence != 100u + k || h.bytes != p.bytes || h.npass != 3) { printf("packet %d is not valid\n", k); return 2; }
-            if (fovpt_packet_decode_host(p.data, p.bytes, FOVPT_PACKET_NEAREST, decoded.data() + k * n, fbSize.x, fbSize.y) != FOVPT_OK) { printf("decode %d failed\n", k); return 2; }
-            if (fovpt_packet_decode_host(p.data, p.bytes, FOVPT_PACKET_SMOOTH, smooth.data(), fbSize.x, fbSize.y) != FOVPT_OK) { printf("smooth decode %d failed\n", k); return 2; }
+            if (fovpt_packet_decode_host(p.data, p.bytes, FOVPT_PACKET_NEAREST, decoded.data() + k * n, scene.fbSize.x, scene.fbSize.y) != FOVPT_OK) { printf("decode %d failed\n", k); return 2; }
+            if (fovpt_packet_decode_host(p.data, p.bytes, FOVPT_PACKET_SMOOTH, smooth.data(), scene.fbSize.x, scene.fbSize.y) != FOVPT_OK) { printf("smooth decode %d failed\n", k); return 2; }
             // every pixel a pass of frame k wrote is that frame's pixel (alpha 0xff); the others -- a few between the rings are
             // nobody's -- keep the 0 the output held
             size_t written = 0;
@@ -71,19 +55,13 @@ int main(int argc, char** argv)
             }
             if (written * 100 < n * 99) { printf("frame %d: only %zu pixels decoded\n", k, written); return 2; }
         }
-        bool threw = false;
-        try { sample.waitPacket(3); } catch (const std::runtime_error&) { threw = true; }      // never submitted
-        if (!threw) { printf("waitPacket(3) did not throw\n"); return 2; }
-        FILE* f = fopen(out, "wb");
-        fwrite(sizes, 4, 3, f);
-        fwrite(frames.data(), 4, frames.size(), f);
-        fwrite(decoded.data(), 4, decoded.size(), f);
-        fclose(f);
+        if (!must_throw([&] { sample.waitPacket(3); }, "waitPacket(3) did not throw")) return 2;      // never submitted
+        OutFile f(out);
+        f.write(sizes, 4, 3);
+        f.write(frames.data(), 4, frames.size());
+        f.write(decoded.data(), 4, decoded.size());
+        f.close();
         printf("ok\n");
-        delete model;
-    } catch (const std::exception& e) {
-        printf("exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

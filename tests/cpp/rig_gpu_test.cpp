@@ -1,4 +1,4 @@
-// A rig through the drop-in C++ API: the box scene of skin_gpu_test.cpp, the red box skinned over two joints that are nodes 0 and
+// A rig through the drop-in C++ API: the tall-box scene of box_scene.h, the red box skinned over two joints that are nodes 0 and
 // 1 of a rig (node 1 turning about z on node 0, which scales), the floor rigid on node 2 (which drops by STEP).
 // SampleRenderer::setRig uploads it, updateAnimated poses it at t = 0.75.  Prints the FNV-1a hashes of the rgba8 frame and of the
 // "scene_vertices" bytes for the python test to compare with the same calls through the python wrapper, then poses again with
@@ -6,7 +6,7 @@
 // setSkins are exceptions.
 #include <cstdio>
 #include <vector>
-#include "SimplePathtracer.h"
+#include "box_scene.h"
 
 namespace {
 unsigned long long fnv1a(const void* p, size_t n)
@@ -33,40 +33,17 @@ unsigned long long frame_hash(SampleRenderer& s, std::vector<uint32_t>& pixels)
     s.downloadPixels(pixels.data());
     return fnv1a(pixels.data(), pixels.size() * 4);
 }
-
-template <class F> bool throws(F f)
-{
-    try { f(); } catch (const std::runtime_error&) { return true; }
-    return false;
-}
 }  // namespace
 
 int main()
 {
-    try {
-        Model* model = new Model;
-        Material grey; grey.color = make_float3(0.7f, 0.7f, 0.7f); grey.emission = make_float3(0.0f);
-        Material red; red.color = make_float3(0.8f, 0.1f, 0.1f); red.emission = make_float3(0.0f);
-        addBox(model, grey, make_float3(0, -1.0f, 0), make_float3(6, 0.5f, 6));
-        addBox(model, red, make_float3(0, 0.5f, 0), make_float3(1, 2, 0.5f));
-        const int2 fbSize = make_int2(160, 96);
-        const size_t n = (size_t)fbSize.x * fbSize.y;
-        std::vector<float4> sky(n, make_float4(2.5f, 2.5f, 2.5f, 1.0f));
-        ProbeData probe;
-        probe.width = fbSize.x; probe.height = fbSize.y; probe.data = sky.data();
-        probe.BuildCDF();
-        sutil::Camera camera(make_float3(4, 3, 6), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, fbSize.x / float(fbSize.y));
-        SampleRenderer sample(model);
-        sample.resize(fbSize);
-        sample.setCamera(camera);
-        sample.setProbe(probe);
-        fovpt_config cfg = sample.config();
-        cfg.r_inner = 12; cfg.r_outer = 36; cfg.spp_periphery = 1; cfg.spp_middle = 2; cfg.spp_fovea = 8;
-        sample.setConfig(cfg);
-        sample.launchParams.frame.c.x = fbSize.x / 2;
-        sample.launchParams.frame.c.y = fbSize.y / 2;
+    return run_main([&]() -> int {
+        BoxScene scene(make_float3(1, 2, 0.5f));
+        const size_t n = scene.n;
+        SampleRenderer sample(scene.model);
+        scene.setup(sample);
 
-        const std::vector<float3>& v = model->meshes[1]->vertex;
+        const std::vector<float3>& v = scene.model->meshes[1]->vertex;
         std::vector<uint16_t> joints(4 * v.size(), 0);
         std::vector<float> weights(4 * v.size(), 0.0f);
         for (size_t i = 0; i < v.size(); i++) {
@@ -98,19 +75,15 @@ int main()
         sample.updateAnimated(0, 0.75f, true);
         const unsigned long long f2 = frame_hash(sample, pixels), v2 = vertex_hash(sample);
         if (f1 != f2 || v1 != v2) { printf("rebuild: frame %016llx vertices %016llx\n", f2, v2); return 2; }
-        if (!throws([&] { sample.updateAnimated(1, 0.0f); })) { printf("a clip out of range did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.updateAnimated(1, 0.0f); }, "a clip out of range did not throw")) return 2;
         sample.setRig(nullptr);
-        if (!throws([&] { sample.updateAnimated(0, 0.0f); })) { printf("updateAnimated after the rig was removed did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.updateAnimated(0, 0.0f); }, "updateAnimated after the rig was removed did not throw")) return 2;
         sample.setRig(&rig);
         sample.updateAnimated(0, 0.75f);
         if (vertex_hash(sample) != v1) { printf("the rig set again poses differently\n"); return 2; }
         sample.setSkins({skin});
-        if (!throws([&] { sample.updateAnimated(0, 0.0f); })) { printf("updateAnimated after setSkins did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.updateAnimated(0, 0.0f); }, "updateAnimated after setSkins did not throw")) return 2;
         printf("ok\n");
-        delete model;
-    } catch (const std::exception& e) {
-        printf("exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -1,4 +1,4 @@
-// fovpt_warp_motion through the drop-in C++ API: the box scene of warp_gpu_test.cpp rendered and stepped with SampleRenderer::post(),
+// fovpt_warp_motion through the drop-in C++ API: the box scene of box_scene.h rendered and stepped with SampleRenderer::post(),
 // the box carried by updateTransforms(), rendered and stepped again and exposed; then the exposed frame warped to a moved camera with
 // warpMotionExposed() -- once tracing its own G-buffer, once with the post step's (reuse_gbuffer) --, the raw frame with a
 // fovpt_warp_motion_config (rgba8 only, fill_radius 0, advance 2.5), and the exposed frame with warpExposed() for comparison.  Writes
@@ -6,44 +6,23 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "SimplePathtracer.h"
+#include "box_scene.h"
 
 int main(int argc, char** argv)
 {
     const char* out = argc > 1 ? argv[1] : "warp_motion_out.bin";
-    try {
-        Model* model = new Model;
-        Material grey; grey.color = make_float3(0.7f, 0.7f, 0.7f); grey.emission = make_float3(0.0f);
-        Material red; red.color = make_float3(0.8f, 0.1f, 0.1f); red.emission = make_float3(0.0f);
-        addBox(model, grey, make_float3(0, -1.0f, 0), make_float3(6, 0.5f, 6));
-        addBox(model, red, make_float3(0, 0.5f, 0), make_float3(1, 1, 1));
-        const int2 fbSize = make_int2(160, 96);
-        const size_t n = (size_t)fbSize.x * fbSize.y;
-        std::vector<float4> sky(n, make_float4(2.5f, 2.5f, 2.5f, 1.0f));
-        ProbeData probe;
-        probe.width = fbSize.x; probe.height = fbSize.y; probe.data = sky.data();
-        probe.BuildCDF();
-        sutil::Camera camera(make_float3(4, 3, 6), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, fbSize.x / float(fbSize.y));
+    return run_main([&]() -> int {
+        BoxScene scene;
+        const size_t n = scene.n;
         sutil::Camera moved(make_float3(3.5f, 3, 6.5f), make_float3(0, 0.5f, 0), make_float3(0, 1, 0), 45.0f, 1.0f);   // (the warp sets the aspect ratio)
 
-        SampleRenderer sample(model);
-        sample.resize(fbSize);
-        sample.setCamera(camera);
-        sample.setProbe(probe);
-        fovpt_config cfg = sample.config();
-        cfg.r_inner = 12; cfg.r_outer = 36; cfg.spp_periphery = 1; cfg.spp_middle = 2; cfg.spp_fovea = 8;
-        cfg.write_guides = 1;
-        sample.setConfig(cfg);
-        sample.launchParams.frame.c.x = fbSize.x / 2;
-        sample.launchParams.frame.c.y = fbSize.y / 2;
-        sample.launchParams.frame.subframe_index = 0;
+        SampleRenderer sample(scene.model);
+        scene.setup(sample, true);
         std::vector<uint32_t> pixels(n * 4);
         struct fovpt_warp_counts counts[4];
         sample.render();
         // before any temporal step the call is an exception, like every other error of the shim
-        bool threw = false;
-        try { sample.warpMotion(moved, 1.0f); } catch (const std::runtime_error&) { threw = true; }
-        if (!threw) { printf("warpMotion before any temporal step did not throw\n"); return 2; }
+        if (!must_throw([&] { sample.warpMotion(moved, 1.0f); }, "warpMotion before any temporal step did not throw")) return 2;
         sample.post();
         fovpt_mesh_transform carry;
         carry.mesh = 1;
@@ -76,19 +55,13 @@ int main(int argc, char** argv)
         sample.downloadWarpedPixels(pixels.data() + 3 * n);
         counts[3] = sample.warpCounts();
         if (memcmp(pixels.data(), pixels.data() + 3 * n, n * 4) == 0) { printf("the moved box is warped as fovpt_warp warps it\n"); return 2; }
-        FILE* f = fopen(out, "wb");
-        fwrite(pixels.data(), 4, pixels.size(), f);
-        fwrite(counts, sizeof(counts[0]), 4, f);
-        fclose(f);
-        threw = false;
+        OutFile f(out);
+        f.write(pixels.data(), 4, pixels.size());
+        f.write(counts, sizeof(counts[0]), 4);
+        f.close();
         mc.advance = FOVPT_WARP_MAX_ADVANCE * 2.0f;
-        try { sample.warpMotion(moved, mc); } catch (const std::runtime_error&) { threw = true; }
-        if (!threw) { printf("warpMotion(advance %g) did not throw\n", (double)mc.advance); return 2; }
+        if (!must_throw([&] { sample.warpMotion(moved, mc); }, text("warpMotion(advance %g) did not throw", (double)mc.advance))) return 2;
         printf("ok\n");
-        delete model;
-    } catch (const std::exception& e) {
-        printf("exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

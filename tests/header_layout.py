@@ -1,10 +1,26 @@
-"""What include/fovpt.h, compiled as C99 by gcc, says about its structs and constants: the one copy of the program the *_cpu tests
-ask for sizeof / offsetof values and #define'd numbers."""
+"""The one place the tests compile against include/: what fovpt.h, compiled as C99 by gcc, says about its structs and constants
+(the one copy of the program the *_cpu tests ask for sizeof / offsetof values and #define'd numbers), and the syntax check of a
+piece of C or C++ that uses the headers."""
 import os
 import subprocess
 import tempfile
 
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+
+
+def _syntax_command(lang, include=()):
+    return ["g++" if "+" in lang else "gcc", "-std=" + lang, "-fsyntax-only", "-I", INCLUDE] + [a for d in include for a in ("-I", d)]
+
+
+def syntax_check(src, lang="c++14"):
+    """The compiler's -fsyntax-only pass over the source text src as `lang` ("c++14", "c99": the -std value, which also picks g++
+    or gcc) against include/; raises CalledProcessError with the compiler's messages on its standard error."""
+    subprocess.run(_syntax_command(lang) + ["-x", "c++" if "+" in lang else "c", "-"], input=src.encode(), check=True)
+
+
+def syntax_check_file(path, lang="c++14", include=()):
+    """The same pass over a source file, against include/ and the directories of `include`."""
+    subprocess.run(_syntax_command(lang, include) + [path], check=True)
 
 
 def _members(mirror, rename):

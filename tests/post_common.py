@@ -9,8 +9,8 @@ import post_ref as po
 import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib
 
-from postprocess_common import bits, guides
-from temporal_common import camera
+from gpu_common import bits, camera, with_entries
+from postprocess_common import guides
 from temporal_motion_common import MotionChecker, download_hits
 
 D, R, T, M = po.DENOISE, po.RECONSTRUCT, po.TEMPORAL, po.MOTION
@@ -23,8 +23,7 @@ def pcfg(stages=None, denoise=None, reconstruct=None, temporal=None):
     if stages is not None:
         c.stages = stages
     for sub, d in ((c.denoise, denoise), (c.reconstruct, reconstruct), (c.temporal, temporal)):
-        for k, v in (d or {}).items():
-            setattr(sub, k, v)
+        with_entries(sub, d)
     return c
 
 

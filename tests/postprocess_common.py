@@ -1,6 +1,7 @@
 """Shared checks of the post-processing of a rendered frame (fovpt_denoise, fovpt_gbuffer, fovpt_reconstruct) against their
 numpy restatements (tests/denoise_ref.py, tests/reconstruct_ref.py) and the oracle: used by test_denoise_gpu.py,
-test_reconstruct_gpu.py and test_postprocess_fuzz_gpu.py.
+test_reconstruct_gpu.py and test_postprocess_fuzz_gpu.py.  The box scene and the other helpers no stage owns are in
+tests/gpu_common.py.
 
 Every expectation is computed from the GPU's own inputs (guide buffers, accum buffer, G-buffer) and from the frame's
 description -- size, gaze, radii, FOV_OFF flag -- as the frame was rendered: by default r.launchParams and cfg, which the
@@ -9,11 +10,9 @@ import numpy as np
 
 import denoise_ref as dn
 import reconstruct_ref as rr
-from fovpathtracing_optixcodelatest_amd import abi, lib, scenes
+from fovpathtracing_optixcodelatest_amd import abi, lib
 
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+from gpu_common import bits, with_entries
 
 
 def _f32(a):
@@ -35,29 +34,14 @@ def dcfg(d):
     """fovpt_denoise_defaults with the entries of d replaced."""
     c = abi.DenoiseConfig()
     lib.check(None, lib.load().fovpt_denoise_defaults(c))
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
+    return with_entries(c, d)
 
 
 def rcfg(d):
     """fovpt_reconstruct_defaults with the entries of d replaced."""
     c = abi.ReconstructConfig()
     lib.check(None, lib.load().fovpt_reconstruct_defaults(c))
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
-    return c
-
-
-def box_model():
-    """A grey slab and a red box: sky misses around them."""
-    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
-    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
-    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
-    return scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 1, 1), red)])
-
-
-BOX_CAMERA = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
+    return with_entries(c, d)
 
 
 # ---- fovpt_denoise -------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""Checks of fovpt_temporal on the GPU against tests/temporal_ref.py: used by test_temporal_gpu.py and
-test_temporal_fuzz_gpu.py.
+"""Checks of fovpt_temporal on the GPU against tests/temporal_ref.py (Checker, tcfg, cap_map) and the quality measurement over
+the atrium: used by the temporal, temporal-motion, post and warp-motion tests.  General helpers are in tests/gpu_common.py.
 
 Every expectation is computed from the GPU's own inputs: the input frame, the G-buffers fovpt_gbuffer builds at the current
 camera (and kept from the previous step), and the history the previous step wrote.  The frame's description -- size, gaze,
@@ -11,28 +11,19 @@ import reconstruct_ref as rr
 import temporal_ref as tr
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
-from postprocess_common import bits
+from gpu_common import bits, camera, with_entries, writer_fills
 
 
 def tcfg(d=None):
     """fovpt_temporal_defaults with the entries of d replaced."""
     c = abi.TemporalConfig()
     lib.check(None, lib.load().fovpt_temporal_defaults(c))
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
-    return c
-
-
-def camera(r):
-    c = r.launchParams.camera
-    vec = lambda v: (float(v.x), float(v.y), float(v.z))
-    return dict(eye=vec(c.eye), U=vec(c.U), V=vec(c.V), W=vec(c.W))
+    return with_entries(c, d)
 
 
 def cap_map(r, d=None):
-    f, cfg = r.launchParams.frame, r.config
-    fill = rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)[0]
-    return tr.caps(fill, cfg.uniform, d)
+    fill, uniform = writer_fills(r)
+    return tr.caps(fill, uniform, d)
 
 
 class Checker:

@@ -1,11 +1,9 @@
-"""Checks of fovpt_temporal_motion on the GPU against tests/temporal_motion_ref.py: used by test_temporal_motion_gpu.py and
-test_temporal_motion_fuzz_gpu.py.
+"""Checks of fovpt_temporal_motion on the GPU against tests/temporal_motion_ref.py (MotionChecker, restate and the ramp's
+geometry): used by the tests of the stages that move meshes.  General helpers are in tests/gpu_common.py.
 
 Like temporal_common.Checker, every expectation is computed from the GPU's own inputs: the input frame, the G-buffer and hit
 records fovpt_gbuffer builds at the current camera after the step (it traces the same rays), the G-buffer and history of the
 previous step, and the vertex arrays the test itself uploaded."""
-import ctypes as C
-
 import numpy as np
 
 import morph_ref as mr
@@ -14,8 +12,8 @@ import temporal_motion_ref as tm
 import temporal_ref as tr
 import transform_ref as tf
 
-from postprocess_common import bits
-from temporal_common import camera, cap_map, tcfg
+from gpu_common import bits, camera, debug_buffer
+from temporal_common import cap_map, tcfg
 
 KINDS = ("vertices", "transforms", "skinned", "morphed")
 METHODS = dict(vertices="update_vertices", transforms="update_transforms", skinned="update_skinned", morphed="update_morphed")
@@ -31,13 +29,6 @@ def vertex_arrays(model):
         base += m.vertex.shape[0]
         first.append(base)
     return np.concatenate(vidx), np.concatenate(vtx), np.concatenate(mesh_of), np.array(first)
-
-
-def debug_buffer(r, name):
-    """(device address, bytes) of fovpt_debug_buffer(name); raises lib.FovptError like every call of the renderer."""
-    p, n = C.c_void_p(), C.c_size_t()
-    r._check(r._L.fovpt_debug_buffer(r._ctx, name.encode(), C.byref(p), C.byref(n)))
-    return p.value, n.value
 
 
 def download_hits(r):

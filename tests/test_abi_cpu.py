@@ -2,6 +2,7 @@
 include/fovpt.h declares, layouts match, the C++ shim compiles, and the product fails loudly
 (no CPU fallback) when there is no GPU."""
 import ctypes as C
+import glob
 import os
 import re
 import subprocess
@@ -79,11 +80,21 @@ def test_struct_layouts_match_reference_abi():
 
 def test_cpp_headers_compile_and_assert_layouts():
     for src in ("shim_compile_check.cpp",):
-        subprocess.check_call(["g++", "-std=c++14", "-fsyntax-only", "-I", os.path.join(ROOT, "include"),
-                               os.path.join(ROOT, "tests", "cpp", src)])
+        header_layout.syntax_check_file(os.path.join(ROOT, "tests", "cpp", src))
     # the plain-C view of the header must compile as C too
-    subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-x", "c", "-I", os.path.join(ROOT, "include"), "-"],
-                   input=b'#include "fovpt.h"\nint main(void){return sizeof(fovpt_launch_params)==248?0:1;}\n', check=True)
+    header_layout.syntax_check('#include "fovpt.h"\nint main(void){return sizeof(fovpt_launch_params)==248?0:1;}\n', lang="c99")
+
+
+CPP_PROGRAMS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "tests", "cpp", "*.cpp")))
+assert len(CPP_PROGRAMS) >= 33, "tests/cpp/*.cpp not found"        # (here, not in a case: no programs would mean no cases to fail)
+
+
+@pytest.mark.parametrize("name", CPP_PROGRAMS)
+def test_every_cpp_program_of_the_tests_compiles(name):
+    """Each tests/cpp/*.cpp passes the compiler's syntax pass against include/ and the library's sources, so a slip in a program
+    or in tests/cpp/box_scene.h shows where there is no GPU to run it on."""
+    header_layout.syntax_check_file(os.path.join(ROOT, "tests", "cpp", name),
+                               include=[os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")])
 
 
 def test_config_mirror_matches_the_header():

@@ -50,7 +50,7 @@ import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import scenes
 
 from app_model import AppModel, LateModel, with_pytest_code
-from postprocess_common import bits
+from gpu_common import bits
 
 pytestmark = pytest.mark.gpu
 PROBE = scenes.ambient_probe(64, 32, 2.0)

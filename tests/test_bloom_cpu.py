@@ -341,4 +341,4 @@ def test_the_dropin_header_compiles():
           'fovpt_bloom_defaults(&bc); bc.flags = FOVPT_BLOOM_KARIS | FOVPT_BLOOM_GAINS | FOVPT_BLOOM_EXPOSURE_STATE; bc.levels = FOVPT_BLOOM_MAX_LEVELS; ' \
           's.bloom(bc); s.bloom(bc, m); s.bloomPost(bc); fovpt_expose_config ec; fovpt_expose_defaults(&ec); s.exposeBloom(ec); ' \
           's.downloadBloomColor(m); s.downloadBloomPixels(h); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)

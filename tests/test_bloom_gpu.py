@@ -6,22 +6,19 @@ fovpt_post -> fovpt_bloom -> fovpt_expose.  The frame description (size, passes,
 scene; the input colour is a seeded synthetic HDR image uploaded by the tests."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bloom_ref as br
 import expose_ref as ex
-import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
-from temporal_motion_common import debug_buffer
+from gpu_common import (bits, box_renderer, build_dropin, debug_buffer, device_images, dropin_renderer, frame_size, host_view,
+                        run_dropin, upload, with_entries, writer_fills)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
 PROBE = scenes.ambient_probe(64, 32, 2.5)
 f32 = np.float32
@@ -37,41 +34,10 @@ def radii(size):
     return max(1, m // 6), max(2, m // 3)
 
 
-def _box(size, cfg=None, gaze=None):
-    cfg = cfg if cfg is not None else cfg_foveated(*radii(size), (1, 1, 2))
-    cfg.write_guides = 1
-    return make_gpu(box_model(), PROBE, BOX_CAMERA, size, cfg, gaze=gaze)
-
-
 def bcfg(d=None):
     """fovpt_bloom_defaults with the entries of d replaced -> (abi.BloomConfig, the dict the restatement takes)."""
-    c = renderer.SampleRenderer.bloom_defaults()
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
+    c = with_entries(renderer.SampleRenderer.bloom_defaults(), d)
     return c, c.as_dict()
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_outputs(size, fill=0x5a):
-    """(colour, rgba) device tensors of a frame, every byte `fill`."""
-    import torch
-    w, h = size
-    t = [torch.full((h, w, 4 * k), fill, dtype=torch.uint8, device="cuda") for k in (4, 1)]
-    torch.cuda.synchronize()
-    return t
-
-
-def host(t, kind):
-    a = t.cpu().numpy()
-    if kind == "color":
-        return a.view(np.float32).reshape(a.shape[0], a.shape[1], 4)
-    return a.view(np.uint32).reshape(a.shape[0], a.shape[1])
 
 
 def hdr_image(size, seed):
@@ -88,22 +54,11 @@ def hdr_image(size, seed):
     return img
 
 
-def fills(r):
-    """The fill of each pixel's last writer for the frame r rendered last (r.launchParams and r.config as at render time)."""
-    f, cfg = r.launchParams.frame, r.config
-    return rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)[0], cfg.uniform
-
-
 def pyramid(r):
     """What fovpt_debug_buffer shows of the pyramid: (texels, 4) float32."""
     p, n = debug_buffer(r, "bloom_pyramid")
     assert n % 16 == 0
     return r.download(p, np.empty((n // 16, 4), np.float32))
-
-
-def frame_size(r):
-    f = r.launchParams.frame
-    return f.size.x, f.size.y
 
 
 def check(oracle, r, d, img, fill=None, in_ptr="upload", out=None, E=None, label=None):
@@ -119,9 +74,9 @@ def check(oracle, r, d, img, fill=None, in_ptr="upload", out=None, E=None, label
         got_c, got_px = r.downloadBloomColor(), r.downloadBloomPixels()
     else:
         r.synchronize()
-        got_c, got_px = host(out[0], "color"), host(out[1], "rgba")
+        got_c, got_px = host_view(out[0], "color"), host_view(out[1], "rgba")
     if full["flags"] & GAINS and fill is None:
-        fill = fills(r)
+        fill = writer_fills(r)
     want = br.bloom(oracle, img, full, E, *(fill if full["flags"] & GAINS else (None, 0)))
     got_pyr = pyramid(r)
     assert got_pyr.shape == want["pyramid"].shape == (br.level_offsets(size[0], size[1], full["levels"])[-1], 4), label
@@ -142,9 +97,9 @@ SIZES = [(1, 1), (2, 2), (3, 5), (17, 9), (65, 5), (64, 4), (130, 67)]
 def test_bit_for_bit(oracle, size):
     """Levels 1, 2, 5 and 8 (8 on 17 x 9 reaches 1 x 1 and keeps going) and every flag combination, each followed by a call with
     spread = 0, which leaves the d_k in the pyramid."""
-    r = _box(size)
+    r = box_renderer(size, cfg_foveated(*radii(size), (1, 1, 2)), write_guides=True)
     r.render()
-    fill = fills(r)
+    fill = writer_fills(r)
     seen = set(np.unique(fill[0]).tolist())
     print(size, "fills", sorted(seen))
     if size == (130, 67):
@@ -169,7 +124,7 @@ def test_bit_for_bit(oracle, size):
 
 def test_a_fov_off_frame_takes_gain_uniform(oracle):
     size = (37, 21)
-    r = _box(size, cfg_uniform(1))
+    r = box_renderer(size, cfg_uniform(1), write_guides=True)
     r.render()
     img = hdr_image(size, 12)
     a = check(oracle, r, dict(BASE, levels=3, flags=KARIS | GAINS), img, label="fov off")
@@ -186,12 +141,12 @@ def test_exposure_state(oracle):
     """No synchronisation between the expose and the bloom calls: the exposure goes from k_expose_adapt's record into
     k_bloom_prefilter on the device."""
     size = (96, 54)
-    r = _box(size)
+    r = box_renderer(size, cfg_foveated(*radii(size), (1, 1, 2)), write_guides=True)
     r.render()
     img = hdr_image(size, 14)
     dev = upload(img)
     d = dict(BASE, levels=4, flags=KARIS | STATE, exposure=0.25)
-    out = device_outputs(size)
+    out = device_images(size, 16, 4)
     before = check(oracle, r, d, img, in_ptr=dev.data_ptr(), out=out, E=0.25, label="before any AUTO step")
     assert r.expose_state().steps == 0
     ec = renderer.SampleRenderer.expose_defaults()
@@ -202,7 +157,7 @@ def test_exposure_state(oracle):
     st = r.expose_state()
     assert st.steps == 1 and f32(st.exposure) != f32(0.25) and 1e-3 < st.exposure < 1e3
     want = br.bloom(oracle, img, full, E=st.exposure)
-    got_c, got_px = host(out[0], "color"), host(out[1], "rgba")
+    got_c, got_px = host_view(out[0], "color"), host_view(out[1], "rgba")
     assert np.array_equal(bits(got_c), bits(want["color"])) and np.array_equal(got_px, want["rgba"])
     assert np.array_equal(bits(pyramid(r)), bits(want["pyramid"]))
     assert not np.array_equal(bits(want["color"]), bits(before["color"])) and not np.array_equal(bits(want["color"]), bits(img))
@@ -211,7 +166,7 @@ def test_exposure_state(oracle):
     r.expose_reset()
     r.bloom(cfg, dev.data_ptr(), out[0].data_ptr(), out[1].data_ptr())         # behind the reset, nothing in between
     r.synchronize()
-    assert np.array_equal(bits(host(out[0], "color")), bits(before["color"])) and np.array_equal(host(out[1], "rgba"), before["rgba"])
+    assert np.array_equal(bits(host_view(out[0], "color")), bits(before["color"])) and np.array_equal(host_view(out[1], "rgba"), before["rgba"])
     assert r.expose_state().steps == 0
     r.close()
 
@@ -219,11 +174,11 @@ def test_exposure_state(oracle):
 # ---- 3. the buffer conventions ---------------------------------------------------------------------------------------------------------
 def test_in_place_equals_out_of_place(oracle):
     size = (130, 67)
-    r = _box(size)
+    r = box_renderer(size, cfg_foveated(*radii(size), (1, 1, 2)), write_guides=True)
     r.render()
     img = hdr_image(size, 15)
     d = dict(BASE, levels=5, flags=KARIS | GAINS)
-    out = device_outputs(size)
+    out = device_images(size, 16, 4)
     apart = check(oracle, r, d, img, out=out, label="out of place")
     dev = upload(img)
     same = check(oracle, r, d, img, in_ptr=dev.data_ptr(), out=(dev, out[1]), label="in place")
@@ -235,7 +190,7 @@ def test_in_place_equals_out_of_place(oracle):
 
 def test_own_buffers_follow_a_resize(oracle):
     size = (64, 48)
-    r = _box(size)
+    r = box_renderer(size, cfg_foveated(*radii(size), (1, 1, 2)), write_guides=True)
     with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
         r.bloom()
     assert e.value.code == E_NO_FRAME
@@ -248,7 +203,7 @@ def test_own_buffers_follow_a_resize(oracle):
     assert own[0] and own[1] and own[0] != own[1]
     # caller-provided buffers leave the context's own alone
     own_c, own_px = r.downloadBloomColor(), r.downloadBloomPixels()
-    check(oracle, r, dict(d, intensity=0.9), hdr_image(size, 17), out=device_outputs(size), label="caller buffers")
+    check(oracle, r, dict(d, intensity=0.9), hdr_image(size, 17), out=device_images(size, 16, 4), label="caller buffers")
     assert np.array_equal(bits(own_c), bits(r.downloadBloomColor())) and np.array_equal(own_px, r.downloadBloomPixels())
     big = (150, 91)
     r.resize(big)
@@ -271,10 +226,10 @@ def test_bloom_is_ordered_with_frames_in_flight():
     size = (384, 216)
     cfg = cfg_foveated(20, 60, (4, 8, 16))
     cfg.frames_in_flight = 2
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg, write_guides=True)
     bc, _ = bcfg(dict(FOUR_GAINS, flags=KARIS | GAINS, threshold=0.5, intensity=0.5))
     views = [((190, 108), 0), ((300, 40), 1), ((80, 60), 2)]
-    outs = [[device_outputs(size) for _ in views] for _ in range(2)]
+    outs = [[device_images(size, 16, 4) for _ in views] for _ in range(2)]
     for sync, out in zip((True, False), outs):
         for g, k in views:                                   # the accum buffer's leftovers where no pass writes, as all views leave them
             r.launchParams.frame.c.x, r.launchParams.frame.c.y = g
@@ -293,10 +248,10 @@ def test_bloom_is_ordered_with_frames_in_flight():
     for want, got in zip(*outs):
         for x, y in zip(want, got):
             assert torch.equal(x, y)
-    a, b = host(outs[0][0][1], "rgba"), host(outs[0][2][1], "rgba")
+    a, b = host_view(outs[0][0][1], "rgba"), host_view(outs[0][2][1], "rgba")
     assert (a != b).mean() > 0.1                             # (the frames differ: the comparison is not of copies)
     accum = r.downloadAccum()
-    assert (bits(host(outs[0][2][0], "color")) != bits(accum)).any()          # and the stage acted on them
+    assert (bits(host_view(outs[0][2][0], "color")) != bits(accum)).any()          # and the stage acted on them
     r.close()
 
 
@@ -319,14 +274,14 @@ def test_rejections_leave_everything_unchanged(oracle):
     """Every FOVPT_E_INVALID case of the header and FOVPT_E_NO_FRAME, each leaving the outputs, the pyramid and the exposure state
     byte for byte.  (Not here: width * height >= 2^31, which needs a rendered frame of 32 GiB.)"""
     size = (64, 48)
-    r = _box(size)
+    r = box_renderer(size, cfg_foveated(*radii(size), (1, 1, 2)), write_guides=True)
     L = lib.load()
     r.render()
     img = hdr_image(size, 19)
     dev = upload(img)
     ec = renderer.SampleRenderer.expose_defaults()
     r.expose(ec, dev.data_ptr())
-    caller = device_outputs(size)
+    caller = device_images(size, 16, 4)
     good = dict(BASE, levels=5, flags=KARIS | GAINS | STATE)
     check(oracle, r, good, img, in_ptr=dev.data_ptr(), out=caller, E=r.expose_state().exposure, label="a valid call into caller's buffers")
     check(oracle, r, good, img, in_ptr=dev.data_ptr(), E=r.expose_state().exposure, label="a valid call")
@@ -406,9 +361,9 @@ def test_seeded_sweep(oracle, seed):
     ri = int(rng.integers(0, 12))
     cfg = cfg_uniform(1) if uniform else cfg_foveated(ri, ri + int(rng.integers(0, 24)), (1, 1, 1))
     gaze = (int(rng.integers(-8, w + 8)) & 0xffffffff, int(rng.integers(-8, h + 8)) & 0xffffffff)
-    r = _box((w, h), cfg, gaze=gaze)
+    r = box_renderer((w, h), cfg, gaze, write_guides=True)
     r.render()
-    fill = fills(r)
+    fill = writer_fills(r)
     for k in range(2):
         d = _random_config(rng)
         print(seed, k, (w, h), d)
@@ -419,21 +374,14 @@ def test_seeded_sweep(oracle, seed):
 # ---- 7. the C++ drop-in ----------------------------------------------------------------------------------------------------------------
 def test_cpp_dropin_bloom(tmp_path):
     """SampleRenderer::bloomPost() / bloom() / exposeBloom() of include/SimplePathtracer.h: the same bytes as Python."""
-    exe, out = str(tmp_path / "bloom_gpu_test"), str(tmp_path / "bloom_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "bloom_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "bloom_gpu_test"), str(tmp_path / "bloom_out.bin")
+    run_dropin(exe, out)
     n = 160 * 96
     raw = np.fromfile(out, np.uint32)
     assert raw.size == 2 * 4 * n + 3 * n
     color = raw[:8 * n].reshape(2, 96, 160, 4)
     px = raw[8 * n:].reshape(3, 96, 160)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r = dropin_renderer(write_guides=True)
     r.render()
     r.post()
     bc, _ = bcfg(dict(flags=KARIS | GAINS, levels=5, threshold=0.5, exposure=1.0, intensity=0.25, gain_fovea=1.0, gain_middle=0.5, gain_periphery=0.25))
@@ -466,15 +414,13 @@ def test_the_atrium_through_post_bloom_expose(oracle):
     ec = renderer.SampleRenderer.expose_defaults()
     r.expose(ec, r.bloomBuffers()[0])
     post = r.downloadPostColor()
-    want_b = br.bloom(oracle, post, bfull, None, *fills(r))
+    want_b = br.bloom(oracle, post, bfull, None, *writer_fills(r))
     assert np.array_equal(bits(r.downloadBloomColor()), bits(want_b["color"])) and np.array_equal(r.downloadBloomPixels(), want_b["rgba"])
     assert np.array_equal(bits(pyramid(r)), bits(want_b["pyramid"]))
     changed = (bits(want_b["color"]) != bits(post)).any(axis=-1).mean()
     print("atrium: pixels the bloom changed", changed, "pyramid maximum", float(want_b["pyramid"].max()))
     assert changed > 0.1
-    f, cfg = r.launchParams.frame, r.config
-    fill = rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)[0]
-    want_c, want_px, _, state = ex.expose(oracle, want_b["color"], ec.as_dict(), ex.new_state(), fill, cfg.uniform)
+    want_c, want_px, _, state = ex.expose(oracle, want_b["color"], ec.as_dict(), ex.new_state(), *writer_fills(r))
     assert np.array_equal(bits(r.downloadExposedColor()), bits(want_c)) and np.array_equal(r.downloadExposedPixels(), want_px)
     assert r.expose_state().steps == 1 and f32(r.expose_state().exposure) == f32(state["exposure"])
     r.close()

@@ -1,8 +1,6 @@
 """fovpt_denoise on the GPU: bit for bit the numpy restatement (tests/denoise_ref.py) applied to the GPU's own guide buffers,
 inputs left untouched, error codes, ordering with frames in flight, the gain in accuracy over the raw foveated frame, and the
 C++ drop-in."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,10 +9,10 @@ import denoise_ref as dn
 from fovpathtracing_optixcodelatest_amd import abi, lib, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import bits as _bits, check_denoise as _check_bits, dcfg as _dcfg, guides as _guides
+from gpu_common import bits as _bits, build_dropin, dropin_renderer, run_dropin
+from postprocess_common import check_denoise as _check_bits, dcfg as _dcfg, guides as _guides
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
 SIGMAS = ("color_sigma", "normal_sigma", "albedo_sigma")
 # the binary32 neighbours just outside [FOVPT_SIGMA_MIN, FOVPT_SIGMA_MAX]
@@ -200,22 +198,10 @@ def test_denoise_reduces_the_periphery_error():
 
 def test_cpp_dropin_denoise(tmp_path):
     """SampleRenderer::denoise() + downloadDenoisedPixels of include/SimplePathtracer.h: the same pixels as the Python surface."""
-    exe, out = str(tmp_path / "denoise_gpu_test"), str(tmp_path / "denoise_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "denoise_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "denoise_gpu_test"), str(tmp_path / "denoise_out.bin")
+    run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(2, 96, 160)
-    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
-    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
-    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
-    model = scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 1, 1), red)])
-    cam = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(model, scenes.ambient_probe(160, 96, 2.5), cam, (160, 96), cfg)
+    r = dropin_renderer(write_guides=True)
     r.render()
     r.denoise()
     assert np.array_equal(px[0], r.downloadPixels())

@@ -4,21 +4,17 @@ the buffer conventions, ordering with frames in flight, the buffers it must leav
 C++ drop-in.  Inputs are synthetic frames uploaded by the tests; the frame description (passes, gaze, FOV_OFF) is the rendered one."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import expose_ref as ex
-import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
-from temporal_motion_common import debug_buffer
+from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin, upload, with_entries, writer_fills
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
 CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
@@ -38,22 +34,7 @@ def ecfg(d):
     """fovpt_expose_defaults with the entries of d replaced -> (abi.ExposeConfig, the full dict for the restatement)."""
     c = abi.ExposeConfig()
     lib.check(None, lib.load().fovpt_expose_defaults(c))
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
-    return c, c.as_dict()
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def fills(r):
-    """The fill of each pixel's last writer for the frame r rendered last (r.launchParams and r.config as at render time)."""
-    f, cfg = r.launchParams.frame, r.config
-    return rr.writers(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)[0], cfg.uniform
+    return with_entries(c, d), c.as_dict()
 
 
 def histogram(r):
@@ -96,7 +77,7 @@ class Checker:
             got_c, got_px = r.downloadExposedColor(), r.downloadExposedPixels()
         else:
             got_c, got_px = r.download(out[0], np.empty(shape + (4,), np.float32)), r.download(out[1], np.empty(shape, np.uint32))
-        fill, uniform = fills(r) if full["metering"] == ex.GAZE and full["mode"] == ex.AUTO else (None, 0)
+        fill, uniform = writer_fills(r) if full["metering"] == ex.GAZE and full["mode"] == ex.AUTO else (None, 0)
         want_c, want_px, want_h, self.state = ex.expose(self.oracle, inp, full, self.state, fill, uniform)
         if want_h is not None:
             assert np.array_equal(histogram(r), want_h), label
@@ -132,7 +113,7 @@ def test_fixed_16_reinhard_1_is_the_resolves_rgba8(oracle, uniform):
     r.expose(c)
     got = r.downloadExposedPixels()
     accum = r.downloadAccum()
-    written = fills(r)[0] > 0
+    written = writer_fills(r)[0] > 0
     assert written.all() if uniform else (~written).sum() == 1
     assert np.array_equal(got[written], r.downloadPixels()[written])
     assert not accum[~written].any() and (r.downloadPixels()[~written] == 0).all()
@@ -517,21 +498,14 @@ def test_seeded_sweep(oracle, seed):
 # ---- 11. the C++ drop-in --------------------------------------------------------------------------------------------------------------
 def test_cpp_dropin_expose(tmp_path):
     """SampleRenderer::exposePost() / expose() / exposeState() of include/SimplePathtracer.h: the same pixels and states as Python."""
-    exe, out = str(tmp_path / "expose_gpu_test"), str(tmp_path / "expose_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "expose_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "expose_gpu_test"), str(tmp_path / "expose_out.bin")
+    run_dropin(exe, out)
     n = 160 * 96
     raw = np.fromfile(out, np.uint32)
     px = raw[:3 * n].reshape(3, 96, 160)
     states = raw[3 * n:].tobytes()
     assert len(states) == 64
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r = dropin_renderer(write_guides=True)
     c, _ = ecfg(dict(adapt_brighter=0.5, adapt_darker=0.5))
     for k in range(2):
         r.launchParams.frame.c.x, r.launchParams.frame.c.y = 80 + 40 * k, 48 - 30 * k

@@ -350,7 +350,7 @@ def test_the_static_asserts_compile():
     src = '#include <cstddef>\n#include "fovpt.h"\nstatic_assert(sizeof(fovpt_focus_config) == 64, "config");\n' \
           'static_assert(sizeof(struct fovpt_focus_state) == 32, "state");\n' \
           'int f(fovpt_ctx* c) { struct fovpt_focus_state s; return fovpt_focus_state(c, &s); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
     hdr = open(os.path.join(ROOT, "include", "fovpt.h")).read()
     for name in ("fovpt_focus_config", "struct fovpt_focus_state"):
         assert re.search(r"static_assert\(sizeof\(%s\) == " % re.escape(name), hdr), name
@@ -361,7 +361,7 @@ def test_the_dropin_header_compiles():
           'fovpt_focus_config fc; fovpt_focus_defaults(&fc); fc.mode = FOVPT_FOCUS_FIXED; fc.max_radius = FOVPT_FOCUS_MAX_RADIUS; ' \
           'fc.strength = s.focusStrength(0.05f); s.focus(fc); s.focus(fc, true, c); s.focusPost(fc); struct fovpt_focus_state st = s.focusState(); ' \
           '(void)st.focus; s.focusReset(); s.downloadFocus(c, h); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
 
 
 def test_focus_strength_is_the_thin_lens_factor():

@@ -4,8 +4,6 @@ the box scene, synthetic G-buffers at the smallest sizes, an AUTO sequence with 
 reallocation, and the C++ drop-in.  The restatement is fed the GPU's own G-buffer and colour; the conditions that keep a case from
 being vacuous are asserted on the restatement's output."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,11 +12,10 @@ import focus_ref as fr
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
-from temporal_motion_common import debug_buffer
+from gpu_common import (BOX_CAMERA, bits, box_renderer, build_dropin, debug_buffer, device_images, dropin_renderer, host_view,
+                        run_dropin, upload, with_entries)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 SIZE = (193, 109)                                   # odd, and no multiple of the gather's 32 x 16 tile: partial edge tiles
 PROBE = scenes.ambient_probe(64, 32, 2.5)
@@ -27,41 +24,10 @@ GAZES = dict(box=(96, 54), floor=(40, 20), sky=(96, 95), corner=(2, 2), outside=
 f32 = np.float32
 
 
-def _box(size=SIZE, cfg=None, gaze=None):
-    cfg = cfg if cfg is not None else cfg_foveated(12, 36, (1, 1, 2))
-    cfg.write_guides = 1
-    return make_gpu(box_model(), PROBE, BOX_CAMERA, size, cfg, gaze=gaze)
-
-
 def fcfg(d=None):
     """fovpt_focus_defaults with the entries of d replaced -> (abi.FocusConfig, the dict the restatement takes)."""
-    c = renderer.SampleRenderer.focus_defaults()
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
+    c = with_entries(renderer.SampleRenderer.focus_defaults(), d)
     return c, c.as_dict()
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_outputs(size, fill=0x5a):
-    """(colour, rgba, coc) device tensors of a frame, every byte `fill`."""
-    import torch
-    w, h = size
-    t = [torch.full((h, w, 4 * k), fill, dtype=torch.uint8, device="cuda") for k in (4, 1, 1)]
-    torch.cuda.synchronize()
-    return t
-
-
-def host(t, kind):
-    a = t.cpu().numpy()
-    if kind == "color":
-        return a.view(np.float32).reshape(a.shape[0], a.shape[1], 4)
-    return a.view(np.uint32 if kind == "rgba" else np.float32).reshape(a.shape[0], a.shape[1])
 
 
 def state_tuple(s):
@@ -89,7 +55,7 @@ class Checker:
         f = self.r.launchParams.frame
         size = (f.size.x, f.size.y)
         cfg, full = fcfg(d)
-        oc, op, oz = device_outputs(size)
+        oc, op, oz = device_images(size, 16, 4, 4)
         self.r.focus(cfg, gbuffer, in_ptr, oc.data_ptr(), op.data_ptr(), oz.data_ptr())
         want = fr.focus(self.oracle, gb, gaze_of(self.r), color, full, self.state)
         self.state = want["state"]
@@ -97,16 +63,16 @@ class Checker:
         print(label, "state", state_tuple(got), "sharp", int((want["covering"] == 1).sum()), "cap", int((want["coc"] == full["max_radius"]).sum()),
               "acted", int(want["acted"].sum()))
         assert state_tuple(got) == state_tuple(self.state), (label, state_tuple(got), state_tuple(self.state))
-        assert np.array_equal(bits(host(oz, "coc")), bits(want["coc"])), label
-        assert np.array_equal(bits(host(oc, "color")), bits(want["color"])), label
-        assert np.array_equal(host(op, "rgba"), want["rgba"]), label
+        assert np.array_equal(bits(host_view(oz, "coc")), bits(want["coc"])), label
+        assert np.array_equal(bits(host_view(oc, "color")), bits(want["color"])), label
+        assert np.array_equal(host_view(op, "rgba"), want["rgba"]), label
         return want
 
 
 # ---- 1. bit for bit ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def box():
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     yield r
     r.close()
 
@@ -174,7 +140,7 @@ def synthetic(size, seed):
 
 @pytest.mark.parametrize("size", [(1, 1), (17, 17), (70, 9), (9, 70), (37, 23)], ids=lambda s: "%dx%d" % s)
 def test_synthetic_gbuffers(oracle, size):
-    r = _box(size, cfg_uniform(1), gaze=(size[0] // 2, size[1] // 2))
+    r = box_renderer(size, cfg_uniform(1), (size[0] // 2, size[1] // 2), write_guides=True)
     r.render()
     ck = Checker(oracle, r)
     for seed, d in enumerate((dict(strength=3.0, max_radius=8), dict(strength=0.7, max_radius=5, rank_permille=900, meter_radius=64),
@@ -194,7 +160,7 @@ def test_synthetic_gbuffers(oracle, size):
 
 # ---- 3. an AUTO sequence and the reset paths ---------------------------------------------------------------------------------------
 def test_an_auto_sequence_and_the_reset_paths(oracle):
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     ck = Checker(oracle, r)
     rates = [(1.0, 1.0), (0.5, 0.25), (0.125, 0.75), (0.3, 0.7), (0.9, 0.05)]
     seen, gazes = [], dict(GAZES, far=(170, 45))                      # far: the slab behind the box
@@ -241,7 +207,7 @@ def test_an_auto_sequence_and_the_reset_paths(oracle):
 
 # ---- 4. the caller's G-buffer --------------------------------------------------------------------------------------------------------
 def test_the_temporal_steps_gbuffer_saves_the_trace(oracle):
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     r.render()
     r.post()
     g = r.temporal_gbuffer()
@@ -256,9 +222,9 @@ def test_the_temporal_steps_gbuffer_saves_the_trace(oracle):
     assert other.prim != g.prim and other.position != g.position
     before = r.downloadGBuffer(other)
     r.focus_reset()
-    oc, op, oz = device_outputs(SIZE)
+    oc, op, oz = device_images(SIZE, 16, 4, 4)
     r.focus(cfg, g, post_color, oc.data_ptr(), op.data_ptr(), oz.data_ptr())
-    assert np.array_equal(bits(host(oc, "color")), bits(own[0])) and np.array_equal(host(op, "rgba"), own[1])
+    assert np.array_equal(bits(host_view(oc, "color")), bits(own[0])) and np.array_equal(host_view(op, "rgba"), own[1])
     assert state_tuple(r.focus_state()) == own[2]
     after = r.downloadGBuffer(other)
     for k in before:
@@ -266,7 +232,7 @@ def test_the_temporal_steps_gbuffer_saves_the_trace(oracle):
     assert (before["prim"] != r.downloadGBuffer(g)["prim"]).mean() > 0.05      # (the two sets do hold different views)
     # against the restatement on the step's set
     want = fr.focus(oracle, r.downloadGBuffer(g), gaze_of(r), r.downloadPostColor(), full, fr.new_state())
-    assert np.array_equal(bits(own[0]), bits(want["color"])) and np.array_equal(bits(host(oz, "coc")), bits(want["coc"]))
+    assert np.array_equal(bits(own[0]), bits(want["color"])) and np.array_equal(bits(host_view(oz, "coc")), bits(want["coc"]))
     assert (want["covering"] > 1).any() and (want["covering"] == 1).any()
     r.close()
 
@@ -274,7 +240,7 @@ def test_the_temporal_steps_gbuffer_saves_the_trace(oracle):
 # ---- 5. a FOV_OFF frame and the atrium -----------------------------------------------------------------------------------------------
 def test_fov_off_160x90(oracle):
     size = (160, 90)
-    r = _box(size, cfg_uniform(2), gaze=(80, 45))
+    r = box_renderer(size, cfg_uniform(2), (80, 45), write_guides=True)
     r.render()
     ck = Checker(oracle, r)
     gb, color = r.downloadGBuffer(), r.downloadAccum()
@@ -307,10 +273,10 @@ def test_focus_is_ordered_with_frames_in_flight():
     size = (384, 216)
     cfg = cfg_foveated(20, 60, (4, 8, 16))
     cfg.frames_in_flight = 2
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg, write_guides=True)
     fc, _ = fcfg(dict(strength=40.0, adapt_nearer=0.5, adapt_farther=0.25))
     views = [((190, 108), 0), ((300, 40), 1), ((80, 60), 2)]
-    outs = [[device_outputs(size) for _ in views] for _ in range(2)]
+    outs = [[device_images(size, 16, 4, 4) for _ in views] for _ in range(2)]
     states = []
     for sync, out in zip((True, False), outs):
         for g, k in views:                                   # the accum buffer's leftovers where no pass writes, as all views leave them
@@ -333,20 +299,20 @@ def test_focus_is_ordered_with_frames_in_flight():
         for x, y in zip(want, got):
             assert torch.equal(x, y)
     assert states[0] == states[1] and states[0][4] == 3
-    a, b = host(outs[0][0][1], "rgba"), host(outs[0][2][1], "rgba")
+    a, b = host_view(outs[0][0][1], "rgba"), host_view(outs[0][2][1], "rgba")
     assert (a != b).mean() > 0.1                             # (the frames differ: the comparison is not of copies)
     r.close()
 
 
 # ---- 7. rejections -------------------------------------------------------------------------------------------------------------------
 def test_rejections_leave_everything_unchanged():
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     L = lib.load()
     with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
         r.focus()
     assert e.value.code == E_NO_FRAME and r.focus_state().steps == 0
     r.render()
-    oc, op, oz = device_outputs(SIZE)
+    oc, op, oz = device_images(SIZE, 16, 4, 4)
     good, _ = fcfg(dict(strength=40.0))
     r.focus(good, None, None, oc.data_ptr(), op.data_ptr(), oz.data_ptr())
     r.focus(good)
@@ -452,7 +418,7 @@ def before_steps(everything):
 # ---- 8. reallocation -----------------------------------------------------------------------------------------------------------------
 def test_resize_reallocates_the_focus_buffers(oracle):
     small, large = (96, 64), (200, 120)
-    r = _box(small)
+    r = box_renderer(small, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     with pytest.raises(lib.FovptError) as e:
         r.focus_buffers()
     assert e.value.code == E_NO_FRAME
@@ -485,13 +451,8 @@ def test_resize_reallocates_the_focus_buffers(oracle):
 # ---- 9. the C++ drop-in --------------------------------------------------------------------------------------------------------------
 def test_cpp_dropin_focus(tmp_path):
     """SampleRenderer::focus() / focusPost() / focusState() of include/SimplePathtracer.h: the same pixels and state as Python."""
-    exe, out = str(tmp_path / "focus_gpu_test"), str(tmp_path / "focus_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "focus_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "focus_gpu_test"), str(tmp_path / "focus_out.bin")
+    run_dropin(exe, out)
     size = (160, 96)
     n = size[0] * size[1]
     raw = np.fromfile(out, np.uint8)
@@ -499,9 +460,7 @@ def test_cpp_dropin_focus(tmp_path):
     col = raw[12 * n:60 * n].view(np.float32).reshape(3, size[1], size[0], 4)
     states = [abi.FocusState.from_buffer_copy(raw[60 * n + 32 * k:60 * n + 32 * (k + 1)].tobytes()) for k in range(2)]
     strength = raw[60 * n + 64:60 * n + 68].view(np.float32)[0]
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg)
+    r = dropin_renderer(write_guides=True)
     r.render()
     r.post()
     fc, _ = fcfg(dict(strength=40.0))

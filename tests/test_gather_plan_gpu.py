@@ -13,6 +13,7 @@ import gather_ref as gr
 from fovpathtracing_optixcodelatest_amd import lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
+from gpu_common import upload
 from gather_cases import CASES, IDS, random_words, restated, restated_for
 
 pytestmark = pytest.mark.gpu
@@ -49,13 +50,6 @@ def set_rank(r, rank):
     cfg = r.config
     cfg.rank = rank
     r.config = cfg
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32)).cuda()
-    torch.cuda.synchronize()
-    return t
 
 
 def words(t):

@@ -10,6 +10,7 @@ import pytest
 import generate_cases as gc
 import generate_ref as gr
 from fovpathtracing_optixcodelatest_amd import scenes
+from gpu_common import bits
 
 CASES = gc.cases()
 BY_NAME = {c.name: c for c in CASES}
@@ -20,10 +21,6 @@ def expected(oracle, case):
     if case.name not in _expected:
         _expected[case.name] = case.expected(oracle)
     return _expected[case.name]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.parametrize("name", ["37x23_spp3_guides", "30x12_ring_5_10", "40x20_blocks_negative_offset", "257x3_spp1"])

@@ -19,16 +19,13 @@ import pytest
 
 import generate_cases as gc
 from common import cfg_uniform, make_gpu
+from gpu_common import bits
 from fovpathtracing_optixcodelatest_amd import abi, renderer, scenes
 
 pytestmark = pytest.mark.gpu
 
 FILL = np.frombuffer(bytes([abi.DEBUG_SHADE_FILL] * 4), np.uint32)[0]
 CASES = gc.cases()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _renderer():

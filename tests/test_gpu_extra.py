@@ -4,7 +4,6 @@ accumulate mode, shadow catchers, tile sharding, the C++ drop-in shim, error beh
 full-size benchmark configurations."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, compare_frames, make_gpu, make_oracle
+from gpu_common import BOX_CAMERA, box_model, build_dropin, run_dropin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -185,27 +185,17 @@ def test_two_rank_tile_shards_sum_to_the_full_frame():
 
 def test_cpp_dropin_shim_end_to_end(oracle, tmp_path):
     """The C++ SampleRenderer of include/SimplePathtracer.h, used as PT_sv5_/main.cpp uses the reference's."""
-    exe, out = str(tmp_path / "shim_gpu_test"), str(tmp_path / "shim_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shim_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "shim_gpu_test"), str(tmp_path / "shim_out.bin")
+    res = run_dropin(exe, out)
     assert "subframe_index=1" in res.stdout
     px = np.fromfile(out, np.uint32).reshape(96, 160)
-    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
-    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
-    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
-    model = scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 1, 1), red)])
-    cam = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
-    S, F = make_oracle(oracle, model, scenes.ambient_probe(160, 96, 2.5), cam, (160, 96))
+    cam = BOX_CAMERA
+    S, F = make_oracle(oracle, box_model(), scenes.ambient_probe(160, 96, 2.5), cam, (160, 96))
     oracle.render(S, F, cfg_foveated(12, 36, (1, 2, 8)))
     assert np.array_equal(px, F.frame)
     # the same program on an OBJ file: loadOBJ of include/Model.h (the library's host-side loader) -> SampleRenderer
     _write_textured_obj(tmp_path)
-    res = subprocess.run([exe, out, str(tmp_path / "s.obj")], capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout + res.stderr
+    run_dropin(exe, out, tmp_path / "s.obj")
     px = np.fromfile(out, np.uint32).reshape(96, 160)
     from fovpathtracing_optixcodelatest_amd import loaders
     S, F = make_oracle(oracle, loaders.load_obj(str(tmp_path / "s.obj")), scenes.ambient_probe(160, 96, 2.5), cam, (160, 96))
@@ -217,8 +207,7 @@ def test_cpp_dropin_shim_end_to_end(oracle, tmp_path):
     rgbe = rng.integers(1, 256, (16, 32, 4), dtype=np.uint8)
     rgbe[..., 3] = rng.integers(126, 131, (16, 32))
     (tmp_path / "sky.hdr").write_bytes(encode_hdr_rle(rgbe))
-    res = subprocess.run([exe, out, str(tmp_path / "s.obj"), str(tmp_path / "sky.hdr")], capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout + res.stderr
+    run_dropin(exe, out, tmp_path / "s.obj", tmp_path / "sky.hdr")
     px = np.fromfile(out, np.uint32).reshape(96, 160)
     S, F = make_oracle(oracle, loaders.load_obj(str(tmp_path / "s.obj")), loaders.load_probe_texels(str(tmp_path / "sky.hdr")), cam, (160, 96))
     oracle.render(S, F, cfg_foveated(12, 36, (1, 2, 8)))
@@ -230,13 +219,8 @@ def test_cpp_host_gathers_over_rccl(tmp_path):
     library's own RCCL gather (fovpt_comm_init / fovpt_gather_frame: pack -> ncclSend / ncclRecv on fovpt_stream() -> unpack)
     with a communicator of one rank, three frames back to back without host synchronisation: the gathered frame is the
     rendered frame."""
-    exe, out = str(tmp_path / "rccl_gather_test"), str(tmp_path / "rccl_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "rccl_gather_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "rccl_gather_test", extra=["-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"]), str(tmp_path / "rccl_out.bin")
+    res = run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(2, 96, 160)
     assert (px[0] != 0).sum() > 0.9 * px[0].size
     assert np.array_equal(px[0], px[1]), res.stdout

@@ -231,7 +231,7 @@ def test_the_dropin_header_compiles():
     src = '#include "SimplePathtracer.h"\nvoid f(SampleRenderer& s, const sutil::Camera& cam, fovpt_float4* c, uint32_t* h) { s.lens(); s.lens(&cam); ' \
           'fovpt_lens_config lc = SampleRenderer::lensDefaults(); lc.filter = FOVPT_LENS_BICUBIC; lc.encode = FOVPT_LENS_ENCODE_RESOLVE; ' \
           'lc = s.lensForFrame(lc); s.lens(lc); s.lens(lc, &cam, c); fovpt_float4* oc; uint32_t* op; s.lensBuffers(&oc, &op); s.downloadLens(c, h); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
 
 
 # ---- the kernel's index function on the host -------------------------------------------------------------------------------------------

@@ -7,23 +7,20 @@ The conditions that keep a case from being vacuous are asserted on the restateme
 import ctypes as C
 import itertools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import lens_ref as lr
-from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
 
-from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
+from common import cfg_foveated
+from gpu_common import (BOX_CAMERA, bits, box_renderer, build_dropin, camera, device_images, dropin_renderer, host_view,
+                        run_dropin, upload, with_entries)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
 SIZES = [(1, 1), (2, 1), (1, 3), (5, 4), (33, 17), (193, 109)]
-PROBE = scenes.ambient_probe(64, 32, 2.5)
 FILTERS = (abi.LENS_NEAREST, abi.LENS_BILINEAR, abi.LENS_BICUBIC)
 DISTINCT, EQUAL = (0.97, 1.0, 1.04), (1.014, 1.014, 1.014)
 BORDER = (0.25, 0.5, 0.75, 0.5)
@@ -37,10 +34,6 @@ CASES = {
 }
 
 
-def _box(size, cfg=None):
-    return make_gpu(box_model(), PROBE, BOX_CAMERA, size, cfg if cfg is not None else cfg_uniform(1))
-
-
 def lcfg(size, **d):
     """fovpt_lens_defaults, fitted to the frame unless fit=False, with the entries of d replaced -> (abi.LensConfig, the dict the
     restatement takes)."""
@@ -51,15 +44,7 @@ def lcfg(size, **d):
     by = d.pop("src_scale_by", None)
     if by is not None:
         c.src_scale[0], c.src_scale[1] = c.src_scale[0] * by, c.src_scale[1] * by
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c, c.as_dict()
-
-
-def camera_of(r):
-    cam = r.launchParams.camera
-    vec = lambda v: (float(v.x), float(v.y), float(v.z))
-    return dict(eye=vec(cam.eye), U=vec(cam.U), V=vec(cam.V), W=vec(cam.W))
+    return with_entries(c, d), c.as_dict()
 
 
 def turned(size, degrees):
@@ -81,37 +66,14 @@ def synthetic(size, seed=0):
     return c
 
 
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_outputs(size, fill=0x5a):
-    """(colour, rgba) device tensors of a frame, every byte `fill`."""
-    import torch
-    w, h = size
-    t = [torch.full((h, w, 4 * k), fill, dtype=torch.uint8, device="cuda") for k in (4, 1)]
-    torch.cuda.synchronize()
-    return t
-
-
-def host(t, kind):
-    a = t.cpu().numpy()
-    if kind == "color":
-        return a.view(np.float32).reshape(a.shape[0], a.shape[1], 4)
-    return a.view(np.uint32).reshape(a.shape[0], a.shape[1])
-
-
 def run(r, oracle, color, dev_color, cfg, full, to=None, label=None):
     """One fovpt_lens of the uploaded colour into caller's buffers, compared with the restatement -> the restatement's output."""
     f = r.launchParams.frame
     size = (f.size.x, f.size.y)
-    oc, op = device_outputs(size)
+    oc, op = device_images(size, 16, 4)
     r.lens(cfg, to[0] if to else None, dev_color.data_ptr(), oc.data_ptr(), op.data_ptr())
     r.synchronize()
-    want = lr.lens(oracle, color, full, camera_of(r), to[1] if to else None)
+    want = lr.lens(oracle, color, full, camera(r), to[1] if to else None)
     n = lr.TAPS[full["filter"]] ** 2
     partly = (want["border_taps"] > 0) & (want["border_taps"] < n)
     x0, y0, ok = want["x0"], want["y0"], want["valid"].all(axis=-1)
@@ -121,15 +83,15 @@ def run(r, oracle, color, dev_color, cfg, full, to=None, label=None):
                           behind=int((~want["front"]).sum()),
                           partly_outside=int(partly.sum()), channels_apart=int(apart.sum()))
     print(label, want["counts"])
-    assert np.array_equal(bits(host(oc, "color")), bits(want["color"])), label
-    assert np.array_equal(host(op, "rgba"), want["rgba"]), label
+    assert np.array_equal(bits(host_view(oc, "color")), bits(want["color"])), label
+    assert np.array_equal(host_view(op, "rgba"), want["rgba"]), label
     return want
 
 
 # ---- 1. bit for bit --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
 def test_bit_for_bit(oracle, size):
-    r = _box(size)
+    r = box_renderer(size)
     r.render()
     color = synthetic(size, size[0])
     dev = upload(color)
@@ -150,7 +112,7 @@ def test_bit_for_bit(oracle, size):
 @pytest.mark.parametrize("flt", FILTERS)
 def test_the_cases_are_what_they_are_meant_to_be(oracle, flt):
     size = SIZES[-1]
-    r = _box(size)
+    r = box_renderer(size)
     r.render()
     color = synthetic(size, 7)
     dev = upload(color)
@@ -175,7 +137,7 @@ def test_the_cases_are_what_they_are_meant_to_be(oracle, flt):
     assert (want["color"][..., 3] == 1.0).all()
     cfg, full = lcfg(size, filter=flt, chroma=EQUAL, border=BORDER)
     want = run(r, oracle, color, dev, cfg, full, small, label=(flt, "equal"))
-    each = lr.lens(oracle, color, full, camera_of(r), small[1], share=False)
+    each = lr.lens(oracle, color, full, camera(r), small[1], share=False)
     assert np.array_equal(bits(want["color"]), bits(each["color"])) and np.array_equal(want["rgba"], each["rgba"])
     # the 120 degree turn: part of the frame looks behind the rendered camera (a.z <= 0), the rest in front of it but far beside its
     # image (the two cameras' fields of view do not meet); a 50 degree turn keeps a part of the image
@@ -195,7 +157,7 @@ def test_the_cases_are_what_they_are_meant_to_be(oracle, flt):
 # ---- 2. the accum buffer, the renderer's own buffers, reallocation ---------------------------------------------------------------------
 def test_the_accum_buffer_the_own_buffers_and_a_resize(oracle):
     small, large = (96, 64), (200, 120)
-    r = _box(small)
+    r = box_renderer(small)
     with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
         r.lens()
     assert e.value.code == E_NO_FRAME
@@ -205,13 +167,13 @@ def test_the_accum_buffer_the_own_buffers_and_a_resize(oracle):
     r.render()
     accum = r.downloadAccum()
     cfg, full = lcfg(small, filter=abi.LENS_BICUBIC, encode=abi.LENS_ENCODE_RESOLVE)
-    oc, op = device_outputs(small)
+    oc, op = device_images(small, 16, 4)
     r.lens(cfg, None, None, oc.data_ptr(), op.data_ptr())    # in_color None: the accum buffer
     r.lens(cfg)                                              # and into the renderer's own buffers
     got_c, got_p = r.downloadLens()
     want = lr.lens(oracle, accum, full)
     assert np.array_equal(bits(got_c), bits(want["color"])) and np.array_equal(got_p, want["rgba"])
-    assert np.array_equal(bits(host(oc, "color")), bits(got_c)) and np.array_equal(host(op, "rgba"), got_p)
+    assert np.array_equal(bits(host_view(oc, "color")), bits(got_c)) and np.array_equal(host_view(op, "rgba"), got_p)
     assert len(np.unique(got_p)) > 20 and np.array_equal(bits(r.downloadAccum()), bits(accum))
     before = r.lens_buffers()
     r.resize(large)
@@ -238,10 +200,10 @@ def test_lens_is_ordered_with_frames_in_flight():
     size = (384, 216)
     cfg = cfg_foveated(20, 60, (4, 8, 16))
     cfg.frames_in_flight = 2
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     lc, _ = lcfg(size, encode=abi.LENS_ENCODE_RESOLVE)
     views = [((190, 108), 0), ((300, 40), 1), ((80, 60), 2)]
-    outs = [[device_outputs(size) for _ in views] for _ in range(2)]
+    outs = [[device_images(size, 16, 4) for _ in views] for _ in range(2)]
     for sync, out in zip((True, False), outs):
         for g, k in views:                                   # the accum buffer's leftovers where no pass writes, as all views leave them
             r.launchParams.frame.c.x, r.launchParams.frame.c.y = g
@@ -260,7 +222,7 @@ def test_lens_is_ordered_with_frames_in_flight():
     for want, got in zip(*outs):
         for x, y in zip(want, got):
             assert torch.equal(x, y)
-    a, b = host(outs[0][0][1], "rgba"), host(outs[0][2][1], "rgba")
+    a, b = host_view(outs[0][0][1], "rgba"), host_view(outs[0][2][1], "rgba")
     assert (a != b).mean() > 0.1                             # (the frames differ: the comparison is not of copies)
     r.close()
 
@@ -268,14 +230,14 @@ def test_lens_is_ordered_with_frames_in_flight():
 # ---- 4. rejections ---------------------------------------------------------------------------------------------------------------------
 def test_rejections_leave_everything_unchanged():
     size = (96, 64)
-    r = _box(size)
+    r = box_renderer(size)
     L = lib.load()
     good, _ = lcfg(size)
     with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
         r.lens(good)
     assert e.value.code == E_NO_FRAME
     r.render()
-    oc, op = device_outputs(size)
+    oc, op = device_images(size, 16, 4)
     to, _ = turned(size, 2.0)
     r.lens(good, to, None, oc.data_ptr(), op.data_ptr())
     r.lens(good, to)
@@ -383,21 +345,15 @@ def test_rejections_leave_everything_unchanged():
 # ---- 5. the C++ drop-in ----------------------------------------------------------------------------------------------------------------
 def test_cpp_dropin_lens(oracle, tmp_path):
     """SampleRenderer::lens() / lensForFrame() / downloadLens() of include/SimplePathtracer.h: the same pixels as Python."""
-    exe, out = str(tmp_path / "lens_gpu_test"), str(tmp_path / "lens_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "lens_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "lens_gpu_test"), str(tmp_path / "lens_out.bin")
+    run_dropin(exe, out)
     size = (160, 96)
     n = size[0] * size[1]
     raw = np.fromfile(out, np.uint8)
     px = raw[:8 * n].view(np.uint32).reshape(2, size[1], size[0])
     col = raw[8 * n:40 * n].view(np.float32).reshape(2, size[1], size[0], 4)
     fitted = abi.LensConfig.from_buffer_copy(raw[40 * n:40 * n + 128].tobytes())
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg)
+    r = dropin_renderer()
     r.render()
     assert bytes(fitted) == bytes(renderer.SampleRenderer.lens_for_frame(renderer.SampleRenderer.lens_defaults(), *size))
     r.lens()
@@ -408,7 +364,7 @@ def test_cpp_dropin_lens(oracle, tmp_path):
     r.lens(lc, to)
     got_c, got_p = r.downloadLens()
     assert np.array_equal(px[1], got_p) and np.array_equal(bits(col[1]), bits(got_c))
-    want = lr.lens(oracle, r.downloadAccum(), full, camera_of(r), camera_of_to(to))
+    want = lr.lens(oracle, r.downloadAccum(), full, camera(r), camera_of_to(to))
     assert np.array_equal(bits(got_c), bits(want["color"])) and np.array_equal(got_p, want["rgba"])
     assert (px[1] != px[0]).mean() > 0.05 and len(np.unique(px[0])) > 20
     r.close()

@@ -6,7 +6,6 @@ FOVPT_FUZZMO_TO widens the sweep."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,13 +17,12 @@ import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import bits
+from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin
 from temporal_common import tcfg
-from temporal_motion_common import debug_buffer, vertex_arrays as motion_arrays
+from temporal_motion_common import vertex_arrays as motion_arrays
 from test_refit_gpu import assert_frame_is_oracle, hierarchy, jitter, moved, oracle_frame, render
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE = -1, -3
 CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
@@ -810,13 +808,8 @@ def test_seeded_targets_and_weights(sweep_scene, seed):
 def test_cpp_set_morphs_and_update_morphed(tmp_path):
     """SampleRenderer::setMorphs / updateMorphed of include/SimplePathtracer.h: the hashes of the frame and of the vertex bytes
     the program prints are those of the same targets and weights through the python wrapper."""
-    exe = str(tmp_path / "morph_gpu_test")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "morph_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run(["timeout", "-k", "10", "300", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe = build_dropin(tmp_path, "morph_gpu_test")
+    res = run_dropin(exe)
     got = re.search(r"frame ([0-9a-f]{16}) vertices ([0-9a-f]{16})", res.stdout)
     assert got and res.stdout.rstrip().endswith("ok"), res.stdout
 
@@ -826,13 +819,8 @@ def test_cpp_set_morphs_and_update_morphed(tmp_path):
             h = ((h ^ x) * 1099511628211) & 0xffffffffffffffff
         return "%016x" % h
 
-    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
-    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
-    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
-    model = scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 2, 0.5), red)])
-    cam = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
-    size = (160, 96)
-    r = make_gpu(model, scenes.ambient_probe(160, 96, 2.5), cam, size, cfg_foveated(12, 36, (1, 2, 8)))
+    r = dropin_renderer(red_half=(1, 2, 0.5))
+    model = r.model
     v = model.meshes[1].vertex
     lean = np.zeros_like(v)
     lean[:, 0], lean[:, 2] = F(0.25) * v[:, 1], F(-0.125)

@@ -282,7 +282,7 @@ def test_struct_mirror_defines_prototypes_and_exports(libs):
     for n in names:
         assert not hasattr(loader, n), n                                  # (the context's entry points need the device)
     assert "submitPacket(uint32_t sequence, const fovpt_packet_config& codec" in open(os.path.join(ROOT, "include", "SimplePathtracer.h")).read()
-    subprocess.check_call(["g++", "-std=c++14", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "packet_bc_shim_check.cpp")])
+    header_layout.syntax_check_file(os.path.join(ROOT, "tests", "cpp", "packet_bc_shim_check.cpp"))
     # the context's entry points without a context
     assert full.fovpt_packet_describe_coded(None, None, None, 0, None) == E_INVALID and full.fovpt_packet_encode_coded(None, None, None, None, 0, None) == E_INVALID
     assert full.fovpt_packet_submit_coded(None, None, None, None, 0, None) == E_INVALID

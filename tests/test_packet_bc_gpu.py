@@ -13,6 +13,7 @@ import packet_ref as pk
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
+from gpu_common import device_filled, upload
 from packet_bc_cases import coded_mutations, masks_for
 from packet_cases import IDS, JUNK, SHAPES, junk_canvas, random_frame
 
@@ -30,20 +31,6 @@ def _cornell(size, gaze, radii, uniform, spp=(1, 1, 2)):
     return make_gpu(scenes.cornell_box(), PROBE, scenes.CORNELL_CAMERA, size, cfg, gaze=gaze)
 
 
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_bytes(n, fill=0x5a):
-    import torch
-    t = torch.full((n,), fill, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    return t
-
-
 def frame_of(r):
     """(size, gaze, radii, FOV_OFF) of the frame r rendered last, as packet_ref takes them."""
     f, cfg = r.launchParams.frame, r.config
@@ -54,7 +41,7 @@ def encode_on_device(r, sequence, codec, in_rgba=None):
     """fovpt_packet_encode_coded into a junk-filled buffer with canary bytes behind the packet -> (the packet's bytes, the device
     buffer); the canary stays."""
     h = r.describePacket(sequence, codec)
-    buf = device_bytes(h.bytes + CANARY)
+    buf = device_filled(h.bytes + CANARY)
     h2 = r.encodePacket(buf.data_ptr(), sequence, in_rgba, codec)
     assert bytes(h) == bytes(h2)
     r.synchronize()
@@ -116,7 +103,7 @@ def test_encode_and_decode_match_the_reference(shape):
     assert [abi.PacketHeader.from_packet(got).passes[p]._reserved for p in range(npass)] == ([0] if uniform else [1, 1, 0])
     # the raw encoder, as it was
     h = r.describePacket(9)
-    buf = device_bytes(h.bytes + CANARY)
+    buf = device_filled(h.bytes + CANARY)
     r.encodePacket(buf.data_ptr(), 9, dev.data_ptr())
     r.synchronize()
     got = buf.cpu().numpy().tobytes()
@@ -170,7 +157,7 @@ def test_error_codes_all_or_nothing():
     r = _cornell(size, gaze, radii, uniform)
     lp = C.byref(r.launchParams)
     hdr, slot = abi.PacketHeader(), C.c_int(-7)
-    buf = device_bytes(4096)
+    buf = device_filled(4096)
     good = abi.PacketConfig((1, 1, 0), 0)
     cfg = C.byref(good)
 

@@ -4,7 +4,6 @@ the calls must leave alone, every rejection of the context's entry points, a see
 Cornell box at the shapes of tests/packet_cases.py, spp 1 / 1 / 2."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,11 +12,10 @@ import packet_ref as pk
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
+from gpu_common import build_dropin, device_filled, dropin_renderer, run_dropin, upload
 from packet_cases import IDS, JUNK, SHAPES, junk_canvas, mutations, random_frame
-from postprocess_common import BOX_CAMERA, box_model
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
 PROBE = scenes.ambient_probe(64, 32, 2.0)
 
@@ -26,20 +24,6 @@ def _cornell(size, gaze, radii, uniform, spp=(1, 1, 2), guides=False):
     cfg = cfg_uniform(1) if uniform else cfg_foveated(radii[0], radii[1], spp)
     cfg.write_guides = 1 if guides else 0
     return make_gpu(scenes.cornell_box(), PROBE, scenes.CORNELL_CAMERA, size, cfg, gaze=gaze)
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_bytes(n, fill=0x5a):
-    import torch
-    t = torch.full((n,), fill, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    return t
 
 
 def frame_of(r):
@@ -51,7 +35,7 @@ def frame_of(r):
 def encode_on_device(r, sequence, in_rgba=None):
     """fovpt_packet_encode into a junk-filled buffer 64 bytes longer than the packet -> the packet's bytes; the tail stays junk."""
     h = r.describePacket(sequence)
-    buf = device_bytes(h.bytes + 64)
+    buf = device_filled(h.bytes + 64)
     h2 = r.encodePacket(buf.data_ptr(), sequence, in_rgba)
     assert bytes(h) == bytes(h2)
     r.synchronize()
@@ -204,7 +188,7 @@ def test_rejections_all_or_nothing():
     r = _cornell(size, gaze, radii, uniform)
     lp = C.byref(r.launchParams)
     hdr, slot, ptr, n = abi.PacketHeader(), C.c_int(-7), C.c_void_p(), C.c_size_t()
-    buf = device_bytes(4096)
+    buf = device_filled(4096)
 
     def untouched():
         r.synchronize()
@@ -316,13 +300,8 @@ def test_seeded_sweep(seed):
 def test_cpp_dropin_packets(tmp_path):
     """SampleRenderer::submitPacket() / waitPacket() of include/SimplePathtracer.h and fovpt_packet_decode_host: three frames in
     flight, each packet decoded on the host and compared with downloadPixels -- there and, with the reference, here."""
-    exe, out = str(tmp_path / "packet_gpu_test"), str(tmp_path / "packet_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "packet_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "packet_gpu_test"), str(tmp_path / "packet_out.bin")
+    run_dropin(exe, out)
     size, n = (160, 96), 160 * 96
     raw = np.fromfile(out, np.uint32)
     sizes, frames, decoded = raw[:3], raw[3:3 + 3 * n].reshape(3, 96, 160), raw[3 + 3 * n:].reshape(3, 96, 160)
@@ -334,8 +313,7 @@ def test_cpp_dropin_packets(tmp_path):
         assert np.array_equal(decoded[k][written], frames[k][written]) and not decoded[k][~written].any() and written.mean() > 0.99
         assert len(np.unique(decoded[k])) > 20
     # the frames are what Python renders
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg, gaze=(150, 10), subframe_index=1)
+    r = dropin_renderer(gaze=(150, 10), subframe_index=1)
     r.render()
     written = pk.owners(size, (150, 10), (12, 36), False)[0] >= 0
     assert np.array_equal(r.downloadPixels()[written], frames[1][written])

@@ -3,8 +3,6 @@ for bit tests/post_ref.py on the GPU's own inputs while meshes move, the modes a
 points, the buffers it must leave alone, ordering with frames in flight, every error code with nothing enqueued and no state
 moved, and the C++ drop-in."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,14 +12,12 @@ from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
 from post_common import D, M, R, T, PostChecker, pcfg, same, separate
-from postprocess_common import BOX_CAMERA, bits, box_model
+from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin
 from temporal_common import tcfg
-from temporal_motion_common import debug_buffer
 from test_refit_gpu import cornell_motions, jitter
 from test_temporal_gpu import ALL_CAPS, _atrium, _scene_again, _view
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
@@ -514,21 +510,14 @@ def test_post_errors_are_all_or_nothing():
 def test_cpp_dropin_post(tmp_path):
     """SampleRenderer::post() + downloadPostPixels / downloadMotion of include/SimplePathtracer.h: the same pixels and motion
     vectors as Python."""
-    exe, out = str(tmp_path / "post_gpu_test"), str(tmp_path / "post_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "post_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "post_gpu_test"), str(tmp_path / "post_out.bin")
+    run_dropin(exe, out)
     n = 160 * 96
     raw = np.fromfile(out, np.uint32)
     px = raw[:2 * n].reshape(2, 96, 160)
     mv = raw[2 * n:].view(np.float32).reshape(96, 160, 4)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    model = box_model()
-    r = make_gpu(model, scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r = dropin_renderer(write_guides=True)
+    model = r.model
     r.render()
     r.post()
     assert np.array_equal(px[0], r.downloadPostPixels())

@@ -10,8 +10,8 @@ import postprocess_fuzz as pf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu, make_oracle
-from postprocess_common import (BOX_CAMERA, bits, box_model, check_denoise, check_gbuffer_prim, check_reconstruct,
-                                expected_gbuffer, expected_reconstruct, rcfg)
+from gpu_common import bits, BOX_CAMERA, box_model
+from postprocess_common import check_denoise, check_gbuffer_prim, check_reconstruct, expected_gbuffer, expected_reconstruct, rcfg
 
 pytestmark = pytest.mark.gpu
 E_INVALID, E_NO_FRAME = -1, -5

@@ -279,4 +279,4 @@ def test_the_dropin_header_compiles():
           'fovpt_quality_config qc = SampleRenderer::qualityDefaults(); qc.ring_width = 8; fovpt_quality_sums out = s.measureQuality(ref); ' \
           'out = s.measureQuality(ref, test, &qc, cls); s.qualityAsync(ref, test, &qc, dev, cls); out = s.readQuality(); ' \
           'double m = fovpt_quality_mse(&out, -1); (void)m; }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)

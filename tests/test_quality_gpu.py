@@ -5,7 +5,6 @@ every rejection, a seeded sweep, and the C++ drop-in.  The test and reference im
 frame description (passes, gaze, FOV_OFF) is the rendered one."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +14,9 @@ import quality_ref as qr
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
+from gpu_common import bits, build_dropin, device_filled, dropin_renderer, run_dropin, upload, with_entries
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_FRAME = -1, -5
 CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
@@ -33,21 +31,6 @@ def _cornell(size=SIZE, cfg=None, gaze=None):
     return make_gpu(scenes.cornell_box(), PROBE, CORNELL, size, cfg, gaze=gaze)
 
 
-def upload(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    t = torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_bytes(n, fill=0xa5):
-    import torch
-    t = torch.full((n,), fill, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    return t
-
-
 def sums_of(t):
     """The abi.QualitySums a device record (a uint8 tensor) holds."""
     return abi.QualitySums.from_buffer_copy(t.cpu().numpy().tobytes())
@@ -55,9 +38,7 @@ def sums_of(t):
 
 def qcfg(d=None):
     """fovpt_quality_defaults with the entries of d replaced -> (abi.QualityConfig, the dict for the restatement)."""
-    c = renderer.SampleRenderer.quality_defaults()
-    for k, v in (d or {}).items():
-        setattr(c, k, v)
+    c = with_entries(renderer.SampleRenderer.quality_defaults(), d)
     return c, dict(flags=c.flags, ring_width=c.ring_width)
 
 
@@ -84,7 +65,7 @@ def check(r, test, ref, d=None, classes=None, label=None):
     w, h = f.size.x, f.size.y
     c, full = qcfg(d)
     dt, dr = upload(test), upload(ref)
-    out, cls = device_bytes(SUMS_BYTES), device_bytes(w * h, 0xee)
+    out, cls = device_filled(SUMS_BYTES, 0xa5), device_filled(w * h, 0xee)
     r.qualityAsync(dr.data_ptr(), dt.data_ptr(), c, out.data_ptr(), cls.data_ptr())
     r.synchronize()
     got, got_cls = sums_of(out), cls.cpu().numpy().reshape(h, w)
@@ -118,7 +99,7 @@ def test_rendered_cornell_frames(uniform):
     want, _ = check(r, test, test, None, classes, "equal images")
     assert want["ssim_q20"] == [n << 20 for n in want["windows"]] and want["differing"] == [0] * 5
     dt = upload(test)
-    out = device_bytes(SUMS_BYTES)
+    out = device_filled(SUMS_BYTES, 0xa5)
     r.qualityAsync(dt.data_ptr(), dt.data_ptr(), None, out.data_ptr())
     r.synchronize()
     assert sums_of(out).as_dict() == want
@@ -212,7 +193,7 @@ def test_quality_measures_the_frame_that_was_rendered_with_frames_in_flight():
         for g, k in views:                                   # the frame buffer's leftovers where no pass writes, as all views leave them
             setup(g, k)
             r.render()
-        outs = [(device_bytes(SUMS_BYTES), device_bytes(size[0] * size[1], 0xee)) for _ in views]
+        outs = [(device_filled(SUMS_BYTES, 0xa5), device_filled(size[0] * size[1], 0xee)) for _ in views]
         for (g, k), (out, cls) in zip(views, outs):
             setup(g, k)
             r.render_async()
@@ -241,7 +222,7 @@ def test_measurements_in_flight_and_the_contexts_own_record():
     jobs = []
     for k, d in enumerate((dict(flags=qr.SSIM), dict(flags=qr.PROFILE, ring_width=2), dict(ring_width=30))):
         test, ref = random_pair(rng, *SIZE, near=k != 1)
-        jobs.append((test, ref, qcfg(d), upload(test), upload(ref), device_bytes(SUMS_BYTES)))
+        jobs.append((test, ref, qcfg(d), upload(test), upload(ref), device_filled(SUMS_BYTES, 0xa5)))
     for test, ref, (c, _), dt, dr, out in jobs:              # three calls back to back, nothing in between
         r.qualityAsync(dr.data_ptr(), dt.data_ptr(), c, out.data_ptr())
     r.synchronize()
@@ -334,7 +315,7 @@ def test_rejections_leave_everything_unchanged():
     assert e.value.code == E_NO_FRAME
     r.render()
     r.qualityAsync(dr.data_ptr(), dt.data_ptr())             # the context's record holds a measurement
-    out, cls = device_bytes(SUMS_BYTES, 0x3c), device_bytes(SIZE[0] * SIZE[1], 0x77)
+    out, cls = device_filled(SUMS_BYTES, 0x3c), device_filled(SIZE[0] * SIZE[1], 0x77)
     L = lib.load()
 
     def everything():
@@ -414,17 +395,12 @@ def test_seeded_sweep(seed):
 def test_cpp_dropin_quality(tmp_path):
     """SampleRenderer::measureQuality() / qualityAsync() / readQuality() of include/SimplePathtracer.h: the same records as Python,
     which are the restatement's."""
-    exe, out = str(tmp_path / "quality_gpu_test"), str(tmp_path / "quality_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "quality_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "quality_gpu_test"), str(tmp_path / "quality_out.bin")
+    run_dropin(exe, out)
     raw = open(out, "rb").read()
     assert len(raw) == 3 * SUMS_BYTES
     recs = [abi.QualitySums.from_buffer_copy(raw[k * SUMS_BYTES:(k + 1) * SUMS_BYTES]) for k in range(3)]
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg_foveated(12, 36, (1, 2, 8)), gaze=(110, 38))
+    r = dropin_renderer(gaze=(110, 38))
     r.render()
     r.lens()
     frame, lens = r.downloadPixels(), r.downloadLens()[1]

@@ -46,7 +46,7 @@ def test_the_cpp_shim_maps_its_third_choice_to_the_flag():
            "void (SampleRenderer::*accel)(const std::vector<int>&, int) = &SampleRenderer::updateAccel;\n"
            "void (SampleRenderer::*anim)(int, float, int) = &SampleRenderer::updateAnimated;\n"
            "int main() { return 0; }\n" % (abi.UPDATE_REBUILD_ASYNC, C.sizeof(abi.RebuildInfo)))
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", INCLUDE, "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
 
 
 def test_library_exports_rebuild_state_and_links_threads():

@@ -4,8 +4,6 @@ flight and with two chains per frame); the adopted tree is a conservative tree o
 measured; the counters and the paths that end a build early; rejections; the temporal chain and the late warp across an
 adoption; and the C++ drop-in.  FOVPT_ASYNC_BUILD_DELAY_MS holds the state at BUILDING where a test needs it there."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,14 +14,13 @@ import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
+from gpu_common import bits, build_dropin, dropin_renderer, run_dropin
 from temporal_common import tcfg
 from test_refit_gpu import hierarchy, jitter, moved, render
 from test_rig_gpu import SHORT, TALL, morph_fixture
 from test_transform_gpu import close, dbits, expected_cost, scene_vertices
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 IDLE, BUILDING, READY = abi.REBUILD_IDLE, abi.REBUILD_BUILDING, abi.REBUILD_READY
 CORNELL = scenes.CORNELL_CAMERA
@@ -483,17 +480,11 @@ def test_temporal_step_and_late_warp_across_an_adoption(monkeypatch):
 def test_cpp_dropin_rebuild_async(tmp_path):
     """SampleRenderer::updateAccel(..., REBUILD_ASYNC) / rebuildState of include/SimplePathtracer.h: request, wait, adopt and
     render; the four frames are the same pixels as Python's."""
-    exe, out = str(tmp_path / "rebuild_async_gpu_test"), str(tmp_path / "rebuild_async_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "rebuild_async_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "rebuild_async_gpu_test"), str(tmp_path / "rebuild_async_out.bin")
+    run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(4, 96, 160)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    model = box_model()
-    r = make_gpu(model, scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r = dropin_renderer()
+    model = r.model
     want = [render(r)[1]]
     v1 = (model.meshes[1].vertex + F([0.5, 0.0, -0.25])).astype(F)
     r.update_vertices({1: v1}, rebuild="async")

@@ -2,8 +2,6 @@
 restatement of the shading kernel's normal / albedo, the reconstruction bit for bit against tests/reconstruct_ref.py applied to
 the GPU's own G-buffer and guides, inputs and later frames left untouched, error codes, ordering with frames in flight, the gain
 in accuracy over the block-filled frame, and the C++ drop-in."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,11 +10,10 @@ import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits as _bits, box_model as _box_model, check_reconstruct as _check_bits, \
-    expected_gbuffer as _expected_gbuffer, rcfg as _rcfg
+from gpu_common import BOX_CAMERA, bits as _bits, box_model as _box_model, build_dropin, dropin_renderer, run_dropin
+from postprocess_common import check_reconstruct as _check_bits, expected_gbuffer as _expected_gbuffer, rcfg as _rcfg
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 # periphery RMSE against a 256-spp render, 384 x 216 atrium, radii 30 / 90, defaults (tools/reconstruct_perf.py --sweep,
 # DESIGN.md 11): block-filled / reconstructed measured 2.12 on an MI355X, denoised / denoised + reconstructed 1.33; the tests
@@ -283,17 +280,10 @@ def test_reconstruct_reduces_the_periphery_error():
 
 def test_cpp_dropin_reconstruct(tmp_path):
     """SampleRenderer::reconstruct() + downloadReconstructedPixels of include/SimplePathtracer.h: the same pixels as Python."""
-    exe, out = str(tmp_path / "reconstruct_gpu_test"), str(tmp_path / "reconstruct_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "reconstruct_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "reconstruct_gpu_test"), str(tmp_path / "reconstruct_out.bin")
+    run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(2, 96, 160)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(_box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r = dropin_renderer(write_guides=True)
     r.render()
     r.reconstruct()
     assert np.array_equal(px[0], r.downloadPixels())

@@ -3,8 +3,6 @@ and G-buffers after motion against the CPU oracle and against a fresh build of t
 flight and post-processing, device pointers, spatial splits and tiny scenes, rejections and the C++ drop-in."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,11 +11,10 @@ import refit_ref as rf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu, make_oracle
-from postprocess_common import bits
+from gpu_common import bits, build_dropin, run_dropin
 from temporal_common import Checker
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE = -1, -3
 NTHREADS = 16
 CORNELL, ATRIUM = scenes.CORNELL_CAMERA, scenes.ATRIUM_CAMERA
@@ -458,13 +455,8 @@ def test_rejections_change_nothing():
 # ---- 12. C++ ------------------------------------------------------------------------------------------------------------------
 def test_cpp_update_accel(tmp_path):
     """SampleRenderer::updateAccel of include/SimplePathtracer.h over the mutated Model: the pixels of a fresh renderer."""
-    exe, out = str(tmp_path / "refit_gpu_test"), str(tmp_path / "refit_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "refit_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "refit_gpu_test"), str(tmp_path / "refit_out.bin")
+    run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(4, 96, 160)
     assert np.array_equal(px[0], px[1]) and np.array_equal(px[2], px[3])     # refit / rebuild == fresh renderer
     assert not np.array_equal(px[0], px[2])

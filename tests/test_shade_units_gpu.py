@@ -16,7 +16,7 @@ import pytest
 import shade_cases as sc
 from common import cfg_uniform, make_gpu
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
-from temporal_motion_common import debug_buffer
+from gpu_common import debug_buffer
 
 pytestmark = pytest.mark.gpu
 

@@ -5,7 +5,6 @@ life cycle of a skin, rejections, a seeded sweep, and the C++ drop-in.  FOVPT_FU
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,13 +15,12 @@ import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import bits
+from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin
 from temporal_common import tcfg
-from temporal_motion_common import debug_buffer, vertex_arrays as motion_arrays
+from temporal_motion_common import vertex_arrays as motion_arrays
 from test_refit_gpu import assert_frame_is_oracle, hierarchy, jitter, moved, oracle_frame, render
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE = -1, -3
 CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
@@ -600,13 +598,8 @@ def test_seeded_skins_and_poses(sweep_scene, seed):
 def test_cpp_set_skins_and_update_skinned(tmp_path):
     """SampleRenderer::setSkins / updateSkinned of include/SimplePathtracer.h: the hashes of the frame and of the vertex bytes
     the program prints are those of the same skin and pose through the python wrapper."""
-    exe = str(tmp_path / "skin_gpu_test")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "skin_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe = build_dropin(tmp_path, "skin_gpu_test")
+    res = run_dropin(exe)
     got = re.search(r"frame ([0-9a-f]{16}) vertices ([0-9a-f]{16})", res.stdout)
     assert got and res.stdout.rstrip().endswith("ok"), res.stdout
 
@@ -616,13 +609,8 @@ def test_cpp_set_skins_and_update_skinned(tmp_path):
             h = ((h ^ x) * 1099511628211) & 0xffffffffffffffff
         return "%016x" % h
 
-    grey, red = abi.Material.reference_default(), abi.Material.reference_default()
-    grey.color.set((0.7, 0.7, 0.7)); grey.emission.set((0, 0, 0))
-    red.color.set((0.8, 0.1, 0.1)); red.emission.set((0, 0, 0))
-    model = scenes.Model([scenes.box_mesh((0, -1.0, 0), (6, 0.5, 6), grey), scenes.box_mesh((0, 0.5, 0), (1, 2, 0.5), red)])
-    cam = dict(eye=(4.0, 3.0, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fovy=45.0)
-    size = (160, 96)
-    r = make_gpu(model, scenes.ambient_probe(160, 96, 2.5), cam, size, cfg_foveated(12, 36, (1, 2, 8)))
+    r = dropin_renderer(red_half=(1, 2, 0.5))
+    model = r.model
     v = model.meshes[1].vertex
     up = v[:, 1] > 0.5
     j, w = np.zeros((len(v), 4), np.uint16), np.zeros((len(v), 4), F)

@@ -11,7 +11,7 @@ import pytest
 from fovpathtracing_optixcodelatest_amd import abi, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, box_model
+from gpu_common import BOX_CAMERA, box_model
 from temporal_common import Checker
 from test_postprocess_fuzz_gpu import SOUP_CAMERA, _soup
 

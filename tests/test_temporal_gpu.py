@@ -2,8 +2,6 @@
 the reset paths, disocclusion judged by the production traversal, inputs and later frames left untouched, ordering with frames
 in flight, error codes, the gain in accuracy over single frames, the full C3 size and the C++ drop-in."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,11 +10,10 @@ import reconstruct_ref as rr
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
-from temporal_common import Checker, camera, quality_run, tcfg
+from gpu_common import BOX_CAMERA, bits, box_model, build_dropin, camera, dropin_renderer, run_dropin
+from temporal_common import Checker, quality_run, tcfg
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 # periphery RMSE against a 256-spp render over the last frame of a 12-frame camera path, 384 x 216 atrium, radii 30 / 90,
 # spp (1, 2, 8), render -> reconstruct -> temporal with the defaults vs render -> reconstruct (tools/temporal_perf.py --sweep,
@@ -378,17 +375,10 @@ def test_temporal_matches_the_restatement_c3(oracle):
 
 def test_cpp_dropin_temporal(tmp_path):
     """SampleRenderer::temporal() + downloadTemporalPixels of include/SimplePathtracer.h: the same pixels as Python."""
-    exe, out = str(tmp_path / "temporal_gpu_test"), str(tmp_path / "temporal_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "temporal_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "temporal_gpu_test"), str(tmp_path / "temporal_out.bin")
+    run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(3, 96, 160)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, (160, 96), cfg)
+    r = dropin_renderer(write_guides=True)
     r.render()
     r.temporal()
     assert np.array_equal(px[0], r.downloadTemporalPixels())

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import header_layout
 import temporal_motion_ref as tm
 import temporal_ref as tr
 from fovpathtracing_optixcodelatest_amd import abi, lib
@@ -46,7 +47,7 @@ def test_the_prototype_agrees_everywhere(so):
 def test_the_dropin_header_compiles(tmp_path):
     src = '#include "SimplePathtracer.h"\nvoid f(SampleRenderer& s, fovpt_float4* m, float4* h) { s.temporalMotion(); s.temporalMotion(nullptr, m); ' \
           'fovpt_temporal_config tc; fovpt_temporal_defaults(&tc); s.temporalMotion(tc, nullptr, m); s.downloadMotion(m, h); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
 
 
 def test_temporal_motion_rejects_a_null_context(so):

@@ -4,8 +4,6 @@ moved model, absolute semantics, rebuild, ordering with frames in flight, fovpt_
 cost: against refit_ref.sah_cost of the downloaded nodes within transform_ref.cost_tolerance, the counters, the two calling
 modes.  And the C++ drop-in."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,13 +14,12 @@ import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import bits
+from gpu_common import bits, build_dropin, debug_buffer, run_dropin
 from temporal_common import tcfg
-from temporal_motion_common import debug_buffer, vertex_arrays as motion_arrays
+from temporal_motion_common import vertex_arrays as motion_arrays
 from test_refit_gpu import assert_frame_is_oracle, hierarchy, jitter, moved, render
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE = -1, -3
 CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
@@ -428,13 +425,8 @@ def test_hierarchy_cost_before_watching_and_with_every_slot_in_flight():
 def test_cpp_update_transforms(tmp_path):
     """SampleRenderer::updateTransforms / hierarchyCost of include/SimplePathtracer.h: the pixels of a fresh renderer over the
     moved Model after a refit and after a rebuild."""
-    exe, out = str(tmp_path / "transform_gpu_test"), str(tmp_path / "transform_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "transform_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "transform_gpu_test"), str(tmp_path / "transform_out.bin")
+    run_dropin(exe, out)
     px = np.fromfile(out, np.uint32).reshape(4, 96, 160)
     assert np.array_equal(px[0], px[1]) and np.array_equal(px[2], px[3])     # refit / rebuild == fresh renderer
     assert not np.array_equal(px[0], px[2])

@@ -16,9 +16,8 @@ import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import scenes
 
 from common import cfg_foveated, make_gpu
-from postprocess_common import bits
+from gpu_common import bits, debug_buffer
 from temporal_common import tcfg
-from temporal_motion_common import debug_buffer
 
 pytestmark = pytest.mark.gpu
 F = np.float32

@@ -129,7 +129,7 @@ def test_the_dropin_header_compiles():
           's.variance(); s.variance(vc, nullptr, a, a, a); s.varianceReset(); fovpt_float4* v; const fovpt_float4* m; s.varianceBuffers(&v, &m); ' \
           'fovpt_variance_filter_config fc = s.varianceFilterDefaults(); s.varianceFilter(); s.varianceFilter(fc, nullptr, a, a, a, p); ' \
           'fovpt_float4* c; uint32_t* q; s.varianceFilterBuffers(&c, &q); s.downloadVarianceFiltered(p); s.downloadVariance(a); s.variancePost(vc, fc, a); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
 
 
 # ---- the moment step ----------------------------------------------------------------------------------------------------------------

@@ -6,23 +6,20 @@ caller's; at frame sizes from 1 x 1 up, foveated and uniform.  Then the lifecycl
 and the C++ drop-in.  The frame is a trivial render of the box scene; colour, variance and motion are synthetic where the case
 needs them.  The conditions that keep a case from being vacuous are asserted on the restatement's output."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import variance_ref as vr
-from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
 
-from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
+from common import cfg_foveated, cfg_uniform
+from gpu_common import (BOX_CAMERA, bits, box_renderer, build_dropin, camera, device_images, dropin_renderer, host_view,
+                        run_dropin, upload, with_entries)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 SIZES = [(1, 1), (2, 1), (1, 3), (5, 4), (33, 17), (193, 109)]
-PROBE = scenes.ambient_probe(64, 32, 2.5)
 FOVEATED = ("foveated", lambda: cfg_foveated(10, 30, (1, 1, 2), max_depth=2))     # fovea 22 px, middle ring 64 px: all three fills at 193 x 109
 UNIFORM = ("uniform", lambda: cfg_uniform(1, max_depth=2))
 MOMENT_CONFIGS = (dict(), dict(history_cap=2, spatial_below=2, spatial_radius=1, depth_tolerance=0.1),
@@ -30,54 +27,17 @@ MOMENT_CONFIGS = (dict(), dict(history_cap=2, spatial_below=2, spatial_radius=1,
 ITERATION_MIXES = ((0, 2, 4, 4), (1, 3, 5, 5), (5, 0, 1, 2), (2, 2, 0, 1), (0, 0, 0, 0), (3, 1, 2, 3))       # fovea, middle, periphery, uniform
 
 
-def _box(size, cfg=None):
-    return make_gpu(box_model(), PROBE, BOX_CAMERA, size, cfg if cfg is not None else UNIFORM[1]())
-
-
 def vcfg(**d):
-    c = renderer.SampleRenderer.variance_defaults()
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
+    return with_entries(renderer.SampleRenderer.variance_defaults(), d)
 
 
 def fcfg(**d):
-    c = renderer.SampleRenderer.variance_filter_defaults()
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
-
-
-def camera_of(r):
-    cam = r.launchParams.camera
-    vec = lambda v: (float(v.x), float(v.y), float(v.z))
-    return dict(eye=vec(cam.eye), U=vec(cam.U), V=vec(cam.V), W=vec(cam.W))
+    return with_entries(renderer.SampleRenderer.variance_filter_defaults(), d)
 
 
 def frame_fills(r, cfg):
     f = r.launchParams.frame
     return vr.fills(f.size.x, f.size.y, (f.c.x, f.c.y), cfg.r_inner, cfg.r_outer, cfg.uniform)
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_frame(size, channels=4, fill=0x5a):
-    import torch
-    t = torch.full((size[1], size[0], 4 * channels), fill, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    return t
-
-
-def host(t, kind="color"):
-    a = t.cpu().numpy()
-    if kind == "color":
-        return a.view(np.float32).reshape(a.shape[0], a.shape[1], 4)
-    return a.view(np.uint32).reshape(a.shape[0], a.shape[1])
 
 
 def synthetic(size, seed, lo=0.0, hi=1.5):
@@ -121,7 +81,7 @@ class Moments:
         f = r.launchParams.frame
         size = (f.size.x, f.size.y)
         keep = [upload(a) if a is not None else None for a in (sample, motion if motion_ptr is None else None)]
-        out = self.out = None if own else device_frame(size)
+        out = self.out = None if own else device_images(size, 16)[0]
         if motion is not None and motion_ptr is None:
             motion_ptr = keep[1].data_ptr()
         r.variance(vcfg(**d), gbuffer, keep[0].data_ptr() if sample is not None else None, motion_ptr if motion is not None else None,
@@ -129,11 +89,11 @@ class Moments:
         r.synchronize()
         var_ptr, mom_ptr = r.variance_buffers()
         got_hist = r._download_frame(mom_ptr, 4)
-        got_var = host(out) if out is not None else r._download_frame(var_ptr, 4)
+        got_var = host_view(out, "color") if out is not None else r._download_frame(var_ptr, 4)
         gb = r.downloadGBuffer(gbuffer if gbuffer is not None else r.gbuffer())       # (the same camera: what the call traced)
         rec = {}
         full = dict(vr.MOMENT_DEFAULTS, **d)
-        hist, var = vr.moments(self.prev, sample if sample is not None else r.downloadAccum(), gb, cam if cam is not None else camera_of(r),
+        hist, var = vr.moments(self.prev, sample if sample is not None else r.downloadAccum(), gb, cam if cam is not None else camera(r),
                                self.fill if fill is None else fill, motion, full, rec)
         assert np.array_equal(bits(got_hist), bits(hist)), (label, "history", int((bits(got_hist) != bits(hist)).any(axis=-1).sum()))
         assert np.array_equal(bits(got_var), bits(var)), (label, "image", int((bits(got_var) != bits(var)).any(axis=-1).sum()))
@@ -146,7 +106,7 @@ class Moments:
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
 def test_moment_sequences_bit_for_bit(size, fov):
     cfg = fov[1]()
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     seen = dict(spatial=0, temporal=0, depth=0, cls=0, capped=0)
     for i, d in enumerate(MOMENT_CONFIGS):
         r.variance_reset()
@@ -175,9 +135,9 @@ def test_a_camera_slide_with_real_motion_vectors():
     """render -> fovpt_temporal_motion(out_motion) -> fovpt_temporal_gbuffer -> fovpt_variance(motion): the loop the stage is for."""
     size = SIZES[-1]
     cfg = FOVEATED[1]()
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     m = Moments(r, cfg)
-    mv_dev = device_frame(size)
+    mv_dev = device_images(size, 16)[0]
     e = np.array(BOX_CAMERA["eye"], np.float64)
     for k in range(4):
         eye = tuple(e + np.array([0.35 * k, 0.0, -0.1 * k]))
@@ -186,7 +146,7 @@ def test_a_camera_slide_with_real_motion_vectors():
         r.render()
         r.temporal_motion(None, None, None, None, mv_dev.data_ptr())
         r.synchronize()
-        motion = host(mv_dev).copy()
+        motion = host_view(mv_dev, "color").copy()
         hist, var, rec = m.step(dict(spatial_below=2), r.temporal_gbuffer(), None, motion, label=("slide", k))
         n = hist[..., 2]
         if k == 0:
@@ -215,10 +175,10 @@ def run_filter(oracle, r, cfg, d, color, variance, gbuffer, own, label, record=N
         got_c, got_p = r.downloadVarianceFiltered()
         ptrs, kept = r.variance_filter_buffers(), []
     else:
-        oc, op = device_frame(size), device_frame(size, 1)
+        oc, op = device_images(size, 16, 4)
         r.variance_filter(fcfg(**d), gbuffer, in_ptr, var_ptr, oc.data_ptr(), op.data_ptr())
         r.synchronize()
-        got_c, got_p = host(oc), host(op, "rgba")
+        got_c, got_p = host_view(oc, "color"), host_view(op, "rgba")
         ptrs, kept = (oc.data_ptr(), op.data_ptr()), [oc, op]
     if outs is not None:
         outs.update(color=ptrs[0], rgba=ptrs[1], keep=kept, got_rgba=got_p)
@@ -236,7 +196,7 @@ def run_filter(oracle, r, cfg, d, color, variance, gbuffer, own, label, record=N
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
 def test_filter_bit_for_bit(oracle, size, fov):
     cfg = fov[1]()
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     r.render()
     color = synthetic(size, size[0] + 1, 0.05, 1.5)
     variance = synthetic(size, size[0] + 2, 0.0, 0.6)
@@ -262,7 +222,7 @@ def test_the_stages_together_on_the_accum_buffer(oracle):
     """in_color None and variance None: the accum buffer filtered by the context's own image, as the last fovpt_variance left it."""
     size = (96, 64)
     cfg = FOVEATED[1]()
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
         r.variance()
     assert e.value.code == E_NO_FRAME
@@ -301,7 +261,7 @@ def _scene_again(r):
 def test_reset_resize_and_set_scene_start_a_new_history():
     small, large = (96, 64), (200, 120)
     cfg = UNIFORM[1]()
-    r = _box(small, cfg)
+    r = box_renderer(small, cfg)
     r.render()
     m = Moments(r, cfg)
     m.step({})
@@ -341,7 +301,7 @@ def test_the_other_stages_buffers_stay_as_they_are():
     size = (96, 64)
     cfg = FOVEATED[1]()
     cfg.write_guides = 1
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     r.render()
     r.denoise()
     r.temporal()
@@ -373,9 +333,9 @@ def test_the_stage_is_ordered_with_frames_in_flight():
     size = (384, 216)
     cfg = cfg_foveated(20, 60, (2, 4, 8))
     cfg.frames_in_flight = 2
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg)
     views = [((190, 108), 0), ((300, 40), 1), ((80, 60), 2)]
-    outs = [[(device_frame(size), device_frame(size), device_frame(size, 1)) for _ in views] for _ in range(2)]
+    outs = [[device_images(size, 16, 16, 4) for _ in views] for _ in range(2)]
     for sync, out in zip((True, False), outs):
         for g, k in views:                                   # the accum buffer's leftovers where no pass writes, as all views leave them
             r.launchParams.frame.c.x, r.launchParams.frame.c.y = g
@@ -394,9 +354,9 @@ def test_the_stage_is_ordered_with_frames_in_flight():
     for want, got in zip(*outs):
         for x, y in zip(want, got):
             assert torch.equal(x, y)
-    a, b = host(outs[0][0][2], "rgba"), host(outs[0][2][2], "rgba")
+    a, b = host_view(outs[0][0][2], "rgba"), host_view(outs[0][2][2], "rgba")
     assert (a != b).mean() > 0.1                             # (the frames differ: the comparison is not of copies)
-    n = host(outs[0][2][0])[..., 3]
+    n = host_view(outs[0][2][0], "color")[..., 3]
     assert (n == 3).any()                                    # (the third step has a history of three)
     r.close()
 
@@ -404,10 +364,10 @@ def test_the_stage_is_ordered_with_frames_in_flight():
 # ---- 4. rejections ---------------------------------------------------------------------------------------------------------------------
 def test_rejections_leave_everything_unchanged():
     size = (96, 64)
-    r = _box(size)
+    r = box_renderer(size, UNIFORM[1]())
     L = lib.load()
     r.render()
-    ov, oc, op = device_frame(size), device_frame(size), device_frame(size, 1)
+    ov, oc, op = device_images(size, 16, 16, 4)
     mv = upload(np.tile(np.float32([0.25, -0.25, 5.0, 1.0]), (size[1], size[0], 1)))
     g = r.gbuffer()
     r.variance(None, g, None, mv.data_ptr(), ov.data_ptr())
@@ -561,21 +521,16 @@ def test_rejections_leave_everything_unchanged():
 def test_cpp_dropin_variance(oracle, tmp_path):
     """SampleRenderer::variance() / varianceFilter() / downloadVarianceFiltered() of include/SimplePathtracer.h: the same pixels as
     Python."""
-    exe, out = str(tmp_path / "variance_gpu_test"), str(tmp_path / "variance_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "variance_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "variance_gpu_test"), str(tmp_path / "variance_out.bin")
+    run_dropin(exe, out)
     size = (160, 96)
     n = size[0] * size[1]
     raw = np.fromfile(out, np.uint8)
     px = raw[:8 * n].view(np.uint32).reshape(2, size[1], size[0])
     col = raw[8 * n:40 * n].view(np.float32).reshape(2, size[1], size[0], 4)
     var = raw[40 * n:56 * n].view(np.float32).reshape(size[1], size[0], 4)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg)
+    r = dropin_renderer()
+    cfg = r.config
     m = Moments(r, cfg)
     for k in range(2):
         r.launchParams.frame.subframe_index = k

@@ -315,7 +315,7 @@ def test_the_static_asserts_compile():
           'static_assert(sizeof(fovpt_warp_config) == 32, "config");\nstatic_assert(sizeof(struct fovpt_warp_counts) == 32, "counts");\n' \
           'static_assert(offsetof(fovpt_launch_params, traversable) - offsetof(fovpt_launch_params, camera) >= sizeof(fovpt_warp_camera), "layout");\n' \
           'int f(fovpt_ctx* c) { struct fovpt_warp_counts n; return fovpt_warp_counts(c, &n); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
     hdr = open(os.path.join(ROOT, "include", "fovpt.h")).read()
     for name in ("fovpt_warp_camera", "fovpt_warp_config", "struct fovpt_warp_counts"):
         assert re.search(r"static_assert\(sizeof\(%s\) == " % re.escape(name), hdr), name
@@ -326,4 +326,4 @@ def test_the_dropin_header_compiles():
           'fovpt_warp_config wc; fovpt_warp_defaults(&wc); wc.images = FOVPT_WARP_RGBA; wc.fill_radius = FOVPT_WARP_MAX_RADIUS; ' \
           's.warp(to, wc); s.warp(to, true); s.warp(to, wc, true, m, h); struct fovpt_warp_counts n = s.warpCounts(); (void)n.splatted; ' \
           's.warpExposed(to); s.warpExposed(to, true); s.downloadWarpedPixels(h); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)

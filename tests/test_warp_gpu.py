@@ -4,8 +4,6 @@ flight, the geometry against the production traversal at the new camera, every r
 The restatement is fed the GPU's own G-buffer and inputs; the conditions that keep a case from being vacuous are asserted on the
 restatement's output."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,12 +12,10 @@ import warp_ref as wr
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
-from temporal_common import camera
-from temporal_motion_common import debug_buffer
+from gpu_common import (BOX_CAMERA, bits, box_renderer, build_dropin, camera, debug_buffer, device_images, dropin_renderer,
+                        host_view, run_dropin, upload, with_entries)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 SIZE = (193, 109)                                   # odd, and no multiple of the kernels' 64 x 4 tile: partial edge tiles
 PROBE = scenes.ambient_probe(64, 32, 2.5)
@@ -32,12 +28,6 @@ MOTIONS = dict(identity=((4.0, 3.0, 6.0), (0.0, 0.5, 0.0)),
                behind=((1.0, 1.0, 1.5), (0.0, 0.5, 0.0)))     # inside the scene: the slab at the frame's bottom is behind this camera
 
 
-def _box(size=SIZE, cfg=None, gaze=None):
-    cfg = cfg if cfg is not None else cfg_foveated(12, 36, (1, 1, 2))
-    cfg.write_guides = 1
-    return make_gpu(box_model(), PROBE, BOX_CAMERA, size, cfg, gaze=gaze)
-
-
 def to_camera(motion, size=SIZE, base=BOX_CAMERA):
     """-> (abi.WarpCamera, the dict the restatement takes) of MOTIONS[motion] (or an (eye, lookat) pair)."""
     eye, lookat = MOTIONS[motion] if isinstance(motion, str) else motion
@@ -47,31 +37,7 @@ def to_camera(motion, size=SIZE, base=BOX_CAMERA):
 
 
 def wcfg(**d):
-    c = renderer.SampleRenderer.warp_defaults()
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
-
-
-def upload(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def device_outputs(size, fill=0x5a):
-    """(colour, rgba, map) device tensors of a frame, every byte `fill`."""
-    import torch
-    w, h = size
-    t = [torch.full((h, w, 4 * k), fill, dtype=torch.uint8, device="cuda") for k in (4, 1, 1)]
-    torch.cuda.synchronize()
-    return t
-
-
-def host(t, channels):
-    a = t.cpu().numpy()
-    return a.view(np.float32).reshape(a.shape[0], a.shape[1], 4) if channels == 4 else a.view(np.uint32).reshape(a.shape[0], a.shape[1])
+    return with_entries(renderer.SampleRenderer.warp_defaults(), d)
 
 
 def counts_of(r):
@@ -84,18 +50,18 @@ def check(r, to, want_cam, gb, color, rgba, radius, images, in_ptrs=(None, None)
     counts; an image that is not enabled keeps its bytes.  -> the restatement's output."""
     f = r.launchParams.frame
     size = (f.size.x, f.size.y)
-    oc, op, om = device_outputs(size)
+    oc, op, om = device_images(size, 16, 4, 4)
     r.warp(to, wcfg(images=images, fill_radius=radius), gbuffer, in_ptrs[0], in_ptrs[1], oc.data_ptr(), op.data_ptr(), om.data_ptr())
     got_counts = counts_of(r)
     want = wr.warp(gb, camera(r), want_cam, dict(images=images, fill_radius=radius), color, rgba)
-    assert np.array_equal(host(om, 1), want["map"]), label
+    assert np.array_equal(host_view(om, "map"), want["map"]), label
     assert got_counts == want["counts"] and sum(got_counts[1:]) == size[0] * size[1], (label, got_counts, want["counts"])
     if images & wr.COLOR:
-        assert np.array_equal(bits(host(oc, 4)), bits(want["color"])), label
+        assert np.array_equal(bits(host_view(oc, "color")), bits(want["color"])), label
     else:
         assert (oc.cpu().numpy() == 0x5a).all(), label
     if images & wr.RGBA:
-        assert np.array_equal(host(op, 1), want["rgba"]), label
+        assert np.array_equal(host_view(op, "rgba"), want["rgba"]), label
     else:
         assert (op.cpu().numpy() == 0x5a).all(), label
     return want
@@ -120,7 +86,7 @@ def non_vacuous(want, motion, n):
 @pytest.fixture(scope="module")
 def rendered_box():
     """One rendered box frame, its G-buffer and images, shared by the motions (none of them changes it)."""
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     r.render()
     gb = r.downloadGBuffer()
     state = dict(r=r, gb=gb, color=r.downloadAccum(), rgba=r.downloadPixels())
@@ -168,7 +134,7 @@ def test_some_winner_is_not_its_pixels_lowest_index_candidate(rendered_box):
 
 def test_fov_off_160x90():
     size = (160, 90)
-    r = _box(size, cfg_uniform(2))
+    r = box_renderer(size, cfg_uniform(2), write_guides=True)
     r.render()
     gb, color, rgba = r.downloadGBuffer(), r.downloadAccum(), r.downloadPixels()
     for motion, radius in (("slide", 2), ("dolly_in", 4)):
@@ -198,7 +164,7 @@ def test_the_atrium():
 def test_the_temporal_steps_gbuffer_saves_the_trace():
     """render -> post -> temporal_gbuffer -> warp(gbuffer=that) is warp(gbuffer=None) bit for bit; the buffers fovpt_gbuffer handed
     out keep their contents, and the inputs, the temporal history and a later frame are those of a context that never warped."""
-    a, b = (_box() for _ in range(2))
+    a, b = (box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True) for _ in range(2))
     to, want_cam = to_camera("slide")
     for r in (a, b):
         with pytest.raises(lib.FovptError) as e:             # no temporal step yet
@@ -216,9 +182,9 @@ def test_the_temporal_steps_gbuffer_saves_the_trace():
     b.setCamera(renderer.Camera(BOX_CAMERA["eye"], BOX_CAMERA["lookat"], BOX_CAMERA["up"], BOX_CAMERA["fovy"], SIZE[0] / float(SIZE[1])))
     assert other.prim != g.prim and other.position != g.position
     before = b.downloadGBuffer(other)
-    oc, op, om = device_outputs(SIZE)
+    oc, op, om = device_images(SIZE, 16, 4, 4)
     b.warp(to, None, g, None, None, oc.data_ptr(), op.data_ptr(), om.data_ptr())
-    assert np.array_equal(bits(host(oc, 4)), bits(own[0])) and np.array_equal(host(op, 1), own[1]) and counts_of(b) == own[2]
+    assert np.array_equal(bits(host_view(oc, "color")), bits(own[0])) and np.array_equal(host_view(op, "rgba"), own[1]) and counts_of(b) == own[2]
     after = b.downloadGBuffer(other)
     for k in before:
         assert np.array_equal(bits(before[k]), bits(after[k])), k
@@ -226,7 +192,7 @@ def test_the_temporal_steps_gbuffer_saves_the_trace():
     # against the restatement on the step's set
     gb = b.downloadGBuffer(g)
     want = wr.warp(gb, camera(b), want_cam, None, b.downloadAccum(), b.downloadPixels())
-    assert np.array_equal(host(om, 1), want["map"]) and np.array_equal(bits(own[0]), bits(want["color"]))
+    assert np.array_equal(host_view(om, "map"), want["map"]) and np.array_equal(bits(own[0]), bits(want["color"]))
     # the context that warped goes on like the one that did not
     for x, y in zip((a.downloadAccum(), a.downloadPixels(), a.downloadPostColor(), a.downloadTemporalHistory()),
                     (b.downloadAccum(), b.downloadPixels(), b.downloadPostColor(), b.downloadTemporalHistory())):
@@ -258,10 +224,10 @@ def test_warp_is_ordered_with_frames_in_flight():
     size = (384, 216)
     cfg = cfg_foveated(20, 60, (4, 8, 16))
     cfg.frames_in_flight = 2
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg, write_guides=True)
     to, _ = to_camera("slide", size)
     views = [((120, 90), 0), ((300, 40), 1), ((30, 200), 2)]
-    outs = [[device_outputs(size) for _ in views] for _ in range(2)]
+    outs = [[device_images(size, 16, 4, 4) for _ in views] for _ in range(2)]
     counts = [[], []]
     for sync, out, cnt in zip((True, False), outs, counts):
         for g, k in views:                                   # the accum buffer's leftovers where no pass writes, as all views leave them
@@ -285,7 +251,7 @@ def test_warp_is_ordered_with_frames_in_flight():
         for x, y in zip(want, got):
             assert torch.equal(x, y)
     assert counts[1][0] == counts[0][-1]
-    a, b = host(outs[0][0][1], 1), host(outs[0][2][1], 1)
+    a, b = host_view(outs[0][0][1], "rgba"), host_view(outs[0][2][1], "rgba")
     assert (a != b).mean() > 0.1                             # (the frames differ: the comparison is not of copies)
     r.close()
 
@@ -295,12 +261,12 @@ def test_warp_is_ordered_with_frames_in_flight():
 def test_warped_pixels_show_what_the_new_camera_sees(motion):
     """Independent of the restatement: over the direct pixels whose source is a hit, the source's primitive is the one fovpt_gbuffer
     traces at the `to` camera more often than the unwarped frame's primitive at the same pixel is."""
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     r.render()
     to, _ = to_camera(motion)
-    om = device_outputs(SIZE)[2]
+    om = device_images(SIZE, 16, 4, 4)[2]
     r.warp(to, wcfg(images=abi.WARP_RGBA), None, None, None, None, None, om.data_ptr())
-    m = host(om, 1).reshape(-1)
+    m = host_view(om, "map").reshape(-1)
     rendered = r.downloadGBuffer()["prim"].reshape(-1)      # (traced at the rendered camera)
     r.setCamera(renderer.Camera(*MOTIONS[motion], BOX_CAMERA["up"], BOX_CAMERA["fovy"], SIZE[0] / float(SIZE[1])))
     target = r.downloadGBuffer()["prim"].reshape(-1)        # the production traversal at the `to` camera
@@ -316,14 +282,14 @@ def test_warped_pixels_show_what_the_new_camera_sees(motion):
 # ---- 4. rejections -------------------------------------------------------------------------------------------------------------------
 def test_rejections_leave_everything_unchanged():
     import torch
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     to, _ = to_camera("slide")
     L = lib.load()
     with pytest.raises(lib.FovptError) as e:                 # nothing rendered yet
         r.warp(to)
     assert e.value.code == E_NO_FRAME and counts_of(r) == (0, 0, 0, 0)
     r.render()
-    oc, op, om = device_outputs(SIZE)
+    oc, op, om = device_images(SIZE, 16, 4, 4)
     r.warp(to, None, None, None, None, oc.data_ptr(), op.data_ptr(), om.data_ptr())
     r.warp(to)
     g = r.gbuffer()
@@ -434,7 +400,7 @@ def test_rejections_leave_everything_unchanged():
 # ---- 5. reallocation -----------------------------------------------------------------------------------------------------------------
 def test_resize_reallocates_the_warps_buffers():
     small, large = (96, 64), (200, 120)
-    r = _box(small)
+    r = box_renderer(small, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     with pytest.raises(lib.FovptError) as e:
         r.warp_buffers()
     assert e.value.code == E_NO_FRAME
@@ -462,21 +428,14 @@ def test_resize_reallocates_the_warps_buffers():
 # ---- 6. the C++ drop-in --------------------------------------------------------------------------------------------------------------
 def test_cpp_dropin_warp(tmp_path):
     """SampleRenderer::warp() / warpExposed() / warpCounts() of include/SimplePathtracer.h: the same pixels and counts as Python."""
-    exe, out = str(tmp_path / "warp_gpu_test"), str(tmp_path / "warp_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "warp_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "warp_gpu_test"), str(tmp_path / "warp_out.bin")
+    run_dropin(exe, out)
     size = (160, 96)
     n = size[0] * size[1]
     raw = np.fromfile(out, np.uint32)
     px = raw[:3 * n].reshape(3, size[1], size[0])
     counts = raw[3 * n:].view(np.uint64).reshape(3, 4)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg)
+    r = dropin_renderer(write_guides=True)
     to, _ = to_camera(((3.5, 3.0, 6.5), (0.0, 0.5, 0.0)), size)
     r.render()
     r.post()

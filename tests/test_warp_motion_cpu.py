@@ -193,7 +193,7 @@ def test_the_struct_mirror_matches_the_header():
 def test_the_static_assert_compiles():
     src = '#include <cstddef>\n#include "fovpt.h"\nstatic_assert(sizeof(fovpt_warp_motion_config) == 32, "config");\n' \
           'static_assert(sizeof(fovpt_warp_motion_config) == sizeof(fovpt_warp_config), "the two configs");\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)
     hdr = open(os.path.join(ROOT, "include", "fovpt.h")).read()
     assert re.search(r"static_assert\(sizeof\(fovpt_warp_motion_config\) == 32", hdr)
 
@@ -204,4 +204,4 @@ def test_the_dropin_header_compiles():
           's.warpMotion(to, mc); s.warpMotion(to, 0.5f, true); s.warpMotion(to, mc, true, m, h); s.warpMotion(to, 2.0f, false, m, h); ' \
           's.warpMotionExposed(to, 1.0f); s.warpMotionExposed(to, 1.5f, true); struct fovpt_warp_counts n = s.warpCounts(); (void)n.filled; ' \
           's.downloadWarpedPixels(h); s.warp(to); s.lens(&to); }\n'
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-"], input=src.encode(), check=True)
+    header_layout.syntax_check(src)

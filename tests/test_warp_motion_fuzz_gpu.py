@@ -15,7 +15,7 @@ import warp_ref as wr
 from fovpathtracing_optixcodelatest_amd import lib, renderer, scenes
 
 from common import cfg_foveated, cfg_uniform, make_gpu
-from postprocess_common import BOX_CAMERA, box_model
+from gpu_common import BOX_CAMERA, box_model
 from temporal_motion_common import KINDS
 from test_warp_gpu import to_camera
 from warp_motion_common import STEPS, Intervals, check, frame_data, mcfg

@@ -4,8 +4,6 @@ the caller's G-buffer and the host's check of the hit records that go with it; t
 the next update; ordering with frames in flight; every rejection; the C++ drop-in.  The restatement is fed the GPU's own G-buffer,
 hit records and inputs; the conditions that keep a case from being vacuous are asserted on the restatement's output."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,18 +11,16 @@ import pytest
 import transform_ref as tf
 import warp_motion_ref as wm
 import warp_ref as wr
-from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
+from fovpathtracing_optixcodelatest_amd import abi, lib, renderer
 
-from common import cfg_foveated, make_gpu
-from postprocess_common import BOX_CAMERA, bits, box_model
-from temporal_common import camera
-from temporal_motion_common import debug_buffer
+from common import cfg_foveated
+from gpu_common import (BOX_CAMERA, bits, box_renderer, build_dropin, camera, debug_buffer, device_images, dropin_renderer,
+                        host_view, run_dropin)
 from test_temporal_gpu import _scene_again
-from test_warp_gpu import MOTIONS, SIZE, _box, counts_of, device_outputs, host, to_camera, wcfg
+from test_warp_gpu import MOTIONS, SIZE, counts_of, to_camera, wcfg
 from warp_motion_common import Intervals, check, frame_data, mcfg
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_NO_SCENE, E_NO_FRAME = -1, -3, -5
 BOX = 1                                                  # box_model(): mesh 0 is the slab, mesh 1 the red box
 N = SIZE[0] * SIZE[1]
@@ -58,7 +54,7 @@ def warp_both(r, to, cfg_m, gbuffer=None):
     """fovpt_warp and fovpt_warp_motion of the same arguments -> two (colour, rgba, map, counts)."""
     out = []
     for motion in (False, True):
-        oc, op, om = device_outputs(SIZE)
+        oc, op, om = device_images(SIZE, 16, 4, 4)
         if motion:
             r.warp_motion(to, cfg_m, gbuffer, None, None, oc.data_ptr(), op.data_ptr(), om.data_ptr())
         else:
@@ -73,7 +69,7 @@ def moved_box(request):
     """render -> temporal_motion, the box carried through update_transforms, render -> temporal_motion, the box turned through
     update_vertices (a refit, or FOVPT_UPDATE_REBUILD: the record order changes, the primitive ids do not), render ->
     temporal_motion: the frame the warps below re-aim, with the GPU's own G-buffer, hit records and images."""
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     ck = Intervals(r)
     next_frame(r, 0)
     ck.end_interval()
@@ -129,7 +125,7 @@ def test_the_renderers_own_buffers_serve_both_warps(moved_box):
 # ---- 2. it is fovpt_warp where it must be --------------------------------------------------------------------------------------------
 def test_it_is_fovpt_warp_where_it_must_be():
     to, _ = to_camera("slide")
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     ck = Intervals(r)
     # (d) the first frame: update -> render -> the first temporal_motion.  Tracking starts there: the step had no history
     ck.update({BOX: shift((0.5, 0.0, 0.0))}, kind="transforms")
@@ -173,7 +169,7 @@ def test_it_is_fovpt_warp_where_it_must_be():
 
 # ---- 3. the caller's G-buffer --------------------------------------------------------------------------------------------------------
 def test_the_callers_gbuffer_and_the_hit_records_that_go_with_it():
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     ck = Intervals(r)
     to, want_cam = to_camera("turn")
     for k, t in enumerate(((0.0, 0.0, 0.0), (0.5, 0.0, 0.25))):
@@ -184,9 +180,9 @@ def test_the_callers_gbuffer_and_the_hit_records_that_go_with_it():
     cfg = mcfg(advance=1.5)
 
     def run(gbuffer):
-        oc, op, om = device_outputs(SIZE)
+        oc, op, om = device_images(SIZE, 16, 4, 4)
         r.warp_motion(to, cfg, gbuffer, None, None, oc.data_ptr(), op.data_ptr(), om.data_ptr())
-        return host(oc, 4).tobytes(), host(op, 1).tobytes(), host(om, 1), counts_of(r)
+        return host_view(oc, "color").tobytes(), host_view(op, "rgba").tobytes(), host_view(om, "map"), counts_of(r)
 
     def refused(gbuffer, label):
         with pytest.raises(lib.FovptError) as e:
@@ -231,7 +227,7 @@ def test_extrapolated_pixels_show_where_the_box_will_be():
     """The box moves by exactly (0.5, 0, 0) per step.  After fovpt_warp_motion(advance 1) and fovpt_warp to the same camera the
     next update is applied and fovpt_gbuffer traces the scene at that camera: over the direct pixels whose source is on the box,
     the source's primitive is the traced one more often for fovpt_warp_motion than for fovpt_warp."""
-    r = _box()
+    r = box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True)
     ck = Intervals(r)
     next_frame(r, 0)
     ck.end_interval()
@@ -241,12 +237,12 @@ def test_extrapolated_pixels_show_where_the_box_will_be():
     to, _ = to_camera("slide")
     maps = []
     for motion in (True, False):
-        om = device_outputs(SIZE)[2]
+        om = device_images(SIZE, 16, 4, 4)[2]
         if motion:
             r.warp_motion(to, mcfg(images=abi.WARP_RGBA, advance=1.0), None, None, None, None, None, om.data_ptr())
         else:
             r.warp(to, wcfg(images=abi.WARP_RGBA), None, None, None, None, None, om.data_ptr())
-        maps.append(host(om, 1).reshape(-1))
+        maps.append(host_view(om, "map").reshape(-1))
     gb = r.downloadGBuffer()
     rendered, box = gb["prim"].reshape(-1), on_box(ck, gb).reshape(-1)
     ck.update({BOX: shift((1.0, 0.0, 0.0))}, kind="transforms")      # the next update: where advance 1 says the box will be
@@ -271,11 +267,11 @@ def test_warp_motion_is_ordered_with_frames_in_flight():
     size = (384, 216)
     cfg = cfg_foveated(20, 60, (4, 8, 16))
     cfg.frames_in_flight = 2
-    r = _box(size, cfg)
+    r = box_renderer(size, cfg, write_guides=True)
     to, _ = to_camera("slide", size)
     views = [((120, 90), 0), ((300, 40), 1), ((30, 200), 2)]
     moves = [shift((0.4 * (k + 1), 0.0, -0.2 * (k + 1))) for k in range(3)]
-    outs = [[device_outputs(size) for _ in views] for _ in range(2)]
+    outs = [[device_images(size, 16, 4, 4) for _ in views] for _ in range(2)]
     counts = []
 
     def frame(g, k):
@@ -311,18 +307,18 @@ def test_warp_motion_is_ordered_with_frames_in_flight():
             assert torch.equal(x, y)
     assert counts[0] == counts[1]
     # the last frame's extrapolation is not fovpt_warp's: the comparison is of moved pixels
-    om = device_outputs(size)[2]
+    om = device_images(size, 16, 4, 4)[2]
     r.warp(to, None, None, None, None, None, None, om.data_ptr())
-    assert (host(om, 1) != host(outs[1][2][2], 1)).sum() > 100
+    assert (host_view(om, "map") != host_view(outs[1][2][2], "map")).sum() > 100
     r.close()
 
 
 # ---- 6. rejections -------------------------------------------------------------------------------------------------------------------
 def test_rejections_leave_everything_unchanged():
-    a, b = (_box() for _ in range(2))                        # a: the twin that is never refused
+    a, b = (box_renderer(SIZE, cfg_foveated(12, 36, (1, 1, 2)), write_guides=True) for _ in range(2))                        # a: the twin that is never refused
     to, _ = to_camera("slide")
     L = lib.load()
-    outs = device_outputs(SIZE)
+    outs = device_images(SIZE, 16, 4, 4)
     oc, op, om = outs
     ptrs = dict(out_color=oc.data_ptr(), out_rgba=op.data_ptr(), out_map=om.data_ptr())
 
@@ -457,21 +453,14 @@ def test_rejections_leave_everything_unchanged():
 # ---- 7. the C++ drop-in --------------------------------------------------------------------------------------------------------------
 def test_cpp_dropin_warp_motion(tmp_path):
     """SampleRenderer::warpMotion() / warpMotionExposed() of include/SimplePathtracer.h: the same pixels and counts as Python."""
-    exe, out = str(tmp_path / "warp_motion_gpu_test"), str(tmp_path / "warp_motion_out.bin")
-    csrc = os.path.join(ROOT, "fovpathtracing_optixcodelatest_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "warp_motion_gpu_test.cpp"), "-o", exe,
-                           "-L", csrc, "-lfovpt", "-Wl,-rpath," + csrc])
-    res = subprocess.run([exe, out], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
+    exe, out = build_dropin(tmp_path, "warp_motion_gpu_test"), str(tmp_path / "warp_motion_out.bin")
+    run_dropin(exe, out)
     size = (160, 96)
     n = size[0] * size[1]
     raw = np.fromfile(out, np.uint32)
     px = raw[:4 * n].reshape(4, size[1], size[0])
     counts = raw[4 * n:].view(np.uint64).reshape(4, 4)
-    cfg = cfg_foveated(12, 36, (1, 2, 8))
-    cfg.write_guides = 1
-    r = make_gpu(box_model(), scenes.ambient_probe(160, 96, 2.5), BOX_CAMERA, size, cfg)
+    r = dropin_renderer(write_guides=True)
     to, _ = to_camera(((3.5, 3.0, 6.5), (0.0, 0.5, 0.0)), size)
     r.render()
     r.post()

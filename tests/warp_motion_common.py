@@ -1,5 +1,5 @@
-"""Checks of fovpt_warp_motion on the GPU against tests/warp_motion_ref.py: used by test_warp_motion_gpu.py and
-test_warp_motion_fuzz_gpu.py.
+"""Checks of fovpt_warp_motion on the GPU against tests/warp_motion_ref.py (Intervals, mcfg, frame_data, check): used by
+test_warp_motion_gpu.py, test_warp_motion_fuzz_gpu.py and the application fuzz.  General helpers are in tests/gpu_common.py.
 
 Every expectation is computed from the GPU's own data -- the G-buffer and hit records fovpt_gbuffer builds at the rendered camera
 (it traces the same rays), the inputs -- and from the vertex arrays the test itself uploaded, in MotionChecker's bookkeeping."""
@@ -9,10 +9,9 @@ import warp_motion_ref as wm
 import warp_ref as wr
 from fovpathtracing_optixcodelatest_amd import renderer
 
-from postprocess_common import bits
-from temporal_common import camera
+from gpu_common import bits, camera, device_images, host_view, with_entries
 from temporal_motion_common import MotionChecker, download_hits
-from test_warp_gpu import counts_of, device_outputs, host
+from test_warp_gpu import counts_of
 
 STEPS = ("temporal", "temporal_motion", "post")
 
@@ -45,10 +44,7 @@ class Intervals(MotionChecker):
 
 
 def mcfg(**d):
-    c = renderer.SampleRenderer.warp_motion_defaults()
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
+    return with_entries(renderer.SampleRenderer.warp_motion_defaults(), d)
 
 
 def frame_data(r):
@@ -62,18 +58,18 @@ def check(r, ck, to, want_cam, gb, uv, color, rgba, advance, radius, images, gbu
     four counts; an image that is not enabled keeps its bytes.  -> the restatement's output."""
     f = r.launchParams.frame
     size = (f.size.x, f.size.y)
-    oc, op, om = device_outputs(size)
+    oc, op, om = device_images(size, 16, 4, 4)
     r.warp_motion(to, mcfg(images=images, fill_radius=radius, advance=advance), gbuffer, None, None, oc.data_ptr(), op.data_ptr(), om.data_ptr())
     got_counts = counts_of(r)
     want = wm.warp(gb, uv, ck.last, camera(r), want_cam, dict(images=images, fill_radius=radius, advance=advance), color, rgba)
-    assert np.array_equal(host(om, 1), want["map"]), label
+    assert np.array_equal(host_view(om, "map"), want["map"]), label
     assert got_counts == want["counts"] and sum(got_counts[1:]) == size[0] * size[1], (label, got_counts, want["counts"])
     if images & wr.COLOR:
-        assert np.array_equal(bits(host(oc, 4)), bits(want["color"])), label
+        assert np.array_equal(bits(host_view(oc, "color")), bits(want["color"])), label
     else:
         assert (oc.cpu().numpy() == 0x5a).all(), label
     if images & wr.RGBA:
-        assert np.array_equal(host(op, 1), want["rgba"]), label
+        assert np.array_equal(host_view(op, "rgba"), want["rgba"]), label
     else:
         assert (op.cpu().numpy() == 0x5a).all(), label
     return want
