@@ -1,7 +1,7 @@
 """The foveated frame packets of SampleRenderer, beside csrc/api_packet.hip (decode_packet, the client's side, is in renderer.py)."""
 import ctypes as C
 
-from . import abi
+from . import abi, abi_depth
 
 
 class Packets:
@@ -65,3 +65,45 @@ class Packets:
         """The device decoder: header an abi.PacketHeader (host), packet and out_rgba device pointers (out_rgba: the header's
         width x height rgba8 pixels; those no texel reaches keep their contents).  Enqueued on the renderer's stream."""
         self._check(self._L.fovpt_packet_decode(self._ctx, C.byref(header), packet, int(mode), out_rgba))
+
+    # -- depth packets (include/fovpt.h, fovpt_packet_*_depth): the frame's depth and camera, for a client that warps (api_post.warp_depth)
+    def depthPacketConfig(self, near=None) -> abi_depth.PacketDepthConfig:
+        """The fovpt_packet_depth_config of a near= argument: None -> fovpt_packet_depth_defaults, a number -> that near; an
+        abi_depth.PacketDepthConfig as it is."""
+        if isinstance(near, abi_depth.PacketDepthConfig):
+            return near
+        cfg = abi_depth.PacketDepthConfig()
+        self._L.fovpt_packet_depth_defaults(C.byref(cfg))
+        if near is not None:
+            cfg.near = near
+        return cfg
+
+    def describeDepthPacket(self, sequence=0, near=None) -> abi_depth.PacketDepthHeader:
+        """The header encodeDepthPacket / submitDepthPacket would write for the frame last rendered (host only); .base.bytes
+        sizes a buffer."""
+        h = abi_depth.PacketDepthHeader()
+        self._check(self._L.fovpt_packet_describe_depth(self._ctx, C.byref(self.launchParams), C.byref(self.depthPacketConfig(near)), sequence, C.byref(h)))
+        return h
+
+    def encodeDepthPacket(self, out_packet, sequence=0, gbuffer=None, near=None) -> abi_depth.PacketDepthHeader:
+        """Encodes the depth of the frame last rendered into out_packet, a device pointer with describeDepthPacket().base.bytes
+        of room.  gbuffer: an abi.GBufferPtrs of the rendered frame (temporal_gbuffer() saves the trace), None: traced by the
+        call.  Enqueued on the renderer's stream, not synchronised.  Returns the header it writes."""
+        h = self.describeDepthPacket(sequence, near)
+        self._check(self._L.fovpt_packet_encode_depth(self._ctx, C.byref(self.launchParams), C.byref(self.depthPacketConfig(near)),
+                                                      C.byref(gbuffer) if gbuffer is not None else None, sequence, out_packet))
+        return h
+
+    def submitDepthPacket(self, sequence=0, gbuffer=None, near=None) -> int:
+        """encodeDepthPacket into the next of the slots submitPacket uses, and the asynchronous copy to the host.  Returns the
+        slot for waitPacket."""
+        slot = C.c_int(-1)
+        self._check(self._L.fovpt_packet_submit_depth(self._ctx, C.byref(self.launchParams), C.byref(self.depthPacketConfig(near)),
+                                                      C.byref(gbuffer) if gbuffer is not None else None, sequence, C.byref(slot)))
+        return slot.value
+
+    def decodeDepthPacket(self, header, packet, out_depth):
+        """The device decoder of a depth packet: header an abi_depth.PacketDepthHeader (host), packet and out_depth device
+        pointers (out_depth: the header's width x height floats, +inf the sky; those no texel reaches keep their contents).
+        Needs no scene and no rendered frame.  Enqueued on the renderer's stream."""
+        self._check(self._L.fovpt_packet_decode_depth(self._ctx, C.byref(header), packet, out_depth))

@@ -301,6 +301,16 @@ class PostStages:
         self._check(self._L.fovpt_warp_motion(self._ctx, C.byref(self.launchParams), C.byref(to), C.byref(cfg),
                                               _ref(gbuffer), in_color, in_rgba, out_color, out_rgba, out_map))
 
+    def warp_depth(self, size, depth, from_camera, to, cfg=None, in_color=None, in_rgba=None, out_color=None, out_rgba=None, out_map=None):
+        """warp() for a client that holds no scene and no rendered frame: the source points are rebuilt from `depth`, a device
+        pointer of size[0] x size[1] floats (depth along W, +inf the sky: what decodeDepthPacket writes), and from_camera, the
+        camera they were rendered with (PacketDepthHeader.camera; anything warp_camera() takes).  Every enabled image needs its
+        input and its output, device pointers of the caller's; warp_counts() reports this warp.  Enqueued on the renderer's stream."""
+        cfg = cfg if cfg is not None else self.warp_defaults()
+        frm, to = self.warp_camera(from_camera), self.warp_camera(to)
+        self._check(self._L.fovpt_warp_depth(self._ctx, int(size[0]), int(size[1]), C.byref(frm), C.byref(to), C.byref(cfg), depth,
+                                             in_color, in_rgba, out_color, out_rgba, out_map))
+
     def warp_buffers(self):
         """Device addresses of the renderer's own warped outputs: (float4 colour, rgba8)."""
         return self._own_buffers("warp")

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "fovpt_camera.h"
 #include "fovpt_ctx.h"
 
 // ---- the shared steps ----------------------------------------------------------------------------------------------------------
@@ -52,22 +53,8 @@ int check_aliases(fovpt_ctx* c, std::initializer_list<const void*> outs, std::in
     return FOVPT_OK;
 }
 
-// The rows of [U V W]^-1 (U, V, W the columns), in binary64: det = U . (V x W), rows (V x W) / det, (W x U) / det,
-// (U x V) / det, each entry rounded to binary32.  false: det is 0 or not finite.
-bool camera_inverse(const float* U, const float* V, const float* W, float* inv)
-{
-    auto cross = [](const double* a, const double* b, double* r) {
-        r[0] = a[1] * b[2] - a[2] * b[1]; r[1] = a[2] * b[0] - a[0] * b[2]; r[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    const double u[3] = {U[0], U[1], U[2]}, v[3] = {V[0], V[1], V[2]}, w[3] = {W[0], W[1], W[2]};
-    double r[3][3];
-    cross(v, w, r[0]); cross(w, u, r[1]); cross(u, v, r[2]);
-    const double det = (u[0] * r[0][0] + u[1] * r[0][1]) + u[2] * r[0][2];
-    if (det == 0.0 || !std::isfinite(det)) return false;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) inv[3 * i + j] = (float)(r[i][j] / det);
-    return true;
-}
+// The rows of [U V W]^-1, each entry rounded to binary32 (fovpt_camera.h, which packet_host.cpp shares).  false: det is 0 or not finite.
+bool camera_inverse(const float* U, const float* V, const float* W, float* inv) { return fovpt_camera_inverse(U, V, W, inv); }
 
 // The G-buffer a caller gave, or with none the context's own (null pointers until the first trace)
 GBufferDev gbuffer_dev(const fovpt_ctx* c, const fovpt_gbuffer_ptrs* given)

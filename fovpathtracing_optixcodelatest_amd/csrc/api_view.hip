@@ -76,18 +76,31 @@ int expose_enqueue(fovpt_ctx* c, const fovpt_expose_config* ec, const fovpt_floa
 // ---- fovpt_warp and fovpt_warp_motion --------------------------------------------------------------------------------------------
 // the validation both share, in fovpt_warp's order; makes the scatter's arguments (the camera's inverse and eye: all there is to
 // them, and a singular camera has none).  reserved: the config's nres words; in, rin: the inputs of the enabled images (null: not enabled)
-int warp_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, int32_t images, int32_t fill_radius, const int32_t* reserved,
-               int nres, const fovpt_gbuffer_ptrs* gbuffer, const fovpt_float4* in, const uint32_t* rin, const char* who, WarpArgs& a)
+// the part of it that fovpt_warp_depth shares: the images, the fill radius and the reserved words of a config ...
+int warp_config_check(fovpt_ctx* c, int32_t images, int32_t fill_radius, const int32_t* reserved, int nres, const char* who)
 {
     if (images == 0 || (images & ~(FOVPT_WARP_COLOR | FOVPT_WARP_RGBA)))
         return fail(c, FOVPT_E_INVALID, "%s: images %d names no image or an unknown one", who, images);
     if (fill_radius < 0 || fill_radius > FOVPT_WARP_MAX_RADIUS)
         return fail(c, FOVPT_E_INVALID, "%s: fill_radius %d outside 0 .. %d", who, fill_radius, FOVPT_WARP_MAX_RADIUS);
-    CHK(check_reserved(c, reserved, nres, who));
+    return check_reserved(c, reserved, nres, who);
+}
+
+// ... and a camera (`which`: "to warp to", "the depths were rendered with"): finite, with an inverse, which goes to inv
+int warp_camera_check(fovpt_ctx* c, const fovpt_warp_camera* cam, const char* which, const char* who, float* inv)
+{
     for (int k = 0; k < 12; k++)                                           // eye, U, V, W: 12 floats
-        if (!std::isfinite((&to->eye.x)[k])) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to has a non-finite entry", who);
+        if (!std::isfinite((&cam->eye.x)[k])) return fail(c, FOVPT_E_INVALID, "%s: the camera %s has a non-finite entry", who, which);
+    if (!camera_inverse(&cam->U.x, &cam->V.x, &cam->W.x, inv)) return fail(c, FOVPT_E_INVALID, "%s: the camera %s is singular", who, which);
+    return FOVPT_OK;
+}
+
+int warp_check(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_warp_camera* to, int32_t images, int32_t fill_radius, const int32_t* reserved,
+               int nres, const fovpt_gbuffer_ptrs* gbuffer, const fovpt_float4* in, const uint32_t* rin, const char* who, WarpArgs& a)
+{
+    CHK(warp_config_check(c, images, fill_radius, reserved, nres, who));
     memset(&a, 0, sizeof(a));
-    if (!camera_inverse(&to->U.x, &to->V.x, &to->W.x, a.inv)) return fail(c, FOVPT_E_INVALID, "%s: the camera to warp to is singular", who);
+    CHK(warp_camera_check(c, to, "to warp to", who, a.inv));
     memcpy(a.eye, &to->eye.x, sizeof(a.eye));
     if (!gbuffer && (!c->has_scene || lp->traversable != c->scene_id)) return fail(c, FOVPT_E_NO_SCENE, "%s without a scene", who);
     CHK(check_rendered_frame(c, lp, who, "warp", nullptr, 1ull << 30));
@@ -422,6 +435,52 @@ int fovpt_warp_motion(fovpt_ctx* c, const fovpt_launch_params* lp, const fovpt_w
     if (!c) return FOVPT_E_INVALID;
     if (!lp || !to || !mc) return fail(c, FOVPT_E_INVALID, "%s: null argument", "fovpt_warp_motion");
     return warp_call(c, lp, to, mc->images, mc->fill_radius, mc->_reserved, 5, &mc->advance, gbuffer, in_color, in_rgba, out_color, out_rgba, out_map, "fovpt_warp_motion");
+}
+
+// ---- fovpt_warp from a depth image and two cameras, for a client that holds no scene and no rendered frame (warp.hip,
+// k_warp_scatter_depth; its definition: tests/warp_depth_ref.py) -------------------------------------------
+// Enqueued on fovpt_stream(): the keys (the context's own for this call) and the counts are cleared, k_warp_scatter_depth, k_warp_resolve.
+int fovpt_warp_depth(fovpt_ctx* c, int width, int height, const fovpt_warp_camera* from, const fovpt_warp_camera* to, const fovpt_warp_config* wc,
+                     const float* depth, const fovpt_float4* in_color, const uint32_t* in_rgba, fovpt_float4* out_color, uint32_t* out_rgba,
+                     uint32_t* out_map)
+{
+    const char* who = "fovpt_warp_depth";
+    if (!c) return FOVPT_E_INVALID;
+    if (!from || !to || !wc || !depth) return fail(c, FOVPT_E_INVALID, "%s: null argument", who);
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 30))
+        return fail(c, FOVPT_E_INVALID, "%s: size %d x %d is empty or has 2^30 pixels or more", who, width, height);
+    CHK(warp_config_check(c, wc->images, wc->fill_radius, wc->_reserved, 6, who));
+    WarpArgs a;
+    memset(&a, 0, sizeof(a));
+    float from_inv[9];
+    CHK(warp_camera_check(c, to, "to warp to", who, a.inv));
+    CHK(warp_camera_check(c, from, "the depths were rendered with", who, from_inv));
+    memcpy(a.eye, &to->eye.x, sizeof(a.eye));
+    const bool C_ = wc->images & FOVPT_WARP_COLOR, R_ = wc->images & FOVPT_WARP_RGBA;
+    if ((C_ && (!in_color || !out_color)) || (R_ && (!in_rgba || !out_rgba)))
+        return fail(c, FOVPT_E_INVALID, "%s: an enabled image has a null input or a null output", who);
+    if (!C_) { in_color = nullptr; out_color = nullptr; }
+    if (!R_) { in_rgba = nullptr; out_rgba = nullptr; }
+    HIPCHK(c, hipSetDevice(c->device));
+    fovpt_ctx::Warp& W = c->warp;
+    const size_t npix = (size_t)width * (size_t)height;
+    HIPCHK(c, W.depth_keys.reserve(npix * 8));
+    CHK(record_make(c, W.counts, FOVPT_WARP_COUNT_BYTES));
+    CHK(check_aliases(c, {out_color, out_rgba, out_map}, {in_color, in_rgba, depth, W.depth_keys.p}, who,
+                      "%s: an output is an input of the call (the resolve reads across pixels)"));
+    FrameDev fd;                                                           // the size and the camera: all the scatter reads of it
+    memset(&fd, 0, sizeof(fd));
+    fd.w = width; fd.h = height;
+    memcpy(fd.eye, &from->eye.x, sizeof(fd.eye)); memcpy(fd.U, &from->U.x, sizeof(fd.U));
+    memcpy(fd.V, &from->V.x, sizeof(fd.V)); memcpy(fd.W, &from->W.x, sizeof(fd.W));
+    const hipStream_t st = c->shadow_stream;
+    uint64_t *keys = (uint64_t*)W.depth_keys.p, *counts = (uint64_t*)W.counts.p;
+    HIPCHK(c, hipMemsetAsync(keys, 0xff, npix * 8, st));
+    HIPCHK(c, hipMemsetAsync(counts, 0, FOVPT_WARP_COUNT_BYTES, st));
+    fovpt_launch_warp_scatter_depth(st, fd, a, depth, keys, counts);
+    fovpt_launch_warp_resolve(st, width, height, wc->fill_radius, keys, in_color, in_rgba, out_color, out_rgba, out_map, counts);
+    HIPCHK(c, hipGetLastError());
+    return FOVPT_OK;
 }
 
 // ---- gaze-metered focus distance and depth of field (focus.hip; its definition: tests/focus_ref.py) ---------------------------

@@ -250,7 +250,9 @@ struct fovpt_ctx {
     // fovpt_warp: the scatter's keys (8 bytes per pixel), the device counts (FOVPT_WARP_COUNT_SLOTS partial records, zeroed on the stream
     // ahead of every warp; the host reads and adds them nowhere but in fovpt_warp_counts) and the context's own outputs; all allocated on
     // first use
-    struct FOVPT_LOCAL Warp { DevBuf keys, counts; OutPair out; } warp;
+    // depth_keys: fovpt_warp_depth's own keys, for the size of its last call (grown on demand; not the rendered frame's, so a
+    // resize leaves them alone); the counts record is the one of all three kinds of warp
+    struct FOVPT_LOCAL Warp { DevBuf keys, counts, depth_keys; OutPair out; } warp;
     // fovpt_focus: the device state record (a struct fovpt_focus_state, zeroed when made and by a reset: steps 0 = the next AUTO
     // step is a first step; the host never reads it outside fovpt_focus_state), the (r, tp) pairs of the last call (8 bytes per
     // pixel) and the context's own outputs; all allocated on first use

@@ -395,6 +395,9 @@ struct WarpMotionArgs {
 };
 void fovpt_launch_warp_scatter_motion(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const WarpMotionArgs& m, const uint32_t* prim,
                                       const float4* pos, uint64_t* keys, uint64_t* counts);
+// fovpt_warp_depth (warp.hip, k_warp_scatter_depth): the scatter from a depth image (fd.w x fd.h floats: depth along W, +inf the
+// sky) and the camera it was rendered with -- fd's size, eye, U, V and W; nothing else of fd is read
+void fovpt_launch_warp_scatter_depth(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const float* depth, uint64_t* keys, uint64_t* counts);
 // in_color / out_color, in_rgba / out_rgba: both null where that image is not warped; out_map: may be null.  No output is an
 // input or another output (a pixel reads other pixels' inputs)
 void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,

@@ -13,7 +13,13 @@
 //                      block with the block's statistics by xor-shuffles
 //   k_packet_decode<MODE, CODED>  CODED fetches every texel through fetch_texel, which decodes one texel from its 8-byte block
 //
-// The definition in integers is tests/packet_ref.py, of the block code tests/packet_bc_ref.py.
+//   k_packet_depth_encode  the depth packet ("FVPD"): the same walk over a texel's owned pixels (walk_owned)
+//                      reading the G-buffer's prim and position, reduced by the maximum of the pixels' 16-bit codes; a 2-byte
+//                      store per texel
+//   k_packet_depth_decode  k_packet_decode's search (find_last_texel) with "code != 0" for "alpha != 0"; a float per pixel
+//
+// The definition in integers is tests/packet_ref.py, of the block code tests/packet_bc_ref.py, of the depth packet
+// tests/packet_depth_ref.py.
 #include "fovpt_packet.h"
 #include "fovpt_pixel.h"
 
@@ -32,9 +38,33 @@ __device__ inline bool seen_before(uint32_t i, uint32_t k, uint32_t dim)
 
 __device__ inline uint32_t pick(const uint4& q, uint32_t u) { return u == 0u ? q.x : u == 1u ? q.y : u == 2u ? q.z : q.w; }
 
-// The texel of launch index (lx, ly) of pass p (factor f, offsets offx / offy): the mean of the pixels it owns -- those of its
-// clamped fill x fill block whose last writer it is (find_last_writer) --, alpha 0xff; 0 where it owns none.  vec: `in` is 16-byte
-// aligned and the frame's width a multiple of 4.
+// The walk over the pixels that launch index (lx, ly) of pass p (factor f, offsets offx / offy) OWNS: those of its clamped
+// fill x fill block, each once, whose last writer it is (find_last_writer).  own(u, v, px, py): pixel (px, py) is column u, row v
+// of the block.  Both encoders' texels are reductions over this walk.
+template <class Own>
+__device__ __forceinline__ void walk_owned(const FrameDev& fd, int p, uint32_t f, uint32_t fill, uint32_t offx, uint32_t offy, uint32_t lx, uint32_t ly,
+                                  Own own)
+{
+    const uint32_t ix = lx * f + offx, iy = ly * f + offy;            // (uint32: wraps)
+    const uint32_t W = (uint32_t)fd.w, H = (uint32_t)fd.h;
+#pragma unroll 1
+    for (uint32_t v = 0; v < fill; v++) {
+        if (seen_before(iy, v, H)) continue;
+        const uint32_t py = block_pixel(iy, v, H);
+#pragma unroll 1
+        for (uint32_t u = 0; u < fill; u++) {
+            if (seen_before(ix, u, W)) continue;
+            const uint32_t px = block_pixel(ix, u, W);
+            int wp = 0;
+            uint32_t wlx, wly;
+            if (!find_last_writer(fd, px, py, wp, wlx, wly) || wp != p || wlx != lx || wly != ly) continue;
+            own(u, v, px, py);
+        }
+    }
+}
+
+// The colour texel of launch index (lx, ly) of pass p: the mean of the pixels it owns, alpha 0xff; 0 where it owns none.  vec:
+// `in` is 16-byte aligned and the frame's width a multiple of 4.
 __device__ inline uint32_t owned_texel(const FrameDev& fd, const uint32_t* __restrict__ in, uint32_t vec, int p, uint32_t f, uint32_t fill,
                                        uint32_t offx, uint32_t offy, uint32_t lx, uint32_t ly)
 {
@@ -50,23 +80,11 @@ __device__ inline uint32_t owned_texel(const FrameDev& fd, const uint32_t* __res
         q0 = r[0]; q1 = r[pitch]; q2 = r[2 * pitch]; q3 = r[3 * pitch];
     }
     uint32_t n = 0u, sr = 0u, sg = 0u, sb = 0u;
-#pragma unroll 1
-    for (uint32_t v = 0; v < fill; v++) {
-        if (seen_before(iy, v, H)) continue;
-        const uint32_t py = block_pixel(iy, v, H);
-        const uint4 q = v == 0u ? q0 : v == 1u ? q1 : v == 2u ? q2 : q3;
-#pragma unroll 1
-        for (uint32_t u = 0; u < fill; u++) {
-            if (seen_before(ix, u, W)) continue;
-            const uint32_t px = block_pixel(ix, u, W);
-            int wp = 0;
-            uint32_t wlx, wly;
-            if (!find_last_writer(fd, px, py, wp, wlx, wly) || wp != p || wlx != lx || wly != ly) continue;
-            const uint32_t c = rows4 ? pick(q, u) : in[(size_t)py * W + px];
-            n++;
-            sr += c & 0xffu; sg += (c >> 8) & 0xffu; sb += (c >> 16) & 0xffu;
-        }
-    }
+    walk_owned(fd, p, f, fill, offx, offy, lx, ly, [&](uint32_t u, uint32_t v, uint32_t px, uint32_t py) __attribute__((always_inline)) {
+        const uint32_t c = rows4 ? (v == 0u ? pick(q0, u) : v == 1u ? pick(q1, u) : v == 2u ? pick(q2, u) : pick(q3, u)) : in[(size_t)py * W + px];
+        n++;
+        sr += c & 0xffu; sg += (c >> 8) & 0xffu; sb += (c >> 16) & 0xffu;
+    });
     uint32_t texel = 0u;
     if (n) {
         const uint32_t h = n >> 1;
@@ -253,16 +271,16 @@ __device__ inline uint32_t fetch_texel(const uint32_t* __restrict__ tex, const f
     return tex[(size_t)ly * P.gw + lx];
 }
 
-template <bool CODED>
-__device__ inline bool find_last_texel(const PacketArgs& a, const uint32_t* __restrict__ pk, uint32_t x, uint32_t y, int& wp, uint32_t& wlx,
-                                       uint32_t& wly, uint32_t& val)
+// fetch(P, lx, ly, val): texel (lx, ly) of pass P into val, true where it is live (a colour texel: alpha != 0; a depth code: != 0)
+template <class Fetch>
+__device__ inline bool find_last_texel(const fovpt_packet_header& h, uint32_t x, uint32_t y, int& wp, uint32_t& wlx, uint32_t& wly, uint32_t& val,
+                                       Fetch fetch)
 {
-    const uint32_t W = (uint32_t)a.h.width, H = (uint32_t)a.h.height;
+    const uint32_t W = (uint32_t)h.width, H = (uint32_t)h.height;
 #pragma unroll
     for (int p = FOVPT_MAX_PASSES - 1; p >= 0; p--) {
-        if ((uint32_t)p >= a.h.npass) continue;
-        const fovpt_packet_pass& P = a.h.pass[p];
-        const uint32_t* tex = pk + (P.texels >> 2);
+        if ((uint32_t)p >= h.npass) continue;
+        const fovpt_packet_pass& P = h.pass[p];
         const uint32_t f = P.factor;
         // blocks that tile the plane, away from the last column and row: one candidate per axis
         if (P.fill == f && (f & (f - 1u)) == 0u && x + 1u != W && y + 1u != H) {
@@ -270,8 +288,8 @@ __device__ inline bool find_last_texel(const PacketArgs& a, const uint32_t* __re
             const long long rx = (long long)x - (long long)(int32_t)P.offx, ry = (long long)y - (long long)(int32_t)P.offy;
             if (rx < 0 || ry < 0 || rx >= ((long long)P.gw << sh) || ry >= ((long long)P.gh << sh)) continue;
             const uint32_t lx = (uint32_t)rx >> sh, ly = (uint32_t)ry >> sh;
-            const uint32_t c = fetch_texel<CODED>(tex, P, lx, ly);
-            if (!(c >> 24)) continue;
+            uint32_t c;
+            if (!fetch(P, lx, ly, c)) continue;
             wp = p; wlx = lx; wly = ly; val = c;
             return true;
         }
@@ -284,8 +302,8 @@ __device__ inline bool find_last_texel(const PacketArgs& a, const uint32_t* __re
             if (ly < ya && ly > yw) { ly = yw + 1; continue; }
             for (long long lx = xb; lx >= x_end; lx--) {
                 if (lx < xa && lx > xw) { lx = xw + 1; continue; }
-                const uint32_t c = fetch_texel<CODED>(tex, P, (uint32_t)lx, (uint32_t)ly);
-                if (!(c >> 24)) continue;
+                uint32_t c;
+                if (!fetch(P, (uint32_t)lx, (uint32_t)ly, c)) continue;
                 wp = p; wlx = (uint32_t)lx; wly = (uint32_t)ly; val = c;
                 return true;
             }
@@ -303,7 +321,11 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_packet_decode(const PacketArgs 
     const uint32_t y = idx / W, x = idx - y * W;
     int p = 0;
     uint32_t lx, ly, val;
-    if (!find_last_texel<CODED>(a, pk, x, y, p, lx, ly, val)) return;        // (no texel reaches the pixel: it keeps what it held)
+    const auto fetch = [pk](const fovpt_packet_pass& P, uint32_t tx, uint32_t ty, uint32_t& c) {
+        c = fetch_texel<CODED>(pk + (P.texels >> 2), P, tx, ty);
+        return (c >> 24) != 0u;
+    };
+    if (!find_last_texel(a.h, x, y, p, lx, ly, val, fetch)) return;          // (no texel reaches the pixel: it keeps what it held)
     if (MODE == FOVPT_PACKET_SMOOTH) {
         const fovpt_packet_pass& P0 = a.h.pass[0];
         const fovpt_packet_pass& P1 = a.h.pass[1];
@@ -347,7 +369,87 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_packet_decode(const PacketArgs 
     out[idx] = val;
 }
 
+// ---- the depth packet ("FVPD"; the definition: tests/packet_depth_ref.py) ------------------------------------
+// The code of G-buffer entry (prim, X): 1 for the sky and for a point not in front of the camera, else 2 .. 65535, linear in
+// near / z with z the point's depth along W (m2: the third row of the rendered camera's inverse).
+__device__ inline uint32_t depth_code(uint32_t prim, const float4& X, const float* eye, const float* m2, float near)
+{
+    if (prim == 0xffffffffu) return 1u;
+    const V3 v = v3(X) - v3(eye[0], eye[1], eye[2]);
+    const float z = (m2[0] * v.x + m2[1] * v.y) + m2[2] * v.z;
+    if (!(z > 0.0f) || !(z < INFINITY)) return 1u;                    // (NaN fails the first)
+    const float q = near / z;
+    const float c = fmaxf(1.0f, fminf(floorf(q * 65534.0f + 0.5f), 65534.0f));
+    return (uint32_t)c + 1u;
+}
+
+// One thread per texel of all passes: the largest code of the pixels it owns (walk_owned), 0 where it owns none, stored as its
+// own 2 bytes; the thread of an odd pass's last texel stores the 2 bytes of padding behind it, and thread 0 the 48 header words.
+__global__ __launch_bounds__(FOVPT_BLOCK) void k_packet_depth_encode(const FrameDev fd, const PacketDepthArgs a, const uint32_t* __restrict__ prim,
+                                                                     const float4* __restrict__ pos, uint32_t* __restrict__ out)
+{
+    const uint32_t t = blockIdx.x * FOVPT_BLOCK + threadIdx.x;
+    if (t == 0u) {
+        store_header(a.h.base, out);
+        const float* cam = &a.h.camera.eye.x;
+#pragma unroll
+        for (int k = 0; k < 12; k++) out[32 + k] = __float_as_uint(cam[k]);
+        out[44] = __float_as_uint(a.h.near); out[45] = a.h._reserved[0]; out[46] = a.h._reserved[1]; out[47] = a.h._reserved[2];
+    }
+    if (t >= a.first[FOVPT_MAX_PASSES]) return;
+    const int p = t < a.first[1] ? 0 : t < a.first[2] ? 1 : 2;
+    const fovpt_packet_pass& P0 = a.h.base.pass[0];
+    const fovpt_packet_pass& P1 = a.h.base.pass[1];
+    const fovpt_packet_pass& P2 = a.h.base.pass[2];
+    const uint32_t gw = p == 0 ? P0.gw : p == 1 ? P1.gw : P2.gw, gh = p == 0 ? P0.gh : p == 1 ? P1.gh : P2.gh;
+    const uint32_t f = p == 0 ? P0.factor : p == 1 ? P1.factor : P2.factor, fill = p == 0 ? P0.fill : p == 1 ? P1.fill : P2.fill;
+    const uint32_t offx = p == 0 ? P0.offx : p == 1 ? P1.offx : P2.offx, offy = p == 0 ? P0.offy : p == 1 ? P1.offy : P2.offy;
+    uint16_t* dst = (uint16_t*)(out + ((p == 0 ? P0.texels : p == 1 ? P1.texels : P2.texels) >> 2));
+    const uint32_t li = t - (p == 0 ? a.first[0] : p == 1 ? a.first[1] : a.first[2]);
+    const uint32_t ly = li / gw, lx = li - ly * gw;
+    const uint32_t W = (uint32_t)fd.w;
+    const float* eye = &a.h.camera.eye.x;
+    uint32_t code = 0u;
+    walk_owned(fd, p, f, fill, offx, offy, lx, ly, [&](uint32_t, uint32_t, uint32_t px, uint32_t py) __attribute__((always_inline)) {
+        const size_t s = (size_t)py * W + px;
+        code = max(code, depth_code(prim[s], pos[s], eye, a.m2, a.h.near));
+    });
+    dst[li] = (uint16_t)code;
+    const uint32_t n = gw * gh;                                       // (<= 2^26)
+    if (li + 1u == n && (n & 1u)) dst[n] = 0;                         // the padding to a multiple of 4
+}
+
+__global__ __launch_bounds__(FOVPT_BLOCK) void k_packet_depth_decode(const PacketDepthArgs a, const uint32_t* __restrict__ pk, float* __restrict__ out)
+{
+    const fovpt_packet_header& h = a.h.base;
+    const uint32_t W = (uint32_t)h.width, H = (uint32_t)h.height;
+    const uint32_t idx = blockIdx.x * FOVPT_BLOCK + threadIdx.x;      // (W * H <= 2^28)
+    if (idx >= W * H) return;
+    const uint32_t y = idx / W, x = idx - y * W;
+    int p = 0;
+    uint32_t lx, ly, code;
+    const auto fetch = [pk](const fovpt_packet_pass& P, uint32_t tx, uint32_t ty, uint32_t& c) {
+        c = ((const uint16_t*)(pk + (P.texels >> 2)))[(size_t)ty * P.gw + tx];
+        return c != 0u;
+    };
+    if (!find_last_texel(h, x, y, p, lx, ly, code, fetch)) return;    // (no texel reaches the pixel: it keeps what it held)
+    out[idx] = code == 1u ? INFINITY : (a.h.near * 65534.0f) / (float)(code - 1u);
+}
+
 }  // namespace
+
+void fovpt_launch_packet_depth_encode(hipStream_t st, const FrameDev& fd, const PacketDepthArgs& a, const uint32_t* prim, const float4* pos,
+                                      uint32_t* out)
+{
+    const uint32_t total = a.first[FOVPT_MAX_PASSES];                 // (>= 1: every pass has a launch index)
+    hipLaunchKernelGGL(k_packet_depth_encode, dim3((total + FOVPT_BLOCK - 1) / FOVPT_BLOCK), dim3(FOVPT_BLOCK), 0, st, fd, a, prim, pos, out);
+}
+
+void fovpt_launch_packet_depth_decode(hipStream_t st, const PacketDepthArgs& a, const uint32_t* packet, float* out)
+{
+    const uint32_t npix = (uint32_t)a.h.base.width * (uint32_t)a.h.base.height;
+    hipLaunchKernelGGL(k_packet_depth_decode, dim3((npix + FOVPT_BLOCK - 1) / FOVPT_BLOCK), dim3(FOVPT_BLOCK), 0, st, a, packet, out);
+}
 
 void fovpt_launch_packet_encode(hipStream_t st, const FrameDev& fd, const PacketArgs& a, const uint32_t* in, uint32_t* out)
 {

@@ -2,24 +2,34 @@
 // the definition in integers: tests/packet_ref.py, of a coded packet's BC1 passes tests/packet_bc_ref.py).  Host-only C++ without a context, for untrusted bytes: compiled into
 // libfovpt.so and into libfovpt_loader.so, the library for machines without ROCm.  Every read goes through memcpy inside
 // [packet, packet + header.bytes), which the checks have shown to lie inside the caller's bytes; every write is to a pixel
-// index clamped into the output.
+// index clamped into the output.  The depth packet ("FVPD": fovpt_packet_depth_defaults, fovpt_packet_check_depth and
+// fovpt_packet_decode_depth_host; the definition: tests/packet_depth_ref.py) shares the checks of the first 128 bytes.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
+#include "fovpt_camera.h"
 #include "fovpt_packet.h"
 
 void fovpt_internal_set_error(const char* text);      // fovpt_api.hip / loader_host.cpp: the text fovpt_last_error(NULL) returns
 
 static_assert(sizeof(fovpt_packet_header) == FOVPT_PACKET_HEADER_BYTES, "packet header");
 
-const char* fovpt_packet_header_error(const fovpt_packet_header* h, uint64_t avail)
+static_assert(sizeof(fovpt_packet_depth_header) == FOVPT_PACKET_DEPTH_HEADER_BYTES, "depth packet header");
+
+namespace {
+
+// The checks on the 128 bytes every kind of packet starts with.  depth: an "FVPD" packet -- the arrays start behind 192 bytes
+// and hold 2 bytes per texel, padded to 4; otherwise "FVPK" or "FVPC" by the magic.
+const char* common_header_error(const fovpt_packet_header* h, uint64_t avail, bool depth)
 {
-    const bool coded = h->magic == FOVPT_PACKET_MAGIC_CODED;             // ("FVPC": the pass's eighth word is its codec)
-    if (h->magic != FOVPT_PACKET_MAGIC && !coded) return "wrong magic";
+    const bool coded = !depth && h->magic == FOVPT_PACKET_MAGIC_CODED;   // ("FVPC": the pass's eighth word is its codec)
+    const uint32_t head = depth ? FOVPT_PACKET_DEPTH_HEADER_BYTES : FOVPT_PACKET_HEADER_BYTES;
+    if (depth ? h->magic != FOVPT_PACKET_MAGIC_DEPTH : h->magic != FOVPT_PACKET_MAGIC && !coded) return "wrong magic";
     if (h->version != FOVPT_PACKET_VERSION) return "unknown version";
-    if (h->bytes > avail || h->bytes < FOVPT_PACKET_HEADER_BYTES) return "bytes field outside 128 .. the bytes given";
+    if (h->bytes > avail || h->bytes < head) return depth ? "bytes field outside 192 .. the bytes given" : "bytes field outside 128 .. the bytes given";
     if (h->width < 1 || h->width > FOVPT_PACKET_MAX_DIM || h->height < 1 || h->height > FOVPT_PACKET_MAX_DIM) return "width / height outside 1 .. 16384";
     if (h->npass < 1 || h->npass > 3) return "npass outside 1 .. 3";
     if (h->_reserved) return "non-zero reserved field";
@@ -36,9 +46,27 @@ const char* fovpt_packet_header_error(const fovpt_packet_header* h, uint64_t ava
         if (n > FOVPT_PACKET_MAX_TEXELS || (texels += n) > FOVPT_PACKET_MAX_TEXELS) return "more than 2^26 texels";
         if (P.factor == 0) return "factor 0";
         if (P.fill < 1 || P.fill > FOVPT_PACKET_MAX_FILL) return "fill outside 1 .. 8";
-        if (P.texels < FOVPT_PACKET_HEADER_BYTES || (P.texels & 3u)) return "texel offset below 128 or not a multiple of 4";
-        if ((uint64_t)P.texels + fovpt_packet_pass_bytes(P.gw, P.gh, P._reserved) > (uint64_t)h->bytes) return "texel array outside the packet";
+        if (P.texels < head || (P.texels & 3u)) return depth ? "code offset below 192 or not a multiple of 4" : "texel offset below 128 or not a multiple of 4";
+        const uint64_t size = depth ? fovpt_packet_depth_pass_bytes(P.gw, P.gh) : fovpt_packet_pass_bytes(P.gw, P.gh, P._reserved);
+        if ((uint64_t)P.texels + size > (uint64_t)h->bytes) return "texel array outside the packet";
     }
+    return nullptr;
+}
+
+}  // namespace
+
+const char* fovpt_packet_header_error(const fovpt_packet_header* h, uint64_t avail) { return common_header_error(h, avail, false); }
+
+const char* fovpt_packet_depth_header_error(const fovpt_packet_depth_header* h, uint64_t avail)
+{
+    if (const char* why = common_header_error(&h->base, avail, true)) return why;
+    const float* cam = &h->camera.eye.x;                                 // eye, U, V, W: 12 floats
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(cam[k])) return "non-finite camera entry";
+    float inv[9];
+    if (!fovpt_camera_inverse(&h->camera.U.x, &h->camera.V.x, &h->camera.W.x, inv)) return "singular camera";
+    if (!(std::isfinite(h->near) && h->near > 0.0f)) return "near is not finite and above 0";
+    if (h->_reserved[0] | h->_reserved[1] | h->_reserved[2]) return "non-zero reserved field";
     return nullptr;
 }
 
@@ -58,6 +86,15 @@ int read_header(const char* who, const void* packet, size_t bytes, fovpt_packet_
     if (bytes < FOVPT_PACKET_HEADER_BYTES) return refuse(who, "fewer than 128 bytes");
     memcpy(&h, packet, sizeof(h));
     if (const char* why = fovpt_packet_header_error(&h, (uint64_t)bytes)) return refuse(who, why);
+    return FOVPT_OK;
+}
+
+int read_depth_header(const char* who, const void* packet, size_t bytes, fovpt_packet_depth_header& h)
+{
+    if (!packet) return refuse(who, "null packet");
+    if (bytes < FOVPT_PACKET_DEPTH_HEADER_BYTES) return refuse(who, "fewer than 192 bytes");
+    memcpy(&h, packet, sizeof(h));
+    if (const char* why = fovpt_packet_depth_header_error(&h, (uint64_t)bytes)) return refuse(who, why);
     return FOVPT_OK;
 }
 
@@ -167,6 +204,50 @@ int fovpt_packet_decode_host(const void* packet, size_t bytes, int mode, uint32_
             for (int k = 0; k < 3; k++) v |= ((sum[k] + total / 2) / total) << (8 * k);
             out_rgba[(size_t)y * W + x] = v;
         }
+    return FOVPT_OK;
+}
+
+// ---- the depth packet ("FVPD"; the definition: tests/packet_depth_ref.py) ------------------------------------------------------
+// (near: a convention, not a measurement: include/fovpt.h)
+void fovpt_packet_depth_defaults(fovpt_packet_depth_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    cfg->near = 0.1f;
+}
+
+int fovpt_packet_check_depth(const void* packet, size_t bytes)
+{
+    fovpt_packet_depth_header h;
+    return read_depth_header("fovpt_packet_check_depth", packet, bytes, h);
+}
+
+int fovpt_packet_decode_depth_host(const void* packet, size_t bytes, float* out_depth, int width, int height)
+{
+    const char* who = "fovpt_packet_decode_depth_host";
+    fovpt_packet_depth_header h;
+    { const int rc_ = read_depth_header(who, packet, bytes, h); if (rc_) return rc_; }
+    if (!out_depth) return refuse(who, "null output");
+    if (width != h.base.width || height != h.base.height) return refuse(who, "the output's size differs from the packet's");
+    const unsigned char* base = (const unsigned char*)packet;
+    const uint32_t W = (uint32_t)h.base.width, H = (uint32_t)h.base.height;
+    const float scale = h.near * 65534.0f;
+    // the forward loop of the definition: pass order, ascending (ly, lx), later writes win
+    for (uint32_t p = 0; p < h.base.npass; p++) {
+        const fovpt_packet_pass& P = h.base.pass[p];
+        for (uint32_t ly = 0; ly < P.gh; ly++)
+            for (uint32_t lx = 0; lx < P.gw; lx++) {
+                uint16_t code;
+                memcpy(&code, base + P.texels + 2ull * ((uint64_t)ly * P.gw + lx), 2);
+                if (!code) continue;
+                const float d = code == 1u ? INFINITY : scale / (float)(code - 1u);
+                const uint32_t ix = lx * P.factor + P.offx, iy = ly * P.factor + P.offy;      // (uint32: wraps)
+                for (uint32_t v = 0; v < P.fill; v++) {
+                    const size_t row = (size_t)clamp_pixel(iy + v, H) * W;
+                    for (uint32_t u = 0; u < P.fill; u++) out_depth[row + clamp_pixel(ix + u, W)] = d;
+                }
+            }
+    }
     return FOVPT_OK;
 }
 

@@ -7,6 +7,8 @@
 //                    depths go to the lower source index: the keys do not depend on the order in which the atomics arrive
 //   k_warp_scatter_motion   fovpt_warp_motion's scatter: k_warp_scatter in which a hit pixel of a mesh that moved in the last
 //                    interval lands where its own motion, extrapolated by `advance` intervals, takes it
+//   k_warp_scatter_depth    fovpt_warp_depth's scatter: k_warp_scatter with the source point rebuilt from a depth image and the
+//                    camera it was rendered with, for a client that holds no scene
 //   k_warp_resolve   per destination pixel: the key's source; for an empty key the farthest key of the nearest non-empty
 //                    Chebyshev ring within fill_radius; else the pixel itself.  Copies the enabled images from the source,
 //                    bit for bit, and writes the map
@@ -109,6 +111,26 @@ __global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter_motion(const Frame
     count_wave(landed, &count_slot(counts)[0]);
 }
 
+// fovpt_warp_depth's scatter (tests/warp_depth_ref.py): k_warp_scatter with the source point rebuilt from a
+// depth image.  fd: the size and the camera the depths were rendered with, all that is read of it.  A pixel at depth z along W is
+// eye + z * pixel_ray; +inf is the sky, which scatters its direction as a miss does; NaN, <= 0 and -inf scatter nothing.
+__global__ __launch_bounds__(FOVPT_BLOCK) void k_warp_scatter_depth(const FrameDev fd, const WarpArgs a, const float* __restrict__ depth,
+                                                                    unsigned long long* __restrict__ keys, unsigned long long* __restrict__ counts)
+{
+    uint32_t x, y, s;
+    bool landed = false;
+    if (tile_pixel(fd.w, fd.h, x, y, s)) {                                // (lanes outside the frame go on to count_wave)
+        const float z = depth[s];
+        if (z > 0.0f) {                                                  // (NaN fails)
+            const bool miss = z == INFINITY;
+            V3 v = pixel_ray(fd, x, y);
+            if (!miss) v = (v3(fd.eye[0], fd.eye[1], fd.eye[2]) + z * v) - v3(a.eye[0], a.eye[1], a.eye[2]);
+            landed = scatter_key(fd, a, v, miss, s, keys);
+        }
+    }
+    count_wave(landed, &count_slot(counts)[0]);
+}
+
 // the largest non-empty key, or 0
 __device__ inline unsigned long long farthest(unsigned long long best, unsigned long long k) { return k != WARP_EMPTY && k > best ? k : best; }
 
@@ -167,6 +189,12 @@ void fovpt_launch_warp_scatter_motion(hipStream_t st, const FrameDev& fd, const 
 {
     hipLaunchKernelGGL(k_warp_scatter_motion, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, m, prim, pos,
                        (unsigned long long*)keys, (unsigned long long*)counts);
+}
+
+void fovpt_launch_warp_scatter_depth(hipStream_t st, const FrameDev& fd, const WarpArgs& a, const float* depth, uint64_t* keys, uint64_t* counts)
+{
+    hipLaunchKernelGGL(k_warp_scatter_depth, fovpt_tile_grid(fd.w, fd.h), dim3(FOVPT_BLOCK), 0, st, fd, a, depth, (unsigned long long*)keys,
+                       (unsigned long long*)counts);
 }
 
 void fovpt_launch_warp_resolve(hipStream_t st, int w, int h, int radius, const uint64_t* keys, const fovpt_float4* in_color, const uint32_t* in_rgba,

@@ -6,7 +6,7 @@ import ctypes as C
 import os
 import subprocess
 
-from . import abi
+from . import abi, abi_depth
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -112,6 +112,15 @@ SIGNATURES = {
     "fovpt_packet_describe_coded": (_i32, [_vp, _params, _P(abi.PacketConfig), _u32, _P(abi.PacketHeader)]),
     "fovpt_packet_encode_coded": (_i32, [_vp, _params, _P(abi.PacketConfig), _vp, _u32, _vp]),
     "fovpt_packet_submit_coded": (_i32, [_vp, _params, _P(abi.PacketConfig), _vp, _u32, _P(_i32)]),
+    # -- depth packets and the client's warp (csrc/api_packet.hip, csrc/packet_host.cpp, csrc/api_view.hip)
+    "fovpt_packet_depth_defaults": (None, [_P(abi_depth.PacketDepthConfig)]),
+    "fovpt_packet_describe_depth": (_i32, [_vp, _params, _P(abi_depth.PacketDepthConfig), _u32, _P(abi_depth.PacketDepthHeader)]),
+    "fovpt_packet_encode_depth": (_i32, [_vp, _params, _P(abi_depth.PacketDepthConfig), _gbuf, _u32, _vp]),
+    "fovpt_packet_submit_depth": (_i32, [_vp, _params, _P(abi_depth.PacketDepthConfig), _gbuf, _u32, _P(_i32)]),
+    "fovpt_packet_check_depth": (_i32, [_vp, _sz]),
+    "fovpt_packet_decode_depth_host": (_i32, [_vp, _sz, _vp, _i32, _i32]),
+    "fovpt_packet_decode_depth": (_i32, [_vp, _P(abi_depth.PacketDepthHeader), _vp, _vp]),
+    "fovpt_warp_depth": (_i32, [_vp, _i32, _i32, _cam, _cam, _P(abi.WarpConfig), _vp, _vp, _vp, _vp, _vp, _vp]),
     # -- animated geometry (csrc/api_animate.hip)
     "fovpt_update_vertices": (_i32, [_vp, _P(abi.VertexUpdate), _i32, _i32]),
     "fovpt_update_transforms": (_i32, [_vp, _P(abi.MeshTransform), _i32, _i32]),
@@ -153,7 +162,8 @@ EXPORTS = list(SIGNATURES)
 # what the host-only libfovpt_loader.so has too (load_loader): the file readers, the packet checks and decoder for a client
 # (csrc/packet_host.cpp), the quality measurement on host images and the scores of a record (csrc/quality_host.cpp)
 LOADER_EXPORTS = [n for n in EXPORTS if n.startswith("fovpt_model_") or n.startswith("fovpt_image_")] + ["fovpt_last_error"]
-PACKET_HOST_EXPORTS = ["fovpt_packet_check", "fovpt_packet_decode_host"]
+PACKET_HOST_EXPORTS = ["fovpt_packet_check", "fovpt_packet_decode_host", "fovpt_packet_depth_defaults", "fovpt_packet_check_depth",
+                       "fovpt_packet_decode_depth_host"]
 QUALITY_SCORE_EXPORTS = ("fovpt_quality_mse", "fovpt_quality_psnr", "fovpt_quality_ssim", "fovpt_quality_score")   # return a double
 QUALITY_HOST_EXPORTS = ["fovpt_quality_host"] + list(QUALITY_SCORE_EXPORTS)
 LOADER_SO_PATH = os.path.join(CSRC, "libfovpt_loader.so")

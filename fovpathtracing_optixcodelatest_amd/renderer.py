@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, lib
+from . import abi, abi_depth, lib
 from .api_animate import Animation
 from .api_debug import DebugHooks
 from .api_packet import Packets
@@ -37,6 +37,29 @@ def decode_packet(data, mode=abi.PACKET_NEAREST, size=None, out=None):
     elif out.shape != (h, w) or out.dtype != np.uint32 or not out.flags["C_CONTIGUOUS"]:
         raise ValueError("decode_packet: out must be a C-contiguous (%d, %d) uint32 array" % (h, w))
     lib.check(None, L.fovpt_packet_decode_host(buf, len(buf), int(mode), out.ctypes.data, w, h), L)
+    return out
+
+
+def decode_depth_packet(packet, size=None, out=None):
+    """A depth packet (bytes-like, what waitPacket returned for a submitDepthPacket) -> the (H, W) float32 depth image along
+    the rendered camera's W, +inf the sky (fovpt_packet_decode_depth_host); abi_depth.PacketDepthHeader.from_packet(packet)
+    has the camera.  size, out: as decode_packet's, out a float32 array (None: zeros).  Needs the host-only loader library
+    alone.  Raises lib.FovptError on bytes that are not a valid depth packet."""
+    buf = bytes(packet)
+    L = lib.load_loader()
+    if size is None:
+        if len(buf) < C.sizeof(abi_depth.PacketDepthHeader):
+            raise lib.FovptError(-1, "decode_depth_packet: fewer than 192 bytes")
+        h = abi_depth.PacketDepthHeader.from_packet(buf).base
+        size = (h.width, h.height)
+    w, h = int(size[0]), int(size[1])
+    if out is None:
+        if not (0 < w <= 16384 and 0 < h <= 16384):
+            raise lib.FovptError(-1, "decode_depth_packet: width / height outside 1 .. 16384")
+        out = np.zeros((h, w), np.float32)
+    elif out.shape != (h, w) or out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("decode_depth_packet: out must be a C-contiguous (%d, %d) float32 array" % (h, w))
+    lib.check(None, L.fovpt_packet_decode_depth_host(buf, len(buf), out.ctypes.data, w, h), L)
     return out
 
 

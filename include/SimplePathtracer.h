@@ -581,6 +581,35 @@ public:
         check(fovpt_packet_decode(ctx, &header, packet, mode, out_rgba));
         check(fovpt_synchronize(ctx));
     }
+    // ---- depth packets and the client's warp (include/fovpt.h, "depth packets"): the frame's depth and camera travel like its
+    // colour -- submitDepthPacket() beside submitPacket(), the same slots and waitPacket() --, and a client that holds no scene
+    // decodes both and re-aims the image itself: decodePacket, decodeDepthPacket, warpDepth.  reuse_gbuffer: as warp()'s
+    int submitDepthPacket(uint32_t sequence, bool reuse_gbuffer = false, float near = 0.1f)
+    {
+        fovpt_packet_depth_config cfg;
+        fovpt_packet_depth_defaults(&cfg);
+        cfg.near = near;
+        fovpt_gbuffer_ptrs g;
+        if (reuse_gbuffer) check(fovpt_temporal_gbuffer(ctx, &g));
+        int slot = -1;
+        check(fovpt_packet_submit_depth(ctx, reinterpret_cast<const fovpt_launch_params*>(&launchParams), &cfg, reuse_gbuffer ? &g : nullptr, sequence, &slot));
+        return slot;
+    }
+    // the device decoder: header on the host, packet and out_depth (the header's width x height floats, +inf the sky) on the
+    // device; needs no scene and no rendered frame; then a device sync like render()
+    void decodeDepthPacket(const fovpt_packet_depth_header& header, const void* packet, float* out_depth)
+    {
+        check(fovpt_packet_decode_depth(ctx, &header, packet, out_depth));
+        check(fovpt_synchronize(ctx));
+    }
+    // fovpt_warp from a decoded depth image and the camera in the depth packet's header to the camera `to`; every buffer is the
+    // caller's, on the device (in_color / out_color may be null where wc leaves the float4 image out); warpCounts() reports it
+    void warpDepth(int width, int height, const float* depth, const fovpt_warp_camera& from, const fovpt_warp_camera& to, const fovpt_warp_config& wc,
+                   const fovpt_float4* in_color, const uint32_t* in_rgba, fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map = nullptr)
+    {
+        check(fovpt_warp_depth(ctx, width, height, &from, &to, &wc, depth, in_color, in_rgba, out_color, out_rgba, out_map));
+        check(fovpt_synchronize(ctx));
+    }
     // ---- animated geometry (new with this library; OptiX's optixAccelBuild with OPERATION_UPDATE over the same build inputs):
     // re-reads model->meshes[i]->vertex of the listed meshes from the Model this renderer was built over and refits the
     // hierarchy on the library's stream (asynchronous: frames rendered afterwards see the new positions), or with rebuild = true

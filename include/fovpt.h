@@ -1136,7 +1136,8 @@ int fovpt_bloom_buffers(fovpt_ctx* ctx, fovpt_float4** color, uint32_t** rgba);
  * interval's difference (no acceleration, and not their reflections and shadows).  Its resolve is fovpt_warp's: a strip that a mesh
  * vacates, if it is wider than fill_radius rings, stays class empty and keeps showing the source pixel -- the mesh's old image (on the
  * wall scene of tests/test_warp_motion_cpu.py already at advance 1 with a move of 8 px).  Resampling: a pixel is copied, not interpolated.  Packets: a packet's texel ownership belongs to the rendered camera, so
- * the warp is the last stage on the server, or a client's job after decoding.
+ * the warp is the last stage on the server, or a client's job after decoding: fovpt_packet_encode_depth sends the depth and the
+ * camera along, fovpt_packet_decode_depth and fovpt_warp_depth are the client's calls (below, "depth packets").
  * On an MI355X at 1920 x 1080, both images, fill_radius 2, a call takes 0.050 .. 0.054 ms with a caller's G-buffer and 0.262 .. 0.265 ms with
  * its own trace over a slide, a turn and a dolly-in (fovpt_expose FIXED, a plain full-frame pass: 0.020 ms; one fovpt_render: 0.70 ms)
  * (DESIGN.md, section 21).  fovpt_warp_motion, same frame, a slide, advance 1, alternated with fovpt_warp in one process: 0.050 ms with
@@ -1707,6 +1708,86 @@ int fovpt_packet_encode_coded(fovpt_ctx* ctx, const fovpt_launch_params* lp, con
 int fovpt_packet_submit_coded(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_config* cfg, const uint32_t* in_rgba,
                               uint32_t sequence, int* slot);
 
+/* ---- depth packets and late reprojection on the client ---------------------------------------------------------------------------
+ * New with this library (the definitions: tests/packet_depth_ref.py, tests/warp_depth_ref.py).  A colour
+ * packet shows the frame at the pose it was rendered for.  A depth packet ("FVPD") carries the frame's depth the way the colour
+ * travels -- one value per launch index -- together with the rendered camera, so that a client which holds no scene decodes both
+ * and re-aims the image itself: fovpt_packet_decode (colour), fovpt_packet_decode_depth, fovpt_warp_depth, fovpt_lens.
+ *   layout    fovpt_packet_depth_header (192 bytes: a fovpt_packet_header with magic "FVPD", version 1 and the pass records of
+ *             the colour packet of the same frame, their eighth word 0; then eye, U, V, W of the rendered camera, `near`, three
+ *             zero words), then per pass gw * gh uint16 codes, row-major ly * gw + lx, and 0 or 2 zero bytes so that the next
+ *             array starts at a multiple of 4; the arrays lie back to back from byte 192.  Little endian.  `bytes` is the whole
+ *             packet, padding included.
+ *   code      of a pixel, from the G-buffer's prim and position.xyz, every *, +, - and / one unfused binary32 operation, M the
+ *             rows of inverse([U V W]) of the rendered camera as fovpt_warp computes them for `to` (binary64, rounded to fp32):
+ *               prim == 0xffffffff: 1 (sky, at infinity).  Else v = X - eye, z = (M_2.x v.x + M_2.y v.y) + M_2.z v.z -- the point
+ *               is eye + z * pixel_ray(x, y): no square root --; !(z > 0) or z not finite: 1; else q = near / z,
+ *               c = floorf(q * 65534.0f + 0.5f) clamped in float to [1, 65534], code = (uint32)c + 1: hits are 2 .. 65535.
+ *             of a texel: 0 where the launch index owns no pixel (ownership: fovpt_packet_encode's), else the LARGEST code of the
+ *             pixels it owns -- the nearest surface, which a disocclusion must not lose; sky only where every owned pixel is sky.
+ *   decode    one mode: a pixel takes the last texel with code != 0 whose block reaches it (the colour decoders' search with
+ *             "code != 0" for "alpha != 0"); out_depth = +inf for code 1, else (near * 65534.0f) / (float)(code - 1); a pixel
+ *             no texel reaches keeps what the output held.
+ *   fovpt_packet_depth_defaults   near 0.1f (a convention, not a measurement): depths below it saturate at code 65535.
+ *   fovpt_packet_describe_depth / _encode_depth / _submit_depth   ordering, validation and error codes of fovpt_packet_encode /
+ *             _submit (a frame rendered whole at lp's size, world == 1, a 4-byte-aligned buffer, written whole and nothing else),
+ *             the same four slots and copy stream (colour, coded and depth submits may alternate; fovpt_packet_wait serves all).
+ *             gbuffer as fovpt_warp takes it: NULL traces into fovpt_gbuffer's buffers and needs the scene (FOVPT_E_NO_SCENE),
+ *             non-NULL is used as given -- only prim and position are read, the size must be the frame's.  Additionally
+ *             FOVPT_E_INVALID for a null cfg, a non-zero reserved word, a `near` that is not finite and above 0, a singular or
+ *             non-finite rendered camera.  k_packet_depth_encode: one thread per texel, a 2-byte store each, no atomics, no LDS.
+ *   fovpt_packet_check_depth / _decode_depth_host   no context, both libraries.  FOVPT_E_INVALID for everything fovpt_packet_check
+ *             rejects with 192 in the place of 128 and an array's end offset + 2 gw gh rounded up to 4 (in 64 bits) above `bytes`;
+ *             a non-zero eighth pass word; a non-finite camera entry; a [U V W] whose determinant is 0 or not finite; `near` not
+ *             finite or not above 0; non-zero words 45 .. 47; an output of another size; null pointers.  fovpt_packet_check,
+ *             fovpt_packet_decode and fovpt_packet_decode_host refuse the magic "FVPD".
+ *   fovpt_packet_decode_depth     device decoder (k_packet_depth_decode, one thread per pixel) on fovpt_stream(): header on the
+ *             host, packet (4-byte aligned) and out_depth (header's width x height floats) on the device.  Needs no rendered frame
+ *             and no scene: a context fresh from fovpt_create does.  The reach limit of fovpt_packet_decode.
+ *   fovpt_warp_depth              fovpt_warp, operation for operation -- the key, the landing test, the depth word, the resolve,
+ *             the classes, the map, the counts, images and fill_radius --, with the source point rebuilt from a depth image and
+ *             the camera `from` it was rendered with; needs no rendered frame and no scene.  Per source pixel s = y * w + x,
+ *             z = depth[s]:  z == +inf: a miss, v = pixel_ray(from; x, y) = (dx U + dy V) + W, dx = 2 ((x + 0.5) / w) - 1, depth
+ *             word 0x7fffffff;  z finite and above 0: r = pixel_ray(from; x, y), X_k = eye_from_k + z * r_k, v = X - eye_to, then
+ *             fovpt_warp's a_k, px, py, fx, fy and key;  anything else (NaN, <= 0, -inf): the pixel scatters nothing.  With
+ *             to == from every pixel with a finite positive or infinite depth lands on itself (tests/test_warp_depth_cpu.py).
+ *             The keys are the context's own for this call (width x height, grown on demand; not fovpt_warp's);
+ *             fovpt_warp_counts reports the last warp of any of the three kinds.  The outputs of enabled images are the caller's.
+ *             FOVPT_E_INVALID: null ctx / from / to / wc / depth; width or height below 1 or width * height >= 2^30; fovpt_warp's
+ *             checks on images, fill_radius and reserved fields, and on `to`, applied to `from` as well; an enabled image with a
+ *             null input or output; any output equal to any input, to depth or to another output.
+ * Out of scope.  Smoothing or predicting depth (a texel is one surface's); a codec for the depth plane; moving meshes
+ * (fovpt_warp_motion needs the server's hit records).
+ * A 1920 x 1080 frame at radii 148 / 482 has 452 660 launch indices: 905 512 bytes of depth beside the colour packet's 1 810 768.
+ * The times of these calls have not been measured on an MI355X yet; tools/packet_perf.py --depth measures them (DESIGN.md,
+ * section 39).                                                                                                                      */
+#define FOVPT_PACKET_MAGIC_DEPTH 0x44505646u   /* "FVPD" */
+#define FOVPT_PACKET_DEPTH_HEADER_BYTES 192
+typedef struct fovpt_packet_depth_config {  /* 16 bytes */
+    float near;                         /* finite, above 0; default 0.1f: depths below it saturate (a convention, not a measurement) */
+    uint32_t _reserved[3];              /* 0 */
+} fovpt_packet_depth_config;
+typedef struct fovpt_packet_depth_header {  /* 192 bytes */
+    fovpt_packet_header base;           /* magic "FVPD"; texels: byte offset of a pass's code array, >= 192 */
+    fovpt_warp_camera camera;           /* the camera the frame was rendered with */
+    float near;
+    uint32_t _reserved[3];              /* 0 */
+} fovpt_packet_depth_header;
+void fovpt_packet_depth_defaults(fovpt_packet_depth_config* cfg);
+int fovpt_packet_describe_depth(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_depth_config* cfg, uint32_t sequence,
+                                fovpt_packet_depth_header* out);
+int fovpt_packet_encode_depth(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_depth_config* cfg,
+                              const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, uint32_t sequence, void* out_packet);
+int fovpt_packet_submit_depth(fovpt_ctx* ctx, const fovpt_launch_params* lp, const fovpt_packet_depth_config* cfg,
+                              const fovpt_gbuffer_ptrs* gbuffer /* NULL: traced by the call */, uint32_t sequence, int* slot);
+int fovpt_packet_check_depth(const void* packet, size_t bytes);
+int fovpt_packet_decode_depth_host(const void* packet, size_t bytes, float* out_depth, int width, int height);
+int fovpt_packet_decode_depth(fovpt_ctx* ctx, const fovpt_packet_depth_header* header /* host */, const void* packet /* device */,
+                              float* out_depth /* device, header's width x height */);
+int fovpt_warp_depth(fovpt_ctx* ctx, int width, int height, const fovpt_warp_camera* from, const fovpt_warp_camera* to,
+                     const fovpt_warp_config* wc, const float* depth, const fovpt_float4* in_color, const uint32_t* in_rgba,
+                     fovpt_float4* out_color, uint32_t* out_rgba, uint32_t* out_map /* may be NULL */);
+
 /* ---- multi-GPU: packed gather of the final framebuffer ----------------------------------
  * New with this library: the reference is single-GPU (SimplePathtracer.cpp:331-340).  With
  * fovpt_config.rank/world every handle renders the launch-index tiles it owns -- interleaved
@@ -2106,6 +2187,9 @@ static_assert(sizeof(fovpt_morph_target) == 24 && offsetof(fovpt_morph_target, i
 static_assert(sizeof(fovpt_mesh_morph) == 24 && offsetof(fovpt_mesh_morph, targets) == 16, "mesh morph ABI");
 static_assert(sizeof(fovpt_morph_pose) == 32 && offsetof(fovpt_morph_pose, weights) == 8 && offsetof(fovpt_morph_pose, num_joints) == 16 &&
               offsetof(fovpt_morph_pose, matrices) == 24, "morph pose ABI");
+static_assert(sizeof(fovpt_packet_depth_config) == 16 && offsetof(fovpt_packet_depth_config, _reserved) == 4, "depth packet config ABI");
+static_assert(sizeof(fovpt_packet_depth_header) == 192 && offsetof(fovpt_packet_depth_header, camera) == 128 &&
+              offsetof(fovpt_packet_depth_header, near) == 176 && offsetof(fovpt_packet_depth_header, _reserved) == 180, "depth packet header ABI");
 static_assert(offsetof(fovpt_launch_params, camera) == 104, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, traversable) == 160, "LaunchParams ABI");
 static_assert(offsetof(fovpt_launch_params, probe) == 168, "LaunchParams ABI");

@@ -14,7 +14,13 @@ for x = fovpt_post's rgba8 output.  Kernel statistics are a separate run:
 --coded measures coded packets ("FVPC") instead: the legs RENDER, PACKET, and render +
 fovpt_packet_submit_coded with P and M as BC1 (CODED_110) and with all three levels as BC1 (CODED_111); k_packet_encode_coded and
 the CODED decoders beside the raw kernels; the bytes per frame; and the RMSE per level of the decoded coded packet against
-fovpt_post's output and against the decoded raw packet."""
+fovpt_post's output and against the decoded raw packet.
+--depth measures depth packets ("FVPD") and the client's warp: the legs RENDER, PACKET (a colour submit per
+frame) and a colour and a depth submit per frame with the call's own G-buffer trace (PACKET_DEPTH_TRACE) and with a caller's
+G-buffer (PACKET_DEPTH_G); k_packet_depth_encode with a caller's G-buffer and with its own trace beside k_packet_encode;
+k_packet_depth_decode beside NEAREST; fovpt_warp_depth beside fovpt_warp with a caller's G-buffer (a slide); the bytes; and for a
+slide, a turn and a dolly-in the share of destination pixels whose source differs from the server's fovpt_warp, with both calls'
+classes."""
 import argparse
 import json
 import os
@@ -170,6 +176,97 @@ def main_coded(frames, warmup, calls, reps):
     r.close()
 
 
+def main_depth(frames, warmup, calls, reps):
+    size = (1920, 1080)
+    n = size[0] * size[1]
+    r = scene(size)
+    per_frame, per_call = timers(r, frames, warmup, calls)
+    g = r.gbuffer()                                              # the rendered frame's: the camera does not move below
+    r.synchronize()
+    hc, hd = r.describePacket(), r.describeDepthPacket()
+
+    def leg_render(k_frames):
+        for _ in range(k_frames):
+            r.render_async()
+
+    def leg_submits(depth, gbuffer):
+        def run(k_frames):
+            slots = []
+            for k in range(k_frames):
+                r.render_async()
+                mine = [r.submitPacket(k)]
+                if depth:
+                    mine.append(r.submitDepthPacket(k, gbuffer))
+                slots.append(mine)
+                if k >= 1:                                        # (four slots: a frame's two packets are waited for one frame later)
+                    for s in slots[k - 1]:
+                        r.waitPacket(s)
+            for s in slots[-1]:
+                r.waitPacket(s)
+        return run
+
+    legs = dict(RENDER=leg_render, PACKET=leg_submits(False, None), PACKET_DEPTH_TRACE=leg_submits(True, None), PACKET_DEPTH_G=leg_submits(True, g))
+    dc = torch.empty(hc.bytes, dtype=torch.uint8, device="cuda")
+    dd = torch.empty(hd.base.bytes, dtype=torch.uint8, device="cuda")
+    rgba = torch.zeros((size[1], size[0]), dtype=torch.int32, device="cuda")
+    depth = torch.zeros((size[1], size[0]), dtype=torch.float32, device="cuda")
+    outs = [torch.zeros((size[1], size[0], c), dtype=torch.int32, device="cuda") for c in (4, 1, 1)]
+    torch.cuda.synchronize()
+    r.encodePacket(dc.data_ptr())
+    r.encodeDepthPacket(dd.data_ptr(), 0, g)
+    r.decodePacket(hc, dc.data_ptr(), rgba.data_ptr(), abi.PACKET_NEAREST)
+    r.decodeDepthPacket(hd, dd.data_ptr(), depth.data_ptr())
+    r.synchronize()
+    cam = scenes.ATRIUM_CAMERA
+    (ex, ey, ez), (lx, ly, lz) = cam["eye"], cam["lookat"]
+    motions = dict(slide=((ex, ey, ez + 20.0), (lx, ly, lz + 20.0)), turn=((ex, ey, ez), (lx, ly, lz + 150.0)), dolly_in=((ex + 100.0, ey, ez), (lx, ly, lz)))
+    tos = {k: r.warp_camera(renderer.Camera(e, l, cam["up"], cam["fovy"], size[0] / size[1])) for k, (e, l) in motions.items()}
+    accum, frame = r.launchParams.frame.accum_buffer, r.launchParams.frame.frame_buffer
+    kernels = dict(ENCODE=lambda: r.encodePacket(dc.data_ptr()),
+                   ENCODE_DEPTH_G=lambda: r.encodeDepthPacket(dd.data_ptr(), 0, g),
+                   ENCODE_DEPTH_TRACE=lambda: r.encodeDepthPacket(dd.data_ptr(), 0),
+                   NEAREST=lambda: r.decodePacket(hc, dc.data_ptr(), rgba.data_ptr(), abi.PACKET_NEAREST),
+                   DECODE_DEPTH=lambda: r.decodeDepthPacket(hd, dd.data_ptr(), depth.data_ptr()),
+                   WARP_G=lambda: r.warp(tos["slide"], None, g, None, None, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr()),
+                   WARP_DEPTH=lambda: r.warp_depth(size, depth.data_ptr(), hd.camera, tos["slide"], None, accum, frame, outs[0].data_ptr(),
+                                                   outs[1].data_ptr(), outs[2].data_ptr()))
+    ms = {k: [] for k in list(legs) + list(kernels)}
+    for _ in range(reps):                                         # alternately
+        for k, fn in legs.items():
+            ms[k].append(per_frame(fn))
+        for k, fn in kernels.items():
+            ms[k].append(per_call(fn))
+    res = dict(config="C3", depth=True, size=list(size), frames_in_flight=2, frames=frames, calls=calls, reps=reps, device=torch.cuda.get_device_name(0))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    for k, v in ms.items():
+        res["ms_" + k] = round(med[k], 4)
+        res["spread_" + k] = [round(min(v), 4), round(max(v), 4)]
+    for k in ("PACKET", "PACKET_DEPTH_TRACE", "PACKET_DEPTH_G"):
+        res[k + "_minus_RENDER"] = round(med[k] - med["RENDER"], 4)
+    res["bytes_colour"], res["bytes_depth"], res["bytes_frame"] = int(hc.bytes), int(hd.base.bytes), n * 4
+
+    # what the client's warp shows against the server's: per motion the share of destination pixels whose source differs, and the classes
+    r.render()
+    r.encodeDepthPacket(dd.data_ptr(), 0)
+    r.decodeDepthPacket(hd, dd.data_ptr(), depth.data_ptr())
+    g = r.gbuffer()
+    agree = {}
+    for name, to in tos.items():
+        maps, shares = [], []
+        for client in (False, True):
+            if client:
+                r.warp_depth(size, depth.data_ptr(), hd.camera, to, None, accum, frame, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr())
+            else:
+                r.warp(to, None, g, None, None, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr())
+            c = r.warp_counts()
+            shares.append(dict(direct=round(c.direct / n, 4), filled=round(c.filled / n, 4), empty=round(c.empty / n, 4)))
+            maps.append(outs[2].cpu().numpy().view(np.uint32).reshape(-1).copy())
+        agree[name] = dict(source_differs=round(float(((maps[0] & 0x3fffffff) != (maps[1] & 0x3fffffff)).mean()), 4), server=shares[0], client=shares[1])
+    res["warp"] = agree
+    print(json.dumps(res), flush=True)
+    r.close()
+
+
 def main(frames, warmup, calls, reps):
     size = (1920, 1080)
     r = scene(size)
@@ -252,5 +349,6 @@ if __name__ == "__main__":
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--coded", action="store_true", help="coded packets (BC1 levels) beside raw ones")
+    ap.add_argument("--depth", action="store_true", help="depth packets and the client's warp beside the colour packet and fovpt_warp")
     args = ap.parse_args()
-    (main_coded if args.coded else main)(args.frames, args.warmup, args.calls, args.reps)
+    (main_depth if args.depth else main_coded if args.coded else main)(args.frames, args.warmup, args.calls, args.reps)
