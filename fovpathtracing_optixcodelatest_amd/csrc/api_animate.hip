@@ -2,7 +2,10 @@
 // fovpt_update_transforms, fovpt_set_skins / fovpt_update_skinned, fovpt_set_morphs / fovpt_update_morphed, fovpt_set_rig /
 // fovpt_update_animated (kernel: rig.hip).
 //
-// Every entry point validates all of its arguments first (all or nothing; Listed is the part they share).  An update is then
+// Every entry point validates all of its arguments first (all or nothing; Listed is the part they share).  What fovpt_set_skins,
+// fovpt_set_morphs and fovpt_set_rig accept and how they lay their data out, and the overflow rules of the update calls, are
+// fovpt_animplan.h's: pure host functions of the caller's description and an AnimScene, tested without a GPU.  This file keeps what
+// needs a context or a device: the set-up calls reserve, upload and commit an accepted plan (replace_buffers).  An update is then
 // three steps on fovpt_stream(), the stream every job's resolve, and so every job's last traversal launch, is ordered on:
 // begin_update (what has to happen ahead of any new position), the source's own write_* (the new positions into up_vtx) and
 // finish_update (the refit, with the event the next job waits for, or the rebuild).  A new source is a new write_*.
@@ -15,6 +18,23 @@
 #include "fovpt_ctx.h"
 
 namespace {
+
+// A refused plan or overflow check of fovpt_animplan.h: its code and its text to the context
+int refused(fovpt_ctx* c, const AnimVerdict& V) { return fail(c, V.code, "%s", V.text.c_str()); }
+
+// What the plan functions read of the scene and of the skins and morphs it has now
+AnimScene anim_scene(const fovpt_ctx* c)
+{
+    AnimScene sc;
+    sc.mesh.resize(c->mesh_nv.size());
+    for (size_t m = 0; m < sc.mesh.size(); m++) {
+        AnimMesh& M = sc.mesh[m];
+        M.nv = c->mesh_nv[m];
+        if (!c->skins.empty()) { M.skin_joints = c->skins[m].num_joints; M.pal_first = c->skins[m].pal_first; }
+        if (!c->morphs.empty()) { M.morph_targets = c->morphs[m].num_targets; M.morph_entries = c->morphs[m].ent.size(); M.w_first = c->morphs[m].w_first; }
+    }
+    return sc;
+}
 
 // What the entry points check first, in this order: open() the context, the scene, the count and the array (`what`: the
 // caller's word for its entries) and the flags (flag_text: the caller's wording); then mesh(), entry by entry between the
@@ -38,10 +58,8 @@ struct Listed {
     }
     int check(int m)
     {
-        if (m < 0 || m >= nmesh) return fail(c, FOVPT_E_INVALID, "%s: mesh %d of %d", who, m, nmesh);
-        if (seen[m]) return fail(c, FOVPT_E_INVALID, "%s: mesh %d is listed twice", who, m);
-        seen[m] = 1;
-        return FOVPT_OK;
+        AnimVerdict V;
+        return anim_list_mesh(V, seen, who, m) ? refused(c, V) : FOVPT_OK;
     }
     int mesh(int m) { CHK(check(m)); meshes.push_back(m); return FOVPT_OK; }      // (at most nmesh entries: none is listed twice)
 };
@@ -64,25 +82,6 @@ void ensure_absmax(fovpt_ctx* c)
         const float* v = c->h_vtx.data() + 3 * (size_t)c->mesh_vbase[m];
         for (size_t i = 0; i < 3 * (size_t)c->mesh_nv[m]; i++) c->mesh_absmax[m] = std::fmax(c->mesh_absmax[m], std::fabs((double)v[i]));
     }
-}
-
-// The overflow rules of a host palette (fovpt_update_skinned, fovpt_update_morphed), which keep every intermediate value of the
-// skinning expression finite: S the skin's largest weight sum, B a bound of the |coordinates| that go through the matrices.
-// (Not fovpt_update_transforms' rule: one matrix is not blended, so that rule has no second part.)
-int check_palette(fovpt_ctx* c, const char* who, int mesh, const float* matrices, uint32_t num_joints, double S, double B)
-{
-    for (size_t i = 0; i < 12 * (size_t)num_joints; i++)
-        if (!std::isfinite(matrices[i])) return fail(c, FOVPT_E_INVALID, "%s: mesh %d joint %zu entry %zu is not finite", who, mesh, i / 12, i % 12);
-    for (size_t r = 0; r < 3 * (size_t)num_joints; r++) {
-        const float* row = matrices + 4 * r;
-        const double bound = S * ((std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * B + std::fabs((double)row[3]));
-        if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "%s: mesh %d joint %zu row %zu could overflow (bound %g > 2^127)", who, mesh, r / 3, r % 3, bound);
-        // (the blended matrix is formed first: its entries are within S times the palette's, which the row's bound covers
-        // for the fourth column and, for the others, only when B >= 1)
-        const double entry = S * std::fmax(std::fmax(std::fabs((double)row[0]), std::fabs((double)row[1])), std::fabs((double)row[2]));
-        if (entry > 0x1p127) return fail(c, FOVPT_E_INVALID, "%s: mesh %d joint %zu row %zu: a blended entry could overflow (%g > 2^127)", who, mesh, r / 3, r % 3, entry);
-    }
-    return FOVPT_OK;
 }
 
 // One of refit.hip's batch structs (up to FOVPT_GATHER_BATCH meshes per launch) and what launches it.  put(): a new entry of n
@@ -608,20 +607,23 @@ void drop_rig(fovpt_ctx* c)
     c->rig.dev = RigDev{};
 }
 
-// the squared norm of a quaternion in binary64, as fovpt_set_rig's rule reads it
-bool rig_norm_ok(const float* q)
+// How fovpt_set_skins, fovpt_set_morphs and fovpt_set_rig end once their plan is accepted.  The new device buffers (bytes[i] 0: none)
+// are there before anything changes; `before` uploads what needs nothing of the context; then the wait for an update in flight,
+// which reads the buffers about to go; the rig goes (its counts were checked against the skins and morphs about to change);
+// `commit` moves the host state in and uploads from it; and the new buffers take the place of the old.
+template <int N, class Before, class Commit>
+int replace_buffers(fovpt_ctx* c, DevBuf* const (&live)[N], const size_t (&bytes)[N], Before before, Commit commit)
 {
-    const double n2 = (((double)q[0] * (double)q[0] + (double)q[1] * (double)q[1]) + (double)q[2] * (double)q[2]) + (double)q[3] * (double)q[3];
-    return n2 >= 0.25 && n2 <= 4.0;
-}
-
-// one section of the rig's device allocation: appended to `blob` at a 16-byte boundary, its offset returned
-template <class T> size_t rig_place(std::vector<char>& blob, const std::vector<T>& v)
-{
-    const size_t at = (blob.size() + 15) & ~(size_t)15;
-    blob.resize(at + sizeof(T) * v.size());
-    if (!v.empty()) memcpy(blob.data() + at, v.data(), sizeof(T) * v.size());
-    return at;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf fresh[N];
+    for (int i = 0; i < N; i++)
+        if (bytes[i]) HIPCHK(c, fresh[i].reserve(bytes[i]));
+    CHK(before(fresh));
+    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));
+    drop_rig(c);
+    CHK(commit(fresh));
+    for (int i = 0; i < N; i++) live[i]->swap(fresh[i]);
+    return FOVPT_OK;
 }
 
 }  // namespace
@@ -690,86 +692,42 @@ int fovpt_update_transforms(fovpt_ctx* c, const fovpt_mesh_transform* tf, int nu
     for (int k = 0; k < num; k++) {
         const fovpt_mesh_transform& T = tf[k];
         CHK(L.mesh(T.mesh));
-        for (int i = 0; i < 12; i++)
-            if (!std::isfinite(T.m[i])) return fail(c, FOVPT_E_INVALID, "%s: mesh %d matrix entry %d is not finite", who, T.mesh, i);
-        for (int r = 0; r < 3; r++) {
-            const float* row = T.m + 4 * r;
-            const double bound = (std::fabs((double)row[0]) + std::fabs((double)row[1]) + std::fabs((double)row[2])) * c->mesh_absmax[T.mesh] + std::fabs((double)row[3]);
-            if (bound > 0x1p127) return fail(c, FOVPT_E_INVALID, "%s: mesh %d row %d could overflow (bound %g > 2^127)", who, T.mesh, r, bound);
-        }
+        AnimVerdict V;
+        if (anim_check_transform(V, who, T.mesh, T.m, c->mesh_absmax[T.mesh])) return refused(c, V);
     }
     return update(L, flags, tf != nullptr, [&] { return write_transforms(c, tf, num); });
 }
 
-// The skins are kept on the host per mesh; every call lays the device copies out anew (the skinned meshes' vertices and joints
-// in mesh order), so a mesh's places in skin_joints / skin_weights / skin_pal are fixed until the next call.
+// The skins are kept on the host per mesh; every call lays the device copies out anew (plan_skins), so a mesh's places in
+// skin_joints / skin_weights / skin_pal are fixed until the next call.
 int fovpt_set_skins(fovpt_ctx* c, const fovpt_mesh_skin* skins, int num)
 {
     const char* who = "fovpt_set_skins";
     Listed L;
     CHK(L.open(c, who, num, skins, "skins"));
-    const int nmesh = L.nmesh;
-    std::vector<double> sums((size_t)(num > 0 ? num : 0), 0.0);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_skin& K = skins[k];
-        CHK(L.check(K.mesh));
-        if (K._reserved) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: _reserved is %u", who, K.mesh, K._reserved);
-        if (K.num_vertices != c->mesh_nv[K.mesh])
-            return fail(c, FOVPT_E_INVALID, "%s: mesh %d has %u vertices, not %u", who, K.mesh, c->mesh_nv[K.mesh], K.num_vertices);
-        if (K.num_joints > FOVPT_SKIN_MAX_JOINTS) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: %u joints (at most %d)", who, K.mesh, K.num_joints, FOVPT_SKIN_MAX_JOINTS);
-        if (K.num_joints == 0) {
-            if (K.joints || K.weights) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: no joints, but a pointer (removing a skin takes two null pointers)", who, K.mesh);
-            continue;
-        }
-        if (!K.joints || !K.weights) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: null joints or weights", who, K.mesh);
-        for (size_t i = 0; i < 4 * (size_t)K.num_vertices; i++) {
-            if (K.joints[i] >= K.num_joints) return fail(c, FOVPT_E_INVALID, "%s: mesh %d vertex %zu: joint %u of %u", who, K.mesh, i / 4, (unsigned)K.joints[i], K.num_joints);
-            if (!(K.weights[i] >= 0.0f && K.weights[i] <= 1.0f)) return fail(c, FOVPT_E_INVALID, "%s: mesh %d vertex %zu: weight %g is not in [0, 1]", who, K.mesh, i / 4, (double)K.weights[i]);
-        }
-        for (size_t i = 0; i < (size_t)K.num_vertices; i++) {
-            const float* w = K.weights + 4 * i;
-            sums[k] = std::fmax(sums[k], (((double)w[0] + (double)w[1]) + (double)w[2]) + (double)w[3]);
-        }
-    }
+    SkinPlan P;
+    if (plan_skins(anim_scene(c), who, skins, num, P)) return refused(c, P);
     if (num == 0) return FOVPT_OK;
-    // the new layout, and its device buffers before anything changes
-    std::vector<uint32_t> nj((size_t)nmesh, 0);
-    for (int m = 0; m < nmesh; m++) nj[m] = c->skins.empty() ? 0 : c->skins[m].num_joints;
-    for (int k = 0; k < num; k++) nj[skins[k].mesh] = skins[k].num_joints;
-    size_t verts = 0, joints = 0;
-    for (int m = 0; m < nmesh; m++)
-        if (nj[m]) { verts += c->mesh_nv[m]; joints += nj[m]; }
-    if (verts >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "%s: more than 2^32 - 1 skinned vertices", who);
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf d_joints, d_weights, d_pal;
-    if (joints) {
-        HIPCHK(c, d_joints.reserve(verts ? verts * 8 : 8));
-        HIPCHK(c, d_weights.reserve(verts ? verts * 16 : 16));
-        HIPCHK(c, d_pal.reserve(joints * 48));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_skinned in flight reads the buffers about to go
-    drop_rig(c);                                           // its joint counts were checked against the skins about to change
-    if (c->skins.empty()) c->skins.resize((size_t)nmesh);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_skin& K = skins[k];
-        fovpt_ctx::Skin& D = c->skins[K.mesh];
-        D.num_joints = K.num_joints; D.S = sums[k];
-        if (K.num_joints) { D.joints.assign(K.joints, K.joints + 4 * (size_t)K.num_vertices); D.weights.assign(K.weights, K.weights + 4 * (size_t)K.num_vertices); }
-        else { std::vector<uint16_t>().swap(D.joints); std::vector<float>().swap(D.weights); }
-    }
-    uint32_t first = 0, pal_first = 0;
-    for (int m = 0; m < nmesh; m++) {
-        fovpt_ctx::Skin& D = c->skins[m];
-        D.first = first; D.pal_first = pal_first;
-        if (!D.num_joints) continue;
-        if (c->mesh_nv[m]) {
-            HIPCHK(c, hipMemcpy((char*)d_joints.p + 8 * (size_t)first, D.joints.data(), 8 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy((char*)d_weights.p + 16 * (size_t)first, D.weights.data(), 16 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
+    DevBuf* const live[3] = {&c->skin_joints, &c->skin_weights, &c->skin_pal};
+    const size_t bytes[3] = {P.joints_bytes, P.weights_bytes, P.pal_bytes};
+    return replace_buffers(c, live, bytes, [](DevBuf*) { return FOVPT_OK; }, [&](DevBuf* fresh) {
+        if (c->skins.empty()) c->skins.resize((size_t)L.nmesh);
+        for (int k = 0; k < num; k++) {
+            const fovpt_mesh_skin& K = skins[k];
+            fovpt_ctx::Skin& D = c->skins[K.mesh];
+            D.num_joints = K.num_joints; D.S = P.S[k];
+            if (K.num_joints) { D.joints.assign(K.joints, K.joints + 4 * (size_t)K.num_vertices); D.weights.assign(K.weights, K.weights + 4 * (size_t)K.num_vertices); }
+            else { std::vector<uint16_t>().swap(D.joints); std::vector<float>().swap(D.weights); }
         }
-        first += c->mesh_nv[m]; pal_first += D.num_joints;
-    }
-    c->skin_joints.swap(d_joints); c->skin_weights.swap(d_weights); c->skin_pal.swap(d_pal);
-    return FOVPT_OK;
+        for (int m = 0; m < L.nmesh; m++) {
+            fovpt_ctx::Skin& D = c->skins[m];
+            D.first = P.first[m]; D.pal_first = P.pal_first[m];
+            if (!D.num_joints || !c->mesh_nv[m]) continue;
+            HIPCHK(c, hipMemcpy((char*)fresh[0].p + 8 * (size_t)D.first, D.joints.data(), 8 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy((char*)fresh[1].p + 16 * (size_t)D.first, D.weights.data(), 16 * (size_t)c->mesh_nv[m], hipMemcpyHostToDevice));
+        }
+        return FOVPT_OK;
+    });
 }
 
 // For host palettes the overflow rules keep every intermediate value finite, as fovpt_update_transforms' does.
@@ -789,116 +747,43 @@ int fovpt_update_skinned(fovpt_ctx* c, const fovpt_skin_pose* poses, int num, in
         if (P.num_joints != K.num_joints) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: %u joints, its skin has %u", who, P.mesh, P.num_joints, K.num_joints);
         if (!P.matrices) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: null matrices", who, P.mesh);
         floats += 12 * (size_t)P.num_joints;
-        if (!device) CHK(check_palette(c, who, P.mesh, P.matrices, P.num_joints, K.S, c->mesh_absmax[P.mesh]));
+        AnimVerdict V;
+        if (!device && anim_check_palette(V, who, P.mesh, P.matrices, P.num_joints, K.S, c->mesh_absmax[P.mesh])) return refused(c, V);
     }
     return update(L, flags, poses != nullptr, [&] { return write_skinned(c, poses, num, device, floats); });
 }
 
-// The morph targets are kept on the host per mesh, transposed into a per-vertex list of {delta, target} records sorted by
-// target (what the kernel walks: the order of the definition is the order in memory, and one launch does a whole pose; a pass per
-// active target would need ordering between passes).  Every call lays the device copies out anew (the morphed meshes' offsets,
-// entries and weights in mesh order), so a mesh's places in morph_off / morph_ent / morph_w are fixed until the next call.
+// The morph targets are kept on the host per mesh, transposed into a per-vertex list (plan_morphs; one launch does a whole pose: a
+// pass per active target would need ordering between passes).  Every call lays the device copies out anew, so a mesh's places
+// in morph_off / morph_ent / morph_w are fixed until the next call.
 int fovpt_set_morphs(fovpt_ctx* c, const fovpt_mesh_morph* morphs, int num)
 {
     const char* who = "fovpt_set_morphs";
     Listed L;
     CHK(L.open(c, who, num, morphs, "morphs"));
-    const int nmesh = L.nmesh;
-    std::vector<size_t> entries((size_t)(num > 0 ? num : 0), 0);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_morph& K = morphs[k];
-        CHK(L.check(K.mesh));
-        if (K._reserved) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: _reserved is %u", who, K.mesh, K._reserved);
-        const uint32_t nv = c->mesh_nv[K.mesh];
-        if (K.num_vertices != nv) return fail(c, FOVPT_E_INVALID, "%s: mesh %d has %u vertices, not %u", who, K.mesh, nv, K.num_vertices);
-        if (K.num_targets > FOVPT_MORPH_MAX_TARGETS) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: %u targets (at most %d)", who, K.mesh, K.num_targets, FOVPT_MORPH_MAX_TARGETS);
-        if (K.num_targets == 0) {
-            if (K.targets) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: no targets, but a pointer (removing morphs takes a null pointer)", who, K.mesh);
-            continue;
-        }
-        if (!K.targets) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: null targets", who, K.mesh);
-        for (uint32_t t = 0; t < K.num_targets; t++) {
-            const fovpt_morph_target& T = K.targets[t];
-            if (T._reserved) return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u: _reserved is %u", who, K.mesh, t, T._reserved);
-            if (T.count > nv) return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u: %u entries for %u vertices", who, K.mesh, t, T.count, nv);
-            if (!T.index && T.count != 0 && T.count != nv)
-                return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u: no indices, but %u entries for %u vertices", who, K.mesh, t, T.count, nv);
-            if (!T.delta && T.count) return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u: null delta", who, K.mesh, t);
-            entries[k] += T.count;
-        }
-    }
+    MorphPlan P;
+    if (plan_morphs(anim_scene(c), who, morphs, num, P)) return refused(c, P);
     if (num == 0) return FOVPT_OK;
-    // the new layout (its size is known from the counts alone: checked before the entries themselves are read)
-    std::vector<uint32_t> nt((size_t)nmesh, 0);
-    std::vector<size_t> ne((size_t)nmesh, 0);
-    for (int m = 0; m < nmesh && !c->morphs.empty(); m++) { nt[m] = c->morphs[m].num_targets; ne[m] = c->morphs[m].ent.size(); }
-    for (int k = 0; k < num; k++) { nt[morphs[k].mesh] = morphs[k].num_targets; ne[morphs[k].mesh] = entries[k]; }
-    size_t offs = 0, ents = 0, targets = 0;
-    for (int m = 0; m < nmesh; m++)
-        if (nt[m]) { offs += (size_t)c->mesh_nv[m] + 1; ents += ne[m]; targets += nt[m]; }
-    if (ents >= (1ull << 32) || offs >= (1ull << 32)) return fail(c, FOVPT_E_INVALID, "%s: more than 2^32 - 1 entries (%zu) or offsets (%zu)", who, ents, offs);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_morph& K = morphs[k];
-        for (uint32_t t = 0; t < K.num_targets; t++) {
-            const fovpt_morph_target& T = K.targets[t];
-            for (uint32_t i = 0; T.index && i < T.count; i++) {
-                if (T.index[i] >= K.num_vertices) return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u entry %u: vertex %u of %u", who, K.mesh, t, i, T.index[i], K.num_vertices);
-                if (i && T.index[i] <= T.index[i - 1]) return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u entry %u: indices are not strictly ascending", who, K.mesh, t, i);
-            }
-            for (size_t i = 0; i < 3 * (size_t)T.count; i++)
-                if (!std::isfinite(T.delta[i])) return fail(c, FOVPT_E_INVALID, "%s: mesh %d target %u entry %zu: a delta is not finite", who, K.mesh, t, i / 3);
+    DevBuf* const live[3] = {&c->morph_off, &c->morph_ent, &c->morph_w};
+    const size_t bytes[3] = {P.off_bytes, P.ent_bytes, P.w_bytes};
+    return replace_buffers(c, live, bytes, [](DevBuf*) { return FOVPT_OK; }, [&](DevBuf* fresh) {
+        if (c->morphs.empty()) c->morphs.resize((size_t)L.nmesh);
+        for (int k = 0; k < num; k++) {
+            fovpt_ctx::Morph& D = c->morphs[morphs[k].mesh];
+            D.D = std::move(P.listed[k].D); D.off = std::move(P.listed[k].off); D.ent = std::move(P.listed[k].ent);
         }
-    }
-    // the named meshes' targets, transposed: a count per vertex, its running sum, then the targets in ascending order
-    std::vector<fovpt_ctx::Morph> fresh((size_t)num);
-    for (int k = 0; k < num; k++) {
-        const fovpt_mesh_morph& K = morphs[k];
-        fovpt_ctx::Morph& D = fresh[k];
-        D.num_targets = K.num_targets;
-        if (!K.num_targets) continue;
-        const uint32_t nv = K.num_vertices;
-        D.D.assign(K.num_targets, 0.0);
-        D.off.assign((size_t)nv + 1, 0);
-        for (uint32_t t = 0; t < K.num_targets; t++)
-            for (uint32_t i = 0; i < K.targets[t].count; i++) D.off[(K.targets[t].index ? K.targets[t].index[i] : i) + 1]++;
-        for (uint32_t i = 0; i < nv; i++) D.off[i + 1] += D.off[i];
-        D.ent.resize(entries[k]);
-        std::vector<uint32_t> fill(D.off.begin(), D.off.end() - 1);
-        for (uint32_t t = 0; t < K.num_targets; t++) {
-            const fovpt_morph_target& T = K.targets[t];
-            for (uint32_t i = 0; i < T.count; i++) {
-                const float* d = T.delta + 3 * (size_t)i;
-                D.ent[fill[T.index ? T.index[i] : i]++] = MorphEntry{d[0], d[1], d[2], t};
-                D.D[t] = std::fmax(D.D[t], std::fmax(std::fabs((double)d[0]), std::fmax(std::fabs((double)d[1]), std::fabs((double)d[2]))));
-            }
+        std::vector<uint32_t> abs_off;
+        for (int m = 0; m < L.nmesh; m++) {
+            fovpt_ctx::Morph& D = c->morphs[m];
+            D.num_targets = P.num_targets[m]; D.off_first = P.off_first[m]; D.ent_first = P.ent_first[m]; D.w_first = P.w_first[m];
+            if (!D.num_targets) continue;
+            abs_off.resize(D.off.size());
+            for (size_t i = 0; i < D.off.size(); i++) abs_off[i] = D.ent_first + D.off[i];
+            HIPCHK(c, hipMemcpy((uint32_t*)fresh[0].p + D.off_first, abs_off.data(), 4 * abs_off.size(), hipMemcpyHostToDevice));
+            if (!D.ent.empty()) HIPCHK(c, hipMemcpy((MorphEntry*)fresh[1].p + D.ent_first, D.ent.data(), 16 * D.ent.size(), hipMemcpyHostToDevice));
         }
-    }
-    // the device buffers before anything changes
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf d_off, d_ent, d_w;
-    if (targets) {
-        HIPCHK(c, d_off.reserve(offs * 4));
-        HIPCHK(c, d_ent.reserve(ents ? ents * 16 : 16));
-        HIPCHK(c, d_w.reserve(targets * 4));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_morphed in flight reads the buffers about to go
-    drop_rig(c);                                           // its target counts were checked against the morphs about to change
-    if (c->morphs.empty()) c->morphs.resize((size_t)nmesh);
-    for (int k = 0; k < num; k++) c->morphs[morphs[k].mesh] = std::move(fresh[k]);
-    uint32_t off_first = 0, ent_first = 0, w_first = 0;
-    std::vector<uint32_t> abs_off;
-    for (int m = 0; m < nmesh; m++) {
-        fovpt_ctx::Morph& D = c->morphs[m];
-        D.off_first = off_first; D.ent_first = ent_first; D.w_first = w_first;
-        if (!D.num_targets) continue;
-        abs_off.resize(D.off.size());
-        for (size_t i = 0; i < D.off.size(); i++) abs_off[i] = ent_first + D.off[i];
-        HIPCHK(c, hipMemcpy((uint32_t*)d_off.p + off_first, abs_off.data(), 4 * abs_off.size(), hipMemcpyHostToDevice));
-        if (!D.ent.empty()) HIPCHK(c, hipMemcpy((MorphEntry*)d_ent.p + ent_first, D.ent.data(), 16 * D.ent.size(), hipMemcpyHostToDevice));
-        off_first += (uint32_t)D.off.size(); ent_first += (uint32_t)D.ent.size(); w_first += D.num_targets;
-    }
-    c->morph_off.swap(d_off); c->morph_ent.swap(d_ent); c->morph_w.swap(d_w);
-    return FOVPT_OK;
+        return FOVPT_OK;
+    });
 }
 
 // For host data the overflow rules keep every intermediate value finite.
@@ -928,19 +813,15 @@ int fovpt_update_morphed(fovpt_ctx* c, const fovpt_morph_pose* poses, int num, i
         }
         floats += (size_t)P.num_targets + 12 * (size_t)P.num_joints;
         if (device) continue;
-        double B = c->mesh_absmax[P.mesh];      // the morphed positions' bound
-        for (uint32_t t = 0; t < P.num_targets; t++) {
-            if (!std::isfinite(P.weights[t])) return fail(c, FOVPT_E_INVALID, "%s: mesh %d: weight %u is not finite", who, P.mesh, t);
-            B += std::fabs((double)P.weights[t]) * M.D[t];
-        }
-        if (B > 0x1p127) return fail(c, FOVPT_E_INVALID, "%s: mesh %d could overflow (bound %g > 2^127)", who, P.mesh, B);
-        if (K) CHK(check_palette(c, who, P.mesh, P.matrices, P.num_joints, K->S, B));
+        AnimVerdict V;
+        double B;      // the morphed positions' bound
+        if (anim_check_weights(V, who, P.mesh, P.weights, P.num_targets, M.D.data(), c->mesh_absmax[P.mesh], &B)) return refused(c, V);
+        if (K && anim_check_palette(V, who, P.mesh, P.matrices, P.num_joints, K->S, B)) return refused(c, V);
     }
     return update(L, flags, poses != nullptr, [&] { return write_morphed(c, poses, num, device, floats); });
 }
 
-// Validated in the order of the description: the counts, the nodes, the bindings, then clip by clip the channels.  Then the
-// device copy is laid out and uploaded whole before the previous rig goes.
+// The rules and the layout are plan_rig's.  The device copy is uploaded whole before the previous rig goes.
 int fovpt_set_rig(fovpt_ctx* c, const fovpt_rig_desc* rig)
 {
     const char* who = "fovpt_set_rig";
@@ -953,161 +834,32 @@ int fovpt_set_rig(fovpt_ctx* c, const fovpt_rig_desc* rig)
         drop_rig(c);
         return FOVPT_OK;
     }
-    const int nmesh = (int)c->mesh_nv.size();
-    const uint32_t nn = rig->num_nodes;
-    if (rig->_reserved0 || rig->_reserved1 || rig->_reserved2) return fail(c, FOVPT_E_INVALID, "%s: a reserved field is not 0", who);
-    if (nn == 0 || nn > FOVPT_RIG_MAX_NODES) return fail(c, FOVPT_E_INVALID, "%s: %u nodes (1 .. %d)", who, nn, FOVPT_RIG_MAX_NODES);
-    if (rig->num_clips > FOVPT_RIG_MAX_CLIPS) return fail(c, FOVPT_E_INVALID, "%s: %u clips (at most %d)", who, rig->num_clips, FOVPT_RIG_MAX_CLIPS);
-    if (rig->num_bindings > (uint32_t)nmesh) return fail(c, FOVPT_E_INVALID, "%s: %u bindings for %d meshes", who, rig->num_bindings, nmesh);
-    if (!rig->nodes || (rig->num_bindings && !rig->bindings) || (rig->num_clips && !rig->clips))
-        return fail(c, FOVPT_E_INVALID, "%s: a null array with a count above 0", who);
-    // nodes
-    std::vector<int32_t> parent(nn);
-    std::vector<uint32_t> level(nn);
-    std::vector<float> rest(10 * (size_t)nn);
-    uint32_t num_levels = 0;
-    for (uint32_t i = 0; i < nn; i++) {
-        const fovpt_rig_node& N = rig->nodes[i];
-        if (N.parent < -1 || N.parent >= (int32_t)i) return fail(c, FOVPT_E_INVALID, "%s: node %u: parent %d (-1, or below the node's own index)", who, i, N.parent);
-        float* r = rest.data() + 10 * (size_t)i;
-        memcpy(r, N.translation, 12); memcpy(r + 3, N.rotation, 16); memcpy(r + 7, N.scale, 12);
-        for (int e = 0; e < 10; e++)
-            if (!std::isfinite(r[e])) return fail(c, FOVPT_E_INVALID, "%s: node %u: a rest value is not finite", who, i);
-        if (!rig_norm_ok(N.rotation)) return fail(c, FOVPT_E_INVALID, "%s: node %u: the rest rotation's squared norm is outside [1/4, 4]", who, i);
-        parent[i] = N.parent;
-        level[i] = N.parent < 0 ? 0u : level[N.parent] + 1u;
-        num_levels = level[i] + 1 > num_levels ? level[i] + 1 : num_levels;
-    }
-    // bindings
-    std::vector<fovpt_ctx::RigBound> bound;
-    std::vector<int> bound_at((size_t)nmesh, -1);           // per mesh its RigWeights, -2: bound without morphs, -1: not bound
-    std::vector<uint32_t> pal_node, pal_dst, rigid_node;
-    std::vector<float> inv_bind;
-    std::vector<RigWeights> wjobs;
-    for (uint32_t k = 0; k < rig->num_bindings; k++) {
-        const fovpt_rig_binding& B = rig->bindings[k];
-        if (B.mesh < 0 || B.mesh >= nmesh) return fail(c, FOVPT_E_INVALID, "%s: binding %u: mesh %d of %d", who, k, B.mesh, nmesh);
-        if (bound_at[B.mesh] != -1) return fail(c, FOVPT_E_INVALID, "%s: binding %u: mesh %d is bound twice", who, k, B.mesh);
-        if (B._reserved) return fail(c, FOVPT_E_INVALID, "%s: binding %u: _reserved is %u", who, k, B._reserved);
-        if (B.node < -1 || B.node >= (int32_t)nn) return fail(c, FOVPT_E_INVALID, "%s: binding %u: node %d of %u", who, k, B.node, nn);
-        if (B.node >= 0 && B.num_joints) return fail(c, FOVPT_E_INVALID, "%s: binding %u: both a node and joints", who, k);
-        const uint32_t skin_joints = c->skins.empty() ? 0u : c->skins[B.mesh].num_joints;
-        const uint32_t targets = c->morphs.empty() ? 0u : c->morphs[B.mesh].num_targets;
-        if (B.num_joints && B.num_joints != skin_joints)
-            return fail(c, FOVPT_E_INVALID, "%s: binding %u: %u joints, the skin of mesh %d has %u", who, k, B.num_joints, B.mesh, skin_joints);
-        if (B.node >= 0 && targets) return fail(c, FOVPT_E_INVALID, "%s: binding %u: a rigid binding of mesh %d, which has morphs", who, k, B.mesh);
-        if (B.node < 0 && !B.num_joints && !targets) return fail(c, FOVPT_E_INVALID, "%s: binding %u: neither a node, joints nor morphs on mesh %d", who, k, B.mesh);
-        if (B.num_joints && (!B.joint_nodes || !B.inverse_bind)) return fail(c, FOVPT_E_INVALID, "%s: binding %u: null joint_nodes or inverse_bind", who, k);
-        for (uint32_t j = 0; j < B.num_joints; j++) {
-            if (B.joint_nodes[j] >= nn) return fail(c, FOVPT_E_INVALID, "%s: binding %u joint %u: node %u of %u", who, k, j, (unsigned)B.joint_nodes[j], nn);
-            for (int e = 0; e < 12; e++)
-                if (!std::isfinite(B.inverse_bind[12 * (size_t)j + e])) return fail(c, FOVPT_E_INVALID, "%s: binding %u joint %u: an inverse bind entry is not finite", who, k, j);
-            pal_node.push_back(B.joint_nodes[j]);
-            pal_dst.push_back(c->skins[B.mesh].pal_first + j);
-        }
-        inv_bind.insert(inv_bind.end(), B.inverse_bind, B.inverse_bind + (B.num_joints ? 12 * (size_t)B.num_joints : 0));
-        fovpt_ctx::RigBound D{B.mesh, 0u, B.num_joints != 0, targets != 0, B.node >= 0};
-        if (D.is_rigid) { D.rigid = (uint32_t)rigid_node.size(); rigid_node.push_back((uint32_t)B.node); }
-        bound_at[B.mesh] = targets ? (int)wjobs.size() : -2;
-        if (targets) wjobs.push_back(RigWeights{c->morphs[B.mesh].w_first, targets});
-        bound.push_back(D);
-    }
-    // clips
-    std::vector<int32_t> node_chan(3 * (size_t)nn * rig->num_clips, -1), w_chan(wjobs.size() * (size_t)rig->num_clips, -1);
-    std::vector<RigChannel> chan;
-    size_t num_times = 0, num_values = 0;
-    for (uint32_t k = 0; k < rig->num_clips; k++) {
-        const fovpt_rig_clip& K = rig->clips[k];
-        if (K._reserved) return fail(c, FOVPT_E_INVALID, "%s: clip %u: _reserved is %u", who, k, K._reserved);
-        if (K.num_channels && !K.channels) return fail(c, FOVPT_E_INVALID, "%s: clip %u: null channels", who, k);
-        if (K.num_channels > 3 * (size_t)nn + (size_t)nmesh) return fail(c, FOVPT_E_INVALID, "%s: clip %u: %u channels name a (target, path) twice", who, k, K.num_channels);
-        int32_t* nc = node_chan.data() + 3 * (size_t)nn * k;
-        int32_t* wc = w_chan.data() + wjobs.size() * (size_t)k;
-        std::vector<char> weights_seen((size_t)nmesh, 0);
-        for (uint32_t h = 0; h < K.num_channels; h++) {
-            const fovpt_rig_channel& H = K.channels[h];
-            if (H.path < FOVPT_RIG_TRANSLATION || H.path > FOVPT_RIG_WEIGHTS) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: path %d", who, k, h, H.path);
-            if (H.interpolation != FOVPT_RIG_STEP && H.interpolation != FOVPT_RIG_LINEAR)
-                return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: interpolation %d", who, k, h, H.interpolation);
-            size_t width;
-            int32_t* slot;
-            if (H.path == FOVPT_RIG_WEIGHTS) {
-                if (H.target < 0 || H.target >= nmesh) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: mesh %d of %d", who, k, h, H.target, nmesh);
-                if (bound_at[H.target] < 0) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: mesh %d is not bound or has no morphs", who, k, h, H.target);
-                if (weights_seen[H.target]) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: the weights of mesh %d twice", who, k, h, H.target);
-                weights_seen[H.target] = 1;
-                slot = wc + bound_at[H.target];
-                width = wjobs[bound_at[H.target]].num_targets;
-            } else {
-                if (H.target < 0 || H.target >= (int32_t)nn) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: node %d of %u", who, k, h, H.target, nn);
-                slot = nc + 3 * (size_t)H.target + H.path;
-                if (*slot >= 0) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: node %d path %d twice", who, k, h, H.target, H.path);
-                width = H.path == FOVPT_RIG_ROTATION ? 4 : 3;
-            }
-            if (H.num_keys < 1 || H.num_keys > FOVPT_RIG_MAX_KEYS) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: %u keys (1 .. %u)", who, k, h, H.num_keys, FOVPT_RIG_MAX_KEYS);
-            if (!H.times || !H.values) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: null times or values", who, k, h);
-            for (uint32_t i = 0; i < H.num_keys; i++) {
-                if (!std::isfinite(H.times[i])) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: time %u is not finite", who, k, h, i);
-                if (i && !(H.times[i] > H.times[i - 1])) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: times are not strictly ascending at key %u", who, k, h, i);
-            }
-            for (size_t i = 0; i < width * H.num_keys; i++)
-                if (!std::isfinite(H.values[i])) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: value %zu is not finite", who, k, h, i);
-            if (H.path == FOVPT_RIG_ROTATION)
-                for (uint32_t i = 0; i < H.num_keys; i++)
-                    if (!rig_norm_ok(H.values + 4 * (size_t)i)) return fail(c, FOVPT_E_INVALID, "%s: clip %u channel %u: key %u's squared norm is outside [1/4, 4]", who, k, h, i);
-            *slot = (int32_t)chan.size();
-            chan.push_back(RigChannel{(uint32_t)num_times, (uint32_t)num_values, H.num_keys, (uint32_t)H.interpolation});
-            num_times += H.num_keys; num_values += width * H.num_keys;
-            if (num_times >= (1ull << 32) || num_values >= (1ull << 32) || chan.size() >= (1ull << 31))
-                return fail(c, FOVPT_E_INVALID, "%s: more than 2^32 - 1 key times or values", who);
-        }
-    }
-    // the device copy: the keys in channel order, then one allocation
-    std::vector<float> times(num_times), values(num_values);
-    {
-        size_t h = 0;
-        for (uint32_t k = 0; k < rig->num_clips; k++)
-            for (uint32_t i = 0; i < rig->clips[k].num_channels; i++, h++) {
-                const fovpt_rig_channel& H = rig->clips[k].channels[i];
-                const size_t end = h + 1 < chan.size() ? chan[h + 1].v_first : num_values;
-                memcpy(times.data() + chan[h].t_first, H.times, 4 * (size_t)H.num_keys);
-                memcpy(values.data() + chan[h].v_first, H.values, 4 * (end - chan[h].v_first));
-            }
-    }
-    std::vector<char> blob;
-    const size_t o_parent = rig_place(blob, parent), o_level = rig_place(blob, level), o_rest = rig_place(blob, rest),
-                 o_nc = rig_place(blob, node_chan), o_wc = rig_place(blob, w_chan), o_chan = rig_place(blob, chan),
-                 o_times = rig_place(blob, times), o_values = rig_place(blob, values), o_pn = rig_place(blob, pal_node),
-                 o_pd = rig_place(blob, pal_dst), o_ib = rig_place(blob, inv_bind), o_rn = rig_place(blob, rigid_node),
-                 o_wj = rig_place(blob, wjobs);
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf d_in, d_out;
-    const size_t outs = 12 * ((size_t)nn + rigid_node.size() + pal_node.size());
-    HIPCHK(c, d_in.reserve(blob.size() + 16));
-    HIPCHK(c, d_out.reserve(4 * outs));
-    HIPCHK(c, hipMemcpy(d_in.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemset(d_out.p, 0, 4 * outs));
-    HIPCHK(c, hipStreamSynchronize(c->shadow_stream));     // a fovpt_update_animated in flight reads the buffers about to go
-    drop_rig(c);
+    RigPlan P;
+    if (plan_rig(anim_scene(c), who, rig, P)) return refused(c, P);
     fovpt_ctx::Rig& R = c->rig;
-    R.in.swap(d_in); R.out.swap(d_out);
-    R.bound.swap(bound);
-    R.num_clips = rig->num_clips;
-    const char* in = (const char*)R.in.p;
-    RigDev& D = R.dev;
-    D.num_nodes = nn; D.num_levels = num_levels; D.num_pal = (uint32_t)pal_node.size(); D.num_rigid = (uint32_t)rigid_node.size();
-    D.num_wjobs = (uint32_t)wjobs.size();
-    D.parent = (const int32_t*)(in + o_parent); D.level = (const uint32_t*)(in + o_level); D.rest = (const float*)(in + o_rest);
-    D.node_chan = (const int32_t*)(in + o_nc); D.w_chan = (const int32_t*)(in + o_wc); D.chan = (const RigChannel*)(in + o_chan);
-    D.times = (const float*)(in + o_times); D.values = (const float*)(in + o_values);
-    D.pal_node = (const uint32_t*)(in + o_pn); D.pal_dst = (const uint32_t*)(in + o_pd); D.inv_bind = (const float*)(in + o_ib);
-    D.rigid_node = (const uint32_t*)(in + o_rn); D.wjobs = (const RigWeights*)(in + o_wj);
-    D.world = (float*)R.out.p; D.rigid = D.world + 12 * (size_t)nn; D.palette = D.rigid + 12 * rigid_node.size();
-    size_t most = nn > D.num_pal ? nn : D.num_pal;
-    for (const RigWeights& w : wjobs) most = w.num_targets > most ? w.num_targets : most;
-    R.threads = (uint32_t)(most >= FOVPT_RIG_MAX_NODES ? FOVPT_RIG_MAX_NODES : (most + 63) / 64 * 64);
-    R.set = true;
-    return FOVPT_OK;
+    DevBuf* const live[2] = {&R.in, &R.out};
+    const size_t bytes[2] = {P.blob.size() + 16, 4 * P.outs};
+    return replace_buffers(c, live, bytes, [&](DevBuf* fresh) {
+        HIPCHK(c, hipMemcpy(fresh[0].p, P.blob.data(), P.blob.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemset(fresh[1].p, 0, 4 * P.outs));
+        return FOVPT_OK;
+    }, [&](DevBuf* fresh) {
+        R.bound.swap(P.bound);
+        R.num_clips = P.num_clips;
+        R.threads = P.threads;
+        const char* in = (const char*)fresh[0].p;
+        RigDev& D = R.dev;
+        D.num_nodes = P.num_nodes; D.num_levels = P.num_levels; D.num_pal = (uint32_t)P.pal_node.size(); D.num_rigid = (uint32_t)P.rigid_node.size();
+        D.num_wjobs = (uint32_t)P.wjobs.size();
+        D.parent = (const int32_t*)(in + P.at[RIG_PARENT]); D.level = (const uint32_t*)(in + P.at[RIG_LEVEL]); D.rest = (const float*)(in + P.at[RIG_REST]);
+        D.node_chan = (const int32_t*)(in + P.at[RIG_NODE_CHAN]); D.w_chan = (const int32_t*)(in + P.at[RIG_W_CHAN]); D.chan = (const RigChannel*)(in + P.at[RIG_CHAN]);
+        D.times = (const float*)(in + P.at[RIG_TIMES]); D.values = (const float*)(in + P.at[RIG_VALUES]);
+        D.pal_node = (const uint32_t*)(in + P.at[RIG_PAL_NODE]); D.pal_dst = (const uint32_t*)(in + P.at[RIG_PAL_DST]); D.inv_bind = (const float*)(in + P.at[RIG_INV_BIND]);
+        D.rigid_node = (const uint32_t*)(in + P.at[RIG_RIGID_NODE]); D.wjobs = (const RigWeights*)(in + P.at[RIG_WJOBS]);
+        D.world = (float*)fresh[1].p; D.rigid = D.world + 12 * (size_t)D.num_nodes; D.palette = D.rigid + 12 * (size_t)D.num_rigid;
+        R.set = true;
+        return FOVPT_OK;
+    });
 }
 
 // The composed matrices are made on the device and not validated, as FOVPT_UPDATE_DEVICE pointers are not.

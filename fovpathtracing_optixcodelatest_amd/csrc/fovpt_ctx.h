@@ -125,7 +125,8 @@ struct fovpt_ctx {
     // (num_joints 0: no skin) with the host copy of the skin, its largest weight sum S (the overflow rule), the mesh's first
     // vertex in skin_joints / skin_weights (the skinned meshes' vertices in mesh order: 8 B of indices and 16 B of weights each)
     // and its first joint in skin_pal (12 floats per joint, where host matrices go; rest_vtx and up_stage are shared with the
-    // calls above).  Laid out anew by every fovpt_set_skins; dropped by fovpt_set_scene.
+    // calls above).  Laid out anew by every fovpt_set_skins (fovpt_animplan.h, plan_skins: the rules, S and the places); dropped by
+    // fovpt_set_scene.
     struct Skin { uint32_t num_joints = 0, first = 0, pal_first = 0; double S = 0.0; std::vector<uint16_t> joints; std::vector<float> weights; };
     std::vector<Skin> skins;
     DevBuf skin_joints, skin_weights, skin_pal;
@@ -134,7 +135,8 @@ struct fovpt_ctx {
     // offsets into ent, relative to the mesh's first entry; ent: 16-byte records {dx, dy, dz, target}, sorted by target within
     // a vertex --, D[t] the largest |delta component| of target t (the overflow rule), the mesh's first offset in morph_off
     // (the morphed meshes in mesh order, num_vertices + 1 each, absolute into morph_ent), its first entry in morph_ent and its
-    // first weight in morph_w (where host weights go).  Laid out anew by every fovpt_set_morphs; dropped by fovpt_set_scene.
+    // first weight in morph_w (where host weights go).  Laid out anew by every fovpt_set_morphs (fovpt_animplan.h, plan_morphs: the
+    // rules, the transposition, D and the places); dropped by fovpt_set_scene.
     struct Morph { uint32_t num_targets = 0, off_first = 0, ent_first = 0, w_first = 0; std::vector<double> D; std::vector<uint32_t> off; std::vector<MorphEntry> ent; };
     std::vector<Morph> morphs;
     DevBuf morph_off, morph_ent, morph_w;
@@ -145,7 +147,8 @@ struct fovpt_ctx {
     // and per palette entry its node, its place in skin_pal and its inverse bind matrix); out: what it writes beside skin_pal and
     // morph_w (the worlds, the rigid matrices and the palettes in binding order: fovpt_debug_buffer "rig_world", "rig_rigid",
     // "rig_palette").  dev: the kernel's arguments, node_chan / w_chan those of clip 0 (a clip's tables follow its predecessor's).
-    struct RigBound { int32_t mesh; uint32_t rigid; bool skinned, morphed, is_rigid; };
+    // The rules, the sections of `in` and the thread count are fovpt_animplan.h's (plan_rig), and so is RigBound.
+    using RigBound = ::RigBound;
     struct Rig {
         bool set = false;
         uint32_t num_clips = 0, threads = 64;

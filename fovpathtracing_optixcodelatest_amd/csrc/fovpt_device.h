@@ -11,6 +11,7 @@
 
 #include "../../include/fovpt.h"
 #include "fovpt_jobplan.h"      // FOVPT_BLOCK, FOVPT_MAX_PASSES, FOVPT_MAX_ITERS, FOVPT_SHARDS and the engine's other constants
+#include "fovpt_animplan.h"     // RigChannel, RigWeights, MorphEntry: what the animation set-up lays out and rig.hip / refit.hip read
 
 #define FOVPT_WAVE 64
 #ifndef FOVPT_V_STEPSTAT
@@ -514,8 +515,7 @@ void fovpt_launch_transform_vertices_dev(hipStream_t st, const VertexTransformDe
 // them the palettes of the bound skinned meshes (into their places in skin_pal), the matrices of the rigid bindings and the
 // weights of the bound morphed meshes (into their places in morph_w).  One workgroup of `threads` (a multiple of 64, at least
 // num_nodes, at most FOVPT_RIG_MAX_NODES).  The definition is include/fovpt.h's, operation by operation.
-struct RigChannel { uint32_t t_first, v_first, num_keys, interp; };      // its keys' places in times / values
-struct RigWeights { uint32_t w_first, num_targets; };                   // a bound morphed mesh's place in morph_w
+// (RigChannel, RigWeights: fovpt_animplan.h, which lays them out)
 struct RigDev {
     uint32_t num_nodes, num_levels, num_pal, num_rigid, num_wjobs;
     const int32_t* parent;          // per node
@@ -556,7 +556,7 @@ void fovpt_launch_skin_vertices(hipStream_t st, const VertexSkin& g, const float
 // entry {dx, dy, dz, target} whose weight w[u][target] is not zero adds w * d to the position (unfused binary32, ascending
 // targets).  pal[u], in a batch given to fovpt_launch_morph_skin_vertices, is the mesh's palette and skin[u] its first vertex
 // in joints and weights: the morphed position then goes through VertexSkin's expression.
-struct MorphEntry { float dx, dy, dz; uint32_t target; };     // 16 bytes
+// (MorphEntry {dx, dy, dz, target}, 16 bytes: fovpt_animplan.h)
 struct VertexMorph {
     const float* w[FOVPT_GATHER_BATCH];     // the mesh's weights, one per target
     const float* pal[FOVPT_GATHER_BATCH];   // (morph and skin only)

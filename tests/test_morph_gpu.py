@@ -16,6 +16,8 @@ import temporal_ref as tr
 import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
+import anim_cases as ac
+from anim_cases import EMPTY, cornell_morphs, cornell_weights, shaped_targets
 from common import cfg_foveated, cfg_uniform, make_gpu
 from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin
 from temporal_common import tcfg
@@ -29,40 +31,15 @@ PROBE = scenes.ambient_probe(64, 32, 2.0)
 CAPS = dict(history_fovea=3, history_middle=5, history_periphery=8, history_uniform=6)      # (the default fovea keeps no history)
 F = np.float32
 SEEDS = range(0, int(os.environ.get("FOVPT_FUZZMO_TO", "8")))
-EMPTY = (np.zeros(0, np.uint32), np.zeros((0, 3), F))
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------------------
-def shaped_targets(rng, n, nt, scale=4.0):
-    """nt targets for n vertices with the shapes that can go wrong: target 0 dense when nt is odd; from five targets on, target
-    2 is empty; the last target is sparse and lists the mesh's last vertex; the others are sparse over about a third of the
-    vertices."""
-    ts = mr.random_targets(rng, n, nt, dense=nt % 2, fraction=0.3, scale=scale)
-    if nt >= 5:
-        ts[2] = EMPTY
-    if isinstance(ts[-1], tuple) and n:
-        idx = np.union1d(ts[-1][0], [n - 1]).astype(np.uint32)
-        ts[-1] = (idx, rng.uniform(-scale, scale, (len(idx), 3)).astype(F))
-    return ts
-
-
 def coverage(targets, n):
     """Per vertex, the number of targets that list it."""
     cnt = np.zeros(n, np.int64)
     for t in targets:
         cnt[mr.split(t, n)[0]] += 1
     return cnt
-
-
-def cornell_morphs(model):
-    """The tall block (mesh 4) has four targets (sparse, sparse, sparse, sparse with the last vertex), the short block (3) one
-    dense target."""
-    rng = np.random.default_rng(17)
-    return {4: shaped_targets(rng, model.meshes[4].vertex.shape[0], 4, 40.0), 3: shaped_targets(rng, model.meshes[3].vertex.shape[0], 1, 30.0)}
-
-
-def cornell_weights(k=1.0):
-    return {4: F([0.9 * k, 0.0, -0.6 * k, 1.4 * k]), 3: F([1.25 * k])}
 
 
 def atrium_morphs(model, big=None, seed=0):
@@ -559,10 +536,8 @@ def test_rejections_change_nothing():
     base = scenes.cornell_box()
     r = renderer.SampleRenderer(base)
     L = r._L
-    n3, n4, n5 = (base.meshes[k].vertex.shape[0] for k in (3, 4, 5))
-    morphs = cornell_morphs(base)
-    morphs[5] = [np.full((n5, 3), 2.0 ** 100, F)]                         # D = 2^100 on mesh 5 (never posed far: for the bound)
-    skins = {4: sk.bend(base.meshes[4].vertex, 3), 3: (np.zeros((n3, 4), np.uint16), np.ones((n3, 4), F), 1)}    # S = 4 on mesh 3
+    n4 = base.meshes[4].vertex.shape[0]
+    morphs, skins = ac.morph_scene(base)                                  # D = 2^100 on mesh 5, S = 4 on mesh 3
     r.set_morphs(morphs)
     r.set_skins(skins)
     w = cornell_weights()
@@ -575,64 +550,11 @@ def test_rejections_change_nothing():
     # -- fovpt_set_morphs
     idx = np.arange(0, n4, 2, dtype=np.uint32)
     delta = np.ones((len(idx), 3), F)
-    dense = np.ones((n4, 3), F)
-    keep = []
-
-    def target(count=len(idx), reserved=0, index=idx, d=delta):
-        return (count, reserved, index, d)
-
-    def morph(mesh=4, nv=n4, nt=None, reserved=0, targets=(target(),), null_targets=False):
-        return (mesh, nv, len(targets) if nt is None else nt, reserved, None if null_targets else targets)
-
-    def set_morphs(entries, n=None, ctx=r._ctx):
-        s = (abi.MeshMorph * max(1, len(entries)))()
-        for k, (mesh, nv, nt, reserved, targets) in enumerate(entries):
-            s[k].mesh, s[k].num_vertices, s[k].num_targets, s[k]._reserved = mesh, nv, nt, reserved
-            if targets is not None:
-                ts = (abi.MorphTarget * max(1, len(targets)))()
-                for t, (count, res, index, d) in enumerate(targets):
-                    ts[t].count, ts[t]._reserved = count, res
-                    ts[t].index = None if index is None else index.ctypes.data
-                    ts[t].delta = None if d is None else d.ctypes.data
-                keep.append(ts)
-                s[k].targets = ts
-        return L.fovpt_set_morphs(ctx, s, len(entries) if n is None else n)
-
-    def with_index(i, v):
-        x = idx.copy()
-        x[i] = v
-        return x
-
-    def with_delta(i, v):
-        x = delta.copy()
-        x.reshape(-1)[i] = v
-        return x
-
-    morph_cases = [
-        ([morph()], -1),                                                  # num < 0
-        ([morph(mesh=6)], None), ([morph(mesh=-1)], None),                # mesh out of range
-        ([morph(), morph()], None),                                       # listed twice
-        ([morph(nv=n4 - 1)], None), ([morph(nv=n4 + 1)], None),           # num_vertices other than the mesh's
-        ([morph(nv=0, nt=0, null_targets=True)], None),                   # ... also when removing
-        ([morph(nt=mr.MAX_TARGETS + 1, targets=(target(),) * (mr.MAX_TARGETS + 1))], None),      # above the cap
-        ([morph(null_targets=True, nt=1)], None),                         # targets to set, but a null pointer
-        ([morph(nt=0)], None),                                            # removing takes a null pointer
-        ([morph(reserved=1)], None), ([morph(targets=(target(reserved=1),))], None),
-        ([morph(targets=(target(count=n4 + 1, index=None, d=np.ones((n4 + 1, 3), F)),))], None),    # count > num_vertices
-        ([morph(targets=(target(count=n4 - 1, index=None, d=dense),))], None), ([morph(targets=(target(count=1, index=None, d=dense),))], None),     # null index, 0 < count < n
-        ([morph(targets=(target(d=None),))], None), ([morph(targets=(target(count=n4, index=None, d=None),))], None),      # null delta, count > 0
-        ([morph(targets=(target(index=with_index(3, idx[2])),))], None),  # an index twice
-        ([morph(targets=(target(index=with_index(3, idx[1])),))], None),  # descending
-        ([morph(targets=(target(index=with_index(len(idx) - 1, n4)),))], None),          # out of range
-        ([morph(targets=(target(index=with_index(0, 0xffffffff)),))], None),
-        ([morph(targets=(target(d=with_delta(4, np.nan)),))], None), ([morph(targets=(target(d=with_delta(0, np.inf)),))], None),
-        ([morph(targets=(target(d=with_delta(3 * len(idx) - 1, -np.inf)),))], None),
-        ([morph(targets=(target(), target(count=n4, index=None, d=dense), target(d=with_delta(1, np.nan))))], None),     # the third target is bad
-        ([morph(mesh=3, nv=n3, targets=(target(count=n3, index=None, d=np.ones((n3, 3), F)),)), morph(targets=(target(reserved=7),))], None),   # the second mesh is bad
-    ]
-    for k, (entries, n) in enumerate(morph_cases):
-        assert set_morphs(entries, n) == E_INVALID, k
-        assert unchanged(), k
+    for what, entries, n in ac.morph_set_cases(base):
+        packed, keep = ac.pack_morphs(entries)
+        assert L.fovpt_set_morphs(r._ctx, packed, len(entries) if n is None else n) == E_INVALID, what
+        ac.assert_recorded("morphs", what, E_INVALID, L.fovpt_last_error(r._ctx))
+        assert unchanged(), what
     assert L.fovpt_set_morphs(r._ctx, None, 1) == E_INVALID
     assert L.fovpt_set_morphs(None, None, 0) == E_INVALID
     assert L.fovpt_set_morphs(r._ctx, None, 0) == 0                       # nothing to do
@@ -647,58 +569,16 @@ def test_rejections_change_nothing():
     P4, P3 = np.ascontiguousarray(sk.bend_pose(base.meshes[4].vertex, 3, 20.0, (1.0, 2.0, 3.0))), np.ascontiguousarray(tf.IDENTITY[None])
 
     def pose(mesh=4, nt=4, wts=W4, nj=0, reserved=0, m=None):
-        return (mesh, nt, wts, nj, reserved, m)
+        return dict(mesh=mesh, nt=nt, weights=wts, nj=nj, reserved=reserved, m=m)
 
     def update(entries, n=None, flags=0, ctx=r._ctx):
-        p = (abi.MorphPose * max(1, len(entries)))()
-        for k, (mesh, nt, wts, nj, reserved, m) in enumerate(entries):
-            p[k].mesh, p[k].num_targets, p[k].weights = mesh, nt, (None if wts is None else wts.ctypes.data)
-            p[k].num_joints, p[k]._reserved, p[k].matrices = nj, reserved, (None if m is None else m.ctypes.data)
-        return L.fovpt_update_morphed(ctx, p, len(entries) if n is None else n, flags)
+        return L.fovpt_update_morphed(ctx, ac.pack_morph_poses(entries), len(entries) if n is None else n, flags)
 
-    def with_entry(a, i, v):
-        x = a.copy()
-        x.reshape(-1)[i] = v
-        return x
-
-    def row_only(t):
-        """One joint whose first row is 0 0 0 t: the row's bound is S |t| whatever B is."""
-        m = np.tile(tf.IDENTITY, (1, 1, 1))
-        m[0, 0] = (0, 0, 0, t)
-        return m
-
-    A5 = float(np.abs(base.meshes[5].vertex).max())
-    assert 0 < A5 < 2.0 ** 20                                             # B of mesh 5 is A5 + |w| 2^100 in binary64: at |w| = 2^27 the sum
-    over27 = np.nextafter(F(2.0 ** 27), F(np.inf))                        # rounds to 2^127 (A5 is below half an ulp); one ulp more is above
-    assert A5 + 2.0 ** 127 == 2.0 ** 127 and mr.bound(base.meshes[5].vertex, morphs[5], F([over27])) == 2.0 ** 127 + 2.0 ** 104
-    pose_cases = [
-        ([pose()], -1, 0),                                                # num < 0
-        ([pose(mesh=6)], None, 0), ([pose(mesh=-1)], None, 0),            # mesh out of range
-        ([pose(), pose()], None, 0),                                      # listed twice
-        ([pose(mesh=2)], None, 0),                                        # a mesh without morphs
-        ([pose(nt=3)], None, 0), ([pose(nt=5)], None, 0),                 # num_targets other than the mesh's
-        ([pose(wts=None)], None, 0), ([pose(wts=None)], None, abi.UPDATE_DEVICE),         # null weights
-        ([pose()], None, 4), ([pose()], None, 8 | abi.UPDATE_REBUILD),    # unknown flag bits
-        ([pose(reserved=1)], None, 0),
-        ([pose(mesh=5, nt=1, wts=F([0.5]), nj=1, m=P3)], None, 0),        # matrices on a mesh without a skin
-        ([pose(nj=2, m=P4)], None, 0), ([pose(nj=4, m=P4)], None, 0),     # num_joints other than the skin's
-        ([pose(nj=3)], None, 0), ([pose(m=P4)], None, 0),                 # exactly one of null matrices and zero joints
-        ([pose(nj=3)], None, abi.UPDATE_DEVICE),
-        ([pose(wts=with_entry(W4, 1, np.nan))], None, 0), ([pose(wts=with_entry(W4, 3, np.inf))], None, 0),
-        ([pose(wts=with_entry(W4, 0, -np.inf))], None, abi.UPDATE_REBUILD),               # with a rebuild asked for
-        ([pose(nj=3, m=with_entry(P4, 5, np.nan))], None, 0), ([pose(nj=3, m=with_entry(P4, 35, -np.inf))], None, 0),
-        ([pose(mesh=5, nt=1, wts=F([over27]))], None, 0),                 # B = A + (2^27 + 2^4) 2^100 > 2^127
-        ([pose(mesh=5, nt=1, wts=F([-over27]))], None, 0),                # (the bound takes |w|)
-        ([pose(nj=3, m=with_entry(P4, 2, 1e36))], None, 0),               # the row rule: 1e36 B > 2^127 = 1.7e38 (B is above 400)
-        ([pose(nj=3, m=with_entry(P4, 19, 1.8e38))], None, 0),            # the translation alone is above 2^127
-        ([pose(mesh=3, nt=1, wts=W3, nj=1, m=row_only(np.nextafter(F(2.0 ** 125), F(np.inf))))], None, 0),     # S = 4: one ulp above 2^125
-        ([pose(mesh=3, nt=1, wts=W3, nj=1, m=with_entry(P3, 1, 2.0 ** 126))], None, 0),                         # an entry with S |m| = 2^128
-        ([pose(), pose(mesh=3, nt=1, wts=with_entry(W3, 0, np.nan))], None, 0),          # the second entry is bad: nothing of the first
-    ]
-    assert 400 < np.abs(base.meshes[4].vertex).max() < 600
-    for k, (entries, n, flags) in enumerate(pose_cases):
-        assert update(entries, n, flags) == E_INVALID, (k, n, flags)
-        assert unchanged(), k
+    row_only = ac.row_only
+    for what, entries, n, flags, _ in ac.morph_pose_cases(base, morphs, w):
+        assert update(entries, n, flags) == E_INVALID, (what, n, flags)
+        ac.assert_recorded("morphed", what, E_INVALID, L.fovpt_last_error(r._ctx))
+        assert unchanged(), what
     assert L.fovpt_update_morphed(r._ctx, None, 1, 0) == E_INVALID
     assert L.fovpt_update_morphed(None, None, 0, 0) == E_INVALID
     assert L.fovpt_update_morphed(r._ctx, None, 0, 0) == 0                # nothing to do

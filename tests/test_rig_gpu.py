@@ -16,6 +16,8 @@ import skin_ref as sk
 import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
+import anim_cases as ac
+from anim_cases import SHORT, TALL, cornell_rig, rig_morph_fixture as morph_fixture, rig_skins as cornell_skins
 from common import cfg_foveated, make_gpu
 from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin
 from temporal_motion_common import MotionChecker
@@ -28,39 +30,10 @@ CORNELL = scenes.CORNELL_CAMERA
 PROBE = scenes.ambient_probe(64, 32, 2.0)
 F = np.float32
 SEEDS = range(0, int(os.environ.get("FOVPT_FUZZRG_TO", "8")))
-TALL, SHORT = 4, 3
 TIMES = (-1.0, 0.0, 0.25, 0.5, 0.75, 1.0, 1.25, 1.5, 1.75, 2.0, 3.0)      # before, at, between and after the keys below
 
 
 # ---- the fixture --------------------------------------------------------------------------------------------------------------
-def cornell_skins(model):
-    return {TALL: sk.bend(model.meshes[TALL].vertex, 3)}
-
-
-def cornell_rig(model):
-    """The tall block on a chain of three joints up its height, the short block rigid on node 4, which hangs from a pivot (node
-    3) at the block's centre.  Clip 0 has translation, rotation and scale channels of 2 to 4 keys, STEP and LINEAR, with rotation
-    keys 20 degrees apart (the sine branch), 2 degrees apart (the linear one) and on opposite hemispheres (the flip); clip 1
-    moves the short block alone."""
-    rig = rg.empty_rig(5)
-    rig["parent"] = np.array([-1, 0, 1, -1, 3], np.int32)
-    rig["translation"] = F([[368, 0, 351], [0, 110, 0], [0, 110, 0], [186, 82, 168], [-186, -82, -168]])
-    rig["rotation"][0] = rg.quat((0, 1, 0), 15.0)
-    z = (0.1, 0.0, 1.0)
-    rig["clips"] = [[
-        rg.channel(0, rg.ROTATION, [0.0, 1.0, 2.0], [rg.quat(z, 0.0), rg.quat(z, 20.0), rg.quat(z, 22.0)]),
-        rg.channel(1, rg.TRANSLATION, [0.5, 1.5], [[0, 110, 0], [12, 100, -6]]),
-        rg.channel(1, rg.ROTATION, [0.0, 0.5, 1.0, 1.5], [rg.quat((1, 0, 0), 0.0), -rg.quat((1, 0, 0), 14.0), rg.quat((1, 0, 0.3), 15.0, 1.3), rg.quat((1, 0, 0.3), 16.5, 0.8)]),
-        rg.channel(2, rg.SCALE, [0.25, 1.75], [[1, 1, 1], [1.2, 0.9, 1.1]]),
-        rg.channel(2, rg.ROTATION, [0.5, 1.0, 2.0], [rg.quat((0, 0, 1), -10.0), rg.quat((0, 0, 1), 10.0), rg.quat((0, 1, 0), 30.0)], rg.STEP),
-        rg.channel(3, rg.TRANSLATION, [0.0, 1.0, 2.0], [[186, 82, 168], [150, 95, 190], [160, 120, 150]], rg.STEP),
-        rg.channel(3, rg.ROTATION, [0.0, 2.0], [rg.quat((0, 1, 0), 0.0), rg.quat((0, 1, 0), 50.0)]),
-        rg.channel(3, rg.SCALE, [0.0, 1.0, 1.25, 2.0], [[1, 1, 1], [1.1, 0.8, 1], [1.1, 0.8, 1.2], [0.9, 1, 1]]),
-    ], [rg.channel(3, rg.TRANSLATION, [0.0, 1.0], [[186, 82, 168], [200, 82, 140]])]]
-    rig["bindings"] = [dict(mesh=TALL, joint_nodes=np.array([0, 1, 2], np.uint16), inverse_bind=rg.inverse_bind_of(rig, [0, 1, 2])), dict(mesh=SHORT, node=4)]
-    return rig
-
-
 def rig_buffers(r):
     out = []
     for name in ("rig_world", "rig_palette", "rig_rigid"):
@@ -180,21 +153,6 @@ def test_more_than_the_most_nodes_is_refused():
 
 
 # ---- 4. morphs -----------------------------------------------------------------------------------------------------------------
-def morph_fixture(model):
-    """The tall block skinned and morphed (4 targets), the short block morphed alone (3 targets), the left wall rigid."""
-    rng = np.random.default_rng(7)
-    skins = cornell_skins(model)
-    morphs = {TALL: mr.random_targets(rng, model.meshes[TALL].vertex.shape[0], 4, dense=1, scale=30.0),
-              SHORT: mr.random_targets(rng, model.meshes[SHORT].vertex.shape[0], 3, dense=3, scale=20.0)}
-    rig = cornell_rig(model)
-    rig["bindings"][1] = dict(mesh=SHORT)
-    rig["bindings"].append(dict(mesh=2, node=3))
-    rig["clips"][0] += [rg.channel(TALL, rg.WEIGHTS, [0.0, 1.0, 2.0], [[0, 0, 0, 0], [1, -0.5, 0, 2], [0, 0.25, 0, 1]]),
-                        rg.channel(SHORT, rg.WEIGHTS, [0.5, 1.5], [[0, 1, 0], [1, 0, -1]], rg.STEP)]
-    rig["clips"][1] = [rg.channel(0, rg.ROTATION, [0.0, 1.0], [rg.quat((0, 0, 1), 0.0), rg.quat((0, 0, 1), 25.0)])]       # no WEIGHTS channel
-    return skins, morphs, rig
-
-
 def test_morph_weights_and_a_clip_without_them(oracle):
     model = scenes.cornell_box()
     skins, morphs, rig = morph_fixture(model)
@@ -397,9 +355,7 @@ def test_set_rig_replaces_removes_and_ends_with_skins_morphs_and_the_scene(oracl
 # ---- 8. rejections -----------------------------------------------------------------------------------------------------------------
 def test_rejections_change_nothing(oracle):
     model = scenes.cornell_box()
-    skins, morphs, rig = morph_fixture(model)
-    morphs[5] = mr.random_targets(np.random.default_rng(2), model.meshes[5].vertex.shape[0], 1)      # morphs, and not bound
-    skins[1] = sk.bend(model.meshes[1].vertex, 2)                         # a skin, and not bound
+    skins, morphs, rig = ac.rig_scene(model)                               # (with morphs and a skin that the rig does not bind)
     r = renderer.SampleRenderer(model)
     L = r._L
     r.set_skins(skins)
@@ -412,93 +368,23 @@ def test_rejections_change_nothing(oracle):
     def unchanged():
         return np.array_equal(bits(scene_vertices(r)), bits(before_v)) and same(hierarchy(r), before_h)
 
-    def refused(change, what):
-        desc, keep = r.pack_rig(rig)
-        keep.append(change(desc))
+    plain = ac.describe_rig(rig)
+
+    def refused(changes, what):
+        desc, keep = ac.pack_rig(ac.changed(plain, changes))
         assert L.fovpt_set_rig(r._ctx, C.byref(desc)) == E_INVALID, what
         assert b"fovpt_set_rig" in L.fovpt_last_error(r._ctx), what
+        ac.assert_recorded("rig", what, E_INVALID, L.fovpt_last_error(r._ctx))
         assert unchanged(), what
         r.update_animated(0, 0.7)                                         # the previous rig is still the rig
         assert unchanged() and np.array_equal(bits(rig_buffers(r)[0]), bits(before_w)), what
 
-    def field(path, value):
-        """Sets desc.<path> = value; path like 'bindings[1].node' or 'clips[0].channels[2].times'."""
-        def change(desc):
-            v = value(desc) if callable(value) else value
-            exec("desc.%s = v" % path, dict(desc=desc, v=v))
-            return v
-        return change
-
-    def floats(get, index, value):
-        """A copy of the float array a pointer field holds, with one entry changed."""
-        def change(desc):
-            a = np.array(get(rig), F).copy()
-            a.reshape(-1)[index] = value
-            return a
-        return change
-
-    def ptr(path, make):
-        def change(desc):
-            a = np.ascontiguousarray(make(desc))
-            exec("desc.%s = p" % path, dict(desc=desc, p=a.ctypes.data))
-            return a
-        return change
-
     nan, inf = np.nan, np.inf
-    below, above = (lambda x: np.nextafter(F(x), F(0))), (lambda x: np.nextafter(F(x), F(inf)))
-    B, CH = "bindings[%d].%s", "clips[0].channels[%d].%s"
-    # clip 0's channels: 0 R(node 0) 1 T(1) 2 R(1) 3 S(2) 4 R(2) 5 T(3) 6 R(3) 7 S(3) 8 W(TALL) 9 W(SHORT)
-    cases = [
-        # the description as a whole
-        ("reserved0", field("_reserved0", 1)), ("reserved1", field("_reserved1", 1)), ("reserved2", field("_reserved2", 7)),
-        ("no nodes", field("num_nodes", 0)), ("too many nodes", field("num_nodes", rg.MAX_NODES + 1)), ("too many clips", field("num_clips", rg.MAX_CLIPS + 1)),
-        ("null nodes", field("nodes", lambda d: C.POINTER(abi.RigNode)())), ("null bindings", field("bindings", lambda d: C.POINTER(abi.RigBinding)())),
-        ("null clips", field("clips", lambda d: C.POINTER(abi.RigClip)())),
-        ("clip reserved", field("clips[1]._reserved", 1)), ("null channels", field("clips[0].channels", lambda d: C.POINTER(abi.RigChannel)())),
-        # nodes
-        ("parent is itself", field("nodes[2].parent", 2)), ("parent above", field("nodes[1].parent", 3)), ("parent below -1", field("nodes[0].parent", -2)),
-        ("rest translation nan", field("nodes[1].translation[2]", nan)), ("rest rotation inf", field("nodes[4].rotation[0]", inf)),
-        ("rest scale -inf", field("nodes[3].scale[1]", -inf)),
-        ("rest rotation too short", field("nodes[2].rotation[3]", below(0.5))), ("rest rotation too long", field("nodes[2].rotation[3]", above(2.0))),
-        # bindings
-        ("mesh above", field(B % (0, "mesh"), 6)), ("mesh below", field(B % (0, "mesh"), -1)), ("bound twice", field(B % (2, "mesh"), TALL)),
-        ("binding reserved", field(B % (1, "_reserved"), 1)),
-        ("node and joints", field(B % (0, "node"), 1)), ("node above", field(B % (2, "node"), 5)), ("node below -1", field(B % (2, "node"), -2)),
-        ("joint node above", ptr(B % (0, "joint_nodes"), lambda d: np.array([0, 5, 2], np.uint16))),
-        ("fewer joints than the skin", field(B % (0, "num_joints"), 2)), ("more joints than the skin", field(B % (0, "num_joints"), 4)),
-        ("joints on a mesh without a skin", lambda d: [field(B % (2, "node"), -1)(d), field(B % (2, "num_joints"), 3)(d),
-                                                       field(B % (2, "joint_nodes"), d.bindings[0].joint_nodes)(d), field(B % (2, "inverse_bind"), d.bindings[0].inverse_bind)(d)]),
-        ("rigid and morphs", field(B % (1, "node"), 2)),
-        ("neither node, joints nor morphs", field(B % (2, "node"), -1)),
-        ("null joint_nodes", field(B % (0, "joint_nodes"), None)), ("null inverse_bind", field(B % (0, "inverse_bind"), None)),
-        ("inverse bind nan", ptr(B % (0, "inverse_bind"), floats(lambda g: g["bindings"][0]["inverse_bind"], 17, nan))),
-        ("inverse bind inf", ptr(B % (0, "inverse_bind"), floats(lambda g: g["bindings"][0]["inverse_bind"], 35, -inf))),
-        # clips and channels
-        ("path above", field(CH % (1, "path"), 4)), ("path below", field(CH % (1, "path"), -1)),
-        ("interpolation above", field(CH % (1, "interpolation"), 2)), ("interpolation below", field(CH % (1, "interpolation"), -1)),
-        ("node target above", field(CH % (1, "target"), 5)), ("node target below", field(CH % (1, "target"), -1)),
-        ("mesh target above", field(CH % (8, "target"), 6)), ("mesh target below", field(CH % (8, "target"), -1)),
-        ("weights of a mesh that is not bound", field(CH % (9, "target"), 5)), ("weights of a bound mesh without morphs", field(CH % (9, "target"), 2)),
-        ("weights of a mesh with neither", field(CH % (9, "target"), 0)),
-        ("the same node and path twice", field(CH % (3, "target"), 3)), ("the same weights twice", lambda d: [field(CH % (1, "path"), rg.WEIGHTS)(d), field(CH % (1, "target"), SHORT)(d)]),
-        ("no keys", field(CH % (1, "num_keys"), 0)), ("too many keys", field(CH % (1, "num_keys"), rg.MAX_KEYS + 1)),
-        ("null times", field(CH % (1, "times"), None)), ("null values", field(CH % (1, "values"), None)),
-        ("time nan", ptr(CH % (0, "times"), lambda d: F([0, nan, 2]))), ("time inf", ptr(CH % (0, "times"), lambda d: F([0, 1, inf]))),
-        ("time -inf", ptr(CH % (0, "times"), lambda d: F([-inf, 1, 2]))),
-        ("times equal", ptr(CH % (0, "times"), lambda d: F([0, 1, 1]))), ("times descending", ptr(CH % (0, "times"), lambda d: F([0, 2, 1]))),
-        ("value nan", ptr(CH % (1, "values"), floats(lambda g: g["clips"][0][1]["values"], 4, nan))),
-        ("value inf", ptr(CH % (3, "values"), floats(lambda g: g["clips"][0][3]["values"], 0, inf))),
-        ("weight nan", ptr(CH % (8, "values"), floats(lambda g: g["clips"][0][8]["values"], 11, nan))),
-        ("rotation key too short", ptr(CH % (0, "values"), lambda d: np.array([[0, 0, 0, 1], [0, below(0.5), 0, 0], [0, 0, 0, 1]], F))),
-        ("rotation key too long", ptr(CH % (0, "values"), lambda d: np.array([[0, 0, 0, 1], [0, 0, 0, 1], [above(1.0), 1, 1, 1]], F))),
-    ]
-    assert len(rig["clips"][0]) == 10 and rig["clips"][0][8]["path"] == rig["clips"][0][9]["path"] == rg.WEIGHTS
-    for what, change in cases:
-        refused(change, what)
+    for what, changes in ac.rig_cases(rig):
+        refused(changes, what)
     # the other side of the norm rule: exactly 1/4 and exactly 4 are taken
-    desc, keep = r.pack_rig(rig)
-    keep.append(ptr(CH % (0, "values"), lambda d: np.array([[0, 0, 0, 0.5], [0, 2, 0, 0], [1, 1, 1, 1]], F))(desc))
-    desc.nodes[2].rotation[3] = 0.5
+    desc, keep = ac.pack_rig(ac.changed(plain, [ac.put("clips[0].channels[0].values", np.array([[0, 0, 0, 0.5], [0, 2, 0, 0], [1, 1, 1, 1]], F)),
+                                                ac.put("nodes[2].rotation[3]", 0.5)]))
     assert L.fovpt_set_rig(r._ctx, C.byref(desc)) == 0
     r.set_rig(rig)
     assert L.fovpt_set_rig(None, None) == E_INVALID

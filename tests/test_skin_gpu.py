@@ -14,6 +14,8 @@ import temporal_ref as tr
 import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
+import anim_cases as ac
+from anim_cases import cornell_poses, cornell_skins
 from common import cfg_foveated, cfg_uniform, make_gpu
 from gpu_common import bits, build_dropin, debug_buffer, dropin_renderer, run_dropin
 from temporal_common import tcfg
@@ -30,16 +32,6 @@ SEEDS = range(0, int(os.environ.get("FOVPT_FUZZSK_TO", "8")))
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------------------
-def cornell_skins(model):
-    """The tall block (mesh 4) bends over 3 joints, the short block (3) has one."""
-    return {4: sk.bend(model.meshes[4].vertex, 3), 3: sk.bend(model.meshes[3].vertex, 1)}
-
-
-def cornell_poses(model, k=1.0):
-    return {4: sk.bend_pose(model.meshes[4].vertex, 3, 50.0 * k, (-45.0 * k, 0.0, -30.0 * k)),
-            3: tf.scale_about((186.0, 0.0, 168.0), (1.0 + 0.3 * k, 1.0 - 0.4 * k, 1.0 - 0.1 * k))[None]}
-
-
 def atrium_skins(model, big=None):
     """Every mesh skinned, joint counts cycling 1, 2, 5 and 17; mesh `big` over FOVPT_SKIN_MAX_JOINTS joints."""
     return {k: sk.bend(m.vertex, sk.MAX_JOINTS if k == big else (1, 2, 5, 17)[k % 4]) for k, m in enumerate(model.meshes)}
@@ -408,15 +400,8 @@ def test_rejections_change_nothing():
     base = scenes.cornell_box()
     r = renderer.SampleRenderer(base)
     L = r._L
-    n3, n4 = base.meshes[3].vertex.shape[0], base.meshes[4].vertex.shape[0]
-    skins = cornell_skins(base)
-    w4 = skins[3][1].copy()
-    w4[0] = 1                                                             # S = 4 on mesh 3
-    skins[3] = (skins[3][0], w4, 1)
-    assert sk.weight_sum(skins[3][1]) == 4.0 and abs(sk.weight_sum(skins[4][1]) - 1.0) < 1e-6
-    one = sk.bend(base.meshes[5].vertex, 1)
-    skins[5] = one
-    assert sk.weight_sum(one[1]) == 1.0                                   # S = 1 on mesh 5
+    n4 = base.meshes[4].vertex.shape[0]
+    skins = ac.skin_scene(base)                                           # S = 4 on mesh 3, S = 1 on mesh 5
     r.set_skins(skins)
     poses = cornell_poses(base)
     r.update_skinned(poses)
@@ -428,50 +413,10 @@ def test_rejections_change_nothing():
     # -- fovpt_set_skins
     j4, wt4 = np.ascontiguousarray(skins[4][0]), np.ascontiguousarray(skins[4][1])
 
-    def skin(mesh=4, nv=n4, nj=3, reserved=0, joints=j4, weights=wt4):
-        return (mesh, nv, nj, reserved, joints, weights)
-
-    def set_skins(entries, n=None, ctx=r._ctx):
-        s = (abi.MeshSkin * max(1, len(entries)))()
-        for k, (mesh, nv, nj, reserved, joints, weights) in enumerate(entries):
-            s[k].mesh, s[k].num_vertices, s[k].num_joints, s[k]._reserved = mesh, nv, nj, reserved
-            s[k].joints = None if joints is None else joints.ctypes.data
-            s[k].weights = None if weights is None else weights.ctypes.data
-        return L.fovpt_set_skins(ctx, s, len(entries) if n is None else n)
-
-    def with_joint(i, v):
-        j = j4.copy()
-        j.reshape(-1)[i] = v
-        return j
-
-    def with_weight(i, v):
-        w = wt4.copy()
-        w.reshape(-1)[i] = v
-        return w
-
-    zero_slot = int(np.flatnonzero(wt4.reshape(-1) == 0)[0])             # a slot whose weight is 0: its index counts all the same
-    skin_cases = [
-        ([skin()], -1),                                                   # num < 0
-        ([skin(mesh=6)], None), ([skin(mesh=-1)], None),                  # mesh out of range
-        ([skin(), skin()], None),                                         # listed twice
-        ([skin(nv=n4 - 1)], None), ([skin(nv=n4 + 1)], None),             # num_vertices other than the mesh's
-        ([skin(nv=0, nj=0, joints=None, weights=None)], None),            # ... also when removing
-        ([skin(nj=sk.MAX_JOINTS + 1)], None),                             # above the cap
-        ([skin(joints=None)], None), ([skin(weights=None)], None),        # one null pointer of the pair
-        ([skin(joints=None, weights=None)], None),                        # both, with joints to set
-        ([skin(nj=0)], None), ([skin(nj=0, weights=None)], None),         # removing takes two null pointers
-        ([skin(reserved=1)], None),
-        ([skin(joints=with_joint(5, 3))], None),                          # a joint index >= num_joints
-        ([skin(joints=with_joint(zero_slot, 3))], None),                  # ... where its weight is 0
-        ([skin(nj=2)], None),                                             # (the skin uses joint 2)
-        ([skin(weights=with_weight(0, np.nan))], None), ([skin(weights=with_weight(7, np.inf))], None),
-        ([skin(weights=with_weight(2, -1e-30))], None), ([skin(weights=with_weight(4 * n4 - 1, np.nextafter(F(1), F(2))))], None),
-        ([skin(mesh=3, nv=n3, nj=1, joints=skins[3][0], weights=skins[3][1]), skin(weights=with_weight(1, 2.0))], None),   # the second is bad
-    ]
-    assert j4.max() == 2
-    for entries, n in skin_cases:
-        assert set_skins(entries, n) == E_INVALID, (entries, n)
-        assert unchanged()
+    for what, entries, n in ac.skin_set_cases(base, skins):
+        assert L.fovpt_set_skins(r._ctx, ac.pack_skins(entries), len(entries) if n is None else n) == E_INVALID, what
+        ac.assert_recorded("skins", what, E_INVALID, L.fovpt_last_error(r._ctx))
+        assert unchanged(), what
     assert L.fovpt_set_skins(r._ctx, None, 1) == E_INVALID
     assert L.fovpt_set_skins(None, None, 0) == E_INVALID
     assert L.fovpt_set_skins(r._ctx, None, 0) == 0                        # nothing to do
@@ -485,50 +430,16 @@ def test_rejections_change_nothing():
     P4, P3, P5 = np.ascontiguousarray(poses[4]), np.ascontiguousarray(poses[3]), np.tile(tf.IDENTITY, (1, 1, 1))
 
     def pose(mesh=4, nj=3, m=P4):
-        return (mesh, nj, m)
+        return dict(mesh=mesh, nj=nj, m=m)
 
     def update(entries, n=None, flags=0, ctx=r._ctx):
-        p = (abi.SkinPose * max(1, len(entries)))()
-        for k, (mesh, nj, m) in enumerate(entries):
-            p[k].mesh, p[k].num_joints, p[k].matrices = mesh, nj, (None if m is None else m.ctypes.data)
-        return L.fovpt_update_skinned(ctx, p, len(entries) if n is None else n, flags)
+        return L.fovpt_update_skinned(ctx, ac.pack_skin_poses(entries), len(entries) if n is None else n, flags)
 
-    def with_entry(base_pal, i, v):
-        m = base_pal.copy()
-        m.reshape(-1)[i] = v
-        return m
-
-    def row_only(t):
-        """One joint whose first row is 0 0 0 t: the row's bound is S |t| whatever A is."""
-        m = np.tile(tf.IDENTITY, (1, 1, 1))
-        m[0, 0] = (0, 0, 0, t)
-        return m
-
-    above = np.nextafter(F(2.0 ** 127), F(np.inf))
-    above4 = np.nextafter(F(2.0 ** 125), F(np.inf))
-    pose_cases = [
-        ([pose()], -1, 0),                                                # num < 0
-        ([pose(mesh=6)], None, 0), ([pose(mesh=-1)], None, 0),            # mesh out of range
-        ([pose(), pose()], None, 0),                                      # listed twice
-        ([pose(mesh=2)], None, 0),                                        # a mesh without a skin
-        ([pose(nj=2)], None, 0), ([pose(nj=4)], None, 0),                 # num_joints other than the skin's
-        ([pose(m=None)], None, 0), ([pose(m=None)], None, abi.UPDATE_DEVICE),     # null matrices
-        ([pose()], None, 4), ([pose()], None, 8 | abi.UPDATE_REBUILD),    # unknown flag bits
-        ([pose(m=with_entry(P4, 5, np.nan))], None, 0),
-        ([pose(m=with_entry(P4, 12, np.inf))], None, 0),
-        ([pose(m=with_entry(P4, 35, -np.inf))], None, abi.UPDATE_REBUILD),        # with a rebuild asked for
-        ([pose(m=with_entry(P4, 2, 1e36))], None, 0),                     # 1e36 A > 2^127 = 1.7e38 (the block's A is between 400 and 600)
-        ([pose(m=with_entry(P4, 19, 1.8e38))], None, 0),                  # the translation alone is above 2^127
-        ([pose(mesh=5, nj=1, m=row_only(above))], None, 0),               # S = 1: one ulp above 2^127
-        ([pose(mesh=3, nj=1, m=row_only(above4))], None, 0),              # S = 4: one ulp above 2^125
-        ([pose(), pose(mesh=3, nj=1, m=with_entry(P3, 9, np.nan))], None, 0),     # the second entry is bad: nothing of the first
-    ]
-    assert 400 < np.abs(base.meshes[4].vertex).max() < 600
-    other = np.ascontiguousarray(cornell_poses(base, 0.5)[4])
-    for k, (entries, n, flags) in enumerate(pose_cases):
-        entries = [(m_, nj, (other if p is P4 else p)) for m_, nj, p in entries]      # (a good entry would move the block)
-        assert update(entries, n, flags) == E_INVALID, (k, n, flags)
-        assert unchanged(), k
+    row_only = ac.row_only
+    for what, entries, n, flags, _ in ac.skin_pose_cases(base, poses):
+        assert update(entries, n, flags) == E_INVALID, (what, n, flags)
+        ac.assert_recorded("skinned", what, E_INVALID, L.fovpt_last_error(r._ctx))
+        assert unchanged(), what
     assert L.fovpt_update_skinned(r._ctx, None, 1, 0) == E_INVALID
     assert L.fovpt_update_skinned(None, None, 0, 0) == E_INVALID
     assert L.fovpt_update_skinned(r._ctx, None, 0, 0) == 0                # nothing to do

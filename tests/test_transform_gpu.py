@@ -13,6 +13,7 @@ import temporal_ref as tr
 import transform_ref as tf
 from fovpathtracing_optixcodelatest_amd import abi, lib, renderer, scenes
 
+import anim_cases as ac
 from common import cfg_foveated, cfg_uniform, make_gpu
 from gpu_common import bits, build_dropin, debug_buffer, run_dropin
 from temporal_common import tcfg
@@ -287,38 +288,17 @@ def test_rejections_change_nothing():
     before = hierarchy(r)
     acc0, px0, _ = render(r)
     st0 = r.stats()
-    good = tf.rotation_translation(10.0, (368.0, 0.0, 351.0), (5.0, 0.0, 0.0))
+    good = ac.TRANSFORM_GOOD
 
     def call(entries, n=None, flags=0):
-        tfs = (abi.MeshTransform * max(1, len(entries)))()
-        for k, (mesh, m) in enumerate(entries):
-            tfs[k].mesh = mesh
-            tfs[k].m[:] = [float(x) for x in np.asarray(m, F).reshape(-1)]
-        return L.fovpt_update_transforms(r._ctx, tfs, len(entries) if n is None else n, flags)
+        return L.fovpt_update_transforms(r._ctx, ac.pack_transforms(entries), len(entries) if n is None else n, flags)
 
     def with_entry(i, v):
-        m = good.copy().reshape(-1)
-        m[i] = v
-        return m
+        return ac.with_entry(good, i, v).reshape(-1)
 
-    ok = (4, good)
-    cases = [
-        ([ok], -1, 0),                                            # num < 0
-        ([(6, good)], None, 0),                                   # mesh out of range
-        ([(-1, good)], None, 0),
-        ([ok, ok], None, 0),                                      # listed twice
-        ([ok], None, abi.UPDATE_DEVICE),                          # flag 1 is fovpt_update_vertices' alone
-        ([ok], None, abi.UPDATE_DEVICE | abi.UPDATE_REBUILD),
-        ([ok], None, 4),                                          # unknown flag bits
-        ([(4, with_entry(5, np.nan))], None, 0),                  # NaN
-        ([(4, with_entry(0, np.inf))], None, 0),                  # inf
-        ([(4, with_entry(11, -np.inf))], None, abi.UPDATE_REBUILD),   # with a rebuild asked for
-        ([(4, with_entry(2, 1e36))], None, 0),                    # 1e36 A > 2^127 = 1.7e38 (the block's A is between 400 and 500)
-        ([(4, with_entry(7, 1.8e38))], None, 0),                  # the translation alone is above 2^127
-        ([ok, (3, with_entry(9, np.nan))], None, 0),              # the second entry is bad: nothing of the first is applied
-    ]
-    for entries, n, flags in cases:
-        assert call(entries, n, flags) == E_INVALID, (entries, n, flags)
+    for what, entries, n, flags, _ in ac.transform_cases(base):
+        assert call(entries, n, flags) == E_INVALID, (what, n, flags)
+        ac.assert_recorded("transforms", what, E_INVALID, L.fovpt_last_error(r._ctx))
     assert 400 < np.abs(base.meshes[4].vertex).max() < 500
     assert call([(4, with_entry(2, 1e35))]) == 0                  # a tenth of it is below the bound: finite, if absurd ...
     assert np.isfinite(scene_vertices(r)).all()
